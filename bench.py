@@ -11,7 +11,13 @@ Which number is which (round 3; the two readings of "end-to-end" are both in the
                   host u8 frame in -> host s16 edge map out, H2D and D2H inside the timed region, same run.  The
                   details (u8 / bit maps, per-rank rows, NUMA placement, config 5) are in `host_to_host`.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run does only what `value` needs: set-up, spin-up and W warm-up steps, the K timed steps, the optional output
+dump, the JSON line (`value`, `ms_per_step`, `config`; `end_to_end` is null).  --full adds everything else below -- the
+oracle parity spot checks, the roofline and per-stage timings, the host-to-host legs, the CPU baseline -- and then also
+brackets the Sobel+NMS kernel of the timed region with HIP events (see the comment at the timed loop).
+--dump-outputs DIR writes the edge maps of the last timed step to DIR/edges.npy as float32 (see dump_outputs).
 
 One process per GPU (the driver launches N>1 through torch.distributed.run).  A *step* is one pass of
 the whole hot path (gaussian -> fused Sobel+NMS -> hysteresis) over this rank's batch of F resident
@@ -22,10 +28,10 @@ Workload (BASELINE.json configs[1]): 3840x2160 gray, sigma 1.4, thresholds 50/15
 (canny_edge_amd.synth, seed 42+i), F = 128 frames per GPU per step: the working set (1 GB u8 in, 2 GB s16 per
 plane) is far beyond the 256 MB Infinity Cache and a step (2.4 ms) is long against its fixed costs -- kernel
 tails, sweep launches, one host round trip: 64 frames per step run 7 % slower per frame, 256 another 3 % faster.
-Untimed before the W warm-up steps: a parity spot check against the oracle and --spinup-seconds of steps that bring
-the device to its steady clocks.
+Untimed before the W warm-up steps: --spinup-seconds of steps that bring the device to its steady clocks (with --full,
+first a parity spot check against the oracle).
 
-The JSON line also carries
+With --full the JSON line also carries
   roofline     -- the Sobel+NMS kernel of the timed region at SURVEY.md 8(d)'s 4 B/px (`frac`; `frac_own_bytes` prices
                   the 4.25 B/px it really moves), with `copy_probe`: a plain device copy of the same 2 + 2 B/px timed
                   in the same run -- what a 1:1 read/write stream reaches on THIS box (boxes differ by up to 14 %).
@@ -89,7 +95,33 @@ def parse():
     ap.add_argument("--h2h-reps", type=int, default=5)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-check", action="store_true", help="skip the pre-timing parity spot check")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the checks and measurements beyond `value` (parity, roofline, stages, host-to-host, "
+                         "CPU baseline); --cpu-frames, --h2h-frames, --h2h-reps, --no-cpu-baseline and --no-check "
+                         "apply only then")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the edge maps of the last timed step (rank 0) to DIR/edges.npy as float32")
     return ap.parse_args()
+
+
+DUMP_BYTES = 48 << 20  # --dump-outputs writes at most this many bytes
+
+
+def dump_outputs(path, edges, np, torch):
+    """Write the [F, H, W] s16 edge maps `edges` (device) to path/edges.npy as float32: all of them when they fit in
+    DUMP_BYTES, otherwise the rows numbered np.random.default_rng(0).choice(F * H, R, replace=False), sorted (row r is
+    row r % H of frame r // H), with R = DUMP_BYTES // (4 * W) -- shape [R, W].  The inputs are seeded, so the same
+    arguments give the same sample in every run."""
+    F, H, W = edges.shape
+    n_rows = F * H
+    keep = min(n_rows, max(1, DUMP_BYTES // (4 * W)))
+    if keep == n_rows:
+        sample = edges
+    else:
+        rows = np.sort(np.random.default_rng(0).choice(n_rows, size=keep, replace=False))
+        sample = edges.view(n_rows, W)[torch.from_numpy(rows).to(edges.device)]
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "edges.npy"), sample.float().cpu().numpy())
 
 
 def cpu_baseline(frames, sigma, lo, hi, n_sample):
@@ -315,7 +347,7 @@ def main():
 
     # parity spot check (outside the timed region): frame 0 of this rank against the oracle
     parity = None
-    if not args.no_check and rank == 0:
+    if args.full and not args.no_check and rank == 0:
         import oracle
         step()
         drain()
@@ -340,11 +372,13 @@ def main():
     # steps right after.
     # ... and only every 4th step carries that pair: even an attached pair makes the dispatch wait for the stream to
     # drain (~0.04 ms per step it is on); `launches_timed` says how many launches the average is over.
-    ctx.set_option("profile_stage_mask", 1 << capi.STAGE_SOBEL_NMS)
-    sample_every = max(1, min(4, args.steps // 3))
-    ctx.set_option("profile_sample_interval", sample_every)
-    ctx.profile_enable(True)
-    ctx.profile_reset()
+    # A plain run (no --full) carries no events at all.
+    if args.full:
+        ctx.set_option("profile_stage_mask", 1 << capi.STAGE_SOBEL_NMS)
+        sample_every = max(1, min(4, args.steps // 3))
+        ctx.set_option("profile_sample_interval", sample_every)
+        ctx.profile_enable(True)
+        ctx.profile_reset()
 
     if world > 1:
         dist.barrier()
@@ -357,6 +391,38 @@ def main():
     if world > 1:
         dist.barrier()
         elapsed = sharding.max_over_ranks(elapsed, red_dev)
+
+    if args.dump_outputs and rank == 0:  # before --full's passes below overwrite d_edges
+        # with --stream the calls alternate between d_edges (odd call count) and d_edges_b
+        last = d_edges_b if args.stream and calls[0] % 2 == 0 else d_edges
+        dump_outputs(args.dump_outputs, last, np, torch)
+
+    px_per_step = F * H * W
+    value = sharding.aggregate_throughput(px_per_step * args.steps, world, elapsed) / 1e6
+    out = {
+        "metric": "Mpixels/s device-resident Canny (4K gray, frames in HBM, whole pipeline); % HBM roofline on "
+                  "Sobel+NMS in `roofline`; the end-to-end (host->host, PCIe-inclusive) rate is `end_to_end`",
+        "value": round(value, 1), "unit": "Mpixels/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "f32+s16",
+        "scope": "device-resident: frames already in HBM when the timed region starts, edge maps left in HBM (the bench "
+                 "contract's definition of `value`); `end_to_end` is the PCIe-inclusive Metric 1 of the same run",
+        "end_to_end": None,
+        "data": "synthetic",
+        "config": {"workload": f"{F}x {W}x{H} gray frames per GPU per step, sigma={args.sigma}, "
+                               f"thresholds {args.min_val}/{args.max_val}, inputs resident in HBM",
+                   "frames_per_gpu": F, "height": H, "width": W, "sigma": args.sigma,
+                   "calls": ("canny_hip_dev_canny_stream: the host checks step i's convergence after queueing the "
+                             "Gaussian of step i+1; all K steps complete inside the timed region") if args.stream
+                   else "canny_hip_dev_canny (asynchronous: K calls queued back to back, the timed region ends with a device "
+                             "synchronize)",
+                   "sharding": "independent frames per GPU, no collective"},
+    }
+    if rehearse:
+        out["rehearsal"] = True
+    if not args.full:
+        report(out, ctx, rank, world, dist)
+        return
 
     sn_ms_total, sn_launches = ctx.profile_get(capi.STAGE_SOBEL_NMS)
     ctx.set_option("profile_stage_mask", 0)  # all stages
@@ -375,9 +441,6 @@ def main():
                            else "inside the timed region, on every step"}
     ctx.profile_enable(False)
     hyst_sweeps = ctx.last_hysteresis_iterations
-
-    px_per_step = F * H * W
-    value = sharding.aggregate_throughput(px_per_step * args.steps, world, elapsed) / 1e6
 
     # the same steps as plain blocking calls (each returns with its edge map complete), for comparison
     plain = None
@@ -560,24 +623,8 @@ def main():
                                 h2h["s16"]["h2d_GBps_per_gpu"])),
                       "transfer": h2h["transfer"],
                       "u8_maps": h2h["u8"]["value"], "bit_maps": h2h["bits"]["value"]}
-    out = {
-        "metric": "Mpixels/s device-resident Canny (4K gray, frames in HBM, whole pipeline); % HBM roofline on "
-                  "Sobel+NMS in `roofline`; the end-to-end (host->host, PCIe-inclusive) rate is `end_to_end`",
-        "value": round(value, 1), "unit": "Mpixels/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": "f32+s16",
-        "scope": "device-resident: frames already in HBM when the timed region starts, edge maps left in HBM (the bench "
-                 "contract's definition of `value`); `end_to_end` is the PCIe-inclusive Metric 1 of the same run",
+    out.update({
         "end_to_end": end_to_end,
-        "data": "synthetic",
-        "config": {"workload": f"{F}x {W}x{H} gray frames per GPU per step, sigma={args.sigma}, "
-                               f"thresholds {args.min_val}/{args.max_val}, inputs resident in HBM",
-                   "frames_per_gpu": F, "height": H, "width": W, "sigma": args.sigma,
-                   "calls": ("canny_hip_dev_canny_stream: the host checks step i's convergence after queueing the "
-                             "Gaussian of step i+1; all K steps complete inside the timed region") if args.stream
-                   else "canny_hip_dev_canny (asynchronous: K calls queued back to back, the timed region ends with a device "
-                             "synchronize)",
-                   "sharding": "independent frames per GPU, no collective"},
         "host_to_host": h2h,
         "roofline": roofline,
         "roofline_sobel_nms_s16": roofline_s16,
@@ -587,9 +634,7 @@ def main():
         "plain_calls": plain,
         "hysteresis_sweeps": hyst_sweeps,
         "parity_checked": parity,
-    }
-    if rehearse:
-        out["rehearsal"] = True
+    })
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(base_np, args.sigma, args.min_val, args.max_val, args.cpu_frames)
         out["vs_cpu_baseline"] = {"device_resident": round(value / out["cpu_baseline"]["value"], 1),
@@ -601,6 +646,10 @@ def main():
             end_to_end["vs_cpu_baseline"] = out["vs_cpu_baseline"]["end_to_end_s16"]
     else:
         out["cpu_baseline"] = None
+    report(out, ctx, rank, world, dist)
+
+
+def report(out, ctx, rank, world, dist):
     if rank == 0:
         print(json.dumps(out), flush=True)
     ctx.close()
