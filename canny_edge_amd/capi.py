@@ -28,9 +28,31 @@ LIB_PATH = os.environ.get("CANNY_HIP_LIB") or os.path.join(_HERE, "libcanny_hip.
 
 OK = 0
 STAGE_GAUSSIAN, STAGE_SOBEL_NMS, STAGE_HYST_CLASSIFY, STAGE_HYST_PROPAGATE, STAGE_HYST_FINALIZE, \
-    STAGE_SOBEL, STAGE_NMS, STAGE_XY_GRADIENT = range(8)
+    STAGE_SOBEL, STAGE_NMS, STAGE_XY_GRADIENT, STAGE_TO_GRAY = range(9)
 STAGE_NAMES = ("gaussian", "sobel_nms", "hyst_classify", "hyst_propagate", "hyst_finalize", "sobel", "nms",
-               "xy_gradient")
+               "xy_gradient", "to_gray")
+
+# colour frame layouts (enum canny_hip_layout): interleaved, 1 byte per channel, no row padding
+LAYOUT_GRAY8, LAYOUT_BGR8, LAYOUT_RGB8, LAYOUT_BGRA8, LAYOUT_RGBA8 = range(5)
+LAYOUT_CHANNELS = {LAYOUT_GRAY8: 1, LAYOUT_BGR8: 3, LAYOUT_RGB8: 3, LAYOUT_BGRA8: 4, LAYOUT_RGBA8: 4}
+
+
+def layout_of(shape, order: str = "bgr", batch: bool = False) -> int:
+    """Layout of a frame of this shape: (H, W) -> GRAY8, (H, W, 3) -> BGR8 / RGB8, (H, W, 4) -> BGRA8 / RGBA8 by
+    ``order`` ("bgr": cv::Mat / VideoCapture, "rgb": PIL / PPM / numpy).  batch=True: the same with a leading frame
+    axis, (N, H, W[, CH]).  Pure host logic."""
+    shape = tuple(int(d) for d in shape)
+    if order not in ("bgr", "rgb"):
+        raise ValueError(f"order must be 'bgr' or 'rgb', not {order!r}")
+    nd = len(shape) - (1 if batch else 0)
+    if nd == 2:
+        return LAYOUT_GRAY8
+    if nd == 3 and shape[-1] in (3, 4):
+        if shape[-1] == 3:
+            return LAYOUT_BGR8 if order == "bgr" else LAYOUT_RGB8
+        return LAYOUT_BGRA8 if order == "bgr" else LAYOUT_RGBA8
+    raise ValueError(f"expected {'(N, ' if batch else '('}H, W) or {'(N, ' if batch else '('}H, W, 3|4) frames, "
+                     f"got shape {shape}")
 
 # every symbol include/canny_hip.h declares (checked by tests/test_abi.py)
 EXPORTS = (
@@ -49,7 +71,9 @@ EXPORTS = (
     "canny_hip_dev_gaussian_u8", "canny_hip_dev_sobel_nms_u8in", "canny_hip_host_register", "canny_hip_host_unregister",
     "canny_hip_canny_batch_bits", "canny_hip_canny_multi_gpu_bits", "canny_hip_dev_canny_bits",
     "canny_hip_probe_copy", "canny_hip_ctx_get_option", "canny_hip_selftest_expand_bits",
-    "canny_hip_selftest_march_order",
+    "canny_hip_selftest_march_order", "canny_hip_to_gray", "canny_hip_dev_to_gray", "canny_hip_dev_gaussian_u8_color",
+    "canny_hip_dev_canny_color", "canny_hip_canny_color", "canny_hip_canny_batch_color", "canny_hip_canny_batch_color_u8",
+    "canny_hip_canny_batch_color_bits",
 )
 
 _lib: Optional[C.CDLL] = None
@@ -141,6 +165,14 @@ def load() -> C.CDLL:
         "canny_hip_selftest_div": ([p, f, C.POINTER(C.c_ulonglong), C.POINTER(C.c_float)], i),
         "canny_hip_selftest_div_fma": ([p, f, f, C.POINTER(C.c_ulonglong), C.POINTER(C.c_float)], i),
         "canny_hip_selftest_div_fma_table": ([i, C.POINTER(C.c_float), C.POINTER(C.c_float)], i),
+        "canny_hip_to_gray": ([p, p, i, i, i, p], i),
+        "canny_hip_dev_to_gray": ([p, p, i, i, i, i, p], i),
+        "canny_hip_dev_gaussian_u8_color": ([p, p, i, f, i, i, i, p], i),
+        "canny_hip_dev_canny_color": ([p, p, i, f, i, i, i, i, i, p], i),
+        "canny_hip_canny_color": ([p, p, i, f, i, i, i, i, p], i),
+        "canny_hip_canny_batch_color": ([p, p, i, i, f, i, i, i, i, p], i),
+        "canny_hip_canny_batch_color_u8": ([p, p, i, i, f, i, i, i, i, p], i),
+        "canny_hip_canny_batch_color_bits": ([p, p, i, i, f, i, i, i, i, p], i),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -212,6 +244,11 @@ def _u8(img) -> np.ndarray:
     if a.ndim != 2:
         raise ValueError("expected a 2-D uint8 image")
     return a
+
+
+def _frame(img, order: str, batch: bool = False) -> Tuple[np.ndarray, int]:
+    a = np.ascontiguousarray(img, dtype=np.uint8)
+    return a, layout_of(a.shape, order, batch)
 
 
 def _s16(img) -> np.ndarray:
@@ -392,6 +429,40 @@ class Context:
                     "canny_batch")
         return out
 
+    # ---- colour frames (interleaved BGR / RGB / BGRA / RGBA; the rule is the "gray_rule" option) --------------
+    def to_gray(self, frame, order: str = "bgr") -> np.ndarray:
+        """(H, W, 3|4) uint8 frame -> its (H, W) gray plane, converted on the GPU."""
+        a, lay = _frame(frame, order)
+        out = np.empty(a.shape[:2], np.uint8)
+        self._check(self._L.canny_hip_to_gray(self._h, _hp(a), lay, a.shape[0], a.shape[1], _hp(out)), "to_gray")
+        return out
+
+    def canny_color(self, frame, sigma: float, min_val: int, max_val: int, order: str = "bgr") -> np.ndarray:
+        """canny() of a colour frame: the same map as canny(to_gray(frame))."""
+        a, lay = _frame(frame, order)
+        out = np.empty(a.shape[:2], np.int16)
+        self._check(self._L.canny_hip_canny_color(self._h, _hp(a), lay, sigma, min_val, max_val, a.shape[0],
+                                                  a.shape[1], _hp(out)), "canny_color")
+        return out
+
+    def canny_batch_color(self, imgs, sigma: float, min_val: int, max_val: int, order: str = "bgr",
+                          out: Optional[np.ndarray] = None, fmt: str = "s16") -> np.ndarray:
+        """canny_batch() of (N, H, W, 3|4) colour frames; fmt "s16" (int16 maps), "u8" or "bits" (see canny_batch)."""
+        a, lay = _frame(imgs, order, batch=True)
+        if fmt not in ("s16", "u8", "bits"):
+            raise ValueError(f"fmt must be 's16', 'u8' or 'bits', not {fmt!r}")
+        n, h, w = a.shape[:3]
+        dtype = np.int16 if fmt == "s16" else np.uint8
+        shape = bits_shape((n, h, w)) if fmt == "bits" else (n, h, w)
+        if out is None:
+            out = np.empty(shape, dtype)
+        elif out.shape != shape or out.dtype != dtype or not out.flags["C_CONTIGUOUS"]:
+            raise ValueError(f"out must be a C-contiguous {np.dtype(dtype).name} array of shape {shape}")
+        fn = {"s16": self._L.canny_hip_canny_batch_color, "u8": self._L.canny_hip_canny_batch_color_u8,
+              "bits": self._L.canny_hip_canny_batch_color_bits}[fmt]
+        self._check(fn(self._h, _hp(a), lay, n, sigma, min_val, max_val, h, w, _hp(out)), "canny_batch_color")
+        return out
+
     def selftest_mag_angle(self, lim: int = 1020):
         side = 2 * lim + 1
         mags = np.empty((side, side), np.int16)
@@ -475,6 +546,20 @@ class Context:
     def dev_canny_u8(self, d_img: int, sigma: float, min_val: int, max_val: int, h: int, w: int, n: int, d_edges: int):
         self._check(self._L.canny_hip_dev_canny_u8(self._h, C.c_void_p(d_img), sigma, min_val, max_val, h, w, n,
                                                    C.c_void_p(d_edges)), "dev_canny_u8")
+
+    def dev_to_gray(self, d_src: int, layout: int, h: int, w: int, n: int, d_gray: int):
+        self._check(self._L.canny_hip_dev_to_gray(self._h, C.c_void_p(d_src), layout, h, w, n, C.c_void_p(d_gray)),
+                    "dev_to_gray")
+
+    def dev_gaussian_u8_color(self, d_src: int, layout: int, sigma: float, h: int, w: int, n: int, d_out: int):
+        """The fused Gaussian alone (colour in, u8 smoothed plane out); raises UNSUPPORTED where it does not apply."""
+        self._check(self._L.canny_hip_dev_gaussian_u8_color(self._h, C.c_void_p(d_src), layout, sigma, h, w, n,
+                                                            C.c_void_p(d_out)), "dev_gaussian_u8_color")
+
+    def dev_canny_color(self, d_src: int, layout: int, sigma: float, min_val: int, max_val: int, h: int, w: int,
+                        n: int, d_edges: int):
+        self._check(self._L.canny_hip_dev_canny_color(self._h, C.c_void_p(d_src), layout, sigma, min_val, max_val, h,
+                                                      w, n, C.c_void_p(d_edges)), "dev_canny_color")
 
 
 def bits_shape(frames_shape) -> Tuple[int, int, int]:
@@ -579,3 +664,8 @@ def findEdgePixels(edgeCandidates, visited, start: int, minVal: int, maxVal: int
 
 def canny(img, sigma: float, minVal: int, maxVal: int) -> np.ndarray:
     return default_context().canny(img, sigma, minVal, maxVal)
+
+
+def canny_color(frame, sigma: float, minVal: int, maxVal: int, order: str = "bgr") -> np.ndarray:
+    """canny() of an (H, W, 3|4) colour frame -- the reference's cvtColor + canny() (src/main.cpp:114-136)."""
+    return default_context().canny_color(frame, sigma, minVal, maxVal, order)

@@ -338,6 +338,11 @@ struct canny_hip_ctx {
     // [0,255], src/utils.cpp:62): 0 = s16 plane, 1 = u8 plane
     int smoothed_u8 = 1; // canny(): the plane between the Gaussian and the fused Sobel+NMS as bytes (round 3 default)
     int last_canny_u8 = 0; // whether the last canny call really used it (window, taps and shape permitting)
+    // colour input (canny_hip_*_color): the conversion rule (0 OpenCV, 1 PIL), whether the Gaussian may convert as it
+    // loads (1) or a standalone pass always converts first (0), and whether the last colour canny call fused
+    int gray_rule = 0;
+    int fuse_gray = 1;
+    int last_fused_gray = 0;
     // canny(): after the two batch-wide sweeps, one launch with a workgroup per frame finishes the propagation
     // (launch_hyst_tail): no further launches, no host round trip, the call returns without waiting.
     // 1 (default) = for frames of up to kTailMaxTiles tiles, 0 = never (the multi-launch scheme with its poll)
@@ -365,6 +370,7 @@ struct canny_hip_ctx {
     DevBuf tmp_f32;   // generic Gaussian row-pass plane
     DevBuf smoothed;  // pipeline: Gaussian output
     DevBuf edges16;   // canny_hip_dev_canny_u8: the s16 edge map before narrowing
+    DevBuf gray;      // colour input: the converted plane when the Gaussian cannot convert itself
     DevBuf plane_s, plane_c, stamps, flags; // hysteresis bit-planes / scheduling words
     DevBuf io[4];     // staging for the host-pointer stage functions
     unsigned *host_flags = nullptr;     // pinned + mapped, 4 words per lane: last_change, domain, sequence number, spare
@@ -515,6 +521,41 @@ bool hysteresis_order_dependent(int min_val, int max_val) { return min_val > 255
 
 size_t npx(int height, int width, int n_frames) { return (size_t)height * (size_t)width * (size_t)n_frames; }
 
+// ---- colour input ---------------------------------------------------------------------------------
+// A colour call's input as the kernels see it: bytes per pixel, the rule with its weights in the layout's byte order,
+// and whether the Gaussian may convert.  Resolved once per call on the caller's context and handed to the batch
+// pipelines' sub-contexts as it is (they do not share the caller's options).
+struct ColorIn {
+    int layout = CANNY_HIP_GRAY8;
+    int ch = 1;
+    GrayRule rule{};
+    bool fuse = true;
+};
+
+int make_color_in(const canny_hip_ctx *ctx, int layout, ColorIn &ci)
+{
+    // (wb, wg, wr, shift): OpenCV's RGB2Gray<uchar> (B2Y / G2Y / R2Y, yuv_shift 14) and PIL's convert('L')
+    static const uint32_t kRules[2][4] = {{1868u, 9617u, 4899u, 14u}, {7471u, 38470u, 19595u, 16u}};
+    const uint32_t *w = kRules[ctx->gray_rule];
+    ci.layout = layout;
+    ci.fuse = ctx->fuse_gray != 0;
+    switch (layout) {
+    case CANNY_HIP_GRAY8: ci.ch = 1; break;
+    case CANNY_HIP_BGR8: ci.ch = 3; break;
+    case CANNY_HIP_RGB8: ci.ch = 3; break;
+    case CANNY_HIP_BGRA8: ci.ch = 4; break;
+    case CANNY_HIP_RGBA8: ci.ch = 4; break;
+    default: return CANNY_HIP_ERR_INVALID;
+    }
+    const bool bgr = layout == CANNY_HIP_BGR8 || layout == CANNY_HIP_BGRA8;
+    ci.rule.k0 = bgr ? w[0] : w[2];
+    ci.rule.k1 = w[1];
+    ci.rule.k2 = bgr ? w[2] : w[0];
+    ci.rule.shift = w[3];
+    ci.rule.rnd = 1u << (w[3] - 1);
+    return CANNY_HIP_OK;
+}
+
 // ---- device-level stages ------------------------------------------------------------------------
 // Can the Gaussian hand its result to Sobel+NMS as bytes?  (marching symmetric-tap kernel on both sides)
 bool gaussian_u8_possible(const canny_hip_ctx *ctx, const GaussTaps &taps, int h, int w)
@@ -555,6 +596,39 @@ int dev_gaussian(canny_hip_ctx *ctx, const unsigned char *d_img, float sigma, in
         HIP_TRY(ctx, ctx->tmp_f32.ensure(npx(h, w, n) * sizeof(float)));
         HIP_TRY(ctx, launch_gaussian_generic(d_img, (float *)ctx->tmp_f32.p, d_out, h, w, n, taps, ctx->stream));
     }
+    return CANNY_HIP_OK;
+}
+
+// colour -> gray on the device (GRAY8: a copy, unless in place)
+int dev_to_gray(canny_hip_ctx *ctx, const unsigned char *d_src, const ColorIn &ci, int h, int w, int n,
+                unsigned char *d_gray)
+{
+    const size_t px = npx(h, w, n);
+    if (ci.ch == 1) {
+        if (d_src != d_gray) HIP_TRY(ctx, hipMemcpyAsync(d_gray, d_src, px, hipMemcpyDeviceToDevice, ctx->stream));
+        return CANNY_HIP_OK;
+    }
+    StageTimer tm(ctx, CANNY_HIP_STAGE_TO_GRAY);
+    HIP_TRY(ctx, launch_to_gray(d_src, ci.ch, ci.rule, d_gray, px, ctx->stream));
+    return CANNY_HIP_OK;
+}
+
+// Can the Gaussian of canny()'s u8 path convert colour input itself?
+bool gaussian_color_fusable(const canny_hip_ctx *ctx, const GaussTaps &taps, const ColorIn &ci, int h, int w)
+{
+    return ci.ch > 1 && gaussian_u8_possible(ctx, taps, h, w) && gaussian_march_color_supported(taps, w, ci.ch);
+}
+
+// The fused Gaussian alone: colour in, u8 smoothed plane out
+int dev_gaussian_u8_color(canny_hip_ctx *ctx, const unsigned char *d_src, const ColorIn &ci, float sigma, int h, int w,
+                          int n, unsigned char *d_out)
+{
+    GaussTaps taps;
+    int rc = make_taps(sigma, taps);
+    if (rc) return rc;
+    if (!gaussian_color_fusable(ctx, taps, ci, h, w)) return CANNY_HIP_ERR_UNSUPPORTED;
+    StageTimer tm(ctx, CANNY_HIP_STAGE_GAUSSIAN);
+    HIP_TRY(ctx, launch_gaussian_march_u8_color(d_src, ci.ch, ci.rule, d_out, h, w, n, taps, ctx->stream));
     return CANNY_HIP_OK;
 }
 
@@ -723,8 +797,9 @@ int dev_sobel_nms(canny_hip_ctx *ctx, const short *d_smoothed, int h, int w, int
     return CANNY_HIP_OK;
 }
 
+// color: interleaved colour input (canny_hip_*_color); null = the gray plane of every other entry point
 int dev_canny(canny_hip_ctx *ctx, const unsigned char *d_img, float sigma, int lo, int hi, int h, int w, int n,
-              short *d_edges)
+              short *d_edges, const ColorIn *color = nullptr)
 {
     if (h < 2 || w < 2) return CANNY_HIP_ERR_UNSUPPORTED;
     if (hysteresis_order_dependent(lo, hi)) return CANNY_HIP_ERR_DOMAIN;
@@ -740,7 +815,26 @@ int dev_canny(canny_hip_ctx *ctx, const unsigned char *d_img, float sigma, int l
         if (gaussian_u8_possible(ctx, taps, h, w)) sm_u8 = ctx->smoothed_u8;
     }
     ctx->last_canny_u8 = sm_u8;
-    if ((rc = dev_gaussian(ctx, d_img, sigma, h, w, n, sm, sm_u8))) return rc;
+    if (color && color->ch > 1) {
+        // colour: the u8 Gaussian converts as it loads where it can, else a standalone pass converts first and the
+        // gray path runs unchanged on the context's gray workspace
+        GaussTaps taps;
+        if ((rc = make_taps(sigma, taps))) return rc;
+        const bool fuse = sm_u8 && color->fuse && gaussian_color_fusable(ctx, taps, *color, h, w);
+        ctx->last_fused_gray = fuse;
+        if (fuse) {
+            StageTimer tm(ctx, CANNY_HIP_STAGE_GAUSSIAN);
+            HIP_TRY(ctx, launch_gaussian_march_u8_color(d_img, color->ch, color->rule, (uint8_t *)sm, h, w, n, taps,
+                                                        ctx->stream));
+        } else {
+            HIP_TRY(ctx, ctx->gray.ensure(npx(h, w, n)));
+            if ((rc = dev_to_gray(ctx, d_img, *color, h, w, n, (unsigned char *)ctx->gray.p))) return rc;
+            if ((rc = dev_gaussian(ctx, (const unsigned char *)ctx->gray.p, sigma, h, w, n, sm, sm_u8))) return rc;
+        }
+    } else {
+        if (color) ctx->last_fused_gray = 0;
+        if ((rc = dev_gaussian(ctx, d_img, sigma, h, w, n, sm, sm_u8))) return rc;
+    }
     // Sobel+NMS+classify on the s16 or the u8 smoothed plane
     auto fused_sobel = [&](const short *smp, short *edges, uint64_t *S, uint64_t *C, const HystGeom &gg, int ev,
                            const LaunchEvents &le) -> hipError_t {
@@ -1088,6 +1182,9 @@ int canny_hip_ctx_get_option(const canny_hip_ctx *ctx, const char *name, int *va
     if (!ctx || !name || !value) return CANNY_HIP_ERR_INVALID;
     if (!std::strcmp(name, "smoothed_u8")) *value = ctx->smoothed_u8;
     else if (!std::strcmp(name, "last_canny_smoothed_u8")) *value = ctx->last_canny_u8; // read-only
+    else if (!std::strcmp(name, "gray_rule")) *value = ctx->gray_rule;
+    else if (!std::strcmp(name, "fuse_gray")) *value = ctx->fuse_gray;
+    else if (!std::strcmp(name, "last_canny_fused_gray")) *value = ctx->last_fused_gray; // read-only
     else if (!std::strcmp(name, "fuse_classify")) *value = ctx->fuse_classify;
     else if (!std::strcmp(name, "hysteresis_tail")) *value = ctx->hyst_tail;
     else if (!std::strcmp(name, "gaussian_path")) *value = ctx->gaussian_path;
@@ -1106,6 +1203,8 @@ int canny_hip_ctx_set_option(canny_hip_ctx *ctx, const char *name, int value)
     else if (!std::strcmp(name, "tune_sobel_seg") && value <= 4096) ctx->tune_sobel_seg = value;
     else if (!std::strcmp(name, "fuse_classify") && value <= 1) ctx->fuse_classify = value;
     else if (!std::strcmp(name, "smoothed_u8") && value <= 1) ctx->smoothed_u8 = value;
+    else if (!std::strcmp(name, "gray_rule") && value <= 1) ctx->gray_rule = value;
+    else if (!std::strcmp(name, "fuse_gray") && value <= 1) ctx->fuse_gray = value;
     else if (!std::strcmp(name, "hysteresis_tail") && value <= 1) ctx->hyst_tail = value;
     else if (!std::strcmp(name, "tune_hyst_tail_after") && value >= 1 && value <= 4) ctx->hyst_tail_after = value;
     else if (!std::strcmp(name, "overlap_hysteresis") && value <= 1) ctx->overlap_hysteresis = value;
@@ -1367,7 +1466,8 @@ int canny_hip_find_edge_pixels(canny_hip_ctx *ctx, short *edge_candidates, unsig
 
 enum MapFormat { kMapS16 = 0, kMapU8 = 1, kMapBits = 2 };
 static int canny_batch_impl(canny_hip_ctx *ctx, const unsigned char *imgs, int n_frames, float sigma, int min_val,
-                            int max_val, int height, int width, void *edges, MapFormat fmt);
+                            int max_val, int height, int width, void *edges, MapFormat fmt,
+                            const ColorIn *color = nullptr);
 
 int canny_hip_canny(canny_hip_ctx *ctx, const unsigned char *img, float sigma, int min_val, int max_val, int height,
                     int width, short *edges)
@@ -1421,8 +1521,9 @@ static size_t map_frame_bytes(MapFormat fmt, int height, int width)
     return npx(height, width, 1) * (fmt == kMapU8 ? 1 : sizeof(short));
 }
 
+// color: interleaved colour frames (CH bytes per pixel): chunks, staging and uploads are sized in input bytes
 static int canny_batch_impl(canny_hip_ctx *ctx, const unsigned char *imgs, int n_frames, float sigma, int min_val,
-                            int max_val, int height, int width, void *edges, MapFormat fmt)
+                            int max_val, int height, int width, void *edges, MapFormat fmt, const ColorIn *color)
 {
     using Pipe = canny_hip_ctx::BatchPipe;
     int rc = bind(ctx);
@@ -1434,6 +1535,7 @@ static int canny_batch_impl(canny_hip_ctx *ctx, const unsigned char *imgs, int n
     GaussTaps probe;
     if ((rc = make_taps(sigma, probe))) return rc;
     const size_t frame_px = npx(height, width, 1);
+    const size_t frame_in = frame_px * (color ? (size_t)color->ch : 1u); // input bytes of one frame
     const int device = ctx->device;
     // Buffers from canny_hip_host_alloc (or any hipHostMalloc / hipHostRegister'd memory) need no staging.
     auto is_pinned = [](const void *p) {
@@ -1480,7 +1582,7 @@ static int canny_batch_impl(canny_hip_ctx *ctx, const unsigned char *imgs, int n
     const bool three_streams = ctx->batch_pipe_mode ? ctx->batch_pipe_mode == 1 : all_pinned;
     size_t chunk_frames = ctx->batch_chunk_frames
                               ? (size_t)ctx->batch_chunk_frames
-                              : ((size_t)(ctx->batch_chunk_mb ? ctx->batch_chunk_mb : (all_pinned ? 24 : 8)) << 20) / frame_px;
+                              : ((size_t)(ctx->batch_chunk_mb ? ctx->batch_chunk_mb : (all_pinned ? 24 : 8)) << 20) / frame_in;
     // never more than the 65535 frames a launch takes
     const int chunk = (int)std::max<size_t>(1, std::min<size_t>(std::min<size_t>((size_t)n_frames, 65535), chunk_frames));
     const int n_chunks = (n_frames + chunk - 1) / chunk;
@@ -1512,7 +1614,7 @@ static int canny_batch_impl(canny_hip_ctx *ctx, const unsigned char *imgs, int n
             return;
         }
         const int my_chunks = (n_chunks - wid + n_workers - 1) / n_workers;
-        const size_t in_bytes = frame_px * chunk, out_bytes = wire_frame * chunk;
+        const size_t in_bytes = frame_in * chunk, out_bytes = wire_frame * chunk;
         hipError_t e = hipSuccess;
         constexpr int n_slots = Pipe::kSlots;
         for (int k = 0; k < std::min(my_chunks, n_slots) && e == hipSuccess; k++) {
@@ -1542,7 +1644,7 @@ static int canny_batch_impl(canny_hip_ctx *ctx, const unsigned char *imgs, int n
             Pipe::Slot &S = P.slot[j % n_slots];
             int f0, nf;
             chunk_range(j, f0, nf);
-            const unsigned char *src = imgs + (size_t)f0 * frame_px;
+            const unsigned char *src = imgs + (size_t)f0 * frame_in;
             hipError_t err = hipSuccess;
             if (j >= n_slots) {
                 // the slot's previous user (chunk j - kSlots): its kernels must have read d_in (dev_canny no longer
@@ -1553,12 +1655,12 @@ static int canny_batch_impl(canny_hip_ctx *ctx, const unsigned char *imgs, int n
             }
             if (!in_pinned) {
                 if (pool_staging)
-                    ctx->expand_pool->parallel_copy(S.pin_in.p, src, frame_px * nf);
+                    ctx->expand_pool->parallel_copy(S.pin_in.p, src, frame_in * nf);
                 else
-                    std::memcpy(S.pin_in.p, src, frame_px * nf);
+                    std::memcpy(S.pin_in.p, src, frame_in * nf);
                 src = (const unsigned char *)S.pin_in.p;
             }
-            err = hipMemcpyAsync(S.d_in.p, src, frame_px * nf, hipMemcpyHostToDevice, s_h2d);
+            err = hipMemcpyAsync(S.d_in.p, src, frame_in * nf, hipMemcpyHostToDevice, s_h2d);
             if (err == hipSuccess) err = hipEventRecord(S.ev_h2d, s_h2d);
             return err;
         };
@@ -1605,7 +1707,7 @@ static int canny_batch_impl(canny_hip_ctx *ctx, const unsigned char *imgs, int n
             if ((e = hipStreamWaitEvent(sub->stream, S.ev_h2d, 0)) != hipSuccess) break;
             if (S.d2h_issued && (e = hipStreamWaitEvent(sub->stream, S.ev_d2h, 0)) != hipSuccess) break;
             st = dev_canny(sub, (const unsigned char *)S.d_in.p, sigma, min_val, max_val, height, width, nf,
-                           (short *)S.d_out.p);
+                           (short *)S.d_out.p, color);
             if (st) break;
             const void *d_res = S.d_out.p;
             if (fmt != kMapS16 || compact) { // narrow on the device: the D2H copy is what these variants are for
@@ -1683,6 +1785,71 @@ int canny_hip_canny_batch_bits(canny_hip_ctx *ctx, const unsigned char *imgs, in
                                int max_val, int height, int width, unsigned char *bits)
 {
     return canny_batch_impl(ctx, imgs, n_frames, sigma, min_val, max_val, height, width, bits, kMapBits);
+}
+
+// ---- colour input on host buffers --------------------------------------------------------------------
+int canny_hip_to_gray(canny_hip_ctx *ctx, const unsigned char *src, int layout, int height, int width,
+                      unsigned char *gray)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!src || !gray) return CANNY_HIP_ERR_INVALID;
+    ColorIn ci;
+    if ((rc = make_color_in(ctx, layout, ci)) || (rc = check_dims(height, width, 1))) return rc;
+    const size_t n = npx(height, width, 1);
+    if ((rc = h2d(ctx, ctx->io[0], src, n * ci.ch))) return rc;
+    HIP_TRY(ctx, ctx->io[1].ensure(n));
+    if ((rc = dev_to_gray(ctx, (const unsigned char *)ctx->io[0].p, ci, height, width, 1, (unsigned char *)ctx->io[1].p)))
+        return rc;
+    return d2h_sync(ctx, gray, ctx->io[1].p, n);
+}
+
+int canny_hip_canny_color(canny_hip_ctx *ctx, const unsigned char *src, int layout, float sigma, int min_val,
+                          int max_val, int height, int width, short *edges)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!src || !edges) return CANNY_HIP_ERR_INVALID;
+    ColorIn ci;
+    if ((rc = make_color_in(ctx, layout, ci)) || (rc = check_dims(height, width, 1))) return rc;
+    const size_t n = npx(height, width, 1);
+    // as canny_hip_canny: a megapixel and more goes through the batch pipeline as a batch of one
+    if (n >= (1u << 20) && height >= 2 && width >= 2 && ctx->batch_compact != 1)
+        return canny_batch_impl(ctx, src, 1, sigma, min_val, max_val, height, width, edges, kMapS16, &ci);
+    if ((rc = h2d(ctx, ctx->io[0], src, n * ci.ch))) return rc;
+    HIP_TRY(ctx, ctx->io[1].ensure(n * 2));
+    if ((rc = dev_canny(ctx, (const unsigned char *)ctx->io[0].p, sigma, min_val, max_val, height, width, 1,
+                        (short *)ctx->io[1].p, &ci)))
+        return rc;
+    return d2h_sync(ctx, edges, ctx->io[1].p, n * 2);
+}
+
+static int canny_batch_color_impl(canny_hip_ctx *ctx, const unsigned char *srcs, int layout, int n_frames, float sigma,
+                                  int min_val, int max_val, int height, int width, void *edges, MapFormat fmt)
+{
+    if (!ctx) return CANNY_HIP_ERR_INVALID;
+    ColorIn ci;
+    int rc = make_color_in(ctx, layout, ci);
+    if (rc) return rc;
+    return canny_batch_impl(ctx, srcs, n_frames, sigma, min_val, max_val, height, width, edges, fmt, &ci);
+}
+
+int canny_hip_canny_batch_color(canny_hip_ctx *ctx, const unsigned char *srcs, int layout, int n_frames, float sigma,
+                                int min_val, int max_val, int height, int width, short *edges)
+{
+    return canny_batch_color_impl(ctx, srcs, layout, n_frames, sigma, min_val, max_val, height, width, edges, kMapS16);
+}
+
+int canny_hip_canny_batch_color_u8(canny_hip_ctx *ctx, const unsigned char *srcs, int layout, int n_frames, float sigma,
+                                   int min_val, int max_val, int height, int width, unsigned char *edges)
+{
+    return canny_batch_color_impl(ctx, srcs, layout, n_frames, sigma, min_val, max_val, height, width, edges, kMapU8);
+}
+
+int canny_hip_canny_batch_color_bits(canny_hip_ctx *ctx, const unsigned char *srcs, int layout, int n_frames,
+                                     float sigma, int min_val, int max_val, int height, int width, unsigned char *bits)
+{
+    return canny_batch_color_impl(ctx, srcs, layout, n_frames, sigma, min_val, max_val, height, width, bits, kMapBits);
 }
 
 // ---- multi-GPU sharder (BASELINE config 5) -----------------------------------------------------------
@@ -1937,6 +2104,40 @@ int canny_hip_dev_canny(canny_hip_ctx *ctx, const unsigned char *d_img, float si
     if (!d_img || !d_edges) return CANNY_HIP_ERR_INVALID;
     if ((rc = check_dims(height, width, n_frames))) return rc;
     return dev_canny(ctx, d_img, sigma, min_val, max_val, height, width, n_frames, d_edges);
+}
+
+int canny_hip_dev_to_gray(canny_hip_ctx *ctx, const unsigned char *d_src, int layout, int height, int width,
+                          int n_frames, unsigned char *d_gray)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!d_src || !d_gray) return CANNY_HIP_ERR_INVALID;
+    ColorIn ci;
+    if ((rc = make_color_in(ctx, layout, ci)) || (rc = check_dims(height, width, n_frames))) return rc;
+    return dev_to_gray(ctx, d_src, ci, height, width, n_frames, d_gray);
+}
+
+int canny_hip_dev_gaussian_u8_color(canny_hip_ctx *ctx, const unsigned char *d_src, int layout, float sigma, int height,
+                                    int width, int n_frames, unsigned char *d_result)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!d_src || !d_result) return CANNY_HIP_ERR_INVALID;
+    ColorIn ci;
+    if ((rc = make_color_in(ctx, layout, ci)) || (rc = check_dims(height, width, n_frames))) return rc;
+    if (ci.ch == 1) return dev_gaussian(ctx, d_src, sigma, height, width, n_frames, d_result, 1);
+    return dev_gaussian_u8_color(ctx, d_src, ci, sigma, height, width, n_frames, d_result);
+}
+
+int canny_hip_dev_canny_color(canny_hip_ctx *ctx, const unsigned char *d_src, int layout, float sigma, int min_val,
+                              int max_val, int height, int width, int n_frames, short *d_edges)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!d_src || !d_edges) return CANNY_HIP_ERR_INVALID;
+    ColorIn ci;
+    if ((rc = make_color_in(ctx, layout, ci)) || (rc = check_dims(height, width, n_frames))) return rc;
+    return dev_canny(ctx, d_src, sigma, min_val, max_val, height, width, n_frames, d_edges, &ci);
 }
 
 int canny_hip_dev_canny_stream(canny_hip_ctx *ctx, const unsigned char *d_img, float sigma, int min_val, int max_val,

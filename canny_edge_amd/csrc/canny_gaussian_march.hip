@@ -37,10 +37,12 @@
 #include <cstring>
 #include <type_traits>
 
-// The file is compiled FOUR times (Makefile: -DCANNY_GAUSS_PART=0..3 -> canny_gaussian_march_p<k>.o) so that the eight
+// The file is compiled FIVE times (Makefile: -DCANNY_GAUSS_PART=0..4 -> canny_gaussian_march_p<k>.o) so that the eight
 // window instantiations, which dominate the library's build time, compile in parallel: part 0 holds the host-side
 // entry points, the switches and windows 3..9 (half-windows 1..4), part 1 half-windows 5 and 6, part 2 half-window 7,
-// part 3 half-window 8.  Without the macro (tools/gauss_isa.sh) everything is one translation unit.
+// part 3 half-window 8; part 4 holds the colour-input kernels (half-windows 1..4), so that parts 0..3 compile what
+// they compiled before those existed.  Without the macro (tools/gauss_isa.sh) everything is one
+// translation unit.
 #ifndef CANNY_GAUSS_PART
 #define CANNY_GAUSS_PART -1
 #endif
@@ -59,6 +61,9 @@ hipError_t launch_gauss_march_part2(int center, const uint8_t *img, void *out, i
                                     const GaussTaps &taps, hipStream_t stream, int out_u8);
 hipError_t launch_gauss_march_part3(int center, const uint8_t *img, void *out, int height, int width, int n_frames,
                                     const GaussTaps &taps, hipStream_t stream, int out_u8);
+// launcher of the colour-input instantiations (part 4)
+hipError_t launch_gauss_color_part4(const uint8_t *src, int ch, const GrayRule &rule, uint8_t *out, int height,
+                                    int width, int n_frames, const GaussTaps &taps, hipStream_t stream);
 
 namespace {
 
@@ -336,10 +341,21 @@ struct SysCfg {
     static constexpr int SW = (64 - NL) * 4;         // output columns per strip
 };
 
-template <int C, bool COL_EDGE, bool ROW_EDGE, bool FMA_DIV, bool USE_LUT, bool OUT_U8 = false, bool SYS = false>
+// CH = 3 / 4 (colour input, SYS + table + OUT_U8 only): the source rows are interleaved CH-byte pixels and each lane
+// loads the 4*CH bytes of its four pixels with ONE load; gray4() turns them into the same gray dword the CH = 1 kernel
+// loads, where the row is used (fix_row).  Everything downstream of that dword is the CH = 1 code.
+template <int CH>
+struct ColorRow {
+    uint32_t w[CH];
+};
+
+template <int C, bool COL_EDGE, bool ROW_EDGE, bool FMA_DIV, bool USE_LUT, bool OUT_U8 = false, bool SYS = false,
+          int CH = 1>
 __device__ __forceinline__ void gauss_sym_strip(const GaussJob &jb, const GaussTaps &t, const float *lut, float *wts,
-                                                float fma_c = 0.0f)
+                                                float fma_c = 0.0f, const GrayRule &rule = GrayRule{})
 {
+    static_assert(CH == 1 || (SYS && USE_LUT && OUT_U8), "colour input: the default (systolic, table, u8) kernel only");
+    using Raw = std::conditional_t<CH == 1, uint32_t, ColorRow<CH>>; // a row's loaded bytes, before conversion
     static_assert(!FMA_DIV || (!COL_EDGE && !ROW_EDGE), "FMA_DIV needs a single wave-uniform divisor");
     constexpr int HL = MarchCfg<C>::HL, RING = 2 * C + 1;
     static_assert(HL <= 2, "products travel at most two lanes");
@@ -408,7 +424,7 @@ __device__ __forceinline__ void gauss_sym_strip(const GaussJob &jb, const GaussT
     // dead at that point and no register copy is needed (opaque_offset() on a loop-invariant value costs a v_mov
     // per use).  Both are only used where x0 >= 0.
     // (The systolic form loads C bytes right of x0: the constant goes into the uniform base.)
-    uint32_t ld_off = (uint32_t)x0, st_off = (OUT_U8 ? 1u : 2u) * (uint32_t)x0;
+    uint32_t ld_off = (uint32_t)CH * (uint32_t)x0, st_off = (OUT_U8 ? 1u : 2u) * (uint32_t)x0;
     // Border strips (W >= 4, the launcher sees to that): a lane whose four columns hang over the left or right image
     // border loads the nearest dword that lies inside the row and shifts the outside bytes away -- zeros come in, which
     // is what an out-of-image pixel has to be (see "Bit-exactness" above).  One load per lane and row as in the
@@ -417,7 +433,7 @@ __device__ __forceinline__ void gauss_sym_strip(const GaussJob &jb, const GaussT
     const bool in_any = xin > -4 && xin < W; // at least one column inside
     if (COL_EDGE) {
         const int xc = min(max(xin, 0), W - 4);
-        ld_off = (uint32_t)xc; // from the row's first byte: the offset register is UNSIGNED (xc - C would wrap)
+        ld_off = (uint32_t)CH * (uint32_t)xc; // from the row's first byte: the offset register is UNSIGNED (xc - C would wrap)
         if (in_any) {
             sh_l = (uint32_t)(8 * (xc - xin)) & 31u;     // xin < 0: pixel 0 moves up to byte -xin
             sh_r = (uint32_t)(8 * (xin - xc)) & 31u;     // xin > W - 4: byte xin - (W - 4) moves down to byte 0
@@ -426,12 +442,12 @@ __device__ __forceinline__ void gauss_sym_strip(const GaussJob &jb, const GaussT
         }
     }
 
-    auto load_row = [&](int r) -> uint32_t {
-        if (ROW_EDGE && (r < 0 || r >= H)) return 0u; // wave-uniform
-        const uint8_t *p = jb.fimg + (size_t)r * W; // wave-uniform
-        uint32_t v = 0u;
+    auto load_row = [&](int r) -> Raw {
+        if (ROW_EDGE && (r < 0 || r >= H)) return Raw{}; // wave-uniform
+        const uint8_t *p = jb.fimg + (size_t)r * W * CH; // wave-uniform
+        Raw v{};
         asm volatile("" : "+v"(ld_off)); // see ld_off
-        __builtin_memcpy(&v, p + (COL_EDGE ? 0 : xin - x0) + ld_off, 4);
+        __builtin_memcpy(&v, p + (COL_EDGE ? 0 : CH * (xin - x0)) + ld_off, 4 * CH);
         return v;
     };
     // applied where the row is USED (two rows after the load): shifting at the load would wait for it there
@@ -697,22 +713,53 @@ __device__ __forceinline__ void gauss_sym_strip(const GaussJob &jb, const GaussT
     // (ROT: three rows ahead -- the look-ups need a row half a step earlier)
     constexpr int AHEAD = ROT ? 3 : 2;
     uint32_t pf[RING];
-    pf[0] = load_row(rfirst);
-    pf[1] = load_row(rfirst + 1);
-    if (ROT) {
-        pf[2] = load_row(rfirst + 2);
-        products(fix_row(pf[0]));
-    }
-    for (int r = rfirst; r <= rlast; r += RING) {
-        for_each_phase(
-            [&](auto ph) {
-                constexpr int PH = decltype(ph)::value;
-                pf[(PH + AHEAD) % RING] = load_row(r + PH + AHEAD);
-                step(ph, r + PH, pf[PH], pf[(PH + 1) % RING]);
-                // keep the scheduler from interleaving rows: one row's products are all the registers allow
-                __builtin_amdgcn_sched_barrier(0);
-            },
-            std::make_integer_sequence<int, RING>{});
+    if constexpr (CH == 1) {
+        pf[0] = load_row(rfirst);
+        pf[1] = load_row(rfirst + 1);
+        if (ROT) {
+            pf[2] = load_row(rfirst + 2);
+            products(fix_row(pf[0]));
+        }
+        for (int r = rfirst; r <= rlast; r += RING) {
+            for_each_phase(
+                [&](auto ph) {
+                    constexpr int PH = decltype(ph)::value;
+                    pf[(PH + AHEAD) % RING] = load_row(r + PH + AHEAD);
+                    step(ph, r + PH, pf[PH], pf[(PH + 1) % RING]);
+                    // keep the scheduler from interleaving rows: one row's products are all the registers allow
+                    __builtin_amdgcn_sched_barrier(0);
+                },
+                std::make_integer_sequence<int, RING>{});
+        }
+    } else {
+        // Colour: pf[] holds the rows already converted to gray dwords; the newest row waits in `pending` (CH registers)
+        // and is converted at the start of the NEXT row step, before that step's load -- a whole row step after its
+        // own load was issued (so the wait is for that load only, vmcnt leaves the step's store in flight), and only
+        // one row is ever held as CH registers instead of the AHEAD rows a conversion at the point of use would keep.
+        Raw pending;
+        pf[0] = gray4<CH>(load_row(rfirst).w, rule);
+        if (ROT) {
+            pf[1] = gray4<CH>(load_row(rfirst + 1).w, rule);
+            pending = load_row(rfirst + 2);
+            products(fix_row(pf[0]));
+        } else {
+            pending = load_row(rfirst + 1);
+        }
+        for (int r = rfirst; r <= rlast; r += RING) {
+            for_each_phase(
+                [&](auto ph) {
+                    constexpr int PH = decltype(ph)::value;
+                    pf[(PH + AHEAD - 1) % RING] = gray4<CH>(pending.w, rule);
+                    // the conversion happens HERE (the scheduler would otherwise keep the CH source registers alive
+                    // beside the next row's and sink the arithmetic into the step)
+                    asm volatile("" : "+v"(pf[(PH + AHEAD - 1) % RING]));
+                    __builtin_amdgcn_sched_barrier(0);
+                    pending = load_row(r + PH + AHEAD);
+                    step(ph, r + PH, pf[PH], pf[(PH + 1) % RING]);
+                    __builtin_amdgcn_sched_barrier(0);
+                },
+                std::make_integer_sequence<int, RING>{});
+        }
     }
 }
 
@@ -777,6 +824,65 @@ void gauss_sym_kernel(const uint8_t *__restrict__ img, void *__restrict__ out, i
             gauss_sym_strip<C, false, false, true, USE_LUT, OUT_U8, SYS>(jb, t, lut, wts, fma_c);
         else
             gauss_sym_strip<C, false, false, false, USE_LUT, OUT_U8, SYS>(jb, t, lut, wts);
+    }
+}
+
+
+// The same kernel on interleaved colour rows (CH = 3 / 4 bytes per pixel; the default variant -- systolic row pass,
+// product table, u8 output -- only), with the same occupancy target: a window whose colour form would spill there is
+// not fused (gaussian_march_color_supported).  Its body is gauss_sym_kernel's with those choices made; the gray kernel
+// keeps its own text so that its code stays exactly what it was.
+template <int C, int CH>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(C <= 5 ? 5 : C <= 7 ? 4 : 3)))
+void gauss_sym_color_kernel(const uint8_t *__restrict__ src, uint8_t *__restrict__ out, int H, int W, int n_strips,
+                            int n_segs, int seg_rows, int total_waves, GaussTaps t, int use_fma_div, float fma_c,
+                            GrayRule rule)
+{
+    using K = MarchCfg<C>;
+    // product table of the row pass (USE_LUT): the only LDS use and the only workgroup barrier of the kernel
+    __shared__ float lut_mem[(C + 1) * 256];
+#pragma unroll
+    for (int a = 0; a <= C; a++) lut_mem[a * 256 + threadIdx.x] = __fmul_rn((float)threadIdx.x, t.tap[C - a]);
+    __syncthreads();
+    const float *lut = lut_mem;
+    // per-lane column-border weights (border strips only, see gauss_sym_strip)
+    __shared__ __attribute__((aligned(16))) float wts_mem[256 * 8];
+    float *wts = wts_mem + threadIdx.x * 8;
+    const int lane = threadIdx.x & 63;
+    const int wave = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); // wave-uniform
+    if (wave >= total_waves) return;
+
+    const int f = wave / (n_strips * n_segs);
+    const MarchCell cell = march_cell_of(wave - f * (n_strips * n_segs), n_segs, n_strips); // border cells first
+    const int s = cell.strip, g = cell.seg;
+    GaussJob jb;
+    jb.lane = lane;
+    jb.H = H;
+    jb.W = W;
+    jb.ybeg = g * seg_rows;
+    jb.yend = min(H, jb.ybeg + seg_rows);
+    constexpr int SW = SysCfg<C>::SW, LEFT = SysCfg<C>::NL;
+    jb.x0 = s * SW + (lane - LEFT) * 4; // first of this lane's 4 output columns (halo lanes may be outside)
+    jb.fimg = src + (size_t)f * H * W * CH;
+    jb.fout = nullptr;
+    jb.fout8 = out + (size_t)f * H * W;
+
+    // the strip's lanes load columns [s*SW - 4HL, s*SW + SW + 4HL); systolic: [s*SW - 4NL + C, s*SW + SW + C)
+    const bool col_edge = (s * SW - 4 * LEFT + C < 0) || (s * SW + SW + C > W);
+    // rows loaded: ybeg-C .. yend-1+C, up to 2C more for the rounding to whole loop trips, +2 prefetched
+    const bool row_edge = (jb.ybeg - C < 0) || (jb.yend + C + K::RING + 1 >= H); // (+3 with rotated look-ups)
+    if (col_edge) {
+        if (row_edge)
+            gauss_sym_strip<C, true, true, false, true, true, true, CH>(jb, t, lut, wts, 0.0f, rule);
+        else
+            gauss_sym_strip<C, true, false, false, true, true, true, CH>(jb, t, lut, wts, 0.0f, rule);
+    } else {
+        if (row_edge)
+            gauss_sym_strip<C, false, true, false, true, true, true, CH>(jb, t, lut, wts, 0.0f, rule);
+        else if (use_fma_div)
+            gauss_sym_strip<C, false, false, true, true, true, true, CH>(jb, t, lut, wts, fma_c, rule);
+        else
+            gauss_sym_strip<C, false, false, false, true, true, true, CH>(jb, t, lut, wts, 0.0f, rule);
     }
 }
 
@@ -901,10 +1007,11 @@ hipError_t launch_selftest_div(float b, int use_fma, float c, unsigned first_bit
 
 #endif // CANNY_GAUSS_HAS_HOST
 
-// out_u8: 0 = s16 plane, 1 = u8 plane; the u8 form exists for the symmetric-tap kernel with the product table only
-template <int C>
+// out_u8: 0 = s16 plane, 1 = u8 plane; the u8 form exists for the symmetric-tap kernel with the product table only.
+// CH > 1: interleaved colour input (gauss_sym_color_kernel; u8 output, systolic variant with the table only).
+template <int C, int CH = 1>
 static hipError_t launch_march_c(const uint8_t *img, void *out, int height, int width, int n_frames,
-                                 const GaussTaps &taps, hipStream_t stream, int out_u8)
+                                 const GaussTaps &taps, hipStream_t stream, int out_u8, const GrayRule *rule = nullptr)
 {
     using K = MarchCfg<C>;
     if (width < 4) return hipErrorInvalidValue; // the border strips load whole dwords inside a row
@@ -983,6 +1090,12 @@ static hipError_t launch_march_c(const uint8_t *img, void *out, int height, int 
         }
     const bool table = g_gauss_march_variant == 0 || g_gauss_march_variant == 3;
     if (out_u8 && !(symmetric && table)) return hipErrorNotSupported;
+    if constexpr (CH > 1) {
+        if (!(out_u8 && symmetric && table && systolic && rule)) return hipErrorNotSupported;
+        hipLaunchKernelGGL((gauss_sym_color_kernel<C, CH>), dim3(blocks), dim3(256), 0, stream, img, (uint8_t *)out,
+                           height, width, n_strips, n_segs, seg, (int)waves, taps, use_fma, fma_c, *rule);
+        return hipGetLastError();
+    }
 #define CANNY_LAUNCH_SYM(LUT, U8, SYS)                                                                                  \
     hipLaunchKernelGGL((gauss_sym_kernel<C, LUT, U8, SYS>), dim3(blocks), dim3(256), 0, stream, img, out, height,     \
                        width, n_strips, n_segs, seg, (int)waves, taps, use_fma, fma_c)
@@ -1031,6 +1144,33 @@ hipError_t launch_gauss_march_part3(int center, const uint8_t *img, void *out, i
     }
 }
 #endif
+
+// ---- colour input (gauss_sym_color_kernel): part 4, or the single translation unit.  Half-windows 1..4 only (windows
+// 3..9): see gaussian_march_color_supported.
+#define CANNY_GAUSS_COLOR_CASE(C)                                                                                      \
+    case C:                                                                                                           \
+        return ch == 3 ? launch_march_c<C, 3>(src, out, height, width, n_frames, taps, stream, 1, &rule)              \
+                       : launch_march_c<C, 4>(src, out, height, width, n_frames, taps, stream, 1, &rule)
+#if CANNY_GAUSS_PART == 4 || CANNY_GAUSS_PART < 0
+hipError_t launch_gauss_color_part4(const uint8_t *src, int ch, const GrayRule &rule, uint8_t *out, int height,
+                                    int width, int n_frames, const GaussTaps &taps, hipStream_t stream)
+{
+    switch (taps.center) {
+#ifdef CANNY_GAUSS_ONLY_C
+#if CANNY_GAUSS_ONLY_C <= 4
+        CANNY_GAUSS_COLOR_CASE(CANNY_GAUSS_ONLY_C);
+#endif
+#else
+        CANNY_GAUSS_COLOR_CASE(1);
+        CANNY_GAUSS_COLOR_CASE(2);
+        CANNY_GAUSS_COLOR_CASE(3);
+        CANNY_GAUSS_COLOR_CASE(4);
+#endif
+    default: return hipErrorNotSupported;
+    }
+}
+#endif
+#undef CANNY_GAUSS_COLOR_CASE
 
 #if CANNY_GAUSS_HAS_HOST
 // (width >= 4: the border strips load whole dwords that must lie inside the row; narrower images take the generic path)
@@ -1081,6 +1221,25 @@ hipError_t launch_gaussian_march_u8(const uint8_t *img, uint8_t *out, int height
                                     const GaussTaps &taps, hipStream_t stream)
 {
     return launch_march_any(img, out, height, width, n_frames, taps, stream, 1);
+}
+
+// Colour input fuses into the default kernel (systolic row pass, table, u8 output) for windows 3..9 (half-windows
+// 1..4).  From window 11 on the gray kernel already uses every register its occupancy target allows (96 VGPRs at five
+// waves per SIMD for windows 11; 113 / 128 / 149 with SGPR spills from window 15 on), and the colour form -- one row
+// held as 3-4 registers, the rule's five SGPRs -- spills at the same target (VGPRs at windows 11 and 15, SGPRs at 13 and
+// 17; DESIGN.md, "Colour input").  Those windows convert first and run the gray kernel.
+// Rows wider than 2^29 pixels would overflow the kernel's 32-bit lane byte offsets.
+bool gaussian_march_color_supported(const GaussTaps &taps, int width, int ch)
+{
+    return (ch == 3 || ch == 4) && g_gauss_march_variant == 0 && taps.center >= 1 && taps.center <= 4 &&
+           gaussian_march_supported(taps.center, 0, width) && width <= (1 << 29) && gaussian_march_u8_supported(taps);
+}
+
+hipError_t launch_gaussian_march_u8_color(const uint8_t *src, int ch, const GrayRule &rule, uint8_t *out, int height,
+                                          int width, int n_frames, const GaussTaps &taps, hipStream_t stream)
+{
+    if (!gaussian_march_color_supported(taps, width, ch)) return hipErrorNotSupported;
+    return launch_gauss_color_part4(src, ch, rule, out, height, width, n_frames, taps, stream);
 }
 #endif // CANNY_GAUSS_HAS_HOST
 #undef CANNY_GAUSS_CASE

@@ -106,6 +106,47 @@ void gaussian_set_fma_div(bool on);
 void gaussian_set_march_variant(int v);
 void gaussian_set_seg_target(int rows); // A/B: approximate rows per wave segment, 0 = automatic
 
+// ---- colour frames -> gray (what the reference's caller does with cvtColor, src/main.cpp:114) ----------------
+// gray = (k0*c0 + k1*c1 + k2*c2 + rnd) >> shift for the first three bytes c0..c2 of an interleaved pixel (a fourth,
+// alpha, is ignored).  The host orders the weights by the layout (BGR: k0 = wb, RGB: k0 = wr), so rules and channel
+// orders are kernel arguments, not instantiations.  Every weight is < 2^16 and the sum < 2^24: 24-bit multiplies
+// are exact.
+struct GrayRule {
+    uint32_t k0, k1, k2, rnd, shift;
+};
+
+// The ONE conversion of the library: four interleaved pixels of CH (3 or 4) bytes, i.e. CH dwords, -> the packed
+// dword of their four gray bytes (pixel 0 in byte 0).  Both the standalone kernel and the fused Gaussian call it.
+template <int CH>
+__device__ __forceinline__ uint32_t gray4(const uint32_t *w, const GrayRule &r)
+{
+    static_assert(CH == 3 || CH == 4, "interleaved 3- or 4-byte pixels");
+    uint32_t out = 0u;
+#pragma unroll
+    for (int p = 0; p < 4; p++) {
+        uint32_t c[3];
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            const int i = CH * p + k; // byte i of the 4*CH
+            c[k] = (w[i >> 2] >> (8 * (i & 3))) & 0xffu;
+        }
+        const uint32_t g = __umul24(c[0], r.k0) + __umul24(c[1], r.k1) + __umul24(c[2], r.k2) + r.rnd;
+        out |= (g >> r.shift) << (8 * p);
+    }
+    return out;
+}
+
+// Standalone conversion of n_px interleaved pixels (the batch as one flat array; any source alignment) into
+// n_px gray bytes.
+hipError_t launch_to_gray(const uint8_t *src, int ch, const GrayRule &rule, uint8_t *gray, size_t n_px,
+                          hipStream_t stream);
+
+// The marching Gaussian (symmetric taps, systolic row pass with the product table, u8 output) reading interleaved
+// CH-byte pixels and converting them as it loads its rows.  Windows listed by gaussian_march_color_supported only.
+bool gaussian_march_color_supported(const GaussTaps &taps, int width, int ch);
+hipError_t launch_gaussian_march_u8_color(const uint8_t *src, int ch, const GrayRule &rule, uint8_t *out, int height,
+                                          int width, int n_frames, const GaussTaps &taps, hipStream_t stream);
+
 // ---- Sobel / NMS (src/utils.cpp:106-308) ----------------------------------------------------
 hipError_t launch_xy_gradient(const int16_t *img, int16_t *gx, int16_t *gy, int height, int width, int n_frames,
                               hipStream_t stream);

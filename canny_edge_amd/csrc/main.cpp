@@ -1,5 +1,5 @@
 // main.cpp -- the reference's command line (StevenChang5/Canny_Edge src/main.cpp:18-142) without
-// the webcam and the GUI:  ./Main sigma minVal maxVal [-c] [-s] [-i in.pgm|in.jpg] [-o dir] [-p] [-n WxH] [-b dir]
+// the webcam and the GUI:  ./Main sigma minVal maxVal [-c] [-s] [-i in.pgm|in.ppm|in.jpg] [-o dir] [-p] [-n WxH] [-b dir]
 //
 // Kept from the reference: the three positionals may appear anywhere relative to the flags
 // (src/main.cpp:29-46); exactly three are required, otherwise the usage text is printed and the
@@ -8,7 +8,9 @@
 // entry point (cuda_canny) instead of canny().  In this build both run on the MI355X.
 // Replaced: VideoCapture(0) 640x480 (:78-115) -> a binary PGM or a baseline JPEG given with -i (the JPEG is read as
 // cv::imread(..., IMREAD_GRAYSCALE) reads it, include/canny_frames.h), or a synthetic frame of the webcam's size
-// (-n overrides the size); imshow -> PGM (or, with -p, PNG) files in the -o directory.
+// (-n overrides the size); imshow -> PGM (or, with -p, PNG) files in the -o directory.  A binary PPM (P6, maxval 255,
+// RGB) is a colour frame: it is converted on the GPU with canny_hip_to_gray and the OpenCV rule, in place of the
+// reference's cvtColor(frame, gray_frame, COLOR_BGR2GRAY) (:114); -s also writes that plane as canny_step0_gray.pgm.
 #include <algorithm>
 #include <cctype>
 #include <chrono>
@@ -30,13 +32,14 @@
 
 using namespace std;
 
-static bool read_pgm(const string &path, vector<unsigned char> &px, int &height, int &width)
+// Binary PGM (P5) -> gray bytes, or with `channels` = 3 binary PPM (P6) -> interleaved R,G,B bytes.
+static bool read_pgm(const string &path, vector<unsigned char> &px, int &height, int &width, int channels = 1)
 {
     ifstream f(path, ios::binary);
     if (!f) return false;
     string magic;
     f >> magic;
-    if (magic != "P5") return false;
+    if (magic != (channels == 3 ? "P6" : "P5")) return false;
     auto next_int = [&](int &v) {
         f >> ws;
         while (f.peek() == '#') {
@@ -49,8 +52,10 @@ static bool read_pgm(const string &path, vector<unsigned char> &px, int &height,
     int maxv = 0;
     if (!next_int(width) || !next_int(height) || !next_int(maxv)) return false;
     if (width < 1 || height < 1 || maxv < 1 || maxv > 255) return false;
+    if (channels == 3 && maxv != 255) return false;
+    if ((long long)width * height > 0x7fffffffLL) return false;
     f.get(); // single whitespace after maxval
-    px.resize((size_t)width * height);
+    px.resize((size_t)width * height * channels);
     f.read((char *)px.data(), (streamsize)px.size());
     return (size_t)f.gcount() == px.size();
 }
@@ -77,8 +82,29 @@ static bool read_frame(const string &path, vector<unsigned char> &px, int &heigh
         if (st) cout << "ERROR: " << path << ": " << canny_frames_last_error() << endl;
         return st == 0;
     }
+    if (f.gcount() == 2 && magic[0] == 'P' && magic[1] == '6') { // colour: to gray on the GPU, OpenCV's rule
+        f.close();
+        vector<unsigned char> rgb;
+        if (!read_pgm(path, rgb, height, width, 3)) return false;
+        px.resize((size_t)width * height);
+        canny_hip_ctx *ctx = nullptr;
+        int st = canny_hip_ctx_create(&ctx, 0);
+        if (!st) st = canny_hip_to_gray(ctx, rgb.data(), CANNY_HIP_RGB8, height, width, px.data());
+        if (st) cout << "ERROR: " << path << ": " << (ctx ? canny_hip_last_error(ctx) : canny_hip_status_string(st)) << endl;
+        if (ctx) canny_hip_ctx_destroy(ctx);
+        return st == 0;
+    }
     f.close();
     return read_pgm(path, px, height, width);
+}
+
+static bool is_ppm(const string &path)
+{
+    if (path.empty()) return false;
+    ifstream f(path, ios::binary);
+    char magic[2] = {0, 0};
+    f.read(magic, 2);
+    return f.gcount() == 2 && magic[0] == 'P' && magic[1] == '6';
 }
 
 static bool is_frame_file(const std::filesystem::path &p)
@@ -222,7 +248,7 @@ int main(int argc, char *argv[])
         fprintf(stderr, "   maxVal: The maximum threshold value used for hysteresis\n");
         fprintf(stderr, "           Must be in the range of [0,255]\n");
         fprintf(stderr, "   -c: use the GPU entry point (cuda_canny)   -s: write every step\n");
-        fprintf(stderr, "   -i frame: input frame (binary PGM or baseline JPEG)   -n WxH: synthetic frame size   -o dir: output dir\n");
+        fprintf(stderr, "   -i frame: input frame (binary PGM, binary PPM or baseline JPEG)   -n WxH: synthetic frame size   -o dir: output dir\n");
         fprintf(stderr, "   -p: write PNG files instead of PGM\n");
         fprintf(stderr, "   -b dir: run every .pgm / .jpg of dir as one batch, write <name>_edges.pgm\n");
         exit(0);
@@ -263,6 +289,11 @@ int main(int argc, char *argv[])
     }
     if (!outdir.empty()) setenv("CANNY_OUTPUT_DIR", outdir.c_str(), 1);
     if (png_output) setenv("CANNY_OUTPUT_FORMAT", "png", 1);
+    if (show_steps && is_ppm(input)) { // the converted plane, the step the reference's cvtColor did
+        const string path = (outdir.empty() ? string(".") : outdir) + "/canny_step0_gray" + (png_output ? ".png" : ".pgm");
+        if (canny_frames_write_gray(path.c_str(), frame.data(), height, width))
+            cerr << "WARNING: cannot write " << path << "\n";
+    }
 
     try {
         if (use_gpu_entry)

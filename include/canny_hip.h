@@ -52,7 +52,8 @@
 extern "C" {
 #endif
 
-#define CANNY_HIP_VERSION 200        /* 0.2.0: + batch u8 / bit maps, multi-GPU options, host_register, async dev_canny */
+#define CANNY_HIP_VERSION 300        /* 0.3.0: + colour frame input (BGR / RGB / BGRA / RGBA -> gray on the GPU) */
+/* 0.2.0: + batch u8 / bit maps, multi-GPU options, host_register, async dev_canny */
 #define CANNY_HIP_MAX_WINDOW 129     /* largest Gaussian window (sigma <= 21.33) */
 
 typedef struct canny_hip_ctx canny_hip_ctx;
@@ -77,7 +78,18 @@ enum canny_hip_stage {
     CANNY_HIP_STAGE_SOBEL = 5,
     CANNY_HIP_STAGE_NMS = 6,
     CANNY_HIP_STAGE_XY_GRADIENT = 7,
-    CANNY_HIP_STAGE_COUNT = 8
+    CANNY_HIP_STAGE_TO_GRAY = 8,        /* the standalone colour -> gray pass (the fused one is timed as GAUSSIAN) */
+    CANNY_HIP_STAGE_COUNT = 9
+};
+
+/* Pixel layouts of the colour entry points (canny_hip_*_color, canny_hip_*to_gray): dense, interleaved, no row
+ * padding -- channel k of pixel (r,c) of frame f at byte ((f*H + r)*W + c)*CH + k. */
+enum canny_hip_layout {
+    CANNY_HIP_GRAY8 = 0,  /* 1 byte: what every other entry point takes (identity) */
+    CANNY_HIP_BGR8 = 1,   /* cv::Mat CV_8UC3 as VideoCapture / imread return it */
+    CANNY_HIP_RGB8 = 2,   /* PPM, PIL, numpy */
+    CANNY_HIP_BGRA8 = 3,  /* alpha ignored */
+    CANNY_HIP_RGBA8 = 4
 };
 
 /* ---- library / context ------------------------------------------------------------------- */
@@ -145,9 +157,17 @@ int canny_hip_ctx_device(const canny_hip_ctx *ctx);
  *   "profile_stage_mask": bit s set = stage s (CANNY_HIP_STAGE_*) gets an event pair while profiling is enabled;
  *                    0 (default) = all stages.  Every pair costs a few microseconds of stream time, so a timed
  *                    region that needs one kernel's duration enables that stage only.
- *   "profile_sample_interval": N >= 1 (default 1): only every N-th launch group of a stage gets its event pair */
+ *   "profile_sample_interval": N >= 1 (default 1): only every N-th launch group of a stage gets its event pair
+ *   "gray_rule": colour input -> gray, gray = (wb*B + wg*G + wr*R + 2^(s-1)) >> s with
+ *                    0 (default) OpenCV cvtColor(*2GRAY) on CV_8U: (1868 B + 9617 G + 4899 R + 8192) >> 14,
+ *                    1 PIL Image.convert('L'):                    (7471 B + 38470 G + 19595 R + 32768) >> 16
+ *                    (the two differ on 39,135 of the 2^24 (R,G,B) triples)
+ *   "fuse_gray": 1 (default) / 0 -- colour canny(): the marching Gaussian of the u8 smoothed path converts the colour rows
+ *                    as it loads them (windows 3..9, width >= 4, default kernel variant); 0 = a standalone conversion
+ *                    pass always runs first (A/B, tests).  Same results bit for bit */
 int canny_hip_ctx_set_option(canny_hip_ctx *ctx, const char *name, int value);
-/* Reads back "smoothed_u8", "fuse_classify", "hysteresis_tail", "gaussian_path", "sobel_nms_path", "tune_batch_compact",
+/* Reads back "gray_rule", "fuse_gray", the read-only "last_canny_fused_gray" (1 if the context's last colour canny call
+ * really ran the fused Gaussian), "smoothed_u8", "fuse_classify", "hysteresis_tail", "gaussian_path", "sobel_nms_path", "tune_batch_compact",
  * the read-only "batch_expand_threads" (threads of the expansion pool once a batch call has created it) and the read-only
  * "last_canny_smoothed_u8": 1 if the context's last canny call really ran on the u8 smoothed plane (the option is a
  * request: windows beyond 17, asymmetric taps and shapes the fused kernel does not take fall back to the s16 plane).
@@ -242,6 +262,49 @@ int canny_hip_multi_gpu_release(void);
 int canny_hip_device_local_cpus(int device, char *buf, int cap);
 /* Frame range [begin, end) of shard `rank` of `world` (what canny_hip_canny_multi_gpu and bench.py use). */
 int canny_hip_shard_range(int n_frames, int rank, int world, int *begin, int *end);
+
+/* ---- colour frame input (the reference's caller converts with cvtColor(frame, gray, COLOR_BGR2GRAY) before canny(),
+ * src/main.cpp:113-114) -------------------------------------------------------------------------------------------
+ * `layout` is an enum canny_hip_layout value, anything else is CANNY_HIP_ERR_INVALID; the rule is the context's "gray_rule".
+ * Every _color call returns the same status and the same map as the gray entry point it mirrors would return on the
+ * converted plane; CANNY_HIP_GRAY8 is accepted everywhere and is the identity.
+ * Not (yet) covered -- follow-ups: the multi-GPU sharder, canny_hip_dev_canny_stream, device-side _u8 / _bits
+ * variants, and converting pageable colour input on the host pool while it is staged (1 byte per pixel up instead
+ * of 3). */
+/* One frame, host buffers, synchronous: `gray` receives height*width bytes. */
+int canny_hip_to_gray(canny_hip_ctx *ctx, const unsigned char *src, int layout, int height, int width,
+                      unsigned char *gray);
+/* canny_hip_canny on a colour frame (frames of 1 MP and more go through the batch pipeline as a batch of one). */
+int canny_hip_canny_color(canny_hip_ctx *ctx, const unsigned char *src, int layout, float sigma, int min_val,
+                          int max_val, int height, int width, short *edges);
+/* canny_hip_canny_batch / _u8 / _bits on colour frames: chunks, pinned staging and uploads are sized in input bytes
+ * (a chunk of colour frames holds fewer frames).  Pinned / registered input is DMA'd in place. */
+int canny_hip_canny_batch_color(canny_hip_ctx *ctx, const unsigned char *srcs, int layout, int n_frames, float sigma,
+                                int min_val, int max_val, int height, int width, short *edges);
+int canny_hip_canny_batch_color_u8(canny_hip_ctx *ctx, const unsigned char *srcs, int layout, int n_frames, float sigma,
+                                   int min_val, int max_val, int height, int width, unsigned char *edges);
+int canny_hip_canny_batch_color_bits(canny_hip_ctx *ctx, const unsigned char *srcs, int layout, int n_frames,
+                                     float sigma, int min_val, int max_val, int height, int width, unsigned char *bits);
+/* Device buffers, asynchronous: n_frames colour frames -> n_frames gray planes (the standalone pass; d_src may have
+ * any byte alignment). */
+int canny_hip_dev_to_gray(canny_hip_ctx *ctx, const unsigned char *d_src, int layout, int height, int width,
+                          int n_frames, unsigned char *d_gray);
+/* The fused kernel alone: canny_hip_dev_gaussian_u8 of the converted plane, converted as the rows are loaded.
+ * CANNY_HIP_ERR_UNSUPPORTED where it does not apply (where canny_hip_dev_gaussian_u8 does not, windows beyond 9, A/B
+ * variants). */
+int canny_hip_dev_gaussian_u8_color(canny_hip_ctx *ctx, const unsigned char *d_src, int layout, float sigma, int height,
+                                    int width, int n_frames, unsigned char *d_result);
+/* canny_hip_dev_canny on colour frames.
+ * COMPLETION CONTRACT: d_edges is complete IN STREAM ORDER on the context's stream when the call has returned (work
+ * queued on that stream afterwards sees the final map) and HOST-VISIBLE after canny_hip_synchronize() -- whatever path
+ * ran.  Whether the call itself blocks the host depends on the shape: frames of <= 4096 hysteresis tiles (64x64 px)
+ * with width % 8 == 0, min_val >= 1 and the option hysteresis_tail = 1 (default) only QUEUE their five kernels and
+ * return; every other shape polls the propagation's convergence flag and returns when it has converged.  The context's
+ * stream is non-blocking with respect to the legacy default stream: a hipMemcpy on the default stream does NOT wait for
+ * it -- copy with canny_hip_memcpy_d2h (same stream), or synchronize first.  (A colour call that converts first queues
+ * one kernel more.)  d_src may be reused once the context's stream has passed the call. */
+int canny_hip_dev_canny_color(canny_hip_ctx *ctx, const unsigned char *d_src, int layout, float sigma, int min_val,
+                              int max_val, int height, int width, int n_frames, short *d_edges);
 
 /* ---- stage entry points on DEVICE buffers (asynchronous on the context's stream) ----------- */
 /* All planes hold n_frames contiguous frames.  Workspace is owned and grown by the context. */
