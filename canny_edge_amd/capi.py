@@ -54,6 +54,17 @@ def layout_of(shape, order: str = "bgr", batch: bool = False) -> int:
     raise ValueError(f"expected {'(N, ' if batch else '('}H, W) or {'(N, ' if batch else '('}H, W, 3|4) frames, "
                      f"got shape {shape}")
 
+# automatic per-frame threshold rules (enum canny_hip_auto_rule)
+AUTO_MEDIAN, AUTO_QUANTILE = 1, 2
+_AUTO_RULES = {"median": AUTO_MEDIAN, "quantile": AUTO_QUANTILE, AUTO_MEDIAN: AUTO_MEDIAN, AUTO_QUANTILE: AUTO_QUANTILE}
+
+
+def _rule(rule) -> int:
+    if rule not in _AUTO_RULES:
+        raise ValueError(f"rule must be 'median', 'quantile', AUTO_MEDIAN or AUTO_QUANTILE, not {rule!r}")
+    return _AUTO_RULES[rule]
+
+
 # every symbol include/canny_hip.h declares (checked by tests/test_abi.py)
 EXPORTS = (
     "canny_hip_version", "canny_hip_status_string", "canny_hip_device_count", "canny_hip_ctx_create",
@@ -73,7 +84,8 @@ EXPORTS = (
     "canny_hip_probe_copy", "canny_hip_ctx_get_option", "canny_hip_selftest_expand_bits",
     "canny_hip_selftest_march_order", "canny_hip_to_gray", "canny_hip_dev_to_gray", "canny_hip_dev_gaussian_u8_color",
     "canny_hip_dev_canny_color", "canny_hip_canny_color", "canny_hip_canny_batch_color", "canny_hip_canny_batch_color_u8",
-    "canny_hip_canny_batch_color_bits",
+    "canny_hip_canny_batch_color_bits", "canny_hip_auto_thresholds_from_histogram", "canny_hip_dev_canny_thresholds",
+    "canny_hip_dev_canny_auto", "canny_hip_canny_batch_thresholds", "canny_hip_canny_batch_auto",
 )
 
 _lib: Optional[C.CDLL] = None
@@ -173,6 +185,11 @@ def load() -> C.CDLL:
         "canny_hip_canny_batch_color": ([p, p, i, i, f, i, i, i, i, p], i),
         "canny_hip_canny_batch_color_u8": ([p, p, i, i, f, i, i, i, i, p], i),
         "canny_hip_canny_batch_color_bits": ([p, p, i, i, f, i, i, i, i, p], i),
+        "canny_hip_auto_thresholds_from_histogram": ([p, i, f, f, ip, ip], i),
+        "canny_hip_dev_canny_thresholds": ([p, p, f, p, i, i, i, p], i),
+        "canny_hip_dev_canny_auto": ([p, p, f, i, f, f, i, i, i, p, p], i),
+        "canny_hip_canny_batch_thresholds": ([p, p, i, f, p, i, i, p], i),
+        "canny_hip_canny_batch_auto": ([p, p, i, f, i, f, f, i, i, p, p], i),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -204,6 +221,20 @@ def expand_bits(bits: np.ndarray, height: int, width: int, u8: bool = False, thr
     if st:
         raise CannyHipError(st, "selftest_expand_bits")
     return out
+
+
+def auto_thresholds_from_histogram(hist, rule="median", low: float = 0.67, high: float = 1.33) -> Tuple[int, int]:
+    """Host-only: the automatic rule (AUTO_MEDIAN / AUTO_QUANTILE, or "median" / "quantile") on one 257-bin histogram
+    -> (min_val, max_val), exactly as the GPU selects it per frame."""
+    h = np.ascontiguousarray(hist, dtype=np.uint32)
+    if h.shape != (257,):
+        raise ValueError(f"expected 257 bins, got shape {h.shape}")
+    lo, hi = C.c_int(0), C.c_int(0)
+    st = load().canny_hip_auto_thresholds_from_histogram(_hp(h), int(rule) if isinstance(rule, (int, np.integer))
+                                                         else _rule(rule), low, high, C.byref(lo), C.byref(hi))
+    if st:
+        raise CannyHipError(st, "auto_thresholds_from_histogram")
+    return lo.value, hi.value
 
 
 def march_order(n_segs: int, n_strips: int) -> np.ndarray:
@@ -428,6 +459,54 @@ class Context:
         self._check(fn(self._h, _hp(a), a.shape[0], sigma, min_val, max_val, a.shape[1], a.shape[2], _hp(out)),
                     "canny_batch")
         return out
+
+    # ---- per-frame thresholds (explicit, or chosen on the GPU: DESIGN.md section 11) ------------------------------
+    def canny_thresholds(self, imgs, sigma: float, thresholds, out: Optional[np.ndarray] = None) -> np.ndarray:
+        """canny() with a pair per frame: imgs (H, W) or (N, H, W) uint8, thresholds (N, 2) -- or (2,) for one frame --
+        with 1 <= min_val <= max_val <= 255 (else CANNY_HIP_ERR_INVALID and nothing is written).  Returns int16 maps
+        shaped like imgs."""
+        a = np.ascontiguousarray(imgs, dtype=np.uint8)
+        single = a.ndim == 2
+        if single:
+            a = a[None]
+        if a.ndim != 3:
+            raise ValueError("expected uint8 [H, W] or [n_frames, H, W]")
+        t = np.ascontiguousarray(thresholds, dtype=np.int32).reshape(-1)
+        if t.size != 2 * a.shape[0]:
+            raise ValueError(f"expected {a.shape[0]} (min_val, max_val) pairs, got {t.size} values")
+        if out is None:
+            out = np.empty(a.shape, np.int16)
+        self._check(self._L.canny_hip_canny_batch_thresholds(self._h, _hp(a), a.shape[0], sigma, _hp(t), a.shape[1],
+                                                             a.shape[2], _hp(out)), "canny_thresholds")
+        return out[0] if single else out
+
+    def canny_auto(self, imgs, sigma: float, rule="median", low: float = 0.67, high: float = 1.33):
+        """canny() with thresholds chosen per frame on the GPU: rule "median" (auto_canny: low / high times the median
+        of the smoothed frame) or "quantile" (low / high quantiles of the gradient magnitude).  imgs (H, W) or
+        (N, H, W) uint8.  Returns (edges int16 shaped like imgs, thresholds int32 [N, 2] -- [2] for one frame)."""
+        a = np.ascontiguousarray(imgs, dtype=np.uint8)
+        single = a.ndim == 2
+        if single:
+            a = a[None]
+        if a.ndim != 3:
+            raise ValueError("expected uint8 [H, W] or [n_frames, H, W]")
+        out = np.empty(a.shape, np.int16)
+        thr = np.empty((a.shape[0], 2), np.int32)
+        self._check(self._L.canny_hip_canny_batch_auto(self._h, _hp(a), a.shape[0], sigma, _rule(rule), low, high,
+                                                       a.shape[1], a.shape[2], _hp(out), _hp(thr)), "canny_auto")
+        return (out[0], thr[0]) if single else (out, thr)
+
+    def dev_canny_thresholds(self, d_img: int, sigma: float, d_thresholds: int, h: int, w: int, n: int, d_edges: int):
+        """dev_canny with per-frame pairs from a device array of 2 * n int32 (clamped into the domain)."""
+        self._check(self._L.canny_hip_dev_canny_thresholds(self._h, C.c_void_p(d_img), sigma, C.c_void_p(d_thresholds),
+                                                           h, w, n, C.c_void_p(d_edges)), "dev_canny_thresholds")
+
+    def dev_canny_auto(self, d_img: int, sigma: float, rule, low: float, high: float, h: int, w: int, n: int,
+                       d_edges: int, d_thresholds: int = 0):
+        """dev_canny with pairs chosen per frame on the GPU; d_thresholds (2 * n int32, device) receives them if set."""
+        self._check(self._L.canny_hip_dev_canny_auto(self._h, C.c_void_p(d_img), sigma, _rule(rule), low, high, h, w,
+                                                     n, C.c_void_p(d_edges), C.c_void_p(d_thresholds or None)),
+                    "dev_canny_auto")
 
     # ---- colour frames (interleaved BGR / RGB / BGRA / RGBA; the rule is the "gray_rule" option) --------------
     def to_gray(self, frame, order: str = "bgr") -> np.ndarray:
@@ -669,3 +748,8 @@ def canny(img, sigma: float, minVal: int, maxVal: int) -> np.ndarray:
 def canny_color(frame, sigma: float, minVal: int, maxVal: int, order: str = "bgr") -> np.ndarray:
     """canny() of an (H, W, 3|4) colour frame -- the reference's cvtColor + canny() (src/main.cpp:114-136)."""
     return default_context().canny_color(frame, sigma, minVal, maxVal, order)
+
+
+def canny_auto(img, sigma: float, rule="median", low: float = 0.67, high: float = 1.33):
+    """canny() with per-frame thresholds chosen on the GPU (see Context.canny_auto): returns (edges, thresholds)."""
+    return default_context().canny_auto(img, sigma, rule, low, high)

@@ -371,6 +371,8 @@ struct canny_hip_ctx {
     DevBuf smoothed;  // pipeline: Gaussian output
     DevBuf edges16;   // canny_hip_dev_canny_u8: the s16 edge map before narrowing
     DevBuf gray;      // colour input: the converted plane when the Gaussian cannot convert itself
+    DevBuf hist;      // automatic thresholds: per-frame histograms (n_frames x 257 u32)
+    DevBuf thr;       // automatic thresholds: the pairs when the caller does not ask for them
     DevBuf plane_s, plane_c, stamps, flags; // hysteresis bit-planes / scheduling words
     DevBuf io[4];     // staging for the host-pointer stage functions
     unsigned *host_flags = nullptr;     // pinned + mapped, 4 words per lane: last_change, domain, sequence number, spare
@@ -418,6 +420,8 @@ struct canny_hip_ctx::BatchPipe {
     struct Slot {
         DevBuf d_in, d_out, d_out8;
         PinBuf pin_in, pin_out;
+        DevBuf d_thr;   // per-frame thresholds of the chunk (canny_hip_canny_batch_thresholds / _auto)
+        PinBuf pin_thr; // ... staged: the chunk's explicit pairs on the way up, the selected pairs on the way down
         hipEvent_t ev_h2d = nullptr, ev_comp = nullptr, ev_d2h = nullptr;
         bool d2h_issued = false;      // ev_d2h has been recorded during the current call
         void *retire_dst = nullptr;   // pageable output: where pin_out goes once ev_d2h has fired
@@ -768,8 +772,30 @@ int propagate_and_finalize(canny_hip_ctx *ctx, const HystGeom &g, short *d_out, 
 
 int finish_pending(canny_hip_ctx *ctx);
 
-int dev_hysteresis(canny_hip_ctx *ctx, short *d_cand, int h, int w, int n, int lo, int hi)
+// Per-frame thresholds of a dev_canny call (canny_hip_*_thresholds / _auto).  No spec = the call's (lo, hi) pair.
+//   pairs:  device array of 2 * n ints, frame f's pair at [2f], [2f+1] (clamped into [1,255] by the kernels), or
+//   rule:   an automatic rule (kAutoMedian / kAutoQuantile) with its parameters; the pairs it selects are written to
+//           `out` (device, 2 * n ints), or to a context workspace if out is null.
+struct ThrSpec {
+    const int *pairs = nullptr;
+    int rule = 0;
+    double low = 0.0, high = 0.0;
+    int *out = nullptr;
+};
+
+// Parameters of an automatic rule (section 1 of DESIGN.md section 11); finite values only.
+bool auto_params_valid(int rule, float low, float high)
 {
+    if (!std::isfinite(low) || !std::isfinite(high)) return false;
+    if (rule == kAutoMedian) return 0.0f <= low && low <= high;
+    if (rule == kAutoQuantile) return 0.0f < low && low <= high && high <= 1.0f;
+    return false;
+}
+
+// pairs != nullptr: per-frame thresholds, lo / hi ignored
+int dev_hysteresis(canny_hip_ctx *ctx, short *d_cand, int h, int w, int n, int lo, int hi, const int *pairs = nullptr)
+{
+    if (pairs) lo = hi = 255; // (a clamped pair is in the domain: promoted pixels are 255)
     if (hysteresis_order_dependent(lo, hi)) return CANNY_HIP_ERR_DOMAIN;
     HystGeom g = make_hyst_geom(h, w, n);
     int rc = finish_pending(ctx); // a streamed call's sweeps own the planes until they are done
@@ -778,7 +804,7 @@ int dev_hysteresis(canny_hip_ctx *ctx, short *d_cand, int h, int w, int n, int l
     {
         StageTimer tm(ctx, CANNY_HIP_STAGE_HYST_CLASSIFY);
         HIP_TRY(ctx, launch_hyst_classify(d_cand, (uint64_t *)ctx->plane_s.p, (uint64_t *)ctx->plane_c.p, g, lo, hi,
-                                          (unsigned *)ctx->flags.p + 1, ctx->stream));
+                                          (unsigned *)ctx->flags.p + 1, ctx->stream, pairs));
     }
     return propagate_and_finalize(ctx, g, d_cand, hi);
 }
@@ -798,10 +824,13 @@ int dev_sobel_nms(canny_hip_ctx *ctx, const short *d_smoothed, int h, int w, int
 }
 
 // color: interleaved colour input (canny_hip_*_color); null = the gray plane of every other entry point
+// thr: per-frame thresholds (ThrSpec); null = (lo, hi) for every frame
 int dev_canny(canny_hip_ctx *ctx, const unsigned char *d_img, float sigma, int lo, int hi, int h, int w, int n,
-              short *d_edges, const ColorIn *color = nullptr)
+              short *d_edges, const ColorIn *color = nullptr, const ThrSpec *thr = nullptr)
 {
     if (h < 2 || w < 2) return CANNY_HIP_ERR_UNSUPPORTED;
+    // per-frame pairs are clamped into [1,255]: the fused kernel takes every frame, promoted pixels are 255
+    if (thr) lo = hi = 255;
     if (hysteresis_order_dependent(lo, hi)) return CANNY_HIP_ERR_DOMAIN;
     int rc = finish_pending(ctx);
     if (rc) return rc;
@@ -835,13 +864,31 @@ int dev_canny(canny_hip_ctx *ctx, const unsigned char *d_img, float sigma, int l
         if (color) ctx->last_fused_gray = 0;
         if ((rc = dev_gaussian(ctx, d_img, sigma, h, w, n, sm, sm_u8))) return rc;
     }
+    // per-frame thresholds: an automatic rule measures every frame's smoothed plane (median) or its gradient
+    // magnitudes (quantile) and selects the pairs on the device; nothing comes back to the host
+    const int *pairs = thr ? thr->pairs : nullptr;
+    if (thr && thr->rule) {
+        int *out = thr->out;
+        if (!out) {
+            HIP_TRY(ctx, ctx->thr.ensure((size_t)n * 2 * sizeof(int)));
+            out = (int *)ctx->thr.p;
+        }
+        HIP_TRY(ctx, ctx->hist.ensure((size_t)n * kHistBins * sizeof(uint32_t)));
+        uint32_t *hist = (uint32_t *)ctx->hist.p;
+        StageTimer tm(ctx, CANNY_HIP_STAGE_HYST_CLASSIFY); // (no stage of its own: the thresholds are classify's input)
+        HIP_TRY(ctx, hipMemsetAsync(hist, 0, (size_t)n * kHistBins * sizeof(uint32_t), ctx->stream));
+        HIP_TRY(ctx, thr->rule == kAutoMedian ? launch_hist_intensity(sm, sm_u8 != 0, hist, h, w, n, ctx->stream)
+                                              : launch_hist_gradient(sm, sm_u8 != 0, hist, h, w, n, ctx->stream));
+        HIP_TRY(ctx, launch_thr_select(hist, n, thr->rule, thr->low, thr->high, out, ctx->stream));
+        pairs = out;
+    }
     // Sobel+NMS+classify on the s16 or the u8 smoothed plane
     auto fused_sobel = [&](const short *smp, short *edges, uint64_t *S, uint64_t *C, const HystGeom &gg, int ev,
-                           const LaunchEvents &le) -> hipError_t {
+                           const LaunchEvents &le, const int *pp) -> hipError_t {
         return sm_u8 ? launch_sobel_nms_classify_march_u8in((const uint8_t *)smp, edges, S, C, gg, lo, hi, ev,
-                                                            ctx->stream, ctx->tune_sobel_seg, le)
+                                                            ctx->stream, ctx->tune_sobel_seg, le, pp)
                      : launch_sobel_nms_classify_march(smp, edges, S, C, gg, lo, hi, ev, ctx->stream,
-                                                       ctx->tune_sobel_seg, le);
+                                                       ctx->tune_sobel_seg, le, pp);
     };
     if (fused) {
         // Sobel+NMS writes the hysteresis bit-planes directly: the suppressed magnitudes never reach memory
@@ -872,7 +919,7 @@ int dev_canny(canny_hip_ctx *ctx, const unsigned char *d_img, float sigma, int l
             B.host_dev += 4;
             {
                 StageTimer tm(ctx, CANNY_HIP_STAGE_SOBEL_NMS, nullptr, /*attached=*/true);
-                HIP_TRY(ctx, fused_sobel(sm, d_edges, A.S, (uint64_t *)A.C, gA, edge_value, tm.launch_events()));
+                HIP_TRY(ctx, fused_sobel(sm, d_edges, A.S, (uint64_t *)A.C, gA, edge_value, tm.launch_events(), pairs));
             }
             HIP_TRY(ctx, hipEventRecord(ctx->fork_event, ctx->stream));
             HIP_TRY(ctx, hipStreamWaitEvent(ctx->aux_stream, ctx->fork_event, 0));
@@ -881,7 +928,8 @@ int dev_canny(canny_hip_ctx *ctx, const unsigned char *d_img, float sigma, int l
             {
                 StageTimer tm(ctx, CANNY_HIP_STAGE_SOBEL_NMS, nullptr, /*attached=*/true);
                 const short *smB = sm_u8 ? (const short *)((const uint8_t *)sm + px_a) : sm + px_a;
-                HIP_TRY(ctx, fused_sobel(smB, d_edges + px_a, B.S, (uint64_t *)B.C, gB, edge_value, tm.launch_events()));
+                HIP_TRY(ctx, fused_sobel(smB, d_edges + px_a, B.S, (uint64_t *)B.C, gB, edge_value, tm.launch_events(),
+                                         pairs ? pairs + 2 * (size_t)nA : nullptr));
             }
             if ((rc = lane_launch_chunk(ctx, B))) return rc;
             for (PropLane *L : {&A, &B}) {
@@ -897,7 +945,7 @@ int dev_canny(canny_hip_ctx *ctx, const unsigned char *d_img, float sigma, int l
         if ((rc = prepare_hyst(ctx, g, /*zero_pad=*/true))) return rc; // the kernel below writes in-image bytes only
         {
             StageTimer tm(ctx, CANNY_HIP_STAGE_SOBEL_NMS, nullptr, /*attached=*/true);
-            HIP_TRY(ctx, fused_sobel(sm, d_edges, S, C, g, edge_value, tm.launch_events()));
+            HIP_TRY(ctx, fused_sobel(sm, d_edges, S, C, g, edge_value, tm.launch_events(), pairs));
         }
         // d_edges now holds the strong pixels; the sweeps add every pixel they promote: no finalize pass
         if (ctx->hyst_tail && g.tiles_x * g.tiles_y <= kTailMaxTiles) {
@@ -917,7 +965,7 @@ int dev_canny(canny_hip_ctx *ctx, const unsigned char *d_img, float sigma, int l
         return run_propagation(ctx, g, /*speculative=*/false, []() -> int { return CANNY_HIP_OK; }, d_edges, edge_value);
     }
     if ((rc = dev_sobel_nms(ctx, sm, h, w, n, d_edges))) return rc;
-    return dev_hysteresis(ctx, d_edges, h, w, n, lo, hi);
+    return dev_hysteresis(ctx, d_edges, h, w, n, lo, hi, pairs);
 }
 
 // Completes the propagation canny_hip_dev_canny_stream left in flight and joins it into the context's stream.
@@ -1026,6 +1074,8 @@ void destroy_batch_pipe(canny_hip_ctx::BatchPipe *w)
         sl.d_out8.release();
         sl.pin_in.release();
         sl.pin_out.release();
+        sl.d_thr.release();
+        sl.pin_thr.release();
         for (hipEvent_t e : {sl.ev_h2d, sl.ev_comp, sl.ev_d2h})
             if (e) (void)hipEventDestroy(e);
     }
@@ -1146,6 +1196,8 @@ void canny_hip_ctx_destroy(canny_hip_ctx *ctx)
     ctx->plane_s.release();
     ctx->plane_c.release();
     ctx->edges16.release();
+    ctx->hist.release();
+    ctx->thr.release();
     ctx->stamps.release();
     ctx->flags.release();
     for (auto &b : ctx->io) b.release();
@@ -1465,9 +1517,17 @@ int canny_hip_find_edge_pixels(canny_hip_ctx *ctx, short *edge_candidates, unsig
 }
 
 enum MapFormat { kMapS16 = 0, kMapU8 = 1, kMapBits = 2 };
+// Per-frame thresholds of a batch call, on HOST memory: explicit pairs (2 * n_frames ints, already validated), or an
+// automatic rule whose selected pairs go to `out` (2 * n_frames ints, or null).
+struct BatchThr {
+    const int *pairs = nullptr;
+    int rule = 0;
+    double low = 0.0, high = 0.0;
+    int *out = nullptr;
+};
 static int canny_batch_impl(canny_hip_ctx *ctx, const unsigned char *imgs, int n_frames, float sigma, int min_val,
                             int max_val, int height, int width, void *edges, MapFormat fmt,
-                            const ColorIn *color = nullptr);
+                            const ColorIn *color = nullptr, const BatchThr *bthr = nullptr);
 
 int canny_hip_canny(canny_hip_ctx *ctx, const unsigned char *img, float sigma, int min_val, int max_val, int height,
                     int width, short *edges)
@@ -1522,8 +1582,11 @@ static size_t map_frame_bytes(MapFormat fmt, int height, int width)
 }
 
 // color: interleaved colour frames (CH bytes per pixel): chunks, staging and uploads are sized in input bytes
+// bthr: per-frame thresholds (BatchThr); each chunk's pairs travel through the slot's small pinned buffer on the compute
+// stream, so frame f keeps its pair whatever the chunking, the number of pipelines or the transfer mode
 static int canny_batch_impl(canny_hip_ctx *ctx, const unsigned char *imgs, int n_frames, float sigma, int min_val,
-                            int max_val, int height, int width, void *edges, MapFormat fmt, const ColorIn *color)
+                            int max_val, int height, int width, void *edges, MapFormat fmt, const ColorIn *color,
+                            const BatchThr *bthr)
 {
     using Pipe = canny_hip_ctx::BatchPipe;
     int rc = bind(ctx);
@@ -1628,6 +1691,8 @@ static int canny_batch_impl(canny_hip_ctx *ctx, const unsigned char *imgs, int n
             if (e == hipSuccess) e = S.d_in.ensure(in_bytes);
             if (e == hipSuccess) e = S.d_out.ensure(frame_px * chunk * sizeof(short));
             if (e == hipSuccess && (fmt != kMapS16 || compact)) e = S.d_out8.ensure(out_bytes);
+            if (e == hipSuccess && bthr) e = S.d_thr.ensure((size_t)chunk * 2 * sizeof(int));
+            if (e == hipSuccess && bthr) e = S.pin_thr.ensure((size_t)chunk * 2 * sizeof(int), device);
         }
         if (e != hipSuccess) {
             st = fail(sub, e, "batch staging allocation");
@@ -1706,9 +1771,29 @@ static int canny_batch_impl(canny_hip_ctx *ctx, const unsigned char *imgs, int n
             where = "batch compute";
             if ((e = hipStreamWaitEvent(sub->stream, S.ev_h2d, 0)) != hipSuccess) break;
             if (S.d2h_issued && (e = hipStreamWaitEvent(sub->stream, S.ev_d2h, 0)) != hipSuccess) break;
+            ThrSpec spec;
+            const size_t thr_bytes = (size_t)nf * 2 * sizeof(int);
+            if (bthr) {
+                // pin_thr is free: the slot's previous chunk was waited for (ev_comp) before its download was queued
+                spec.rule = bthr->rule;
+                spec.low = bthr->low;
+                spec.high = bthr->high;
+                if (bthr->rule) {
+                    spec.out = (int *)S.d_thr.p;
+                } else {
+                    std::memcpy(S.pin_thr.p, bthr->pairs + 2 * (size_t)f0, thr_bytes);
+                    if ((e = hipMemcpyAsync(S.d_thr.p, S.pin_thr.p, thr_bytes, hipMemcpyHostToDevice, sub->stream)) !=
+                        hipSuccess)
+                        break;
+                    spec.pairs = (const int *)S.d_thr.p;
+                }
+            }
             st = dev_canny(sub, (const unsigned char *)S.d_in.p, sigma, min_val, max_val, height, width, nf,
-                           (short *)S.d_out.p, color);
+                           (short *)S.d_out.p, color, bthr ? &spec : nullptr);
             if (st) break;
+            if (bthr && bthr->rule && bthr->out &&
+                (e = hipMemcpyAsync(S.pin_thr.p, S.d_thr.p, thr_bytes, hipMemcpyDeviceToHost, sub->stream)) != hipSuccess)
+                break;
             const void *d_res = S.d_out.p;
             if (fmt != kMapS16 || compact) { // narrow on the device: the D2H copy is what these variants are for
                 e = (fmt == kMapU8 && !compact)
@@ -1727,6 +1812,7 @@ static int canny_batch_impl(canny_hip_ctx *ctx, const unsigned char *imgs, int n
             // and what measured best and steadiest (profiles/r02/c3_sweep_*.txt, pipe_patterns.txt "P2b"); letting
             // the host run five chunks ahead kept the s16 rate but made the u8 rate erratic (27-44 ms per 128 x 4K).
             if ((e = hipEventSynchronize(S.ev_comp)) != hipSuccess) break;
+            if (bthr && bthr->rule && bthr->out) std::memcpy(bthr->out + 2 * (size_t)f0, S.pin_thr.p, thr_bytes);
             // download of chunk j (pin_out of this slot was retired kSlots - 1 iterations ago)
             where = "batch D2H";
             unsigned char *dst = (unsigned char *)edges + (size_t)f0 * out_frame;
@@ -1785,6 +1871,73 @@ int canny_hip_canny_batch_bits(canny_hip_ctx *ctx, const unsigned char *imgs, in
                                int max_val, int height, int width, unsigned char *bits)
 {
     return canny_batch_impl(ctx, imgs, n_frames, sigma, min_val, max_val, height, width, bits, kMapBits);
+}
+
+// ---- per-frame thresholds ------------------------------------------------------
+int canny_hip_auto_thresholds_from_histogram(const unsigned int *hist257, int rule, float low, float high, int *min_val,
+                                             int *max_val)
+{
+    if (!hist257 || !min_val || !max_val || !auto_params_valid(rule, low, high)) return CANNY_HIP_ERR_INVALID;
+    unsigned long long cum[kHistBins], run = 0;
+    for (int b = 0; b < kHistBins; b++) cum[b] = run += hist257[b];
+    if (run == 0) return CANNY_HIP_ERR_INVALID; // an empty histogram has no quantiles
+    int lo, hi;
+    auto_thresholds([&](int b) { return cum[b]; }, rule, (double)low, (double)high, lo, hi);
+    *min_val = lo;
+    *max_val = hi;
+    return CANNY_HIP_OK;
+}
+
+int canny_hip_dev_canny_thresholds(canny_hip_ctx *ctx, const unsigned char *d_img, float sigma, const int *d_thresholds,
+                                   int height, int width, int n_frames, short *d_edges)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!d_img || !d_edges || !d_thresholds) return CANNY_HIP_ERR_INVALID;
+    if ((rc = check_dims(height, width, n_frames))) return rc;
+    ThrSpec spec;
+    spec.pairs = d_thresholds;
+    return dev_canny(ctx, d_img, sigma, 0, 0, height, width, n_frames, d_edges, nullptr, &spec);
+}
+
+int canny_hip_dev_canny_auto(canny_hip_ctx *ctx, const unsigned char *d_img, float sigma, int rule, float low, float high,
+                             int height, int width, int n_frames, short *d_edges, int *d_thresholds)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!d_img || !d_edges || !auto_params_valid(rule, low, high)) return CANNY_HIP_ERR_INVALID;
+    if ((rc = check_dims(height, width, n_frames))) return rc;
+    ThrSpec spec;
+    spec.rule = rule;
+    spec.low = low;
+    spec.high = high;
+    spec.out = d_thresholds;
+    return dev_canny(ctx, d_img, sigma, 0, 0, height, width, n_frames, d_edges, nullptr, &spec);
+}
+
+int canny_hip_canny_batch_thresholds(canny_hip_ctx *ctx, const unsigned char *imgs, int n_frames, float sigma,
+                                     const int *thresholds, int height, int width, short *edges)
+{
+    if (!ctx || !thresholds || n_frames < 1) return CANNY_HIP_ERR_INVALID;
+    for (int f = 0; f < n_frames; f++) { // host pairs must already lie in the domain: nothing is written otherwise
+        const int lo = thresholds[2 * f], hi = thresholds[2 * f + 1];
+        if (lo < 1 || lo > hi || hi > 255) return CANNY_HIP_ERR_INVALID;
+    }
+    BatchThr bt;
+    bt.pairs = thresholds;
+    return canny_batch_impl(ctx, imgs, n_frames, sigma, 0, 0, height, width, edges, kMapS16, nullptr, &bt);
+}
+
+int canny_hip_canny_batch_auto(canny_hip_ctx *ctx, const unsigned char *imgs, int n_frames, float sigma, int rule,
+                               float low, float high, int height, int width, short *edges, int *thresholds)
+{
+    if (!ctx || !auto_params_valid(rule, low, high)) return CANNY_HIP_ERR_INVALID;
+    BatchThr bt;
+    bt.rule = rule;
+    bt.low = low;
+    bt.high = high;
+    bt.out = thresholds;
+    return canny_batch_impl(ctx, imgs, n_frames, sigma, 0, 0, height, width, edges, kMapS16, nullptr, &bt);
 }
 
 // ---- colour input on host buffers --------------------------------------------------------------------

@@ -178,10 +178,13 @@ hipError_t launch_sobel_nms_march(const int16_t *smoothed, int16_t *out, int hei
 // only: pair it with launch_hyst_prepare(..., zero_pad = true)) and the provisional edge map `edges`
 // (strong pixels -> edge_value, everything else 0) that launch_hyst_propagate(..., edges, edge_value) completes.
 // Needs width % 8 == 0 and min_val >= 1.
+// pairs != nullptr: per-frame thresholds (clamp_thresholds applied to each, edge_value must then be 255); a separate
+// instantiation, so the kernels of the fixed-threshold call compile exactly as without it.
 bool sobel_nms_classify_supported(int height, int width, int min_val);
 hipError_t launch_sobel_nms_classify_march(const int16_t *smoothed, int16_t *edges, uint64_t *strong, uint64_t *conn,
                                            const HystGeom &g, int min_val, int max_val, int edge_value,
-                                           hipStream_t stream, int tune_seg = 0, const LaunchEvents &ev = {});
+                                           hipStream_t stream, int tune_seg = 0, const LaunchEvents &ev = {},
+                                           const int *pairs = nullptr);
 
 // The two marching kernels reading the smoothed plane as BYTES (8 pixels per lane, LDS-staged planes only).
 bool sobel_nms_u8_input_supported();
@@ -190,11 +193,74 @@ hipError_t launch_sobel_nms_march_u8in(const uint8_t *smoothed, int16_t *out, in
 hipError_t launch_sobel_nms_classify_march_u8in(const uint8_t *smoothed, int16_t *edges, uint64_t *strong,
                                                 uint64_t *conn, const HystGeom &g, int min_val, int max_val,
                                                 int edge_value, hipStream_t stream, int tune_seg = 0,
-                                                const LaunchEvents &ev = {});
+                                                const LaunchEvents &ev = {}, const int *pairs = nullptr);
+
+// ---- per-frame hysteresis thresholds (canny_hip_*_thresholds, canny_hip_*_auto) ----------
+// A pair array holds (min_val, max_val) of frame f at [2f], [2f+1].  Every consumer clamps a pair into the domain
+// 1 <= min_val <= max_val <= 255 first: there the edge map is the reference's for that pair, promoted pixels are
+// always 255 and the scan-order-dependent case (hysteresis_order_dependent) cannot occur.
+__host__ __device__ inline void clamp_thresholds(int &lo, int &hi)
+{
+    lo = lo < 1 ? 1 : (lo > 255 ? 255 : lo);
+    hi = hi < lo ? lo : (hi > 255 ? 255 : hi);
+}
+
+constexpr int kAutoMedian = 1, kAutoQuantile = 2; // CANNY_HIP_AUTO_*
+constexpr int kHistBins = 257;                     // per-frame histograms: values 0..255, and 256 = "256 or more"
+
+// Q(q) = min { b : h[0] + ... + h[b] >= max(1, ceil(q * N)) } on a cumulative histogram cum(b) (N = cum(256)),
+// in IEEE double like the host restatement.  257 when no bin reaches the count (N = 0).
+template <class Cum>
+__host__ __device__ inline int hist_quantile(const Cum &cum, double q)
+{
+    const double t = ceil(q * (double)cum(kHistBins - 1));
+    const unsigned long long need = t < 1.0 ? 1ull : (unsigned long long)t;
+    int a = 0, b = kHistBins; // smallest index in [a, b) whose count reaches `need`, b if none
+    while (a < b) {
+        const int m = (a + b) >> 1;
+        if (cum(m) >= need)
+            b = m;
+        else
+            a = m + 1;
+    }
+    return a;
+}
+
+// THE selection rule (host export canny_hip_auto_thresholds_from_histogram and the device select kernel):
+//   median:   m = Q(0.5), (floor(low * m), floor(high * m))   on the smoothed plane's histogram
+//   quantile: (Q(low), Q(high))                                on the histogram of min(magnitude, 256)
+// then clamp_thresholds.  Parameters are validated by the caller (0 <= low <= high finite; quantile 0 < low <= high <= 1).
+template <class Cum>
+__host__ __device__ inline void auto_thresholds(const Cum &cum, int rule, double low, double high, int &lo, int &hi)
+{
+    if (rule == kAutoMedian) {
+        const double m = (double)hist_quantile(cum, 0.5);
+        // (products above 256 clamp to 255 anyway; capping first keeps the conversion to int defined)
+        lo = (int)floor(fmin(low * m, 256.0));
+        hi = (int)floor(fmin(high * m, 256.0));
+    } else {
+        lo = hist_quantile(cum, low);
+        hi = hist_quantile(cum, high);
+    }
+    clamp_thresholds(lo, hi);
+}
+
+// Histograms of n_frames planes into hist[n_frames][kHistBins] (u32, must be zero beforehand; integer atomics, so
+// the counts are exact whatever the order).  The plane is the smoothed one, bytes (in_u8) or shorts in [0,255].
+//   intensity: bin = value
+//   gradient:  bin = min(magnitude, 256) of the reference's Sobel (sobelOperator, its border rule) on that plane
+hipError_t launch_hist_intensity(const void *plane, bool in_u8, uint32_t *hist, int height, int width, int n_frames,
+                                 hipStream_t stream);
+hipError_t launch_hist_gradient(const void *plane, bool in_u8, uint32_t *hist, int height, int width, int n_frames,
+                                hipStream_t stream);
+// One wave per frame: the rule above on hist[f] -> pairs[2f], pairs[2f+1].
+hipError_t launch_thr_select(const uint32_t *hist, int n_frames, int rule, double low, double high, int *pairs,
+                             hipStream_t stream);
 
 // ---- Hysteresis (src/utils.cpp:322-427) -----------------------------------------------------
+// pairs != nullptr: per-frame thresholds (clamp_thresholds applied to each; min_val / max_val are then ignored)
 hipError_t launch_hyst_classify(const int16_t *cand, uint64_t *strong, uint64_t *conn, const HystGeom &g, int min_val,
-                                int max_val, unsigned *domain_flag, hipStream_t stream);
+                                int max_val, unsigned *domain_flag, hipStream_t stream, const int *pairs = nullptr);
 // One propagation sweep (`iter` = 0,1,2,...).  sched holds hyst_sched_words(g) words (tile stamps, two batch-wide
 // work queues with three counters, two per-frame work queues with four counter words per frame) and, like the
 // single word last_change, must be zero before sweep 0.

@@ -103,6 +103,23 @@ __device__ __forceinline__ void sobel_at(const int16_t *__restrict__ f, int H, i
     gy = (int16_t)u;
 }
 
+// The same derivatives from a staged tile: at(ly, lx) reads the tile, (ly, lx) is where image pixel (r,c) sits in it and
+// the tile holds its in-image neighbours (sobel_nms_tile_kernel, hist_gradient_kernel).
+template <class At>
+__device__ __forceinline__ void sobel_staged(const At &at, int H, int W, int r, int c, int ly, int lx, int &gx, int &gy)
+{
+    int lxl = c > 0 ? lx - 1 : lx, lxr = c < W - 1 ? lx + 1 : lx;
+    int lyu = r > 0 ? ly - 1 : ly, lyd = r < H - 1 ? ly + 1 : ly;
+    int v = 2 * at(ly, lxr) - 2 * at(ly, lxl);
+    if (r < H - 1) v += at(ly + 1, lxr) - at(ly + 1, lxl);
+    if (r > 0) v += at(ly - 1, lxr) - at(ly - 1, lxl);
+    int u = 2 * at(lyd, lx) - 2 * at(lyu, lx);
+    if (c < W - 1) u += at(lyd, lx + 1) - at(lyu, lx + 1);
+    if (c > 0) u += at(lyd, lx - 1) - at(lyu, lx - 1);
+    gx = (int16_t)v;
+    gy = (int16_t)u;
+}
+
 // ================================================================================================
 // Gaussian, general two-pass path (any window <= 129).  One thread per pixel, taps visited in
 // ascending order, out-of-image taps skipped in both the sum and the weight.
@@ -299,16 +316,8 @@ __global__ __launch_bounds__(256) void sobel_nms_tile_kernel(const int16_t *__re
         int m = 0, b = 0;
         if (r >= 0 && r < H && c >= 0 && c < W) {
             // LDS coordinates of (r,c) are (my+1, mx+1); clamp/drop decided in image coordinates
-            int ly = my + 1, lx = mx + 1;
-            int lxl = c > 0 ? lx - 1 : lx, lxr = c < W - 1 ? lx + 1 : lx;
-            int lyu = r > 0 ? ly - 1 : ly, lyd = r < H - 1 ? ly + 1 : ly;
-            int v = 2 * sm[ly][lxr] - 2 * sm[ly][lxl];
-            if (r < H - 1) v += sm[ly + 1][lxr] - sm[ly + 1][lxl];
-            if (r > 0) v += sm[ly - 1][lxr] - sm[ly - 1][lxl];
-            int u = 2 * sm[lyd][lx] - 2 * sm[lyu][lx];
-            if (c < W - 1) u += sm[lyd][lx + 1] - sm[lyu][lx + 1];
-            if (c > 0) u += sm[lyd][lx - 1] - sm[lyu][lx - 1];
-            int gx = (int16_t)v, gy = (int16_t)u;
+            int gx, gy;
+            sobel_staged([&](int y, int x) -> int { return sm[y][x]; }, H, W, r, c, my + 1, mx + 1, gx, gy);
             if (D8) {
                 m = magnitude_d8(gx, gy);
                 b = angle_bin_d8(gx, gy);
@@ -364,6 +373,241 @@ hipError_t launch_sobel_nms(const int16_t *smoothed, int16_t *out, int height, i
 }
 
 // ================================================================================================
+// Per-frame histograms and the threshold select of the automatic rules (canny_hip_*_auto).
+// Each workgroup takes a share of ONE frame (blockIdx.y), counts into per-wave LDS sub-histograms and flushes the
+// non-zero bins into hist[frame] with integer global atomics: exact, whatever the order.  ~8 workgroups per CU in
+// all, so that the flush (<= 257 global atomics per workgroup) stays a small part of the traffic.
+// ================================================================================================
+constexpr int kHistWaves = 4;
+constexpr int kHistBlocks = 2048;
+
+// +1 in bin `bin` of the wave's sub-histogram.  When every active lane has the same bin (flat regions, constant
+// frames: LDS atomics to one address serialise) one lane adds the wave's count instead.
+__device__ __forceinline__ void wave_hist_add(uint32_t *h, int bin)
+{
+    const uint64_t active = __ballot(1);
+    const int first = __builtin_amdgcn_readfirstlane(bin);
+    if (__ballot(bin == first) == active) {
+        if ((int)(threadIdx.x & 63) == __ffsll((unsigned long long)active) - 1)
+            atomicAdd(&h[first], (uint32_t)__popcll(active));
+    } else {
+        atomicAdd(&h[bin], 1u);
+    }
+}
+
+__device__ __forceinline__ void hist_clear(uint32_t (*sh)[kHistBins])
+{
+    for (int i = threadIdx.x; i < kHistWaves * kHistBins; i += blockDim.x) (&sh[0][0])[i] = 0u;
+    __syncthreads();
+}
+
+__device__ __forceinline__ void hist_flush(uint32_t (*sh)[kHistBins], uint32_t *__restrict__ out)
+{
+    __syncthreads();
+    for (int b = threadIdx.x; b < kHistBins; b += blockDim.x) {
+        uint32_t sum = 0u;
+#pragma unroll
+        for (int w = 0; w < kHistWaves; w++) sum += sh[w][b];
+        if (sum) atomicAdd(&out[b], sum);
+    }
+}
+
+// Intensity: 16-pixel groups of the batch (aligned to the plane's base, so frames may start inside a group) that
+// overlap frame blockIdx.y; pixels of other frames are masked.  A lane loads kHistGroups groups before it counts any
+// (the loop is bound by load latency otherwise).  A group of 16 equal pixels is one atomic of 16, and a wave whose lanes
+// all hold the same such group is one atomic for the wave.
+constexpr int kHistGroups = 4;
+template <bool U8>
+__global__ __launch_bounds__(kHistWaves * 64) void hist_intensity_kernel(const void *__restrict__ plane,
+                                                                        uint32_t *__restrict__ hist, size_t frame_px,
+                                                                        size_t total_px)
+{
+    constexpr int NW = U8 ? 4 : 8; // words per 16-pixel group
+    __shared__ uint32_t sh[kHistWaves][kHistBins];
+    hist_clear(sh);
+    uint32_t *h = sh[threadIdx.x >> 6];
+    const size_t f = blockIdx.y, beg = f * frame_px, end = beg + frame_px;
+    const size_t g1 = (end + 15) / 16, stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t gb = beg / 16 + (size_t)blockIdx.x * blockDim.x + threadIdx.x; gb < g1; gb += kHistGroups * stride) {
+        uint32_t w[kHistGroups][NW];
+#pragma unroll
+        for (int k = 0; k < kHistGroups; k++) { // all loads first
+            const size_t p0 = (gb + k * stride) * 16;
+#pragma unroll
+            for (int i = 0; i < NW; i++) w[k][i] = 0u;
+            if (gb + k * stride >= g1) continue;
+            if (p0 + 16 <= total_px) {
+                __builtin_memcpy(w[k], (const uint8_t *)plane + p0 * (U8 ? 1 : 2), sizeof w[k]);
+            } else { // the batch's last, partial group
+                for (int e = 0; e < 16 && p0 + e < total_px; e++) {
+                    const uint32_t v =
+                        U8 ? ((const uint8_t *)plane)[p0 + e] : (uint16_t)((const int16_t *)plane)[p0 + e];
+                    w[k][U8 ? e >> 2 : e >> 1] |= v << (U8 ? 8 * (e & 3) : 16 * (e & 1));
+                }
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < kHistGroups; k++) {
+            const size_t g = gb + k * stride, p0 = g * 16;
+            if (g >= g1) break; // (the later groups of this lane lie further out)
+            const uint32_t v0 = U8 ? (w[k][0] & 0xffu) : (w[k][0] & 0xffffu);
+            const uint32_t rep = U8 ? v0 * 0x01010101u : v0 * 0x00010001u;
+            bool flat = p0 >= beg && p0 + 16 <= end;
+#pragma unroll
+            for (int i = 0; i < NW; i++) flat = flat && w[k][i] == rep;
+            const uint64_t active = __ballot(1);
+            const uint32_t first = (uint32_t)__builtin_amdgcn_readfirstlane((int)v0);
+            if (__ballot(flat && v0 == first) == active) {
+                if ((int)(threadIdx.x & 63) == __ffsll((unsigned long long)active) - 1)
+                    atomicAdd(&h[min(first, 255u)], 16u * (uint32_t)__popcll(active));
+            } else if (flat) {
+                atomicAdd(&h[min(v0, 255u)], 16u);
+            } else {
+#pragma unroll
+                for (int e = 0; e < 16; e++) {
+                    const size_t p = p0 + e;
+                    if (p < beg || p >= end) continue;
+                    const uint32_t v =
+                        U8 ? (w[k][e >> 2] >> (8 * (e & 3))) & 0xffu : (w[k][e >> 1] >> (16 * (e & 1))) & 0xffffu;
+                    atomicAdd(&h[min(v, 255u)], 1u); // the plane lies in [0,255]; the min only bounds the index
+                }
+            }
+        }
+    }
+    hist_flush(sh, hist + f * kHistBins);
+}
+
+// Gradient magnitude: 64 x 32 tiles of frame blockIdx.y staged with a 1-pixel halo, then per pixel the reference's
+// Sobel (sobel_staged: in-axis clamp, off-axis drop) and magnitude (magnitude_d8: the plane lies in [0,255]).  The next
+// tile's pixels are loaded into registers while the current one is counted.
+constexpr int HG_TW = 64, HG_TH = 32;
+constexpr int HG_STAGE = (HG_TH + 2) * (HG_TW + 2);
+constexpr int HG_PER_THREAD = (HG_STAGE + kHistWaves * 64 - 1) / (kHistWaves * 64);
+template <bool U8>
+__global__ __launch_bounds__(kHistWaves * 64) void hist_gradient_kernel(const void *__restrict__ plane,
+                                                                       uint32_t *__restrict__ hist, int H, int W)
+{
+    __shared__ uint32_t sh[kHistWaves][kHistBins];
+    __shared__ int16_t tile[HG_TH + 2][HG_TW + 2];
+    hist_clear(sh);
+    uint32_t *h = sh[threadIdx.x >> 6];
+    const size_t f = blockIdx.y, frame_px = (size_t)H * W;
+    const int tiles_x = (W + HG_TW - 1) / HG_TW, tiles = tiles_x * ((H + HG_TH - 1) / HG_TH);
+    int v[HG_PER_THREAD];
+    auto fetch = [&](int t) {
+        const int x0 = (t % tiles_x) * HG_TW, y0 = (t / tiles_x) * HG_TH;
+#pragma unroll
+        for (int k = 0; k < HG_PER_THREAD; k++) {
+            const int i = (int)threadIdx.x + k * kHistWaves * 64;
+            const int ly = i / (HG_TW + 2), lx = i - ly * (HG_TW + 2);
+            const int r = y0 - 1 + ly, c = x0 - 1 + lx;
+            v[k] = 0;
+            if (t < tiles && i < HG_STAGE && r >= 0 && r < H && c >= 0 && c < W) {
+                const size_t q = f * frame_px + (size_t)r * W + c;
+                v[k] = U8 ? ((const uint8_t *)plane)[q] : ((const int16_t *)plane)[q];
+            }
+        }
+    };
+    fetch(blockIdx.x);
+    for (int t = blockIdx.x; t < tiles; t += gridDim.x) {
+        const int x0 = (t % tiles_x) * HG_TW, y0 = (t / tiles_x) * HG_TH;
+        __syncthreads(); // the previous tile has been read
+#pragma unroll
+        for (int k = 0; k < HG_PER_THREAD; k++) {
+            const int i = (int)threadIdx.x + k * kHistWaves * 64;
+            if (i < HG_STAGE) (&tile[0][0])[i] = (int16_t)v[k];
+        }
+        __syncthreads();
+        fetch(t + gridDim.x); // in flight while this tile is counted
+        for (int i = threadIdx.x; i < HG_TH * HG_TW; i += blockDim.x) {
+            const int my = i / HG_TW, mx = i - my * HG_TW; // a wave takes one tile row
+            const int r = y0 + my, c = x0 + mx;
+            if (r >= H || c >= W) continue;
+            int gx, gy;
+            sobel_staged([&](int y, int x) -> int { return tile[y][x]; }, H, W, r, c, my + 1, mx + 1, gx, gy);
+            wave_hist_add(h, min(magnitude_d8(gx, gy), kHistBins - 1));
+        }
+    }
+    hist_flush(sh, hist + f * kHistBins);
+}
+
+static unsigned hist_blocks_per_frame(int n_frames, size_t units_per_frame)
+{
+    size_t b = ((size_t)kHistBlocks + n_frames - 1) / n_frames;
+    if (b > units_per_frame) b = units_per_frame;
+    return (unsigned)(b < 1 ? 1 : b);
+}
+
+hipError_t launch_hist_intensity(const void *plane, bool in_u8, uint32_t *hist, int height, int width, int n_frames,
+                                 hipStream_t stream)
+{
+    const size_t frame_px = (size_t)height * width, total = frame_px * n_frames;
+    const size_t lanes = (frame_px / 16 + 2 + kHistGroups - 1) / kHistGroups;
+    const dim3 grid(hist_blocks_per_frame(n_frames, (lanes + kHistWaves * 64 - 1) / (kHistWaves * 64)), n_frames);
+    if (in_u8)
+        hipLaunchKernelGGL(hist_intensity_kernel<true>, grid, dim3(kHistWaves * 64), 0, stream, plane, hist, frame_px,
+                           total);
+    else
+        hipLaunchKernelGGL(hist_intensity_kernel<false>, grid, dim3(kHistWaves * 64), 0, stream, plane, hist, frame_px,
+                           total);
+    return hipGetLastError();
+}
+
+hipError_t launch_hist_gradient(const void *plane, bool in_u8, uint32_t *hist, int height, int width, int n_frames,
+                                hipStream_t stream)
+{
+    const size_t tiles = (size_t)((width + HG_TW - 1) / HG_TW) * ((height + HG_TH - 1) / HG_TH);
+    const dim3 grid(hist_blocks_per_frame(n_frames, tiles), n_frames);
+    if (in_u8)
+        hipLaunchKernelGGL(hist_gradient_kernel<true>, grid, dim3(kHistWaves * 64), 0, stream, plane, hist, height,
+                           width);
+    else
+        hipLaunchKernelGGL(hist_gradient_kernel<false>, grid, dim3(kHistWaves * 64), 0, stream, plane, hist, height,
+                           width);
+    return hipGetLastError();
+}
+
+// One wave per frame: inclusive prefix sum of the 257 bins (lane l owns bins 5l .. 5l+4) into LDS, then
+// auto_thresholds (canny_kernels.h) on it.
+__global__ __launch_bounds__(64) void thr_select_kernel(const uint32_t *__restrict__ hist, int rule, double low,
+                                                        double high, int *__restrict__ pairs)
+{
+    __shared__ unsigned long long cs[kHistBins];
+    const int f = blockIdx.x, lane = threadIdx.x;
+    const uint32_t *hf = hist + (size_t)f * kHistBins;
+    unsigned long long part[5], run = 0;
+#pragma unroll
+    for (int k = 0; k < 5; k++) {
+        const int b = 5 * lane + k;
+        run += b < kHistBins ? hf[b] : 0u;
+        part[k] = run;
+    }
+    unsigned long long x = run; // inclusive scan of the lane totals
+    for (int d = 1; d < 64; d <<= 1) {
+        const unsigned lo = __shfl_up((unsigned)x, d), hi = __shfl_up((unsigned)(x >> 32), d);
+        if (lane >= d) x += ((unsigned long long)hi << 32) | lo;
+    }
+    const unsigned long long excl = x - run;
+#pragma unroll
+    for (int k = 0; k < 5; k++)
+        if (5 * lane + k < kHistBins) cs[5 * lane + k] = excl + part[k];
+    __syncthreads();
+    if (lane == 0) {
+        int lo, hi;
+        auto_thresholds([&](int b) { return cs[b]; }, rule, low, high, lo, hi);
+        pairs[2 * f] = lo;
+        pairs[2 * f + 1] = hi;
+    }
+}
+
+hipError_t launch_thr_select(const uint32_t *hist, int n_frames, int rule, double low, double high, int *pairs,
+                             hipStream_t stream)
+{
+    hipLaunchKernelGGL(thr_select_kernel, dim3(n_frames), dim3(64), 0, stream, hist, rule, low, high, pairs);
+    return hipGetLastError();
+}
+
+// ================================================================================================
 // Hysteresis on bit-planes.
 //   classify : one wave per 64-pixel word; __ballot turns the two threshold tests into the
 //              `connectable` (v >= min) and `strong` (connectable && v >= max) bit-planes.
@@ -380,10 +624,12 @@ __device__ __forceinline__ size_t word_index(const HystGeom &g, int f, int y, in
     return ((((size_t)f * g.tiles_y + (y >> 6)) * g.tiles_x + wx) << 6) + (y & 63);
 }
 
+// THR: per-frame pairs (clamp_thresholds; lo / hi ignored).  A template flag, like the fused kernel's.
+template <bool THR>
 __global__ __launch_bounds__(256) void hyst_classify_kernel(const int16_t *__restrict__ cand,
                                                             uint64_t *__restrict__ strong,
                                                             uint64_t *__restrict__ conn, HystGeom g, int lo, int hi,
-                                                            unsigned *domain_flag)
+                                                            unsigned *domain_flag, const int *__restrict__ pairs)
 {
     const int lane = threadIdx.x & 63;
     const size_t rows_padded = (size_t)g.tiles_y * kTile;
@@ -394,6 +640,11 @@ __global__ __launch_bounds__(256) void hyst_classify_kernel(const int16_t *__res
         size_t t = wv / (size_t)g.tiles_x;
         int y = (int)(t % rows_padded);
         int f = (int)(t / rows_padded);
+        if constexpr (THR) {
+            lo = pairs[2 * f];
+            hi = pairs[2 * f + 1];
+            clamp_thresholds(lo, hi);
+        }
         int x = wx * kTile + lane;
         bool inside = (y < g.height) && (x < g.width);
         int v = 0;
@@ -854,10 +1105,17 @@ __device__ __forceinline__ bool patch_tile_exists(const HystGeom &g, int k)
     return (int)blockIdx.x * 2 + (k >> 1) < g.tiles_x;
 }
 
+template <bool THR>
 __global__ __launch_bounds__(256) void hyst_classify8_kernel(const int16_t *__restrict__ cand,
                                                              uint8_t *__restrict__ strong, uint8_t *__restrict__ conn,
-                                                             HystGeom g, int lo, int hi, unsigned *domain_flag)
+                                                             HystGeom g, int lo, int hi, unsigned *domain_flag,
+                                                             const int *__restrict__ pairs)
 {
+    if constexpr (THR) { // one frame per workgroup (blockIdx.z, patch_coords)
+        lo = pairs[2 * blockIdx.z];
+        hi = pairs[2 * blockIdx.z + 1];
+        clamp_thresholds(lo, hi);
+    }
     const bool fast = lo >= -32768 && lo <= 32767 && hi >= -32768 && hi <= 32767; // wave-uniform
     const uint32_t lo2 = ((uint32_t)lo & 0xffffu) * 0x10001u, hi2 = ((uint32_t)hi & 0xffffu) * 0x10001u;
     uint4 px4[kPatchItems];
@@ -941,15 +1199,22 @@ __global__ __launch_bounds__(256) void hyst_finalize8_kernel(int16_t *__restrict
 }
 
 hipError_t launch_hyst_classify(const int16_t *cand, uint64_t *strong, uint64_t *conn, const HystGeom &g, int min_val,
-                                int max_val, unsigned *domain_flag, hipStream_t stream)
+                                int max_val, unsigned *domain_flag, hipStream_t stream, const int *pairs)
 {
     size_t n_words = (size_t)g.n_frames * g.tiles_y * kTile * g.tiles_x;
-    if (g.width % 8 == 0)
-        hipLaunchKernelGGL(hyst_classify8_kernel, dim3((g.tiles_x + 1) / 2, g.tiles_y, g.n_frames), dim3(256), 0, stream,
-                           cand, (uint8_t *)strong, (uint8_t *)conn, g, min_val, max_val, domain_flag);
+    const dim3 grid8((g.tiles_x + 1) / 2, g.tiles_y, g.n_frames), grid(grid_for(n_words * 64, 256));
+    if (g.width % 8 == 0 && pairs)
+        hipLaunchKernelGGL(hyst_classify8_kernel<true>, grid8, dim3(256), 0, stream, cand, (uint8_t *)strong,
+                           (uint8_t *)conn, g, min_val, max_val, domain_flag, pairs);
+    else if (g.width % 8 == 0)
+        hipLaunchKernelGGL(hyst_classify8_kernel<false>, grid8, dim3(256), 0, stream, cand, (uint8_t *)strong,
+                           (uint8_t *)conn, g, min_val, max_val, domain_flag, pairs);
+    else if (pairs)
+        hipLaunchKernelGGL(hyst_classify_kernel<true>, grid, dim3(256), 0, stream, cand, strong, conn, g, min_val,
+                           max_val, domain_flag, pairs);
     else
-        hipLaunchKernelGGL(hyst_classify_kernel, dim3(grid_for(n_words * 64, 256)), dim3(256), 0, stream, cand,
-                           strong, conn, g, min_val, max_val, domain_flag);
+        hipLaunchKernelGGL(hyst_classify_kernel<false>, grid, dim3(256), 0, stream, cand, strong, conn, g, min_val,
+                           max_val, domain_flag, pairs);
     return hipGetLastError();
 }
 // Start of every hysteresis call.  With zero_pad it zeroes the parts of both planes that lie outside the image

@@ -948,10 +948,13 @@ __device__ __forceinline__ void fmarch_strip(const StripJob &jb, uint8_t *stage_
 struct PlaneArgs { // PLANES instantiation only
     uint8_t *conn, *strong;
     int tiles_x, tiles_y, lo1, hi1, edge_value;
+    const int *thr; // THR instantiation only: per-frame (min_val, max_val) pairs, frame-major; lo1 / hi1 unused
 };
 
 // FLT: the f32 marching arithmetic (fmarch_strip, 8 pixels per lane only) instead of the packed-i16 one.
-template <bool PLANES, int NP, bool LDS_PLANES, bool IN_U8 = false, bool FLT = false>
+// THR (PLANES only): the thresholds come per frame from pl.thr.  A template flag rather than a run-time null test, so
+// that the fixed-threshold kernels canny() runs compile exactly as before.
+template <bool PLANES, int NP, bool LDS_PLANES, bool IN_U8 = false, bool FLT = false, bool THR = false>
 __global__ __launch_bounds__(SNM_WPB * 64) __attribute__((amdgpu_waves_per_eu(FLT ? FLT_WAVES : 1)))
 void sobel_nms_march_kernel(const void *__restrict__ in,
                                                                        int16_t *__restrict__ out, int H, int W,
@@ -1005,8 +1008,16 @@ void sobel_nms_march_kernel(const void *__restrict__ in,
         jb.pconn = pl.conn + (size_t)f * frame_bytes;
         jb.pstrong = pl.strong + (size_t)f * frame_bytes;
         jb.tiles_x = pl.tiles_x;
-        jb.lo1 = pl.lo1;
-        jb.hi1 = pl.hi1;
+        if constexpr (THR) {
+            // f is wave-uniform: two scalar loads per strip job
+            int lo = pl.thr[2 * f], hi = pl.thr[2 * f + 1];
+            clamp_thresholds(lo, hi);
+            jb.lo1 = lo - 1;
+            jb.hi1 = hi - 1;
+        } else {
+            jb.lo1 = pl.lo1;
+            jb.hi1 = pl.hi1;
+        }
     }
     // first strip: column 0 and the out-of-image halo lane; last strip: column W-1 and columns >= W
     const bool col_edge = (s == 0) || ((s + 1) * SnmCfg<NP>::SW + SnmCfg<NP>::PX >= W);
@@ -1069,6 +1080,7 @@ static void launch_timed(K kernel, dim3 grid, dim3 block, hipStream_t stream, co
         hipLaunchKernelGGL(kernel, grid, block, 0, stream, args...);
 }
 
+template <bool THR = false>
 static hipError_t launch_march(const void *smoothed, int16_t *out, const PlaneArgs *planes, int height, int width,
                                int n_frames, hipStream_t stream, int tune_seg, const LaunchEvents &ev,
                                bool in_u8 = false)
@@ -1095,8 +1107,8 @@ static hipError_t launch_march(const void *smoothed, int16_t *out, const PlaneAr
     if (use_f32 && np == 4) { // the f32 arithmetic: every 8-pixel form
         const bool lds = planes && plane_store_variant == 0;
 #define CANNY_FLT_LAUNCH(P, L, U)                                                                                      \
-    launch_timed(sobel_nms_march_kernel<P, 4, L, U, true>, grid, block, stream, ev, smoothed, out, height, width,      \
-                 n_strips, n_segs, seg, (int)waves, pl)
+    launch_timed(sobel_nms_march_kernel<P, 4, L, U, true, P && THR>, grid, block, stream, ev, smoothed, out, height,   \
+                 width, n_strips, n_segs, seg, (int)waves, pl)
         if (planes && lds && in_u8) CANNY_FLT_LAUNCH(true, true, true);
         else if (planes && lds) CANNY_FLT_LAUNCH(true, true, false);
         else if (planes) CANNY_FLT_LAUNCH(true, false, false);
@@ -1106,19 +1118,19 @@ static hipError_t launch_march(const void *smoothed, int16_t *out, const PlaneAr
         return hipGetLastError();
     }
     if (in_u8 && planes)
-        launch_timed(sobel_nms_march_kernel<true, 4, true, true>, grid, block, stream, ev, smoothed, out, height, width,
+        launch_timed(sobel_nms_march_kernel<true, 4, true, true, false, THR>, grid, block, stream, ev, smoothed, out, height, width,
                      n_strips, n_segs, seg, (int)waves, pl);
     else if (in_u8)
         launch_timed(sobel_nms_march_kernel<false, 4, false, true>, grid, block, stream, ev, smoothed, out, height,
                      width, n_strips, n_segs, seg, (int)waves, pl);
     else if (planes && np == 4 && plane_store_variant == 0)
-        launch_timed(sobel_nms_march_kernel<true, 4, true>, grid, block, stream, ev, smoothed, out, height, width,
+        launch_timed(sobel_nms_march_kernel<true, 4, true, false, false, THR>, grid, block, stream, ev, smoothed, out, height, width,
                      n_strips, n_segs, seg, (int)waves, pl);
     else if (planes && np == 4)
-        launch_timed(sobel_nms_march_kernel<true, 4, false>, grid, block, stream, ev, smoothed, out, height, width,
+        launch_timed(sobel_nms_march_kernel<true, 4, false, false, false, THR>, grid, block, stream, ev, smoothed, out, height, width,
                      n_strips, n_segs, seg, (int)waves, pl);
     else if (planes)
-        launch_timed(sobel_nms_march_kernel<true, 2, false>, grid, block, stream, ev, smoothed, out, height, width,
+        launch_timed(sobel_nms_march_kernel<true, 2, false, false, false, THR>, grid, block, stream, ev, smoothed, out, height, width,
                      n_strips, n_segs, seg, (int)waves, pl);
     else if (np == 4)
         launch_timed(sobel_nms_march_kernel<false, 4, false>, grid, block, stream, ev, smoothed, out, height, width,
@@ -1150,27 +1162,30 @@ hipError_t launch_sobel_nms_march_u8in(const uint8_t *smoothed, int16_t *out, in
 
 static hipError_t classify_march_any(const void *smoothed, bool in_u8, int16_t *edges, uint64_t *strong, uint64_t *conn,
                                      const HystGeom &g, int min_val, int max_val, int edge_value, hipStream_t stream,
-                                     int tune_seg, const LaunchEvents &ev);
+                                     int tune_seg, const LaunchEvents &ev, const int *pairs);
 
 hipError_t launch_sobel_nms_classify_march(const int16_t *smoothed, int16_t *edges, uint64_t *strong, uint64_t *conn,
                                            const HystGeom &g, int min_val, int max_val, int edge_value,
-                                           hipStream_t stream, int tune_seg, const LaunchEvents &ev)
+                                           hipStream_t stream, int tune_seg, const LaunchEvents &ev, const int *pairs)
 {
-    return classify_march_any(smoothed, false, edges, strong, conn, g, min_val, max_val, edge_value, stream, tune_seg, ev);
+    return classify_march_any(smoothed, false, edges, strong, conn, g, min_val, max_val, edge_value, stream, tune_seg, ev,
+                              pairs);
 }
 
 hipError_t launch_sobel_nms_classify_march_u8in(const uint8_t *smoothed, int16_t *edges, uint64_t *strong,
                                                 uint64_t *conn, const HystGeom &g, int min_val, int max_val,
                                                 int edge_value, hipStream_t stream, int tune_seg,
-                                                const LaunchEvents &ev)
+                                                const LaunchEvents &ev, const int *pairs)
 {
-    return classify_march_any(smoothed, true, edges, strong, conn, g, min_val, max_val, edge_value, stream, tune_seg, ev);
+    return classify_march_any(smoothed, true, edges, strong, conn, g, min_val, max_val, edge_value, stream, tune_seg, ev,
+                              pairs);
 }
 
 static hipError_t classify_march_any(const void *smoothed, bool in_u8, int16_t *edges, uint64_t *strong, uint64_t *conn,
                                      const HystGeom &g, int min_val, int max_val, int edge_value, hipStream_t stream,
-                                     int tune_seg, const LaunchEvents &ev)
+                                     int tune_seg, const LaunchEvents &ev, const int *pairs)
 {
+    if (pairs) min_val = max_val = 255; // every clamped pair is in [1, 255]: the shape test and edge value below
     if (!sobel_nms_classify_supported(g.height, g.width, min_val)) return hipErrorNotSupported;
     if (edge_value < 0 || edge_value > 32767) return hipErrorInvalidValue;
     // magnitudes are <= 1442, so thresholds beyond that all mean "never"; clamping keeps hi1 from overflowing
@@ -1184,6 +1199,11 @@ static hipError_t classify_march_any(const void *smoothed, bool in_u8, int16_t *
     pl.lo1 = lo - 1;
     pl.hi1 = (hi > lo ? hi : lo) - 1;
     pl.edge_value = edge_value;
+    pl.thr = pairs;
+    if (pairs) {
+        if (edge_value != 255) return hipErrorInvalidValue; // promoted pixels of a clamped pair are 255
+        return launch_march<true>(smoothed, edges, &pl, g.height, g.width, g.n_frames, stream, tune_seg, ev, in_u8);
+    }
     return launch_march(smoothed, edges, &pl, g.height, g.width, g.n_frames, stream, tune_seg, ev, in_u8);
 }
 

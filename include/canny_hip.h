@@ -52,7 +52,8 @@
 extern "C" {
 #endif
 
-#define CANNY_HIP_VERSION 300        /* 0.3.0: + colour frame input (BGR / RGB / BGRA / RGBA -> gray on the GPU) */
+#define CANNY_HIP_VERSION 400        /* 0.4.0: + per-frame thresholds, explicit or chosen on the GPU (median / quantile) */
+/* 0.3.0: + colour frame input (BGR / RGB / BGRA / RGBA -> gray on the GPU) */
 /* 0.2.0: + batch u8 / bit maps, multi-GPU options, host_register, async dev_canny */
 #define CANNY_HIP_MAX_WINDOW 129     /* largest Gaussian window (sigma <= 21.33) */
 
@@ -305,6 +306,45 @@ int canny_hip_dev_gaussian_u8_color(canny_hip_ctx *ctx, const unsigned char *d_s
  * one kernel more.)  d_src may be reused once the context's stream has passed the call. */
 int canny_hip_dev_canny_color(canny_hip_ctx *ctx, const unsigned char *d_src, int layout, float sigma, int min_val,
                               int max_val, int height, int width, int n_frames, short *d_edges);
+
+/* ---- per-frame hysteresis thresholds -------------------------------------------------------------------------------
+ * Frame f of a call gets its own pair (min_val[f], max_val[f]), stored at [2f], [2f+1] of a pair array.  Domain:
+ * 1 <= min_val <= max_val <= 255 (everything the reference's CLI accepts except min_val = 0).  In it frame f's edge map is
+ * bit-identical to canny_hip_canny(frame f, sigma, min_val[f], max_val[f]); promoted pixels are always 255.
+ * Automatic rules, on a per-frame 257-bin histogram h[0..256] with N = sum(h) and the inverted-CDF quantile
+ *     Q(q) = min { b : h[0] + ... + h[b] >= max(1, ceil((double)q * (double)N)) },  0 < q <= 1:
+ *   CANNY_HIP_AUTO_MEDIAN    histogram of the smoothed plane (the Gaussian's output, 0..255); m = Q(0.5),
+ *                            min_val = floor((double)low * m), max_val = floor((double)high * m); 0 <= low <= high.
+ *                            The "auto_canny" idiom is low = 1 - s, high = 1 + s.
+ *   CANNY_HIP_AUTO_QUANTILE  histogram of min(magnitude, 256) of the pre-NMS gradient magnitude (canny_hip_sobel's plane,
+ *                            borders included); min_val = Q(low), max_val = Q(high); 0 < low <= high <= 1 (skimage's
+ *                            use_quantiles).
+ * then min_val = clamp(min_val, 1, 255), max_val = clamp(max_val, min_val, 255) (a black frame gets (1, 1)).  low and high
+ * are widened to double exactly and all arithmetic is IEEE double, on the host and on the device.  An unknown rule, low /
+ * high outside these ranges, NaN or infinity: CANNY_HIP_ERR_INVALID.  Every other status is as for canny_hip_canny.
+ * The histogram and select passes are timed as CANNY_HIP_STAGE_HYST_CLASSIFY.
+ * Not (yet) covered -- follow-ups: colour input, u8 / bit-map output, the multi-GPU sharder. */
+enum canny_hip_auto_rule { CANNY_HIP_AUTO_MEDIAN = 1, CANNY_HIP_AUTO_QUANTILE = 2 };
+/* Host-only: the selection rule on one 257-bin histogram (tests; callers with histograms of their own).
+ * CANNY_HIP_ERR_INVALID also for an empty histogram. */
+int canny_hip_auto_thresholds_from_histogram(const unsigned int *hist257, int rule, float low, float high, int *min_val,
+                                             int *max_val);
+/* canny_hip_dev_canny with per-frame pairs from a DEVICE array of 2 * n_frames ints; entries outside the domain are
+ * clamped as above.  Same completion contract as canny_hip_dev_canny. */
+int canny_hip_dev_canny_thresholds(canny_hip_ctx *ctx, const unsigned char *d_img, float sigma, const int *d_thresholds,
+                                   int height, int width, int n_frames, short *d_edges);
+/* canny_hip_dev_canny with the pairs chosen per frame on the GPU by `rule`; nothing is read back to the host.
+ * d_thresholds: device array of 2 * n_frames ints receiving the pairs used, or NULL. */
+int canny_hip_dev_canny_auto(canny_hip_ctx *ctx, const unsigned char *d_img, float sigma, int rule, float low, float high,
+                             int height, int width, int n_frames, short *d_edges, int *d_thresholds);
+/* canny_hip_canny_batch with per-frame pairs from a HOST array of 2 * n_frames ints.  Pairs outside the domain are
+ * CANNY_HIP_ERR_INVALID, and then nothing is written. */
+int canny_hip_canny_batch_thresholds(canny_hip_ctx *ctx, const unsigned char *imgs, int n_frames, float sigma,
+                                     const int *thresholds, int height, int width, short *edges);
+/* canny_hip_canny_batch with automatic per-frame pairs.  thresholds: HOST array of 2 * n_frames ints receiving the pairs
+ * used, or NULL. */
+int canny_hip_canny_batch_auto(canny_hip_ctx *ctx, const unsigned char *imgs, int n_frames, float sigma, int rule,
+                               float low, float high, int height, int width, short *edges, int *thresholds);
 
 /* ---- stage entry points on DEVICE buffers (asynchronous on the context's stream) ----------- */
 /* All planes hold n_frames contiguous frames.  Workspace is owned and grown by the context. */
