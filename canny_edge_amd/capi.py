@@ -56,6 +56,8 @@ def layout_of(shape, order: str = "bgr", batch: bool = False) -> int:
 
 # automatic per-frame threshold rules (enum canny_hip_auto_rule)
 AUTO_MEDIAN, AUTO_QUANTILE = 1, 2
+# Context.selftest_sobel_pixel forms (enum canny_hip_pixel_form)
+PIXEL_LDS_TILE, PIXEL_PACKED_I16, PIXEL_F32, PIXEL_F32_FLOOR = 0, 1, 2, 3
 _AUTO_RULES = {"median": AUTO_MEDIAN, "quantile": AUTO_QUANTILE, AUTO_MEDIAN: AUTO_MEDIAN, AUTO_QUANTILE: AUTO_QUANTILE}
 
 
@@ -76,7 +78,7 @@ EXPORTS = (
     "canny_hip_canny_batch_u8", "canny_hip_dev_canny_u8", "canny_hip_canny_multi_gpu", "canny_hip_shard_range", "canny_hip_dev_gaussian", "canny_hip_dev_xy_gradient",
     "canny_hip_dev_sobel", "canny_hip_dev_nms", "canny_hip_dev_sobel_nms", "canny_hip_dev_hysteresis",
     "canny_hip_dev_canny", "canny_hip_dev_canny_stream", "canny_hip_dev_canny_stream_flush", "canny_hip_profile_enable", "canny_hip_profile_reset", "canny_hip_profile_get",
-    "canny_hip_selftest_mag_angle", "canny_hip_selftest_div", "canny_hip_selftest_div_fma",
+    "canny_hip_selftest_mag_angle", "canny_hip_selftest_sobel_pixel", "canny_hip_selftest_div", "canny_hip_selftest_div_fma",
     "canny_hip_selftest_div_fma_table", "canny_hip_canny_multi_gpu_u8", "canny_hip_multi_gpu_set_option",
     "canny_hip_multi_gpu_release", "canny_hip_device_local_cpus", "canny_hip_selftest_cpulist_count",
     "canny_hip_dev_gaussian_u8", "canny_hip_dev_sobel_nms_u8in", "canny_hip_host_register", "canny_hip_host_unregister",
@@ -174,6 +176,7 @@ def load() -> C.CDLL:
         "canny_hip_selftest_expand_bits": ([p, i, i, i, p, i], i),
         "canny_hip_selftest_march_order": ([i, i, p], i),
         "canny_hip_selftest_mag_angle": ([p, i, p, p], i),
+        "canny_hip_selftest_sobel_pixel": ([p, i, i, p, p], i),
         "canny_hip_selftest_div": ([p, f, C.POINTER(C.c_ulonglong), C.POINTER(C.c_float)], i),
         "canny_hip_selftest_div_fma": ([p, f, f, C.POINTER(C.c_ulonglong), C.POINTER(C.c_float)], i),
         "canny_hip_selftest_div_fma_table": ([i, C.POINTER(C.c_float), C.POINTER(C.c_float)], i),
@@ -547,6 +550,16 @@ class Context:
         mags = np.empty((side, side), np.int16)
         bins = np.empty((side, side), np.uint8)
         self._check(self._L.canny_hip_selftest_mag_angle(self._h, lim, _hp(mags), _hp(bins)), "selftest")
+        return mags, bins
+
+    def selftest_sobel_pixel(self, form: int, lim: int = 1020):
+        """Magnitude and bin tables of one Sobel+NMS kernel form's per-pixel helpers (PIXEL_* constants), indexed
+        [gy + lim, gx + lim] like selftest_mag_angle."""
+        side = 2 * lim + 1
+        mags = np.empty((side, side), np.int16)
+        bins = np.empty((side, side), np.uint8)
+        self._check(self._L.canny_hip_selftest_sobel_pixel(self._h, form, lim, _hp(mags), _hp(bins)),
+                    "selftest_sobel_pixel")
         return mags, bins
 
     def selftest_div(self, divisor: float) -> Tuple[int, float]:

@@ -2474,6 +2474,26 @@ int canny_hip_selftest_mag_angle(canny_hip_ctx *ctx, int lim, short *magnitudes,
     return d2h_sync(ctx, bins, ctx->io[1].p, total);
 }
 
+int canny_hip_selftest_sobel_pixel(canny_hip_ctx *ctx, int form, int lim, short *magnitudes, unsigned char *bins)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!magnitudes || !bins || lim < 0 || lim > 1020 || form < CANNY_HIP_PIXEL_LDS_TILE ||
+        form > CANNY_HIP_PIXEL_F32_FLOOR)
+        return CANNY_HIP_ERR_INVALID;
+    size_t total = (size_t)(2 * lim + 1) * (2 * lim + 1);
+    HIP_TRY(ctx, ctx->io[0].ensure(total * 2));
+    HIP_TRY(ctx, ctx->io[1].ensure(total));
+    int16_t *d_mags = (int16_t *)ctx->io[0].p;
+    uint8_t *d_bins = (uint8_t *)ctx->io[1].p;
+    if (form == CANNY_HIP_PIXEL_LDS_TILE)
+        HIP_TRY(ctx, launch_selftest_mag_angle(lim, d_mags, d_bins, ctx->stream));
+    else
+        HIP_TRY(ctx, launch_selftest_sobel_pixel(form, lim, d_mags, d_bins, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(magnitudes, d_mags, total * 2, hipMemcpyDeviceToHost, ctx->stream));
+    return d2h_sync(ctx, bins, d_bins, total);
+}
+
 static int selftest_div_common(canny_hip_ctx *ctx, float divisor, int use_fma, float c,
                                unsigned long long *mismatches, float *largest_mismatching_dividend)
 {

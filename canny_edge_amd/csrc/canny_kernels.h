@@ -308,6 +308,8 @@ hipError_t launch_probe_copy(const void *src, void *dst, size_t nbytes, hipStrea
 
 // ---- self-test ------------------------------------------------------------------------------
 hipError_t launch_selftest_mag_angle(int lim, int16_t *mags, uint8_t *bins, hipStream_t stream);
+// The marching kernels' per-pixel helpers (canny_sobel_nms_march.hip); form as canny_hip_selftest_sobel_pixel, 1..3.
+hipError_t launch_selftest_sobel_pixel(int form, int lim, int16_t *mags, uint8_t *bins, hipStream_t stream);
 // Counts floats a (bit patterns first_bits..last_bits) for which the Gaussian's reciprocal-based
 // division a/b differs from the IEEE divide; *d_mismatches must be zero beforehand.
 // use_fma != 0 checks the one-instruction form fma(a, c, a) instead of the 5-op reciprocal division.

@@ -176,6 +176,34 @@ __device__ __forceinline__ void store_row(int16_t *dst, const uint32_t (&outp)[N
     __builtin_memcpy(dst, outp, 4 * NP);
 }
 
+// ---- per-pixel arithmetic of march_strip (also run over every (gx, gy) by canny_hip_selftest_sobel_pixel) ----------
+// magnitude floor(sqrt(n)) (see magnitude_d8); Ah = gx^2 + 1/2 and nh = gx^2 + gy^2 + 1/2 are returned for the bins.
+// All exact in f32 (integers and halves below 2^24).
+__device__ __forceinline__ int pk_pixel_mag(float fx, float fy, float &Ah, float &nh)
+{
+    Ah = __fmaf_rn(fx, fx, 0.5f);
+    nh = __fmaf_rn(fy, fy, Ah);
+    return (int)__builtin_amdgcn_sqrtf(nh);
+}
+// bin discriminants P = gx*gy, Q = Ah - nh/2 = (gx^2-gy^2)/2 + 1/4
+__device__ __forceinline__ void pk_pixel_disc(float fx, float fy, float Ah, float nh, float &P, float &Q)
+{
+    P = __fmul_rn(fx, fy);
+    Q = __fmaf_rn(nh, -0.5f, Ah);
+}
+// The neighbour maximum NMS compares against, picked by the bin.  With X = gx^2-gy^2 and Y = 2 gx gy (the doubled
+// angle) the bins are the quadrants of (X+Y, X-Y):  0: both >= 0,  90: both < 0,  45: X+Y >= 0 > X-Y,  135: the rest.
+// P and X/2 are multiples of 1/2 and Q = X/2 + 1/4, so  X-Y >= 0  <=>  P <= Q  and  X+Y >= 0  <=>  P > -Q  exactly
+// (same rule as angle_bin_d8).
+__device__ __forceinline__ int pk_nms_select(float P, float Q, int n0, int n45, int n90, int n135)
+{
+    const bool v_ge0 = P <= Q; // X - Y >= 0
+    const bool u_ge0 = P > -Q; // X + Y >= 0
+    const int na = v_ge0 ? n0 : n45;
+    const int nb = v_ge0 ? n135 : n90;
+    return u_ge0 ? na : nb;
+}
+
 template <bool COL_EDGE, bool ROW_EDGE, bool PLANES, int NP, bool LDS_PLANES, bool IN_U8 = false>
 __device__ __forceinline__ void march_strip(const StripJob &jb, uint8_t *stage_mem, const uint4 *edge_lut = nullptr)
 {
@@ -402,14 +430,10 @@ __device__ __forceinline__ void march_strip(const StripJob &jb, uint8_t *stage_m
                     const int e = 2 * i + hf;
                     const float fx = hf ? (float)((int)gx >> 16) : (float)(int)(short)(gx & 0xffffu);
                     const float fy = hf ? (float)((int)gy[i] >> 16) : (float)(int)(short)(gy[i] & 0xffffu);
-                    // all exact in f32 (integers and halves below 2^24):
-                    //   Ah = gx^2 + 1/2,  nh = gx^2 + gy^2 + 1/2,  P = gx*gy,  Q = Ah - nh/2 = (gx^2-gy^2)/2 + 1/4
-                    const float Ah = __fmaf_rn(fx, fx, 0.5f);
-                    const float nh = __fmaf_rn(fy, fy, Ah);
-                    const int mag = (int)__builtin_amdgcn_sqrtf(nh); // floor(sqrt(n)), see magnitude_d8
+                    float Ah, nh;
+                    const int mag = pk_pixel_mag(fx, fy, Ah, nh);
                     M[m2][e + 1] = PLANES ? max_u16(mag, skip) : mag;
-                    cP[m2][e] = __fmul_rn(fx, fy);
-                    cQ[m2][e] = __fmaf_rn(nh, -0.5f, Ah);
+                    pk_pixel_disc(fx, fy, Ah, nh, cP[m2][e], cQ[m2][e]);
                 }
             }
             if (COL_EDGE) { // columns outside the image never win a comparison
@@ -441,16 +465,8 @@ __device__ __forceinline__ void march_strip(const StripJob &jb, uint8_t *stage_m
                 const int n90 = nmax(M[m0][c], M[m2][c]);
                 const int n45 = nmax(M[m0][c + 1], M[m2][c - 1]);  // up-right, down-left
                 const int n135 = nmax(M[m0][c - 1], M[m2][c + 1]); // up-left, down-right
-                // Bin from two sign tests.  With X = gx^2-gy^2 and Y = 2 gx gy (the doubled angle) the bins are
-                // the quadrants of (X+Y, X-Y):  0: both >= 0,  90: both < 0,  45: X+Y >= 0 > X-Y,  135: the rest.
-                // P and X/2 are multiples of 1/2 and Q = X/2 + 1/4, so  X-Y >= 0  <=>  P <= Q  and
-                // X+Y >= 0  <=>  P > -Q  exactly (same rule as angle_bin_d8, checked exhaustively on the device).
-                const float P = cP[m1][e], Q = cQ[m1][e];
-                const bool v_ge0 = P <= Q;  // X - Y >= 0
-                const bool u_ge0 = P > -Q;  // X + Y >= 0
-                const int na = v_ge0 ? n0 : n45;
-                const int nb = v_ge0 ? n135 : n90;
-                const int nsel = u_ge0 ? na : nb;
+                // bin from two sign tests (pk_nms_select)
+                const int nsel = pk_nms_select(cP[m1][e], cQ[m1][e], n0, n45, n90, n135);
                 if (PLANES) {
                     // cbits: survived NMS and mc >= min_val;  sbits: mc >= max(min_val, max_val), ANDed with cbits below
                     push_gt2(cbits, sbits, mc, nsel, jb.hi1);
@@ -582,6 +598,51 @@ __device__ __forceinline__ int bfi(int m, int a, int b)
 __device__ __forceinline__ unsigned push_sign(unsigned acc, int d)
 {
     return __builtin_amdgcn_alignbit(acc, (unsigned)d, 31);
+}
+
+// ---- per-pixel arithmetic of fmarch_strip (also run over every (gx, gy) by canny_hip_selftest_sobel_pixel) ---------
+// All exact in f32 (integers and quarters below 2^24):  Ah = gx^2 + 1/2,  nh = gx^2 + gy^2 + 1/2.
+// Magnitude word: the bits of 2^23 + floor(sqrt(n)); its low 16 bits are the magnitude, the rest is the exponent.
+__device__ __forceinline__ int f_pixel_mag_word(float gx, float gy, float &Ah, float &nh)
+{
+    Ah = __fmaf_rn(gx, gx, 0.5f);
+    nh = __fmaf_rn(gy, gy, Ah);
+    const float mb = __fadd_rn(__builtin_amdgcn_sqrtf(nh), 8388607.5f); // 2^23 + floor(sqrt(n))
+    return __float_as_int(mb);
+}
+// The stored magnitude: raised to the threshold floor `skip` by the PLANES kernels (v_max_u16 drops the exponent
+// bits in the same step), masked to the low half by the plain ones.
+template <bool PLANES>
+__device__ __forceinline__ int f_pixel_mag_store(int m, int skip)
+{
+    return PLANES ? max_u16(m, skip) : (m & 0xffff);
+}
+// The signs of Q - P and Q + P, with Q = (gx^2 - gy^2)/2 + 1/4 and P = gx gy (never zero: Q has a fractional part
+// of 1/4): Q - P < 0  <=>  not (X - Y >= 0),  Q + P < 0  <=>  not (X + Y >= 0).
+__device__ __forceinline__ void f_pixel_bin_signs(float gx, float gy, float Ah, float nh, float &qm, float &qp)
+{
+    const float Q = __fmaf_rn(nh, -0.5f, Ah);
+    qm = __fmaf_rn(-gx, gy, Q);
+    qp = __fmaf_rn(gx, gy, Q);
+}
+// one carrier per pixel: byte 3 = sign of Q - P, bytes 0-2 = sign of Q + P, eight copies each
+// (v_perm_b32 selectors 11 / 9 replicate bit 31 of the first / second source)
+__device__ __forceinline__ int f_pixel_carrier(float qm, float qp)
+{
+    return (int)__builtin_amdgcn_perm(__float_as_uint(qm), __float_as_uint(qp), 0x0b090909u);
+}
+// The neighbour maximum of the bin (see pk_nms_select): mv / mu are all ones where the test FAILS (mu: at least in
+// the 16 low bits, which is as wide as the selected values are).
+__device__ __forceinline__ int f_nms_select_masks(int mv, int mu, int n0, int n45, int n90, int n135)
+{
+    const int na = bfi(mv, n45, n0);  // X - Y >= 0 ? n0 : n45
+    const int nb = bfi(mv, n90, n135); // X - Y >= 0 ? n135 : n90
+    return bfi(mu, nb, na);            // X + Y >= 0 ? na : nb
+}
+// ... from the packed carrier: its sign is the mask of Q - P, its low 16 bits are the mask of Q + P
+__device__ __forceinline__ int f_nms_select(int carrier, int n0, int n45, int n90, int n135)
+{
+    return f_nms_select_masks(carrier >> 31, carrier, n0, n45, n90, n135);
 }
 
 template <bool COL_EDGE, bool ROW_EDGE, bool PLANES, bool LDS_PLANES, bool IN_U8>
@@ -802,21 +863,14 @@ __device__ __forceinline__ void fmarch_strip(const StripJob &jb, uint8_t *stage_
                     gx = __fadd_rn(gx, __int_as_float(__float_as_int(a[e]) & (inside(e) ^ inside(e + 1))));
                 }
                 const float gy = __fadd_rn(__fmaf_rn(2.0f, b[e], bl), br);
-                // all exact in f32 (integers and quarters below 2^24):
-                //   Ah = gx^2 + 1/2,  nh = gx^2 + gy^2 + 1/2,  Q = (gx^2 - gy^2)/2 + 1/4,  P = gx gy
-                const float Ah = __fmaf_rn(gx, gx, 0.5f);
-                const float nh = __fmaf_rn(gy, gy, Ah);
-                const float mb = __fadd_rn(__builtin_amdgcn_sqrtf(nh), 8388607.5f); // 2^23 + floor(sqrt(n))
-                int m = __float_as_int(mb);
+                float Ah, nh;
+                int m = f_pixel_mag_word(gx, gy, Ah, nh);
                 if (COL_EDGE) m &= inside(e); // out-of-image magnitudes become the floor
-                M[m2][e + 1] = PLANES ? max_u16(m, skip) : (m & 0xffff);
-                const float Q = __fmaf_rn(nh, -0.5f, Ah);
-                const float qm = __fmaf_rn(-gx, gy, Q); // Q - P < 0  <=>  not (X - Y >= 0)
-                const float qp = __fmaf_rn(gx, gy, Q);  // Q + P < 0  <=>  not (X + Y >= 0)
+                M[m2][e + 1] = f_pixel_mag_store<PLANES>(m, skip);
+                float qm, qp;
+                f_pixel_bin_signs(gx, gy, Ah, nh, qm, qp);
 #if FLT_CARRIERS == 1
-                // one carrier per pixel: byte 3 = sign of Q - P, bytes 0-2 = sign of Q + P, eight copies each
-                // (v_perm_b32 selectors 11 / 9 replicate bit 31 of the first / second source)
-                cz[m2][e] = (int)__builtin_amdgcn_perm(__float_as_uint(qm), __float_as_uint(qp), 0x0b090909u);
+                cz[m2][e] = f_pixel_carrier(qm, qp);
                 // Materialise the carrier HERE: its only use is in the next row's step, and the optimiser otherwise
                 // sinks its computation behind that row's NMS branch and keeps gx, gy, Ah and nh alive instead.
                 asm volatile("" : "+v"(cz[m2][e]));
@@ -850,17 +904,11 @@ __device__ __forceinline__ void fmarch_strip(const StripJob &jb, uint8_t *stage_
                 const int n90 = max_u16(M[m0][c], M[m2][c]);
                 const int n45 = max_u16(M[m0][c + 1], M[m2][c - 1]);  // up-right, down-left
                 const int n135 = max_u16(M[m0][c - 1], M[m2][c + 1]); // up-left, down-right
-                // bins are the quadrants of (X + Y, X - Y), see march_strip: 0: both >= 0, 90: both < 0,
-                // 45: X + Y >= 0 > X - Y, 135: the rest.  mv / mu are all ones where the test FAILS.
-                const int mv = cz[m1][e] >> 31; // all 32 bits
 #if FLT_CARRIERS == 1
-                const int mu = cz[m1][e];       // its low 16 bits are the mask; the selected values are 16 bits wide
+                const int nsel = f_nms_select(cz[m1][e], n0, n45, n90, n135);
 #else
-                const int mu = cy[m1][e] >> 31;
+                const int nsel = f_nms_select_masks(cz[m1][e] >> 31, cy[m1][e] >> 31, n0, n45, n90, n135);
 #endif
-                const int na = bfi(mv, n45, n0);   // X - Y >= 0 ? n0 : n45
-                const int nb = bfi(mv, n90, n135); // X - Y >= 0 ? n135 : n90
-                const int nsel = bfi(mu, nb, na);  // X + Y >= 0 ? na : nb
                 const int dc = nsel - mc;          // < 0  <=>  mc > nsel
                 if (PLANES) {
                     cacc = push_sign(cacc, dc);
@@ -943,7 +991,49 @@ __device__ __forceinline__ void fmarch_strip(const StripJob &jb, uint8_t *stage_
     if (STAGE) stage_flush_segment();
 }
 
+// ---- self-test: the marching kernels' per-pixel helpers over every (gx, gy) in [-lim, lim]^2 ---------------------
+// form 1: packed-i16 (march_strip), 2: f32 with the plain store, 3: f32 with the PLANES floor at skip = 0.  The bin
+// is what the real select helper returns with the neighbour maxima set to the bin codes.  A magnitude whose upper
+// half is not zero is reported as -1: the kernels compare whole words.
+__global__ __launch_bounds__(256) void selftest_sobel_pixel_kernel(int form, int lim, int16_t *__restrict__ mags,
+                                                                   uint8_t *__restrict__ bins)
+{
+    const int side = 2 * lim + 1;
+    const size_t total = (size_t)side * side;
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    int skip = 0;
+    asm volatile("" : "+v"(skip)); // a VGPR, as in the kernels
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
+        const float gx = (float)((int)(i % side) - lim), gy = (float)((int)(i / side) - lim);
+        float Ah, nh;
+        int mag, bin;
+        if (form == 1) {
+            mag = pk_pixel_mag(gx, gy, Ah, nh);
+            float P, Q;
+            pk_pixel_disc(gx, gy, Ah, nh, P, Q);
+            bin = pk_nms_select(P, Q, 0, 45, 90, 135);
+        } else {
+            const int m = f_pixel_mag_word(gx, gy, Ah, nh);
+            mag = form == 3 ? f_pixel_mag_store<true>(m, skip) : f_pixel_mag_store<false>(m, skip);
+            float qm, qp;
+            f_pixel_bin_signs(gx, gy, Ah, nh, qm, qp);
+            bin = f_nms_select(f_pixel_carrier(qm, qp), 0, 45, 90, 135);
+        }
+        mags[i] = (int16_t)((mag >> 16) ? -1 : mag);
+        bins[i] = (uint8_t)bin;
+    }
+}
+
 } // namespace
+
+hipError_t launch_selftest_sobel_pixel(int form, int lim, int16_t *mags, uint8_t *bins, hipStream_t stream)
+{
+    if (form < 1 || form > 3 || lim < 0 || lim > 1020) return hipErrorInvalidValue;
+    const size_t total = (size_t)(2 * lim + 1) * (2 * lim + 1);
+    hipLaunchKernelGGL(selftest_sobel_pixel_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, form,
+                       lim, mags, bins);
+    return hipGetLastError();
+}
 
 struct PlaneArgs { // PLANES instantiation only
     uint8_t *conn, *strong;

@@ -52,7 +52,8 @@
 extern "C" {
 #endif
 
-#define CANNY_HIP_VERSION 400        /* 0.4.0: + per-frame thresholds, explicit or chosen on the GPU (median / quantile) */
+#define CANNY_HIP_VERSION 401        /* 0.4.1: + canny_hip_selftest_sobel_pixel */
+/* 0.4.0: + per-frame thresholds, explicit or chosen on the GPU (median / quantile) */
 /* 0.3.0: + colour frame input (BGR / RGB / BGRA / RGBA -> gray on the GPU) */
 /* 0.2.0: + batch u8 / bit maps, multi-GPU options, host_register, async dev_canny */
 #define CANNY_HIP_MAX_WINDOW 129     /* largest Gaussian window (sigma <= 21.33) */
@@ -413,6 +414,16 @@ int canny_hip_profile_get(canny_hip_ctx *ctx, int stage, double *total_ms, long 
 /* Runs the DEVICE magnitude / angle-bin functions over every (gx,gy) in [-lim,lim]^2 and writes
  * tables indexed [gy+lim][gx+lim] to host memory. */
 int canny_hip_selftest_mag_angle(canny_hip_ctx *ctx, int lim, short *magnitudes, unsigned char *bins);
+/* The same tables from the per-pixel arithmetic of each Sobel+NMS kernel form, run by the kernels' own device helpers.
+ * The bin is what the kernel's neighbour select returns when the four neighbour maxima are the codes 0, 45, 90, 135.
+ * A magnitude word whose upper 16 bits are not zero is reported as -1.  lim in [0, 1020]. */
+enum canny_hip_pixel_form {
+    CANNY_HIP_PIXEL_LDS_TILE = 0,    /* the LDS-tiled kernel (magnitude_d8 / angle_bin_d8) */
+    CANNY_HIP_PIXEL_PACKED_I16 = 1,  /* the packed-i16 marching kernel */
+    CANNY_HIP_PIXEL_F32 = 2,         /* the f32 marching kernel, plain magnitude store */
+    CANNY_HIP_PIXEL_F32_FLOOR = 3    /* the f32 marching kernel, PLANES threshold floor at 0 */
+};
+int canny_hip_selftest_sobel_pixel(canny_hip_ctx *ctx, int form, int lim, short *magnitudes, unsigned char *bins);
 /* Measurement aid (bench.py): a plain device copy of nbytes (a multiple of 16; both pointers 16-byte aligned), launched
  * `launches` times on the context's stream; *avg_ms receives the average device time of one launch (HIP events attached
  * to the dispatch).  It calibrates what a 1:1 read/write stream reaches on THIS device beside the Sobel+NMS pass, whose
