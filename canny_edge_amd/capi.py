@@ -31,6 +31,8 @@ STAGE_GAUSSIAN, STAGE_SOBEL_NMS, STAGE_HYST_CLASSIFY, STAGE_HYST_PROPAGATE, STAG
     STAGE_SOBEL, STAGE_NMS, STAGE_XY_GRADIENT, STAGE_TO_GRAY = range(9)
 STAGE_NAMES = ("gaussian", "sobel_nms", "hyst_classify", "hyst_propagate", "hyst_finalize", "sobel", "nms",
                "xy_gradient", "to_gray")
+# stage of what is derived from a finished map (CANNY_HIP_STAGE_COMPACT; not one of the CANNY_HIP_STAGE_COUNT stages above)
+STAGE_COMPACT = 9
 
 # colour frame layouts (enum canny_hip_layout): interleaved, 1 byte per channel, no row padding
 LAYOUT_GRAY8, LAYOUT_BGR8, LAYOUT_RGB8, LAYOUT_BGRA8, LAYOUT_RGBA8 = range(5)
@@ -88,6 +90,8 @@ EXPORTS = (
     "canny_hip_dev_canny_color", "canny_hip_canny_color", "canny_hip_canny_batch_color", "canny_hip_canny_batch_color_u8",
     "canny_hip_canny_batch_color_bits", "canny_hip_auto_thresholds_from_histogram", "canny_hip_dev_canny_thresholds",
     "canny_hip_dev_canny_auto", "canny_hip_canny_batch_thresholds", "canny_hip_canny_batch_auto",
+    "canny_hip_dev_canny_points", "canny_hip_dev_points_from_bits", "canny_hip_canny_points",
+    "canny_hip_points_from_bits",
 )
 
 _lib: Optional[C.CDLL] = None
@@ -193,6 +197,10 @@ def load() -> C.CDLL:
         "canny_hip_dev_canny_auto": ([p, p, f, i, f, f, i, i, i, p, p], i),
         "canny_hip_canny_batch_thresholds": ([p, p, i, f, p, i, i, p], i),
         "canny_hip_canny_batch_auto": ([p, p, i, f, i, f, f, i, i, p, p], i),
+        "canny_hip_dev_canny_points": ([p, p, f, i, i, i, i, i, p, p, C.c_ulonglong, p], i),
+        "canny_hip_dev_points_from_bits": ([p, p, i, i, i, p, C.c_ulonglong, p], i),
+        "canny_hip_canny_points": ([p, p, i, f, i, i, i, i, p, C.c_ulonglong, p], i),
+        "canny_hip_points_from_bits": ([p, i, i, p, C.c_ulonglong, C.POINTER(C.c_ulonglong)], i),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -224,6 +232,33 @@ def expand_bits(bits: np.ndarray, height: int, width: int, u8: bool = False, thr
     if st:
         raise CannyHipError(st, "selftest_expand_bits")
     return out
+
+
+def points_from_bits(bits, height: int, width: int, capacity: Optional[int] = None) -> np.ndarray:
+    """Host-only: one packed bit map (rows MSB-first, padded to bytes: numpy.packbits(mask, axis=-1)) -> the ascending
+    indices r * width + c of its set pixels, uint32 -- np.flatnonzero(mask).  Padding bits are ignored.  With a capacity
+    the result is the prefix that fits, and the true count is returned too: (points, count)."""
+    b = np.ascontiguousarray(bits, dtype=np.uint8)
+    if b.size != height * ((width + 7) // 8):
+        raise ValueError(f"expected {height} rows of {(width + 7) // 8} bytes, got {b.size} bytes")
+    n = C.c_ulonglong(0)
+    L = load()
+    if capacity is None:
+        st = L.canny_hip_points_from_bits(_hp(b), height, width, None, 0, C.byref(n))
+        if st:
+            raise CannyHipError(st, "points_from_bits")
+    cap = n.value if capacity is None else int(capacity)
+    pts = np.empty(cap, np.uint32)
+    st = L.canny_hip_points_from_bits(_hp(b), height, width, _hp(pts) if cap else None, cap, C.byref(n))
+    if st:
+        raise CannyHipError(st, "points_from_bits")
+    return pts if capacity is None else (pts[:min(cap, n.value)], n.value)
+
+
+def points_to_rc(points, width: int) -> Tuple[np.ndarray, np.ndarray]:
+    """Pixel indices r * width + c -> (rows, cols), int64 (what np.nonzero(mask) returns for the same map)."""
+    p = np.asarray(points).astype(np.int64)
+    return p // int(width), p % int(width)
 
 
 def auto_thresholds_from_histogram(hist, rule="median", low: float = 0.67, high: float = 1.33) -> Tuple[int, int]:
@@ -510,6 +545,44 @@ class Context:
         self._check(self._L.canny_hip_dev_canny_auto(self._h, C.c_void_p(d_img), sigma, _rule(rule), low, high, h, w,
                                                      n, C.c_void_p(d_edges), C.c_void_p(d_thresholds or None)),
                     "dev_canny_auto")
+
+    # ---- edge point lists (CSR of pixel indices r * width + c) ----------------------------
+    def canny_points(self, imgs, sigma: float, min_val: int, max_val: int, capacity: Optional[int] = None):
+        """canny() returning the edge pixels as index lists: imgs (H, W) or (N, H, W) uint8 ->
+        (points uint32 [total], offsets uint64 [N + 1]); frame f's pixels are points[offsets[f]:offsets[f + 1]], ascending
+        -- np.flatnonzero(canny(frame f)).  capacity=None sizes the buffer itself and never returns a truncated list (a
+        batch denser than one pixel in eight runs twice); with a capacity, points holds the first
+        min(offsets[-1], capacity) entries and offsets still holds the true counts."""
+        a = np.ascontiguousarray(imgs, dtype=np.uint8)
+        if a.ndim == 2:
+            a = a[None]
+        if a.ndim != 3:
+            raise ValueError("expected uint8 [H, W] or [n_frames, H, W]")
+        n, h, w = a.shape
+        offsets = np.zeros(n + 1, np.uint64)
+        cap = max(1024, a.size // 8) if capacity is None else int(capacity)
+        while True:
+            pts = np.empty(cap, np.uint32)
+            self._check(self._L.canny_hip_canny_points(self._h, _hp(a), n, sigma, min_val, max_val, h, w,
+                                                       _hp(pts) if cap else None, cap, _hp(offsets)), "canny_points")
+            total = int(offsets[-1])
+            if capacity is not None or total <= cap:
+                return pts[:min(total, cap)], offsets
+            cap = total
+
+    def dev_canny_points(self, d_img: int, sigma: float, min_val: int, max_val: int, h: int, w: int, n: int,
+                         d_points: int, capacity: int, d_offsets: int, d_edges: int = 0):
+        """dev_canny, then its map compacted to index lists on the same stream: d_points (capacity uint32, device; 0 with
+        capacity 0 = counts only), d_offsets (n + 1 uint64, device), d_edges (the s16 map, device) or 0."""
+        self._check(self._L.canny_hip_dev_canny_points(self._h, C.c_void_p(d_img), sigma, min_val, max_val, h, w, n,
+                                                       C.c_void_p(d_edges or None), C.c_void_p(d_points or None),
+                                                       capacity, C.c_void_p(d_offsets)), "dev_canny_points")
+
+    def dev_points_from_bits(self, d_bits: int, h: int, w: int, n: int, d_points: int, capacity: int, d_offsets: int):
+        """The compaction alone on device bit maps (layout of dev_canny_bits, any byte alignment)."""
+        self._check(self._L.canny_hip_dev_points_from_bits(self._h, C.c_void_p(d_bits), h, w, n,
+                                                           C.c_void_p(d_points or None), capacity,
+                                                           C.c_void_p(d_offsets)), "dev_points_from_bits")
 
     # ---- colour frames (interleaved BGR / RGB / BGRA / RGBA; the rule is the "gray_rule" option) --------------
     def to_gray(self, frame, order: str = "bgr") -> np.ndarray:

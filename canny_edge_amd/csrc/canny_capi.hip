@@ -373,6 +373,7 @@ struct canny_hip_ctx {
     DevBuf gray;      // colour input: the converted plane when the Gaussian cannot convert itself
     DevBuf hist;      // automatic thresholds: per-frame histograms (n_frames x 257 u32)
     DevBuf thr;       // automatic thresholds: the pairs when the caller does not ask for them
+    DevBuf points;    // edge point lists: per-frame totals (n_frames u64), then per-row counts / prefixes (u32)
     DevBuf plane_s, plane_c, stamps, flags; // hysteresis bit-planes / scheduling words
     DevBuf io[4];     // staging for the host-pointer stage functions
     unsigned *host_flags = nullptr;     // pinned + mapped, 4 words per lane: last_change, domain, sequence number, spare
@@ -395,11 +396,11 @@ struct canny_hip_ctx {
     bool prof = false;
     unsigned prof_mask = ~0u; // stages whose launches get an event pair (each pair costs a few us of stream time)
     unsigned prof_every = 1;  // ... and only every prof_every-th launch group of a stage gets one
-    unsigned prof_seen[CANNY_HIP_STAGE_COUNT] = {0};
-    std::vector<EventPair> pending[CANNY_HIP_STAGE_COUNT];
+    unsigned prof_seen[CANNY_HIP_STAGE_END] = {0};
+    std::vector<EventPair> pending[CANNY_HIP_STAGE_END];
     std::vector<EventPair> pool;
-    double total_ms[CANNY_HIP_STAGE_COUNT] = {0};
-    long launches[CANNY_HIP_STAGE_COUNT] = {0};
+    double total_ms[CANNY_HIP_STAGE_END] = {0};
+    long launches[CANNY_HIP_STAGE_END] = {0};
 };
 
 // One batch pipeline: three streams and a ring of chunk slots.  Chunk j of the pipeline lives in slot j % kSlots:
@@ -1062,6 +1063,56 @@ int d2h_sync(canny_hip_ctx *ctx, void *dst, const void *src, size_t bytes)
     return CANNY_HIP_OK;
 }
 
+// ---- edge point lists (canny_points.hip) ----------------------------------
+// The source is the context's strong plane (strong != nullptr: hysteresis has converged in stream order) or a packed
+// bit map.  count + scan: d_offsets[0..n] receives the CSR offsets; the per-row prefixes stay in ctx->points.
+int dev_points_count(canny_hip_ctx *ctx, const uint64_t *strong, const uint8_t *bits, const HystGeom &g,
+                     unsigned long long *d_offsets)
+{
+    const size_t rows = (size_t)g.n_frames * g.height;
+    HIP_TRY(ctx, ctx->points.ensure(g.n_frames * sizeof(unsigned long long) + rows * sizeof(uint32_t)));
+    unsigned long long *totals = (unsigned long long *)ctx->points.p;
+    uint32_t *row_words = (uint32_t *)(totals + g.n_frames);
+    StageTimer tm(ctx, CANNY_HIP_STAGE_COMPACT);
+    HIP_TRY(ctx, launch_points_count(strong, bits, g, row_words, ctx->stream));
+    HIP_TRY(ctx, launch_points_scan(row_words, totals, d_offsets, g.height, g.n_frames, ctx->stream));
+    return CANNY_HIP_OK;
+}
+
+// scatter, behind dev_points_count of the same source on the same stream
+int dev_points_scatter(canny_hip_ctx *ctx, const uint64_t *strong, const uint8_t *bits, const HystGeom &g,
+                       const unsigned long long *d_offsets, unsigned *d_points, unsigned long long capacity)
+{
+    if (!capacity) return CANNY_HIP_OK;
+    const uint32_t *row_words = (const uint32_t *)((const unsigned long long *)ctx->points.p + g.n_frames);
+    StageTimer tm(ctx, CANNY_HIP_STAGE_COMPACT);
+    HIP_TRY(ctx, launch_points_scatter(strong, bits, g, row_words, d_offsets, d_points, capacity, ctx->stream));
+    return CANNY_HIP_OK;
+}
+
+// dev_canny (unchanged, into d_edges or the edges16 workspace), then count + scan of its map.  *strong_out receives the
+// source for the scatter: the strong plane, or null when the map is empty by rule (max_val > 255: the reference zeroes
+// every reached pixel, src/utils.cpp:336-340, although strong bits are set) and the offsets have been zeroed.
+// Every route through dev_canny leaves the converged strong plane of the WHOLE batch in ctx->plane_s, in stream order
+// (DESIGN.md section 12 goes through them), so the s16 map is never re-read.
+int dev_canny_points_count(canny_hip_ctx *ctx, const unsigned char *d_img, float sigma, int lo, int hi, int h, int w,
+                           int n, short *d_edges, unsigned long long *d_offsets, const uint64_t **strong_out)
+{
+    int rc;
+    if (!d_edges) {
+        HIP_TRY(ctx, ctx->edges16.ensure(npx(h, w, n) * sizeof(short)));
+        d_edges = (short *)ctx->edges16.p;
+    }
+    if ((rc = dev_canny(ctx, d_img, sigma, lo, hi, h, w, n, d_edges))) return rc;
+    if (hi > 255) {
+        *strong_out = nullptr;
+        HIP_TRY(ctx, hipMemsetAsync(d_offsets, 0, ((size_t)n + 1) * sizeof(unsigned long long), ctx->stream));
+        return CANNY_HIP_OK;
+    }
+    *strong_out = (const uint64_t *)ctx->plane_s.p;
+    return dev_points_count(ctx, *strong_out, nullptr, make_hyst_geom(h, w, n), d_offsets);
+}
+
 void destroy_batch_pipe(canny_hip_ctx::BatchPipe *w)
 {
     if (!w) return;
@@ -1198,6 +1249,7 @@ void canny_hip_ctx_destroy(canny_hip_ctx *ctx)
     ctx->edges16.release();
     ctx->hist.release();
     ctx->thr.release();
+    ctx->points.release();
     ctx->stamps.release();
     ctx->flags.release();
     for (auto &b : ctx->io) b.release();
@@ -2339,6 +2391,93 @@ int canny_hip_dev_canny_bits(canny_hip_ctx *ctx, const unsigned char *d_img, flo
     return CANNY_HIP_OK;
 }
 
+// ---- edge point lists ---------------------------------------------------------------------------------
+int canny_hip_dev_canny_points(canny_hip_ctx *ctx, const unsigned char *d_img, float sigma, int min_val, int max_val,
+                               int height, int width, int n_frames, short *d_edges, unsigned int *d_points,
+                               unsigned long long capacity, unsigned long long *d_offsets)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!d_img || !d_offsets || (!d_points && capacity)) return CANNY_HIP_ERR_INVALID;
+    if ((rc = check_dims(height, width, n_frames))) return rc;
+    const uint64_t *strong = nullptr;
+    if ((rc = dev_canny_points_count(ctx, d_img, sigma, min_val, max_val, height, width, n_frames, d_edges, d_offsets,
+                                     &strong)))
+        return rc;
+    if (!strong) return CANNY_HIP_OK;
+    return dev_points_scatter(ctx, strong, nullptr, make_hyst_geom(height, width, n_frames), d_offsets, d_points,
+                              capacity);
+}
+
+int canny_hip_dev_points_from_bits(canny_hip_ctx *ctx, const unsigned char *d_bits, int height, int width, int n_frames,
+                                   unsigned int *d_points, unsigned long long capacity, unsigned long long *d_offsets)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!d_bits || !d_offsets || (!d_points && capacity)) return CANNY_HIP_ERR_INVALID;
+    if ((rc = check_dims(height, width, n_frames)) || (rc = finish_pending(ctx))) return rc;
+    const HystGeom g = make_hyst_geom(height, width, n_frames);
+    if ((rc = dev_points_count(ctx, nullptr, d_bits, g, d_offsets))) return rc;
+    return dev_points_scatter(ctx, nullptr, d_bits, g, d_offsets, d_points, capacity);
+}
+
+int canny_hip_canny_points(canny_hip_ctx *ctx, const unsigned char *imgs, int n_frames, float sigma, int min_val,
+                           int max_val, int height, int width, unsigned int *points, unsigned long long capacity,
+                           unsigned long long *offsets)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!imgs || !offsets || (!points && capacity)) return CANNY_HIP_ERR_INVALID;
+    if ((rc = check_dims(height, width, n_frames))) return rc;
+    const size_t off_bytes = ((size_t)n_frames + 1) * sizeof(unsigned long long);
+    if ((rc = h2d(ctx, ctx->io[0], imgs, npx(height, width, n_frames)))) return rc;
+    HIP_TRY(ctx, ctx->io[1].ensure(off_bytes));
+    unsigned long long *d_offsets = (unsigned long long *)ctx->io[1].p;
+    const uint64_t *strong = nullptr;
+    if ((rc = dev_canny_points_count(ctx, (const unsigned char *)ctx->io[0].p, sigma, min_val, max_val, height, width,
+                                     n_frames, nullptr, d_offsets, &strong)))
+        return rc;
+    // the offsets come down first: they say how many points there are to scatter and to download
+    std::vector<unsigned long long> off((size_t)n_frames + 1);
+    if ((rc = d2h_sync(ctx, off.data(), d_offsets, off_bytes))) return rc;
+    const unsigned long long n_pts = std::min(off[n_frames], capacity);
+    if (n_pts) {
+        HIP_TRY(ctx, ctx->io[2].ensure((size_t)n_pts * sizeof(unsigned)));
+        if ((rc = dev_points_scatter(ctx, strong, nullptr, make_hyst_geom(height, width, n_frames), d_offsets,
+                                     (unsigned *)ctx->io[2].p, n_pts)) ||
+            (rc = d2h_sync(ctx, points, ctx->io[2].p, (size_t)n_pts * sizeof(unsigned))))
+            return rc;
+    }
+    std::memcpy(offsets, off.data(), off_bytes);
+    return CANNY_HIP_OK;
+}
+
+int canny_hip_points_from_bits(const unsigned char *bits, int height, int width, unsigned int *points,
+                               unsigned long long capacity, unsigned long long *count)
+{
+    if (!bits || !count || (!points && capacity)) return CANNY_HIP_ERR_INVALID;
+    int rc = check_dims(height, width, 1);
+    if (rc) return rc;
+    const size_t row_bytes = ((size_t)width + 7) / 8;
+    unsigned long long n = 0;
+    for (int y = 0; y < height; y++) {
+        const unsigned char *row = bits + (size_t)y * row_bytes;
+        for (size_t xb = 0; xb < row_bytes; xb++) {
+            unsigned v = row[xb];
+            const int left = width - (int)(xb * 8); // pixels of this row from this byte on
+            if (left < 8) v &= 0xffu << (8 - left); // the row's padding bits are not pixels
+            while (v) {
+                const int k = __builtin_clz(v) - 24; // MSB-first: the highest set bit is the leftmost pixel
+                if (n < capacity) points[n] = (unsigned)((size_t)y * width + xb * 8 + k);
+                n++;
+                v &= ~(0x80u >> k);
+            }
+        }
+    }
+    *count = n;
+    return CANNY_HIP_OK;
+}
+
 // ---- profiling --------------------------------------------------------------------------------------
 int canny_hip_profile_enable(canny_hip_ctx *ctx, int on)
 {
@@ -2350,7 +2489,7 @@ int canny_hip_profile_enable(canny_hip_ctx *ctx, int on)
 static int profile_collect(canny_hip_ctx *ctx)
 {
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    for (int s = 0; s < CANNY_HIP_STAGE_COUNT; s++) {
+    for (int s = 0; s < CANNY_HIP_STAGE_END; s++) {
         for (auto &e : ctx->pending[s]) {
             float ms = 0.0f;
             if (hipEventElapsedTime(&ms, e.a, e.b) == hipSuccess) {
@@ -2371,7 +2510,7 @@ int canny_hip_profile_reset(canny_hip_ctx *ctx)
     int rc = bind(ctx);
     if (rc) return rc;
     if ((rc = profile_collect(ctx))) return rc;
-    for (int s = 0; s < CANNY_HIP_STAGE_COUNT; s++) {
+    for (int s = 0; s < CANNY_HIP_STAGE_END; s++) {
         ctx->total_ms[s] = 0.0;
         ctx->launches[s] = 0;
     }
@@ -2382,7 +2521,7 @@ int canny_hip_profile_get(canny_hip_ctx *ctx, int stage, double *total_ms, long 
 {
     int rc = bind(ctx);
     if (rc) return rc;
-    if (stage < 0 || stage >= CANNY_HIP_STAGE_COUNT || !total_ms || !launches) return CANNY_HIP_ERR_INVALID;
+    if (stage < 0 || stage >= CANNY_HIP_STAGE_END || !total_ms || !launches) return CANNY_HIP_ERR_INVALID;
     if ((rc = profile_collect(ctx))) return rc;
     *total_ms = ctx->total_ms[stage];
     *launches = ctx->launches[stage];

@@ -302,6 +302,27 @@ hipError_t launch_fep_classify(const int16_t *cand, const uint8_t *visited, uint
 hipError_t launch_fep_finalize(int16_t *cand, uint8_t *visited, const uint64_t *strong, const HystGeom &g, int start,
                                int min_val, hipStream_t stream);
 
+// ---- Edge point lists (canny_points.hip) -------------------------------
+// Word of the bit-planes that holds columns 64*wx .. 64*wx + 63 of row y of frame f (word_index() of canny_kernels.hip).
+__host__ __device__ inline size_t hyst_word_index(const HystGeom &g, int f, int y, int wx)
+{
+    return ((((size_t)f * g.tiles_y + (y >> 6)) * g.tiles_x + wx) << 6) + (y & 63);
+}
+// The source is the strong plane of geometry g, or -- bits != nullptr -- a packed bit map (rows MSB-first, padded to
+// bytes, any byte address; padding bits ignored).
+// count: row_counts[f * height + y] = set pixels of that row.
+hipError_t launch_points_count(const uint64_t *strong, const uint8_t *bits, const HystGeom &g, uint32_t *row_counts,
+                               hipStream_t stream);
+// scan: rows (in place) -> set pixels of the frame before the row; frame_totals[f] = the frame's count;
+// offsets[0 .. n_frames] = exclusive prefix of the totals.
+hipError_t launch_points_scan(uint32_t *rows, unsigned long long *frame_totals, unsigned long long *offsets, int height,
+                              int n_frames, hipStream_t stream);
+// scatter: points[offsets[f] + row_offsets[f * height + y] + k] = y * width + (k-th set column of the row), for every
+// position below capacity; nothing is stored at or beyond points + capacity.
+hipError_t launch_points_scatter(const uint64_t *strong, const uint8_t *bits, const HystGeom &g,
+                                 const uint32_t *row_offsets, const unsigned long long *offsets, uint32_t *points,
+                                 unsigned long long capacity, hipStream_t stream);
+
 // ---- measurement aid ------------------------------------------------------------------------
 // Plain device copy of nbytes (multiple of 16; both pointers 16-byte aligned): what a 1:1 read/write stream reaches.
 hipError_t launch_probe_copy(const void *src, void *dst, size_t nbytes, hipStream_t stream, const LaunchEvents &ev = {});

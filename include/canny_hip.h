@@ -52,7 +52,8 @@
 extern "C" {
 #endif
 
-#define CANNY_HIP_VERSION 401        /* 0.4.1: + canny_hip_selftest_sobel_pixel */
+#define CANNY_HIP_VERSION 500        /* 0.5.0: + edge point lists (CSR of pixel indices), compacted on the GPU */
+/* 0.4.1: + canny_hip_selftest_sobel_pixel */
 /* 0.4.0: + per-frame thresholds, explicit or chosen on the GPU (median / quantile) */
 /* 0.3.0: + colour frame input (BGR / RGB / BGRA / RGBA -> gray on the GPU) */
 /* 0.2.0: + batch u8 / bit maps, multi-GPU options, host_register, async dev_canny */
@@ -81,7 +82,11 @@ enum canny_hip_stage {
     CANNY_HIP_STAGE_NMS = 6,
     CANNY_HIP_STAGE_XY_GRADIENT = 7,
     CANNY_HIP_STAGE_TO_GRAY = 8,        /* the standalone colour -> gray pass (the fused one is timed as GAUSSIAN) */
-    CANNY_HIP_STAGE_COUNT = 9
+    CANNY_HIP_STAGE_COUNT = 9,          /* the stages of the edge map itself, 0..8: unchanged, callers iterate over it */
+    /* stages of what is derived from a finished map follow the map's own; canny_hip_profile_get and the bits of
+     * "profile_stage_mask" take every value below CANNY_HIP_STAGE_END */
+    CANNY_HIP_STAGE_COMPACT = 9,        /* edge point lists: the count, scan and scatter kernels */
+    CANNY_HIP_STAGE_END = 10
 };
 
 /* Pixel layouts of the colour entry points (canny_hip_*_color, canny_hip_*to_gray): dense, interleaved, no row
@@ -403,6 +408,47 @@ int canny_hip_dev_canny_u8(canny_hip_ctx *ctx, const unsigned char *d_img, float
 /* ... and with a bit map as output (layout as canny_hip_canny_batch_bits: n_frames * height * ((width + 7) / 8) bytes). */
 int canny_hip_dev_canny_bits(canny_hip_ctx *ctx, const unsigned char *d_img, float sigma, int min_val, int max_val,
                              int height, int width, int n_frames, unsigned char *d_bits);
+
+/* ---- edge point lists ------------------------------------------------------------------------------------------------
+ * The pixels of an edge map as INDICES -- what a Hough transform, RANSAC fitting or contour following start from
+ * (np.flatnonzero(edges), cv::findNonZero(edges)); the reference's own convention: findEdgePixels(..., start, ...), pixel
+ * (r,c) at r*width+c.  A typical frame has a few percent of its pixels set.
+ * For frame f of a call with edge map E_f (the map canny_hip_canny returns for that frame, bit for bit):
+ *   P_f = the indices r*width + c of all pixels with E_f[r][c] != 0, ASCENDING (raster order), as unsigned int.
+ * The batch result is CSR-shaped: offsets[0 .. n_frames] with offsets[0] = 0 and offsets[f+1] - offsets[f] = |P_f| --
+ * always the TRUE counts -- and the lists concatenated densely in frame order: points[offsets[f] + k] = P_f[k].
+ * `capacity` is the number of unsigned ints `points` holds.  Entries whose global position is >= capacity are not written,
+ * nothing is ever written at or past points + capacity, and every entry below it is written as above: overflow shows as
+ * offsets[n_frames] > capacity, and the prefix that fits is exact.  points == NULL with capacity == 0 is the legal
+ * "counts only" call (per-frame edge density); points == NULL with capacity > 0 is CANNY_HIP_ERR_INVALID.
+ * The output is deterministic: same input, same bytes (no atomics on the ordering path).
+ * The list follows the MAP, not the plane it is derived from: max_val > 255 makes the reference zero every reached pixel
+ * (src/utils.cpp:336-340), so every list is then empty.  Statuses are those of canny_hip_dev_canny for the same arguments
+ * (CANNY_HIP_ERR_DOMAIN for min_val <= 0, ...), and on a status other than OK neither points nor offsets are written.
+ * The kernels are timed as CANNY_HIP_STAGE_COMPACT.
+ * Not (yet) covered -- follow-ups: the overlapped three-stream batch pipeline (canny_hip_canny_points uploads the whole batch,
+ * then computes), the multi-GPU sharder, colour input, per-frame / automatic thresholds, (x, y) pair output, and skipping
+ * the s16 map's write when only the points are wanted. */
+/* Device buffers, asynchronous; completion contract as canny_hip_dev_canny: d_points, d_offsets (and d_edges) are complete
+ * in stream order on the context's stream when the call has returned.  d_edges receives the s16 map exactly as
+ * canny_hip_dev_canny writes it, or is NULL (a context workspace then holds it).  d_offsets: n_frames + 1 entries. */
+int canny_hip_dev_canny_points(canny_hip_ctx *ctx, const unsigned char *d_img, float sigma, int min_val, int max_val,
+                               int height, int width, int n_frames, short *d_edges, unsigned int *d_points,
+                               unsigned long long capacity, unsigned long long *d_offsets);
+/* The compaction alone, on a device bit map in the layout of canny_hip_dev_canny_bits (rows MSB-first, padded to bytes;
+ * d_bits may have any byte alignment): for callers who already hold bit maps.  The padding bits of a row are ignored,
+ * whatever they hold.  Asynchronous. */
+int canny_hip_dev_points_from_bits(canny_hip_ctx *ctx, const unsigned char *d_bits, int height, int width, int n_frames,
+                                   unsigned int *d_points, unsigned long long capacity, unsigned long long *d_offsets);
+/* Host buffers, synchronous: upload, canny, count; the offsets come down, then only min(offsets[n_frames], capacity) points
+ * are compacted and downloaded -- a few percent of a plane crosses PCIe instead of the plane. */
+int canny_hip_canny_points(canny_hip_ctx *ctx, const unsigned char *imgs, int n_frames, float sigma, int min_val,
+                           int max_val, int height, int width, unsigned int *points, unsigned long long capacity,
+                           unsigned long long *offsets);
+/* Host-only, needs no device: the same rule on ONE host bit map (what a caller of canny_hip_canny_batch_bits runs on the
+ * maps it received); *count receives the true count. */
+int canny_hip_points_from_bits(const unsigned char *bits, int height, int width, unsigned int *points,
+                               unsigned long long capacity, unsigned long long *count);
 
 /* ---- per-stage HIP-event timing (events are recorded on the launch stream) ----------------- */
 int canny_hip_profile_enable(canny_hip_ctx *ctx, int on);
