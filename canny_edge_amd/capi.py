@@ -92,6 +92,8 @@ EXPORTS = (
     "canny_hip_dev_canny_auto", "canny_hip_canny_batch_thresholds", "canny_hip_canny_batch_auto",
     "canny_hip_dev_canny_points", "canny_hip_dev_points_from_bits", "canny_hip_canny_points",
     "canny_hip_points_from_bits",
+    "canny_hip_hough_geometry", "canny_hip_hough_tables", "canny_hip_hough_line_of", "canny_hip_dev_hough_points",
+    "canny_hip_dev_hough_bits", "canny_hip_dev_canny_hough", "canny_hip_canny_hough", "canny_hip_hough_profile_get",
 )
 
 _lib: Optional[C.CDLL] = None
@@ -201,6 +203,14 @@ def load() -> C.CDLL:
         "canny_hip_dev_points_from_bits": ([p, p, i, i, i, p, C.c_ulonglong, p], i),
         "canny_hip_canny_points": ([p, p, i, f, i, i, i, i, p, C.c_ulonglong, p], i),
         "canny_hip_points_from_bits": ([p, i, i, p, C.c_ulonglong, C.POINTER(C.c_ulonglong)], i),
+        "canny_hip_hough_geometry": ([i, i, f, f, f, f, ip, ip], i),
+        "canny_hip_hough_tables": ([f, f, f, i, p, p], i),
+        "canny_hip_hough_line_of": ([C.c_uint, i, f, f, f, C.POINTER(f), C.POINTER(f)], i),
+        "canny_hip_dev_hough_points": ([p, p, p, i, i, i, f, f, i, i, f, f, p, p, p, p, p], i),
+        "canny_hip_dev_hough_bits": ([p, p, i, i, i, f, f, i, i, f, f, p, p, p, p, p], i),
+        "canny_hip_dev_canny_hough": ([p, p, f, i, i, i, i, i, p, f, f, i, i, f, f, p, p, p, p, p], i),
+        "canny_hip_canny_hough": ([p, p, i, f, i, i, i, i, f, f, i, i, f, f, p, p, p, p], i),
+        "canny_hip_hough_profile_get": ([p, i, C.POINTER(C.c_double), C.POINTER(C.c_long)], i),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -253,6 +263,40 @@ def points_from_bits(bits, height: int, width: int, capacity: Optional[int] = No
     if st:
         raise CannyHipError(st, "points_from_bits")
     return pts if capacity is None else (pts[:min(cap, n.value)], n.value)
+
+
+HOUGH_MAX_LINES = 4096
+HOUGH_PARTS = ("vote", "peaks", "select")
+
+
+def hough_geometry(height: int, width: int, rho: float = 1.0, theta: float = np.pi / 180, min_theta: float = 0.0,
+                   max_theta: float = np.pi) -> Tuple[int, int]:
+    """(numangle, numrho) of the Hough accumulator for a frame size and resolution (host-only; the rule of
+    include/canny_hip.h).  The accumulator of a frame is (numangle + 2) x (numrho + 2) int32."""
+    na, nr = C.c_int(0), C.c_int(0)
+    st = load().canny_hip_hough_geometry(height, width, rho, theta, min_theta, max_theta, C.byref(na), C.byref(nr))
+    if st != OK:
+        raise CannyHipError(st, "hough_geometry")
+    return na.value, nr.value
+
+
+def hough_tables(rho: float, theta: float, min_theta: float, numangle: int) -> Tuple[np.ndarray, np.ndarray]:
+    """The vote tables (cos / rho, sin / rho per angle, float32) exactly as the device uses them (host-only)."""
+    tc, ts = np.empty(max(numangle, 0), np.float32), np.empty(max(numangle, 0), np.float32)
+    st = load().canny_hip_hough_tables(rho, theta, min_theta, numangle, _hp(tc) if numangle > 0 else None,
+                                       _hp(ts) if numangle > 0 else None)
+    if st != OK:
+        raise CannyHipError(st, "hough_tables")
+    return tc, ts
+
+
+def hough_line_of(base: int, numrho: int, rho: float, theta: float, min_theta: float = 0.0) -> Tuple[np.float32, np.float32]:
+    """(rho, theta) of accumulator cell `base`, as float32, exactly as the device writes them (host-only)."""
+    lr, lt = C.c_float(0), C.c_float(0)
+    st = load().canny_hip_hough_line_of(base, numrho, rho, theta, min_theta, C.byref(lr), C.byref(lt))
+    if st != OK:
+        raise CannyHipError(st, "hough_line_of")
+    return np.float32(lr.value), np.float32(lt.value)
 
 
 def points_to_rc(points, width: int) -> Tuple[np.ndarray, np.ndarray]:
@@ -583,6 +627,68 @@ class Context:
         self._check(self._L.canny_hip_dev_points_from_bits(self._h, C.c_void_p(d_bits), h, w, n,
                                                            C.c_void_p(d_points or None), capacity,
                                                            C.c_void_p(d_offsets)), "dev_points_from_bits")
+
+    # ---- Hough lines of the finished map (cv::HoughLines semantics) -----------------------
+    def canny_hough(self, imgs, sigma: float, min_val: int, max_val: int, rho: float = 1.0, theta: float = np.pi / 180,
+                    threshold: int = 100, lines_max: int = 256, min_theta: float = 0.0, max_theta: float = np.pi):
+        """canny(), then the standard Hough line transform of each map on the GPU: imgs (H, W) or (N, H, W) uint8 ->
+        (results, counts): results[f] = (lines float32 [k, 2] as (rho, theta), votes int32 [k], bases uint32 [k]) with
+        k = min(lines_max, counts[f]), strongest first; counts int32 [N] holds the true number of peaks per frame."""
+        a = np.ascontiguousarray(imgs, dtype=np.uint8)
+        if a.ndim == 2:
+            a = a[None]
+        if a.ndim != 3:
+            raise ValueError("expected uint8 [H, W] or [n_frames, H, W]")
+        n, h, w = a.shape
+        slots = n * max(int(lines_max), 1)
+        lines, votes = np.zeros((slots, 2), np.float32), np.zeros(slots, np.int32)
+        bases, counts = np.zeros(slots, np.uint32), np.zeros(n, np.int32)
+        self._check(self._L.canny_hip_canny_hough(self._h, _hp(a), n, sigma, min_val, max_val, h, w, rho, theta,
+                                                  threshold, lines_max, min_theta, max_theta, _hp(lines), _hp(votes),
+                                                  _hp(bases), _hp(counts)), "canny_hough")
+        out = []
+        for f in range(n):
+            k, at = min(int(counts[f]), lines_max), f * lines_max
+            out.append((lines[at:at + k].copy(), votes[at:at + k].copy(), bases[at:at + k].copy()))
+        return out, counts
+
+    def dev_hough_points(self, d_points: int, d_offsets: int, n: int, h: int, w: int, rho: float, theta: float,
+                         threshold: int, lines_max: int, min_theta: float, max_theta: float, d_lines: int, d_votes: int,
+                         d_bases: int, d_counts: int, d_accum: int = 0):
+        """The transform of CSR point lists (as dev_canny_points writes them) on device pointers; d_lines (2 float32 per
+        slot), d_votes, d_bases, d_accum may be 0; slot f * lines_max + k; d_counts: n int32."""
+        v = C.c_void_p
+        self._check(self._L.canny_hip_dev_hough_points(self._h, v(d_points or None), v(d_offsets or None), n, h, w, rho,
+                                                       theta, threshold, lines_max, min_theta, max_theta,
+                                                       v(d_lines or None), v(d_votes or None), v(d_bases or None),
+                                                       v(d_counts or None), v(d_accum or None)), "dev_hough_points")
+
+    def dev_hough_bits(self, d_bits: int, n: int, h: int, w: int, rho: float, theta: float, threshold: int,
+                       lines_max: int, min_theta: float, max_theta: float, d_lines: int, d_votes: int, d_bases: int,
+                       d_counts: int, d_accum: int = 0):
+        """The same from device bit maps (layout of dev_canny_bits, padding bits ignored)."""
+        v = C.c_void_p
+        self._check(self._L.canny_hip_dev_hough_bits(self._h, v(d_bits or None), n, h, w, rho, theta, threshold,
+                                                     lines_max, min_theta, max_theta, v(d_lines or None),
+                                                     v(d_votes or None), v(d_bases or None), v(d_counts or None),
+                                                     v(d_accum or None)), "dev_hough_bits")
+
+    def dev_canny_hough(self, d_img: int, sigma: float, min_val: int, max_val: int, h: int, w: int, n: int, rho: float,
+                        theta: float, threshold: int, lines_max: int, min_theta: float, max_theta: float, d_lines: int,
+                        d_votes: int, d_bases: int, d_counts: int, d_accum: int = 0, d_edges: int = 0):
+        """dev_canny, then the transform of its map queued behind it on the same stream (no point list in between)."""
+        v = C.c_void_p
+        self._check(self._L.canny_hip_dev_canny_hough(self._h, v(d_img or None), sigma, min_val, max_val, h, w, n,
+                                                      v(d_edges or None), rho, theta, threshold, lines_max, min_theta,
+                                                      max_theta, v(d_lines or None), v(d_votes or None),
+                                                      v(d_bases or None), v(d_counts or None), v(d_accum or None)),
+                    "dev_canny_hough")
+
+    def hough_profile_get(self, part: int) -> Tuple[float, int]:
+        """Accumulated device milliseconds and launch groups of a Hough part (0 vote, 1 peaks, 2 select + sort)."""
+        ms, n = C.c_double(0), C.c_long(0)
+        self._check(self._L.canny_hip_hough_profile_get(self._h, part, C.byref(ms), C.byref(n)), "hough_profile_get")
+        return ms.value, n.value
 
     # ---- colour frames (interleaved BGR / RGB / BGRA / RGBA; the rule is the "gray_rule" option) --------------
     def to_gray(self, frame, order: str = "bgr") -> np.ndarray:

@@ -374,6 +374,14 @@ struct canny_hip_ctx {
     DevBuf hist;      // automatic thresholds: per-frame histograms (n_frames x 257 u32)
     DevBuf thr;       // automatic thresholds: the pairs when the caller does not ask for them
     DevBuf points;    // edge point lists: per-frame totals (n_frames u64), then per-row counts / prefixes (u32)
+    // Hough lines: the accumulators when the caller passes none; candidate keys, histograms, tie counts, cut words; the
+    // vote tables on the device with the host copy they were sent from and the arguments they belong to
+    DevBuf hough_accum, hough_ws, hough_tab;
+    std::vector<float> hough_tab_host;
+    float hough_tab_key[3] = {0, 0, 0};
+    int hough_tab_n = 0;
+    int hough_path = 0;   // 0 auto (LDS rows when a row fits), 1 global atomics, 2 LDS rows
+    int hough_lds_kb = 0; // A/B: LDS budget of a vote workgroup in KiB, 0 = automatic
     DevBuf plane_s, plane_c, stamps, flags; // hysteresis bit-planes / scheduling words
     DevBuf io[4];     // staging for the host-pointer stage functions
     unsigned *host_flags = nullptr;     // pinned + mapped, 4 words per lane: last_change, domain, sequence number, spare
@@ -396,11 +404,13 @@ struct canny_hip_ctx {
     bool prof = false;
     unsigned prof_mask = ~0u; // stages whose launches get an event pair (each pair costs a few us of stream time)
     unsigned prof_every = 1;  // ... and only every prof_every-th launch group of a stage gets one
-    unsigned prof_seen[CANNY_HIP_STAGE_END] = {0};
-    std::vector<EventPair> pending[CANNY_HIP_STAGE_END];
+    // slots: the stages, then the three Hough parts (canny_hip_hough_profile_get)
+    static constexpr int kProfSlots = CANNY_HIP_STAGE_END + 3;
+    unsigned prof_seen[kProfSlots] = {0};
+    std::vector<EventPair> pending[kProfSlots];
     std::vector<EventPair> pool;
-    double total_ms[CANNY_HIP_STAGE_END] = {0};
-    long launches[CANNY_HIP_STAGE_END] = {0};
+    double total_ms[kProfSlots] = {0};
+    long launches[kProfSlots] = {0};
 };
 
 // One batch pipeline: three streams and a ring of chunk slots.  Chunk j of the pipeline lives in slot j % kSlots:
@@ -1113,6 +1123,137 @@ int dev_canny_points_count(canny_hip_ctx *ctx, const unsigned char *d_img, float
     return dev_points_count(ctx, *strong_out, nullptr, make_hyst_geom(h, w, n), d_offsets);
 }
 
+// ---- Hough lines (canny_hough.hip) -----------------------------------------
+struct HoughOut {
+    float *d_lines;
+    int *d_votes;
+    unsigned *d_bases;
+    int *d_counts;
+    int *d_accum;
+};
+
+bool hough_args_valid(float rho, float theta, float min_theta, float max_theta)
+{
+    return std::isfinite(rho) && std::isfinite(theta) && std::isfinite(min_theta) && std::isfinite(max_theta) &&
+           rho > 0.0f && theta > 0.0f && min_theta >= 0.0f && min_theta < max_theta && max_theta <= (float)M_PI;
+}
+
+// The geometry of the rule, in double on the host.
+int hough_geometry(int height, int width, float rho, float theta, float min_theta, float max_theta, int *numangle,
+                   int *numrho)
+{
+    if (height < 1 || width < 1 || !hough_args_valid(rho, theta, min_theta, max_theta)) return CANNY_HIP_ERR_INVALID;
+    double na = std::floor(((double)max_theta - (double)min_theta) / (double)theta) + 1.0;
+    if (na > 1.0 && std::fabs(M_PI - (na - 1.0) * (double)theta) < (double)theta / 2) na -= 1.0;
+    const double nr = std::nearbyint((2.0 * ((double)width + (double)height) + 1.0) / (double)rho); // half to even
+    if (nr < 1.0 || (na + 2.0) * (nr + 2.0) > 2147483647.0) return CANNY_HIP_ERR_UNSUPPORTED; // bases are 32-bit
+    *numangle = (int)na;
+    *numrho = (int)nr;
+    return CANNY_HIP_OK;
+}
+
+void hough_tables(float rho, float theta, float min_theta, int numangle, float *tab_cos, float *tab_sin)
+{
+    const float irho = 1.0f / rho;
+    float ang = min_theta;
+    for (int n = 0; n < numangle; n++) {
+        tab_cos[n] = (float)(std::cos((double)ang) * (double)irho);
+        tab_sin[n] = (float)(std::sin((double)ang) * (double)irho);
+        ang = ang + theta;
+    }
+}
+
+// No cell collects more votes than this: along the axis whose table entry is the larger one (at least 1 / (rho sqrt 2))
+// a run of pixels that round to one r is at most rho * sqrt 2 + 1 long (+ 2 for the float roundings at its ends), and
+// there are at most max(height, width) such runs.  The peak histogram has one bin per possible vote value.
+int hough_hist_bins(int height, int width, float rho, double *bins)
+{
+    const double per_run = std::ceil(1.4143 * (double)rho) + 3.0;
+    *bins = std::min((double)height * width, (double)std::max(height, width) * per_run) + 1.0;
+    return *bins <= (double)(1 << 26) ? CANNY_HIP_OK : CANNY_HIP_ERR_UNSUPPORTED;
+}
+
+// Checks that need no device and write nothing; the geometry on success.
+int hough_prepare(const canny_hip_ctx *ctx, int height, int width, float rho, float theta, int lines_max,
+                  float min_theta, float max_theta, const HoughOut &out, HoughGeom &hg, int *lds_rows)
+{
+    if (!out.d_counts || lines_max < 1) return CANNY_HIP_ERR_INVALID;
+    int rc = hough_geometry(height, width, rho, theta, min_theta, max_theta, &hg.numangle, &hg.numrho);
+    if (rc) return rc;
+    if (lines_max > kHoughMaxLines) return CANNY_HIP_ERR_UNSUPPORTED;
+    double bins;
+    if ((rc = hough_hist_bins(height, width, rho, &bins))) return rc;
+    hg.rho = rho;
+    hg.theta = theta;
+    hg.min_theta = min_theta;
+    // 48 KiB by default: two 1024-lane workgroups per CU; a row of a 4K frame at rho 1 is 46.9 KiB
+    const int fit = hough_lds_rows(hg, ctx->hough_lds_kb ? ctx->hough_lds_kb * 1024 : 48 * 1024);
+    if (ctx->hough_path == 2 && !fit) return CANNY_HIP_ERR_UNSUPPORTED; // a row does not fit in LDS
+    *lds_rows = ctx->hough_path == 1 ? 0 : fit;
+    return CANNY_HIP_OK;
+}
+
+// The transform of one source (CSR points, packed bits or the context's strong plane), queued on the context's stream.
+// All three null: the empty map (counts 0, a zero accumulator if the caller asked for it).
+int dev_hough(canny_hip_ctx *ctx, const uint64_t *strong, const uint8_t *bits, const unsigned *points,
+              const unsigned long long *offsets, const HystGeom &g, const HoughGeom &hg, int lds_rows, int threshold,
+              int lines_max, const HoughOut &out)
+{
+    const int n = g.n_frames;
+    HIP_TRY(ctx, hipMemsetAsync(out.d_counts, 0, (size_t)n * sizeof(int), ctx->stream));
+    if (!strong && !bits && !points) {
+        if (out.d_accum) HIP_TRY(ctx, hipMemsetAsync(out.d_accum, 0, hough_accum_bytes(hg, n), ctx->stream));
+        return CANNY_HIP_OK;
+    }
+    int *accum = out.d_accum;
+    if (!accum) {
+        HIP_TRY(ctx, ctx->hough_accum.ensure(hough_accum_bytes(hg, n)));
+        accum = (int *)ctx->hough_accum.p;
+    }
+    // the tables travel once per set of arguments; the host copy outlives its transfer
+    const size_t tab_bytes = 2 * (size_t)hg.numangle * sizeof(float);
+    const bool tab_moved = ctx->hough_tab.bytes < tab_bytes;
+    HIP_TRY(ctx, ctx->hough_tab.ensure(tab_bytes));
+    if (tab_moved || ctx->hough_tab_n != hg.numangle || ctx->hough_tab_key[0] != hg.rho ||
+        ctx->hough_tab_key[1] != hg.theta || ctx->hough_tab_key[2] != hg.min_theta) {
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); // an earlier transfer may still read the host copy
+        ctx->hough_tab_host.resize(2 * (size_t)hg.numangle);
+        hough_tables(hg.rho, hg.theta, hg.min_theta, hg.numangle, ctx->hough_tab_host.data(),
+                     ctx->hough_tab_host.data() + hg.numangle);
+        ctx->hough_tab_n = 0;
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->hough_tab.p, ctx->hough_tab_host.data(), tab_bytes, hipMemcpyHostToDevice,
+                                    ctx->stream));
+        ctx->hough_tab_n = hg.numangle;
+        ctx->hough_tab_key[0] = hg.rho, ctx->hough_tab_key[1] = hg.theta, ctx->hough_tab_key[2] = hg.min_theta;
+    }
+    double bins_d;
+    (void)hough_hist_bins(g.height, g.width, hg.rho, &bins_d);
+    const int bins = (int)bins_d;
+    // workspace: candidate keys | histograms | tie counts per accumulator row | cut words
+    const size_t cand_bytes = (size_t)n * lines_max * sizeof(unsigned long long);
+    const size_t hist_bytes = (size_t)n * bins * sizeof(unsigned), ties_bytes = (size_t)n * hg.numangle * sizeof(unsigned);
+    HIP_TRY(ctx, ctx->hough_ws.ensure(cand_bytes + hist_bytes + ties_bytes + (size_t)n * 8 * sizeof(unsigned)));
+    unsigned long long *cand = (unsigned long long *)ctx->hough_ws.p;
+    unsigned *hist = (unsigned *)((char *)ctx->hough_ws.p + cand_bytes);
+    unsigned *ties = hist + (size_t)n * bins, *cut = ties + (size_t)n * hg.numangle;
+    HIP_TRY(ctx, hipMemsetAsync(hist, 0, hist_bytes + ties_bytes, ctx->stream));
+    {
+        StageTimer tm(ctx, CANNY_HIP_STAGE_END + 0);
+        HIP_TRY(ctx, launch_hough_vote(strong, bits, points, offsets, g, hg, (const float *)ctx->hough_tab.p, accum,
+                                       lds_rows, ctx->stream));
+    }
+    {
+        StageTimer tm(ctx, CANNY_HIP_STAGE_END + 1);
+        HIP_TRY(ctx, launch_hough_peaks(accum, n, hg, threshold, out.d_counts, hist, bins, ctx->stream));
+    }
+    if (out.d_lines || out.d_votes || out.d_bases) {
+        StageTimer tm(ctx, CANNY_HIP_STAGE_END + 2);
+        HIP_TRY(ctx, launch_hough_select(accum, n, hg, threshold, lines_max, out.d_counts, hist, bins, ties, cut, cand,
+                                         out.d_lines, out.d_votes, out.d_bases, ctx->stream));
+    }
+    return CANNY_HIP_OK;
+}
+
 void destroy_batch_pipe(canny_hip_ctx::BatchPipe *w)
 {
     if (!w) return;
@@ -1250,6 +1391,9 @@ void canny_hip_ctx_destroy(canny_hip_ctx *ctx)
     ctx->hist.release();
     ctx->thr.release();
     ctx->points.release();
+    ctx->hough_accum.release();
+    ctx->hough_ws.release();
+    ctx->hough_tab.release();
     ctx->stamps.release();
     ctx->flags.release();
     for (auto &b : ctx->io) b.release();
@@ -1294,6 +1438,8 @@ int canny_hip_ctx_get_option(const canny_hip_ctx *ctx, const char *name, int *va
     else if (!std::strcmp(name, "gaussian_path")) *value = ctx->gaussian_path;
     else if (!std::strcmp(name, "sobel_nms_path")) *value = ctx->sobel_nms_path;
     else if (!std::strcmp(name, "tune_batch_compact")) *value = ctx->batch_compact;
+    else if (!std::strcmp(name, "hough_path")) *value = ctx->hough_path;
+    else if (!std::strcmp(name, "tune_hough_lds_kb")) *value = ctx->hough_lds_kb;
     else if (!std::strcmp(name, "batch_expand_threads")) *value = ctx->expand_pool ? ctx->expand_pool->size() : 0; // read-only
     else return CANNY_HIP_ERR_INVALID;
     return CANNY_HIP_OK;
@@ -1317,6 +1463,8 @@ int canny_hip_ctx_set_option(canny_hip_ctx *ctx, const char *name, int value)
     else if (!std::strcmp(name, "tune_batch_chunk_frames") && value <= 65535) ctx->batch_chunk_frames = value;
     else if (!std::strcmp(name, "tune_batch_pipe_mode") && value <= 2) ctx->batch_pipe_mode = value;
     else if (!std::strcmp(name, "tune_batch_compact") && value <= 1) ctx->batch_compact = value;
+    else if (!std::strcmp(name, "hough_path") && value <= 2) ctx->hough_path = value;
+    else if (!std::strcmp(name, "tune_hough_lds_kb") && value <= kHoughLdsMax / 1024) ctx->hough_lds_kb = value;
     else if (!std::strcmp(name, "tune_batch_expand_threads") && value <= 64) {
         if (value != ctx->batch_expand_threads) ctx->expand_pool.reset();
         ctx->batch_expand_threads = value;
@@ -2489,7 +2637,7 @@ int canny_hip_profile_enable(canny_hip_ctx *ctx, int on)
 static int profile_collect(canny_hip_ctx *ctx)
 {
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    for (int s = 0; s < CANNY_HIP_STAGE_END; s++) {
+    for (int s = 0; s < canny_hip_ctx::kProfSlots; s++) {
         for (auto &e : ctx->pending[s]) {
             float ms = 0.0f;
             if (hipEventElapsedTime(&ms, e.a, e.b) == hipSuccess) {
@@ -2510,7 +2658,7 @@ int canny_hip_profile_reset(canny_hip_ctx *ctx)
     int rc = bind(ctx);
     if (rc) return rc;
     if ((rc = profile_collect(ctx))) return rc;
-    for (int s = 0; s < CANNY_HIP_STAGE_END; s++) {
+    for (int s = 0; s < canny_hip_ctx::kProfSlots; s++) {
         ctx->total_ms[s] = 0.0;
         ctx->launches[s] = 0;
     }
@@ -2525,6 +2673,154 @@ int canny_hip_profile_get(canny_hip_ctx *ctx, int stage, double *total_ms, long 
     if ((rc = profile_collect(ctx))) return rc;
     *total_ms = ctx->total_ms[stage];
     *launches = ctx->launches[stage];
+    return CANNY_HIP_OK;
+}
+
+// ---- Hough lines ----------------------------------------------------------------------------------------
+int canny_hip_hough_geometry(int height, int width, float rho, float theta, float min_theta, float max_theta,
+                             int *numangle, int *numrho)
+{
+    if (!numangle || !numrho) return CANNY_HIP_ERR_INVALID;
+    return hough_geometry(height, width, rho, theta, min_theta, max_theta, numangle, numrho);
+}
+
+int canny_hip_hough_tables(float rho, float theta, float min_theta, int numangle, float *tab_cos, float *tab_sin)
+{
+    if (!tab_cos || !tab_sin || numangle < 1 || !std::isfinite(rho) || !std::isfinite(theta) ||
+        !std::isfinite(min_theta) || rho <= 0.0f || theta <= 0.0f || min_theta < 0.0f || min_theta >= (float)M_PI)
+        return CANNY_HIP_ERR_INVALID;
+    hough_tables(rho, theta, min_theta, numangle, tab_cos, tab_sin);
+    return CANNY_HIP_OK;
+}
+
+int canny_hip_hough_line_of(unsigned int base, int numrho, float rho, float theta, float min_theta, float *line_rho,
+                            float *line_theta)
+{
+    if (!line_rho || !line_theta || numrho < 1 || numrho > 0x7ffffff0 || !std::isfinite(rho) || !std::isfinite(theta) ||
+        !std::isfinite(min_theta) || rho <= 0.0f || theta <= 0.0f)
+        return CANNY_HIP_ERR_INVALID;
+    const unsigned stride = (unsigned)numrho + 2u;
+    const int n = (int)(base / stride) - 1, r = (int)(base % stride) - 1;
+    const float centre = (float)(numrho - 1) * 0.5f;
+    const float d = (float)r - centre; // each operation rounded on its own (-ffp-contract=off)
+    const float t = (float)n * theta;
+    *line_rho = d * rho;
+    *line_theta = min_theta + t;
+    return CANNY_HIP_OK;
+}
+
+int canny_hip_dev_hough_points(canny_hip_ctx *ctx, const unsigned int *d_points, const unsigned long long *d_offsets,
+                               int n_frames, int height, int width, float rho, float theta, int threshold, int lines_max,
+                               float min_theta, float max_theta, float *d_lines, int *d_votes, unsigned int *d_bases,
+                               int *d_counts, int *d_accum)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!d_points || !d_offsets) return CANNY_HIP_ERR_INVALID;
+    if ((rc = check_dims(height, width, n_frames))) return rc;
+    const HoughOut out{d_lines, d_votes, d_bases, d_counts, d_accum};
+    HoughGeom hg;
+    int lds_rows = 0;
+    if ((rc = hough_prepare(ctx, height, width, rho, theta, lines_max, min_theta, max_theta, out, hg, &lds_rows)) ||
+        (rc = finish_pending(ctx)))
+        return rc;
+    return dev_hough(ctx, nullptr, nullptr, d_points, d_offsets, make_hyst_geom(height, width, n_frames), hg, lds_rows,
+                     threshold, lines_max, out);
+}
+
+int canny_hip_dev_hough_bits(canny_hip_ctx *ctx, const unsigned char *d_bits, int n_frames, int height, int width,
+                             float rho, float theta, int threshold, int lines_max, float min_theta, float max_theta,
+                             float *d_lines, int *d_votes, unsigned int *d_bases, int *d_counts, int *d_accum)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!d_bits) return CANNY_HIP_ERR_INVALID;
+    if ((rc = check_dims(height, width, n_frames))) return rc;
+    const HoughOut out{d_lines, d_votes, d_bases, d_counts, d_accum};
+    HoughGeom hg;
+    int lds_rows = 0;
+    if ((rc = hough_prepare(ctx, height, width, rho, theta, lines_max, min_theta, max_theta, out, hg, &lds_rows)) ||
+        (rc = finish_pending(ctx)))
+        return rc;
+    return dev_hough(ctx, nullptr, d_bits, nullptr, nullptr, make_hyst_geom(height, width, n_frames), hg, lds_rows,
+                     threshold, lines_max, out);
+}
+
+int canny_hip_dev_canny_hough(canny_hip_ctx *ctx, const unsigned char *d_img, float sigma, int min_val, int max_val,
+                              int height, int width, int n_frames, short *d_edges, float rho, float theta, int threshold,
+                              int lines_max, float min_theta, float max_theta, float *d_lines, int *d_votes,
+                              unsigned int *d_bases, int *d_counts, int *d_accum)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!d_img) return CANNY_HIP_ERR_INVALID;
+    if ((rc = check_dims(height, width, n_frames))) return rc;
+    const HoughOut out{d_lines, d_votes, d_bases, d_counts, d_accum};
+    HoughGeom hg;
+    int lds_rows = 0;
+    if ((rc = hough_prepare(ctx, height, width, rho, theta, lines_max, min_theta, max_theta, out, hg, &lds_rows)))
+        return rc;
+    if (!d_edges) {
+        HIP_TRY(ctx, ctx->edges16.ensure(npx(height, width, n_frames) * sizeof(short)));
+        d_edges = (short *)ctx->edges16.p;
+    }
+    if ((rc = dev_canny(ctx, d_img, sigma, min_val, max_val, height, width, n_frames, d_edges))) return rc;
+    // the transform follows the MAP: max_val > 255 zeroes every reached pixel although strong bits are set
+    const uint64_t *strong = max_val > 255 ? nullptr : (const uint64_t *)ctx->plane_s.p;
+    return dev_hough(ctx, strong, nullptr, nullptr, nullptr, make_hyst_geom(height, width, n_frames), hg, lds_rows,
+                     threshold, lines_max, out);
+}
+
+int canny_hip_canny_hough(canny_hip_ctx *ctx, const unsigned char *imgs, int n_frames, float sigma, int min_val,
+                          int max_val, int height, int width, float rho, float theta, int threshold, int lines_max,
+                          float min_theta, float max_theta, float *lines, int *votes, unsigned int *bases, int *counts)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!imgs || !counts) return CANNY_HIP_ERR_INVALID;
+    if ((rc = check_dims(height, width, n_frames))) return rc;
+    HoughGeom hg;
+    int lds_rows = 0;
+    {
+        const HoughOut probe{nullptr, nullptr, nullptr, counts, nullptr};
+        if ((rc = hough_prepare(ctx, height, width, rho, theta, lines_max, min_theta, max_theta, probe, hg, &lds_rows)))
+            return rc;
+    }
+    const size_t slots = (size_t)n_frames * lines_max;
+    // one staging block: lines (2 floats per slot) | votes | bases | counts
+    HIP_TRY(ctx, ctx->io[1].ensure(slots * 16 + (size_t)n_frames * sizeof(int)));
+    char *d = (char *)ctx->io[1].p;
+    const HoughOut out{lines ? (float *)d : nullptr, votes ? (int *)(d + slots * 8) : nullptr,
+                       bases ? (unsigned *)(d + slots * 12) : nullptr, (int *)(d + slots * 16), nullptr};
+    if ((rc = h2d(ctx, ctx->io[0], imgs, npx(height, width, n_frames)))) return rc;
+    if ((rc = canny_hip_dev_canny_hough(ctx, (const unsigned char *)ctx->io[0].p, sigma, min_val, max_val, height, width,
+                                        n_frames, nullptr, rho, theta, threshold, lines_max, min_theta, max_theta,
+                                        out.d_lines, out.d_votes, out.d_bases, out.d_counts, nullptr)))
+        return rc;
+    std::vector<int> cnt((size_t)n_frames);
+    if ((rc = d2h_sync(ctx, cnt.data(), out.d_counts, cnt.size() * sizeof(int)))) return rc;
+    // only the lines come down: the filled slots of each frame, nothing of the accumulators
+    for (int f = 0; f < n_frames; f++) {
+        const size_t k = (size_t)std::min(cnt[f], lines_max), at = (size_t)f * lines_max;
+        if (!k) continue;
+        if (lines)
+            HIP_TRY(ctx, hipMemcpyAsync(lines + 2 * at, out.d_lines + 2 * at, k * 8, hipMemcpyDeviceToHost, ctx->stream));
+        if (votes) HIP_TRY(ctx, hipMemcpyAsync(votes + at, out.d_votes + at, k * 4, hipMemcpyDeviceToHost, ctx->stream));
+        if (bases) HIP_TRY(ctx, hipMemcpyAsync(bases + at, out.d_bases + at, k * 4, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    std::memcpy(counts, cnt.data(), cnt.size() * sizeof(int));
+    return CANNY_HIP_OK;
+}
+
+int canny_hip_hough_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches)
+{
+    if (part < 0 || part > 2 || !total_ms || !launches) return CANNY_HIP_ERR_INVALID;
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if ((rc = profile_collect(ctx))) return rc;
+    *total_ms = ctx->total_ms[CANNY_HIP_STAGE_END + part];
+    *launches = ctx->launches[CANNY_HIP_STAGE_END + part];
     return CANNY_HIP_OK;
 }
 

@@ -323,6 +323,37 @@ hipError_t launch_points_scatter(const uint64_t *strong, const uint8_t *bits, co
                                  const uint32_t *row_offsets, const unsigned long long *offsets, uint32_t *points,
                                  unsigned long long capacity, hipStream_t stream);
 
+// ---- Hough lines (canny_hough.hip) -------------------------------------
+struct HoughGeom {
+    int numangle, numrho;
+    float rho, theta, min_theta;
+};
+constexpr int kHoughMaxLines = 4096;          // CANNY_HIP_HOUGH_MAX_LINES: the sort's keys of one frame fit in LDS
+constexpr int kHoughLdsMax = 160 * 1024;      // what one workgroup may declare on gfx950
+inline size_t hough_accum_bytes(const HoughGeom &hg, int n_frames)
+{
+    return (size_t)n_frames * (hg.numangle + 2) * (size_t)(hg.numrho + 2) * sizeof(int);
+}
+// Accumulator rows a vote workgroup keeps in LDS for a budget in bytes: at least one row if a row fits in LDS at all
+// (then the budget yields), at most 16; 0 = a row does not fit, only the global-atomic form applies.
+int hough_lds_rows(const HoughGeom &hg, int budget_bytes);
+// vote: accum[f] = the whole (numangle + 2) x (numrho + 2) int accumulator of frame f, border included.  Source: points
+// + offsets (CSR; indices >= height * width are skipped), else bits (packed, as above), else the strong plane.
+// tab = numangle cosines then numangle sines (device).  lds_rows > 0: LDS rows, nothing needs zeroing; 0: the accumulator
+// is zeroed, then global atomics.
+hipError_t launch_hough_vote(const uint64_t *strong, const uint8_t *bits, const uint32_t *points,
+                             const unsigned long long *offsets, const HystGeom &g, const HoughGeom &hg, const float *tab,
+                             int *accum, int lds_rows, hipStream_t stream);
+// peaks: counts[f] += peaks of frame f, hist[f * hist_bins + votes] += 1 per peak (both zeroed by the caller)
+hipError_t launch_hough_peaks(const int *accum, int n_frames, const HoughGeom &hg, int threshold, int *counts,
+                              unsigned *hist, int hist_bins, hipStream_t stream);
+// select: the first min(lines_max, counts[f]) peaks by (votes descending, base ascending) into slot f * lines_max + k of
+// lines (2 floats per slot), votes, bases (each may be null).  Workspaces: ties n_frames * numangle (zeroed by the
+// caller), cut n_frames * 8 words, cand n_frames * lines_max keys.  lines_max <= kHoughMaxLines.
+hipError_t launch_hough_select(const int *accum, int n_frames, const HoughGeom &hg, int threshold, int lines_max,
+                               const int *counts, const unsigned *hist, int hist_bins, unsigned *ties, unsigned *cut,
+                               unsigned long long *cand, float *lines, int *votes, unsigned *bases, hipStream_t stream);
+
 // ---- measurement aid ------------------------------------------------------------------------
 // Plain device copy of nbytes (multiple of 16; both pointers 16-byte aligned): what a 1:1 read/write stream reaches.
 hipError_t launch_probe_copy(const void *src, void *dst, size_t nbytes, hipStream_t stream, const LaunchEvents &ev = {});

@@ -1,5 +1,6 @@
 // main.cpp -- the reference's command line (StevenChang5/Canny_Edge src/main.cpp:18-142) without
 // the webcam and the GUI:  ./Main sigma minVal maxVal [-c] [-s] [-i in.pgm|in.ppm|in.jpg] [-o dir] [-p] [-n WxH] [-b dir]
+//        [-l rho,theta_degrees,threshold[,lines_max]]
 //
 // Kept from the reference: the three positionals may appear anywhere relative to the flags
 // (src/main.cpp:29-46); exactly three are required, otherwise the usage text is printed and the
@@ -11,8 +12,12 @@
 // (-n overrides the size); imshow -> PGM (or, with -p, PNG) files in the -o directory.  A binary PPM (P6, maxval 255,
 // RGB) is a colour frame: it is converted on the GPU with canny_hip_to_gray and the OpenCV rule, in place of the
 // reference's cvtColor(frame, gray_frame, COLOR_BGR2GRAY) (:114); -s also writes that plane as canny_step0_gray.pgm.
+// Added: -l runs the Hough line transform of the frame's edge map on the GPU as well (canny_hip_canny_hough) and writes
+// one "rho theta votes" row per detected line, strongest first, to canny_lines.txt in the -o directory (to stdout
+// without -o).  Without -l nothing changes.
 #include <algorithm>
 #include <cctype>
+#include <cmath>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -202,6 +207,35 @@ static int run_batch(const string &dir, const string &outdir, float sigma, int m
     return 0;
 }
 
+// -l: the lines of the frame's edge map, "%.9g %.9g %d" per line
+static int run_hough(const vector<unsigned char> &frame, int height, int width, float sigma, int minVal, int maxVal,
+                     double rho, double theta_deg, int threshold, int lines_max, const string &outdir)
+{
+    const float theta = (float)(theta_deg * M_PI / 180.0);
+    vector<float> lines((size_t)2 * max(lines_max, 1));
+    vector<int> votes((size_t)max(lines_max, 1));
+    int count = 0;
+    canny_hip_ctx *ctx = nullptr;
+    int st = canny_hip_ctx_create(&ctx, 0);
+    if (!st)
+        st = canny_hip_canny_hough(ctx, frame.data(), 1, sigma, minVal, maxVal, height, width, (float)rho, theta, threshold,
+                                   lines_max, 0.0f, (float)M_PI, lines.data(), votes.data(), nullptr, &count);
+    if (st) {
+        fprintf(stderr, "ERROR: -l: %s\n", st == CANNY_HIP_ERR_RUNTIME && ctx ? canny_hip_last_error(ctx) : canny_hip_status_string(st));
+        if (ctx) canny_hip_ctx_destroy(ctx);
+        return 1;
+    }
+    canny_hip_ctx_destroy(ctx);
+    FILE *f = outdir.empty() ? stdout : fopen((outdir + "/canny_lines.txt").c_str(), "w");
+    if (!f) {
+        fprintf(stderr, "ERROR: cannot write %s/canny_lines.txt\n", outdir.c_str());
+        return 1;
+    }
+    for (int k = 0; k < min(count, lines_max); k++) fprintf(f, "%.9g %.9g %d\n", lines[2 * k], lines[2 * k + 1], votes[k]);
+    if (f != stdout) fclose(f);
+    return 0;
+}
+
 int main(int argc, char *argv[])
 {
     // The batch pipeline wants its upload, compute and download streams on separate hardware queues; HIP reads this
@@ -213,6 +247,9 @@ int main(int argc, char *argv[])
     bool use_gpu_entry = false;
     bool show_steps = false;
     string input, outdir, batch_dir;
+    bool want_lines = false;
+    double line_rho = 1.0, line_theta_deg = 1.0;
+    int line_threshold = 0, lines_max = 256;
     int width = WIDTH, height = HEIGHT;
     vector<string> values;
 
@@ -230,6 +267,13 @@ int main(int argc, char *argv[])
             outdir = argv[++i];
         } else if (arg == "-b" && i + 1 < argc) {
             batch_dir = argv[++i];
+        } else if (arg == "-l" && i + 1 < argc) {
+            const int got = sscanf(argv[++i], "%lf,%lf,%d,%d", &line_rho, &line_theta_deg, &line_threshold, &lines_max);
+            if (got < 3) {
+                fprintf(stderr, "ERROR: -l expects rho,theta_degrees,threshold[,lines_max]\n");
+                exit(0);
+            }
+            want_lines = true;
         } else if (arg == "-n" && i + 1 < argc) {
             if (sscanf(argv[++i], "%dx%d", &width, &height) != 2 || width < 2 || height < 2) {
                 fprintf(stderr, "ERROR: -n expects WIDTHxHEIGHT\n");
@@ -251,6 +295,7 @@ int main(int argc, char *argv[])
         fprintf(stderr, "   -i frame: input frame (binary PGM, binary PPM or baseline JPEG)   -n WxH: synthetic frame size   -o dir: output dir\n");
         fprintf(stderr, "   -p: write PNG files instead of PGM\n");
         fprintf(stderr, "   -b dir: run every .pgm / .jpg of dir as one batch, write <name>_edges.pgm\n");
+        fprintf(stderr, "   -l rho,theta_degrees,threshold[,lines_max]: Hough lines of the edge map -> canny_lines.txt in the -o dir\n");
         exit(0);
     }
 
@@ -304,5 +349,8 @@ int main(int argc, char *argv[])
         fprintf(stderr, "ERROR: %s\n", e.what());
         return 1;
     }
+    if (want_lines)
+        return run_hough(frame, height, width, sigma, minVal, maxVal, line_rho, line_theta_deg, line_threshold, lines_max,
+                         outdir);
     return 0;
 }

@@ -52,7 +52,8 @@
 extern "C" {
 #endif
 
-#define CANNY_HIP_VERSION 500        /* 0.5.0: + edge point lists (CSR of pixel indices), compacted on the GPU */
+#define CANNY_HIP_VERSION 600        /* 0.6.0: + Hough lines of the finished map (cv::HoughLines semantics) on the GPU */
+/* 0.5.0: + edge point lists (CSR of pixel indices), compacted on the GPU */
 /* 0.4.1: + canny_hip_selftest_sobel_pixel */
 /* 0.4.0: + per-frame thresholds, explicit or chosen on the GPU (median / quantile) */
 /* 0.3.0: + colour frame input (BGR / RGB / BGRA / RGBA -> gray on the GPU) */
@@ -450,11 +451,82 @@ int canny_hip_canny_points(canny_hip_ctx *ctx, const unsigned char *imgs, int n_
 int canny_hip_points_from_bits(const unsigned char *bits, int height, int width, unsigned int *points,
                                unsigned long long capacity, unsigned long long *count);
 
+/* ---- Hough lines -------------------------------------------------------------------------------------------------------
+ * The standard Hough line transform of a finished edge map, per frame of a batch, on the GPU, in stream order, with no host
+ * round trip: cv::HoughLines semantics (accumulator, local-maximum peaks, strongest lines first), i.e. OpenCV's
+ * HoughLinesStandard restated without its build-dependent parts, so that a few lines of numpy (tests/hough_rule.py) reproduce
+ * every accumulator cell and every returned line bit for bit.  THE RULE:
+ * All float arithmetic is IEEE binary32, round to nearest even, not contracted (no fused multiply-add).
+ * Arguments: rho > 0, theta > 0 (finite), threshold (int), lines_max >= 1, 0 <= min_theta < max_theta <= (float)pi.
+ *   Geometry (double): numangle = floor(((double)max_theta - (double)min_theta) / (double)theta) + 1; if numangle > 1 and
+ *     |pi - (numangle - 1) * (double)theta| < (double)theta / 2 then numangle -= 1;
+ *     numrho = rint_half_even((2.0 * (width + height) + 1.0) / (double)rho).   (3840 x 2160, rho 1, theta pi/180: 180 x 12001)
+ *   Tables (host): irho = 1.0f / rho; float ang = min_theta, advanced by ang = ang + theta in float;
+ *     tab_cos[n] = (float)(cos((double)ang) * (double)irho), tab_sin[n] likewise.  canny_hip_hough_tables returns them; they
+ *     are the only place a transcendental function is used, so the device result depends on no libm.
+ *   Votes: for every set pixel (y, x) = (row, column) of the frame's map and every n < numangle
+ *     r = (int)rint_half_even(fl(fl((float)x * tab_cos[n]) + fl((float)y * tab_sin[n]))) + (numrho - 1) / 2
+ *     accum[(n + 1) * (numrho + 2) + r + 1] += 1.  accum is int, (numangle + 2) x (numrho + 2), its border row / column zero.
+ *   Peaks: cell base = (n + 1) * (numrho + 2) + r + 1, 0 <= n < numangle, 0 <= r < numrho, is a peak iff
+ *     a[base] > threshold && a[base] > a[base - 1] && a[base] >= a[base + 1] && a[base] > a[base - (numrho + 2)] &&
+ *     a[base] >= a[base + (numrho + 2)].
+ *   Order: peaks sorted by (votes descending, base ascending), a total order.  Frame f returns the first
+ *     min(lines_max, n_peaks_f) of them; counts[f] = n_peaks_f, always the TRUE count.
+ *   A line is returned three ways, in slot f * lines_max + k of each array: bases (unsigned), votes (int) and lines, two
+ *     floats per slot: line_rho = ((float)r - (float)(numrho - 1) * 0.5f) * rho, line_theta = min_theta + (float)n * theta.
+ *     Slots k >= min(lines_max, counts[f]) are not written.
+ * The output is the same bytes on every run (integer atomics touch counters only; the final order comes from a sort on a
+ * total order).  Any of lines, votes, bases, accum may be NULL; counts (n_frames ints) is mandatory.  d_accum, if given,
+ * receives n_frames accumulators of (numangle + 2) * (numrho + 2) ints, border included; otherwise they live in a context
+ * workspace of that size.
+ * Statuses: rho / theta non-positive, NaN or infinite, a theta range outside [0, (float)pi] or empty, lines_max < 1, a NULL
+ * counts -> CANNY_HIP_ERR_INVALID; lines_max > CANNY_HIP_HOUGH_MAX_LINES, an accumulator of 2^31 cells or more, numrho < 1
+ * -> CANNY_HIP_ERR_UNSUPPORTED; nothing is written in either case.
+ * "hough_path" (canny_hip_ctx_set_option): 0 automatic (default), 1 global integer atomics into a zeroed accumulator,
+ *   2 accumulator rows in LDS.  The LDS form needs one row, numrho ints, to fit in the 160 KiB of a workgroup (numrho <=
+ *   40960: every frame up to 8K at rho >= 0.6); beyond that 0 takes the global form and 2 is CANNY_HIP_ERR_UNSUPPORTED.  Same
+ *   bytes either way.  "tune_hough_lds_kb": LDS budget of a vote workgroup in KiB (0 = automatic, 48), for A/B.
+ * The three parts are timed by canny_hip_hough_profile_get (0 vote, 1 peaks, 2 select + sort).
+ * Not covered -- follow-ups: probabilistic / segment output (HoughLinesP), multi-scale srn / stn, weighted votes, circles,
+ * the three-stream batch pipeline, the multi-GPU sharder, colour and automatic-threshold variants. */
+#define CANNY_HIP_HOUGH_MAX_LINES 4096 /* largest lines_max: the 64-bit sort keys of one frame fit in LDS */
+/* Host-only, no device needed. */
+int canny_hip_hough_geometry(int height, int width, float rho, float theta, float min_theta, float max_theta,
+                             int *numangle, int *numrho);
+int canny_hip_hough_tables(float rho, float theta, float min_theta, int numangle, float *tab_cos, float *tab_sin);
+/* (line_rho, line_theta) of an accumulator cell, as the device writes them. */
+int canny_hip_hough_line_of(unsigned int base, int numrho, float rho, float theta, float min_theta, float *line_rho,
+                            float *line_theta);
+/* From a CSR point list as canny_hip_dev_canny_points writes it: d_points must hold all d_offsets[n_frames] entries (a list
+ * truncated by its capacity is not a valid input).  An index >= height * width is not a pixel: it casts no vote and causes
+ * no access (what the result then means is up to the caller; the call stays memory-safe).  Asynchronous. */
+int canny_hip_dev_hough_points(canny_hip_ctx *ctx, const unsigned int *d_points, const unsigned long long *d_offsets,
+                               int n_frames, int height, int width, float rho, float theta, int threshold, int lines_max,
+                               float min_theta, float max_theta, float *d_lines, int *d_votes, unsigned int *d_bases,
+                               int *d_counts, int *d_accum);
+/* From packed bit maps in the layout of canny_hip_dev_canny_bits (padding bits ignored).  Asynchronous. */
+int canny_hip_dev_hough_bits(canny_hip_ctx *ctx, const unsigned char *d_bits, int n_frames, int height, int width,
+                             float rho, float theta, int threshold, int lines_max, float min_theta, float max_theta,
+                             float *d_lines, int *d_votes, unsigned int *d_bases, int *d_counts, int *d_accum);
+/* canny_hip_dev_canny unchanged (d_edges as in canny_hip_dev_canny_points: the s16 map, or NULL), then the transform of its
+ * map queued behind it on the same stream, read from the converged hysteresis bit-plane: no point list, no capacity.
+ * Completion contract and statuses as canny_hip_dev_canny_points; the result follows the MAP (max_val > 255: all counts 0). */
+int canny_hip_dev_canny_hough(canny_hip_ctx *ctx, const unsigned char *d_img, float sigma, int min_val, int max_val,
+                              int height, int width, int n_frames, short *d_edges, float rho, float theta, int threshold,
+                              int lines_max, float min_theta, float max_theta, float *d_lines, int *d_votes,
+                              unsigned int *d_bases, int *d_counts, int *d_accum);
+/* Host buffers, synchronous: upload, canny, transform; the counts come down, then only the filled slots of each frame. */
+int canny_hip_canny_hough(canny_hip_ctx *ctx, const unsigned char *imgs, int n_frames, float sigma, int min_val,
+                          int max_val, int height, int width, float rho, float theta, int threshold, int lines_max,
+                          float min_theta, float max_theta, float *lines, int *votes, unsigned int *bases, int *counts);
+
 /* ---- per-stage HIP-event timing (events are recorded on the launch stream) ----------------- */
 int canny_hip_profile_enable(canny_hip_ctx *ctx, int on);
 int canny_hip_profile_reset(canny_hip_ctx *ctx);
 /* Synchronises the stream, then returns accumulated device milliseconds and launch count. */
 int canny_hip_profile_get(canny_hip_ctx *ctx, int stage, double *total_ms, long *launches);
+/* The same for the Hough passes, which are not stages of the map: part 0 vote, 1 peaks, 2 select + sort. */
+int canny_hip_hough_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches);
 
 /* ---- self-test hooks used by the GPU test-suite -------------------------------------------- */
 /* Runs the DEVICE magnitude / angle-bin functions over every (gx,gy) in [-lim,lim]^2 and writes
