@@ -94,6 +94,8 @@ EXPORTS = (
     "canny_hip_points_from_bits",
     "canny_hip_hough_geometry", "canny_hip_hough_tables", "canny_hip_hough_line_of", "canny_hip_dev_hough_points",
     "canny_hip_dev_hough_bits", "canny_hip_dev_canny_hough", "canny_hip_canny_hough", "canny_hip_hough_profile_get",
+    "canny_hip_dev_canny_components", "canny_hip_dev_components_bits", "canny_hip_canny_components",
+    "canny_hip_components_from_bits", "canny_hip_components_profile_get",
 )
 
 _lib: Optional[C.CDLL] = None
@@ -211,6 +213,11 @@ def load() -> C.CDLL:
         "canny_hip_dev_canny_hough": ([p, p, f, i, i, i, i, i, p, f, f, i, i, f, f, p, p, p, p, p], i),
         "canny_hip_canny_hough": ([p, p, i, f, i, i, i, i, f, f, i, i, f, f, p, p, p, p], i),
         "canny_hip_hough_profile_get": ([p, i, C.POINTER(C.c_double), C.POINTER(C.c_long)], i),
+        "canny_hip_dev_canny_components": ([p, p, f, i, i, i, i, i, p, i, p, p, p, C.c_ulonglong, p], i),
+        "canny_hip_dev_components_bits": ([p, p, i, i, i, i, p, p, p, C.c_ulonglong, p], i),
+        "canny_hip_canny_components": ([p, p, i, f, i, i, i, i, i, p, p, p, C.c_ulonglong, p], i),
+        "canny_hip_components_from_bits": ([p, i, i, i, p, p, C.c_ulonglong, C.POINTER(C.c_ulonglong)], i),
+        "canny_hip_components_profile_get": ([p, i, C.POINTER(C.c_double), C.POINTER(C.c_long)], i),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -263,6 +270,36 @@ def points_from_bits(bits, height: int, width: int, capacity: Optional[int] = No
     if st:
         raise CannyHipError(st, "points_from_bits")
     return pts if capacity is None else (pts[:min(cap, n.value)], n.value)
+
+
+CC_STATS = 6                                                    # ints per record: CANNY_HIP_CC_STAT_*
+CC_LEFT, CC_TOP, CC_WIDTH, CC_HEIGHT, CC_AREA, CC_FIRST = range(6)
+CC_PARTS = ("link", "resolve", "number", "write")
+
+
+def components_from_bits(bits, height: int, width: int, min_area: int = 1, want_labels: bool = True,
+                         capacity: Optional[int] = None):
+    """Host-only: the 8-connected components of one packed bit map (numpy.packbits(mask, axis=-1); padding bits ignored)
+    with at least min_area pixels, numbered 1..K by ascending first pixel -- scipy.ndimage.label(mask, np.ones((3, 3)))
+    for min_area <= 1.  Returns (labels int32 [height, width] or None, stats int32 [K, 6], K); with a capacity, stats
+    holds the first min(K, capacity) records and K is still the true count."""
+    b = np.ascontiguousarray(bits, dtype=np.uint8)
+    if b.size != height * ((width + 7) // 8):
+        raise ValueError(f"expected {height} rows of {(width + 7) // 8} bytes, got {b.size} bytes")
+    L = load()
+    n = C.c_ulonglong(0)
+    if capacity is None:
+        st = L.canny_hip_components_from_bits(_hp(b), height, width, min_area, None, None, 0, C.byref(n))
+        if st:
+            raise CannyHipError(st, "components_from_bits")
+    cap = n.value if capacity is None else int(capacity)
+    labels = np.empty((height, width), np.int32) if want_labels else None
+    stats = np.empty((cap, CC_STATS), np.int32)
+    st = L.canny_hip_components_from_bits(_hp(b), height, width, min_area, _hp(labels) if want_labels else None,
+                                          _hp(stats) if cap else None, cap, C.byref(n))
+    if st:
+        raise CannyHipError(st, "components_from_bits")
+    return labels, stats[:min(cap, n.value)], n.value
 
 
 HOUGH_MAX_LINES = 4096
@@ -627,6 +664,62 @@ class Context:
         self._check(self._L.canny_hip_dev_points_from_bits(self._h, C.c_void_p(d_bits), h, w, n,
                                                            C.c_void_p(d_points or None), capacity,
                                                            C.c_void_p(d_offsets)), "dev_points_from_bits")
+
+    # ---- connected components of the finished map ----------------------------------------
+    def canny_components(self, imgs, sigma: float, min_val: int, max_val: int, min_area: int = 1,
+                         want_labels: bool = True, want_kept: bool = False, capacity: Optional[int] = None):
+        """canny(), then the 8-connected components of each map with at least min_area pixels, numbered 1..K_f by
+        ascending first pixel: imgs (H, W) or (N, H, W) uint8 -> (labels int32 [N, H, W] or None, kept uint8 [N, H, W] or
+        None, stats int32 [total, 6], offsets uint64 [N + 1]); the record of label k of frame f is stats[offsets[f] + k - 1]
+        = (left, top, width, height, area, first).  capacity=None never returns a truncated table (a batch with more
+        components than one per 64 pixels runs twice); with a capacity, stats holds the first min(offsets[-1], capacity)
+        records and offsets still holds the true counts."""
+        a = np.ascontiguousarray(imgs, dtype=np.uint8)
+        if a.ndim == 2:
+            a = a[None]
+        if a.ndim != 3:
+            raise ValueError("expected uint8 [H, W] or [n_frames, H, W]")
+        n, h, w = a.shape
+        offsets = np.zeros(n + 1, np.uint64)
+        labels = np.empty((n, h, w), np.int32) if want_labels else None
+        kept = np.empty((n, h, w), np.uint8) if want_kept else None
+        cap = max(1024, a.size // 64) if capacity is None else int(capacity)
+        while True:
+            stats = np.empty((cap, CC_STATS), np.int32)
+            self._check(self._L.canny_hip_canny_components(
+                self._h, _hp(a), n, sigma, min_val, max_val, h, w, min_area, _hp(labels) if want_labels else None,
+                _hp(kept) if want_kept else None, _hp(stats) if cap else None, cap, _hp(offsets)), "canny_components")
+            total = int(offsets[-1])
+            if capacity is not None or total <= cap:
+                return labels, kept, stats[:min(total, cap)], offsets
+            cap = total
+
+    def dev_canny_components(self, d_img: int, sigma: float, min_val: int, max_val: int, h: int, w: int, n: int,
+                             min_area: int, d_labels: int, d_kept_u8: int, d_stats: int, capacity: int, d_offsets: int,
+                             d_edges: int = 0):
+        """dev_canny, then its map labelled on the same stream: d_labels (n*h*w int32), d_kept_u8 (n*h*w uint8), d_stats
+        (capacity records of 6 int32) -- each a device pointer or 0 --, d_offsets (n + 1 uint64, device), d_edges (the
+        s16 map, device) or 0."""
+        v = C.c_void_p
+        self._check(self._L.canny_hip_dev_canny_components(self._h, v(d_img), sigma, min_val, max_val, h, w, n,
+                                                           v(d_edges or None), min_area, v(d_labels or None),
+                                                           v(d_kept_u8 or None), v(d_stats or None), capacity,
+                                                           v(d_offsets or None)), "dev_canny_components")
+
+    def dev_components_bits(self, d_bits: int, h: int, w: int, n: int, min_area: int, d_labels: int, d_kept_u8: int,
+                            d_stats: int, capacity: int, d_offsets: int):
+        """The labelling alone on device bit maps (layout of dev_canny_bits, any byte alignment, padding ignored)."""
+        v = C.c_void_p
+        self._check(self._L.canny_hip_dev_components_bits(self._h, v(d_bits or None), h, w, n, min_area,
+                                                          v(d_labels or None), v(d_kept_u8 or None), v(d_stats or None),
+                                                          capacity, v(d_offsets or None)), "dev_components_bits")
+
+    def components_profile_get(self, part: int) -> Tuple[float, int]:
+        """(total ms, launch groups) of part 0 link, 1 resolve, 2 number, 3 write (CC_PARTS)."""
+        ms, n = C.c_double(0.0), C.c_long(0)
+        self._check(self._L.canny_hip_components_profile_get(self._h, part, C.byref(ms), C.byref(n)),
+                    "components_profile_get")
+        return ms.value, n.value
 
     # ---- Hough lines of the finished map (cv::HoughLines semantics; DESIGN.md section 13) -----------------------
     def canny_hough(self, imgs, sigma: float, min_val: int, max_val: int, rho: float = 1.0, theta: float = np.pi / 180,

@@ -21,6 +21,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cctype>
+#include <climits>
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
@@ -382,6 +383,9 @@ struct canny_hip_ctx {
     int hough_tab_n = 0;
     int hough_path = 0;   // 0 auto (LDS rows when a row fits), 1 global atomics, 2 LDS rows
     int hough_lds_kb = 0; // A/B: LDS budget of a vote workgroup in KiB, 0 = automatic
+    // connected components: the parent array (4 B/px) when the caller passes no label plane; per-frame totals and per-row
+    // counts / prefixes of the numbering scan
+    DevBuf cc_parent, cc_ws;
     DevBuf plane_s, plane_c, stamps, flags; // hysteresis bit-planes / scheduling words
     DevBuf io[4];     // staging for the host-pointer stage functions
     unsigned *host_flags = nullptr;     // pinned + mapped, 4 words per lane: last_change, domain, sequence number, spare
@@ -404,8 +408,10 @@ struct canny_hip_ctx {
     bool prof = false;
     unsigned prof_mask = ~0u; // stages whose launches get an event pair (each pair costs a few us of stream time)
     unsigned prof_every = 1;  // ... and only every prof_every-th launch group of a stage gets one
-    // slots: the stages, then the three Hough parts (canny_hip_hough_profile_get)
-    static constexpr int kProfSlots = CANNY_HIP_STAGE_END + 3;
+    // slots: the stages, then the three Hough parts (canny_hip_hough_profile_get), then the four parts of the component
+    // labelling (canny_hip_components_profile_get)
+    static constexpr int kProfHough = CANNY_HIP_STAGE_END, kProfComponents = CANNY_HIP_STAGE_END + 3;
+    static constexpr int kProfSlots = kProfComponents + CANNY_HIP_CC_PARTS;
     unsigned prof_seen[kProfSlots] = {0};
     std::vector<EventPair> pending[kProfSlots];
     std::vector<EventPair> pool;
@@ -1123,6 +1129,71 @@ int dev_canny_points_count(canny_hip_ctx *ctx, const unsigned char *d_img, float
     return dev_points_count(ctx, *strong_out, nullptr, make_hyst_geom(h, w, n), d_offsets);
 }
 
+// ---- connected components (canny_components.hip) ---------------------------
+struct CcOut {
+    int *labels;
+    unsigned char *kept;
+    int *stats;
+    unsigned long long capacity;
+    unsigned long long *offsets;
+};
+
+// The labelling of one source (the context's strong plane or packed bits), queued on the context's stream.
+int dev_components(canny_hip_ctx *ctx, const uint64_t *strong, const uint8_t *bits, const HystGeom &g, int min_area,
+                   const CcOut &out)
+{
+    const size_t rows = (size_t)g.n_frames * g.height;
+    int *parent = out.labels;
+    if (!parent) {
+        HIP_TRY(ctx, ctx->cc_parent.ensure(npx(g.height, g.width, g.n_frames) * sizeof(int)));
+        parent = (int *)ctx->cc_parent.p;
+    }
+    HIP_TRY(ctx, ctx->cc_ws.ensure(g.n_frames * sizeof(unsigned long long) + rows * sizeof(uint32_t)));
+    unsigned long long *totals = (unsigned long long *)ctx->cc_ws.p;
+    uint32_t *row_words = (uint32_t *)(totals + g.n_frames);
+    {
+        StageTimer tm(ctx, canny_hip_ctx::kProfComponents + CANNY_HIP_CC_PART_LINK);
+        HIP_TRY(ctx, launch_cc_link(strong, bits, g, parent, ctx->stream));
+    }
+    {
+        StageTimer tm(ctx, canny_hip_ctx::kProfComponents + CANNY_HIP_CC_PART_RESOLVE);
+        HIP_TRY(ctx, launch_cc_resolve(strong, bits, g, parent, ctx->stream));
+    }
+    {
+        StageTimer tm(ctx, canny_hip_ctx::kProfComponents + CANNY_HIP_CC_PART_NUMBER);
+        HIP_TRY(ctx, launch_cc_count(strong, bits, g, parent, min_area, row_words, ctx->stream));
+        HIP_TRY(ctx, launch_points_scan(row_words, totals, out.offsets, g.height, g.n_frames, ctx->stream));
+        if (out.labels || out.kept || (out.stats && out.capacity))
+            HIP_TRY(ctx, launch_cc_number(strong, bits, g, parent, min_area, row_words, out.offsets, out.stats,
+                                          out.capacity, ctx->stream));
+    }
+    if (out.labels || out.kept) {
+        StageTimer tm(ctx, canny_hip_ctx::kProfComponents + CANNY_HIP_CC_PART_WRITE);
+        HIP_TRY(ctx, launch_cc_write(strong, bits, g, parent, out.labels, out.kept, ctx->stream));
+    }
+    return CANNY_HIP_OK;
+}
+
+// dev_canny (unchanged), then the labelling of its map from the converged strong plane.  The result follows the MAP:
+// max_val > 255 leaves no edge pixel (see dev_canny_points_count).
+int dev_canny_components(canny_hip_ctx *ctx, const unsigned char *d_img, float sigma, int lo, int hi, int h, int w, int n,
+                         short *d_edges, int min_area, const CcOut &out)
+{
+    int rc;
+    if (!d_edges) {
+        HIP_TRY(ctx, ctx->edges16.ensure(npx(h, w, n) * sizeof(short)));
+        d_edges = (short *)ctx->edges16.p;
+    }
+    if ((rc = dev_canny(ctx, d_img, sigma, lo, hi, h, w, n, d_edges))) return rc;
+    if (hi > 255) {
+        HIP_TRY(ctx, hipMemsetAsync(out.offsets, 0, ((size_t)n + 1) * sizeof(unsigned long long), ctx->stream));
+        if (out.labels) HIP_TRY(ctx, hipMemsetAsync(out.labels, 0, npx(h, w, n) * sizeof(int), ctx->stream));
+        if (out.kept) HIP_TRY(ctx, hipMemsetAsync(out.kept, 0, npx(h, w, n), ctx->stream));
+        return CANNY_HIP_OK;
+    }
+    return dev_components(ctx, (const uint64_t *)ctx->plane_s.p, nullptr, make_hyst_geom(h, w, n), min_area, out);
+}
+
 // ---- Hough lines (canny_hough.hip) -----------------------------------------
 struct HoughOut {
     float *d_lines;
@@ -1394,6 +1465,8 @@ void canny_hip_ctx_destroy(canny_hip_ctx *ctx)
     ctx->hough_accum.release();
     ctx->hough_ws.release();
     ctx->hough_tab.release();
+    ctx->cc_parent.release();
+    ctx->cc_ws.release();
     ctx->stamps.release();
     ctx->flags.release();
     for (auto &b : ctx->io) b.release();
@@ -2626,6 +2699,151 @@ int canny_hip_points_from_bits(const unsigned char *bits, int height, int width,
     return CANNY_HIP_OK;
 }
 
+// ---- connected components ----------------------------------------------------------------------------
+int canny_hip_dev_canny_components(canny_hip_ctx *ctx, const unsigned char *d_img, float sigma, int min_val, int max_val,
+                                   int height, int width, int n_frames, short *d_edges, int min_area, int *d_labels,
+                                   unsigned char *d_kept_u8, int *d_stats, unsigned long long capacity,
+                                   unsigned long long *d_offsets)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!d_img || !d_offsets || (!d_stats && capacity)) return CANNY_HIP_ERR_INVALID;
+    if ((rc = check_dims(height, width, n_frames))) return rc;
+    return dev_canny_components(ctx, d_img, sigma, min_val, max_val, height, width, n_frames, d_edges, min_area,
+                                CcOut{d_labels, d_kept_u8, d_stats, capacity, d_offsets});
+}
+
+int canny_hip_dev_components_bits(canny_hip_ctx *ctx, const unsigned char *d_bits, int height, int width, int n_frames,
+                                  int min_area, int *d_labels, unsigned char *d_kept_u8, int *d_stats,
+                                  unsigned long long capacity, unsigned long long *d_offsets)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!d_bits || !d_offsets || (!d_stats && capacity)) return CANNY_HIP_ERR_INVALID;
+    if ((rc = check_dims(height, width, n_frames)) || (rc = finish_pending(ctx))) return rc;
+    return dev_components(ctx, nullptr, d_bits, make_hyst_geom(height, width, n_frames), min_area,
+                          CcOut{d_labels, d_kept_u8, d_stats, capacity, d_offsets});
+}
+
+int canny_hip_canny_components(canny_hip_ctx *ctx, const unsigned char *imgs, int n_frames, float sigma, int min_val,
+                               int max_val, int height, int width, int min_area, int *labels, unsigned char *kept_u8,
+                               int *stats, unsigned long long capacity, unsigned long long *offsets)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!imgs || !offsets || (!stats && capacity)) return CANNY_HIP_ERR_INVALID;
+    if ((rc = check_dims(height, width, n_frames))) return rc;
+    const size_t n = npx(height, width, n_frames);
+    const size_t off_bytes = ((size_t)n_frames + 1) * sizeof(unsigned long long);
+    // the records of a frame cannot outnumber its pixels: a larger capacity buys nothing
+    const unsigned long long cap = std::min<unsigned long long>(capacity, n);
+    const size_t stats_bytes = (size_t)cap * CANNY_HIP_CC_STATS * sizeof(int);
+    if ((rc = h2d(ctx, ctx->io[0], imgs, n))) return rc;
+    // one staging block: offsets | stats | kept; the label plane has a block of its own
+    const size_t stats_at = (off_bytes + 15) & ~(size_t)15, kept_at = (stats_at + stats_bytes + 15) & ~(size_t)15;
+    HIP_TRY(ctx, ctx->io[1].ensure(kept_at + (kept_u8 ? n : 0)));
+    if (labels) HIP_TRY(ctx, ctx->io[2].ensure(n * sizeof(int)));
+    char *d = (char *)ctx->io[1].p;
+    const CcOut out{labels ? (int *)ctx->io[2].p : nullptr, kept_u8 ? (unsigned char *)(d + kept_at) : nullptr,
+                    cap ? (int *)(d + stats_at) : nullptr, cap, (unsigned long long *)d};
+    if ((rc = dev_canny_components(ctx, (const unsigned char *)ctx->io[0].p, sigma, min_val, max_val, height, width,
+                                   n_frames, nullptr, min_area, out)))
+        return rc;
+    // the offsets come down first: they say how many records there are to download
+    std::vector<unsigned long long> off((size_t)n_frames + 1);
+    if ((rc = d2h_sync(ctx, off.data(), out.offsets, off_bytes))) return rc;
+    const unsigned long long n_rec = std::min(off[n_frames], cap);
+    if (n_rec)
+        HIP_TRY(ctx, hipMemcpyAsync(stats, out.stats, (size_t)n_rec * CANNY_HIP_CC_STATS * sizeof(int),
+                                    hipMemcpyDeviceToHost, ctx->stream));
+    if (labels) HIP_TRY(ctx, hipMemcpyAsync(labels, out.labels, n * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    if (kept_u8) HIP_TRY(ctx, hipMemcpyAsync(kept_u8, out.kept, n, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    std::memcpy(offsets, off.data(), off_bytes);
+    return CANNY_HIP_OK;
+}
+
+// The rule on one host bit map: two passes with a union-find over provisional labels.  Provisional labels are handed out
+// in raster order and the smaller root always wins, so a component's root label is the one its first pixel received and
+// ascending root labels are ascending first pixels.
+int canny_hip_components_from_bits(const unsigned char *bits, int height, int width, int min_area, int *labels,
+                                   int *stats, unsigned long long capacity, unsigned long long *count)
+{
+    if (!bits || !count || (!stats && capacity)) return CANNY_HIP_ERR_INVALID;
+    int rc = check_dims(height, width, 1);
+    if (rc) return rc;
+    const size_t row_bytes = ((size_t)width + 7) / 8, n = (size_t)height * width;
+    std::vector<int> own;
+    if (!labels) {
+        own.resize(n);
+        labels = own.data();
+    }
+    std::vector<int> parent(1, 0); // provisional label -> a smaller label of the same component (itself: a root)
+    auto find = [&](int x) {
+        while (parent[x] != x) x = parent[x] = parent[parent[x]];
+        return x;
+    };
+    auto unite = [&](int a, int b) {
+        a = find(a), b = find(b);
+        if (a < b) parent[b] = a;
+        else parent[a] = b;
+        return a < b ? a : b;
+    };
+    auto set_at = [&](int y, int x) { return (bits[(size_t)y * row_bytes + (x >> 3)] >> (7 - (x & 7))) & 1; };
+    for (int y = 0; y < height; y++) {
+        int *row = labels + (size_t)y * width;
+        const int *up = y ? row - width : nullptr;
+        for (int x = 0; x < width; x++) {
+            if (!set_at(y, x)) {
+                row[x] = 0;
+                continue;
+            }
+            int l = x ? row[x - 1] : 0;
+            if (up)
+                for (int dx = -1; dx <= 1; dx++) {
+                    const int xx = x + dx;
+                    if (xx < 0 || xx >= width || !up[xx]) continue;
+                    l = l ? unite(l, up[xx]) : up[xx];
+                }
+            if (!l) {
+                l = (int)parent.size();
+                parent.push_back(l);
+            }
+            row[x] = l;
+        }
+    }
+    const size_t n_prov = parent.size();
+    // per root: area, box, first pixel
+    std::vector<int> area(n_prov, 0), left(n_prov, INT_MAX), top(n_prov, INT_MAX), right(n_prov, -1), bottom(n_prov, -1),
+        first(n_prov, -1);
+    for (int y = 0; y < height; y++) {
+        const int *row = labels + (size_t)y * width;
+        for (int x = 0; x < width; x++) {
+            if (!row[x]) continue;
+            const int r = find(row[x]);
+            if (!area[r]++) first[r] = (int)((size_t)y * width + x), top[r] = y;
+            left[r] = std::min(left[r], x), right[r] = std::max(right[r], x), bottom[r] = y;
+        }
+    }
+    std::vector<int> number(n_prov, 0);
+    unsigned long long k = 0;
+    for (size_t r = 1; r < n_prov; r++) {
+        if (parent[r] != (int)r || area[r] < min_area) continue;
+        if (k < capacity) {
+            int *rec = stats + k * CANNY_HIP_CC_STATS;
+            rec[CANNY_HIP_CC_STAT_LEFT] = left[r], rec[CANNY_HIP_CC_STAT_TOP] = top[r];
+            rec[CANNY_HIP_CC_STAT_WIDTH] = right[r] - left[r] + 1, rec[CANNY_HIP_CC_STAT_HEIGHT] = bottom[r] - top[r] + 1;
+            rec[CANNY_HIP_CC_STAT_AREA] = area[r], rec[CANNY_HIP_CC_STAT_FIRST] = first[r];
+        }
+        number[r] = (int)++k;
+    }
+    if (own.empty())
+        for (size_t i = 0; i < n; i++)
+            if (labels[i]) labels[i] = number[find(labels[i])];
+    *count = k;
+    return CANNY_HIP_OK;
+}
+
 // ---- profiling --------------------------------------------------------------------------------------
 int canny_hip_profile_enable(canny_hip_ctx *ctx, int on)
 {
@@ -2821,6 +3039,17 @@ int canny_hip_hough_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, 
     if ((rc = profile_collect(ctx))) return rc;
     *total_ms = ctx->total_ms[CANNY_HIP_STAGE_END + part];
     *launches = ctx->launches[CANNY_HIP_STAGE_END + part];
+    return CANNY_HIP_OK;
+}
+
+int canny_hip_components_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches)
+{
+    if (part < 0 || part >= CANNY_HIP_CC_PARTS || !total_ms || !launches) return CANNY_HIP_ERR_INVALID;
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if ((rc = profile_collect(ctx))) return rc;
+    *total_ms = ctx->total_ms[canny_hip_ctx::kProfComponents + part];
+    *launches = ctx->launches[canny_hip_ctx::kProfComponents + part];
     return CANNY_HIP_OK;
 }
 

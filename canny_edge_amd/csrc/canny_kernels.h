@@ -354,6 +354,30 @@ hipError_t launch_hough_select(const int *accum, int n_frames, const HoughGeom &
                                const int *counts, const unsigned *hist, int hist_bins, unsigned *ties, unsigned *cut,
                                unsigned long long *cand, float *lines, int *votes, unsigned *bases, hipStream_t stream);
 
+// ---- Connected components (canny_components.hip) -----------------------
+// Source as for the point lists: the strong plane of geometry g, or -- bits != nullptr -- a packed bit map.
+// parent: n_frames * height * width ints, indexed by pixel, touched at run starts only (a run = a maximal row of set
+// pixels within one 64-pixel word); it may be the label plane that launch_cc_write fills.  height * width < 2^31.
+// The four launchers run in this order on one stream; their phases are described at the head of canny_components.hip.
+// link: parent[s] = s, then the union of touching runs (8-connectivity) -> forest whose roots are the components' first pixels.
+hipError_t launch_cc_link(const uint64_t *strong, const uint8_t *bits, const HystGeom &g, int *parent, hipStream_t stream);
+// resolve: every run start points at its root; a root's entry = INT_MIN + the component's area.
+hipError_t launch_cc_resolve(const uint64_t *strong, const uint8_t *bits, const HystGeom &g, int *parent,
+                             hipStream_t stream);
+// count: row_counts[f * height + y] = roots of that row with area >= min_area (then launch_points_scan numbers them).
+hipError_t launch_cc_count(const uint64_t *strong, const uint8_t *bits, const HystGeom &g, const int *parent, int min_area,
+                           uint32_t *row_counts, hipStream_t stream);
+// number: every run start's entry becomes its component's number (1 .. K_f by ascending first pixel, 0 = dropped); the
+// 6-int records (LEFT, TOP, WIDTH, HEIGHT, AREA, FIRST) of the numbers whose position offsets[f] + k - 1 lies below
+// capacity are written into stats (may be null).
+hipError_t launch_cc_number(const uint64_t *strong, const uint8_t *bits, const HystGeom &g, int *parent, int min_area,
+                            const uint32_t *row_offsets, const unsigned long long *offsets, int *stats,
+                            unsigned long long capacity, hipStream_t stream);
+// write: labels[f][y][x] = the entry of the pixel's run start, 0 off the map (every pixel is stored); kept likewise as
+// 255 / 0.  Either may be null; labels may be `entries` itself.
+hipError_t launch_cc_write(const uint64_t *strong, const uint8_t *bits, const HystGeom &g, const int *entries, int *labels,
+                           uint8_t *kept, hipStream_t stream);
+
 // ---- measurement aid ------------------------------------------------------------------------
 // Plain device copy of nbytes (multiple of 16; both pointers 16-byte aligned): what a 1:1 read/write stream reaches.
 hipError_t launch_probe_copy(const void *src, void *dst, size_t nbytes, hipStream_t stream, const LaunchEvents &ev = {});

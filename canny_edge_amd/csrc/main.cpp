@@ -1,6 +1,6 @@
 // main.cpp -- the reference's command line (StevenChang5/Canny_Edge src/main.cpp:18-142) without
 // the webcam and the GUI:  ./Main sigma minVal maxVal [-c] [-s] [-i in.pgm|in.ppm|in.jpg] [-o dir] [-p] [-n WxH] [-b dir]
-//        [-l rho,theta_degrees,threshold[,lines_max]]
+//        [-l rho,theta_degrees,threshold[,lines_max]] [-m min_area]
 //
 // Kept from the reference: the three positionals may appear anywhere relative to the flags
 // (src/main.cpp:29-46); exactly three are required, otherwise the usage text is printed and the
@@ -15,6 +15,10 @@
 // Added: -l runs the Hough line transform of the frame's edge map on the GPU as well (canny_hip_canny_hough) and writes
 // one "rho theta votes" row per detected line, strongest first, to canny_lines.txt in the -o directory (to stdout
 // without -o).  Without -l nothing changes.
+// Added: -m labels the 8-connected components of the frame's edge map on the GPU (canny_hip_canny_components), drops those
+// with fewer than min_area pixels and writes one "label left top width height area" row per kept component to
+// canny_components.txt and the filtered map to canny_kept.pgm (.png with -p) in the -o directory (rows to stdout without
+// -o).  Without -m nothing changes.
 #include <algorithm>
 #include <cctype>
 #include <cmath>
@@ -236,6 +240,52 @@ static int run_hough(const vector<unsigned char> &frame, int height, int width, 
     return 0;
 }
 
+// -m: the kept components of the frame's edge map and the map without the dropped ones
+static int run_components(const vector<unsigned char> &frame, int height, int width, float sigma, int minVal, int maxVal,
+                          int min_area, const string &outdir)
+{
+    const size_t n = (size_t)height * width;
+    vector<unsigned char> kept(n);
+    vector<int> stats;
+    unsigned long long offsets[2] = {0, 0};
+    canny_hip_ctx *ctx = nullptr;
+    int st = canny_hip_ctx_create(&ctx, 0);
+    // counts first, then exactly the records there are
+    if (!st)
+        st = canny_hip_canny_components(ctx, frame.data(), 1, sigma, minVal, maxVal, height, width, min_area, nullptr,
+                                        nullptr, nullptr, 0, offsets);
+    if (!st) {
+        stats.resize((size_t)offsets[1] * CANNY_HIP_CC_STATS + 1);
+        st = canny_hip_canny_components(ctx, frame.data(), 1, sigma, minVal, maxVal, height, width, min_area, nullptr,
+                                        kept.data(), stats.data(), offsets[1], offsets);
+    }
+    if (st) {
+        fprintf(stderr, "ERROR: -m: %s\n", st == CANNY_HIP_ERR_RUNTIME && ctx ? canny_hip_last_error(ctx) : canny_hip_status_string(st));
+        if (ctx) canny_hip_ctx_destroy(ctx);
+        return 1;
+    }
+    canny_hip_ctx_destroy(ctx);
+    FILE *f = outdir.empty() ? stdout : fopen((outdir + "/canny_components.txt").c_str(), "w");
+    if (!f) {
+        fprintf(stderr, "ERROR: cannot write %s/canny_components.txt\n", outdir.c_str());
+        return 1;
+    }
+    for (unsigned long long k = 0; k < offsets[1]; k++) {
+        const int *r = stats.data() + k * CANNY_HIP_CC_STATS;
+        fprintf(f, "%llu %d %d %d %d %d\n", k + 1, r[CANNY_HIP_CC_STAT_LEFT], r[CANNY_HIP_CC_STAT_TOP],
+                r[CANNY_HIP_CC_STAT_WIDTH], r[CANNY_HIP_CC_STAT_HEIGHT], r[CANNY_HIP_CC_STAT_AREA]);
+    }
+    if (f != stdout) fclose(f);
+    if (!outdir.empty()) {
+        const string path = outdir + "/canny_kept" + (png_output ? ".png" : ".pgm");
+        if (!write_frame(path, kept.data(), height, width)) {
+            fprintf(stderr, "ERROR: cannot write %s\n", path.c_str());
+            return 1;
+        }
+    }
+    return 0;
+}
+
 int main(int argc, char *argv[])
 {
     // The batch pipeline wants its upload, compute and download streams on separate hardware queues; HIP reads this
@@ -250,6 +300,8 @@ int main(int argc, char *argv[])
     bool want_lines = false;
     double line_rho = 1.0, line_theta_deg = 1.0;
     int line_threshold = 0, lines_max = 256;
+    bool want_components = false;
+    int min_area = 1;
     int width = WIDTH, height = HEIGHT;
     vector<string> values;
 
@@ -274,6 +326,12 @@ int main(int argc, char *argv[])
                 exit(0);
             }
             want_lines = true;
+        } else if (arg == "-m" && i + 1 < argc) {
+            if (sscanf(argv[++i], "%d", &min_area) != 1) {
+                fprintf(stderr, "ERROR: -m expects min_area\n");
+                exit(0);
+            }
+            want_components = true;
         } else if (arg == "-n" && i + 1 < argc) {
             if (sscanf(argv[++i], "%dx%d", &width, &height) != 2 || width < 2 || height < 2) {
                 fprintf(stderr, "ERROR: -n expects WIDTHxHEIGHT\n");
@@ -296,6 +354,8 @@ int main(int argc, char *argv[])
         fprintf(stderr, "   -p: write PNG files instead of PGM\n");
         fprintf(stderr, "   -b dir: run every .pgm / .jpg of dir as one batch, write <name>_edges.pgm\n");
         fprintf(stderr, "   -l rho,theta_degrees,threshold[,lines_max]: Hough lines of the edge map -> canny_lines.txt in the -o dir\n");
+        fprintf(stderr, "   -m min_area: connected components of the edge map with at least min_area pixels -> canny_components.txt,\n");
+        fprintf(stderr, "                canny_kept.pgm in the -o dir\n");
         exit(0);
     }
 
@@ -348,6 +408,10 @@ int main(int argc, char *argv[])
     } catch (const exception &e) {
         fprintf(stderr, "ERROR: %s\n", e.what());
         return 1;
+    }
+    if (want_components) {
+        const int rc = run_components(frame, height, width, sigma, minVal, maxVal, min_area, outdir);
+        if (rc) return rc;
     }
     if (want_lines)
         return run_hough(frame, height, width, sigma, minVal, maxVal, line_rho, line_theta_deg, line_threshold, lines_max,

@@ -52,7 +52,7 @@
 extern "C" {
 #endif
 
-#define CANNY_HIP_VERSION 600        /* 0.6.0: + Hough lines of the finished map (cv::HoughLines semantics) on the GPU */
+#define CANNY_HIP_VERSION 700        /* 0.7.0: + 8-connected components of the finished map: labels, stats, minimum-area filter */
 /* 0.5.0: + edge point lists (CSR of pixel indices), compacted on the GPU */
 /* 0.4.1: + canny_hip_selftest_sobel_pixel */
 /* 0.4.0: + per-frame thresholds, explicit or chosen on the GPU (median / quantile) */
@@ -520,6 +520,79 @@ int canny_hip_canny_hough(canny_hip_ctx *ctx, const unsigned char *imgs, int n_f
                           int max_val, int height, int width, float rho, float theta, int threshold, int lines_max,
                           float min_theta, float max_theta, float *lines, int *votes, unsigned int *bases, int *counts);
 
+/* ---- connected components ------------------------------------------------------------------------------------------------
+ * Eight-connected component labelling of the finished edge map, per frame of a batch, on the GPU, queued behind the detector
+ * on the same stream with no host round trip: the grouping of edge pixels into curves that contour following starts from, and
+ * the "drop the short fragments" filter that is usually applied first.  THE RULE, for frame f with
+ * edge map E_f (the map canny_hip_canny returns for that frame, bit for bit):
+ *   Components: the set pixels (E_f[r][c] != 0) are partitioned by 8-connectivity (two set pixels whose rows and columns both
+ *     differ by at most 1 belong together).  A component has area = its pixel count and first = its smallest index r*width+c.
+ *   Filter: components with area >= min_area are KEPT; min_area <= 1 keeps all of them.
+ *   Numbering: kept components are numbered 1 .. K_f by ascending first.  With min_area <= 1 this is
+ *     scipy.ndimage.label(mask, structure=np.ones((3, 3))); up to the numbering it is cv::connectedComponents(mask, 8).
+ *   labels (int, [n][height][width]): the component's number on its pixels; 0 on background and on dropped components.
+ *     Every element is written.
+ *   kept_u8 (unsigned char, layout of canny_hip_dev_canny_u8): 255 where labels != 0, else 0.  Every element is written.
+ *   stats: CANNY_HIP_CC_STATS = 6 ints per kept component, CANNY_HIP_CC_STAT_LEFT, _TOP, _WIDTH, _HEIGHT, _AREA (the bounding
+ *     box and pixel count: the column order of cv::connectedComponentsWithStats, without its background row), then
+ *     CANNY_HIP_CC_STAT_FIRST.
+ *   CSR over the batch, as for the point lists: offsets[0 .. n_frames] (unsigned long long), offsets[0] = 0,
+ *     offsets[f+1] - offsets[f] = K_f -- always the TRUE counts; the record of label k of frame f is record
+ *     offsets[f] + k - 1 of stats.  `capacity` counts RECORDS and bounds the writes, never the counts: records at positions
+ *     >= capacity are not written, nothing is written at or past stats + 6 * capacity, and every record below it is exact.
+ *   offsets is mandatory; any of labels, kept_u8, stats may be NULL, and what the others receive does not depend on that.
+ *     stats == NULL with capacity > 0 is CANNY_HIP_ERR_INVALID (stats == NULL, capacity == 0: counts only).
+ *   The result follows the MAP, not the plane it is derived from: max_val > 255 empties every map (see the point lists), so
+ *     all offsets are 0 and labels / kept_u8 all zero.
+ *   Statuses are those of canny_hip_dev_canny for the same arguments, which runs first; on a status other than OK nothing
+ *     is written.  Pixel indices are 32-bit: a frame of 2^31 pixels or more is CANNY_HIP_ERR_UNSUPPORTED, as everywhere.
+ *   The output is the same bytes on every run.  Integer atomics (min, max, add) decide WHEN two trees of the union-find are
+ *     merged, never what comes out: partition, first, area and box are order-independent, and the numbering is a prefix sum
+ *     in raster order, not a counter.
+ * Memory: with labels == NULL a context workspace of 4 bytes per pixel of the batch holds the union-find's parent array (it
+ *   is touched per run of set pixels, not per pixel); with labels given that array lives in the label plane itself.
+ * The four parts are timed by canny_hip_components_profile_get (CANNY_HIP_CC_PART_*); with "profile_stage_mask" they are
+ *   bits 13 .. 16 (the Hough parts are bits 10 .. 12).
+ * Not covered -- follow-ups: 4-connectivity, centroids, contour chains (cv::findContours), the three-stream batch pipeline,
+ * the multi-GPU sharder, colour and per-frame / automatic-threshold variants. */
+#define CANNY_HIP_CC_STATS 6
+enum canny_hip_cc_stat {
+    CANNY_HIP_CC_STAT_LEFT = 0,
+    CANNY_HIP_CC_STAT_TOP = 1,
+    CANNY_HIP_CC_STAT_WIDTH = 2,
+    CANNY_HIP_CC_STAT_HEIGHT = 3,
+    CANNY_HIP_CC_STAT_AREA = 4,
+    CANNY_HIP_CC_STAT_FIRST = 5
+};
+enum canny_hip_cc_part {
+    CANNY_HIP_CC_PART_LINK = 0,     /* parent array set up, touching runs united (union-find, atomicMin) */
+    CANNY_HIP_CC_PART_RESOLVE = 1,  /* every run finds its root; areas summed onto the roots */
+    CANNY_HIP_CC_PART_NUMBER = 2,   /* kept roots counted per row, scanned, numbered; records and boxes written */
+    CANNY_HIP_CC_PART_WRITE = 3,    /* labels and kept_u8 stored */
+    CANNY_HIP_CC_PARTS = 4
+};
+/* Device buffers, asynchronous; completion contract and d_edges as canny_hip_dev_canny_points.  canny_hip_dev_canny itself
+ * queues exactly what it queues on its own; the labelling reads the converged hysteresis bit-plane behind it. */
+int canny_hip_dev_canny_components(canny_hip_ctx *ctx, const unsigned char *d_img, float sigma, int min_val, int max_val,
+                                   int height, int width, int n_frames, short *d_edges, int min_area, int *d_labels,
+                                   unsigned char *d_kept_u8, int *d_stats, unsigned long long capacity,
+                                   unsigned long long *d_offsets);
+/* The labelling alone, on device bit maps in the layout of canny_hip_dev_canny_bits (rows MSB-first, padded to bytes; any
+ * byte alignment; the padding bits of a row are ignored, whatever they hold).  Asynchronous. */
+int canny_hip_dev_components_bits(canny_hip_ctx *ctx, const unsigned char *d_bits, int height, int width, int n_frames,
+                                  int min_area, int *d_labels, unsigned char *d_kept_u8, int *d_stats,
+                                  unsigned long long capacity, unsigned long long *d_offsets);
+/* Host buffers, synchronous: upload, canny, labelling; the offsets come down first, then min(offsets[n_frames], capacity)
+ * records and only the planes that were asked for. */
+int canny_hip_canny_components(canny_hip_ctx *ctx, const unsigned char *imgs, int n_frames, float sigma, int min_val,
+                               int max_val, int height, int width, int min_area, int *labels, unsigned char *kept_u8,
+                               int *stats, unsigned long long capacity, unsigned long long *offsets);
+/* Host-only, needs no device: the same rule on ONE host bit map, in plain C++ (two passes, union-find) -- what a caller of
+ * canny_hip_canny_batch_bits runs on the maps it received.  labels (height * width ints) and stats may be NULL; *count
+ * receives the true number of kept components. */
+int canny_hip_components_from_bits(const unsigned char *bits, int height, int width, int min_area, int *labels,
+                                   int *stats, unsigned long long capacity, unsigned long long *count);
+
 /* ---- per-stage HIP-event timing (events are recorded on the launch stream) ----------------- */
 int canny_hip_profile_enable(canny_hip_ctx *ctx, int on);
 int canny_hip_profile_reset(canny_hip_ctx *ctx);
@@ -527,6 +600,8 @@ int canny_hip_profile_reset(canny_hip_ctx *ctx);
 int canny_hip_profile_get(canny_hip_ctx *ctx, int stage, double *total_ms, long *launches);
 /* The same for the Hough passes, which are not stages of the map: part 0 vote, 1 peaks, 2 select + sort. */
 int canny_hip_hough_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches);
+/* ... and for the four parts of the component labelling (CANNY_HIP_CC_PART_*). */
+int canny_hip_components_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches);
 
 /* ---- self-test hooks used by the GPU test-suite -------------------------------------------- */
 /* Runs the DEVICE magnitude / angle-bin functions over every (gx,gy) in [-lim,lim]^2 and writes
