@@ -96,6 +96,8 @@ EXPORTS = (
     "canny_hip_dev_hough_bits", "canny_hip_dev_canny_hough", "canny_hip_canny_hough", "canny_hip_hough_profile_get",
     "canny_hip_dev_canny_components", "canny_hip_dev_components_bits", "canny_hip_canny_components",
     "canny_hip_components_from_bits", "canny_hip_components_profile_get",
+    "canny_hip_dev_canny_edt", "canny_hip_dev_edt_bits", "canny_hip_canny_edt", "canny_hip_edt_from_bits",
+    "canny_hip_edt_profile_get",
 )
 
 _lib: Optional[C.CDLL] = None
@@ -218,6 +220,11 @@ def load() -> C.CDLL:
         "canny_hip_canny_components": ([p, p, i, f, i, i, i, i, i, p, p, p, C.c_ulonglong, p], i),
         "canny_hip_components_from_bits": ([p, i, i, i, p, p, C.c_ulonglong, C.POINTER(C.c_ulonglong)], i),
         "canny_hip_components_profile_get": ([p, i, C.POINTER(C.c_double), C.POINTER(C.c_long)], i),
+        "canny_hip_dev_canny_edt": ([p, p, f, i, i, i, i, i, p, p, p, p], i),
+        "canny_hip_dev_edt_bits": ([p, p, i, i, i, p, p, p], i),
+        "canny_hip_canny_edt": ([p, p, i, f, i, i, i, i, p, p, p], i),
+        "canny_hip_edt_from_bits": ([p, i, i, p, p, p], i),
+        "canny_hip_edt_profile_get": ([p, i, C.POINTER(C.c_double), C.POINTER(C.c_long)], i),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -300,6 +307,32 @@ def components_from_bits(bits, height: int, width: int, min_area: int = 1, want_
     if st:
         raise CannyHipError(st, "components_from_bits")
     return labels, stats[:min(cap, n.value)], n.value
+
+
+EDT_NONE = 0x7FFFFFFF                                           # CANNY_HIP_EDT_NONE: dist2 of a frame without edge pixels
+EDT_PARTS = ("rows", "columns")
+
+
+def edt_from_bits(bits, height: int, width: int, want_dist2: bool = True, want_dist: bool = True,
+                  want_nearest: bool = True):
+    """Host-only: the exact Euclidean distance transform of one packed bit map (numpy.packbits(mask, axis=-1); padding
+    bits ignored).  Returns (dist2 int32, dist float32, nearest int32), each [height, width] or None when not asked for:
+    the squared distance to the nearest set pixel, its correctly rounded root -- scipy.ndimage.distance_transform_edt(
+    ~mask).astype(float32) -- and that pixel's index r * width + c (the smallest among equally near ones).  A map
+    without set pixels gives EDT_NONE, +inf and -1."""
+    b = np.ascontiguousarray(bits, dtype=np.uint8)
+    if height >= 1 and width >= 1 and b.size != height * ((width + 7) // 8):
+        raise ValueError(f"expected {height} rows of {(width + 7) // 8} bytes, got {b.size} bytes")
+    ok = height >= 1 and width >= 1 and height * width < 2 ** 31
+    shape = (height, width) if ok else (1, 1)           # sizes the library rejects: it must not be handed real planes
+    d2 = np.empty(shape, np.int32) if want_dist2 else None
+    d = np.empty(shape, np.float32) if want_dist else None
+    nn = np.empty(shape, np.int32) if want_nearest else None
+    st = load().canny_hip_edt_from_bits(_hp(b), height, width, _hp(d2) if want_dist2 else None,
+                                        _hp(d) if want_dist else None, _hp(nn) if want_nearest else None)
+    if st:
+        raise CannyHipError(st, "edt_from_bits")
+    return d2, d, nn
 
 
 HOUGH_MAX_LINES = 4096
@@ -719,6 +752,48 @@ class Context:
         ms, n = C.c_double(0.0), C.c_long(0)
         self._check(self._L.canny_hip_components_profile_get(self._h, part, C.byref(ms), C.byref(n)),
                     "components_profile_get")
+        return ms.value, n.value
+
+    # ---- Euclidean distance transform of the finished map ---------------------------------
+    def canny_edt(self, imgs, sigma: float, min_val: int, max_val: int, want_dist2: bool = True, want_dist: bool = True,
+                  want_nearest: bool = True):
+        """canny(), then the exact Euclidean distance transform of each map: imgs (H, W) or (N, H, W) uint8 -> (dist2
+        int32, dist float32, nearest int32), each [N, H, W] or None when not asked for (it is then neither computed for
+        its own sake nor downloaded): the squared distance to the nearest edge pixel, its correctly rounded root, that
+        pixel's index r * W + c.  A frame without edge pixels gives EDT_NONE, +inf and -1."""
+        a = np.ascontiguousarray(imgs, dtype=np.uint8)
+        if a.ndim == 2:
+            a = a[None]
+        if a.ndim != 3:
+            raise ValueError("expected uint8 [H, W] or [n_frames, H, W]")
+        n, h, w = a.shape
+        d2 = np.empty((n, h, w), np.int32) if want_dist2 else None
+        d = np.empty((n, h, w), np.float32) if want_dist else None
+        nn = np.empty((n, h, w), np.int32) if want_nearest else None
+        self._check(self._L.canny_hip_canny_edt(self._h, _hp(a), n, sigma, min_val, max_val, h, w,
+                                                _hp(d2) if want_dist2 else None, _hp(d) if want_dist else None,
+                                                _hp(nn) if want_nearest else None), "canny_edt")
+        return d2, d, nn
+
+    def dev_canny_edt(self, d_img: int, sigma: float, min_val: int, max_val: int, h: int, w: int, n: int, d_dist2: int,
+                      d_dist: int, d_nearest: int, d_edges: int = 0):
+        """dev_canny, then its map's distance transform on the same stream: d_dist2 (n*h*w int32), d_dist (n*h*w float32),
+        d_nearest (n*h*w int32) -- each a device pointer or 0, not all 0 --, d_edges (the s16 map, device) or 0."""
+        v = C.c_void_p
+        self._check(self._L.canny_hip_dev_canny_edt(self._h, v(d_img), sigma, min_val, max_val, h, w, n,
+                                                    v(d_edges or None), v(d_dist2 or None), v(d_dist or None),
+                                                    v(d_nearest or None)), "dev_canny_edt")
+
+    def dev_edt_bits(self, d_bits: int, h: int, w: int, n: int, d_dist2: int, d_dist: int, d_nearest: int):
+        """The transform alone on device bit maps (layout of dev_canny_bits, any byte alignment, padding ignored)."""
+        v = C.c_void_p
+        self._check(self._L.canny_hip_dev_edt_bits(self._h, v(d_bits or None), h, w, n, v(d_dist2 or None),
+                                                   v(d_dist or None), v(d_nearest or None)), "dev_edt_bits")
+
+    def edt_profile_get(self, part: int) -> Tuple[float, int]:
+        """(total ms, launch groups) of part 0 rows, 1 columns (EDT_PARTS)."""
+        ms, n = C.c_double(0.0), C.c_long(0)
+        self._check(self._L.canny_hip_edt_profile_get(self._h, part, C.byref(ms), C.byref(n)), "edt_profile_get")
         return ms.value, n.value
 
     # ---- Hough lines of the finished map (cv::HoughLines semantics; DESIGN.md section 13) -----------------------

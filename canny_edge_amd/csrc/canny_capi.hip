@@ -386,6 +386,9 @@ struct canny_hip_ctx {
     // connected components: the parent array (4 B/px) when the caller passes no label plane; per-frame totals and per-row
     // counts / prefixes of the numbering scan
     DevBuf cc_parent, cc_ws;
+    // distance transform: the row pass's u16 plane (2 B/px, rows padded to 64 pixels); the column scan's stack (4 B/px) when
+    // the caller passes no dist2 plane to keep it in
+    DevBuf edt_cols, edt_stack;
     DevBuf plane_s, plane_c, stamps, flags; // hysteresis bit-planes / scheduling words
     DevBuf io[4];     // staging for the host-pointer stage functions
     unsigned *host_flags = nullptr;     // pinned + mapped, 4 words per lane: last_change, domain, sequence number, spare
@@ -409,9 +412,10 @@ struct canny_hip_ctx {
     unsigned prof_mask = ~0u; // stages whose launches get an event pair (each pair costs a few us of stream time)
     unsigned prof_every = 1;  // ... and only every prof_every-th launch group of a stage gets one
     // slots: the stages, then the three Hough parts (canny_hip_hough_profile_get), then the four parts of the component
-    // labelling (canny_hip_components_profile_get)
+    // labelling (canny_hip_components_profile_get), then the two of the distance transform (canny_hip_edt_profile_get)
     static constexpr int kProfHough = CANNY_HIP_STAGE_END, kProfComponents = CANNY_HIP_STAGE_END + 3;
-    static constexpr int kProfSlots = kProfComponents + CANNY_HIP_CC_PARTS;
+    static constexpr int kProfEdt = kProfComponents + CANNY_HIP_CC_PARTS;
+    static constexpr int kProfSlots = kProfEdt + CANNY_HIP_EDT_PARTS;
     unsigned prof_seen[kProfSlots] = {0};
     std::vector<EventPair> pending[kProfSlots];
     std::vector<EventPair> pool;
@@ -1194,6 +1198,62 @@ int dev_canny_components(canny_hip_ctx *ctx, const unsigned char *d_img, float s
     return dev_components(ctx, (const uint64_t *)ctx->plane_s.p, nullptr, make_hyst_geom(h, w, n), min_area, out);
 }
 
+// ---- Euclidean distance transform (canny_edt.hip) --------------------------
+struct EdtOut {
+    int *dist2;
+    float *dist;
+    int *nearest;
+};
+
+int check_edt_dims(int height, int width, int n_frames)
+{
+    const int rc = check_dims(height, width, n_frames);
+    if (rc) return rc;
+    // dist2 and the pixel indices are 32-bit
+    if ((long long)height * width >= 0x80000000LL || (long long)height * height + (long long)width * width >= 0x80000000LL)
+        return CANNY_HIP_ERR_UNSUPPORTED;
+    return CANNY_HIP_OK;
+}
+
+// The transform of one source (the context's strong plane or packed bits), queued on the context's stream.
+int dev_edt(canny_hip_ctx *ctx, const uint64_t *strong, const uint8_t *bits, const HystGeom &g, const EdtOut &out)
+{
+    const size_t padded = (size_t)g.n_frames * g.height * edt_pitch(g);
+    HIP_TRY(ctx, ctx->edt_cols.ensure(padded * sizeof(uint16_t)));
+    if (!out.dist2) HIP_TRY(ctx, ctx->edt_stack.ensure(padded * sizeof(uint32_t)));
+    {
+        StageTimer tm(ctx, canny_hip_ctx::kProfEdt + CANNY_HIP_EDT_PART_ROWS);
+        HIP_TRY(ctx, launch_edt_rows(strong, bits, g, (uint16_t *)ctx->edt_cols.p, ctx->stream));
+    }
+    {
+        StageTimer tm(ctx, canny_hip_ctx::kProfEdt + CANNY_HIP_EDT_PART_COLUMNS);
+        HIP_TRY(ctx, launch_edt_columns(g, (uint16_t *)ctx->edt_cols.p, out.dist2 ? nullptr : (uint32_t *)ctx->edt_stack.p,
+                                        out.dist2, out.dist, out.nearest, ctx->stream));
+    }
+    return CANNY_HIP_OK;
+}
+
+// dev_canny (unchanged), then the transform of its map from the converged strong plane.  The result follows the MAP:
+// max_val > 255 leaves no edge pixel (see dev_canny_points_count), so every plane takes its "no edge pixel" value.
+int dev_canny_edt(canny_hip_ctx *ctx, const unsigned char *d_img, float sigma, int lo, int hi, int h, int w, int n,
+                  short *d_edges, const EdtOut &out)
+{
+    int rc;
+    if (!d_edges) {
+        HIP_TRY(ctx, ctx->edges16.ensure(npx(h, w, n) * sizeof(short)));
+        d_edges = (short *)ctx->edges16.p;
+    }
+    if ((rc = dev_canny(ctx, d_img, sigma, lo, hi, h, w, n, d_edges))) return rc;
+    if (hi > 255) {
+        const size_t count = npx(h, w, n);
+        if (out.dist2) HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)out.dist2, CANNY_HIP_EDT_NONE, count, ctx->stream));
+        if (out.dist) HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)out.dist, 0x7F800000, count, ctx->stream)); // +inf
+        if (out.nearest) HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)out.nearest, -1, count, ctx->stream));
+        return CANNY_HIP_OK;
+    }
+    return dev_edt(ctx, (const uint64_t *)ctx->plane_s.p, nullptr, make_hyst_geom(h, w, n), out);
+}
+
 // ---- Hough lines (canny_hough.hip) -----------------------------------------
 struct HoughOut {
     float *d_lines;
@@ -1467,6 +1527,8 @@ void canny_hip_ctx_destroy(canny_hip_ctx *ctx)
     ctx->hough_tab.release();
     ctx->cc_parent.release();
     ctx->cc_ws.release();
+    ctx->edt_cols.release();
+    ctx->edt_stack.release();
     ctx->stamps.release();
     ctx->flags.release();
     for (auto &b : ctx->io) b.release();
@@ -2844,6 +2906,116 @@ int canny_hip_components_from_bits(const unsigned char *bits, int height, int wi
     return CANNY_HIP_OK;
 }
 
+// ---- Euclidean distance transform -------------------------------------------------------------------
+int canny_hip_dev_canny_edt(canny_hip_ctx *ctx, const unsigned char *d_img, float sigma, int min_val, int max_val,
+                            int height, int width, int n_frames, short *d_edges, int *d_dist2, float *d_dist,
+                            int *d_nearest)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!d_img || (!d_dist2 && !d_dist && !d_nearest)) return CANNY_HIP_ERR_INVALID;
+    if ((rc = check_edt_dims(height, width, n_frames))) return rc;
+    return dev_canny_edt(ctx, d_img, sigma, min_val, max_val, height, width, n_frames, d_edges,
+                         EdtOut{d_dist2, d_dist, d_nearest});
+}
+
+int canny_hip_dev_edt_bits(canny_hip_ctx *ctx, const unsigned char *d_bits, int height, int width, int n_frames,
+                           int *d_dist2, float *d_dist, int *d_nearest)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!d_bits || (!d_dist2 && !d_dist && !d_nearest)) return CANNY_HIP_ERR_INVALID;
+    if ((rc = check_edt_dims(height, width, n_frames)) || (rc = finish_pending(ctx))) return rc;
+    return dev_edt(ctx, nullptr, d_bits, make_hyst_geom(height, width, n_frames), EdtOut{d_dist2, d_dist, d_nearest});
+}
+
+int canny_hip_canny_edt(canny_hip_ctx *ctx, const unsigned char *imgs, int n_frames, float sigma, int min_val, int max_val,
+                        int height, int width, int *dist2, float *dist, int *nearest)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!imgs || (!dist2 && !dist && !nearest)) return CANNY_HIP_ERR_INVALID;
+    if ((rc = check_edt_dims(height, width, n_frames))) return rc;
+    const size_t n = npx(height, width, n_frames);
+    if ((rc = h2d(ctx, ctx->io[0], imgs, n))) return rc;
+    // one staging block per plane asked for
+    void *host[3] = {dist2, dist, nearest};
+    void *dev[3] = {nullptr, nullptr, nullptr};
+    for (int k = 0; k < 3; k++) {
+        if (!host[k]) continue;
+        HIP_TRY(ctx, ctx->io[1 + k].ensure(n * 4));
+        dev[k] = ctx->io[1 + k].p;
+    }
+    if ((rc = dev_canny_edt(ctx, (const unsigned char *)ctx->io[0].p, sigma, min_val, max_val, height, width, n_frames,
+                            nullptr, EdtOut{(int *)dev[0], (float *)dev[1], (int *)dev[2]})))
+        return rc;
+    for (int k = 0; k < 3; k++)
+        if (host[k]) HIP_TRY(ctx, hipMemcpyAsync(host[k], dev[k], n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return CANNY_HIP_OK;
+}
+
+// The rule on one host bit map, the two passes of canny_edt.hip in plain C++: per row the column of the nearest set pixel
+// (ties to the left), then per column the lower envelope of the rows' parabolas with a strict pop (ties to the smaller row).
+int canny_hip_edt_from_bits(const unsigned char *bits, int height, int width, int *dist2, float *dist, int *nearest)
+{
+    if (!bits || (!dist2 && !dist && !nearest)) return CANNY_HIP_ERR_INVALID;
+    int rc = check_edt_dims(height, width, 1);
+    if (rc) return rc;
+    const size_t row_bytes = ((size_t)width + 7) / 8, n = (size_t)height * width;
+    constexpr int kNone = -1;
+    std::vector<int> col(n); // column of the nearest set pixel of the row, kNone if the row has none
+    for (int y = 0; y < height; y++) {
+        const unsigned char *row = bits + (size_t)y * row_bytes;
+        int *g = col.data() + (size_t)y * width;
+        int last = kNone;
+        for (int x = 0; x < width; x++) {
+            if ((row[x >> 3] >> (7 - (x & 7))) & 1) last = x;
+            g[x] = last;
+        }
+        int next = kNone;
+        for (int x = width - 1; x >= 0; x--) {
+            if (g[x] == x) next = x;
+            if (next != kNone && (g[x] == kNone || next - x < x - g[x])) g[x] = next; // strictly nearer: ties stay left
+        }
+    }
+    std::vector<int> s(height), t(height);
+    for (int c = 0; c < width; c++) {
+        auto G = [&](int r) { return col[(size_t)r * width + c]; };
+        auto f = [&](int x, int r) {
+            const long long dx = x - r, hx = c - G(r);
+            return dx * dx + hx * hx;
+        };
+        int q = -1;
+        for (int u = 0; u < height; u++) {
+            if (G(u) == kNone) continue;
+            while (q >= 0 && f(t[q], s[q]) > f(t[q], u)) q--;
+            if (q < 0) {
+                q = 0, s[0] = u, t[0] = 0;
+                continue;
+            }
+            const long long i = s[q], hu = c - G(u), hi = c - G((int)i);
+            const long long sep = ((long long)u * u - i * i + hu * hu - hi * hi) / (2 * (u - i)) + 1; // numerator >= 0
+            if (sep < height) q++, s[q] = u, t[q] = (int)sep;
+        }
+        for (int x = height - 1; x >= 0; x--) {
+            const size_t o = (size_t)x * width + c;
+            if (q < 0) {
+                if (dist2) dist2[o] = CANNY_HIP_EDT_NONE;
+                if (dist) dist[o] = INFINITY;
+                if (nearest) nearest[o] = -1;
+                continue;
+            }
+            while (x < t[q]) q--;
+            const int d2 = (int)f(x, s[q]);
+            if (dist2) dist2[o] = d2;
+            if (dist) dist[o] = (float)std::sqrt((double)d2);
+            if (nearest) nearest[o] = s[q] * width + G(s[q]);
+        }
+    }
+    return CANNY_HIP_OK;
+}
+
 // ---- profiling --------------------------------------------------------------------------------------
 int canny_hip_profile_enable(canny_hip_ctx *ctx, int on)
 {
@@ -3050,6 +3222,17 @@ int canny_hip_components_profile_get(canny_hip_ctx *ctx, int part, double *total
     if ((rc = profile_collect(ctx))) return rc;
     *total_ms = ctx->total_ms[canny_hip_ctx::kProfComponents + part];
     *launches = ctx->launches[canny_hip_ctx::kProfComponents + part];
+    return CANNY_HIP_OK;
+}
+
+int canny_hip_edt_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches)
+{
+    if (part < 0 || part >= CANNY_HIP_EDT_PARTS || !total_ms || !launches) return CANNY_HIP_ERR_INVALID;
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if ((rc = profile_collect(ctx))) return rc;
+    *total_ms = ctx->total_ms[canny_hip_ctx::kProfEdt + part];
+    *launches = ctx->launches[canny_hip_ctx::kProfEdt + part];
     return CANNY_HIP_OK;
 }
 

@@ -64,18 +64,7 @@ __device__ __forceinline__ uint64_t cc_word(const void *__restrict__ src, const 
                                             int k)
 {
     if (y < 0 || y >= g.height || k < 0 || k >= g.tiles_x) return 0ull;
-    const int left = g.width - (k << 6); // > 0
-    const uint64_t mask = left >= 64 ? ~0ull : ((1ull << left) - 1ull);
-    if constexpr (!BITS) {
-        return static_cast<const uint64_t *>(src)[hyst_word_index(g, f, y, k)] & mask;
-    } else {
-        const uint8_t *row = static_cast<const uint8_t *>(src) + ((size_t)f * g.height + y) * (size_t)row_bytes +
-                             (size_t)k * 8;
-        const int nb = min(8, row_bytes - k * 8);
-        uint64_t w = 0;
-        for (int j = 0; j < nb; j++) w |= (uint64_t)(__brev((unsigned)row[j]) >> 24) << (8 * j); // MSB-first -> LSB-first
-        return w & mask;
-    }
+    return row_word<BITS>(src, g, row_bytes, f, y, k);
 }
 
 __device__ __forceinline__ uint64_t run_starts(uint64_t w) { return w & ~(w << 1); }

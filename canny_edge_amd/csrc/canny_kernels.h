@@ -310,6 +310,27 @@ __host__ __device__ inline size_t hyst_word_index(const HystGeom &g, int f, int 
 }
 // The source is the strong plane of geometry g, or -- bits != nullptr -- a packed bit map (rows MSB-first, padded to
 // bytes, any byte address; padding bits ignored).
+#ifdef __HIPCC__
+// Columns 64*k .. 64*k + 63 of row y of frame f of either source (BITS: the packed map, row_bytes = (width + 7) / 8), bit i
+// = column 64*k + i, columns >= width cleared.  0 <= y < height, 0 <= k < tiles_x.
+template <bool BITS>
+__device__ __forceinline__ uint64_t row_word(const void *__restrict__ src, const HystGeom &g, int row_bytes, int f,
+                                             int y, int k)
+{
+    const int left = g.width - (k << 6); // > 0
+    const uint64_t mask = left >= 64 ? ~0ull : ((1ull << left) - 1ull);
+    if constexpr (!BITS) {
+        return static_cast<const uint64_t *>(src)[hyst_word_index(g, f, y, k)] & mask;
+    } else {
+        const uint8_t *row = static_cast<const uint8_t *>(src) + ((size_t)f * g.height + y) * (size_t)row_bytes +
+                             (size_t)k * 8;
+        const int nb = min(8, row_bytes - k * 8);
+        uint64_t w = 0;
+        for (int j = 0; j < nb; j++) w |= (uint64_t)(__brev((unsigned)row[j]) >> 24) << (8 * j); // MSB-first -> LSB-first
+        return w & mask;
+    }
+}
+#endif
 // count: row_counts[f * height + y] = set pixels of that row.
 hipError_t launch_points_count(const uint64_t *strong, const uint8_t *bits, const HystGeom &g, uint32_t *row_counts,
                                hipStream_t stream);
@@ -377,6 +398,20 @@ hipError_t launch_cc_number(const uint64_t *strong, const uint8_t *bits, const H
 // 255 / 0.  Either may be null; labels may be `entries` itself.
 hipError_t launch_cc_write(const uint64_t *strong, const uint8_t *bits, const HystGeom &g, const int *entries, int *labels,
                            uint8_t *kept, hipStream_t stream);
+
+// ---- Euclidean distance transform (canny_edt.hip) ----------------------
+// Source as for the point lists.  height * width < 2^31 and height^2 + width^2 < 2^31.
+// Elements per row of the u16 plane between the two passes: rows are padded to whole 64-pixel words.
+inline size_t edt_pitch(const HystGeom &g) { return (size_t)g.tiles_x << 6; }
+// rows: cols[f][r][c] = the column of the set pixel of row r nearest to column c (ties to the left), 0xFFFF if the row has
+// none.  cols holds n_frames * height * edt_pitch(g) u16.
+hipError_t launch_edt_rows(const uint64_t *strong, const uint8_t *bits, const HystGeom &g, uint16_t *cols,
+                           hipStream_t stream);
+// columns: the lower envelope of the rows' parabolas down every column -> dist2, dist, nearest ([n][height][width]; any may
+// be null, every element of the others is stored).  cols is consumed (it becomes part of the scan's stack).  stack:
+// n_frames * height * edt_pitch(g) u32, or null when dist2 is given -- the scan then keeps its stack in dist2.
+hipError_t launch_edt_columns(const HystGeom &g, uint16_t *cols, uint32_t *stack, int *dist2, float *dist, int *nearest,
+                              hipStream_t stream);
 
 // ---- measurement aid ------------------------------------------------------------------------
 // Plain device copy of nbytes (multiple of 16; both pointers 16-byte aligned): what a 1:1 read/write stream reaches.

@@ -28,25 +28,6 @@ namespace {
 
 constexpr int kPtsBlock = 1024; // 16 waves = 16 consecutive rows per workgroup step
 
-// columns 64*k .. 64*k + 63 of row y of frame f, bit i = column 64*k + i, columns >= width cleared
-template <bool BITS>
-__device__ __forceinline__ uint64_t row_word(const void *__restrict__ src, const HystGeom &g, int row_bytes, int f,
-                                             int y, int k)
-{
-    const int left = g.width - (k << 6); // > 0
-    const uint64_t mask = left >= 64 ? ~0ull : ((1ull << left) - 1ull);
-    if constexpr (!BITS) {
-        return static_cast<const uint64_t *>(src)[hyst_word_index(g, f, y, k)] & mask;
-    } else {
-        const uint8_t *row = static_cast<const uint8_t *>(src) + ((size_t)f * g.height + y) * (size_t)row_bytes +
-                             (size_t)k * 8;
-        const int nb = min(8, row_bytes - k * 8);
-        uint64_t w = 0;
-        for (int j = 0; j < nb; j++) w |= (uint64_t)(__brev((unsigned)row[j]) >> 24) << (8 * j); // MSB-first -> LSB-first
-        return w & mask;
-    }
-}
-
 template <bool BITS>
 __global__ __launch_bounds__(kPtsBlock) void points_count_kernel(const void *__restrict__ src, HystGeom g, int row_bytes,
                                                                  uint32_t *__restrict__ row_counts)

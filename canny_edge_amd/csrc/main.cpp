@@ -1,6 +1,6 @@
 // main.cpp -- the reference's command line (StevenChang5/Canny_Edge src/main.cpp:18-142) without
 // the webcam and the GUI:  ./Main sigma minVal maxVal [-c] [-s] [-i in.pgm|in.ppm|in.jpg] [-o dir] [-p] [-n WxH] [-b dir]
-//        [-l rho,theta_degrees,threshold[,lines_max]] [-m min_area]
+//        [-l rho,theta_degrees,threshold[,lines_max]] [-m min_area] [-d]
 //
 // Kept from the reference: the three positionals may appear anywhere relative to the flags
 // (src/main.cpp:29-46); exactly three are required, otherwise the usage text is printed and the
@@ -19,6 +19,9 @@
 // with fewer than min_area pixels and writes one "label left top width height area" row per kept component to
 // canny_components.txt and the filtered map to canny_kept.pgm (.png with -p) in the -o directory (rows to stdout without
 // -o).  Without -m nothing changes.
+// Added: -d runs the exact Euclidean distance transform of the frame's edge map on the GPU (canny_hip_canny_edt) and writes
+// canny_dist.pgm (.png with -p) to the -o directory (the current one without -o): one byte per pixel,
+// min(255, floor(sqrt(dist2))), 255 everywhere for a map without edge pixels.  Without -d nothing changes.
 #include <algorithm>
 #include <cctype>
 #include <cmath>
@@ -286,6 +289,35 @@ static int run_components(const vector<unsigned char> &frame, int height, int wi
     return 0;
 }
 
+// -d: the distance of every pixel to the nearest edge pixel, as a byte image
+static int run_edt(const vector<unsigned char> &frame, int height, int width, float sigma, int minVal, int maxVal,
+                   const string &outdir)
+{
+    const size_t n = (size_t)height * width;
+    vector<int> dist2(n);
+    canny_hip_ctx *ctx = nullptr;
+    int st = canny_hip_ctx_create(&ctx, 0);
+    if (!st) st = canny_hip_canny_edt(ctx, frame.data(), 1, sigma, minVal, maxVal, height, width, dist2.data(), nullptr, nullptr);
+    if (st) {
+        fprintf(stderr, "ERROR: -d: %s\n", st == CANNY_HIP_ERR_RUNTIME && ctx ? canny_hip_last_error(ctx) : canny_hip_status_string(st));
+        if (ctx) canny_hip_ctx_destroy(ctx);
+        return 1;
+    }
+    canny_hip_ctx_destroy(ctx);
+    vector<unsigned char> out(n);
+    for (size_t i = 0; i < n; i++) {
+        int root = 0; // integer square root, capped: 255^2 <= dist2 gives 255
+        while (root < 255 && (root + 1) * (root + 1) <= dist2[i]) root++;
+        out[i] = (unsigned char)root;
+    }
+    const string path = (outdir.empty() ? string(".") : outdir) + "/canny_dist" + (png_output ? ".png" : ".pgm");
+    if (!write_frame(path, out.data(), height, width)) {
+        fprintf(stderr, "ERROR: cannot write %s\n", path.c_str());
+        return 1;
+    }
+    return 0;
+}
+
 int main(int argc, char *argv[])
 {
     // The batch pipeline wants its upload, compute and download streams on separate hardware queues; HIP reads this
@@ -302,6 +334,7 @@ int main(int argc, char *argv[])
     int line_threshold = 0, lines_max = 256;
     bool want_components = false;
     int min_area = 1;
+    bool want_dist = false;
     int width = WIDTH, height = HEIGHT;
     vector<string> values;
 
@@ -332,6 +365,8 @@ int main(int argc, char *argv[])
                 exit(0);
             }
             want_components = true;
+        } else if (arg == "-d") {
+            want_dist = true;
         } else if (arg == "-n" && i + 1 < argc) {
             if (sscanf(argv[++i], "%dx%d", &width, &height) != 2 || width < 2 || height < 2) {
                 fprintf(stderr, "ERROR: -n expects WIDTHxHEIGHT\n");
@@ -356,6 +391,7 @@ int main(int argc, char *argv[])
         fprintf(stderr, "   -l rho,theta_degrees,threshold[,lines_max]: Hough lines of the edge map -> canny_lines.txt in the -o dir\n");
         fprintf(stderr, "   -m min_area: connected components of the edge map with at least min_area pixels -> canny_components.txt,\n");
         fprintf(stderr, "                canny_kept.pgm in the -o dir\n");
+        fprintf(stderr, "   -d: distance of every pixel to the nearest edge pixel, min(255, floor) -> canny_dist.pgm in the -o dir\n");
         exit(0);
     }
 
@@ -411,6 +447,10 @@ int main(int argc, char *argv[])
     }
     if (want_components) {
         const int rc = run_components(frame, height, width, sigma, minVal, maxVal, min_area, outdir);
+        if (rc) return rc;
+    }
+    if (want_dist) {
+        const int rc = run_edt(frame, height, width, sigma, minVal, maxVal, outdir);
         if (rc) return rc;
     }
     if (want_lines)

@@ -52,7 +52,8 @@
 extern "C" {
 #endif
 
-#define CANNY_HIP_VERSION 700        /* 0.7.0: + 8-connected components of the finished map: labels, stats, minimum-area filter */
+#define CANNY_HIP_VERSION 800        /* 0.8.0: + exact Euclidean distance transform of the finished map: dist2, dist, nearest */
+/* 0.7.0: + 8-connected components of the finished map: labels, stats, minimum-area filter */
 /* 0.5.0: + edge point lists (CSR of pixel indices), compacted on the GPU */
 /* 0.4.1: + canny_hip_selftest_sobel_pixel */
 /* 0.4.0: + per-frame thresholds, explicit or chosen on the GPU (median / quantile) */
@@ -593,6 +594,58 @@ int canny_hip_canny_components(canny_hip_ctx *ctx, const unsigned char *imgs, in
 int canny_hip_components_from_bits(const unsigned char *bits, int height, int width, int min_area, int *labels,
                                    int *stats, unsigned long long capacity, unsigned long long *count);
 
+/* ---- Euclidean distance transform ----------------------------------------------------------------------------------------
+ * For every pixel of every frame the distance to the nearest edge pixel, on the GPU, queued behind the detector on the same
+ * stream with no host round trip: what chamfer and template matching, edge-based registration, "snap to the nearest edge" and
+ * contour-deviation scores start from.  THE RULE, for frame f with edge map E_f (the map
+ * canny_hip_canny returns for that frame, bit for bit) and S_f = { (r', c') : E_f[r'][c'] != 0 }:
+ *   dist2 (int, [n][height][width]): dist2[r][c] = min over (r', c') in S_f of (r - r')^2 + (c - c')^2 -- an integer, so the
+ *     transform is EXACT; 0 on edge pixels.
+ *   nearest (int, same shape): the index r' * width + c' of a pixel of S_f that attains that minimum; where several do, the
+ *     smallest index.  On an edge pixel its own index.
+ *   dist (float, same shape): (float)sqrt((double)dist2), the correctly rounded single-precision root, computed in double on
+ *     the device (dist2 exceeds 2^24 on large frames: a float root of a float-converted dist2 is NOT the rule).  It equals
+ *     numpy.sqrt(dist2.astype(float64)).astype(float32) and scipy.ndimage.distance_transform_edt(~mask).astype(float32)
+ *     bit for bit, and is what cv::distanceTransform(DIST_L2, DIST_MASK_PRECISE) approximates.
+ *   A frame without edge pixels: every dist2 is CANNY_HIP_EDT_NONE, every dist +inf, every nearest -1.  The result follows
+ *     the MAP, not the plane it is derived from: max_val > 255 empties every map (see the point lists).
+ *   Any of the three output pointers may be NULL, and what the others receive does not depend on that; all three NULL is
+ *     CANNY_HIP_ERR_INVALID.  Every element of every plane given is written, nothing beyond it.
+ *   Limits: height * width < 2^31 and height^2 + width^2 < 2^31 (dist2 and the indices are 32-bit); beyond that
+ *     CANNY_HIP_ERR_UNSUPPORTED, before anything is queued.  Otherwise the statuses of the canny forms are those of
+ *     canny_hip_dev_canny for the same arguments, which runs first; on a status other than OK nothing is written.
+ *   The output is the same bytes on every run: there are no atomics, every element is stored once by one thread, and the
+ *     launches depend on the shapes and on which planes were asked for, never on the data.  The work per frame is
+ *     O(height * width) whatever the map holds (one edge pixel or none included).
+ * Memory: a context workspace of 2 bytes per pixel (rows padded to 64 pixels) holds the row pass's result; with
+ *   dist2 == NULL another 4 bytes per pixel hold the column scan's stack, which otherwise lives in the dist2 plane itself.
+ * The two parts are timed by canny_hip_edt_profile_get (CANNY_HIP_EDT_PART_*); with "profile_stage_mask" they are bits 17
+ *   and 18.
+ * Not covered -- follow-ups: truncated or u8 outputs, L1 / chessboard metrics, the distance to the nearest NON-edge pixel,
+ * the three-stream batch pipeline, the multi-GPU sharder, colour and per-frame / automatic-threshold variants. */
+#define CANNY_HIP_EDT_NONE 0x7FFFFFFF
+enum canny_hip_edt_part {
+    CANNY_HIP_EDT_PART_ROWS = 0,     /* per row: the column of the nearest set pixel of that row (u16 workspace) */
+    CANNY_HIP_EDT_PART_COLUMNS = 1,  /* per column: lower envelope of the rows' parabolas; the planes are stored */
+    CANNY_HIP_EDT_PARTS = 2
+};
+/* Device buffers, asynchronous; completion contract and d_edges as canny_hip_dev_canny_points.  canny_hip_dev_canny itself
+ * queues exactly what it queues on its own; the transform reads the converged hysteresis bit-plane behind it, never the
+ * s16 map. */
+int canny_hip_dev_canny_edt(canny_hip_ctx *ctx, const unsigned char *d_img, float sigma, int min_val, int max_val,
+                            int height, int width, int n_frames, short *d_edges, int *d_dist2, float *d_dist,
+                            int *d_nearest);
+/* The transform alone, on device bit maps in the layout of canny_hip_dev_canny_bits (rows MSB-first, padded to bytes; any
+ * byte alignment; the padding bits of a row are ignored, whatever they hold).  Asynchronous. */
+int canny_hip_dev_edt_bits(canny_hip_ctx *ctx, const unsigned char *d_bits, int height, int width, int n_frames,
+                           int *d_dist2, float *d_dist, int *d_nearest);
+/* Host buffers, synchronous: upload, canny, transform; only the planes that were asked for come down. */
+int canny_hip_canny_edt(canny_hip_ctx *ctx, const unsigned char *imgs, int n_frames, float sigma, int min_val, int max_val,
+                        int height, int width, int *dist2, float *dist, int *nearest);
+/* Host-only, needs no device: the same rule on ONE host bit map, in plain C++ (the same two passes) -- what a caller of
+ * canny_hip_canny_batch_bits runs on the maps it received. */
+int canny_hip_edt_from_bits(const unsigned char *bits, int height, int width, int *dist2, float *dist, int *nearest);
+
 /* ---- per-stage HIP-event timing (events are recorded on the launch stream) ----------------- */
 int canny_hip_profile_enable(canny_hip_ctx *ctx, int on);
 int canny_hip_profile_reset(canny_hip_ctx *ctx);
@@ -602,6 +655,8 @@ int canny_hip_profile_get(canny_hip_ctx *ctx, int stage, double *total_ms, long 
 int canny_hip_hough_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches);
 /* ... and for the four parts of the component labelling (CANNY_HIP_CC_PART_*). */
 int canny_hip_components_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches);
+/* ... and for the two parts of the distance transform (CANNY_HIP_EDT_PART_*). */
+int canny_hip_edt_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches);
 
 /* ---- self-test hooks used by the GPU test-suite -------------------------------------------- */
 /* Runs the DEVICE magnitude / angle-bin functions over every (gx,gy) in [-lim,lim]^2 and writes
