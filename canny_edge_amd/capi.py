@@ -98,6 +98,8 @@ EXPORTS = (
     "canny_hip_components_from_bits", "canny_hip_components_profile_get",
     "canny_hip_dev_canny_edt", "canny_hip_dev_edt_bits", "canny_hip_canny_edt", "canny_hip_edt_from_bits",
     "canny_hip_edt_profile_get",
+    "canny_hip_hough_segments_from_bits", "canny_hip_dev_hough_segments_bits", "canny_hip_dev_canny_hough_segments",
+    "canny_hip_canny_hough_segments", "canny_hip_hough_segments_profile_get",
 )
 
 _lib: Optional[C.CDLL] = None
@@ -225,6 +227,12 @@ def load() -> C.CDLL:
         "canny_hip_canny_edt": ([p, p, i, f, i, i, i, i, p, p, p], i),
         "canny_hip_edt_from_bits": ([p, i, i, p, p, p], i),
         "canny_hip_edt_profile_get": ([p, i, C.POINTER(C.c_double), C.POINTER(C.c_long)], i),
+        "canny_hip_hough_segments_from_bits": ([p, i, i, f, f, f, f, p, i, i, i, i, p, i, ip], i),
+        "canny_hip_dev_hough_segments_bits": ([p, p, i, i, i, f, f, f, f, p, p, i, i, i, i, p, i, p], i),
+        "canny_hip_dev_canny_hough_segments": ([p, p, f, i, i, i, i, i, p, f, f, i, i, f, f, p, p, p, p, p, i, i, i, p, i,
+                                                p], i),
+        "canny_hip_canny_hough_segments": ([p, p, i, f, i, i, i, i, f, f, i, i, f, f, i, i, i, p, p, p, p, p, i, p], i),
+        "canny_hip_hough_segments_profile_get": ([p, i, C.POINTER(C.c_double), C.POINTER(C.c_long)], i),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -367,6 +375,40 @@ def hough_line_of(base: int, numrho: int, rho: float, theta: float, min_theta: f
     if st != OK:
         raise CannyHipError(st, "hough_line_of")
     return np.float32(lr.value), np.float32(lt.value)
+
+
+SEGMENT_INTS = 6                                                # ints per record: x0, y0, x1, y1, line, support
+SEGMENT_PARTS = ("count", "emit", "exclusive")
+
+
+def hough_segments_from_bits(bits, height: int, width: int, bases, rho: float = 1.0, theta: float = np.pi / 180,
+                             min_theta: float = 0.0, max_theta: float = np.pi, min_length: int = 0, max_gap: int = 0,
+                             exclusive: int = 0, segments_max: Optional[int] = None, out=None):
+    """Host-only: the segment rule of include/canny_hip.h on one packed bit map (numpy.packbits(mask, axis=-1); padding
+    bits ignored) along the lines `bases` (accumulator cells, in order).  Returns (segments int32 [k, 6], count): the rows
+    x0, y0, x1, y1, line, support of the first k = min(segments_max, count) segments and the true count.  Without a
+    segments_max everything is returned.  `out` (int32, at least segments_max * 6) receives the records in place."""
+    b = np.ascontiguousarray(bits, dtype=np.uint8)
+    if height >= 1 and width >= 1 and b.size != height * ((width + 7) // 8):
+        raise ValueError(f"expected {height} rows of {(width + 7) // 8} bytes, got {b.size} bytes")
+    ba = np.ascontiguousarray(bases, dtype=np.uint32).ravel()
+    L = load()
+    n = C.c_int(0)
+
+    def run(buf, cap):
+        st = L.canny_hip_hough_segments_from_bits(_hp(b), height, width, rho, theta, min_theta, max_theta,
+                                                  _hp(ba) if ba.size else None, int(ba.size), min_length, max_gap,
+                                                  exclusive, _hp(buf), cap, C.byref(n))
+        if st:
+            raise CannyHipError(st, "hough_segments_from_bits")
+
+    if segments_max is None:
+        run(np.empty(SEGMENT_INTS, np.int32), 1)
+        segments_max = max(n.value, 1)
+    buf = out if out is not None else np.empty(max(int(segments_max), 1) * SEGMENT_INTS, np.int32)
+    run(buf, int(segments_max))
+    k = min(n.value, max(int(segments_max), 0))
+    return buf[:k * SEGMENT_INTS].reshape(k, SEGMENT_INTS), n.value
 
 
 def points_to_rc(points, width: int) -> Tuple[np.ndarray, np.ndarray]:
@@ -856,6 +898,73 @@ class Context:
         """Accumulated device milliseconds and launch groups of a Hough part (0 vote, 1 peaks, 2 select + sort)."""
         ms, n = C.c_double(0), C.c_long(0)
         self._check(self._L.canny_hip_hough_profile_get(self._h, part, C.byref(ms), C.byref(n)), "hough_profile_get")
+        return ms.value, n.value
+
+    # ---- Hough line segments (DESIGN.md section 16) --------------------------------------------------------------
+    def canny_hough_segments(self, imgs, sigma: float, min_val: int, max_val: int, rho: float = 1.0,
+                             theta: float = np.pi / 180, threshold: int = 100, lines_max: int = 256, min_length: int = 0,
+                             max_gap: int = 0, exclusive: int = 0, segments_max: int = 4096, min_theta: float = 0.0,
+                             max_theta: float = np.pi):
+        """canny(), the Hough lines of each map and the segments along them, all on the GPU: imgs (H, W) or (N, H, W)
+        uint8 -> (lines, line_counts, segments, seg_counts).  lines[f] as canny_hough returns it; segments[f] int32
+        [k, 6] rows x0, y0, x1, y1, line, support with k = min(segments_max, seg_counts[f]), ordered by (line, start);
+        both count arrays hold the true counts."""
+        a = np.ascontiguousarray(imgs, dtype=np.uint8)
+        if a.ndim == 2:
+            a = a[None]
+        if a.ndim != 3:
+            raise ValueError("expected uint8 [H, W] or [n_frames, H, W]")
+        n, h, w = a.shape
+        slots = n * max(int(lines_max), 1)
+        lines, votes = np.zeros((slots, 2), np.float32), np.zeros(slots, np.int32)
+        bases, counts = np.zeros(slots, np.uint32), np.zeros(n, np.int32)
+        segs = np.zeros((n, max(int(segments_max), 1), SEGMENT_INTS), np.int32)
+        seg_counts = np.zeros(n, np.int32)
+        self._check(self._L.canny_hip_canny_hough_segments(self._h, _hp(a), n, sigma, min_val, max_val, h, w, rho, theta,
+                                                           threshold, lines_max, min_theta, max_theta, min_length,
+                                                           max_gap, exclusive, _hp(lines), _hp(votes), _hp(bases),
+                                                           _hp(counts), _hp(segs), segments_max, _hp(seg_counts)),
+                    "canny_hough_segments")
+        out_l, out_s = [], []
+        for f in range(n):
+            k, at = min(int(counts[f]), lines_max), f * lines_max
+            out_l.append((lines[at:at + k].copy(), votes[at:at + k].copy(), bases[at:at + k].copy()))
+            out_s.append(segs[f, :min(int(seg_counts[f]), segments_max)].copy())
+        return out_l, counts, out_s, seg_counts
+
+    def dev_hough_segments_bits(self, d_bits: int, n: int, h: int, w: int, rho: float, theta: float, min_theta: float,
+                                max_theta: float, d_bases: int, d_line_counts: int, lines_max: int, min_length: int,
+                                max_gap: int, exclusive: int, d_segments: int, segments_max: int, d_seg_counts: int):
+        """The segments of device bit maps (layout of dev_canny_bits) along the lines a Hough call left on the device
+        (d_bases, d_line_counts, slot f * lines_max + k); d_segments: n * segments_max * 6 int32, d_seg_counts: n int32."""
+        v = C.c_void_p
+        self._check(self._L.canny_hip_dev_hough_segments_bits(self._h, v(d_bits or None), n, h, w, rho, theta, min_theta,
+                                                              max_theta, v(d_bases or None), v(d_line_counts or None),
+                                                              lines_max, min_length, max_gap, exclusive,
+                                                              v(d_segments or None), segments_max,
+                                                              v(d_seg_counts or None)), "dev_hough_segments_bits")
+
+    def dev_canny_hough_segments(self, d_img: int, sigma: float, min_val: int, max_val: int, h: int, w: int, n: int,
+                                 rho: float, theta: float, threshold: int, lines_max: int, min_theta: float,
+                                 max_theta: float, min_length: int, max_gap: int, exclusive: int, d_segments: int,
+                                 segments_max: int, d_seg_counts: int, d_lines: int = 0, d_votes: int = 0, d_bases: int = 0,
+                                 d_line_counts: int = 0, d_accum: int = 0, d_edges: int = 0):
+        """dev_canny_hough, then the segments along its lines queued behind it on the same stream; the line outputs and
+        d_edges are optional (0)."""
+        v = C.c_void_p
+        self._check(self._L.canny_hip_dev_canny_hough_segments(self._h, v(d_img or None), sigma, min_val, max_val, h, w, n,
+                                                               v(d_edges or None), rho, theta, threshold, lines_max,
+                                                               min_theta, max_theta, v(d_lines or None),
+                                                               v(d_votes or None), v(d_bases or None),
+                                                               v(d_line_counts or None), v(d_accum or None), min_length,
+                                                               max_gap, exclusive, v(d_segments or None), segments_max,
+                                                               v(d_seg_counts or None)), "dev_canny_hough_segments")
+
+    def hough_segments_profile_get(self, part: int) -> Tuple[float, int]:
+        """(total ms, launch groups) of part 0 count, 1 emit, 2 exclusive (SEGMENT_PARTS)."""
+        ms, n = C.c_double(0), C.c_long(0)
+        self._check(self._L.canny_hip_hough_segments_profile_get(self._h, part, C.byref(ms), C.byref(n)),
+                    "hough_segments_profile_get")
         return ms.value, n.value
 
     # ---- colour frames (interleaved BGR / RGB / BGRA / RGBA; the rule is the "gray_rule" option) --------------

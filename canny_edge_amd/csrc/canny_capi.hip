@@ -389,6 +389,9 @@ struct canny_hip_ctx {
     // distance transform: the row pass's u16 plane (2 B/px, rows padded to 64 pixels); the column scan's stack (4 B/px) when
     // the caller passes no dist2 plane to keep it in
     DevBuf edt_cols, edt_stack;
+    // Hough segments: per-line counts and offsets; bases and line counts when the caller passes none; the private copy of
+    // the map that exclusive mode clears pixels from
+    DevBuf seg_ws, seg_lines, seg_work;
     DevBuf plane_s, plane_c, stamps, flags; // hysteresis bit-planes / scheduling words
     DevBuf io[4];     // staging for the host-pointer stage functions
     unsigned *host_flags = nullptr;     // pinned + mapped, 4 words per lane: last_change, domain, sequence number, spare
@@ -412,10 +415,12 @@ struct canny_hip_ctx {
     unsigned prof_mask = ~0u; // stages whose launches get an event pair (each pair costs a few us of stream time)
     unsigned prof_every = 1;  // ... and only every prof_every-th launch group of a stage gets one
     // slots: the stages, then the three Hough parts (canny_hip_hough_profile_get), then the four parts of the component
-    // labelling (canny_hip_components_profile_get), then the two of the distance transform (canny_hip_edt_profile_get)
+    // labelling (canny_hip_components_profile_get), then the two of the distance transform (canny_hip_edt_profile_get),
+    // then the three of the Hough segments (canny_hip_hough_segments_profile_get)
     static constexpr int kProfHough = CANNY_HIP_STAGE_END, kProfComponents = CANNY_HIP_STAGE_END + 3;
     static constexpr int kProfEdt = kProfComponents + CANNY_HIP_CC_PARTS;
-    static constexpr int kProfSlots = kProfEdt + CANNY_HIP_EDT_PARTS;
+    static constexpr int kProfSegments = kProfEdt + CANNY_HIP_EDT_PARTS;
+    static constexpr int kProfSlots = kProfSegments + CANNY_HIP_SEGMENT_PARTS;
     unsigned prof_seen[kProfSlots] = {0};
     std::vector<EventPair> pending[kProfSlots];
     std::vector<EventPair> pool;
@@ -1324,6 +1329,28 @@ int hough_prepare(const canny_hip_ctx *ctx, int height, int width, float rho, fl
     return CANNY_HIP_OK;
 }
 
+// The vote tables of hg on the device (ctx->hough_tab): they travel once per set of arguments; the host copy outlives its
+// transfer.
+int hough_tab_ensure(canny_hip_ctx *ctx, const HoughGeom &hg)
+{
+    const size_t tab_bytes = 2 * (size_t)hg.numangle * sizeof(float);
+    const bool tab_moved = ctx->hough_tab.bytes < tab_bytes;
+    HIP_TRY(ctx, ctx->hough_tab.ensure(tab_bytes));
+    if (tab_moved || ctx->hough_tab_n != hg.numangle || ctx->hough_tab_key[0] != hg.rho ||
+        ctx->hough_tab_key[1] != hg.theta || ctx->hough_tab_key[2] != hg.min_theta) {
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); // an earlier transfer may still read the host copy
+        ctx->hough_tab_host.resize(2 * (size_t)hg.numangle);
+        hough_tables(hg.rho, hg.theta, hg.min_theta, hg.numangle, ctx->hough_tab_host.data(),
+                     ctx->hough_tab_host.data() + hg.numangle);
+        ctx->hough_tab_n = 0;
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->hough_tab.p, ctx->hough_tab_host.data(), tab_bytes, hipMemcpyHostToDevice,
+                                    ctx->stream));
+        ctx->hough_tab_n = hg.numangle;
+        ctx->hough_tab_key[0] = hg.rho, ctx->hough_tab_key[1] = hg.theta, ctx->hough_tab_key[2] = hg.min_theta;
+    }
+    return CANNY_HIP_OK;
+}
+
 // The transform of one source (CSR points, packed bits or the context's strong plane), queued on the context's stream.
 // All three null: the empty map (counts 0, a zero accumulator if the caller asked for it).
 int dev_hough(canny_hip_ctx *ctx, const uint64_t *strong, const uint8_t *bits, const unsigned *points,
@@ -1341,22 +1368,8 @@ int dev_hough(canny_hip_ctx *ctx, const uint64_t *strong, const uint8_t *bits, c
         HIP_TRY(ctx, ctx->hough_accum.ensure(hough_accum_bytes(hg, n)));
         accum = (int *)ctx->hough_accum.p;
     }
-    // the tables travel once per set of arguments; the host copy outlives its transfer
-    const size_t tab_bytes = 2 * (size_t)hg.numangle * sizeof(float);
-    const bool tab_moved = ctx->hough_tab.bytes < tab_bytes;
-    HIP_TRY(ctx, ctx->hough_tab.ensure(tab_bytes));
-    if (tab_moved || ctx->hough_tab_n != hg.numangle || ctx->hough_tab_key[0] != hg.rho ||
-        ctx->hough_tab_key[1] != hg.theta || ctx->hough_tab_key[2] != hg.min_theta) {
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); // an earlier transfer may still read the host copy
-        ctx->hough_tab_host.resize(2 * (size_t)hg.numangle);
-        hough_tables(hg.rho, hg.theta, hg.min_theta, hg.numangle, ctx->hough_tab_host.data(),
-                     ctx->hough_tab_host.data() + hg.numangle);
-        ctx->hough_tab_n = 0;
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->hough_tab.p, ctx->hough_tab_host.data(), tab_bytes, hipMemcpyHostToDevice,
-                                    ctx->stream));
-        ctx->hough_tab_n = hg.numangle;
-        ctx->hough_tab_key[0] = hg.rho, ctx->hough_tab_key[1] = hg.theta, ctx->hough_tab_key[2] = hg.min_theta;
-    }
+    int rc = hough_tab_ensure(ctx, hg);
+    if (rc) return rc;
     double bins_d;
     (void)hough_hist_bins(g.height, g.width, hg.rho, &bins_d);
     const int bins = (int)bins_d;
@@ -1381,6 +1394,83 @@ int dev_hough(canny_hip_ctx *ctx, const uint64_t *strong, const uint8_t *bits, c
         StageTimer tm(ctx, CANNY_HIP_STAGE_END + 2);
         HIP_TRY(ctx, launch_hough_select(accum, n, hg, threshold, lines_max, out.d_counts, hist, bins, ties, cut, cand,
                                          out.d_lines, out.d_votes, out.d_bases, ctx->stream));
+    }
+    return CANNY_HIP_OK;
+}
+
+// ---- Hough line segments (canny_hough_segments.hip) ---------------------
+struct SegArgs {
+    int min_length, max_gap, exclusive, segments_max;
+};
+
+// THE check of the segment arguments; needs no device and writes nothing.  lines: the longest line list of a frame;
+// on_device: the kernels' limit on exclusive mode applies (the host walk has none).
+int segments_check(int height, int width, int n_frames, int lines, const SegArgs &a, bool on_device)
+{
+    if (a.min_length < 0 || a.max_gap < 0 || (a.exclusive != 0 && a.exclusive != 1) || a.segments_max < 1)
+        return CANNY_HIP_ERR_INVALID;
+    if ((double)n_frames * (double)a.segments_max * CANNY_HIP_SEGMENT_INTS >= 2147483648.0) return CANNY_HIP_ERR_UNSUPPORTED;
+    // a line has at most ceil(L / 2) segments; a frame's count is an int
+    if ((double)lines * (((double)std::max(height, width) + 1.0) / 2.0) >= 2147483648.0) return CANNY_HIP_ERR_UNSUPPORTED;
+    // exclusive mode keeps one bit per major position in LDS
+    if (on_device && a.exclusive && std::max(height, width) > kSegExclusiveMaxAxis) return CANNY_HIP_ERR_UNSUPPORTED;
+    return CANNY_HIP_OK;
+}
+
+// The rule's vote on the host (built with -ffp-contract=off: three roundings), for canny_hip_hough_segments_from_bits.
+inline int host_vote_r(int x, int y, float c, float s, int half)
+{
+    const float a = (float)x * c, b = (float)y * s;
+    return (int)std::nearbyintf(a + b) + half;
+}
+
+// The segments of one source (packed bits or the context's strong plane) along the lines in d_bases / d_line_counts,
+// queued on the context's stream.  Both sources null: the empty map (all counts 0).
+int dev_segments(canny_hip_ctx *ctx, const uint64_t *strong, const uint8_t *bits, const HystGeom &g, const HoughGeom &hg,
+                 const unsigned *d_bases, const int *d_line_counts, int lines_max, const SegArgs &a, int *d_segments,
+                 int *d_seg_counts)
+{
+    const int n = g.n_frames;
+    if (!strong && !bits) {
+        HIP_TRY(ctx, hipMemsetAsync(d_seg_counts, 0, (size_t)n * sizeof(int), ctx->stream));
+        return CANNY_HIP_OK;
+    }
+    int rc = hough_tab_ensure(ctx, hg);
+    if (rc) return rc;
+    const float *tab = (const float *)ctx->hough_tab.p;
+    const SegGeom sg{hg.numangle, hg.numrho, hough_segments_halfwin(g.height, g.width, hg.rho), a.min_length, a.max_gap,
+                     lines_max, a.segments_max};
+    const int part = canny_hip_ctx::kProfSegments;
+    if (a.exclusive) {
+        // The private copy is read and cleared as 32-bit words by one workgroup per frame with workgroup-scope atomics, so
+        // no word may belong to two frames.  The plane's frames are whole 64-bit words already; packed bytes get a stride
+        // of their own per frame (hough_segments_work_stride: a multiple of 128 bytes), whatever height * row bytes is.
+        const size_t frame_bytes = bits ? (size_t)g.height * ((g.width + 7) / 8) : g.words() / n * sizeof(uint64_t);
+        const size_t stride = bits ? hough_segments_work_stride(g) : frame_bytes;
+        HIP_TRY(ctx, ctx->seg_work.ensure(stride * n));
+        StageTimer tm(ctx, part + CANNY_HIP_SEGMENT_PART_EXCLUSIVE);
+        if (bits)
+            HIP_TRY(ctx, hipMemcpy2DAsync(ctx->seg_work.p, stride, bits, frame_bytes, frame_bytes, (size_t)n,
+                                          hipMemcpyDeviceToDevice, ctx->stream));
+        else
+            HIP_TRY(ctx, hipMemcpyAsync(ctx->seg_work.p, strong, frame_bytes * n, hipMemcpyDeviceToDevice, ctx->stream));
+        HIP_TRY(ctx, launch_hough_segments_exclusive((uint32_t *)ctx->seg_work.p, bits != nullptr, g, sg, tab, d_bases,
+                                                     d_line_counts, d_segments, d_seg_counts, ctx->stream));
+        return CANNY_HIP_OK;
+    }
+    // per-line segment counts | their exclusive prefix within the frame
+    const size_t slots = (size_t)n * lines_max;
+    HIP_TRY(ctx, ctx->seg_ws.ensure(2 * slots * sizeof(int)));
+    int *nseg = (int *)ctx->seg_ws.p, *line_off = nseg + slots;
+    {
+        StageTimer tm(ctx, part + CANNY_HIP_SEGMENT_PART_COUNT);
+        HIP_TRY(ctx, launch_hough_segments_count(strong, bits, g, sg, tab, d_bases, d_line_counts, nseg, line_off,
+                                                 d_seg_counts, ctx->stream));
+    }
+    {
+        StageTimer tm(ctx, part + CANNY_HIP_SEGMENT_PART_EMIT);
+        HIP_TRY(ctx, launch_hough_segments_emit(strong, bits, g, sg, tab, d_bases, d_line_counts, line_off, d_segments,
+                                                ctx->stream));
     }
     return CANNY_HIP_OK;
 }
@@ -1525,6 +1615,9 @@ void canny_hip_ctx_destroy(canny_hip_ctx *ctx)
     ctx->hough_accum.release();
     ctx->hough_ws.release();
     ctx->hough_tab.release();
+    ctx->seg_ws.release();
+    ctx->seg_lines.release();
+    ctx->seg_work.release();
     ctx->cc_parent.release();
     ctx->cc_ws.release();
     ctx->edt_cols.release();
@@ -3203,6 +3296,193 @@ int canny_hip_canny_hough(canny_hip_ctx *ctx, const unsigned char *imgs, int n_f
     return CANNY_HIP_OK;
 }
 
+// ---- Hough line segments ------------------------------------------------------------------------------------
+int canny_hip_hough_segments_from_bits(const unsigned char *bits, int height, int width, float rho, float theta,
+                                       float min_theta, float max_theta, const unsigned int *bases, int n_lines,
+                                       int min_length, int max_gap, int exclusive, int *segments, int segments_max,
+                                       int *count)
+{
+    if (!bits || !segments || !count || n_lines < 0 || (n_lines && !bases)) return CANNY_HIP_ERR_INVALID;
+    int rc = check_dims(height, width, 1);
+    if (rc) return rc;
+    const SegArgs a{min_length, max_gap, exclusive, segments_max};
+    int numangle, numrho;
+    if ((rc = hough_geometry(height, width, rho, theta, min_theta, max_theta, &numangle, &numrho))) return rc;
+    if ((rc = segments_check(height, width, 1, n_lines, a, false))) return rc;
+    std::vector<float> tab(2 * (size_t)numangle);
+    hough_tables(rho, theta, min_theta, numangle, tab.data(), tab.data() + numangle);
+    // the working map W as the list of its set pixels
+    const size_t row_bytes = ((size_t)width + 7) / 8;
+    std::vector<int> px, py;
+    for (int y = 0; y < height; y++)
+        for (int x = 0; x < width; x++)
+            if (bits[(size_t)y * row_bytes + (x >> 3)] >> (7 - (x & 7)) & 1) px.push_back(x), py.push_back(y);
+    std::vector<char> alive(px.size(), 1);
+    const int half = (numrho - 1) / 2, axis = std::max(height, width);
+    std::vector<int> cnt((size_t)axis), lo((size_t)axis);
+    std::vector<char> keep((size_t)axis);
+    std::vector<size_t> members;
+    const unsigned stride = (unsigned)numrho + 2u;
+    int total = 0;
+    for (int k = 0; k < n_lines; k++) {
+        const int n = (int)(bases[k] / stride) - 1, r = (int)(bases[k] % stride) - 1;
+        if (n < 0 || n >= numangle || r < 0 || r >= numrho) continue; // not a line
+        const float c = tab[n], s = tab[(size_t)numangle + n];
+        const bool major_x = std::fabs(s) >= std::fabs(c);
+        const int L = major_x ? width : height;
+        std::fill(cnt.begin(), cnt.begin() + L, 0);
+        std::fill(keep.begin(), keep.begin() + L, 0);
+        members.clear();
+        for (size_t i = 0; i < px.size(); i++) { // the support: every pixel of W that votes for the cell
+            if (!alive[i] || host_vote_r(px[i], py[i], c, s, half) != r) continue;
+            const int t = major_x ? px[i] : py[i], m = major_x ? py[i] : px[i];
+            if (!cnt[t] || m < lo[t]) lo[t] = m;
+            cnt[t]++;
+            members.push_back(i);
+        }
+        int ta = -1, last = -1, support = 0;
+        auto close = [&]() {
+            if (last - ta < min_length) return;
+            if (total < segments_max) {
+                int *rec = segments + (size_t)total * CANNY_HIP_SEGMENT_INTS;
+                rec[0] = major_x ? ta : lo[ta], rec[1] = major_x ? lo[ta] : ta;
+                rec[2] = major_x ? last : lo[last], rec[3] = major_x ? lo[last] : last;
+                rec[4] = k, rec[5] = support;
+            }
+            total++;
+            std::fill(keep.begin() + ta, keep.begin() + last + 1, 1);
+        };
+        for (int t = 0; t < L; t++) {
+            if (!cnt[t]) continue;
+            if (ta >= 0 && t - last - 1 > max_gap) close(), ta = -1;
+            if (ta < 0) ta = t, support = 0;
+            support += cnt[t];
+            last = t;
+        }
+        if (ta >= 0) close();
+        if (exclusive)
+            for (size_t i : members)
+                if (keep[major_x ? px[i] : py[i]]) alive[i] = 0;
+    }
+    *count = total;
+    return CANNY_HIP_OK;
+}
+
+int canny_hip_dev_hough_segments_bits(canny_hip_ctx *ctx, const unsigned char *d_bits, int n_frames, int height, int width,
+                                      float rho, float theta, float min_theta, float max_theta,
+                                      const unsigned int *d_bases, const int *d_line_counts, int lines_max, int min_length,
+                                      int max_gap, int exclusive, int *d_segments, int segments_max, int *d_seg_counts)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!d_bits || !d_bases || !d_line_counts || !d_segments || !d_seg_counts || lines_max < 1) return CANNY_HIP_ERR_INVALID;
+    if ((rc = check_dims(height, width, n_frames))) return rc;
+    const SegArgs a{min_length, max_gap, exclusive, segments_max};
+    HoughGeom hg;
+    if ((rc = hough_geometry(height, width, rho, theta, min_theta, max_theta, &hg.numangle, &hg.numrho))) return rc;
+    if (lines_max > kHoughMaxLines) return CANNY_HIP_ERR_UNSUPPORTED;
+    if ((rc = segments_check(height, width, n_frames, lines_max, a, true))) return rc;
+    hg.rho = rho, hg.theta = theta, hg.min_theta = min_theta;
+    if ((rc = finish_pending(ctx))) return rc;
+    return dev_segments(ctx, nullptr, d_bits, make_hyst_geom(height, width, n_frames), hg, d_bases, d_line_counts,
+                        lines_max, a, d_segments, d_seg_counts);
+}
+
+int canny_hip_dev_canny_hough_segments(canny_hip_ctx *ctx, const unsigned char *d_img, float sigma, int min_val,
+                                       int max_val, int height, int width, int n_frames, short *d_edges, float rho,
+                                       float theta, int threshold, int lines_max, float min_theta, float max_theta,
+                                       float *d_lines, int *d_votes, unsigned int *d_bases, int *d_line_counts,
+                                       int *d_accum, int min_length, int max_gap, int exclusive, int *d_segments,
+                                       int segments_max, int *d_seg_counts)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!d_img || !d_segments || !d_seg_counts || lines_max < 1) return CANNY_HIP_ERR_INVALID;
+    if ((rc = check_dims(height, width, n_frames))) return rc;
+    const SegArgs a{min_length, max_gap, exclusive, segments_max};
+    HoughGeom hg;
+    {
+        int lds_rows = 0, probe = 0;
+        const HoughOut out{nullptr, nullptr, nullptr, &probe, nullptr};
+        if ((rc = hough_prepare(ctx, height, width, rho, theta, lines_max, min_theta, max_theta, out, hg, &lds_rows)))
+            return rc;
+    }
+    if ((rc = segments_check(height, width, n_frames, lines_max, a, true))) return rc;
+    // bases and line counts the caller does not want live in the context: line counts | bases
+    const size_t slots = (size_t)n_frames * lines_max;
+    if (!d_bases || !d_line_counts) {
+        HIP_TRY(ctx, ctx->seg_lines.ensure((slots + (size_t)n_frames) * sizeof(int)));
+        int *own = (int *)ctx->seg_lines.p;
+        if (!d_bases) d_bases = (unsigned int *)own;
+        if (!d_line_counts) d_line_counts = own + slots;
+    }
+    if ((rc = canny_hip_dev_canny_hough(ctx, d_img, sigma, min_val, max_val, height, width, n_frames, d_edges, rho, theta,
+                                        threshold, lines_max, min_theta, max_theta, d_lines, d_votes, d_bases,
+                                        d_line_counts, d_accum)))
+        return rc;
+    // the segments follow the MAP: max_val > 255 zeroes every reached pixel although strong bits are set
+    const uint64_t *strong = max_val > 255 ? nullptr : (const uint64_t *)ctx->plane_s.p;
+    return dev_segments(ctx, strong, nullptr, make_hyst_geom(height, width, n_frames), hg, d_bases, d_line_counts,
+                        lines_max, a, d_segments, d_seg_counts);
+}
+
+int canny_hip_canny_hough_segments(canny_hip_ctx *ctx, const unsigned char *imgs, int n_frames, float sigma, int min_val,
+                                   int max_val, int height, int width, float rho, float theta, int threshold,
+                                   int lines_max, float min_theta, float max_theta, int min_length, int max_gap,
+                                   int exclusive, float *lines, int *votes, unsigned int *bases, int *line_counts,
+                                   int *segments, int segments_max, int *seg_counts)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!imgs || !segments || !seg_counts || lines_max < 1) return CANNY_HIP_ERR_INVALID;
+    if ((rc = check_dims(height, width, n_frames))) return rc;
+    {
+        const SegArgs a{min_length, max_gap, exclusive, segments_max};
+        HoughGeom hg;
+        int lds_rows = 0, probe = 0;
+        const HoughOut out{nullptr, nullptr, nullptr, &probe, nullptr};
+        if ((rc = hough_prepare(ctx, height, width, rho, theta, lines_max, min_theta, max_theta, out, hg, &lds_rows)) ||
+            (rc = segments_check(height, width, n_frames, lines_max, a, true)))
+            return rc;
+    }
+    const size_t slots = (size_t)n_frames * lines_max, seg_ints = (size_t)n_frames * segments_max * CANNY_HIP_SEGMENT_INTS;
+    // staging: lines (2 floats per slot) | votes | bases | line counts | segment counts; the records in a block of their own
+    HIP_TRY(ctx, ctx->io[1].ensure(slots * 16 + 2 * (size_t)n_frames * sizeof(int)));
+    HIP_TRY(ctx, ctx->io[2].ensure(seg_ints * sizeof(int)));
+    char *d = (char *)ctx->io[1].p;
+    float *d_lines = (float *)d;
+    int *d_votes = (int *)(d + slots * 8);
+    unsigned *d_bases = (unsigned *)(d + slots * 12);
+    int *d_line_counts = (int *)(d + slots * 16), *d_seg_counts = d_line_counts + n_frames;
+    int *d_segments = (int *)ctx->io[2].p;
+    if ((rc = h2d(ctx, ctx->io[0], imgs, npx(height, width, n_frames)))) return rc;
+    if ((rc = canny_hip_dev_canny_hough_segments(ctx, (const unsigned char *)ctx->io[0].p, sigma, min_val, max_val, height,
+                                                 width, n_frames, nullptr, rho, theta, threshold, lines_max, min_theta,
+                                                 max_theta, lines ? d_lines : nullptr, votes ? d_votes : nullptr, d_bases,
+                                                 d_line_counts, nullptr, min_length, max_gap, exclusive, d_segments,
+                                                 segments_max, d_seg_counts)))
+        return rc;
+    std::vector<int> cnt(2 * (size_t)n_frames);
+    if ((rc = d2h_sync(ctx, cnt.data(), d_line_counts, cnt.size() * sizeof(int)))) return rc;
+    // the counts first, then only the filled slots of each frame
+    for (int f = 0; f < n_frames; f++) {
+        const size_t k = (size_t)std::min(cnt[f], lines_max), at = (size_t)f * lines_max;
+        if (k && lines)
+            HIP_TRY(ctx, hipMemcpyAsync(lines + 2 * at, d_lines + 2 * at, k * 8, hipMemcpyDeviceToHost, ctx->stream));
+        if (k && votes) HIP_TRY(ctx, hipMemcpyAsync(votes + at, d_votes + at, k * 4, hipMemcpyDeviceToHost, ctx->stream));
+        if (k && bases) HIP_TRY(ctx, hipMemcpyAsync(bases + at, d_bases + at, k * 4, hipMemcpyDeviceToHost, ctx->stream));
+        const size_t j = (size_t)std::min(cnt[(size_t)n_frames + f], segments_max);
+        const size_t sat = (size_t)f * segments_max * CANNY_HIP_SEGMENT_INTS;
+        if (j)
+            HIP_TRY(ctx, hipMemcpyAsync(segments + sat, d_segments + sat, j * CANNY_HIP_SEGMENT_INTS * sizeof(int),
+                                        hipMemcpyDeviceToHost, ctx->stream));
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (line_counts) std::memcpy(line_counts, cnt.data(), (size_t)n_frames * sizeof(int));
+    std::memcpy(seg_counts, cnt.data() + n_frames, (size_t)n_frames * sizeof(int));
+    return CANNY_HIP_OK;
+}
+
 int canny_hip_hough_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches)
 {
     if (part < 0 || part > 2 || !total_ms || !launches) return CANNY_HIP_ERR_INVALID;
@@ -3233,6 +3513,17 @@ int canny_hip_edt_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, lo
     if ((rc = profile_collect(ctx))) return rc;
     *total_ms = ctx->total_ms[canny_hip_ctx::kProfEdt + part];
     *launches = ctx->launches[canny_hip_ctx::kProfEdt + part];
+    return CANNY_HIP_OK;
+}
+
+int canny_hip_hough_segments_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches)
+{
+    if (part < 0 || part >= CANNY_HIP_SEGMENT_PARTS || !total_ms || !launches) return CANNY_HIP_ERR_INVALID;
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if ((rc = profile_collect(ctx))) return rc;
+    *total_ms = ctx->total_ms[canny_hip_ctx::kProfSegments + part];
+    *launches = ctx->launches[canny_hip_ctx::kProfSegments + part];
     return CANNY_HIP_OK;
 }
 

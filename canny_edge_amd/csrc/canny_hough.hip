@@ -42,11 +42,6 @@ struct VoteSrc {
     const unsigned long long *offsets;
 };
 
-__device__ __forceinline__ int vote_r(int x, int y, float c, float s, int half)
-{
-    return (int)rintf(__fadd_rn(__fmul_rn((float)x, c), __fmul_rn((float)y, s))) + half;
-}
-
 // word u of frame f: 64 consecutive pixels of one row, bit i = column x0 + i, columns >= width cleared.
 // Strong plane: u runs over the plane's words in memory order (a wave's load is one coalesced 512 bytes = 64 rows of
 // one tile); rows past the height hold nothing.  Packed bits: u = y * tiles_x + k, rows MSB-first, padding bits masked.

@@ -355,6 +355,15 @@ inline size_t hough_accum_bytes(const HoughGeom &hg, int n_frames)
 {
     return (size_t)n_frames * (hg.numangle + 2) * (size_t)(hg.numrho + 2) * sizeof(int);
 }
+#ifdef __HIPCC__
+// THE vote of the rule: accumulator column of pixel (x, y) for one angle's table entries c, s; half = (numrho - 1) / 2.
+// Three operations, each rounded to binary32 on its own, then round-half-even to int (v_rndne_f32).  The vote kernels
+// and the segment walk (canny_hough_segments.hip) both call it, so the pixels of a cell are exactly those that voted.
+__device__ __forceinline__ int vote_r(int x, int y, float c, float s, int half)
+{
+    return (int)rintf(__fadd_rn(__fmul_rn((float)x, c), __fmul_rn((float)y, s))) + half;
+}
+#endif
 // Accumulator rows a vote workgroup keeps in LDS for a budget in bytes: at least one row if a row fits in LDS at all
 // (then the budget yields), at most 16; 0 = a row does not fit, only the global-atomic form applies.
 int hough_lds_rows(const HoughGeom &hg, int budget_bytes);
@@ -374,6 +383,41 @@ hipError_t launch_hough_peaks(const int *accum, int n_frames, const HoughGeom &h
 hipError_t launch_hough_select(const int *accum, int n_frames, const HoughGeom &hg, int threshold, int lines_max,
                                const int *counts, const unsigned *hist, int hist_bins, unsigned *ties, unsigned *cut,
                                unsigned long long *cand, float *lines, int *votes, unsigned *bases, hipStream_t stream);
+
+// ---- Hough line segments (canny_hough_segments.hip) --------------------
+// Runs of edge pixels along detected lines.  The line list of frame f is bases[f * lines_max .. + min(lines_max,
+// line_counts[f])), as launch_hough_select leaves it; tab as for the vote.  halfwin: half width of the minor-axis window a
+// lane searches around its float estimate (hough_segments_halfwin); the exact vote decides inside it.
+struct SegGeom {
+    int numangle, numrho;
+    float halfwin;
+    int min_length, max_gap, lines_max, segments_max;
+};
+constexpr int kSegRecord = 6;                  // CANNY_HIP_SEGMENT_INTS: x0, y0, x1, y1, line, support
+constexpr int kSegExclusiveMaxAxis = 1 << 20;  // exclusive mode: one bit per major position in LDS (128 KiB)
+float hough_segments_halfwin(int height, int width, float rho);
+// Non-exclusive, pass 1: one wave per (frame, line) walks the line and counts its segments into nseg[f * lines_max + k];
+// one workgroup per frame then scans them: line_off = exclusive prefix, seg_counts[f] = the frame's total.
+// Source: bits (packed, as for the point lists) or else the strong plane.
+hipError_t launch_hough_segments_count(const uint64_t *strong, const uint8_t *bits, const HystGeom &g, const SegGeom &sg,
+                                       const float *tab, const unsigned *bases, const int *line_counts, int *nseg,
+                                       int *line_off, int *seg_counts, hipStream_t stream);
+// Non-exclusive, pass 2: the same walk; the j-th segment of line k goes to record line_off + j of the frame if that lies
+// below segments_max.
+hipError_t launch_hough_segments_emit(const uint64_t *strong, const uint8_t *bits, const HystGeom &g, const SegGeom &sg,
+                                      const float *tab, const unsigned *bases, const int *line_counts, const int *line_off,
+                                      int *segments, hipStream_t stream);
+// Exclusive: one workgroup per frame takes the lines in order on `work`, a PRIVATE copy of the source, read and cleared as
+// 32-bit words with workgroup-scope atomics -- so no 32-bit word of it may hold bits of two frames.  work_is_bits: frame f's
+// packed rows start at byte f * hough_segments_work_stride(g), densely packed behind that; otherwise the strong plane's words
+// as they are (a frame is whole 64-bit words).  max(height, width) <= kSegExclusiveMaxAxis.
+inline size_t hough_segments_work_stride(const HystGeom &g)
+{
+    return ((size_t)g.height * ((g.width + 7) / 8) + 127) & ~(size_t)127;
+}
+hipError_t launch_hough_segments_exclusive(uint32_t *work, bool work_is_bits, const HystGeom &g, const SegGeom &sg,
+                                           const float *tab, const unsigned *bases, const int *line_counts, int *segments,
+                                           int *seg_counts, hipStream_t stream);
 
 // ---- Connected components (canny_components.hip) -----------------------
 // Source as for the point lists: the strong plane of geometry g, or -- bits != nullptr -- a packed bit map.

@@ -1,6 +1,6 @@
 // main.cpp -- the reference's command line (StevenChang5/Canny_Edge src/main.cpp:18-142) without
 // the webcam and the GUI:  ./Main sigma minVal maxVal [-c] [-s] [-i in.pgm|in.ppm|in.jpg] [-o dir] [-p] [-n WxH] [-b dir]
-//        [-l rho,theta_degrees,threshold[,lines_max]] [-m min_area] [-d]
+//        [-l rho,theta_degrees,threshold[,lines_max]] [-g min_length,max_gap[,exclusive]] [-m min_area] [-d]
 //
 // Kept from the reference: the three positionals may appear anywhere relative to the flags
 // (src/main.cpp:29-46); exactly three are required, otherwise the usage text is printed and the
@@ -15,6 +15,8 @@
 // Added: -l runs the Hough line transform of the frame's edge map on the GPU as well (canny_hip_canny_hough) and writes
 // one "rho theta votes" row per detected line, strongest first, to canny_lines.txt in the -o directory (to stdout
 // without -o).  Without -l nothing changes.
+// Added: -g min_length,max_gap[,exclusive] (with -l) also writes the segments along those lines, one "x0 y0 x1 y1 line
+// support" row each, to canny_segments.txt (canny_hip_canny_hough_segments).  -g without -l is a usage error (exit 2).
 // Added: -m labels the 8-connected components of the frame's edge map on the GPU (canny_hip_canny_components), drops those
 // with fewer than min_area pixels and writes one "label left top width height area" row per kept component to
 // canny_components.txt and the filtered map to canny_kept.pgm (.png with -p) in the -o directory (rows to stdout without
@@ -214,7 +216,20 @@ static int run_batch(const string &dir, const string &outdir, float sigma, int m
     return 0;
 }
 
-// -l: the lines of the frame's edge map, "%.9g %.9g %d" per line
+// canny_lines.txt (stdout without -o): "%.9g %.9g %d" per line, strongest first -- the one writer behind -l and -l -g
+static int write_lines(const vector<float> &lines, const vector<int> &votes, int n_lines, const string &outdir)
+{
+    FILE *f = outdir.empty() ? stdout : fopen((outdir + "/canny_lines.txt").c_str(), "w");
+    if (!f) {
+        fprintf(stderr, "ERROR: cannot write %s/canny_lines.txt\n", outdir.c_str());
+        return 1;
+    }
+    for (int k = 0; k < n_lines; k++) fprintf(f, "%.9g %.9g %d\n", lines[2 * k], lines[2 * k + 1], votes[k]);
+    if (f != stdout) fclose(f);
+    return 0;
+}
+
+// -l: the lines of the frame's edge map
 static int run_hough(const vector<unsigned char> &frame, int height, int width, float sigma, int minVal, int maxVal,
                      double rho, double theta_deg, int threshold, int lines_max, const string &outdir)
 {
@@ -233,12 +248,45 @@ static int run_hough(const vector<unsigned char> &frame, int height, int width, 
         return 1;
     }
     canny_hip_ctx_destroy(ctx);
-    FILE *f = outdir.empty() ? stdout : fopen((outdir + "/canny_lines.txt").c_str(), "w");
-    if (!f) {
-        fprintf(stderr, "ERROR: cannot write %s/canny_lines.txt\n", outdir.c_str());
+    return write_lines(lines, votes, min(count, lines_max), outdir);
+}
+
+// -l with -g: the lines as above and the segments along them, "x0 y0 x1 y1 line support" per segment
+static int run_segments(const vector<unsigned char> &frame, int height, int width, float sigma, int minVal, int maxVal,
+                        double rho, double theta_deg, int threshold, int lines_max, int min_length, int max_gap,
+                        int exclusive, const string &outdir)
+{
+    const float theta = (float)(theta_deg * M_PI / 180.0);
+    vector<float> lines((size_t)2 * max(lines_max, 1));
+    vector<int> votes((size_t)max(lines_max, 1));
+    vector<int> segs;
+    int count = 0, seg_count = 0, cap = 4096;
+    canny_hip_ctx *ctx = nullptr;
+    int st = canny_hip_ctx_create(&ctx, 0);
+    for (int pass = 0; !st && pass < 2; pass++) { // a second time only if the first capacity was too small
+        segs.resize((size_t)cap * CANNY_HIP_SEGMENT_INTS);
+        st = canny_hip_canny_hough_segments(ctx, frame.data(), 1, sigma, minVal, maxVal, height, width, (float)rho, theta,
+                                            threshold, lines_max, 0.0f, (float)M_PI, min_length, max_gap, exclusive,
+                                            lines.data(), votes.data(), nullptr, &count, segs.data(), cap, &seg_count);
+        if (seg_count <= cap) break;
+        cap = seg_count;
+    }
+    if (st) {
+        fprintf(stderr, "ERROR: -g: %s\n", st == CANNY_HIP_ERR_RUNTIME && ctx ? canny_hip_last_error(ctx) : canny_hip_status_string(st));
+        if (ctx) canny_hip_ctx_destroy(ctx);
         return 1;
     }
-    for (int k = 0; k < min(count, lines_max); k++) fprintf(f, "%.9g %.9g %d\n", lines[2 * k], lines[2 * k + 1], votes[k]);
+    canny_hip_ctx_destroy(ctx);
+    if (write_lines(lines, votes, min(count, lines_max), outdir)) return 1;
+    FILE *f = outdir.empty() ? stdout : fopen((outdir + "/canny_segments.txt").c_str(), "w");
+    if (!f) {
+        fprintf(stderr, "ERROR: cannot write %s/canny_segments.txt\n", outdir.c_str());
+        return 1;
+    }
+    for (int j = 0; j < seg_count; j++) {
+        const int *r = segs.data() + (size_t)j * CANNY_HIP_SEGMENT_INTS;
+        fprintf(f, "%d %d %d %d %d %d\n", r[0], r[1], r[2], r[3], r[4], r[5]);
+    }
     if (f != stdout) fclose(f);
     return 0;
 }
@@ -332,6 +380,8 @@ int main(int argc, char *argv[])
     bool want_lines = false;
     double line_rho = 1.0, line_theta_deg = 1.0;
     int line_threshold = 0, lines_max = 256;
+    bool want_segments = false;
+    int seg_min_length = 0, seg_max_gap = 0, seg_exclusive = 0;
     bool want_components = false;
     int min_area = 1;
     bool want_dist = false;
@@ -359,6 +409,12 @@ int main(int argc, char *argv[])
                 exit(0);
             }
             want_lines = true;
+        } else if (arg == "-g" && i + 1 < argc) {
+            if (sscanf(argv[++i], "%d,%d,%d", &seg_min_length, &seg_max_gap, &seg_exclusive) < 2) {
+                fprintf(stderr, "ERROR: -g expects min_length,max_gap[,exclusive]\n");
+                exit(2);
+            }
+            want_segments = true;
         } else if (arg == "-m" && i + 1 < argc) {
             if (sscanf(argv[++i], "%d", &min_area) != 1) {
                 fprintf(stderr, "ERROR: -m expects min_area\n");
@@ -377,6 +433,10 @@ int main(int argc, char *argv[])
         }
     }
 
+    if (want_segments && !want_lines) {
+        fprintf(stderr, "ERROR: -g needs the lines of -l rho,theta_degrees,threshold[,lines_max]\n");
+        exit(2);
+    }
     if (values.size() != 3) {
         fprintf(stderr, "USAGE: %s sigma minVal maxVal\n", argv[0]);
         fprintf(stderr, "   sigma: Standard deviation used for the gaussian blurring kernel\n");
@@ -389,6 +449,7 @@ int main(int argc, char *argv[])
         fprintf(stderr, "   -p: write PNG files instead of PGM\n");
         fprintf(stderr, "   -b dir: run every .pgm / .jpg of dir as one batch, write <name>_edges.pgm\n");
         fprintf(stderr, "   -l rho,theta_degrees,threshold[,lines_max]: Hough lines of the edge map -> canny_lines.txt in the -o dir\n");
+        fprintf(stderr, "   -g min_length,max_gap[,exclusive]: with -l, the segments along the lines -> canny_segments.txt in the -o dir\n");
         fprintf(stderr, "   -m min_area: connected components of the edge map with at least min_area pixels -> canny_components.txt,\n");
         fprintf(stderr, "                canny_kept.pgm in the -o dir\n");
         fprintf(stderr, "   -d: distance of every pixel to the nearest edge pixel, min(255, floor) -> canny_dist.pgm in the -o dir\n");
@@ -453,6 +514,9 @@ int main(int argc, char *argv[])
         const int rc = run_edt(frame, height, width, sigma, minVal, maxVal, outdir);
         if (rc) return rc;
     }
+    if (want_lines && want_segments)
+        return run_segments(frame, height, width, sigma, minVal, maxVal, line_rho, line_theta_deg, line_threshold, lines_max,
+                            seg_min_length, seg_max_gap, seg_exclusive, outdir);
     if (want_lines)
         return run_hough(frame, height, width, sigma, minVal, maxVal, line_rho, line_theta_deg, line_threshold, lines_max,
                          outdir);

@@ -52,7 +52,8 @@
 extern "C" {
 #endif
 
-#define CANNY_HIP_VERSION 800        /* 0.8.0: + exact Euclidean distance transform of the finished map: dist2, dist, nearest */
+#define CANNY_HIP_VERSION 900        /* 0.9.0: + Hough line segments: runs of edge pixels along each detected line */
+/* 0.8.0: + exact Euclidean distance transform of the finished map: dist2, dist, nearest */
 /* 0.7.0: + 8-connected components of the finished map: labels, stats, minimum-area filter */
 /* 0.5.0: + edge point lists (CSR of pixel indices), compacted on the GPU */
 /* 0.4.1: + canny_hip_selftest_sobel_pixel */
@@ -488,8 +489,9 @@ int canny_hip_points_from_bits(const unsigned char *bits, int height, int width,
  *   40960: every frame up to 8K at rho >= 0.6); beyond that 0 takes the global form and 2 is CANNY_HIP_ERR_UNSUPPORTED.  Same
  *   bytes either way.  "tune_hough_lds_kb": LDS budget of a vote workgroup in KiB (0 = automatic, 48), for A/B.
  * The three parts are timed by canny_hip_hough_profile_get (0 vote, 1 peaks, 2 select + sort).
- * Not covered -- follow-ups: probabilistic / segment output (HoughLinesP), multi-scale srn / stn, weighted votes, circles,
- * the three-stream batch pipeline, the multi-GPU sharder, colour and automatic-threshold variants. */
+ * Segment output (cv::HoughLinesP's use) is the next section.
+ * Not covered -- follow-ups: multi-scale srn / stn, weighted votes, circles, the three-stream batch pipeline, the multi-GPU
+ * sharder, colour and automatic-threshold variants. */
 #define CANNY_HIP_HOUGH_MAX_LINES 4096 /* largest lines_max: the 64-bit sort keys of one frame fit in LDS */
 /* Host-only, no device needed. */
 int canny_hip_hough_geometry(int height, int width, float rho, float theta, float min_theta, float max_theta,
@@ -520,6 +522,89 @@ int canny_hip_dev_canny_hough(canny_hip_ctx *ctx, const unsigned char *d_img, fl
 int canny_hip_canny_hough(canny_hip_ctx *ctx, const unsigned char *imgs, int n_frames, float sigma, int min_val,
                           int max_val, int height, int width, float rho, float theta, int threshold, int lines_max,
                           float min_theta, float max_theta, float *lines, int *votes, unsigned int *bases, int *counts);
+
+/* ---- Hough line segments ------------------------------------------------------------------------------------------------
+ * Where on a detected line the edge is: the runs of edge pixels along each line of a list, per frame of a batch, on the GPU,
+ * in stream order behind the Hough call, with no host round trip -- what cv::HoughLinesP is used for.  HoughLinesP itself
+ * picks pixels with a random number generator and cannot be reproduced; this is a deterministic rule of the library's own,
+ * which a few lines of numpy restate byte for byte (tests/hough_segments_rule.py).  THE RULE:
+ * Inputs for one frame: its edge map E (height x width); rho, theta, min_theta, max_theta, hence numangle, numrho, tab_cos,
+ *   tab_sin exactly as above; an ordered list of lines bases[0 .. K), accumulator cells; min_length >= 0, max_gap >= 0,
+ *   exclusive in {0, 1}, segments_max >= 1.  All float arithmetic is binary32, round to nearest even, not contracted.
+ *   1. Line: for each k, n = bases[k] / (numrho + 2) - 1, r = bases[k] % (numrho + 2) - 1.  A base with n outside
+ *      [0, numangle) or r outside [0, numrho) is not a line: it yields no segment and causes no memory access.  Duplicate
+ *      bases are allowed; each is a line of its own.
+ *   2. Support: vote(x, y) = (int)rint_half_even(fl(fl((float)x * tab_cos[n]) + fl((float)y * tab_sin[n]))) + (numrho - 1) / 2
+ *      -- the vote above, to the bit.  S_k = the pixels (y, x) set in the working map W with vote(x, y) == r: exactly the
+ *      pixels that voted for the cell.  With exclusive = 0, W = E for every line, so |S_k| is the cell's vote count.
+ *   3. Axes: the major axis is x if |tab_sin[n]| >= |tab_cos[n]| (compared as floats), else y.  t = the major coordinate,
+ *      0 <= t < L (L = width or height), m = the minor one.  cnt[t] = the number of pixels of S_k at major position t,
+ *      on[t] = cnt[t] > 0, lo[t] = the smallest m among them.
+ *   4. Runs: take the on positions in ascending order; consecutive on positions t' < t'' belong to the same run iff
+ *      t'' - t' - 1 <= max_gap (HoughLinesP's maxLineGap: up to max_gap consecutive off positions are bridged).  A run
+ *      [ta, tb] is a segment iff tb - ta >= min_length (HoughLinesP's test on the larger coordinate difference);
+ *      min_length = 0 keeps single pixels.
+ *   5. Record: CANNY_HIP_SEGMENT_INTS = 6 ints x0, y0, x1, y1, k, support.  (x0, y0) is the pixel (ta, lo[ta]) mapped back
+ *      to (x, y), (x1, y1) is (tb, lo[tb]) likewise, support = the sum of cnt[t] over ta <= t <= tb.  Both end points are set
+ *      pixels of the map.
+ *   6. Exclusive mode (exclusive = 1: a pixel serves one segment only, as in HoughLinesP): W starts as E; lines are handled
+ *      in list order; after line k every pixel of S_k whose t lies inside a kept segment of line k is cleared from W, and
+ *      line k + 1 sees the cleared map.  W is a private working copy: neither the context's hysteresis plane nor a caller's
+ *      d_bits is ever written.
+ *   7. Order and capacity: records sorted by (k ascending, ta ascending), a total order.  Frame f's records go to slots
+ *      f * segments_max + j; only the first min(segments_max, total_f) are written; seg_counts[f] = total_f, always the TRUE
+ *      count; later slots are not touched.  The result is the same bytes on every run.
+ * In the device flavours the line list of frame f is d_bases[f * lines_max .. f * lines_max + min(lines_max,
+ *   d_line_counts[f])): the arrays a Hough call leaves on the device.  Nothing comes back to the host between the two calls.
+ * The kernels search the minor axis only near the line (a float estimate +- (0.7072 * rho + 2), widened by the float error
+ *   of the largest product); inside that window the exact vote decides, and the tests show the result equal to the
+ *   full-plane rule.  The rule itself knows no window.
+ * Statuses: min_length < 0, max_gap < 0, exclusive not 0 / 1, segments_max < 1, lines_max < 1, a NULL mandatory pointer ->
+ *   CANNY_HIP_ERR_INVALID; the Hough argument errors as above; n_frames * segments_max * 6 >= 2^31, lines_max >
+ *   CANNY_HIP_HOUGH_MAX_LINES, a frame whose lines could hold 2^31 segments (lines * ceil(L / 2)), and exclusive mode with
+ *   max(height, width) > 2^20 -> CANNY_HIP_ERR_UNSUPPORTED.  Nothing is written in either case.
+ * Memory: exclusive mode keeps a private copy of the map in a context workspace (1 bit per pixel, tile padding included).
+ * The parts are timed by canny_hip_hough_segments_profile_get (CANNY_HIP_SEGMENT_PART_*); with "profile_stage_mask" they
+ *   are bits 19 .. 21.
+ * Not covered -- follow-ups: randomised sampling as in HoughLinesP proper, decrementing the accumulator when pixels are
+ * claimed, sub-pixel end points, merging collinear segments of neighbouring cells, the three-stream batch pipeline, the
+ * multi-GPU sharder. */
+#define CANNY_HIP_SEGMENT_INTS 6
+enum canny_hip_segment_part {
+    CANNY_HIP_SEGMENT_PART_COUNT = 0,      /* exclusive = 0: every line walked, its segments counted; scan over the lines */
+    CANNY_HIP_SEGMENT_PART_EMIT = 1,       /* exclusive = 0: every line walked again, the records stored */
+    CANNY_HIP_SEGMENT_PART_EXCLUSIVE = 2,  /* exclusive = 1: the private copy, then one workgroup per frame, lines in order */
+    CANNY_HIP_SEGMENT_PARTS = 3
+};
+/* Host-only, needs no device: the rule on ONE host bit map (layout of canny_hip_dev_canny_bits), a plain C++ walk of the
+ * full plane.  bases may be NULL if n_lines == 0.  *count receives the true count. */
+int canny_hip_hough_segments_from_bits(const unsigned char *bits, int height, int width, float rho, float theta,
+                                       float min_theta, float max_theta, const unsigned int *bases, int n_lines,
+                                       int min_length, int max_gap, int exclusive, int *segments, int segments_max,
+                                       int *count);
+/* Device bit maps (layout of canny_hip_dev_canny_bits, any byte alignment, padding bits ignored) and the line lists a Hough
+ * call left on the device.  d_segments: n_frames * segments_max * 6 ints; d_seg_counts: n_frames ints.  Asynchronous. */
+int canny_hip_dev_hough_segments_bits(canny_hip_ctx *ctx, const unsigned char *d_bits, int n_frames, int height, int width,
+                                      float rho, float theta, float min_theta, float max_theta,
+                                      const unsigned int *d_bases, const int *d_line_counts, int lines_max, int min_length,
+                                      int max_gap, int exclusive, int *d_segments, int segments_max, int *d_seg_counts);
+/* canny_hip_dev_canny_hough unchanged, then the segments queued behind it on the same stream, read from the converged
+ * hysteresis bit-plane and from the bases that call wrote.  d_lines, d_votes, d_bases, d_line_counts, d_accum may be NULL
+ * (bases and line counts then live in a context workspace); d_segments and d_seg_counts are mandatory.  The result follows
+ * the MAP (max_val > 255: all counts 0).  Completion contract and statuses as canny_hip_dev_canny_hough. */
+int canny_hip_dev_canny_hough_segments(canny_hip_ctx *ctx, const unsigned char *d_img, float sigma, int min_val,
+                                       int max_val, int height, int width, int n_frames, short *d_edges, float rho,
+                                       float theta, int threshold, int lines_max, float min_theta, float max_theta,
+                                       float *d_lines, int *d_votes, unsigned int *d_bases, int *d_line_counts,
+                                       int *d_accum, int min_length, int max_gap, int exclusive, int *d_segments,
+                                       int segments_max, int *d_seg_counts);
+/* Host buffers, synchronous: upload, canny, lines, segments; the counts come down first, then only the filled slots.
+ * lines, votes, bases, line_counts may be NULL. */
+int canny_hip_canny_hough_segments(canny_hip_ctx *ctx, const unsigned char *imgs, int n_frames, float sigma, int min_val,
+                                   int max_val, int height, int width, float rho, float theta, int threshold,
+                                   int lines_max, float min_theta, float max_theta, int min_length, int max_gap,
+                                   int exclusive, float *lines, int *votes, unsigned int *bases, int *line_counts,
+                                   int *segments, int segments_max, int *seg_counts);
 
 /* ---- connected components ------------------------------------------------------------------------------------------------
  * Eight-connected component labelling of the finished edge map, per frame of a batch, on the GPU, queued behind the detector
@@ -657,6 +742,8 @@ int canny_hip_hough_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, 
 int canny_hip_components_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches);
 /* ... and for the two parts of the distance transform (CANNY_HIP_EDT_PART_*). */
 int canny_hip_edt_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches);
+/* ... and for the three parts of the Hough segments (CANNY_HIP_SEGMENT_PART_*). */
+int canny_hip_hough_segments_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches);
 
 /* ---- self-test hooks used by the GPU test-suite -------------------------------------------- */
 /* Runs the DEVICE magnitude / angle-bin functions over every (gx,gy) in [-lim,lim]^2 and writes
