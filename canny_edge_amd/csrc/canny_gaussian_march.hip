@@ -34,6 +34,7 @@
 // in SGPRs.
 #include "canny_kernels.h"
 
+#include <atomic>
 #include <cstring>
 #include <type_traits>
 
@@ -349,14 +350,28 @@ struct ColorRow {
     uint32_t w[CH];
 };
 
-template <int C, bool COL_EDGE, bool ROW_EDGE, bool FMA_DIV, bool USE_LUT, bool OUT_U8 = false, bool SYS = false,
-          int CH = 1>
+//
+// Quotients.  a / S for the full-window weight S is the single instruction fma(a, fma_c, a) where the host found (S, c)
+// in kFmaDivTable (see FMA_DIV above gauss_march_strip); every other divisor takes the five instructions of div_by.
+// Which divisors a wave meets is decided per PASS: the row pass divides by S in every lane unless the strip touches a
+// frame's left or right border (COL_EDGE: per-lane weights), the column pass divides by S on every row except the
+// first and last C rows of a frame, which only ROW_EDGE waves see.  ROW_DIV and COL_DIV say what each pass does:
+// DIV_LONG always div_by, DIV_FMA always the fma, DIV_ROWS (column pass of ROW_EDGE waves) the fma on every row that
+// has the full weight and div_by on the others -- a wave-uniform test per row; `use_fma` (wave-uniform too) switches
+// that form back to div_by on all rows.  The kernels instantiate five of the combinations, see gauss_sym_kernel.
+enum { DIV_LONG = 0, DIV_FMA = 1, DIV_ROWS = 2 };
+
+template <int C, bool COL_EDGE, bool ROW_EDGE, int ROW_DIV, int COL_DIV, bool USE_LUT, bool OUT_U8 = false,
+          bool SYS = false, int CH = 1>
 __device__ __forceinline__ void gauss_sym_strip(const GaussJob &jb, const GaussTaps &t, const float *lut, float *wts,
-                                                float fma_c = 0.0f, const GrayRule &rule = GrayRule{})
+                                                bool use_fma = false, float fma_c = 0.0f,
+                                                const GrayRule &rule = GrayRule{})
 {
     static_assert(CH == 1 || (SYS && USE_LUT && OUT_U8), "colour input: the default (systolic, table, u8) kernel only");
     using Raw = std::conditional_t<CH == 1, uint32_t, ColorRow<CH>>; // a row's loaded bytes, before conversion
-    static_assert(!FMA_DIV || (!COL_EDGE && !ROW_EDGE), "FMA_DIV needs a single wave-uniform divisor");
+    static_assert(ROW_DIV == DIV_LONG || (ROW_DIV == DIV_FMA && !COL_EDGE),
+                  "border strips divide by per-lane weights in the row pass");
+    static_assert(COL_DIV != DIV_FMA || !ROW_EDGE, "the first and last C rows of a frame renormalise");
     constexpr int HL = MarchCfg<C>::HL, RING = 2 * C + 1;
     static_assert(HL <= 2, "products travel at most two lanes");
     const int H = jb.H, W = jb.W, x0 = jb.x0, ybeg = jb.ybeg, yend = jb.yend, lane = jb.lane;
@@ -383,9 +398,17 @@ __device__ __forceinline__ void gauss_sym_strip(const GaussJob &jb, const GaussT
     for (int k = 1; k < RING; k++) cnt_full = __fadd_rn(cnt_full, t.tap[k]);
     const float inv_full = __fdiv_rn(1.0f, cnt_full);
     // At the column borders every lane has four weights of its own.  They (and their reciprocals) live in the lane's
-    // LDS slot `wts`, not in eight registers: the border strips are the register-hungriest instantiation and the one
-    // that spilled (private segment -> every wave of the launch pays for scratch).
+    // LDS slot (eight floats of `wts`, the workgroup's array), not in eight registers: the border strips are the
+    // register-hungriest instantiation and the one that spilled (private segment -> every wave of the launch pays for
+    // scratch).  The slot's byte offset is the one register kept for it; it goes through an empty asm at every use (as
+    // ld_off below does), so that the reads stay in the loop.
+    uint32_t wts_off = 32u * threadIdx.x;
+    auto wts_slot = [&]() {
+        asm volatile("" : "+v"(wts_off));
+        return reinterpret_cast<float *>(reinterpret_cast<char *>(wts) + wts_off);
+    };
     if (COL_EDGE) {
+        float *slot = wts_slot();
 #pragma unroll
         for (int j = 0; j < 4; j++) {
             const int x = x0 + j;
@@ -396,19 +419,17 @@ __device__ __forceinline__ void gauss_sym_strip(const GaussJob &jb, const GaussT
                 if (xx >= 0 && xx < W) c = __fadd_rn(c, t.tap[k]);
             }
             const float cnt = (x >= 0 && x < W) ? c : 1.0f;
-            wts[j] = cnt;
-            wts[4 + j] = __fdiv_rn(1.0f, cnt);
+            slot[j] = cnt;
+            slot[4 + j] = __fdiv_rn(1.0f, cnt);
         }
     }
-    uint32_t wts_off = 0; // opaque zero added to the slot's address at every use, so that the reads stay in the loop
     auto row_quot = [&](float (&v)[4]) { // v[i] / (weight of output column i), in place
-        if (FMA_DIV) {
+        if (ROW_DIV == DIV_FMA) {
 #pragma unroll
             for (int i = 0; i < 4; i++) v[i] = __fmaf_rn(v[i], fma_c, v[i]);
         } else if (COL_EDGE) {
             typedef float f32x4 __attribute__((ext_vector_type(4)));
-            asm volatile("" : "+v"(wts_off));
-            const float *w = reinterpret_cast<const float *>(reinterpret_cast<const char *>(wts) + wts_off);
+            const float *w = wts_slot();
             const f32x4 cw = *reinterpret_cast<const f32x4 *>(w), iw = *reinterpret_cast<const f32x4 *>(w + 4);
 #pragma unroll
             for (int i = 0; i < 4; i++) v[i] = div_by(v[i], cw[i], iw[i]);
@@ -655,7 +676,8 @@ __device__ __forceinline__ void gauss_sym_strip(const GaussJob &jb, const GaussT
         constexpr int DONE = (PH + 1) % RING;
         const bool in_seg = y >= ybeg && y < yend; // wave-uniform
         float cnt_v = cnt_full, inv_v = inv_full;
-        if (ROW_EDGE && in_seg && (y < C || y + C >= H)) { // top/bottom border rows renormalise
+        const bool border_row = ROW_EDGE && in_seg && (y < C || y + C >= H); // wave-uniform
+        if (border_row) { // top/bottom border rows renormalise
             cnt_v = 0.0f;
             for (int k = 0; k < RING; k++) {
                 int yy = y + k - C;
@@ -664,11 +686,18 @@ __device__ __forceinline__ void gauss_sym_strip(const GaussJob &jb, const GaussT
             inv_v = __fdiv_rn(1.0f, cnt_v);
         }
         // float -> short truncates toward zero (src/utils.cpp:62)
-        auto quot = [&](float a) { return FMA_DIV ? __fmaf_rn(a, fma_c, a) : div_by(a, cnt_v, inv_v); };
+        float q[4];
+        if (COL_DIV == DIV_FMA || (COL_DIV == DIV_ROWS && use_fma && !border_row)) { // wave-uniform
+#pragma unroll
+            for (int i = 0; i < 4; i++) q[i] = __fmaf_rn(acc[DONE][i], fma_c, acc[DONE][i]);
+        } else {
+#pragma unroll
+            for (int i = 0; i < 4; i++) q[i] = div_by(acc[DONE][i], cnt_v, inv_v);
+        }
         uint2 pk;
         {
-            const int o0 = (int)quot(acc[DONE][0]), o1 = (int)quot(acc[DONE][1]);
-            const int o2 = (int)quot(acc[DONE][2]), o3 = (int)quot(acc[DONE][3]);
+            const int o0 = (int)q[0], o1 = (int)q[1];
+            const int o2 = (int)q[2], o3 = (int)q[3];
             if (OUT_U8) {
                 // quotients of non-negative sums <= 255 * (1 + ulps): 0 <= o <= 255
                 pk.x = ((uint32_t)o0 | ((uint32_t)o1 << 8)) | (((uint32_t)o2 | ((uint32_t)o3 << 8)) << 16);
@@ -785,9 +814,9 @@ void gauss_sym_kernel(const uint8_t *__restrict__ img, void *__restrict__ out, i
         __syncthreads();
     }
     const float *lut = lut_mem;
-    // per-lane column-border weights (border strips only, see gauss_sym_strip)
+    // per-lane column-border weights, eight floats each (border strips only, see gauss_sym_strip)
     __shared__ __attribute__((aligned(16))) float wts_mem[256 * 8];
-    float *wts = wts_mem + threadIdx.x * 8;
+    float *wts = wts_mem;
     const int lane = threadIdx.x & 63;
     const int wave = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); // wave-uniform
     if (wave >= total_waves) return;
@@ -812,18 +841,25 @@ void gauss_sym_kernel(const uint8_t *__restrict__ img, void *__restrict__ out, i
                               : (s * SW - 4 * LEFT < 0) || (s * SW + SW + 4 * LEFT > W);
     // rows loaded: ybeg-C .. yend-1+C, up to 2C more for the rounding to whole loop trips, +2 prefetched
     const bool row_edge = (jb.ybeg - C < 0) || (jb.yend + C + K::RING + 1 >= H); // (+3 with rotated look-ups)
-    if (col_edge) {
-        if (row_edge)
-            gauss_sym_strip<C, true, true, false, USE_LUT, OUT_U8, SYS>(jb, t, lut, wts);
+    // Five strip bodies.  With the one-instruction quotient (use_fma_div) every pass of every wave that divides by the
+    // full-window weight uses it: both passes of an interior wave, the column pass of a border strip, the row pass and
+    // the full-weight rows of a wave at a frame's top or bottom.  Without it the interior waves keep their own
+    // straight-line body and every border wave runs the general one (border columns and rows), with div_by throughout:
+    // results are the same, the stage is 2 % slower than with a body of their own for waves at one border only (DESIGN
+    // section 9); that is what a sigma whose weight misses kFmaDivTable pays for the five-body limit.
+    const bool fma = use_fma_div != 0; // kernel argument: wave-uniform
+    if (col_edge || row_edge) {
+        if (!fma || (col_edge && row_edge))
+            gauss_sym_strip<C, true, true, DIV_LONG, DIV_ROWS, USE_LUT, OUT_U8, SYS>(jb, t, lut, wts, fma, fma_c);
+        else if (col_edge)
+            gauss_sym_strip<C, true, false, DIV_LONG, DIV_FMA, USE_LUT, OUT_U8, SYS>(jb, t, lut, wts, true, fma_c);
         else
-            gauss_sym_strip<C, true, false, false, USE_LUT, OUT_U8, SYS>(jb, t, lut, wts);
+            gauss_sym_strip<C, false, true, DIV_FMA, DIV_ROWS, USE_LUT, OUT_U8, SYS>(jb, t, lut, wts, true, fma_c);
     } else {
-        if (row_edge)
-            gauss_sym_strip<C, false, true, false, USE_LUT, OUT_U8, SYS>(jb, t, lut, wts);
-        else if (use_fma_div)
-            gauss_sym_strip<C, false, false, true, USE_LUT, OUT_U8, SYS>(jb, t, lut, wts, fma_c);
+        if (fma)
+            gauss_sym_strip<C, false, false, DIV_FMA, DIV_FMA, USE_LUT, OUT_U8, SYS>(jb, t, lut, wts, true, fma_c);
         else
-            gauss_sym_strip<C, false, false, false, USE_LUT, OUT_U8, SYS>(jb, t, lut, wts);
+            gauss_sym_strip<C, false, false, DIV_LONG, DIV_LONG, USE_LUT, OUT_U8, SYS>(jb, t, lut, wts);
     }
 }
 
@@ -845,9 +881,9 @@ void gauss_sym_color_kernel(const uint8_t *__restrict__ src, uint8_t *__restrict
     for (int a = 0; a <= C; a++) lut_mem[a * 256 + threadIdx.x] = __fmul_rn((float)threadIdx.x, t.tap[C - a]);
     __syncthreads();
     const float *lut = lut_mem;
-    // per-lane column-border weights (border strips only, see gauss_sym_strip)
+    // per-lane column-border weights, eight floats each (border strips only, see gauss_sym_strip)
     __shared__ __attribute__((aligned(16))) float wts_mem[256 * 8];
-    float *wts = wts_mem + threadIdx.x * 8;
+    float *wts = wts_mem;
     const int lane = threadIdx.x & 63;
     const int wave = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); // wave-uniform
     if (wave >= total_waves) return;
@@ -871,18 +907,20 @@ void gauss_sym_color_kernel(const uint8_t *__restrict__ src, uint8_t *__restrict
     const bool col_edge = (s * SW - 4 * LEFT + C < 0) || (s * SW + SW + C > W);
     // rows loaded: ybeg-C .. yend-1+C, up to 2C more for the rounding to whole loop trips, +2 prefetched
     const bool row_edge = (jb.ybeg - C < 0) || (jb.yend + C + K::RING + 1 >= H); // (+3 with rotated look-ups)
-    if (col_edge) {
-        if (row_edge)
-            gauss_sym_strip<C, true, true, false, true, true, true, CH>(jb, t, lut, wts, 0.0f, rule);
+    // the five strip bodies of gauss_sym_kernel
+    const bool fma = use_fma_div != 0; // kernel argument: wave-uniform
+    if (col_edge || row_edge) {
+        if (!fma || (col_edge && row_edge))
+            gauss_sym_strip<C, true, true, DIV_LONG, DIV_ROWS, true, true, true, CH>(jb, t, lut, wts, fma, fma_c, rule);
+        else if (col_edge)
+            gauss_sym_strip<C, true, false, DIV_LONG, DIV_FMA, true, true, true, CH>(jb, t, lut, wts, true, fma_c, rule);
         else
-            gauss_sym_strip<C, true, false, false, true, true, true, CH>(jb, t, lut, wts, 0.0f, rule);
+            gauss_sym_strip<C, false, true, DIV_FMA, DIV_ROWS, true, true, true, CH>(jb, t, lut, wts, true, fma_c, rule);
     } else {
-        if (row_edge)
-            gauss_sym_strip<C, false, true, false, true, true, true, CH>(jb, t, lut, wts, 0.0f, rule);
-        else if (use_fma_div)
-            gauss_sym_strip<C, false, false, true, true, true, true, CH>(jb, t, lut, wts, fma_c, rule);
+        if (fma)
+            gauss_sym_strip<C, false, false, DIV_FMA, DIV_FMA, true, true, true, CH>(jb, t, lut, wts, true, fma_c, rule);
         else
-            gauss_sym_strip<C, false, false, false, true, true, true, CH>(jb, t, lut, wts, 0.0f, rule);
+            gauss_sym_strip<C, false, false, DIV_LONG, DIV_LONG, true, true, true, CH>(jb, t, lut, wts, false, 0.0f, rule);
     }
 }
 
@@ -1044,15 +1082,20 @@ static hipError_t launch_march_c(const uint8_t *img, void *out, int height, int 
     // 133-row default of the rule above needs 7 rounds (17 segments per frame, the last one 32 rows): 1.069 -> 1.032 ms
     // (profiles/r03/ab4_segments_whole_rounds.txt; 166 rows: 1.120, 100 rows: 1.050, as the model ranks them).
     if (symmetric && g_gauss_seg_target < 8) {
-        static int n_simds = 0; // SIMDs of the device (4 per CU); one device family, so one value per process
+        // SIMDs of the device (4 per CU); one device family, so one value per process.  Launches come from several host
+        // threads: whichever of them asks first, all store the same value.
+        static std::atomic<int> n_simds_cache{0};
+        int n_simds = n_simds_cache.load(std::memory_order_relaxed);
         if (n_simds == 0) {
             int dev = 0, cus = 0;
             if (hipGetDevice(&dev) != hipSuccess ||
                 hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
                 cus = 256;
             n_simds = 4 * cus;
+            n_simds_cache.store(n_simds, std::memory_order_relaxed);
         }
-        // waves per SIMD the kernel's registers allow (gauss_sym_kernel<C, true>: 38/49/68/76/95/105/125/128 VGPRs)
+        // waves per SIMD the kernel's registers allow (gauss_sym_kernel<C, true, true, true>: 36/49/64/79/94 VGPRs for
+        // C = 1..5)
         static const int kWavesPerSimd[9] = {0, 8, 8, 7, 6, 5, 4, 4, 3};
         const long long slots = (long long)n_simds * kWavesPerSimd[C];
         const long long frames_strips = (long long)n_frames * n_strips;
