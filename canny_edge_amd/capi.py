@@ -100,6 +100,7 @@ EXPORTS = (
     "canny_hip_edt_profile_get",
     "canny_hip_hough_segments_from_bits", "canny_hip_dev_hough_segments_bits", "canny_hip_dev_canny_hough_segments",
     "canny_hip_canny_hough_segments", "canny_hip_hough_segments_profile_get",
+    "canny_hip_selftest_histogram", "canny_hip_selftest_select",
 )
 
 _lib: Optional[C.CDLL] = None
@@ -233,6 +234,8 @@ def load() -> C.CDLL:
                                                 p], i),
         "canny_hip_canny_hough_segments": ([p, p, i, f, i, i, i, i, f, f, i, i, f, f, i, i, i, p, p, p, p, p, i, p], i),
         "canny_hip_hough_segments_profile_get": ([p, i, C.POINTER(C.c_double), C.POINTER(C.c_long)], i),
+        "canny_hip_selftest_histogram": ([p, p, i, i, i, i, i, p], i),
+        "canny_hip_selftest_select": ([p, p, i, i, f, f, p], i),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -1031,6 +1034,18 @@ class Context:
         self._check(self._L.canny_hip_selftest_div_fma(self._h, divisor, c, C.byref(bad), C.byref(worst)),
                     "selftest_div_fma")
         return bad.value, worst.value
+
+    def selftest_histogram(self, d_plane: int, plane_is_u8: bool, kind, h: int, w: int, n: int, d_hist: int):
+        """The automatic rules' histogram pass alone on a device plane (bytes or shorts in [0,255], n frames of h x w):
+        kind "median" counts the values, "quantile" min(Sobel magnitude, 256), into d_hist (n x 257 uint32, device; zeroed
+        first).  Asynchronous."""
+        self._check(self._L.canny_hip_selftest_histogram(self._h, C.c_void_p(d_plane), int(plane_is_u8), _rule(kind), h,
+                                                         w, n, C.c_void_p(d_hist)), "selftest_histogram")
+
+    def selftest_select(self, d_hist: int, n: int, rule, low: float, high: float, d_pairs: int):
+        """The select pass alone: the rule on n device histograms (n x 257 uint32) -> d_pairs (2 * n int32, device)."""
+        self._check(self._L.canny_hip_selftest_select(self._h, C.c_void_p(d_hist), n, _rule(rule), low, high,
+                                                      C.c_void_p(d_pairs)), "selftest_select")
 
     # ---- device-pointer stage API (ints are device addresses; n_frames contiguous planes) -------
     def dev_gaussian(self, d_img: int, sigma: float, h: int, w: int, n: int, d_out: int):

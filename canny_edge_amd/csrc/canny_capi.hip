@@ -3673,4 +3673,30 @@ int canny_hip_selftest_div_fma(canny_hip_ctx *ctx, float divisor, float c, unsig
     return selftest_div_common(ctx, divisor, 1, c, mismatches, largest_mismatching_dividend);
 }
 
+// The histogram and select passes of the automatic rules on their own, launched as dev_canny launches them.
+int canny_hip_selftest_histogram(canny_hip_ctx *ctx, const void *d_plane, int plane_is_u8, int kind, int height, int width,
+                                 int n_frames, unsigned int *d_hist)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!d_plane || !d_hist || (kind != kAutoMedian && kind != kAutoQuantile)) return CANNY_HIP_ERR_INVALID;
+    if ((rc = check_dims(height, width, n_frames))) return rc;
+    HIP_TRY(ctx, hipMemsetAsync(d_hist, 0, (size_t)n_frames * kHistBins * sizeof(uint32_t), ctx->stream));
+    HIP_TRY(ctx, kind == kAutoMedian
+                     ? launch_hist_intensity(d_plane, plane_is_u8 != 0, d_hist, height, width, n_frames, ctx->stream)
+                     : launch_hist_gradient(d_plane, plane_is_u8 != 0, d_hist, height, width, n_frames, ctx->stream));
+    return CANNY_HIP_OK;
+}
+
+int canny_hip_selftest_select(canny_hip_ctx *ctx, const unsigned int *d_hist, int n_frames, int rule, float low, float high,
+                              int *d_pairs)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!d_hist || !d_pairs || !auto_params_valid(rule, low, high)) return CANNY_HIP_ERR_INVALID;
+    if ((rc = check_dims(1, 1, n_frames))) return rc;
+    HIP_TRY(ctx, launch_thr_select(d_hist, n_frames, rule, low, high, d_pairs, ctx->stream));
+    return CANNY_HIP_OK;
+}
+
 } // extern "C"

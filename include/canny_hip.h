@@ -52,7 +52,8 @@
 extern "C" {
 #endif
 
-#define CANNY_HIP_VERSION 900        /* 0.9.0: + Hough line segments: runs of edge pixels along each detected line */
+#define CANNY_HIP_VERSION 901        /* 0.9.1: + canny_hip_selftest_histogram, canny_hip_selftest_select */
+/* 0.9.0: + Hough line segments: runs of edge pixels along each detected line */
 /* 0.8.0: + exact Euclidean distance transform of the finished map: dist2, dist, nearest */
 /* 0.7.0: + 8-connected components of the finished map: labels, stats, minimum-area filter */
 /* 0.5.0: + edge point lists (CSR of pixel indices), compacted on the GPU */
@@ -789,6 +790,17 @@ int canny_hip_selftest_march_order(int n_segs, int n_strips, int *out_pairs);
 /* Host-only: number of CPUs in a sysfs-style list ("0-3,8,10-11" -> 7; 0 if malformed) -- the parser behind the
  * sharder's NUMA binding. */
 int canny_hip_selftest_cpulist_count(const char *text);
+/* The histogram pass of the automatic rules alone, launched exactly as canny_hip_dev_canny_auto launches it, on a
+ * caller-supplied device plane of n_frames contiguous height x width frames: bytes (plane_is_u8 != 0) or shorts, values in
+ * [0,255].  kind CANNY_HIP_AUTO_MEDIAN counts the values, CANNY_HIP_AUTO_QUANTILE counts min(magnitude, 256) of the
+ * plane's Sobel magnitudes.  d_hist (device, n_frames x 257 unsigned int) is zeroed first; everything runs on the
+ * context's stream and nothing is read back. */
+int canny_hip_selftest_histogram(canny_hip_ctx *ctx, const void *d_plane, int plane_is_u8, int kind, int height, int width,
+                                 int n_frames, unsigned int *d_hist);
+/* The select pass alone: the rule (parameters as canny_hip_dev_canny_auto) on each of n_frames device histograms of 257
+ * unsigned int; d_pairs (device, 2 * n_frames ints) receives the clamped pairs.  Asynchronous like the above. */
+int canny_hip_selftest_select(canny_hip_ctx *ctx, const unsigned int *d_hist, int n_frames, int rule, float low, float high,
+                              int *d_pairs);
 
 #ifdef __cplusplus
 }

@@ -255,6 +255,22 @@ def test_paths_overlap_hysteresis(octx, dev, smoothed_u8, rule, low, high):
     assert np.array_equal(dev.down(d_out, frames.shape, np.int16), _oracle_thr_maps(frames, 1.4, pairs))
 
 
+@pytest.mark.parametrize("smoothed_u8", [1, 0])
+@pytest.mark.parametrize("shape", [(37, 53), (33, 31)])
+@pytest.mark.parametrize("rule,low,high", RULES)
+def test_paths_odd_pixel_counts(octx, dev, shape, smoothed_u8, rule, low, high):
+    """Frames whose pixel count is no multiple of 16 start inside the intensity histogram's 16-pixel groups and end the
+    batch with a partial one: the masked paths, on the plane the real Gaussian wrote (bytes and shorts).
+    tests/test_gpu_histograms.py pins the same paths bin by bin on designed planes."""
+    frames = mixed_batch(*shape, seed=12)
+    assert frames[0].size % 16 not in (0, 8)
+    octx.set_option("smoothed_u8", smoothed_u8)
+    edges, thr = dev_auto(octx, dev, frames, 1.4, rule, low, high)
+    check_auto(frames, 1.4, rule, low, high, edges, thr)
+    edges, thr = octx.canny_auto(frames, 1.4, rule, low, high)
+    check_auto(frames, 1.4, rule, low, high, edges, thr)
+
+
 # ---- batch pipeline ------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("compact", [0, 1])
 @pytest.mark.parametrize("pinned", [False, True])
