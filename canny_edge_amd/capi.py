@@ -96,6 +96,8 @@ EXPORTS = (
     "canny_hip_dev_hough_bits", "canny_hip_dev_canny_hough", "canny_hip_canny_hough", "canny_hip_hough_profile_get",
     "canny_hip_dev_canny_components", "canny_hip_dev_components_bits", "canny_hip_canny_components",
     "canny_hip_components_from_bits", "canny_hip_components_profile_get",
+    "canny_hip_dev_canny_contours", "canny_hip_dev_contours_bits", "canny_hip_canny_contours",
+    "canny_hip_contours_from_bits", "canny_hip_contours_profile_get",
     "canny_hip_dev_canny_edt", "canny_hip_dev_edt_bits", "canny_hip_canny_edt", "canny_hip_edt_from_bits",
     "canny_hip_edt_profile_get",
     "canny_hip_hough_segments_from_bits", "canny_hip_dev_hough_segments_bits", "canny_hip_dev_canny_hough_segments",
@@ -223,6 +225,12 @@ def load() -> C.CDLL:
         "canny_hip_canny_components": ([p, p, i, f, i, i, i, i, i, p, p, p, C.c_ulonglong, p], i),
         "canny_hip_components_from_bits": ([p, i, i, i, p, p, C.c_ulonglong, C.POINTER(C.c_ulonglong)], i),
         "canny_hip_components_profile_get": ([p, i, C.POINTER(C.c_double), C.POINTER(C.c_long)], i),
+        "canny_hip_dev_canny_contours": ([p, p, f, i, i, i, i, i, p, i, p, C.c_ulonglong, p, p, p, C.c_ulonglong, p], i),
+        "canny_hip_dev_contours_bits": ([p, p, i, i, i, i, p, C.c_ulonglong, p, p, p, C.c_ulonglong, p], i),
+        "canny_hip_canny_contours": ([p, p, i, f, i, i, i, i, i, p, C.c_ulonglong, p, p, p, C.c_ulonglong, p], i),
+        "canny_hip_contours_from_bits": ([p, i, i, i, p, C.c_ulonglong, C.POINTER(C.c_ulonglong), p, p, C.c_ulonglong,
+                                          C.POINTER(C.c_ulonglong)], i),
+        "canny_hip_contours_profile_get": ([p, i, C.POINTER(C.c_double), C.POINTER(C.c_long)], i),
         "canny_hip_dev_canny_edt": ([p, p, f, i, i, i, i, i, p, p, p, p], i),
         "canny_hip_dev_edt_bits": ([p, p, i, i, i, p, p, p], i),
         "canny_hip_canny_edt": ([p, p, i, f, i, i, i, i, p, p, p], i),
@@ -318,6 +326,40 @@ def components_from_bits(bits, height: int, width: int, min_area: int = 1, want_
     if st:
         raise CannyHipError(st, "components_from_bits")
     return labels, stats[:min(cap, n.value)], n.value
+
+
+CONTOUR_PARTS = ("label", "count", "write", "stats")
+
+
+def contours_from_bits(bits, height: int, width: int, min_area: int = 1, want_stats: bool = True,
+                       capacity: Optional[int] = None, point_capacity: Optional[int] = None):
+    """Host-only: the outer contour chain of every 8-connected component of one packed bit map (numpy.packbits(mask,
+    axis=-1); padding bits ignored) with at least min_area pixels, in the components' order.  Returns (stats int32 [k, 6]
+    or None, chain_offsets uint64 [k + 1], points int32, K, P): record j's chain is points[chain_offsets[j] :
+    chain_offsets[j + 1]], pixel indices r * width + c.  With capacity / point_capacity None everything is returned
+    (k = K, len(points) = P); otherwise k = min(K, capacity), points holds the positions below point_capacity that belong
+    to those records, and K, P are still the true counts."""
+    b = np.ascontiguousarray(bits, dtype=np.uint8)
+    if b.size != height * ((width + 7) // 8):
+        raise ValueError(f"expected {height} rows of {(width + 7) // 8} bytes, got {b.size} bytes")
+    L = load()
+    k, n = C.c_ulonglong(0), C.c_ulonglong(0)
+    if capacity is None or point_capacity is None:
+        st = L.canny_hip_contours_from_bits(_hp(b), height, width, min_area, None, 0, C.byref(k), None, None, 0,
+                                            C.byref(n))
+        if st:
+            raise CannyHipError(st, "contours_from_bits")
+    cap = k.value if capacity is None else int(capacity)
+    pcap = n.value if point_capacity is None else int(point_capacity)
+    stats = np.empty((cap, CC_STATS), np.int32) if want_stats else None
+    chain = np.zeros(cap + 1, np.uint64)
+    points = np.empty(pcap, np.int32)
+    st = L.canny_hip_contours_from_bits(_hp(b), height, width, min_area, _hp(stats) if want_stats and cap else None, cap,
+                                        C.byref(k), _hp(chain), _hp(points) if pcap else None, pcap, C.byref(n))
+    if st:
+        raise CannyHipError(st, "contours_from_bits")
+    fit = min(cap, k.value)
+    return (stats[:fit] if want_stats else None, chain[:fit + 1], points[:min(pcap, int(chain[fit]))], k.value, n.value)
 
 
 EDT_NONE = 0x7FFFFFFF                                           # CANNY_HIP_EDT_NONE: dist2 of a frame without edge pixels
@@ -797,6 +839,71 @@ class Context:
         ms, n = C.c_double(0.0), C.c_long(0)
         self._check(self._L.canny_hip_components_profile_get(self._h, part, C.byref(ms), C.byref(n)),
                     "components_profile_get")
+        return ms.value, n.value
+
+    # ---- outer contour chains of the finished map ----------------------------------------
+    def canny_contours(self, imgs, sigma: float, min_val: int, max_val: int, min_area: int = 1, want_stats: bool = True,
+                       capacity: Optional[int] = None, point_capacity: Optional[int] = None):
+        """canny(), then the outer contour chain of every component of each map with at least min_area pixels: imgs
+        (H, W) or (N, H, W) uint8 -> (stats int32 [k, 6] or None, offsets uint64 [N + 1], chain_offsets uint64 [k + 1],
+        points int32, point_offsets uint64 [N + 1]).  Record j (offsets[f] <= j < offsets[f + 1] for frame f) has the chain
+        points[chain_offsets[j] : chain_offsets[j + 1]], pixel indices r * W + c in the order of the walk.  With both
+        capacities None a counts-only call sizes the buffers and everything is returned; otherwise k = min(offsets[-1],
+        capacity), points holds the positions below point_capacity of those records, and offsets / point_offsets still hold
+        the true counts."""
+        a = np.ascontiguousarray(imgs, dtype=np.uint8)
+        if a.ndim == 2:
+            a = a[None]
+        if a.ndim != 3:
+            raise ValueError("expected uint8 [H, W] or [n_frames, H, W]")
+        n, h, w = a.shape
+        offsets, point_offsets = np.zeros(n + 1, np.uint64), np.zeros(n + 1, np.uint64)
+
+        def call(stats, cap, chain, points, pcap):
+            self._check(self._L.canny_hip_canny_contours(
+                self._h, _hp(a), n, sigma, min_val, max_val, h, w, min_area, _hp(stats) if stats is not None and cap else None,
+                cap, _hp(offsets), _hp(chain) if chain is not None else None, _hp(points) if pcap else None, pcap,
+                _hp(point_offsets)), "canny_contours")
+
+        if capacity is None or point_capacity is None:
+            call(None, 0, None, None, 0)
+        cap = int(offsets[-1]) if capacity is None else int(capacity)
+        pcap = int(point_offsets[-1]) if point_capacity is None else int(point_capacity)
+        stats = np.empty((cap, CC_STATS), np.int32) if want_stats else None
+        chain = np.zeros(cap + 1, np.uint64)
+        points = np.empty(pcap, np.int32)
+        call(stats, cap, chain, points, pcap)
+        fit = min(cap, int(offsets[-1]))
+        return (stats[:fit] if want_stats else None, offsets, chain[:fit + 1], points[:min(pcap, int(chain[fit]))],
+                point_offsets)
+
+    def dev_canny_contours(self, d_img: int, sigma: float, min_val: int, max_val: int, h: int, w: int, n: int,
+                           min_area: int, d_stats: int, capacity: int, d_offsets: int, d_chain_offsets: int, d_points: int,
+                           point_capacity: int, d_point_offsets: int, d_edges: int = 0):
+        """dev_canny, then the chains of its map on the same stream: d_stats (capacity records of 6 int32) or 0,
+        d_offsets and d_point_offsets (n + 1 uint64 each), d_chain_offsets (capacity + 1 uint64) or 0 with capacity 0,
+        d_points (point_capacity int32) or 0 with point_capacity 0, d_edges (the s16 map) or 0 -- device pointers."""
+        v = C.c_void_p
+        self._check(self._L.canny_hip_dev_canny_contours(self._h, v(d_img or None), sigma, min_val, max_val, h, w, n,
+                                                         v(d_edges or None), min_area, v(d_stats or None), capacity,
+                                                         v(d_offsets or None), v(d_chain_offsets or None),
+                                                         v(d_points or None), point_capacity, v(d_point_offsets or None)),
+                    "dev_canny_contours")
+
+    def dev_contours_bits(self, d_bits: int, h: int, w: int, n: int, min_area: int, d_stats: int, capacity: int,
+                          d_offsets: int, d_chain_offsets: int, d_points: int, point_capacity: int, d_point_offsets: int):
+        """The chains alone on device bit maps (layout of dev_canny_bits, any byte alignment, padding ignored)."""
+        v = C.c_void_p
+        self._check(self._L.canny_hip_dev_contours_bits(self._h, v(d_bits or None), h, w, n, min_area, v(d_stats or None),
+                                                        capacity, v(d_offsets or None), v(d_chain_offsets or None),
+                                                        v(d_points or None), point_capacity, v(d_point_offsets or None)),
+                    "dev_contours_bits")
+
+    def contours_profile_get(self, part: int) -> Tuple[float, int]:
+        """(total ms, launch groups) of part 0 label, 1 count, 2 write, 3 stats (CONTOUR_PARTS)."""
+        ms, n = C.c_double(0.0), C.c_long(0)
+        self._check(self._L.canny_hip_contours_profile_get(self._h, part, C.byref(ms), C.byref(n)),
+                    "contours_profile_get")
         return ms.value, n.value
 
     # ---- Euclidean distance transform of the finished map (DESIGN.md section 15) ---------------------------------

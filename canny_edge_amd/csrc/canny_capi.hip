@@ -386,6 +386,8 @@ struct canny_hip_ctx {
     // connected components: the parent array (4 B/px) when the caller passes no label plane; per-frame totals and per-row
     // counts / prefixes of the numbering scan
     DevBuf cc_parent, cc_ws;
+    // contour chains: per-frame totals and per-row sums / prefixes of the chain points (the scan's second use)
+    DevBuf ct_ws;
     // distance transform: the row pass's u16 plane (2 B/px, rows padded to 64 pixels); the column scan's stack (4 B/px) when
     // the caller passes no dist2 plane to keep it in
     DevBuf edt_cols, edt_stack;
@@ -416,11 +418,13 @@ struct canny_hip_ctx {
     unsigned prof_every = 1;  // ... and only every prof_every-th launch group of a stage gets one
     // slots: the stages, then the three Hough parts (canny_hip_hough_profile_get), then the four parts of the component
     // labelling (canny_hip_components_profile_get), then the two of the distance transform (canny_hip_edt_profile_get),
-    // then the three of the Hough segments (canny_hip_hough_segments_profile_get)
+    // then the three of the Hough segments (canny_hip_hough_segments_profile_get), then the four of the contour chains
+    // (canny_hip_contours_profile_get)
     static constexpr int kProfHough = CANNY_HIP_STAGE_END, kProfComponents = CANNY_HIP_STAGE_END + 3;
     static constexpr int kProfEdt = kProfComponents + CANNY_HIP_CC_PARTS;
     static constexpr int kProfSegments = kProfEdt + CANNY_HIP_EDT_PARTS;
-    static constexpr int kProfSlots = kProfSegments + CANNY_HIP_SEGMENT_PARTS;
+    static constexpr int kProfContours = kProfSegments + CANNY_HIP_SEGMENT_PARTS;
+    static constexpr int kProfSlots = kProfContours + CANNY_HIP_CONTOUR_PARTS;
     unsigned prof_seen[kProfSlots] = {0};
     std::vector<EventPair> pending[kProfSlots];
     std::vector<EventPair> pool;
@@ -1203,6 +1207,92 @@ int dev_canny_components(canny_hip_ctx *ctx, const unsigned char *d_img, float s
     return dev_components(ctx, (const uint64_t *)ctx->plane_s.p, nullptr, make_hyst_geom(h, w, n), min_area, out);
 }
 
+// ---- outer contour chains (canny_contours.hip) -----------------------------
+struct CtOut {
+    int *stats;
+    unsigned long long capacity;
+    unsigned long long *offsets, *chain_offsets;
+    int *points;
+    unsigned long long point_capacity;
+    unsigned long long *point_offsets;
+};
+
+// the chain points of a frame are summed in 32 bits: a chain has at most 8 * area + 1 of them
+int check_contour_dims(int height, int width, int n_frames)
+{
+    const int rc = check_dims(height, width, n_frames);
+    if (rc) return rc;
+    return (long long)height * width > kContourMaxPixels ? CANNY_HIP_ERR_UNSUPPORTED : CANNY_HIP_OK;
+}
+
+bool contour_args_ok(const CtOut &out)
+{
+    return out.offsets && out.point_offsets && (out.chain_offsets || !out.capacity) && (out.points || !out.point_capacity);
+}
+
+// The chains of one source (the context's strong plane or packed bits), queued on the context's stream: the labelling up
+// to its scan, the two walks around the second scan, and the records last (launch_cc_number replaces the roots' entries).
+int dev_contours(canny_hip_ctx *ctx, const uint64_t *strong, const uint8_t *bits, const HystGeom &g, int min_area,
+                 const CtOut &out)
+{
+    const size_t rows = (size_t)g.n_frames * g.height;
+    const size_t ws_bytes = g.n_frames * sizeof(unsigned long long) + rows * sizeof(uint32_t);
+    HIP_TRY(ctx, ctx->cc_parent.ensure(npx(g.height, g.width, g.n_frames) * sizeof(int)));
+    HIP_TRY(ctx, ctx->cc_ws.ensure(ws_bytes));
+    HIP_TRY(ctx, ctx->ct_ws.ensure(ws_bytes));
+    int *parent = (int *)ctx->cc_parent.p;
+    unsigned long long *totals = (unsigned long long *)ctx->cc_ws.p, *point_totals = (unsigned long long *)ctx->ct_ws.p;
+    uint32_t *row_words = (uint32_t *)(totals + g.n_frames), *row_points = (uint32_t *)(point_totals + g.n_frames);
+    {
+        StageTimer tm(ctx, canny_hip_ctx::kProfContours + CANNY_HIP_CONTOUR_PART_LABEL);
+        HIP_TRY(ctx, launch_cc_link(strong, bits, g, parent, ctx->stream));
+        HIP_TRY(ctx, launch_cc_resolve(strong, bits, g, parent, ctx->stream));
+        HIP_TRY(ctx, launch_cc_count(strong, bits, g, parent, min_area, row_words, ctx->stream));
+        HIP_TRY(ctx, launch_points_scan(row_words, totals, out.offsets, g.height, g.n_frames, ctx->stream));
+    }
+    {
+        StageTimer tm(ctx, canny_hip_ctx::kProfContours + CANNY_HIP_CONTOUR_PART_COUNT);
+        HIP_TRY(ctx, launch_ct_count(strong, bits, g, parent, min_area, row_words, out.offsets, out.chain_offsets,
+                                     out.capacity, row_points, ctx->stream));
+        HIP_TRY(ctx, launch_points_scan(row_points, point_totals, out.point_offsets, g.height, g.n_frames, ctx->stream));
+        if (out.capacity)
+            HIP_TRY(ctx, launch_ct_place(g, row_words, out.offsets, row_points, out.point_offsets, out.chain_offsets,
+                                         out.capacity, ctx->stream));
+    }
+    if (out.capacity && out.point_capacity) {
+        StageTimer tm(ctx, canny_hip_ctx::kProfContours + CANNY_HIP_CONTOUR_PART_WRITE);
+        HIP_TRY(ctx, launch_ct_write(strong, bits, g, parent, min_area, row_words, out.offsets, out.chain_offsets,
+                                     out.capacity, out.points, out.point_capacity, ctx->stream));
+    }
+    if (out.stats && out.capacity) {
+        StageTimer tm(ctx, canny_hip_ctx::kProfContours + CANNY_HIP_CONTOUR_PART_STATS);
+        HIP_TRY(ctx, launch_cc_number(strong, bits, g, parent, min_area, row_words, out.offsets, out.stats, out.capacity,
+                                      ctx->stream));
+    }
+    return CANNY_HIP_OK;
+}
+
+// dev_canny (unchanged), then the chains of its map from the converged strong plane.  The result follows the MAP:
+// max_val > 255 leaves no edge pixel (see dev_canny_points_count).
+int dev_canny_contours(canny_hip_ctx *ctx, const unsigned char *d_img, float sigma, int lo, int hi, int h, int w, int n,
+                       short *d_edges, int min_area, const CtOut &out)
+{
+    int rc;
+    if (!d_edges) {
+        HIP_TRY(ctx, ctx->edges16.ensure(npx(h, w, n) * sizeof(short)));
+        d_edges = (short *)ctx->edges16.p;
+    }
+    if ((rc = dev_canny(ctx, d_img, sigma, lo, hi, h, w, n, d_edges))) return rc;
+    if (hi > 255) {
+        const size_t off_bytes = ((size_t)n + 1) * sizeof(unsigned long long);
+        HIP_TRY(ctx, hipMemsetAsync(out.offsets, 0, off_bytes, ctx->stream));
+        HIP_TRY(ctx, hipMemsetAsync(out.point_offsets, 0, off_bytes, ctx->stream));
+        if (out.chain_offsets) HIP_TRY(ctx, hipMemsetAsync(out.chain_offsets, 0, sizeof(unsigned long long), ctx->stream));
+        return CANNY_HIP_OK;
+    }
+    return dev_contours(ctx, (const uint64_t *)ctx->plane_s.p, nullptr, make_hyst_geom(h, w, n), min_area, out);
+}
+
 // ---- Euclidean distance transform (canny_edt.hip) --------------------------
 struct EdtOut {
     int *dist2;
@@ -1620,6 +1710,7 @@ void canny_hip_ctx_destroy(canny_hip_ctx *ctx)
     ctx->seg_work.release();
     ctx->cc_parent.release();
     ctx->cc_ws.release();
+    ctx->ct_ws.release();
     ctx->edt_cols.release();
     ctx->edt_stack.release();
     ctx->stamps.release();
@@ -2999,6 +3090,156 @@ int canny_hip_components_from_bits(const unsigned char *bits, int height, int wi
     return CANNY_HIP_OK;
 }
 
+// ---- outer contour chains ----------------------------------------------------------------------------
+int canny_hip_dev_canny_contours(canny_hip_ctx *ctx, const unsigned char *d_img, float sigma, int min_val, int max_val,
+                                 int height, int width, int n_frames, short *d_edges, int min_area, int *d_stats,
+                                 unsigned long long capacity, unsigned long long *d_offsets,
+                                 unsigned long long *d_chain_offsets, int *d_points, unsigned long long point_capacity,
+                                 unsigned long long *d_point_offsets)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    const CtOut out{d_stats, capacity, d_offsets, d_chain_offsets, d_points, point_capacity, d_point_offsets};
+    if (!d_img || !contour_args_ok(out)) return CANNY_HIP_ERR_INVALID;
+    if ((rc = check_contour_dims(height, width, n_frames))) return rc;
+    return dev_canny_contours(ctx, d_img, sigma, min_val, max_val, height, width, n_frames, d_edges, min_area, out);
+}
+
+int canny_hip_dev_contours_bits(canny_hip_ctx *ctx, const unsigned char *d_bits, int height, int width, int n_frames,
+                                int min_area, int *d_stats, unsigned long long capacity, unsigned long long *d_offsets,
+                                unsigned long long *d_chain_offsets, int *d_points, unsigned long long point_capacity,
+                                unsigned long long *d_point_offsets)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    const CtOut out{d_stats, capacity, d_offsets, d_chain_offsets, d_points, point_capacity, d_point_offsets};
+    if (!d_bits || !contour_args_ok(out)) return CANNY_HIP_ERR_INVALID;
+    if ((rc = check_contour_dims(height, width, n_frames)) || (rc = finish_pending(ctx))) return rc;
+    return dev_contours(ctx, nullptr, d_bits, make_hyst_geom(height, width, n_frames), min_area, out);
+}
+
+int canny_hip_canny_contours(canny_hip_ctx *ctx, const unsigned char *imgs, int n_frames, float sigma, int min_val,
+                             int max_val, int height, int width, int min_area, int *stats, unsigned long long capacity,
+                             unsigned long long *offsets, unsigned long long *chain_offsets, int *points,
+                             unsigned long long point_capacity, unsigned long long *point_offsets)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!imgs || !contour_args_ok(CtOut{stats, capacity, offsets, chain_offsets, points, point_capacity, point_offsets}))
+        return CANNY_HIP_ERR_INVALID;
+    if ((rc = check_contour_dims(height, width, n_frames))) return rc;
+    const size_t n = npx(height, width, n_frames);
+    const size_t off_bytes = ((size_t)n_frames + 1) * sizeof(unsigned long long);
+    // a frame has no more records than pixels and no more chain points than 8 per pixel and one per record
+    const unsigned long long cap = std::min<unsigned long long>(capacity, n);
+    const unsigned long long pcap = std::min<unsigned long long>(point_capacity, 9ull * n);
+    if ((rc = h2d(ctx, ctx->io[0], imgs, n))) return rc;
+    // one staging block: offsets | point_offsets | chain_offsets | stats | points
+    auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+    const size_t poff_at = up16(off_bytes), chain_at = up16(poff_at + off_bytes);
+    const size_t stats_at = up16(chain_at + ((size_t)cap + 1) * sizeof(unsigned long long));
+    const size_t points_at = up16(stats_at + (stats ? (size_t)cap * CANNY_HIP_CC_STATS * sizeof(int) : 0));
+    HIP_TRY(ctx, ctx->io[1].ensure(points_at + (size_t)pcap * sizeof(int)));
+    char *d = (char *)ctx->io[1].p;
+    const CtOut out{stats && cap ? (int *)(d + stats_at) : nullptr,
+                    cap,
+                    (unsigned long long *)d,
+                    (unsigned long long *)(d + chain_at),
+                    pcap ? (int *)(d + points_at) : nullptr,
+                    pcap,
+                    (unsigned long long *)(d + poff_at)};
+    if ((rc = dev_canny_contours(ctx, (const unsigned char *)ctx->io[0].p, sigma, min_val, max_val, height, width,
+                                 n_frames, nullptr, min_area, out)))
+        return rc;
+    // the offsets come down first: they say how many records and points there are to download
+    std::vector<unsigned long long> off(2 * ((size_t)n_frames + 1));
+    HIP_TRY(ctx, hipMemcpyAsync(off.data(), out.offsets, off_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = d2h_sync(ctx, off.data() + n_frames + 1, out.point_offsets, off_bytes))) return rc;
+    const unsigned long long n_rec = std::min(off[n_frames], cap);
+    if (chain_offsets)
+        HIP_TRY(ctx, hipMemcpyAsync(chain_offsets, out.chain_offsets, ((size_t)n_rec + 1) * sizeof(unsigned long long),
+                                    hipMemcpyDeviceToHost, ctx->stream));
+    if (n_rec && out.stats)
+        HIP_TRY(ctx, hipMemcpyAsync(stats, out.stats, (size_t)n_rec * CANNY_HIP_CC_STATS * sizeof(int),
+                                    hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (n_rec && pcap) {
+        // chain_offsets is needed on the host to know where the records that fit end
+        unsigned long long end = 0;
+        HIP_TRY(ctx, hipMemcpyAsync(&end, out.chain_offsets + n_rec, sizeof end, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        const unsigned long long n_pts = std::min(end, pcap);
+        if (n_pts) {
+            HIP_TRY(ctx, hipMemcpyAsync(points, out.points, (size_t)n_pts * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        }
+    }
+    std::memcpy(offsets, off.data(), off_bytes);
+    std::memcpy(point_offsets, off.data() + n_frames + 1, off_bytes);
+    return CANNY_HIP_OK;
+}
+
+// The rule on one host bit map in plain C++: the components of canny_hip_components_from_bits, then the walk of the
+// rule from every kept component's first pixel on a byte map with a one-pixel border of zeros.
+int canny_hip_contours_from_bits(const unsigned char *bits, int height, int width, int min_area, int *stats,
+                                 unsigned long long capacity, unsigned long long *count,
+                                 unsigned long long *chain_offsets, int *points, unsigned long long point_capacity,
+                                 unsigned long long *point_count)
+{
+    if (!bits || !count || !point_count || (!chain_offsets && capacity) || (!points && point_capacity))
+        return CANNY_HIP_ERR_INVALID;
+    int rc = check_contour_dims(height, width, 1);
+    if (rc) return rc;
+    unsigned long long k = 0;
+    if ((rc = canny_hip_components_from_bits(bits, height, width, min_area, nullptr, nullptr, 0, &k))) return rc;
+    std::vector<int> rec((size_t)k * CANNY_HIP_CC_STATS);
+    if (k && (rc = canny_hip_components_from_bits(bits, height, width, min_area, nullptr, rec.data(), k, &k))) return rc;
+    const size_t row_bytes = ((size_t)width + 7) / 8, pitch = (size_t)width + 2;
+    std::vector<unsigned char> map(((size_t)height + 2) * pitch, 0);
+    for (int y = 0; y < height; y++)
+        for (int x = 0; x < width; x++)
+            map[((size_t)y + 1) * pitch + x + 1] = (bits[(size_t)y * row_bytes + (x >> 3)] >> (7 - (x & 7))) & 1;
+    static const int dy[8] = {0, 1, 1, 1, 0, -1, -1, -1}, dx[8] = {1, 1, 0, -1, -1, -1, 0, 1};
+    unsigned long long total = 0;
+    if (chain_offsets) chain_offsets[0] = 0;
+    for (unsigned long long j = 0; j < k; j++) {
+        const int *r = rec.data() + j * CANNY_HIP_CC_STATS;
+        const int p0 = r[CANNY_HIP_CC_STAT_FIRST];
+        const bool fits = j < capacity;
+        auto emit = [&](int px) {
+            if (fits && total < point_capacity) points[total] = px;
+            total++;
+        };
+        auto set_at = [&](int y, int x) { return map[((size_t)y + 1) * pitch + x + 1] != 0; };
+        int y = p0 / width, x = p0 % width;
+        emit(p0);
+        int d = -1;
+        for (int i = 0; i < 7 && d < 0; i++)
+            if (set_at(y + dy[(5 + i) & 7], x + dx[(5 + i) & 7])) d = (5 + i) & 7;
+        if (d >= 0) {
+            const int q1 = p0 + dy[d] * width + dx[d];
+            int cur = p0, s = (d - 1) & 7;
+            const unsigned long long cap = 8ull * (unsigned long long)r[CANNY_HIP_CC_STAT_AREA];
+            for (unsigned long long step = 0; step < cap; step++) {
+                d = -1;
+                for (int i = 0; i < 8 && d < 0; i++)
+                    if (set_at(y + dy[(s - i) & 7], x + dx[(s - i) & 7])) d = (s - i) & 7;
+                if (d < 0) break;
+                const int nxt = cur + dy[d] * width + dx[d];
+                if (nxt == p0 && cur == q1) break;
+                emit(nxt);
+                y += dy[d], x += dx[d], cur = nxt, s = (d + 3) & 7;
+            }
+        }
+        if (fits) chain_offsets[j + 1] = total;
+    }
+    if (stats)
+        std::memcpy(stats, rec.data(), (size_t)std::min(k, capacity) * CANNY_HIP_CC_STATS * sizeof(int));
+    *count = k;
+    *point_count = total;
+    return CANNY_HIP_OK;
+}
+
 // ---- Euclidean distance transform -------------------------------------------------------------------
 int canny_hip_dev_canny_edt(canny_hip_ctx *ctx, const unsigned char *d_img, float sigma, int min_val, int max_val,
                             int height, int width, int n_frames, short *d_edges, int *d_dist2, float *d_dist,
@@ -3524,6 +3765,17 @@ int canny_hip_hough_segments_profile_get(canny_hip_ctx *ctx, int part, double *t
     if ((rc = profile_collect(ctx))) return rc;
     *total_ms = ctx->total_ms[canny_hip_ctx::kProfSegments + part];
     *launches = ctx->launches[canny_hip_ctx::kProfSegments + part];
+    return CANNY_HIP_OK;
+}
+
+int canny_hip_contours_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches)
+{
+    if (part < 0 || part >= CANNY_HIP_CONTOUR_PARTS || !total_ms || !launches) return CANNY_HIP_ERR_INVALID;
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if ((rc = profile_collect(ctx))) return rc;
+    *total_ms = ctx->total_ms[canny_hip_ctx::kProfContours + part];
+    *launches = ctx->launches[canny_hip_ctx::kProfContours + part];
     return CANNY_HIP_OK;
 }
 

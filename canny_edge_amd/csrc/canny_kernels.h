@@ -443,6 +443,30 @@ hipError_t launch_cc_number(const uint64_t *strong, const uint8_t *bits, const H
 hipError_t launch_cc_write(const uint64_t *strong, const uint8_t *bits, const HystGeom &g, const int *entries, int *labels,
                            uint8_t *kept, hipStream_t stream);
 
+// ---- Outer contour chains (canny_contours.hip) -------------------------
+// Source as for the point lists.  They run behind launch_cc_link, launch_cc_resolve, launch_cc_count and
+// launch_points_scan on the same stream and BEFORE launch_cc_number (which replaces the roots' entries): parent is as
+// resolve leaves it, row_offsets / offsets are the record CSR of the scan.  height * width <= kContourMaxPixels: a chain has
+// at most 8 * area + 1 points, and the per-frame sums of the scan are 32-bit.
+constexpr long long kContourMaxPixels = 1ll << 28;
+// count: every kept component's border is followed once; chain_offsets[j + 1] = the length of record j's chain for
+// j < capacity (chain_offsets may be null: capacity counts as 0), chain_offsets[0] = 0, row_points[f * height + y] = chain
+// points of ALL kept components whose first pixel lies in that row (then launch_points_scan gives point_offsets).
+hipError_t launch_ct_count(const uint64_t *strong, const uint8_t *bits, const HystGeom &g, const int *parent, int min_area,
+                           const uint32_t *row_offsets, const unsigned long long *offsets,
+                           unsigned long long *chain_offsets, unsigned long long capacity, uint32_t *row_points,
+                           hipStream_t stream);
+// place: the lengths in chain_offsets[1 .. min(K, capacity)] become prefix sums over the whole batch (in place).
+hipError_t launch_ct_place(const HystGeom &g, const uint32_t *row_offsets, const unsigned long long *offsets,
+                           const uint32_t *row_point_offsets, const unsigned long long *point_offsets,
+                           unsigned long long *chain_offsets, unsigned long long capacity, hipStream_t stream);
+// write: the same walks; points[chain_offsets[j] + i] = the i-th pixel (r * width + c) of record j's chain, for j < capacity
+// and positions below point_capacity; nothing is stored at or beyond points + point_capacity.
+hipError_t launch_ct_write(const uint64_t *strong, const uint8_t *bits, const HystGeom &g, const int *parent, int min_area,
+                           const uint32_t *row_offsets, const unsigned long long *offsets,
+                           unsigned long long *chain_offsets, unsigned long long capacity, int *points,
+                           unsigned long long point_capacity, hipStream_t stream);
+
 // ---- Euclidean distance transform (canny_edt.hip) ----------------------
 // Source as for the point lists.  height * width < 2^31 and height^2 + width^2 < 2^31.
 // Elements per row of the u16 plane between the two passes: rows are padded to whole 64-pixel words.

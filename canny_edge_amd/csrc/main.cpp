@@ -1,6 +1,6 @@
 // main.cpp -- the reference's command line (StevenChang5/Canny_Edge src/main.cpp:18-142) without
 // the webcam and the GUI:  ./Main sigma minVal maxVal [-c] [-s] [-i in.pgm|in.ppm|in.jpg] [-o dir] [-p] [-n WxH] [-b dir]
-//        [-l rho,theta_degrees,threshold[,lines_max]] [-g min_length,max_gap[,exclusive]] [-m min_area] [-d]
+//        [-l rho,theta_degrees,threshold[,lines_max]] [-g min_length,max_gap[,exclusive]] [-m min_area] [-t] [-d]
 //
 // Kept from the reference: the three positionals may appear anywhere relative to the flags
 // (src/main.cpp:29-46); exactly three are required, otherwise the usage text is printed and the
@@ -21,6 +21,9 @@
 // with fewer than min_area pixels and writes one "label left top width height area" row per kept component to
 // canny_components.txt and the filtered map to canny_kept.pgm (.png with -p) in the -o directory (rows to stdout without
 // -o).  Without -m nothing changes.
+// Added: -t follows the outer border of every component of the frame's edge map with at least min_area pixels (-m, default
+// 1) on the GPU (canny_hip_canny_contours) and writes one "label n x0 y0 x1 y1 ..." line per contour to canny_contours.txt
+// in the -o directory (stdout without -o).
 // Added: -d runs the exact Euclidean distance transform of the frame's edge map on the GPU (canny_hip_canny_edt) and writes
 // canny_dist.pgm (.png with -p) to the -o directory (the current one without -o): one byte per pixel,
 // min(255, floor(sqrt(dist2))), 255 everywhere for a map without edge pixels.  Without -d nothing changes.
@@ -337,6 +340,45 @@ static int run_components(const vector<unsigned char> &frame, int height, int wi
     return 0;
 }
 
+// -t: the outer contour chain of every kept component, one "label n x0 y0 x1 y1 ..." line each
+static int run_contours(const vector<unsigned char> &frame, int height, int width, float sigma, int minVal, int maxVal,
+                        int min_area, const string &outdir)
+{
+    vector<unsigned long long> chain(1, 0);
+    vector<int> points;
+    unsigned long long offsets[2] = {0, 0}, point_offsets[2] = {0, 0};
+    canny_hip_ctx *ctx = nullptr;
+    int st = canny_hip_ctx_create(&ctx, 0);
+    // counts first, then exactly the chains there are
+    if (!st)
+        st = canny_hip_canny_contours(ctx, frame.data(), 1, sigma, minVal, maxVal, height, width, min_area, nullptr, 0,
+                                      offsets, nullptr, nullptr, 0, point_offsets);
+    if (!st) {
+        chain.resize((size_t)offsets[1] + 1);
+        points.resize((size_t)point_offsets[1] + 1);
+        st = canny_hip_canny_contours(ctx, frame.data(), 1, sigma, minVal, maxVal, height, width, min_area, nullptr,
+                                      offsets[1], offsets, chain.data(), points.data(), point_offsets[1], point_offsets);
+    }
+    if (st) {
+        fprintf(stderr, "ERROR: -t: %s\n", st == CANNY_HIP_ERR_RUNTIME && ctx ? canny_hip_last_error(ctx) : canny_hip_status_string(st));
+        if (ctx) canny_hip_ctx_destroy(ctx);
+        return 1;
+    }
+    canny_hip_ctx_destroy(ctx);
+    FILE *f = outdir.empty() ? stdout : fopen((outdir + "/canny_contours.txt").c_str(), "w");
+    if (!f) {
+        fprintf(stderr, "ERROR: cannot write %s/canny_contours.txt\n", outdir.c_str());
+        return 1;
+    }
+    for (unsigned long long k = 0; k < offsets[1]; k++) {
+        fprintf(f, "%llu %llu", k + 1, chain[k + 1] - chain[k]);
+        for (unsigned long long q = chain[k]; q < chain[k + 1]; q++) fprintf(f, " %d %d", points[q] % width, points[q] / width);
+        fprintf(f, "\n");
+    }
+    if (f != stdout) fclose(f);
+    return 0;
+}
+
 // -d: the distance of every pixel to the nearest edge pixel, as a byte image
 static int run_edt(const vector<unsigned char> &frame, int height, int width, float sigma, int minVal, int maxVal,
                    const string &outdir)
@@ -385,6 +427,7 @@ int main(int argc, char *argv[])
     bool want_components = false;
     int min_area = 1;
     bool want_dist = false;
+    bool want_contours = false;
     int width = WIDTH, height = HEIGHT;
     vector<string> values;
 
@@ -423,6 +466,8 @@ int main(int argc, char *argv[])
             want_components = true;
         } else if (arg == "-d") {
             want_dist = true;
+        } else if (arg == "-t") {
+            want_contours = true;
         } else if (arg == "-n" && i + 1 < argc) {
             if (sscanf(argv[++i], "%dx%d", &width, &height) != 2 || width < 2 || height < 2) {
                 fprintf(stderr, "ERROR: -n expects WIDTHxHEIGHT\n");
@@ -452,6 +497,8 @@ int main(int argc, char *argv[])
         fprintf(stderr, "   -g min_length,max_gap[,exclusive]: with -l, the segments along the lines -> canny_segments.txt in the -o dir\n");
         fprintf(stderr, "   -m min_area: connected components of the edge map with at least min_area pixels -> canny_components.txt,\n");
         fprintf(stderr, "                canny_kept.pgm in the -o dir\n");
+        fprintf(stderr, "   -t: outer contour chain of every component with at least min_area (-m, default 1) pixels, one\n");
+        fprintf(stderr, "       \"label n x0 y0 x1 y1 ...\" line each -> canny_contours.txt in the -o dir\n");
         fprintf(stderr, "   -d: distance of every pixel to the nearest edge pixel, min(255, floor) -> canny_dist.pgm in the -o dir\n");
         exit(0);
     }
@@ -508,6 +555,10 @@ int main(int argc, char *argv[])
     }
     if (want_components) {
         const int rc = run_components(frame, height, width, sigma, minVal, maxVal, min_area, outdir);
+        if (rc) return rc;
+    }
+    if (want_contours) {
+        const int rc = run_contours(frame, height, width, sigma, minVal, maxVal, min_area, outdir);
         if (rc) return rc;
     }
     if (want_dist) {

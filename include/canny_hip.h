@@ -52,7 +52,8 @@
 extern "C" {
 #endif
 
-#define CANNY_HIP_VERSION 901        /* 0.9.1: + canny_hip_selftest_histogram, canny_hip_selftest_select */
+#define CANNY_HIP_VERSION 1000       /* 0.10.0: + outer contour chains of the finished map, traced on the GPU */
+/* 0.9.1: + canny_hip_selftest_histogram, canny_hip_selftest_select */
 /* 0.9.0: + Hough line segments: runs of edge pixels along each detected line */
 /* 0.8.0: + exact Euclidean distance transform of the finished map: dist2, dist, nearest */
 /* 0.7.0: + 8-connected components of the finished map: labels, stats, minimum-area filter */
@@ -640,8 +641,8 @@ int canny_hip_canny_hough_segments(canny_hip_ctx *ctx, const unsigned char *imgs
  *   is touched per run of set pixels, not per pixel); with labels given that array lives in the label plane itself.
  * The four parts are timed by canny_hip_components_profile_get (CANNY_HIP_CC_PART_*); with "profile_stage_mask" they are
  *   bits 13 .. 16 (the Hough parts are bits 10 .. 12).
- * Not covered -- follow-ups: 4-connectivity, centroids, contour chains (cv::findContours), the three-stream batch pipeline,
- * the multi-GPU sharder, colour and per-frame / automatic-threshold variants. */
+ * Not covered -- follow-ups: 4-connectivity, centroids, the three-stream batch pipeline, the multi-GPU sharder, colour and
+ * per-frame / automatic-threshold variants.  (Contour chains: the next section.) */
 #define CANNY_HIP_CC_STATS 6
 enum canny_hip_cc_stat {
     CANNY_HIP_CC_STAT_LEFT = 0,
@@ -679,6 +680,95 @@ int canny_hip_canny_components(canny_hip_ctx *ctx, const unsigned char *imgs, in
  * receives the true number of kept components. */
 int canny_hip_components_from_bits(const unsigned char *bits, int height, int width, int min_area, int *labels,
                                    int *stats, unsigned long long capacity, unsigned long long *count);
+
+/* ---- outer contour chains ------------------------------------------------------------------------------------------------
+ * For every kept component of the finished edge map its outer border as an ORDERED list of pixels, per frame of a batch, on
+ * the GPU, queued behind the detector on the same stream with no host round trip: what curve fitting, polygon approximation,
+ * arc-length measures, shape descriptors and vector export start from -- the use of
+ * cv::findContours(RETR_EXTERNAL, CHAIN_APPROX_NONE) after cv::Canny.  (The same curves; no claim is made that the points
+ * come in the order OpenCV lists them.)  THE RULE, for frame f with edge map E_f (the map
+ * canny_hip_canny returns for that frame, bit for bit):
+ *   Components, the min_area filter and the numbering are exactly those of the connected components above.  For each kept
+ *     component the CHAIN is its outer border, followed as in Suzuki & Abe's border following restricted to outer borders,
+ *     with 8-connectivity, starting at the component's first pixel.
+ *   Directions are numbered clockwise on the displayed image, as (row, column) steps: 0 = E (0,+1), 1 = SE (+1,+1),
+ *     2 = S (+1,0), 3 = SW (+1,-1), 4 = W (0,-1), 5 = NW (-1,-1), 6 = N (-1,0), 7 = NE (-1,+1).  Pixels outside the frame
+ *     are unset.
+ *   1. p0 = first.  Examine p0's neighbours clockwise after W, in directions 5, 6, 7, 0, 1, 2, 3.  The first set one is q1,
+ *      in direction d_last.  If there is none, the chain is [p0].
+ *   2. Otherwise cur = p0 and s = (d_last - 1) & 7.  Repeat: examine cur's neighbours counter-clockwise in directions
+ *      s, s - 1, ... (mod 8, all eight); the first set one is nxt, in direction d.  If nxt == p0 and cur == q1, stop.
+ *      Otherwise append nxt, then cur = nxt and s = (d + 3) & 7.
+ *   3. The chain is p0 followed by the appended pixels, as indices r * width + c (the point lists' convention); p0 is not
+ *      repeated at the end.  Consecutive chain pixels, cyclically, are distinct 8-neighbours; a one-pixel-wide curve is
+ *      walked out and back, so a pixel may occur more than once.  As a set the chain is the component's pixels that have a
+ *      4-neighbour in the background region outside the component.
+ *   A walk is a sequence of states (cur, s) that ends before a state recurs, so a chain has at most 8 * area points; the
+ *     device walks are capped at 8 * area steps, which no map reaches.
+ *   Outputs, CSR on two levels (all offsets unsigned long long):
+ *     offsets[0 .. n_frames]: the record CSR over the batch, identical to what the components calls return for the same
+ *       min_area -- always the TRUE counts.  K = offsets[n_frames].
+ *     point_offsets[0 .. n_frames]: the CSR of chain POINTS per frame -- always the TRUE counts.  A counts-only call
+ *       (capacity = 0, point_capacity = 0, the other pointers NULL) sizes both buffers.
+ *     chain_offsets[j] for j = 0 .. min(K, capacity) (so capacity + 1 entries at most): the number of chain points of
+ *       records 0 .. j - 1, true prefix sums over the whole batch.  Record j's chain is
+ *       points[chain_offsets[j] .. chain_offsets[j + 1]).  Entries past min(K, capacity) are not written.
+ *       point_offsets[f] == chain_offsets[offsets[f]] wherever that entry exists.
+ *     points (int): position q is written iff q < point_capacity and it belongs to a record < capacity: the prefix that fits
+ *       is exact, a chain may be cut, nothing is written at or past points + point_capacity.
+ *     stats (optional, may be NULL at any capacity): the 6-int records of the connected components, bounded by capacity.
+ *   offsets and point_offsets are mandatory.  points == NULL with point_capacity > 0 and chain_offsets == NULL with
+ *     capacity > 0 are CANNY_HIP_ERR_INVALID.
+ *   The result follows the MAP: max_val > 255 empties every map, so all offsets and point_offsets are 0 (and
+ *     chain_offsets[0] = 0 if given).
+ *   Limits: height * width <= 2^28 (the chain points of a frame are summed in 32 bits), beyond that
+ *     CANNY_HIP_ERR_UNSUPPORTED before anything is queued.  Otherwise the statuses are those of canny_hip_dev_canny for the
+ *     same arguments, which runs first; on a status other than OK nothing is written.
+ *   The output is the same bytes on every run: lengths and positions are prefix sums in raster order of the first pixels,
+ *     every point is stored once by the one thread that walks its chain, and the launches depend on the shapes and on which
+ *     outputs were asked for, never on the data.
+ * Memory: a context workspace of 4 bytes per pixel of the batch (the union-find's parent array, shared with the components
+ *   calls) and 4 bytes per image row.
+ * Cost: a chain is walked by ONE thread, twice (lengths, then points), so a call takes as long as its longest chain; see
+ *   DESIGN.md section 17 for the measured time per step.
+ * The four parts are timed by canny_hip_contours_profile_get (CANNY_HIP_CONTOUR_PART_*); with "profile_stage_mask" they are
+ *   bits 22 .. 25.
+ * Not covered -- follow-ups: hole borders and the hierarchy, CHAIN_APPROX_SIMPLE and polygon approximation, 4-connectivity,
+ * sub-pixel positions, parallel ranking of long chains, the three-stream batch pipeline, the multi-GPU sharder, colour and
+ * per-frame / automatic-threshold variants. */
+enum canny_hip_contour_part {
+    CANNY_HIP_CONTOUR_PART_LABEL = 0,  /* union-find on runs, roots and areas, kept roots counted and scanned: offsets */
+    CANNY_HIP_CONTOUR_PART_COUNT = 1,  /* first walk: chain lengths, scanned and placed: point_offsets, chain_offsets */
+    CANNY_HIP_CONTOUR_PART_WRITE = 2,  /* second walk: points stored */
+    CANNY_HIP_CONTOUR_PART_STATS = 3,  /* the components' records, when stats was asked for */
+    CANNY_HIP_CONTOUR_PARTS = 4
+};
+/* Device buffers, asynchronous; completion contract and d_edges as canny_hip_dev_canny_points.  canny_hip_dev_canny itself
+ * queues exactly what it queues on its own; the walks read the converged hysteresis bit-plane behind it. */
+int canny_hip_dev_canny_contours(canny_hip_ctx *ctx, const unsigned char *d_img, float sigma, int min_val, int max_val,
+                                 int height, int width, int n_frames, short *d_edges, int min_area, int *d_stats,
+                                 unsigned long long capacity, unsigned long long *d_offsets,
+                                 unsigned long long *d_chain_offsets, int *d_points, unsigned long long point_capacity,
+                                 unsigned long long *d_point_offsets);
+/* The chains alone, on device bit maps in the layout of canny_hip_dev_canny_bits (rows MSB-first, padded to bytes; any
+ * byte alignment; the padding bits of a row are ignored, whatever they hold).  Asynchronous. */
+int canny_hip_dev_contours_bits(canny_hip_ctx *ctx, const unsigned char *d_bits, int height, int width, int n_frames,
+                                int min_area, int *d_stats, unsigned long long capacity, unsigned long long *d_offsets,
+                                unsigned long long *d_chain_offsets, int *d_points, unsigned long long point_capacity,
+                                unsigned long long *d_point_offsets);
+/* Host buffers, synchronous: upload, canny, chains; offsets and point_offsets come down first, then what fits:
+ * min(K, capacity) + 1 chain offsets, as many records, and the points below min(chain_offsets[min(K, capacity)],
+ * point_capacity). */
+int canny_hip_canny_contours(canny_hip_ctx *ctx, const unsigned char *imgs, int n_frames, float sigma, int min_val,
+                             int max_val, int height, int width, int min_area, int *stats, unsigned long long capacity,
+                             unsigned long long *offsets, unsigned long long *chain_offsets, int *points,
+                             unsigned long long point_capacity, unsigned long long *point_offsets);
+/* Host-only, needs no device: the same rule on ONE host bit map, in plain C++.  *count receives the true number of kept
+ * components, *point_count the true number of chain points; both are mandatory. */
+int canny_hip_contours_from_bits(const unsigned char *bits, int height, int width, int min_area, int *stats,
+                                 unsigned long long capacity, unsigned long long *count,
+                                 unsigned long long *chain_offsets, int *points, unsigned long long point_capacity,
+                                 unsigned long long *point_count);
 
 /* ---- Euclidean distance transform ----------------------------------------------------------------------------------------
  * For every pixel of every frame the distance to the nearest edge pixel, on the GPU, queued behind the detector on the same
@@ -745,6 +835,9 @@ int canny_hip_components_profile_get(canny_hip_ctx *ctx, int part, double *total
 int canny_hip_edt_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches);
 /* ... and for the three parts of the Hough segments (CANNY_HIP_SEGMENT_PART_*). */
 int canny_hip_hough_segments_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches);
+
+/* ... and for the four parts of the contour chains (CANNY_HIP_CONTOUR_PART_*). */
+int canny_hip_contours_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches);
 
 /* ---- self-test hooks used by the GPU test-suite -------------------------------------------- */
 /* Runs the DEVICE magnitude / angle-bin functions over every (gx,gy) in [-lim,lim]^2 and writes
