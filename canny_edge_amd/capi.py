@@ -103,6 +103,9 @@ EXPORTS = (
     "canny_hip_hough_segments_from_bits", "canny_hip_dev_hough_segments_bits", "canny_hip_dev_canny_hough_segments",
     "canny_hip_canny_hough_segments", "canny_hip_hough_segments_profile_get",
     "canny_hip_selftest_histogram", "canny_hip_selftest_select",
+    "canny_hip_hough_circles_step_of", "canny_hip_hough_circles_from_bits", "canny_hip_dev_hough_circles_bits",
+    "canny_hip_dev_canny_hough_circles", "canny_hip_canny_hough_circles", "canny_hip_dev_hough_circles_steps",
+    "canny_hip_hough_circles_profile_get",
 )
 
 _lib: Optional[C.CDLL] = None
@@ -244,6 +247,13 @@ def load() -> C.CDLL:
         "canny_hip_hough_segments_profile_get": ([p, i, C.POINTER(C.c_double), C.POINTER(C.c_long)], i),
         "canny_hip_selftest_histogram": ([p, p, i, i, i, i, i, p], i),
         "canny_hip_selftest_select": ([p, p, i, i, f, f, p], i),
+        "canny_hip_hough_circles_step_of": ([i, i, ip, ip], i),
+        "canny_hip_hough_circles_from_bits": ([p, p, p, i, i, i, i, i, i, i, i, i, p, ip, ip, p], i),
+        "canny_hip_dev_hough_circles_bits": ([p, p, p, p, i, i, i, i, i, i, i, i, i, i, p, p, p, p], i),
+        "canny_hip_dev_canny_hough_circles": ([p, p, f, i, i, i, i, i, p, i, i, i, i, i, i, i, p, p, p, p], i),
+        "canny_hip_canny_hough_circles": ([p, p, i, f, i, i, i, i, i, i, i, i, i, i, i, p, p, p], i),
+        "canny_hip_dev_hough_circles_steps": ([p, p, p, C.c_size_t, p, p], i),
+        "canny_hip_hough_circles_profile_get": ([p, i, C.POINTER(C.c_double), C.POINTER(C.c_long)], i),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -454,6 +464,48 @@ def hough_segments_from_bits(bits, height: int, width: int, bases, rho: float = 
     run(buf, int(segments_max))
     k = min(n.value, max(int(segments_max), 0))
     return buf[:k * SEGMENT_INTS].reshape(k, SEGMENT_INTS), n.value
+
+
+CIRCLES_MAX_RADIUS = 1024                                       # CANNY_HIP_CIRCLES_MAX_RADIUS
+CIRCLE_INTS = 6                                                 # ints per record: x2, y2, radius, votes, support, base
+CIRCLE_PARTS = ("vote", "centres", "radius", "accept")
+CIRCLE_DTYPE = np.dtype([("x", np.float32), ("y", np.float32), ("x2", np.int32), ("y2", np.int32), ("radius", np.int32),
+                         ("votes", np.int32), ("support", np.int32), ("base", np.int32)])
+
+
+def hough_circles_step_of(gx: int, gy: int) -> Tuple[int, int]:
+    """Host-only: the step (sx, sy) of one gradient as the rule of include/canny_hip.h defines it."""
+    sx, sy = C.c_int(0), C.c_int(0)
+    st = load().canny_hip_hough_circles_step_of(int(gx), int(gy), C.byref(sx), C.byref(sy))
+    if st:
+        raise CannyHipError(st, "hough_circles_step_of")
+    return sx.value, sy.value
+
+
+def hough_circles_from_bits(bits, gx, gy, height: int, width: int, min_radius: int, max_radius: int, cell_shift: int = 0,
+                            threshold: int = 20, support_threshold: int = 10, min_dist: int = 0, centres_max: int = 256,
+                            want_accum: bool = False, out=None):
+    """Host-only: the circle rule of include/canny_hip.h on one packed bit map (numpy.packbits(mask, axis=-1); padding bits
+    ignored) and its int16 gradient planes.  Returns (circles int32 [k, 6], n_peaks[, accum]): the accepted records x2, y2,
+    radius, votes, support, base and the true number of peaks.  `out` (int32, at least centres_max * 6) receives the
+    records in place."""
+    b = np.ascontiguousarray(bits, dtype=np.uint8)
+    if height >= 1 and width >= 1 and b.size != height * ((width + 7) // 8):
+        raise ValueError(f"expected {height} rows of {(width + 7) // 8} bytes, got {b.size} bytes")
+    px, py = np.ascontiguousarray(gx, dtype=np.int16), np.ascontiguousarray(gy, dtype=np.int16)
+    if px.size != height * width or py.size != height * width:
+        raise ValueError("gx and gy must hold height * width shorts each")
+    c = 1 << max(0, min(int(cell_shift), 3))
+    acc = np.zeros(((height + c - 1) // c + 2, (width + c - 1) // c + 2), np.int32) if want_accum else None
+    buf = out if out is not None else np.empty(max(int(centres_max), 1) * CIRCLE_INTS, np.int32)
+    n, peaks = C.c_int(0), C.c_int(0)
+    st = load().canny_hip_hough_circles_from_bits(_hp(b), _hp(px), _hp(py), height, width, min_radius, max_radius,
+                                                  cell_shift, threshold, support_threshold, min_dist, centres_max,
+                                                  _hp(buf), C.byref(n), C.byref(peaks), _hp(acc) if want_accum else None)
+    if st:
+        raise CannyHipError(st, "hough_circles_from_bits")
+    rec = buf[:n.value * CIRCLE_INTS].reshape(n.value, CIRCLE_INTS)
+    return (rec, peaks.value, acc) if want_accum else (rec, peaks.value)
 
 
 def points_to_rc(points, width: int) -> Tuple[np.ndarray, np.ndarray]:
@@ -1075,6 +1127,77 @@ class Context:
         ms, n = C.c_double(0), C.c_long(0)
         self._check(self._L.canny_hip_hough_segments_profile_get(self._h, part, C.byref(ms), C.byref(n)),
                     "hough_segments_profile_get")
+        return ms.value, n.value
+
+    # ---- Hough circles (cv::HoughCircles(HOUGH_GRADIENT) semantics) ------------------------
+    def canny_hough_circles(self, imgs, sigma: float, min_val: int, max_val: int, min_radius: int, max_radius: int,
+                            cell_shift: int = 0, threshold: int = 20, support_threshold: int = 10, min_dist: int = 0,
+                            centres_max: int = 256):
+        """canny(), then the circle transform of each map on the GPU: imgs (H, W) or (N, H, W) uint8 -> (circles,
+        centre_counts): circles[f] is a structured array (CIRCLE_DTYPE) of the accepted circles in candidate order, with
+        float x = x2 / 2, y = y2 / 2 (pixel coordinates of the centre) beside the record's six ints; centre_counts int32
+        [N] holds the true number of accumulator peaks per frame."""
+        a = np.ascontiguousarray(imgs, dtype=np.uint8)
+        if a.ndim == 2:
+            a = a[None]
+        if a.ndim != 3:
+            raise ValueError("expected uint8 [H, W] or [n_frames, H, W]")
+        n, h, w = a.shape
+        rec = np.zeros((n, max(int(centres_max), 1), CIRCLE_INTS), np.int32)
+        counts, peaks = np.zeros(n, np.int32), np.zeros(n, np.int32)
+        self._check(self._L.canny_hip_canny_hough_circles(self._h, _hp(a), n, sigma, min_val, max_val, h, w, min_radius,
+                                                          max_radius, cell_shift, threshold, support_threshold, min_dist,
+                                                          centres_max, _hp(rec), _hp(counts), _hp(peaks)),
+                    "canny_hough_circles")
+        out = []
+        for f in range(n):
+            r = rec[f, :int(counts[f])]
+            c = np.zeros(len(r), CIRCLE_DTYPE)
+            c["x"], c["y"] = r[:, 0] / np.float32(2), r[:, 1] / np.float32(2)
+            for j, name in enumerate(("x2", "y2", "radius", "votes", "support", "base")):
+                c[name] = r[:, j]
+            out.append(c)
+        return out, peaks
+
+    def dev_hough_circles_bits(self, d_bits: int, d_gx: int, d_gy: int, n: int, h: int, w: int, min_radius: int,
+                               max_radius: int, cell_shift: int, threshold: int, support_threshold: int, min_dist: int,
+                               centres_max: int, d_circles: int, d_counts: int, d_centre_counts: int = 0, d_accum: int = 0):
+        """The transform of device bit maps (layout of dev_canny_bits, padding bits ignored) with full int16 gradient
+        planes; d_circles (6 int32 per slot, slot f * centres_max + j), d_centre_counts, d_accum may be 0; d_counts: n
+        int32."""
+        v = C.c_void_p
+        self._check(self._L.canny_hip_dev_hough_circles_bits(self._h, v(d_bits or None), v(d_gx or None), v(d_gy or None), n,
+                                                             h, w, min_radius, max_radius, cell_shift, threshold,
+                                                             support_threshold, min_dist, centres_max,
+                                                             v(d_circles or None), v(d_counts or None),
+                                                             v(d_centre_counts or None), v(d_accum or None)),
+                    "dev_hough_circles_bits")
+
+    def dev_canny_hough_circles(self, d_img: int, sigma: float, min_val: int, max_val: int, h: int, w: int, n: int,
+                                min_radius: int, max_radius: int, cell_shift: int, threshold: int, support_threshold: int,
+                                min_dist: int, centres_max: int, d_circles: int, d_counts: int, d_centre_counts: int = 0,
+                                d_accum: int = 0, d_edges: int = 0):
+        """dev_canny, then the circle transform queued behind it on the same stream: the map from the hysteresis bit-plane,
+        the gradient recomputed at the edge pixels from that call's smoothed plane."""
+        v = C.c_void_p
+        self._check(self._L.canny_hip_dev_canny_hough_circles(self._h, v(d_img or None), sigma, min_val, max_val, h, w, n,
+                                                              v(d_edges or None), min_radius, max_radius, cell_shift,
+                                                              threshold, support_threshold, min_dist, centres_max,
+                                                              v(d_circles or None), v(d_counts or None),
+                                                              v(d_centre_counts or None), v(d_accum or None)),
+                    "dev_canny_hough_circles")
+
+    def dev_hough_circles_steps(self, d_gx: int, d_gy: int, n: int, d_sx: int, d_sy: int):
+        """The device's step arithmetic on n int16 gradient pairs -> n int32 each in d_sx, d_sy."""
+        v = C.c_void_p
+        self._check(self._L.canny_hip_dev_hough_circles_steps(self._h, v(d_gx or None), v(d_gy or None), n,
+                                                              v(d_sx or None), v(d_sy or None)), "dev_hough_circles_steps")
+
+    def hough_circles_profile_get(self, part: int) -> Tuple[float, int]:
+        """(total ms, launch groups) of part 0 vote, 1 centres, 2 radius, 3 accept (CIRCLE_PARTS)."""
+        ms, n = C.c_double(0), C.c_long(0)
+        self._check(self._L.canny_hip_hough_circles_profile_get(self._h, part, C.byref(ms), C.byref(n)),
+                    "hough_circles_profile_get")
         return ms.value, n.value
 
     # ---- colour frames (interleaved BGR / RGB / BGRA / RGBA; the rule is the "gray_rule" option) --------------

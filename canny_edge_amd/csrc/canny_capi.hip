@@ -394,6 +394,9 @@ struct canny_hip_ctx {
     // Hough segments: per-line counts and offsets; bases and line counts when the caller passes none; the private copy of
     // the map that exclusive mode clears pixels from
     DevBuf seg_ws, seg_lines, seg_work;
+    // Hough circles: the accumulators when the caller passes none; candidate keys, votes, bases, radii, supports, peak
+    // counts, histograms, tie counts, cut words
+    DevBuf circ_accum, circ_ws;
     DevBuf plane_s, plane_c, stamps, flags; // hysteresis bit-planes / scheduling words
     DevBuf io[4];     // staging for the host-pointer stage functions
     unsigned *host_flags = nullptr;     // pinned + mapped, 4 words per lane: last_change, domain, sequence number, spare
@@ -419,12 +422,14 @@ struct canny_hip_ctx {
     // slots: the stages, then the three Hough parts (canny_hip_hough_profile_get), then the four parts of the component
     // labelling (canny_hip_components_profile_get), then the two of the distance transform (canny_hip_edt_profile_get),
     // then the three of the Hough segments (canny_hip_hough_segments_profile_get), then the four of the contour chains
-    // (canny_hip_contours_profile_get)
+    // (canny_hip_contours_profile_get), then the four of the Hough circles (canny_hip_hough_circles_profile_get)
     static constexpr int kProfHough = CANNY_HIP_STAGE_END, kProfComponents = CANNY_HIP_STAGE_END + 3;
     static constexpr int kProfEdt = kProfComponents + CANNY_HIP_CC_PARTS;
     static constexpr int kProfSegments = kProfEdt + CANNY_HIP_EDT_PARTS;
     static constexpr int kProfContours = kProfSegments + CANNY_HIP_SEGMENT_PARTS;
-    static constexpr int kProfSlots = kProfContours + CANNY_HIP_CONTOUR_PARTS;
+    static constexpr int kProfCircles = kProfContours + CANNY_HIP_CONTOUR_PARTS;
+    static constexpr int kProfSlots = kProfCircles + CANNY_HIP_CIRCLE_PARTS;
+    static_assert(kProfSlots <= 32, "profile_stage_mask has one bit per slot");
     unsigned prof_seen[kProfSlots] = {0};
     std::vector<EventPair> pending[kProfSlots];
     std::vector<EventPair> pool;
@@ -1488,6 +1493,116 @@ int dev_hough(canny_hip_ctx *ctx, const uint64_t *strong, const uint8_t *bits, c
     return CANNY_HIP_OK;
 }
 
+// ---- Hough circles (canny_hough_circles.hip) --------------------------------
+struct CircleArgs {
+    int min_radius, max_radius, cell_shift, threshold, support_threshold, min_dist, centres_max;
+};
+struct CircleOut {
+    int *d_circles, *d_counts, *d_centre_counts, *d_accum;
+};
+
+// No cell collects more votes than this: the samples of a ray are |step| / 1024 >= 0.9993 pixels
+// apart, so at most ceil(c sqrt 2) + 1 of them (and never more than there are radii) fall into one c x c cell; a pixel has
+// two rays; a sample lies less than max_radius + 1 pixels from its pixel, so only the pixels of the cell grown by that much on
+// every side, clipped to the frame, reach it.  The peak histogram has one bin per possible vote value.
+int circles_hist_bins(int height, int width, const CircleGeom &cg, double *bins)
+{
+    const double c = (double)(1 << cg.cell_shift);
+    const double per_ray = std::min((double)(cg.max_radius - cg.min_radius + 1), std::ceil(1.4143 * c) + 1.0);
+    const double reach = c + 2.0 * ((double)cg.max_radius + 1.0);
+    *bins = std::min((double)width, reach) * std::min((double)height, reach) * 2.0 * per_ray + 1.0;
+    return *bins <= (double)(1 << 26) ? CANNY_HIP_OK : CANNY_HIP_ERR_UNSUPPORTED;
+}
+
+// Checks that need no device and write nothing; the geometry on success.
+int circles_prepare(int height, int width, const CircleArgs &a, const int *counts, CircleGeom &cg)
+{
+    if (!counts || a.min_radius < 1 || a.min_radius > a.max_radius || a.cell_shift < 0 || a.cell_shift > 3 ||
+        a.centres_max < 1 || a.min_dist < 0 || height < 2 || width < 2)
+        return CANNY_HIP_ERR_INVALID;
+    if (a.max_radius > kCircleMaxRadius || a.centres_max > kHoughMaxLines) return CANNY_HIP_ERR_UNSUPPORTED;
+    const int c = 1 << a.cell_shift;
+    cg.min_radius = a.min_radius, cg.max_radius = a.max_radius, cg.cell_shift = a.cell_shift;
+    cg.aw = (width + c - 1) / c;
+    cg.ah = (height + c - 1) / c;
+    if (((double)cg.ah + 2.0) * ((double)cg.aw + 2.0) > 2147483647.0) return CANNY_HIP_ERR_UNSUPPORTED; // bases are 32-bit
+    double bins;
+    return circles_hist_bins(height, width, cg, &bins);
+}
+
+// THE step of the rule on the host (built with -ffp-contract=off): conversion, root and quotient each round once.
+void circles_step_of(int gx, int gy, int *sx, int *sy)
+{
+    const unsigned q = (unsigned)(gx * gx) + (unsigned)(gy * gy);
+    if (!q) {
+        *sx = *sy = 0;
+        return;
+    }
+    const float m = std::sqrt((float)q);
+    const float qx = (float)(gx * 1024) / m, qy = (float)(gy * 1024) / m;
+    *sx = (int)std::nearbyint(qx); // half to even (the default rounding mode)
+    *sy = (int)std::nearbyint(qy);
+}
+
+// The transform of one source (packed bits with gradient planes, or the context's strong plane with its smoothed plane),
+// queued on the context's stream.  Both sources null: the empty map (counts 0, a zero accumulator if the caller asked).
+int dev_circles(canny_hip_ctx *ctx, const uint64_t *strong, const uint8_t *bits, const HystGeom &g, const void *smoothed,
+                bool smoothed_u8, const short *d_gx, const short *d_gy, const CircleGeom &cg, const CircleArgs &a,
+                const CircleOut &out)
+{
+    const int n = g.n_frames, cm = a.centres_max;
+    HIP_TRY(ctx, hipMemsetAsync(out.d_counts, 0, (size_t)n * sizeof(int), ctx->stream));
+    if (out.d_centre_counts) HIP_TRY(ctx, hipMemsetAsync(out.d_centre_counts, 0, (size_t)n * sizeof(int), ctx->stream));
+    if (!strong && !bits) {
+        if (out.d_accum) HIP_TRY(ctx, hipMemsetAsync(out.d_accum, 0, circles_accum_bytes(cg, n), ctx->stream));
+        return CANNY_HIP_OK;
+    }
+    int *accum = out.d_accum;
+    if (!accum) {
+        HIP_TRY(ctx, ctx->circ_accum.ensure(circles_accum_bytes(cg, n)));
+        accum = (int *)ctx->circ_accum.p;
+    }
+    double bins_d;
+    (void)circles_hist_bins(g.height, g.width, cg, &bins_d);
+    const int bins = (int)bins_d;
+    // workspace: candidate keys | votes | bases | radii | supports | cut words | peak counts | histograms | tie counts per
+    // accumulator row (the last three are zeroed together)
+    const size_t slots = (size_t)n * cm;
+    const size_t zero_words = (size_t)n + (size_t)n * bins + (size_t)n * cg.ah;
+    HIP_TRY(ctx, ctx->circ_ws.ensure(slots * 8 + slots * 16 + ((size_t)n * 8 + zero_words) * sizeof(unsigned)));
+    unsigned long long *cand = (unsigned long long *)ctx->circ_ws.p;
+    int *votes = (int *)(cand + slots);
+    unsigned *bases = (unsigned *)(votes + slots);
+    int *radius = (int *)(bases + slots), *support = radius + slots;
+    unsigned *cut = (unsigned *)(support + slots);
+    int *peaks = (int *)(cut + (size_t)n * 8);
+    unsigned *hist = (unsigned *)(peaks + n), *ties = hist + (size_t)n * bins;
+    HIP_TRY(ctx, hipMemsetAsync(peaks, 0, zero_words * sizeof(unsigned), ctx->stream));
+    if (out.d_centre_counts) peaks = out.d_centre_counts; // zeroed above
+    const HoughGeom hg{cg.ah, cg.aw, 1.0f, 1.0f, 0.0f};   // the accumulator read as ah rows of aw cells
+    const int part = canny_hip_ctx::kProfCircles;
+    {
+        StageTimer tm(ctx, part + CANNY_HIP_CIRCLE_PART_VOTE);
+        HIP_TRY(ctx, launch_circles_vote(strong, bits, g, smoothed, smoothed_u8, d_gx, d_gy, cg, accum, ctx->stream));
+    }
+    {
+        StageTimer tm(ctx, part + CANNY_HIP_CIRCLE_PART_CENTRES);
+        HIP_TRY(ctx, launch_hough_peaks(accum, n, hg, a.threshold, peaks, hist, bins, ctx->stream));
+        HIP_TRY(ctx, launch_hough_select(accum, n, hg, a.threshold, cm, peaks, hist, bins, ties, cut, cand, nullptr, votes,
+                                         bases, ctx->stream));
+    }
+    {
+        StageTimer tm(ctx, part + CANNY_HIP_CIRCLE_PART_RADIUS);
+        HIP_TRY(ctx, launch_circles_radius(strong, bits, g, cg, bases, peaks, cm, radius, support, ctx->stream));
+    }
+    {
+        StageTimer tm(ctx, part + CANNY_HIP_CIRCLE_PART_ACCEPT);
+        HIP_TRY(ctx, launch_circles_accept(g, cg, bases, votes, radius, support, peaks, cm, a.support_threshold, a.min_dist,
+                                           out.d_circles, out.d_counts, ctx->stream));
+    }
+    return CANNY_HIP_OK;
+}
+
 // ---- Hough line segments (canny_hough_segments.hip) ---------------------
 struct SegArgs {
     int min_length, max_gap, exclusive, segments_max;
@@ -1708,6 +1823,8 @@ void canny_hip_ctx_destroy(canny_hip_ctx *ctx)
     ctx->seg_ws.release();
     ctx->seg_lines.release();
     ctx->seg_work.release();
+    ctx->circ_accum.release();
+    ctx->circ_ws.release();
     ctx->cc_parent.release();
     ctx->cc_ws.release();
     ctx->ct_ws.release();
@@ -3776,6 +3893,198 @@ int canny_hip_contours_profile_get(canny_hip_ctx *ctx, int part, double *total_m
     if ((rc = profile_collect(ctx))) return rc;
     *total_ms = ctx->total_ms[canny_hip_ctx::kProfContours + part];
     *launches = ctx->launches[canny_hip_ctx::kProfContours + part];
+    return CANNY_HIP_OK;
+}
+
+// ---- Hough circles ----------------------------------------------------------------------------------------
+int canny_hip_hough_circles_step_of(int gx, int gy, int *sx, int *sy)
+{
+    if (!sx || !sy || gx < -32768 || gx > 32767 || gy < -32768 || gy > 32767) return CANNY_HIP_ERR_INVALID;
+    circles_step_of(gx, gy, sx, sy);
+    return CANNY_HIP_OK;
+}
+
+int canny_hip_hough_circles_from_bits(const unsigned char *bits, const short *gx, const short *gy, int height, int width,
+                                      int min_radius, int max_radius, int cell_shift, int threshold, int support_threshold,
+                                      int min_dist, int centres_max, int *circles, int *count, int *centre_count,
+                                      int *accum)
+{
+    const CircleArgs a{min_radius, max_radius, cell_shift, threshold, support_threshold, min_dist, centres_max};
+    CircleGeom cg;
+    if (!bits || !gx || !gy) return CANNY_HIP_ERR_INVALID;
+    int rc = circles_prepare(height, width, a, count, cg);
+    if (rc) return rc;
+    if ((rc = check_dims(height, width, 1))) return rc;
+    const int c = 1 << cell_shift, stride = cg.aw + 2, row_bytes = (width + 7) / 8;
+    std::vector<int> acc((size_t)(cg.ah + 2) * stride, 0);
+    std::vector<int> px, py; // the set pixels, in raster order
+    for (int y = 0; y < height; y++)
+        for (int x = 0; x < width; x++) {
+            if (!(bits[(size_t)y * row_bytes + (x >> 3)] >> (7 - (x & 7)) & 1)) continue;
+            px.push_back(x);
+            py.push_back(y);
+            int sx, sy;
+            circles_step_of(gx[(size_t)y * width + x], gy[(size_t)y * width + x], &sx, &sy);
+            if (!sx && !sy) continue;
+            for (int s = 1; s >= -1; s -= 2)
+                for (int k = min_radius; k <= max_radius; k++) {
+                    const long long X = (long long)x * 1024 + (long long)s * k * sx, Y = (long long)y * 1024 + (long long)s * k * sy;
+                    const long long qx = X >> 10, qy = Y >> 10;
+                    if (qx < 0 || qx >= width || qy < 0 || qy >= height) break; // the frame is convex
+                    acc[(size_t)((qy >> cell_shift) + 1) * stride + (qx >> cell_shift) + 1] += 1;
+                }
+        }
+    std::vector<std::pair<int, unsigned>> peaks; // (-votes, base): ascending = votes descending, base ascending
+    for (int ay = 0; ay < cg.ah; ay++)
+        for (int ax = 0; ax < cg.aw; ax++) {
+            const size_t b = (size_t)(ay + 1) * stride + ax + 1;
+            const int v = acc[b];
+            if (v > threshold && v > acc[b - 1] && v >= acc[b + 1] && v > acc[b - stride] && v >= acc[b + stride])
+                peaks.emplace_back(-v, (unsigned)b);
+        }
+    std::sort(peaks.begin(), peaks.end());
+    const int K = (int)std::min<size_t>((size_t)centres_max, peaks.size());
+    const int nr = max_radius - min_radius + 1;
+    std::vector<long long> hist((size_t)nr);
+    std::vector<int> ax2, ay2; // accepted centres
+    int n_acc = 0;
+    const unsigned long long md = 2ull * (unsigned long long)min_dist;
+    for (int k = 0; k < K; k++) {
+        const unsigned base = peaks[k].second;
+        const long long x2 = (2ll * ((int)(base % (unsigned)stride) - 1) + 1) * c;
+        const long long y2 = (2ll * ((int)(base / (unsigned)stride) - 1) + 1) * c;
+        std::fill(hist.begin(), hist.end(), 0);
+        for (size_t i = 0; i < px.size(); i++) {
+            const long long dx = 2ll * px[i] - x2, dy = 2ll * py[i] - y2, d = dx * dx + dy * dy;
+            long long s = (long long)std::sqrt((double)d); // floor of the root, corrected
+            while (s * s > d) s--;
+            while ((s + 1) * (s + 1) <= d) s++;
+            const long long r = (s + 1) >> 1; // (2r - 1)^2 <= d < (2r + 1)^2
+            if (r >= min_radius && r <= max_radius) hist[(size_t)(r - min_radius)]++;
+        }
+        int best = min_radius;
+        for (int r = min_radius + 1; r <= max_radius; r++) // count[r] / r > count[best] / best; products below 2^41
+            if (hist[(size_t)(r - min_radius)] * best > hist[(size_t)(best - min_radius)] * r) best = r;
+        const long long support = hist[(size_t)(best - min_radius)];
+        if (support <= support_threshold) continue;
+        bool near = false;
+        for (size_t j = 0; j < ax2.size() && !near; j++) {
+            const long long dx = x2 - ax2[j], dy = y2 - ay2[j];
+            near = (unsigned long long)(dx * dx) + (unsigned long long)(dy * dy) < md * md;
+        }
+        if (near) continue;
+        ax2.push_back((int)x2);
+        ay2.push_back((int)y2);
+        if (circles) {
+            int *rec = circles + (size_t)n_acc * kCircleRecord;
+            rec[0] = (int)x2, rec[1] = (int)y2, rec[2] = best, rec[3] = -peaks[k].first, rec[4] = (int)support;
+            rec[5] = (int)base;
+        }
+        n_acc++;
+    }
+    if (accum) std::memcpy(accum, acc.data(), acc.size() * sizeof(int));
+    if (centre_count) *centre_count = (int)std::min<size_t>(peaks.size(), 0x7fffffff);
+    *count = n_acc;
+    return CANNY_HIP_OK;
+}
+
+int canny_hip_dev_hough_circles_bits(canny_hip_ctx *ctx, const unsigned char *d_bits, const short *d_gx, const short *d_gy,
+                                     int n_frames, int height, int width, int min_radius, int max_radius, int cell_shift,
+                                     int threshold, int support_threshold, int min_dist, int centres_max, int *d_circles,
+                                     int *d_counts, int *d_centre_counts, int *d_accum)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!d_bits || !d_gx || !d_gy) return CANNY_HIP_ERR_INVALID;
+    const CircleArgs a{min_radius, max_radius, cell_shift, threshold, support_threshold, min_dist, centres_max};
+    CircleGeom cg;
+    if ((rc = circles_prepare(height, width, a, d_counts, cg)) || (rc = check_dims(height, width, n_frames)) ||
+        (rc = finish_pending(ctx)))
+        return rc;
+    return dev_circles(ctx, nullptr, d_bits, make_hyst_geom(height, width, n_frames), nullptr, false, d_gx, d_gy, cg, a,
+                       CircleOut{d_circles, d_counts, d_centre_counts, d_accum});
+}
+
+int canny_hip_dev_canny_hough_circles(canny_hip_ctx *ctx, const unsigned char *d_img, float sigma, int min_val, int max_val,
+                                      int height, int width, int n_frames, short *d_edges, int min_radius, int max_radius,
+                                      int cell_shift, int threshold, int support_threshold, int min_dist, int centres_max,
+                                      int *d_circles, int *d_counts, int *d_centre_counts, int *d_accum)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!d_img) return CANNY_HIP_ERR_INVALID;
+    const CircleArgs a{min_radius, max_radius, cell_shift, threshold, support_threshold, min_dist, centres_max};
+    CircleGeom cg;
+    if ((rc = circles_prepare(height, width, a, d_counts, cg)) || (rc = check_dims(height, width, n_frames))) return rc;
+    if (!d_edges) {
+        HIP_TRY(ctx, ctx->edges16.ensure(npx(height, width, n_frames) * sizeof(short)));
+        d_edges = (short *)ctx->edges16.p;
+    }
+    if ((rc = dev_canny(ctx, d_img, sigma, min_val, max_val, height, width, n_frames, d_edges))) return rc;
+    // the transform follows the MAP: max_val > 255 zeroes every reached pixel although strong bits are set.  Every route of
+    // dev_canny leaves the whole batch's smoothed plane in ctx->smoothed, as bytes iff last_canny_u8.
+    const uint64_t *strong = max_val > 255 ? nullptr : (const uint64_t *)ctx->plane_s.p;
+    return dev_circles(ctx, strong, nullptr, make_hyst_geom(height, width, n_frames), ctx->smoothed.p,
+                       ctx->last_canny_u8 != 0, nullptr, nullptr, cg, a,
+                       CircleOut{d_circles, d_counts, d_centre_counts, d_accum});
+}
+
+int canny_hip_canny_hough_circles(canny_hip_ctx *ctx, const unsigned char *imgs, int n_frames, float sigma, int min_val,
+                                  int max_val, int height, int width, int min_radius, int max_radius, int cell_shift,
+                                  int threshold, int support_threshold, int min_dist, int centres_max, int *circles,
+                                  int *counts, int *centre_counts)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!imgs) return CANNY_HIP_ERR_INVALID;
+    {
+        const CircleArgs a{min_radius, max_radius, cell_shift, threshold, support_threshold, min_dist, centres_max};
+        CircleGeom cg;
+        if ((rc = circles_prepare(height, width, a, counts, cg)) || (rc = check_dims(height, width, n_frames))) return rc;
+    }
+    const size_t slots = (size_t)n_frames * centres_max;
+    // one staging block: records (6 ints per slot) | counts | centre counts
+    HIP_TRY(ctx, ctx->io[1].ensure((slots * kCircleRecord + 2 * (size_t)n_frames) * sizeof(int)));
+    int *d_rec = (int *)ctx->io[1].p, *d_cnt = d_rec + slots * kCircleRecord;
+    if ((rc = h2d(ctx, ctx->io[0], imgs, npx(height, width, n_frames)))) return rc;
+    if ((rc = canny_hip_dev_canny_hough_circles(ctx, (const unsigned char *)ctx->io[0].p, sigma, min_val, max_val, height,
+                                                width, n_frames, nullptr, min_radius, max_radius, cell_shift, threshold,
+                                                support_threshold, min_dist, centres_max, circles ? d_rec : nullptr, d_cnt,
+                                                d_cnt + n_frames, nullptr)))
+        return rc;
+    std::vector<int> cnt(2 * (size_t)n_frames);
+    if ((rc = d2h_sync(ctx, cnt.data(), d_cnt, cnt.size() * sizeof(int)))) return rc;
+    // only the circles come down: the filled slots of each frame
+    for (int f = 0; circles && f < n_frames; f++) {
+        const size_t k = (size_t)cnt[f], at = (size_t)f * centres_max * kCircleRecord;
+        if (k) HIP_TRY(ctx, hipMemcpyAsync(circles + at, d_rec + at, k * kCircleRecord * sizeof(int), hipMemcpyDeviceToHost,
+                                          ctx->stream));
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    std::memcpy(counts, cnt.data(), (size_t)n_frames * sizeof(int));
+    if (centre_counts) std::memcpy(centre_counts, cnt.data() + n_frames, (size_t)n_frames * sizeof(int));
+    return CANNY_HIP_OK;
+}
+
+int canny_hip_dev_hough_circles_steps(canny_hip_ctx *ctx, const short *d_gx, const short *d_gy, size_t n, int *d_sx,
+                                      int *d_sy)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!d_gx || !d_gy || !d_sx || !d_sy || !n) return CANNY_HIP_ERR_INVALID;
+    if ((rc = finish_pending(ctx))) return rc;
+    HIP_TRY(ctx, launch_circles_steps(d_gx, d_gy, n, d_sx, d_sy, ctx->stream));
+    return CANNY_HIP_OK;
+}
+
+int canny_hip_hough_circles_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches)
+{
+    if (part < 0 || part >= CANNY_HIP_CIRCLE_PARTS || !total_ms || !launches) return CANNY_HIP_ERR_INVALID;
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if ((rc = profile_collect(ctx))) return rc;
+    *total_ms = ctx->total_ms[canny_hip_ctx::kProfCircles + part];
+    *launches = ctx->launches[canny_hip_ctx::kProfCircles + part];
     return CANNY_HIP_OK;
 }
 

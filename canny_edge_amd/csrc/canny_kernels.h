@@ -384,6 +384,38 @@ hipError_t launch_hough_select(const int *accum, int n_frames, const HoughGeom &
                                const int *counts, const unsigned *hist, int hist_bins, unsigned *ties, unsigned *cut,
                                unsigned long long *cand, float *lines, int *votes, unsigned *bases, hipStream_t stream);
 
+// ---- Hough circles (canny_hough_circles.hip) ---------------------------
+// The accumulator of a frame is (ah + 2) x (aw + 2) ints with a zero border, cells of 1 << cell_shift pixels: the shape
+// convention of the line accumulator with ah for numangle and aw for numrho, so launch_hough_peaks / launch_hough_select
+// find the candidate centres in it unchanged.
+struct CircleGeom {
+    int min_radius, max_radius, cell_shift, aw, ah;
+};
+constexpr int kCircleMaxRadius = 1024; // CANNY_HIP_CIRCLES_MAX_RADIUS: a radius window's squared distances stay below 2^24
+constexpr int kCircleRecord = 6;       // CANNY_HIP_CIRCLE_INTS: x2, y2, radius, votes, support, base
+inline size_t circles_accum_bytes(const CircleGeom &cg, int n_frames)
+{
+    return (size_t)n_frames * (cg.ah + 2) * (size_t)(cg.aw + 2) * sizeof(int);
+}
+// vote: zeroes the accumulators, then every set pixel with a non-zero gradient votes along both rays.  Source: bits (packed,
+// as for the point lists) with the caller's gx / gy planes (n_frames * height * width shorts each), or else the strong plane
+// with the batch's smoothed plane (bytes if smoothed_u8, else shorts), whose Sobel pair is recomputed at the set pixels.
+hipError_t launch_circles_vote(const uint64_t *strong, const uint8_t *bits, const HystGeom &g, const void *smoothed,
+                               bool smoothed_u8, const int16_t *gx, const int16_t *gy, const CircleGeom &cg, int *accum,
+                               hipStream_t stream);
+// The step arithmetic of the vote kernel alone on n pairs (the exhaustive test's hook).
+hipError_t launch_circles_steps(const int16_t *gx, const int16_t *gy, size_t n, int *sx, int *sy, hipStream_t stream);
+// radius: candidate k of frame f is cell bases[f * centres_max + k], k < min(centres_max, peak_counts[f]) (as
+// launch_hough_select leaves them); radius / support receive its best-supported radius and that radius's pixel count.
+hipError_t launch_circles_radius(const uint64_t *strong, const uint8_t *bits, const HystGeom &g, const CircleGeom &cg,
+                                 const unsigned *bases, const int *peak_counts, int centres_max, int *radius, int *support,
+                                 hipStream_t stream);
+// accept: the candidates in order; a valid one (support > support_threshold) is accepted unless an accepted one lies within
+// min_dist pixels.  circles (may be null) receives the 6-int records compactly from slot f * centres_max, counts[f] their number.
+hipError_t launch_circles_accept(const HystGeom &g, const CircleGeom &cg, const unsigned *bases, const int *votes,
+                                 const int *radius, const int *support, const int *peak_counts, int centres_max,
+                                 int support_threshold, int min_dist, int *circles, int *counts, hipStream_t stream);
+
 // ---- Hough line segments (canny_hough_segments.hip) --------------------
 // Runs of edge pixels along detected lines.  The line list of frame f is bases[f * lines_max .. + min(lines_max,
 // line_counts[f])), as launch_hough_select leaves it; tab as for the vote.  halfwin: half width of the minor-axis window a

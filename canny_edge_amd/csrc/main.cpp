@@ -1,6 +1,7 @@
 // main.cpp -- the reference's command line (StevenChang5/Canny_Edge src/main.cpp:18-142) without
 // the webcam and the GUI:  ./Main sigma minVal maxVal [-c] [-s] [-i in.pgm|in.ppm|in.jpg] [-o dir] [-p] [-n WxH] [-b dir]
 //        [-l rho,theta_degrees,threshold[,lines_max]] [-g min_length,max_gap[,exclusive]] [-m min_area] [-t] [-d]
+//        [-r min_radius,max_radius,threshold,support[,min_dist[,cell_shift]]]
 //
 // Kept from the reference: the three positionals may appear anywhere relative to the flags
 // (src/main.cpp:29-46); exactly three are required, otherwise the usage text is printed and the
@@ -27,6 +28,10 @@
 // Added: -d runs the exact Euclidean distance transform of the frame's edge map on the GPU (canny_hip_canny_edt) and writes
 // canny_dist.pgm (.png with -p) to the -o directory (the current one without -o): one byte per pixel,
 // min(255, floor(sqrt(dist2))), 255 everywhere for a map without edge pixels.  Without -d nothing changes.
+// Added: -r min_radius,max_radius,threshold,support[,min_dist[,cell_shift]] detects the circles of the frame's edge map on the
+// GPU (canny_hip_canny_hough_circles) and writes one "frame x y radius votes support" row per circle, in candidate order,
+// to canny_circles.txt in the -o directory (stdout without -o); x and y are the centre in pixels (multiples of 0.5).  A
+// malformed -r is a usage error (exit 2).  Without -r nothing changes.
 #include <algorithm>
 #include <cctype>
 #include <cmath>
@@ -408,6 +413,37 @@ static int run_edt(const vector<unsigned char> &frame, int height, int width, fl
     return 0;
 }
 
+// -r: the circles of the frame's edge map, "frame x y radius votes support" per circle
+static int run_circles(const vector<unsigned char> &frame, int height, int width, float sigma, int minVal, int maxVal,
+                       const int *r, const string &outdir)
+{
+    const int centres_max = 256;
+    vector<int> rec((size_t)centres_max * CANNY_HIP_CIRCLE_INTS);
+    int count = 0;
+    canny_hip_ctx *ctx = nullptr;
+    int st = canny_hip_ctx_create(&ctx, 0);
+    if (!st)
+        st = canny_hip_canny_hough_circles(ctx, frame.data(), 1, sigma, minVal, maxVal, height, width, r[0], r[1], r[5], r[2],
+                                           r[3], r[4], centres_max, rec.data(), &count, nullptr);
+    if (st) {
+        fprintf(stderr, "ERROR: -r: %s\n", st == CANNY_HIP_ERR_RUNTIME && ctx ? canny_hip_last_error(ctx) : canny_hip_status_string(st));
+        if (ctx) canny_hip_ctx_destroy(ctx);
+        return 1;
+    }
+    canny_hip_ctx_destroy(ctx);
+    FILE *f = outdir.empty() ? stdout : fopen((outdir + "/canny_circles.txt").c_str(), "w");
+    if (!f) {
+        fprintf(stderr, "ERROR: cannot write %s/canny_circles.txt\n", outdir.c_str());
+        return 1;
+    }
+    for (int j = 0; j < count; j++) {
+        const int *c = rec.data() + (size_t)j * CANNY_HIP_CIRCLE_INTS;
+        fprintf(f, "0 %.1f %.1f %d %d %d\n", c[0] * 0.5, c[1] * 0.5, c[2], c[3], c[4]);
+    }
+    if (f != stdout) fclose(f);
+    return 0;
+}
+
 int main(int argc, char *argv[])
 {
     // The batch pipeline wants its upload, compute and download streams on separate hardware queues; HIP reads this
@@ -428,6 +464,8 @@ int main(int argc, char *argv[])
     int min_area = 1;
     bool want_dist = false;
     bool want_contours = false;
+    bool want_circles = false;
+    int circle_args[6] = {0, 0, 0, 0, 0, 0}; // min_radius, max_radius, threshold, support, min_dist, cell_shift
     int width = WIDTH, height = HEIGHT;
     vector<string> values;
 
@@ -464,6 +502,25 @@ int main(int argc, char *argv[])
                 exit(0);
             }
             want_components = true;
+        } else if (arg == "-r" && i + 1 < argc) {
+            int *c = circle_args;
+            int got = 0; // whole comma-separated integers only: nothing empty, nothing behind the last one
+            bool clean = true;
+            for (const char *p = argv[++i]; clean; got++) {
+                char *end = nullptr;
+                const long v = strtol(p, &end, 10);
+                clean = end != p && got < 6 && v >= -0x7fffffffL && v <= 0x7fffffffL;
+                if (clean) c[got] = (int)v;
+                if (!clean || *end == '\0') break;
+                clean = *end == ',';
+                p = end + 1;
+            }
+            got = clean ? got + 1 : 0;
+            if (got < 4 || got > 6 || c[0] < 1 || c[1] < c[0] || c[4] < 0 || c[5] < 0 || c[5] > 3) {
+                fprintf(stderr, "ERROR: -r expects min_radius,max_radius,threshold,support[,min_dist[,cell_shift]]\n");
+                exit(2);
+            }
+            want_circles = true;
         } else if (arg == "-d") {
             want_dist = true;
         } else if (arg == "-t") {
@@ -499,6 +556,8 @@ int main(int argc, char *argv[])
         fprintf(stderr, "                canny_kept.pgm in the -o dir\n");
         fprintf(stderr, "   -t: outer contour chain of every component with at least min_area (-m, default 1) pixels, one\n");
         fprintf(stderr, "       \"label n x0 y0 x1 y1 ...\" line each -> canny_contours.txt in the -o dir\n");
+        fprintf(stderr, "   -r min_radius,max_radius,threshold,support[,min_dist[,cell_shift]]: circles of the edge map, one\n");
+        fprintf(stderr, "       \"frame x y radius votes support\" line each -> canny_circles.txt in the -o dir\n");
         fprintf(stderr, "   -d: distance of every pixel to the nearest edge pixel, min(255, floor) -> canny_dist.pgm in the -o dir\n");
         exit(0);
     }
@@ -563,6 +622,10 @@ int main(int argc, char *argv[])
     }
     if (want_dist) {
         const int rc = run_edt(frame, height, width, sigma, minVal, maxVal, outdir);
+        if (rc) return rc;
+    }
+    if (want_circles) {
+        const int rc = run_circles(frame, height, width, sigma, minVal, maxVal, circle_args, outdir);
         if (rc) return rc;
     }
     if (want_lines && want_segments)

@@ -52,7 +52,8 @@
 extern "C" {
 #endif
 
-#define CANNY_HIP_VERSION 1000       /* 0.10.0: + outer contour chains of the finished map, traced on the GPU */
+#define CANNY_HIP_VERSION 1100       /* 0.11.0: + Hough circles: gradient rays, centre peaks, radius by support */
+/* 0.10.0: + outer contour chains of the finished map, traced on the GPU */
 /* 0.9.1: + canny_hip_selftest_histogram, canny_hip_selftest_select */
 /* 0.9.0: + Hough line segments: runs of edge pixels along each detected line */
 /* 0.8.0: + exact Euclidean distance transform of the finished map: dist2, dist, nearest */
@@ -491,9 +492,9 @@ int canny_hip_points_from_bits(const unsigned char *bits, int height, int width,
  *   40960: every frame up to 8K at rho >= 0.6); beyond that 0 takes the global form and 2 is CANNY_HIP_ERR_UNSUPPORTED.  Same
  *   bytes either way.  "tune_hough_lds_kb": LDS budget of a vote workgroup in KiB (0 = automatic, 48), for A/B.
  * The three parts are timed by canny_hip_hough_profile_get (0 vote, 1 peaks, 2 select + sort).
- * Segment output (cv::HoughLinesP's use) is the next section.
- * Not covered -- follow-ups: multi-scale srn / stn, weighted votes, circles, the three-stream batch pipeline, the multi-GPU
- * sharder, colour and automatic-threshold variants. */
+ * Segment output (cv::HoughLinesP's use) is the next section, circles the one after it.
+ * Not covered -- follow-ups: multi-scale srn / stn, weighted votes, the three-stream batch pipeline, the multi-GPU sharder,
+ * colour and automatic-threshold variants. */
 #define CANNY_HIP_HOUGH_MAX_LINES 4096 /* largest lines_max: the 64-bit sort keys of one frame fit in LDS */
 /* Host-only, no device needed. */
 int canny_hip_hough_geometry(int height, int width, float rho, float theta, float min_theta, float max_theta,
@@ -607,6 +608,96 @@ int canny_hip_canny_hough_segments(canny_hip_ctx *ctx, const unsigned char *imgs
                                    int lines_max, float min_theta, float max_theta, int min_length, int max_gap,
                                    int exclusive, float *lines, int *votes, unsigned int *bases, int *line_counts,
                                    int *segments, int segments_max, int *seg_counts);
+
+/* ---- Hough circles -------------------------------------------------------------------------------------------------------
+ * Circle detection on a finished edge map, per frame of a batch, on the GPU, in stream order, with no host round trip:
+ * cv::HoughCircles(HOUGH_GRADIENT) semantics, i.e. OpenCV's HoughCirclesGradient with its build-dependent and sequential-float
+ * parts replaced by integer arithmetic, so that a few lines of numpy (tests/hough_circles_rule.py) reproduce every accumulator
+ * cell and every returned record byte for byte.  THE RULE:
+ * All float arithmetic is IEEE binary32, round to nearest even, not contracted.
+ * Arguments: 1 <= min_radius <= max_radius <= CANNY_HIP_CIRCLES_MAX_RADIUS; cell_shift in 0..3 (an accumulator cell is
+ *     c = 1 << cell_shift pixels wide: OpenCV's dp = c); threshold (int, centre votes); support_threshold (int, pixels on the
+ *     circle); min_dist (int >= 0 pixels, 0 disables it); centres_max in 1..CANNY_HIP_HOUGH_MAX_LINES.
+ *   Gradient: (gx, gy) at a pixel is the 3x3 Sobel pair of the reference (calculateXYGradient, src/utils.cpp:106-187: gx clamps
+ *     columns and drops rows outside the frame, gy clamps rows and drops columns).  The canny forms take it on the smoothed plane
+ *     of that call; the bit-map forms read it from two caller-supplied s16 planes.
+ *   Step: m = sqrt((float)(unsigned)(gx * gx + gy * gy)) -- the sum in unsigned 32-bit (it cannot overflow for s16 inputs), the
+ *     conversion and the root each rounded once; sx = (int)rint_half_even((float)(gx * 1024) / m) (gx * 1024 is exact in
+ *     binary32 for every s16 gx), sy likewise.  A pixel with gx = gy = 0 casts no vote.  canny_hip_hough_circles_step_of
+ *     returns the pair.
+ *   Votes: aw = ceil(width / c), ah = ceil(height / c); accum is int, (ah + 2) x (aw + 2), its border row / column zero (the
+ *     shape convention of the line accumulator with ah for numangle, aw for numrho).  For every set pixel (y, x) = (row, column)
+ *     with a non-zero gradient, every sign s in {+1, -1} and every k in min_radius .. max_radius:
+ *       X = x * 1024 + s * k * sx, Y = y * 1024 + s * k * sy; px = X >> 10, py = Y >> 10 (arithmetic shift: floor);
+ *       if 0 <= px < width and 0 <= py < height: accum[((py >> cell_shift) + 1) * (aw + 2) + (px >> cell_shift) + 1] += 1.
+ *   Centres: the five-way peak rule and the order of the Hough lines apply unchanged: cell base = (ay + 1) * (aw + 2) + ax + 1 is
+ *     a peak iff a[base] > threshold && a[base] > a[base - 1] && a[base] >= a[base + 1] && a[base] > a[base - (aw + 2)] &&
+ *     a[base] >= a[base + (aw + 2)]; peaks sorted by (votes descending, base ascending); the first K = min(centres_max,
+ *     n_peaks) are the candidates.  A candidate's centre in DOUBLED pixel coordinates is x2 = (2 * ax + 1) * c,
+ *     y2 = (2 * ay + 1) * c: OpenCV's (ax + 0.5) * dp, kept as an integer.
+ *   Radius: every set pixel (y, x) of the map (zero-gradient ones included, as in OpenCV) has d = (2x - x2)^2 + (2y - y2)^2 and
+ *     falls into radius bin r, the integer with (2r - 1)^2 <= d < (2r + 1)^2.  Among the bins min_radius .. max_radius the
+ *     candidate's radius is the one with the largest count[r] / r, compared in integers (count[q] * r > count[r] * q), the
+ *     smaller r on a tie; support = count[radius].  A candidate is VALID iff support > support_threshold.
+ *   Acceptance: the candidates in order; a valid one is accepted iff no earlier ACCEPTED one has
+ *     (dx2)^2 + (dy2)^2 < (2 * min_dist)^2.
+ *   Output: frame f writes its accepted circles to slots f * centres_max + j of circles, compactly and in candidate order,
+ *     CANNY_HIP_CIRCLE_INTS = 6 ints each: x2, y2, radius, votes, support, base.  counts[f] = the number accepted -- always the
+ *     true count, it cannot exceed centres_max; centre_counts[f] = the true n_peaks.  Later slots are not written.
+ * The output is the same bytes on every run (integer adds commute; the order comes from a sort on a total order; the acceptance
+ * pass is a defined sequence).  circles, centre_counts and accum may be NULL; counts (n_frames ints) is mandatory.  d_accum, if
+ * given, receives n_frames accumulators of (ah + 2) * (aw + 2) ints, border included; otherwise they live in a context
+ * workspace of that size, freed with the context.
+ * Statuses: a bad radius range (min_radius < 1 or > max_radius), cell_shift outside 0..3, centres_max < 1, min_dist < 0, a NULL
+ * counts, NULL gradient planes in the bit-map forms, height < 2 or width < 2 -> CANNY_HIP_ERR_INVALID; max_radius >
+ * CANNY_HIP_CIRCLES_MAX_RADIUS, centres_max > CANNY_HIP_HOUGH_MAX_LINES, an accumulator of 2^31 cells or more (and a bound
+ * on a cell's votes, DESIGN.md section 18, above 2^26: only max_radius > 797 with cell_shift 3 on a frame larger than
+ * 1606 x 1606) -> CANNY_HIP_ERR_UNSUPPORTED; nothing is written in either case.  max_val > 255 follows the MAP: all counts 0.
+ * The four parts are timed by canny_hip_hough_circles_profile_get (CANNY_HIP_CIRCLE_PART_*); with "profile_stage_mask" they
+ *   are bits 26 .. 29.
+ * Not covered -- follow-ups: an accumulator-tile vote in LDS, HOUGH_GRADIENT_ALT, sub-cell centre refinement, several radii per
+ * centre, the three-stream batch pipeline, the multi-GPU sharder, colour and per-frame / automatic-threshold variants. */
+#define CANNY_HIP_CIRCLES_MAX_RADIUS 1024
+#define CANNY_HIP_CIRCLE_INTS 6
+enum canny_hip_circle_part {
+    CANNY_HIP_CIRCLE_PART_VOTE = 0,     /* accumulators zeroed; set pixels queued in LDS, Sobel pair, step, ray votes */
+    CANNY_HIP_CIRCLE_PART_CENTRES = 1,  /* peaks, cut-off, ties, collect, sort: the candidates in order */
+    CANNY_HIP_CIRCLE_PART_RADIUS = 2,   /* per candidate: radius histogram of its window of the map, best radius, support */
+    CANNY_HIP_CIRCLE_PART_ACCEPT = 3,   /* per frame: validity, minimum distance, records and counts */
+    CANNY_HIP_CIRCLE_PARTS = 4
+};
+/* Host-only, no device needed: the step of one gradient (s16 range), as the device computes it. */
+int canny_hip_hough_circles_step_of(int gx, int gy, int *sx, int *sy);
+/* Host-only, needs no device: the same rule on ONE host bit map (layout of canny_hip_canny_batch_bits) and its two gradient
+ * planes (height * width shorts each), in plain C++.  circles (centres_max * 6 ints; only the accepted records are written),
+ * centre_count and accum ((ah + 2) * (aw + 2) ints) may be NULL. */
+int canny_hip_hough_circles_from_bits(const unsigned char *bits, const short *gx, const short *gy, int height, int width,
+                                      int min_radius, int max_radius, int cell_shift, int threshold, int support_threshold,
+                                      int min_dist, int centres_max, int *circles, int *count, int *centre_count,
+                                      int *accum);
+/* From packed bit maps in the layout of canny_hip_dev_canny_bits (padding bits ignored) and full gradient planes d_gx, d_gy
+ * (n_frames * height * width shorts each).  Asynchronous. */
+int canny_hip_dev_hough_circles_bits(canny_hip_ctx *ctx, const unsigned char *d_bits, const short *d_gx, const short *d_gy,
+                                     int n_frames, int height, int width, int min_radius, int max_radius, int cell_shift,
+                                     int threshold, int support_threshold, int min_dist, int centres_max, int *d_circles,
+                                     int *d_counts, int *d_centre_counts, int *d_accum);
+/* canny_hip_dev_canny unchanged (d_edges as in canny_hip_dev_canny_points: the s16 map, or NULL), then the transform queued
+ * behind it on the same stream: the map is read from the converged hysteresis bit-plane, the gradient is recomputed at the
+ * edge pixels from the smoothed plane that call left on the device (bytes or shorts, whichever it ran with).  Completion
+ * contract and statuses as canny_hip_dev_canny_points; the result follows the MAP (max_val > 255: all counts 0). */
+int canny_hip_dev_canny_hough_circles(canny_hip_ctx *ctx, const unsigned char *d_img, float sigma, int min_val, int max_val,
+                                      int height, int width, int n_frames, short *d_edges, int min_radius, int max_radius,
+                                      int cell_shift, int threshold, int support_threshold, int min_dist, int centres_max,
+                                      int *d_circles, int *d_counts, int *d_centre_counts, int *d_accum);
+/* Host buffers, synchronous: upload, canny, transform; the counts come down, then only the filled slots of each frame. */
+int canny_hip_canny_hough_circles(canny_hip_ctx *ctx, const unsigned char *imgs, int n_frames, float sigma, int min_val,
+                                  int max_val, int height, int width, int min_radius, int max_radius, int cell_shift,
+                                  int threshold, int support_threshold, int min_dist, int centres_max, int *circles,
+                                  int *counts, int *centre_counts);
+/* The device's step arithmetic alone on n gradient pairs (device arrays; d_sx, d_sy receive n ints each): the hook of the
+ * exhaustive test, which runs every pair of the Sobel domain through it.  Asynchronous. */
+int canny_hip_dev_hough_circles_steps(canny_hip_ctx *ctx, const short *d_gx, const short *d_gy, size_t n, int *d_sx,
+                                      int *d_sy);
 
 /* ---- connected components ------------------------------------------------------------------------------------------------
  * Eight-connected component labelling of the finished edge map, per frame of a batch, on the GPU, queued behind the detector
@@ -838,6 +929,8 @@ int canny_hip_hough_segments_profile_get(canny_hip_ctx *ctx, int part, double *t
 
 /* ... and for the four parts of the contour chains (CANNY_HIP_CONTOUR_PART_*). */
 int canny_hip_contours_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches);
+/* ... and for the four parts of the Hough circles (CANNY_HIP_CIRCLE_PART_*). */
+int canny_hip_hough_circles_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches);
 
 /* ---- self-test hooks used by the GPU test-suite -------------------------------------------- */
 /* Runs the DEVICE magnitude / angle-bin functions over every (gx,gy) in [-lim,lim]^2 and writes
