@@ -106,6 +106,8 @@ EXPORTS = (
     "canny_hip_hough_circles_step_of", "canny_hip_hough_circles_from_bits", "canny_hip_dev_hough_circles_bits",
     "canny_hip_dev_canny_hough_circles", "canny_hip_canny_hough_circles", "canny_hip_dev_hough_circles_steps",
     "canny_hip_hough_circles_profile_get",
+    "canny_hip_dev_polygons_chains", "canny_hip_dev_canny_polygons", "canny_hip_dev_polygons_bits",
+    "canny_hip_canny_polygons", "canny_hip_polygons_from_chains", "canny_hip_polygons_profile_get",
 )
 
 _lib: Optional[C.CDLL] = None
@@ -134,6 +136,7 @@ def load() -> C.CDLL:
     L = C.CDLL(LIB_PATH)
     i, f, p, sz = C.c_int, C.c_float, C.c_void_p, C.c_size_t
     pp, ip = C.POINTER(C.c_void_p), C.POINTER(C.c_int)
+    ull = C.c_ulonglong
     sig = {
         "canny_hip_version": ([], i),
         "canny_hip_status_string": ([i], C.c_char_p),
@@ -254,6 +257,14 @@ def load() -> C.CDLL:
         "canny_hip_canny_hough_circles": ([p, p, i, f, i, i, i, i, i, i, i, i, i, i, i, p, p, p], i),
         "canny_hip_dev_hough_circles_steps": ([p, p, p, C.c_size_t, p, p], i),
         "canny_hip_hough_circles_profile_get": ([p, i, C.POINTER(C.c_double), C.POINTER(C.c_long)], i),
+        "canny_hip_dev_polygons_chains": ([p, p, i, ull, p, p, ull, i, i, C.c_uint, C.c_uint, p, p, ull, p], i),
+        "canny_hip_dev_canny_polygons": ([p, p, f, i, i, i, i, i, p, i, p, ull, p, p, p, ull, p, C.c_uint, C.c_uint, p, p,
+                                          ull, p], i),
+        "canny_hip_dev_polygons_bits": ([p, p, i, i, i, i, p, ull, p, p, p, ull, p, C.c_uint, C.c_uint, p, p, ull, p], i),
+        "canny_hip_canny_polygons": ([p, p, i, f, i, i, i, i, i, p, ull, p, p, p, ull, p, C.c_uint, C.c_uint, p, p, ull,
+                                      p], i),
+        "canny_hip_polygons_from_chains": ([p, p, ull, ull, i, i, C.c_uint, C.c_uint, p, p, ull, p], i),
+        "canny_hip_polygons_profile_get": ([p, i, C.POINTER(C.c_double), C.POINTER(C.c_long)], i),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -370,6 +381,54 @@ def contours_from_bits(bits, height: int, width: int, min_area: int = 1, want_st
         raise CannyHipError(st, "contours_from_bits")
     fit = min(cap, k.value)
     return (stats[:fit] if want_stats else None, chain[:fit + 1], points[:min(pcap, int(chain[fit]))], k.value, n.value)
+
+
+POLYGON_PARTS = ("simplify", "scan", "emit")
+POLYGON_MEASURES = ("vertices", "length_q8", "area2", "convex")
+
+
+def polygon_tolerance(epsilon: float = 0.0, ratio: float = 0.0) -> Tuple[int, int]:
+    """(epsilon_q8, ratio_q16) of a tolerance in pixels and one relative to the chain's length, by rounding."""
+    eq, rq = int(round(float(epsilon) * 256.0)), int(round(float(ratio) * 65536.0))
+    if not (0 <= eq < 2 ** 32 and 0 <= rq < 65536):
+        raise ValueError("epsilon must lie in [0, 2^24) pixels and ratio in [0, 1)")
+    return eq, rq
+
+
+def polygons_from_chains(chain_offsets, points, width: int, height: int, epsilon_q8: int = 0, ratio_q16: int = 0,
+                         point_capacity: Optional[int] = None, vertex_capacity: Optional[int] = None,
+                         want_measures: bool = True):
+    """Host-only: the polygon of every chain.  chain_offsets uint64 [k + 1] and points int32 are
+    what contours_from_bits / Context.canny_contours return.  Returns (vertex_offsets uint64 [k + 1], vertices int32,
+    measures int64 [k, 4] or None): record j's polygon is vertices[vertex_offsets[j] : vertex_offsets[j + 1]], pixel
+    indices r * width + c in chain order.  point_capacity (default: len(points)) says which chains are complete: one that
+    ends beyond it has no vertices and the measures (-1, 0, 0, 0).  With vertex_capacity given, vertices holds the
+    positions below it and vertex_offsets are still the true counts."""
+    co = np.ascontiguousarray(chain_offsets, dtype=np.uint64)
+    pts = np.ascontiguousarray(points, dtype=np.int32)
+    k = co.size - 1
+    if k < 0:
+        raise ValueError("chain_offsets needs at least one entry")
+    pcap = pts.size if point_capacity is None else int(point_capacity)
+    if pcap > pts.size:
+        raise ValueError("point_capacity exceeds the points given")
+    L = load()
+    voff = np.zeros(k + 1, np.uint64)
+    measures = np.zeros((k, 4), np.int64) if want_measures else None
+
+    def call(verts, vcap):
+        st = L.canny_hip_polygons_from_chains(_hp(co), _hp(pts) if pts.size else None, k, pcap, width, height, epsilon_q8,
+                                              ratio_q16, _hp(voff), _hp(verts) if vcap else None, vcap,
+                                              _hp(measures) if want_measures and k else None)
+        if st:
+            raise CannyHipError(st, "polygons_from_chains")
+
+    if vertex_capacity is None:
+        call(None, 0)
+    vcap = int(voff[-1]) if vertex_capacity is None else int(vertex_capacity)
+    verts = np.empty(vcap, np.int32)
+    call(verts, vcap)
+    return voff, verts[:min(vcap, int(voff[-1]))], measures
 
 
 EDT_NONE = 0x7FFFFFFF                                           # CANNY_HIP_EDT_NONE: dist2 of a frame without edge pixels
@@ -956,6 +1015,89 @@ class Context:
         ms, n = C.c_double(0.0), C.c_long(0)
         self._check(self._L.canny_hip_contours_profile_get(self._h, part, C.byref(ms), C.byref(n)),
                     "contours_profile_get")
+        return ms.value, n.value
+
+    # ---- polygon approximation of the contour chains ---------------------------------------
+    def canny_polygons(self, imgs, sigma: float, min_val: int, max_val: int, min_area: int = 1, epsilon: float = 0.0,
+                       ratio: float = 0.0, want_stats: bool = False, want_points: bool = False):
+        """canny(), the outer contour chains, then the polygon of every chain: imgs (H, W) or (N, H, W) uint8 ->
+        (polygons, measures int64 [K, 4], offsets uint64 [N + 1], extra).  polygons is a list of K int32 arrays, views into
+        one vertex array through the CSR, record j (offsets[f] <= j < offsets[f + 1] for frame f) holding its vertices as
+        pixel indices r * W + c in chain order; measures[j] = (vertices, length_q8, area2, convex).  epsilon (pixels) and
+        ratio (of the chain's length; 0.02 is the usual choice) are rounded to 1/256 and 1/65536 and add.  extra is a dict
+        with vertex_offsets, vertices, point_offsets, and stats / chain_offsets, points when asked for.  Unless
+        want_points, the chains never leave the device."""
+        eq, rq = polygon_tolerance(epsilon, ratio)
+        a = np.ascontiguousarray(imgs, dtype=np.uint8)
+        if a.ndim == 2:
+            a = a[None]
+        if a.ndim != 3:
+            raise ValueError("expected uint8 [H, W] or [n_frames, H, W]")
+        n, h, w = a.shape
+        offsets, point_offsets = np.zeros(n + 1, np.uint64), np.zeros(n + 1, np.uint64)
+        sized = self.canny_contours(a, sigma, min_val, max_val, min_area, want_stats=False, capacity=0, point_capacity=0)
+        cap, pcap = int(sized[1][-1]), int(sized[4][-1])
+        stats = np.empty((cap, CC_STATS), np.int32) if want_stats else None
+        chain = np.zeros(cap + 1, np.uint64)
+        points = np.empty(pcap, np.int32) if want_points else None
+        voff = np.zeros(cap + 1, np.uint64)
+        verts = np.empty(pcap, np.int32)   # a polygon has no more vertices than its chain has points
+        measures = np.zeros((cap, 4), np.int64)
+        self._check(self._L.canny_hip_canny_polygons(
+            self._h, _hp(a), n, sigma, min_val, max_val, h, w, min_area, _hp(stats) if want_stats and cap else None, cap,
+            _hp(offsets), _hp(chain), _hp(points) if want_points and pcap else None, pcap, _hp(point_offsets), eq, rq,
+            _hp(voff), _hp(verts) if pcap else None, pcap, _hp(measures) if cap else None), "canny_polygons")
+        verts = verts[:int(voff[-1])]
+        polygons = [verts[int(voff[j]):int(voff[j + 1])] for j in range(cap)]
+        extra = dict(vertex_offsets=voff, vertices=verts, point_offsets=point_offsets, chain_offsets=chain)
+        if want_stats:
+            extra["stats"] = stats
+        if want_points:
+            extra["points"] = points
+        return polygons, measures, offsets, extra
+
+    def dev_polygons_chains(self, d_offsets: int, n: int, capacity: int, d_chain_offsets: int, d_points: int,
+                            point_capacity: int, w: int, h: int, epsilon_q8: int, ratio_q16: int, d_vertex_offsets: int,
+                            d_vertices: int, vertex_capacity: int, d_measures: int = 0):
+        """The polygon stage alone on chains a contours call left on the device: d_vertex_offsets (capacity + 1 uint64),
+        d_vertices (vertex_capacity int32) or 0 with vertex_capacity 0, d_measures (capacity x 4 int64) or 0."""
+        v = C.c_void_p
+        self._check(self._L.canny_hip_dev_polygons_chains(self._h, v(d_offsets or None), n, capacity,
+                                                          v(d_chain_offsets or None), v(d_points or None), point_capacity,
+                                                          w, h, epsilon_q8, ratio_q16, v(d_vertex_offsets or None),
+                                                          v(d_vertices or None), vertex_capacity, v(d_measures or None)),
+                    "dev_polygons_chains")
+
+    def dev_canny_polygons(self, d_img: int, sigma: float, min_val: int, max_val: int, h: int, w: int, n: int,
+                           min_area: int, d_stats: int, capacity: int, d_offsets: int, d_chain_offsets: int, d_points: int,
+                           point_capacity: int, d_point_offsets: int, epsilon_q8: int, ratio_q16: int,
+                           d_vertex_offsets: int, d_vertices: int, vertex_capacity: int, d_measures: int = 0,
+                           d_edges: int = 0):
+        """dev_canny_contours (same arguments), then the polygon stage on what it stored, on the same stream."""
+        v = C.c_void_p
+        self._check(self._L.canny_hip_dev_canny_polygons(
+            self._h, v(d_img or None), sigma, min_val, max_val, h, w, n, v(d_edges or None), min_area, v(d_stats or None),
+            capacity, v(d_offsets or None), v(d_chain_offsets or None), v(d_points or None), point_capacity,
+            v(d_point_offsets or None), epsilon_q8, ratio_q16, v(d_vertex_offsets or None), v(d_vertices or None),
+            vertex_capacity, v(d_measures or None)), "dev_canny_polygons")
+
+    def dev_polygons_bits(self, d_bits: int, h: int, w: int, n: int, min_area: int, d_stats: int, capacity: int,
+                          d_offsets: int, d_chain_offsets: int, d_points: int, point_capacity: int, d_point_offsets: int,
+                          epsilon_q8: int, ratio_q16: int, d_vertex_offsets: int, d_vertices: int, vertex_capacity: int,
+                          d_measures: int = 0):
+        """dev_contours_bits (same arguments), then the polygon stage on what it stored."""
+        v = C.c_void_p
+        self._check(self._L.canny_hip_dev_polygons_bits(
+            self._h, v(d_bits or None), h, w, n, min_area, v(d_stats or None), capacity, v(d_offsets or None),
+            v(d_chain_offsets or None), v(d_points or None), point_capacity, v(d_point_offsets or None), epsilon_q8,
+            ratio_q16, v(d_vertex_offsets or None), v(d_vertices or None), vertex_capacity, v(d_measures or None)),
+            "dev_polygons_bits")
+
+    def polygons_profile_get(self, part: int) -> Tuple[float, int]:
+        """(total ms, launch groups) of part 0 simplify, 1 scan, 2 emit (POLYGON_PARTS)."""
+        ms, n = C.c_double(0.0), C.c_long(0)
+        self._check(self._L.canny_hip_polygons_profile_get(self._h, part, C.byref(ms), C.byref(n)),
+                    "polygons_profile_get")
         return ms.value, n.value
 
     # ---- Euclidean distance transform of the finished map (DESIGN.md section 15) ---------------------------------

@@ -388,6 +388,9 @@ struct canny_hip_ctx {
     DevBuf cc_parent, cc_ws;
     // contour chains: per-frame totals and per-row sums / prefixes of the chain points (the scan's second use)
     DevBuf ct_ws;
+    // polygon approximation: the vertex masks (8 B per record slot), the scan's block sums, the vertex flags of long chains
+    // (1 B per point slot); the chains themselves when canny_hip_canny_polygons keeps them on the device
+    DevBuf pg_ws, pg_points;
     // distance transform: the row pass's u16 plane (2 B/px, rows padded to 64 pixels); the column scan's stack (4 B/px) when
     // the caller passes no dist2 plane to keep it in
     DevBuf edt_cols, edt_stack;
@@ -422,14 +425,18 @@ struct canny_hip_ctx {
     // slots: the stages, then the three Hough parts (canny_hip_hough_profile_get), then the four parts of the component
     // labelling (canny_hip_components_profile_get), then the two of the distance transform (canny_hip_edt_profile_get),
     // then the three of the Hough segments (canny_hip_hough_segments_profile_get), then the four of the contour chains
-    // (canny_hip_contours_profile_get), then the four of the Hough circles (canny_hip_hough_circles_profile_get)
+    // (canny_hip_contours_profile_get), then the four of the Hough circles (canny_hip_hough_circles_profile_get), then the
+    // three of the polygon approximation (canny_hip_polygons_profile_get).  The mask is a non-negative int option: bit 30
+    // is the last it can carry, and the three polygon slots go by it together
     static constexpr int kProfHough = CANNY_HIP_STAGE_END, kProfComponents = CANNY_HIP_STAGE_END + 3;
     static constexpr int kProfEdt = kProfComponents + CANNY_HIP_CC_PARTS;
     static constexpr int kProfSegments = kProfEdt + CANNY_HIP_EDT_PARTS;
     static constexpr int kProfContours = kProfSegments + CANNY_HIP_SEGMENT_PARTS;
     static constexpr int kProfCircles = kProfContours + CANNY_HIP_CONTOUR_PARTS;
-    static constexpr int kProfSlots = kProfCircles + CANNY_HIP_CIRCLE_PARTS;
-    static_assert(kProfSlots <= 32, "profile_stage_mask has one bit per slot");
+    static constexpr int kProfPolygons = kProfCircles + CANNY_HIP_CIRCLE_PARTS;
+    static constexpr int kProfSlots = kProfPolygons + CANNY_HIP_POLYGON_PARTS;
+    static constexpr int kProfLastBit = 30;
+    static_assert(kProfPolygons == kProfLastBit, "profile_stage_mask has one bit per slot up to the polygon parts");
     unsigned prof_seen[kProfSlots] = {0};
     std::vector<EventPair> pending[kProfSlots];
     std::vector<EventPair> pool;
@@ -501,7 +508,7 @@ struct StageTimer {
     StageTimer(canny_hip_ctx *c, int s, hipStream_t on_stream = nullptr, bool attached = false)
         : ctx(c), stage(s), stream(on_stream ? on_stream : c->stream), attach(attached)
     {
-        if (!ctx->prof || !(ctx->prof_mask >> s & 1u)) return;
+        if (!ctx->prof || !(ctx->prof_mask >> (s < canny_hip_ctx::kProfLastBit ? s : canny_hip_ctx::kProfLastBit) & 1u)) return;
         if (ctx->prof_seen[s]++ % ctx->prof_every != 0) return;
         if (!ctx->pool.empty()) {
             ev = ctx->pool.back();
@@ -1298,6 +1305,68 @@ int dev_canny_contours(canny_hip_ctx *ctx, const unsigned char *d_img, float sig
     return dev_contours(ctx, (const uint64_t *)ctx->plane_s.p, nullptr, make_hyst_geom(h, w, n), min_area, out);
 }
 
+// ---- polygon approximation of the chains (canny_polygons.hip) --------------
+struct PgOut {
+    unsigned epsilon_q8, ratio_q16;
+    unsigned long long *vertex_offsets;
+    int *vertices;
+    unsigned long long vertex_capacity;
+    long long *measures;
+};
+
+bool polygon_args_ok(const PgOut &out)
+{
+    return out.vertex_offsets && (out.vertices || !out.vertex_capacity) && out.ratio_q16 < 65536u;
+}
+
+int check_polygon_dims(int height, int width)
+{
+    if (height < 1 || width < 1) return CANNY_HIP_ERR_INVALID;
+    return height > kPolygonMaxSide || width > kPolygonMaxSide ? CANNY_HIP_ERR_UNSUPPORTED : CANNY_HIP_OK;
+}
+
+// The stage on stored chains, queued on the context's stream.  The launches depend on capacity and on which outputs were
+// asked for; the number of records is read on the device.
+int dev_polygons(canny_hip_ctx *ctx, const unsigned long long *offsets, int n_frames, unsigned long long capacity,
+                 const unsigned long long *chain_offsets, const int *points, unsigned long long point_capacity, int width,
+                 const PgOut &out)
+{
+    // one block: masks | block sums | flags
+    const size_t masks_bytes = (size_t)capacity * sizeof(unsigned long long);
+    const size_t sums_bytes = (size_t)polygons_scan_blocks(capacity) * sizeof(unsigned long long);
+    HIP_TRY(ctx, ctx->pg_ws.ensure(masks_bytes + sums_bytes + (size_t)point_capacity + 16));
+    unsigned long long *masks = (unsigned long long *)ctx->pg_ws.p;
+    unsigned long long *sums = (unsigned long long *)((char *)ctx->pg_ws.p + masks_bytes);
+    uint8_t *flags = (uint8_t *)ctx->pg_ws.p + masks_bytes + sums_bytes;
+    const int part = canny_hip_ctx::kProfPolygons;
+    {
+        StageTimer tm(ctx, part + CANNY_HIP_POLYGON_PART_SIMPLIFY);
+        HIP_TRY(ctx, launch_pg_simplify(offsets, n_frames, capacity, chain_offsets, points, point_capacity, width,
+                                        out.epsilon_q8, out.ratio_q16, out.vertex_offsets, masks, flags, out.measures,
+                                        ctx->stream));
+    }
+    if (capacity) {
+        StageTimer tm(ctx, part + CANNY_HIP_POLYGON_PART_SCAN);
+        HIP_TRY(ctx, launch_pg_scan(offsets, n_frames, capacity, out.vertex_offsets, sums, ctx->stream));
+    }
+    if (capacity && (out.vertex_capacity || out.measures)) {
+        StageTimer tm(ctx, part + CANNY_HIP_POLYGON_PART_EMIT);
+        HIP_TRY(ctx, launch_pg_emit(offsets, n_frames, capacity, chain_offsets, points, point_capacity, width,
+                                    out.vertex_offsets, masks, flags, out.vertices, out.vertex_capacity, out.measures,
+                                    ctx->stream));
+    }
+    return CANNY_HIP_OK;
+}
+
+// dev_canny_contours (unchanged), then the stage.  max_val > 255 leaves offsets all zero, so the stage finds no record.
+int dev_canny_polygons(canny_hip_ctx *ctx, const unsigned char *d_img, float sigma, int lo, int hi, int h, int w, int n,
+                       short *d_edges, int min_area, const CtOut &ct, const PgOut &out)
+{
+    const int rc = dev_canny_contours(ctx, d_img, sigma, lo, hi, h, w, n, d_edges, min_area, ct);
+    if (rc) return rc;
+    return dev_polygons(ctx, ct.offsets, n, ct.capacity, ct.chain_offsets, ct.points, ct.point_capacity, w, out);
+}
+
 // ---- Euclidean distance transform (canny_edt.hip) --------------------------
 struct EdtOut {
     int *dist2;
@@ -1828,6 +1897,8 @@ void canny_hip_ctx_destroy(canny_hip_ctx *ctx)
     ctx->cc_parent.release();
     ctx->cc_ws.release();
     ctx->ct_ws.release();
+    ctx->pg_ws.release();
+    ctx->pg_points.release();
     ctx->edt_cols.release();
     ctx->edt_stack.release();
     ctx->stamps.release();
@@ -3357,6 +3428,139 @@ int canny_hip_contours_from_bits(const unsigned char *bits, int height, int widt
     return CANNY_HIP_OK;
 }
 
+// ---- polygon approximation of the chains -------------------------------------------------------------
+int canny_hip_dev_polygons_chains(canny_hip_ctx *ctx, const unsigned long long *d_offsets, int n_frames,
+                                  unsigned long long capacity, const unsigned long long *d_chain_offsets,
+                                  const int *d_points, unsigned long long point_capacity, int width, int height,
+                                  unsigned epsilon_q8, unsigned ratio_q16, unsigned long long *d_vertex_offsets,
+                                  int *d_vertices, unsigned long long vertex_capacity, long long *d_measures)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    const PgOut out{epsilon_q8, ratio_q16, d_vertex_offsets, d_vertices, vertex_capacity, d_measures};
+    if (!d_offsets || n_frames < 1 || !d_chain_offsets || (!d_points && point_capacity) || !polygon_args_ok(out))
+        return CANNY_HIP_ERR_INVALID;
+    if ((rc = check_polygon_dims(height, width)) || (rc = finish_pending(ctx))) return rc;
+    return dev_polygons(ctx, d_offsets, n_frames, capacity, d_chain_offsets, d_points, point_capacity, width, out);
+}
+
+int canny_hip_dev_canny_polygons(canny_hip_ctx *ctx, const unsigned char *d_img, float sigma, int min_val, int max_val,
+                                 int height, int width, int n_frames, short *d_edges, int min_area, int *d_stats,
+                                 unsigned long long capacity, unsigned long long *d_offsets,
+                                 unsigned long long *d_chain_offsets, int *d_points, unsigned long long point_capacity,
+                                 unsigned long long *d_point_offsets, unsigned epsilon_q8, unsigned ratio_q16,
+                                 unsigned long long *d_vertex_offsets, int *d_vertices, unsigned long long vertex_capacity,
+                                 long long *d_measures)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    const CtOut ct{d_stats, capacity, d_offsets, d_chain_offsets, d_points, point_capacity, d_point_offsets};
+    const PgOut out{epsilon_q8, ratio_q16, d_vertex_offsets, d_vertices, vertex_capacity, d_measures};
+    if (!d_img || !d_chain_offsets || !contour_args_ok(ct) || !polygon_args_ok(out)) return CANNY_HIP_ERR_INVALID;
+    if ((rc = check_contour_dims(height, width, n_frames)) || (rc = check_polygon_dims(height, width))) return rc;
+    return dev_canny_polygons(ctx, d_img, sigma, min_val, max_val, height, width, n_frames, d_edges, min_area, ct, out);
+}
+
+int canny_hip_dev_polygons_bits(canny_hip_ctx *ctx, const unsigned char *d_bits, int height, int width, int n_frames,
+                                int min_area, int *d_stats, unsigned long long capacity, unsigned long long *d_offsets,
+                                unsigned long long *d_chain_offsets, int *d_points, unsigned long long point_capacity,
+                                unsigned long long *d_point_offsets, unsigned epsilon_q8, unsigned ratio_q16,
+                                unsigned long long *d_vertex_offsets, int *d_vertices, unsigned long long vertex_capacity,
+                                long long *d_measures)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    const CtOut ct{d_stats, capacity, d_offsets, d_chain_offsets, d_points, point_capacity, d_point_offsets};
+    const PgOut out{epsilon_q8, ratio_q16, d_vertex_offsets, d_vertices, vertex_capacity, d_measures};
+    if (!d_bits || !d_chain_offsets || !contour_args_ok(ct) || !polygon_args_ok(out)) return CANNY_HIP_ERR_INVALID;
+    if ((rc = check_contour_dims(height, width, n_frames)) || (rc = check_polygon_dims(height, width)) ||
+        (rc = finish_pending(ctx)))
+        return rc;
+    if ((rc = dev_contours(ctx, nullptr, d_bits, make_hyst_geom(height, width, n_frames), min_area, ct))) return rc;
+    return dev_polygons(ctx, d_offsets, n_frames, capacity, d_chain_offsets, d_points, point_capacity, width, out);
+}
+
+int canny_hip_canny_polygons(canny_hip_ctx *ctx, const unsigned char *imgs, int n_frames, float sigma, int min_val,
+                             int max_val, int height, int width, int min_area, int *stats, unsigned long long capacity,
+                             unsigned long long *offsets, unsigned long long *chain_offsets, int *points,
+                             unsigned long long point_capacity, unsigned long long *point_offsets, unsigned epsilon_q8,
+                             unsigned ratio_q16, unsigned long long *vertex_offsets, int *vertices,
+                             unsigned long long vertex_capacity, long long *measures)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!imgs || !offsets || !point_offsets ||
+        !polygon_args_ok(PgOut{epsilon_q8, ratio_q16, vertex_offsets, vertices, vertex_capacity, measures}))
+        return CANNY_HIP_ERR_INVALID;
+    if ((rc = check_contour_dims(height, width, n_frames)) || (rc = check_polygon_dims(height, width))) return rc;
+    const size_t n = npx(height, width, n_frames);
+    const size_t off_bytes = ((size_t)n_frames + 1) * sizeof(unsigned long long);
+    // a frame has no more records than pixels, no more chain points than 8 per pixel and one per record, and a polygon no
+    // more vertices than its chain has points.  point_capacity itself decides which chains are complete, so it is
+    // clamped only where that changes nothing: every chain ends at or below 9 n.
+    const unsigned long long cap = std::min<unsigned long long>(capacity, n);
+    const unsigned long long pcap = std::min<unsigned long long>(point_capacity, 9ull * n);
+    const unsigned long long vcap = std::min<unsigned long long>(vertex_capacity, pcap);
+    if ((rc = h2d(ctx, ctx->io[0], imgs, n))) return rc;
+    // one staging block: offsets | point_offsets | chain_offsets | vertex_offsets | measures | stats | vertices; the chain
+    // points in a block of their own, which never crosses to the host when points == NULL
+    auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+    const size_t csr_bytes = ((size_t)cap + 1) * sizeof(unsigned long long);
+    const size_t poff_at = up16(off_bytes), chain_at = up16(poff_at + off_bytes), voff_at = up16(chain_at + csr_bytes);
+    const size_t meas_at = up16(voff_at + csr_bytes);
+    const size_t stats_at = up16(meas_at + (measures ? (size_t)cap * 4 * sizeof(long long) : 0));
+    const size_t verts_at = up16(stats_at + (stats ? (size_t)cap * CANNY_HIP_CC_STATS * sizeof(int) : 0));
+    HIP_TRY(ctx, ctx->io[1].ensure(verts_at + (size_t)vcap * sizeof(int)));
+    HIP_TRY(ctx, ctx->pg_points.ensure((size_t)pcap * sizeof(int) + 16));
+    char *d = (char *)ctx->io[1].p;
+    const CtOut ct{stats && cap ? (int *)(d + stats_at) : nullptr,
+                   cap,
+                   (unsigned long long *)d,
+                   (unsigned long long *)(d + chain_at),
+                   pcap ? (int *)ctx->pg_points.p : nullptr,
+                   pcap,
+                   (unsigned long long *)(d + poff_at)};
+    const PgOut out{epsilon_q8,
+                    ratio_q16,
+                    (unsigned long long *)(d + voff_at),
+                    vcap ? (int *)(d + verts_at) : nullptr,
+                    vcap,
+                    measures && cap ? (long long *)(d + meas_at) : nullptr};
+    if ((rc = dev_canny_polygons(ctx, (const unsigned char *)ctx->io[0].p, sigma, min_val, max_val, height, width, n_frames,
+                                 nullptr, min_area, ct, out)))
+        return rc;
+    // the offsets come down first: they say how many records there are to download
+    std::vector<unsigned long long> off(2 * ((size_t)n_frames + 1));
+    HIP_TRY(ctx, hipMemcpyAsync(off.data(), ct.offsets, off_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = d2h_sync(ctx, off.data() + n_frames + 1, ct.point_offsets, off_bytes))) return rc;
+    const unsigned long long n_rec = std::min(off[n_frames], cap);
+    unsigned long long ends[2] = {0, 0}; // where the stored chains and the polygons end
+    HIP_TRY(ctx, hipMemcpyAsync(&ends[0], ct.chain_offsets + n_rec, sizeof ends[0], hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(&ends[1], out.vertex_offsets + n_rec, sizeof ends[1], hipMemcpyDeviceToHost, ctx->stream));
+    if (chain_offsets)
+        HIP_TRY(ctx, hipMemcpyAsync(chain_offsets, ct.chain_offsets, ((size_t)n_rec + 1) * sizeof(unsigned long long),
+                                    hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(vertex_offsets, out.vertex_offsets, ((size_t)n_rec + 1) * sizeof(unsigned long long),
+                                hipMemcpyDeviceToHost, ctx->stream));
+    if (n_rec && ct.stats)
+        HIP_TRY(ctx, hipMemcpyAsync(stats, ct.stats, (size_t)n_rec * CANNY_HIP_CC_STATS * sizeof(int),
+                                    hipMemcpyDeviceToHost, ctx->stream));
+    if (n_rec && out.measures)
+        HIP_TRY(ctx, hipMemcpyAsync(measures, out.measures, (size_t)n_rec * 4 * sizeof(long long), hipMemcpyDeviceToHost,
+                                    ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    const unsigned long long n_pts = points ? std::min(ends[0], pcap) : 0, n_verts = std::min(ends[1], vcap);
+    if (n_pts) HIP_TRY(ctx, hipMemcpyAsync(points, ct.points, (size_t)n_pts * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    if (n_verts)
+        HIP_TRY(ctx, hipMemcpyAsync(vertices, out.vertices, (size_t)n_verts * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    std::memcpy(offsets, off.data(), off_bytes);
+    std::memcpy(point_offsets, off.data() + n_frames + 1, off_bytes);
+    return CANNY_HIP_OK;
+}
+
+// canny_hip_polygons_from_chains, the rule in plain C++, lives in canny_polygons_host.cpp: it needs no HIP.
+
 // ---- Euclidean distance transform -------------------------------------------------------------------
 int canny_hip_dev_canny_edt(canny_hip_ctx *ctx, const unsigned char *d_img, float sigma, int min_val, int max_val,
                             int height, int width, int n_frames, short *d_edges, int *d_dist2, float *d_dist,
@@ -3893,6 +4097,17 @@ int canny_hip_contours_profile_get(canny_hip_ctx *ctx, int part, double *total_m
     if ((rc = profile_collect(ctx))) return rc;
     *total_ms = ctx->total_ms[canny_hip_ctx::kProfContours + part];
     *launches = ctx->launches[canny_hip_ctx::kProfContours + part];
+    return CANNY_HIP_OK;
+}
+
+int canny_hip_polygons_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches)
+{
+    if (part < 0 || part >= CANNY_HIP_POLYGON_PARTS || !total_ms || !launches) return CANNY_HIP_ERR_INVALID;
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if ((rc = profile_collect(ctx))) return rc;
+    *total_ms = ctx->total_ms[canny_hip_ctx::kProfPolygons + part];
+    *launches = ctx->launches[canny_hip_ctx::kProfPolygons + part];
     return CANNY_HIP_OK;
 }
 

@@ -499,6 +499,30 @@ hipError_t launch_ct_write(const uint64_t *strong, const uint8_t *bits, const Hy
                            unsigned long long *chain_offsets, unsigned long long capacity, int *points,
                            unsigned long long point_capacity, hipStream_t stream);
 
+// ---- Polygon approximation of the chains (canny_polygons.hip) ----------
+// They read what a contours call stored: offsets (the record CSR, only offsets[n_frames] is used), chain_offsets and points.
+// R = min(offsets[n_frames], capacity) is read on the device.  height, width <= kPolygonMaxSide keep every cross product
+// below 2^31.  masks: capacity u64; flags: point_capacity bytes; block_sums: polygons_scan_blocks(capacity) u64.
+constexpr int kPolygonMaxSide = 32768;
+unsigned long long polygons_scan_blocks(unsigned long long capacity);
+// simplify: vertex_offsets[0] = 0, vertex_offsets[j + 1] = the vertex count of record j (0 for a chain cut by
+// point_capacity); the vertex set goes to masks[j] (chains of at most 64 points) or flags[chain_offsets[j] + i];
+// measures (may be null) [j][0 .. 1] = vertices, length_q8, and (-1, 0, 0, 0) for a cut chain.
+hipError_t launch_pg_simplify(const unsigned long long *offsets, int n_frames, unsigned long long capacity,
+                              const unsigned long long *chain_offsets, const int *points, unsigned long long point_capacity,
+                              int width, unsigned epsilon_q8, unsigned ratio_q16, unsigned long long *vertex_offsets,
+                              unsigned long long *masks, uint8_t *flags, long long *measures, hipStream_t stream);
+// scan: vertex_offsets[1 .. R] become inclusive prefix sums, in place.
+hipError_t launch_pg_scan(const unsigned long long *offsets, int n_frames, unsigned long long capacity,
+                          unsigned long long *vertex_offsets, unsigned long long *block_sums, hipStream_t stream);
+// emit: vertices[vertex_offsets[j] + rank] below vertex_capacity (vertices may be null with capacity 0);
+// measures (may be null) [j][2 .. 3] = area2, convex of the complete records.
+hipError_t launch_pg_emit(const unsigned long long *offsets, int n_frames, unsigned long long capacity,
+                          const unsigned long long *chain_offsets, const int *points, unsigned long long point_capacity,
+                          int width, const unsigned long long *vertex_offsets, const unsigned long long *masks,
+                          const uint8_t *flags, int *vertices, unsigned long long vertex_capacity, long long *measures,
+                          hipStream_t stream);
+
 // ---- Euclidean distance transform (canny_edt.hip) ----------------------
 // Source as for the point lists.  height * width < 2^31 and height^2 + width^2 < 2^31.
 // Elements per row of the u16 plane between the two passes: rows are padded to whole 64-pixel words.

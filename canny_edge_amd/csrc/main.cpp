@@ -1,7 +1,7 @@
 // main.cpp -- the reference's command line (StevenChang5/Canny_Edge src/main.cpp:18-142) without
 // the webcam and the GUI:  ./Main sigma minVal maxVal [-c] [-s] [-i in.pgm|in.ppm|in.jpg] [-o dir] [-p] [-n WxH] [-b dir]
 //        [-l rho,theta_degrees,threshold[,lines_max]] [-g min_length,max_gap[,exclusive]] [-m min_area] [-t] [-d]
-//        [-r min_radius,max_radius,threshold,support[,min_dist[,cell_shift]]]
+//        [-r min_radius,max_radius,threshold,support[,min_dist[,cell_shift]]] [-y epsilon[,ratio]]
 //
 // Kept from the reference: the three positionals may appear anywhere relative to the flags
 // (src/main.cpp:29-46); exactly three are required, otherwise the usage text is printed and the
@@ -25,6 +25,12 @@
 // Added: -t follows the outer border of every component of the frame's edge map with at least min_area pixels (-m, default
 // 1) on the GPU (canny_hip_canny_contours) and writes one "label n x0 y0 x1 y1 ..." line per contour to canny_contours.txt
 // in the -o directory (stdout without -o).
+// Added: -y epsilon[,ratio] (with -t) also approximates every contour by a polygon on the GPU (canny_hip_canny_polygons; the
+// chains stay on the device): the tolerance is epsilon pixels plus ratio times the contour's own length, as
+// approxPolyDP(c, epsilon + ratio * arcLength(c, true), true).  One "frame record vertices length area2 convex x0 y0 x1 y1
+// ..." line per contour goes to canny_polygons.txt in the -o directory (stdout without -o); record is the label of
+// canny_contours.txt, length is in 1/256 pixel, area2 is twice the polygon's area.  -y without -t and a malformed -y are
+// usage errors (exit 2).
 // Added: -d runs the exact Euclidean distance transform of the frame's edge map on the GPU (canny_hip_canny_edt) and writes
 // canny_dist.pgm (.png with -p) to the -o directory (the current one without -o): one byte per pixel,
 // min(255, floor(sqrt(dist2))), 255 everywhere for a map without edge pixels.  Without -d nothing changes.
@@ -384,6 +390,52 @@ static int run_contours(const vector<unsigned char> &frame, int height, int widt
     return 0;
 }
 
+// -y (with -t): the polygon of every contour, "frame record vertices length area2 convex x0 y0 x1 y1 ..." each.  Only the
+// polygons come down: the chains stay on the device.
+static int run_polygons(const vector<unsigned char> &frame, int height, int width, float sigma, int minVal, int maxVal,
+                        int min_area, unsigned epsilon_q8, unsigned ratio_q16, const string &outdir)
+{
+    vector<unsigned long long> vertex_offsets(1, 0);
+    vector<int> vertices;
+    vector<long long> measures;
+    unsigned long long offsets[2] = {0, 0}, point_offsets[2] = {0, 0};
+    canny_hip_ctx *ctx = nullptr;
+    int st = canny_hip_ctx_create(&ctx, 0);
+    // counts first: a polygon has no more vertices than its chain has points
+    if (!st)
+        st = canny_hip_canny_contours(ctx, frame.data(), 1, sigma, minVal, maxVal, height, width, min_area, nullptr, 0,
+                                      offsets, nullptr, nullptr, 0, point_offsets);
+    if (!st) {
+        vertex_offsets.resize((size_t)offsets[1] + 1);
+        vertices.resize((size_t)point_offsets[1] + 1);
+        measures.resize((size_t)offsets[1] * CANNY_HIP_POLYGON_MEASURES + 1);
+        st = canny_hip_canny_polygons(ctx, frame.data(), 1, sigma, minVal, maxVal, height, width, min_area, nullptr,
+                                      offsets[1], offsets, nullptr, nullptr, point_offsets[1], point_offsets, epsilon_q8,
+                                      ratio_q16, vertex_offsets.data(), vertices.data(), point_offsets[1], measures.data());
+    }
+    if (st) {
+        fprintf(stderr, "ERROR: -y: %s\n", st == CANNY_HIP_ERR_RUNTIME && ctx ? canny_hip_last_error(ctx) : canny_hip_status_string(st));
+        if (ctx) canny_hip_ctx_destroy(ctx);
+        return 1;
+    }
+    canny_hip_ctx_destroy(ctx);
+    FILE *f = outdir.empty() ? stdout : fopen((outdir + "/canny_polygons.txt").c_str(), "w");
+    if (!f) {
+        fprintf(stderr, "ERROR: cannot write %s/canny_polygons.txt\n", outdir.c_str());
+        return 1;
+    }
+    for (unsigned long long k = 0; k < offsets[1]; k++) {
+        const long long *m = measures.data() + k * CANNY_HIP_POLYGON_MEASURES;
+        fprintf(f, "0 %llu %lld %lld %lld %lld", k + 1, m[CANNY_HIP_POLYGON_VERTICES], m[CANNY_HIP_POLYGON_LENGTH_Q8],
+                m[CANNY_HIP_POLYGON_AREA2], m[CANNY_HIP_POLYGON_CONVEX]);
+        for (unsigned long long q = vertex_offsets[k]; q < vertex_offsets[k + 1]; q++)
+            fprintf(f, " %d %d", vertices[q] % width, vertices[q] / width);
+        fprintf(f, "\n");
+    }
+    if (f != stdout) fclose(f);
+    return 0;
+}
+
 // -d: the distance of every pixel to the nearest edge pixel, as a byte image
 static int run_edt(const vector<unsigned char> &frame, int height, int width, float sigma, int minVal, int maxVal,
                    const string &outdir)
@@ -465,6 +517,8 @@ int main(int argc, char *argv[])
     bool want_dist = false;
     bool want_contours = false;
     bool want_circles = false;
+    bool want_polygons = false;
+    unsigned polygon_epsilon_q8 = 0, polygon_ratio_q16 = 0;
     int circle_args[6] = {0, 0, 0, 0, 0, 0}; // min_radius, max_radius, threshold, support, min_dist, cell_shift
     int width = WIDTH, height = HEIGHT;
     vector<string> values;
@@ -521,6 +575,27 @@ int main(int argc, char *argv[])
                 exit(2);
             }
             want_circles = true;
+        } else if (arg == "-y" && i + 1 < argc) {
+            // one or two non-negative numbers, nothing empty, nothing behind the last one
+            double v[2] = {0.0, 0.0};
+            int got = 0;
+            bool clean = true;
+            for (const char *p = argv[++i]; clean; got++) {
+                char *end = nullptr;
+                const double d = strtod(p, &end);
+                clean = end != p && got < 2 && std::isfinite(d) && d >= 0.0 && !isspace((unsigned char)*p);
+                if (clean) v[got] = d;
+                if (!clean || *end == '\0') break;
+                clean = *end == ',';
+                p = end + 1;
+            }
+            const double eq = std::floor(v[0] * 256.0 + 0.5), rq = std::floor(v[1] * 65536.0 + 0.5);
+            if (!clean || eq > 4294967295.0 || rq >= 65536.0) {
+                fprintf(stderr, "ERROR: -y expects epsilon[,ratio]: pixels >= 0 and a fraction of the contour's length in [0, 1)\n");
+                exit(2);
+            }
+            polygon_epsilon_q8 = (unsigned)eq, polygon_ratio_q16 = (unsigned)rq;
+            want_polygons = true;
         } else if (arg == "-d") {
             want_dist = true;
         } else if (arg == "-t") {
@@ -537,6 +612,10 @@ int main(int argc, char *argv[])
 
     if (want_segments && !want_lines) {
         fprintf(stderr, "ERROR: -g needs the lines of -l rho,theta_degrees,threshold[,lines_max]\n");
+        exit(2);
+    }
+    if (want_polygons && !want_contours) {
+        fprintf(stderr, "ERROR: -y needs the contours of -t\n");
         exit(2);
     }
     if (values.size() != 3) {
@@ -556,6 +635,9 @@ int main(int argc, char *argv[])
         fprintf(stderr, "                canny_kept.pgm in the -o dir\n");
         fprintf(stderr, "   -t: outer contour chain of every component with at least min_area (-m, default 1) pixels, one\n");
         fprintf(stderr, "       \"label n x0 y0 x1 y1 ...\" line each -> canny_contours.txt in the -o dir\n");
+        fprintf(stderr, "   -y epsilon[,ratio]: with -t, the polygon of every contour at a tolerance of epsilon pixels plus ratio times\n");
+        fprintf(stderr, "       its length, one \"frame record vertices length area2 convex x0 y0 x1 y1 ...\" line each (length in 1/256\n");
+        fprintf(stderr, "       pixel, area2 twice the area) -> canny_polygons.txt in the -o dir\n");
         fprintf(stderr, "   -r min_radius,max_radius,threshold,support[,min_dist[,cell_shift]]: circles of the edge map, one\n");
         fprintf(stderr, "       \"frame x y radius votes support\" line each -> canny_circles.txt in the -o dir\n");
         fprintf(stderr, "   -d: distance of every pixel to the nearest edge pixel, min(255, floor) -> canny_dist.pgm in the -o dir\n");
@@ -618,6 +700,11 @@ int main(int argc, char *argv[])
     }
     if (want_contours) {
         const int rc = run_contours(frame, height, width, sigma, minVal, maxVal, min_area, outdir);
+        if (rc) return rc;
+    }
+    if (want_polygons) {
+        const int rc = run_polygons(frame, height, width, sigma, minVal, maxVal, min_area, polygon_epsilon_q8,
+                                    polygon_ratio_q16, outdir);
         if (rc) return rc;
     }
     if (want_dist) {

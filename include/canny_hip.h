@@ -52,8 +52,9 @@
 extern "C" {
 #endif
 
-#define CANNY_HIP_VERSION 1100       /* 0.11.0: + Hough circles: gradient rays, centre peaks, radius by support */
+#define CANNY_HIP_VERSION 1200       /* 0.12.0: + polygon approximation of the contour chains, on the GPU */
 /* 0.10.0: + outer contour chains of the finished map, traced on the GPU */
+/* 0.11.0: + Hough circles: gradient rays, centre peaks, radius by support */
 /* 0.9.1: + canny_hip_selftest_histogram, canny_hip_selftest_select */
 /* 0.9.0: + Hough line segments: runs of edge pixels along each detected line */
 /* 0.8.0: + exact Euclidean distance transform of the finished map: dist2, dist, nearest */
@@ -775,7 +776,8 @@ int canny_hip_components_from_bits(const unsigned char *bits, int height, int wi
 /* ---- outer contour chains ------------------------------------------------------------------------------------------------
  * For every kept component of the finished edge map its outer border as an ORDERED list of pixels, per frame of a batch, on
  * the GPU, queued behind the detector on the same stream with no host round trip: what curve fitting, polygon approximation,
- * arc-length measures, shape descriptors and vector export start from -- the use of
+ * arc-length measures, shape descriptors and vector export start from (polygon approximation: the section after this one) --
+ * the use of
  * cv::findContours(RETR_EXTERNAL, CHAIN_APPROX_NONE) after cv::Canny.  (The same curves; no claim is made that the points
  * come in the order OpenCV lists them.)  THE RULE, for frame f with edge map E_f (the map
  * canny_hip_canny returns for that frame, bit for bit):
@@ -824,7 +826,7 @@ int canny_hip_components_from_bits(const unsigned char *bits, int height, int wi
  *   DESIGN.md section 17 for the measured time per step.
  * The four parts are timed by canny_hip_contours_profile_get (CANNY_HIP_CONTOUR_PART_*); with "profile_stage_mask" they are
  *   bits 22 .. 25.
- * Not covered -- follow-ups: hole borders and the hierarchy, CHAIN_APPROX_SIMPLE and polygon approximation, 4-connectivity,
+ * Not covered -- follow-ups: hole borders and the hierarchy, CHAIN_APPROX_SIMPLE as its own call, 4-connectivity,
  * sub-pixel positions, parallel ranking of long chains, the three-stream batch pipeline, the multi-GPU sharder, colour and
  * per-frame / automatic-threshold variants. */
 enum canny_hip_contour_part {
@@ -860,6 +862,112 @@ int canny_hip_contours_from_bits(const unsigned char *bits, int height, int widt
                                  unsigned long long capacity, unsigned long long *count,
                                  unsigned long long *chain_offsets, int *points, unsigned long long point_capacity,
                                  unsigned long long *point_count);
+
+/* ---- polygon approximation of the contour chains ---------------------------------------------------------------------------
+ * For every stored chain of a contours call the few vertices that describe it, on the GPU, queued behind the chains on the
+ * same stream: the use of cv::approxPolyDP(c, eps * cv::arcLength(c, true), true) after cv::findContours, and what "four
+ * vertices, convex, large enough: a rectangle" is decided on.  A chain is every border pixel in order; a polygon is a
+ * handful of vertices, the only form of the contours that is cheap to bring to the host.  Everything is integers.
+ * THE RULE, for one stored chain P_0 .. P_{n-1}.  Points are pixel indices r * width + c, read as
+ * (x, y) = (c, r); the chain is closed, P_n means P_0.  The parameters of a call: epsilon_q8 (unsigned), an absolute
+ * tolerance in 1/256 pixel, and ratio_q16 (unsigned, < 65536), a tolerance relative to the chain's own length in 1/65536.
+ * Both may be given; they add.
+ *   1. Length.  length_q8 = 256 * (number of axis steps) + 362 * (number of diagonal steps) over the n cyclic steps
+ *      P_i -> P_{i+1}: a step that changes both coordinates is diagonal, one that changes exactly one is an axis step, a
+ *      step between equal points (n == 1) counts nothing, so the length of a one-point chain is 0.  362 / 256 stands for
+ *      sqrt(2) and is part of the rule: length_q8 / 256 is cv::arcLength(chain, true) to within 0.02 %.  64-bit arithmetic.
+ *   2. Tolerance.  eps = min(epsilon_q8 + ((ratio_q16 * length_q8) >> 16), 2^24).
+ *   3. Anchors.  n == 1: the polygon is [P_0].  Otherwise k is the smallest i that maximises |P_i - P_0|^2; positions 0 and
+ *      k are vertices.
+ *   4. Simplify the two open runs (0, k) and (k, n).  Simplifying (a, b) with b - a >= 2: for a < i < b let
+ *      c_i = |cross(P_b - P_a, P_i - P_a)|; m is the smallest i that maximises c_i.  If c_m^2 * 2^16 > eps^2 * |P_b - P_a|^2,
+ *      compared exactly (128 bits), position m is a vertex and (a, m) and (m, b) are simplified in turn; otherwise nothing
+ *      between a and b is a vertex.  The two ends of every run are different pixels (the anchors differ, and a kept m has
+ *      c_m > 0), so no zero-length base occurs and there is no special case.
+ *   5. The polygon is the list of vertex positions in chain order, returned as the pixel indices P_i.  eps = 0 drops
+ *      exactly the collinear points; a one-pixel-wide curve, which the chain walks out and back, comes down to its turning
+ *      points.
+ *   6. Measures per record, four long long: CANNY_HIP_POLYGON_VERTICES the true count V; _LENGTH_Q8; _AREA2 =
+ *      |sum of x_i * y_{i+1} - x_{i+1} * y_i| over the polygon's vertices, cyclically -- twice cv::contourArea of the
+ *      polygon; _CONVEX = 1 iff V >= 3 and the turns cross(v_{i+1} - v_i, v_{i+2} - v_{i+1}) are all >= 0 or all <= 0 with
+ *      at least one of them non-zero, otherwise 0.
+ *   Which chains: the stage reads chains where a contours call stored them, so it handles the records
+ *     j < R = min(K, capacity).  A record is COMPLETE iff chain_offsets[j + 1] <= point_capacity.  An incomplete record --
+ *     its chain was cut by the caller's buffer -- has no vertices and the measures (-1, 0, 0, 0).
+ *   Outputs:
+ *     vertex_offsets[0 .. R] (unsigned long long, capacity + 1 entries at most; mandatory): the true prefix sums of V over
+ *       the records, incomplete records counting 0.  Entries past R are not written.
+ *     vertices (int): position q is written iff q < vertex_capacity: the prefix that fits is exact, a polygon may be cut,
+ *       nothing is written at or past vertices + vertex_capacity.  NULL is allowed with vertex_capacity == 0 only.
+ *     measures (optional, long long [R][4]); what the other outputs receive does not depend on its presence.
+ *   Arguments: chain_offsets, offsets and vertex_offsets are mandatory (chain_offsets and vertex_offsets have capacity + 1
+ *     entries, so they exist at capacity 0 too); points may be NULL with point_capacity == 0 only; ratio_q16 >= 65536 and
+ *     n_frames < 1 are CANNY_HIP_ERR_INVALID.  A height or width above 32768 is CANNY_HIP_ERR_UNSUPPORTED before anything is
+ *     queued (every cross product stays below 2^31).  All other limits and statuses are those of the contours calls, which
+ *     run first and unchanged; on a status other than OK nothing is written.  An empty map (max_val > 255 included) gives
+ *     all zeros: vertex_offsets[0] = 0 and nothing else.
+ *   The output is the same bytes on every run: there are no atomics, every element is stored once by one wave, and the
+ *     launches depend on the shapes, the capacities and on which outputs were asked for, never on the data.
+ * Memory: a context workspace of one byte per point slot (point_capacity) for the vertex flags of chains longer than 64
+ *   points, 8 bytes per record slot (capacity) for the vertex masks of the others, and 8 bytes per 2048 record slots.
+ * Cost: a chain is simplified by ONE wave; chains of at most 64 points, the bulk of an edge map, stay in registers.  See
+ *   DESIGN.md section 19 for the measured times, the long-chain tail included.
+ * The three parts are timed by canny_hip_polygons_profile_get (CANNY_HIP_POLYGON_PART_*); with "profile_stage_mask" the
+ *   three go by bit 30 together, the last bit a non-negative int option carries.
+ * Not covered -- follow-ups: hole borders, open-curve mode (closed = false), CHAIN_APPROX_SIMPLE as its own call, long
+ * chains split over a workgroup, the three-stream batch pipeline, the multi-GPU sharder, colour and per-frame /
+ * automatic-threshold variants. */
+#define CANNY_HIP_POLYGON_MEASURES 4
+enum canny_hip_polygon_measure {
+    CANNY_HIP_POLYGON_VERTICES = 0,
+    CANNY_HIP_POLYGON_LENGTH_Q8 = 1,
+    CANNY_HIP_POLYGON_AREA2 = 2,
+    CANNY_HIP_POLYGON_CONVEX = 3
+};
+enum canny_hip_polygon_part {
+    CANNY_HIP_POLYGON_PART_SIMPLIFY = 0,  /* one wave per chain: length, anchors, the descent; vertex counts */
+    CANNY_HIP_POLYGON_PART_SCAN = 1,      /* prefix sums of the counts: vertex_offsets */
+    CANNY_HIP_POLYGON_PART_EMIT = 2,      /* vertices stored in chain order; area2 and convex */
+    CANNY_HIP_POLYGON_PARTS = 3
+};
+/* The stage alone, on chains already on the device: d_offsets, d_chain_offsets and d_points are what a contours call with
+ * the same n_frames, capacity and point_capacity left.  Asynchronous, on the context's stream. */
+int canny_hip_dev_polygons_chains(canny_hip_ctx *ctx, const unsigned long long *d_offsets, int n_frames,
+                                  unsigned long long capacity, const unsigned long long *d_chain_offsets,
+                                  const int *d_points, unsigned long long point_capacity, int width, int height,
+                                  unsigned epsilon_q8, unsigned ratio_q16, unsigned long long *d_vertex_offsets,
+                                  int *d_vertices, unsigned long long vertex_capacity, long long *d_measures);
+/* canny_hip_dev_canny_contours / canny_hip_dev_contours_bits, unchanged, then the stage on what they stored. */
+int canny_hip_dev_canny_polygons(canny_hip_ctx *ctx, const unsigned char *d_img, float sigma, int min_val, int max_val,
+                                 int height, int width, int n_frames, short *d_edges, int min_area, int *d_stats,
+                                 unsigned long long capacity, unsigned long long *d_offsets,
+                                 unsigned long long *d_chain_offsets, int *d_points, unsigned long long point_capacity,
+                                 unsigned long long *d_point_offsets, unsigned epsilon_q8, unsigned ratio_q16,
+                                 unsigned long long *d_vertex_offsets, int *d_vertices, unsigned long long vertex_capacity,
+                                 long long *d_measures);
+int canny_hip_dev_polygons_bits(canny_hip_ctx *ctx, const unsigned char *d_bits, int height, int width, int n_frames,
+                                int min_area, int *d_stats, unsigned long long capacity, unsigned long long *d_offsets,
+                                unsigned long long *d_chain_offsets, int *d_points, unsigned long long point_capacity,
+                                unsigned long long *d_point_offsets, unsigned epsilon_q8, unsigned ratio_q16,
+                                unsigned long long *d_vertex_offsets, int *d_vertices, unsigned long long vertex_capacity,
+                                long long *d_measures);
+/* Host buffers, synchronous: upload, canny, chains, polygons.  Everything canny_hip_canny_contours returns comes down, plus
+ * min(K, capacity) + 1 vertex offsets, as many measures, and the vertices below min(vertex_offsets[min(K, capacity)],
+ * vertex_capacity).  points may be NULL here at any point_capacity: the chains then stay in a device buffer of
+ * point_capacity ints and only the polygons cross to the host -- the point of the feature.  chain_offsets, stats and
+ * measures may be NULL. */
+int canny_hip_canny_polygons(canny_hip_ctx *ctx, const unsigned char *imgs, int n_frames, float sigma, int min_val,
+                             int max_val, int height, int width, int min_area, int *stats, unsigned long long capacity,
+                             unsigned long long *offsets, unsigned long long *chain_offsets, int *points,
+                             unsigned long long point_capacity, unsigned long long *point_offsets, unsigned epsilon_q8,
+                             unsigned ratio_q16, unsigned long long *vertex_offsets, int *vertices,
+                             unsigned long long vertex_capacity, long long *measures);
+/* Host-only, needs no device: the same rule in plain C++ on n_records chains in host memory (what a caller of
+ * canny_hip_canny_contours or canny_hip_contours_from_bits holds).  vertex_offsets has n_records + 1 entries. */
+int canny_hip_polygons_from_chains(const unsigned long long *chain_offsets, const int *points,
+                                   unsigned long long n_records, unsigned long long point_capacity, int width, int height,
+                                   unsigned epsilon_q8, unsigned ratio_q16, unsigned long long *vertex_offsets,
+                                   int *vertices, unsigned long long vertex_capacity, long long *measures);
 
 /* ---- Euclidean distance transform ----------------------------------------------------------------------------------------
  * For every pixel of every frame the distance to the nearest edge pixel, on the GPU, queued behind the detector on the same
@@ -931,6 +1039,8 @@ int canny_hip_hough_segments_profile_get(canny_hip_ctx *ctx, int part, double *t
 int canny_hip_contours_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches);
 /* ... and for the four parts of the Hough circles (CANNY_HIP_CIRCLE_PART_*). */
 int canny_hip_hough_circles_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches);
+/* ... and for the three parts of the polygon approximation (CANNY_HIP_POLYGON_PART_*). */
+int canny_hip_polygons_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches);
 
 /* ---- self-test hooks used by the GPU test-suite -------------------------------------------- */
 /* Runs the DEVICE magnitude / angle-bin functions over every (gx,gy) in [-lim,lim]^2 and writes
