@@ -60,6 +60,8 @@ def layout_of(shape, order: str = "bgr", batch: bool = False) -> int:
 AUTO_MEDIAN, AUTO_QUANTILE = 1, 2
 # Context.selftest_sobel_pixel forms (enum canny_hip_pixel_form)
 PIXEL_LDS_TILE, PIXEL_PACKED_I16, PIXEL_F32, PIXEL_F32_FLOOR = 0, 1, 2, 3
+# Context.selftest_workspaces kinds (enum canny_hip_workspace_kind)
+WS_DATA, WS_INDEX, WS_CACHE = 0, 1, 2
 _AUTO_RULES = {"median": AUTO_MEDIAN, "quantile": AUTO_QUANTILE, AUTO_MEDIAN: AUTO_MEDIAN, AUTO_QUANTILE: AUTO_QUANTILE}
 
 
@@ -102,7 +104,7 @@ EXPORTS = (
     "canny_hip_edt_profile_get",
     "canny_hip_hough_segments_from_bits", "canny_hip_dev_hough_segments_bits", "canny_hip_dev_canny_hough_segments",
     "canny_hip_canny_hough_segments", "canny_hip_hough_segments_profile_get",
-    "canny_hip_selftest_histogram", "canny_hip_selftest_select",
+    "canny_hip_selftest_histogram", "canny_hip_selftest_select", "canny_hip_selftest_workspace",
     "canny_hip_hough_circles_step_of", "canny_hip_hough_circles_from_bits", "canny_hip_dev_hough_circles_bits",
     "canny_hip_dev_canny_hough_circles", "canny_hip_canny_hough_circles", "canny_hip_dev_hough_circles_steps",
     "canny_hip_hough_circles_profile_get",
@@ -250,6 +252,7 @@ def load() -> C.CDLL:
         "canny_hip_hough_segments_profile_get": ([p, i, C.POINTER(C.c_double), C.POINTER(C.c_long)], i),
         "canny_hip_selftest_histogram": ([p, p, i, i, i, i, i, p], i),
         "canny_hip_selftest_select": ([p, p, i, i, f, f, p], i),
+        "canny_hip_selftest_workspace": ([p, i, C.POINTER(C.c_char_p), pp, C.POINTER(sz), ip], i),
         "canny_hip_hough_circles_step_of": ([i, i, ip, ip], i),
         "canny_hip_hough_circles_from_bits": ([p, p, p, i, i, i, i, i, i, i, i, i, p, ip, ip, p], i),
         "canny_hip_dev_hough_circles_bits": ([p, p, p, p, i, i, i, i, i, i, i, i, i, i, p, p, p, p], i),
@@ -1420,6 +1423,20 @@ class Context:
                                                       C.c_void_p(d_pairs)), "selftest_select")
 
     # ---- device-pointer stage API (ints are device addresses; n_frames contiguous planes) -------
+    def selftest_workspaces(self):
+        """Every device workspace of the context as (name, device pointer, allocated bytes, kind) -- kind is WS_DATA,
+        WS_INDEX or WS_CACHE (canny_hip_selftest_workspace).  Synchronises the stream; launches and changes nothing."""
+        out, index = [], 0
+        while True:
+            name, ptr, size, kind = C.c_char_p(), C.c_void_p(), C.c_size_t(), C.c_int()
+            st = self._L.canny_hip_selftest_workspace(self._h, index, C.byref(name), C.byref(ptr), C.byref(size),
+                                                      C.byref(kind))
+            if st == 1 and index > 0:  # CANNY_HIP_ERR_INVALID: past the end
+                return out
+            self._check(st, "selftest_workspace")
+            out.append((name.value.decode(), ptr.value or 0, size.value, kind.value))
+            index += 1
+
     def dev_gaussian(self, d_img: int, sigma: float, h: int, w: int, n: int, d_out: int):
         self._check(self._L.canny_hip_dev_gaussian(self._h, C.c_void_p(d_img), sigma, h, w, n, C.c_void_p(d_out)),
                     "dev_gaussian")

@@ -402,6 +402,7 @@ struct canny_hip_ctx {
     DevBuf circ_accum, circ_ws;
     DevBuf plane_s, plane_c, stamps, flags; // hysteresis bit-planes / scheduling words
     DevBuf io[4];     // staging for the host-pointer stage functions
+    std::string ws_name; // canny_hip_selftest_workspace: the name it handed out last
     unsigned *host_flags = nullptr;     // pinned + mapped, 4 words per lane: last_change, domain, sequence number, spare
     unsigned *host_flags_dev = nullptr; // the same memory as the device sees it
     unsigned publish_seq = 0;           // sequence number of the last launch_hyst_publish
@@ -1804,6 +1805,61 @@ int ensure_copy_streams(canny_hip_ctx *ctx, canny_hip_ctx::BatchPipe &w)
     if (!w.s_h2d) HIP_TRY(ctx, hipStreamCreateWithFlags(&w.s_h2d, hipStreamNonBlocking));
     if (!w.s_d2h) HIP_TRY(ctx, hipStreamCreateWithFlags(&w.s_d2h, hipStreamNonBlocking));
     return CANNY_HIP_OK;
+}
+
+// Every device workspace of a context, in struct order, for canny_hip_selftest_workspace: one line per DevBuf member of
+// canny_hip_ctx (DESIGN.md section 20 has a row for each), then the staging of the cached batch pipelines and the
+// workspaces of the sub-contexts they own.  Pipeline 0 computes on the context itself, so only its staging is new.
+struct WsEntry {
+    std::string name;
+    const DevBuf *buf;
+    int kind;
+};
+
+void collect_workspaces(const canny_hip_ctx *c, const std::string &prefix, std::vector<WsEntry> &v)
+{
+    const int D = CANNY_HIP_WS_DATA, I = CANNY_HIP_WS_INDEX;
+    auto add = [&](const char *name, const DevBuf &b, int kind) { v.push_back({prefix + name, &b, kind}); };
+    add("tmp_f32", c->tmp_f32, D);
+    add("smoothed", c->smoothed, D);
+    add("edges16", c->edges16, D);
+    add("gray", c->gray, D);
+    add("hist", c->hist, D);
+    add("thr", c->thr, D);
+    add("points", c->points, I);           // row prefixes: the scatter's write offsets
+    add("hough_accum", c->hough_accum, D);
+    add("hough_ws", c->hough_ws, I);       // cut words: the select pass's slot counters
+    add("hough_tab", c->hough_tab, CANNY_HIP_WS_CACHE);
+    add("cc_parent", c->cc_parent, I);
+    add("cc_ws", c->cc_ws, I);
+    add("ct_ws", c->ct_ws, I);
+    add("pg_ws", c->pg_ws, I);             // block sums of the vertex scan
+    add("pg_points", c->pg_points, I);     // pixel indices the stage decodes
+    add("edt_cols", c->edt_cols, I);       // reused as the column scan's stack of row numbers
+    add("edt_stack", c->edt_stack, I);
+    add("seg_ws", c->seg_ws, I);
+    add("seg_lines", c->seg_lines, I);     // bases decode into table rows, counts bound loops
+    add("seg_work", c->seg_work, D);
+    add("circ_accum", c->circ_accum, D);
+    add("circ_ws", c->circ_ws, I);         // bases address accumulator cells, peak counts bound loops
+    add("plane_s", c->plane_s, D);
+    add("plane_c", c->plane_c, D);
+    add("stamps", c->stamps, I);           // tile queues and their counters
+    add("flags", c->flags, D);
+    for (int k = 0; k < 4; k++) add(("io" + std::to_string(k)).c_str(), c->io[k], I); // whatever a stage call staged last
+    for (size_t p = 0; p < c->batch_pool.size(); p++) {
+        const canny_hip_ctx::BatchPipe *w = c->batch_pool[p];
+        if (!w) continue;
+        const std::string pipe = prefix + "pipe" + std::to_string(p) + ".";
+        for (int s = 0; s < canny_hip_ctx::BatchPipe::kSlots; s++) {
+            const std::string slot = pipe + "slot" + std::to_string(s) + ".";
+            v.push_back({slot + "d_in", &w->slot[s].d_in, D});
+            v.push_back({slot + "d_out", &w->slot[s].d_out, D});
+            v.push_back({slot + "d_out8", &w->slot[s].d_out8, D});
+            v.push_back({slot + "d_thr", &w->slot[s].d_thr, D});
+        }
+        if (w->owns_sub && w->sub) collect_workspaces(w->sub, pipe, v);
+    }
 }
 
 } // namespace
@@ -4472,6 +4528,25 @@ int canny_hip_selftest_select(canny_hip_ctx *ctx, const unsigned int *d_hist, in
     if (!d_hist || !d_pairs || !auto_params_valid(rule, low, high)) return CANNY_HIP_ERR_INVALID;
     if ((rc = check_dims(1, 1, n_frames))) return rc;
     HIP_TRY(ctx, launch_thr_select(d_hist, n_frames, rule, low, high, d_pairs, ctx->stream));
+    return CANNY_HIP_OK;
+}
+
+// Workspace `index` of the context as it stands: no launch, no allocation, nothing of the workspaces changes.
+int canny_hip_selftest_workspace(canny_hip_ctx *ctx, int index, const char **name, void **d_ptr, size_t *bytes, int *kind)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (index < 0 || !name || !d_ptr || !bytes || !kind) return CANNY_HIP_ERR_INVALID;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (ctx->has_pend) return CANNY_HIP_ERR_INVALID; // a streamed batch's sweeps still own the planes
+    std::vector<WsEntry> all;
+    collect_workspaces(ctx, "", all);
+    if ((size_t)index >= all.size()) return CANNY_HIP_ERR_INVALID;
+    ctx->ws_name = all[(size_t)index].name;
+    *name = ctx->ws_name.c_str();
+    *d_ptr = all[(size_t)index].buf->p;
+    *bytes = all[(size_t)index].buf->bytes;
+    *kind = all[(size_t)index].kind;
     return CANNY_HIP_OK;
 }
 

@@ -52,7 +52,8 @@
 extern "C" {
 #endif
 
-#define CANNY_HIP_VERSION 1200       /* 0.12.0: + polygon approximation of the contour chains, on the GPU */
+#define CANNY_HIP_VERSION 1201       /* 0.12.1: + canny_hip_selftest_workspace */
+/* 0.12.0: + polygon approximation of the contour chains, on the GPU */
 /* 0.10.0: + outer contour chains of the finished map, traced on the GPU */
 /* 0.11.0: + Hough circles: gradient rays, centre peaks, radius by support */
 /* 0.9.1: + canny_hip_selftest_histogram, canny_hip_selftest_select */
@@ -1097,6 +1098,19 @@ int canny_hip_selftest_histogram(canny_hip_ctx *ctx, const void *d_plane, int pl
  * unsigned int; d_pairs (device, 2 * n_frames ints) receives the clamped pairs.  Asynchronous like the above. */
 int canny_hip_selftest_select(canny_hip_ctx *ctx, const unsigned int *d_hist, int n_frames, int rule, float low, float high,
                               int *d_pairs);
+/* The device workspaces a context owns, one per index from 0 up, in the order of the members of the context (DESIGN.md
+ * section 20 has a row for each): name (valid until the next call on the context), current device pointer (null while
+ * it was never needed), allocated size, and what its words are to the kernels that read them:
+ *   DATA:  bits, votes, histogram bins, flags, distances, pixels: a consumer only compares or adds these words;
+ *   INDEX: words that some kernel uses as an index, offset or count that addresses memory (parent entries, CSR
+ *          prefixes, stack slots, queue entries); a buffer with one such part is INDEX as a whole;
+ *   CACHE: contents kept on purpose between calls (the Hough vote tables, with their key on the host).
+ * After the members come the device staging of every cached batch pipeline ("pipe0.slot1.d_in" ...) and the workspaces
+ * of the sub-contexts that pipelines 1.. compute on ("pipe1.plane_s" ...).  CANNY_HIP_ERR_INVALID past the end, and while
+ * a canny_hip_dev_canny_stream batch is still pending (flush first).  Synchronises the context's stream, launches
+ * nothing and changes nothing. */
+enum canny_hip_workspace_kind { CANNY_HIP_WS_DATA = 0, CANNY_HIP_WS_INDEX = 1, CANNY_HIP_WS_CACHE = 2 };
+int canny_hip_selftest_workspace(canny_hip_ctx *ctx, int index, const char **name, void **d_ptr, size_t *bytes, int *kind);
 
 #ifdef __cplusplus
 }
