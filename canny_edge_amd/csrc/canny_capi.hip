@@ -992,14 +992,14 @@ int dev_canny(canny_hip_ctx *ctx, const unsigned char *d_img, float sigma, int l
         }
         // d_edges now holds the strong pixels; the sweeps add every pixel they promote: no finalize pass
         if (ctx->hyst_tail && g.tiles_x * g.tiles_y <= kTailMaxTiles) {
-            // two batch-wide sweeps (all tiles; then the tiles those re-scheduled), then one workgroup per frame
-            // runs the rest to convergence: everything is queued, nothing is waited for
+            // two batch-wide sweeps (all tiles; then the tiles those re-scheduled, from the per-frame queues), then one
+            // workgroup per frame runs the rest to convergence: everything is queued, nothing is waited for
             StageTimer tm(ctx, CANNY_HIP_STAGE_HYST_PROPAGATE);
             unsigned *sched = (unsigned *)ctx->stamps.p, *flags = (unsigned *)ctx->flags.p;
             const int wide = ctx->hyst_tail_after;
             for (int k = 0; k < wide; k++)
                 HIP_TRY(ctx, launch_hyst_propagate(S, C, sched, flags, k, g, ctx->stream, d_edges, edge_value,
-                                                   /*to_frame_queues=*/k == wide - 1));
+                                                   /*frame_queues=*/true));
             HIP_TRY(ctx, launch_hyst_tail(S, C, sched, flags, wide, g, ctx->stream, d_edges, edge_value));
             ctx->hyst_iters_async = true;
             return CANNY_HIP_OK;

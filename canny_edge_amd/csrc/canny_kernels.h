@@ -274,13 +274,15 @@ hipError_t launch_hyst_prepare(uint64_t *strong, uint64_t *conn, const HystGeom 
                                unsigned *flags, hipStream_t stream, int n_lanes = 1);
 // edges != nullptr: an edge map that already holds the initially strong pixels; each sweep writes edge_value
 // into the pixels it promotes, so the map is final when propagation has converged (no finalize pass).
-// to_frame_queues: the tiles this sweep schedules go into their frame's queue (the sweep before launch_hyst_tail).
+// frame_queues: the route that ends in launch_hyst_tail (frames of at most 4096 tiles).  The tiles a sweep schedules go
+// into their FRAME's queue, and a sweep >= 1 walks those queues, a few workgroups per frame: the appends of a batch meet
+// on one counter word per frame instead of one per batch.  All sweeps of a call use the same setting.
 hipError_t launch_hyst_propagate(uint64_t *strong, const uint64_t *conn, unsigned *sched, unsigned *last_change,
                                  int iter, const HystGeom &g, hipStream_t stream, int16_t *edges = nullptr,
-                                 int edge_value = 0, bool to_frame_queues = false);
+                                 int edge_value = 0, bool frame_queues = false);
 // Every sweep from first_iter on, to convergence, in ONE launch: one workgroup per frame walks that frame's queue
-// with a workgroup barrier between sweeps (frames are independent; see hyst_tail_kernel).  The sweep first_iter - 1
-// must have been launched with to_frame_queues = true.  No host round trip: the propagation is complete when the
+// with a workgroup barrier between sweeps (frames are independent; see hyst_tail_kernel).  The sweeps before it
+// must have been launched with frame_queues = true.  No host round trip: the propagation is complete when the
 // stream has passed this kernel.
 hipError_t launch_hyst_tail(uint64_t *strong, const uint64_t *conn, unsigned *sched, unsigned *last_change,
                             int first_iter, const HystGeom &g, hipStream_t stream, int16_t *edges = nullptr,

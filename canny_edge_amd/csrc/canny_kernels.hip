@@ -695,7 +695,8 @@ __device__ __forceinline__ uint64_t fill_runs(uint64_t p, uint64_t g)
 //   queue[2][tiles] tiles to run in sweep k are queue[k & 1][0 .. count[k % 3])
 //   count[3]        sweep k reads count[k%3], appends to count[(k+1)%3] and clears count[(k+2)%3]
 //   fq0/fq1[tiles]  the same two queues PER FRAME (frame f owns [f * tiles_per_frame, (f+1) * tiles_per_frame)),
-//   fcount[4 * frames] ... and their counters (3 used per frame): what hyst_tail_kernel walks, one workgroup per frame
+//   fcount[4 * frames] ... and their counters (3 used per frame, rotating like count[3]): what the sweeps of the tail
+//                   route append to and walk -- the launch-per-sweep kernel a few workgroups per frame, hyst_tail_kernel one
 struct HystSched {
     unsigned *stamp, *queue0, *queue1, *count;
     unsigned *fq0, *fq1, *fcount;
@@ -757,16 +758,31 @@ __device__ __forceinline__ TileIn load_tile(int t, int lane, const uint64_t *__r
     return in;
 }
 
+// Schedules the up-to-eight neighbours of one tile for sweep nxt with ONE reservation in the queue.  Called by the whole
+// wave; the lanes with `want` hold one neighbour each (stamp word `slot`, queue entry `entry`).  The lanes whose stamp
+// exchange won (the first to stamp that tile for this sweep) are counted, lane 0 reserves that many slots and each winner
+// writes at its rank: one returning atomic on the counter per tile instead of one per neighbour.
+__device__ __forceinline__ void push_neighbours(bool want, int lane, unsigned *stamp, unsigned slot, unsigned entry,
+                                                unsigned nxt, unsigned *q, unsigned *cnt)
+{
+    const bool won = want && atomicExch(&stamp[slot], nxt) != nxt;
+    const uint64_t winners = __ballot(won);
+    if (winners == 0) return; // wave-uniform
+    unsigned first = 0;
+    if (lane == 0) first = atomicAdd(cnt, (unsigned)__popcll(winners));
+    first = (unsigned)__builtin_amdgcn_readlane((int)first, 0);
+    if (won) q[first + (unsigned)__popcll(winners & ((1ull << lane) - 1ull))] = entry;
+}
+
 // c = this lane's word of the tile's connectable plane (the caller has checked that the tile has any), in = the
 // tile as load_tile() returned it.
-// to_frame: neighbours are queued in their FRAME's queue (for hyst_tail_kernel) instead of the batch-wide one.
-// push(nb): schedules tile nb for sweep iter + 1 (once per sweep); called by up to eight lanes at once, each with a
-// different neighbour tile.
+// push(want, nb): called by the whole wave when the tile changed; the lanes with `want` (up to eight, each with a
+// different neighbour tile nb) schedule nb for sweep iter + 1 (once per sweep), and the caller's record of the last
+// sweep that scheduled anything is brought up to date if any lane wants to.
 template <class Push>
-__device__ __forceinline__ void process_tile_with(int t, int lane, uint64_t *__restrict__ strong,
-                                                  unsigned *__restrict__ last_change, int iter, const HystGeom &g,
-                                                  int16_t *__restrict__ edges, int edge_value, uint64_t c,
-                                                  const TileIn &in, Push push_tile)
+__device__ __forceinline__ void process_tile_with(int t, int lane, uint64_t *__restrict__ strong, int iter,
+                                                  const HystGeom &g, int16_t *__restrict__ edges, int edge_value,
+                                                  uint64_t c, const TileIn &in, Push push_tiles)
 {
     const int tpf = g.tiles_x * g.tiles_y;
     const int tt = t % tpf;
@@ -843,12 +859,26 @@ __device__ __forceinline__ void process_tile_with(int t, int lane, uint64_t *__r
                                  : (dx == 0 ? facing != 0 : (dx < 0 ? (facing & 1ull) != 0 : (facing >> 63) != 0));
         const bool there = (dy >= 0 || hasU) && (dy <= 0 || hasD) && (dx >= 0 || hasL) && (dx <= 0 || hasR);
         const bool want = lane < 8 && hit && there;
-        if (want) push_tile(t + dy * g.tiles_x + dx);
-        if (__any(want) && lane == 0) atomicMax(last_change, (unsigned)iter + 1u);
+        push_tiles(want, t + dy * g.tiles_x + dx);
     }
 }
 
-// ... with the queues in global memory (batch-wide, or per frame for the sweep that hands over to hyst_tail_kernel)
+// last_change = the largest iter + 1 of any sweep that scheduled a tile (what the host's convergence test and
+// canny_hip_ctx_last_hysteresis_iterations read).  Every writer of a launch-per-sweep kernel writes the same iter + 1 and
+// kernel boundaries order the sweeps, so the word is read first and the atomic issued only while it is still smaller:
+// after the first few have landed nobody else issues one.  (One atomicMax per pushing tile was 10-12 thousand
+// read-modify-writes of ONE word in sweep 0 of a 128 x 4K batch, and a word takes them one at a time.)  A stale read
+// only costs an atomic that was not needed.  The read comes AFTER the tile's pushes: issued ahead of them, to return
+// under their round trips, it sees the word before the first writers have landed far more often, and sweep 1 of a
+// 128 x 4K batch took 42 us instead of 26.
+__device__ __forceinline__ void note_push(unsigned *last_change, unsigned nxt)
+{
+    if (__hip_atomic_load(last_change, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < nxt) atomicMax(last_change, nxt);
+}
+
+// ... with the queues in global memory: batch-wide, or per frame (to_frame: the sweeps of the route that ends in
+// hyst_tail_kernel).  A batch-wide sweep appends through ONE counter word, and a word takes its atomics one at a time;
+// per frame the appends of a 128-frame batch meet on 128 words.  A tile's neighbours all lie in its own frame.
 __device__ __forceinline__ void process_tile(int t, int lane, uint64_t *__restrict__ strong, const HystSched &sch,
                                              unsigned *__restrict__ last_change, int iter, const HystGeom &g,
                                              int16_t *__restrict__ edges, int edge_value, uint64_t c,
@@ -863,8 +893,9 @@ __device__ __forceinline__ void process_tile(int t, int lane, uint64_t *__restri
         q = ((nxt & 1u) ? sch.fq1 : sch.fq0) + (size_t)f * tpf;
         cnt = sch.fcount + 4 * (size_t)f + nxt % 3u;
     }
-    process_tile_with(t, lane, strong, last_change, iter, g, edges, edge_value, c, in, [&](int nb) {
-        if (atomicExch(&sch.stamp[nb], nxt) != nxt) q[atomicAdd(cnt, 1u)] = (unsigned)nb;
+    process_tile_with(t, lane, strong, iter, g, edges, edge_value, c, in, [&](bool want, int nb) {
+        push_neighbours(want, lane, sch.stamp, (unsigned)nb, (unsigned)nb, nxt, q, cnt);
+        if (__any(want) && lane == 0) note_push(last_change, nxt);
     });
 }
 
@@ -885,11 +916,16 @@ __device__ __forceinline__ void propagate_tile(int t, int lane, uint64_t *__rest
 // Sweep 0 visits every tile (grid = tiles / (4 kSweep0Tiles) workgroups); later sweeps are launched with a small fixed
 // grid whose waves walk the work queue, so a sweep with little or nothing to do costs one short launch
 // instead of 130 k waves that each read a stamp and exit.
+// frame_groups = 0: the batch-wide queue (the routes whose host polls for convergence).
+// frame_groups > 0: the per-frame queues (the route that ends in hyst_tail_kernel) -- every sweep appends to its tiles'
+// frames' queues, and a sweep >= 1 is launched with frame_groups workgroups per frame, whose waves stride over that
+// frame's queue.
 __global__ __launch_bounds__(256) void hyst_propagate_kernel(uint64_t *__restrict__ strong,
                                                              const uint64_t *__restrict__ conn,
                                                              unsigned *__restrict__ sched_words,
                                                              unsigned *__restrict__ last_change, int iter, HystGeom g,
-                                                             int16_t *__restrict__ edges, int edge_value, int to_frame)
+                                                             int16_t *__restrict__ edges, int edge_value,
+                                                             int frame_groups)
 {
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
@@ -910,7 +946,25 @@ __global__ __launch_bounds__(256) void hyst_propagate_kernel(uint64_t *__restric
 #pragma unroll
             for (int k = 0; k < kSweep0Tiles; k++)
                 propagate_tile(t0 + k, lane, strong, conn, sch, last_change, iter, g, edges, edge_value, c[k],
-                               to_frame != 0);
+                               frame_groups > 0);
+        }
+        return;
+    }
+    if (frame_groups > 0) {
+        const int tpf = g.tiles_x * g.tiles_y;
+        const int f = (int)blockIdx.x / frame_groups, part = (int)blockIdx.x - f * frame_groups;
+        unsigned *const fcount = sch.fcount + 4 * (size_t)f;
+        if (part == 0 && threadIdx.x == 0) fcount[(iter + 2) % 3] = 0; // the slot this frame's sweep iter+1 appends to
+        // (a tile is queued once per sweep, so a counter never exceeds the frame's tiles: the min() only keeps corrupted
+        // scheduling words from turning into an out-of-bounds walk)
+        const unsigned n = min(__hip_atomic_load(fcount + iter % 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT),
+                               (unsigned)tpf);
+        const unsigned *q = ((iter & 1) ? sch.fq1 : sch.fq0) + (size_t)f * tpf;
+        const unsigned w = (unsigned)__builtin_amdgcn_readfirstlane(part * 4 + (int)(threadIdx.x >> 6));
+        for (unsigned i = w; i < n; i += (unsigned)frame_groups * 4u) {
+            const int t = (int)q[i];
+            propagate_tile(t, lane, strong, conn, sch, last_change, iter, g, edges, edge_value,
+                           conn[(size_t)t * kTile + lane], true);
         }
         return;
     }
@@ -919,7 +973,7 @@ __global__ __launch_bounds__(256) void hyst_propagate_kernel(uint64_t *__restric
     for (unsigned i = (unsigned)wave; i < n; i += (unsigned)n_waves) {
         const int t = (int)q[i];
         propagate_tile(t, lane, strong, conn, sch, last_change, iter, g, edges, edge_value,
-                       conn[(size_t)t * kTile + lane], to_frame != 0);
+                       conn[(size_t)t * kTile + lane]);
     }
 }
 
@@ -927,7 +981,7 @@ __global__ __launch_bounds__(256) void hyst_propagate_kernel(uint64_t *__restric
 // queue stays empty.  Frames never interact (the reference processes one frame per call, src/main.cpp:120-137), so a
 // frame's sweeps only have to be ordered among the waves that work on that frame -- a workgroup barrier -- and no
 // grid-wide barrier, no cross-workgroup visibility protocol and no host round trip is needed: after the two
-// batch-wide sweeps that do the bulk of the work (sweep 1 queues into the per-frame queues), this kernel replaces
+// batch-wide sweeps that do the bulk of the work (they queue into the per-frame queues), this kernel replaces
 // the 6+ nearly empty launches and the host's convergence poll of the multi-launch scheme.
 // The frame's two queues, their counters and the tile stamps live in LDS (48 KB: a frame has at most kTailTiles
 // tiles): a sweep of this kernel is a chain of dependent steps -- how many tiles, which tile, its words, the flood,
@@ -946,13 +1000,14 @@ __global__ __launch_bounds__(1024) void hyst_tail_kernel(uint64_t *__restrict__ 
     __shared__ unsigned s_queue[2][kTailTiles]; // tile numbers within the frame
     __shared__ unsigned s_stamp[kTailTiles];    // sweep for which a tile was last queued (dedupes pushes)
     __shared__ unsigned s_count[2];
+    __shared__ unsigned s_last; // the frame's largest iter + 1 of a sweep that scheduled a tile (0: none did)
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), n_waves = blockDim.x >> 6;
     const int f = blockIdx.x;
     const int tpf = g.tiles_x * g.tiles_y;
     const int t_base = f * tpf;
     const HystSched sch = make_sched(sched_words, g.tiles());
-    // what sweep first_iter - 1 (batch-wide, to_frame_queues) left for this frame
+    // what sweep first_iter - 1 (batch-wide, into the per-frame queues) left for this frame
     int cur = first_iter & 1;
     {
         const unsigned n0 = __hip_atomic_load(sch.fcount + 4 * (size_t)f + first_iter % 3, __ATOMIC_RELAXED,
@@ -964,8 +1019,10 @@ __global__ __launch_bounds__(1024) void hyst_tail_kernel(uint64_t *__restrict__ 
         if (threadIdx.x == 0) {
             s_count[cur] = n0;
             s_count[cur ^ 1] = 0;
+            s_last = 0;
         }
     }
+    unsigned pushed = 0; // this wave's part of s_last
     for (int iter = first_iter;; iter++, cur ^= 1) {
         __syncthreads(); // the previous sweep's stores and pushes (or the set-up above) are complete
         const unsigned n = s_count[cur];
@@ -982,12 +1039,18 @@ __global__ __launch_bounds__(1024) void hyst_tail_kernel(uint64_t *__restrict__ 
             const uint64_t c = conn[(size_t)t * kTile + lane];
             const TileIn in = load_tile(t, lane, strong, g);
             if (!__any(c != 0)) continue;
-            process_tile_with(t, lane, strong, last_change, iter, g, edges, edge_value, c, in, [&](int nb) {
+            process_tile_with(t, lane, strong, iter, g, edges, edge_value, c, in, [&](bool want, int nb) {
                 const unsigned loc = (unsigned)(nb - t_base);
-                if (atomicExch(&s_stamp[loc], nxt) != nxt) q_next[atomicAdd(n_next, 1u)] = loc;
+                push_neighbours(want, lane, s_stamp, loc, loc, nxt, q_next, n_next);
+                if (__any(want)) pushed = nxt; // sweeps only count up
             });
         }
     }
+    // The frames are at different sweeps at the same moment, so reading last_change first (as process_tile does) would
+    // not stop the later frames' atomics; instead a frame keeps its maximum here and issues ONE atomic when it is done.
+    if (lane == 0 && pushed != 0) atomicMax(&s_last, pushed);
+    __syncthreads();
+    if (threadIdx.x == 0 && s_last != 0) atomicMax(last_change, s_last);
 }
 
 __global__ __launch_bounds__(256) void hyst_finalize_kernel(int16_t *__restrict__ cand,
@@ -1371,16 +1434,25 @@ hipError_t launch_hyst_tail(uint64_t *strong, const uint64_t *conn, unsigned *sc
 
 hipError_t launch_hyst_propagate(uint64_t *strong, const uint64_t *conn, unsigned *stamp, unsigned *last_change,
                                  int iter, const HystGeom &g, hipStream_t stream, int16_t *edges, int edge_value,
-                                 bool to_frame_queues)
+                                 bool frame_queues)
 {
+    if (frame_queues && (g.n_frames < 1 || g.tiles_x * g.tiles_y > kTailTiles)) return hipErrorInvalidValue;
     unsigned blocks = (unsigned)((g.tiles() + 4 * kSweep0Tiles - 1) / (4 * kSweep0Tiles)); // sweep 0: all tiles
+    int frame_groups = frame_queues ? 1 : 0;
     if (iter > 0) { // queue walkers: at most 16 waves per CU, and no more than a wave per 4 tiles (a single frame's
                     // 2040 tiles: 128 workgroups instead of 1024, whose dispatch alone took 4 of a sweep's 9 us)
         const unsigned want = (unsigned)((g.tiles() + 15) / 16);
         blocks = want < 8u ? 8u : (want > 1024u ? 1024u : want);
+        if (frame_queues) {
+            // the same number of walkers, split evenly over the frames (128 x 4K: 8 workgroups per frame; one 4K
+            // frame: 128; at least one per frame)
+            frame_groups = (int)(blocks / (unsigned)g.n_frames);
+            if (frame_groups < 1) frame_groups = 1;
+            blocks = (unsigned)frame_groups * (unsigned)g.n_frames;
+        }
     }
     hipLaunchKernelGGL(hyst_propagate_kernel, dim3(blocks), dim3(256), 0, stream, strong, conn, stamp, last_change,
-                       iter, g, edges, edge_value, to_frame_queues ? 1 : 0);
+                       iter, g, edges, edge_value, frame_groups);
     return hipGetLastError();
 }
 // Row-major finalize: a wave writes 512 consecutive pixels of ONE row (1 KB contiguous, four rows per

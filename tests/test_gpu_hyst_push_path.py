@@ -1,0 +1,185 @@
+"""The hysteresis sweeps' push path: the queues a sweep schedules tiles in, and the word that says which sweep pushed last.
+
+The suite's synthetic frames converge in two or three sweeps, so the sweeps that walk the per-frame queues, the hand-over to
+the tail kernel and the polling routes' second look at the flag hardly run there.  The frames here are designed to need
+many sweeps: a one-pixel line of weak pixels across 9 tiles (or, transposed, down 9 tiles) that is strong only in its first
+`strong_cols` pixels, so the flood has to travel tile by tile.  The recipe (sigma 1.4, thresholds 50/150, 136 x 520 = 3 x 9
+tiles of 64 x 64, the last tile row and column 8 pixels deep): background 60, a step of lev = 120 (strong part) or 40 (weak
+part) below row 70, and row 70 itself at 60 + lev // 3 -- a symmetric step is suppressed entirely by the strict NMS compare,
+the intermediate row is what leaves a line.  strong_cols = 0 gives a frame full of weak pixels and no edge at all: whatever a
+neighbour's queue leaks into that frame shows.
+
+How many sweeps a frame needs is computed here, from the oracle's NMS plane, by a synchronous model of the tile sweeps (every
+tile of a sweep sees the planes as the previous sweep left them, floods to convergence and schedules the neighbours its
+changed border faces).  The device may be quicker -- a tile can see what a neighbour stored in the same sweep -- but not
+slower: by induction over the sweeps its planes hold at least the model's, so a border pixel is gained, and its neighbour
+scheduled, no later than in the model.  Hence the bounds on last_hysteresis_iterations (the last sweep that scheduled a tile,
+plus two): at least 2 when any frame of the batch pushes in sweep 0, at most the model's sweep count plus one."""
+import numpy as np
+import pytest
+
+import oracle
+from canny_edge_amd.synth import synth_frame
+
+pytestmark = pytest.mark.gpu
+
+SIGMA, LO, HI = 1.4, 50, 150
+H, W, T = 136, 520, 64
+STRONG_COLS = (24, 200, 0)
+# name -> options set on a fresh context; "stream" = dev_canny_stream + flush instead of dev_canny
+ROUTES = {
+    "default": {},
+    "tail_after_1": {"tune_hyst_tail_after": 1},
+    "tail_after_2": {"tune_hyst_tail_after": 2},
+    "tail_after_3": {"tune_hyst_tail_after": 3},
+    "tail_after_4": {"tune_hyst_tail_after": 4},
+    "no_tail": {"hysteresis_tail": 0},
+    "overlap": {"overlap_hysteresis": 1},
+    "stream": {},
+    "stream_no_tail": {"hysteresis_tail": 0},
+}
+
+_cache = {}
+
+
+def designed_frame(strong_cols):
+    img = np.full((H, W), 60, np.int32)
+    lev = np.where(np.arange(W) < strong_cols, 120, 40)
+    img[70, :] = 60 + lev // 3
+    img[71:, :] = 60 + lev
+    return img.astype(np.uint8)
+
+
+def model_sweeps(nms):
+    """Sweeps of the synchronous tile model, the last one (which schedules nothing) included."""
+    h, w = nms.shape
+    ty_n, tx_n = (h + T - 1) // T, (w + T - 1) // T
+    conn = np.zeros((ty_n * T + 2, tx_n * T + 2), bool)
+    strong = np.zeros_like(conn)
+    conn[1:h + 1, 1:w + 1] = nms >= LO
+    strong[1:h + 1, 1:w + 1] = nms >= HI
+    todo = [(ty, tx) for ty in range(ty_n) for tx in range(tx_n)]
+    sweeps = 0
+    while todo:
+        before, nxt = strong.copy(), set()
+        for ty, tx in todo:
+            y0, x0 = 1 + ty * T, 1 + tx * T
+            c = conn[y0:y0 + T, x0:x0 + T]
+            win = before[y0 - 1:y0 + T + 1, x0 - 1:x0 + T + 1].copy()
+            own = win[1:-1, 1:-1]
+            start = own.copy()
+            while True:
+                near = np.zeros((T, T), bool)
+                for dy in range(3):
+                    for dx in range(3):
+                        near |= win[dy:dy + T, dx:dx + T]
+                grown = own | (c & near)
+                if (grown == own).all():
+                    break
+                own[:] = grown
+            chg = own & ~start
+            if not chg.any():
+                continue
+            strong[y0:y0 + T, x0:x0 + T] = own
+            for dy, dx, hit in ((-1, 0, chg[0].any()), (1, 0, chg[-1].any()), (0, -1, chg[:, 0].any()),
+                                (0, 1, chg[:, -1].any()), (-1, -1, chg[0, 0]), (-1, 1, chg[0, -1]),
+                                (1, -1, chg[-1, 0]), (1, 1, chg[-1, -1])):
+                if hit and 0 <= ty + dy < ty_n and 0 <= tx + dx < tx_n:
+                    nxt.add((ty + dy, tx + dx))
+        todo = sorted(nxt)
+        sweeps += 1
+    return sweeps
+
+
+def _mix(transposed):
+    """The four distinct frames of one shape with their oracle maps and model sweep counts (computed once)."""
+    def make():
+        frames = [designed_frame(sc) for sc in STRONG_COLS]
+        if transposed:
+            frames = [np.ascontiguousarray(f.T) for f in frames]
+        h, w = frames[0].shape
+        frames.append(synth_frame(h, w, 11 + int(transposed)))
+        stages = [oracle.canny(f, SIGMA, LO, HI, stages=True) for f in frames]
+        for f, s in zip(frames, stages):
+            assert np.array_equal(s["edges"], oracle.canny(f, SIGMA, LO, HI))
+        return {"frames": np.stack(frames), "want": np.stack([s["edges"] for s in stages]),
+                "sweeps": [model_sweeps(s["nms"]) for s in stages]}
+    key = ("mix", transposed)
+    if key not in _cache:
+        _cache[key] = make()
+    return _cache[key]
+
+
+def _batch(transposed, n):
+    m = _mix(transposed)
+    pick = np.arange(n) % len(m["frames"])
+    return m["frames"][pick], m["want"][pick], pick
+
+
+def _run(ctx, frames, stream=False):
+    n, h, w = frames.shape
+    d_in, d_out = ctx.malloc(frames.nbytes), ctx.malloc(frames.nbytes * 2)
+    try:
+        ctx.h2d(d_in, frames)
+        ctx.h2d(d_out, np.full(frames.shape, 0x5A5A, np.int16))
+        if stream:
+            ctx.dev_canny_stream(d_in, SIGMA, LO, HI, h, w, n, d_out)
+            ctx.dev_canny_stream_flush()
+        else:
+            ctx.dev_canny(d_in, SIGMA, LO, HI, h, w, n, d_out)
+        ctx.synchronize()
+        iters = ctx.last_hysteresis_iterations
+        out = np.empty(frames.shape, np.int16)
+        ctx.d2h(out, d_out)
+    finally:
+        ctx.free(d_in)
+        ctx.free(d_out)
+    return out, iters
+
+
+@pytest.mark.parametrize("transposed", (False, True))
+def test_designed_frames_stay_hard(transposed):
+    """The inputs cannot go soft: the model needs 7 or more sweeps for one frame, different numbers for two, and a single
+    sweep for the frame without a strong pixel, whose oracle map is empty while the strong-ended lines are kept whole."""
+    m = _mix(transposed)
+    sweeps = m["sweeps"]
+    print("model sweeps per frame:", sweeps)
+    assert max(sweeps) >= 7
+    assert len(set(sweeps[:2])) == 2
+    assert sweeps[2] == 1 and not m["want"][2].any()
+    assert np.count_nonzero(m["want"][0]) >= W and np.count_nonzero(m["want"][1]) >= W
+
+
+@pytest.mark.parametrize("smoothed_u8", (0, 1))
+@pytest.mark.parametrize("route", sorted(ROUTES))
+@pytest.mark.parametrize("transposed", (False, True))
+def test_every_route_matches_the_oracle(hip, transposed, route, smoothed_u8):
+    sweeps = _mix(transposed)["sweeps"]
+    for n in (4, 17):   # 17: overlap_hysteresis really splits the batch (8 + 9 frames)
+        frames, want, pick = _batch(transposed, n)
+        with hip.Context(0) as ctx:
+            ctx.set_option("smoothed_u8", smoothed_u8)
+            for name, value in ROUTES[route].items():
+                ctx.set_option(name, value)
+            got, iters = _run(ctx, frames, stream=route.startswith("stream"))
+        for i in range(n):
+            bad = int((got[i] != want[i]).sum())
+            assert bad == 0, f"{route}, {n} frames: frame {i} (kind {pick[i]}) differs from the oracle in {bad} pixels"
+            if pick[i] == 2:
+                assert not got[i].any(), f"{route}, {n} frames: the frame without a strong pixel has edges"
+        print(f"{route} u8={smoothed_u8} n={n}: last_hysteresis_iterations {iters}, model {max(sweeps)}")
+        assert 2 <= iters <= max(sweeps) + 1, f"{route}, {n} frames: {iters} sweeps reported, model {sweeps}"
+
+
+@pytest.mark.parametrize("transposed", (False, True))
+def test_each_frame_alone_gives_the_batch_map(hip, transposed):
+    m = _mix(transposed)
+    frames, _, pick = _batch(transposed, 17)
+    with hip.Context(0) as ctx:
+        in_batch, _ = _run(ctx, frames)
+        for k in range(len(m["frames"])):
+            alone, iters = _run(ctx, m["frames"][k:k + 1])
+            assert np.array_equal(alone[0], m["want"][k])
+            assert 1 <= iters <= m["sweeps"][k] + 1, f"frame kind {k} alone: {iters} sweeps reported, model {m['sweeps'][k]}"
+            for i in np.flatnonzero(pick == k):
+                assert np.array_equal(in_batch[i], alone[0]), f"frame {i} (kind {k}) differs between batch and alone"
