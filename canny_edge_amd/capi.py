@@ -15,6 +15,7 @@ is present, the call raises.
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import os
 import threading
@@ -62,6 +63,10 @@ AUTO_MEDIAN, AUTO_QUANTILE = 1, 2
 PIXEL_LDS_TILE, PIXEL_PACKED_I16, PIXEL_F32, PIXEL_F32_FLOOR = 0, 1, 2, 3
 # Context.selftest_workspaces kinds (enum canny_hip_workspace_kind)
 WS_DATA, WS_INDEX, WS_CACHE = 0, 1, 2
+# launch_plan kinds (enum canny_hip_launch_plan_kind)
+PLAN_KINDS = ("points_rows", "scan_frames", "cc_tiles", "cc_rows", "cc_fixup", "ct_rows", "edt_rows", "edt_columns",
+              "pg_records", "pg_scan_sums", "hough_vote_strong", "hough_vote_bits", "hough_vote_points", "hough_cells",
+              "circles_vote_strong", "circles_vote_bits", "circles_steps", "to_gray")
 _AUTO_RULES = {"median": AUTO_MEDIAN, "quantile": AUTO_QUANTILE, AUTO_MEDIAN: AUTO_MEDIAN, AUTO_QUANTILE: AUTO_QUANTILE}
 
 
@@ -105,6 +110,7 @@ EXPORTS = (
     "canny_hip_hough_segments_from_bits", "canny_hip_dev_hough_segments_bits", "canny_hip_dev_canny_hough_segments",
     "canny_hip_canny_hough_segments", "canny_hip_hough_segments_profile_get",
     "canny_hip_selftest_histogram", "canny_hip_selftest_select", "canny_hip_selftest_workspace",
+    "canny_hip_selftest_launch_plan",
     "canny_hip_hough_circles_step_of", "canny_hip_hough_circles_from_bits", "canny_hip_dev_hough_circles_bits",
     "canny_hip_dev_canny_hough_circles", "canny_hip_canny_hough_circles", "canny_hip_dev_hough_circles_steps",
     "canny_hip_hough_circles_profile_get",
@@ -253,6 +259,7 @@ def load() -> C.CDLL:
         "canny_hip_selftest_histogram": ([p, p, i, i, i, i, i, p], i),
         "canny_hip_selftest_select": ([p, p, i, i, f, f, p], i),
         "canny_hip_selftest_workspace": ([p, i, C.POINTER(C.c_char_p), pp, C.POINTER(sz), ip], i),
+        "canny_hip_selftest_launch_plan": ([i, i, i, i, C.c_longlong, p], i),
         "canny_hip_hough_circles_step_of": ([i, i, ip, ip], i),
         "canny_hip_hough_circles_from_bits": ([p, p, p, i, i, i, i, i, i, i, i, i, p, ip, ip, p], i),
         "canny_hip_dev_hough_circles_bits": ([p, p, p, p, i, i, i, i, i, i, i, i, i, i, p, p, p, p], i),
@@ -597,6 +604,25 @@ def march_order(n_segs: int, n_strips: int) -> np.ndarray:
     if st:
         raise CannyHipError(st, "selftest_march_order")
     return out
+
+
+LaunchPlan = collections.namedtuple("LaunchPlan", "units per_group grid trips aux")
+
+
+def launch_plan(kind, n_frames: int = 1, height: int = 1, width: int = 1, extra: int = 0) -> "LaunchPlan":
+    """Host-only: how the capped grid of a launch divides its work.  kind is a name of PLAN_KINDS
+    or its number; extra: the capacity, cell, pair or pixel count of the kinds sized by it, and the points of the frame
+    for "hough_vote_points".  units: work items of the launch (of one frame for the Hough and circle votes and the cell passes),
+    per_group: items a workgroup takes per trip of its grid-stride loop, grid: workgroups, trips: ceil(units / (grid *
+    per_group)) -- 2 or more means some workgroup takes a second item --, aux: rows per wave for "edt_rows", else 0.
+    The launchers take their grids from the helpers this reports, so it cannot drift from what runs."""
+    k = PLAN_KINDS.index(kind) if isinstance(kind, str) else int(kind)
+    out = np.zeros(5, np.uint64)
+    st = load().canny_hip_selftest_launch_plan(k, int(n_frames), int(height), int(width), int(extra),
+                                               out.ctypes.data_as(C.c_void_p))
+    if st:
+        raise CannyHipError(st, "selftest_launch_plan")
+    return LaunchPlan(*(int(v) for v in out))
 
 
 def fma_div_table():

@@ -4406,6 +4406,58 @@ int canny_hip_selftest_march_order(int n_segs, int n_strips, int *out_pairs)
     return CANNY_HIP_OK;
 }
 
+// Host-only: the launch plan of a capped grid, from the helper its launchers take their grid from (canny_kernels.h).
+int canny_hip_selftest_launch_plan(int kind, int n_frames, int height, int width, long long extra,
+                                   unsigned long long *out)
+{
+    if (!out) return CANNY_HIP_ERR_INVALID;
+    LaunchPlan p;
+    switch (kind) {
+    case CANNY_HIP_PLAN_CC_FIXUP:
+    case CANNY_HIP_PLAN_PG_RECORDS:
+    case CANNY_HIP_PLAN_PG_SCAN_SUMS:
+    case CANNY_HIP_PLAN_HOUGH_CELLS:
+    case CANNY_HIP_PLAN_CIRCLES_STEPS:
+    case CANNY_HIP_PLAN_TO_GRAY: // sized by `extra` alone
+        if (extra < 1) return CANNY_HIP_ERR_INVALID;
+        p = kind == CANNY_HIP_PLAN_CC_FIXUP       ? plan_cc_fixup((unsigned long long)extra)
+            : kind == CANNY_HIP_PLAN_PG_RECORDS   ? plan_pg_records((unsigned long long)extra)
+            : kind == CANNY_HIP_PLAN_PG_SCAN_SUMS ? plan_pg_scan_sums((unsigned long long)extra)
+            : kind == CANNY_HIP_PLAN_HOUGH_CELLS  ? plan_hough_cells((unsigned long long)extra)
+            : kind == CANNY_HIP_PLAN_CIRCLES_STEPS ? plan_circles_steps((size_t)extra)
+                                                  : plan_to_gray((size_t)extra);
+        break;
+    case CANNY_HIP_PLAN_SCAN_FRAMES:
+        if (check_dims(1, 1, n_frames)) return CANNY_HIP_ERR_INVALID;
+        p = plan_scan_frames(n_frames);
+        break;
+    default: {
+        if (kind < 0 || kind >= CANNY_HIP_PLAN_KINDS || check_dims(height, width, n_frames))
+            return CANNY_HIP_ERR_INVALID;
+        const HystGeom g = make_hyst_geom(height, width, n_frames);
+        switch (kind) {
+        case CANNY_HIP_PLAN_POINTS_ROWS: p = plan_points_rows(g); break;
+        case CANNY_HIP_PLAN_CC_TILES: p = plan_cc_tiles(g); break;
+        case CANNY_HIP_PLAN_CC_ROWS: p = plan_cc_rows(g); break;
+        case CANNY_HIP_PLAN_CT_ROWS: p = plan_ct_rows(g); break;
+        case CANNY_HIP_PLAN_EDT_ROWS: p = plan_edt_rows(g); break;
+        case CANNY_HIP_PLAN_EDT_COLUMNS: p = plan_edt_columns(g); break;
+        case CANNY_HIP_PLAN_HOUGH_VOTE_STRONG: p = plan_hough_vote_global(g, kSrcStrong); break;
+        case CANNY_HIP_PLAN_HOUGH_VOTE_BITS: p = plan_hough_vote_global(g, kSrcBits); break;
+        case CANNY_HIP_PLAN_HOUGH_VOTE_POINTS: // the frame's points are the caller's to say
+            if (extra < 0) return CANNY_HIP_ERR_INVALID;
+            p = plan_hough_vote_global(g, kSrcPoints, (unsigned long long)extra);
+            break;
+        case CANNY_HIP_PLAN_CIRCLES_VOTE_STRONG: p = plan_circles_vote(g, false); break;
+        case CANNY_HIP_PLAN_CIRCLES_VOTE_BITS: p = plan_circles_vote(g, true); break;
+        default: return CANNY_HIP_ERR_INVALID;
+        }
+    }
+    }
+    out[0] = p.units, out[1] = p.per_group, out[2] = p.grid, out[3] = p.trips(), out[4] = (unsigned long long)p.aux;
+    return CANNY_HIP_OK;
+}
+
 // Host-only: the batch pipelines' bit-map expansion (ExpandPool) on a caller-supplied bit map; needs no device.
 int canny_hip_selftest_expand_bits(const unsigned char *bits, int height, int width, int to_u8, void *out, int n_threads)
 {

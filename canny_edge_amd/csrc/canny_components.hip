@@ -417,17 +417,6 @@ __global__ __launch_bounds__(kCcBlock) void cc_write_kernel(const void *__restri
     }
 }
 
-unsigned cc_tile_grid(const HystGeom &g)
-{
-    const size_t per_block = kCcBlock / 64;
-    return (unsigned)std::max<size_t>(1, std::min<size_t>(((size_t)g.tiles() + per_block - 1) / per_block, 1u << 16));
-}
-unsigned cc_row_grid(const HystGeom &g)
-{
-    const size_t n_rows = (size_t)g.n_frames * g.height, per_block = kCcBlock / 64;
-    return (unsigned)std::max<size_t>(1, std::min<size_t>((n_rows + per_block - 1) / per_block, 1u << 16));
-}
-
 #define CC_LAUNCH(kernel, grid, ...)                                                                                    \
     do {                                                                                                                \
         if (bits)                                                                                                       \
@@ -442,25 +431,35 @@ unsigned cc_row_grid(const HystGeom &g)
 
 } // namespace
 
+LaunchPlan plan_cc_tiles(const HystGeom &g)
+{
+    return capped_plan((unsigned long long)g.tiles(), kCcBlock / 64, 1u << 16);
+}
+LaunchPlan plan_cc_rows(const HystGeom &g)
+{
+    return capped_plan((unsigned long long)g.n_frames * g.height, kCcBlock / 64, 1u << 16);
+}
+LaunchPlan plan_cc_fixup(unsigned long long capacity) { return capped_plan(capacity, 256, 4096); }
+
 hipError_t launch_cc_link(const uint64_t *strong, const uint8_t *bits, const HystGeom &g, int *parent, hipStream_t stream)
 {
-    CC_LAUNCH(cc_init_kernel, cc_tile_grid(g), parent);
-    CC_LAUNCH(cc_merge_kernel, cc_tile_grid(g), parent);
+    CC_LAUNCH(cc_init_kernel, plan_cc_tiles(g).grid, parent);
+    CC_LAUNCH(cc_merge_kernel, plan_cc_tiles(g).grid, parent);
     return hipSuccess;
 }
 
 hipError_t launch_cc_resolve(const uint64_t *strong, const uint8_t *bits, const HystGeom &g, int *parent,
                              hipStream_t stream)
 {
-    CC_LAUNCH(cc_flatten_kernel, cc_tile_grid(g), parent);
-    CC_LAUNCH(cc_area_kernel, cc_tile_grid(g), parent);
+    CC_LAUNCH(cc_flatten_kernel, plan_cc_tiles(g).grid, parent);
+    CC_LAUNCH(cc_area_kernel, plan_cc_tiles(g).grid, parent);
     return hipSuccess;
 }
 
 hipError_t launch_cc_count(const uint64_t *strong, const uint8_t *bits, const HystGeom &g, const int *parent, int min_area,
                            uint32_t *row_counts, hipStream_t stream)
 {
-    CC_LAUNCH(cc_count_kernel, cc_row_grid(g), parent, min_area, row_counts);
+    CC_LAUNCH(cc_count_kernel, plan_cc_rows(g).grid, parent, min_area, row_counts);
     return hipSuccess;
 }
 
@@ -469,11 +468,11 @@ hipError_t launch_cc_number(const uint64_t *strong, const uint8_t *bits, const H
                             unsigned long long capacity, hipStream_t stream)
 {
     if (!capacity) stats = nullptr;
-    CC_LAUNCH(cc_number_kernel, cc_row_grid(g), parent, min_area, row_offsets, offsets, stats, capacity);
-    CC_LAUNCH(cc_relabel_kernel, cc_tile_grid(g), parent, offsets, stats, capacity);
+    CC_LAUNCH(cc_number_kernel, plan_cc_rows(g).grid, parent, min_area, row_offsets, offsets, stats, capacity);
+    CC_LAUNCH(cc_relabel_kernel, plan_cc_tiles(g).grid, parent, offsets, stats, capacity);
     if (stats) {
-        const unsigned grid = (unsigned)std::min<unsigned long long>((capacity + 255) / 256, 4096);
-        hipLaunchKernelGGL(cc_fixup_kernel, dim3(grid), dim3(256), 0, stream, stats, offsets, g.n_frames, capacity);
+        hipLaunchKernelGGL(cc_fixup_kernel, dim3(plan_cc_fixup(capacity).grid), dim3(256), 0, stream, stats, offsets,
+                           g.n_frames, capacity);
         return hipGetLastError();
     }
     return hipSuccess;
@@ -482,7 +481,7 @@ hipError_t launch_cc_number(const uint64_t *strong, const uint8_t *bits, const H
 hipError_t launch_cc_write(const uint64_t *strong, const uint8_t *bits, const HystGeom &g, const int *entries, int *labels,
                            uint8_t *kept, hipStream_t stream)
 {
-    CC_LAUNCH(cc_write_kernel, cc_tile_grid(g), entries, labels, kept);
+    CC_LAUNCH(cc_write_kernel, plan_cc_tiles(g).grid, entries, labels, kept);
     return hipSuccess;
 }
 

@@ -246,24 +246,24 @@ __global__ __launch_bounds__(kCtBlock) void ct_place_kernel(HystGeom g, const ui
     }
 }
 
-unsigned ct_row_grid(const HystGeom &g)
-{
-    const size_t n_rows = (size_t)g.n_frames * g.height, per_block = kCtBlock / 64;
-    return (unsigned)std::max<size_t>(1, std::min<size_t>((n_rows + per_block - 1) / per_block, 1u << 16));
-}
-
 #define CT_LAUNCH(WRITE, ...)                                                                                           \
     do {                                                                                                                \
+        const unsigned grid_ = plan_ct_rows(g).grid;                                                                    \
         if (bits)                                                                                                       \
-            hipLaunchKernelGGL((ct_walk_kernel<true, WRITE>), dim3(ct_row_grid(g)), dim3(kCtBlock), 0, stream,         \
+            hipLaunchKernelGGL((ct_walk_kernel<true, WRITE>), dim3(grid_), dim3(kCtBlock), 0, stream,                   \
                                (const void *)bits, g, (g.width + 7) / 8, __VA_ARGS__);                                  \
         else                                                                                                            \
-            hipLaunchKernelGGL((ct_walk_kernel<false, WRITE>), dim3(ct_row_grid(g)), dim3(kCtBlock), 0, stream,        \
+            hipLaunchKernelGGL((ct_walk_kernel<false, WRITE>), dim3(grid_), dim3(kCtBlock), 0, stream,                  \
                                (const void *)strong, g, (g.width + 7) / 8, __VA_ARGS__);                                \
         return hipGetLastError();                                                                                       \
     } while (0)
 
 } // namespace
+
+LaunchPlan plan_ct_rows(const HystGeom &g)
+{
+    return capped_plan((unsigned long long)g.n_frames * g.height, kCtBlock / 64, 1u << 16);
+}
 
 hipError_t launch_ct_count(const uint64_t *strong, const uint8_t *bits, const HystGeom &g, const int *parent, int min_area,
                            const uint32_t *row_offsets, const unsigned long long *offsets,
@@ -278,7 +278,7 @@ hipError_t launch_ct_place(const HystGeom &g, const uint32_t *row_offsets, const
                            const uint32_t *row_point_offsets, const unsigned long long *point_offsets,
                            unsigned long long *chain_offsets, unsigned long long capacity, hipStream_t stream)
 {
-    hipLaunchKernelGGL(ct_place_kernel, dim3(ct_row_grid(g)), dim3(kCtBlock), 0, stream, g, row_offsets, offsets,
+    hipLaunchKernelGGL(ct_place_kernel, dim3(plan_ct_rows(g).grid), dim3(kCtBlock), 0, stream, g, row_offsets, offsets,
                        row_point_offsets, point_offsets, chain_offsets, capacity);
     return hipGetLastError();
 }

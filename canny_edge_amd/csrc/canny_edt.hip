@@ -206,20 +206,25 @@ __global__ __launch_bounds__(kEdtBlock) void edt_columns_kernel(uint16_t *cols, 
     }
 }
 
-unsigned edt_grid(size_t waves)
-{
-    const size_t per_block = kEdtBlock / 64;
-    return (unsigned)std::max<size_t>(1, std::min<size_t>((waves + per_block - 1) / per_block, 1u << 16));
-}
-
 } // namespace
+
+LaunchPlan plan_edt_rows(const HystGeom &g)
+{
+    const unsigned long long n_rows = (unsigned long long)g.n_frames * g.height;
+    const int rows_per_wave = n_rows >= (1u << 16) ? 8 : 1; // enough waves for the chip either way
+    return capped_plan((n_rows + rows_per_wave - 1) / rows_per_wave, kEdtBlock / 64, 1u << 16, rows_per_wave);
+}
+LaunchPlan plan_edt_columns(const HystGeom &g)
+{
+    return capped_plan((unsigned long long)g.n_frames * g.tiles_x, kEdtBlock / 64, 1u << 16);
+}
 
 hipError_t launch_edt_rows(const uint64_t *strong, const uint8_t *bits, const HystGeom &g, uint16_t *cols,
                            hipStream_t stream)
 {
-    const size_t n_rows = (size_t)g.n_frames * g.height;
-    const int rows_per_wave = n_rows >= (1u << 16) ? 8 : 1; // enough waves for the chip either way
-    const unsigned grid = edt_grid((n_rows + rows_per_wave - 1) / rows_per_wave);
+    const LaunchPlan plan = plan_edt_rows(g);
+    const int rows_per_wave = plan.aux;
+    const unsigned grid = plan.grid;
     const size_t lds = (size_t)(kEdtBlock / 64) * g.tiles_x * sizeof(int); // < 12 KiB at the widest row
     const int row_bytes = (g.width + 7) / 8;
     if (bits)
@@ -236,7 +241,7 @@ hipError_t launch_edt_columns(const HystGeom &g, uint16_t *cols, uint32_t *stack
 {
     const size_t stack_pitch = stack ? edt_pitch(g) : (size_t)g.width;
     if (!stack) stack = reinterpret_cast<uint32_t *>(dist2);
-    hipLaunchKernelGGL(edt_columns_kernel, dim3(edt_grid((size_t)g.n_frames * g.tiles_x)), dim3(kEdtBlock), 0, stream,
+    hipLaunchKernelGGL(edt_columns_kernel, dim3(plan_edt_columns(g).grid), dim3(kEdtBlock), 0, stream,
                        cols, g, stack, stack_pitch, dist2, dist, nearest);
     return hipGetLastError();
 }

@@ -32,7 +32,6 @@ constexpr int kCellBlock = 256;   // passes over the accumulator's cells
 constexpr int kSortBlock = 1024;
 constexpr int kSortMax = 4096;    // = CANNY_HIP_HOUGH_MAX_LINES: 32 KB of 64-bit keys
 
-enum { kSrcStrong = 0, kSrcBits = 1, kSrcPoints = 2 };
 enum { kCutK = 0, kCutVote = 1, kCutNeed = 2, kCutBase = 3, kCutTaken = 4, kCutWords = 8 };
 
 struct VoteSrc {
@@ -382,11 +381,7 @@ __global__ __launch_bounds__(kSortBlock) void hough_sort_kernel(const unsigned *
     }
 }
 
-unsigned cell_grid(const HoughGeom &hg)
-{
-    const size_t cells = (size_t)hg.numangle * hg.numrho;
-    return (unsigned)std::max<size_t>(1, std::min<size_t>((cells + kCellBlock * 4 - 1) / (kCellBlock * 4), 4096));
-}
+unsigned cell_grid(const HoughGeom &hg) { return plan_hough_cells((unsigned long long)hg.numangle * hg.numrho).grid; }
 
 template <int SRC>
 hipError_t vote_lds(const VoteSrc &src, const HystGeom &g, const HoughGeom &hg, const float *tab, int *accum, int rows,
@@ -409,15 +404,27 @@ hipError_t vote_global(const VoteSrc &src, const HystGeom &g, const HoughGeom &h
 {
     hipError_t e = hipMemsetAsync(accum, 0, hough_accum_bytes(hg, g.n_frames), stream);
     if (e != hipSuccess) return e;
-    // enough lanes that each takes a few pixels' worth of words; every lane then walks all angles
-    const size_t units = SRC == kSrcPoints ? (size_t)g.height * g.width / 16 : (size_t)g.tiles_y * g.tiles_x * 64;
-    const unsigned blocks = (unsigned)std::max<size_t>(1, std::min<size_t>((units + 255) / 256, 2048));
+    const unsigned blocks = plan_hough_vote_global(g, (VoteSource)SRC).grid;
     hipLaunchKernelGGL(hough_vote_global_kernel<SRC>, dim3(blocks, g.n_frames), dim3(256), 0, stream, src, g,
                        (g.width + 7) / 8, tab, hg.numangle, hg.numrho, accum);
     return hipGetLastError();
 }
 
 } // namespace
+
+// enough lanes that each takes a few pixels' worth of words; every lane then walks all angles.  The grid is sized by the
+// strong plane's words for both plane sources.
+LaunchPlan plan_hough_vote_global(const HystGeom &g, VoteSource src, unsigned long long n_points)
+{
+    const unsigned long long words = (unsigned long long)g.tiles_y * g.tiles_x * 64;
+    if (src == kSrcPoints) return sized_plan(n_points, 256, (unsigned long long)g.height * g.width / 16, 256, 2048);
+    return sized_plan(src == kSrcBits ? (unsigned long long)g.height * g.tiles_x : words, 256, words, 256, 2048);
+}
+// a workgroup takes kCellBlock cells per trip; uncapped, the grid is sized for four trips
+LaunchPlan plan_hough_cells(unsigned long long cells)
+{
+    return sized_plan(cells, kCellBlock, cells, kCellBlock * 4, 4096);
+}
 
 int hough_lds_rows(const HoughGeom &hg, int budget_bytes)
 {

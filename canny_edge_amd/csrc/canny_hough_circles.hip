@@ -332,14 +332,21 @@ __global__ __launch_bounds__(kAcceptBlock) void circles_accept_kernel(const unsi
 template <bool BITS, int GRAD>
 hipError_t vote(const void *src, const HystGeom &g, const GradSrc &grad, const VoteArgs &a, int *accum, hipStream_t stream)
 {
-    const size_t units = BITS ? (size_t)g.height * g.tiles_x : (size_t)g.tiles_y * g.tiles_x * 64;
-    const unsigned chunks = (unsigned)((units + kVoteWords - 1) / kVoteWords);
-    hipLaunchKernelGGL((circles_vote_kernel<BITS, GRAD>), dim3(std::min(chunks, 2048u), g.n_frames), dim3(kVoteBlock), 0,
-                       stream, src, g, (g.width + 7) / 8, grad, a, accum);
+    const dim3 grid(plan_circles_vote(g, BITS).grid, g.n_frames);
+    hipLaunchKernelGGL((circles_vote_kernel<BITS, GRAD>), grid, dim3(kVoteBlock), 0, stream, src, g, (g.width + 7) / 8,
+                       grad, a, accum);
     return hipGetLastError();
 }
 
 } // namespace
+
+LaunchPlan plan_circles_vote(const HystGeom &g, bool from_bits)
+{
+    const unsigned long long words =
+        from_bits ? (unsigned long long)g.height * g.tiles_x : (unsigned long long)g.tiles_y * g.tiles_x * 64;
+    return capped_plan((words + kVoteWords - 1) / kVoteWords, 1, 2048);
+}
+LaunchPlan plan_circles_steps(size_t n) { return capped_plan(n, 256, 8192); }
 
 hipError_t launch_circles_vote(const uint64_t *strong, const uint8_t *bits, const HystGeom &g, const void *smoothed,
                                bool smoothed_u8, const int16_t *gx, const int16_t *gy, const CircleGeom &cg, int *accum,
@@ -360,8 +367,7 @@ hipError_t launch_circles_vote(const uint64_t *strong, const uint8_t *bits, cons
 
 hipError_t launch_circles_steps(const int16_t *gx, const int16_t *gy, size_t n, int *sx, int *sy, hipStream_t stream)
 {
-    const unsigned blocks = (unsigned)std::max<size_t>(1, std::min<size_t>((n + 255) / 256, 8192));
-    hipLaunchKernelGGL(circles_steps_kernel, dim3(blocks), dim3(256), 0, stream, gx, gy, n, sx, sy);
+    hipLaunchKernelGGL(circles_steps_kernel, dim3(plan_circles_steps(n).grid), dim3(256), 0, stream, gx, gy, n, sx, sy);
     return hipGetLastError();
 }
 

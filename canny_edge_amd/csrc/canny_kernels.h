@@ -539,6 +539,55 @@ hipError_t launch_edt_rows(const uint64_t *strong, const uint8_t *bits, const Hy
 hipError_t launch_edt_columns(const HystGeom &g, uint16_t *cols, uint32_t *stack, int *dist2, float *dist, int *nearest,
                               hipStream_t stream);
 
+// ---- launch plans of the capped grids ---------------------------------
+// A launcher whose grid is capped hands its kernel `units` work items and `grid` workgroups that take `per_group` items
+// per trip of their grid-stride loop.  Each plan_* below is computed from sizes alone, is THE grid computation of the
+// launchers named beside it (they launch plan.grid workgroups), and is what canny_hip_selftest_launch_plan reports: a
+// test asks it whether a call sends some wave into a second trip.
+struct LaunchPlan {
+    unsigned long long units; // work items of the launch (of one frame where the grid's y is the frame)
+    unsigned per_group;       // items one workgroup takes per trip
+    unsigned grid;            // workgroups (x)
+    int aux;                  // plan_edt_rows: rows per wave; otherwise 0
+    unsigned long long trips() const
+    {
+        const unsigned long long per_trip = (unsigned long long)grid * per_group;
+        return (units + per_trip - 1) / per_trip;
+    }
+};
+// The kernel walks `units` items, per_group a workgroup and trip; grid = ceil(sizing / per_sizing), at least 1 and at most
+// cap -- for the launches whose grid is sized by another figure than what their loop walks.
+inline LaunchPlan sized_plan(unsigned long long units, unsigned per_group, unsigned long long sizing, unsigned per_sizing,
+                             unsigned cap, int aux = 0)
+{
+    const unsigned long long want = (sizing + per_sizing - 1) / per_sizing;
+    return LaunchPlan{units, per_group, (unsigned)(want < 1 ? 1 : (want > cap ? cap : want)), aux};
+}
+// grid = ceil(units / per_group), at least 1 and at most cap
+inline LaunchPlan capped_plan(unsigned long long units, unsigned per_group, unsigned cap, int aux = 0)
+{
+    return sized_plan(units, per_group, units, per_group, cap, aux);
+}
+LaunchPlan plan_points_rows(const HystGeom &g);    // points count, scatter: image rows of the batch
+LaunchPlan plan_scan_frames(int n_frames);         // points_scan_frames_kernel: frames, one workgroup
+LaunchPlan plan_cc_tiles(const HystGeom &g);       // cc init, merge, flatten, area, relabel, write: tiles of the batch
+LaunchPlan plan_cc_rows(const HystGeom &g);        // cc count, number: image rows of the batch
+LaunchPlan plan_cc_fixup(unsigned long long capacity); // cc_fixup_kernel: record slots
+LaunchPlan plan_ct_rows(const HystGeom &g);        // contour walk (count, write), place: image rows of the batch
+LaunchPlan plan_edt_rows(const HystGeom &g);       // edt rows: groups of aux consecutive rows
+LaunchPlan plan_edt_columns(const HystGeom &g);    // edt columns: 64-column strips of the batch
+LaunchPlan plan_pg_records(unsigned long long capacity);   // polygon simplify, emit: record slots
+LaunchPlan plan_pg_scan_sums(unsigned long long capacity); // pg_scan_sums_kernel: chunk sums, one workgroup
+// global vote: the items of a frame as the kernel walks them -- the plane's words (tile padding included for the strong
+// plane; a trip is one word per lane, and a lane keeps four in flight) or the n_points points of the frame's list (only
+// the query knows them: the grid is sized by pixels / 16, and by the strong plane's words for both plane sources)
+enum VoteSource { kSrcStrong = 0, kSrcBits = 1, kSrcPoints = 2 };
+LaunchPlan plan_hough_vote_global(const HystGeom &g, VoteSource src, unsigned long long n_points = 0);
+LaunchPlan plan_hough_cells(unsigned long long cells);    // peaks, ties, collect: the numangle * numrho cells of a frame
+LaunchPlan plan_circles_vote(const HystGeom &g, bool from_bits); // circle vote: 64-word chunks of a frame
+LaunchPlan plan_circles_steps(size_t n);           // circles_steps_kernel: gradient pairs
+LaunchPlan plan_to_gray(size_t n_px);              // to_gray_kernel: 16-pixel groups
+
 // ---- measurement aid ------------------------------------------------------------------------
 // Plain device copy of nbytes (multiple of 16; both pointers 16-byte aligned): what a 1:1 read/write stream reaches.
 hipError_t launch_probe_copy(const void *src, void *dst, size_t nbytes, hipStream_t stream, const LaunchEvents &ev = {});

@@ -140,24 +140,25 @@ __global__ __launch_bounds__(kPtsBlock) void points_scatter_kernel(const void *_
     }
 }
 
-unsigned row_grid(const HystGeom &g)
-{
-    const size_t n_rows = (size_t)g.n_frames * g.height, per_block = kPtsBlock / 64;
-    return (unsigned)std::max<size_t>(1, std::min<size_t>((n_rows + per_block - 1) / per_block, 1u << 16));
-}
-
 } // namespace
+
+LaunchPlan plan_points_rows(const HystGeom &g)
+{
+    return capped_plan((unsigned long long)g.n_frames * g.height, kPtsBlock / 64, 1u << 16);
+}
+LaunchPlan plan_scan_frames(int n_frames) { return capped_plan((unsigned long long)n_frames, 256, 1); }
 
 hipError_t launch_points_count(const uint64_t *strong, const uint8_t *bits, const HystGeom &g, uint32_t *row_counts,
                                hipStream_t stream)
 {
     const int row_bytes = (g.width + 7) / 8;
+    const unsigned grid = plan_points_rows(g).grid;
     if (bits)
-        hipLaunchKernelGGL(points_count_kernel<true>, dim3(row_grid(g)), dim3(kPtsBlock), 0, stream, (const void *)bits, g,
+        hipLaunchKernelGGL(points_count_kernel<true>, dim3(grid), dim3(kPtsBlock), 0, stream, (const void *)bits, g,
                            row_bytes, row_counts);
     else
-        hipLaunchKernelGGL(points_count_kernel<false>, dim3(row_grid(g)), dim3(kPtsBlock), 0, stream,
-                           (const void *)strong, g, row_bytes, row_counts);
+        hipLaunchKernelGGL(points_count_kernel<false>, dim3(grid), dim3(kPtsBlock), 0, stream, (const void *)strong, g,
+                           row_bytes, row_counts);
     return hipGetLastError();
 }
 
@@ -167,7 +168,8 @@ hipError_t launch_points_scan(uint32_t *rows, unsigned long long *frame_totals, 
     hipLaunchKernelGGL(points_scan_rows_kernel, dim3(n_frames), dim3(256), 0, stream, rows, frame_totals, height);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(points_scan_frames_kernel, dim3(1), dim3(256), 0, stream, frame_totals, offsets, n_frames);
+    hipLaunchKernelGGL(points_scan_frames_kernel, dim3(plan_scan_frames(n_frames).grid), dim3(256), 0, stream,
+                       frame_totals, offsets, n_frames);
     return hipGetLastError();
 }
 
@@ -177,12 +179,13 @@ hipError_t launch_points_scatter(const uint64_t *strong, const uint8_t *bits, co
 {
     if (capacity == 0) return hipSuccess;
     const int row_bytes = (g.width + 7) / 8;
+    const unsigned grid = plan_points_rows(g).grid;
     if (bits)
-        hipLaunchKernelGGL(points_scatter_kernel<true>, dim3(row_grid(g)), dim3(kPtsBlock), 0, stream, (const void *)bits,
-                           g, row_bytes, row_offsets, offsets, points, capacity);
+        hipLaunchKernelGGL(points_scatter_kernel<true>, dim3(grid), dim3(kPtsBlock), 0, stream, (const void *)bits, g,
+                           row_bytes, row_offsets, offsets, points, capacity);
     else
-        hipLaunchKernelGGL(points_scatter_kernel<false>, dim3(row_grid(g)), dim3(kPtsBlock), 0, stream,
-                           (const void *)strong, g, row_bytes, row_offsets, offsets, points, capacity);
+        hipLaunchKernelGGL(points_scatter_kernel<false>, dim3(grid), dim3(kPtsBlock), 0, stream, (const void *)strong, g,
+                           row_bytes, row_offsets, offsets, points, capacity);
     return hipGetLastError();
 }
 

@@ -425,13 +425,13 @@ __global__ __launch_bounds__(kPgBlock) void pg_emit_kernel(const unsigned long l
     }
 }
 
-unsigned pg_record_grid(unsigned long long capacity)
-{
-    const unsigned long long per_block = kPgBlock / 64;
-    return (unsigned)std::max<unsigned long long>(1, std::min<unsigned long long>((capacity + per_block - 1) / per_block, 1u << 16));
-}
-
 } // namespace
+
+LaunchPlan plan_pg_records(unsigned long long capacity) { return capped_plan(capacity, kPgBlock / 64, 1u << 16); }
+LaunchPlan plan_pg_scan_sums(unsigned long long capacity)
+{
+    return capped_plan(polygons_scan_blocks(capacity), 256, 1);
+}
 
 unsigned long long polygons_scan_blocks(unsigned long long capacity)
 {
@@ -443,9 +443,9 @@ hipError_t launch_pg_simplify(const unsigned long long *offsets, int n_frames, u
                               int width, unsigned epsilon_q8, unsigned ratio_q16, unsigned long long *vertex_offsets,
                               unsigned long long *masks, uint8_t *flags, long long *measures, hipStream_t stream)
 {
-    hipLaunchKernelGGL(pg_simplify_kernel, dim3(pg_record_grid(capacity)), dim3(kPgBlock), 0, stream, offsets, n_frames,
-                       capacity, chain_offsets, points, point_capacity, width, epsilon_q8, ratio_q16, vertex_offsets, masks,
-                       flags, measures);
+    hipLaunchKernelGGL(pg_simplify_kernel, dim3(plan_pg_records(capacity).grid), dim3(kPgBlock), 0, stream, offsets,
+                       n_frames, capacity, chain_offsets, points, point_capacity, width, epsilon_q8, ratio_q16,
+                       vertex_offsets, masks, flags, measures);
     return hipGetLastError();
 }
 
@@ -457,7 +457,8 @@ hipError_t launch_pg_scan(const unsigned long long *offsets, int n_frames, unsig
                        vertex_offsets, block_sums);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || n_blocks == 1) return e;
-    hipLaunchKernelGGL(pg_scan_sums_kernel, dim3(1), dim3(256), 0, stream, block_sums, n_blocks);
+    hipLaunchKernelGGL(pg_scan_sums_kernel, dim3(plan_pg_scan_sums(capacity).grid), dim3(256), 0, stream, block_sums,
+                       n_blocks);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     hipLaunchKernelGGL(pg_scan_add_kernel, dim3(n_blocks), dim3(256), 0, stream, offsets, n_frames, capacity, vertex_offsets,
                        (const unsigned long long *)block_sums);
@@ -470,9 +471,9 @@ hipError_t launch_pg_emit(const unsigned long long *offsets, int n_frames, unsig
                           const uint8_t *flags, int *vertices, unsigned long long vertex_capacity, long long *measures,
                           hipStream_t stream)
 {
-    hipLaunchKernelGGL(pg_emit_kernel, dim3(pg_record_grid(capacity)), dim3(kPgBlock), 0, stream, offsets, n_frames,
-                       capacity, chain_offsets, points, point_capacity, width, vertex_offsets, masks, flags, vertices,
-                       vertex_capacity, measures);
+    hipLaunchKernelGGL(pg_emit_kernel, dim3(plan_pg_records(capacity).grid), dim3(kPgBlock), 0, stream, offsets,
+                       n_frames, capacity, chain_offsets, points, point_capacity, width, vertex_offsets, masks, flags,
+                       vertices, vertex_capacity, measures);
     return hipGetLastError();
 }
 

@@ -41,13 +41,14 @@ __global__ __launch_bounds__(256) void to_gray_kernel(const uint8_t *__restrict_
 
 } // namespace
 
+// enough waves to fill the chip several times over; the grid-stride loop takes the rest
+LaunchPlan plan_to_gray(size_t n_px) { return capped_plan(n_px / 16, 256, 8192); }
+
 hipError_t launch_to_gray(const uint8_t *src, int ch, const GrayRule &rule, uint8_t *gray, size_t n_px,
                           hipStream_t stream)
 {
     if (n_px == 0) return hipSuccess;
-    // enough waves to fill the chip several times over; the grid-stride loop takes the rest
-    const size_t groups = n_px / 16;
-    const unsigned blocks = (unsigned)std::max<size_t>(1, std::min<size_t>((groups + 255) / 256, 8192));
+    const unsigned blocks = plan_to_gray(n_px).grid;
     if (ch == 3)
         hipLaunchKernelGGL(to_gray_kernel<3>, dim3(blocks), dim3(256), 0, stream, src, gray, n_px, rule);
     else if (ch == 4)

@@ -52,7 +52,8 @@
 extern "C" {
 #endif
 
-#define CANNY_HIP_VERSION 1201       /* 0.12.1: + canny_hip_selftest_workspace */
+#define CANNY_HIP_VERSION 1202       /* 0.12.2: + canny_hip_selftest_launch_plan */
+/* 0.12.1: + canny_hip_selftest_workspace */
 /* 0.12.0: + polygon approximation of the contour chains, on the GPU */
 /* 0.10.0: + outer contour chains of the finished map, traced on the GPU */
 /* 0.11.0: + Hough circles: gradient rays, centre peaks, radius by support */
@@ -1111,6 +1112,46 @@ int canny_hip_selftest_select(canny_hip_ctx *ctx, const unsigned int *d_hist, in
  * nothing and changes nothing. */
 enum canny_hip_workspace_kind { CANNY_HIP_WS_DATA = 0, CANNY_HIP_WS_INDEX = 1, CANNY_HIP_WS_CACHE = 2 };
 int canny_hip_selftest_workspace(canny_hip_ctx *ctx, int index, const char **name, void **d_ptr, size_t *bytes, int *kind);
+/* Host-only (needs no device, launches nothing, touches no context): how a launch whose grid is capped divides its work
+ * (DESIGN.md section 21 has a row for each kind).  Such a kernel walks its work items in a grid-stride loop; the grid is
+ * computed by a helper that takes sizes only, the launchers call that helper, and so does this entry.  out[0 .. 4] =
+ * the work items of the launch (of ONE frame for the kinds whose grid has the frame as its second dimension), the items
+ * a workgroup takes per trip of its loop, the workgroups, the trips = ceil(items / (workgroups * items per trip)), and
+ * for CANNY_HIP_PLAN_EDT_ROWS the image rows a wave takes per item (1 or 8), 0 otherwise.
+ *   sized by n_frames, height, width (valid as for every batch call; extra ignored except for HOUGH_VOTE_POINTS):
+ *     POINTS_ROWS, CC_ROWS, CT_ROWS: image rows of the batch; CC_TILES: 64 x 64 tiles of the batch;
+ *     EDT_ROWS: groups of out[4] rows; EDT_COLUMNS: 64-column strips of the batch;
+ *     HOUGH_VOTE_STRONG / _BITS: 64-pixel words of a frame, one per lane and trip (the strong plane's count includes the
+ *     rows that pad the last tile); HOUGH_VOTE_POINTS: the points of a frame's list, given in extra >= 0 (the grid is
+ *     sized by pixels / 16, whatever the list holds); CIRCLES_VOTE_STRONG / _BITS: chunks of 64 words of a frame
+ *   SCAN_FRAMES: n_frames alone (one workgroup, 256 frames per trip)
+ *   sized by extra >= 1 alone: CC_FIXUP, PG_RECORDS: the record capacity; PG_SCAN_SUMS: the record capacity (items: its
+ *     chunks of 2048 records); HOUGH_CELLS: numangle * numrho; CIRCLES_STEPS: gradient pairs; TO_GRAY: pixels (items:
+ *     groups of 16)
+ * CANNY_HIP_ERR_INVALID for an unknown kind, sizes a batch call would refuse, or extra < 1 where it counts. */
+enum canny_hip_launch_plan_kind {
+    CANNY_HIP_PLAN_POINTS_ROWS = 0,
+    CANNY_HIP_PLAN_SCAN_FRAMES = 1,
+    CANNY_HIP_PLAN_CC_TILES = 2,
+    CANNY_HIP_PLAN_CC_ROWS = 3,
+    CANNY_HIP_PLAN_CC_FIXUP = 4,
+    CANNY_HIP_PLAN_CT_ROWS = 5,
+    CANNY_HIP_PLAN_EDT_ROWS = 6,
+    CANNY_HIP_PLAN_EDT_COLUMNS = 7,
+    CANNY_HIP_PLAN_PG_RECORDS = 8,
+    CANNY_HIP_PLAN_PG_SCAN_SUMS = 9,
+    CANNY_HIP_PLAN_HOUGH_VOTE_STRONG = 10,
+    CANNY_HIP_PLAN_HOUGH_VOTE_BITS = 11,
+    CANNY_HIP_PLAN_HOUGH_VOTE_POINTS = 12,
+    CANNY_HIP_PLAN_HOUGH_CELLS = 13,
+    CANNY_HIP_PLAN_CIRCLES_VOTE_STRONG = 14,
+    CANNY_HIP_PLAN_CIRCLES_VOTE_BITS = 15,
+    CANNY_HIP_PLAN_CIRCLES_STEPS = 16,
+    CANNY_HIP_PLAN_TO_GRAY = 17,
+    CANNY_HIP_PLAN_KINDS = 18
+};
+int canny_hip_selftest_launch_plan(int kind, int n_frames, int height, int width, long long extra,
+                                   unsigned long long *out);
 
 #ifdef __cplusplus
 }
