@@ -9,9 +9,9 @@ part) below row 70, and row 70 itself at 60 + lev // 3 -- a symmetric step is su
 the intermediate row is what leaves a line.  strong_cols = 0 gives a frame full of weak pixels and no edge at all: whatever a
 neighbour's queue leaks into that frame shows.
 
-How many sweeps a frame needs is computed here, from the oracle's NMS plane, by a synchronous model of the tile sweeps (every
-tile of a sweep sees the planes as the previous sweep left them, floods to convergence and schedules the neighbours its
-changed border faces).  The device may be quicker -- a tile can see what a neighbour stored in the same sweep -- but not
+How many sweeps a frame needs is computed from the oracle's NMS plane by the synchronous model of the tile sweeps in
+tests/hyst_maps.py (every tile of a sweep sees the planes as the previous sweep left them, floods to convergence and
+schedules the neighbours its changed border faces).  The device may be quicker -- a tile can see what a neighbour stored in the same sweep -- but not
 slower: by induction over the sweeps its planes hold at least the model's, so a border pixel is gained, and its neighbour
 scheduled, no later than in the model.  Hence the bounds on last_hysteresis_iterations (the last sweep that scheduled a tile,
 plus two): at least 2 when any frame of the batch pushes in sweep 0, at most the model's sweep count plus one."""
@@ -20,6 +20,7 @@ import pytest
 
 import oracle
 from canny_edge_amd.synth import synth_frame
+from hyst_maps import model_sweeps
 
 pytestmark = pytest.mark.gpu
 
@@ -50,47 +51,6 @@ def designed_frame(strong_cols):
     return img.astype(np.uint8)
 
 
-def model_sweeps(nms):
-    """Sweeps of the synchronous tile model, the last one (which schedules nothing) included."""
-    h, w = nms.shape
-    ty_n, tx_n = (h + T - 1) // T, (w + T - 1) // T
-    conn = np.zeros((ty_n * T + 2, tx_n * T + 2), bool)
-    strong = np.zeros_like(conn)
-    conn[1:h + 1, 1:w + 1] = nms >= LO
-    strong[1:h + 1, 1:w + 1] = nms >= HI
-    todo = [(ty, tx) for ty in range(ty_n) for tx in range(tx_n)]
-    sweeps = 0
-    while todo:
-        before, nxt = strong.copy(), set()
-        for ty, tx in todo:
-            y0, x0 = 1 + ty * T, 1 + tx * T
-            c = conn[y0:y0 + T, x0:x0 + T]
-            win = before[y0 - 1:y0 + T + 1, x0 - 1:x0 + T + 1].copy()
-            own = win[1:-1, 1:-1]
-            start = own.copy()
-            while True:
-                near = np.zeros((T, T), bool)
-                for dy in range(3):
-                    for dx in range(3):
-                        near |= win[dy:dy + T, dx:dx + T]
-                grown = own | (c & near)
-                if (grown == own).all():
-                    break
-                own[:] = grown
-            chg = own & ~start
-            if not chg.any():
-                continue
-            strong[y0:y0 + T, x0:x0 + T] = own
-            for dy, dx, hit in ((-1, 0, chg[0].any()), (1, 0, chg[-1].any()), (0, -1, chg[:, 0].any()),
-                                (0, 1, chg[:, -1].any()), (-1, -1, chg[0, 0]), (-1, 1, chg[0, -1]),
-                                (1, -1, chg[-1, 0]), (1, 1, chg[-1, -1])):
-                if hit and 0 <= ty + dy < ty_n and 0 <= tx + dx < tx_n:
-                    nxt.add((ty + dy, tx + dx))
-        todo = sorted(nxt)
-        sweeps += 1
-    return sweeps
-
-
 def _mix(transposed):
     """The four distinct frames of one shape with their oracle maps and model sweep counts (computed once)."""
     def make():
@@ -103,7 +63,7 @@ def _mix(transposed):
         for f, s in zip(frames, stages):
             assert np.array_equal(s["edges"], oracle.canny(f, SIGMA, LO, HI))
         return {"frames": np.stack(frames), "want": np.stack([s["edges"] for s in stages]),
-                "sweeps": [model_sweeps(s["nms"]) for s in stages]}
+                "sweeps": [model_sweeps(s["nms"], LO, HI)[1] for s in stages]}
     key = ("mix", transposed)
     if key not in _cache:
         _cache[key] = make()
