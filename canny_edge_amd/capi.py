@@ -116,6 +116,8 @@ EXPORTS = (
     "canny_hip_hough_circles_profile_get",
     "canny_hip_dev_polygons_chains", "canny_hip_dev_canny_polygons", "canny_hip_dev_polygons_bits",
     "canny_hip_canny_polygons", "canny_hip_polygons_from_chains", "canny_hip_polygons_profile_get",
+    "canny_hip_dev_canny_edgels", "canny_hip_dev_edgels_at", "canny_hip_canny_edgels", "canny_hip_edgels_from_plane",
+    "canny_hip_dev_edgels_arith", "canny_hip_edgels_profile_get", "canny_hip_selftest_edgels_plan",
 )
 
 _lib: Optional[C.CDLL] = None
@@ -275,6 +277,13 @@ def load() -> C.CDLL:
                                       p], i),
         "canny_hip_polygons_from_chains": ([p, p, ull, ull, i, i, C.c_uint, C.c_uint, p, p, ull, p], i),
         "canny_hip_polygons_profile_get": ([p, i, C.POINTER(C.c_double), C.POINTER(C.c_long)], i),
+        "canny_hip_dev_canny_edgels": ([p, p, f, i, i, i, i, i, p, p, ull, p, p], i),
+        "canny_hip_dev_edgels_at": ([p, p, i, i, i, i, p, p, p, ull], i),
+        "canny_hip_canny_edgels": ([p, p, i, f, i, i, i, i, p, ull, p, p], i),
+        "canny_hip_edgels_from_plane": ([p, i, i, i, p, ull, p], i),
+        "canny_hip_dev_edgels_arith": ([p, p, p, sz, p, p, p, sz, p, p], i),
+        "canny_hip_edgels_profile_get": ([p, i, C.POINTER(C.c_double), C.POINTER(C.c_long)], i),
+        "canny_hip_selftest_edgels_plan": ([i, i, i, ull, p], i),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -575,6 +584,61 @@ def hough_circles_from_bits(bits, gx, gy, height: int, width: int, min_radius: i
         raise CannyHipError(st, "hough_circles_from_bits")
     rec = buf[:n.value * CIRCLE_INTS].reshape(n.value, CIRCLE_INTS)
     return (rec, peaks.value, acc) if want_accum else (rec, peaks.value)
+
+
+# sub-pixel edgel records (include/canny_hip.h): (n, EDGEL_INTS) int32
+EDGEL_INTS = 4
+EDGEL_MAG_MASK, EDGEL_DIR_SHIFT, EDGEL_REFINED, EDGEL_INVALID = 0x00FFFFFF, 24, 0x10000000, 0x80000000
+EDGEL_PART_LAYOUT, EDGEL_PART_REFINE = 0, 1
+
+
+def edgels_from_plane(plane, points) -> np.ndarray:
+    """Host-only: the edgel rule on one host plane (uint8 or int16, [H, W], H and W >= 2) at the pixel indices r * W + c of
+    `points` (any unsigned 32-bit values; those >= H * W give invalid records) -> (n, 4) int32 records."""
+    a = np.ascontiguousarray(plane)
+    if a.ndim != 2 or a.dtype not in (np.uint8, np.int16):
+        raise ValueError("expected a 2-D uint8 or int16 plane")
+    pts = np.ascontiguousarray(points, dtype=np.uint32).reshape(-1)
+    rec = np.empty((pts.size, EDGEL_INTS), np.int32)
+    st = load().canny_hip_edgels_from_plane(_hp(a), int(a.dtype == np.uint8), a.shape[0], a.shape[1],
+                                            _hp(pts) if pts.size else None, pts.size, _hp(rec) if pts.size else None)
+    if st:
+        raise CannyHipError(st, "edgels_from_plane")
+    return rec
+
+
+def edgels_xy(rec) -> Tuple[np.ndarray, np.ndarray]:
+    """Sub-pixel (x, y) of edgel records, float64 pixels (x = column, y = row)."""
+    r = np.asarray(rec, np.int32).reshape(-1, EDGEL_INTS)
+    return r[:, 0] / 256.0, r[:, 1] / 256.0
+
+
+def edgels_gradient(rec) -> Tuple[np.ndarray, np.ndarray]:
+    """(gx, gy) of edgel records, int16."""
+    w = np.ascontiguousarray(np.asarray(rec, np.int32).reshape(-1, EDGEL_INTS)[:, 2]).view(np.uint32)
+    return (w & 0xFFFF).astype(np.uint16).view(np.int16), (w >> 16).astype(np.uint16).view(np.int16)
+
+
+def edgels_magnitude(rec) -> np.ndarray:
+    """Gradient magnitude of edgel records in grey levels, float64 (the record holds 1/16 levels)."""
+    w = np.ascontiguousarray(np.asarray(rec, np.int32).reshape(-1, EDGEL_INTS)[:, 3]).view(np.uint32)
+    return (w & EDGEL_MAG_MASK) / 16.0
+
+
+def edgels_flags(rec) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """(dir 0..3 -- step (1,0), (1,1), (0,1), (1,-1) --, refined, invalid) of edgel records."""
+    w = np.ascontiguousarray(np.asarray(rec, np.int32).reshape(-1, EDGEL_INTS)[:, 3]).view(np.uint32)
+    return ((w >> EDGEL_DIR_SHIFT) & 3).astype(np.int32), (w & EDGEL_REFINED) != 0, (w & EDGEL_INVALID) != 0
+
+
+def edgels_plan(n_frames: int, height: int, width: int, n_points: int) -> "LaunchPlan":
+    """Host-only: the launch plan of the index-driven edgel kernel (Context.dev_edgels_at) for a frame's list of n_points
+    entries; fields as launch_plan."""
+    out = np.zeros(5, np.uint64)
+    st = load().canny_hip_selftest_edgels_plan(int(n_frames), int(height), int(width), int(n_points), _hp(out))
+    if st:
+        raise CannyHipError(st, "selftest_edgels_plan")
+    return LaunchPlan(*(int(v) for v in out))
 
 
 def points_to_rc(points, width: int) -> Tuple[np.ndarray, np.ndarray]:
@@ -924,6 +988,66 @@ class Context:
         self._check(self._L.canny_hip_dev_points_from_bits(self._h, C.c_void_p(d_bits), h, w, n,
                                                            C.c_void_p(d_points or None), capacity,
                                                            C.c_void_p(d_offsets)), "dev_points_from_bits")
+
+    # ---- sub-pixel edgels (one 16-byte record per edge pixel) -----------------------------
+    def canny_edgels(self, imgs, sigma: float, min_val: int, max_val: int, capacity: Optional[int] = None,
+                     want_points: bool = False):
+        """canny() returning one edgel record per edge pixel: imgs (H, W) or (N, H, W) uint8 -> (edgels int32 [total, 4],
+        offsets uint64 [N + 1]) and, with want_points, the pixel indices as canny_points returns them.  Records are in
+        canny_points' order; unpack them with edgels_xy / edgels_gradient / edgels_magnitude / edgels_flags.  capacity as
+        in canny_points."""
+        a = np.ascontiguousarray(imgs, dtype=np.uint8)
+        if a.ndim == 2:
+            a = a[None]
+        if a.ndim != 3:
+            raise ValueError("expected uint8 [H, W] or [n_frames, H, W]")
+        n, h, w = a.shape
+        offsets = np.zeros(n + 1, np.uint64)
+        cap = max(1024, a.size // 8) if capacity is None else int(capacity)
+        while True:
+            rec = np.empty((cap, EDGEL_INTS), np.int32)
+            pts = np.empty(cap, np.uint32) if want_points else None
+            self._check(self._L.canny_hip_canny_edgels(self._h, _hp(a), n, sigma, min_val, max_val, h, w,
+                                                       _hp(rec) if cap else None, cap, _hp(offsets),
+                                                       _hp(pts) if want_points and cap else None), "canny_edgels")
+            total = int(offsets[-1])
+            if capacity is not None or total <= cap:
+                fit = min(total, cap)
+                return (rec[:fit], offsets, pts[:fit]) if want_points else (rec[:fit], offsets)
+            cap = total
+
+    def dev_canny_edgels(self, d_img: int, sigma: float, min_val: int, max_val: int, h: int, w: int, n: int,
+                         d_edgels: int, capacity: int, d_offsets: int, d_edges: int = 0, d_points: int = 0):
+        """dev_canny, then one record per edge pixel on the same stream: d_edgels (capacity records of 4 int32, device,
+        16-byte aligned; 0 with capacity 0 for counts only), d_offsets (N + 1 uint64, device), d_edges (the s16 map) or 0,
+        d_points (capacity uint32: the indices dev_canny_points would write) or 0."""
+        v = C.c_void_p
+        self._check(self._L.canny_hip_dev_canny_edgels(self._h, v(d_img), sigma, min_val, max_val, h, w, n,
+                                                       v(d_edges or None), v(d_edgels or None), capacity, v(d_offsets),
+                                                       v(d_points or None)), "dev_canny_edgels")
+
+    def dev_edgels_at(self, d_plane: int, plane_is_u8: bool, h: int, w: int, n: int, d_points: int, d_point_offsets: int,
+                      d_edgels: int, capacity: int):
+        """The edgel rule at listed pixels: record q describes index d_points[q] (uint32 / int32, device) of the frame whose
+        range in d_point_offsets (N + 1 uint64, device) holds q.  d_plane: N planes of h x w bytes (plane_is_u8) or shorts,
+        or 0 for the smoothed plane the last dev_canny-family call on this context left (same n, h, w only)."""
+        v = C.c_void_p
+        self._check(self._L.canny_hip_dev_edgels_at(self._h, v(d_plane or None), int(plane_is_u8), h, w, n,
+                                                    v(d_points or None), v(d_point_offsets or None), v(d_edgels or None),
+                                                    capacity), "dev_edgels_at")
+
+    def dev_edgels_arith(self, d_gx: int, d_gy: int, n_pairs: int, d_mag: int, d_dir: int, d_abc: int = 0,
+                         n_triples: int = 0, d_t: int = 0, d_refined: int = 0):
+        """Test hook: the kernels' device arithmetic on arrays (pairs -> mag_q4, dir; (a, b, c) triples -> t_q8, refined)."""
+        v = C.c_void_p
+        self._check(self._L.canny_hip_dev_edgels_arith(self._h, v(d_gx or None), v(d_gy or None), n_pairs,
+                                                       v(d_mag or None), v(d_dir or None), v(d_abc or None), n_triples,
+                                                       v(d_t or None), v(d_refined or None)), "dev_edgels_arith")
+
+    def edgels_profile_get(self, part: int) -> Tuple[float, int]:
+        ms, n = C.c_double(0), C.c_long(0)
+        self._check(self._L.canny_hip_edgels_profile_get(self._h, part, C.byref(ms), C.byref(n)), "edgels_profile_get")
+        return ms.value, n.value
 
     # ---- connected components of the finished map (DESIGN.md section 14) ----------------------------------------
     def canny_components(self, imgs, sigma: float, min_val: int, max_val: int, min_area: int = 1,

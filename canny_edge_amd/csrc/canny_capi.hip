@@ -339,6 +339,9 @@ struct canny_hip_ctx {
     // [0,255], src/utils.cpp:62): 0 = s16 plane, 1 = u8 plane
     int smoothed_u8 = 1; // canny(): the plane between the Gaussian and the fused Sobel+NMS as bytes (round 3 default)
     int last_canny_u8 = 0; // whether the last canny call really used it (window, taps and shape permitting)
+    // (n_frames, height, width) of the batch whose smoothed plane that call left in `smoothed` (0: no call yet):
+    // canny_hip_dev_edgels_at with d_plane == NULL reads it
+    int last_canny_n = 0, last_canny_h = 0, last_canny_w = 0;
     // colour input (canny_hip_*_color): the conversion rule (0 OpenCV, 1 PIL), whether the Gaussian may convert as it
     // loads (1) or a standalone pass always converts first (0), and whether the last colour canny call fused
     int gray_rule = 0;
@@ -427,17 +430,20 @@ struct canny_hip_ctx {
     // labelling (canny_hip_components_profile_get), then the two of the distance transform (canny_hip_edt_profile_get),
     // then the three of the Hough segments (canny_hip_hough_segments_profile_get), then the four of the contour chains
     // (canny_hip_contours_profile_get), then the four of the Hough circles (canny_hip_hough_circles_profile_get), then the
-    // three of the polygon approximation (canny_hip_polygons_profile_get).  The mask is a non-negative int option: bit 30
-    // is the last it can carry, and the three polygon slots go by it together
+    // three of the polygon approximation (canny_hip_polygons_profile_get), then the two of the sub-pixel edgels
+    // (canny_hip_edgels_profile_get).  The mask is a non-negative int option: bit 30 is the last it can carry, and the
+    // three polygon slots and the two edgel slots behind them go by it together
     static constexpr int kProfHough = CANNY_HIP_STAGE_END, kProfComponents = CANNY_HIP_STAGE_END + 3;
     static constexpr int kProfEdt = kProfComponents + CANNY_HIP_CC_PARTS;
     static constexpr int kProfSegments = kProfEdt + CANNY_HIP_EDT_PARTS;
     static constexpr int kProfContours = kProfSegments + CANNY_HIP_SEGMENT_PARTS;
     static constexpr int kProfCircles = kProfContours + CANNY_HIP_CONTOUR_PARTS;
     static constexpr int kProfPolygons = kProfCircles + CANNY_HIP_CIRCLE_PARTS;
-    static constexpr int kProfSlots = kProfPolygons + CANNY_HIP_POLYGON_PARTS;
+    static constexpr int kProfEdgels = kProfPolygons + CANNY_HIP_POLYGON_PARTS;
+    static constexpr int kProfSlots = kProfEdgels + CANNY_HIP_EDGEL_PARTS;
     static constexpr int kProfLastBit = 30;
-    static_assert(kProfPolygons == kProfLastBit, "profile_stage_mask has one bit per slot up to the polygon parts");
+    static_assert(kProfPolygons == kProfLastBit && kProfEdgels > kProfLastBit,
+                  "profile_stage_mask has one bit per slot up to the polygon parts; every slot from there on follows bit 30");
     unsigned prof_seen[kProfSlots] = {0};
     std::vector<EventPair> pending[kProfSlots];
     std::vector<EventPair> pool;
@@ -887,6 +893,7 @@ int dev_canny(canny_hip_ctx *ctx, const unsigned char *d_img, float sigma, int l
         if (gaussian_u8_possible(ctx, taps, h, w)) sm_u8 = ctx->smoothed_u8;
     }
     ctx->last_canny_u8 = sm_u8;
+    ctx->last_canny_n = n, ctx->last_canny_h = h, ctx->last_canny_w = w;
     if (color && color->ch > 1) {
         // colour: the u8 Gaussian converts as it loads where it can, else a standalone pass converts first and the
         // gray path runs unchanged on the context's gray workspace
@@ -1060,6 +1067,7 @@ int dev_canny_stream(canny_hip_ctx *ctx, const unsigned char *d_img, float sigma
         if (gaussian_u8_possible(ctx, taps, h, w)) sm_u8 = ctx->smoothed_u8;
     }
     ctx->last_canny_u8 = sm_u8;
+    ctx->last_canny_n = n, ctx->last_canny_h = h, ctx->last_canny_w = w;
     int rc = dev_gaussian(ctx, d_img, sigma, h, w, n, sm, sm_u8);
     if (rc) return rc;
     if ((rc = finish_pending(ctx))) return rc; // host waits here while the Gaussian runs
@@ -3186,6 +3194,164 @@ int canny_hip_points_from_bits(const unsigned char *bits, int height, int width,
         }
     }
     *count = n;
+    return CANNY_HIP_OK;
+}
+
+// ---- sub-pixel edgels (canny_edgels.hip) -----------------------------------------
+namespace {
+
+// dev_canny (unchanged), count + scan of its map as the point lists do it, timed as the edgels' layout part.  *strong_out
+// as dev_canny_points_count.
+int dev_canny_edgels_count(canny_hip_ctx *ctx, const unsigned char *d_img, float sigma, int lo, int hi, int h, int w, int n,
+                           short *d_edges, unsigned long long *d_offsets, const uint64_t **strong_out)
+{
+    int rc;
+    if (!d_edges) {
+        HIP_TRY(ctx, ctx->edges16.ensure(npx(h, w, n) * sizeof(short)));
+        d_edges = (short *)ctx->edges16.p;
+    }
+    if ((rc = dev_canny(ctx, d_img, sigma, lo, hi, h, w, n, d_edges))) return rc;
+    if (hi > 255) { // the records follow the MAP: the reference zeroes every reached pixel
+        *strong_out = nullptr;
+        HIP_TRY(ctx, hipMemsetAsync(d_offsets, 0, ((size_t)n + 1) * sizeof(unsigned long long), ctx->stream));
+        return CANNY_HIP_OK;
+    }
+    *strong_out = (const uint64_t *)ctx->plane_s.p;
+    const HystGeom g = make_hyst_geom(h, w, n);
+    HIP_TRY(ctx, ctx->points.ensure(g.n_frames * sizeof(unsigned long long) + (size_t)n * h * sizeof(uint32_t)));
+    unsigned long long *totals = (unsigned long long *)ctx->points.p;
+    uint32_t *row_words = (uint32_t *)(totals + g.n_frames);
+    StageTimer tm(ctx, canny_hip_ctx::kProfEdgels + CANNY_HIP_EDGEL_PART_LAYOUT);
+    HIP_TRY(ctx, launch_points_count(*strong_out, nullptr, g, row_words, ctx->stream));
+    HIP_TRY(ctx, launch_points_scan(row_words, totals, d_offsets, g.height, g.n_frames, ctx->stream));
+    return CANNY_HIP_OK;
+}
+
+// the records, behind dev_canny_edgels_count on the same stream: the strong plane and the smoothed plane that call left
+int dev_edgels_rows(canny_hip_ctx *ctx, const uint64_t *strong, const HystGeom &g, const unsigned long long *d_offsets,
+                    int *d_edgels, unsigned *d_points, unsigned long long capacity)
+{
+    if (!capacity) return CANNY_HIP_OK;
+    const uint32_t *row_words = (const uint32_t *)((const unsigned long long *)ctx->points.p + g.n_frames);
+    StageTimer tm(ctx, canny_hip_ctx::kProfEdgels + CANNY_HIP_EDGEL_PART_REFINE);
+    HIP_TRY(ctx, launch_edgels_rows(strong, g, ctx->smoothed.p, ctx->last_canny_u8 != 0, row_words, d_offsets, d_edgels,
+                                    d_points, capacity, ctx->stream));
+    return CANNY_HIP_OK;
+}
+
+} // namespace
+
+int canny_hip_dev_canny_edgels(canny_hip_ctx *ctx, const unsigned char *d_img, float sigma, int min_val, int max_val,
+                               int height, int width, int n_frames, short *d_edges, int *d_edgels,
+                               unsigned long long capacity, unsigned long long *d_offsets, unsigned int *d_points)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!d_img || !d_offsets || (!d_edgels && capacity) || ((uintptr_t)d_edgels & 15)) return CANNY_HIP_ERR_INVALID;
+    if ((rc = check_dims(height, width, n_frames))) return rc;
+    const uint64_t *strong = nullptr;
+    if ((rc = dev_canny_edgels_count(ctx, d_img, sigma, min_val, max_val, height, width, n_frames, d_edges, d_offsets,
+                                     &strong)))
+        return rc;
+    if (!strong) return CANNY_HIP_OK;
+    return dev_edgels_rows(ctx, strong, make_hyst_geom(height, width, n_frames), d_offsets, d_edgels, d_points, capacity);
+}
+
+int canny_hip_dev_edgels_at(canny_hip_ctx *ctx, const void *d_plane, int plane_is_u8, int height, int width, int n_frames,
+                            const unsigned int *d_points, const unsigned long long *d_point_offsets, int *d_edgels,
+                            unsigned long long capacity)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!d_point_offsets || ((!d_edgels || !d_points) && capacity) || ((uintptr_t)d_edgels & 15) || height < 2 || width < 2)
+        return CANNY_HIP_ERR_INVALID;
+    if ((rc = check_dims(height, width, n_frames))) return rc;
+    if (!d_plane) {
+        // the plane the last canny call left: only for the batch it belongs to
+        if (!ctx->last_canny_n || !ctx->smoothed.p || ctx->last_canny_n != n_frames || ctx->last_canny_h != height ||
+            ctx->last_canny_w != width)
+            return CANNY_HIP_ERR_INVALID;
+        d_plane = ctx->smoothed.p;
+        plane_is_u8 = ctx->last_canny_u8;
+    }
+    if ((rc = finish_pending(ctx))) return rc;
+    if (!capacity) return CANNY_HIP_OK;
+    StageTimer tm(ctx, canny_hip_ctx::kProfEdgels + CANNY_HIP_EDGEL_PART_REFINE);
+    HIP_TRY(ctx, launch_edgels_at(d_plane, plane_is_u8 != 0, height, width, n_frames, d_points, d_point_offsets, d_edgels,
+                                  capacity, ctx->stream));
+    return CANNY_HIP_OK;
+}
+
+int canny_hip_canny_edgels(canny_hip_ctx *ctx, const unsigned char *imgs, int n_frames, float sigma, int min_val,
+                           int max_val, int height, int width, int *edgels, unsigned long long capacity,
+                           unsigned long long *offsets, unsigned int *points)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!imgs || !offsets || (!edgels && capacity)) return CANNY_HIP_ERR_INVALID;
+    if ((rc = check_dims(height, width, n_frames))) return rc;
+    const size_t off_bytes = ((size_t)n_frames + 1) * sizeof(unsigned long long);
+    if ((rc = h2d(ctx, ctx->io[0], imgs, npx(height, width, n_frames)))) return rc;
+    HIP_TRY(ctx, ctx->io[1].ensure(off_bytes));
+    unsigned long long *d_offsets = (unsigned long long *)ctx->io[1].p;
+    const uint64_t *strong = nullptr;
+    if ((rc = dev_canny_edgels_count(ctx, (const unsigned char *)ctx->io[0].p, sigma, min_val, max_val, height, width,
+                                     n_frames, nullptr, d_offsets, &strong)))
+        return rc;
+    // the offsets come down first: they say how many records there are to compute and to download
+    std::vector<unsigned long long> off((size_t)n_frames + 1);
+    if ((rc = d2h_sync(ctx, off.data(), d_offsets, off_bytes))) return rc;
+    const unsigned long long n_rec = std::min(off[n_frames], capacity);
+    if (n_rec) {
+        const size_t rec_bytes = (size_t)n_rec * CANNY_HIP_EDGEL_INTS * sizeof(int);
+        HIP_TRY(ctx, ctx->io[2].ensure(rec_bytes));
+        if (points) HIP_TRY(ctx, ctx->io[3].ensure((size_t)n_rec * sizeof(unsigned)));
+        if ((rc = dev_edgels_rows(ctx, strong, make_hyst_geom(height, width, n_frames), d_offsets, (int *)ctx->io[2].p,
+                                  points ? (unsigned *)ctx->io[3].p : nullptr, n_rec)))
+            return rc;
+        if (points)
+            HIP_TRY(ctx, hipMemcpyAsync(points, ctx->io[3].p, (size_t)n_rec * sizeof(unsigned), hipMemcpyDeviceToHost,
+                                        ctx->stream));
+        if ((rc = d2h_sync(ctx, edgels, ctx->io[2].p, rec_bytes))) return rc;
+    }
+    std::memcpy(offsets, off.data(), off_bytes);
+    return CANNY_HIP_OK;
+}
+
+int canny_hip_dev_edgels_arith(canny_hip_ctx *ctx, const short *d_gx, const short *d_gy, size_t n_pairs,
+                               unsigned int *d_mag, int *d_dir, const unsigned int *d_abc, size_t n_triples, int *d_t,
+                               int *d_refined)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if ((n_pairs && (!d_gx || !d_gy || !d_mag || !d_dir)) || (n_triples && (!d_abc || !d_t || !d_refined)) ||
+        (!n_pairs && !n_triples))
+        return CANNY_HIP_ERR_INVALID;
+    if ((rc = finish_pending(ctx))) return rc;
+    HIP_TRY(ctx, launch_edgels_arith(d_gx, d_gy, n_pairs, d_mag, d_dir, d_abc, n_triples, d_t, d_refined, ctx->stream));
+    return CANNY_HIP_OK;
+}
+
+static int profile_collect(canny_hip_ctx *ctx);
+
+int canny_hip_edgels_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches)
+{
+    if (part < 0 || part >= CANNY_HIP_EDGEL_PARTS || !total_ms || !launches) return CANNY_HIP_ERR_INVALID;
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if ((rc = profile_collect(ctx))) return rc;
+    *total_ms = ctx->total_ms[canny_hip_ctx::kProfEdgels + part];
+    *launches = ctx->launches[canny_hip_ctx::kProfEdgels + part];
+    return CANNY_HIP_OK;
+}
+
+// Host-only: the launch plan of the index-driven edgel kernel (plan_edgels_at), outputs as canny_hip_selftest_launch_plan.
+int canny_hip_selftest_edgels_plan(int n_frames, int height, int width, unsigned long long n_points,
+                                   unsigned long long *out)
+{
+    if (!out || !n_points || height < 2 || width < 2 || check_dims(height, width, n_frames)) return CANNY_HIP_ERR_INVALID;
+    const LaunchPlan p = plan_edgels_at(height, width, n_points);
+    out[0] = p.units, out[1] = p.per_group, out[2] = p.grid, out[3] = p.trips(), out[4] = (unsigned long long)p.aux;
     return CANNY_HIP_OK;
 }
 

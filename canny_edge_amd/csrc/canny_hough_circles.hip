@@ -56,27 +56,6 @@ __device__ __forceinline__ void circle_step(int gx, int gy, int *sx, int *sy)
     *sy = (int)rintf((float)(gy * 1024) / m);
 }
 
-// The reference's 3x3 Sobel pair (calculateXYGradient) at one pixel of a frame: gx clamps columns and drops rows outside
-// the frame, gy clamps rows and drops columns.
-template <class T>
-__device__ __forceinline__ void sobel_pair(const T *__restrict__ img, int h, int w, int y, int x, int *gx, int *gy)
-{
-    const int cl = x > 0 ? x - 1 : 0, cr = x < w - 1 ? x + 1 : w - 1;
-    const int ru = y > 0 ? y - 1 : 0, rd = y < h - 1 ? y + 1 : h - 1;
-    const T *row = img + (size_t)y * w, *up = img + (size_t)ru * w, *dn = img + (size_t)rd * w;
-    const int ul = up[cl], uc = up[x], ur = up[cr];
-    const int ml = row[cl], mr = row[cr];
-    const int dl = dn[cl], dc = dn[x], dr = dn[cr];
-    int v = 2 * mr - 2 * ml;
-    if (y != h - 1) v += dr - dl;
-    if (y != 0) v += ur - ul;
-    int u = 2 * dc - 2 * uc;
-    if (x != w - 1) u += dr - ur;
-    if (x != 0) u += dl - ul;
-    *gx = (int)(short)v;
-    *gy = (int)(short)u;
-}
-
 struct VoteArgs {
     int min_radius, max_radius, cell_shift, aw, ah;
     int per, shift; // samples per pixel (2 * radii); log2 of the lanes that share one pixel

@@ -399,6 +399,28 @@ inline size_t circles_accum_bytes(const CircleGeom &cg, int n_frames)
 {
     return (size_t)n_frames * (cg.ah + 2) * (size_t)(cg.aw + 2) * sizeof(int);
 }
+#ifdef __HIPCC__
+// The reference's 3x3 Sobel pair (calculateXYGradient) at one pixel of a frame: gx clamps columns and drops rows outside
+// the frame, gy clamps rows and drops columns.  One copy for the circle votes and the edgels (canny_edgels.hip).
+template <class T>
+__device__ __forceinline__ void sobel_pair(const T *__restrict__ img, int h, int w, int y, int x, int *gx, int *gy)
+{
+    const int cl = x > 0 ? x - 1 : 0, cr = x < w - 1 ? x + 1 : w - 1;
+    const int ru = y > 0 ? y - 1 : 0, rd = y < h - 1 ? y + 1 : h - 1;
+    const T *row = img + (size_t)y * w, *up = img + (size_t)ru * w, *dn = img + (size_t)rd * w;
+    const int ul = up[cl], uc = up[x], ur = up[cr];
+    const int ml = row[cl], mr = row[cr];
+    const int dl = dn[cl], dc = dn[x], dr = dn[cr];
+    int v = 2 * mr - 2 * ml;
+    if (y != h - 1) v += dr - dl;
+    if (y != 0) v += ur - ul;
+    int u = 2 * dc - 2 * uc;
+    if (x != w - 1) u += dr - ur;
+    if (x != 0) u += dl - ul;
+    *gx = (int)(short)v;
+    *gy = (int)(short)u;
+}
+#endif
 // vote: zeroes the accumulators, then every set pixel with a non-zero gradient votes along both rays.  Source: bits (packed,
 // as for the point lists) with the caller's gx / gy planes (n_frames * height * width shorts each), or else the strong plane
 // with the batch's smoothed plane (bytes if smoothed_u8, else shorts), whose Sobel pair is recomputed at the set pixels.
@@ -539,6 +561,25 @@ hipError_t launch_edt_rows(const uint64_t *strong, const uint8_t *bits, const Hy
 hipError_t launch_edt_columns(const HystGeom &g, uint16_t *cols, uint32_t *stack, int *dist2, float *dist, int *nearest,
                               hipStream_t stream);
 
+// ---- Sub-pixel edgels (canny_edgels.hip) --------------------------------
+// Records are 4 ints (CANNY_HIP_EDGEL_INTS), 16-byte aligned.  plane: n_frames contiguous height x width planes, bytes if
+// plane_u8 else shorts.
+// rows: behind launch_points_count / launch_points_scan of the same strong plane on the same stream; record
+// offsets[f] + row_offsets[f * height + y] + k describes the k-th set column of the row, for every position below
+// capacity; points (optional) receives y * width + column at the same position.  The grid is plan_points_rows' rows at
+// four waves a workgroup.
+hipError_t launch_edgels_rows(const uint64_t *strong, const HystGeom &g, const void *plane, bool plane_u8,
+                              const uint32_t *row_offsets, const unsigned long long *offsets, int *edgels,
+                              uint32_t *points, unsigned long long capacity, hipStream_t stream);
+// at: record q describes pixel index points[q] of the frame f with offsets[f] <= q < offsets[f + 1], for q < capacity;
+// an index >= height * width gives the invalid record and is never dereferenced.
+hipError_t launch_edgels_at(const void *plane, bool plane_u8, int height, int width, int n_frames, const uint32_t *points,
+                            const unsigned long long *offsets, int *edgels, unsigned long long capacity,
+                            hipStream_t stream);
+// The arithmetic of the kernels alone (the exhaustive test's hook): pairs -> mag_q4, dir; (a, b, c) triples -> t_q8, refined.
+hipError_t launch_edgels_arith(const int16_t *gx, const int16_t *gy, size_t n_pairs, uint32_t *mag, int *dir,
+                               const uint32_t *abc, size_t n_triples, int *t, int *refined, hipStream_t stream);
+
 // ---- launch plans of the capped grids ---------------------------------
 // A launcher whose grid is capped hands its kernel `units` work items and `grid` workgroups that take `per_group` items
 // per trip of their grid-stride loop.  Each plan_* below is computed from sizes alone, is THE grid computation of the
@@ -587,6 +628,10 @@ LaunchPlan plan_hough_cells(unsigned long long cells);    // peaks, ties, collec
 LaunchPlan plan_circles_vote(const HystGeom &g, bool from_bits); // circle vote: 64-word chunks of a frame
 LaunchPlan plan_circles_steps(size_t n);           // circles_steps_kernel: gradient pairs
 LaunchPlan plan_to_gray(size_t n_px);              // to_gray_kernel: 16-pixel groups
+// edgels_at_kernel: the n_points points of a frame's list; the grid is sized by the frame's pixels / 1024 (only the device
+// knows the lists).  edgels_arith_kernel: pairs or triples.  (Reported by canny_hip_selftest_edgels_plan, not by a kind.)
+LaunchPlan plan_edgels_at(int height, int width, unsigned long long n_points);
+LaunchPlan plan_edgels_arith(size_t n);
 
 // ---- measurement aid ------------------------------------------------------------------------
 // Plain device copy of nbytes (multiple of 16; both pointers 16-byte aligned): what a 1:1 read/write stream reaches.

@@ -1,6 +1,6 @@
 // main.cpp -- the reference's command line (StevenChang5/Canny_Edge src/main.cpp:18-142) without
 // the webcam and the GUI:  ./Main sigma minVal maxVal [-c] [-s] [-i in.pgm|in.ppm|in.jpg] [-o dir] [-p] [-n WxH] [-b dir]
-//        [-l rho,theta_degrees,threshold[,lines_max]] [-g min_length,max_gap[,exclusive]] [-m min_area] [-t] [-d]
+//        [-l rho,theta_degrees,threshold[,lines_max]] [-g min_length,max_gap[,exclusive]] [-m min_area] [-t] [-d] [-e]
 //        [-r min_radius,max_radius,threshold,support[,min_dist[,cell_shift]]] [-y epsilon[,ratio]]
 //
 // Kept from the reference: the three positionals may appear anywhere relative to the flags
@@ -38,6 +38,10 @@
 // GPU (canny_hip_canny_hough_circles) and writes one "frame x y radius votes support" row per circle, in candidate order,
 // to canny_circles.txt in the -o directory (stdout without -o); x and y are the centre in pixels (multiples of 0.5).  A
 // malformed -r is a usage error (exit 2).  Without -r nothing changes.
+// Added: -e computes the sub-pixel edgel of every pixel of the frame's edge map on the GPU (canny_hip_canny_edgels) and
+// writes one "x y gx gy mag dir refined" row per edge pixel, in raster order, to canny_edgels.txt in the -o directory
+// (stdout without -o): x and y in pixels to three decimals, mag in grey levels, dir 0..3 (step (1,0), (1,1), (0,1), (1,-1)),
+// refined 0 / 1.  Without -e nothing changes.
 #include <algorithm>
 #include <cctype>
 #include <cmath>
@@ -390,6 +394,43 @@ static int run_contours(const vector<unsigned char> &frame, int height, int widt
     return 0;
 }
 
+// -e: one sub-pixel edgel per edge pixel of the frame's map, in raster order: "x y gx gy mag dir refined" each.
+static int run_edgels(const vector<unsigned char> &frame, int height, int width, float sigma, int minVal, int maxVal,
+                      const string &outdir)
+{
+    vector<int> rec;
+    unsigned long long offsets[2] = {0, 0};
+    canny_hip_ctx *ctx = nullptr;
+    int st = canny_hip_ctx_create(&ctx, 0);
+    // counts first, then exactly the records there are
+    if (!st) st = canny_hip_canny_edgels(ctx, frame.data(), 1, sigma, minVal, maxVal, height, width, nullptr, 0, offsets, nullptr);
+    if (!st && offsets[1]) {
+        rec.resize((size_t)offsets[1] * CANNY_HIP_EDGEL_INTS);
+        st = canny_hip_canny_edgels(ctx, frame.data(), 1, sigma, minVal, maxVal, height, width, rec.data(), offsets[1],
+                                    offsets, nullptr);
+    }
+    if (st) {
+        fprintf(stderr, "ERROR: -e: %s\n", st == CANNY_HIP_ERR_RUNTIME && ctx ? canny_hip_last_error(ctx) : canny_hip_status_string(st));
+        if (ctx) canny_hip_ctx_destroy(ctx);
+        return 1;
+    }
+    canny_hip_ctx_destroy(ctx);
+    FILE *f = outdir.empty() ? stdout : fopen((outdir + "/canny_edgels.txt").c_str(), "w");
+    if (!f) {
+        fprintf(stderr, "ERROR: cannot write %s/canny_edgels.txt\n", outdir.c_str());
+        return 1;
+    }
+    for (size_t k = 0; k < rec.size() / CANNY_HIP_EDGEL_INTS; k++) {
+        const int *r = &rec[k * CANNY_HIP_EDGEL_INTS];
+        const unsigned g = (unsigned)r[2], w3 = (unsigned)r[3];
+        fprintf(f, "%.3f %.3f %d %d %.4f %u %u\n", r[0] / 256.0, r[1] / 256.0, (int)(short)(g & 0xffffu), (int)(short)(g >> 16),
+                (w3 & CANNY_HIP_EDGEL_MAG_MASK) / 16.0, (w3 >> CANNY_HIP_EDGEL_DIR_SHIFT) & 3u,
+                (w3 & CANNY_HIP_EDGEL_REFINED) ? 1u : 0u);
+    }
+    if (f != stdout) fclose(f);
+    return 0;
+}
+
 // -y (with -t): the polygon of every contour, "frame record vertices length area2 convex x0 y0 x1 y1 ..." each.  Only the
 // polygons come down: the chains stay on the device.
 static int run_polygons(const vector<unsigned char> &frame, int height, int width, float sigma, int minVal, int maxVal,
@@ -518,6 +559,7 @@ int main(int argc, char *argv[])
     bool want_contours = false;
     bool want_circles = false;
     bool want_polygons = false;
+    bool want_edgels = false;
     unsigned polygon_epsilon_q8 = 0, polygon_ratio_q16 = 0;
     int circle_args[6] = {0, 0, 0, 0, 0, 0}; // min_radius, max_radius, threshold, support, min_dist, cell_shift
     int width = WIDTH, height = HEIGHT;
@@ -600,6 +642,8 @@ int main(int argc, char *argv[])
             want_dist = true;
         } else if (arg == "-t") {
             want_contours = true;
+        } else if (arg == "-e") {
+            want_edgels = true;
         } else if (arg == "-n" && i + 1 < argc) {
             if (sscanf(argv[++i], "%dx%d", &width, &height) != 2 || width < 2 || height < 2) {
                 fprintf(stderr, "ERROR: -n expects WIDTHxHEIGHT\n");
@@ -641,6 +685,8 @@ int main(int argc, char *argv[])
         fprintf(stderr, "   -r min_radius,max_radius,threshold,support[,min_dist[,cell_shift]]: circles of the edge map, one\n");
         fprintf(stderr, "       \"frame x y radius votes support\" line each -> canny_circles.txt in the -o dir\n");
         fprintf(stderr, "   -d: distance of every pixel to the nearest edge pixel, min(255, floor) -> canny_dist.pgm in the -o dir\n");
+        fprintf(stderr, "   -e: sub-pixel edgel of every edge pixel, one \"x y gx gy mag dir refined\" line each (x, y in pixels to three\n");
+        fprintf(stderr, "       decimals, mag in grey levels, dir 0..3) -> canny_edgels.txt in the -o dir\n");
         exit(0);
     }
 
@@ -705,6 +751,10 @@ int main(int argc, char *argv[])
     if (want_polygons) {
         const int rc = run_polygons(frame, height, width, sigma, minVal, maxVal, min_area, polygon_epsilon_q8,
                                     polygon_ratio_q16, outdir);
+        if (rc) return rc;
+    }
+    if (want_edgels) {
+        const int rc = run_edgels(frame, height, width, sigma, minVal, maxVal, outdir);
         if (rc) return rc;
     }
     if (want_dist) {

@@ -52,7 +52,8 @@
 extern "C" {
 #endif
 
-#define CANNY_HIP_VERSION 1202       /* 0.12.2: + canny_hip_selftest_launch_plan */
+#define CANNY_HIP_VERSION 1300       /* 0.13.0: + sub-pixel edgels: position, gradient and strength per edge pixel */
+/* 0.12.2: + canny_hip_selftest_launch_plan */
 /* 0.12.1: + canny_hip_selftest_workspace */
 /* 0.12.0: + polygon approximation of the contour chains, on the GPU */
 /* 0.10.0: + outer contour chains of the finished map, traced on the GPU */
@@ -458,6 +459,91 @@ int canny_hip_canny_points(canny_hip_ctx *ctx, const unsigned char *imgs, int n_
  * maps it received); *count receives the true count. */
 int canny_hip_points_from_bits(const unsigned char *bits, int height, int width, unsigned int *points,
                                unsigned long long capacity, unsigned long long *count);
+
+/* ---- sub-pixel edgels ---------------------------------------------------------------------------------------------------
+ * One record per edge pixel: its position along the gradient to 1/256 pixel, its gradient pair, its gradient magnitude to
+ * 1/16 grey level and its direction -- what a least-squares line or circle fit, a calibration target or a stereo match
+ * starts from.  The rule is all integers, so the records are the same bytes on every run and every machine;
+ * tests/edgels_rule.py restates it in numpy / Python ints, DESIGN.md section 23 describes the kernels.
+ * Input: one plane P per frame, unsigned char or short, height and width >= 2 (the smoothed plane of the detector: what
+ * canny_hip_dev_gaussian writes, or any u8 / s16 plane), and one pixel (x, y).
+ *   1. Gradient.  (gx, gy) is the reference's 3x3 pair at (x, y) with its border rules (gx clamps columns and drops rows
+ *      outside the frame, gy clamps rows and drops columns) and its wrap through short: what canny_hip_xy_gradient returns.
+ *      M(gx, gy) = (unsigned)(gx * gx) + (unsigned)(gy * gy) <= 2^31.  mag_q4 = floor(sqrt(256 * M)), EXACT: r * r <=
+ *      256 * M < (r + 1) * (r + 1) in 64 bits, r < 2^20 -- the magnitude in 1/16 grey level.
+ *   2. Direction: OpenCV's integer octant test (tan 22.5 deg = 13573 / 2^15), NOT the reference's float atan2 bins.
+ *      ax = |gx|, ay = |gy|, t22 = ax * 13573, y15 = ay << 15, t67 = t22 + (ax << 16), unsigned, all below 2^32.
+ *        gx = gy = 0       : dir 0, not refined
+ *        y15 < t22         : dir 0, step (dx, dy) = (1, 0)
+ *        y15 > t67         : dir 2, step (0, 1)
+ *        otherwise         : gx and gy of the same sign: dir 1, step (1, 1); else dir 3, step (1, -1)
+ *   3. Offset.  b = mag_q4 at (x, y), a = mag_q4 at (x - dx, y - dy), c = mag_q4 at (x + dx, y + dy), each neighbour's own
+ *      pair from step 1 with its own border rules.  Dn = 2 * b - a - c.  The edgel is REFINED iff both neighbours lie inside
+ *      the frame, the gradient is not zero, b >= a, b >= c and Dn > 0; then
+ *        t_q8 = sgn(c - a) * ((256 * |c - a| + Dn) / (2 * Dn))      (floor division)
+ *      -- the peak of the parabola through the three magnitudes, rounded half away from zero, in 1/256 of the step; b >=
+ *      max(a, c) gives |t_q8| <= 128.  Not refined: t_q8 = 0.
+ *   4. Record: CANNY_HIP_EDGEL_INTS = 4 32-bit words, 16 bytes, stored as a unit:
+ *        word 0: x_q8 = 256 * x + t_q8 * dx  (int)
+ *        word 1: y_q8 = 256 * y + t_q8 * dy  (int)
+ *        word 2: (unsigned short)gx | (unsigned short)gy << 16
+ *        word 3: mag_q4 in bits 0-23, dir in bits 24-25, CANNY_HIP_EDGEL_REFINED (bit 28), CANNY_HIP_EDGEL_INVALID (bit 31)
+ *      An INVALID record answers an index >= height * width (possible in the index-list forms only): its other 127 bits are
+ *      zero, and such an index never becomes an address.
+ * The reference's non-maximum suppression decides by float atan2 bins, and for its bins 45 and 135 it compares the two
+ * neighbours ALONG the edge (the up-right / down-left pair for a gradient that points down-right).  So a pixel of Canny's
+ * own map need not be a maximum along this rule's step.  Those pixels come back unrefined, at the pixel centre, with their
+ * gradient: that is deliberate -- the record says what the plane says, the map only chooses the pixels.
+ * Records: 16-byte aligned buffers of `capacity` records.  Nothing is stored at or past capacity records.
+ * The two parts are timed by canny_hip_edgels_profile_get (CANNY_HIP_EDGEL_PART_*); with "profile_stage_mask" they go by
+ * bit 30 together with the polygon parts.
+ * Not (yet) covered -- follow-ups: true-direction (Devernay) interpolation between neighbours in place of the quantised
+ * step; colour, per-frame-threshold and automatic-threshold forms; the three-stream batch pipeline and the sharder;
+ * sub-pixel end points for Hough segments and least-squares refits of lines and circles from edgels; dropping the s16
+ * map's store when only edgels are wanted. */
+#define CANNY_HIP_EDGEL_INTS 4
+#define CANNY_HIP_EDGEL_MAG_MASK 0x00ffffffu
+#define CANNY_HIP_EDGEL_DIR_SHIFT 24
+#define CANNY_HIP_EDGEL_REFINED 0x10000000u
+#define CANNY_HIP_EDGEL_INVALID 0x80000000u
+enum canny_hip_edgel_part {
+    CANNY_HIP_EDGEL_PART_LAYOUT = 0, /* count + scan of the map's rows */
+    CANNY_HIP_EDGEL_PART_REFINE = 1, /* the records */
+    CANNY_HIP_EDGEL_PARTS = 2
+};
+/* canny_hip_dev_canny unchanged (d_edges: the s16 map, or NULL), then count + scan as canny_hip_dev_canny_points, then one
+ * record per edge pixel in that call's order (ascending r * width + c per frame, CSR over the batch), from the converged
+ * strong plane and the smoothed plane the call left on the context.  d_offsets[0 .. n_frames] always holds the true counts;
+ * d_edgels == NULL with capacity == 0 is the counts-only call.  d_points (optional, capacity unsigned ints) receives the
+ * indices canny_hip_dev_canny_points would write.  max_val > 255 empties every list.  Asynchronous, same stream, no host
+ * round trip, no atomics; statuses as canny_hip_dev_canny_points, CANNY_HIP_ERR_INVALID for a misaligned d_edgels. */
+int canny_hip_dev_canny_edgels(canny_hip_ctx *ctx, const unsigned char *d_img, float sigma, int min_val, int max_val,
+                               int height, int width, int n_frames, short *d_edges, int *d_edgels,
+                               unsigned long long capacity, unsigned long long *d_offsets, unsigned int *d_points);
+/* The rule at caller-chosen pixels: record q describes index d_points[q] of the frame whose range in d_point_offsets[0 ..
+ * n_frames] (ascending, device) holds q -- a contour chain, a Hough segment's pixels, any list; entries are read as
+ * unsigned.  Records at q >= capacity are not written.  d_plane: n_frames contiguous height x width planes, bytes if
+ * plane_is_u8 else shorts; NULL = the smoothed plane the last canny_hip_dev_canny-family call on this context left (then
+ * plane_is_u8 is ignored) -- CANNY_HIP_ERR_INVALID, with nothing queued, if no such call ran or its (n_frames, height,
+ * width) differ.  Asynchronous; flushes a pending canny_hip_dev_canny_stream batch first. */
+int canny_hip_dev_edgels_at(canny_hip_ctx *ctx, const void *d_plane, int plane_is_u8, int height, int width, int n_frames,
+                            const unsigned int *d_points, const unsigned long long *d_point_offsets, int *d_edgels,
+                            unsigned long long capacity);
+/* Host buffers, synchronous: upload, canny, count; the offsets come down, then only min(offsets[n_frames], capacity)
+ * records (and points, if asked for) are computed and downloaded. */
+int canny_hip_canny_edgels(canny_hip_ctx *ctx, const unsigned char *imgs, int n_frames, float sigma, int min_val,
+                           int max_val, int height, int width, int *edgels, unsigned long long capacity,
+                           unsigned long long *offsets, unsigned int *points);
+/* Host-only, needs no device: the rule in plain C++ on ONE host plane and one index list; edgels receives n_points
+ * records. */
+int canny_hip_edgels_from_plane(const void *plane, int plane_is_u8, int height, int width, const unsigned int *points,
+                                unsigned long long n_points, int *edgels);
+/* Test hook: the device arithmetic of the kernels on arrays.  (a) d_gx, d_gy (n_pairs shorts each) -> d_mag (mag_q4) and
+ * d_dir; (b) d_abc (n_triples x 3 unsigned ints, each < 2^20) -> d_t (t_q8) and d_refined (1 iff b >= a, b >= c and Dn >
+ * 0).  Either part may be empty (count 0, pointers ignored).  Asynchronous. */
+int canny_hip_dev_edgels_arith(canny_hip_ctx *ctx, const short *d_gx, const short *d_gy, size_t n_pairs,
+                               unsigned int *d_mag, int *d_dir, const unsigned int *d_abc, size_t n_triples, int *d_t,
+                               int *d_refined);
 
 /* ---- Hough lines -------------------------------------------------------------------------------------------------------
  * The standard Hough line transform of a finished edge map, per frame of a batch, on the GPU, in stream order, with no host
@@ -1043,6 +1129,8 @@ int canny_hip_contours_profile_get(canny_hip_ctx *ctx, int part, double *total_m
 int canny_hip_hough_circles_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches);
 /* ... and for the three parts of the polygon approximation (CANNY_HIP_POLYGON_PART_*). */
 int canny_hip_polygons_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches);
+/* ... and for the two parts of the sub-pixel edgels (CANNY_HIP_EDGEL_PART_*). */
+int canny_hip_edgels_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches);
 
 /* ---- self-test hooks used by the GPU test-suite -------------------------------------------- */
 /* Runs the DEVICE magnitude / angle-bin functions over every (gx,gy) in [-lim,lim]^2 and writes
@@ -1151,6 +1239,12 @@ enum canny_hip_launch_plan_kind {
     CANNY_HIP_PLAN_KINDS = 18
 };
 int canny_hip_selftest_launch_plan(int kind, int n_frames, int height, int width, long long extra,
+                                   unsigned long long *out);
+/* Host-only, the same five outputs for the index-driven edgel kernel of canny_hip_dev_edgels_at (no kind of its own above:
+ * the row kernel of canny_hip_dev_canny_edgels goes by CANNY_HIP_PLAN_POINTS_ROWS).  Its grid is (out[2], n_frames), sized
+ * by the frame's pixels -- height * width / 1024 workgroups of 256 points, at least 1 and at most 1024 -- since only the
+ * device knows the lists; n_points >= 1 is the list length of ONE frame, the items the loop walks. */
+int canny_hip_selftest_edgels_plan(int n_frames, int height, int width, unsigned long long n_points,
                                    unsigned long long *out);
 
 #ifdef __cplusplus
