@@ -118,6 +118,9 @@ EXPORTS = (
     "canny_hip_canny_polygons", "canny_hip_polygons_from_chains", "canny_hip_polygons_profile_get",
     "canny_hip_dev_canny_edgels", "canny_hip_dev_edgels_at", "canny_hip_canny_edgels", "canny_hip_edgels_from_plane",
     "canny_hip_dev_edgels_arith", "canny_hip_edgels_profile_get", "canny_hip_selftest_edgels_plan",
+    "canny_hip_line_fits_from_plane", "canny_hip_dev_line_fits_bits", "canny_hip_dev_canny_hough_line_fits",
+    "canny_hip_canny_hough_line_fits", "canny_hip_dev_line_fits_arith", "canny_hip_line_fits_profile_get",
+    "canny_hip_line_fits_finish",
 )
 
 _lib: Optional[C.CDLL] = None
@@ -284,6 +287,15 @@ def load() -> C.CDLL:
         "canny_hip_dev_edgels_arith": ([p, p, p, sz, p, p, p, sz, p, p], i),
         "canny_hip_edgels_profile_get": ([p, i, C.POINTER(C.c_double), C.POINTER(C.c_long)], i),
         "canny_hip_selftest_edgels_plan": ([i, i, i, ull, p], i),
+        "canny_hip_line_fits_from_plane": ([p, p, i, i, i, f, i, i, p, p, p, i, p, i, i, p], i),
+        "canny_hip_dev_line_fits_bits": ([p, p, p, i, i, i, i, f, f, f, f, p, p, i, p, p, i, i, p], i),
+        "canny_hip_dev_canny_hough_line_fits": ([p, p, f, i, i, i, i, i, p, f, f, i, i, f, f, p, p, p, p, p, i, i, i, p, i,
+                                                 p, i, p], i),
+        "canny_hip_canny_hough_line_fits": ([p, p, i, f, i, i, i, i, f, f, i, i, f, f, i, i, i, i, p, p, p, p, p, i, p, p],
+                                            i),
+        "canny_hip_dev_line_fits_arith": ([p, p, sz, p], i),
+        "canny_hip_line_fits_finish": ([p, sz, p], i),
+        "canny_hip_line_fits_profile_get": ([p, i, C.POINTER(C.c_double), C.POINTER(C.c_long)], i),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -639,6 +651,63 @@ def edgels_plan(n_frames: int, height: int, width: int, n_points: int) -> "Launc
     if st:
         raise CannyHipError(st, "selftest_edgels_plan")
     return LaunchPlan(*(int(v) for v in out))
+
+
+LINE_FIT_INTS = 12
+LINE_FIT_GATE, LINE_FIT_REFINED_ONLY = 1, 2
+LINE_FIT_MAXD_MASK, LINE_FIT_DEGENERATE, LINE_FIT_INVALID = 0x00FFFFFF, 0x10000000, 0x80000000
+LINE_FIT_PART_FIT = 0
+
+
+def line_fits_from_plane(bits, plane, bases, segments, rho: float = 1.0, theta: float = np.pi / 180,
+                         min_theta: float = 0.0, max_theta: float = np.pi, options: int = 0) -> np.ndarray:
+    """Host-only: the line-fit rule of include/canny_hip.h on one host frame: a packed bit map (numpy.packbits(mask,
+    axis=-1)), its plane (uint8 or int16 [H, W]), the line list `bases` and segment records (k, 6) as
+    hough_segments_from_bits returns them -> (k, 12) int32 fit records; unpack them with line_fits_unpack."""
+    a = np.ascontiguousarray(plane)
+    if a.ndim != 2 or a.dtype not in (np.uint8, np.int16):
+        raise ValueError("expected a 2-D uint8 or int16 plane")
+    h, w = a.shape
+    b = np.ascontiguousarray(bits, dtype=np.uint8)
+    if b.size != h * ((w + 7) // 8):
+        raise ValueError("bits must hold height * ceil(width / 8) bytes")
+    numangle, numrho = hough_geometry(h, w, rho, theta, min_theta, max_theta)
+    tc, ts = hough_tables(rho, theta, min_theta, numangle)
+    bs = np.ascontiguousarray(bases, dtype=np.uint32).reshape(-1)
+    seg = np.ascontiguousarray(segments, dtype=np.int32).reshape(-1, SEGMENT_INTS)
+    fits = np.empty((seg.shape[0], LINE_FIT_INTS), np.int32)
+    st = load().canny_hip_line_fits_from_plane(_hp(b), _hp(a), int(a.dtype == np.uint8), h, w, rho, numangle, numrho,
+                                               _hp(tc), _hp(ts), _hp(bs) if bs.size else None, bs.size,
+                                               _hp(seg) if seg.size else None, seg.shape[0], int(options),
+                                               _hp(fits) if seg.size else None)
+    if st:
+        raise CannyHipError(st, "line_fits_from_plane")
+    return fits
+
+
+def line_fits_finish(moments) -> np.ndarray:
+    """Host-only test hook: the finishing arithmetic of the rule in plain C++ on (k, 8) int64 moment sets (n, Su, Sv, Suu,
+    Suv, Svv, ddx, ddy) -> (k, 6) int32 (mu, mv, dx_q30, dy_q30, n, DEGENERATE or 0)."""
+    m = np.ascontiguousarray(moments, dtype=np.int64).reshape(-1, 8)
+    out = np.empty((m.shape[0], 6), np.int32)
+    st = load().canny_hip_line_fits_finish(_hp(m), m.shape[0], _hp(out))
+    if st:
+        raise CannyHipError(st, "line_fits_finish")
+    return out
+
+
+def line_fits_unpack(fits) -> dict:
+    """Floats from (k, 12) int32 fit records: p0, p1, centre ([k, 2] pixels, x then y), direction ([k, 2], unit), n,
+    rms and maxd (pixels), degenerate, invalid."""
+    r = np.ascontiguousarray(np.asarray(fits, np.int32).reshape(-1, LINE_FIT_INTS))
+    w9 = np.ascontiguousarray(r[:, 9]).view(np.uint32)
+    n = r[:, 8].astype(np.int64)
+    sdd = (np.ascontiguousarray(r[:, 10]).view(np.uint32).astype(np.float64) +
+           np.ascontiguousarray(r[:, 11]).view(np.uint32).astype(np.float64) * 4294967296.0)
+    return {"p0": r[:, 0:2] / 65536.0, "p1": r[:, 2:4] / 65536.0, "centre": r[:, 4:6] / 65536.0,
+            "direction": r[:, 6:8] / float(1 << 30), "n": n, "rms": np.sqrt(sdd / np.maximum(n, 1)) / 256.0,
+            "maxd": (w9 & LINE_FIT_MAXD_MASK) / 256.0, "degenerate": (w9 & LINE_FIT_DEGENERATE) != 0,
+            "invalid": (w9 & LINE_FIT_INVALID) != 0}
 
 
 def points_to_rc(points, width: int) -> Tuple[np.ndarray, np.ndarray]:
@@ -1422,6 +1491,85 @@ class Context:
         ms, n = C.c_double(0), C.c_long(0)
         self._check(self._L.canny_hip_hough_segments_profile_get(self._h, part, C.byref(ms), C.byref(n)),
                     "hough_segments_profile_get")
+        return ms.value, n.value
+
+    # ---- sub-pixel line fits (least-squares refit of the Hough segments from edgels) -------
+    def canny_hough_line_fits(self, imgs, sigma: float, min_val: int, max_val: int, rho: float = 1.0,
+                              theta: float = np.pi / 180, threshold: int = 100, lines_max: int = 256, min_length: int = 0,
+                              max_gap: int = 0, exclusive: int = 0, segments_max: int = 4096, options: int = 0,
+                              min_theta: float = 0.0, max_theta: float = np.pi):
+        """canny_hough_segments plus one line-fit record per segment, all on the GPU: imgs (H, W) or (N, H, W) uint8 ->
+        (lines, line_counts, segments, seg_counts, fits); fits[f] int32 [k, 12], slot for slot with segments[f]; unpack
+        them with line_fits_unpack."""
+        a = np.ascontiguousarray(imgs, dtype=np.uint8)
+        if a.ndim == 2:
+            a = a[None]
+        if a.ndim != 3:
+            raise ValueError("expected uint8 [H, W] or [n_frames, H, W]")
+        n, h, w = a.shape
+        slots = n * max(int(lines_max), 1)
+        lines, votes = np.zeros((slots, 2), np.float32), np.zeros(slots, np.int32)
+        bases, counts = np.zeros(slots, np.uint32), np.zeros(n, np.int32)
+        segs = np.zeros((n, max(int(segments_max), 1), SEGMENT_INTS), np.int32)
+        fits = np.zeros((n, max(int(segments_max), 1), LINE_FIT_INTS), np.int32)
+        seg_counts = np.zeros(n, np.int32)
+        self._check(self._L.canny_hip_canny_hough_line_fits(self._h, _hp(a), n, sigma, min_val, max_val, h, w, rho, theta,
+                                                            threshold, lines_max, min_theta, max_theta, min_length,
+                                                            max_gap, exclusive, options, _hp(lines), _hp(votes),
+                                                            _hp(bases), _hp(counts), _hp(segs), segments_max,
+                                                            _hp(seg_counts), _hp(fits)), "canny_hough_line_fits")
+        out_l, out_s, out_f = [], [], []
+        for f in range(n):
+            k, at = min(int(counts[f]), lines_max), f * lines_max
+            out_l.append((lines[at:at + k].copy(), votes[at:at + k].copy(), bases[at:at + k].copy()))
+            j = min(int(seg_counts[f]), segments_max)
+            out_s.append(segs[f, :j].copy())
+            out_f.append(fits[f, :j].copy())
+        return out_l, counts, out_s, seg_counts, out_f
+
+    def dev_line_fits_bits(self, d_bits: int, d_plane: int, plane_is_u8: bool, n: int, h: int, w: int, rho: float,
+                           theta: float, min_theta: float, max_theta: float, d_bases: int, d_line_counts: int,
+                           lines_max: int, d_segments: int, d_seg_counts: int, segments_max: int, options: int,
+                           d_fits: int):
+        """The fits of the segment records an earlier call left on the device (d_segments, d_seg_counts; lines in d_bases,
+        d_line_counts) on device bit maps (layout of dev_canny_bits) and a device plane (u8 or s16; 0 = the smoothed plane
+        the last canny call of the same shape left).  d_fits: n * segments_max * 12 int32, 16-byte aligned."""
+        v = C.c_void_p
+        self._check(self._L.canny_hip_dev_line_fits_bits(self._h, v(d_bits or None), v(d_plane or None), int(plane_is_u8),
+                                                         n, h, w, rho, theta, min_theta, max_theta, v(d_bases or None),
+                                                         v(d_line_counts or None), lines_max, v(d_segments or None),
+                                                         v(d_seg_counts or None), segments_max, options,
+                                                         v(d_fits or None)), "dev_line_fits_bits")
+
+    def dev_canny_hough_line_fits(self, d_img: int, sigma: float, min_val: int, max_val: int, h: int, w: int, n: int,
+                                  rho: float, theta: float, threshold: int, lines_max: int, min_theta: float,
+                                  max_theta: float, min_length: int, max_gap: int, exclusive: int, d_segments: int,
+                                  segments_max: int, d_seg_counts: int, options: int, d_fits: int, d_lines: int = 0,
+                                  d_votes: int = 0, d_bases: int = 0, d_line_counts: int = 0, d_accum: int = 0,
+                                  d_edges: int = 0):
+        """dev_canny_hough_segments, then the fits of its segments queued behind it on the same stream."""
+        v = C.c_void_p
+        self._check(self._L.canny_hip_dev_canny_hough_line_fits(self._h, v(d_img or None), sigma, min_val, max_val, h, w, n,
+                                                                v(d_edges or None), rho, theta, threshold, lines_max,
+                                                                min_theta, max_theta, v(d_lines or None),
+                                                                v(d_votes or None), v(d_bases or None),
+                                                                v(d_line_counts or None), v(d_accum or None), min_length,
+                                                                max_gap, exclusive, v(d_segments or None), segments_max,
+                                                                v(d_seg_counts or None), options, v(d_fits or None)),
+                    "dev_canny_hough_line_fits")
+
+    def dev_line_fits_arith(self, d_moments: int, n_sets: int, d_out: int):
+        """Test hook: the device finishing arithmetic on n_sets x 8 int64 (n, Su, Sv, Suu, Suv, Svv, ddx, ddy) -> n_sets
+        x 6 int32 (mu, mv, dx_q30, dy_q30, n, DEGENERATE or 0)."""
+        v = C.c_void_p
+        self._check(self._L.canny_hip_dev_line_fits_arith(self._h, v(d_moments or None), n_sets, v(d_out or None)),
+                    "dev_line_fits_arith")
+
+    def line_fits_profile_get(self, part: int = 0) -> Tuple[float, int]:
+        """(total ms, launch groups) of part 0, the fit kernel (LINE_FIT_PART_FIT)."""
+        ms, n = C.c_double(0), C.c_long(0)
+        self._check(self._L.canny_hip_line_fits_profile_get(self._h, part, C.byref(ms), C.byref(n)),
+                    "line_fits_profile_get")
         return ms.value, n.value
 
     # ---- Hough circles (cv::HoughCircles(HOUGH_GRADIENT) semantics; DESIGN.md section 18) ------------------------

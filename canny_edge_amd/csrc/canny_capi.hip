@@ -431,8 +431,9 @@ struct canny_hip_ctx {
     // then the three of the Hough segments (canny_hip_hough_segments_profile_get), then the four of the contour chains
     // (canny_hip_contours_profile_get), then the four of the Hough circles (canny_hip_hough_circles_profile_get), then the
     // three of the polygon approximation (canny_hip_polygons_profile_get), then the two of the sub-pixel edgels
-    // (canny_hip_edgels_profile_get).  The mask is a non-negative int option: bit 30 is the last it can carry, and the
-    // three polygon slots and the two edgel slots behind them go by it together
+    // (canny_hip_edgels_profile_get), then the one of the line fits (canny_hip_line_fits_profile_get).  The mask is a
+    // non-negative int option: bit 30 is the last it can carry, and the three polygon slots, the two edgel slots and the
+    // line-fit slot behind them go by it together
     static constexpr int kProfHough = CANNY_HIP_STAGE_END, kProfComponents = CANNY_HIP_STAGE_END + 3;
     static constexpr int kProfEdt = kProfComponents + CANNY_HIP_CC_PARTS;
     static constexpr int kProfSegments = kProfEdt + CANNY_HIP_EDT_PARTS;
@@ -440,7 +441,8 @@ struct canny_hip_ctx {
     static constexpr int kProfCircles = kProfContours + CANNY_HIP_CONTOUR_PARTS;
     static constexpr int kProfPolygons = kProfCircles + CANNY_HIP_CIRCLE_PARTS;
     static constexpr int kProfEdgels = kProfPolygons + CANNY_HIP_POLYGON_PARTS;
-    static constexpr int kProfSlots = kProfEdgels + CANNY_HIP_EDGEL_PARTS;
+    static constexpr int kProfLineFits = kProfEdgels + CANNY_HIP_EDGEL_PARTS;
+    static constexpr int kProfSlots = kProfLineFits + CANNY_HIP_LINE_FIT_PARTS;
     static constexpr int kProfLastBit = 30;
     static_assert(kProfPolygons == kProfLastBit && kProfEdgels > kProfLastBit,
                   "profile_stage_mask has one bit per slot up to the polygon parts; every slot from there on follows bit 30");
@@ -4264,6 +4266,183 @@ int canny_hip_canny_hough_segments(canny_hip_ctx *ctx, const unsigned char *imgs
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     if (line_counts) std::memcpy(line_counts, cnt.data(), (size_t)n_frames * sizeof(int));
     std::memcpy(seg_counts, cnt.data() + n_frames, (size_t)n_frames * sizeof(int));
+    return CANNY_HIP_OK;
+}
+
+// ---- sub-pixel line fits (canny_line_fits.hip) ------------------------------------
+namespace {
+
+// THE check of the fit arguments; needs no device and writes nothing
+int line_fits_check(int height, int width, int n_frames, float rho, int segments_max, int options, const int *d_fits)
+{
+    if ((options & ~(CANNY_HIP_LINE_FIT_GATE | CANNY_HIP_LINE_FIT_REFINED_ONLY)) || !d_fits || ((uintptr_t)d_fits & 15) ||
+        segments_max < 1 || height < 2 || width < 2)
+        return CANNY_HIP_ERR_INVALID;
+    if (std::max(height, width) > CANNY_HIP_LINE_FIT_MAX_AXIS || rho > CANNY_HIP_LINE_FIT_MAX_RHO)
+        return CANNY_HIP_ERR_UNSUPPORTED;
+    if ((double)n_frames * (double)segments_max * CANNY_HIP_LINE_FIT_INTS >= 2147483648.0) return CANNY_HIP_ERR_UNSUPPORTED;
+    return CANNY_HIP_OK;
+}
+
+// the fits of the segment records in d_segments, queued on the context's stream
+int dev_line_fits(canny_hip_ctx *ctx, const uint64_t *strong, const uint8_t *bits, const HystGeom &g, const HoughGeom &hg,
+                  const unsigned *d_bases, const int *d_line_counts, int lines_max, const int *d_segments,
+                  const int *d_seg_counts, int segments_max, const void *d_plane, bool plane_u8, int options, int *d_fits)
+{
+    int rc = hough_tab_ensure(ctx, hg);
+    if (rc) return rc;
+    const SegGeom sg{hg.numangle, hg.numrho, hough_segments_halfwin(g.height, g.width, hg.rho), 0, 0, lines_max,
+                     segments_max};
+    StageTimer tm(ctx, canny_hip_ctx::kProfLineFits + CANNY_HIP_LINE_FIT_PART_FIT);
+    HIP_TRY(ctx, launch_line_fits(strong, bits, g, sg, (const float *)ctx->hough_tab.p, d_bases, d_line_counts, d_segments,
+                                  d_seg_counts, d_plane, plane_u8, options, d_fits, ctx->stream));
+    return CANNY_HIP_OK;
+}
+
+} // namespace
+
+int canny_hip_dev_line_fits_bits(canny_hip_ctx *ctx, const unsigned char *d_bits, const void *d_plane, int plane_is_u8,
+                                 int n_frames, int height, int width, float rho, float theta, float min_theta,
+                                 float max_theta, const unsigned int *d_bases, const int *d_line_counts, int lines_max,
+                                 const int *d_segments, const int *d_seg_counts, int segments_max, int options,
+                                 int *d_fits)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!d_bits || !d_bases || !d_line_counts || !d_segments || !d_seg_counts || lines_max < 1) return CANNY_HIP_ERR_INVALID;
+    if ((rc = check_dims(height, width, n_frames))) return rc;
+    HoughGeom hg;
+    if ((rc = hough_geometry(height, width, rho, theta, min_theta, max_theta, &hg.numangle, &hg.numrho))) return rc;
+    if (lines_max > kHoughMaxLines) return CANNY_HIP_ERR_UNSUPPORTED;
+    if ((rc = line_fits_check(height, width, n_frames, rho, segments_max, options, d_fits))) return rc;
+    hg.rho = rho, hg.theta = theta, hg.min_theta = min_theta;
+    if (!d_plane) {
+        // the plane the last canny call left: only for the batch it belongs to
+        if (!ctx->last_canny_n || !ctx->smoothed.p || ctx->last_canny_n != n_frames || ctx->last_canny_h != height ||
+            ctx->last_canny_w != width)
+            return CANNY_HIP_ERR_INVALID;
+        d_plane = ctx->smoothed.p;
+        plane_is_u8 = ctx->last_canny_u8;
+    }
+    if ((rc = finish_pending(ctx))) return rc;
+    return dev_line_fits(ctx, nullptr, d_bits, make_hyst_geom(height, width, n_frames), hg, d_bases, d_line_counts,
+                         lines_max, d_segments, d_seg_counts, segments_max, d_plane, plane_is_u8 != 0, options, d_fits);
+}
+
+int canny_hip_dev_canny_hough_line_fits(canny_hip_ctx *ctx, const unsigned char *d_img, float sigma, int min_val,
+                                        int max_val, int height, int width, int n_frames, short *d_edges, float rho,
+                                        float theta, int threshold, int lines_max, float min_theta, float max_theta,
+                                        float *d_lines, int *d_votes, unsigned int *d_bases, int *d_line_counts,
+                                        int *d_accum, int min_length, int max_gap, int exclusive, int *d_segments,
+                                        int segments_max, int *d_seg_counts, int options, int *d_fits)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!d_img || !d_segments || !d_seg_counts || lines_max < 1) return CANNY_HIP_ERR_INVALID;
+    if ((rc = check_dims(height, width, n_frames))) return rc;
+    HoughGeom hg;
+    if ((rc = hough_geometry(height, width, rho, theta, min_theta, max_theta, &hg.numangle, &hg.numrho))) return rc;
+    if ((rc = line_fits_check(height, width, n_frames, rho, segments_max, options, d_fits))) return rc;
+    hg.rho = rho, hg.theta = theta, hg.min_theta = min_theta;
+    // the fits need the bases and the line counts: the context's own where the caller wants none (as the segments do)
+    const size_t slots = (size_t)n_frames * lines_max;
+    if (!d_bases || !d_line_counts) {
+        HIP_TRY(ctx, ctx->seg_lines.ensure((slots + (size_t)n_frames) * sizeof(int)));
+        int *own = (int *)ctx->seg_lines.p;
+        if (!d_bases) d_bases = (unsigned int *)own;
+        if (!d_line_counts) d_line_counts = own + slots;
+    }
+    if ((rc = canny_hip_dev_canny_hough_segments(ctx, d_img, sigma, min_val, max_val, height, width, n_frames, d_edges, rho,
+                                                 theta, threshold, lines_max, min_theta, max_theta, d_lines, d_votes,
+                                                 d_bases, d_line_counts, d_accum, min_length, max_gap, exclusive,
+                                                 d_segments, segments_max, d_seg_counts)))
+        return rc;
+    if (max_val > 255) return CANNY_HIP_OK; // the empty map: every segment count is 0
+    return dev_line_fits(ctx, (const uint64_t *)ctx->plane_s.p, nullptr, make_hyst_geom(height, width, n_frames), hg,
+                         d_bases, d_line_counts, lines_max, d_segments, d_seg_counts, segments_max, ctx->smoothed.p,
+                         ctx->last_canny_u8 != 0, options, d_fits);
+}
+
+int canny_hip_canny_hough_line_fits(canny_hip_ctx *ctx, const unsigned char *imgs, int n_frames, float sigma, int min_val,
+                                    int max_val, int height, int width, float rho, float theta, int threshold,
+                                    int lines_max, float min_theta, float max_theta, int min_length, int max_gap,
+                                    int exclusive, int options, float *lines, int *votes, unsigned int *bases,
+                                    int *line_counts, int *segments, int segments_max, int *seg_counts, int *fits)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!imgs || !fits || !seg_counts || lines_max < 1) return CANNY_HIP_ERR_INVALID;
+    if ((rc = check_dims(height, width, n_frames))) return rc;
+    {
+        const SegArgs a{min_length, max_gap, exclusive, segments_max};
+        HoughGeom hg;
+        int lds_rows = 0, probe = 0;
+        const HoughOut out{nullptr, nullptr, nullptr, &probe, nullptr};
+        if ((rc = hough_prepare(ctx, height, width, rho, theta, lines_max, min_theta, max_theta, out, hg, &lds_rows)) ||
+            (rc = segments_check(height, width, n_frames, lines_max, a, true)) ||
+            (rc = line_fits_check(height, width, n_frames, rho, segments_max, options, (const int *)16)))
+            return rc;
+    }
+    const size_t slots = (size_t)n_frames * lines_max, seg_slots = (size_t)n_frames * segments_max;
+    // staging: lines (2 floats per slot) | votes | bases | line counts | segment counts; the fits, then the segment records
+    HIP_TRY(ctx, ctx->io[1].ensure(slots * 16 + 2 * (size_t)n_frames * sizeof(int)));
+    HIP_TRY(ctx, ctx->io[2].ensure(seg_slots * (CANNY_HIP_LINE_FIT_INTS + CANNY_HIP_SEGMENT_INTS) * sizeof(int)));
+    char *d = (char *)ctx->io[1].p;
+    float *d_lines = (float *)d;
+    int *d_votes = (int *)(d + slots * 8);
+    unsigned *d_bases = (unsigned *)(d + slots * 12);
+    int *d_line_counts = (int *)(d + slots * 16), *d_seg_counts = d_line_counts + n_frames;
+    int *d_fits = (int *)ctx->io[2].p, *d_segments = d_fits + seg_slots * CANNY_HIP_LINE_FIT_INTS;
+    if ((rc = h2d(ctx, ctx->io[0], imgs, npx(height, width, n_frames)))) return rc;
+    if ((rc = canny_hip_dev_canny_hough_line_fits(ctx, (const unsigned char *)ctx->io[0].p, sigma, min_val, max_val, height,
+                                                  width, n_frames, nullptr, rho, theta, threshold, lines_max, min_theta,
+                                                  max_theta, lines ? d_lines : nullptr, votes ? d_votes : nullptr, d_bases,
+                                                  d_line_counts, nullptr, min_length, max_gap, exclusive, d_segments,
+                                                  segments_max, d_seg_counts, options, d_fits)))
+        return rc;
+    std::vector<int> cnt(2 * (size_t)n_frames);
+    if ((rc = d2h_sync(ctx, cnt.data(), d_line_counts, cnt.size() * sizeof(int)))) return rc;
+    // the counts first, then only the filled slots of each frame
+    for (int f = 0; f < n_frames; f++) {
+        const size_t k = (size_t)std::min(cnt[f], lines_max), at = (size_t)f * lines_max;
+        if (k && lines)
+            HIP_TRY(ctx, hipMemcpyAsync(lines + 2 * at, d_lines + 2 * at, k * 8, hipMemcpyDeviceToHost, ctx->stream));
+        if (k && votes) HIP_TRY(ctx, hipMemcpyAsync(votes + at, d_votes + at, k * 4, hipMemcpyDeviceToHost, ctx->stream));
+        if (k && bases) HIP_TRY(ctx, hipMemcpyAsync(bases + at, d_bases + at, k * 4, hipMemcpyDeviceToHost, ctx->stream));
+        const size_t j = (size_t)std::min(cnt[(size_t)n_frames + f], segments_max);
+        const size_t sat = (size_t)f * segments_max * CANNY_HIP_SEGMENT_INTS;
+        const size_t fat = (size_t)f * segments_max * CANNY_HIP_LINE_FIT_INTS;
+        if (j && segments)
+            HIP_TRY(ctx, hipMemcpyAsync(segments + sat, d_segments + sat, j * CANNY_HIP_SEGMENT_INTS * sizeof(int),
+                                        hipMemcpyDeviceToHost, ctx->stream));
+        if (j)
+            HIP_TRY(ctx, hipMemcpyAsync(fits + fat, d_fits + fat, j * CANNY_HIP_LINE_FIT_INTS * sizeof(int),
+                                        hipMemcpyDeviceToHost, ctx->stream));
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (line_counts) std::memcpy(line_counts, cnt.data(), (size_t)n_frames * sizeof(int));
+    std::memcpy(seg_counts, cnt.data() + n_frames, (size_t)n_frames * sizeof(int));
+    return CANNY_HIP_OK;
+}
+
+int canny_hip_dev_line_fits_arith(canny_hip_ctx *ctx, const long long *d_moments, size_t n_sets, int *d_out)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!n_sets || !d_moments || !d_out) return CANNY_HIP_ERR_INVALID;
+    if ((rc = finish_pending(ctx))) return rc;
+    HIP_TRY(ctx, launch_line_fits_arith(d_moments, n_sets, d_out, ctx->stream));
+    return CANNY_HIP_OK;
+}
+
+int canny_hip_line_fits_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches)
+{
+    if (part < 0 || part >= CANNY_HIP_LINE_FIT_PARTS || !total_ms || !launches) return CANNY_HIP_ERR_INVALID;
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if ((rc = profile_collect(ctx))) return rc;
+    *total_ms = ctx->total_ms[canny_hip_ctx::kProfLineFits + part];
+    *launches = ctx->launches[canny_hip_ctx::kProfLineFits + part];
     return CANNY_HIP_OK;
 }
 

@@ -17,9 +17,7 @@
 //          and the waves of a workgroup never wait for one another.
 //   at   : one lane per entry of a caller's index list, grid (blocks, n_frames), grid-stride over the frame's range; the
 //          index is tested against height * width before any address is formed.
-#include "canny_kernels.h"
-
-#include "canny_hip.h"
+#include "canny_line_support.h"
 
 namespace canny {
 
@@ -30,69 +28,7 @@ constexpr int kEdgelWaves = kEdgelBlock / 64;
 constexpr int kEdgelQueue = 64 * 64;             // every pixel of a round's 64 words set
 constexpr int kAtBlock = 256;
 
-// floor(sqrt(256 * (gx^2 + gy^2))), exact: the double root of a value below 2^40 is within one of the integer root, and
-// the two steps settle it in 64 bits.  gx, gy in [-32768, 32767]: the sum of squares is <= 2^31, formed in unsigned.
-__device__ __forceinline__ unsigned edgel_mag_q4(int gx, int gy)
-{
-    const unsigned m = (unsigned)(gx * gx) + (unsigned)(gy * gy);
-    const unsigned long long v = (unsigned long long)m << 8;
-    unsigned long long r = (unsigned long long)sqrt((double)v);
-    if (r * r > v) r--;
-    if ((r + 1) * (r + 1) <= v) r++;
-    return (unsigned)r;
-}
-
-// OpenCV's integer octant test: 0 = step (1, 0), 1 = (1, 1), 2 = (0, 1), 3 = (1, -1); (0, 0) -> 0
-__device__ __forceinline__ int edgel_dir(int gx, int gy)
-{
-    const unsigned ax = (unsigned)(gx < 0 ? -gx : gx), ay = (unsigned)(gy < 0 ? -gy : gy);
-    const unsigned t22 = ax * 13573u, y15 = ay << 15, t67 = t22 + (ax << 16);
-    if (!(gx | gy) || y15 < t22) return 0;
-    if (y15 > t67) return 2;
-    return (gx ^ gy) >= 0 ? 1 : 3;
-}
-
-// t_q8 of three magnitudes (each < 2^20); *refined = b >= a, b >= c and 2b - a - c > 0
-__device__ __forceinline__ int edgel_offset(unsigned a, unsigned b, unsigned c, bool *refined)
-{
-    const bool ok = b >= a && b >= c && 2u * b > a + c;
-    *refined = ok;
-    if (!ok) return 0;
-    const unsigned dn = 2u * b - a - c, d = c >= a ? c - a : a - c;
-    const int t = (int)((256u * d + dn) / (2u * dn));
-    return c >= a ? t : -t;
-}
-
-template <class T>
-__device__ __forceinline__ unsigned edgel_mag_at(const T *__restrict__ img, int h, int w, int y, int x)
-{
-    int gx, gy;
-    sobel_pair(img, h, w, y, x, &gx, &gy);
-    return edgel_mag_q4(gx, gy);
-}
-
-// THE record of pixel (x, y), 0 <= x < w, 0 <= y < h
-template <class T>
-__device__ __forceinline__ uint4 edgel_record(const T *__restrict__ img, int h, int w, int y, int x)
-{
-    int gx, gy;
-    sobel_pair(img, h, w, y, x, &gx, &gy);
-    const unsigned b = edgel_mag_q4(gx, gy);
-    const int dir = edgel_dir(gx, gy);
-    const int dx = dir != 2, dy = dir == 0 ? 0 : (dir == 3 ? -1 : 1);
-    const int xa = x - dx, ya = y - dy, xc = x + dx, yc = y + dy;
-    int t = 0;
-    unsigned flag = 0;
-    if ((gx | gy) && xa >= 0 && xc < w && (unsigned)ya < (unsigned)h && (unsigned)yc < (unsigned)h) {
-        const unsigned a = edgel_mag_at(img, h, w, ya, xa), c = edgel_mag_at(img, h, w, yc, xc);
-        bool ok;
-        t = edgel_offset(a, b, c, &ok);
-        if (ok) flag = CANNY_HIP_EDGEL_REFINED;
-    }
-    return make_uint4((unsigned)(256 * x + t * dx), (unsigned)(256 * y + t * dy),
-                      ((unsigned)gx & 0xffffu) | ((unsigned)gy << 16),
-                      b | (unsigned)dir << CANNY_HIP_EDGEL_DIR_SHIFT | flag);
-}
+// edgel_mag_q4, edgel_dir, edgel_offset and edgel_record live in canny_line_support.h: the line fits sum the same records.
 
 // one wave per image row; grid-stride over the rows of the batch
 template <class T>

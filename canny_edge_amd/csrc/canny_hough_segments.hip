@@ -24,7 +24,7 @@
 //                  because no 32-bit word of the copy is shared between frames: the strong plane's frames are whole
 //                  64-bit words, and packed bytes are copied to a stride of their own per frame.  The kernel is handed
 //                  the copy alone (the source pointers of its SegSrc are null): it cannot write the plane or d_bits.
-#include "canny_kernels.h"
+#include "canny_line_support.h"
 
 #include <algorithm>
 #include <cmath>
@@ -36,29 +36,8 @@ namespace {
 constexpr int kSegBlock = 256;   // non-exclusive: four waves, four lines
 constexpr int kExclBlock = 1024; // exclusive: 16 waves share one frame
 
-struct SegSrc {
-    const uint32_t *strong32; // the strong plane as 32-bit halves of its words
-    const uint8_t *bits;      // packed rows, any byte address
-    uint32_t *work;           // exclusive mode: the private copy (see launch_hough_segments_exclusive)
-    size_t work_frame_words;  // ... of packed bytes: 32-bit words from one frame's start to the next
-};
-
-// Where pixel (y, x) of frame f lives in a 32-bit view: of the strong plane (or its copy), or -- BITS -- of the private
-// copy of packed bytes, whose frames each start on a word of their own (frame_words apart): no word holds two frames' bits.
-template <bool BITS>
-__device__ __forceinline__ void bit_of(const HystGeom &g, int row_bytes, size_t frame_words, int f, int y, int x,
-                                       size_t *word, unsigned *mask)
-{
-    if constexpr (!BITS) {
-        *word = hyst_word_index(g, f, y, x >> 6) * 2 + (size_t)((x >> 5) & 1);
-        *mask = 1u << (x & 31);
-    } else {
-        const size_t b = (size_t)y * (size_t)row_bytes + (size_t)(x >> 3); // byte within the frame; rows MSB-first
-        *word = (size_t)f * frame_words + (b >> 2);
-        *mask = 1u << (8 * (int)(b & 3) + 7 - (x & 7));
-    }
-}
-
+// SegSrc, bit_of, pixel_set_src, SegLine, seg_line and seg_window live in canny_line_support.h: the line fits walk the same
+// support.
 template <bool BITS, bool EXCL>
 __device__ __forceinline__ bool pixel_set(const SegSrc &src, const HystGeom &g, int row_bytes, int f, int y, int x)
 {
@@ -67,39 +46,9 @@ __device__ __forceinline__ bool pixel_set(const SegSrc &src, const HystGeom &g, 
         unsigned mask;
         bit_of<BITS>(g, row_bytes, src.work_frame_words, f, y, x, &word, &mask);
         return (__hip_atomic_load(&src.work[word], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) & mask) != 0;
-    } else if constexpr (!BITS) {
-        size_t word;
-        unsigned mask;
-        bit_of<false>(g, row_bytes, 0, f, y, x, &word, &mask);
-        return (src.strong32[word] & mask) != 0;
     } else {
-        const size_t b = ((size_t)f * g.height + y) * (size_t)row_bytes + (size_t)(x >> 3);
-        return ((src.bits[b] >> (7 - (x & 7))) & 1) != 0;
+        return pixel_set_src<BITS>(src, g, row_bytes, f, y, x);
     }
-}
-
-struct SegLine {
-    float c, s;   // the angle's table entries
-    int r, half;  // the cell's column; (numrho - 1) / 2
-    bool major_x;
-    int L, M;     // extent of the major and of the minor axis
-};
-
-// false: the base is not a cell of the accumulator -- no segment, no access
-__device__ __forceinline__ bool seg_line(unsigned base, const float *__restrict__ tab, const SegGeom &sg, const HystGeom &g,
-                                         SegLine &ln)
-{
-    const unsigned stride = (unsigned)sg.numrho + 2u;
-    const int n = (int)(base / stride) - 1, r = (int)(base % stride) - 1;
-    if ((unsigned)n >= (unsigned)sg.numangle || (unsigned)r >= (unsigned)sg.numrho) return false;
-    ln.c = tab[n];
-    ln.s = tab[sg.numangle + n];
-    ln.r = r;
-    ln.half = (sg.numrho - 1) / 2;
-    ln.major_x = fabsf(ln.s) >= fabsf(ln.c);
-    ln.L = ln.major_x ? g.width : g.height;
-    ln.M = ln.major_x ? g.height : g.width;
-    return true;
 }
 
 // The support of the line at major position t: how many pixels (return value) and the smallest minor coordinate (*lo).
@@ -108,15 +57,10 @@ template <bool BITS, bool EXCL, bool CLEAR>
 __device__ __forceinline__ int probe(const SegSrc &src, const HystGeom &g, int row_bytes, int f, const SegLine &ln,
                                      float halfwin, int t, int *lo)
 {
-    const float c_major = ln.major_x ? ln.c : ln.s, c_minor = ln.major_x ? ln.s : ln.c; // |c_minor| >= |c_major|, never 0
-    const float m0 = ((float)(ln.r - ln.half) - (float)t * c_major) / c_minor;
-    const float a = fmaxf(floorf(m0 - halfwin), 0.0f);
-    const float b = fminf(fminf(ceilf(m0 + halfwin), (float)(ln.M - 1)), 2147483520.0f);
-    int cnt = 0;
+    int cnt = 0, ma, mb;
     *lo = 0;
-    if (!(a <= b)) return 0; // off the frame (or no estimate at all)
-    const int mb = min((int)b, ln.M - 1);
-    for (int m = (int)a; m <= mb; m++) {
+    if (!seg_window(ln, halfwin, t, &ma, &mb)) return 0; // off the frame (or no estimate at all)
+    for (int m = ma; m <= mb; m++) {
         const int x = ln.major_x ? t : m, y = ln.major_x ? m : t;
         if (vote_r(x, y, ln.c, ln.s, ln.half) != ln.r) continue;
         if (!pixel_set<BITS, EXCL>(src, g, row_bytes, f, y, x)) continue;
@@ -205,7 +149,7 @@ __global__ __launch_bounds__(kSegBlock) void seg_walk_kernel(SegSrc src, HystGeo
     const size_t slot = (size_t)f * sg.lines_max + k;
     SegLine ln;
     int found = 0;
-    if (seg_line(bases[slot], tab, sg, g, ln)) {
+    if (seg_line(bases[slot], tab, sg.numangle, sg.numrho, g, ln)) {
         const int off = EMIT ? line_off[slot] : 0;
         int *out = segments + (size_t)f * sg.segments_max * kSegRecord;
         auto close = [&](int ta, int lo_ta, int tb, int lo_tb, int support) {
@@ -282,7 +226,8 @@ __global__ __launch_bounds__(kExclBlock) void seg_exclusive_kernel(SegSrc src, H
     int total = 0; // wave 0: segments of the frame so far
     for (int k = 0; k < K; k++) {
         SegLine ln;
-        if (!seg_line(bases[(size_t)f * sg.lines_max + k], tab, sg, g, ln)) continue; // the same for every thread
+        // the same for every thread
+        if (!seg_line(bases[(size_t)f * sg.lines_max + k], tab, sg.numangle, sg.numrho, g, ln)) continue;
         for (int i = tid; i < (ln.L + 31) / 32; i += kExclBlock) s_keep[i] = 0u;
         if (tid == 0) s_kept_any = 0;
         auto close = [&](int ta, int lo_ta, int tb, int lo_tb, int support) { // wave 0

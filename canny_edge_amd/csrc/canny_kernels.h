@@ -580,6 +580,18 @@ hipError_t launch_edgels_at(const void *plane, bool plane_u8, int height, int wi
 hipError_t launch_edgels_arith(const int16_t *gx, const int16_t *gy, size_t n_pairs, uint32_t *mag, int *dir,
                                const uint32_t *abc, size_t n_triples, int *t, int *refined, hipStream_t stream);
 
+// ---- Sub-pixel line fits (canny_line_fits.hip) ---------------------------
+// One 12-int record (CANNY_HIP_LINE_FIT_INTS) per segment slot f * segments_max + j, j < min(segments_max, seg_counts[f]),
+// from the records launch_hough_segments_* left in `segments`; source (bits or else the strong plane), tab, bases and
+// line_counts as there; of sg only numangle, numrho, halfwin, lines_max and segments_max are read.  plane: n_frames
+// contiguous height x width planes, bytes if plane_u8 else shorts.  Grid (ceil(segments_max / 4), n_frames): no cap.
+hipError_t launch_line_fits(const uint64_t *strong, const uint8_t *bits, const HystGeom &g, const SegGeom &sg,
+                            const float *tab, const unsigned *bases, const int *line_counts, const int *segments,
+                            const int *seg_counts, const void *plane, bool plane_u8, int options, int *fits,
+                            hipStream_t stream);
+// The finishing arithmetic alone (the test hook): n sets of 8 long longs -> 6 ints each; one lane per set, no cap.
+hipError_t launch_line_fits_arith(const long long *moments, size_t n, int *out, hipStream_t stream);
+
 // ---- launch plans of the capped grids ---------------------------------
 // A launcher whose grid is capped hands its kernel `units` work items and `grid` workgroups that take `per_group` items
 // per trip of their grid-stride loop.  Each plan_* below is computed from sizes alone, is THE grid computation of the

@@ -38,6 +38,9 @@
 // GPU (canny_hip_canny_hough_circles) and writes one "frame x y radius votes support" row per circle, in candidate order,
 // to canny_circles.txt in the -o directory (stdout without -o); x and y are the centre in pixels (multiples of 0.5).  A
 // malformed -r is a usage error (exit 2).  Without -r nothing changes.
+// Added: -f options (with -l and -g) also computes the sub-pixel line fit of every segment on the GPU
+// (canny_hip_canny_hough_line_fits) and writes one "x0 y0 x1 y1 cx cy dx dy n rms maxd degenerate" row per segment to
+// canny_line_fits.txt.  -f without -l and -g, or with anything but 0..3, is a usage error (exit 2).
 // Added: -e computes the sub-pixel edgel of every pixel of the frame's edge map on the GPU (canny_hip_canny_edgels) and
 // writes one "x y gx gy mag dir refined" row per edge pixel, in raster order, to canny_edgels.txt in the -o directory
 // (stdout without -o): x and y in pixels to three decimals, mag in grey levels, dir 0..3 (step (1,0), (1,1), (0,1), (1,-1)),
@@ -269,28 +272,39 @@ static int run_hough(const vector<unsigned char> &frame, int height, int width, 
     return write_lines(lines, votes, min(count, lines_max), outdir);
 }
 
-// -l with -g: the lines as above and the segments along them, "x0 y0 x1 y1 line support" per segment
+// -l with -g: the lines as above and the segments along them, "x0 y0 x1 y1 line support" per segment; with -f
+// (fit_options >= 0) also the line fit of every segment, "x0 y0 x1 y1 cx cy dx dy n rms maxd degenerate" per segment
 static int run_segments(const vector<unsigned char> &frame, int height, int width, float sigma, int minVal, int maxVal,
                         double rho, double theta_deg, int threshold, int lines_max, int min_length, int max_gap,
-                        int exclusive, const string &outdir)
+                        int exclusive, int fit_options, const string &outdir)
 {
     const float theta = (float)(theta_deg * M_PI / 180.0);
     vector<float> lines((size_t)2 * max(lines_max, 1));
     vector<int> votes((size_t)max(lines_max, 1));
-    vector<int> segs;
+    vector<int> segs, fits;
     int count = 0, seg_count = 0, cap = 4096;
     canny_hip_ctx *ctx = nullptr;
     int st = canny_hip_ctx_create(&ctx, 0);
     for (int pass = 0; !st && pass < 2; pass++) { // a second time only if the first capacity was too small
         segs.resize((size_t)cap * CANNY_HIP_SEGMENT_INTS);
-        st = canny_hip_canny_hough_segments(ctx, frame.data(), 1, sigma, minVal, maxVal, height, width, (float)rho, theta,
-                                            threshold, lines_max, 0.0f, (float)M_PI, min_length, max_gap, exclusive,
-                                            lines.data(), votes.data(), nullptr, &count, segs.data(), cap, &seg_count);
+        if (fit_options >= 0) {
+            fits.resize((size_t)cap * CANNY_HIP_LINE_FIT_INTS);
+            st = canny_hip_canny_hough_line_fits(ctx, frame.data(), 1, sigma, minVal, maxVal, height, width, (float)rho,
+                                                 theta, threshold, lines_max, 0.0f, (float)M_PI, min_length, max_gap,
+                                                 exclusive, fit_options, lines.data(), votes.data(), nullptr, &count,
+                                                 segs.data(), cap, &seg_count, fits.data());
+        } else {
+            st = canny_hip_canny_hough_segments(ctx, frame.data(), 1, sigma, minVal, maxVal, height, width, (float)rho,
+                                                theta, threshold, lines_max, 0.0f, (float)M_PI, min_length, max_gap,
+                                                exclusive, lines.data(), votes.data(), nullptr, &count, segs.data(), cap,
+                                                &seg_count);
+        }
         if (seg_count <= cap) break;
         cap = seg_count;
     }
     if (st) {
-        fprintf(stderr, "ERROR: -g: %s\n", st == CANNY_HIP_ERR_RUNTIME && ctx ? canny_hip_last_error(ctx) : canny_hip_status_string(st));
+        fprintf(stderr, "ERROR: %s: %s\n", fit_options >= 0 ? "-f" : "-g",
+                st == CANNY_HIP_ERR_RUNTIME && ctx ? canny_hip_last_error(ctx) : canny_hip_status_string(st));
         if (ctx) canny_hip_ctx_destroy(ctx);
         return 1;
     }
@@ -304,6 +318,22 @@ static int run_segments(const vector<unsigned char> &frame, int height, int widt
     for (int j = 0; j < seg_count; j++) {
         const int *r = segs.data() + (size_t)j * CANNY_HIP_SEGMENT_INTS;
         fprintf(f, "%d %d %d %d %d %d\n", r[0], r[1], r[2], r[3], r[4], r[5]);
+    }
+    if (f != stdout) fclose(f);
+    if (fit_options < 0) return 0;
+    f = outdir.empty() ? stdout : fopen((outdir + "/canny_line_fits.txt").c_str(), "w");
+    if (!f) {
+        fprintf(stderr, "ERROR: cannot write %s/canny_line_fits.txt\n", outdir.c_str());
+        return 1;
+    }
+    for (int j = 0; j < seg_count; j++) {
+        const int *r = fits.data() + (size_t)j * CANNY_HIP_LINE_FIT_INTS;
+        const unsigned flags = (unsigned)r[9];
+        const double sdd = (double)(unsigned)r[10] + 4294967296.0 * (double)(unsigned)r[11];
+        fprintf(f, "%.4f %.4f %.4f %.4f %.4f %.4f %.6f %.6f %d %.4f %.4f %d\n", r[0] / 65536.0, r[1] / 65536.0,
+                r[2] / 65536.0, r[3] / 65536.0, r[4] / 65536.0, r[5] / 65536.0, r[6] / 1073741824.0, r[7] / 1073741824.0,
+                r[8], sqrt(sdd / (r[8] > 0 ? r[8] : 1)) / 256.0, (flags & CANNY_HIP_LINE_FIT_MAXD_MASK) / 256.0,
+                (flags & CANNY_HIP_LINE_FIT_DEGENERATE) ? 1 : 0);
     }
     if (f != stdout) fclose(f);
     return 0;
@@ -560,6 +590,7 @@ int main(int argc, char *argv[])
     bool want_circles = false;
     bool want_polygons = false;
     bool want_edgels = false;
+    int fit_options = -1; // -f: the line fits of the segments; -1 = not asked for
     unsigned polygon_epsilon_q8 = 0, polygon_ratio_q16 = 0;
     int circle_args[6] = {0, 0, 0, 0, 0, 0}; // min_radius, max_radius, threshold, support, min_dist, cell_shift
     int width = WIDTH, height = HEIGHT;
@@ -592,6 +623,15 @@ int main(int argc, char *argv[])
                 exit(2);
             }
             want_segments = true;
+        } else if (arg == "-f" && i + 1 < argc) {
+            char *end = nullptr;
+            const char *p = argv[++i];
+            const long v = strtol(p, &end, 10);
+            if (end == p || *end != '\0' || isspace((unsigned char)*p) || v < 0 || v > 3) {
+                fprintf(stderr, "ERROR: -f expects options: 0, 1 (gate), 2 (refined only) or 3\n");
+                exit(2);
+            }
+            fit_options = (int)v;
         } else if (arg == "-m" && i + 1 < argc) {
             if (sscanf(argv[++i], "%d", &min_area) != 1) {
                 fprintf(stderr, "ERROR: -m expects min_area\n");
@@ -658,6 +698,10 @@ int main(int argc, char *argv[])
         fprintf(stderr, "ERROR: -g needs the lines of -l rho,theta_degrees,threshold[,lines_max]\n");
         exit(2);
     }
+    if (fit_options >= 0 && !(want_lines && want_segments)) {
+        fprintf(stderr, "ERROR: -f needs the segments of -l rho,theta_degrees,threshold[,lines_max] and -g min_length,max_gap[,exclusive]\n");
+        exit(2);
+    }
     if (want_polygons && !want_contours) {
         fprintf(stderr, "ERROR: -y needs the contours of -t\n");
         exit(2);
@@ -675,6 +719,9 @@ int main(int argc, char *argv[])
         fprintf(stderr, "   -b dir: run every .pgm / .jpg of dir as one batch, write <name>_edges.pgm\n");
         fprintf(stderr, "   -l rho,theta_degrees,threshold[,lines_max]: Hough lines of the edge map -> canny_lines.txt in the -o dir\n");
         fprintf(stderr, "   -g min_length,max_gap[,exclusive]: with -l, the segments along the lines -> canny_segments.txt in the -o dir\n");
+        fprintf(stderr, "   -f options: with -l and -g, the sub-pixel line fit of every segment (options 0..3: 1 = gate by gradient\n");
+        fprintf(stderr, "       direction, 2 = refined edgels only), one \"x0 y0 x1 y1 cx cy dx dy n rms maxd degenerate\" line each (pixels)\n");
+        fprintf(stderr, "       -> canny_line_fits.txt in the -o dir\n");
         fprintf(stderr, "   -m min_area: connected components of the edge map with at least min_area pixels -> canny_components.txt,\n");
         fprintf(stderr, "                canny_kept.pgm in the -o dir\n");
         fprintf(stderr, "   -t: outer contour chain of every component with at least min_area (-m, default 1) pixels, one\n");
@@ -767,7 +814,7 @@ int main(int argc, char *argv[])
     }
     if (want_lines && want_segments)
         return run_segments(frame, height, width, sigma, minVal, maxVal, line_rho, line_theta_deg, line_threshold, lines_max,
-                            seg_min_length, seg_max_gap, seg_exclusive, outdir);
+                            seg_min_length, seg_max_gap, seg_exclusive, fit_options, outdir);
     if (want_lines)
         return run_hough(frame, height, width, sigma, minVal, maxVal, line_rho, line_theta_deg, line_threshold, lines_max,
                          outdir);

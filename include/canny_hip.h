@@ -52,7 +52,8 @@
 extern "C" {
 #endif
 
-#define CANNY_HIP_VERSION 1300       /* 0.13.0: + sub-pixel edgels: position, gradient and strength per edge pixel */
+#define CANNY_HIP_VERSION 1400       /* 0.14.0: + sub-pixel line fits: least-squares refit of Hough segments from edgels */
+/* 0.13.0: + sub-pixel edgels: position, gradient and strength per edge pixel */
 /* 0.12.2: + canny_hip_selftest_launch_plan */
 /* 0.12.1: + canny_hip_selftest_workspace */
 /* 0.12.0: + polygon approximation of the contour chains, on the GPU */
@@ -499,7 +500,7 @@ int canny_hip_points_from_bits(const unsigned char *bits, int height, int width,
  * bit 30 together with the polygon parts.
  * Not (yet) covered -- follow-ups: true-direction (Devernay) interpolation between neighbours in place of the quantised
  * step; colour, per-frame-threshold and automatic-threshold forms; the three-stream batch pipeline and the sharder;
- * sub-pixel end points for Hough segments and least-squares refits of lines and circles from edgels; dropping the s16
+ * least-squares refits of circles from edgels (lines and segment end points: the line fits below); dropping the s16
  * map's store when only edgels are wanted. */
 #define CANNY_HIP_EDGEL_INTS 4
 #define CANNY_HIP_EDGEL_MAG_MASK 0x00ffffffu
@@ -659,8 +660,8 @@ int canny_hip_canny_hough(canny_hip_ctx *ctx, const unsigned char *imgs, int n_f
  * The parts are timed by canny_hip_hough_segments_profile_get (CANNY_HIP_SEGMENT_PART_*); with "profile_stage_mask" they
  *   are bits 19 .. 21.
  * Not covered -- follow-ups: randomised sampling as in HoughLinesP proper, decrementing the accumulator when pixels are
- * claimed, sub-pixel end points, merging collinear segments of neighbouring cells, the three-stream batch pipeline, the
- * multi-GPU sharder. */
+ * claimed, merging collinear segments of neighbouring cells, the three-stream batch pipeline, the multi-GPU sharder.
+ * (Sub-pixel end points: the line fits, the section after next.) */
 #define CANNY_HIP_SEGMENT_INTS 6
 enum canny_hip_segment_part {
     CANNY_HIP_SEGMENT_PART_COUNT = 0,      /* exclusive = 0: every line walked, its segments counted; scan over the lines */
@@ -697,6 +698,130 @@ int canny_hip_canny_hough_segments(canny_hip_ctx *ctx, const unsigned char *imgs
                                    int lines_max, float min_theta, float max_theta, int min_length, int max_gap,
                                    int exclusive, float *lines, int *votes, unsigned int *bases, int *line_counts,
                                    int *segments, int segments_max, int *seg_counts);
+
+/* ---- sub-pixel line fits --------------------------------------------------------------------------------------------------
+ * For every segment record of the section above one LINE FIT record: the total-least-squares line through the sub-pixel
+ * edgels of the segment's pixels, the sub-pixel end points on that line, and the residuals -- on the GPU behind the segments
+ * call, on the same stream, with no host round trip and no atomics.  A Hough cell is only as fine as rho x theta; the fit
+ * is typically 4 to 40 times closer to the edge (DESIGN.md section 24 has the table).  The rule is all integers, so the
+ * records are the same bytes on every run and every machine; tests/line_fits_rule.py restates it in Python ints,
+ * csrc/canny_line_fits_host.cpp in plain C++.  THE RULE:
+ * Inputs for one frame: the edge map E; a plane P, unsigned char or short (the smoothed plane of the detector call, or a
+ *   caller's plane), height and width >= 2; the Hough geometry and tables exactly as in the two sections above; the line
+ *   list bases[0 .. K); the segment records of the section above, taken in their slots; options: bit 0 =
+ *   CANNY_HIP_LINE_FIT_GATE, bit 1 = CANNY_HIP_LINE_FIT_REFINED_ONLY, any other bit -> CANNY_HIP_ERR_INVALID.
+ * For segment j with record (x0, y0, x1, y1, k, support):
+ *   1. Line.  (n, r) from bases[k] as in step 1 of the segments, the major axis as in their step 3; ta, tb = the major
+ *      coordinates of (x0, y0) and (x1, y1).  The record is INVALID -- word 9 = CANNY_HIP_LINE_FIT_INVALID, the other
+ *      eleven words zero -- if k lies outside [0, K), the base is not an accumulator cell, an end point lies outside the
+ *      frame, or ta > tb.  That can happen only in the forms that take caller-made records; an invalid record causes no
+ *      memory access beyond the record and the base.
+ *   2. Pixels.  The set pixels of E with vote(x, y) == r (step 2 of the segments, to the bit) and major coordinate in
+ *      [ta, tb].  E itself, NOT the working map W of exclusive mode: the fit takes what lies on the line inside the
+ *      segment's extent, even where an earlier line claimed it.  So with exclusive = 1, n may exceed the record's support;
+ *      with exclusive = 0 and options = 0, n == support.
+ *   3. Edgels.  Each pixel yields its record of the edgel section from P, unchanged: (x_q8, y_q8), (gx, gy), refined.
+ *      With GATE a pixel is used only if (gx, gy) != (0, 0) and
+ *        4 * (gx * ddx + gy * ddy)^2 <= (gx^2 + gy^2) * (ddx^2 + ddy^2),  (ddx, ddy) = (x1 - x0, y1 - y0)
+ *      -- gradients within 30 degrees of the segment's normal; |gx * ddx + gy * ddy| < 2^30, so the left side is below
+ *      2^62 and the right below 2^31 * 2^29.  With REFINED_ONLY a pixel is used only if refined.  n = the used pixels.
+ *   4. Moments, relative to the first end point: u = x_q8 - 256 * x0, v = y_q8 - 256 * y0.  Su, Sv, Suu, Suv, Svv exactly.
+ *      A = n * Suu - Su^2, B = n * Suv - Su * Sv, C = n * Svv - Sv^2, exact (128 bits).  A, C >= 0.
+ *      s = max(0, bitlength(max(A, C, |B|)) - 28); A, B, C >>= s, an arithmetic shift (floor).
+ *   5. Direction.  D = A - C, E = 2 * B, h = isqrt(D^2 + E^2), the exact floor; |D| < 2^28, |E| <= 2^29, the argument
+ *      below 2^59.  The fit is DEGENERATE if n < 2 or h == 0.  Otherwise w = (h + D, E) if D >= 0, else
+ *      w = (|E|, (h - D) * sgn(E)) with sgn(0) = +1 -- the eigenvector of the larger eigenvalue in the form that does not
+ *      cancel.  w is negated iff wx * ddx + wy * ddy < 0: the direction follows the record's order.
+ *      Then w <<= k with k = 31 - bitlength(max(|wx|, |wy|)): the larger component gets exactly 31 bits (max(|wx|, |wy|)
+ *      <= 2^28 * (1 + sqrt 5) < 2^30, so k >= 1, and it is not 0 because h > 0).  Without this step a short segment with
+ *      small moments (len = 6, say) would get a "unit" direction that is off by a tenth.
+ *      len = isqrt(wx^2 + wy^2) (2^30 <= len, argument below 2^63), dx_q30 = rdiv(wx * 2^30, len), dy_q30 likewise;
+ *      rdiv(a, b) rounds to nearest, halves away from zero: sgn(a) * ((2 * |a| + b) / (2 * b)), floor division.  So
+ *      dx_q30^2 + dy_q30^2 lies within 2^-28 of 2^60: the floor in len costs at most 2 / len <= 2^-29, the two roundings
+ *      less than 2^-29 more.
+ *   6. Centroid in 1/65536 px: mu = rdiv(256 * Su, n), mv = rdiv(256 * Sv, n); cx_q16 = 65536 * x0 + mu, cy_q16 likewise.
+ *   7. Residuals and extent, a second pass over the same used pixels; all shifts arithmetic.  U = 256 * u - mu,
+ *      V = 256 * v - mv; d_q8 = (V * dx_q30 - U * dy_q30 + 2^37) >> 38; p_q16 = (U * dx_q30 + V * dy_q30 + 2^29) >> 30.
+ *      Sdd = the sum of d_q8^2 (unsigned 64 bits), maxd = max |d_q8|, pmin and pmax over p_q16.
+ *      End point 0 = (cx_q16 + ((pmin * dx_q30 + 2^29) >> 30), cy_q16 + ((pmin * dy_q30 + 2^29) >> 30)); end point 1 the
+ *      same with pmax.  pmin <= 0 <= pmax up to the rounding of the centroid.
+ *   8. Record: CANNY_HIP_LINE_FIT_INTS = 12 32-bit words, 48 bytes:
+ *        words 0-3: x0_q16, y0_q16, x1_q16, y1_q16 (the fitted end points, 1/65536 px)
+ *        words 4-5: cx_q16, cy_q16                  words 6-7: dx_q30, dy_q30 (unit direction, 2^-30)
+ *        word 8: n       word 9: maxd in bits 0-23, CANNY_HIP_LINE_FIT_DEGENERATE (bit 28), CANNY_HIP_LINE_FIT_INVALID (bit 31)
+ *        words 10-11: Sdd, low word first.  The caller's RMS distance is sqrt(Sdd / n) / 256 px.
+ *      A DEGENERATE record carries words 0-3 = 65536 * the record's own end points, words 4-5 = the centroid if n >= 1,
+ *      else the first end point, words 6, 7, 10, 11 = 0, word 8 = n, maxd = 0.
+ *   9. Order and capacity: the fit of segment slot f * segments_max + j goes to fit slot f * segments_max + j, for j <
+ *      min(segments_max, seg_counts[f]); later slots are not touched.
+ * Limits: max(height, width) <= CANNY_HIP_LINE_FIT_MAX_AXIS = 16384 and rho <= CANNY_HIP_LINE_FIT_MAX_RHO = 8, else
+ *   CANNY_HIP_ERR_UNSUPPORTED with nothing written.  They keep every sum inside 64 bits:
+ *     |u|, |v| <= 256 * 16383 + 128 < 2^22.01      (a pixel of the frame against an end point of the frame, |t_q8| <= 128)
+ *     n <= 16384 * (sqrt(2) * 8 + 1) < 2^18        (the votes of one t with vote == r span less than sqrt(2) * rho + 1
+ *                                                   minor coordinates: the vote moves by at least 1 / (rho * sqrt 2) per pixel)
+ *     Suu, Svv, |Suv| <= n * u^2 < 2^18 * 2^44.02 < 2^63;   |Su|, |Sv| < 2^40.01;   A, C, |B| < 2^18 * 2^62.02 < 2^81
+ *     |U|, |V| < 2^30.02 (a point against the centroid of points of the same frame), so |V * dx - U * dy| and
+ *     |U * dx + V * dy| are at most 2^30 * sqrt(U^2 + V^2) < 2^60.6 (Cauchy-Schwarz; the direction has length 2^30);
+ *     |d_q8| <= 256 * the frame's diagonal + 1 < 2^22.51, which fits the 24 bits of maxd, and with n <= 201716 < 2^17.63
+ *     Sdd < 2^17.63 * 2^45.02 < 2^63.
+ *   Frames under 2 x 2: CANNY_HIP_ERR_INVALID, as for the edgels.
+ * The part is timed by canny_hip_line_fits_profile_get (CANNY_HIP_LINE_FIT_PART_FIT); with "profile_stage_mask" it goes by
+ * bit 30 together with the polygon and edgel parts.
+ * Not (yet) covered -- follow-ups: magnitude-weighted fits, circle refits for the Hough circles, merging collinear
+ * segments, colour / automatic-threshold / batch-pipeline / sharder forms, keeping the used (u, v) pairs in LDS for the
+ * second pass. */
+#define CANNY_HIP_LINE_FIT_INTS 12
+#define CANNY_HIP_LINE_FIT_GATE 1
+#define CANNY_HIP_LINE_FIT_REFINED_ONLY 2
+#define CANNY_HIP_LINE_FIT_MAXD_MASK 0x00ffffffu
+#define CANNY_HIP_LINE_FIT_DEGENERATE 0x10000000u
+#define CANNY_HIP_LINE_FIT_INVALID 0x80000000u
+#define CANNY_HIP_LINE_FIT_MAX_AXIS 16384
+#define CANNY_HIP_LINE_FIT_MAX_RHO 8.0f
+enum canny_hip_line_fit_part {
+    CANNY_HIP_LINE_FIT_PART_FIT = 0, /* the one kernel: both walks and the finishing arithmetic */
+    CANNY_HIP_LINE_FIT_PARTS = 1
+};
+/* Host-only, needs no device: the rule in plain C++ on ONE host frame.  bits: the edge map in the layout of
+ * canny_hip_dev_canny_bits; plane: height x width bytes if plane_is_u8 else shorts; numangle, numrho, tab_cos, tab_sin: what
+ * canny_hip_hough_geometry and canny_hip_hough_tables return for the Hough arguments; bases[0 .. n_lines); segments:
+ * n_segments records of 6 ints; fits receives n_segments records of 12 ints.  The support is found on the full plane. */
+int canny_hip_line_fits_from_plane(const unsigned char *bits, const void *plane, int plane_is_u8, int height, int width,
+                                   float rho, int numangle, int numrho, const float *tab_cos, const float *tab_sin,
+                                   const unsigned int *bases, int n_lines, const int *segments, int n_segments,
+                                   int options, int *fits);
+/* Device bit maps (layout of canny_hip_dev_canny_bits), a device plane (bytes if plane_is_u8 else shorts, n_frames contiguous
+ * planes) and the bases, line counts, segments and segment counts that the earlier calls left on the device.  d_plane ==
+ * NULL means the smoothed plane the last canny_hip_dev_canny-family call on this context left, under the rule of
+ * canny_hip_dev_edgels_at: CANNY_HIP_ERR_INVALID, nothing queued, if no such call ran or its shape differs.  d_fits:
+ * n_frames * segments_max * 12 ints, 16-byte aligned.  Asynchronous. */
+int canny_hip_dev_line_fits_bits(canny_hip_ctx *ctx, const unsigned char *d_bits, const void *d_plane, int plane_is_u8,
+                                 int n_frames, int height, int width, float rho, float theta, float min_theta,
+                                 float max_theta, const unsigned int *d_bases, const int *d_line_counts, int lines_max,
+                                 const int *d_segments, const int *d_seg_counts, int segments_max, int options,
+                                 int *d_fits);
+/* canny_hip_dev_canny_hough_segments unchanged, then the fits queued behind it on the same stream, read from the converged
+ * strong bit-plane and the smoothed plane that call left on the context.  d_fits is mandatory; everything else as there.
+ * max_val > 255: all segment counts are 0 and no fit is written. */
+int canny_hip_dev_canny_hough_line_fits(canny_hip_ctx *ctx, const unsigned char *d_img, float sigma, int min_val,
+                                        int max_val, int height, int width, int n_frames, short *d_edges, float rho,
+                                        float theta, int threshold, int lines_max, float min_theta, float max_theta,
+                                        float *d_lines, int *d_votes, unsigned int *d_bases, int *d_line_counts,
+                                        int *d_accum, int min_length, int max_gap, int exclusive, int *d_segments,
+                                        int segments_max, int *d_seg_counts, int options, int *d_fits);
+/* Host buffers, synchronous, in the pattern of canny_hip_canny_hough_segments: the counts come down first, then only the
+ * filled slots.  lines, votes, bases, line_counts, segments may be NULL; fits and seg_counts are mandatory. */
+int canny_hip_canny_hough_line_fits(canny_hip_ctx *ctx, const unsigned char *imgs, int n_frames, float sigma, int min_val,
+                                    int max_val, int height, int width, float rho, float theta, int threshold,
+                                    int lines_max, float min_theta, float max_theta, int min_length, int max_gap,
+                                    int exclusive, int options, float *lines, int *votes, unsigned int *bases,
+                                    int *line_counts, int *segments, int segments_max, int *seg_counts, int *fits);
+/* Test hook: the device finishing function (steps 4 to 6) on n_sets moment sets of 8 long longs (n, Su, Sv, Suu, Suv, Svv,
+ * ddx, ddy), n <= 2^18 and the sums within the limits above; d_out receives 6 ints per set: words 4 to 8 of the record
+ * for (x0, y0) = (0, 0), i.e. mu, mv, dx_q30, dy_q30, n, then CANNY_HIP_LINE_FIT_DEGENERATE or 0.  Asynchronous. */
+int canny_hip_dev_line_fits_arith(canny_hip_ctx *ctx, const long long *d_moments, size_t n_sets, int *d_out);
+/* Host-only, the same hook on the plain C++ restatement (host arrays). */
+int canny_hip_line_fits_finish(const long long *moments, size_t n_sets, int *out);
 
 /* ---- Hough circles -------------------------------------------------------------------------------------------------------
  * Circle detection on a finished edge map, per frame of a batch, on the GPU, in stream order, with no host round trip:
@@ -1131,6 +1256,8 @@ int canny_hip_hough_circles_profile_get(canny_hip_ctx *ctx, int part, double *to
 int canny_hip_polygons_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches);
 /* ... and for the two parts of the sub-pixel edgels (CANNY_HIP_EDGEL_PART_*). */
 int canny_hip_edgels_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches);
+/* ... and for the one part of the line fits (CANNY_HIP_LINE_FIT_PART_*). */
+int canny_hip_line_fits_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches);
 
 /* ---- self-test hooks used by the GPU test-suite -------------------------------------------- */
 /* Runs the DEVICE magnitude / angle-bin functions over every (gx,gy) in [-lim,lim]^2 and writes
