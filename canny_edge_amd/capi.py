@@ -121,6 +121,9 @@ EXPORTS = (
     "canny_hip_line_fits_from_plane", "canny_hip_dev_line_fits_bits", "canny_hip_dev_canny_hough_line_fits",
     "canny_hip_canny_hough_line_fits", "canny_hip_dev_line_fits_arith", "canny_hip_line_fits_profile_get",
     "canny_hip_line_fits_finish",
+    "canny_hip_circle_fits_from_plane", "canny_hip_dev_circle_fits_bits", "canny_hip_dev_canny_hough_circle_fits",
+    "canny_hip_canny_hough_circle_fits", "canny_hip_dev_circle_fits_arith", "canny_hip_circle_fits_finish",
+    "canny_hip_circle_fits_profile_get", "canny_hip_circle_fits_queue_capacity",
 )
 
 _lib: Optional[C.CDLL] = None
@@ -296,6 +299,15 @@ def load() -> C.CDLL:
         "canny_hip_dev_line_fits_arith": ([p, p, sz, p], i),
         "canny_hip_line_fits_finish": ([p, sz, p], i),
         "canny_hip_line_fits_profile_get": ([p, i, C.POINTER(C.c_double), C.POINTER(C.c_long)], i),
+        "canny_hip_circle_fits_from_plane": ([p, p, i, i, i, p, i, i, i, i, p], i),
+        "canny_hip_dev_circle_fits_bits": ([p, p, p, i, i, i, i, p, p, i, i, i, i, p], i),
+        "canny_hip_dev_canny_hough_circle_fits": ([p, p, f, i, i, i, i, i, p, i, i, i, i, i, i, i, p, p, p, p, i, i, i, p],
+                                                   i),
+        "canny_hip_canny_hough_circle_fits": ([p, p, i, f, i, i, i, i, i, i, i, i, i, i, i, i, i, i, p, p, p, p], i),
+        "canny_hip_dev_circle_fits_arith": ([p, p, sz, p], i),
+        "canny_hip_circle_fits_finish": ([p, sz, p], i),
+        "canny_hip_circle_fits_profile_get": ([p, i, C.POINTER(C.c_double), C.POINTER(C.c_long)], i),
+        "canny_hip_circle_fits_queue_capacity": ([], i),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -708,6 +720,69 @@ def line_fits_unpack(fits) -> dict:
             "direction": r[:, 6:8] / float(1 << 30), "n": n, "rms": np.sqrt(sdd / np.maximum(n, 1)) / 256.0,
             "maxd": (w9 & LINE_FIT_MAXD_MASK) / 256.0, "degenerate": (w9 & LINE_FIT_DEGENERATE) != 0,
             "invalid": (w9 & LINE_FIT_INVALID) != 0}
+
+
+CIRCLE_FIT_INTS = 8
+CIRCLE_FIT_GATE, CIRCLE_FIT_REFINED_ONLY = 1, 2
+CIRCLE_FIT_MAXD_MASK, CIRCLE_FIT_TRIM_FAILED = 0x00FFFFFF, 0x08000000
+CIRCLE_FIT_DEGENERATE, CIRCLE_FIT_INVALID = 0x10000000, 0x80000000
+CIRCLE_FIT_MAX_BAND, CIRCLE_FIT_MOMENT_WORDS = 4, 12
+CIRCLE_FIT_PART_FIT = 0
+
+
+def circle_fits_from_plane(bits, plane, circles, band: int = 1, trim_q8: int = 0, options: int = 0) -> np.ndarray:
+    """Host-only: the circle-fit rule of include/canny_hip.h on one host frame: a packed bit map (numpy.packbits(mask,
+    axis=-1)), its plane (uint8 or int16 [H, W]) and circle records (k, 6) as hough_circles_from_bits returns them ->
+    (k, 8) int32 fit records; unpack them with circle_fits_unpack."""
+    a = np.ascontiguousarray(plane)
+    if a.ndim != 2 or a.dtype not in (np.uint8, np.int16):
+        raise ValueError("expected a 2-D uint8 or int16 plane")
+    h, w = a.shape
+    b = np.ascontiguousarray(bits, dtype=np.uint8)
+    if b.size != h * ((w + 7) // 8):
+        raise ValueError("bits must hold height * ceil(width / 8) bytes")
+    rec = np.ascontiguousarray(circles, dtype=np.int32).reshape(-1, CIRCLE_INTS)
+    fits = np.empty((rec.shape[0], CIRCLE_FIT_INTS), np.int32)
+    st = load().canny_hip_circle_fits_from_plane(_hp(b), _hp(a), int(a.dtype == np.uint8), h, w,
+                                                 _hp(rec) if rec.size else None, rec.shape[0], int(band), int(trim_q8),
+                                                 int(options), _hp(fits) if rec.size else None)
+    if st:
+        raise CannyHipError(st, "circle_fits_from_plane")
+    return fits
+
+
+def circle_fits_finish(moments) -> np.ndarray:
+    """Host-only test hook: the finishing arithmetic of the rule in plain C++ on (k, 12) int64 moment sets (n, Su, Sv, Sz,
+    Suu, Suv, Svv, Suz low, Suz high, Svz low, Svz high, band) -> (k, 4) int32 (move_x, move_y, n, DEGENERATE or 0)."""
+    m = np.ascontiguousarray(moments, dtype=np.int64).reshape(-1, CIRCLE_FIT_MOMENT_WORDS)
+    out = np.empty((m.shape[0], 4), np.int32)
+    st = load().canny_hip_circle_fits_finish(_hp(m), m.shape[0], _hp(out))
+    if st:
+        raise CannyHipError(st, "circle_fits_finish")
+    return out
+
+
+def circle_fits_queue_capacity() -> int:
+    """Host-only: the band pixels of one record that the fit kernel keeps in LDS (more are recomputed, same bytes)."""
+    return int(load().canny_hip_circle_fits_queue_capacity())
+
+
+def circle_fits_unpack(fits) -> dict:
+    """Floats from (k, 8) int32 fit records: centre ([k, 2] pixels, x then y), radius (pixels), n, rms and maxd (pixels),
+    sectors (the 16-bit mask), sector_count, trim_failed, degenerate, invalid."""
+    r = np.ascontiguousarray(np.asarray(fits, np.int32).reshape(-1, CIRCLE_FIT_INTS))
+    w4 = np.ascontiguousarray(r[:, 4]).view(np.uint32)
+    sec = np.ascontiguousarray(r[:, 5]).view(np.uint32) & 0xFFFF
+    n = r[:, 3].astype(np.int64)
+    sdd = (np.ascontiguousarray(r[:, 6]).view(np.uint32).astype(np.float64) +
+           np.ascontiguousarray(r[:, 7]).view(np.uint32).astype(np.float64) * 4294967296.0)
+    count = np.zeros(len(sec), np.int64)
+    for k in range(16):
+        count += (sec >> k) & 1
+    return {"centre": r[:, 0:2] / 65536.0, "radius": r[:, 2] / 65536.0, "n": n,
+            "rms": np.sqrt(sdd / np.maximum(n, 1)) / 256.0, "maxd": (w4 & CIRCLE_FIT_MAXD_MASK) / 256.0,
+            "sectors": sec, "sector_count": count, "trim_failed": (w4 & CIRCLE_FIT_TRIM_FAILED) != 0,
+            "degenerate": (w4 & CIRCLE_FIT_DEGENERATE) != 0, "invalid": (w4 & CIRCLE_FIT_INVALID) != 0}
 
 
 def points_to_rc(points, width: int) -> Tuple[np.ndarray, np.ndarray]:
@@ -1641,6 +1716,72 @@ class Context:
         ms, n = C.c_double(0), C.c_long(0)
         self._check(self._L.canny_hip_hough_circles_profile_get(self._h, part, C.byref(ms), C.byref(n)),
                     "hough_circles_profile_get")
+        return ms.value, n.value
+
+    # ---- sub-pixel circle fits (least-squares refit of the Hough circles from edgels) ------
+    def canny_hough_circle_fits(self, imgs, sigma: float, min_val: int, max_val: int, min_radius: int, max_radius: int,
+                                cell_shift: int = 0, threshold: int = 20, support_threshold: int = 10, min_dist: int = 0,
+                                centres_max: int = 256, band: int = 1, trim_q8: int = 0,
+                                options: int = CIRCLE_FIT_REFINED_ONLY):
+        """canny_hough_circles plus one circle-fit record per circle, all on the GPU: imgs (H, W) or (N, H, W) uint8 ->
+        (records, counts, centre_counts, fits); records[f] int32 [k, 6] and fits[f] int32 [k, 8], slot for slot; unpack
+        the fits with circle_fits_unpack."""
+        a = np.ascontiguousarray(imgs, dtype=np.uint8)
+        if a.ndim == 2:
+            a = a[None]
+        if a.ndim != 3:
+            raise ValueError("expected uint8 [H, W] or [n_frames, H, W]")
+        n, h, w = a.shape
+        rec = np.zeros((n, max(int(centres_max), 1), CIRCLE_INTS), np.int32)
+        fits = np.zeros((n, max(int(centres_max), 1), CIRCLE_FIT_INTS), np.int32)
+        counts, peaks = np.zeros(n, np.int32), np.zeros(n, np.int32)
+        self._check(self._L.canny_hip_canny_hough_circle_fits(self._h, _hp(a), n, sigma, min_val, max_val, h, w, min_radius,
+                                                              max_radius, cell_shift, threshold, support_threshold,
+                                                              min_dist, centres_max, band, trim_q8, options, _hp(rec),
+                                                              _hp(counts), _hp(peaks), _hp(fits)),
+                    "canny_hough_circle_fits")
+        return ([rec[f, :int(counts[f])].copy() for f in range(n)], counts, peaks,
+                [fits[f, :int(counts[f])].copy() for f in range(n)])
+
+    def dev_circle_fits_bits(self, d_bits: int, d_plane: int, plane_is_u8: bool, n: int, h: int, w: int, d_circles: int,
+                             d_counts: int, centres_max: int, band: int, trim_q8: int, options: int, d_fits: int):
+        """The fits of circle records on the device (d_circles, d_counts; an earlier call's or the caller's) on device bit
+        maps (layout of dev_canny_bits) and a device plane (u8 or s16; 0 = the smoothed plane the last canny call of the
+        same shape left).  d_fits: n * centres_max * 8 int32, 16-byte aligned."""
+        v = C.c_void_p
+        self._check(self._L.canny_hip_dev_circle_fits_bits(self._h, v(d_bits or None), v(d_plane or None), int(plane_is_u8),
+                                                           n, h, w, v(d_circles or None), v(d_counts or None), centres_max,
+                                                           band, trim_q8, options, v(d_fits or None)),
+                    "dev_circle_fits_bits")
+
+    def dev_canny_hough_circle_fits(self, d_img: int, sigma: float, min_val: int, max_val: int, h: int, w: int, n: int,
+                                    min_radius: int, max_radius: int, cell_shift: int, threshold: int,
+                                    support_threshold: int, min_dist: int, centres_max: int, band: int, trim_q8: int,
+                                    options: int, d_fits: int, d_circles: int = 0, d_counts: int = 0,
+                                    d_centre_counts: int = 0, d_accum: int = 0, d_edges: int = 0):
+        """dev_canny_hough_circles, then the fits of its circles queued behind it on the same stream; d_circles and
+        d_counts are optional (0: a context workspace holds them)."""
+        v = C.c_void_p
+        self._check(self._L.canny_hip_dev_canny_hough_circle_fits(self._h, v(d_img or None), sigma, min_val, max_val, h, w,
+                                                                  n, v(d_edges or None), min_radius, max_radius,
+                                                                  cell_shift, threshold, support_threshold, min_dist,
+                                                                  centres_max, v(d_circles or None), v(d_counts or None),
+                                                                  v(d_centre_counts or None), v(d_accum or None), band,
+                                                                  trim_q8, options, v(d_fits or None)),
+                    "dev_canny_hough_circle_fits")
+
+    def dev_circle_fits_arith(self, d_moments: int, n_sets: int, d_out: int):
+        """Test hook: the device finishing arithmetic on n_sets x 12 int64 moment sets -> n_sets x 4 int32 (move_x, move_y,
+        n, DEGENERATE or 0)."""
+        v = C.c_void_p
+        self._check(self._L.canny_hip_dev_circle_fits_arith(self._h, v(d_moments or None), n_sets, v(d_out or None)),
+                    "dev_circle_fits_arith")
+
+    def circle_fits_profile_get(self, part: int = 0) -> Tuple[float, int]:
+        """(total ms, launch groups) of part 0, the fit kernel (CIRCLE_FIT_PART_FIT)."""
+        ms, n = C.c_double(0), C.c_long(0)
+        self._check(self._L.canny_hip_circle_fits_profile_get(self._h, part, C.byref(ms), C.byref(n)),
+                    "circle_fits_profile_get")
         return ms.value, n.value
 
     # ---- colour frames (interleaved BGR / RGB / BGRA / RGBA; the rule is the "gray_rule" option) --------------

@@ -403,6 +403,8 @@ struct canny_hip_ctx {
     // Hough circles: the accumulators when the caller passes none; candidate keys, votes, bases, radii, supports, peak
     // counts, histograms, tie counts, cut words
     DevBuf circ_accum, circ_ws;
+    // circle fits: the circle records and counts when the caller passes none
+    DevBuf circ_recs;
     DevBuf plane_s, plane_c, stamps, flags; // hysteresis bit-planes / scheduling words
     DevBuf io[4];     // staging for the host-pointer stage functions
     std::string ws_name; // canny_hip_selftest_workspace: the name it handed out last
@@ -431,9 +433,10 @@ struct canny_hip_ctx {
     // then the three of the Hough segments (canny_hip_hough_segments_profile_get), then the four of the contour chains
     // (canny_hip_contours_profile_get), then the four of the Hough circles (canny_hip_hough_circles_profile_get), then the
     // three of the polygon approximation (canny_hip_polygons_profile_get), then the two of the sub-pixel edgels
-    // (canny_hip_edgels_profile_get), then the one of the line fits (canny_hip_line_fits_profile_get).  The mask is a
-    // non-negative int option: bit 30 is the last it can carry, and the three polygon slots, the two edgel slots and the
-    // line-fit slot behind them go by it together
+    // (canny_hip_edgels_profile_get), then the one of the line fits (canny_hip_line_fits_profile_get), then the one of the
+    // circle fits (canny_hip_circle_fits_profile_get).  The mask is a non-negative int option: bit 30 is the last it can
+    // carry, and the three polygon slots, the two edgel slots, the line-fit slot and the circle-fit slot behind them go by
+    // it together
     static constexpr int kProfHough = CANNY_HIP_STAGE_END, kProfComponents = CANNY_HIP_STAGE_END + 3;
     static constexpr int kProfEdt = kProfComponents + CANNY_HIP_CC_PARTS;
     static constexpr int kProfSegments = kProfEdt + CANNY_HIP_EDT_PARTS;
@@ -442,7 +445,8 @@ struct canny_hip_ctx {
     static constexpr int kProfPolygons = kProfCircles + CANNY_HIP_CIRCLE_PARTS;
     static constexpr int kProfEdgels = kProfPolygons + CANNY_HIP_POLYGON_PARTS;
     static constexpr int kProfLineFits = kProfEdgels + CANNY_HIP_EDGEL_PARTS;
-    static constexpr int kProfSlots = kProfLineFits + CANNY_HIP_LINE_FIT_PARTS;
+    static constexpr int kProfCircleFits = kProfLineFits + CANNY_HIP_LINE_FIT_PARTS;
+    static constexpr int kProfSlots = kProfCircleFits + CANNY_HIP_CIRCLE_FIT_PARTS;
     static constexpr int kProfLastBit = 30;
     static_assert(kProfPolygons == kProfLastBit && kProfEdgels > kProfLastBit,
                   "profile_stage_mask has one bit per slot up to the polygon parts; every slot from there on follows bit 30");
@@ -1852,6 +1856,7 @@ void collect_workspaces(const canny_hip_ctx *c, const std::string &prefix, std::
     add("seg_work", c->seg_work, D);
     add("circ_accum", c->circ_accum, D);
     add("circ_ws", c->circ_ws, I);         // bases address accumulator cells, peak counts bound loops
+    add("circ_recs", c->circ_recs, I);     // radii and centres bound the fit's row walk, counts its grid
     add("plane_s", c->plane_s, D);
     add("plane_c", c->plane_c, D);
     add("stamps", c->stamps, I);           // tile queues and their counters
@@ -1960,6 +1965,7 @@ void canny_hip_ctx_destroy(canny_hip_ctx *ctx)
     ctx->seg_work.release();
     ctx->circ_accum.release();
     ctx->circ_ws.release();
+    ctx->circ_recs.release();
     ctx->cc_parent.release();
     ctx->cc_ws.release();
     ctx->ct_ws.release();
@@ -4701,6 +4707,159 @@ int canny_hip_hough_circles_profile_get(canny_hip_ctx *ctx, int part, double *to
     if ((rc = profile_collect(ctx))) return rc;
     *total_ms = ctx->total_ms[canny_hip_ctx::kProfCircles + part];
     *launches = ctx->launches[canny_hip_ctx::kProfCircles + part];
+    return CANNY_HIP_OK;
+}
+
+// ---- sub-pixel circle fits (canny_circle_fits.hip) --------------------------------
+namespace {
+
+// THE check of the fit arguments; needs no device and writes nothing
+int circle_fits_check(int height, int width, int n_frames, int centres_max, int band, int trim_q8, int options,
+                      const int *d_fits)
+{
+    if ((options & ~(CANNY_HIP_CIRCLE_FIT_GATE | CANNY_HIP_CIRCLE_FIT_REFINED_ONLY)) || !d_fits || ((uintptr_t)d_fits & 15) ||
+        centres_max < 1 || band < 0 || trim_q8 < 0 || height < 2 || width < 2)
+        return CANNY_HIP_ERR_INVALID;
+    if (std::max(height, width) > CANNY_HIP_CIRCLE_FIT_MAX_AXIS || band > CANNY_HIP_CIRCLE_FIT_MAX_BAND)
+        return CANNY_HIP_ERR_UNSUPPORTED;
+    if ((double)n_frames * (double)centres_max * CANNY_HIP_CIRCLE_FIT_INTS >= 2147483648.0) return CANNY_HIP_ERR_UNSUPPORTED;
+    return CANNY_HIP_OK;
+}
+
+// the fits of the circle records in d_circles, queued on the context's stream
+int dev_circle_fits(canny_hip_ctx *ctx, const uint64_t *strong, const uint8_t *bits, const HystGeom &g, const int *d_circles,
+                    const int *d_counts, int centres_max, const void *d_plane, bool plane_u8, int band, int trim_q8,
+                    int options, int *d_fits)
+{
+    StageTimer tm(ctx, canny_hip_ctx::kProfCircleFits + CANNY_HIP_CIRCLE_FIT_PART_FIT);
+    HIP_TRY(ctx, launch_circle_fits(strong, bits, g, d_circles, d_counts, centres_max, d_plane, plane_u8, band, trim_q8,
+                                    options, d_fits, ctx->stream));
+    return CANNY_HIP_OK;
+}
+
+} // namespace
+
+int canny_hip_circle_fits_queue_capacity(void) { return circle_fits_queue_capacity(); }
+
+int canny_hip_dev_circle_fits_bits(canny_hip_ctx *ctx, const unsigned char *d_bits, const void *d_plane, int plane_is_u8,
+                                   int n_frames, int height, int width, const int *d_circles, const int *d_counts,
+                                   int centres_max, int band, int trim_q8, int options, int *d_fits)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!d_bits || !d_circles || !d_counts) return CANNY_HIP_ERR_INVALID;
+    if ((rc = check_dims(height, width, n_frames))) return rc;
+    if ((rc = circle_fits_check(height, width, n_frames, centres_max, band, trim_q8, options, d_fits))) return rc;
+    if (!d_plane) {
+        // the plane the last canny call left: only for the batch it belongs to
+        if (!ctx->last_canny_n || !ctx->smoothed.p || ctx->last_canny_n != n_frames || ctx->last_canny_h != height ||
+            ctx->last_canny_w != width)
+            return CANNY_HIP_ERR_INVALID;
+        d_plane = ctx->smoothed.p;
+        plane_is_u8 = ctx->last_canny_u8;
+    }
+    if ((rc = finish_pending(ctx))) return rc;
+    return dev_circle_fits(ctx, nullptr, d_bits, make_hyst_geom(height, width, n_frames), d_circles, d_counts, centres_max,
+                           d_plane, plane_is_u8 != 0, band, trim_q8, options, d_fits);
+}
+
+int canny_hip_dev_canny_hough_circle_fits(canny_hip_ctx *ctx, const unsigned char *d_img, float sigma, int min_val,
+                                          int max_val, int height, int width, int n_frames, short *d_edges, int min_radius,
+                                          int max_radius, int cell_shift, int threshold, int support_threshold,
+                                          int min_dist, int centres_max, int *d_circles, int *d_counts,
+                                          int *d_centre_counts, int *d_accum, int band, int trim_q8, int options,
+                                          int *d_fits)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!d_img) return CANNY_HIP_ERR_INVALID;
+    {
+        const CircleArgs a{min_radius, max_radius, cell_shift, threshold, support_threshold, min_dist, centres_max};
+        CircleGeom cg;
+        int probe = 0;
+        if ((rc = circles_prepare(height, width, a, &probe, cg)) || (rc = check_dims(height, width, n_frames)) ||
+            (rc = circle_fits_check(height, width, n_frames, centres_max, band, trim_q8, options, d_fits)))
+            return rc;
+    }
+    // the fits need the records and the counts: the context's own where the caller wants none
+    const size_t slots = (size_t)n_frames * centres_max;
+    if (!d_circles || !d_counts) {
+        HIP_TRY(ctx, ctx->circ_recs.ensure((slots * kCircleRecord + (size_t)n_frames) * sizeof(int)));
+        int *own = (int *)ctx->circ_recs.p;
+        if (!d_circles) d_circles = own;
+        if (!d_counts) d_counts = own + slots * kCircleRecord;
+    }
+    if ((rc = canny_hip_dev_canny_hough_circles(ctx, d_img, sigma, min_val, max_val, height, width, n_frames, d_edges,
+                                                min_radius, max_radius, cell_shift, threshold, support_threshold, min_dist,
+                                                centres_max, d_circles, d_counts, d_centre_counts, d_accum)))
+        return rc;
+    if (max_val > 255) return CANNY_HIP_OK; // the empty map: every count is 0
+    return dev_circle_fits(ctx, (const uint64_t *)ctx->plane_s.p, nullptr, make_hyst_geom(height, width, n_frames), d_circles,
+                           d_counts, centres_max, ctx->smoothed.p, ctx->last_canny_u8 != 0, band, trim_q8, options, d_fits);
+}
+
+int canny_hip_canny_hough_circle_fits(canny_hip_ctx *ctx, const unsigned char *imgs, int n_frames, float sigma, int min_val,
+                                      int max_val, int height, int width, int min_radius, int max_radius, int cell_shift,
+                                      int threshold, int support_threshold, int min_dist, int centres_max, int band,
+                                      int trim_q8, int options, int *circles, int *counts, int *centre_counts, int *fits)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!imgs || !fits) return CANNY_HIP_ERR_INVALID;
+    {
+        const CircleArgs a{min_radius, max_radius, cell_shift, threshold, support_threshold, min_dist, centres_max};
+        CircleGeom cg;
+        if ((rc = circles_prepare(height, width, a, counts, cg)) || (rc = check_dims(height, width, n_frames)) ||
+            (rc = circle_fits_check(height, width, n_frames, centres_max, band, trim_q8, options, (const int *)16)))
+            return rc;
+    }
+    const size_t slots = (size_t)n_frames * centres_max;
+    // staging: fits (8 ints per slot, 16-byte aligned at the block's start) | records (6 ints per slot) | counts | centre counts
+    HIP_TRY(ctx, ctx->io[1].ensure((slots * (CANNY_HIP_CIRCLE_FIT_INTS + kCircleRecord) + 2 * (size_t)n_frames) * sizeof(int)));
+    int *d_fits = (int *)ctx->io[1].p, *d_rec = d_fits + slots * CANNY_HIP_CIRCLE_FIT_INTS;
+    int *d_cnt = d_rec + slots * kCircleRecord;
+    if ((rc = h2d(ctx, ctx->io[0], imgs, npx(height, width, n_frames)))) return rc;
+    if ((rc = canny_hip_dev_canny_hough_circle_fits(ctx, (const unsigned char *)ctx->io[0].p, sigma, min_val, max_val, height,
+                                                    width, n_frames, nullptr, min_radius, max_radius, cell_shift, threshold,
+                                                    support_threshold, min_dist, centres_max, d_rec, d_cnt, d_cnt + n_frames,
+                                                    nullptr, band, trim_q8, options, d_fits)))
+        return rc;
+    std::vector<int> cnt(2 * (size_t)n_frames);
+    if ((rc = d2h_sync(ctx, cnt.data(), d_cnt, cnt.size() * sizeof(int)))) return rc;
+    // the counts first, then only the filled slots of each frame
+    for (int f = 0; f < n_frames; f++) {
+        const size_t k = (size_t)cnt[f], at = (size_t)f * centres_max;
+        if (k && circles)
+            HIP_TRY(ctx, hipMemcpyAsync(circles + at * kCircleRecord, d_rec + at * kCircleRecord,
+                                        k * kCircleRecord * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+        if (k)
+            HIP_TRY(ctx, hipMemcpyAsync(fits + at * CANNY_HIP_CIRCLE_FIT_INTS, d_fits + at * CANNY_HIP_CIRCLE_FIT_INTS,
+                                        k * CANNY_HIP_CIRCLE_FIT_INTS * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    std::memcpy(counts, cnt.data(), (size_t)n_frames * sizeof(int));
+    if (centre_counts) std::memcpy(centre_counts, cnt.data() + n_frames, (size_t)n_frames * sizeof(int));
+    return CANNY_HIP_OK;
+}
+
+int canny_hip_dev_circle_fits_arith(canny_hip_ctx *ctx, const long long *d_moments, size_t n_sets, int *d_out)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!n_sets || !d_moments || !d_out) return CANNY_HIP_ERR_INVALID;
+    if ((rc = finish_pending(ctx))) return rc;
+    HIP_TRY(ctx, launch_circle_fits_arith(d_moments, n_sets, d_out, ctx->stream));
+    return CANNY_HIP_OK;
+}
+
+int canny_hip_circle_fits_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches)
+{
+    if (part < 0 || part >= CANNY_HIP_CIRCLE_FIT_PARTS || !total_ms || !launches) return CANNY_HIP_ERR_INVALID;
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if ((rc = profile_collect(ctx))) return rc;
+    *total_ms = ctx->total_ms[canny_hip_ctx::kProfCircleFits + part];
+    *launches = ctx->launches[canny_hip_ctx::kProfCircleFits + part];
     return CANNY_HIP_OK;
 }
 

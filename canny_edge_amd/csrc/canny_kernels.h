@@ -592,6 +592,19 @@ hipError_t launch_line_fits(const uint64_t *strong, const uint8_t *bits, const H
 // The finishing arithmetic alone (the test hook): n sets of 8 long longs -> 6 ints each; one lane per set, no cap.
 hipError_t launch_line_fits_arith(const long long *moments, size_t n, int *out, hipStream_t stream);
 
+// ---- Sub-pixel circle fits (canny_circle_fits.hip) -----------------------
+// One 8-int record (CANNY_HIP_CIRCLE_FIT_INTS) per circle slot f * centres_max + j, j < min(centres_max, counts[f]), from
+// the 6-int records launch_circles_accept (or the caller) left in `circles`; source (bits or else the strong plane) as for
+// the line fits.  plane: n_frames contiguous height x width planes, bytes if plane_u8 else shorts.  fits: 16-byte aligned.
+// Grid (centres_max, n_frames), one workgroup per slot: no cap.
+hipError_t launch_circle_fits(const uint64_t *strong, const uint8_t *bits, const HystGeom &g, const int *circles,
+                              const int *counts, int centres_max, const void *plane, bool plane_u8, int band, int trim_q8,
+                              int options, int *fits, hipStream_t stream);
+// The finishing arithmetic alone (the test hook): n sets of 12 long longs -> 4 ints each; one lane per set, no cap.
+hipError_t launch_circle_fits_arith(const long long *moments, size_t n, int *out, hipStream_t stream);
+// Pixels of one record that the kernel's LDS queue holds (the rest is recomputed in every pass).
+int circle_fits_queue_capacity();
+
 // ---- launch plans of the capped grids ---------------------------------
 // A launcher whose grid is capped hands its kernel `units` work items and `grid` workgroups that take `per_group` items
 // per trip of their grid-stride loop.  Each plan_* below is computed from sizes alone, is THE grid computation of the

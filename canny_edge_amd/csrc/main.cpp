@@ -41,6 +41,10 @@
 // Added: -f options (with -l and -g) also computes the sub-pixel line fit of every segment on the GPU
 // (canny_hip_canny_hough_line_fits) and writes one "x0 y0 x1 y1 cx cy dx dy n rms maxd degenerate" row per segment to
 // canny_line_fits.txt.  -f without -l and -g, or with anything but 0..3, is a usage error (exit 2).
+// Added: -k band,trim_q8[,options] (with -r) also computes the sub-pixel circle fit of every circle on the GPU
+// (canny_hip_canny_hough_circle_fits) and writes one "frame cx cy r n rms maxd sectors trim_failed degenerate" row per
+// circle to canny_circle_fits.txt.  -k without -r, or with a band outside 0..4, a negative trim or options outside 0..3, is
+// a usage error (exit 2).
 // Added: -e computes the sub-pixel edgel of every pixel of the frame's edge map on the GPU (canny_hip_canny_edgels) and
 // writes one "x y gx gy mag dir refined" row per edge pixel, in raster order, to canny_edgels.txt in the -o directory
 // (stdout without -o): x and y in pixels to three decimals, mag in grey levels, dir 0..3 (step (1,0), (1,1), (0,1), (1,-1)),
@@ -536,20 +540,30 @@ static int run_edt(const vector<unsigned char> &frame, int height, int width, fl
     return 0;
 }
 
-// -r: the circles of the frame's edge map, "frame x y radius votes support" per circle
+// -r: the circles of the frame's edge map, "frame x y radius votes support" per circle; with -k (fit != nullptr: band,
+// trim_q8, options) also the circle fit of every circle, "frame cx cy r n rms maxd sectors trim_failed degenerate" per circle
 static int run_circles(const vector<unsigned char> &frame, int height, int width, float sigma, int minVal, int maxVal,
-                       const int *r, const string &outdir)
+                       const int *r, const int *fit, const string &outdir)
 {
     const int centres_max = 256;
-    vector<int> rec((size_t)centres_max * CANNY_HIP_CIRCLE_INTS);
+    vector<int> rec((size_t)centres_max * CANNY_HIP_CIRCLE_INTS), fits;
     int count = 0;
     canny_hip_ctx *ctx = nullptr;
     int st = canny_hip_ctx_create(&ctx, 0);
-    if (!st)
-        st = canny_hip_canny_hough_circles(ctx, frame.data(), 1, sigma, minVal, maxVal, height, width, r[0], r[1], r[5], r[2],
-                                           r[3], r[4], centres_max, rec.data(), &count, nullptr);
+    if (!st) {
+        if (fit) {
+            fits.resize((size_t)centres_max * CANNY_HIP_CIRCLE_FIT_INTS);
+            st = canny_hip_canny_hough_circle_fits(ctx, frame.data(), 1, sigma, minVal, maxVal, height, width, r[0], r[1], r[5],
+                                                   r[2], r[3], r[4], centres_max, fit[0], fit[1], fit[2], rec.data(), &count,
+                                                   nullptr, fits.data());
+        } else {
+            st = canny_hip_canny_hough_circles(ctx, frame.data(), 1, sigma, minVal, maxVal, height, width, r[0], r[1], r[5],
+                                               r[2], r[3], r[4], centres_max, rec.data(), &count, nullptr);
+        }
+    }
     if (st) {
-        fprintf(stderr, "ERROR: -r: %s\n", st == CANNY_HIP_ERR_RUNTIME && ctx ? canny_hip_last_error(ctx) : canny_hip_status_string(st));
+        fprintf(stderr, "ERROR: %s: %s\n", fit ? "-k" : "-r",
+                st == CANNY_HIP_ERR_RUNTIME && ctx ? canny_hip_last_error(ctx) : canny_hip_status_string(st));
         if (ctx) canny_hip_ctx_destroy(ctx);
         return 1;
     }
@@ -562,6 +576,22 @@ static int run_circles(const vector<unsigned char> &frame, int height, int width
     for (int j = 0; j < count; j++) {
         const int *c = rec.data() + (size_t)j * CANNY_HIP_CIRCLE_INTS;
         fprintf(f, "0 %.1f %.1f %d %d %d\n", c[0] * 0.5, c[1] * 0.5, c[2], c[3], c[4]);
+    }
+    if (f != stdout) fclose(f);
+    if (!fit) return 0;
+    f = outdir.empty() ? stdout : fopen((outdir + "/canny_circle_fits.txt").c_str(), "w");
+    if (!f) {
+        fprintf(stderr, "ERROR: cannot write %s/canny_circle_fits.txt\n", outdir.c_str());
+        return 1;
+    }
+    for (int j = 0; j < count; j++) {
+        const int *c = fits.data() + (size_t)j * CANNY_HIP_CIRCLE_FIT_INTS;
+        const unsigned flags = (unsigned)c[4];
+        const double sdd = (double)(unsigned)c[6] + 4294967296.0 * (double)(unsigned)c[7];
+        fprintf(f, "0 %.4f %.4f %.4f %d %.4f %.4f %04x %d %d\n", c[0] / 65536.0, c[1] / 65536.0, c[2] / 65536.0, c[3],
+                sqrt(sdd / (c[3] > 0 ? c[3] : 1)) / 256.0, (flags & CANNY_HIP_CIRCLE_FIT_MAXD_MASK) / 256.0,
+                (unsigned)c[5] & 0xffffu, (flags & CANNY_HIP_CIRCLE_FIT_TRIM_FAILED) ? 1 : 0,
+                (flags & CANNY_HIP_CIRCLE_FIT_DEGENERATE) ? 1 : 0);
     }
     if (f != stdout) fclose(f);
     return 0;
@@ -593,6 +623,8 @@ int main(int argc, char *argv[])
     int fit_options = -1; // -f: the line fits of the segments; -1 = not asked for
     unsigned polygon_epsilon_q8 = 0, polygon_ratio_q16 = 0;
     int circle_args[6] = {0, 0, 0, 0, 0, 0}; // min_radius, max_radius, threshold, support, min_dist, cell_shift
+    bool want_circle_fits = false;
+    int circle_fit_args[3] = {0, 0, 0}; // -k: band, trim_q8, options
     int width = WIDTH, height = HEIGHT;
     vector<string> values;
 
@@ -657,6 +689,25 @@ int main(int argc, char *argv[])
                 exit(2);
             }
             want_circles = true;
+        } else if (arg == "-k" && i + 1 < argc) {
+            int *c = circle_fit_args;
+            int got = 0; // whole comma-separated integers only, as -r
+            bool clean = true;
+            for (const char *p = argv[++i]; clean; got++) {
+                char *end = nullptr;
+                const long v = strtol(p, &end, 10);
+                clean = end != p && got < 3 && !isspace((unsigned char)*p) && v >= -0x7fffffffL && v <= 0x7fffffffL;
+                if (clean) c[got] = (int)v;
+                if (!clean || *end == '\0') break;
+                clean = *end == ',';
+                p = end + 1;
+            }
+            got = clean ? got + 1 : 0;
+            if (got < 2 || got > 3 || c[0] < 0 || c[0] > CANNY_HIP_CIRCLE_FIT_MAX_BAND || c[1] < 0 || c[2] < 0 || c[2] > 3) {
+                fprintf(stderr, "ERROR: -k expects band,trim_q8[,options]: band 0..4, trim_q8 >= 0 (1/256 px, 0 = off), options 0..3\n");
+                exit(2);
+            }
+            want_circle_fits = true;
         } else if (arg == "-y" && i + 1 < argc) {
             // one or two non-negative numbers, nothing empty, nothing behind the last one
             double v[2] = {0.0, 0.0};
@@ -702,6 +753,10 @@ int main(int argc, char *argv[])
         fprintf(stderr, "ERROR: -f needs the segments of -l rho,theta_degrees,threshold[,lines_max] and -g min_length,max_gap[,exclusive]\n");
         exit(2);
     }
+    if (want_circle_fits && !want_circles) {
+        fprintf(stderr, "ERROR: -k needs the circles of -r min_radius,max_radius,threshold,support[,min_dist[,cell_shift]]\n");
+        exit(2);
+    }
     if (want_polygons && !want_contours) {
         fprintf(stderr, "ERROR: -y needs the contours of -t\n");
         exit(2);
@@ -731,6 +786,9 @@ int main(int argc, char *argv[])
         fprintf(stderr, "       pixel, area2 twice the area) -> canny_polygons.txt in the -o dir\n");
         fprintf(stderr, "   -r min_radius,max_radius,threshold,support[,min_dist[,cell_shift]]: circles of the edge map, one\n");
         fprintf(stderr, "       \"frame x y radius votes support\" line each -> canny_circles.txt in the -o dir\n");
+        fprintf(stderr, "   -k band,trim_q8[,options]: with -r, the sub-pixel circle fit of every circle (band 0..4 bins each side, trim_q8 in\n");
+        fprintf(stderr, "       1/256 px or 0, options 0..3: 1 = gate by gradient direction, 2 = refined edgels only), one \"frame cx cy r n rms\n");
+        fprintf(stderr, "       maxd sectors trim_failed degenerate\" line each (pixels; sectors in hex) -> canny_circle_fits.txt in the -o dir\n");
         fprintf(stderr, "   -d: distance of every pixel to the nearest edge pixel, min(255, floor) -> canny_dist.pgm in the -o dir\n");
         fprintf(stderr, "   -e: sub-pixel edgel of every edge pixel, one \"x y gx gy mag dir refined\" line each (x, y in pixels to three\n");
         fprintf(stderr, "       decimals, mag in grey levels, dir 0..3) -> canny_edgels.txt in the -o dir\n");
@@ -809,7 +867,8 @@ int main(int argc, char *argv[])
         if (rc) return rc;
     }
     if (want_circles) {
-        const int rc = run_circles(frame, height, width, sigma, minVal, maxVal, circle_args, outdir);
+        const int rc = run_circles(frame, height, width, sigma, minVal, maxVal, circle_args, want_circle_fits ? circle_fit_args : nullptr,
+                                   outdir);
         if (rc) return rc;
     }
     if (want_lines && want_segments)

@@ -52,7 +52,7 @@
 extern "C" {
 #endif
 
-#define CANNY_HIP_VERSION 1400       /* 0.14.0: + sub-pixel line fits: least-squares refit of Hough segments from edgels */
+#define CANNY_HIP_VERSION 1500       /* 0.15.0: + sub-pixel circle fits: least-squares refit of Hough circles from edgels */
 /* 0.13.0: + sub-pixel edgels: position, gradient and strength per edge pixel */
 /* 0.12.2: + canny_hip_selftest_launch_plan */
 /* 0.12.1: + canny_hip_selftest_workspace */
@@ -767,7 +767,7 @@ int canny_hip_canny_hough_segments(canny_hip_ctx *ctx, const unsigned char *imgs
  *   Frames under 2 x 2: CANNY_HIP_ERR_INVALID, as for the edgels.
  * The part is timed by canny_hip_line_fits_profile_get (CANNY_HIP_LINE_FIT_PART_FIT); with "profile_stage_mask" it goes by
  * bit 30 together with the polygon and edgel parts.
- * Not (yet) covered -- follow-ups: magnitude-weighted fits, circle refits for the Hough circles, merging collinear
+ * Not (yet) covered -- follow-ups: magnitude-weighted fits, merging collinear
  * segments, colour / automatic-threshold / batch-pipeline / sharder forms, keeping the used (u, v) pairs in LDS for the
  * second pass. */
 #define CANNY_HIP_LINE_FIT_INTS 12
@@ -912,6 +912,145 @@ int canny_hip_canny_hough_circles(canny_hip_ctx *ctx, const unsigned char *imgs,
  * exhaustive test, which runs every pair of the Sobel domain through it.  Asynchronous. */
 int canny_hip_dev_hough_circles_steps(canny_hip_ctx *ctx, const short *d_gx, const short *d_gy, size_t n, int *d_sx,
                                       int *d_sy);
+
+/* ---- sub-pixel circle fits ------------------------------------------------------------------------------------------------
+ * For every circle record of the section above one CIRCLE FIT record: the least-squares (Kasa) circle through the sub-pixel
+ * edgels of the edge pixels in a band around the Hough circle, the mean-distance radius, the residuals and a mask of the
+ * angular sectors that hold points -- on the GPU behind the circles call, on the same stream, with no host round trip and no
+ * atomics.  A Hough circle is only as fine as its cell and its whole-pixel radius; the fitted centre is typically 5 to 100
+ * times closer to the truth (DESIGN.md section 25 has the table).  The rule is all integers, so the records are the same
+ * bytes on every run and every machine; tests/circle_fits_rule.py restates it in Python ints,
+ * csrc/canny_circle_fits_host.cpp in plain C++.  THE RULE:
+ * Inputs for one frame: the edge map E; a plane P, unsigned char or short (the smoothed plane of the detector call, or a
+ *   caller's plane), height and width >= 2; the circle records (x2, y2, radius, votes, support, base) of the section above,
+ *   taken in their slots; band in 0 .. CANNY_HIP_CIRCLE_FIT_MAX_BAND; trim_q8 >= 0 (0 = off); options: bit 0 =
+ *   CANNY_HIP_CIRCLE_FIT_GATE, bit 1 = CANNY_HIP_CIRCLE_FIT_REFINED_ONLY, any other bit -> CANNY_HIP_ERR_INVALID.
+ * For record j:
+ *   1. Validity.  The record is INVALID -- word 4 = CANNY_HIP_CIRCLE_FIT_INVALID, the other seven words zero -- iff radius
+ *      lies outside [1, CANNY_HIP_CIRCLES_MAX_RADIUS], x2 outside [0, 2 * width) or y2 outside [0, 2 * height).  This is
+ *      decided before any access beyond the record; only caller-made records can be invalid.
+ *   2. Pixels.  The set pixels of E with (2 * lo - 1)^2 <= d < (2 * (radius + band) + 1)^2, d = (2x - x2)^2 + (2y - y2)^2,
+ *      lo = max(radius - band, 1): the bin rule of the circles, widened by band bins on each side.  With band = 0,
+ *      options = 0 and trim_q8 = 0, n == support for every record the circle call produced.
+ *   3. Edgels.  Each pixel yields its record of the edgel section from P, unchanged: (x_q8, y_q8), (gx, gy), refined.
+ *      With GATE a pixel is used only if (gx, gy) != (0, 0) and
+ *        4 * (gx * wx + gy * wy)^2 >= 3 * (gx^2 + gy^2) * (wx^2 + wy^2),  (wx, wy) = (2x - x2, 2y - y2)
+ *      -- gradients within 30 degrees of the radius; |wx|, |wy| <= 2057 and |gx|, |gy| <= 32768, so |gx * wx + gy * wy| <
+ *      2^27.1, the left side is below 2^56.2 and the right below 3 * 2^31 * 2^23.1 < 2^55.7.  With REFINED_ONLY a pixel is
+ *      used only if refined.  n = the used pixels.
+ *   4. Moments, relative to the Hough circle: u = x_q8 - 128 * x2, v = y_q8 - 128 * y2, z = u^2 + v^2 - (256 * radius)^2.
+ *      n, Su, Sv, Sz, Suu, Suv, Svv, Suz, Svz exactly (Suz, Svz in 128 bits, see the limits).  The Kasa fit z ~ a * u +
+ *      b * v + c in a form whose numbers stay small because the points lie near the Hough circle.  Centred, exact (128 bits):
+ *      A = n * Suu - Su^2, B = n * Suv - Su * Sv, C = n * Svv - Sv^2, P = n * Suz - Su * Sz, Q = n * Svz - Sv * Sz.
+ *   5. Centre.  [A B; B C] * (a, b) = (P, Q); the centre moves by (a / 2, b / 2) in 1/256 px, i.e. by 128 * a in 1/65536 px.
+ *      s = max(0, bitlength(max(A, C, |B|)) - 31); a' = A >> s, b' = B >> s, c' = C >> s (arithmetic shift: floor);
+ *      det' = a' * c' - b'^2 (|.| < 2^62).  P and Q are NOT shifted (128-bit products carry them).
+ *      Na = P * c' - Q * b', Nb = Q * a' - P * b'; e = 7 - s; for N in (Na, Nb):
+ *        X = |N| * 2^max(e, 0), Y = det' * 2^max(-e, 0), q = floor((2 * X + Y) / (2 * Y)), the move = sgn(N) * q
+ *      -- N * 2^e / det' to nearest, halves away from zero.  q <= limit is decided first, by 2 * X < Y * (2 * limit + 1) with
+ *      limit = 65536 * (band + 2) < 2^19; the quotient then takes twenty steps of restoring division (compare, subtract,
+ *      shift) on 128-bit values: the device has no 128-bit division and needs none.
+ *      DEGENERATE iff n < 3, or det' <= 0, or either q > limit (the centre would move by more than band + 2 pixels).
+ *      cx_q16 = 32768 * x2 + move_x, cy_q16 likewise.
+ *      Error against the exact rational solution (a, b) of the unshifted system: the quotient is exact for the SHIFTED
+ *      system, so with s = 0 the move is 128 * a rounded once.  With s > 0 each of a', b', c' is low by less than 1, and
+ *        |move_x - 128 * a| <= 1/2 + 128 * (c' + |b'|) * (|a| + |b|) / det',
+ *        |move_y - 128 * b| <= 1/2 + 128 * (a' + |b'|) * (|a| + |b|) / det'
+ *      (x' - x = M'^-1 * E * x for the shifted matrix M' = M / 2^s - E, 0 <= E < 1 entrywise; M'^-1 = adj(M') / det').  For a
+ *      full circle a' ~ c' ~ 2^30, b' ~ 0, det' ~ 2^60 and |a| + |b| < 2^12.6: the second term is below 2^-10.
+ *   6. Radius and residuals, a pass over the used pixels: U = 256 * u - move_x, V = 256 * v - move_y (the point against the
+ *      fitted centre in 1/65536 px), rho_q16 = isqrt(U^2 + V^2), the exact floor; e = rho_q16 - 65536 * radius;
+ *      r_q16 = 65536 * radius + rdiv(sum of e, n), rdiv as in the line fits: the mean distance, the least-squares radius
+ *      for the fitted centre.  d_q8 = (rho_q16 - r_q16 + 128) >> 8 (arithmetic shift).
+ *   7. Trim, if trim_q8 > 0 and the first fit is not degenerate: the used set becomes the pixels of step 3 with
+ *      |d_q8| <= trim_q8 against the first fit, and steps 4 to 6 run once more on that set.  One refit, never more.  If the
+ *      trimmed set is degenerate, the record is the first fit's with CANNY_HIP_CIRCLE_FIT_TRIM_FAILED set.
+ *   8. Statistics over the final used set against the final fit: n, Sdd = the sum of d_q8^2 (unsigned 64 bits), maxd =
+ *      max |d_q8|, and sectors: bit k is set iff a used pixel lies in angular sector k around the fitted centre, with
+ *      (dx, dy) = (U, V).  The plane is cut by the lines dy = 0, dx = 0, |dx| = |dy|, |dx| = 2 |dy|, |dy| = 2 |dx| into 16
+ *      sectors, numbered from the +x axis towards the +y axis (clockwise on the screen, y pointing down): quadrant 0 is dx > 0,
+ *      dy >= 0 with (p, q) = (dx, dy); quadrant 1 is dx <= 0, dy > 0 with (p, q) = (dy, -dx); quadrant 2 is dx < 0, dy <= 0
+ *      with (p, q) = (-dx, -dy); quadrant 3 is dx >= 0, dy < 0 with (p, q) = (-dy, dx); k = 4 * quadrant + (2q >= p) +
+ *      (q >= p) + (q >= 2p).  A pixel ON a boundary line belongs to the sector that STARTS there in this order; (0, 0)
+ *      belongs to sector 0.  Sixteen bits set: a full circle; a run of few: an arc.
+ *   9. Record: CANNY_HIP_CIRCLE_FIT_INTS = 8 32-bit words, 32 bytes:
+ *        words 0-2: cx_q16, cy_q16, r_q16 (1/65536 px)      word 3: n
+ *        word 4: maxd in bits 0-23, CANNY_HIP_CIRCLE_FIT_TRIM_FAILED (bit 27), _DEGENERATE (bit 28), _INVALID (bit 31)
+ *        word 5: sectors in bits 0-15                        words 6-7: Sdd, low word first
+ *      The caller's RMS distance is sqrt(Sdd / n) / 256 px.  A DEGENERATE record carries the Hough circle -- words 0-2 =
+ *      32768 * x2, 32768 * y2, 65536 * radius -- then n; its words 5-7 and maxd are zero.
+ *      The fit of circle slot f * centres_max + j goes to fit slot f * centres_max + j, for j < counts[f]; later slots are
+ *      not touched.
+ * Limits: max(height, width) <= CANNY_HIP_CIRCLE_FIT_MAX_AXIS = 16384 and band <= CANNY_HIP_CIRCLE_FIT_MAX_BAND = 4, else
+ *   CANNY_HIP_ERR_UNSUPPORTED with nothing written; frames under 2 x 2: CANNY_HIP_ERR_INVALID, as for the edgels.  Widths:
+ *     |u|, |v| <= 128 * (2 * 1028 + 1) + 128 < 2^18.01   (a pixel of the band against the centre, |t_q8| <= 128)
+ *     n < 2^17           (the band is at most 9 pixels wide: fewer than 2 pi * 1029 * 10.5 < 2^16.1 lattice points)
+ *     |z| < 2^29.5       (|rho - 256 * radius| <= 256 * 4.5 + 182, rho + 256 * radius < 2^19.01)
+ *     |Su|, |Sv| < 2^35.1; |Sz| < 2^46.5; Suu, Svv, |Suv| < 2^53.1: 64 bits.
+ *     |Suz|, |Svz| < 2^17 * 2^18.01 * 2^29.5 = 2^64.6: NOT 64 bits.  A lane of the kernel sums fewer than 2^15 products, each
+ *       below 2^47.6, in 64 bits (16 queued pixels, or one 64-pixel word per turn of its rows' trips when the queue is
+ *       full); across lanes the sums are carried as a high and a low half and joined in 128 bits.
+ *     A, C, |B| < 2^70.1; |P|, |Q| < 2^82.6; a', c', |b'| < 2^31; |Na|, |Nb| < 2^114.6; e in -33 .. 7; X < 2^121.6, 2 X + Y <
+ *       2^122.7; Y < 2^95, Y * (2 * limit + 1) < 2^115, 2 Y * 2^19 < 2^115: signed 128 bits throughout.
+ *     |U|, |V| < 2^26.1 (the move is at most 2^18.6), U^2 + V^2 < 2^53.2: the root's argument is far below 2^63.
+ *     |e| < 2^20; |sum of e| < 2^37; |d_q8| < 2^13, which fits the 24 bits of maxd; Sdd < 2^43.
+ * The part is timed by canny_hip_circle_fits_profile_get (CANNY_HIP_CIRCLE_FIT_PART_FIT); with "profile_stage_mask" it goes
+ * by bit 30 together with the polygon, edgel and line-fit parts.
+ * Not covered -- follow-ups: Pratt / Taubin weighting, ellipses, several refits, colour / automatic-threshold /
+ * batch-pipeline / sharder forms. */
+#define CANNY_HIP_CIRCLE_FIT_INTS 8
+#define CANNY_HIP_CIRCLE_FIT_GATE 1
+#define CANNY_HIP_CIRCLE_FIT_REFINED_ONLY 2
+#define CANNY_HIP_CIRCLE_FIT_MAXD_MASK 0x00ffffffu
+#define CANNY_HIP_CIRCLE_FIT_TRIM_FAILED 0x08000000u
+#define CANNY_HIP_CIRCLE_FIT_DEGENERATE 0x10000000u
+#define CANNY_HIP_CIRCLE_FIT_INVALID 0x80000000u
+#define CANNY_HIP_CIRCLE_FIT_MAX_AXIS 16384
+#define CANNY_HIP_CIRCLE_FIT_MAX_BAND 4
+#define CANNY_HIP_CIRCLE_FIT_MOMENT_WORDS 12
+enum canny_hip_circle_fit_part {
+    CANNY_HIP_CIRCLE_FIT_PART_FIT = 0, /* the one kernel: row walk, queue, edgels, the fits and the statistics */
+    CANNY_HIP_CIRCLE_FIT_PARTS = 1
+};
+/* Host-only, needs no device: the rule in plain C++ on ONE host frame.  bits: the edge map in the layout of
+ * canny_hip_dev_canny_bits; plane: height x width bytes if plane_is_u8 else shorts; circles: n_circles records of 6 ints;
+ * fits receives n_circles records of 8 ints. */
+int canny_hip_circle_fits_from_plane(const unsigned char *bits, const void *plane, int plane_is_u8, int height, int width,
+                                     const int *circles, int n_circles, int band, int trim_q8, int options, int *fits);
+/* Device bit maps (layout of canny_hip_dev_canny_bits), a device plane (bytes if plane_is_u8 else shorts, n_frames contiguous
+ * planes) and the circle records and counts an earlier call left on the device (or the caller made: this is where INVALID
+ * records come from).  d_plane == NULL means the smoothed plane the last canny_hip_dev_canny-family call on this context
+ * left, under the rule of canny_hip_dev_edgels_at: CANNY_HIP_ERR_INVALID, nothing queued, if no such call ran or its shape
+ * differs.  d_fits: n_frames * centres_max * 8 ints, 16-byte aligned, mandatory.  Asynchronous. */
+int canny_hip_dev_circle_fits_bits(canny_hip_ctx *ctx, const unsigned char *d_bits, const void *d_plane, int plane_is_u8,
+                                   int n_frames, int height, int width, const int *d_circles, const int *d_counts,
+                                   int centres_max, int band, int trim_q8, int options, int *d_fits);
+/* canny_hip_dev_canny_hough_circles unchanged, then the fits queued behind it on the same stream, read from the converged
+ * strong bit-plane and the smoothed plane that call left on the context.  d_circles and d_counts may be NULL (they then
+ * live in a context workspace); d_fits is mandatory; everything else as there.  max_val > 255: all counts are 0 and no fit is
+ * written. */
+int canny_hip_dev_canny_hough_circle_fits(canny_hip_ctx *ctx, const unsigned char *d_img, float sigma, int min_val,
+                                          int max_val, int height, int width, int n_frames, short *d_edges, int min_radius,
+                                          int max_radius, int cell_shift, int threshold, int support_threshold,
+                                          int min_dist, int centres_max, int *d_circles, int *d_counts,
+                                          int *d_centre_counts, int *d_accum, int band, int trim_q8, int options,
+                                          int *d_fits);
+/* Host buffers, synchronous, in the pattern of canny_hip_canny_hough_circles: the counts come down first, then only the
+ * filled slots of circles and fits.  circles and centre_counts may be NULL; counts and fits are mandatory. */
+int canny_hip_canny_hough_circle_fits(canny_hip_ctx *ctx, const unsigned char *imgs, int n_frames, float sigma, int min_val,
+                                      int max_val, int height, int width, int min_radius, int max_radius, int cell_shift,
+                                      int threshold, int support_threshold, int min_dist, int centres_max, int band,
+                                      int trim_q8, int options, int *circles, int *counts, int *centre_counts, int *fits);
+/* Test hook: the device finishing function (steps 4 and 5) on n_sets moment sets of CANNY_HIP_CIRCLE_FIT_MOMENT_WORDS = 12
+ * long longs (n, Su, Sv, Sz, Suu, Suv, Svv, Suz low, Suz high, Svz low, Svz high, band; Suz and Svz two's-complement 128-bit
+ * values), the sums within the limits above and band in 0 .. 4; d_out receives 4 ints per set: move_x, move_y (both 0 if
+ * degenerate), n, then CANNY_HIP_CIRCLE_FIT_DEGENERATE or 0.  Asynchronous. */
+int canny_hip_dev_circle_fits_arith(canny_hip_ctx *ctx, const long long *d_moments, size_t n_sets, int *d_out);
+/* Host-only, the same hook on the plain C++ restatement (host arrays). */
+int canny_hip_circle_fits_finish(const long long *moments, size_t n_sets, int *out);
+/* Host-only: how many pixels of one record the fit kernel keeps in its LDS queue; a record with more pixels in its band is
+ * finished by recomputing the rest, with the same bytes.  For the test that exceeds it on purpose. */
+int canny_hip_circle_fits_queue_capacity(void);
 
 /* ---- connected components ------------------------------------------------------------------------------------------------
  * Eight-connected component labelling of the finished edge map, per frame of a batch, on the GPU, queued behind the detector
@@ -1258,6 +1397,8 @@ int canny_hip_polygons_profile_get(canny_hip_ctx *ctx, int part, double *total_m
 int canny_hip_edgels_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches);
 /* ... and for the one part of the line fits (CANNY_HIP_LINE_FIT_PART_*). */
 int canny_hip_line_fits_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches);
+/* ... and for the one part of the circle fits (CANNY_HIP_CIRCLE_FIT_PART_*). */
+int canny_hip_circle_fits_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches);
 
 /* ---- self-test hooks used by the GPU test-suite -------------------------------------------- */
 /* Runs the DEVICE magnitude / angle-bin functions over every (gx,gy) in [-lim,lim]^2 and writes
