@@ -124,6 +124,10 @@ EXPORTS = (
     "canny_hip_circle_fits_from_plane", "canny_hip_dev_circle_fits_bits", "canny_hip_dev_canny_hough_circle_fits",
     "canny_hip_canny_hough_circle_fits", "canny_hip_dev_circle_fits_arith", "canny_hip_circle_fits_finish",
     "canny_hip_circle_fits_profile_get", "canny_hip_circle_fits_queue_capacity",
+    "canny_hip_chamfer_set_create", "canny_hip_chamfer_set_destroy", "canny_hip_dev_chamfer_dist2",
+    "canny_hip_dev_chamfer_bits", "canny_hip_dev_canny_chamfer", "canny_hip_canny_chamfer", "canny_hip_chamfer_from_dist2",
+    "canny_hip_chamfer_cost_of", "canny_hip_dev_chamfer_costs", "canny_hip_chamfer_profile_get",
+    "canny_hip_selftest_chamfer_plan", "canny_hip_selftest_chamfer_bands",
 )
 
 _lib: Optional[C.CDLL] = None
@@ -308,6 +312,18 @@ def load() -> C.CDLL:
         "canny_hip_circle_fits_finish": ([p, sz, p], i),
         "canny_hip_circle_fits_profile_get": ([p, i, C.POINTER(C.c_double), C.POINTER(C.c_long)], i),
         "canny_hip_circle_fits_queue_capacity": ([], i),
+        "canny_hip_chamfer_set_create": ([p, p, p, i, p], i),
+        "canny_hip_chamfer_set_destroy": ([p, p], i),
+        "canny_hip_dev_chamfer_dist2": ([p, p, i, i, i, p, i, i, i, i, p, p, p, p], i),
+        "canny_hip_dev_chamfer_bits": ([p, p, i, i, i, p, p, i, i, i, i, p, p, p, p], i),
+        "canny_hip_dev_canny_chamfer": ([p, p, f, i, i, i, i, i, p, p, p, i, i, i, i, p, p, p, p], i),
+        "canny_hip_canny_chamfer": ([p, p, i, f, i, i, i, i, p, i, i, i, i, p, p, p], i),
+        "canny_hip_chamfer_from_dist2": ([p, i, i, p, p, i, i, i, i, i, p, ip, ip, p], i),
+        "canny_hip_chamfer_cost_of": ([i, i], i),
+        "canny_hip_dev_chamfer_costs": ([p, p, sz, i, p], i),
+        "canny_hip_chamfer_profile_get": ([p, i, C.POINTER(C.c_double), C.POINTER(C.c_long)], i),
+        "canny_hip_selftest_chamfer_plan": ([i, i, i, i, i, i, p], i),
+        "canny_hip_selftest_chamfer_bands": ([p, p, i, i, p], i),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -783,6 +799,106 @@ def circle_fits_unpack(fits) -> dict:
             "rms": np.sqrt(sdd / np.maximum(n, 1)) / 256.0, "maxd": (w4 & CIRCLE_FIT_MAXD_MASK) / 256.0,
             "sectors": sec, "sector_count": count, "trim_failed": (w4 & CIRCLE_FIT_TRIM_FAILED) != 0,
             "degenerate": (w4 & CIRCLE_FIT_DEGENERATE) != 0, "invalid": (w4 & CIRCLE_FIT_INVALID) != 0}
+
+
+# ---- chamfer template matching --------------------------------------------------------------------
+MATCH_INTS = 6
+CHAMFER_MAX_EXTENT, CHAMFER_MAX_TEMPLATES, CHAMFER_MAX_POINTS, CHAMFER_MAX_TRUNC = 255, 1024, 65536, 4095
+CHAMFER_PARTS = ("cost", "score", "candidates", "accept")
+CHAMFER_PLANS = ("cost", "cells")
+MATCH_DTYPE = np.dtype([("x", np.int32), ("y", np.int32), ("template", np.int32), ("score", np.int32),
+                        ("mean_q12", np.int32), ("base", np.int32)])
+
+
+def chamfer_csr(templates) -> Tuple[np.ndarray, np.ndarray]:
+    """A list of (K_t, 2) integer arrays of (dx, dy) -> (offsets int32 [T + 1], points int16 [sum K_t, 2]), the CSR shape
+    the C entry points take.  Values outside int16 raise; the limits of the rule are the library's to check."""
+    tpl = [np.asarray(t).reshape(-1, 2) for t in templates]
+    off = np.zeros(len(tpl) + 1, np.int32)
+    off[1:] = np.cumsum([len(t) for t in tpl])
+    cat = np.concatenate(tpl, axis=0) if tpl else np.zeros((0, 2), np.int64)
+    if len(cat) and (cat.min() < -32768 or cat.max() > 32767):
+        raise ValueError("template offsets must fit int16")
+    return off, np.ascontiguousarray(cat, dtype=np.int16)
+
+
+def chamfer_template_from_mask(mask, anchor=None) -> np.ndarray:
+    """The non-zero pixels of a 2-D mask as template points (dx, dy) int16 [K, 2], in raster order, relative to anchor =
+    (x, y); the default anchor is the centre (width // 2, height // 2)."""
+    m = np.asarray(mask)
+    if m.ndim != 2:
+        raise ValueError("expected a 2-D mask")
+    ax, ay = (m.shape[1] // 2, m.shape[0] // 2) if anchor is None else (int(anchor[0]), int(anchor[1]))
+    ys, xs = np.nonzero(m)
+    return np.stack([xs - ax, ys - ay], axis=1).astype(np.int16)
+
+
+def chamfer_rotations(points, angles_deg) -> list:
+    """Host-side input preparation (not part of the rule): the template rotated about its anchor by each angle (degrees,
+    counter-clockwise in image coordinates with y down: x' = x cos a + y sin a, y' = -x sin a + y cos a), rounded half
+    away from zero to whole pixels and de-duplicated (np.unique order).  -> a list of int16 [K_a, 2] arrays."""
+    pts = np.asarray(points, dtype=np.float64).reshape(-1, 2)
+    out = []
+    for a in angles_deg:
+        c, s_ = np.cos(np.deg2rad(float(a))), np.sin(np.deg2rad(float(a)))
+        x = pts[:, 0] * c + pts[:, 1] * s_
+        y = -pts[:, 0] * s_ + pts[:, 1] * c
+        r = np.stack([np.sign(x) * np.floor(np.abs(x) + 0.5), np.sign(y) * np.floor(np.abs(y) + 0.5)], axis=1)
+        out.append(np.unique(r.astype(np.int16), axis=0))
+    return out
+
+
+def chamfer_cost_of(d2: int, trunc_q4: int) -> int:
+    """Host-only: cost(d2) of the rule = min(isqrt(d2 * 256), trunc_q4)."""
+    v = load().canny_hip_chamfer_cost_of(int(d2), int(trunc_q4))
+    if v < 0:
+        raise CannyHipError(1, "chamfer_cost_of")
+    return v
+
+
+def chamfer_from_dist2(dist2, templates, trunc_q4: int, max_mean_q4: int, min_dist: int = 0, matches_max: int = 256,
+                       want_scores: bool = False, csr=None):
+    """Host-only, needs no GPU: the chamfer-matching rule on ONE int32 dist2 plane [H, W] with a list of templates (or
+    csr = (offsets, points) as they are) -> (matches int32 [k, 6]: x, y, template, score, mean_q12, base; the true
+    candidate count; scores uint32 [T, H, W] or None)."""
+    d = np.ascontiguousarray(dist2, dtype=np.int32)
+    if d.ndim != 2:
+        raise ValueError("expected a 2-D dist2 plane")
+    off, pts = csr if csr is not None else chamfer_csr(templates)
+    off, pts = np.ascontiguousarray(off, dtype=np.int32), np.ascontiguousarray(pts, dtype=np.int16)
+    h, w = d.shape
+    T = len(off) - 1
+    rec = np.zeros((max(int(matches_max), 1), MATCH_INTS), np.int32)
+    scores = np.zeros((max(T, 1), h, w), np.uint32) if want_scores else None
+    n, nc = C.c_int(0), C.c_int(0)
+    st = load().canny_hip_chamfer_from_dist2(_hp(d), h, w, _hp(off), _hp(pts), T, trunc_q4, max_mean_q4, min_dist,
+                                             matches_max, _hp(rec), C.byref(n), C.byref(nc),
+                                             _hp(scores) if want_scores else None)
+    if st:
+        raise CannyHipError(st, "chamfer_from_dist2")
+    return rec[:n.value].copy(), nc.value, scores
+
+
+def chamfer_plan(which, n_frames: int, height: int, width: int, n_templates: int, with_scores: bool = False):
+    """Host-only: (LaunchPlan, frames per chunk) of a capped chamfer launch ("cost" or "cells") for a full chunk."""
+    k = CHAMFER_PLANS.index(which) if isinstance(which, str) else int(which)
+    out = np.zeros(6, np.uint64)
+    st = load().canny_hip_selftest_chamfer_plan(k, int(n_frames), int(height), int(width), int(n_templates),
+                                                int(bool(with_scores)), _hp(out))
+    if st:
+        raise CannyHipError(st, "selftest_chamfer_plan")
+    return LaunchPlan(*(int(v) for v in out[:5])), int(out[5])
+
+
+def chamfer_bands(templates, t: int = 0, csr=None) -> Tuple[int, int, int, int]:
+    """Host-only: (bands of dy, largest LDS tile of template t in u16, largest of the set, automatic route) of the tiled
+    score kernel for a template list."""
+    off, pts = csr if csr is not None else chamfer_csr(templates)
+    out = np.zeros(4, np.int32)
+    st = load().canny_hip_selftest_chamfer_bands(_hp(off), _hp(pts), len(off) - 1, int(t), _hp(out))
+    if st:
+        raise CannyHipError(st, "selftest_chamfer_bands")
+    return tuple(int(v) for v in out)
 
 
 def points_to_rc(points, width: int) -> Tuple[np.ndarray, np.ndarray]:
@@ -1716,6 +1832,82 @@ class Context:
         ms, n = C.c_double(0), C.c_long(0)
         self._check(self._L.canny_hip_hough_circles_profile_get(self._h, part, C.byref(ms), C.byref(n)),
                     "hough_circles_profile_get")
+        return ms.value, n.value
+
+    # ---- chamfer template matching on the distance transform -----------------------------
+    def chamfer_set_create(self, templates=None, csr=None) -> int:
+        """A template set on this context from a list of (K_t, 2) arrays of (dx, dy), or csr = (offsets, points) as they
+        are -> an opaque handle for the chamfer calls; chamfer_set_destroy releases it (the context does at the latest)."""
+        off, pts = csr if csr is not None else chamfer_csr(templates)
+        off, pts = np.ascontiguousarray(off, dtype=np.int32), np.ascontiguousarray(pts, dtype=np.int16)
+        h = C.c_void_p()
+        self._check(self._L.canny_hip_chamfer_set_create(self._h, _hp(off), _hp(pts), len(off) - 1, C.byref(h)),
+                    "chamfer_set_create")
+        return h.value
+
+    def chamfer_set_destroy(self, cset: int):
+        self._check(self._L.canny_hip_chamfer_set_destroy(self._h, C.c_void_p(cset or None)), "chamfer_set_destroy")
+
+    def dev_chamfer_dist2(self, d_dist2: int, n: int, h: int, w: int, cset: int, trunc_q4: int, max_mean_q4: int,
+                          min_dist: int, matches_max: int, d_matches: int, d_counts: int, d_cand_counts: int = 0,
+                          d_scores: int = 0):
+        """Matching alone on a device dist2 plane; d_matches (6 int32 per slot, slot f * matches_max + j), d_cand_counts,
+        d_scores ([n][T][h][w] uint32) may be 0; d_counts: n int32.  Asynchronous."""
+        v = C.c_void_p
+        self._check(self._L.canny_hip_dev_chamfer_dist2(self._h, v(d_dist2 or None), n, h, w, v(cset or None), trunc_q4,
+                                                        max_mean_q4, min_dist, matches_max, v(d_matches or None),
+                                                        v(d_counts or None), v(d_cand_counts or None), v(d_scores or None)),
+                    "dev_chamfer_dist2")
+
+    def dev_chamfer_bits(self, d_bits: int, n: int, h: int, w: int, cset: int, trunc_q4: int, max_mean_q4: int,
+                         min_dist: int, matches_max: int, d_matches: int, d_counts: int, d_cand_counts: int = 0,
+                         d_scores: int = 0, d_dist2: int = 0):
+        """dev_edt_bits on device bit maps, then the matching; d_dist2 0: a workspace holds the plane."""
+        v = C.c_void_p
+        self._check(self._L.canny_hip_dev_chamfer_bits(self._h, v(d_bits or None), n, h, w, v(d_dist2 or None),
+                                                       v(cset or None), trunc_q4, max_mean_q4, min_dist, matches_max,
+                                                       v(d_matches or None), v(d_counts or None), v(d_cand_counts or None),
+                                                       v(d_scores or None)), "dev_chamfer_bits")
+
+    def dev_canny_chamfer(self, d_img: int, sigma: float, min_val: int, max_val: int, h: int, w: int, n: int, cset: int,
+                          trunc_q4: int, max_mean_q4: int, min_dist: int, matches_max: int, d_matches: int, d_counts: int,
+                          d_cand_counts: int = 0, d_scores: int = 0, d_edges: int = 0, d_dist2: int = 0):
+        """dev_canny_edt, then the matching queued behind it on the same stream."""
+        v = C.c_void_p
+        self._check(self._L.canny_hip_dev_canny_chamfer(self._h, v(d_img or None), sigma, min_val, max_val, h, w, n,
+                                                        v(d_edges or None), v(d_dist2 or None), v(cset or None), trunc_q4,
+                                                        max_mean_q4, min_dist, matches_max, v(d_matches or None),
+                                                        v(d_counts or None), v(d_cand_counts or None), v(d_scores or None)),
+                    "dev_canny_chamfer")
+
+    def canny_chamfer(self, imgs, sigma: float, min_val: int, max_val: int, cset: int, trunc_q4: int, max_mean_q4: int,
+                      min_dist: int = 0, matches_max: int = 256):
+        """canny(), the distance transform and the matching of each map on the GPU: imgs (H, W) or (N, H, W) uint8 ->
+        (matches, cand_counts): matches[f] is a structured array (MATCH_DTYPE) of the accepted matches in order,
+        cand_counts int32 [N] the true number of candidates per frame."""
+        a = np.ascontiguousarray(imgs, dtype=np.uint8)
+        if a.ndim == 2:
+            a = a[None]
+        if a.ndim != 3:
+            raise ValueError("expected uint8 [H, W] or [n_frames, H, W]")
+        n, h, w = a.shape
+        rec = np.zeros((n, max(int(matches_max), 1), MATCH_INTS), np.int32)
+        counts, cands = np.zeros(n, np.int32), np.zeros(n, np.int32)
+        self._check(self._L.canny_hip_canny_chamfer(self._h, _hp(a), n, sigma, min_val, max_val, h, w,
+                                                    C.c_void_p(cset or None), trunc_q4, max_mean_q4, min_dist, matches_max,
+                                                    _hp(rec), _hp(counts), _hp(cands)), "canny_chamfer")
+        return [np.ascontiguousarray(rec[f, :int(counts[f])]).view(MATCH_DTYPE).reshape(-1) for f in range(n)], cands
+
+    def dev_chamfer_costs(self, d_dist2: int, n: int, trunc_q4: int, d_costs: int):
+        """The device's cost arithmetic on n int32 dist2 values -> n uint32 (trunc_q4 = 0: the untruncated root)."""
+        v = C.c_void_p
+        self._check(self._L.canny_hip_dev_chamfer_costs(self._h, v(d_dist2 or None), n, trunc_q4, v(d_costs or None)),
+                    "dev_chamfer_costs")
+
+    def chamfer_profile_get(self, part: int) -> Tuple[float, int]:
+        """(total ms, launch groups) of part 0 cost, 1 score, 2 candidates, 3 accept (CHAMFER_PARTS)."""
+        ms, n = C.c_double(0), C.c_long(0)
+        self._check(self._L.canny_hip_chamfer_profile_get(self._h, part, C.byref(ms), C.byref(n)), "chamfer_profile_get")
         return ms.value, n.value
 
     # ---- sub-pixel circle fits (least-squares refit of the Hough circles from edgels; DESIGN.md section 25) ------

@@ -405,6 +405,12 @@ struct canny_hip_ctx {
     DevBuf circ_accum, circ_ws;
     // circle fits: the circle records and counts when the caller passes none
     DevBuf circ_recs;
+    // chamfer matching, per chunk of frames: the u16 cost plane; the scores when the caller passes no plane for them; the
+    // candidate passes' keys, histograms and counters; and the dist2 plane of the whole batch when the caller passes none
+    DevBuf chamfer_cost, chamfer_scores, chamfer_ws, chamfer_dist2;
+    int chamfer_route = 0; // 0 auto, 1 direct, 2 tiled
+    int chamfer_chunk_mb = 0; // A/B and tests: budget of the score workspace in MiB, 0 = 256
+    std::vector<canny_hip_chamfer_set *> chamfer_sets; // the sets created on this context and not yet destroyed
     DevBuf plane_s, plane_c, stamps, flags; // hysteresis bit-planes / scheduling words
     DevBuf io[4];     // staging for the host-pointer stage functions
     std::string ws_name; // canny_hip_selftest_workspace: the name it handed out last
@@ -434,7 +440,8 @@ struct canny_hip_ctx {
     // (canny_hip_contours_profile_get), then the four of the Hough circles (canny_hip_hough_circles_profile_get), then the
     // three of the polygon approximation (canny_hip_polygons_profile_get), then the two of the sub-pixel edgels
     // (canny_hip_edgels_profile_get), then the one of the line fits (canny_hip_line_fits_profile_get), then the one of the
-    // circle fits (canny_hip_circle_fits_profile_get).  The mask is a non-negative int option: bit 30 is the last it can
+    // circle fits (canny_hip_circle_fits_profile_get), then the four of the chamfer matching
+    // (canny_hip_chamfer_profile_get).  The mask is a non-negative int option: bit 30 is the last it can
     // carry, and the three polygon slots, the two edgel slots, the line-fit slot and the circle-fit slot behind them go by
     // it together
     static constexpr int kProfHough = CANNY_HIP_STAGE_END, kProfComponents = CANNY_HIP_STAGE_END + 3;
@@ -446,7 +453,8 @@ struct canny_hip_ctx {
     static constexpr int kProfEdgels = kProfPolygons + CANNY_HIP_POLYGON_PARTS;
     static constexpr int kProfLineFits = kProfEdgels + CANNY_HIP_EDGEL_PARTS;
     static constexpr int kProfCircleFits = kProfLineFits + CANNY_HIP_LINE_FIT_PARTS;
-    static constexpr int kProfSlots = kProfCircleFits + CANNY_HIP_CIRCLE_FIT_PARTS;
+    static constexpr int kProfChamfer = kProfCircleFits + CANNY_HIP_CIRCLE_FIT_PARTS;
+    static constexpr int kProfSlots = kProfChamfer + CANNY_HIP_CHAMFER_PARTS;
     static constexpr int kProfLastBit = 30;
     static_assert(kProfPolygons == kProfLastBit && kProfEdgels > kProfLastBit,
                   "profile_stage_mask has one bit per slot up to the polygon parts; every slot from there on follows bit 30");
@@ -1857,6 +1865,10 @@ void collect_workspaces(const canny_hip_ctx *c, const std::string &prefix, std::
     add("circ_accum", c->circ_accum, D);
     add("circ_ws", c->circ_ws, I);         // bases address accumulator cells, peak counts bound loops
     add("circ_recs", c->circ_recs, I);     // radii and centres bound the fit's row walk, counts its grid
+    add("chamfer_cost", c->chamfer_cost, D);
+    add("chamfer_scores", c->chamfer_scores, D);
+    add("chamfer_ws", c->chamfer_ws, I);   // keys address score cells, totals bound the sort, counters hand out slots
+    add("chamfer_dist2", c->chamfer_dist2, I); // doubles as the column scan's stack (see edt_stack)
     add("plane_s", c->plane_s, D);
     add("plane_c", c->plane_c, D);
     add("stamps", c->stamps, I);           // tile queues and their counters
@@ -1966,6 +1978,11 @@ void canny_hip_ctx_destroy(canny_hip_ctx *ctx)
     ctx->circ_accum.release();
     ctx->circ_ws.release();
     ctx->circ_recs.release();
+    while (!ctx->chamfer_sets.empty()) (void)canny_hip_chamfer_set_destroy(ctx, ctx->chamfer_sets.back());
+    ctx->chamfer_cost.release();
+    ctx->chamfer_scores.release();
+    ctx->chamfer_ws.release();
+    ctx->chamfer_dist2.release();
     ctx->cc_parent.release();
     ctx->cc_ws.release();
     ctx->ct_ws.release();
@@ -2019,6 +2036,8 @@ int canny_hip_ctx_get_option(const canny_hip_ctx *ctx, const char *name, int *va
     else if (!std::strcmp(name, "tune_batch_compact")) *value = ctx->batch_compact;
     else if (!std::strcmp(name, "hough_path")) *value = ctx->hough_path;
     else if (!std::strcmp(name, "tune_hough_lds_kb")) *value = ctx->hough_lds_kb;
+    else if (!std::strcmp(name, "chamfer_route")) *value = ctx->chamfer_route;
+    else if (!std::strcmp(name, "tune_chamfer_chunk_mb")) *value = ctx->chamfer_chunk_mb;
     else if (!std::strcmp(name, "batch_expand_threads")) *value = ctx->expand_pool ? ctx->expand_pool->size() : 0; // read-only
     else return CANNY_HIP_ERR_INVALID;
     return CANNY_HIP_OK;
@@ -2043,6 +2062,8 @@ int canny_hip_ctx_set_option(canny_hip_ctx *ctx, const char *name, int value)
     else if (!std::strcmp(name, "tune_batch_pipe_mode") && value <= 2) ctx->batch_pipe_mode = value;
     else if (!std::strcmp(name, "tune_batch_compact") && value <= 1) ctx->batch_compact = value;
     else if (!std::strcmp(name, "hough_path") && value <= 2) ctx->hough_path = value;
+    else if (!std::strcmp(name, "chamfer_route") && value <= 2) ctx->chamfer_route = value;
+    else if (!std::strcmp(name, "tune_chamfer_chunk_mb") && value <= 4096) ctx->chamfer_chunk_mb = value;
     else if (!std::strcmp(name, "tune_hough_lds_kb") && value <= kHoughLdsMax / 1024) ctx->hough_lds_kb = value;
     else if (!std::strcmp(name, "tune_batch_expand_threads") && value <= 64) {
         if (value != ctx->batch_expand_threads) ctx->expand_pool.reset();
@@ -5103,6 +5124,289 @@ int canny_hip_selftest_workspace(canny_hip_ctx *ctx, int index, const char **nam
     *d_ptr = all[(size_t)index].buf->p;
     *bytes = all[(size_t)index].buf->bytes;
     *kind = all[(size_t)index].kind;
+    return CANNY_HIP_OK;
+}
+
+// ---- chamfer template matching (canny_chamfer.hip) ---------------------------------
+} // extern "C"
+
+struct canny_hip_chamfer_set {
+    canny_hip_ctx *ctx = nullptr;
+    ChamferLayout lay;
+    DevBuf dev; // offsets | points | boxes | band offsets | bands
+    ChamferSetDev d{};
+};
+
+namespace {
+
+struct ChamferArgs {
+    int trunc_q4, max_mean_q4, min_dist, matches_max;
+};
+struct ChamferOut {
+    int *d_matches, *d_counts, *d_cand_counts;
+    unsigned *d_scores;
+};
+
+// Whether `set` is a live set of this context.  The handle is looked up among the sets the context created and has not
+// destroyed, and is not read: a destroyed set's memory is gone, a foreign one belongs to another context's list.
+bool chamfer_set_alive(const canny_hip_ctx *ctx, const canny_hip_chamfer_set *set)
+{
+    return set && std::find(ctx->chamfer_sets.begin(), ctx->chamfer_sets.end(), set) != ctx->chamfer_sets.end();
+}
+
+// THE check of the matching arguments; needs no device and writes nothing
+int chamfer_check(const canny_hip_ctx *ctx, int height, int width, int n_frames, const canny_hip_chamfer_set *set,
+                  const ChamferArgs &a, const int *d_counts)
+{
+    if (!chamfer_set_alive(ctx, set) || !d_counts || a.trunc_q4 < 1 || a.max_mean_q4 < 0 || a.max_mean_q4 >= a.trunc_q4 ||
+        a.min_dist < 0 || a.matches_max < 1)
+        return CANNY_HIP_ERR_INVALID;
+    int rc = check_dims(height, width, n_frames);
+    if (rc) return rc;
+    if (a.trunc_q4 > CANNY_HIP_CHAMFER_MAX_TRUNC || a.matches_max > kHoughMaxLines || height > 65535 || width > 65535 ||
+        (long long)height * width * set->lay.n_templates >= 0x80000000LL)
+        return CANNY_HIP_ERR_UNSUPPORTED;
+    return CANNY_HIP_OK;
+}
+
+// The matching of n frames of a device dist2 plane, queued on the context's stream, chunk of frames by chunk of frames.
+int dev_chamfer(canny_hip_ctx *ctx, const int *d_dist2, int n, int h, int w, const canny_hip_chamfer_set *set,
+                const ChamferArgs &a, const ChamferOut &out)
+{
+    const int T = set->lay.n_templates;
+    const size_t hw = (size_t)h * w;
+    const int chunk = chamfer_chunk_frames(n, h, w, T, out.d_scores != nullptr, ctx->chamfer_chunk_mb);
+    const bool tiled = (ctx->chamfer_route ? ctx->chamfer_route : chamfer_auto_route(set->lay)) == 2;
+    HIP_TRY(ctx, ctx->chamfer_cost.ensure((size_t)chunk * hw * sizeof(uint16_t)));
+    if (!out.d_scores) HIP_TRY(ctx, ctx->chamfer_scores.ensure((size_t)chunk * hw * T * sizeof(unsigned)));
+    HIP_TRY(ctx, ctx->chamfer_ws.ensure(chamfer_ws_bytes(chunk, a.matches_max)));
+    uint16_t *cost = (uint16_t *)ctx->chamfer_cost.p;
+    const int part = canny_hip_ctx::kProfChamfer;
+    for (int f0 = 0; f0 < n; f0 += chunk) {
+        const int nf = std::min(chunk, n - f0);
+        unsigned *scores = out.d_scores ? out.d_scores + (size_t)f0 * hw * T : (unsigned *)ctx->chamfer_scores.p;
+        {
+            StageTimer tm(ctx, part + CANNY_HIP_CHAMFER_PART_COST);
+            HIP_TRY(ctx, launch_chamfer_cost(d_dist2 + (size_t)f0 * hw, (size_t)nf * hw, a.trunc_q4, cost, ctx->stream));
+        }
+        {
+            StageTimer tm(ctx, part + CANNY_HIP_CHAMFER_PART_SCORE);
+            HIP_TRY(ctx, launch_chamfer_score(cost, nf, h, w, set->d, a.trunc_q4, tiled, scores, ctx->stream));
+        }
+        {
+            StageTimer tm(ctx, part + CANNY_HIP_CHAMFER_PART_CANDIDATES);
+            HIP_TRY(ctx, launch_chamfer_candidates(scores, nf, h, w, set->d, a.max_mean_q4, a.matches_max, ctx->chamfer_ws.p,
+                                                   out.d_cand_counts ? out.d_cand_counts + f0 : nullptr, ctx->stream));
+        }
+        {
+            StageTimer tm(ctx, part + CANNY_HIP_CHAMFER_PART_ACCEPT);
+            HIP_TRY(ctx, launch_chamfer_accept(scores, nf, h, w, T, a.matches_max, a.min_dist, ctx->chamfer_ws.p,
+                                               out.d_matches ? out.d_matches + (size_t)f0 * a.matches_max * CANNY_HIP_MATCH_INTS
+                                                             : nullptr,
+                                               out.d_counts + f0, ctx->stream));
+        }
+    }
+    return CANNY_HIP_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int canny_hip_chamfer_set_create(canny_hip_ctx *ctx, const int *offsets, const short *points, int n_templates,
+                                 canny_hip_chamfer_set **set)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!set) return CANNY_HIP_ERR_INVALID;
+    *set = nullptr;
+    std::unique_ptr<canny_hip_chamfer_set> s(new (std::nothrow) canny_hip_chamfer_set());
+    if (!s) return CANNY_HIP_ERR_RUNTIME;
+    if ((rc = chamfer_build_layout(offsets, points, n_templates, s->lay))) return rc;
+    const ChamferLayout &L = s->lay;
+    const size_t b_off = L.offsets.size() * sizeof(int), b_pts = L.points.size() * sizeof(uint32_t);
+    const size_t b_box = L.boxes.size() * sizeof(ChamferBox), b_bo = L.band_offsets.size() * sizeof(int);
+    const size_t b_bands = L.bands.size() * sizeof(ChamferBand);
+    HIP_TRY(ctx, s->dev.ensure(b_off + b_pts + b_box + b_bo + b_bands));
+    char *p = (char *)s->dev.p;
+    s->d.offsets = (const int *)p;
+    s->d.points = (const uint32_t *)(p + b_off);
+    s->d.boxes = (const ChamferBox *)(p + b_off + b_pts);
+    s->d.band_offsets = (const int *)(p + b_off + b_pts + b_box);
+    s->d.bands = (const ChamferBand *)(p + b_off + b_pts + b_box + b_bo);
+    s->d.n_templates = L.n_templates;
+    s->d.max_elems = L.max_elems;
+    hipError_t e = hipMemcpyAsync((void *)s->d.offsets, L.offsets.data(), b_off, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync((void *)s->d.points, L.points.data(), b_pts, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync((void *)s->d.boxes, L.boxes.data(), b_box, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync((void *)s->d.band_offsets, L.band_offsets.data(), b_bo, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync((void *)s->d.bands, L.bands.data(), b_bands, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) {
+        s->dev.release();
+        return fail(ctx, e, "canny_hip_chamfer_set_create");
+    }
+    s->ctx = ctx;
+    ctx->chamfer_sets.push_back(s.get());
+    *set = s.release();
+    return CANNY_HIP_OK;
+}
+
+int canny_hip_chamfer_set_destroy(canny_hip_ctx *ctx, canny_hip_chamfer_set *set)
+{
+    if (!ctx || !set) return CANNY_HIP_ERR_INVALID;
+    // looked up before it is read: a destroyed or foreign handle is refused without touching its memory
+    auto it = std::find(ctx->chamfer_sets.begin(), ctx->chamfer_sets.end(), set);
+    if (it == ctx->chamfer_sets.end()) return CANNY_HIP_ERR_INVALID;
+    (void)hipSetDevice(ctx->device);
+    (void)hipStreamSynchronize(ctx->stream); // a queued launch may still read the set
+    ctx->chamfer_sets.erase(it);
+    set->dev.release();
+    delete set;
+    return CANNY_HIP_OK;
+}
+
+int canny_hip_dev_chamfer_dist2(canny_hip_ctx *ctx, const int *d_dist2, int n_frames, int height, int width,
+                                const canny_hip_chamfer_set *set, int trunc_q4, int max_mean_q4, int min_dist,
+                                int matches_max, int *d_matches, int *d_counts, int *d_cand_counts, unsigned int *d_scores)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!d_dist2) return CANNY_HIP_ERR_INVALID;
+    const ChamferArgs a{trunc_q4, max_mean_q4, min_dist, matches_max};
+    if ((rc = chamfer_check(ctx, height, width, n_frames, set, a, d_counts)) || (rc = finish_pending(ctx))) return rc;
+    return dev_chamfer(ctx, d_dist2, n_frames, height, width, set, a, ChamferOut{d_matches, d_counts, d_cand_counts, d_scores});
+}
+
+int canny_hip_dev_chamfer_bits(canny_hip_ctx *ctx, const unsigned char *d_bits, int n_frames, int height, int width,
+                               int *d_dist2, const canny_hip_chamfer_set *set, int trunc_q4, int max_mean_q4, int min_dist,
+                               int matches_max, int *d_matches, int *d_counts, int *d_cand_counts, unsigned int *d_scores)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!d_bits) return CANNY_HIP_ERR_INVALID;
+    const ChamferArgs a{trunc_q4, max_mean_q4, min_dist, matches_max};
+    if ((rc = chamfer_check(ctx, height, width, n_frames, set, a, d_counts)) ||
+        (rc = check_edt_dims(height, width, n_frames)) || (rc = finish_pending(ctx)))
+        return rc;
+    if (!d_dist2) {
+        HIP_TRY(ctx, ctx->chamfer_dist2.ensure(npx(height, width, n_frames) * sizeof(int)));
+        d_dist2 = (int *)ctx->chamfer_dist2.p;
+    }
+    if ((rc = dev_edt(ctx, nullptr, d_bits, make_hyst_geom(height, width, n_frames), EdtOut{d_dist2, nullptr, nullptr})))
+        return rc;
+    return dev_chamfer(ctx, d_dist2, n_frames, height, width, set, a, ChamferOut{d_matches, d_counts, d_cand_counts, d_scores});
+}
+
+int canny_hip_dev_canny_chamfer(canny_hip_ctx *ctx, const unsigned char *d_img, float sigma, int min_val, int max_val,
+                                int height, int width, int n_frames, short *d_edges, int *d_dist2,
+                                const canny_hip_chamfer_set *set, int trunc_q4, int max_mean_q4, int min_dist,
+                                int matches_max, int *d_matches, int *d_counts, int *d_cand_counts, unsigned int *d_scores)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!d_img) return CANNY_HIP_ERR_INVALID;
+    const ChamferArgs a{trunc_q4, max_mean_q4, min_dist, matches_max};
+    if ((rc = chamfer_check(ctx, height, width, n_frames, set, a, d_counts)) || (rc = check_edt_dims(height, width, n_frames)))
+        return rc;
+    if (!d_dist2) {
+        HIP_TRY(ctx, ctx->chamfer_dist2.ensure(npx(height, width, n_frames) * sizeof(int)));
+        d_dist2 = (int *)ctx->chamfer_dist2.p;
+    }
+    if ((rc = dev_canny_edt(ctx, d_img, sigma, min_val, max_val, height, width, n_frames, d_edges,
+                            EdtOut{d_dist2, nullptr, nullptr})))
+        return rc;
+    return dev_chamfer(ctx, d_dist2, n_frames, height, width, set, a, ChamferOut{d_matches, d_counts, d_cand_counts, d_scores});
+}
+
+int canny_hip_canny_chamfer(canny_hip_ctx *ctx, const unsigned char *imgs, int n_frames, float sigma, int min_val,
+                            int max_val, int height, int width, const canny_hip_chamfer_set *set, int trunc_q4,
+                            int max_mean_q4, int min_dist, int matches_max, int *matches, int *counts, int *cand_counts)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!imgs) return CANNY_HIP_ERR_INVALID;
+    const ChamferArgs a{trunc_q4, max_mean_q4, min_dist, matches_max};
+    if ((rc = chamfer_check(ctx, height, width, n_frames, set, a, counts)) || (rc = check_edt_dims(height, width, n_frames)))
+        return rc;
+    const size_t slots = (size_t)n_frames * matches_max;
+    // one staging block: records (6 ints per slot) | counts | candidate counts
+    HIP_TRY(ctx, ctx->io[1].ensure((slots * CANNY_HIP_MATCH_INTS + 2 * (size_t)n_frames) * sizeof(int)));
+    int *d_rec = (int *)ctx->io[1].p, *d_cnt = d_rec + slots * CANNY_HIP_MATCH_INTS;
+    if ((rc = h2d(ctx, ctx->io[0], imgs, npx(height, width, n_frames)))) return rc;
+    if ((rc = canny_hip_dev_canny_chamfer(ctx, (const unsigned char *)ctx->io[0].p, sigma, min_val, max_val, height, width,
+                                          n_frames, nullptr, nullptr, set, trunc_q4, max_mean_q4, min_dist, matches_max,
+                                          matches ? d_rec : nullptr, d_cnt, d_cnt + n_frames, nullptr)))
+        return rc;
+    std::vector<int> cnt(2 * (size_t)n_frames);
+    if ((rc = d2h_sync(ctx, cnt.data(), d_cnt, cnt.size() * sizeof(int)))) return rc;
+    for (int f = 0; matches && f < n_frames; f++) { // only the filled slots of each frame come down
+        const size_t k = (size_t)cnt[f], at = (size_t)f * matches_max * CANNY_HIP_MATCH_INTS;
+        if (k) HIP_TRY(ctx, hipMemcpyAsync(matches + at, d_rec + at, k * CANNY_HIP_MATCH_INTS * sizeof(int),
+                                          hipMemcpyDeviceToHost, ctx->stream));
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    std::memcpy(counts, cnt.data(), (size_t)n_frames * sizeof(int));
+    if (cand_counts) std::memcpy(cand_counts, cnt.data() + n_frames, (size_t)n_frames * sizeof(int));
+    return CANNY_HIP_OK;
+}
+
+// canny_hip_chamfer_from_dist2 and canny_hip_chamfer_cost_of, the rule in plain C++, live in canny_chamfer_host.cpp.
+
+int canny_hip_dev_chamfer_costs(canny_hip_ctx *ctx, const int *d_dist2, size_t n, int trunc_q4, unsigned int *d_costs)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!d_dist2 || !d_costs || !n || trunc_q4 < 0) return CANNY_HIP_ERR_INVALID;
+    if (trunc_q4 > CANNY_HIP_CHAMFER_MAX_TRUNC) return CANNY_HIP_ERR_UNSUPPORTED;
+    if ((rc = finish_pending(ctx))) return rc;
+    HIP_TRY(ctx, launch_chamfer_costs_hook(d_dist2, n, trunc_q4, d_costs, ctx->stream));
+    return CANNY_HIP_OK;
+}
+
+int canny_hip_chamfer_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches)
+{
+    if (part < 0 || part >= CANNY_HIP_CHAMFER_PARTS || !total_ms || !launches) return CANNY_HIP_ERR_INVALID;
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if ((rc = profile_collect(ctx))) return rc;
+    *total_ms = ctx->total_ms[canny_hip_ctx::kProfChamfer + part];
+    *launches = ctx->launches[canny_hip_ctx::kProfChamfer + part];
+    return CANNY_HIP_OK;
+}
+
+// Host-only: the launch plans of the capped chamfer launches for a full chunk of the batch.
+int canny_hip_selftest_chamfer_plan(int which, int n_frames, int height, int width, int n_templates, int with_scores,
+                                    unsigned long long *out)
+{
+    if (!out || check_dims(height, width, n_frames) || n_templates < 1 || n_templates > CANNY_HIP_CHAMFER_MAX_TEMPLATES ||
+        (long long)height * width * n_templates >= 0x80000000LL)
+        return CANNY_HIP_ERR_INVALID;
+    const int chunk = chamfer_chunk_frames(n_frames, height, width, n_templates, with_scores != 0);
+    LaunchPlan p;
+    if (which == CANNY_HIP_CHAMFER_PLAN_COST) p = plan_chamfer_cost((unsigned long long)chunk * height * width);
+    else if (which == CANNY_HIP_CHAMFER_PLAN_CELLS) p = plan_chamfer_cells((unsigned long long)height * width * n_templates);
+    else return CANNY_HIP_ERR_INVALID;
+    out[0] = p.units, out[1] = p.per_group, out[2] = p.grid, out[3] = p.trips(), out[4] = (unsigned long long)p.aux;
+    out[5] = (unsigned long long)chunk;
+    return CANNY_HIP_OK;
+}
+
+int canny_hip_selftest_chamfer_bands(const int *offsets, const short *points, int n_templates, int t, int *out)
+{
+    if (!out || t < 0) return CANNY_HIP_ERR_INVALID;
+    ChamferLayout lay;
+    const int rc = chamfer_build_layout(offsets, points, n_templates, lay);
+    if (rc) return rc;
+    if (t >= n_templates) return CANNY_HIP_ERR_INVALID;
+    const int cols = kChamferTileX + lay.boxes[(size_t)t].max_x - lay.boxes[(size_t)t].min_x;
+    out[0] = lay.band_offsets[(size_t)t + 1] - lay.band_offsets[(size_t)t];
+    out[1] = 0;
+    for (int b = lay.band_offsets[(size_t)t]; b < lay.band_offsets[(size_t)t + 1]; b++)
+        out[1] = std::max(out[1], lay.bands[(size_t)b].rows * cols);
+    out[2] = lay.max_elems;
+    out[3] = chamfer_auto_route(lay);
     return CANNY_HIP_OK;
 }
 

@@ -6,6 +6,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <vector>
+
 namespace canny {
 
 constexpr int kMaxCenter = 64;                 // Gaussian half-window (window <= 129)
@@ -657,6 +659,61 @@ LaunchPlan plan_to_gray(size_t n_px);              // to_gray_kernel: 16-pixel g
 // knows the lists).  edgels_arith_kernel: pairs or triples.  (Reported by canny_hip_selftest_edgels_plan, not by a kind.)
 LaunchPlan plan_edgels_at(int height, int width, unsigned long long n_points);
 LaunchPlan plan_edgels_arith(size_t n);
+
+// ---- chamfer template matching (canny_chamfer.hip) ----------------------
+// A template set as the kernels read it: the points of every template sorted by (dy, dx) and packed (dx in the low half,
+// dy in the high half of a word), per template its bounding box, and the bands of dy the tiled kernel walks: the points
+// [begin, end) of a band lie in rows dy0 .. dy0 + rows - kChamferTileY of the template, and rows * cols(t) u16 fit in LDS.
+constexpr int kChamferTileX = 64, kChamferTileY = 16; // anchors of one workgroup: a lane per column, 4 rows per lane
+constexpr int kChamferLdsElems = 32768;               // u16 elements of the tile with its halo: 64 KiB
+struct ChamferBox {
+    int min_x, max_x, min_y, max_y;
+};
+struct ChamferBand {
+    int begin, end, dy0, rows;
+};
+struct ChamferLayout {
+    int n_templates = 0;
+    std::vector<int> offsets;      // T + 1
+    std::vector<uint32_t> points;  // packed, sorted per template
+    std::vector<ChamferBox> boxes; // T
+    std::vector<int> band_offsets; // T + 1
+    std::vector<ChamferBand> bands;
+    int max_elems = 0;             // the largest rows * cols of any band
+    int max_k = 0;                 // the largest K_t
+};
+// Validates host template arrays (0 ok, 1 invalid, 2 unsupported: the values of CANNY_HIP_ERR_*) and lays them out.
+int chamfer_build_layout(const int *offsets, const short *points, int n_templates, ChamferLayout &out);
+// The route the automatic choice takes for a layout: 1 direct, 2 tiled.
+int chamfer_auto_route(const ChamferLayout &lay);
+struct ChamferSetDev { // device copies of a layout
+    const int *offsets;
+    const uint32_t *points;
+    const ChamferBox *boxes;
+    const int *band_offsets;
+    const ChamferBand *bands;
+    int n_templates, max_elems;
+};
+LaunchPlan plan_chamfer_cost(unsigned long long n_px);   // cost pass: pixels of the chunk
+LaunchPlan plan_chamfer_cells(unsigned long long cells); // direct score, histogram, collect: the T * h * w anchors of a frame
+// Frames of one chunk of the batch: at most 4096, and as many as keep the larger workspace of the chunk -- the scores, or
+// with the caller's score plane the u16 costs -- within budget_mb MiB (0: 256), one frame at least.
+int chamfer_chunk_frames(int n_frames, int height, int width, int n_templates, bool with_scores, int budget_mb = 0);
+// The candidate passes' workspace for a chunk of nf frames: histogram | state | collect counters | keys.
+size_t chamfer_ws_bytes(int nf, int matches_max);
+// cost: dist2 (n_px ints) -> u16 costs.  costs_hook: the same arithmetic (trunc_q4 >= 1) or the untruncated root (0) as u32.
+hipError_t launch_chamfer_cost(const int *dist2, size_t n_px, int trunc_q4, uint16_t *cost, hipStream_t stream);
+hipError_t launch_chamfer_costs_hook(const int *dist2, size_t n, int trunc_q4, unsigned *out, hipStream_t stream);
+// score: scores[f][t][y][x] for the nf frames of cost.  tiled: the LDS route, else one lane per anchor.
+hipError_t launch_chamfer_score(const uint16_t *cost, int nf, int height, int width, const ChamferSetDev &set, int trunc_q4,
+                                bool tiled, unsigned *scores, hipStream_t stream);
+// candidates + accept of nf frames: local minima under the threshold, the matches_max smallest keys (radix select over four
+// digit passes, then collect), sort and ordered acceptance.  ws: chamfer_ws_bytes(nf, matches_max), zeroed here.  matches,
+// counts, cand_counts: already offset to the chunk's first frame; matches and cand_counts may be null.
+hipError_t launch_chamfer_candidates(const unsigned *scores, int nf, int height, int width, const ChamferSetDev &set,
+                                     int max_mean_q4, int matches_max, void *ws, int *cand_counts, hipStream_t stream);
+hipError_t launch_chamfer_accept(const unsigned *scores, int nf, int height, int width, int n_templates, int matches_max,
+                                 int min_dist, void *ws, int *matches, int *counts, hipStream_t stream);
 
 // ---- measurement aid ------------------------------------------------------------------------
 // Plain device copy of nbytes (multiple of 16; both pointers 16-byte aligned): what a 1:1 read/write stream reaches.

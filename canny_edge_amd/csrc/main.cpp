@@ -45,6 +45,10 @@
 // (canny_hip_canny_hough_circle_fits) and writes one "frame cx cy r n rms maxd sectors trim_failed degenerate" row per
 // circle to canny_circle_fits.txt.  -k without -r, or with a band outside 0..4, a negative trim or options outside 0..3, is
 // a usage error (exit 2).
+// Added: -x a.pgm[:b.pgm...],trunc_q4,max_mean_q4,min_dist matches the frame's edge map against the shapes of the PGM files
+// (their non-zero pixels, anchored at the centre) on the GPU (canny_hip_canny_chamfer) and writes one "frame x y template
+// score mean" row per match, in order, to canny_matches.txt in the -o directory (stdout without -o); mean is the mean
+// cost in pixels to four decimals.  A malformed -x is a usage error (exit 2).  Without -x nothing changes.
 // Added: -e computes the sub-pixel edgel of every pixel of the frame's edge map on the GPU (canny_hip_canny_edgels) and
 // writes one "x y gx gy mag dir refined" row per edge pixel, in raster order, to canny_edgels.txt in the -o directory
 // (stdout without -o): x and y in pixels to three decimals, mag in grey levels, dir 0..3 (step (1,0), (1,1), (0,1), (1,-1)),
@@ -597,6 +601,57 @@ static int run_circles(const vector<unsigned char> &frame, int height, int width
     return 0;
 }
 
+// -x: chamfer matching of the frame's edge map against the shapes of PGM files (their non-zero pixels, anchored at the
+// centre), "frame x y template score mean" per match, in order; mean in pixels
+static int run_chamfer(const vector<unsigned char> &frame, int height, int width, float sigma, int minVal, int maxVal,
+                       const vector<string> &shapes, const int *a, const string &outdir)
+{
+    vector<int> offsets(1, 0);
+    vector<short> points;
+    for (const string &path : shapes) {
+        vector<unsigned char> px;
+        int h = 0, w = 0;
+        if (!read_pgm(path, px, h, w)) {
+            fprintf(stderr, "ERROR: -x: cannot read %s as a binary PGM\n", path.c_str());
+            return 1;
+        }
+        for (int y = 0; y < h; y++)
+            for (int x = 0; x < w; x++)
+                if (px[(size_t)y * w + x]) {
+                    points.push_back((short)(x - w / 2));
+                    points.push_back((short)(y - h / 2));
+                }
+        offsets.push_back((int)(points.size() / 2));
+    }
+    const int matches_max = 256;
+    vector<int> rec((size_t)matches_max * CANNY_HIP_MATCH_INTS);
+    int count = 0;
+    canny_hip_ctx *ctx = nullptr;
+    canny_hip_chamfer_set *set = nullptr;
+    int st = canny_hip_ctx_create(&ctx, 0);
+    if (!st) st = canny_hip_chamfer_set_create(ctx, offsets.data(), points.data(), (int)shapes.size(), &set);
+    if (!st)
+        st = canny_hip_canny_chamfer(ctx, frame.data(), 1, sigma, minVal, maxVal, height, width, set, a[0], a[1], a[2],
+                                     matches_max, rec.data(), &count, nullptr);
+    if (st) {
+        fprintf(stderr, "ERROR: -x: %s\n", st == CANNY_HIP_ERR_RUNTIME && ctx ? canny_hip_last_error(ctx) : canny_hip_status_string(st));
+        if (ctx) canny_hip_ctx_destroy(ctx);
+        return 1;
+    }
+    canny_hip_ctx_destroy(ctx); // the set dies with its context
+    FILE *f = outdir.empty() ? stdout : fopen((outdir + "/canny_matches.txt").c_str(), "w");
+    if (!f) {
+        fprintf(stderr, "ERROR: cannot write %s/canny_matches.txt\n", outdir.c_str());
+        return 1;
+    }
+    for (int j = 0; j < count; j++) {
+        const int *m = rec.data() + (size_t)j * CANNY_HIP_MATCH_INTS;
+        fprintf(f, "0 %d %d %d %d %.4f\n", m[0], m[1], m[2], m[3], m[4] / 4096.0);
+    }
+    if (f != stdout) fclose(f);
+    return 0;
+}
+
 int main(int argc, char *argv[])
 {
     // The batch pipeline wants its upload, compute and download streams on separate hardware queues; HIP reads this
@@ -625,6 +680,8 @@ int main(int argc, char *argv[])
     int circle_args[6] = {0, 0, 0, 0, 0, 0}; // min_radius, max_radius, threshold, support, min_dist, cell_shift
     bool want_circle_fits = false;
     int circle_fit_args[3] = {0, 0, 0}; // -k: band, trim_q8, options
+    vector<string> chamfer_shapes;      // -x: the PGM files of the shapes
+    int chamfer_args[3] = {0, 0, 0};    // ... trunc_q4, max_mean_q4, min_dist
     int width = WIDTH, height = HEIGHT;
     vector<string> values;
 
@@ -708,6 +765,37 @@ int main(int argc, char *argv[])
                 exit(2);
             }
             want_circle_fits = true;
+        } else if (arg == "-x" && i + 1 < argc) {
+            // a.pgm[:b.pgm...],trunc_q4,max_mean_q4,min_dist: the last three commas separate whole integers
+            const string spec = argv[++i];
+            size_t cut[3];
+            size_t at = string::npos;
+            bool clean = true;
+            for (int k = 2; k >= 0 && clean; k--) {
+                at = spec.rfind(',', at == string::npos ? at : at - 1);
+                clean = at != string::npos && at > 0;
+                cut[k] = at;
+            }
+            for (int k = 0; k < 3 && clean; k++) {
+                const string v = spec.substr(cut[k] + 1, (k < 2 ? cut[k + 1] : spec.size()) - cut[k] - 1);
+                char *end = nullptr;
+                const long n = strtol(v.c_str(), &end, 10);
+                clean = !v.empty() && *end == '\0' && !isspace((unsigned char)v[0]) && n >= 0 && n <= 0x7fffffffL;
+                chamfer_args[k] = (int)n;
+            }
+            chamfer_shapes.clear();
+            for (size_t b = 0; clean && b <= cut[0];) {
+                size_t e = spec.find(':', b);
+                if (e == string::npos || e > cut[0]) e = cut[0];
+                clean = e > b;
+                chamfer_shapes.push_back(spec.substr(b, e - b));
+                b = e + 1;
+            }
+            if (!clean || chamfer_shapes.empty() || chamfer_args[0] < 1 || chamfer_args[0] > CANNY_HIP_CHAMFER_MAX_TRUNC ||
+                chamfer_args[1] >= chamfer_args[0]) {
+                fprintf(stderr, "ERROR: -x expects a.pgm[:b.pgm...],trunc_q4,max_mean_q4,min_dist: 1/16 px, 1 <= trunc_q4 <= 4095, max_mean_q4 < trunc_q4\n");
+                exit(2);
+            }
         } else if (arg == "-y" && i + 1 < argc) {
             // one or two non-negative numbers, nothing empty, nothing behind the last one
             double v[2] = {0.0, 0.0};
@@ -789,6 +877,9 @@ int main(int argc, char *argv[])
         fprintf(stderr, "   -k band,trim_q8[,options]: with -r, the sub-pixel circle fit of every circle (band 0..4 bins each side, trim_q8 in\n");
         fprintf(stderr, "       1/256 px or 0, options 0..3: 1 = gate by gradient direction, 2 = refined edgels only), one \"frame cx cy r n rms\n");
         fprintf(stderr, "       maxd sectors trim_failed degenerate\" line each (pixels; sectors in hex) -> canny_circle_fits.txt in the -o dir\n");
+        fprintf(stderr, "   -x a.pgm[:b.pgm...],trunc_q4,max_mean_q4,min_dist: chamfer matching of the edge map against the shapes of the\n");
+        fprintf(stderr, "       PGM files (non-zero pixels, anchored at the centre; costs in 1/16 px), one \"frame x y template score mean\"\n");
+        fprintf(stderr, "       line per match (mean in pixels) -> canny_matches.txt in the -o dir\n");
         fprintf(stderr, "   -d: distance of every pixel to the nearest edge pixel, min(255, floor) -> canny_dist.pgm in the -o dir\n");
         fprintf(stderr, "   -e: sub-pixel edgel of every edge pixel, one \"x y gx gy mag dir refined\" line each (x, y in pixels to three\n");
         fprintf(stderr, "       decimals, mag in grey levels, dir 0..3) -> canny_edgels.txt in the -o dir\n");
@@ -864,6 +955,10 @@ int main(int argc, char *argv[])
     }
     if (want_dist) {
         const int rc = run_edt(frame, height, width, sigma, minVal, maxVal, outdir);
+        if (rc) return rc;
+    }
+    if (!chamfer_shapes.empty()) {
+        const int rc = run_chamfer(frame, height, width, sigma, minVal, maxVal, chamfer_shapes, chamfer_args, outdir);
         if (rc) return rc;
     }
     if (want_circles) {

@@ -52,7 +52,8 @@
 extern "C" {
 #endif
 
-#define CANNY_HIP_VERSION 1500       /* 0.15.0: + sub-pixel circle fits: least-squares refit of Hough circles from edgels */
+#define CANNY_HIP_VERSION 1600       /* 0.16.0: + chamfer template matching on the distance transform */
+/* 0.15.0: + sub-pixel circle fits: least-squares refit of Hough circles from edgels */
 /* 0.13.0: + sub-pixel edgels: position, gradient and strength per edge pixel */
 /* 0.12.2: + canny_hip_selftest_launch_plan */
 /* 0.12.1: + canny_hip_selftest_workspace */
@@ -1373,6 +1374,111 @@ int canny_hip_canny_edt(canny_hip_ctx *ctx, const unsigned char *imgs, int n_fra
  * canny_hip_canny_batch_bits runs on the maps it received. */
 int canny_hip_edt_from_bits(const unsigned char *bits, int height, int width, int *dist2, float *dist, int *nearest);
 
+/* ---- chamfer template matching -------------------------------------------------------------------------------------------
+ * Where does a given shape sit in a frame?  Given a set of point templates, every finished edge map gets, per frame, the
+ * truncated chamfer score of every template at every anchor, its local minima under a mean-cost threshold, and an ordered,
+ * distance-suppressed list of matches -- on the GPU behind the distance transform, on the same stream, with no host round
+ * trip.  All integers: the same bytes on every run and every machine.  tests/chamfer_rule.py restates the rule in numpy,
+ * csrc/canny_chamfer_host.cpp in plain C++.  THE RULE:
+ *   Templates: a set of T templates, 1 <= T <= CANNY_HIP_CHAMFER_MAX_TEMPLATES, CSR-shaped: offsets holds T + 1 ints,
+ *     offsets[0] = 0, non-decreasing; points holds offsets[T] pairs of shorts (dx, dy) = (column offset, row offset) from the
+ *     template's anchor.  Template t has K_t = offsets[t + 1] - offsets[t] points, 1 <= K_t <= 65536; offsets[T] <= 2^20;
+ *     |dx|, |dy| <= CANNY_HIP_CHAMFER_MAX_EXTENT.  Duplicates are allowed and count as often as they occur.  (The sum below is
+ *     an integer sum: the set stores the points in the order its kernels like.)
+ *   Cost: cost(d2) = min(isqrt(d2 * 256), trunc_q4): isqrt is the floor integer square root of the 64-bit product, i.e. the
+ *     distance in 1/16 pixel, truncated; 1 <= trunc_q4 <= 4095.  d2 = CANNY_HIP_EDT_NONE gives trunc_q4 (isqrt(2^39) > 4095),
+ *     so a frame with an empty map -- max_val > 255 included: the result follows the MAP -- costs trunc_q4 everywhere.
+ *   Score, for frame f, template t and anchor (y, x) anywhere in the frame:
+ *     S[f][t][y][x] = sum over the template's points k of cost_f(y + dy_k, x + dx_k),
+ *     where a point that falls outside the frame contributes trunc_q4.  S <= 4095 * 65536 < 2^28.
+ *   Candidates: (t, y, x) is a candidate iff
+ *     1. S <= max_mean_q4 * K_t, the mean-cost threshold in 1/16 pixel, 0 <= max_mean_q4 < trunc_q4 (the strict bound keeps
+ *        saturated plateaus out), and
+ *     2. S is a five-way local minimum in its own template's plane, mirroring the Hough peak rule:
+ *        S < left && S <= right && S < up && S <= down, neighbours outside the frame counting as +infinity (on a plateau
+ *        the first pixel in raster order wins).
+ *   Order: mean_q12 = floor(S * 256 / K_t) (64 bits); base = t * height * width + y * width + x, with
+ *     T * height * width < 2^31 (beyond: CANNY_HIP_ERR_UNSUPPORTED).  The candidates are sorted by (mean_q12 ascending, base
+ *     ascending); the first min(matches_max, n_candidates) go on, 1 <= matches_max <= CANNY_HIP_HOUGH_MAX_LINES.
+ *   Acceptance (the pattern of the circles): the candidates are taken in that order; one is accepted iff no earlier ACCEPTED
+ *     one, of whatever template, has (dx)^2 + (dy)^2 < min_dist^2.  min_dist >= 0; 0 disables the check.
+ *   Output: frame f writes its accepted matches compactly, in that order, to slots f * matches_max + j of matches; a match is
+ *     CANNY_HIP_MATCH_INTS = 6 ints: x, y, template, score, mean_q12, base.  counts[f] (mandatory) is the number accepted,
+ *     cand_counts[f] (may be NULL) the true number of candidates; later slots are not written.  matches may be NULL (counts
+ *     only).  d_scores, if given, is [n][T][height][width] unsigned ints and receives every S; what the other outputs hold
+ *     does not depend on whether it is given.
+ *   Statuses: bad ranges (trunc_q4 < 1, max_mean_q4 outside 0 .. trunc_q4 - 1, min_dist < 0, matches_max < 1, sizes < 1),
+ *     NULL mandatory pointers, a bad template set (offsets[0] != 0, a template without points, no template; for the device
+ *     forms a set of another context or a destroyed one): CANNY_HIP_ERR_INVALID; over a documented limit (trunc_q4 > 4095,
+ *     matches_max > CANNY_HIP_HOUGH_MAX_LINES, more than 1024 templates, 65536 points in one or 2^20 in all, a point of
+ *     extent 256, T * height * width >= 2^31, and for the device forms height or width > 65535):
+ *     CANNY_HIP_ERR_UNSUPPORTED; both before anything is queued, nothing is written.  Otherwise the detector's or the
+ *     transform's own status comes first.  A dist2 word is read as unsigned: a negative one costs trunc_q4.
+ *   The context option "chamfer_route" chooses the score kernel: 0 automatic, 1 direct (one lane per anchor, costs gathered
+ *     from the cost plane in memory), 2 tiled (the cost tile with the template's halo in LDS).  Same bytes either way.
+ * Memory: the batch is walked in CHUNKS of whole frames, a function of the shapes alone: at most 4096 frames, and no more
+ *   than keep the larger per-chunk workspace within 256 MiB (one frame at least, whatever it takes).  That workspace is
+ *   the scores, 4 B per template and pixel, or, with d_scores given, the u16 cost plane, 2 B per pixel (which is there in
+ *   both cases).  A third workspace holds, per frame of the chunk, the cut-off's histogram and the collected keys:
+ *   32 KiB + 8 * matches_max bytes, 256 MiB at 4096 frames and 4096 matches.  With d_dist2 == NULL the canny and bits forms
+ *   keep the dist2 plane of the WHOLE batch in a fourth, 4 B per pixel.
+ * The four parts are timed by canny_hip_chamfer_profile_get (CANNY_HIP_CHAMFER_PART_*); with "profile_stage_mask" they go
+ *   by bit 30 like every part behind the polygons.
+ * Not covered -- follow-ups: oriented chamfer (the edgels' directions), anchor strides and coarse-to-fine search, sub-pixel
+ * match refinement, the three-stream batch pipeline, the multi-GPU sharder, colour and per-frame-threshold variants. */
+#define CANNY_HIP_CHAMFER_MAX_EXTENT 255
+#define CANNY_HIP_CHAMFER_MAX_TEMPLATES 1024
+#define CANNY_HIP_CHAMFER_MAX_POINTS 65536      /* per template */
+#define CANNY_HIP_CHAMFER_MAX_TOTAL (1 << 20)   /* points of a set */
+#define CANNY_HIP_CHAMFER_MAX_TRUNC 4095
+#define CANNY_HIP_MATCH_INTS 6
+enum canny_hip_chamfer_part {
+    CANNY_HIP_CHAMFER_PART_COST = 0,        /* dist2 -> u16 cost plane */
+    CANNY_HIP_CHAMFER_PART_SCORE = 1,       /* the sliding sums */
+    CANNY_HIP_CHAMFER_PART_CANDIDATES = 2,  /* local minima, cut-off (radix select on the keys), collect */
+    CANNY_HIP_CHAMFER_PART_ACCEPT = 3,      /* sort + ordered acceptance, one workgroup per frame */
+    CANNY_HIP_CHAMFER_PARTS = 4
+};
+typedef struct canny_hip_chamfer_set canny_hip_chamfer_set;
+/* Validates, uploads once and precomputes what the launches need (K_t, bounding boxes, the points sorted by (dy, dx) and
+ * cut into bands of dy whose halo fits in LDS).  A set belongs to its context and dies with it at the latest; destroy
+ * synchronises the context's stream first.  Synchronous. */
+int canny_hip_chamfer_set_create(canny_hip_ctx *ctx, const int *offsets, const short *points, int n_templates,
+                                 canny_hip_chamfer_set **set);
+int canny_hip_chamfer_set_destroy(canny_hip_ctx *ctx, canny_hip_chamfer_set *set);
+/* Matching alone on a device dist2 plane ([n][height][width] ints, what canny_hip_dev_canny_edt writes).  Any height,
+ * width >= 1.  Asynchronous. */
+int canny_hip_dev_chamfer_dist2(canny_hip_ctx *ctx, const int *d_dist2, int n_frames, int height, int width,
+                                const canny_hip_chamfer_set *set, int trunc_q4, int max_mean_q4, int min_dist,
+                                int matches_max, int *d_matches, int *d_counts, int *d_cand_counts, unsigned int *d_scores);
+/* canny_hip_dev_edt_bits unchanged, then the matching.  d_dist2 may be the caller's plane or NULL (a workspace then). */
+int canny_hip_dev_chamfer_bits(canny_hip_ctx *ctx, const unsigned char *d_bits, int n_frames, int height, int width,
+                               int *d_dist2, const canny_hip_chamfer_set *set, int trunc_q4, int max_mean_q4, int min_dist,
+                               int matches_max, int *d_matches, int *d_counts, int *d_cand_counts, unsigned int *d_scores);
+/* canny_hip_dev_canny_edt unchanged (d_edges, d_dist2 as there; either may be NULL), then the matching, on the same
+ * stream. */
+int canny_hip_dev_canny_chamfer(canny_hip_ctx *ctx, const unsigned char *d_img, float sigma, int min_val, int max_val,
+                                int height, int width, int n_frames, short *d_edges, int *d_dist2,
+                                const canny_hip_chamfer_set *set, int trunc_q4, int max_mean_q4, int min_dist,
+                                int matches_max, int *d_matches, int *d_counts, int *d_cand_counts, unsigned int *d_scores);
+/* Host buffers, synchronous, in the pattern of canny_hip_canny_hough_circles: the counts come down first, then only the
+ * filled slots of matches.  matches and cand_counts may be NULL. */
+int canny_hip_canny_chamfer(canny_hip_ctx *ctx, const unsigned char *imgs, int n_frames, float sigma, int min_val,
+                            int max_val, int height, int width, const canny_hip_chamfer_set *set, int trunc_q4,
+                            int max_mean_q4, int min_dist, int matches_max, int *matches, int *counts, int *cand_counts);
+/* Host-only, needs no device: the rule on ONE host dist2 plane with host template arrays, in plain C++.  matches
+ * (matches_max * 6 ints; only the accepted records are written) and cand_count may be NULL; scores, if given, receives
+ * n_templates * height * width unsigned ints. */
+int canny_hip_chamfer_from_dist2(const int *dist2, int height, int width, const int *offsets, const short *points,
+                                 int n_templates, int trunc_q4, int max_mean_q4, int min_dist, int matches_max,
+                                 int *matches, int *count, int *cand_count, unsigned int *scores);
+/* Host-only: cost(d2) of the rule; -1 for d2 < 0 or trunc_q4 outside 1..4095. */
+int canny_hip_chamfer_cost_of(int d2, int trunc_q4);
+/* Test hook: the device's cost arithmetic alone on n dist2 values; d_costs receives n unsigned ints.  trunc_q4 in
+ * 1..4095 runs the cost pass's own function; trunc_q4 = 0 stores the untruncated root isqrt(d2 * 256), which the device
+ * takes in floating point and corrects to the exact integer root.  Asynchronous. */
+int canny_hip_dev_chamfer_costs(canny_hip_ctx *ctx, const int *d_dist2, size_t n, int trunc_q4, unsigned int *d_costs);
+
 /* ---- per-stage HIP-event timing (events are recorded on the launch stream) ----------------- */
 int canny_hip_profile_enable(canny_hip_ctx *ctx, int on);
 int canny_hip_profile_reset(canny_hip_ctx *ctx);
@@ -1399,6 +1505,8 @@ int canny_hip_edgels_profile_get(canny_hip_ctx *ctx, int part, double *total_ms,
 int canny_hip_line_fits_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches);
 /* ... and for the one part of the circle fits (CANNY_HIP_CIRCLE_FIT_PART_*). */
 int canny_hip_circle_fits_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches);
+/* ... and for the four parts of the chamfer matching (CANNY_HIP_CHAMFER_PART_*). */
+int canny_hip_chamfer_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches);
 
 /* ---- self-test hooks used by the GPU test-suite -------------------------------------------- */
 /* Runs the DEVICE magnitude / angle-bin functions over every (gx,gy) in [-lim,lim]^2 and writes
@@ -1514,6 +1622,21 @@ int canny_hip_selftest_launch_plan(int kind, int n_frames, int height, int width
  * device knows the lists; n_points >= 1 is the list length of ONE frame, the items the loop walks. */
 int canny_hip_selftest_edgels_plan(int n_frames, int height, int width, unsigned long long n_points,
                                    unsigned long long *out);
+/* Host-only, the same five outputs for the capped launches of the chamfer matching (they have no kind above).  The batch is
+ * walked in chunks of out[5] frames (see the section's Memory note); the plans are those of a full chunk:
+ *   CANNY_HIP_CHAMFER_PLAN_COST:  the cost pass, items = the chunk's pixels, grid (out[2]);
+ *   CANNY_HIP_CHAMFER_PLAN_CELLS: the direct score kernel and the candidate passes (histogram, collect), items = the
+ *     n_templates * height * width anchors of ONE frame, grid (out[2], frames of the chunk).
+ * The tiled score kernel's grid is (16 x 64 tiles of a frame, templates, frames of the chunk) and has no cap.
+ * with_scores != 0: the caller passes d_scores (the cost plane, not the score workspace, limits the chunk). */
+enum canny_hip_chamfer_plan { CANNY_HIP_CHAMFER_PLAN_COST = 0, CANNY_HIP_CHAMFER_PLAN_CELLS = 1 };
+int canny_hip_selftest_chamfer_plan(int which, int n_frames, int height, int width, int n_templates, int with_scores,
+                                    unsigned long long *out);
+/* Host-only: how the tiled score kernel walks template t of the set these host arrays describe (validated as by
+ * canny_hip_chamfer_set_create, which lays its set out with the same function): out[0] = bands of dy, out[1] = the
+ * largest LDS tile of a band of t in u16 elements, out[2] = the largest of the whole set (the launch's LDS), out[3] = the
+ * route the automatic choice takes for the set (1 direct, 2 tiled). */
+int canny_hip_selftest_chamfer_bands(const int *offsets, const short *points, int n_templates, int t, int *out);
 
 #ifdef __cplusplus
 }
