@@ -128,6 +128,8 @@ EXPORTS = (
     "canny_hip_dev_chamfer_bits", "canny_hip_dev_canny_chamfer", "canny_hip_canny_chamfer", "canny_hip_chamfer_from_dist2",
     "canny_hip_chamfer_cost_of", "canny_hip_dev_chamfer_costs", "canny_hip_chamfer_profile_get",
     "canny_hip_selftest_chamfer_plan", "canny_hip_selftest_chamfer_bands",
+    "canny_hip_dev_shapes_chains", "canny_hip_dev_canny_shapes", "canny_hip_dev_shapes_bits", "canny_hip_canny_shapes",
+    "canny_hip_shapes_from_chains", "canny_hip_shapes_profile_get", "canny_hip_selftest_shapes_plan",
 )
 
 _lib: Optional[C.CDLL] = None
@@ -324,6 +326,13 @@ def load() -> C.CDLL:
         "canny_hip_chamfer_profile_get": ([p, i, C.POINTER(C.c_double), C.POINTER(C.c_long)], i),
         "canny_hip_selftest_chamfer_plan": ([i, i, i, i, i, i, p], i),
         "canny_hip_selftest_chamfer_bands": ([p, p, i, i, p], i),
+        "canny_hip_dev_shapes_chains": ([p, p, i, ull, p, p, ull, i, i, p, p, ull, p], i),
+        "canny_hip_dev_canny_shapes": ([p, p, f, i, i, i, i, i, p, i, p, ull, p, p, p, ull, p, p, p, ull, p], i),
+        "canny_hip_dev_shapes_bits": ([p, p, i, i, i, i, p, ull, p, p, p, ull, p, p, p, ull, p], i),
+        "canny_hip_canny_shapes": ([p, p, i, f, i, i, i, i, i, p, ull, p, p, p, ull, p, p, p, ull, p], i),
+        "canny_hip_shapes_from_chains": ([p, p, ull, ull, i, i, p, p, ull, p], i),
+        "canny_hip_shapes_profile_get": ([p, i, C.POINTER(C.c_double), C.POINTER(C.c_long)], i),
+        "canny_hip_selftest_shapes_plan": ([i, ull, p], i),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -488,6 +497,78 @@ def polygons_from_chains(chain_offsets, points, width: int, height: int, epsilon
     verts = np.empty(vcap, np.int32)
     call(verts, vcap)
     return voff, verts[:min(vcap, int(voff[-1]))], measures
+
+
+SHAPE_PARTS = ("measure", "scan", "emit")
+SHAPE_WORDS = 20
+SHAPE_MEASURES = ("hull_vertices", "points", "anchor", "area2", "m10_6", "m01_6", "m20_12", "m11_24", "m02_12", "s10", "s01",
+                  "s20", "s11", "s02", "hull_area2", "rect_edge", "rect_along_min", "rect_along_max", "rect_across",
+                  "rect_len2")
+SHAPES_PLANS = {"records": 0, "scan_sums": 1}
+
+
+def shapes_from_chains(chain_offsets, points, width: int, height: int, point_capacity: Optional[int] = None,
+                       hull_capacity: Optional[int] = None, want_measures: bool = True):
+    """Host-only: the shape measures of every chain.  chain_offsets uint64 [k + 1] and points int32
+    are what contours_from_bits / Context.canny_contours return.  Returns (hull_offsets uint64 [k + 1], hull int32,
+    measures int64 [k, 20] or None): record j's convex hull is hull[hull_offsets[j] : hull_offsets[j + 1]], pixel indices
+    r * width + c from the leftmost vertex on, and measures[j] holds the words named in SHAPE_MEASURES.  point_capacity
+    (default: len(points)) says which chains are complete: one that ends beyond it has no hull and the measures
+    (-1, 0, ...).  With hull_capacity given, hull holds the positions below it and hull_offsets are still the true counts."""
+    co = np.ascontiguousarray(chain_offsets, dtype=np.uint64)
+    pts = np.ascontiguousarray(points, dtype=np.int32)
+    k = co.size - 1
+    if k < 0:
+        raise ValueError("chain_offsets needs at least one entry")
+    pcap = pts.size if point_capacity is None else int(point_capacity)
+    if pcap > pts.size:
+        raise ValueError("point_capacity exceeds the points given")
+    L = load()
+    hoff = np.zeros(k + 1, np.uint64)
+    measures = np.zeros((k, SHAPE_WORDS), np.int64) if want_measures else None
+
+    def call(hull, hcap):
+        st = L.canny_hip_shapes_from_chains(_hp(co), _hp(pts) if pts.size else None, k, pcap, width, height, _hp(hoff),
+                                            _hp(hull) if hcap else None, hcap,
+                                            _hp(measures) if want_measures and k else None)
+        if st:
+            raise CannyHipError(st, "shapes_from_chains")
+
+    if hull_capacity is None:
+        call(None, 0)
+    hcap = int(hoff[-1]) if hull_capacity is None else int(hull_capacity)
+    hull = np.empty(hcap, np.int32)
+    call(hull, hcap)
+    return hoff, hull[:min(hcap, int(hoff[-1]))], measures
+
+
+def shape_rectangle(measures_row, hull, width: int):
+    """The minimum-area rectangle of one record as floats: (corners [4, 2] as (x, y), (length, breadth), angle in radians of
+    the side on the hull edge), from the exact words of measures_row and the record's hull (pixel indices).  A hull of one
+    vertex gives that point four times."""
+    m = [int(v) for v in measures_row]
+    hx, hy = [int(q) % width for q in hull], [int(q) // width for q in hull]
+    v = len(hx)
+    if v == 0:
+        raise ValueError("the record has no hull")
+    k, lo, hi, across, len2 = m[15:20]
+    if v == 1 or len2 == 0:
+        return np.array([[hx[0], hy[0]]] * 4, float), (0.0, 0.0), 0.0
+    ax, ay = hx[k], hy[k]
+    dx, dy = hx[(k + 1) % v] - ax, hy[(k + 1) % v] - ay
+    nx, ny = -dy, dx                     # cross(d, n) = len2 > 0: the side the hull lies on
+    c = [(ax + (a * dx + b * nx) / len2, ay + (a * dy + b * ny) / len2) for a, b in ((lo, 0), (hi, 0), (hi, across), (lo, across))]
+    return np.array(c, float), ((hi - lo) / len2 ** 0.5, across / len2 ** 0.5), float(np.arctan2(dy, dx))
+
+
+def shapes_plan(which, capacity: int) -> "LaunchPlan":
+    """Host-only: the launch plan of a capped launch of the shape stage ("records": the measure and the emit kernel,
+    "scan_sums": the scan's pass over its chunks) at a record capacity; fields as launch_plan."""
+    out = np.zeros(5, np.uint64)
+    st = load().canny_hip_selftest_shapes_plan(SHAPES_PLANS.get(which, which), int(capacity), _hp(out))
+    if st:
+        raise CannyHipError(st, "selftest_shapes_plan")
+    return LaunchPlan(*(int(v) for v in out))
 
 
 EDT_NONE = 0x7FFFFFFF                                           # CANNY_HIP_EDT_NONE: dist2 of a frame without edge pixels
@@ -1511,6 +1592,82 @@ class Context:
         ms, n = C.c_double(0.0), C.c_long(0)
         self._check(self._L.canny_hip_polygons_profile_get(self._h, part, C.byref(ms), C.byref(n)),
                     "polygons_profile_get")
+        return ms.value, n.value
+
+    # ---- contour shape measures ------------------------------------------------------------
+    def canny_shapes(self, imgs, sigma: float, min_val: int, max_val: int, min_area: int = 1, want_stats: bool = False,
+                     want_points: bool = False):
+        """canny(), the outer contour chains, then the shape measures of every chain: imgs (H, W) or (N, H, W) uint8 ->
+        (hulls, measures int64 [K, 20], offsets uint64 [N + 1], extra).  hulls is a list of K int32 arrays, views into one
+        array through the CSR, record j (offsets[f] <= j < offsets[f + 1] for frame f) holding its convex hull as pixel
+        indices r * W + c; measures[j] holds the words named in SHAPE_MEASURES.  extra is a dict with hull_offsets, hull,
+        point_offsets, chain_offsets, and stats / points when asked for.  Unless want_points, the chains never leave the
+        device."""
+        a = np.ascontiguousarray(imgs, dtype=np.uint8)
+        if a.ndim == 2:
+            a = a[None]
+        if a.ndim != 3:
+            raise ValueError("expected uint8 [H, W] or [n_frames, H, W]")
+        n, h, w = a.shape
+        offsets, point_offsets = np.zeros(n + 1, np.uint64), np.zeros(n + 1, np.uint64)
+        sized = self.canny_contours(a, sigma, min_val, max_val, min_area, want_stats=False, capacity=0, point_capacity=0)
+        cap, pcap = int(sized[1][-1]), int(sized[4][-1])
+        stats = np.empty((cap, CC_STATS), np.int32) if want_stats else None
+        chain = np.zeros(cap + 1, np.uint64)
+        points = np.empty(pcap, np.int32) if want_points else None
+        hoff = np.zeros(cap + 1, np.uint64)
+        hull = np.empty(pcap, np.int32)   # a hull has no more vertices than its chain has points
+        measures = np.zeros((cap, SHAPE_WORDS), np.int64)
+        self._check(self._L.canny_hip_canny_shapes(
+            self._h, _hp(a), n, sigma, min_val, max_val, h, w, min_area, _hp(stats) if want_stats and cap else None, cap,
+            _hp(offsets), _hp(chain), _hp(points) if want_points and pcap else None, pcap, _hp(point_offsets),
+            _hp(hoff), _hp(hull) if pcap else None, pcap, _hp(measures) if cap else None), "canny_shapes")
+        hull = hull[:int(hoff[-1])]
+        hulls = [hull[int(hoff[j]):int(hoff[j + 1])] for j in range(cap)]
+        extra = dict(hull_offsets=hoff, hull=hull, point_offsets=point_offsets, chain_offsets=chain)
+        if want_stats:
+            extra["stats"] = stats
+        if want_points:
+            extra["points"] = points
+        return hulls, measures, offsets, extra
+
+    def dev_shapes_chains(self, d_offsets: int, n: int, capacity: int, d_chain_offsets: int, d_points: int,
+                          point_capacity: int, w: int, h: int, d_hull_offsets: int, d_hull: int, hull_capacity: int,
+                          d_measures: int = 0):
+        """The shape stage alone on chains a contours call left on the device: d_hull_offsets (capacity + 1 uint64), d_hull
+        (hull_capacity int32) or 0 with hull_capacity 0, d_measures (capacity x 20 int64) or 0."""
+        v = C.c_void_p
+        self._check(self._L.canny_hip_dev_shapes_chains(self._h, v(d_offsets or None), n, capacity,
+                                                        v(d_chain_offsets or None), v(d_points or None), point_capacity,
+                                                        w, h, v(d_hull_offsets or None), v(d_hull or None), hull_capacity,
+                                                        v(d_measures or None)), "dev_shapes_chains")
+
+    def dev_canny_shapes(self, d_img: int, sigma: float, min_val: int, max_val: int, h: int, w: int, n: int,
+                         min_area: int, d_stats: int, capacity: int, d_offsets: int, d_chain_offsets: int, d_points: int,
+                         point_capacity: int, d_point_offsets: int, d_hull_offsets: int, d_hull: int, hull_capacity: int,
+                         d_measures: int = 0, d_edges: int = 0):
+        """dev_canny_contours (same arguments), then the shape stage on what it stored, on the same stream."""
+        v = C.c_void_p
+        self._check(self._L.canny_hip_dev_canny_shapes(
+            self._h, v(d_img or None), sigma, min_val, max_val, h, w, n, v(d_edges or None), min_area, v(d_stats or None),
+            capacity, v(d_offsets or None), v(d_chain_offsets or None), v(d_points or None), point_capacity,
+            v(d_point_offsets or None), v(d_hull_offsets or None), v(d_hull or None), hull_capacity,
+            v(d_measures or None)), "dev_canny_shapes")
+
+    def dev_shapes_bits(self, d_bits: int, h: int, w: int, n: int, min_area: int, d_stats: int, capacity: int,
+                        d_offsets: int, d_chain_offsets: int, d_points: int, point_capacity: int, d_point_offsets: int,
+                        d_hull_offsets: int, d_hull: int, hull_capacity: int, d_measures: int = 0):
+        """dev_contours_bits (same arguments), then the shape stage on what it stored."""
+        v = C.c_void_p
+        self._check(self._L.canny_hip_dev_shapes_bits(
+            self._h, v(d_bits or None), h, w, n, min_area, v(d_stats or None), capacity, v(d_offsets or None),
+            v(d_chain_offsets or None), v(d_points or None), point_capacity, v(d_point_offsets or None),
+            v(d_hull_offsets or None), v(d_hull or None), hull_capacity, v(d_measures or None)), "dev_shapes_bits")
+
+    def shapes_profile_get(self, part: int) -> Tuple[float, int]:
+        """(total ms, launch groups) of part 0 measure, 1 scan, 2 emit (SHAPE_PARTS)."""
+        ms, n = C.c_double(0.0), C.c_long(0)
+        self._check(self._L.canny_hip_shapes_profile_get(self._h, part, C.byref(ms), C.byref(n)), "shapes_profile_get")
         return ms.value, n.value
 
     # ---- Euclidean distance transform of the finished map (DESIGN.md section 15) ---------------------------------

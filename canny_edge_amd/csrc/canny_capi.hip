@@ -394,6 +394,9 @@ struct canny_hip_ctx {
     // polygon approximation: the vertex masks (8 B per record slot), the scan's block sums, the vertex flags of long chains
     // (1 B per point slot); the chains themselves when canny_hip_canny_polygons keeps them on the device
     DevBuf pg_ws, pg_points;
+    // contour shape measures: per point slot the column extremes, the two lists of the hull's rounds and the finished hull
+    // (20 B per point slot), then the scan's block sums
+    DevBuf sh_ws;
     // distance transform: the row pass's u16 plane (2 B/px, rows padded to 64 pixels); the column scan's stack (4 B/px) when
     // the caller passes no dist2 plane to keep it in
     DevBuf edt_cols, edt_stack;
@@ -441,7 +444,7 @@ struct canny_hip_ctx {
     // three of the polygon approximation (canny_hip_polygons_profile_get), then the two of the sub-pixel edgels
     // (canny_hip_edgels_profile_get), then the one of the line fits (canny_hip_line_fits_profile_get), then the one of the
     // circle fits (canny_hip_circle_fits_profile_get), then the four of the chamfer matching
-    // (canny_hip_chamfer_profile_get).  The mask is a non-negative int option: bit 30 is the last it can
+    // (canny_hip_chamfer_profile_get), then the three of the contour shape measures (canny_hip_shapes_profile_get).  The mask is a non-negative int option: bit 30 is the last it can
     // carry, and the three polygon slots, the two edgel slots, the line-fit slot and the circle-fit slot behind them go by
     // it together
     static constexpr int kProfHough = CANNY_HIP_STAGE_END, kProfComponents = CANNY_HIP_STAGE_END + 3;
@@ -454,7 +457,8 @@ struct canny_hip_ctx {
     static constexpr int kProfLineFits = kProfEdgels + CANNY_HIP_EDGEL_PARTS;
     static constexpr int kProfCircleFits = kProfLineFits + CANNY_HIP_LINE_FIT_PARTS;
     static constexpr int kProfChamfer = kProfCircleFits + CANNY_HIP_CIRCLE_FIT_PARTS;
-    static constexpr int kProfSlots = kProfChamfer + CANNY_HIP_CHAMFER_PARTS;
+    static constexpr int kProfShapes = kProfChamfer + CANNY_HIP_CHAMFER_PARTS;
+    static constexpr int kProfSlots = kProfShapes + CANNY_HIP_SHAPE_PARTS;
     static constexpr int kProfLastBit = 30;
     static_assert(kProfPolygons == kProfLastBit && kProfEdgels > kProfLastBit,
                   "profile_stage_mask has one bit per slot up to the polygon parts; every slot from there on follows bit 30");
@@ -1390,6 +1394,61 @@ int dev_canny_polygons(canny_hip_ctx *ctx, const unsigned char *d_img, float sig
     return dev_polygons(ctx, ct.offsets, n, ct.capacity, ct.chain_offsets, ct.points, ct.point_capacity, w, out);
 }
 
+// ---- contour shape measures (canny_shapes.hip) ------------------------------
+struct ShOut {
+    unsigned long long *hull_offsets;
+    int *hull;
+    unsigned long long hull_capacity;
+    long long *measures;
+};
+
+bool shape_args_ok(const ShOut &out) { return out.hull_offsets && (out.hull || !out.hull_capacity); }
+
+int check_shape_dims(int height, int width)
+{
+    if (height < 1 || width < 1) return CANNY_HIP_ERR_INVALID;
+    return height > kShapeMaxSide || width > kShapeMaxSide ? CANNY_HIP_ERR_UNSUPPORTED : CANNY_HIP_OK;
+}
+
+// The stage on stored chains, queued on the context's stream.  The launches depend on capacity and on which outputs were
+// asked for; the number of records is read on the device.
+int dev_shapes(canny_hip_ctx *ctx, const unsigned long long *offsets, int n_frames, unsigned long long capacity,
+               const unsigned long long *chain_offsets, const int *points, unsigned long long point_capacity, int width,
+               const ShOut &out)
+{
+    // one block: column extremes | lists | hulls | block sums
+    const size_t ints_bytes = (shapes_ws_ints(point_capacity) * sizeof(int) + 15) & ~(size_t)15;
+    const size_t sums_bytes = (size_t)polygons_scan_blocks(capacity) * sizeof(unsigned long long);
+    HIP_TRY(ctx, ctx->sh_ws.ensure(ints_bytes + sums_bytes + 16));
+    int *ws = (int *)ctx->sh_ws.p;
+    unsigned long long *sums = (unsigned long long *)((char *)ctx->sh_ws.p + ints_bytes);
+    const int part = canny_hip_ctx::kProfShapes;
+    {
+        StageTimer tm(ctx, part + CANNY_HIP_SHAPE_PART_MEASURE);
+        HIP_TRY(ctx, launch_sh_measure(offsets, n_frames, capacity, chain_offsets, points, point_capacity, width,
+                                       out.hull_offsets, ws, out.measures, ctx->stream));
+    }
+    if (capacity) {
+        StageTimer tm(ctx, part + CANNY_HIP_SHAPE_PART_SCAN);
+        HIP_TRY(ctx, launch_pg_scan(offsets, n_frames, capacity, out.hull_offsets, sums, ctx->stream));
+    }
+    if (capacity && (out.hull_capacity || out.measures)) {
+        StageTimer tm(ctx, part + CANNY_HIP_SHAPE_PART_EMIT);
+        HIP_TRY(ctx, launch_sh_emit(offsets, n_frames, capacity, chain_offsets, point_capacity, width, out.hull_offsets, ws,
+                                    out.hull, out.hull_capacity, out.measures, ctx->stream));
+    }
+    return CANNY_HIP_OK;
+}
+
+// dev_canny_contours (unchanged), then the stage.  max_val > 255 leaves offsets all zero, so the stage finds no record.
+int dev_canny_shapes(canny_hip_ctx *ctx, const unsigned char *d_img, float sigma, int lo, int hi, int h, int w, int n,
+                     short *d_edges, int min_area, const CtOut &ct, const ShOut &out)
+{
+    const int rc = dev_canny_contours(ctx, d_img, sigma, lo, hi, h, w, n, d_edges, min_area, ct);
+    if (rc) return rc;
+    return dev_shapes(ctx, ct.offsets, n, ct.capacity, ct.chain_offsets, ct.points, ct.point_capacity, w, out);
+}
+
 // ---- Euclidean distance transform (canny_edt.hip) --------------------------
 struct EdtOut {
     int *dist2;
@@ -1857,6 +1916,7 @@ void collect_workspaces(const canny_hip_ctx *c, const std::string &prefix, std::
     add("ct_ws", c->ct_ws, I);
     add("pg_ws", c->pg_ws, I);             // block sums of the vertex scan
     add("pg_points", c->pg_points, I);     // pixel indices the stage decodes
+    add("sh_ws", c->sh_ws, I);             // lists of columns that index the extremes; block sums of the hull scan
     add("edt_cols", c->edt_cols, I);       // reused as the column scan's stack of row numbers
     add("edt_stack", c->edt_stack, I);
     add("seg_ws", c->seg_ws, I);
@@ -1988,6 +2048,7 @@ void canny_hip_ctx_destroy(canny_hip_ctx *ctx)
     ctx->ct_ws.release();
     ctx->pg_ws.release();
     ctx->pg_points.release();
+    ctx->sh_ws.release();
     ctx->edt_cols.release();
     ctx->edt_stack.release();
     ctx->stamps.release();
@@ -3812,6 +3873,129 @@ int canny_hip_canny_polygons(canny_hip_ctx *ctx, const unsigned char *imgs, int 
 
 // canny_hip_polygons_from_chains, the rule in plain C++, lives in canny_polygons_host.cpp: it needs no HIP.
 
+// ---- contour shape measures ---------------------------------------------------------------------------
+int canny_hip_dev_shapes_chains(canny_hip_ctx *ctx, const unsigned long long *d_offsets, int n_frames,
+                                unsigned long long capacity, const unsigned long long *d_chain_offsets, const int *d_points,
+                                unsigned long long point_capacity, int width, int height,
+                                unsigned long long *d_hull_offsets, int *d_hull, unsigned long long hull_capacity,
+                                long long *d_measures)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    const ShOut out{d_hull_offsets, d_hull, hull_capacity, d_measures};
+    if (!d_offsets || n_frames < 1 || !d_chain_offsets || (!d_points && point_capacity) || !shape_args_ok(out))
+        return CANNY_HIP_ERR_INVALID;
+    if ((rc = check_shape_dims(height, width)) || (rc = finish_pending(ctx))) return rc;
+    return dev_shapes(ctx, d_offsets, n_frames, capacity, d_chain_offsets, d_points, point_capacity, width, out);
+}
+
+int canny_hip_dev_canny_shapes(canny_hip_ctx *ctx, const unsigned char *d_img, float sigma, int min_val, int max_val,
+                               int height, int width, int n_frames, short *d_edges, int min_area, int *d_stats,
+                               unsigned long long capacity, unsigned long long *d_offsets,
+                               unsigned long long *d_chain_offsets, int *d_points, unsigned long long point_capacity,
+                               unsigned long long *d_point_offsets, unsigned long long *d_hull_offsets, int *d_hull,
+                               unsigned long long hull_capacity, long long *d_measures)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    const CtOut ct{d_stats, capacity, d_offsets, d_chain_offsets, d_points, point_capacity, d_point_offsets};
+    const ShOut out{d_hull_offsets, d_hull, hull_capacity, d_measures};
+    if (!d_img || !d_chain_offsets || !contour_args_ok(ct) || !shape_args_ok(out)) return CANNY_HIP_ERR_INVALID;
+    if ((rc = check_contour_dims(height, width, n_frames)) || (rc = check_shape_dims(height, width))) return rc;
+    return dev_canny_shapes(ctx, d_img, sigma, min_val, max_val, height, width, n_frames, d_edges, min_area, ct, out);
+}
+
+int canny_hip_dev_shapes_bits(canny_hip_ctx *ctx, const unsigned char *d_bits, int height, int width, int n_frames,
+                              int min_area, int *d_stats, unsigned long long capacity, unsigned long long *d_offsets,
+                              unsigned long long *d_chain_offsets, int *d_points, unsigned long long point_capacity,
+                              unsigned long long *d_point_offsets, unsigned long long *d_hull_offsets, int *d_hull,
+                              unsigned long long hull_capacity, long long *d_measures)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    const CtOut ct{d_stats, capacity, d_offsets, d_chain_offsets, d_points, point_capacity, d_point_offsets};
+    const ShOut out{d_hull_offsets, d_hull, hull_capacity, d_measures};
+    if (!d_bits || !d_chain_offsets || !contour_args_ok(ct) || !shape_args_ok(out)) return CANNY_HIP_ERR_INVALID;
+    if ((rc = check_contour_dims(height, width, n_frames)) || (rc = check_shape_dims(height, width)) ||
+        (rc = finish_pending(ctx)))
+        return rc;
+    if ((rc = dev_contours(ctx, nullptr, d_bits, make_hyst_geom(height, width, n_frames), min_area, ct))) return rc;
+    return dev_shapes(ctx, d_offsets, n_frames, capacity, d_chain_offsets, d_points, point_capacity, width, out);
+}
+
+int canny_hip_canny_shapes(canny_hip_ctx *ctx, const unsigned char *imgs, int n_frames, float sigma, int min_val,
+                           int max_val, int height, int width, int min_area, int *stats, unsigned long long capacity,
+                           unsigned long long *offsets, unsigned long long *chain_offsets, int *points,
+                           unsigned long long point_capacity, unsigned long long *point_offsets,
+                           unsigned long long *hull_offsets, int *hull, unsigned long long hull_capacity,
+                           long long *measures)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!imgs || !offsets || !point_offsets || !shape_args_ok(ShOut{hull_offsets, hull, hull_capacity, measures}))
+        return CANNY_HIP_ERR_INVALID;
+    if ((rc = check_contour_dims(height, width, n_frames)) || (rc = check_shape_dims(height, width))) return rc;
+    const size_t n = npx(height, width, n_frames);
+    const size_t off_bytes = ((size_t)n_frames + 1) * sizeof(unsigned long long);
+    // the clamps of canny_hip_canny_polygons: a hull has no more vertices than its chain has points
+    const unsigned long long cap = std::min<unsigned long long>(capacity, n);
+    const unsigned long long pcap = std::min<unsigned long long>(point_capacity, 9ull * n);
+    const unsigned long long hcap = std::min<unsigned long long>(hull_capacity, pcap);
+    if ((rc = h2d(ctx, ctx->io[0], imgs, n))) return rc;
+    // one staging block: offsets | point_offsets | chain_offsets | hull_offsets | measures | stats | hull; the chain points
+    // in a block of their own, which never crosses to the host when points == NULL
+    auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+    const size_t csr_bytes = ((size_t)cap + 1) * sizeof(unsigned long long);
+    const size_t poff_at = up16(off_bytes), chain_at = up16(poff_at + off_bytes), hoff_at = up16(chain_at + csr_bytes);
+    const size_t meas_at = up16(hoff_at + csr_bytes);
+    const size_t stats_at = up16(meas_at + (measures ? (size_t)cap * CANNY_HIP_SHAPE_WORDS * sizeof(long long) : 0));
+    const size_t hull_at = up16(stats_at + (stats ? (size_t)cap * CANNY_HIP_CC_STATS * sizeof(int) : 0));
+    HIP_TRY(ctx, ctx->io[1].ensure(hull_at + (size_t)hcap * sizeof(int)));
+    HIP_TRY(ctx, ctx->pg_points.ensure((size_t)pcap * sizeof(int) + 16));
+    char *d = (char *)ctx->io[1].p;
+    const CtOut ct{stats && cap ? (int *)(d + stats_at) : nullptr,
+                   cap,
+                   (unsigned long long *)d,
+                   (unsigned long long *)(d + chain_at),
+                   pcap ? (int *)ctx->pg_points.p : nullptr,
+                   pcap,
+                   (unsigned long long *)(d + poff_at)};
+    const ShOut out{(unsigned long long *)(d + hoff_at), hcap ? (int *)(d + hull_at) : nullptr, hcap,
+                    measures && cap ? (long long *)(d + meas_at) : nullptr};
+    if ((rc = dev_canny_shapes(ctx, (const unsigned char *)ctx->io[0].p, sigma, min_val, max_val, height, width, n_frames,
+                               nullptr, min_area, ct, out)))
+        return rc;
+    // the offsets come down first: they say how many records there are to download
+    std::vector<unsigned long long> off(2 * ((size_t)n_frames + 1));
+    HIP_TRY(ctx, hipMemcpyAsync(off.data(), ct.offsets, off_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = d2h_sync(ctx, off.data() + n_frames + 1, ct.point_offsets, off_bytes))) return rc;
+    const unsigned long long n_rec = std::min(off[n_frames], cap);
+    unsigned long long ends[2] = {0, 0}; // where the stored chains and the hulls end
+    HIP_TRY(ctx, hipMemcpyAsync(&ends[0], ct.chain_offsets + n_rec, sizeof ends[0], hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(&ends[1], out.hull_offsets + n_rec, sizeof ends[1], hipMemcpyDeviceToHost, ctx->stream));
+    if (chain_offsets)
+        HIP_TRY(ctx, hipMemcpyAsync(chain_offsets, ct.chain_offsets, ((size_t)n_rec + 1) * sizeof(unsigned long long),
+                                    hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(hull_offsets, out.hull_offsets, ((size_t)n_rec + 1) * sizeof(unsigned long long),
+                                hipMemcpyDeviceToHost, ctx->stream));
+    if (n_rec && ct.stats)
+        HIP_TRY(ctx, hipMemcpyAsync(stats, ct.stats, (size_t)n_rec * CANNY_HIP_CC_STATS * sizeof(int),
+                                    hipMemcpyDeviceToHost, ctx->stream));
+    if (n_rec && out.measures)
+        HIP_TRY(ctx, hipMemcpyAsync(measures, out.measures, (size_t)n_rec * CANNY_HIP_SHAPE_WORDS * sizeof(long long),
+                                    hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    const unsigned long long n_pts = points ? std::min(ends[0], pcap) : 0, n_hull = std::min(ends[1], hcap);
+    if (n_pts) HIP_TRY(ctx, hipMemcpyAsync(points, ct.points, (size_t)n_pts * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    if (n_hull) HIP_TRY(ctx, hipMemcpyAsync(hull, out.hull, (size_t)n_hull * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    std::memcpy(offsets, off.data(), off_bytes);
+    std::memcpy(point_offsets, off.data() + n_frames + 1, off_bytes);
+    return CANNY_HIP_OK;
+}
+
+// canny_hip_shapes_from_chains, the rule in plain C++, lives in canny_shapes_host.cpp: it needs no HIP.
+
 // ---- Euclidean distance transform -------------------------------------------------------------------
 int canny_hip_dev_canny_edt(canny_hip_ctx *ctx, const unsigned char *d_img, float sigma, int min_val, int max_val,
                             int height, int width, int n_frames, short *d_edges, int *d_dist2, float *d_dist,
@@ -5373,6 +5557,29 @@ int canny_hip_chamfer_profile_get(canny_hip_ctx *ctx, int part, double *total_ms
     if ((rc = profile_collect(ctx))) return rc;
     *total_ms = ctx->total_ms[canny_hip_ctx::kProfChamfer + part];
     *launches = ctx->launches[canny_hip_ctx::kProfChamfer + part];
+    return CANNY_HIP_OK;
+}
+
+int canny_hip_shapes_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches)
+{
+    if (part < 0 || part >= CANNY_HIP_SHAPE_PARTS || !total_ms || !launches) return CANNY_HIP_ERR_INVALID;
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if ((rc = profile_collect(ctx))) return rc;
+    *total_ms = ctx->total_ms[canny_hip_ctx::kProfShapes + part];
+    *launches = ctx->launches[canny_hip_ctx::kProfShapes + part];
+    return CANNY_HIP_OK;
+}
+
+// Host-only: the launch plans of the capped launches of the contour shape measures.
+int canny_hip_selftest_shapes_plan(int which, unsigned long long capacity, unsigned long long *out)
+{
+    if (!out || capacity < 1) return CANNY_HIP_ERR_INVALID;
+    LaunchPlan p;
+    if (which == CANNY_HIP_SHAPES_PLAN_RECORDS) p = plan_sh_records(capacity);
+    else if (which == CANNY_HIP_SHAPES_PLAN_SCAN_SUMS) p = plan_pg_scan_sums(capacity);
+    else return CANNY_HIP_ERR_INVALID;
+    out[0] = p.units, out[1] = p.per_group, out[2] = p.grid, out[3] = p.trips(), out[4] = (unsigned long long)p.aux;
     return CANNY_HIP_OK;
 }
 

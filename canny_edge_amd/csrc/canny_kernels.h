@@ -549,6 +549,24 @@ hipError_t launch_pg_emit(const unsigned long long *offsets, int n_frames, unsig
                           const uint8_t *flags, int *vertices, unsigned long long vertex_capacity, long long *measures,
                           hipStream_t stream);
 
+// ---- contour shape measures (canny_shapes.hip) --------------------------
+// Same inputs as the polygon stage.  height, width <= kShapeMaxSide keep every coordinate in 15 bits.  ws: shapes_ws_ints
+// (point_capacity) ints, five arrays of point_capacity ints each, indexed like points: the smallest and the largest y per
+// column of a chain's bounding box, the two lists of the hull's rounds, and the finished hull packed (y << 16 | x).
+constexpr int kShapeMaxSide = 32767;
+inline size_t shapes_ws_ints(unsigned long long point_capacity) { return 5 * (size_t)point_capacity; }
+// measure: hull_offsets[0] = 0, hull_offsets[j + 1] = V_h of record j (0 for a cut chain); the hull goes to the workspace;
+// measures (may be null) [j][0 .. 13], and (-1, 0, ...) for a cut chain.
+hipError_t launch_sh_measure(const unsigned long long *offsets, int n_frames, unsigned long long capacity,
+                             const unsigned long long *chain_offsets, const int *points, unsigned long long point_capacity,
+                             int width, unsigned long long *hull_offsets, int *ws, long long *measures, hipStream_t stream);
+// emit (behind launch_pg_scan on hull_offsets): hull[hull_offsets[j] + k] below hull_capacity (hull may be null with
+// capacity 0); measures (may be null) [j][14 .. 19] of the complete records.
+hipError_t launch_sh_emit(const unsigned long long *offsets, int n_frames, unsigned long long capacity,
+                          const unsigned long long *chain_offsets, unsigned long long point_capacity, int width,
+                          const unsigned long long *hull_offsets, const int *ws, int *hull, unsigned long long hull_capacity,
+                          long long *measures, hipStream_t stream);
+
 // ---- Euclidean distance transform (canny_edt.hip) ----------------------
 // Source as for the point lists.  height * width < 2^31 and height^2 + width^2 < 2^31.
 // Elements per row of the u16 plane between the two passes: rows are padded to whole 64-pixel words.
@@ -646,6 +664,7 @@ LaunchPlan plan_edt_rows(const HystGeom &g);       // edt rows: groups of aux co
 LaunchPlan plan_edt_columns(const HystGeom &g);    // edt columns: 64-column strips of the batch
 LaunchPlan plan_pg_records(unsigned long long capacity);   // polygon simplify, emit: record slots
 LaunchPlan plan_pg_scan_sums(unsigned long long capacity); // pg_scan_sums_kernel: chunk sums, one workgroup
+LaunchPlan plan_sh_records(unsigned long long capacity);   // shape measure, emit: record slots
 // global vote: the items of a frame as the kernel walks them -- the plane's words (tile padding included for the strong
 // plane; a trip is one word per lane, and a lane keeps four in flight) or the n_points points of the frame's list (only
 // the query knows them: the grid is sized by pixels / 16, and by the strong plane's words for both plane sources)

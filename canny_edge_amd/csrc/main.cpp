@@ -1,7 +1,7 @@
 // main.cpp -- the reference's command line (StevenChang5/Canny_Edge src/main.cpp:18-142) without
 // the webcam and the GUI:  ./Main sigma minVal maxVal [-c] [-s] [-i in.pgm|in.ppm|in.jpg] [-o dir] [-p] [-n WxH] [-b dir]
 //        [-l rho,theta_degrees,threshold[,lines_max]] [-g min_length,max_gap[,exclusive]] [-m min_area] [-t] [-d] [-e]
-//        [-r min_radius,max_radius,threshold,support[,min_dist[,cell_shift]]] [-y epsilon[,ratio]]
+//        [-r min_radius,max_radius,threshold,support[,min_dist[,cell_shift]]] [-y epsilon[,ratio]] [-u]
 //
 // Kept from the reference: the three positionals may appear anywhere relative to the flags
 // (src/main.cpp:29-46); exactly three are required, otherwise the usage text is printed and the
@@ -31,6 +31,10 @@
 // ..." line per contour goes to canny_polygons.txt in the -o directory (stdout without -o); record is the label of
 // canny_contours.txt, length is in 1/256 pixel, area2 is twice the polygon's area.  -y without -t and a malformed -y are
 // usage errors (exit 2).
+// Added: -u (with -t) also measures every contour on the GPU (canny_hip_canny_shapes; the chains stay on the device): one
+// "frame record points hull_vertices area2 hull_area2 rect_edge rect_along_min rect_along_max rect_across rect_len2 x0 y0 x1
+// y1 ..." line per contour goes to canny_shapes.txt in the -o directory (stdout without -o), the trailing pairs being the
+// vertices of the convex hull.  -u without -t is a usage error (exit 2).
 // Added: -d runs the exact Euclidean distance transform of the frame's edge map on the GPU (canny_hip_canny_edt) and writes
 // canny_dist.pgm (.png with -p) to the -o directory (the current one without -o): one byte per pixel,
 // min(255, floor(sqrt(dist2))), 255 everywhere for a map without edge pixels.  Without -d nothing changes.
@@ -515,6 +519,55 @@ static int run_polygons(const vector<unsigned char> &frame, int height, int widt
     return 0;
 }
 
+// -u (with -t): the shape measures of every contour, "frame record points hull_vertices area2 hull_area2 rect_edge
+// rect_along_min rect_along_max rect_across rect_len2 x0 y0 x1 y1 ..." each, the pairs being the hull.  Only the measures and
+// the hulls come down: the chains stay on the device.
+static int run_shapes(const vector<unsigned char> &frame, int height, int width, float sigma, int minVal, int maxVal,
+                      int min_area, const string &outdir)
+{
+    vector<unsigned long long> hull_offsets(1, 0);
+    vector<int> hull;
+    vector<long long> measures;
+    unsigned long long offsets[2] = {0, 0}, point_offsets[2] = {0, 0};
+    canny_hip_ctx *ctx = nullptr;
+    int st = canny_hip_ctx_create(&ctx, 0);
+    // counts first: a hull has no more vertices than its chain has points
+    if (!st)
+        st = canny_hip_canny_contours(ctx, frame.data(), 1, sigma, minVal, maxVal, height, width, min_area, nullptr, 0,
+                                      offsets, nullptr, nullptr, 0, point_offsets);
+    if (!st) {
+        hull_offsets.resize((size_t)offsets[1] + 1);
+        hull.resize((size_t)point_offsets[1] + 1);
+        measures.resize((size_t)offsets[1] * CANNY_HIP_SHAPE_WORDS + 1);
+        st = canny_hip_canny_shapes(ctx, frame.data(), 1, sigma, minVal, maxVal, height, width, min_area, nullptr, offsets[1],
+                                    offsets, nullptr, nullptr, point_offsets[1], point_offsets, hull_offsets.data(),
+                                    hull.data(), point_offsets[1], measures.data());
+    }
+    if (st) {
+        fprintf(stderr, "ERROR: -u: %s\n", st == CANNY_HIP_ERR_RUNTIME && ctx ? canny_hip_last_error(ctx) : canny_hip_status_string(st));
+        if (ctx) canny_hip_ctx_destroy(ctx);
+        return 1;
+    }
+    canny_hip_ctx_destroy(ctx);
+    FILE *f = outdir.empty() ? stdout : fopen((outdir + "/canny_shapes.txt").c_str(), "w");
+    if (!f) {
+        fprintf(stderr, "ERROR: cannot write %s/canny_shapes.txt\n", outdir.c_str());
+        return 1;
+    }
+    for (unsigned long long k = 0; k < offsets[1]; k++) {
+        const long long *m = measures.data() + k * CANNY_HIP_SHAPE_WORDS;
+        fprintf(f, "0 %llu %lld %lld %lld %lld %lld %lld %lld %lld %lld", k + 1, m[CANNY_HIP_SHAPE_POINTS],
+                m[CANNY_HIP_SHAPE_HULL_VERTICES], m[CANNY_HIP_SHAPE_AREA2], m[CANNY_HIP_SHAPE_HULL_AREA2],
+                m[CANNY_HIP_SHAPE_RECT_EDGE], m[CANNY_HIP_SHAPE_RECT_ALONG_MIN], m[CANNY_HIP_SHAPE_RECT_ALONG_MAX],
+                m[CANNY_HIP_SHAPE_RECT_ACROSS], m[CANNY_HIP_SHAPE_RECT_LEN2]);
+        for (unsigned long long q = hull_offsets[k]; q < hull_offsets[k + 1]; q++)
+            fprintf(f, " %d %d", hull[q] % width, hull[q] / width);
+        fprintf(f, "\n");
+    }
+    if (f != stdout) fclose(f);
+    return 0;
+}
+
 // -d: the distance of every pixel to the nearest edge pixel, as a byte image
 static int run_edt(const vector<unsigned char> &frame, int height, int width, float sigma, int minVal, int maxVal,
                    const string &outdir)
@@ -674,6 +727,7 @@ int main(int argc, char *argv[])
     bool want_contours = false;
     bool want_circles = false;
     bool want_polygons = false;
+    bool want_shapes = false;
     bool want_edgels = false;
     int fit_options = -1; // -f: the line fits of the segments; -1 = not asked for
     unsigned polygon_epsilon_q8 = 0, polygon_ratio_q16 = 0;
@@ -817,6 +871,8 @@ int main(int argc, char *argv[])
             }
             polygon_epsilon_q8 = (unsigned)eq, polygon_ratio_q16 = (unsigned)rq;
             want_polygons = true;
+        } else if (arg == "-u") {
+            want_shapes = true;
         } else if (arg == "-d") {
             want_dist = true;
         } else if (arg == "-t") {
@@ -849,6 +905,10 @@ int main(int argc, char *argv[])
         fprintf(stderr, "ERROR: -y needs the contours of -t\n");
         exit(2);
     }
+    if (want_shapes && !want_contours) {
+        fprintf(stderr, "ERROR: -u needs the contours of -t\n");
+        exit(2);
+    }
     if (values.size() != 3) {
         fprintf(stderr, "USAGE: %s sigma minVal maxVal\n", argv[0]);
         fprintf(stderr, "   sigma: Standard deviation used for the gaussian blurring kernel\n");
@@ -872,6 +932,9 @@ int main(int argc, char *argv[])
         fprintf(stderr, "   -y epsilon[,ratio]: with -t, the polygon of every contour at a tolerance of epsilon pixels plus ratio times\n");
         fprintf(stderr, "       its length, one \"frame record vertices length area2 convex x0 y0 x1 y1 ...\" line each (length in 1/256\n");
         fprintf(stderr, "       pixel, area2 twice the area) -> canny_polygons.txt in the -o dir\n");
+        fprintf(stderr, "   -u: with -t, the moments, convex hull and minimum-area rectangle of every contour, one \"frame record points\n");
+        fprintf(stderr, "       hull_vertices area2 hull_area2 rect_edge rect_along_min rect_along_max rect_across rect_len2 x0 y0 x1 y1 ...\"\n");
+        fprintf(stderr, "       line each (the pairs are the hull) -> canny_shapes.txt in the -o dir\n");
         fprintf(stderr, "   -r min_radius,max_radius,threshold,support[,min_dist[,cell_shift]]: circles of the edge map, one\n");
         fprintf(stderr, "       \"frame x y radius votes support\" line each -> canny_circles.txt in the -o dir\n");
         fprintf(stderr, "   -k band,trim_q8[,options]: with -r, the sub-pixel circle fit of every circle (band 0..4 bins each side, trim_q8 in\n");
@@ -947,6 +1010,10 @@ int main(int argc, char *argv[])
     if (want_polygons) {
         const int rc = run_polygons(frame, height, width, sigma, minVal, maxVal, min_area, polygon_epsilon_q8,
                                     polygon_ratio_q16, outdir);
+        if (rc) return rc;
+    }
+    if (want_shapes) {
+        const int rc = run_shapes(frame, height, width, sigma, minVal, maxVal, min_area, outdir);
         if (rc) return rc;
     }
     if (want_edgels) {

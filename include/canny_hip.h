@@ -52,7 +52,8 @@
 extern "C" {
 #endif
 
-#define CANNY_HIP_VERSION 1600       /* 0.16.0: + chamfer template matching on the distance transform */
+#define CANNY_HIP_VERSION 1700       /* 0.17.0: + contour shape measures: moments, convex hull, minimum-area rectangle */
+/* 0.16.0: + chamfer template matching on the distance transform */
 /* 0.15.0: + sub-pixel circle fits: least-squares refit of Hough circles from edgels */
 /* 0.13.0: + sub-pixel edgels: position, gradient and strength per edge pixel */
 /* 0.12.2: + canny_hip_selftest_launch_plan */
@@ -1322,6 +1323,127 @@ int canny_hip_polygons_from_chains(const unsigned long long *chain_offsets, cons
                                    unsigned epsilon_q8, unsigned ratio_q16, unsigned long long *vertex_offsets,
                                    int *vertices, unsigned long long vertex_capacity, long long *measures);
 
+/* ---- contour shape measures: moments, convex hull, minimum-area rectangle ---------------------------------------------------
+ * For every stored chain of a contours call what a caller of cv::findContours reaches for next, on the GPU, queued behind the
+ * chains on the same stream: the integers behind cv::moments (centroid, orientation), cv::convexHull (solidity) and
+ * cv::minAreaRect (the oriented box: "a rotated rectangle / a bar / a part in a gripper"), 20 words and a handful of hull
+ * vertices per contour instead of a download of the chains.  Everything is integers and exact.
+ * THE RULE, for one stored chain P_0 .. P_{n-1}.  Points are pixel indices r * width + c, read as
+ * (x, y) = (c, r); the chain is closed, P_n means P_0.  All moments are relative to the anchor P_0: u_i = x_i - x_0,
+ * v_i = y_i - y_0.  Every sum below is taken in 64-bit two's-complement WRAPPING arithmetic and read back as signed: the
+ * stored word is the true value whenever that fits, whatever the partial sums did in between, and it fits for every outer
+ * border of a frame within the size limit (height, width < 32768).
+ *   1. Polygon moments (Green's theorem; the integers behind cv::moments(contour)).  With a_i = u_i * v_{i+1} - u_{i+1} * v_i
+ *      over the n cyclic steps:
+ *        area2  = sum a_i   (signed: the sign is the walk's orientation; twice the area)
+ *        m10_6  = sum a_i * (u_i + u_{i+1})                              m01_6 likewise in v   (6 * m10, 6 * m01)
+ *        m20_12 = sum a_i * (u_i^2 + u_i * u_{i+1} + u_{i+1}^2)          m02_12 likewise in v  (12 * m20, 12 * m02)
+ *        m11_24 = sum a_i * (2 u_i v_i + u_i v_{i+1} + u_{i+1} v_i + 2 u_{i+1} v_{i+1})         (24 * m11)
+ *   2. Point sums over the n chain points: s10 = sum u, s01 = sum v, s20 = sum u^2, s11 = sum u * v, s02 = sum v^2.  A Canny
+ *      map is mostly one-pixel curves that the border follower walks out and back; their area2 is 0, and these sums are what
+ *      gives such a curve a centre and an axis.
+ *   3. Convex hull of the chain's point set.  The vertices are the strictly extreme points (a point on a hull edge between
+ *      two others is no vertex).  The order begins at the vertex with the smallest x, among those the smallest y, and
+ *      continues so that every turn cross(H_{k+1} - H_k, H_{k+2} - H_{k+1}) > 0 with x to the right and y down.  The hull is
+ *      stored as pixel indices; V_h is its true vertex count.  hull_area2 = sum x_k * y_{k+1} - x_{k+1} * y_k >= 0.
+ *   4. Minimum-area rectangle with a side on a hull edge.  For edge k: d = H_{k+1} - H_k, len2 = |d|^2,
+ *      along_i = dot(H_i - H_k, d), across_i = cross(d, H_i - H_k) (>= 0 by the orientation), E_k = max along - min along,
+ *      N_k = max across; the rectangle's area is E_k * N_k / len2_k.  The chosen edge is the smallest k that minimises that
+ *      area; two edges are compared exactly as E_k N_k len2_k' against E_k' N_k' len2_k (E * N < 2^63, len2 < 2^31: 128
+ *      bits).  Stored: rect_edge = k, rect_along_min, rect_along_max, rect_across = N_k, rect_len2: the caller gets corners,
+ *      size and angle from these and the two hull vertices H_k, H_{k+1} without any rounding by the library.  V_h = 2:
+ *      rect_edge 0, along_min 0, along_max = len2, across 0.  V_h = 1: all zero.
+ *   5. Measures per record, CANNY_HIP_SHAPE_WORDS = 20 long long, in the order of enum canny_hip_shape_measure.
+ *   Which chains: as for the polygons, the records j < R = min(K, capacity); a record is COMPLETE iff
+ *     chain_offsets[j + 1] <= point_capacity.  An incomplete record has hull_vertices = -1, 19 zeros and no hull vertices.
+ *   Outputs:
+ *     hull_offsets[0 .. R] (unsigned long long, capacity + 1 entries at most; mandatory): the true prefix sums of V_h,
+ *       incomplete records counting 0.  Entries past R are not written.
+ *     hull (int): position q is written iff q < hull_capacity: the prefix that fits is exact, nothing is written at or past
+ *       hull + hull_capacity.  NULL is allowed with hull_capacity == 0 only.
+ *     measures (optional, long long [R][20]); what the other outputs receive does not depend on which outputs are absent.
+ *       hull_area2 and the rectangle come from the hull itself, not from what fitted into the caller's buffer.
+ *   Arguments: as for the polygons calls without the tolerances.  A height or width of 32768 or more is
+ *     CANNY_HIP_ERR_UNSUPPORTED before anything is queued.  On a status other than OK nothing is written.  An empty map
+ *     (max_val > 255 included) gives hull_offsets[0] = 0 and nothing else.  The device calls expect what a contours call
+ *     stores, closed 8-connected walks: a chain whose bounding box is wider than the chain is long, or that visits no point
+ *     of some column of its box, is answered like an incomplete record (canny_hip_shapes_from_chains measures any chain).
+ *   The output is the same bytes on every run: every output element is stored once by one wave; the only atomics are
+ *     integer minima and maxima into a workspace, whose result does not depend on the order in which they land; the
+ *     launches depend on the shapes, the capacities and on which outputs were asked for, never on the data.
+ * Memory: a context workspace of 20 bytes per point slot (point_capacity): per column of a chain's bounding box the smallest
+ *   and the largest y, two lists for the rounds of the hull, and the finished hull; plus 8 bytes per 2048 record slots.
+ * Cost: a chain is measured by ONE wave.  See DESIGN.md section 27 for the measured times, the long-chain tail included.
+ * The three parts are timed by canny_hip_shapes_profile_get (CANNY_HIP_SHAPE_PART_*); with "profile_stage_mask" they go by
+ *   bit 30 like every part behind the polygons.
+ * Not covered -- follow-ups: hole borders, convexity defects, ellipse fits, the minimum enclosing circle, Hu invariants
+ * (floats the caller derives from these words), the three-stream batch pipeline, the multi-GPU sharder, colour and
+ * per-frame / automatic-threshold variants, long chains split over a workgroup. */
+#define CANNY_HIP_SHAPE_WORDS 20
+enum canny_hip_shape_measure {
+    CANNY_HIP_SHAPE_HULL_VERTICES = 0,
+    CANNY_HIP_SHAPE_POINTS = 1,
+    CANNY_HIP_SHAPE_ANCHOR = 2,
+    CANNY_HIP_SHAPE_AREA2 = 3,
+    CANNY_HIP_SHAPE_M10_6 = 4,
+    CANNY_HIP_SHAPE_M01_6 = 5,
+    CANNY_HIP_SHAPE_M20_12 = 6,
+    CANNY_HIP_SHAPE_M11_24 = 7,
+    CANNY_HIP_SHAPE_M02_12 = 8,
+    CANNY_HIP_SHAPE_S10 = 9,
+    CANNY_HIP_SHAPE_S01 = 10,
+    CANNY_HIP_SHAPE_S20 = 11,
+    CANNY_HIP_SHAPE_S11 = 12,
+    CANNY_HIP_SHAPE_S02 = 13,
+    CANNY_HIP_SHAPE_HULL_AREA2 = 14,
+    CANNY_HIP_SHAPE_RECT_EDGE = 15,
+    CANNY_HIP_SHAPE_RECT_ALONG_MIN = 16,
+    CANNY_HIP_SHAPE_RECT_ALONG_MAX = 17,
+    CANNY_HIP_SHAPE_RECT_ACROSS = 18,
+    CANNY_HIP_SHAPE_RECT_LEN2 = 19
+};
+enum canny_hip_shape_part {
+    CANNY_HIP_SHAPE_PART_MEASURE = 0,  /* one wave per chain: the eleven sums, the column extremes, the hull; hull counts */
+    CANNY_HIP_SHAPE_PART_SCAN = 1,     /* prefix sums of the counts: hull_offsets */
+    CANNY_HIP_SHAPE_PART_EMIT = 2,     /* hull vertices stored; hull_area2 and the rectangle */
+    CANNY_HIP_SHAPE_PARTS = 3
+};
+/* The stage alone, on chains already on the device: d_offsets, d_chain_offsets and d_points are what a contours call with
+ * the same n_frames, capacity and point_capacity left (a polygons call may have run on them in between).  Asynchronous, on
+ * the context's stream. */
+int canny_hip_dev_shapes_chains(canny_hip_ctx *ctx, const unsigned long long *d_offsets, int n_frames,
+                                unsigned long long capacity, const unsigned long long *d_chain_offsets, const int *d_points,
+                                unsigned long long point_capacity, int width, int height,
+                                unsigned long long *d_hull_offsets, int *d_hull, unsigned long long hull_capacity,
+                                long long *d_measures);
+/* canny_hip_dev_canny_contours / canny_hip_dev_contours_bits, unchanged, then the stage on what they stored. */
+int canny_hip_dev_canny_shapes(canny_hip_ctx *ctx, const unsigned char *d_img, float sigma, int min_val, int max_val,
+                               int height, int width, int n_frames, short *d_edges, int min_area, int *d_stats,
+                               unsigned long long capacity, unsigned long long *d_offsets,
+                               unsigned long long *d_chain_offsets, int *d_points, unsigned long long point_capacity,
+                               unsigned long long *d_point_offsets, unsigned long long *d_hull_offsets, int *d_hull,
+                               unsigned long long hull_capacity, long long *d_measures);
+int canny_hip_dev_shapes_bits(canny_hip_ctx *ctx, const unsigned char *d_bits, int height, int width, int n_frames,
+                              int min_area, int *d_stats, unsigned long long capacity, unsigned long long *d_offsets,
+                              unsigned long long *d_chain_offsets, int *d_points, unsigned long long point_capacity,
+                              unsigned long long *d_point_offsets, unsigned long long *d_hull_offsets, int *d_hull,
+                              unsigned long long hull_capacity, long long *d_measures);
+/* Host buffers, synchronous: upload, canny, chains, shapes.  Everything canny_hip_canny_contours returns comes down, plus
+ * min(K, capacity) + 1 hull offsets, as many measures, and the hull vertices below min(hull_offsets[min(K, capacity)],
+ * hull_capacity).  points may be NULL here at any point_capacity: the chains then stay in a device buffer of point_capacity
+ * ints and only the shapes cross to the host.  chain_offsets, stats and measures may be NULL. */
+int canny_hip_canny_shapes(canny_hip_ctx *ctx, const unsigned char *imgs, int n_frames, float sigma, int min_val,
+                           int max_val, int height, int width, int min_area, int *stats, unsigned long long capacity,
+                           unsigned long long *offsets, unsigned long long *chain_offsets, int *points,
+                           unsigned long long point_capacity, unsigned long long *point_offsets,
+                           unsigned long long *hull_offsets, int *hull, unsigned long long hull_capacity,
+                           long long *measures);
+/* Host-only, needs no device: the same rule in plain C++ on n_records chains in host memory.  hull_offsets has
+ * n_records + 1 entries. */
+int canny_hip_shapes_from_chains(const unsigned long long *chain_offsets, const int *points, unsigned long long n_records,
+                                 unsigned long long point_capacity, int width, int height, unsigned long long *hull_offsets,
+                                 int *hull, unsigned long long hull_capacity, long long *measures);
+
 /* ---- Euclidean distance transform ----------------------------------------------------------------------------------------
  * For every pixel of every frame the distance to the nearest edge pixel, on the GPU, queued behind the detector on the same
  * stream with no host round trip: what chamfer and template matching, edge-based registration, "snap to the nearest edge" and
@@ -1507,6 +1629,8 @@ int canny_hip_line_fits_profile_get(canny_hip_ctx *ctx, int part, double *total_
 int canny_hip_circle_fits_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches);
 /* ... and for the four parts of the chamfer matching (CANNY_HIP_CHAMFER_PART_*). */
 int canny_hip_chamfer_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches);
+/* ... and for the three parts of the contour shape measures (CANNY_HIP_SHAPE_PART_*). */
+int canny_hip_shapes_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches);
 
 /* ---- self-test hooks used by the GPU test-suite -------------------------------------------- */
 /* Runs the DEVICE magnitude / angle-bin functions over every (gx,gy) in [-lim,lim]^2 and writes
@@ -1637,6 +1761,14 @@ int canny_hip_selftest_chamfer_plan(int which, int n_frames, int height, int wid
  * largest LDS tile of a band of t in u16 elements, out[2] = the largest of the whole set (the launch's LDS), out[3] = the
  * route the automatic choice takes for the set (1 direct, 2 tiled). */
 int canny_hip_selftest_chamfer_bands(const int *offsets, const short *points, int n_templates, int t, int *out);
+/* Host-only, the same five outputs for the capped launches of the contour shape measures (they have no kind above); both
+ * are sized by the record capacity >= 1 alone:
+ *   CANNY_HIP_SHAPES_PLAN_RECORDS:   the measure and the emit kernel, one wave per record and trip, 4 records per
+ *     workgroup, at most 65536 workgroups;
+ *   CANNY_HIP_SHAPES_PLAN_SCAN_SUMS: the scan's pass over its chunks of 2048 records (the polygons' scan, unchanged): one
+ *     workgroup, 256 chunks per trip. */
+enum canny_hip_shapes_plan { CANNY_HIP_SHAPES_PLAN_RECORDS = 0, CANNY_HIP_SHAPES_PLAN_SCAN_SUMS = 1 };
+int canny_hip_selftest_shapes_plan(int which, unsigned long long capacity, unsigned long long *out);
 
 #ifdef __cplusplus
 }
