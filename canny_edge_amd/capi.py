@@ -130,6 +130,8 @@ EXPORTS = (
     "canny_hip_selftest_chamfer_plan", "canny_hip_selftest_chamfer_bands",
     "canny_hip_dev_shapes_chains", "canny_hip_dev_canny_shapes", "canny_hip_dev_shapes_bits", "canny_hip_canny_shapes",
     "canny_hip_shapes_from_chains", "canny_hip_shapes_profile_get", "canny_hip_selftest_shapes_plan",
+    "canny_hip_dev_canny_curves", "canny_hip_dev_curves_bits", "canny_hip_canny_curves", "canny_hip_curves_from_bits",
+    "canny_hip_curves_profile_get", "canny_hip_selftest_curves_plan",
 )
 
 _lib: Optional[C.CDLL] = None
@@ -333,6 +335,12 @@ def load() -> C.CDLL:
         "canny_hip_shapes_from_chains": ([p, p, ull, ull, i, i, p, p, ull, p], i),
         "canny_hip_shapes_profile_get": ([p, i, C.POINTER(C.c_double), C.POINTER(C.c_long)], i),
         "canny_hip_selftest_shapes_plan": ([i, ull, p], i),
+        "canny_hip_dev_canny_curves": ([p, p, f, i, i, i, i, i, p, i, p, ull, p, p, p, ull, p], i),
+        "canny_hip_dev_curves_bits": ([p, p, i, i, i, i, p, ull, p, p, p, ull, p], i),
+        "canny_hip_canny_curves": ([p, p, i, f, i, i, i, i, i, p, ull, p, p, p, ull, p], i),
+        "canny_hip_curves_from_bits": ([p, i, i, i, p, ull, C.POINTER(ull), p, p, ull, C.POINTER(ull)], i),
+        "canny_hip_curves_profile_get": ([p, i, C.POINTER(C.c_double), C.POINTER(C.c_long)], i),
+        "canny_hip_selftest_curves_plan": ([i, i, i, p], i),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -568,6 +576,52 @@ def shapes_plan(which, capacity: int) -> "LaunchPlan":
     st = load().canny_hip_selftest_shapes_plan(SHAPES_PLANS.get(which, which), int(capacity), _hp(out))
     if st:
         raise CannyHipError(st, "selftest_shapes_plan")
+    return LaunchPlan(*(int(v) for v in out))
+
+
+CURVE_PARTS = ("count", "write")
+CURVE_RECORD = 4                                                # CANNY_HIP_CURVE_RECORD: start, end, points, flags
+CURVE_CLOSED, CURVE_START_JUNCTION, CURVE_END_JUNCTION, CURVE_ISOLATED = 1, 2, 4, 8   # canny_hip_curve_flag
+CURVE_FIRST_DIR_SHIFT, CURVE_LAST_DIR_SHIFT = 4, 8
+
+
+def curves_from_bits(bits, height: int, width: int, min_length: int = 1, want_records: bool = True,
+                     capacity: Optional[int] = None, point_capacity: Optional[int] = None):
+    """Host-only: the edge curves of one packed bit map (numpy.packbits(mask, axis=-1); padding bits ignored) with at least
+    min_length points, in key order: every set pixel once, in order along its curve, curves split at junctions.  Returns
+    (records int32 [k, 4] or None, chain_offsets uint64 [k + 1], points int32, K, P): record j (start, end, points, flags)
+    has the points points[chain_offsets[j] : chain_offsets[j + 1]], pixel indices r * width + c.  With capacity /
+    point_capacity None everything is returned (k = K, len(points) = P); otherwise k = min(K, capacity), points holds the
+    positions below point_capacity that belong to those records, and K, P are still the true counts."""
+    b = np.ascontiguousarray(bits, dtype=np.uint8)
+    if b.size != height * ((width + 7) // 8):
+        raise ValueError(f"expected {height} rows of {(width + 7) // 8} bytes, got {b.size} bytes")
+    L = load()
+    k, n = C.c_ulonglong(0), C.c_ulonglong(0)
+    if capacity is None or point_capacity is None:
+        st = L.canny_hip_curves_from_bits(_hp(b), height, width, min_length, None, 0, C.byref(k), None, None, 0, C.byref(n))
+        if st:
+            raise CannyHipError(st, "curves_from_bits")
+    cap = k.value if capacity is None else int(capacity)
+    pcap = n.value if point_capacity is None else int(point_capacity)
+    records = np.empty((cap, CURVE_RECORD), np.int32) if want_records else None
+    chain = np.zeros(cap + 1, np.uint64)
+    points = np.empty(pcap, np.int32)
+    st = L.canny_hip_curves_from_bits(_hp(b), height, width, min_length, _hp(records) if want_records and cap else None, cap,
+                                      C.byref(k), _hp(chain), _hp(points) if pcap else None, pcap, C.byref(n))
+    if st:
+        raise CannyHipError(st, "curves_from_bits")
+    fit = min(cap, k.value)
+    return (records[:fit] if want_records else None, chain[:fit + 1], points[:min(pcap, int(chain[fit]))], k.value, n.value)
+
+
+def curves_plan(n_frames: int, height: int, width: int) -> "LaunchPlan":
+    """Host-only: the launch plan of the edge curves' row kernels (count and write: one wave per image row of the batch and
+    trip) for a batch of these sizes; fields as launch_plan."""
+    out = np.zeros(5, np.uint64)
+    st = load().canny_hip_selftest_curves_plan(int(n_frames), int(height), int(width), _hp(out))
+    if st:
+        raise CannyHipError(st, "selftest_curves_plan")
     return LaunchPlan(*(int(v) for v in out))
 
 
@@ -1509,6 +1563,71 @@ class Context:
         ms, n = C.c_double(0.0), C.c_long(0)
         self._check(self._L.canny_hip_contours_profile_get(self._h, part, C.byref(ms), C.byref(n)),
                     "contours_profile_get")
+        return ms.value, n.value
+
+    # ---- edge curves: the map linked into ordered chains ------------------------------------
+    def canny_curves(self, imgs, sigma: float, min_val: int, max_val: int, min_length: int = 1, want_records: bool = True,
+                     capacity: Optional[int] = None, point_capacity: Optional[int] = None):
+        """canny(), then the edge curves of each map with at least min_length points: imgs (H, W) or (N, H, W) uint8 ->
+        (records int32 [k, 4] or None, offsets uint64 [N + 1], chain_offsets uint64 [k + 1], points int32, point_offsets
+        uint64 [N + 1]).  Record j (offsets[f] <= j < offsets[f + 1] for frame f) is (start, end, points, flags) and has the
+        points points[chain_offsets[j] : chain_offsets[j + 1]], pixel indices r * W + c along the curve.  With both
+        capacities None a counts-only call sizes the buffers and everything is returned; otherwise k = min(offsets[-1],
+        capacity), points holds the positions below point_capacity of those records, and offsets / point_offsets still hold
+        the true counts."""
+        a = np.ascontiguousarray(imgs, dtype=np.uint8)
+        if a.ndim == 2:
+            a = a[None]
+        if a.ndim != 3:
+            raise ValueError("expected uint8 [H, W] or [n_frames, H, W]")
+        n, h, w = a.shape
+        offsets, point_offsets = np.zeros(n + 1, np.uint64), np.zeros(n + 1, np.uint64)
+
+        def call(records, cap, chain, points, pcap):
+            self._check(self._L.canny_hip_canny_curves(
+                self._h, _hp(a), n, sigma, min_val, max_val, h, w, min_length,
+                _hp(records) if records is not None and cap else None, cap, _hp(offsets),
+                _hp(chain) if chain is not None else None, _hp(points) if pcap else None, pcap, _hp(point_offsets)),
+                "canny_curves")
+
+        if capacity is None or point_capacity is None:
+            call(None, 0, None, None, 0)
+        cap = int(offsets[-1]) if capacity is None else int(capacity)
+        pcap = int(point_offsets[-1]) if point_capacity is None else int(point_capacity)
+        records = np.empty((cap, CURVE_RECORD), np.int32) if want_records else None
+        chain = np.zeros(cap + 1, np.uint64)
+        points = np.empty(pcap, np.int32)
+        call(records, cap, chain, points, pcap)
+        fit = min(cap, int(offsets[-1]))
+        return (records[:fit] if want_records else None, offsets, chain[:fit + 1], points[:min(pcap, int(chain[fit]))],
+                point_offsets)
+
+    def dev_canny_curves(self, d_img: int, sigma: float, min_val: int, max_val: int, h: int, w: int, n: int,
+                         min_length: int, d_records: int, capacity: int, d_offsets: int, d_chain_offsets: int,
+                         d_points: int, point_capacity: int, d_point_offsets: int, d_edges: int = 0):
+        """dev_canny, then the curves of its map on the same stream: d_records (capacity records of 4 int32) or 0,
+        d_offsets and d_point_offsets (n + 1 uint64 each), d_chain_offsets (capacity + 1 uint64) or 0 with capacity 0,
+        d_points (point_capacity int32) or 0 with point_capacity 0, d_edges (the s16 map) or 0 -- device pointers."""
+        v = C.c_void_p
+        self._check(self._L.canny_hip_dev_canny_curves(self._h, v(d_img or None), sigma, min_val, max_val, h, w, n,
+                                                       v(d_edges or None), min_length, v(d_records or None), capacity,
+                                                       v(d_offsets or None), v(d_chain_offsets or None),
+                                                       v(d_points or None), point_capacity, v(d_point_offsets or None)),
+                    "dev_canny_curves")
+
+    def dev_curves_bits(self, d_bits: int, h: int, w: int, n: int, min_length: int, d_records: int, capacity: int,
+                        d_offsets: int, d_chain_offsets: int, d_points: int, point_capacity: int, d_point_offsets: int):
+        """The curves alone on device bit maps (layout of dev_canny_bits, any byte alignment, padding ignored)."""
+        v = C.c_void_p
+        self._check(self._L.canny_hip_dev_curves_bits(self._h, v(d_bits or None), h, w, n, min_length,
+                                                      v(d_records or None), capacity, v(d_offsets or None),
+                                                      v(d_chain_offsets or None), v(d_points or None), point_capacity,
+                                                      v(d_point_offsets or None)), "dev_curves_bits")
+
+    def curves_profile_get(self, part: int) -> Tuple[float, int]:
+        """(total ms, launch groups) of part 0 count, 1 write (CURVE_PARTS)."""
+        ms, n = C.c_double(0.0), C.c_long(0)
+        self._check(self._L.canny_hip_curves_profile_get(self._h, part, C.byref(ms), C.byref(n)), "curves_profile_get")
         return ms.value, n.value
 
     # ---- polygon approximation of the contour chains (DESIGN.md section 19) ---------------------------------------

@@ -444,7 +444,8 @@ struct canny_hip_ctx {
     // three of the polygon approximation (canny_hip_polygons_profile_get), then the two of the sub-pixel edgels
     // (canny_hip_edgels_profile_get), then the one of the line fits (canny_hip_line_fits_profile_get), then the one of the
     // circle fits (canny_hip_circle_fits_profile_get), then the four of the chamfer matching
-    // (canny_hip_chamfer_profile_get), then the three of the contour shape measures (canny_hip_shapes_profile_get).  The mask is a non-negative int option: bit 30 is the last it can
+    // (canny_hip_chamfer_profile_get), then the three of the contour shape measures (canny_hip_shapes_profile_get), then the two of the edge curves
+    // (canny_hip_curves_profile_get).  The mask is a non-negative int option: bit 30 is the last it can
     // carry, and the three polygon slots, the two edgel slots, the line-fit slot and the circle-fit slot behind them go by
     // it together
     static constexpr int kProfHough = CANNY_HIP_STAGE_END, kProfComponents = CANNY_HIP_STAGE_END + 3;
@@ -458,7 +459,8 @@ struct canny_hip_ctx {
     static constexpr int kProfCircleFits = kProfLineFits + CANNY_HIP_LINE_FIT_PARTS;
     static constexpr int kProfChamfer = kProfCircleFits + CANNY_HIP_CIRCLE_FIT_PARTS;
     static constexpr int kProfShapes = kProfChamfer + CANNY_HIP_CHAMFER_PARTS;
-    static constexpr int kProfSlots = kProfShapes + CANNY_HIP_SHAPE_PARTS;
+    static constexpr int kProfCurves = kProfShapes + CANNY_HIP_SHAPE_PARTS;
+    static constexpr int kProfSlots = kProfCurves + CANNY_HIP_CURVE_PARTS;
     static constexpr int kProfLastBit = 30;
     static_assert(kProfPolygons == kProfLastBit && kProfEdgels > kProfLastBit,
                   "profile_stage_mask has one bit per slot up to the polygon parts; every slot from there on follows bit 30");
@@ -1330,6 +1332,71 @@ int dev_canny_contours(canny_hip_ctx *ctx, const unsigned char *d_img, float sig
         return CANNY_HIP_OK;
     }
     return dev_contours(ctx, (const uint64_t *)ctx->plane_s.p, nullptr, make_hyst_geom(h, w, n), min_area, out);
+}
+
+// ---- edge curves (canny_curves.hip) ----------------------------------------
+struct CvOut {
+    int *records;
+    unsigned long long capacity;
+    unsigned long long *offsets, *chain_offsets;
+    int *points;
+    unsigned long long point_capacity;
+    unsigned long long *point_offsets;
+};
+
+bool curve_args_ok(const CvOut &out)
+{
+    return out.offsets && out.point_offsets && (out.chain_offsets || !out.capacity) && (out.points || !out.point_capacity);
+}
+
+// The curves of one source (the context's strong plane or packed bits), queued on the context's stream: the count walks,
+// the two scans, and -- when records were asked for -- the write walks.  The row sums and frame totals live in the two
+// workspaces of the contour chains' scans; the count kernel writes every row's word before a scan reads it.
+int dev_curves(canny_hip_ctx *ctx, const uint64_t *strong, const uint8_t *bits, const HystGeom &g, int min_length,
+               const CvOut &out)
+{
+    const size_t rows = (size_t)g.n_frames * g.height;
+    const size_t ws_bytes = g.n_frames * sizeof(unsigned long long) + rows * sizeof(uint32_t);
+    HIP_TRY(ctx, ctx->cc_ws.ensure(ws_bytes));
+    HIP_TRY(ctx, ctx->ct_ws.ensure(ws_bytes));
+    unsigned long long *totals = (unsigned long long *)ctx->cc_ws.p, *point_totals = (unsigned long long *)ctx->ct_ws.p;
+    uint32_t *row_curves = (uint32_t *)(totals + g.n_frames), *row_points = (uint32_t *)(point_totals + g.n_frames);
+    {
+        StageTimer tm(ctx, canny_hip_ctx::kProfCurves + CANNY_HIP_CURVE_PART_COUNT);
+        HIP_TRY(ctx, launch_cv_count(strong, bits, g, min_length, row_curves, row_points, ctx->stream));
+        HIP_TRY(ctx, launch_points_scan(row_curves, totals, out.offsets, g.height, g.n_frames, ctx->stream));
+        HIP_TRY(ctx, launch_points_scan(row_points, point_totals, out.point_offsets, g.height, g.n_frames, ctx->stream));
+    }
+    if (out.capacity) {
+        StageTimer tm(ctx, canny_hip_ctx::kProfCurves + CANNY_HIP_CURVE_PART_WRITE);
+        HIP_TRY(ctx, launch_cv_write(strong, bits, g, min_length, row_curves, row_points, out.offsets, out.point_offsets,
+                                     out.chain_offsets, out.capacity, out.records, out.points, out.point_capacity,
+                                     ctx->stream));
+    } else if (out.chain_offsets) {
+        HIP_TRY(ctx, hipMemsetAsync(out.chain_offsets, 0, sizeof(unsigned long long), ctx->stream));
+    }
+    return CANNY_HIP_OK;
+}
+
+// dev_canny (unchanged), then the curves of its map from the converged strong plane.  The result follows the MAP:
+// max_val > 255 leaves no edge pixel (see dev_canny_points_count).
+int dev_canny_curves(canny_hip_ctx *ctx, const unsigned char *d_img, float sigma, int lo, int hi, int h, int w, int n,
+                     short *d_edges, int min_length, const CvOut &out)
+{
+    int rc;
+    if (!d_edges) {
+        HIP_TRY(ctx, ctx->edges16.ensure(npx(h, w, n) * sizeof(short)));
+        d_edges = (short *)ctx->edges16.p;
+    }
+    if ((rc = dev_canny(ctx, d_img, sigma, lo, hi, h, w, n, d_edges))) return rc;
+    if (hi > 255) {
+        const size_t off_bytes = ((size_t)n + 1) * sizeof(unsigned long long);
+        HIP_TRY(ctx, hipMemsetAsync(out.offsets, 0, off_bytes, ctx->stream));
+        HIP_TRY(ctx, hipMemsetAsync(out.point_offsets, 0, off_bytes, ctx->stream));
+        if (out.chain_offsets) HIP_TRY(ctx, hipMemsetAsync(out.chain_offsets, 0, sizeof(unsigned long long), ctx->stream));
+        return CANNY_HIP_OK;
+    }
+    return dev_curves(ctx, (const uint64_t *)ctx->plane_s.p, nullptr, make_hyst_geom(h, w, n), min_length, out);
 }
 
 // ---- polygon approximation of the chains (canny_polygons.hip) --------------
@@ -3740,6 +3807,95 @@ int canny_hip_contours_from_bits(const unsigned char *bits, int height, int widt
     return CANNY_HIP_OK;
 }
 
+// ---- edge curves -------------------------------------------------------------------------------------
+int canny_hip_dev_canny_curves(canny_hip_ctx *ctx, const unsigned char *d_img, float sigma, int min_val, int max_val,
+                               int height, int width, int n_frames, short *d_edges, int min_length, int *d_records,
+                               unsigned long long capacity, unsigned long long *d_offsets,
+                               unsigned long long *d_chain_offsets, int *d_points, unsigned long long point_capacity,
+                               unsigned long long *d_point_offsets)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    const CvOut out{d_records, capacity, d_offsets, d_chain_offsets, d_points, point_capacity, d_point_offsets};
+    if (!d_img || !curve_args_ok(out)) return CANNY_HIP_ERR_INVALID;
+    if ((rc = check_contour_dims(height, width, n_frames))) return rc;
+    return dev_canny_curves(ctx, d_img, sigma, min_val, max_val, height, width, n_frames, d_edges, min_length, out);
+}
+
+int canny_hip_dev_curves_bits(canny_hip_ctx *ctx, const unsigned char *d_bits, int height, int width, int n_frames,
+                              int min_length, int *d_records, unsigned long long capacity, unsigned long long *d_offsets,
+                              unsigned long long *d_chain_offsets, int *d_points, unsigned long long point_capacity,
+                              unsigned long long *d_point_offsets)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    const CvOut out{d_records, capacity, d_offsets, d_chain_offsets, d_points, point_capacity, d_point_offsets};
+    if (!d_bits || !curve_args_ok(out)) return CANNY_HIP_ERR_INVALID;
+    if ((rc = check_contour_dims(height, width, n_frames)) || (rc = finish_pending(ctx))) return rc;
+    return dev_curves(ctx, nullptr, d_bits, make_hyst_geom(height, width, n_frames), min_length, out);
+}
+
+int canny_hip_canny_curves(canny_hip_ctx *ctx, const unsigned char *imgs, int n_frames, float sigma, int min_val,
+                           int max_val, int height, int width, int min_length, int *records, unsigned long long capacity,
+                           unsigned long long *offsets, unsigned long long *chain_offsets, int *points,
+                           unsigned long long point_capacity, unsigned long long *point_offsets)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!imgs || !curve_args_ok(CvOut{records, capacity, offsets, chain_offsets, points, point_capacity, point_offsets}))
+        return CANNY_HIP_ERR_INVALID;
+    if ((rc = check_contour_dims(height, width, n_frames))) return rc;
+    const size_t n = npx(height, width, n_frames);
+    const size_t off_bytes = ((size_t)n_frames + 1) * sizeof(unsigned long long);
+    // a frame has no more than 2 curves and 4 curve points per pixel
+    const unsigned long long cap = std::min<unsigned long long>(capacity, 2ull * n);
+    const unsigned long long pcap = std::min<unsigned long long>(point_capacity, 4ull * n);
+    if ((rc = h2d(ctx, ctx->io[0], imgs, n))) return rc;
+    // one staging block: offsets | point_offsets | chain_offsets | records | points
+    auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+    const size_t poff_at = up16(off_bytes), chain_at = up16(poff_at + off_bytes);
+    const size_t recs_at = up16(chain_at + ((size_t)cap + 1) * sizeof(unsigned long long));
+    const size_t points_at = up16(recs_at + (records ? (size_t)cap * CANNY_HIP_CURVE_RECORD * sizeof(int) : 0));
+    HIP_TRY(ctx, ctx->io[1].ensure(points_at + (size_t)pcap * sizeof(int)));
+    char *d = (char *)ctx->io[1].p;
+    const CvOut out{records && cap ? (int *)(d + recs_at) : nullptr,
+                    cap,
+                    (unsigned long long *)d,
+                    (unsigned long long *)(d + chain_at),
+                    pcap ? (int *)(d + points_at) : nullptr,
+                    pcap,
+                    (unsigned long long *)(d + poff_at)};
+    if ((rc = dev_canny_curves(ctx, (const unsigned char *)ctx->io[0].p, sigma, min_val, max_val, height, width, n_frames,
+                               nullptr, min_length, out)))
+        return rc;
+    // the offsets come down first: they say how many records and points there are to download
+    std::vector<unsigned long long> off(2 * ((size_t)n_frames + 1));
+    HIP_TRY(ctx, hipMemcpyAsync(off.data(), out.offsets, off_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = d2h_sync(ctx, off.data() + n_frames + 1, out.point_offsets, off_bytes))) return rc;
+    const unsigned long long n_rec = std::min(off[n_frames], cap);
+    if (chain_offsets)
+        HIP_TRY(ctx, hipMemcpyAsync(chain_offsets, out.chain_offsets, ((size_t)n_rec + 1) * sizeof(unsigned long long),
+                                    hipMemcpyDeviceToHost, ctx->stream));
+    if (n_rec && out.records)
+        HIP_TRY(ctx, hipMemcpyAsync(records, out.records, (size_t)n_rec * CANNY_HIP_CURVE_RECORD * sizeof(int),
+                                    hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (n_rec && pcap) {
+        // chain_offsets is needed on the host to know where the records that fit end
+        unsigned long long end = 0;
+        HIP_TRY(ctx, hipMemcpyAsync(&end, out.chain_offsets + n_rec, sizeof end, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        const unsigned long long n_pts = std::min(end, pcap);
+        if (n_pts) {
+            HIP_TRY(ctx, hipMemcpyAsync(points, out.points, (size_t)n_pts * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        }
+    }
+    std::memcpy(offsets, off.data(), off_bytes);
+    std::memcpy(point_offsets, off.data() + n_frames + 1, off_bytes);
+    return CANNY_HIP_OK;
+}
+
 // ---- polygon approximation of the chains -------------------------------------------------------------
 int canny_hip_dev_polygons_chains(canny_hip_ctx *ctx, const unsigned long long *d_offsets, int n_frames,
                                   unsigned long long capacity, const unsigned long long *d_chain_offsets,
@@ -5568,6 +5724,26 @@ int canny_hip_shapes_profile_get(canny_hip_ctx *ctx, int part, double *total_ms,
     if ((rc = profile_collect(ctx))) return rc;
     *total_ms = ctx->total_ms[canny_hip_ctx::kProfShapes + part];
     *launches = ctx->launches[canny_hip_ctx::kProfShapes + part];
+    return CANNY_HIP_OK;
+}
+
+int canny_hip_curves_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches)
+{
+    if (part < 0 || part >= CANNY_HIP_CURVE_PARTS || !total_ms || !launches) return CANNY_HIP_ERR_INVALID;
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if ((rc = profile_collect(ctx))) return rc;
+    *total_ms = ctx->total_ms[canny_hip_ctx::kProfCurves + part];
+    *launches = ctx->launches[canny_hip_ctx::kProfCurves + part];
+    return CANNY_HIP_OK;
+}
+
+// Host-only: the launch plan of the edge curves' row kernels.
+int canny_hip_selftest_curves_plan(int n_frames, int height, int width, unsigned long long *out)
+{
+    if (!out || check_contour_dims(height, width, n_frames)) return CANNY_HIP_ERR_INVALID;
+    const LaunchPlan p = plan_cv_rows(make_hyst_geom(height, width, n_frames));
+    out[0] = p.units, out[1] = p.per_group, out[2] = p.grid, out[3] = p.trips(), out[4] = (unsigned long long)p.aux;
     return CANNY_HIP_OK;
 }
 

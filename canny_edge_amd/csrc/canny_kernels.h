@@ -525,6 +525,22 @@ hipError_t launch_ct_write(const uint64_t *strong, const uint8_t *bits, const Hy
                            unsigned long long *chain_offsets, unsigned long long capacity, int *points,
                            unsigned long long point_capacity, hipStream_t stream);
 
+// ---- Edge curves (canny_curves.hip) -------------------------------------
+// Source as for the point lists.  height * width <= kContourMaxPixels: a frame has at most 4 points per pixel and 2 curves
+// per pixel, and the per-frame sums of the scan are 32-bit.
+// count: row_curves[f * height + y] / row_points[f * height + y] = the kept curves (at least min_length points) that start
+// in that row / their points; every row's word is written (then launch_points_scan on each gives offsets / point_offsets).
+hipError_t launch_cv_count(const uint64_t *strong, const uint8_t *bits, const HystGeom &g, int min_length,
+                           uint32_t *row_curves, uint32_t *row_points, hipStream_t stream);
+// write: behind the two scans; chain_offsets[0] = 0, chain_offsets[j + 1] = the end of record j's points and records[4 * j
+// ..] (records may be null) for j < capacity (>= 1, chain_offsets not null), points[chain_offsets[j] + i] = the curve's i-th
+// pixel for positions below point_capacity (points may be null); nothing is stored past either capacity.
+hipError_t launch_cv_write(const uint64_t *strong, const uint8_t *bits, const HystGeom &g, int min_length,
+                           uint32_t *row_curves, uint32_t *row_points, const unsigned long long *offsets,
+                           const unsigned long long *point_offsets, unsigned long long *chain_offsets,
+                           unsigned long long capacity, int *records, int *points, unsigned long long point_capacity,
+                           hipStream_t stream);
+
 // ---- Polygon approximation of the chains (canny_polygons.hip) ----------
 // They read what a contours call stored: offsets (the record CSR, only offsets[n_frames] is used), chain_offsets and points.
 // R = min(offsets[n_frames], capacity) is read on the device.  height, width <= kPolygonMaxSide keep every cross product
@@ -660,6 +676,7 @@ LaunchPlan plan_cc_tiles(const HystGeom &g);       // cc init, merge, flatten, a
 LaunchPlan plan_cc_rows(const HystGeom &g);        // cc count, number: image rows of the batch
 LaunchPlan plan_cc_fixup(unsigned long long capacity); // cc_fixup_kernel: record slots
 LaunchPlan plan_ct_rows(const HystGeom &g);        // contour walk (count, write), place: image rows of the batch
+LaunchPlan plan_cv_rows(const HystGeom &g);        // curve walks (count, write): image rows of the batch
 LaunchPlan plan_edt_rows(const HystGeom &g);       // edt rows: groups of aux consecutive rows
 LaunchPlan plan_edt_columns(const HystGeom &g);    // edt columns: 64-column strips of the batch
 LaunchPlan plan_pg_records(unsigned long long capacity);   // polygon simplify, emit: record slots

@@ -1,6 +1,6 @@
 // main.cpp -- the reference's command line (StevenChang5/Canny_Edge src/main.cpp:18-142) without
 // the webcam and the GUI:  ./Main sigma minVal maxVal [-c] [-s] [-i in.pgm|in.ppm|in.jpg] [-o dir] [-p] [-n WxH] [-b dir]
-//        [-l rho,theta_degrees,threshold[,lines_max]] [-g min_length,max_gap[,exclusive]] [-m min_area] [-t] [-d] [-e]
+//        [-l rho,theta_degrees,threshold[,lines_max]] [-g min_length,max_gap[,exclusive]] [-m min_area] [-t] [-w min_length] [-d] [-e]
 //        [-r min_radius,max_radius,threshold,support[,min_dist[,cell_shift]]] [-y epsilon[,ratio]] [-u]
 //
 // Kept from the reference: the three positionals may appear anywhere relative to the flags
@@ -22,6 +22,10 @@
 // with fewer than min_area pixels and writes one "label left top width height area" row per kept component to
 // canny_components.txt and the filtered map to canny_kept.pgm (.png with -p) in the -o directory (rows to stdout without
 // -o).  Without -m nothing changes.
+// Added: -w min_length links the frame's edge map into curves on the GPU (canny_hip_canny_curves): every edge pixel once, in
+// order along its curve, curves split at junctions; one "start end points flags x0 y0 x1 y1 ..." line per curve with at
+// least min_length points goes to canny_curves.txt (start and end are pixel indices r * width + c; flags:
+// canny_hip_curve_flag).  A malformed -w is a usage error (exit status 2).  Without -w nothing changes.
 // Added: -t follows the outer border of every component of the frame's edge map with at least min_area pixels (-m, default
 // 1) on the GPU (canny_hip_canny_contours) and writes one "label n x0 y0 x1 y1 ..." line per contour to canny_contours.txt
 // in the -o directory (stdout without -o).
@@ -436,6 +440,49 @@ static int run_contours(const vector<unsigned char> &frame, int height, int widt
     return 0;
 }
 
+// -w: the edge curves of the frame's map with at least min_length points, one "start end points flags x0 y0 x1 y1 ..." line
+// each: the record (start and end as pixel indices r * width + c), then the points
+static int run_curves(const vector<unsigned char> &frame, int height, int width, float sigma, int minVal, int maxVal,
+                      int min_length, const string &outdir)
+{
+    vector<unsigned long long> chain(1, 0);
+    vector<int> points, records;
+    unsigned long long offsets[2] = {0, 0}, point_offsets[2] = {0, 0};
+    canny_hip_ctx *ctx = nullptr;
+    int st = canny_hip_ctx_create(&ctx, 0);
+    // counts first, then exactly the curves there are
+    if (!st)
+        st = canny_hip_canny_curves(ctx, frame.data(), 1, sigma, minVal, maxVal, height, width, min_length, nullptr, 0,
+                                    offsets, nullptr, nullptr, 0, point_offsets);
+    if (!st) {
+        chain.resize((size_t)offsets[1] + 1);
+        records.resize((size_t)offsets[1] * CANNY_HIP_CURVE_RECORD + 1);
+        points.resize((size_t)point_offsets[1] + 1);
+        st = canny_hip_canny_curves(ctx, frame.data(), 1, sigma, minVal, maxVal, height, width, min_length, records.data(),
+                                    offsets[1], offsets, chain.data(), points.data(), point_offsets[1], point_offsets);
+    }
+    if (st) {
+        fprintf(stderr, "ERROR: -w: %s\n", st == CANNY_HIP_ERR_RUNTIME && ctx ? canny_hip_last_error(ctx) : canny_hip_status_string(st));
+        if (ctx) canny_hip_ctx_destroy(ctx);
+        return 1;
+    }
+    canny_hip_ctx_destroy(ctx);
+    FILE *f = outdir.empty() ? stdout : fopen((outdir + "/canny_curves.txt").c_str(), "w");
+    if (!f) {
+        fprintf(stderr, "ERROR: cannot write %s/canny_curves.txt\n", outdir.c_str());
+        return 1;
+    }
+    for (unsigned long long k = 0; k < offsets[1]; k++) {
+        const int *rec = records.data() + k * CANNY_HIP_CURVE_RECORD;
+        fprintf(f, "%d %d %d %d", rec[CANNY_HIP_CURVE_START], rec[CANNY_HIP_CURVE_END], rec[CANNY_HIP_CURVE_POINTS],
+                rec[CANNY_HIP_CURVE_FLAGS]);
+        for (unsigned long long q = chain[k]; q < chain[k + 1]; q++) fprintf(f, " %d %d", points[q] % width, points[q] / width);
+        fprintf(f, "\n");
+    }
+    if (f != stdout) fclose(f);
+    return 0;
+}
+
 // -e: one sub-pixel edgel per edge pixel of the frame's map, in raster order: "x y gx gy mag dir refined" each.
 static int run_edgels(const vector<unsigned char> &frame, int height, int width, float sigma, int minVal, int maxVal,
                       const string &outdir)
@@ -725,6 +772,8 @@ int main(int argc, char *argv[])
     int min_area = 1;
     bool want_dist = false;
     bool want_contours = false;
+    bool want_curves = false;
+    int curve_min_length = 1;
     bool want_circles = false;
     bool want_polygons = false;
     bool want_shapes = false;
@@ -877,6 +926,13 @@ int main(int argc, char *argv[])
             want_dist = true;
         } else if (arg == "-t") {
             want_contours = true;
+        } else if (arg == "-w" && i + 1 < argc) {
+            char tail = 0; // a whole integer only
+            if (sscanf(argv[++i], "%d%c", &curve_min_length, &tail) != 1) {
+                fprintf(stderr, "ERROR: -w expects min_length\n");
+                exit(2);
+            }
+            want_curves = true;
         } else if (arg == "-e") {
             want_edgels = true;
         } else if (arg == "-n" && i + 1 < argc) {
@@ -929,6 +985,9 @@ int main(int argc, char *argv[])
         fprintf(stderr, "                canny_kept.pgm in the -o dir\n");
         fprintf(stderr, "   -t: outer contour chain of every component with at least min_area (-m, default 1) pixels, one\n");
         fprintf(stderr, "       \"label n x0 y0 x1 y1 ...\" line each -> canny_contours.txt in the -o dir\n");
+        fprintf(stderr, "   -w min_length: edge curves of the edge map with at least min_length points (every edge pixel once, in order\n");
+        fprintf(stderr, "       along its curve, split at junctions), one \"start end points flags x0 y0 x1 y1 ...\" line each ->\n");
+        fprintf(stderr, "       canny_curves.txt in the -o dir\n");
         fprintf(stderr, "   -y epsilon[,ratio]: with -t, the polygon of every contour at a tolerance of epsilon pixels plus ratio times\n");
         fprintf(stderr, "       its length, one \"frame record vertices length area2 convex x0 y0 x1 y1 ...\" line each (length in 1/256\n");
         fprintf(stderr, "       pixel, area2 twice the area) -> canny_polygons.txt in the -o dir\n");
@@ -1005,6 +1064,10 @@ int main(int argc, char *argv[])
     }
     if (want_contours) {
         const int rc = run_contours(frame, height, width, sigma, minVal, maxVal, min_area, outdir);
+        if (rc) return rc;
+    }
+    if (want_curves) {
+        const int rc = run_curves(frame, height, width, sigma, minVal, maxVal, curve_min_length, outdir);
         if (rc) return rc;
     }
     if (want_polygons) {

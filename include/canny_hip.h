@@ -52,7 +52,8 @@
 extern "C" {
 #endif
 
-#define CANNY_HIP_VERSION 1700       /* 0.17.0: + contour shape measures: moments, convex hull, minimum-area rectangle */
+#define CANNY_HIP_VERSION 1800       /* 0.18.0: + edge curves: the edge map linked into ordered chains */
+/* 0.17.0: + contour shape measures: moments, convex hull, minimum-area rectangle */
 /* 0.16.0: + chamfer template matching on the distance transform */
 /* 0.15.0: + sub-pixel circle fits: least-squares refit of Hough circles from edgels */
 /* 0.13.0: + sub-pixel edgels: position, gradient and strength per edge pixel */
@@ -1444,6 +1445,120 @@ int canny_hip_shapes_from_chains(const unsigned long long *chain_offsets, const 
                                  unsigned long long point_capacity, int width, int height, unsigned long long *hull_offsets,
                                  int *hull, unsigned long long hull_capacity, long long *measures);
 
+/* ---- edge curves: the edge map linked into ordered chains ------------------------------------------------------------------
+ * Edge linking, per frame of a batch, on the GPU, queued behind the detector on the same stream with no host round trip:
+ * every edge pixel is taken ONCE, in order along its curve; curves are split where they meet; open and closed curves are
+ * told apart -- what curve fitting to the edges, skeleton graphs and vector export start from (the use of Kovesi's
+ * edgelink after a Canny map).  A contour chain (the section above the polygons) is the border of a component and walks a
+ * one-pixel curve out and back; a curve lists it once.  THE RULE, for frame f with edge map E_f
+ * (the map canny_hip_canny returns for that frame, bit for bit).  It is all integers and purely a function of the map.
+ *   Directions are those of the contour chains: 0 = E (0,+1), 1 = SE (+1,+1), 2 = S (+1,0), 3 = SW (+1,-1), 4 = W (0,-1),
+ *     5 = NW (-1,-1), 6 = N (-1,0), 7 = NE (-1,+1), as (row, column) steps.  Pixels outside the frame are unset.  Frames
+ *     never see each other.  index(p) = r * width + c.
+ *   1. Links.  Two set 8-neighbours are LINKED if they are 4-neighbours; diagonal neighbours are linked only if neither of
+ *      the two pixels 4-adjacent to both is set (a diagonal that a staircase corner already bridges is not a link).  As a
+ *      byte operation on the 3 x 3 ring r of a set pixel (bit d = the neighbour in direction d is set):
+ *        links = r & (0x55 | ~(rotl8(r, 1) | rotr8(r, 1))).
+ *      deg(p) = popcount(links).  deg <= 4, and the components of the link graph are the 8-connected components.
+ *   2. Nodes.  A NODE is a set pixel with deg != 2: an isolated pixel (0), a curve end (1) or a junction (3 or 4).  Every
+ *      other set pixel is a PATH PIXEL.
+ *   3. Curves.
+ *      Isolated pixel p: the curve [p], key 8 * index(p).
+ *      Open curve: from a node p along a link in direction d, step to the neighbour; while that pixel is a path pixel,
+ *        leave it by its other link.  The walk ends at a node e, entered by a link that points back from e in direction
+ *        d' (the last step's direction + 4, mod 8).  p and e may be the same junction: a loop hanging on it.  The path has
+ *        two descriptors with the keys 8 * index(p) + d and 8 * index(e) + d', which always differ; the curve is emitted
+ *        once, from the smaller key, as p, the path pixels in walking order, e.  So a junction pixel ends deg curves, and
+ *        a curve between two adjacent nodes has two points.
+ *      Closed curve: a component of the link graph made of path pixels only.  It starts at its smallest index p0, whose
+ *        two links lie among directions 0 .. 3, leaves by the smaller of the two, d, and lists every pixel once; p0 is not
+ *        repeated.  Its key is 8 * index(p0) + d.
+ *      Every link lies on exactly one curve; every path pixel and every isolated pixel is listed exactly once; a node of
+ *      degree k >= 1 is listed k times, always as a first or last point; consecutive points are linked.
+ *   4. Selection and order.  A curve is kept if it has at least min_length points; min_length <= 1 keeps all.  Dropping a
+ *      short curve (a spur) does NOT re-link what remains across the junction: the junction stays a node and the curves
+ *      that meet there stay split.  Within a frame the kept curves are ordered by key (start index, then first
+ *      direction), ascending; across the batch by frame.
+ *   5. Record: CANNY_HIP_CURVE_RECORD = 4 ints per kept curve -- start, end, points, flags (enum canny_hip_curve_field).
+ *      For a closed curve `end` is the last listed pixel; for an isolated pixel end == start.  flags: enum
+ *      canny_hip_curve_flag; the last direction is that of the step that reaches `end`; both direction fields are 0 when
+ *      there is no step.
+ *   Outputs, the two-level CSR of the contour chains (all offsets unsigned long long), so that canny_hip_dev_edgels_at,
+ *   canny_hip_dev_polygons_chains and canny_hip_dev_shapes_chains take them as they are (the latter two treat every chain
+ *   as closed):
+ *     offsets[0 .. n_frames]: records per frame, point_offsets[0 .. n_frames]: points per frame -- always the TRUE counts,
+ *       both mandatory.  K = offsets[n_frames].  A counts-only call (capacity = 0, point_capacity = 0, the other pointers
+ *       NULL) sizes the buffers.
+ *     chain_offsets[j] for j = 0 .. min(K, capacity): the points of records 0 .. j - 1, true prefix sums over the whole
+ *       batch.  Entries past min(K, capacity) are not written.
+ *     points (int): position q is written iff q < point_capacity and it belongs to a record < capacity: a chain may be
+ *       cut, nothing is written at or past points + point_capacity.
+ *     records (optional, may be NULL at any capacity): 4 ints per curve, bounded by capacity.
+ *   points == NULL with point_capacity > 0 and chain_offsets == NULL with capacity > 0 are CANNY_HIP_ERR_INVALID.
+ *   The result follows the MAP: max_val > 255 empties every map, so all offsets and point_offsets are 0 (and
+ *     chain_offsets[0] = 0 if given).
+ *   Limits: height * width <= 2^28, beyond that CANNY_HIP_ERR_UNSUPPORTED before anything is queued (a frame has at most 4
+ *     points per pixel and 2 records per pixel, which fit the 32-bit row sums below that).  Otherwise the statuses are
+ *     those of canny_hip_dev_canny for the same arguments, which runs first; on a status other than OK nothing is written.
+ *   The output is the same bytes on every run and machine: record numbers and positions are prefix sums in key order,
+ *     every word is stored once by the one thread that owns its curve, no atomic and no counter hands out space, and the
+ *     launches depend on the shapes and on which outputs were asked for, never on the data.
+ * Memory: two context workspaces of 4 bytes per image row and 8 bytes per frame (those of the contour chains' scans).
+ * Cost: a curve is walked by ONE thread, from both of its ends, in the count pass and again in the write pass, which
+ *   walks the owned curves once more to store them; a call takes as long as its longest curve.  DESIGN.md section 28 has
+ *   the measured time per step.
+ * The two parts are timed by canny_hip_curves_profile_get (CANNY_HIP_CURVE_PART_*); with "profile_stage_mask" they go by
+ *   bit 30, like every part added after the polygons.
+ * Not covered -- follow-ups: spur pruning WITH re-linking across the junction, an open-curve mode for the polygons and the
+ * shape measures, parallel ranking of long curves, the three-stream batch pipeline, the multi-GPU sharder, colour and
+ * per-frame / automatic-threshold variants. */
+#define CANNY_HIP_CURVE_RECORD 4
+enum canny_hip_curve_field {
+    CANNY_HIP_CURVE_START = 0,   /* index of the first point */
+    CANNY_HIP_CURVE_END = 1,     /* index of the last listed point */
+    CANNY_HIP_CURVE_POINTS = 2,  /* number of points */
+    CANNY_HIP_CURVE_FLAGS = 3
+};
+enum canny_hip_curve_flag {
+    CANNY_HIP_CURVE_CLOSED = 1,          /* bit 0: a closed curve */
+    CANNY_HIP_CURVE_START_JUNCTION = 2,  /* bit 1: the start is a junction (deg >= 3) */
+    CANNY_HIP_CURVE_END_JUNCTION = 4,    /* bit 2: the end is a junction */
+    CANNY_HIP_CURVE_ISOLATED = 8,        /* bit 3: an isolated pixel */
+    CANNY_HIP_CURVE_FIRST_DIR_SHIFT = 4, /* bits 4 .. 6: the direction of the first step */
+    CANNY_HIP_CURVE_LAST_DIR_SHIFT = 8,  /* bits 8 .. 10: the direction of the last step */
+    CANNY_HIP_CURVE_DIR_MASK = 7
+};
+enum canny_hip_curve_part {
+    CANNY_HIP_CURVE_PART_COUNT = 0,  /* first walks: kept curves and their points per row, scanned: offsets, point_offsets */
+    CANNY_HIP_CURVE_PART_WRITE = 1,  /* the walks again: record numbers and chain_offsets, then records and points stored */
+    CANNY_HIP_CURVE_PARTS = 2
+};
+/* Device buffers, asynchronous; completion contract and d_edges as canny_hip_dev_canny_points.  canny_hip_dev_canny itself
+ * queues exactly what it queues on its own; the walks read the converged hysteresis bit-plane behind it. */
+int canny_hip_dev_canny_curves(canny_hip_ctx *ctx, const unsigned char *d_img, float sigma, int min_val, int max_val,
+                               int height, int width, int n_frames, short *d_edges, int min_length, int *d_records,
+                               unsigned long long capacity, unsigned long long *d_offsets,
+                               unsigned long long *d_chain_offsets, int *d_points, unsigned long long point_capacity,
+                               unsigned long long *d_point_offsets);
+/* The curves alone, on device bit maps in the layout of canny_hip_dev_canny_bits (rows MSB-first, padded to bytes; any
+ * byte alignment; the padding bits of a row are ignored, whatever they hold).  Asynchronous. */
+int canny_hip_dev_curves_bits(canny_hip_ctx *ctx, const unsigned char *d_bits, int height, int width, int n_frames,
+                              int min_length, int *d_records, unsigned long long capacity, unsigned long long *d_offsets,
+                              unsigned long long *d_chain_offsets, int *d_points, unsigned long long point_capacity,
+                              unsigned long long *d_point_offsets);
+/* Host buffers, synchronous: upload, canny, curves; offsets and point_offsets come down first, then what fits:
+ * min(K, capacity) + 1 chain offsets, as many records, and the points below min(chain_offsets[min(K, capacity)],
+ * point_capacity). */
+int canny_hip_canny_curves(canny_hip_ctx *ctx, const unsigned char *imgs, int n_frames, float sigma, int min_val,
+                           int max_val, int height, int width, int min_length, int *records, unsigned long long capacity,
+                           unsigned long long *offsets, unsigned long long *chain_offsets, int *points,
+                           unsigned long long point_capacity, unsigned long long *point_offsets);
+/* Host-only, needs no device: the same rule on ONE host bit map, in plain C++.  *count receives the true number of kept
+ * curves, *point_count the true number of their points; both are mandatory. */
+int canny_hip_curves_from_bits(const unsigned char *bits, int height, int width, int min_length, int *records,
+                               unsigned long long capacity, unsigned long long *count, unsigned long long *chain_offsets,
+                               int *points, unsigned long long point_capacity, unsigned long long *point_count);
+
 /* ---- Euclidean distance transform ----------------------------------------------------------------------------------------
  * For every pixel of every frame the distance to the nearest edge pixel, on the GPU, queued behind the detector on the same
  * stream with no host round trip: what chamfer and template matching, edge-based registration, "snap to the nearest edge" and
@@ -1631,6 +1746,8 @@ int canny_hip_circle_fits_profile_get(canny_hip_ctx *ctx, int part, double *tota
 int canny_hip_chamfer_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches);
 /* ... and for the three parts of the contour shape measures (CANNY_HIP_SHAPE_PART_*). */
 int canny_hip_shapes_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches);
+/* ... and for the two parts of the edge curves (CANNY_HIP_CURVE_PART_*). */
+int canny_hip_curves_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches);
 
 /* ---- self-test hooks used by the GPU test-suite -------------------------------------------- */
 /* Runs the DEVICE magnitude / angle-bin functions over every (gx,gy) in [-lim,lim]^2 and writes
@@ -1769,6 +1886,10 @@ int canny_hip_selftest_chamfer_bands(const int *offsets, const short *points, in
  *     workgroup, 256 chunks per trip. */
 enum canny_hip_shapes_plan { CANNY_HIP_SHAPES_PLAN_RECORDS = 0, CANNY_HIP_SHAPES_PLAN_SCAN_SUMS = 1 };
 int canny_hip_selftest_shapes_plan(int which, unsigned long long capacity, unsigned long long *out);
+/* Host-only, the same five outputs for the one capped launch shape of the edge curves (it has no kind above): the count
+ * and the write kernel walk the image rows of the batch, one wave per row and trip, 4 rows per workgroup, at most 65536
+ * workgroups.  Sized by n_frames, height, width, valid as for a curves call. */
+int canny_hip_selftest_curves_plan(int n_frames, int height, int width, unsigned long long *out);
 
 #ifdef __cplusplus
 }
