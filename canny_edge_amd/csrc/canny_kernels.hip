@@ -10,6 +10,7 @@
 //   * Three different border conventions (H4 in SURVEY.md): Gaussian = truncate + renormalise,
 //     Sobel = clamp in-axis + drop off-axis, NMS / hysteresis = skip.
 #include "canny_kernels.h"
+#include "canny_tile_div.h"
 
 #include <hip/hip_ext.h>
 
@@ -662,17 +663,21 @@ __global__ __launch_bounds__(256) void hyst_classify_kernel(const int16_t *__res
 }
 
 // row above / below (lane = row) through wave-wide DPP shifts; the wave's end lanes read 0
+__device__ __forceinline__ unsigned row_above_u32(unsigned v)
+{
+    return (unsigned)__builtin_amdgcn_mov_dpp((int)v, 0x138 /* wave_shr:1 */, 0xf, 0xf, true);
+}
+__device__ __forceinline__ unsigned row_below_u32(unsigned v)
+{
+    return (unsigned)__builtin_amdgcn_mov_dpp((int)v, 0x130 /* wave_shl:1 */, 0xf, 0xf, true);
+}
 __device__ __forceinline__ uint64_t row_above_u64(uint64_t v)
 {
-    unsigned lo = (unsigned)__builtin_amdgcn_mov_dpp((int)(unsigned)v, 0x138 /* wave_shr:1 */, 0xf, 0xf, true);
-    unsigned hi = (unsigned)__builtin_amdgcn_mov_dpp((int)(unsigned)(v >> 32), 0x138, 0xf, 0xf, true);
-    return ((uint64_t)hi << 32) | lo;
+    return ((uint64_t)row_above_u32((unsigned)(v >> 32)) << 32) | row_above_u32((unsigned)v);
 }
 __device__ __forceinline__ uint64_t row_below_u64(uint64_t v)
 {
-    unsigned lo = (unsigned)__builtin_amdgcn_mov_dpp((int)(unsigned)v, 0x130 /* wave_shl:1 */, 0xf, 0xf, true);
-    unsigned hi = (unsigned)__builtin_amdgcn_mov_dpp((int)(unsigned)(v >> 32), 0x130, 0xf, 0xf, true);
-    return ((uint64_t)hi << 32) | lo;
+    return ((uint64_t)row_below_u32((unsigned)(v >> 32)) << 32) | row_below_u32((unsigned)v);
 }
 
 // Row flood: every run of ones in p that contains a bit of g (g is a subset of p) becomes selected entirely.
@@ -717,7 +722,57 @@ __device__ __forceinline__ HystSched make_sched(unsigned *words, int tiles)
 
 // edges (may be null): edge map that already holds the initially strong pixels (written by the kernel that
 // filled the planes); every pixel this sweep promotes is written there at once, so no finalize pass is needed.
-// A tile's own strong words and what it sees of its eight neighbours, as loaded (nothing here waits for memory).
+// Where a tile lies: its number in the batch, its frame, and its row and column among the frame's tiles.  Worked out
+// once per tile and handed to load_tile() and process_tile_with() both, and without a division: the quotients come
+// from the reciprocals the launchers prepare (canny_tile_div.h; a division by a kernel argument is a chain of ~25
+// scalar instructions, and a tile used to pay two or three of them).
+struct TilePos {
+    int t, f, ty, tx;
+};
+struct HystDiv {
+    TileDiv by_frame, by_row; // tile number / tiles per frame; tile number within the frame / tiles_x
+};
+inline HystDiv make_hyst_div(const HystGeom &g)
+{
+    HystDiv dv;
+    dv.by_frame = make_tile_div(g.tiles_x * g.tiles_y);
+    dv.by_row = make_tile_div(g.tiles_x);
+    return dv;
+}
+// tt = the tile's number within frame f
+__device__ __forceinline__ TilePos tile_pos(int t, int f, int tt, const HystGeom &g, const HystDiv &dv)
+{
+    TilePos p;
+    p.t = t;
+    p.f = f;
+    p.ty = (int)tile_div((unsigned)tt, dv.by_row);
+    p.tx = tt - p.ty * g.tiles_x;
+    return p;
+}
+__device__ __forceinline__ TilePos tile_pos(int t, const HystGeom &g, const HystDiv &dv)
+{
+    const int f = (int)tile_div((unsigned)t, dv.by_frame);
+    return tile_pos(t, f, t - f * (g.tiles_x * g.tiles_y), g, dv);
+}
+// the tile after p in the batch's order: the next column, the next tile row, the next frame
+__device__ __forceinline__ TilePos next_tile(TilePos p, const HystGeom &g)
+{
+    p.t++;
+    if (++p.tx == g.tiles_x) {
+        p.tx = 0;
+        if (++p.ty == g.tiles_y) {
+            p.ty = 0;
+            p.f++;
+        }
+    }
+    return p;
+}
+
+// A tile's own strong words and what it sees of its eight neighbours.  load_tile() issues every load of the tile before
+// it uses the result of any: the halo words come back raw, each under its condition, and their bits are taken out
+// behind the last load, so a tile waits for memory once.  (With the shift or mask inside the conditional expression the
+// compiler put the load's wait there too, and a tile that needed its left and right neighbours paid two round trips
+// one after the other, with corners three or four.)
 struct TileIn {
     uint64_t s0, su, sd;          // own word; bottom row of the tile above; top row of the tile below
     unsigned lb, rb;              // this row's column 63 of the left tile / column 0 of the right tile
@@ -731,30 +786,44 @@ struct TileIn {
 // that neighbour is not read at all.  The left and right neighbours are the expensive ones: a whole tile (512 bytes)
 // each for one bit per row, as much as the tile's own two words.
 constexpr uint64_t kAllHalo = ~0ull;
-__device__ __forceinline__ TileIn load_tile(int t, int lane, const uint64_t *__restrict__ strong, const HystGeom &g,
-                                            uint64_t c = kAllHalo)
+__device__ __forceinline__ TileIn load_tile(const TilePos &p, int lane, const uint64_t *__restrict__ strong,
+                                            const HystGeom &g, uint64_t c = kAllHalo)
 {
-    const int tpf = g.tiles_x * g.tiles_y;
-    const int tt = t % tpf;
-    const int ty = tt / g.tiles_x, tx = tt - ty * g.tiles_x;
+    const int ty = p.ty, tx = p.tx;
     const uint64_t c_top = readlane_u64(c, 0), c_bot = readlane_u64(c, 63); // wave-uniform
     const bool needL = __any((c & 1ull) != 0), needR = __any((c >> 63) != 0);
     const bool hasU = ty > 0 && c_top != 0, hasD = ty < g.tiles_y - 1 && c_bot != 0;
     const bool hasL = tx > 0 && needL, hasR = tx < g.tiles_x - 1 && needR;
-    const size_t base = (size_t)t * kTile;
+    // three bases -- this tile, the tile above, the tile below -- and constant distances from them
     const size_t rowstep = (size_t)g.tiles_x * kTile; // words between vertically adjacent tiles
+    const uint64_t *const own = strong + (size_t)p.t * kTile, *const up = own - rowstep, *const dn = own + rowstep;
     TileIn in;
-    in.s0 = strong[base + lane];
+    in.s0 = own[lane];
     // halo from the eight neighbouring tiles (read once per sweep; a change made there during
     // this sweep re-stamps us for the next one)
-    in.su = hasU ? strong[base - rowstep + 63] : 0;
-    in.sd = hasD ? strong[base + rowstep] : 0;
-    in.lb = hasL ? (unsigned)(strong[base - kTile + lane] >> 63) : 0u;
-    in.rb = hasR ? (unsigned)(strong[base + kTile + lane] & 1u) : 0u;
-    in.ul = (hasU && hasL && (c_top & 1ull)) ? (unsigned)(strong[base - rowstep - kTile + 63] >> 63) : 0u;
-    in.ur = (hasU && hasR && (c_top >> 63)) ? (unsigned)(strong[base - rowstep + kTile + 63] & 1u) : 0u;
-    in.dl = (hasD && hasL && (c_bot & 1ull)) ? (unsigned)(strong[base + rowstep - kTile] >> 63) : 0u;
-    in.dr = (hasD && hasR && (c_bot >> 63)) ? (unsigned)(strong[base + rowstep + kTile] & 1u) : 0u;
+    in.su = hasU ? up[63] : 0;
+    in.sd = hasD ? dn[0] : 0;
+    // the 32-bit half of a word that holds its column 63 (hi) / column 0 (lo); may_alias: these are the words the
+    // sweeps store as uint64_t, and a load the compiler believes unrelated to those stores may go through the scalar
+    // cache, which does not see them
+    typedef unsigned __attribute__((may_alias)) half_t;
+    auto hi = [](const uint64_t *word) { return ((const half_t *)word)[1]; };
+    auto lo = [](const uint64_t *word) { return ((const half_t *)word)[0]; };
+    unsigned wl = 0, wr = 0, wul = 0, wur = 0, wdl = 0, wdr = 0;
+    if (hasL) wl = hi(own - kTile + lane);
+    if (hasR) wr = lo(own + kTile + lane);
+    if (hasU && hasL && (c_top & 1ull)) wul = hi(up - kTile + 63);
+    if (hasU && hasR && (c_top >> 63)) wur = lo(up + kTile + 63);
+    if (hasD && hasL && (c_bot & 1ull)) wdl = hi(dn - kTile);
+    if (hasD && hasR && (c_bot >> 63)) wdr = lo(dn + kTile);
+    // pinned: the bits are taken out here, behind the last load, and not in the branches above
+    asm volatile("" : "+v"(wl), "+v"(wr), "+v"(wul), "+v"(wur), "+v"(wdl), "+v"(wdr));
+    in.lb = wl >> 31;
+    in.rb = wr & 1u;
+    in.ul = wul >> 31;
+    in.ur = wur & 1u;
+    in.dl = wdl >> 31;
+    in.dr = wdr & 1u;
     return in;
 }
 
@@ -780,19 +849,18 @@ __device__ __forceinline__ void push_neighbours(bool want, int lane, unsigned *s
 // different neighbour tile nb) schedule nb for sweep iter + 1 (once per sweep), and the caller's record of the last
 // sweep that scheduled anything is brought up to date if any lane wants to.
 template <class Push>
-__device__ __forceinline__ void process_tile_with(int t, int lane, uint64_t *__restrict__ strong, int iter,
+__device__ __forceinline__ void process_tile_with(const TilePos &p, int lane, uint64_t *__restrict__ strong, int iter,
                                                   const HystGeom &g, int16_t *__restrict__ edges, int edge_value,
                                                   uint64_t c, const TileIn &in, Push push_tiles)
 {
-    const int tpf = g.tiles_x * g.tiles_y;
-    const int tt = t % tpf;
-    const int ty = tt / g.tiles_x, tx = tt - ty * g.tiles_x;
+    const int t = p.t, ty = p.ty, tx = p.tx;
     const bool hasU = ty > 0, hasD = ty < g.tiles_y - 1, hasL = tx > 0, hasR = tx < g.tiles_x - 1;
     const size_t base = (size_t)t * kTile;
     const uint64_t s0 = in.s0, su = in.su, sd = in.sd;
     const unsigned lb = in.lb, rb = in.rb, ul = in.ul, ur = in.ur, dl = in.dl, dr = in.dr;
-    unsigned lb_up = __shfl_up(lb, 1), lb_dn = __shfl_down(lb, 1);
-    unsigned rb_up = __shfl_up(rb, 1), rb_dn = __shfl_down(rb, 1);
+    // the rows above and below (DPP, as in the flood; what the wave's end lanes get is replaced by the corners)
+    unsigned lb_up = row_above_u32(lb), lb_dn = row_below_u32(lb);
+    unsigned rb_up = row_above_u32(rb), rb_dn = row_below_u32(rb);
     if (lane == 0) { lb_up = ul; rb_up = ur; }
     if (lane == 63) { lb_dn = dl; rb_dn = dr; }
     const uint64_t in_left = (uint64_t)(lb | lb_up | lb_dn);         // enters at bit 0
@@ -825,7 +893,7 @@ __device__ __forceinline__ void process_tile_with(int t, int lane, uint64_t *__r
         if (edges) {
             // (padding bits are never connectable, so every set bit lies inside the image; the row and column tests
             // only keep a corrupted plane from turning into an out-of-bounds store)
-            const int f = t / tpf;
+            const int f = p.f;
             const int cols = min(kTile, g.width - tx * kTile), rows = min(kTile, g.height - ty * kTile);
             int16_t *const tile0 = edges + ((size_t)f * g.height + (size_t)ty * kTile) * g.width + tx * kTile;
             if (__popcll(rows_changed) <= 16) {
@@ -879,27 +947,26 @@ __device__ __forceinline__ void note_push(unsigned *last_change, unsigned nxt)
 // ... with the queues in global memory: batch-wide, or per frame (to_frame: the sweeps of the route that ends in
 // hyst_tail_kernel).  A batch-wide sweep appends through ONE counter word, and a word takes its atomics one at a time;
 // per frame the appends of a 128-frame batch meet on 128 words.  A tile's neighbours all lie in its own frame.
-__device__ __forceinline__ void process_tile(int t, int lane, uint64_t *__restrict__ strong, const HystSched &sch,
+__device__ __forceinline__ void process_tile(const TilePos &p, int lane, uint64_t *__restrict__ strong, const HystSched &sch,
                                              unsigned *__restrict__ last_change, int iter, const HystGeom &g,
                                              int16_t *__restrict__ edges, int edge_value, uint64_t c,
                                              const TileIn &in, bool to_frame = false)
 {
     const unsigned nxt = (unsigned)iter + 1u;
-    unsigned *q = (nxt & 1u) ? sch.queue1 : sch.queue0;
-    unsigned *cnt = sch.count + nxt % 3u;
-    if (to_frame) {
-        const int tpf = g.tiles_x * g.tiles_y;
-        const int f = t / tpf;
-        q = ((nxt & 1u) ? sch.fq1 : sch.fq0) + (size_t)f * tpf;
-        cnt = sch.fcount + 4 * (size_t)f + nxt % 3u;
-    }
-    process_tile_with(t, lane, strong, iter, g, edges, edge_value, c, in, [&](bool want, int nb) {
+    process_tile_with(p, lane, strong, iter, g, edges, edge_value, c, in, [&](bool want, int nb) {
+        // (the queue's address is worked out here, by the tiles that changed, and not on every tile's way to its flood)
+        unsigned *q = (nxt & 1u) ? sch.queue1 : sch.queue0;
+        unsigned *cnt = sch.count + nxt % 3u;
+        if (to_frame) {
+            q = ((nxt & 1u) ? sch.fq1 : sch.fq0) + (size_t)p.f * (g.tiles_x * g.tiles_y);
+            cnt = sch.fcount + 4 * (size_t)p.f + nxt % 3u;
+        }
         push_neighbours(want, lane, sch.stamp, (unsigned)nb, (unsigned)nb, nxt, q, cnt);
         if (__any(want) && lane == 0) note_push(last_change, nxt);
     });
 }
 
-__device__ __forceinline__ void propagate_tile(int t, int lane, uint64_t *__restrict__ strong,
+__device__ __forceinline__ void propagate_tile(const TilePos &p, int lane, uint64_t *__restrict__ strong,
                                                const uint64_t *__restrict__ conn, const HystSched &sch,
                                                unsigned *__restrict__ last_change, int iter, const HystGeom &g,
                                                int16_t *__restrict__ edges, int edge_value, uint64_t c,
@@ -909,8 +976,8 @@ __device__ __forceinline__ void propagate_tile(int t, int lane, uint64_t *__rest
     // ever be added, so a tile without a single one (flat regions: most tiles of a natural frame) cannot
     // change: leave before the strong plane and the nine halo loads are touched.
     if (!__any(c != 0)) return;
-    const TileIn in = load_tile(t, lane, strong, g, c);
-    process_tile(t, lane, strong, sch, last_change, iter, g, edges, edge_value, c, in, to_frame);
+    const TileIn in = load_tile(p, lane, strong, g, c);
+    process_tile(p, lane, strong, sch, last_change, iter, g, edges, edge_value, c, in, to_frame);
 }
 
 // Sweep 0 visits every tile (grid = tiles / (4 kSweep0Tiles) workgroups); later sweeps are launched with a small fixed
@@ -920,11 +987,14 @@ __device__ __forceinline__ void propagate_tile(int t, int lane, uint64_t *__rest
 // frame_groups > 0: the per-frame queues (the route that ends in hyst_tail_kernel) -- every sweep appends to its tiles'
 // frames' queues, and a sweep >= 1 is launched with frame_groups workgroups per frame, whose waves stride over that
 // frame's queue.
-__global__ __launch_bounds__(256) void hyst_propagate_kernel(uint64_t *__restrict__ strong,
+// amdgpu_waves_per_eu(8, 8): left alone the compiler takes 104 SGPRs, which leaves 7 waves per SIMD; asked for 8 it keeps
+// 78 (a few more values parked in VGPR lanes off the tiles' common path, no scratch).  A sweep is a chain of memory round
+// trips per wave, so the eighth wave is worth a tenth of sweep 0.
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void hyst_propagate_kernel(uint64_t *__restrict__ strong,
                                                              const uint64_t *__restrict__ conn,
                                                              unsigned *__restrict__ sched_words,
                                                              unsigned *__restrict__ last_change, int iter, HystGeom g,
-                                                             int16_t *__restrict__ edges, int edge_value,
+                                                             HystDiv dv, int16_t *__restrict__ edges, int edge_value,
                                                              int frame_groups)
 {
     const int lane = threadIdx.x & 63;
@@ -943,10 +1013,14 @@ __global__ __launch_bounds__(256) void hyst_propagate_kernel(uint64_t *__restric
 #pragma unroll
             for (int k = 0; k < kSweep0Tiles; k++)
                 c[k] = (t0 + k < tiles) ? conn[(size_t)(t0 + k) * kTile + lane] : 0ull;
+            // the wave's tiles are consecutive numbers: the first is placed by the reciprocals, the others follow it
+            TilePos p = tile_pos(t0, g, dv);
 #pragma unroll
-            for (int k = 0; k < kSweep0Tiles; k++)
-                propagate_tile(t0 + k, lane, strong, conn, sch, last_change, iter, g, edges, edge_value, c[k],
+            for (int k = 0; k < kSweep0Tiles; k++) {
+                if (k > 0) p = next_tile(p, g);
+                propagate_tile(p, lane, strong, conn, sch, last_change, iter, g, edges, edge_value, c[k],
                                frame_groups > 0);
+            }
         }
         return;
     }
@@ -963,8 +1037,8 @@ __global__ __launch_bounds__(256) void hyst_propagate_kernel(uint64_t *__restric
         const unsigned w = (unsigned)__builtin_amdgcn_readfirstlane(part * 4 + (int)(threadIdx.x >> 6));
         for (unsigned i = w; i < n; i += (unsigned)frame_groups * 4u) {
             const int t = (int)q[i];
-            propagate_tile(t, lane, strong, conn, sch, last_change, iter, g, edges, edge_value,
-                           conn[(size_t)t * kTile + lane], true);
+            propagate_tile(tile_pos(t, f, t - f * tpf, g, dv), lane, strong, conn, sch, last_change, iter, g, edges,
+                           edge_value, conn[(size_t)t * kTile + lane], true);
         }
         return;
     }
@@ -972,7 +1046,7 @@ __global__ __launch_bounds__(256) void hyst_propagate_kernel(uint64_t *__restric
     const unsigned *q = (iter & 1) ? sch.queue1 : sch.queue0;
     for (unsigned i = (unsigned)wave; i < n; i += (unsigned)n_waves) {
         const int t = (int)q[i];
-        propagate_tile(t, lane, strong, conn, sch, last_change, iter, g, edges, edge_value,
+        propagate_tile(tile_pos(t, g, dv), lane, strong, conn, sch, last_change, iter, g, edges, edge_value,
                        conn[(size_t)t * kTile + lane]);
     }
 }
@@ -995,7 +1069,7 @@ constexpr int kTailTiles = 4096; // = kTailMaxTiles of canny_capi.hip (checked b
 __global__ __launch_bounds__(1024) void hyst_tail_kernel(uint64_t *__restrict__ strong, const uint64_t *__restrict__ conn,
                                                          unsigned *__restrict__ sched_words,
                                                          unsigned *__restrict__ last_change, int first_iter, HystGeom g,
-                                                         int16_t *__restrict__ edges, int edge_value)
+                                                         HystDiv dv, int16_t *__restrict__ edges, int edge_value)
 {
     __shared__ unsigned s_queue[2][kTailTiles]; // tile numbers within the frame
     __shared__ unsigned s_stamp[kTailTiles];    // sweep for which a tile was last queued (dedupes pushes)
@@ -1033,13 +1107,15 @@ __global__ __launch_bounds__(1024) void hyst_tail_kernel(uint64_t *__restrict__ 
         unsigned *const n_next = &s_count[cur ^ 1];
         const unsigned nxt = (unsigned)iter + 1u;
         for (unsigned i = (unsigned)wave; i < n; i += (unsigned)n_waves) {
-            const int t = t_base + (int)s_queue[cur][i];
+            const int tt = (int)s_queue[cur][i];
+            const int t = t_base + tt;
+            const TilePos p = tile_pos(t, f, tt, g, dv);
             // the tile's connectable word and its strong words + halo are requested together (a queued tile nearly
             // always has connectable pixels: it was queued because a neighbour's border towards it changed)
             const uint64_t c = conn[(size_t)t * kTile + lane];
-            const TileIn in = load_tile(t, lane, strong, g);
+            const TileIn in = load_tile(p, lane, strong, g);
             if (!__any(c != 0)) continue;
-            process_tile_with(t, lane, strong, iter, g, edges, edge_value, c, in, [&](bool want, int nb) {
+            process_tile_with(p, lane, strong, iter, g, edges, edge_value, c, in, [&](bool want, int nb) {
                 const unsigned loc = (unsigned)(nb - t_base);
                 push_neighbours(want, lane, s_stamp, loc, loc, nxt, q_next, n_next);
                 if (__any(want)) pushed = nxt; // sweeps only count up
@@ -1428,7 +1504,7 @@ hipError_t launch_hyst_tail(uint64_t *strong, const uint64_t *conn, unsigned *sc
     const int tpf = g.tiles_x * g.tiles_y;
     const unsigned threads = tpf >= 256 ? 1024u : (tpf >= 64 ? 512u : 256u);
     hipLaunchKernelGGL(hyst_tail_kernel, dim3((unsigned)g.n_frames), dim3(threads), 0, stream, strong, conn, sched,
-                       last_change, first_iter, g, edges, edge_value);
+                       last_change, first_iter, g, make_hyst_div(g), edges, edge_value);
     return hipGetLastError();
 }
 
@@ -1452,7 +1528,7 @@ hipError_t launch_hyst_propagate(uint64_t *strong, const uint64_t *conn, unsigne
         }
     }
     hipLaunchKernelGGL(hyst_propagate_kernel, dim3(blocks), dim3(256), 0, stream, strong, conn, stamp, last_change,
-                       iter, g, edges, edge_value, frame_groups);
+                       iter, g, make_hyst_div(g), edges, edge_value, frame_groups);
     return hipGetLastError();
 }
 // Row-major finalize: a wave writes 512 consecutive pixels of ONE row (1 KB contiguous, four rows per

@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
 """Interleaved A/B of library builds and/or option sets in ONE GPU session (boxes differ by +-4 %, runs by +-3 %):
 
-    python tools/ab_stage_times.py --rounds 3 name1:lib=<path.so>,opt=val,... name2:...
+    python tools/ab_stage_times.py --rounds 3 [--stop-on-failure] name1:lib=<path.so>,opt=val,... name2:...
 
-Every variant runs tools/stage_times.py in its own process, round-robin; prints the median per stage."""
+Every variant runs tools/stage_times.py in its own process, round-robin; prints the median per stage.
+--stop-on-failure: a run that fails ends the session (nothing more is started on a device a variant may have faulted)."""
 import json
 import os
 import statistics
@@ -15,12 +16,14 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def main():
     args = sys.argv[1:]
-    rounds, frames = 3, 128
+    rounds, frames, stop_on_failure = 3, 128, False
     variants = []
     i = 0
     while i < len(args):
         if args[i] == "--rounds":
             rounds = int(args[i + 1]); i += 2
+        elif args[i] == "--stop-on-failure":
+            stop_on_failure = True; i += 1
         elif args[i] == "--frames":
             frames = int(args[i + 1]); i += 2
         else:
@@ -46,7 +49,9 @@ def main():
                 cmd += ["--opt", o]
             p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300)
             if p.returncode != 0:
-                print(f"[{name}] FAILED: {p.stderr[-400:]}", flush=True)
+                print(f"[{name}] FAILED (exit status {p.returncode}): {p.stderr[-400:]}", flush=True)
+                if stop_on_failure:
+                    sys.exit(1)
                 continue
             d = json.loads(p.stdout.strip().splitlines()[-1])
             res[name].append(d)
