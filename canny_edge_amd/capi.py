@@ -132,6 +132,9 @@ EXPORTS = (
     "canny_hip_shapes_from_chains", "canny_hip_shapes_profile_get", "canny_hip_selftest_shapes_plan",
     "canny_hip_dev_canny_curves", "canny_hip_dev_curves_bits", "canny_hip_canny_curves", "canny_hip_curves_from_bits",
     "canny_hip_curves_profile_get", "canny_hip_selftest_curves_plan",
+    "canny_hip_dev_canny_corners", "canny_hip_dev_corners_plane", "canny_hip_canny_corners",
+    "canny_hip_corners_from_plane", "canny_hip_corner_response_of", "canny_hip_dev_corners_arith",
+    "canny_hip_corners_profile_get", "canny_hip_selftest_corners_plan",
 )
 
 _lib: Optional[C.CDLL] = None
@@ -341,6 +344,15 @@ def load() -> C.CDLL:
         "canny_hip_curves_from_bits": ([p, i, i, i, p, ull, C.POINTER(ull), p, p, ull, C.POINTER(ull)], i),
         "canny_hip_curves_profile_get": ([p, i, C.POINTER(C.c_double), C.POINTER(C.c_long)], i),
         "canny_hip_selftest_curves_plan": ([i, i, i, p], i),
+        "canny_hip_dev_canny_corners": ([p, p, f, i, i, i, i, i, p, i, i, i, i, C.c_longlong, i, i, p, p, p, p, p], i),
+        "canny_hip_dev_corners_plane": ([p, p, i, i, i, i, i, i, i, C.c_longlong, i, i, p, p, p, p, p], i),
+        "canny_hip_canny_corners": ([p, p, i, f, i, i, i, i, i, i, i, i, C.c_longlong, i, i, p, p, p, p], i),
+        "canny_hip_corners_from_plane": ([p, i, i, i, i, i, i, C.c_longlong, i, i, p, ip, ip,
+                                          C.POINTER(C.c_longlong), p], i),
+        "canny_hip_corner_response_of": ([i, i, i, i, i, C.POINTER(C.c_longlong)], i),
+        "canny_hip_dev_corners_arith": ([p, p, sz, i, i, p], i),
+        "canny_hip_corners_profile_get": ([p, i, C.POINTER(C.c_double), C.POINTER(C.c_long)], i),
+        "canny_hip_selftest_corners_plan": ([i, i, i, i, ull, p], i),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -934,6 +946,54 @@ def circle_fits_unpack(fits) -> dict:
             "rms": np.sqrt(sdd / np.maximum(n, 1)) / 256.0, "maxd": (w4 & CIRCLE_FIT_MAXD_MASK) / 256.0,
             "sectors": sec, "sector_count": count, "trim_failed": (w4 & CIRCLE_FIT_TRIM_FAILED) != 0,
             "degenerate": (w4 & CIRCLE_FIT_DEGENERATE) != 0, "invalid": (w4 & CIRCLE_FIT_INVALID) != 0}
+
+
+# ---- corners, Harris / Shi-Tomasi -----------------------------------------------------------------
+CORNER_WORDS = 4
+CORNERS_MIN_EIGEN, CORNERS_HARRIS = 0, 1
+CORNERS_MAX_SUM, CORNERS_MAX_K_Q8 = 50979600, 64
+CORNER_PARTS = ("max", "candidates", "collect", "accept")
+CORNERS_PLANS = ("tiles", "arith")
+CORNER_DTYPE = np.dtype([("x", np.int64), ("y", np.int64), ("response", np.int64), ("rank", np.int64)])
+
+
+def corner_response_of(sxx: int, syy: int, sxy: int, mode: int = CORNERS_MIN_EIGEN, k_q8: int = 0) -> int:
+    """Host-only: the response R of the rule for one tensor (Sxx, Syy, Sxy)."""
+    r = C.c_longlong(0)
+    st = load().canny_hip_corner_response_of(int(sxx), int(syy), int(sxy), int(mode), int(k_q8), C.byref(r))
+    if st:
+        raise CannyHipError(st, "corner_response_of")
+    return r.value
+
+
+def corners_from_plane(plane, mode: int = CORNERS_MIN_EIGEN, block: int = 3, k_q8: int = 0, quality_q16: int = 655,
+                       min_response: int = 0, min_dist: int = 0, corners_max: int = 256, want_response: bool = False):
+    """Host-only, needs no GPU: the corner rule on ONE uint8 plane [H, W] -> (corners int64 [k, 4]: x, y, response,
+    rank; cand_count; max_response; response int64 [H, W] or None)."""
+    a = np.ascontiguousarray(plane, dtype=np.uint8)
+    if a.ndim != 2:
+        raise ValueError("expected a 2-D uint8 plane")
+    h, w = a.shape
+    rec = np.zeros((max(int(corners_max), 1), CORNER_WORDS), np.int64)
+    resp = np.zeros((h, w), np.int64) if want_response else None
+    n, nc, rmax = C.c_int(0), C.c_int(0), C.c_longlong(0)
+    st = load().canny_hip_corners_from_plane(_hp(a), h, w, int(mode), int(block), int(k_q8), int(quality_q16),
+                                             int(min_response), int(min_dist), int(corners_max), _hp(rec), C.byref(n),
+                                             C.byref(nc), C.byref(rmax), _hp(resp) if want_response else None)
+    if st:
+        raise CannyHipError(st, "corners_from_plane")
+    return rec[:n.value].copy(), nc.value, rmax.value, resp
+
+
+def corners_plan(which, n_frames: int = 1, height: int = 2, width: int = 2, n: int = 0):
+    """Host-only: (LaunchPlan, frames per chunk) of a capped corners launch: "tiles" (the passes over the plane, sized by
+    one frame) or "arith" (dev_corners_arith on n triples)."""
+    k = CORNERS_PLANS.index(which) if isinstance(which, str) else int(which)
+    out = np.zeros(6, np.uint64)
+    st = load().canny_hip_selftest_corners_plan(k, int(n_frames), int(height), int(width), int(n), _hp(out))
+    if st:
+        raise CannyHipError(st, "selftest_corners_plan")
+    return LaunchPlan(*(int(v) for v in out[:5])), int(out[5])
 
 
 # ---- chamfer template matching (DESIGN.md section 26) --------------------------------------------------------------------
@@ -2184,6 +2244,64 @@ class Context:
         """(total ms, launch groups) of part 0 cost, 1 score, 2 candidates, 3 accept (CHAMFER_PARTS)."""
         ms, n = C.c_double(0), C.c_long(0)
         self._check(self._L.canny_hip_chamfer_profile_get(self._h, part, C.byref(ms), C.byref(n)), "chamfer_profile_get")
+        return ms.value, n.value
+
+    # ---- corners, Harris / Shi-Tomasi on the smoothed plane (DESIGN.md section 29) ---------------------------------
+    def dev_canny_corners(self, d_img: int, sigma: float, min_val: int, max_val: int, h: int, w: int, n: int, mode: int,
+                          block: int, k_q8: int, quality_q16: int, min_response: int, min_dist: int, corners_max: int,
+                          d_corners: int, d_counts: int, d_cand_counts: int = 0, d_max_response: int = 0,
+                          d_response: int = 0, d_edges: int = 0):
+        """dev_canny, then the corners of the smoothed plane it left, on the same stream; d_corners (4 int64 per slot,
+        slot f * corners_max + j) and d_counts (n int32) are mandatory; d_cand_counts (n int32), d_max_response (n
+        int64), d_response ([n][h][w] int64), d_edges may be 0.  Asynchronous."""
+        v = C.c_void_p
+        self._check(self._L.canny_hip_dev_canny_corners(self._h, v(d_img or None), sigma, min_val, max_val, h, w, n,
+                                                        v(d_edges or None), mode, block, k_q8, quality_q16, min_response,
+                                                        min_dist, corners_max, v(d_corners or None), v(d_counts or None),
+                                                        v(d_cand_counts or None), v(d_max_response or None),
+                                                        v(d_response or None)), "dev_canny_corners")
+
+    def dev_corners_plane(self, d_plane: int, n: int, h: int, w: int, mode: int, block: int, k_q8: int, quality_q16: int,
+                          min_response: int, min_dist: int, corners_max: int, d_corners: int, d_counts: int,
+                          d_cand_counts: int = 0, d_max_response: int = 0, d_response: int = 0):
+        """The corners of a device u8 plane [n][h][w]; d_plane 0: of the plane the context's last canny call left."""
+        v = C.c_void_p
+        self._check(self._L.canny_hip_dev_corners_plane(self._h, v(d_plane or None), n, h, w, mode, block, k_q8,
+                                                        quality_q16, min_response, min_dist, corners_max,
+                                                        v(d_corners or None), v(d_counts or None), v(d_cand_counts or None),
+                                                        v(d_max_response or None), v(d_response or None)),
+                    "dev_corners_plane")
+
+    def canny_corners(self, imgs, sigma: float, min_val: int, max_val: int, mode: int = CORNERS_MIN_EIGEN, block: int = 3,
+                      k_q8: int = 0, quality_q16: int = 655, min_response: int = 0, min_dist: int = 0,
+                      corners_max: int = 256):
+        """canny() and the corners of each smoothed plane on the GPU: imgs (H, W) or (N, H, W) uint8 -> (corners,
+        cand_counts, max_response): corners[f] is a structured array (CORNER_DTYPE) of the accepted corners in order,
+        cand_counts int32 [N] the true number of candidates, max_response int64 [N] the largest response per frame."""
+        a = np.ascontiguousarray(imgs, dtype=np.uint8)
+        if a.ndim == 2:
+            a = a[None]
+        if a.ndim != 3:
+            raise ValueError("expected uint8 [H, W] or [n_frames, H, W]")
+        n, h, w = a.shape
+        rec = np.zeros((n, max(int(corners_max), 1), CORNER_WORDS), np.int64)
+        counts, cands, rmax = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.int64)
+        self._check(self._L.canny_hip_canny_corners(self._h, _hp(a), n, sigma, min_val, max_val, h, w, mode, block, k_q8,
+                                                    quality_q16, min_response, min_dist, corners_max, _hp(rec),
+                                                    _hp(counts), _hp(cands), _hp(rmax)), "canny_corners")
+        return ([np.ascontiguousarray(rec[f, :int(counts[f])]).view(CORNER_DTYPE).reshape(-1) for f in range(n)], cands,
+                rmax)
+
+    def dev_corners_arith(self, d_sums: int, n: int, mode: int, k_q8: int, d_r: int):
+        """The device's response function on n int32 triples (sxx, syy, sxy) -> n int64."""
+        v = C.c_void_p
+        self._check(self._L.canny_hip_dev_corners_arith(self._h, v(d_sums or None), n, mode, k_q8, v(d_r or None)),
+                    "dev_corners_arith")
+
+    def corners_profile_get(self, part: int) -> Tuple[float, int]:
+        """(total ms, launch groups) of part 0 max, 1 candidates, 2 collect, 3 accept (CORNER_PARTS)."""
+        ms, n = C.c_double(0), C.c_long(0)
+        self._check(self._L.canny_hip_corners_profile_get(self._h, part, C.byref(ms), C.byref(n)), "corners_profile_get")
         return ms.value, n.value
 
     # ---- sub-pixel circle fits (least-squares refit of the Hough circles from edgels; DESIGN.md section 25) ------

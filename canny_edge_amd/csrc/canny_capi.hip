@@ -414,6 +414,8 @@ struct canny_hip_ctx {
     int chamfer_route = 0; // 0 auto, 1 direct, 2 tiled
     int chamfer_chunk_mb = 0; // A/B and tests: budget of the score workspace in MiB, 0 = 256
     std::vector<canny_hip_chamfer_set *> chamfer_sets; // the sets created on this context and not yet destroyed
+    // corners, per chunk of frames: the collected keys, the radix select's state, the maxima, histograms and counters
+    DevBuf corners_ws;
     DevBuf plane_s, plane_c, stamps, flags; // hysteresis bit-planes / scheduling words
     DevBuf io[4];     // staging for the host-pointer stage functions
     std::string ws_name; // canny_hip_selftest_workspace: the name it handed out last
@@ -445,7 +447,7 @@ struct canny_hip_ctx {
     // (canny_hip_edgels_profile_get), then the one of the line fits (canny_hip_line_fits_profile_get), then the one of the
     // circle fits (canny_hip_circle_fits_profile_get), then the four of the chamfer matching
     // (canny_hip_chamfer_profile_get), then the three of the contour shape measures (canny_hip_shapes_profile_get), then the two of the edge curves
-    // (canny_hip_curves_profile_get).  The mask is a non-negative int option: bit 30 is the last it can
+    // (canny_hip_curves_profile_get), then the four of the corners (canny_hip_corners_profile_get).  The mask is a non-negative int option: bit 30 is the last it can
     // carry, and the three polygon slots, the two edgel slots, the line-fit slot and the circle-fit slot behind them go by
     // it together
     static constexpr int kProfHough = CANNY_HIP_STAGE_END, kProfComponents = CANNY_HIP_STAGE_END + 3;
@@ -460,7 +462,8 @@ struct canny_hip_ctx {
     static constexpr int kProfChamfer = kProfCircleFits + CANNY_HIP_CIRCLE_FIT_PARTS;
     static constexpr int kProfShapes = kProfChamfer + CANNY_HIP_CHAMFER_PARTS;
     static constexpr int kProfCurves = kProfShapes + CANNY_HIP_SHAPE_PARTS;
-    static constexpr int kProfSlots = kProfCurves + CANNY_HIP_CURVE_PARTS;
+    static constexpr int kProfCorners = kProfCurves + CANNY_HIP_CURVE_PARTS;
+    static constexpr int kProfSlots = kProfCorners + CANNY_HIP_CORNER_PARTS;
     static constexpr int kProfLastBit = 30;
     static_assert(kProfPolygons == kProfLastBit && kProfEdgels > kProfLastBit,
                   "profile_stage_mask has one bit per slot up to the polygon parts; every slot from there on follows bit 30");
@@ -1996,6 +1999,7 @@ void collect_workspaces(const canny_hip_ctx *c, const std::string &prefix, std::
     add("chamfer_scores", c->chamfer_scores, D);
     add("chamfer_ws", c->chamfer_ws, I);   // keys address score cells, totals bound the sort, counters hand out slots
     add("chamfer_dist2", c->chamfer_dist2, I); // doubles as the column scan's stack (see edt_stack)
+    add("corners_ws", c->corners_ws, I);   // keys address pixels, totals bound the sort, counters hand out slots
     add("plane_s", c->plane_s, D);
     add("plane_c", c->plane_c, D);
     add("stamps", c->stamps, I);           // tile queues and their counters
@@ -2110,6 +2114,7 @@ void canny_hip_ctx_destroy(canny_hip_ctx *ctx)
     ctx->chamfer_scores.release();
     ctx->chamfer_ws.release();
     ctx->chamfer_dist2.release();
+    ctx->corners_ws.release();
     ctx->cc_parent.release();
     ctx->cc_ws.release();
     ctx->ct_ws.release();
@@ -5790,6 +5795,202 @@ int canny_hip_selftest_chamfer_bands(const int *offsets, const short *points, in
         out[1] = std::max(out[1], lay.bands[(size_t)b].rows * cols);
     out[2] = lay.max_elems;
     out[3] = chamfer_auto_route(lay);
+    return CANNY_HIP_OK;
+}
+
+// ---- corners, Harris / Shi-Tomasi (canny_corners.hip) ------------------------------
+} // extern "C"
+
+namespace {
+
+struct CornerOut {
+    long long *d_corners;
+    int *d_counts, *d_cand_counts;
+    long long *d_max_response, *d_response;
+};
+
+// THE check of the corner arguments; needs no device and writes nothing
+int corners_check(int height, int width, int n_frames, const CornerArgs &a, const CornerOut &out)
+{
+    const bool mode_ok = a.mode == CANNY_HIP_CORNERS_MIN_EIGEN || a.mode == CANNY_HIP_CORNERS_HARRIS;
+    if (!mode_ok || (a.block != 3 && a.block != 5 && a.block != 7) || a.k_q8 < 0 || a.k_q8 > CANNY_HIP_CORNERS_MAX_K_Q8 ||
+        (a.mode == CANNY_HIP_CORNERS_MIN_EIGEN && a.k_q8 != 0) || a.quality_q16 < 0 || a.quality_q16 > 65536 ||
+        a.min_response < 0 || a.min_dist < 0 || a.corners_max < 1 || !out.d_corners || !out.d_counts ||
+        ((uintptr_t)out.d_corners & 7) || ((uintptr_t)out.d_response & 7) || ((uintptr_t)out.d_max_response & 7) ||
+        height < 2 || width < 2 || n_frames < 1)
+        return CANNY_HIP_ERR_INVALID;
+    if ((long long)height * width >= 0x80000000LL || n_frames > 65535 || a.corners_max > kHoughMaxLines || height > 65535 ||
+        width > 65535)
+        return CANNY_HIP_ERR_UNSUPPORTED;
+    return CANNY_HIP_OK;
+}
+
+// The corners of n frames of a device plane, queued on the context's stream, chunk of frames by chunk of frames.
+int dev_corners(canny_hip_ctx *ctx, const void *plane, bool plane_u8, int n, int h, int w, const CornerArgs &a,
+                const CornerOut &out)
+{
+    const size_t hw = (size_t)h * w, px_bytes = plane_u8 ? 1 : 2;
+    const int chunk = std::min(n, kCornersChunk);
+    HIP_TRY(ctx, ctx->corners_ws.ensure(corners_ws_bytes(chunk, a.corners_max, h, w)));
+    void *ws = ctx->corners_ws.p;
+    const int part = canny_hip_ctx::kProfCorners;
+    for (int f0 = 0; f0 < n; f0 += chunk) {
+        const int nf = std::min(chunk, n - f0);
+        const void *pl = (const char *)plane + (size_t)f0 * hw * px_bytes;
+        {
+            StageTimer tm(ctx, part + CANNY_HIP_CORNER_PART_MAX);
+            HIP_TRY(ctx, launch_corners_max(pl, plane_u8, nf, h, w, a, ws,
+                                            out.d_response ? out.d_response + (size_t)f0 * hw : nullptr, ctx->stream));
+        }
+        {
+            StageTimer tm(ctx, part + CANNY_HIP_CORNER_PART_CANDIDATES);
+            HIP_TRY(ctx, launch_corners_candidates(pl, plane_u8, nf, h, w, a, ws,
+                                                   out.d_cand_counts ? out.d_cand_counts + f0 : nullptr,
+                                                   out.d_max_response ? out.d_max_response + f0 : nullptr, ctx->stream));
+        }
+        {
+            StageTimer tm(ctx, part + CANNY_HIP_CORNER_PART_COLLECT);
+            HIP_TRY(ctx, launch_corners_collect(pl, plane_u8, nf, h, w, a, ws, ctx->stream));
+        }
+        {
+            StageTimer tm(ctx, part + CANNY_HIP_CORNER_PART_ACCEPT);
+            HIP_TRY(ctx, launch_corners_accept(nf, h, w, a, ws,
+                                               out.d_corners + (size_t)f0 * a.corners_max * CANNY_HIP_CORNER_WORDS,
+                                               out.d_counts + f0, ctx->stream));
+        }
+    }
+    return CANNY_HIP_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int canny_hip_dev_canny_corners(canny_hip_ctx *ctx, const unsigned char *d_img, float sigma, int min_val, int max_val,
+                                int height, int width, int n_frames, short *d_edges, int mode, int block, int k_q8,
+                                int quality_q16, long long min_response, int min_dist, int corners_max,
+                                long long *d_corners, int *d_counts, int *d_cand_counts, long long *d_max_response,
+                                long long *d_response)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!d_img) return CANNY_HIP_ERR_INVALID;
+    const CornerArgs a{mode, block, k_q8, quality_q16, min_response, min_dist, corners_max};
+    const CornerOut out{d_corners, d_counts, d_cand_counts, d_max_response, d_response};
+    if ((rc = corners_check(height, width, n_frames, a, out))) return rc;
+    if (!d_edges) {
+        HIP_TRY(ctx, ctx->edges16.ensure(npx(height, width, n_frames) * sizeof(short)));
+        d_edges = (short *)ctx->edges16.p;
+    }
+    if ((rc = dev_canny(ctx, d_img, sigma, min_val, max_val, height, width, n_frames, d_edges))) return rc;
+    // dev_canny leaves the whole batch's smoothed plane in ctx->smoothed, as bytes iff last_canny_u8
+    return dev_corners(ctx, ctx->smoothed.p, ctx->last_canny_u8 != 0, n_frames, height, width, a, out);
+}
+
+int canny_hip_dev_corners_plane(canny_hip_ctx *ctx, const unsigned char *d_plane, int n_frames, int height, int width,
+                                int mode, int block, int k_q8, int quality_q16, long long min_response, int min_dist,
+                                int corners_max, long long *d_corners, int *d_counts, int *d_cand_counts,
+                                long long *d_max_response, long long *d_response)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    const CornerArgs a{mode, block, k_q8, quality_q16, min_response, min_dist, corners_max};
+    const CornerOut out{d_corners, d_counts, d_cand_counts, d_max_response, d_response};
+    if ((rc = corners_check(height, width, n_frames, a, out))) return rc;
+    const void *plane = d_plane;
+    bool plane_u8 = true;
+    if (!d_plane) {
+        // the plane the last canny call left: only for the batch it belongs to
+        if (!ctx->last_canny_n || !ctx->smoothed.p || ctx->last_canny_n != n_frames || ctx->last_canny_h != height ||
+            ctx->last_canny_w != width)
+            return CANNY_HIP_ERR_INVALID;
+        plane = ctx->smoothed.p;
+        plane_u8 = ctx->last_canny_u8 != 0;
+    }
+    if ((rc = finish_pending(ctx))) return rc;
+    return dev_corners(ctx, plane, plane_u8, n_frames, height, width, a, out);
+}
+
+int canny_hip_canny_corners(canny_hip_ctx *ctx, const unsigned char *imgs, int n_frames, float sigma, int min_val,
+                            int max_val, int height, int width, int mode, int block, int k_q8, int quality_q16,
+                            long long min_response, int min_dist, int corners_max, long long *corners, int *counts,
+                            int *cand_counts, long long *max_response)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!imgs) return CANNY_HIP_ERR_INVALID;
+    const CornerArgs a{mode, block, k_q8, quality_q16, min_response, min_dist, corners_max};
+    if ((rc = corners_check(height, width, n_frames, a, CornerOut{corners, counts, nullptr, nullptr, nullptr}))) return rc;
+    const size_t slots = (size_t)n_frames * corners_max;
+    // one staging block: records (4 long long per slot) | maxima | counts | candidate counts
+    HIP_TRY(ctx, ctx->io[1].ensure((slots * CANNY_HIP_CORNER_WORDS + (size_t)n_frames) * sizeof(long long) +
+                                   2 * (size_t)n_frames * sizeof(int)));
+    long long *d_rec = (long long *)ctx->io[1].p, *d_max = d_rec + slots * CANNY_HIP_CORNER_WORDS;
+    int *d_cnt = (int *)(d_max + n_frames);
+    if ((rc = h2d(ctx, ctx->io[0], imgs, npx(height, width, n_frames)))) return rc;
+    if ((rc = canny_hip_dev_canny_corners(ctx, (const unsigned char *)ctx->io[0].p, sigma, min_val, max_val, height, width,
+                                          n_frames, nullptr, mode, block, k_q8, quality_q16, min_response, min_dist,
+                                          corners_max, d_rec, d_cnt, d_cnt + n_frames, d_max, nullptr)))
+        return rc;
+    std::vector<long long> words((size_t)n_frames * 2); // maxima | counts, candidate counts (as they lie on the device)
+    if ((rc = d2h_sync(ctx, words.data(), d_max, words.size() * sizeof(long long)))) return rc;
+    const int *cnt = (const int *)(words.data() + n_frames);
+    for (int f = 0; f < n_frames; f++) { // only the filled slots of each frame come down
+        const size_t k = (size_t)cnt[f], at = (size_t)f * corners_max * CANNY_HIP_CORNER_WORDS;
+        if (k) HIP_TRY(ctx, hipMemcpyAsync(corners + at, d_rec + at, k * CANNY_HIP_CORNER_WORDS * sizeof(long long),
+                                          hipMemcpyDeviceToHost, ctx->stream));
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    std::memcpy(counts, cnt, (size_t)n_frames * sizeof(int));
+    if (cand_counts) std::memcpy(cand_counts, cnt + n_frames, (size_t)n_frames * sizeof(int));
+    if (max_response) std::memcpy(max_response, words.data(), (size_t)n_frames * sizeof(long long));
+    return CANNY_HIP_OK;
+}
+
+// canny_hip_corners_from_plane and canny_hip_corner_response_of, the rule in plain C++, live in canny_corners_host.cpp.
+
+int canny_hip_dev_corners_arith(canny_hip_ctx *ctx, const int *d_sums, size_t n, int mode, int k_q8, long long *d_r)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!d_sums || !d_r || !n || ((uintptr_t)d_r & 7) ||
+        (mode != CANNY_HIP_CORNERS_MIN_EIGEN && mode != CANNY_HIP_CORNERS_HARRIS) || k_q8 < 0 ||
+        k_q8 > CANNY_HIP_CORNERS_MAX_K_Q8 || (mode == CANNY_HIP_CORNERS_MIN_EIGEN && k_q8 != 0))
+        return CANNY_HIP_ERR_INVALID;
+    if ((rc = finish_pending(ctx))) return rc;
+    HIP_TRY(ctx, launch_corners_arith(d_sums, n, mode, k_q8, d_r, ctx->stream));
+    return CANNY_HIP_OK;
+}
+
+int canny_hip_corners_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches)
+{
+    if (part < 0 || part >= CANNY_HIP_CORNER_PARTS || !total_ms || !launches) return CANNY_HIP_ERR_INVALID;
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if ((rc = profile_collect(ctx))) return rc;
+    *total_ms = ctx->total_ms[canny_hip_ctx::kProfCorners + part];
+    *launches = ctx->launches[canny_hip_ctx::kProfCorners + part];
+    return CANNY_HIP_OK;
+}
+
+// Host-only: the launch plans of the capped launches of the corners.
+int canny_hip_selftest_corners_plan(int which, int n_frames, int height, int width, unsigned long long n,
+                                    unsigned long long *out)
+{
+    if (!out) return CANNY_HIP_ERR_INVALID;
+    LaunchPlan p;
+    if (which == CANNY_HIP_CORNERS_PLAN_TILES) {
+        if (height < 2 || width < 2 || check_dims(height, width, n_frames)) return CANNY_HIP_ERR_INVALID;
+        p = plan_corners_tiles(height, width);
+        out[5] = (unsigned long long)std::min(n_frames, kCornersChunk);
+    } else if (which == CANNY_HIP_CORNERS_PLAN_ARITH) {
+        if (!n) return CANNY_HIP_ERR_INVALID;
+        p = plan_corners_arith((size_t)n);
+        out[5] = 0;
+    } else {
+        return CANNY_HIP_ERR_INVALID;
+    }
+    out[0] = p.units, out[1] = p.per_group, out[2] = p.grid, out[3] = p.trips(), out[4] = (unsigned long long)p.aux;
     return CANNY_HIP_OK;
 }
 

@@ -751,6 +751,33 @@ hipError_t launch_chamfer_candidates(const unsigned *scores, int nf, int height,
 hipError_t launch_chamfer_accept(const unsigned *scores, int nf, int height, int width, int n_templates, int matches_max,
                                  int min_dist, void *ws, int *matches, int *counts, hipStream_t stream);
 
+// ---- corners, Harris / Shi-Tomasi (canny_corners.hip) --------------------
+struct CornerArgs { // validated by the caller: the ranges of include/canny_hip.h
+    int mode, block, k_q8, quality_q16;
+    long long min_response;
+    int min_dist, corners_max;
+};
+constexpr int kCornersChunk = 1024; // frames of one chunk of the batch (the grid's y)
+// max, candidates (histograms), collect: the 64 x 16 tiles of ONE frame, one per workgroup and trip.  arith: triples.
+// (Reported by canny_hip_selftest_corners_plan, not by a kind.)
+LaunchPlan plan_corners_tiles(int height, int width);
+LaunchPlan plan_corners_arith(size_t n);
+// The workspace of a chunk of nf frames: keys | key lists | prefix, cutoff | maxima | histogram | state | counters.
+size_t corners_ws_bytes(int nf, int corners_max, int height, int width);
+// The four parts, in this order, for the nf <= kCornersChunk frames of plane (bytes if plane_u8, else shorts in [0, 255]).
+// max zeroes what the call reads before writing (the rest of ws is written first); response (may be null) receives every R.
+// cand_counts, max_response (may be null), corners, counts: already offset to the chunk's first frame.
+hipError_t launch_corners_max(const void *plane, bool plane_u8, int nf, int height, int width, const CornerArgs &a, void *ws,
+                              long long *response, hipStream_t stream);
+hipError_t launch_corners_candidates(const void *plane, bool plane_u8, int nf, int height, int width, const CornerArgs &a,
+                                     void *ws, int *cand_counts, long long *max_response, hipStream_t stream);
+hipError_t launch_corners_collect(const void *plane, bool plane_u8, int nf, int height, int width, const CornerArgs &a,
+                                  void *ws, hipStream_t stream);
+hipError_t launch_corners_accept(int nf, int height, int width, const CornerArgs &a, void *ws, long long *corners,
+                                 int *counts, hipStream_t stream);
+// The response function alone on n triples (sxx, syy, sxy): the arithmetic test's hook.
+hipError_t launch_corners_arith(const int *sums, size_t n, int mode, int k_q8, long long *out, hipStream_t stream);
+
 // ---- measurement aid ------------------------------------------------------------------------
 // Plain device copy of nbytes (multiple of 16; both pointers 16-byte aligned): what a 1:1 read/write stream reaches.
 hipError_t launch_probe_copy(const void *src, void *dst, size_t nbytes, hipStream_t stream, const LaunchEvents &ev = {});

@@ -2,6 +2,7 @@
 // the webcam and the GUI:  ./Main sigma minVal maxVal [-c] [-s] [-i in.pgm|in.ppm|in.jpg] [-o dir] [-p] [-n WxH] [-b dir]
 //        [-l rho,theta_degrees,threshold[,lines_max]] [-g min_length,max_gap[,exclusive]] [-m min_area] [-t] [-w min_length] [-d] [-e]
 //        [-r min_radius,max_radius,threshold,support[,min_dist[,cell_shift]]] [-y epsilon[,ratio]] [-u]
+//        [-q quality_q16,min_dist,corners_max[,block[,k_q8]]]
 //
 // Kept from the reference: the three positionals may appear anywhere relative to the flags
 // (src/main.cpp:29-46); exactly three are required, otherwise the usage text is printed and the
@@ -53,6 +54,9 @@
 // (canny_hip_canny_hough_circle_fits) and writes one "frame cx cy r n rms maxd sectors trim_failed degenerate" row per
 // circle to canny_circle_fits.txt.  -k without -r, or with a band outside 0..4, a negative trim or options outside 0..3, is
 // a usage error (exit 2).
+// Added: -q quality_q16,min_dist,corners_max[,block[,k_q8]] finds the corners of the frame's smoothed plane on the GPU
+// (canny_hip_canny_corners; Shi-Tomasi, or Harris when k_q8 is given) and writes one "frame x y response rank" line per
+// corner to canny_corners.txt.  A malformed -q is a usage error (exit 2).  Without -q nothing changes.
 // Added: -x a.pgm[:b.pgm...],trunc_q4,max_mean_q4,min_dist matches the frame's edge map against the shapes of the PGM files
 // (their non-zero pixels, anchored at the centre) on the GPU (canny_hip_canny_chamfer) and writes one "frame x y template
 // score mean" row per match, in order, to canny_matches.txt in the -o directory (stdout without -o); mean is the mean
@@ -752,6 +756,37 @@ static int run_chamfer(const vector<unsigned char> &frame, int height, int width
     return 0;
 }
 
+// -q: the corners of the frame's smoothed plane, "frame x y response rank" per corner, in order
+static int run_corners(const vector<unsigned char> &frame, int height, int width, float sigma, int minVal, int maxVal,
+                       const int *a, const string &outdir)
+{
+    const int corners_max = a[2], mode = a[4] >= 0 ? CANNY_HIP_CORNERS_HARRIS : CANNY_HIP_CORNERS_MIN_EIGEN;
+    vector<long long> rec((size_t)corners_max * CANNY_HIP_CORNER_WORDS);
+    int count = 0;
+    canny_hip_ctx *ctx = nullptr;
+    int st = canny_hip_ctx_create(&ctx, 0);
+    if (!st)
+        st = canny_hip_canny_corners(ctx, frame.data(), 1, sigma, minVal, maxVal, height, width, mode, a[3],
+                                     a[4] >= 0 ? a[4] : 0, a[0], 0, a[1], corners_max, rec.data(), &count, nullptr, nullptr);
+    if (st) {
+        fprintf(stderr, "ERROR: -q: %s\n", st == CANNY_HIP_ERR_RUNTIME && ctx ? canny_hip_last_error(ctx) : canny_hip_status_string(st));
+        if (ctx) canny_hip_ctx_destroy(ctx);
+        return 1;
+    }
+    canny_hip_ctx_destroy(ctx);
+    FILE *f = outdir.empty() ? stdout : fopen((outdir + "/canny_corners.txt").c_str(), "w");
+    if (!f) {
+        fprintf(stderr, "ERROR: cannot write %s/canny_corners.txt\n", outdir.c_str());
+        return 1;
+    }
+    for (int j = 0; j < count; j++) {
+        const long long *c = rec.data() + (size_t)j * CANNY_HIP_CORNER_WORDS;
+        fprintf(f, "0 %lld %lld %lld %lld\n", c[0], c[1], c[2], c[3]);
+    }
+    if (f != stdout) fclose(f);
+    return 0;
+}
+
 int main(int argc, char *argv[])
 {
     // The batch pipeline wants its upload, compute and download streams on separate hardware queues; HIP reads this
@@ -785,6 +820,8 @@ int main(int argc, char *argv[])
     int circle_fit_args[3] = {0, 0, 0}; // -k: band, trim_q8, options
     vector<string> chamfer_shapes;      // -x: the PGM files of the shapes
     int chamfer_args[3] = {0, 0, 0};    // ... trunc_q4, max_mean_q4, min_dist
+    bool want_corners = false;
+    int corner_args[5] = {0, 0, 0, 3, -1}; // -q: quality_q16, min_dist, corners_max, block, k_q8 (-1: Shi-Tomasi)
     int width = WIDTH, height = HEIGHT;
     vector<string> values;
 
@@ -926,6 +963,29 @@ int main(int argc, char *argv[])
             want_dist = true;
         } else if (arg == "-t") {
             want_contours = true;
+        } else if (arg == "-q" && i + 1 < argc) {
+            // three to five whole non-negative integers, nothing empty, nothing behind the last one
+            int got = 0;
+            bool clean = true;
+            corner_args[3] = 3, corner_args[4] = -1;
+            for (const char *p = argv[++i]; clean; got++) {
+                char *end = nullptr;
+                const long v = strtol(p, &end, 10);
+                clean = end != p && got < 5 && v >= 0 && v <= 65536 && isdigit((unsigned char)*p);
+                if (clean) corner_args[got] = (int)v;
+                if (!clean || *end == '\0') break;
+                clean = *end == ',';
+                p = end + 1;
+            }
+            got++;
+            const int b = corner_args[3];
+            if (!clean || got < 3 || corner_args[2] < 1 || corner_args[2] > CANNY_HIP_HOUGH_MAX_LINES ||
+                (b != 3 && b != 5 && b != 7) || corner_args[4] > CANNY_HIP_CORNERS_MAX_K_Q8) {
+                fprintf(stderr, "ERROR: -q expects quality_q16,min_dist,corners_max[,block[,k_q8]]: quality in 1/65536 of the largest "
+                                "response, 1 <= corners_max <= 4096, block 3, 5 or 7, k_q8 <= 64 (in 1/256) chooses Harris\n");
+                exit(2);
+            }
+            want_corners = true;
         } else if (arg == "-w" && i + 1 < argc) {
             char tail = 0; // a whole integer only
             if (sscanf(argv[++i], "%d%c", &curve_min_length, &tail) != 1) {
@@ -1002,6 +1062,8 @@ int main(int argc, char *argv[])
         fprintf(stderr, "   -x a.pgm[:b.pgm...],trunc_q4,max_mean_q4,min_dist: chamfer matching of the edge map against the shapes of the\n");
         fprintf(stderr, "       PGM files (non-zero pixels, anchored at the centre; costs in 1/16 px), one \"frame x y template score mean\"\n");
         fprintf(stderr, "       line per match (mean in pixels) -> canny_matches.txt in the -o dir\n");
+        fprintf(stderr, "   -q quality_q16,min_dist,corners_max[,block[,k_q8]]: corners of the smoothed plane (Shi-Tomasi; with k_q8 Harris,\n");
+        fprintf(stderr, "       k in 1/256), one \"frame x y response rank\" line each -> canny_corners.txt in the -o dir\n");
         fprintf(stderr, "   -d: distance of every pixel to the nearest edge pixel, min(255, floor) -> canny_dist.pgm in the -o dir\n");
         fprintf(stderr, "   -e: sub-pixel edgel of every edge pixel, one \"x y gx gy mag dir refined\" line each (x, y in pixels to three\n");
         fprintf(stderr, "       decimals, mag in grey levels, dir 0..3) -> canny_edgels.txt in the -o dir\n");
@@ -1089,6 +1151,10 @@ int main(int argc, char *argv[])
     }
     if (!chamfer_shapes.empty()) {
         const int rc = run_chamfer(frame, height, width, sigma, minVal, maxVal, chamfer_shapes, chamfer_args, outdir);
+        if (rc) return rc;
+    }
+    if (want_corners) {
+        const int rc = run_corners(frame, height, width, sigma, minVal, maxVal, corner_args, outdir);
         if (rc) return rc;
     }
     if (want_circles) {

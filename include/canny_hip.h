@@ -52,7 +52,8 @@
 extern "C" {
 #endif
 
-#define CANNY_HIP_VERSION 1800       /* 0.18.0: + edge curves: the edge map linked into ordered chains */
+#define CANNY_HIP_VERSION 1900       /* 0.19.0: + corners: Harris / Shi-Tomasi on the smoothed plane */
+/* 0.18.0: + edge curves: the edge map linked into ordered chains */
 /* 0.17.0: + contour shape measures: moments, convex hull, minimum-area rectangle */
 /* 0.16.0: + chamfer template matching on the distance transform */
 /* 0.15.0: + sub-pixel circle fits: least-squares refit of Hough circles from edgels */
@@ -1716,6 +1717,102 @@ int canny_hip_chamfer_cost_of(int d2, int trunc_q4);
  * takes in floating point and corrects to the exact integer root.  Asynchronous. */
 int canny_hip_dev_chamfer_costs(canny_hip_ctx *ctx, const int *d_dist2, size_t n, int trunc_q4, unsigned int *d_costs);
 
+/* ---- corners (Harris / Shi-Tomasi) ----------------------------------------------------------------------------------------
+ * Where are the corners of a frame?  What cv::goodFeaturesToTrack and cv::cornerHarris answer, computed per frame from the
+ * smoothed plane every canny call leaves on the device: a structure-tensor response at every pixel, its local maxima over
+ * a quality threshold, and an ordered, distance-suppressed list of corners -- on the GPU, on the same stream, with no host
+ * round trip.  All integers: the same bytes on every run and every machine.  tests/corners_rule.py restates the rule in
+ * numpy and in plain Python ints, csrc/canny_corners_host.cpp in plain C++.  THE RULE:
+ *   Plane: P is a u8 plane of height x width, height, width >= 2.  (The context's own plane may be s16 when option
+ *     "smoothed_u8" is 0; the Gaussian keeps its values in [0, 255], and the bounds below rest on that: a caller's plane is
+ *     u8 only.)
+ *   Gradient: (gx, gy) = the reference's 3 x 3 Sobel pair at (y, x) with its border rules (gx clamps columns and drops
+ *     rows outside the frame, gy clamps rows and drops columns), as for the edgels and the circles.  |gx|, |gy| <= 1020.
+ *   Tensor, for block in {3, 5, 7}, r = block / 2: Sxx(y, x) = the sum of gx^2 over the block x block window centred on
+ *     (y, x), Syy that of gy^2, Sxy that of gx * gy; a window position outside the frame contributes 0.
+ *     Sxx, Syy <= 49 * 1020^2 = 50,979,600 = CANNY_HIP_CORNERS_MAX_SUM and |Sxy| <= the same: all three fit in an int.
+ *   Response R, a signed 64-bit value:
+ *     CANNY_HIP_CORNERS_MIN_EIGEN (Shi-Tomasi): R = Sxx + Syy - ceil_sqrt(D), D = (Sxx - Syy)^2 + 4 * Sxy^2 < 2^54,
+ *       ceil_sqrt the exact integer ceiling root: R = floor(2 * lambda_min), 0 <= R < 2^27.  k_q8 must be 0.
+ *     CANNY_HIP_CORNERS_HARRIS: R = 256 * (Sxx * Syy - Sxy^2) - k_q8 * (Sxx + Syy)^2, 0 <= k_q8 <= 64 (10 is k ~ 0.04);
+ *       both terms stay below 6.7e17, |R| < 2^61, and a positive R is below 2^60.
+ *   Threshold: Rmax[f] = the largest R of frame f over all its pixels; thr[f] = floor(max(Rmax, 0) * quality_q16 / 65536),
+ *     0 <= quality_q16 <= 65536 (the product is taken exactly, beyond 64 bits); min_response >= 0 is an absolute floor.
+ *   Candidates: (y, x) is a candidate iff R >= max(thr, min_response, 1), and R > each of the four 3 x 3 neighbours that
+ *     precede it in raster order (up-left, up, up-right, left), and R >= each of the four that follow it; neighbours
+ *     outside the frame are ignored.  On a plateau the first pixel in raster order wins (the Hough peak rule taken to
+ *     eight neighbours).
+ *   Order: base = y * width + x; the candidates are sorted by (R descending, base ascending); the first
+ *     min(corners_max, n_candidates) go on, 1 <= corners_max <= CANNY_HIP_HOUGH_MAX_LINES.
+ *   Acceptance (the pattern of the chamfer matches and the circles): the selected candidates are taken in that order; one
+ *     is accepted iff no earlier ACCEPTED one has dx^2 + dy^2 < min_dist^2.  min_dist >= 0; 0 disables the check.
+ *   Output: frame f writes its accepted corners compactly, in that order, to slots f * corners_max + j of corners; a
+ *     corner is CANNY_HIP_CORNER_WORDS = 4 long long: x, y, response, rank -- rank its position in the selected order, so a
+ *     caller sees what the distance rule removed.  counts[f] (mandatory) is the number accepted, cand_counts[f] (may be
+ *     NULL) the true number of candidates, max_response[f] (may be NULL) Rmax; later slots are not written.  d_response, if
+ *     given, is [n][height][width] long long and receives every R; what the other outputs hold does not depend on whether
+ *     it is given.
+ *   Statuses: bad ranges (block, mode, k_q8, quality_q16, min_response, min_dist, corners_max < 1, sizes < 1), NULL
+ *     mandatory pointers (the corner records are mandatory), frames under 2 x 2, a record or response buffer that is not
+ *     8-byte aligned: CANNY_HIP_ERR_INVALID; over a documented limit (corners_max > CANNY_HIP_HOUGH_MAX_LINES,
+ *     height * width >= 2^31, and for the device forms height or width > 65535): CANNY_HIP_ERR_UNSUPPORTED; both before
+ *     anything is queued, nothing is written.  Otherwise the detector's own status comes first.  max_val > 255 empties
+ *     the MAP but not the corners: the result follows the PLANE.
+ * Memory: the response plane is not kept (16 B/px stored and read back against 1 B/px per pass over the plane): the
+ *   response is computed again wherever it is needed.  The batch is walked in chunks of at most 1024 frames; the workspace
+ *   holds, per frame of a chunk, a histogram of 32 KiB, the collected keys (16 * corners_max bytes), a list of the frame's
+ *   candidate keys (16 bytes each, min(16384, ceil(height / 2) * ceil(width / 2)) of them: a frame with more candidates
+ *   than corners_max AND than the list holds computes its responses once more per 13 bits of the key) and a few words.
+ * The four parts are timed by canny_hip_corners_profile_get (CANNY_HIP_CORNER_PART_*); with "profile_stage_mask" they go
+ *   by bit 30 like every part behind the polygons.
+ * Not covered -- follow-ups: sub-pixel corner refinement (cornerSubPix); a mask, such as corners only near edge pixels of
+ * the finished map; block sizes above 7; Gaussian-weighted windows; s16 caller planes; colour, per-frame and
+ * automatic-threshold forms; the three-stream batch pipeline; the multi-GPU sharder. */
+#define CANNY_HIP_CORNER_WORDS 4
+#define CANNY_HIP_CORNERS_MAX_SUM 50979600
+#define CANNY_HIP_CORNERS_MAX_K_Q8 64
+enum canny_hip_corners_mode { CANNY_HIP_CORNERS_MIN_EIGEN = 0, CANNY_HIP_CORNERS_HARRIS = 1 };
+enum canny_hip_corner_part {
+    CANNY_HIP_CORNER_PART_MAX = 0,         /* pass 1: every R, the frame's maximum, the response plane if asked for */
+    CANNY_HIP_CORNER_PART_CANDIDATES = 1,  /* pass 2: R again, threshold, local maxima; the cut-off's digit histograms */
+    CANNY_HIP_CORNER_PART_COLLECT = 2,     /* pass 2 once more: every key up to the cut-off */
+    CANNY_HIP_CORNER_PART_ACCEPT = 3,      /* sort + ordered acceptance, one workgroup per frame */
+    CANNY_HIP_CORNER_PARTS = 4
+};
+/* canny_hip_dev_canny unchanged (d_edges as there), then the corners of the smoothed plane it left, on the same stream.
+ * d_corners: n_frames * corners_max * 4 long long.  Asynchronous. */
+int canny_hip_dev_canny_corners(canny_hip_ctx *ctx, const unsigned char *d_img, float sigma, int min_val, int max_val,
+                                int height, int width, int n_frames, short *d_edges, int mode, int block, int k_q8,
+                                int quality_q16, long long min_response, int min_dist, int corners_max,
+                                long long *d_corners, int *d_counts, int *d_cand_counts, long long *d_max_response,
+                                long long *d_response);
+/* The corners of a caller's device u8 plane ([n][height][width] bytes).  With d_plane == NULL: of the plane the context's
+ * last canny call left, under the rule of canny_hip_dev_edgels_at -- a context that ran no such call, or a call for
+ * another shape, gives CANNY_HIP_ERR_INVALID with nothing queued.  Asynchronous. */
+int canny_hip_dev_corners_plane(canny_hip_ctx *ctx, const unsigned char *d_plane, int n_frames, int height, int width,
+                                int mode, int block, int k_q8, int quality_q16, long long min_response, int min_dist,
+                                int corners_max, long long *d_corners, int *d_counts, int *d_cand_counts,
+                                long long *d_max_response, long long *d_response);
+/* Host buffers, synchronous, in the pattern of canny_hip_canny_chamfer: the counts come down first, then only the filled
+ * slots of corners.  cand_counts and max_response may be NULL. */
+int canny_hip_canny_corners(canny_hip_ctx *ctx, const unsigned char *imgs, int n_frames, float sigma, int min_val,
+                            int max_val, int height, int width, int mode, int block, int k_q8, int quality_q16,
+                            long long min_response, int min_dist, int corners_max, long long *corners, int *counts,
+                            int *cand_counts, long long *max_response);
+/* Host-only, needs no device: the rule on ONE host u8 plane, in plain C++.  corners (corners_max * 4 long long; only the
+ * accepted records are written) and count are mandatory; cand_count, max_response and response (height * width long
+ * long) may be NULL. */
+int canny_hip_corners_from_plane(const unsigned char *plane, int height, int width, int mode, int block, int k_q8,
+                                 int quality_q16, long long min_response, int min_dist, int corners_max,
+                                 long long *corners, int *count, int *cand_count, long long *max_response,
+                                 long long *response);
+/* Host-only: R of the rule for one tensor (0 <= sxx, syy <= CANNY_HIP_CORNERS_MAX_SUM, |sxy| <= the same; otherwise, or
+ * with a bad mode or k_q8, CANNY_HIP_ERR_INVALID and *r untouched). */
+int canny_hip_corner_response_of(int sxx, int syy, int sxy, int mode, int k_q8, long long *r);
+/* Test hook: the device's response function alone on n triples (d_sums: n * 3 ints sxx, syy, sxy within the bounds above;
+ * d_r receives n long long).  Asynchronous. */
+int canny_hip_dev_corners_arith(canny_hip_ctx *ctx, const int *d_sums, size_t n, int mode, int k_q8, long long *d_r);
+
 /* ---- per-stage HIP-event timing (events are recorded on the launch stream) ----------------- */
 int canny_hip_profile_enable(canny_hip_ctx *ctx, int on);
 int canny_hip_profile_reset(canny_hip_ctx *ctx);
@@ -1748,6 +1845,8 @@ int canny_hip_chamfer_profile_get(canny_hip_ctx *ctx, int part, double *total_ms
 int canny_hip_shapes_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches);
 /* ... and for the two parts of the edge curves (CANNY_HIP_CURVE_PART_*). */
 int canny_hip_curves_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches);
+/* ... and for the four parts of the corners (CANNY_HIP_CORNER_PART_*). */
+int canny_hip_corners_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches);
 
 /* ---- self-test hooks used by the GPU test-suite -------------------------------------------- */
 /* Runs the DEVICE magnitude / angle-bin functions over every (gx,gy) in [-lim,lim]^2 and writes
@@ -1890,6 +1989,16 @@ int canny_hip_selftest_shapes_plan(int which, unsigned long long capacity, unsig
  * and the write kernel walk the image rows of the batch, one wave per row and trip, 4 rows per workgroup, at most 65536
  * workgroups.  Sized by n_frames, height, width, valid as for a curves call. */
 int canny_hip_selftest_curves_plan(int n_frames, int height, int width, unsigned long long *out);
+/* Host-only, the same five outputs for the capped launches of the corners (they have no kind above):
+ *   CANNY_HIP_CORNERS_PLAN_TILES: the two passes over the plane (maximum; histograms and collect), items = the 64 x 16
+ *     tiles of ONE frame, one per workgroup and trip, grid (out[2], frames of the chunk), at most 1024 workgroups in x;
+ *     out[5] = frames of a chunk;
+ *   CANNY_HIP_CORNERS_PLAN_ARITH: canny_hip_dev_corners_arith, items = n triples, 256 per workgroup, at most 1024
+ *     workgroups (n_frames, height, width are not read).
+ * out holds 6 words. */
+enum canny_hip_corners_plan { CANNY_HIP_CORNERS_PLAN_TILES = 0, CANNY_HIP_CORNERS_PLAN_ARITH = 1 };
+int canny_hip_selftest_corners_plan(int which, int n_frames, int height, int width, unsigned long long n,
+                                    unsigned long long *out);
 
 #ifdef __cplusplus
 }
