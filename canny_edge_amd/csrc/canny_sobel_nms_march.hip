@@ -131,6 +131,18 @@ using IC = std::integral_constant<int, N>;
 #ifndef FLT_CARRIERS
 #define FLT_CARRIERS 1 // 1: one v_perm_b32-packed bin carrier per pixel; 2: the two floats themselves
 #endif
+// f32 strips at the column borders of the PLANES kernels (W % 8 == 0, so a lane lies wholly inside or wholly outside
+// the image; see fmarch_strip): 0 = the any-width border code, 1 = per-lane border constants, 2 = also the interior
+// strips' addressing for the row loads / stores and byte pairs in the plane flush.  (A/B switch, like the ones above.)
+#ifndef FLT_LEAN_BORDER
+#define FLT_LEAN_BORDER 2
+#endif
+// f32 strips: 1 = the gradient / magnitude / carrier block runs only for the rows whose magnitudes a stored pixel reads
+// (ybeg-1 .. yend); 2 = also no carriers for rows ybeg-1 and yend, whose own NMS is never taken (a scalar branch per
+// pixel, no peeled copy of the loop); 0 = every row.  (A/B switch; profiles/sobel_border_strips.jsonl)
+#ifndef FLT_SKIP_DEAD_ROWS
+#define FLT_SKIP_DEAD_ROWS 2
+#endif
 #define FLT_SCHED_FENCE() __builtin_amdgcn_sched_barrier(0)
 
 struct StripJob {
@@ -645,13 +657,26 @@ __device__ __forceinline__ int f_nms_select(int carrier, int n0, int n45, int n9
     return f_nms_select_masks(carrier >> 31, carrier, n0, n45, n90, n135);
 }
 
-template <bool COL_EDGE, bool ROW_EDGE, bool PLANES, bool LDS_PLANES, bool IN_U8>
+// WHOLE_LANES: the launch guarantees W % 8 == 0 (the PLANES kernels: sobel_nms_classify_supported), and x0 % 8 == 0
+// always, so each lane's eight pixels lie all inside or all outside the image.  A border strip then needs no per-pixel
+// masks: column 0 can only be a lane's pixel 0 and column W-1 only its pixel 7; outside lanes load zeros, so a = b = 0
+// in every outside pixel but the two that have an inside neighbour -- pixel 0 of the lane at x0 == W and pixel 7 of the
+// lane at x0 == -8 -- and a zero gradient lands on the floor `skip` through the v_max_u16 every magnitude gets anyway.
+template <bool COL_EDGE, bool ROW_EDGE, bool PLANES, bool LDS_PLANES, bool IN_U8, bool WHOLE_LANES = false>
 __device__ __forceinline__ void fmarch_strip(const StripJob &jb, uint8_t *stage_mem, const uint4 *edge_lut = nullptr)
 {
+    static_assert(!WHOLE_LANES || PLANES, "only the PLANES launches guarantee W % 8 == 0");
     constexpr int NP = 4, PX = 8;
+    constexpr bool LEAN = COL_EDGE && WHOLE_LANES && FLT_LEAN_BORDER >= 1;     // per-lane border constants
+    constexpr bool LEAN_MEM = COL_EDGE && WHOLE_LANES && FLT_LEAN_BORDER >= 2; // ... and the interior strips' addressing
     const int H = jb.H, W = jb.W, x0 = jb.x0, ybeg = jb.ybeg, yend = jb.yend;
     const bool full8 = x0 >= 0 && x0 + PX - 1 < W; // all of this lane's pixels are inside the image
     const bool owner = jb.lane >= 1 && jb.lane <= 62 && x0 < W;
+    // LEAN: all ones iff ...
+    const int lane_in = (!LEAN || full8) ? -1 : 0;       // ... the lane lies inside the image (else its row loads read as 0)
+    const int last_m = (LEAN && x0 + PX == W) ? -1 : 0;  // ... column W-1 is this lane's pixel 7 (column clamp of gx)
+    const int keep0_m = (LEAN && x0 == W) ? 0 : -1;      // ... pixel 0 is NOT the outside pixel right of column W-1
+    const int keep7_m = (LEAN && x0 == -PX) ? 0 : -1;    // ... pixel 7 is NOT the outside pixel left of column 0
 
     // lane-varying border constants (COL_EDGE only).  Out-of-image columns load as zero, so a = b = 0 there:
     // "columns dropped" (gy) needs nothing, "column clamp" (gx) is gx -= a[0] at column 0 and gx += a[e] at column W-1.
@@ -663,19 +688,21 @@ __device__ __forceinline__ void fmarch_strip(const StripJob &jb, uint8_t *stage_
     // recomputing them per row cost two instructions per pixel in a quarter of a 4K frame's waves.
     int in_m[PX + 1];
 #pragma unroll
-    for (int e = 0; e <= PX; e++) in_m[e] = COL_EDGE ? (e - 1 - elast) >> 31 : -1;
+    for (int e = 0; e <= PX; e++) in_m[e] = (COL_EDGE && !LEAN) ? (e - 1 - elast) >> 31 : -1; // (LEAN: not used)
     auto inside = [&](int e) { return in_m[e]; }; // all ones iff x0 + e lies inside the image
 
     // Lane offset (in pixels) of the interior strips' row loads and stores, passed through an empty asm at every use so
     // that the optimiser cannot fold it into loop-invariant 64-bit VGPR pointers (as in the Gaussian: the addresses stay
-    // "uniform row base + 32-bit lane offset").  Interior strips have x0 >= 0.
-    uint32_t lane_off = (uint32_t)x0;
+    // "uniform row base + 32-bit lane offset").  Interior strips have x0 >= 0.  LEAN_MEM border strips use it too: the
+    // offset of an outside lane is clamped into the row (W >= 8) and step() zeroes what the lane loaded with lane_in;
+    // owner lanes lie inside, their offset is x0.
+    uint32_t lane_off = (uint32_t)(LEAN_MEM ? min(max(x0, 0), W - PX) : x0);
     auto load_row = [&](int r, uint32_t (&p)[NP]) {
 #pragma unroll
         for (int i = 0; i < NP; i++) p[i] = 0u;
         if (ROW_EDGE && (r < 0 || r >= H)) return; // wave-uniform: virtual rows are zero
         if (IN_U8) {
-            if (!COL_EDGE) { // uniform row base (SGPR pair) + 32-bit lane offset: no 64-bit address arithmetic per lane
+            if (!COL_EDGE || LEAN_MEM) { // uniform row base (SGPR pair) + 32-bit lane offset: no 64-bit address arithmetic per lane
                 asm volatile("" : "+v"(lane_off));
                 __builtin_memcpy(p, jb.fin8 + (size_t)r * W + lane_off, 8);
                 return;
@@ -692,7 +719,7 @@ __device__ __forceinline__ void fmarch_strip(const StripJob &jb, uint8_t *stage_
             }
             return;
         }
-        if (!COL_EDGE) {
+        if (!COL_EDGE || LEAN_MEM) {
             asm volatile("" : "+v"(lane_off));
             __builtin_memcpy(p, reinterpret_cast<const char *>(jb.fin + (size_t)r * W) + 2 * lane_off, 4 * NP);
             return;
@@ -760,10 +787,11 @@ __device__ __forceinline__ void fmarch_strip(const StripJob &jb, uint8_t *stage_
                     *reinterpret_cast<const uint64_t *>(stage + kStagePlane + lrow + 8 * k);
             }
         }
-        auto leftover = [&](int i) {
+        // byte column i alone, or i and i + 1 (i is even then: every strip starts on an even byte column)
+        auto leftover = [&](int i, bool pair) {
             if (!row_ok) return;
             const unsigned g = grow + (unsigned)(st_w0 + (i >> 3)) * 512u + (unsigned)(i & 7);
-            if (!COL_EDGE) {
+            if (pair) {
                 *reinterpret_cast<uint16_t *>(jb.pconn + g) = *reinterpret_cast<const uint16_t *>(stage + lrow + i);
                 *reinterpret_cast<uint16_t *>(jb.pstrong + g) =
                     *reinterpret_cast<const uint16_t *>(stage + kStagePlane + lrow + i);
@@ -772,10 +800,20 @@ __device__ __forceinline__ void fmarch_strip(const StripJob &jb, uint8_t *stage_
                 jb.pstrong[g] = stage[kStagePlane + lrow + i];
             }
         };
-        constexpr int kStep = COL_EDGE ? 1 : 2;
+        // byte columns [beg, end), beg even: interior strips own an even count; a border strip's count may be odd
+        // (LEAN_MEM: byte pairs and one single byte at the end; the any-width code: single bytes)
+        auto leftovers = [&](int beg, int end) {
+            if (!COL_EDGE || LEAN_MEM) {
+                int i = beg;
+                for (; i + 1 < end; i += 2) leftover(i, true);
+                if (COL_EDGE && i < end) leftover(i, false);
+            } else {
+                for (int i = beg; i < end; i++) leftover(i, false);
+            }
+        };
         const int head_end = min(8 * wf0, st_e), tail_beg = max(8 * wf1, head_end);
-        for (int i = st_o; i < head_end; i += kStep) leftover(i);
-        for (int i = tail_beg; i < st_e; i += kStep) leftover(i);
+        leftovers(st_o, head_end);
+        leftovers(tail_beg, st_e);
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     };
 
@@ -793,7 +831,7 @@ __device__ __forceinline__ void fmarch_strip(const StripJob &jb, uint8_t *stage_
     constexpr bool PARKS = DEFER && ((PLANES && STAGE) || (!PLANES && !COL_EDGE));
     auto store_pending = [&](int y) { // y: the row that is parked if any row is
         if (PARKS && y >= ybeg && y < yend) {
-            if (!COL_EDGE) {
+            if (!COL_EDGE || LEAN_MEM) {
                 asm volatile("" : "+v"(lane_off));
                 if (owner)
                     store_row<NP>(reinterpret_cast<int16_t *>(reinterpret_cast<char *>(jb.fout + (size_t)y * W) +
@@ -811,9 +849,12 @@ __device__ __forceinline__ void fmarch_strip(const StripJob &jb, uint8_t *stage_
         constexpr int m2 = PH % 3, m1 = (PH + 2) % 3, m0 = (PH + 1) % 3; // M of rows r-1, r-2, r-3; carriers alike
 
         // ---- row r as floats (exact: the plane's values are 0..255) ----------------------------------------------
+        uint32_t pin[NP]; // LEAN_MEM: an outside lane loaded pixels of the row's first / last lane; they count as zero
+#pragma unroll
+        for (int i = 0; i < NP; i++) pin[i] = LEAN_MEM ? praw[i] & (uint32_t)lane_in : praw[i];
 #pragma unroll
         for (int e = 0; e < PX; e++) {
-            const uint32_t w = IN_U8 ? praw[e >> 2] >> (8 * (e & 3)) : praw[e >> 1] >> (16 * (e & 1));
+            const uint32_t w = IN_U8 ? pin[e >> 2] >> (8 * (e & 3)) : pin[e >> 1] >> (16 * (e & 1));
             F[k2][e] = (float)(w & 0xffu); // v_cvt_f32_ubyteN
         }
         // The previous row's edge-map pixels (DEFER) go out HERE, right behind the wait for this row's pixels: the
@@ -837,8 +878,11 @@ __device__ __forceinline__ void fmarch_strip(const StripJob &jb, uint8_t *stage_
         }
 
         // ---- gradient, magnitude and bin carriers for row y1 = r-1 -----------------------------------------------
+        // Only the rows ybeg-1 .. yend have a magnitude that a stored pixel's NMS reads: the two warm-up steps (rows
+        // ybeg-3, ybeg-2) and the steps of the rounded-up trip behind row yend skip the block on a scalar test.
         const int y1 = r - 1;
-        if (!ROW_EDGE || (y1 >= 0 && y1 < H)) {
+        const bool y1_read = !FLT_SKIP_DEAD_ROWS || (y1 >= ybeg - 1 && y1 <= yend);
+        if (y1_read && (!ROW_EDGE || (y1 >= 0 && y1 < H))) {
             float a[PX], b[PX];
 #pragma unroll
             for (int e = 0; e < PX; e++) {
@@ -859,14 +903,24 @@ __device__ __forceinline__ void fmarch_strip(const StripJob &jb, uint8_t *stage_
                 float gx = __fsub_rn(ar, al);
                 if (COL_EDGE) {
                     if (e == 0) gx = __fmaf_rn(-fix_l, a[0], gx); // column clamp at 0 ...
-                    // ... and at W-1: pixel e is the last column iff it is inside and pixel e + 1 is not
-                    gx = __fadd_rn(gx, __int_as_float(__float_as_int(a[e]) & (inside(e) ^ inside(e + 1))));
+                    if (LEAN) { // ... and at W-1, which can only be pixel 7
+                        if (e == PX - 1) gx = __fadd_rn(gx, __int_as_float(__float_as_int(a[e]) & last_m));
+                    } else {
+                        // ... and at W-1: pixel e is the last column iff it is inside and pixel e + 1 is not
+                        gx = __fadd_rn(gx, __int_as_float(__float_as_int(a[e]) & (inside(e) ^ inside(e + 1))));
+                    }
                 }
                 const float gy = __fadd_rn(__fmaf_rn(2.0f, b[e], bl), br);
                 float Ah, nh;
                 int m = f_pixel_mag_word(gx, gy, Ah, nh);
-                if (COL_EDGE) m &= inside(e); // out-of-image magnitudes become the floor
+                if (LEAN) { // the two outside pixels with an inside neighbour; every other outside gradient is zero
+                    if (e == 0) m &= keep0_m;
+                    if (e == PX - 1) m &= keep7_m;
+                } else if (COL_EDGE) {
+                    m &= inside(e); // out-of-image magnitudes become the floor
+                }
                 M[m2][e + 1] = f_pixel_mag_store<PLANES>(m, skip);
+                if (FLT_SKIP_DEAD_ROWS >= 2 && !(y1 >= ybeg && y1 < yend)) continue; // (wave-uniform) no NMS of this row
                 float qm, qp;
                 f_pixel_bin_signs(gx, gy, Ah, nh, qm, qp);
 #if FLT_CARRIERS == 1
@@ -882,7 +936,7 @@ __device__ __forceinline__ void fmarch_strip(const StripJob &jb, uint8_t *stage_
             }
         } else {
 #pragma unroll
-            for (int e = 0; e < PX; e++) M[m2][e + 1] = skip; // rows outside the image are skipped by NMS
+            for (int e = 0; e < PX; e++) M[m2][e + 1] = skip; // rows outside the image are skipped by NMS, dead rows never read
         }
         M[m2][0] = (int)from_left((uint32_t)M[m2][PX]);
         M[m2][PX + 1] = (int)from_right((uint32_t)M[m2][1]);
@@ -1115,20 +1169,22 @@ void sobel_nms_march_kernel(const void *__restrict__ in,
     const bool row_edge = (jb.ybeg < 2) || (jb.yend + (FLT && FLT_EARLY_RELOAD ? 6 : 5) >= H);
     if constexpr (FLT) {
         static_assert(NP == 4, "the f32 variant processes 8 pixels per lane");
+        // every PLANES launch (THR included) has W % 8 == 0: classify_march_any refuses other widths
+        constexpr bool WHOLE_LANES = PLANES;
 #ifdef PROBE_VARIANT
-        fmarch_strip<(PROBE_VARIANT & 1) != 0, (PROBE_VARIANT & 2) != 0, PLANES, LDS_PLANES, IN_U8>(jb, stage_mem, edge_lut);
+        fmarch_strip<(PROBE_VARIANT & 1) != 0, (PROBE_VARIANT & 2) != 0, PLANES, LDS_PLANES, IN_U8, WHOLE_LANES>(jb, stage_mem, edge_lut);
         return;
 #endif
         if (col_edge) {
             if (row_edge)
-                fmarch_strip<true, true, PLANES, LDS_PLANES, IN_U8>(jb, stage_mem, edge_lut);
+                fmarch_strip<true, true, PLANES, LDS_PLANES, IN_U8, WHOLE_LANES>(jb, stage_mem, edge_lut);
             else
-                fmarch_strip<true, false, PLANES, LDS_PLANES, IN_U8>(jb, stage_mem, edge_lut);
+                fmarch_strip<true, false, PLANES, LDS_PLANES, IN_U8, WHOLE_LANES>(jb, stage_mem, edge_lut);
         } else {
             if (row_edge)
-                fmarch_strip<false, true, PLANES, LDS_PLANES, IN_U8>(jb, stage_mem, edge_lut);
+                fmarch_strip<false, true, PLANES, LDS_PLANES, IN_U8, WHOLE_LANES>(jb, stage_mem, edge_lut);
             else
-                fmarch_strip<false, false, PLANES, LDS_PLANES, IN_U8>(jb, stage_mem, edge_lut);
+                fmarch_strip<false, false, PLANES, LDS_PLANES, IN_U8, WHOLE_LANES>(jb, stage_mem, edge_lut);
         }
     } else if (col_edge) {
         if (row_edge)
