@@ -135,6 +135,9 @@ EXPORTS = (
     "canny_hip_dev_canny_corners", "canny_hip_dev_corners_plane", "canny_hip_canny_corners",
     "canny_hip_corners_from_plane", "canny_hip_corner_response_of", "canny_hip_dev_corners_arith",
     "canny_hip_corners_profile_get", "canny_hip_selftest_corners_plan",
+    "canny_hip_dev_canny_corner_descriptors", "canny_hip_dev_corner_descriptors", "canny_hip_canny_corner_descriptors",
+    "canny_hip_corner_descriptors_from_plane", "canny_hip_descriptor_pattern", "canny_hip_dev_match_descriptors",
+    "canny_hip_match_descriptors", "canny_hip_descriptors_profile_get", "canny_hip_selftest_descriptors_plan",
 )
 
 _lib: Optional[C.CDLL] = None
@@ -353,6 +356,16 @@ def load() -> C.CDLL:
         "canny_hip_dev_corners_arith": ([p, p, sz, i, i, p], i),
         "canny_hip_corners_profile_get": ([p, i, C.POINTER(C.c_double), C.POINTER(C.c_long)], i),
         "canny_hip_selftest_corners_plan": ([i, i, i, i, ull, p], i),
+        "canny_hip_dev_canny_corner_descriptors": ([p, p, f, i, i, i, i, i, p, i, i, i, i, C.c_longlong, i, i, p, p, p, p,
+                                                    p, i, p, p], i),
+        "canny_hip_dev_corner_descriptors": ([p, p, i, i, i, p, p, i, i, p, p], i),
+        "canny_hip_canny_corner_descriptors": ([p, p, i, f, i, i, i, i, i, i, i, i, C.c_longlong, i, i, i, p, p, p, p], i),
+        "canny_hip_corner_descriptors_from_plane": ([p, i, i, p, i, i, p, p], i),
+        "canny_hip_descriptor_pattern": ([i, p], i),
+        "canny_hip_dev_match_descriptors": ([p, p, p, i, i, p, p, i, i, p, i, i, i, i, p, p], i),
+        "canny_hip_match_descriptors": ([p, i, p, i, i, i, i, p, ip], i),
+        "canny_hip_descriptors_profile_get": ([p, i, C.POINTER(C.c_double), C.POINTER(C.c_long)], i),
+        "canny_hip_selftest_descriptors_plan": ([i, ull, i, p], i),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -994,6 +1007,72 @@ def corners_plan(which, n_frames: int = 1, height: int = 2, width: int = 2, n: i
     if st:
         raise CannyHipError(st, "selftest_corners_plan")
     return LaunchPlan(*(int(v) for v in out[:5])), int(out[5])
+
+
+# ---- corner descriptors and Hamming matching -------------------------------------------------------
+DESC_BITS, DESC_WORDS, DESC_RADIUS, DESC_ROTATIONS, MATCH_WORDS = 256, 4, 15, 32, 4
+DESC_STEERED, MATCH_CROSS_CHECK = 1, 1
+MATCH_MAX_PAIRS = 1 << 20
+DESC_PARTS = ("describe", "match", "reverse", "finalize")
+DESCRIPTORS_PLANS = ("describe", "match")
+DESC_MATCH_DTYPE = np.dtype([("j", np.int32), ("d1", np.int32), ("d2", np.int32), ("flags", np.int32)])
+
+
+def descriptor_pattern(k: int):
+    """Host-only: int8 [256, 4], (ax, ay, bx, by) of every test in rotation k."""
+    out = np.zeros((DESC_BITS, 4), np.int8)
+    st = load().canny_hip_descriptor_pattern(int(k), _hp(out))
+    if st:
+        raise CannyHipError(st, "descriptor_pattern")
+    return out
+
+
+def corner_descriptors_from_plane(plane, corners, steered: bool = False):
+    """Host-only, needs no GPU: the descriptor rule on ONE uint8 plane [H, W] for records int64 [k, 4] (x, y, response,
+    rank; or [k, 2]: x, y) -> (uint64 [k, 4], int32 [k]: k + 256 * border, -1 outside the frame)."""
+    a = np.ascontiguousarray(plane, dtype=np.uint8)
+    if a.ndim != 2:
+        raise ValueError("expected a 2-D uint8 plane")
+    c = np.asarray(corners, np.int64).reshape(len(corners), -1)
+    rec = np.zeros((len(c), CORNER_WORDS), np.int64)
+    rec[:, :min(c.shape[1], CORNER_WORDS)] = c[:, :CORNER_WORDS]
+    desc, meta = np.zeros((len(c), DESC_WORDS), np.uint64), np.zeros(len(c), np.int32)
+    st = load().canny_hip_corner_descriptors_from_plane(_hp(a), a.shape[0], a.shape[1], _hp(rec), len(c),
+                                                        DESC_STEERED if steered else 0, _hp(desc), _hp(meta))
+    if st:
+        raise CannyHipError(st, "corner_descriptors_from_plane")
+    return desc, meta
+
+
+def match_descriptors(q, t, max_distance: int = 64, ratio_q8: int = 205, options: int = MATCH_CROSS_CHECK):
+    """Host-only, needs no GPU: the matching rule on ONE pair of sets uint64 [nq, 4], [nt, 4] -> (int32 [nq, 4]: j, d1,
+    d2, flags; the number accepted)."""
+    q = np.ascontiguousarray(q, np.uint64).reshape(-1, DESC_WORDS)
+    t = np.ascontiguousarray(t, np.uint64).reshape(-1, DESC_WORDS)
+    out, acc = np.zeros((len(q), MATCH_WORDS), np.int32), C.c_int(0)
+    st = load().canny_hip_match_descriptors(_hp(q) if len(q) else None, len(q), _hp(t) if len(t) else None, len(t),
+                                            int(max_distance), int(ratio_q8), int(options),
+                                            _hp(out) if len(q) else None, C.byref(acc))
+    if st:
+        raise CannyHipError(st, "match_descriptors")
+    return out, acc.value
+
+
+def consecutive_pairs(n_frames: int):
+    """int32 [n_frames - 1, 2]: the pairs (f, f + 1) of a batch of consecutive video frames, as the matcher takes them."""
+    f = np.arange(max(int(n_frames) - 1, 0), dtype=np.int32)
+    return np.ascontiguousarray(np.stack([f, f + 1], axis=1))
+
+
+def descriptors_plan(which, n: int, stride: int):
+    """Host-only: the LaunchPlan of a capped descriptor launch: "describe" (n frames, stride = corners_max) or "match" (n
+    pairs, stride of the side held in registers)."""
+    k = DESCRIPTORS_PLANS.index(which) if isinstance(which, str) else int(which)
+    out = np.zeros(5, np.uint64)
+    st = load().canny_hip_selftest_descriptors_plan(k, int(n), int(stride), _hp(out))
+    if st:
+        raise CannyHipError(st, "selftest_descriptors_plan")
+    return LaunchPlan(*(int(v) for v in out))
 
 
 # ---- chamfer template matching (DESIGN.md section 26) --------------------------------------------------------------------
@@ -2302,6 +2381,75 @@ class Context:
         """(total ms, launch groups) of part 0 max, 1 candidates, 2 collect, 3 accept (CORNER_PARTS)."""
         ms, n = C.c_double(0), C.c_long(0)
         self._check(self._L.canny_hip_corners_profile_get(self._h, part, C.byref(ms), C.byref(n)), "corners_profile_get")
+        return ms.value, n.value
+
+    # ---- corner descriptors and Hamming matching (DESIGN.md section 30) ---------------------------------------------
+    def dev_canny_corner_descriptors(self, d_img: int, sigma: float, min_val: int, max_val: int, h: int, w: int, n: int,
+                                     mode: int, block: int, k_q8: int, quality_q16: int, min_response: int, min_dist: int,
+                                     corners_max: int, d_corners: int, d_counts: int, d_desc: int, d_meta: int,
+                                     desc_options: int = 0, d_cand_counts: int = 0, d_max_response: int = 0,
+                                     d_response: int = 0, d_edges: int = 0):
+        """dev_canny_corners, then the descriptors of the corners on the smoothed plane, on the same stream; d_desc (4
+        uint64 per slot) and d_meta (int32 per slot) are mandatory.  Asynchronous."""
+        v = C.c_void_p
+        self._check(self._L.canny_hip_dev_canny_corner_descriptors(
+            self._h, v(d_img or None), sigma, min_val, max_val, h, w, n, v(d_edges or None), mode, block, k_q8, quality_q16,
+            min_response, min_dist, corners_max, v(d_corners or None), v(d_counts or None), v(d_cand_counts or None),
+            v(d_max_response or None), v(d_response or None), desc_options, v(d_desc or None), v(d_meta or None)),
+            "dev_canny_corner_descriptors")
+
+    def dev_corner_descriptors(self, d_plane: int, n: int, h: int, w: int, d_corners: int, d_counts: int, corners_max: int,
+                               d_desc: int, d_meta: int, desc_options: int = 0):
+        """The descriptors of device records on a device u8 plane [n][h][w]; d_plane 0: on the plane the context's last
+        canny call left."""
+        v = C.c_void_p
+        self._check(self._L.canny_hip_dev_corner_descriptors(self._h, v(d_plane or None), n, h, w, v(d_corners or None),
+                                                             v(d_counts or None), corners_max, desc_options,
+                                                             v(d_desc or None), v(d_meta or None)),
+                    "dev_corner_descriptors")
+
+    def canny_corner_descriptors(self, imgs, sigma: float, min_val: int, max_val: int, mode: int = CORNERS_MIN_EIGEN,
+                                 block: int = 3, k_q8: int = 0, quality_q16: int = 655, min_response: int = 0,
+                                 min_dist: int = 0, corners_max: int = 256, steered: bool = False):
+        """canny(), the corners and their descriptors on the GPU: imgs (H, W) or (N, H, W) uint8 -> per frame a tuple
+        (corners as CORNER_DTYPE, descriptors uint64 [k, 4], meta int32 [k])."""
+        a = np.ascontiguousarray(imgs, dtype=np.uint8)
+        if a.ndim == 2:
+            a = a[None]
+        if a.ndim != 3:
+            raise ValueError("expected uint8 [H, W] or [n_frames, H, W]")
+        n, h, w = a.shape
+        cm = max(int(corners_max), 1)
+        rec = np.zeros((n, cm, CORNER_WORDS), np.int64)
+        desc, meta = np.zeros((n, cm, DESC_WORDS), np.uint64), np.zeros((n, cm), np.int32)
+        counts = np.zeros(n, np.int32)
+        self._check(self._L.canny_hip_canny_corner_descriptors(self._h, _hp(a), n, sigma, min_val, max_val, h, w, mode,
+                                                               block, k_q8, quality_q16, min_response, min_dist,
+                                                               corners_max, DESC_STEERED if steered else 0, _hp(rec),
+                                                               _hp(counts), _hp(desc), _hp(meta)),
+                    "canny_corner_descriptors")
+        return [(np.ascontiguousarray(rec[f, :int(counts[f])]).view(CORNER_DTYPE).reshape(-1),
+                 desc[f, :int(counts[f])].copy(), meta[f, :int(counts[f])].copy()) for f in range(n)]
+
+    def dev_match_descriptors(self, d_q_desc: int, d_q_counts: int, n_q_frames: int, stride_q: int, d_t_desc: int,
+                              d_t_counts: int, n_t_frames: int, stride_t: int, pairs, d_matches: int, d_pair_counts: int,
+                              max_distance: int = 64, ratio_q8: int = 205, options: int = MATCH_CROSS_CHECK):
+        """Brute-force Hamming matching of the pairs (host int array [n_pairs, 2]: q frame, t frame; see
+        consecutive_pairs) between two descriptor sets on the device (they may be the same buffers); d_matches receives
+        [n_pairs][stride_q][4] int32 (j, d1, d2, flags), d_pair_counts [n_pairs] int32.  Asynchronous."""
+        v = C.c_void_p
+        pr = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+        self._check(self._L.canny_hip_dev_match_descriptors(self._h, v(d_q_desc or None), v(d_q_counts or None), n_q_frames,
+                                                            stride_q, v(d_t_desc or None), v(d_t_counts or None),
+                                                            n_t_frames, stride_t, _hp(pr) if len(pr) else None, len(pr),
+                                                            max_distance, ratio_q8, options, v(d_matches or None),
+                                                            v(d_pair_counts or None)), "dev_match_descriptors")
+
+    def descriptors_profile_get(self, part: int) -> Tuple[float, int]:
+        """(total ms, launch groups) of part 0 describe, 1 match, 2 reverse, 3 finalize (DESC_PARTS)."""
+        ms, n = C.c_double(0), C.c_long(0)
+        self._check(self._L.canny_hip_descriptors_profile_get(self._h, part, C.byref(ms), C.byref(n)),
+                    "descriptors_profile_get")
         return ms.value, n.value
 
     # ---- sub-pixel circle fits (least-squares refit of the Hough circles from edgels; DESIGN.md section 25) ------

@@ -416,6 +416,9 @@ struct canny_hip_ctx {
     std::vector<canny_hip_chamfer_set *> chamfer_sets; // the sets created on this context and not yet destroyed
     // corners, per chunk of frames: the collected keys, the radix select's state, the maxima, histograms and counters
     DevBuf corners_ws;
+    // descriptor matching: the pairs as the kernels read them, then per (pair, train slot) its best query
+    DevBuf desc_ws;
+    std::vector<int> desc_pairs; // the validated pairs of the last match call: what its upload reads
     DevBuf plane_s, plane_c, stamps, flags; // hysteresis bit-planes / scheduling words
     DevBuf io[4];     // staging for the host-pointer stage functions
     std::string ws_name; // canny_hip_selftest_workspace: the name it handed out last
@@ -447,7 +450,8 @@ struct canny_hip_ctx {
     // (canny_hip_edgels_profile_get), then the one of the line fits (canny_hip_line_fits_profile_get), then the one of the
     // circle fits (canny_hip_circle_fits_profile_get), then the four of the chamfer matching
     // (canny_hip_chamfer_profile_get), then the three of the contour shape measures (canny_hip_shapes_profile_get), then the two of the edge curves
-    // (canny_hip_curves_profile_get), then the four of the corners (canny_hip_corners_profile_get).  The mask is a non-negative int option: bit 30 is the last it can
+    // (canny_hip_curves_profile_get), then the four of the corners (canny_hip_corners_profile_get), then the four of the descriptors and their matching
+    // (canny_hip_descriptors_profile_get).  The mask is a non-negative int option: bit 30 is the last it can
     // carry, and the three polygon slots, the two edgel slots, the line-fit slot and the circle-fit slot behind them go by
     // it together
     static constexpr int kProfHough = CANNY_HIP_STAGE_END, kProfComponents = CANNY_HIP_STAGE_END + 3;
@@ -463,7 +467,8 @@ struct canny_hip_ctx {
     static constexpr int kProfShapes = kProfChamfer + CANNY_HIP_CHAMFER_PARTS;
     static constexpr int kProfCurves = kProfShapes + CANNY_HIP_SHAPE_PARTS;
     static constexpr int kProfCorners = kProfCurves + CANNY_HIP_CURVE_PARTS;
-    static constexpr int kProfSlots = kProfCorners + CANNY_HIP_CORNER_PARTS;
+    static constexpr int kProfDescriptors = kProfCorners + CANNY_HIP_CORNER_PARTS;
+    static constexpr int kProfSlots = kProfDescriptors + CANNY_HIP_DESC_PARTS;
     static constexpr int kProfLastBit = 30;
     static_assert(kProfPolygons == kProfLastBit && kProfEdgels > kProfLastBit,
                   "profile_stage_mask has one bit per slot up to the polygon parts; every slot from there on follows bit 30");
@@ -2000,6 +2005,7 @@ void collect_workspaces(const canny_hip_ctx *c, const std::string &prefix, std::
     add("chamfer_ws", c->chamfer_ws, I);   // keys address score cells, totals bound the sort, counters hand out slots
     add("chamfer_dist2", c->chamfer_dist2, I); // doubles as the column scan's stack (see edt_stack)
     add("corners_ws", c->corners_ws, I);   // keys address pixels, totals bound the sort, counters hand out slots
+    add("desc_ws", c->desc_ws, I);         // the pairs address frames, the best queries are compared with indices
     add("plane_s", c->plane_s, D);
     add("plane_c", c->plane_c, D);
     add("stamps", c->stamps, I);           // tile queues and their counters
@@ -2115,6 +2121,7 @@ void canny_hip_ctx_destroy(canny_hip_ctx *ctx)
     ctx->chamfer_ws.release();
     ctx->chamfer_dist2.release();
     ctx->corners_ws.release();
+    ctx->desc_ws.release();
     ctx->cc_parent.release();
     ctx->cc_ws.release();
     ctx->ct_ws.release();
@@ -5987,6 +5994,200 @@ int canny_hip_selftest_corners_plan(int which, int n_frames, int height, int wid
         if (!n) return CANNY_HIP_ERR_INVALID;
         p = plan_corners_arith((size_t)n);
         out[5] = 0;
+    } else {
+        return CANNY_HIP_ERR_INVALID;
+    }
+    out[0] = p.units, out[1] = p.per_group, out[2] = p.grid, out[3] = p.trips(), out[4] = (unsigned long long)p.aux;
+    return CANNY_HIP_OK;
+}
+
+// ---- corner descriptors and Hamming matching (canny_descriptors.hip) ------------------------------
+} // extern "C"
+
+namespace {
+
+// THE check of the descriptor arguments; needs no device and writes nothing
+int descriptors_check(int height, int width, int n_frames, int corners_max, int options, const void *d_corners,
+                      const void *d_counts, const void *d_desc, const void *d_meta)
+{
+    if ((options & ~CANNY_HIP_DESC_STEERED) || corners_max < 1 || !d_corners || !d_counts || !d_desc || !d_meta ||
+        ((uintptr_t)d_corners & 7) || ((uintptr_t)d_desc & 7) || height < 2 || width < 2 || n_frames < 1)
+        return CANNY_HIP_ERR_INVALID;
+    if ((long long)height * width >= 0x80000000LL || n_frames > 65535 || corners_max > kHoughMaxLines)
+        return CANNY_HIP_ERR_UNSUPPORTED;
+    return CANNY_HIP_OK;
+}
+
+int dev_describe(canny_hip_ctx *ctx, const void *plane, bool plane_u8, int n, int h, int w, const long long *d_corners,
+                 const int *d_counts, int corners_max, int options, unsigned long long *d_desc, int *d_meta)
+{
+    StageTimer tm(ctx, canny_hip_ctx::kProfDescriptors + CANNY_HIP_DESC_PART_DESCRIBE);
+    HIP_TRY(ctx, launch_desc_describe(plane, plane_u8, n, h, w, d_corners, d_counts, corners_max,
+                                      (options & CANNY_HIP_DESC_STEERED) != 0, d_desc, d_meta, ctx->stream));
+    return CANNY_HIP_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int canny_hip_dev_canny_corner_descriptors(canny_hip_ctx *ctx, const unsigned char *d_img, float sigma, int min_val,
+                                           int max_val, int height, int width, int n_frames, short *d_edges, int mode,
+                                           int block, int k_q8, int quality_q16, long long min_response, int min_dist,
+                                           int corners_max, long long *d_corners, int *d_counts, int *d_cand_counts,
+                                           long long *d_max_response, long long *d_response, int desc_options,
+                                           unsigned long long *d_desc, int *d_meta)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if ((rc = descriptors_check(height, width, n_frames, corners_max, desc_options, d_corners, d_counts, d_desc, d_meta)))
+        return rc;
+    // the corners call checks its own arguments before it queues anything
+    if ((rc = canny_hip_dev_canny_corners(ctx, d_img, sigma, min_val, max_val, height, width, n_frames, d_edges, mode, block,
+                                          k_q8, quality_q16, min_response, min_dist, corners_max, d_corners, d_counts,
+                                          d_cand_counts, d_max_response, d_response)))
+        return rc;
+    return dev_describe(ctx, ctx->smoothed.p, ctx->last_canny_u8 != 0, n_frames, height, width, d_corners, d_counts,
+                        corners_max, desc_options, d_desc, d_meta);
+}
+
+int canny_hip_dev_corner_descriptors(canny_hip_ctx *ctx, const unsigned char *d_plane, int n_frames, int height, int width,
+                                     const long long *d_corners, const int *d_counts, int corners_max, int desc_options,
+                                     unsigned long long *d_desc, int *d_meta)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if ((rc = descriptors_check(height, width, n_frames, corners_max, desc_options, d_corners, d_counts, d_desc, d_meta)))
+        return rc;
+    const void *plane = d_plane;
+    bool plane_u8 = true;
+    if (!d_plane) {
+        // the plane the last canny call left: only for the batch it belongs to
+        if (!ctx->last_canny_n || !ctx->smoothed.p || ctx->last_canny_n != n_frames || ctx->last_canny_h != height ||
+            ctx->last_canny_w != width)
+            return CANNY_HIP_ERR_INVALID;
+        plane = ctx->smoothed.p;
+        plane_u8 = ctx->last_canny_u8 != 0;
+    }
+    if ((rc = finish_pending(ctx))) return rc;
+    return dev_describe(ctx, plane, plane_u8, n_frames, height, width, d_corners, d_counts, corners_max, desc_options,
+                        d_desc, d_meta);
+}
+
+int canny_hip_canny_corner_descriptors(canny_hip_ctx *ctx, const unsigned char *imgs, int n_frames, float sigma,
+                                       int min_val, int max_val, int height, int width, int mode, int block, int k_q8,
+                                       int quality_q16, long long min_response, int min_dist, int corners_max,
+                                       int desc_options, long long *corners, int *counts, unsigned long long *desc,
+                                       int *meta)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!imgs) return CANNY_HIP_ERR_INVALID;
+    if ((rc = descriptors_check(height, width, n_frames, corners_max, desc_options, corners, counts, desc, meta))) return rc;
+    const CornerArgs a{mode, block, k_q8, quality_q16, min_response, min_dist, corners_max};
+    if ((rc = corners_check(height, width, n_frames, a, CornerOut{corners, counts, nullptr, nullptr, nullptr}))) return rc;
+    const size_t slots = (size_t)n_frames * corners_max;
+    // one staging block: records (4 long long per slot) | descriptors (4 words per slot) | meta | counts
+    HIP_TRY(ctx, ctx->io[1].ensure(slots * (CANNY_HIP_CORNER_WORDS * sizeof(long long) +
+                                            CANNY_HIP_DESC_WORDS * sizeof(unsigned long long) + sizeof(int)) +
+                                   (size_t)n_frames * sizeof(int)));
+    long long *d_rec = (long long *)ctx->io[1].p;
+    unsigned long long *d_desc = (unsigned long long *)(d_rec + slots * CANNY_HIP_CORNER_WORDS);
+    int *d_meta = (int *)(d_desc + slots * CANNY_HIP_DESC_WORDS), *d_cnt = d_meta + slots;
+    if ((rc = h2d(ctx, ctx->io[0], imgs, npx(height, width, n_frames)))) return rc;
+    if ((rc = canny_hip_dev_canny_corner_descriptors(ctx, (const unsigned char *)ctx->io[0].p, sigma, min_val, max_val,
+                                                     height, width, n_frames, nullptr, mode, block, k_q8, quality_q16,
+                                                     min_response, min_dist, corners_max, d_rec, d_cnt, nullptr, nullptr,
+                                                     nullptr, desc_options, d_desc, d_meta)))
+        return rc;
+    std::vector<int> cnt((size_t)n_frames);
+    if ((rc = d2h_sync(ctx, cnt.data(), d_cnt, cnt.size() * sizeof(int)))) return rc;
+    for (int f = 0; f < n_frames; f++) { // only the filled slots of each frame come down
+        const size_t k = (size_t)cnt[f], at = (size_t)f * corners_max;
+        if (!k) continue;
+        HIP_TRY(ctx, hipMemcpyAsync(corners + at * CANNY_HIP_CORNER_WORDS, d_rec + at * CANNY_HIP_CORNER_WORDS,
+                                    k * CANNY_HIP_CORNER_WORDS * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(desc + at * CANNY_HIP_DESC_WORDS, d_desc + at * CANNY_HIP_DESC_WORDS,
+                                    k * CANNY_HIP_DESC_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost,
+                                    ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(meta + at, d_meta + at, k * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    std::memcpy(counts, cnt.data(), (size_t)n_frames * sizeof(int));
+    return CANNY_HIP_OK;
+}
+
+// canny_hip_corner_descriptors_from_plane, canny_hip_descriptor_pattern and canny_hip_match_descriptors, the rule in plain
+// C++, live in canny_descriptors_host.cpp.
+
+int canny_hip_dev_match_descriptors(canny_hip_ctx *ctx, const unsigned long long *d_q_desc, const int *d_q_counts,
+                                    int n_q_frames, int stride_q, const unsigned long long *d_t_desc, const int *d_t_counts,
+                                    int n_t_frames, int stride_t, const int *pairs, int n_pairs, int max_distance,
+                                    int ratio_q8, int options, int *d_matches, int *d_pair_counts)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!d_q_desc || !d_q_counts || !d_t_desc || !d_t_counts || !pairs || !d_matches || !d_pair_counts || n_q_frames < 1 ||
+        n_t_frames < 1 || stride_q < 1 || stride_t < 1 || n_pairs < 1 || max_distance < 0 ||
+        max_distance > CANNY_HIP_DESC_BITS || ratio_q8 < 0 || ratio_q8 > 256 || (options & ~CANNY_HIP_MATCH_CROSS_CHECK) ||
+        ((uintptr_t)d_q_desc & 7) || ((uintptr_t)d_t_desc & 7))
+        return CANNY_HIP_ERR_INVALID;
+    if (stride_q > kHoughMaxLines || stride_t > kHoughMaxLines || n_q_frames > 65535 || n_t_frames > 65535 ||
+        n_pairs > CANNY_HIP_MATCH_MAX_PAIRS)
+        return CANNY_HIP_ERR_UNSUPPORTED;
+    for (int p = 0; p < n_pairs; p++)
+        if (pairs[2 * p] < 0 || pairs[2 * p] >= n_q_frames || pairs[2 * p + 1] < 0 || pairs[2 * p + 1] >= n_t_frames)
+            return CANNY_HIP_ERR_INVALID;
+    if ((rc = finish_pending(ctx))) return rc;
+    // the workspace: the pairs | per (pair, train slot) its best query
+    const size_t pair_ints = 2 * (size_t)n_pairs;
+    HIP_TRY(ctx, ctx->desc_ws.ensure((pair_ints + (size_t)n_pairs * stride_t) * sizeof(int)));
+    int *d_pairs = (int *)ctx->desc_ws.p, *d_back = d_pairs + pair_ints;
+    ctx->desc_pairs.assign(pairs, pairs + pair_ints);
+    HIP_TRY(ctx, hipMemcpyAsync(d_pairs, ctx->desc_pairs.data(), pair_ints * sizeof(int), hipMemcpyHostToDevice,
+                                ctx->stream));
+    const int part = canny_hip_ctx::kProfDescriptors;
+    {
+        StageTimer tm(ctx, part + CANNY_HIP_DESC_PART_MATCH);
+        HIP_TRY(ctx, launch_desc_match(d_q_desc, d_q_counts, stride_q, d_t_desc, d_t_counts, stride_t, d_pairs, n_pairs,
+                                       false, d_matches, ctx->stream));
+    }
+    {
+        StageTimer tm(ctx, part + CANNY_HIP_DESC_PART_REVERSE);
+        HIP_TRY(ctx, launch_desc_match(d_t_desc, d_t_counts, stride_t, d_q_desc, d_q_counts, stride_q, d_pairs, n_pairs,
+                                       true, d_back, ctx->stream));
+    }
+    {
+        StageTimer tm(ctx, part + CANNY_HIP_DESC_PART_FINALIZE);
+        HIP_TRY(ctx, launch_desc_finalize(d_q_counts, stride_q, stride_t, d_pairs, n_pairs, d_back, max_distance, ratio_q8,
+                                          (options & CANNY_HIP_MATCH_CROSS_CHECK) != 0, d_matches, d_pair_counts,
+                                          ctx->stream));
+    }
+    return CANNY_HIP_OK;
+}
+
+int canny_hip_descriptors_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches)
+{
+    if (part < 0 || part >= CANNY_HIP_DESC_PARTS || !total_ms || !launches) return CANNY_HIP_ERR_INVALID;
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if ((rc = profile_collect(ctx))) return rc;
+    *total_ms = ctx->total_ms[canny_hip_ctx::kProfDescriptors + part];
+    *launches = ctx->launches[canny_hip_ctx::kProfDescriptors + part];
+    return CANNY_HIP_OK;
+}
+
+// Host-only: the launch plans of the capped launches of the descriptors and their matching.
+int canny_hip_selftest_descriptors_plan(int which, unsigned long long n, int stride, unsigned long long *out)
+{
+    if (!out || !n || stride < 1 || stride > kHoughMaxLines) return CANNY_HIP_ERR_INVALID;
+    LaunchPlan p;
+    if (which == CANNY_HIP_DESCRIPTORS_PLAN_DESCRIBE) {
+        if (n > 65535) return CANNY_HIP_ERR_INVALID;
+        p = plan_desc_slots(n * (unsigned long long)stride);
+    } else if (which == CANNY_HIP_DESCRIPTORS_PLAN_MATCH) {
+        if (n > CANNY_HIP_MATCH_MAX_PAIRS) return CANNY_HIP_ERR_INVALID;
+        p = plan_desc_match(n, stride);
     } else {
         return CANNY_HIP_ERR_INVALID;
     }

@@ -778,6 +778,28 @@ hipError_t launch_corners_accept(int nf, int height, int width, const CornerArgs
 // The response function alone on n triples (sxx, syy, sxy): the arithmetic test's hook.
 hipError_t launch_corners_arith(const int *sums, size_t n, int mode, int k_q8, long long *out, hipStream_t stream);
 
+// ---- corner descriptors and Hamming matching (canny_descriptors.hip) --------------------
+// describe: the n_frames * corners_max record slots, four (one a wave) per workgroup and trip.  match, reverse: the
+// (pair, block of 256 descriptors of the register side) units, one per workgroup and trip.  (Reported by
+// canny_hip_selftest_descriptors_plan, not by a kind.)
+LaunchPlan plan_desc_slots(unsigned long long slots);
+LaunchPlan plan_desc_match(unsigned long long n_pairs, int stride);
+// Descriptors of the records (4 long long a slot, slot f * corners_max + j, j < counts[f]) on plane (bytes if plane_u8, else
+// shorts in [0, 255]): desc 4 words and meta one int per slot; slots past counts[f] are not written.
+hipError_t launch_desc_describe(const void *plane, bool plane_u8, int n_frames, int height, int width,
+                                const long long *corners, const int *counts, int corners_max, int steered,
+                                unsigned long long *desc, int *meta, hipStream_t stream);
+// Best and second-best neighbour of every descriptor of the q side among the t side's, per pair (pairs: device, 2 ints a
+// pair: q frame, t frame).  !reverse: out [n_pairs][stride_q][4] receives j, d1, d2.  reverse: the caller passes the train
+// set as q and the query set as t, the pairs are read the other way round, out [n_pairs][stride_q] receives j.
+hipError_t launch_desc_match(const unsigned long long *q_desc, const int *q_counts, int stride_q,
+                             const unsigned long long *t_desc, const int *t_counts, int stride_t, const int *pairs,
+                             int n_pairs, bool reverse, int *out, hipStream_t stream);
+// The flags (word 3 of every match) and the accepted matches of each pair; back is the reverse launch's output.
+hipError_t launch_desc_finalize(const int *q_counts, int stride_q, int stride_t, const int *pairs, int n_pairs,
+                                const int *back, int max_distance, int ratio_q8, int cross, int *matches, int *pair_counts,
+                                hipStream_t stream);
+
 // ---- measurement aid ------------------------------------------------------------------------
 // Plain device copy of nbytes (multiple of 16; both pointers 16-byte aligned): what a 1:1 read/write stream reaches.
 hipError_t launch_probe_copy(const void *src, void *dst, size_t nbytes, hipStream_t stream, const LaunchEvents &ev = {});

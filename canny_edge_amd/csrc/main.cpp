@@ -2,7 +2,7 @@
 // the webcam and the GUI:  ./Main sigma minVal maxVal [-c] [-s] [-i in.pgm|in.ppm|in.jpg] [-o dir] [-p] [-n WxH] [-b dir]
 //        [-l rho,theta_degrees,threshold[,lines_max]] [-g min_length,max_gap[,exclusive]] [-m min_area] [-t] [-w min_length] [-d] [-e]
 //        [-r min_radius,max_radius,threshold,support[,min_dist[,cell_shift]]] [-y epsilon[,ratio]] [-u]
-//        [-q quality_q16,min_dist,corners_max[,block[,k_q8]]]
+//        [-q quality_q16,min_dist,corners_max[,block[,k_q8]]] [-j upright|steered]
 //
 // Kept from the reference: the three positionals may appear anywhere relative to the flags
 // (src/main.cpp:29-46); exactly three are required, otherwise the usage text is printed and the
@@ -57,6 +57,10 @@
 // Added: -q quality_q16,min_dist,corners_max[,block[,k_q8]] finds the corners of the frame's smoothed plane on the GPU
 // (canny_hip_canny_corners; Shi-Tomasi, or Harris when k_q8 is given) and writes one "frame x y response rank" line per
 // corner to canny_corners.txt.  A malformed -q is a usage error (exit 2).  Without -q nothing changes.
+// Added: -j upright|steered (with -q) also describes every corner on the GPU (canny_hip_canny_corner_descriptors; steered:
+// the pattern turned to the patch's intensity centroid) and writes one "x y k border" and 64 hex digits (words 0..3, 16
+// digits each) per corner to canny_descriptors.txt.  -j without -q, or with another word, is a usage error (exit 2).  (-b
+// is the batch directory, so the descriptors took the next free letter.)
 // Added: -x a.pgm[:b.pgm...],trunc_q4,max_mean_q4,min_dist matches the frame's edge map against the shapes of the PGM files
 // (their non-zero pixels, anchored at the centre) on the GPU (canny_hip_canny_chamfer) and writes one "frame x y template
 // score mean" row per match, in order, to canny_matches.txt in the -o directory (stdout without -o); mean is the mean
@@ -787,6 +791,48 @@ static int run_corners(const vector<unsigned char> &frame, int height, int width
     return 0;
 }
 
+// -q with -j: the corners as run_corners writes them, and their descriptors, "x y k border hex" per corner, in order
+static int run_descriptors(const vector<unsigned char> &frame, int height, int width, float sigma, int minVal, int maxVal,
+                           const int *a, int desc_options, const string &outdir)
+{
+    const int corners_max = a[2], mode = a[4] >= 0 ? CANNY_HIP_CORNERS_HARRIS : CANNY_HIP_CORNERS_MIN_EIGEN;
+    vector<long long> rec((size_t)corners_max * CANNY_HIP_CORNER_WORDS);
+    vector<unsigned long long> desc((size_t)corners_max * CANNY_HIP_DESC_WORDS);
+    vector<int> meta((size_t)corners_max);
+    int count = 0;
+    canny_hip_ctx *ctx = nullptr;
+    int st = canny_hip_ctx_create(&ctx, 0);
+    if (!st)
+        st = canny_hip_canny_corner_descriptors(ctx, frame.data(), 1, sigma, minVal, maxVal, height, width, mode, a[3],
+                                                a[4] >= 0 ? a[4] : 0, a[0], 0, a[1], corners_max, desc_options, rec.data(),
+                                                &count, desc.data(), meta.data());
+    if (st) {
+        fprintf(stderr, "ERROR: -j: %s\n", st == CANNY_HIP_ERR_RUNTIME && ctx ? canny_hip_last_error(ctx) : canny_hip_status_string(st));
+        if (ctx) canny_hip_ctx_destroy(ctx);
+        return 1;
+    }
+    canny_hip_ctx_destroy(ctx);
+    FILE *fc = outdir.empty() ? stdout : fopen((outdir + "/canny_corners.txt").c_str(), "w");
+    FILE *fd = outdir.empty() ? stdout : fopen((outdir + "/canny_descriptors.txt").c_str(), "w");
+    if (!fc || !fd) {
+        fprintf(stderr, "ERROR: cannot write %s/canny_descriptors.txt\n", outdir.c_str());
+        return 1;
+    }
+    for (int j = 0; j < count; j++) {
+        const long long *c = rec.data() + (size_t)j * CANNY_HIP_CORNER_WORDS;
+        fprintf(fc, "0 %lld %lld %lld %lld\n", c[0], c[1], c[2], c[3]);
+    }
+    for (int j = 0; j < count; j++) {
+        const long long *c = rec.data() + (size_t)j * CANNY_HIP_CORNER_WORDS;
+        const unsigned long long *d = desc.data() + (size_t)j * CANNY_HIP_DESC_WORDS;
+        fprintf(fd, "%lld %lld %d %d %016llx%016llx%016llx%016llx\n", c[0], c[1], meta[j] & 255, meta[j] >> 8, d[0], d[1], d[2],
+                d[3]);
+    }
+    if (fc != stdout) fclose(fc);
+    if (fd != stdout) fclose(fd);
+    return 0;
+}
+
 int main(int argc, char *argv[])
 {
     // The batch pipeline wants its upload, compute and download streams on separate hardware queues; HIP reads this
@@ -822,6 +868,7 @@ int main(int argc, char *argv[])
     int chamfer_args[3] = {0, 0, 0};    // ... trunc_q4, max_mean_q4, min_dist
     bool want_corners = false;
     int corner_args[5] = {0, 0, 0, 3, -1}; // -q: quality_q16, min_dist, corners_max, block, k_q8 (-1: Shi-Tomasi)
+    int desc_options = -1;                 // -j: -1 absent, 0 upright, CANNY_HIP_DESC_STEERED
     int width = WIDTH, height = HEIGHT;
     vector<string> values;
 
@@ -986,6 +1033,13 @@ int main(int argc, char *argv[])
                 exit(2);
             }
             want_corners = true;
+        } else if (arg == "-j") {
+            const string word = i + 1 < argc ? argv[++i] : "";
+            if (word != "upright" && word != "steered") {
+                fprintf(stderr, "ERROR: -j expects upright or steered (the descriptors of the corners of -q)\n");
+                exit(2);
+            }
+            desc_options = word == "steered" ? CANNY_HIP_DESC_STEERED : 0;
         } else if (arg == "-w" && i + 1 < argc) {
             char tail = 0; // a whole integer only
             if (sscanf(argv[++i], "%d%c", &curve_min_length, &tail) != 1) {
@@ -1015,6 +1069,10 @@ int main(int argc, char *argv[])
     }
     if (want_circle_fits && !want_circles) {
         fprintf(stderr, "ERROR: -k needs the circles of -r min_radius,max_radius,threshold,support[,min_dist[,cell_shift]]\n");
+        exit(2);
+    }
+    if (desc_options >= 0 && !want_corners) {
+        fprintf(stderr, "ERROR: -j needs the corners of -q quality_q16,min_dist,corners_max[,block[,k_q8]]\n");
         exit(2);
     }
     if (want_polygons && !want_contours) {
@@ -1064,6 +1122,8 @@ int main(int argc, char *argv[])
         fprintf(stderr, "       line per match (mean in pixels) -> canny_matches.txt in the -o dir\n");
         fprintf(stderr, "   -q quality_q16,min_dist,corners_max[,block[,k_q8]]: corners of the smoothed plane (Shi-Tomasi; with k_q8 Harris,\n");
         fprintf(stderr, "       k in 1/256), one \"frame x y response rank\" line each -> canny_corners.txt in the -o dir\n");
+        fprintf(stderr, "   -j upright|steered: with -q, the 256-bit descriptor of every corner (steered: turned to the patch's centroid),\n");
+        fprintf(stderr, "       one \"x y k border\" and 64 hex digits each -> canny_descriptors.txt in the -o dir\n");
         fprintf(stderr, "   -d: distance of every pixel to the nearest edge pixel, min(255, floor) -> canny_dist.pgm in the -o dir\n");
         fprintf(stderr, "   -e: sub-pixel edgel of every edge pixel, one \"x y gx gy mag dir refined\" line each (x, y in pixels to three\n");
         fprintf(stderr, "       decimals, mag in grey levels, dir 0..3) -> canny_edgels.txt in the -o dir\n");
@@ -1153,7 +1213,10 @@ int main(int argc, char *argv[])
         const int rc = run_chamfer(frame, height, width, sigma, minVal, maxVal, chamfer_shapes, chamfer_args, outdir);
         if (rc) return rc;
     }
-    if (want_corners) {
+    if (want_corners && desc_options >= 0) {
+        const int rc = run_descriptors(frame, height, width, sigma, minVal, maxVal, corner_args, desc_options, outdir);
+        if (rc) return rc;
+    } else if (want_corners) {
         const int rc = run_corners(frame, height, width, sigma, minVal, maxVal, corner_args, outdir);
         if (rc) return rc;
     }

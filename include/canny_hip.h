@@ -52,7 +52,8 @@
 extern "C" {
 #endif
 
-#define CANNY_HIP_VERSION 1900       /* 0.19.0: + corners: Harris / Shi-Tomasi on the smoothed plane */
+#define CANNY_HIP_VERSION 2000       /* 0.20.0: + corner descriptors and Hamming matching between frames */
+/* 0.19.0: + corners: Harris / Shi-Tomasi on the smoothed plane */
 /* 0.18.0: + edge curves: the edge map linked into ordered chains */
 /* 0.17.0: + contour shape measures: moments, convex hull, minimum-area rectangle */
 /* 0.16.0: + chamfer template matching on the distance transform */
@@ -1813,6 +1814,111 @@ int canny_hip_corner_response_of(int sxx, int syy, int sxy, int mode, int k_q8, 
  * d_r receives n long long).  Asynchronous. */
 int canny_hip_dev_corners_arith(canny_hip_ctx *ctx, const int *d_sums, size_t n, int mode, int k_q8, long long *d_r);
 
+/* ---- corner descriptors and Hamming matching --------------------------------------------------------------------------------
+ * Which corner of this frame is which corner of the next?  A binary descriptor per corner -- 256 intensity comparisons on the
+ * smoothed plane, optionally steered by the patch's intensity centroid: the BRIEF / ORB idea, with a pattern and rounding of
+ * the library's own -- and a brute-force Hamming matcher between the descriptor sets of pairs of frames (best and
+ * second-best neighbour, distance, ratio and mutual tests: what cv::BFMatcher(NORM_HAMMING) with knnMatch(k = 2) and
+ * crossCheck answer).  On the GPU, on the context's stream, no host round trip, no atomics.  All integers: the same bytes on
+ * every run and every machine.  tests/descriptors_rule.py restates the rule in numpy and plain Python ints,
+ * csrc/canny_descriptors_host.cpp in plain C++.  THE RULE:
+ *   Plane: P is a u8 plane of height x width, height, width >= 2.  (The context's own plane may be s16 with values in
+ *     [0, 255], as for the corners; a caller's plane is u8 only.)  Every read is
+ *     P(clamp(y + dy, 0, height - 1), clamp(x + dx, 0, width - 1)): every corner gets a descriptor, nothing is read
+ *     outside the plane.
+ *   Corners: the 4-word records (x, y, response, rank) of the corners calls at slots f * corners_max + j, j < counts[f];
+ *     only x and y are read.  A record whose x or y lies outside the frame reads nothing: its descriptor is four zero words
+ *     and its meta word is -1.
+ *   Pattern (CANNY_HIP_DESC_BITS = 256 tests, CANNY_HIP_DESC_RADIUS = 15): a generator with state s = 0x43414E59.  A draw
+ *     is s = (s * 1664525 + 1013904223) mod 2^32, then v = (s >> 16) % 27 - 13.  An attempt draws ax, ay, bx, by in that
+ *     order and is rejected if ax^2 + ay^2 > 169 or bx^2 + by^2 > 169, or |ax - bx| + |ay - by| < 4, or the pair was
+ *     already taken, in either order; 256 tests exist after 491 attempts.
+ *   Rotation k of CANNY_HIP_DESC_ROTATIONS = 32: rot_k(x, y) = (rd(x * C_k - y * S_k), rd(x * S_k + y * C_k)),
+ *     rd(v) = floor((v + 8192) / 16384); C_k = cos(2 pi k / 32) in Q14 from the nine constants 16384, 16069, 15137, 13623,
+ *     11585, 9102, 6270, 3196, 0 by symmetry, S_k = C_(k - 8); y points down.  Every rotated offset stays within +-13, the
+ *     256 tests stay distinct in every rotation, no test has both ends equal, and rotation k + 8 is exactly the 90-degree
+ *     rotation (x, y) -> (-y, x) of rotation k, for every k.  The 32 x 256 x 4 signed bytes are data in
+ *     csrc/canny_desc_pattern.h; canny_hip_descriptor_pattern returns one rotation.
+ *   Orientation (option CANNY_HIP_DESC_STEERED): m10 = sum of dx * P, m01 = sum of dy * P over the 709 offsets with
+ *     dx^2 + dy^2 <= 225 (clamped reads); k = the smallest index that maximises m10 * C_k + m01 * S_k, in 64 bits; a flat
+ *     patch gives k = 0.  Without the option k = 0.
+ *   Descriptor: bit t % 64 of word t / 64 is 1 iff P(corner + rot_k(a_t)) < P(corner + rot_k(b_t)).  desc is
+ *     [n][corners_max][4] unsigned long long, meta [n][corners_max] int = k + 256 * border, border = 1 iff the 31 x 31 patch
+ *     leaves the frame.  Slots past counts[f] are not written.
+ *   Matching: a query set and a train set, each descriptor words ([frames][stride][4]), per-frame counts and a slot stride,
+ *     0 <= counts <= stride (a count outside is clamped into that range), 1 <= stride <= CANNY_HIP_HOUGH_MAX_LINES; the two
+ *     sets may be the same buffers.  n_pairs pairs (q frame, t frame), 2 ints each, as a HOST array: the call copies it,
+ *     so the frame indices are validated before anything is queued.  For query i of a pair: d(i, j) = the popcount of the
+ *     XOR of the four words; the best neighbour is the j with the smallest (d, j), d1 its distance; d2 the smallest
+ *     distance among j != best (it may equal d1; 257 if there is none); an empty train set gives j = -1, d1 = d2 = 257.
+ *   Flags: bit 0: d1 <= max_distance (0..256).  bit 1: ratio_q8 == 0 or d1 * 256 < ratio_q8 * d2 (ratio_q8 0..256; 205 is
+ *     Lowe's 0.8).  bit 2, mutual: i is the query with the smallest (d(i', j), i') for its best j; always computed.
+ *     bit 3, accepted: bits 0 and 1, and bit 2 if option CANNY_HIP_MATCH_CROSS_CHECK is set.
+ *   Output: matches is [n_pairs][stride_q][CANNY_HIP_MATCH_WORDS = 4] int: j, d1, d2, flags; slots past the query count are
+ *     not written.  pair_counts[p] = the number accepted.
+ *   Statuses: bad ranges, NULL mandatory pointers, descriptor or record buffers that are not 8-byte aligned, pair indices
+ *     outside the sets: CANNY_HIP_ERR_INVALID; over a documented limit (corners_max or a stride >
+ *     CANNY_HIP_HOUGH_MAX_LINES, height * width >= 2^31, more than 65535 frames, more than 2^20 pairs):
+ *     CANNY_HIP_ERR_UNSUPPORTED; both before anything is queued, nothing is written.
+ * Memory: the matcher's workspace holds the pairs and one int per (pair, train slot).
+ * The four parts are timed by canny_hip_descriptors_profile_get (CANNY_HIP_DESC_PART_*); with "profile_stage_mask" they go
+ *   by bit 30 like every part behind the polygons.
+ * Not covered -- follow-ups: scale pyramids; sub-pixel corner refinement; geometric verification (RANSAC) of the matches;
+ * matching through the batch pipeline or the multi-GPU sharder. */
+#define CANNY_HIP_DESC_BITS 256
+#define CANNY_HIP_DESC_WORDS 4
+#define CANNY_HIP_DESC_RADIUS 15
+#define CANNY_HIP_DESC_ROTATIONS 32
+#define CANNY_HIP_MATCH_WORDS 4
+#define CANNY_HIP_MATCH_MAX_PAIRS 1048576
+enum canny_hip_desc_option { CANNY_HIP_DESC_STEERED = 1 };
+enum canny_hip_match_option { CANNY_HIP_MATCH_CROSS_CHECK = 1 };
+enum canny_hip_desc_part {
+    CANNY_HIP_DESC_PART_DESCRIBE = 0, /* patch, orientation, 256 tests: one wave per corner */
+    CANNY_HIP_DESC_PART_MATCH = 1,    /* best and second-best train descriptor of every query */
+    CANNY_HIP_DESC_PART_REVERSE = 2,  /* best query of every train descriptor */
+    CANNY_HIP_DESC_PART_FINALIZE = 3, /* flags and accepted counts */
+    CANNY_HIP_DESC_PARTS = 4
+};
+/* canny_hip_dev_canny_corners unchanged (d_edges and the corner outputs exactly as there), then the descriptors of the
+ * corners on the smoothed plane, on the same stream.  d_desc: n_frames * corners_max * 4 unsigned long long; d_meta:
+ * n_frames * corners_max int; both mandatory.  Asynchronous. */
+int canny_hip_dev_canny_corner_descriptors(canny_hip_ctx *ctx, const unsigned char *d_img, float sigma, int min_val,
+                                           int max_val, int height, int width, int n_frames, short *d_edges, int mode,
+                                           int block, int k_q8, int quality_q16, long long min_response, int min_dist,
+                                           int corners_max, long long *d_corners, int *d_counts, int *d_cand_counts,
+                                           long long *d_max_response, long long *d_response, int desc_options,
+                                           unsigned long long *d_desc, int *d_meta);
+/* The descriptors of device records and counts on a caller's device u8 plane ([n][height][width] bytes).  With
+ * d_plane == NULL: on the plane the context's last canny call left, under the rule of canny_hip_dev_edgels_at -- a context
+ * that ran no such call, or a call for another shape, gives CANNY_HIP_ERR_INVALID with nothing queued.  Asynchronous. */
+int canny_hip_dev_corner_descriptors(canny_hip_ctx *ctx, const unsigned char *d_plane, int n_frames, int height, int width,
+                                     const long long *d_corners, const int *d_counts, int corners_max, int desc_options,
+                                     unsigned long long *d_desc, int *d_meta);
+/* Host buffers, synchronous: the counts come down first, then only the filled slots of corners, desc and meta. */
+int canny_hip_canny_corner_descriptors(canny_hip_ctx *ctx, const unsigned char *imgs, int n_frames, float sigma,
+                                       int min_val, int max_val, int height, int width, int mode, int block, int k_q8,
+                                       int quality_q16, long long min_response, int min_dist, int corners_max,
+                                       int desc_options, long long *corners, int *counts, unsigned long long *desc,
+                                       int *meta);
+/* Host-only, needs no device: the descriptor rule for `count` records (4 long long each) on ONE host u8 plane, in plain
+ * C++.  desc receives count * 4 words, meta count ints.  0 <= count <= CANNY_HIP_HOUGH_MAX_LINES. */
+int canny_hip_corner_descriptors_from_plane(const unsigned char *plane, int height, int width, const long long *corners,
+                                            int count, int options, unsigned long long *desc, int *meta);
+/* Host-only: the 256 x 4 signed bytes (ax, ay, bx, by) of rotation k, 0 <= k < 32. */
+int canny_hip_descriptor_pattern(int k, signed char *out);
+/* The matcher.  pairs is a HOST array of 2 * n_pairs ints (q frame, t frame), 0 <= q frame < n_q_frames, 0 <= t frame <
+ * n_t_frames; every other pointer is a device pointer.  d_matches: n_pairs * stride_q * 4 ints; d_pair_counts: n_pairs
+ * ints.  Asynchronous. */
+int canny_hip_dev_match_descriptors(canny_hip_ctx *ctx, const unsigned long long *d_q_desc, const int *d_q_counts,
+                                    int n_q_frames, int stride_q, const unsigned long long *d_t_desc, const int *d_t_counts,
+                                    int n_t_frames, int stride_t, const int *pairs, int n_pairs, int max_distance,
+                                    int ratio_q8, int options, int *d_matches, int *d_pair_counts);
+/* Host-only, needs no device: the matching rule on ONE pair of host descriptor sets (n_q, n_t descriptors of 4 words).
+ * matches receives n_q * 4 ints, *accepted the number accepted. */
+int canny_hip_match_descriptors(const unsigned long long *q_desc, int n_q, const unsigned long long *t_desc, int n_t,
+                                int max_distance, int ratio_q8, int options, int *matches, int *accepted);
+
 /* ---- per-stage HIP-event timing (events are recorded on the launch stream) ----------------- */
 int canny_hip_profile_enable(canny_hip_ctx *ctx, int on);
 int canny_hip_profile_reset(canny_hip_ctx *ctx);
@@ -1847,6 +1953,8 @@ int canny_hip_shapes_profile_get(canny_hip_ctx *ctx, int part, double *total_ms,
 int canny_hip_curves_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches);
 /* ... and for the four parts of the corners (CANNY_HIP_CORNER_PART_*). */
 int canny_hip_corners_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches);
+/* ... and for the four parts of the descriptors and their matching (CANNY_HIP_DESC_PART_*). */
+int canny_hip_descriptors_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches);
 
 /* ---- self-test hooks used by the GPU test-suite -------------------------------------------- */
 /* Runs the DEVICE magnitude / angle-bin functions over every (gx,gy) in [-lim,lim]^2 and writes
@@ -1999,6 +2107,15 @@ int canny_hip_selftest_curves_plan(int n_frames, int height, int width, unsigned
 enum canny_hip_corners_plan { CANNY_HIP_CORNERS_PLAN_TILES = 0, CANNY_HIP_CORNERS_PLAN_ARITH = 1 };
 int canny_hip_selftest_corners_plan(int which, int n_frames, int height, int width, unsigned long long n,
                                     unsigned long long *out);
+/* Host-only, the same five outputs for the capped launches of the descriptors and their matching (no kind above):
+ *   CANNY_HIP_DESCRIPTORS_PLAN_DESCRIBE: items = the n * stride record slots (n frames, stride = corners_max), one wave
+ *     per slot, 4 per workgroup and trip, at most 2048 workgroups;
+ *   CANNY_HIP_DESCRIPTORS_PLAN_MATCH: the match and the reverse launch, items = n * ceil(stride / 256) (n pairs, stride
+ *     that of the side held in registers: the query's for the match, the train's for the reverse), one per workgroup and
+ *     trip, at most 2048 workgroups.
+ * 1 <= stride <= CANNY_HIP_HOUGH_MAX_LINES, n >= 1 and within the calls' limits.  out holds 5 words. */
+enum canny_hip_descriptors_plan { CANNY_HIP_DESCRIPTORS_PLAN_DESCRIBE = 0, CANNY_HIP_DESCRIPTORS_PLAN_MATCH = 1 };
+int canny_hip_selftest_descriptors_plan(int which, unsigned long long n, int stride, unsigned long long *out);
 
 #ifdef __cplusplus
 }
