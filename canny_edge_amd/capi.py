@@ -138,6 +138,8 @@ EXPORTS = (
     "canny_hip_dev_canny_corner_descriptors", "canny_hip_dev_corner_descriptors", "canny_hip_canny_corner_descriptors",
     "canny_hip_corner_descriptors_from_plane", "canny_hip_descriptor_pattern", "canny_hip_dev_match_descriptors",
     "canny_hip_match_descriptors", "canny_hip_descriptors_profile_get", "canny_hip_selftest_descriptors_plan",
+    "canny_hip_dev_estimate_motion", "canny_hip_estimate_motion", "canny_hip_canny_motion", "canny_hip_motion_profile_get",
+    "canny_hip_selftest_motion_plan",
 )
 
 _lib: Optional[C.CDLL] = None
@@ -366,6 +368,12 @@ def load() -> C.CDLL:
         "canny_hip_match_descriptors": ([p, i, p, i, i, i, i, p, ip], i),
         "canny_hip_descriptors_profile_get": ([p, i, C.POINTER(C.c_double), C.POINTER(C.c_long)], i),
         "canny_hip_selftest_descriptors_plan": ([i, ull, i, p], i),
+        "canny_hip_dev_estimate_motion": ([p, p, p, i, i, p, p, i, i, p, i, p, i, i, i, C.c_uint, p, p], i),
+        "canny_hip_estimate_motion": ([p, i, p, i, p, i, i, i, C.c_uint, p, p], i),
+        "canny_hip_canny_motion": ([p, p, i, f, i, i, i, i, i, i, i, i, C.c_longlong, i, i, i, p, i, i, i, i, i, i, i,
+                                    C.c_uint, p, p, p, p, p], i),
+        "canny_hip_motion_profile_get": ([p, i, C.POINTER(C.c_double), C.POINTER(C.c_long)], i),
+        "canny_hip_selftest_motion_plan": ([i, ull, i, p], i),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -1072,6 +1080,51 @@ def descriptors_plan(which, n: int, stride: int):
     st = load().canny_hip_selftest_descriptors_plan(k, int(n), int(stride), _hp(out))
     if st:
         raise CannyHipError(st, "selftest_descriptors_plan")
+    return LaunchPlan(*(int(v) for v in out))
+
+
+# ---- frame-to-frame motion from the corner matches -------------------------------------------------
+MOTION_TRANSLATION, MOTION_SIMILARITY, MOTION_AFFINE = 0, 1, 2
+MOTION_WORDS, MOTION_MAX_HYPOTHESES = 16, 4096
+MOTION_HAS_MODEL, MOTION_HAS_REFIT = 1, 2
+MOTION_PARTS = ("gather", "score", "refit")
+MOTION_PLANS = ("gather", "score", "refit")
+MOTION_DTYPE = np.dtype([("flags", np.int64), ("m", np.int64), ("inliers", np.int64), ("h", np.int64), ("a11", np.int64),
+                         ("a12", np.int64), ("tx", np.int64), ("a21", np.int64), ("a22", np.int64), ("ty", np.int64),
+                         ("residual_sum", np.int64), ("residual_max", np.int64), ("i1", np.int64), ("i2", np.int64),
+                         ("i3", np.int64), ("d", np.int64)])
+
+
+def estimate_motion(q_corners, t_corners, matches, model: int = MOTION_SIMILARITY, thr_q4: int = 48, hypotheses: int = 256,
+                    seed: int = 0):
+    """Host-only, needs no GPU: the motion rule on ONE pair: records int64 [n_q, 4] and [n_t, 4] (x, y, response, rank; or
+    [k, 2]: x, y), the matcher's row int32 [n_q, 4] -> (int64 [16] record, int32 [n_q] inlier flags: 1, 0, -1)."""
+    def records(c):
+        rec = np.zeros((len(c), CORNER_WORDS), np.int64)
+        if len(c):
+            c = np.asarray(c, np.int64).reshape(len(c), -1)
+            rec[:, :min(c.shape[1], CORNER_WORDS)] = c[:, :CORNER_WORDS]
+        return rec
+    q, t = records(q_corners), records(t_corners)
+    mt = np.ascontiguousarray(matches, np.int32).reshape(-1, MATCH_WORDS)
+    if len(mt) != len(q):
+        raise ValueError("one match row per query record")
+    out, flags = np.zeros(MOTION_WORDS, np.int64), np.zeros(len(q), np.int32)
+    st = load().canny_hip_estimate_motion(_hp(q) if len(q) else None, len(q), _hp(t) if len(t) else None, len(t),
+                                          _hp(mt) if len(q) else None, int(model), int(thr_q4), int(hypotheses),
+                                          int(seed) & 0xFFFFFFFF, _hp(out), _hp(flags) if len(q) else None)
+    if st:
+        raise CannyHipError(st, "estimate_motion")
+    return out, flags
+
+
+def motion_plan(which, n_pairs: int, hypotheses: int = 1):
+    """Host-only: the LaunchPlan of a capped launch of the motion estimate: "gather", "score" or "refit"."""
+    k = MOTION_PLANS.index(which) if isinstance(which, str) else int(which)
+    out = np.zeros(5, np.uint64)
+    st = load().canny_hip_selftest_motion_plan(k, int(n_pairs), int(hypotheses), _hp(out))
+    if st:
+        raise CannyHipError(st, "selftest_motion_plan")
     return LaunchPlan(*(int(v) for v in out))
 
 
@@ -2450,6 +2503,61 @@ class Context:
         ms, n = C.c_double(0), C.c_long(0)
         self._check(self._L.canny_hip_descriptors_profile_get(self._h, part, C.byref(ms), C.byref(n)),
                     "descriptors_profile_get")
+        return ms.value, n.value
+
+    # ---- frame-to-frame motion from the corner matches ---------------------------------------
+    def dev_estimate_motion(self, d_q_corners: int, d_q_counts: int, n_q_frames: int, stride_q: int, d_t_corners: int,
+                            d_t_counts: int, n_t_frames: int, stride_t: int, pairs, d_matches: int, d_motion: int,
+                            d_inlier: int = 0, model: int = MOTION_SIMILARITY, thr_q4: int = 48, hypotheses: int = 256,
+                            seed: int = 0):
+        """Consensus over the accepted matches of the pairs (host int array [n_pairs, 2]: q frame, t frame) and one motion
+        model per pair: d_matches is the matcher's [n_pairs][stride_q][4] int32, d_motion receives [n_pairs][16] int64
+        (MOTION_DTYPE), d_inlier (optional) [n_pairs][stride_q] int32.  Asynchronous."""
+        v = C.c_void_p
+        pr = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+        self._check(self._L.canny_hip_dev_estimate_motion(self._h, v(d_q_corners or None), v(d_q_counts or None), n_q_frames,
+                                                          stride_q, v(d_t_corners or None), v(d_t_counts or None),
+                                                          n_t_frames, stride_t, _hp(pr) if len(pr) else None, len(pr),
+                                                          v(d_matches or None), model, thr_q4, hypotheses,
+                                                          int(seed) & 0xFFFFFFFF, v(d_motion or None), v(d_inlier or None)),
+                    "dev_estimate_motion")
+
+    def canny_motion(self, imgs, sigma: float, min_val: int, max_val: int, pairs=None, mode: int = CORNERS_MIN_EIGEN,
+                     block: int = 3, k_q8: int = 0, quality_q16: int = 655, min_response: int = 0, min_dist: int = 0,
+                     corners_max: int = 256, steered: bool = False, max_distance: int = 64, ratio_q8: int = 205,
+                     match_options: int = MATCH_CROSS_CHECK, model: int = MOTION_SIMILARITY, thr_q4: int = 48,
+                     hypotheses: int = 256, seed: int = 0, details: bool = False):
+        """canny(), corners, descriptors, matching over `pairs` (default: consecutive frames) and the motion of every pair,
+        all on the GPU: imgs (N, H, W) uint8 -> the records as MOTION_DTYPE [n_pairs]; with details also (corners per frame
+        as CORNER_DTYPE, matches per pair int32 [k, 4], inlier flags per pair int32 [k])."""
+        a = np.ascontiguousarray(imgs, dtype=np.uint8)
+        if a.ndim != 3:
+            raise ValueError("expected uint8 [n_frames, H, W]")
+        n, h, w = a.shape
+        pr = np.ascontiguousarray(consecutive_pairs(n) if pairs is None else pairs, dtype=np.int32).reshape(-1, 2)
+        cm = max(int(corners_max), 1)
+        motion = np.zeros((len(pr), MOTION_WORDS), np.int64)
+        rec, counts = np.zeros((n, cm, CORNER_WORDS), np.int64), np.zeros(n, np.int32)
+        mt, flags = np.zeros((len(pr), cm, MATCH_WORDS), np.int32), np.zeros((len(pr), cm), np.int32)
+        self._check(self._L.canny_hip_canny_motion(self._h, _hp(a), n, sigma, min_val, max_val, h, w, mode, block, k_q8,
+                                                   quality_q16, min_response, min_dist, corners_max,
+                                                   DESC_STEERED if steered else 0, _hp(pr) if len(pr) else None, len(pr),
+                                                   max_distance, ratio_q8, match_options, model, thr_q4, hypotheses,
+                                                   int(seed) & 0xFFFFFFFF, _hp(motion) if len(pr) else None,
+                                                   _hp(rec) if details else None, _hp(counts) if details else None,
+                                                   _hp(mt) if details else None, _hp(flags) if details else None),
+                    "canny_motion")
+        records = motion.view(MOTION_DTYPE).reshape(-1)
+        if not details:
+            return records
+        k = [int(counts[q]) for q, _ in pr.tolist()]
+        return (records, [np.ascontiguousarray(rec[f, :int(counts[f])]).view(CORNER_DTYPE).reshape(-1) for f in range(n)],
+                [mt[p, :k[p]].copy() for p in range(len(pr))], [flags[p, :k[p]].copy() for p in range(len(pr))])
+
+    def motion_profile_get(self, part: int) -> Tuple[float, int]:
+        """(total ms, launch groups) of part 0 gather, 1 score, 2 refit (MOTION_PARTS)."""
+        ms, n = C.c_double(0), C.c_long(0)
+        self._check(self._L.canny_hip_motion_profile_get(self._h, part, C.byref(ms), C.byref(n)), "motion_profile_get")
         return ms.value, n.value
 
     # ---- sub-pixel circle fits (least-squares refit of the Hough circles from edgels; DESIGN.md section 25) ------

@@ -419,6 +419,9 @@ struct canny_hip_ctx {
     // descriptor matching: the pairs as the kernels read them, then per (pair, train slot) its best query
     DevBuf desc_ws;
     std::vector<int> desc_pairs; // the validated pairs of the last match call: what its upload reads
+    // motion estimate: the compacted correspondences and their slots, the inlier counts per (pair, hypothesis), m, the pairs
+    DevBuf motion_ws;
+    std::vector<int> motion_pairs; // the validated pairs of the last motion call: what its upload reads
     DevBuf plane_s, plane_c, stamps, flags; // hysteresis bit-planes / scheduling words
     DevBuf io[4];     // staging for the host-pointer stage functions
     std::string ws_name; // canny_hip_selftest_workspace: the name it handed out last
@@ -451,7 +454,7 @@ struct canny_hip_ctx {
     // circle fits (canny_hip_circle_fits_profile_get), then the four of the chamfer matching
     // (canny_hip_chamfer_profile_get), then the three of the contour shape measures (canny_hip_shapes_profile_get), then the two of the edge curves
     // (canny_hip_curves_profile_get), then the four of the corners (canny_hip_corners_profile_get), then the four of the descriptors and their matching
-    // (canny_hip_descriptors_profile_get).  The mask is a non-negative int option: bit 30 is the last it can
+    // (canny_hip_descriptors_profile_get), then the three of the motion estimate (canny_hip_motion_profile_get).  The mask is a non-negative int option: bit 30 is the last it can
     // carry, and the three polygon slots, the two edgel slots, the line-fit slot and the circle-fit slot behind them go by
     // it together
     static constexpr int kProfHough = CANNY_HIP_STAGE_END, kProfComponents = CANNY_HIP_STAGE_END + 3;
@@ -468,7 +471,8 @@ struct canny_hip_ctx {
     static constexpr int kProfCurves = kProfShapes + CANNY_HIP_SHAPE_PARTS;
     static constexpr int kProfCorners = kProfCurves + CANNY_HIP_CURVE_PARTS;
     static constexpr int kProfDescriptors = kProfCorners + CANNY_HIP_CORNER_PARTS;
-    static constexpr int kProfSlots = kProfDescriptors + CANNY_HIP_DESC_PARTS;
+    static constexpr int kProfMotion = kProfDescriptors + CANNY_HIP_DESC_PARTS;
+    static constexpr int kProfSlots = kProfMotion + CANNY_HIP_MOTION_PARTS;
     static constexpr int kProfLastBit = 30;
     static_assert(kProfPolygons == kProfLastBit && kProfEdgels > kProfLastBit,
                   "profile_stage_mask has one bit per slot up to the polygon parts; every slot from there on follows bit 30");
@@ -2006,6 +2010,7 @@ void collect_workspaces(const canny_hip_ctx *c, const std::string &prefix, std::
     add("chamfer_dist2", c->chamfer_dist2, I); // doubles as the column scan's stack (see edt_stack)
     add("corners_ws", c->corners_ws, I);   // keys address pixels, totals bound the sort, counters hand out slots
     add("desc_ws", c->desc_ws, I);         // the pairs address frames, the best queries are compared with indices
+    add("motion_ws", c->motion_ws, I);     // the pairs address frames, m bounds the lists, the slots address the flags
     add("plane_s", c->plane_s, D);
     add("plane_c", c->plane_c, D);
     add("stamps", c->stamps, I);           // tile queues and their counters
@@ -2122,6 +2127,7 @@ void canny_hip_ctx_destroy(canny_hip_ctx *ctx)
     ctx->chamfer_dist2.release();
     ctx->corners_ws.release();
     ctx->desc_ws.release();
+    ctx->motion_ws.release();
     ctx->cc_parent.release();
     ctx->cc_ws.release();
     ctx->ct_ws.release();
@@ -6191,6 +6197,156 @@ int canny_hip_selftest_descriptors_plan(int which, unsigned long long n, int str
     } else {
         return CANNY_HIP_ERR_INVALID;
     }
+    out[0] = p.units, out[1] = p.per_group, out[2] = p.grid, out[3] = p.trips(), out[4] = (unsigned long long)p.aux;
+    return CANNY_HIP_OK;
+}
+
+// ---- frame-to-frame motion from the corner matches (canny_motion.hip) -----------------------------
+// canny_hip_estimate_motion, the rule in plain C++, lives in canny_motion_host.cpp.
+
+int canny_hip_dev_estimate_motion(canny_hip_ctx *ctx, const long long *d_q_corners, const int *d_q_counts, int n_q_frames,
+                                  int stride_q, const long long *d_t_corners, const int *d_t_counts, int n_t_frames,
+                                  int stride_t, const int *pairs, int n_pairs, const int *d_matches, int model, int thr_q4,
+                                  int hypotheses, unsigned seed, long long *d_motion, int *d_inlier)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!d_q_corners || !d_q_counts || !d_t_corners || !d_t_counts || !pairs || !d_matches || !d_motion || n_q_frames < 1 ||
+        n_t_frames < 1 || stride_q < 1 || stride_t < 1 || n_pairs < 1 || model < CANNY_HIP_MOTION_TRANSLATION ||
+        model > CANNY_HIP_MOTION_AFFINE || thr_q4 < 0 || thr_q4 > 4095 || hypotheses < 1 || ((uintptr_t)d_q_corners & 7) ||
+        ((uintptr_t)d_t_corners & 7) || ((uintptr_t)d_motion & 7))
+        return CANNY_HIP_ERR_INVALID;
+    if (stride_q > kHoughMaxLines || stride_t > kHoughMaxLines || n_q_frames > 65535 || n_t_frames > 65535 ||
+        n_pairs > CANNY_HIP_MATCH_MAX_PAIRS || hypotheses > CANNY_HIP_MOTION_MAX_HYPOTHESES)
+        return CANNY_HIP_ERR_UNSUPPORTED;
+    for (int p = 0; p < n_pairs; p++)
+        if (pairs[2 * p] < 0 || pairs[2 * p] >= n_q_frames || pairs[2 * p + 1] < 0 || pairs[2 * p + 1] >= n_t_frames)
+            return CANNY_HIP_ERR_INVALID;
+    if ((rc = finish_pending(ctx))) return rc;
+    HIP_TRY(ctx, ctx->motion_ws.ensure(motion_workspace(nullptr, n_pairs, stride_q, hypotheses).bytes));
+    const MotionWs w = motion_workspace(ctx->motion_ws.p, n_pairs, stride_q, hypotheses);
+    ctx->motion_pairs.assign(pairs, pairs + 2 * (size_t)n_pairs);
+    HIP_TRY(ctx, hipMemcpyAsync(w.pairs, ctx->motion_pairs.data(), 2 * (size_t)n_pairs * sizeof(int), hipMemcpyHostToDevice,
+                                ctx->stream));
+    const int part = canny_hip_ctx::kProfMotion;
+    {
+        StageTimer tm(ctx, part + CANNY_HIP_MOTION_PART_GATHER);
+        HIP_TRY(ctx, launch_motion_gather(d_q_corners, d_q_counts, stride_q, d_t_corners, d_t_counts, stride_t, n_pairs,
+                                          d_matches, w, d_inlier, ctx->stream));
+    }
+    {
+        StageTimer tm(ctx, part + CANNY_HIP_MOTION_PART_SCORE);
+        HIP_TRY(ctx, launch_motion_score(stride_q, n_pairs, model, thr_q4, hypotheses, seed, w, ctx->stream));
+    }
+    {
+        StageTimer tm(ctx, part + CANNY_HIP_MOTION_PART_REFIT);
+        HIP_TRY(ctx, launch_motion_refit(stride_q, n_pairs, model, thr_q4, hypotheses, seed, w, d_motion, d_inlier,
+                                         ctx->stream));
+    }
+    return CANNY_HIP_OK;
+}
+
+int canny_hip_canny_motion(canny_hip_ctx *ctx, const unsigned char *imgs, int n_frames, float sigma, int min_val,
+                           int max_val, int height, int width, int mode, int block, int k_q8, int quality_q16,
+                           long long min_response, int min_dist, int corners_max, int desc_options, const int *pairs,
+                           int n_pairs, int max_distance, int ratio_q8, int match_options, int model, int thr_q4,
+                           int hypotheses, unsigned seed, long long *motion, long long *corners, int *counts, int *matches,
+                           int *inlier)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    // every check of the chained calls, before anything is uploaded or queued
+    if (!imgs || !pairs || !motion || n_pairs < 1 || (corners == nullptr) != (counts == nullptr) || max_distance < 0 ||
+        max_distance > CANNY_HIP_DESC_BITS || ratio_q8 < 0 || ratio_q8 > 256 || (match_options & ~CANNY_HIP_MATCH_CROSS_CHECK) ||
+        model < CANNY_HIP_MOTION_TRANSLATION || model > CANNY_HIP_MOTION_AFFINE || thr_q4 < 0 || thr_q4 > 4095 ||
+        hypotheses < 1 || ((uintptr_t)motion & 7) || ((uintptr_t)corners & 7))
+        return CANNY_HIP_ERR_INVALID;
+    // the descriptor check wants its four pointers: the outputs that stay on the device stand in
+    if ((rc = descriptors_check(height, width, n_frames, corners_max, desc_options, motion, motion, motion, motion))) return rc;
+    const CornerArgs a{mode, block, k_q8, quality_q16, min_response, min_dist, corners_max};
+    long long *probe_rec = motion;
+    int *probe_cnt = (int *)motion;
+    if ((rc = corners_check(height, width, n_frames, a, CornerOut{probe_rec, probe_cnt, nullptr, nullptr, nullptr}))) return rc;
+    if (n_pairs > CANNY_HIP_MATCH_MAX_PAIRS || hypotheses > CANNY_HIP_MOTION_MAX_HYPOTHESES) return CANNY_HIP_ERR_UNSUPPORTED;
+    for (int p = 0; p < n_pairs; p++)
+        if (pairs[2 * p] < 0 || pairs[2 * p] >= n_frames || pairs[2 * p + 1] < 0 || pairs[2 * p + 1] >= n_frames)
+            return CANNY_HIP_ERR_INVALID;
+    const size_t slots = (size_t)n_frames * corners_max, pslots = (size_t)n_pairs * corners_max;
+    // one staging block: records | descriptors | motion records | meta | counts | matches | pair counts | inlier flags
+    HIP_TRY(ctx, ctx->io[1].ensure(slots * (CANNY_HIP_CORNER_WORDS * sizeof(long long) +
+                                            CANNY_HIP_DESC_WORDS * sizeof(unsigned long long) + sizeof(int)) +
+                                   (size_t)n_pairs * CANNY_HIP_MOTION_WORDS * sizeof(long long) +
+                                   (size_t)n_frames * sizeof(int) + pslots * (CANNY_HIP_MATCH_WORDS + 1) * sizeof(int) +
+                                   (size_t)n_pairs * sizeof(int)));
+    long long *d_rec = (long long *)ctx->io[1].p;
+    unsigned long long *d_desc = (unsigned long long *)(d_rec + slots * CANNY_HIP_CORNER_WORDS);
+    long long *d_motion = (long long *)(d_desc + slots * CANNY_HIP_DESC_WORDS);
+    int *d_meta = (int *)(d_motion + (size_t)n_pairs * CANNY_HIP_MOTION_WORDS), *d_cnt = d_meta + slots;
+    int *d_matches = d_cnt + n_frames, *d_pc = d_matches + pslots * CANNY_HIP_MATCH_WORDS, *d_in = d_pc + n_pairs;
+    if ((rc = h2d(ctx, ctx->io[0], imgs, npx(height, width, n_frames)))) return rc;
+    if ((rc = canny_hip_dev_canny_corner_descriptors(ctx, (const unsigned char *)ctx->io[0].p, sigma, min_val, max_val,
+                                                     height, width, n_frames, nullptr, mode, block, k_q8, quality_q16,
+                                                     min_response, min_dist, corners_max, d_rec, d_cnt, nullptr, nullptr,
+                                                     nullptr, desc_options, d_desc, d_meta)))
+        return rc;
+    if ((rc = canny_hip_dev_match_descriptors(ctx, d_desc, d_cnt, n_frames, corners_max, d_desc, d_cnt, n_frames,
+                                              corners_max, pairs, n_pairs, max_distance, ratio_q8, match_options, d_matches,
+                                              d_pc)))
+        return rc;
+    if ((rc = canny_hip_dev_estimate_motion(ctx, d_rec, d_cnt, n_frames, corners_max, d_rec, d_cnt, n_frames, corners_max,
+                                            pairs, n_pairs, d_matches, model, thr_q4, hypotheses, seed, d_motion,
+                                            inlier ? d_in : nullptr)))
+        return rc;
+    std::vector<int> cnt((size_t)n_frames);
+    if ((rc = d2h_sync(ctx, cnt.data(), d_cnt, cnt.size() * sizeof(int)))) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(motion, d_motion, (size_t)n_pairs * CANNY_HIP_MOTION_WORDS * sizeof(long long),
+                                hipMemcpyDeviceToHost, ctx->stream));
+    if (corners)
+        for (int f = 0; f < n_frames; f++) { // only the filled slots of each frame come down
+            const size_t k = (size_t)cnt[f], at = (size_t)f * corners_max;
+            if (k)
+                HIP_TRY(ctx, hipMemcpyAsync(corners + at * CANNY_HIP_CORNER_WORDS, d_rec + at * CANNY_HIP_CORNER_WORDS,
+                                            k * CANNY_HIP_CORNER_WORDS * sizeof(long long), hipMemcpyDeviceToHost,
+                                            ctx->stream));
+        }
+    for (int p = 0; p < n_pairs; p++) { // of every pair the slots below the query's count
+        const size_t k = (size_t)cnt[pairs[2 * p]], at = (size_t)p * corners_max;
+        if (!k) continue;
+        if (matches)
+            HIP_TRY(ctx, hipMemcpyAsync(matches + at * CANNY_HIP_MATCH_WORDS, d_matches + at * CANNY_HIP_MATCH_WORDS,
+                                        k * CANNY_HIP_MATCH_WORDS * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+        if (inlier)
+            HIP_TRY(ctx, hipMemcpyAsync(inlier + at, d_in + at, k * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (counts) std::memcpy(counts, cnt.data(), (size_t)n_frames * sizeof(int));
+    return CANNY_HIP_OK;
+}
+
+int canny_hip_motion_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches)
+{
+    if (part < 0 || part >= CANNY_HIP_MOTION_PARTS || !total_ms || !launches) return CANNY_HIP_ERR_INVALID;
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if ((rc = profile_collect(ctx))) return rc;
+    *total_ms = ctx->total_ms[canny_hip_ctx::kProfMotion + part];
+    *launches = ctx->launches[canny_hip_ctx::kProfMotion + part];
+    return CANNY_HIP_OK;
+}
+
+// Host-only: the launch plans of the capped launches of the motion estimate.
+int canny_hip_selftest_motion_plan(int which, unsigned long long n_pairs, int hypotheses, unsigned long long *out)
+{
+    if (!out || !n_pairs || n_pairs > CANNY_HIP_MATCH_MAX_PAIRS || hypotheses < 1 ||
+        hypotheses > CANNY_HIP_MOTION_MAX_HYPOTHESES)
+        return CANNY_HIP_ERR_INVALID;
+    LaunchPlan p;
+    if (which == CANNY_HIP_MOTION_PLAN_GATHER || which == CANNY_HIP_MOTION_PLAN_REFIT)
+        p = plan_motion_pairs(n_pairs);
+    else if (which == CANNY_HIP_MOTION_PLAN_SCORE)
+        p = plan_motion_score(n_pairs, hypotheses);
+    else
+        return CANNY_HIP_ERR_INVALID;
     out[0] = p.units, out[1] = p.per_group, out[2] = p.grid, out[3] = p.trips(), out[4] = (unsigned long long)p.aux;
     return CANNY_HIP_OK;
 }

@@ -800,6 +800,31 @@ hipError_t launch_desc_finalize(const int *q_counts, int stride_q, int stride_t,
                                 const int *back, int max_distance, int ratio_q8, int cross, int *matches, int *pair_counts,
                                 hipStream_t stream);
 
+// ---- frame-to-frame motion from the corner matches (canny_motion.hip) --------------------
+// gather, refit: the pairs, one per workgroup and trip.  score: the (pair, block of 256 hypotheses) units, one per workgroup
+// and trip.  (Reported by canny_hip_selftest_motion_plan, not by a kind.)
+LaunchPlan plan_motion_pairs(unsigned long long n_pairs);
+LaunchPlan plan_motion_score(unsigned long long n_pairs, int hypotheses);
+// The workspace of one call, carved from `base` (8-byte aligned; a NULL base gives the size alone): per (pair, query slot) the
+// compacted correspondence (four u16) and its slot, per (pair, hypothesis) its inlier count, per pair m, then the pairs
+// (device copy, 2 ints a pair: the caller uploads them before the gather).
+struct MotionWs {
+    void *list;
+    int *slot, *counts, *m, *pairs;
+    size_t bytes;
+};
+MotionWs motion_workspace(void *base, int n_pairs, int stride_q, int hypotheses);
+// The correspondences of every pair in query order, m, and (inlier != NULL) the -1 flags of the other slots below the count.
+hipError_t launch_motion_gather(const long long *q_corners, const int *q_counts, int stride_q, const long long *t_corners,
+                                const int *t_counts, int stride_t, int n_pairs, const int *matches, const MotionWs &w,
+                                int *inlier, hipStream_t stream);
+// The inlier count of every (pair, hypothesis); -1 where the hypothesis is invalid.
+hipError_t launch_motion_score(int stride_q, int n_pairs, int model, int thr_q4, int hypotheses, unsigned seed,
+                               const MotionWs &w, hipStream_t stream);
+// The best hypothesis, the flags of the correspondences, the refit and the 16-word record of every pair.
+hipError_t launch_motion_refit(int stride_q, int n_pairs, int model, int thr_q4, int hypotheses, unsigned seed,
+                               const MotionWs &w, long long *motion, int *inlier, hipStream_t stream);
+
 // ---- measurement aid ------------------------------------------------------------------------
 // Plain device copy of nbytes (multiple of 16; both pointers 16-byte aligned): what a 1:1 read/write stream reaches.
 hipError_t launch_probe_copy(const void *src, void *dst, size_t nbytes, hipStream_t stream, const LaunchEvents &ev = {});

@@ -52,7 +52,8 @@
 extern "C" {
 #endif
 
-#define CANNY_HIP_VERSION 2000       /* 0.20.0: + corner descriptors and Hamming matching between frames */
+#define CANNY_HIP_VERSION 2100       /* 0.21.0: + frame-to-frame motion from the corner matches (RANSAC) */
+/* 0.20.0: + corner descriptors and Hamming matching between frames */
 /* 0.19.0: + corners: Harris / Shi-Tomasi on the smoothed plane */
 /* 0.18.0: + edge curves: the edge map linked into ordered chains */
 /* 0.17.0: + contour shape measures: moments, convex hull, minimum-area rectangle */
@@ -1863,8 +1864,9 @@ int canny_hip_dev_corners_arith(canny_hip_ctx *ctx, const int *d_sums, size_t n,
  * Memory: the matcher's workspace holds the pairs and one int per (pair, train slot).
  * The four parts are timed by canny_hip_descriptors_profile_get (CANNY_HIP_DESC_PART_*); with "profile_stage_mask" they go
  *   by bit 30 like every part behind the polygons.
- * Not covered -- follow-ups: scale pyramids; sub-pixel corner refinement; geometric verification (RANSAC) of the matches;
- * matching through the batch pipeline or the multi-GPU sharder. */
+ * Geometric verification (RANSAC) of the matches: canny_hip_dev_estimate_motion below.
+ * Not covered -- follow-ups: scale pyramids; sub-pixel corner refinement; matching through the batch pipeline or the
+ * multi-GPU sharder. */
 #define CANNY_HIP_DESC_BITS 256
 #define CANNY_HIP_DESC_WORDS 4
 #define CANNY_HIP_DESC_RADIUS 15
@@ -1919,6 +1921,91 @@ int canny_hip_dev_match_descriptors(canny_hip_ctx *ctx, const unsigned long long
 int canny_hip_match_descriptors(const unsigned long long *q_desc, int n_q, const unsigned long long *t_desc, int n_t,
                                 int max_distance, int ratio_q8, int options, int *matches, int *accepted);
 
+/* ---- frame-to-frame motion from the corner matches (RANSAC) -------------------------------------------------------------------
+ * How did the camera move between these two frames?  The accepted matches of a pair of frames are verified by consensus and
+ * one motion model is fitted to the ones that agree -- what cv::estimateAffinePartial2D / cv::estimateAffine2D answer -- on
+ * the GPU, on the context's stream, no host round trip, no atomics.  All integers: the same bytes on every run and every
+ * machine.  tests/motion_rule.py restates the rule in numpy and plain Python ints, csrc/canny_motion_host.cpp in plain C++.
+ * THE RULE:
+ *   Inputs per pair p = (q frame, t frame): the corner records of both frames ([frames][stride][4] long long; only x and y
+ *     are read), the per-frame counts (clamped to [0, stride], as in the matcher), and the matcher's output row
+ *     [stride_q][4] int (j, d1, d2, flags).  1 <= stride <= CANNY_HIP_HOUGH_MAX_LINES = 4096.
+ *   Correspondences: the query slots i < count_q in ascending i; slot i is a correspondence iff flags & 8 (accepted),
+ *     0 <= j < count_t, and all four coordinates lie in [0, 65535].  It is c = (x, y, x', y'); m is their number.
+ *   Models: CANNY_HIP_MOTION_TRANSLATION = 0 (sample size k = 1), CANNY_HIP_MOTION_SIMILARITY = 1 (k = 2: rotation, uniform
+ *     scale, shift), CANNY_HIP_MOTION_AFFINE = 2 (k = 3).
+ *   Sampling: hypothesis h, 0 <= h < hypotheses, 1 <= hypotheses <= CANNY_HIP_MOTION_MAX_HYPOTHESES = 4096; it does not
+ *     depend on the pair's position in the call.  s = (seed + 0x9E3779B9 * (h + 1)) mod 2^32; draw(n):
+ *     s = (s * 1664525 + 1013904223) mod 2^32, the result is (s >> 16) % n.  i1 = draw(m); i2 = draw(m - 1), +1 if >= i1;
+ *     i3 = draw(m - 2), +1 if >= min(i1, i2), then +1 if >= max(i1, i2).  Only the first k indices are drawn.  m < k: no
+ *     model for this pair.
+ *   Hypothesis, exact integers; q1, q1' the first sample.  TRANSLATION: D = 1, M = I.  SIMILARITY, d = q2 - q1,
+ *     d' = q2' - q1': D = dx^2 + dy^2, A = dx dx' + dy dy', B = dx dy' - dy dx', M = [[A, -B], [B, A]].  AFFINE, e = q2 - q1,
+ *     f = q3 - q1, e', f' likewise: D = ex fy - ey fx, M11 = e'x fy - f'x ey, M12 = f'x ex - e'x fx, M21 = e'y fy - f'y ey,
+ *     M22 = f'y ex - e'y fx.  D == 0 makes the hypothesis invalid.
+ *   Inlier test: r = D (c' - q1') - M (c - q1); c is an inlier iff 256 (rx^2 + ry^2) <= thr_q4^2 D^2; thr_q4 in 1/16 px,
+ *     0 <= thr_q4 <= 4095.  |D| <= 2^33, |M| <= 2^34, |r| < 2^53: both sides fit unsigned 128 bits, the comparison is exact.
+ *   Best hypothesis: the valid h with the most inliers, ties to the smallest h.  None: the "model" bit is clear and the
+ *     inlier flags of all correspondences are 0.
+ *   Refit over the n inliers of the best hypothesis: 64-bit sums Sx, Sy, Sx', Sy', Sxx, Sxy, Syy, Sxx', Sxy', Syx', Syy';
+ *     C(ab) = n Sab - Sa Sb, |C| <= n^2 2^30 <= 2^54; fl = floor toward -inf.  TRANSLATION: a = [[65536, 0], [0, 65536]].
+ *     SIMILARITY: Dn = Cxx + Cyy, a11 = a22 = fl(65536 (Cxx' + Cyy') / Dn), a21 = fl(65536 (Cxy' - Cyx') / Dn),
+ *     a12 = -a21.  AFFINE: det = Cxx Cyy - Cxy^2, a11 = fl(65536 (Cxx' Cyy - Cyx' Cxy) / det),
+ *     a12 = fl(65536 (Cyx' Cxx - Cxx' Cxy) / det), a21, a22 the same with y' for x'.  Every numerator times 65536 stays under
+ *     2^126.  Dn or det <= 0, or any |a_ij| > 2^24: the "refit" bit is clear and words 4..11 are zero.  Then
+ *     tx = fl((65536 Sx' - a11 Sx - a12 Sy) / n), ty likewise.  Residual per inlier: ex = 65536 x' - (a11 x + a12 y + tx),
+ *     gx = ex >> 8 (arithmetic), clamped to +-2^24, gy likewise; word 10 is the sum of gx^2 + gy^2, word 11 its maximum.
+ *   Record, CANNY_HIP_MOTION_WORDS = 16 long long per pair: 0 flags (bit 0 model, bit 1 refit); 1 m; 2 inliers; 3 best h
+ *     (-1 if none); 4..9 a11, a12, tx, a21, a22, ty (Q16, query -> train); 10, 11 the residual words; 12..14 i1, i2, i3 as
+ *     slot indices i of the query (-1 unused); 15 D.  Every pair writes all 16 words.
+ *   Inlier flags: [n_pairs][stride_q] int: 1 an inlier of the best hypothesis, 0 a correspondence that is not, -1 a slot
+ *     that is no correspondence; slots past the query count are not written.
+ *   Statuses: bad ranges, NULL mandatory pointers, record buffers that are not 8-byte aligned, pair indices outside the
+ *     sets: CANNY_HIP_ERR_INVALID; over a documented limit (a stride > 4096, hypotheses > 4096, more than 65535 frames,
+ *     more than CANNY_HIP_MATCH_MAX_PAIRS pairs): CANNY_HIP_ERR_UNSUPPORTED; both before anything is queued, nothing is
+ *     written.
+ * Memory: the workspace holds the pairs, per (pair, query slot) 12 bytes and per (pair, hypothesis) one int.
+ * The three parts are timed by canny_hip_motion_profile_get (CANNY_HIP_MOTION_PART_*); with "profile_stage_mask" they go by
+ *   bit 30 like every part behind the polygons.
+ * Not covered -- follow-ups: homography (8 degrees of freedom need wider than 128-bit exact arithmetic or another rule);
+ * re-selecting the inliers after the refit (LO-RANSAC); a two-frame grammar of Main; motion through the batch pipeline or
+ * the multi-GPU sharder. */
+#define CANNY_HIP_MOTION_WORDS 16
+#define CANNY_HIP_MOTION_MAX_HYPOTHESES 4096
+enum canny_hip_motion_model {
+    CANNY_HIP_MOTION_TRANSLATION = 0,
+    CANNY_HIP_MOTION_SIMILARITY = 1,
+    CANNY_HIP_MOTION_AFFINE = 2
+};
+enum canny_hip_motion_part {
+    CANNY_HIP_MOTION_PART_GATHER = 0, /* the correspondences of every pair, compacted in query order */
+    CANNY_HIP_MOTION_PART_SCORE = 1,  /* the inlier count of every (pair, hypothesis) */
+    CANNY_HIP_MOTION_PART_REFIT = 2,  /* best hypothesis, inlier flags, refit, residuals, the record */
+    CANNY_HIP_MOTION_PARTS = 3
+};
+/* pairs is a HOST array of 2 * n_pairs ints (q frame, t frame); every other pointer is a device pointer.  d_matches:
+ * n_pairs * stride_q * 4 ints as the matcher wrote them; d_motion: n_pairs * 16 long long; d_inlier: n_pairs * stride_q
+ * ints, may be NULL.  The two sets may be the same buffers.  Asynchronous. */
+int canny_hip_dev_estimate_motion(canny_hip_ctx *ctx, const long long *d_q_corners, const int *d_q_counts, int n_q_frames,
+                                  int stride_q, const long long *d_t_corners, const int *d_t_counts, int n_t_frames,
+                                  int stride_t, const int *pairs, int n_pairs, const int *d_matches, int model, int thr_q4,
+                                  int hypotheses, unsigned seed, long long *d_motion, int *d_inlier);
+/* Host-only, needs no device: the rule on ONE pair of host record sets (n_q, n_t records of 4 long long; matches n_q * 4
+ * ints).  motion receives 16 words, inlier (may be NULL) n_q ints.  0 <= n_q, n_t <= 4096. */
+int canny_hip_estimate_motion(const long long *q_corners, int n_q, const long long *t_corners, int n_t, const int *matches,
+                              int model, int thr_q4, int hypotheses, unsigned seed, long long *motion, int *inlier);
+/* Host buffers, synchronous: canny, the corners, their descriptors, the matching over `pairs` (HOST, frames of this batch)
+ * and the motion of every pair, all on the device; only motion (n_pairs * 16 long long) comes down and, where the pointer is
+ * not NULL, corners (n_frames * corners_max * 4 long long, the filled slots) with counts (n_frames ints; both or neither),
+ * matches (n_pairs * corners_max * 4 ints) and inlier (n_pairs * corners_max ints; of both, the slots below the query's
+ * count). */
+int canny_hip_canny_motion(canny_hip_ctx *ctx, const unsigned char *imgs, int n_frames, float sigma, int min_val,
+                           int max_val, int height, int width, int mode, int block, int k_q8, int quality_q16,
+                           long long min_response, int min_dist, int corners_max, int desc_options, const int *pairs,
+                           int n_pairs, int max_distance, int ratio_q8, int match_options, int model, int thr_q4,
+                           int hypotheses, unsigned seed, long long *motion, long long *corners, int *counts, int *matches,
+                           int *inlier);
+
 /* ---- per-stage HIP-event timing (events are recorded on the launch stream) ----------------- */
 int canny_hip_profile_enable(canny_hip_ctx *ctx, int on);
 int canny_hip_profile_reset(canny_hip_ctx *ctx);
@@ -1955,6 +2042,8 @@ int canny_hip_curves_profile_get(canny_hip_ctx *ctx, int part, double *total_ms,
 int canny_hip_corners_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches);
 /* ... and for the four parts of the descriptors and their matching (CANNY_HIP_DESC_PART_*). */
 int canny_hip_descriptors_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches);
+/* ... and for the three parts of the motion estimate (CANNY_HIP_MOTION_PART_*). */
+int canny_hip_motion_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches);
 
 /* ---- self-test hooks used by the GPU test-suite -------------------------------------------- */
 /* Runs the DEVICE magnitude / angle-bin functions over every (gx,gy) in [-lim,lim]^2 and writes
@@ -2116,6 +2205,15 @@ int canny_hip_selftest_corners_plan(int which, int n_frames, int height, int wid
  * 1 <= stride <= CANNY_HIP_HOUGH_MAX_LINES, n >= 1 and within the calls' limits.  out holds 5 words. */
 enum canny_hip_descriptors_plan { CANNY_HIP_DESCRIPTORS_PLAN_DESCRIBE = 0, CANNY_HIP_DESCRIPTORS_PLAN_MATCH = 1 };
 int canny_hip_selftest_descriptors_plan(int which, unsigned long long n, int stride, unsigned long long *out);
+/* Host-only, the same five outputs for the capped launches of the motion estimate (no kind above), n_pairs >= 1 and at most
+ * CANNY_HIP_MATCH_MAX_PAIRS, 1 <= hypotheses <= CANNY_HIP_MOTION_MAX_HYPOTHESES:
+ *   CANNY_HIP_MOTION_PLAN_GATHER, CANNY_HIP_MOTION_PLAN_REFIT: items = the n_pairs pairs, one per workgroup and trip, at most
+ *     2048 workgroups;
+ *   CANNY_HIP_MOTION_PLAN_SCORE: items = n_pairs * ceil(hypotheses / 256), one (pair, block of 256 hypotheses) per workgroup
+ *     and trip, at most 2048 workgroups.
+ * out holds 5 words. */
+enum canny_hip_motion_plan { CANNY_HIP_MOTION_PLAN_GATHER = 0, CANNY_HIP_MOTION_PLAN_SCORE = 1, CANNY_HIP_MOTION_PLAN_REFIT = 2 };
+int canny_hip_selftest_motion_plan(int which, unsigned long long n_pairs, int hypotheses, unsigned long long *out);
 
 #ifdef __cplusplus
 }
