@@ -140,6 +140,8 @@ EXPORTS = (
     "canny_hip_match_descriptors", "canny_hip_descriptors_profile_get", "canny_hip_selftest_descriptors_plan",
     "canny_hip_dev_estimate_motion", "canny_hip_estimate_motion", "canny_hip_canny_motion", "canny_hip_motion_profile_get",
     "canny_hip_selftest_motion_plan",
+    "canny_hip_dev_compose_motion", "canny_hip_compose_motion", "canny_hip_dev_warp_frames", "canny_hip_warp_frames",
+    "canny_hip_canny_align", "canny_hip_warp_profile_get", "canny_hip_selftest_warp_plan",
 )
 
 _lib: Optional[C.CDLL] = None
@@ -374,6 +376,14 @@ def load() -> C.CDLL:
                                     C.c_uint, p, p, p, p, p], i),
         "canny_hip_motion_profile_get": ([p, i, C.POINTER(C.c_double), C.POINTER(C.c_long)], i),
         "canny_hip_selftest_motion_plan": ([i, ull, i, p], i),
+        "canny_hip_dev_compose_motion": ([p, p, i, i, p], i),
+        "canny_hip_compose_motion": ([p, i, i, p], i),
+        "canny_hip_dev_warp_frames": ([p, p, i, i, i, p, i, i, i, i, i, p, p], i),
+        "canny_hip_warp_frames": ([p, i, i, i, p, i, i, i, i, i, p, p], i),
+        "canny_hip_canny_align": ([p, p, i, f, i, i, i, i, i, i, i, i, C.c_longlong, i, i, i, i, i, i, i, i, i, C.c_uint, i, i,
+                                   p, p, p, p], i),
+        "canny_hip_warp_profile_get": ([p, i, C.POINTER(C.c_double), C.POINTER(C.c_long)], i),
+        "canny_hip_selftest_warp_plan": ([i, i, i, p, p, i, i, i, i, i, p], i),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -1126,6 +1136,74 @@ def motion_plan(which, n_pairs: int, hypotheses: int = 1):
     if st:
         raise CannyHipError(st, "selftest_motion_plan")
     return LaunchPlan(*(int(v) for v in out))
+
+
+# ---- frame alignment: the motions chained, frames warped ---------------------------------------------
+XFORM_WORDS = 8
+WARP_NEAREST, WARP_BILINEAR = 0, 1
+WARP_LDS_BYTES = 16384
+WARP_PARTS = ("compose", "warp")
+WARP_ROUTE_AUTO, WARP_ROUTE_DIRECT, WARP_ROUTE_TILED = 0, 1, 2
+XFORM_DTYPE = np.dtype([("flags", np.int64), ("src", np.int64), ("a11", np.int64), ("a12", np.int64), ("tx", np.int64),
+                        ("a21", np.int64), ("a22", np.int64), ("ty", np.int64)])
+
+
+def _words(records, words: int):
+    a = np.asarray(records)
+    if a.dtype.names:
+        a = np.ascontiguousarray(a).view(np.int64)
+    return np.ascontiguousarray(a, dtype=np.int64).reshape(-1, words)
+
+
+def compose_motion(motion, first_frame: int = 0):
+    """Host-only, needs no GPU: the motion records of the consecutive pairs (MOTION_DTYPE or int64 [n_pairs, 16]) chained
+    into n_pairs + 1 transform records (XFORM_DTYPE); record k maps frame first_frame's pixels into frame first_frame + k."""
+    m = _words(motion, MOTION_WORDS)
+    out = np.zeros((len(m) + 1, XFORM_WORDS), np.int64)
+    st = load().canny_hip_compose_motion(_hp(m) if len(m) else None, len(m), int(first_frame), _hp(out))
+    if st:
+        raise CannyHipError(st, "compose_motion")
+    return out.view(XFORM_DTYPE).reshape(-1)
+
+
+def warp_frames(src, xforms, out_h: int, out_w: int, interp: int = WARP_BILINEAR, border: int = 0):
+    """Host-only, needs no GPU: src uint8 [n_src, H, W] warped by the transform records (XFORM_DTYPE or int64 [n_out, 8]) ->
+    (uint8 [n_out, out_h, out_w], valid bit maps uint8 [n_out, out_h, ceil(out_w / 8)], rows MSB-first)."""
+    a = np.ascontiguousarray(src, dtype=np.uint8)
+    if a.ndim != 3:
+        raise ValueError("expected uint8 [n_src, H, W]")
+    x = _words(xforms, XFORM_WORDS)
+    out = np.zeros((len(x), max(int(out_h), 0), max(int(out_w), 0)), np.uint8)
+    valid = np.zeros((len(x), max(int(out_h), 0), (max(int(out_w), 0) + 7) // 8), np.uint8)
+    st = load().canny_hip_warp_frames(_hp(a), a.shape[0], a.shape[1], a.shape[2], _hp(x) if len(x) else None, len(x),
+                                      int(out_h), int(out_w), int(interp), int(border), _hp(out), _hp(valid))
+    if st:
+        raise CannyHipError(st, "warp_frames")
+    return out, valid
+
+
+WarpTile = collections.namedtuple("WarpTile", "staged x0 y0 x1 y1")
+
+
+def warp_plan(n_out: int, out_h: int, out_w: int):
+    """Host-only: the LaunchPlan of the warp's capped launch (one 64 x 16 output tile per workgroup and trip)."""
+    out = np.zeros(5, np.uint64)
+    st = load().canny_hip_selftest_warp_plan(int(n_out), int(out_h), int(out_w), _hp(out), None, 1, 1, 0, 0, 0, None)
+    if st:
+        raise CannyHipError(st, "selftest_warp_plan")
+    return LaunchPlan(*(int(v) for v in out))
+
+
+def warp_tile(xform, src_h: int, src_w: int, out_h: int, out_w: int, interp: int, tile_x: int, tile_y: int):
+    """Host-only: what the tiled route does with one 64 x 16 output tile under one transform record: WarpTile(staged, x0, y0,
+    x1, y1) -- staged in LDS or gathered directly, and the clipped source footprint (inclusive; x1 < x0: empty)."""
+    x = _words(xform, XFORM_WORDS)[:1]
+    out, box = np.zeros(5, np.uint64), np.zeros(5, np.int32)
+    st = load().canny_hip_selftest_warp_plan(1, int(out_h), int(out_w), _hp(out), _hp(x), int(src_h), int(src_w), int(interp),
+                                             int(tile_x), int(tile_y), _hp(box))
+    if st:
+        raise CannyHipError(st, "selftest_warp_plan")
+    return WarpTile(bool(box[0]), *(int(v) for v in box[1:]))
 
 
 # ---- chamfer template matching (DESIGN.md section 26) --------------------------------------------------------------------
@@ -2553,6 +2631,56 @@ class Context:
         k = [int(counts[q]) for q, _ in pr.tolist()]
         return (records, [np.ascontiguousarray(rec[f, :int(counts[f])]).view(CORNER_DTYPE).reshape(-1) for f in range(n)],
                 [mt[p, :k[p]].copy() for p in range(len(pr))], [flags[p, :k[p]].copy() for p in range(len(pr))])
+
+    # ---- frame alignment: the motions chained, frames warped ---------------------------------
+    def dev_compose_motion(self, d_motion: int, n_pairs: int, first_frame: int, d_xforms: int):
+        """The device motion records of the consecutive pairs (f, f + 1), f = first_frame .., chained into n_pairs + 1
+        transform records at d_xforms ([n_pairs + 1][8] int64, XFORM_DTYPE).  Asynchronous."""
+        v = C.c_void_p
+        self._check(self._L.canny_hip_dev_compose_motion(self._h, v(d_motion or None), n_pairs, first_frame,
+                                                         v(d_xforms or None)), "dev_compose_motion")
+
+    def dev_warp_frames(self, d_src: int, n_src: int, src_h: int, src_w: int, d_xforms: int, n_out: int, out_h: int,
+                        out_w: int, d_out: int, d_valid_bits: int = 0, interp: int = WARP_BILINEAR, border: int = 0):
+        """u8 planes [n_src][src_h][src_w] warped by the n_out device transform records into d_out [n_out][out_h][out_w]
+        and, if given, the valid bit maps [n_out][out_h][ceil(out_w / 8)].  Asynchronous."""
+        v = C.c_void_p
+        self._check(self._L.canny_hip_dev_warp_frames(self._h, v(d_src or None), n_src, src_h, src_w, v(d_xforms or None),
+                                                      n_out, out_h, out_w, interp, border, v(d_out or None),
+                                                      v(d_valid_bits or None)), "dev_warp_frames")
+
+    def canny_align(self, imgs, sigma: float, min_val: int, max_val: int, mode: int = CORNERS_MIN_EIGEN, block: int = 3,
+                    k_q8: int = 0, quality_q16: int = 655, min_response: int = 0, min_dist: int = 0, corners_max: int = 256,
+                    steered: bool = False, max_distance: int = 64, ratio_q8: int = 205,
+                    match_options: int = MATCH_CROSS_CHECK, model: int = MOTION_SIMILARITY, thr_q4: int = 48,
+                    hypotheses: int = 256, seed: int = 0, interp: int = WARP_BILINEAR, border: int = 0,
+                    details: bool = False):
+        """canny(), corners, descriptors, matching and motion over the consecutive pairs, the chain from frame 0 and the warp
+        of the input frames onto frame 0, all on the GPU: imgs (N, H, W) uint8 -> (aligned uint8 [N, H, W], transform
+        records XFORM_DTYPE [N]); with details also (motion records MOTION_DTYPE [N - 1], valid bit maps uint8
+        [N, H, ceil(W / 8)])."""
+        a = np.ascontiguousarray(imgs, dtype=np.uint8)
+        if a.ndim != 3:
+            raise ValueError("expected uint8 [n_frames, H, W]")
+        n, h, w = a.shape
+        aligned, xf = np.zeros((n, h, w), np.uint8), np.zeros((n, XFORM_WORDS), np.int64)
+        motion, valid = np.zeros((max(n - 1, 0), MOTION_WORDS), np.int64), np.zeros((n, h, (w + 7) // 8), np.uint8)
+        self._check(self._L.canny_hip_canny_align(self._h, _hp(a), n, sigma, min_val, max_val, h, w, mode, block, k_q8,
+                                                  quality_q16, min_response, min_dist, corners_max,
+                                                  DESC_STEERED if steered else 0, max_distance, ratio_q8, match_options,
+                                                  model, thr_q4, hypotheses, int(seed) & 0xFFFFFFFF, interp, border,
+                                                  _hp(aligned), _hp(xf), _hp(motion) if details and n > 1 else None,
+                                                  _hp(valid) if details else None), "canny_align")
+        records = xf.view(XFORM_DTYPE).reshape(-1)
+        if not details:
+            return aligned, records
+        return aligned, records, motion.view(MOTION_DTYPE).reshape(-1), valid
+
+    def warp_profile_get(self, part: int) -> Tuple[float, int]:
+        """(total ms, launch groups) of part 0 compose, 1 warp (WARP_PARTS)."""
+        ms, n = C.c_double(0), C.c_long(0)
+        self._check(self._L.canny_hip_warp_profile_get(self._h, part, C.byref(ms), C.byref(n)), "warp_profile_get")
+        return ms.value, n.value
 
     def motion_profile_get(self, part: int) -> Tuple[float, int]:
         """(total ms, launch groups) of part 0 gather, 1 score, 2 refit (MOTION_PARTS)."""

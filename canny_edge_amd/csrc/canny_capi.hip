@@ -412,6 +412,7 @@ struct canny_hip_ctx {
     // candidate passes' keys, histograms and counters; and the dist2 plane of the whole batch when the caller passes none
     DevBuf chamfer_cost, chamfer_scores, chamfer_ws, chamfer_dist2;
     int chamfer_route = 0; // 0 auto, 1 direct, 2 tiled
+    int warp_route = 0;    // 0 auto, 1 direct, 2 tiled
     int chamfer_chunk_mb = 0; // A/B and tests: budget of the score workspace in MiB, 0 = 256
     std::vector<canny_hip_chamfer_set *> chamfer_sets; // the sets created on this context and not yet destroyed
     // corners, per chunk of frames: the collected keys, the radix select's state, the maxima, histograms and counters
@@ -454,7 +455,7 @@ struct canny_hip_ctx {
     // circle fits (canny_hip_circle_fits_profile_get), then the four of the chamfer matching
     // (canny_hip_chamfer_profile_get), then the three of the contour shape measures (canny_hip_shapes_profile_get), then the two of the edge curves
     // (canny_hip_curves_profile_get), then the four of the corners (canny_hip_corners_profile_get), then the four of the descriptors and their matching
-    // (canny_hip_descriptors_profile_get), then the three of the motion estimate (canny_hip_motion_profile_get).  The mask is a non-negative int option: bit 30 is the last it can
+    // (canny_hip_descriptors_profile_get), then the three of the motion estimate (canny_hip_motion_profile_get), then the two of the frame alignment (canny_hip_warp_profile_get).  The mask is a non-negative int option: bit 30 is the last it can
     // carry, and the three polygon slots, the two edgel slots, the line-fit slot and the circle-fit slot behind them go by
     // it together
     static constexpr int kProfHough = CANNY_HIP_STAGE_END, kProfComponents = CANNY_HIP_STAGE_END + 3;
@@ -472,7 +473,8 @@ struct canny_hip_ctx {
     static constexpr int kProfCorners = kProfCurves + CANNY_HIP_CURVE_PARTS;
     static constexpr int kProfDescriptors = kProfCorners + CANNY_HIP_CORNER_PARTS;
     static constexpr int kProfMotion = kProfDescriptors + CANNY_HIP_DESC_PARTS;
-    static constexpr int kProfSlots = kProfMotion + CANNY_HIP_MOTION_PARTS;
+    static constexpr int kProfWarp = kProfMotion + CANNY_HIP_MOTION_PARTS;
+    static constexpr int kProfSlots = kProfWarp + CANNY_HIP_WARP_PARTS;
     static constexpr int kProfLastBit = 30;
     static_assert(kProfPolygons == kProfLastBit && kProfEdgels > kProfLastBit,
                   "profile_stage_mask has one bit per slot up to the polygon parts; every slot from there on follows bit 30");
@@ -2183,6 +2185,7 @@ int canny_hip_ctx_get_option(const canny_hip_ctx *ctx, const char *name, int *va
     else if (!std::strcmp(name, "hough_path")) *value = ctx->hough_path;
     else if (!std::strcmp(name, "tune_hough_lds_kb")) *value = ctx->hough_lds_kb;
     else if (!std::strcmp(name, "chamfer_route")) *value = ctx->chamfer_route;
+    else if (!std::strcmp(name, "warp_route")) *value = ctx->warp_route;
     else if (!std::strcmp(name, "tune_chamfer_chunk_mb")) *value = ctx->chamfer_chunk_mb;
     else if (!std::strcmp(name, "batch_expand_threads")) *value = ctx->expand_pool ? ctx->expand_pool->size() : 0; // read-only
     else return CANNY_HIP_ERR_INVALID;
@@ -2209,6 +2212,7 @@ int canny_hip_ctx_set_option(canny_hip_ctx *ctx, const char *name, int value)
     else if (!std::strcmp(name, "tune_batch_compact") && value <= 1) ctx->batch_compact = value;
     else if (!std::strcmp(name, "hough_path") && value <= 2) ctx->hough_path = value;
     else if (!std::strcmp(name, "chamfer_route") && value <= 2) ctx->chamfer_route = value;
+    else if (!std::strcmp(name, "warp_route") && value <= 2) ctx->warp_route = value;
     else if (!std::strcmp(name, "tune_chamfer_chunk_mb") && value <= 4096) ctx->chamfer_chunk_mb = value;
     else if (!std::strcmp(name, "tune_hough_lds_kb") && value <= kHoughLdsMax / 1024) ctx->hough_lds_kb = value;
     else if (!std::strcmp(name, "tune_batch_expand_threads") && value <= 64) {
@@ -6348,6 +6352,164 @@ int canny_hip_selftest_motion_plan(int which, unsigned long long n_pairs, int hy
     else
         return CANNY_HIP_ERR_INVALID;
     out[0] = p.units, out[1] = p.per_group, out[2] = p.grid, out[3] = p.trips(), out[4] = (unsigned long long)p.aux;
+    return CANNY_HIP_OK;
+}
+
+// ---- frame alignment: the motions chained, frames warped (canny_warp.hip) --------------------------
+// canny_hip_compose_motion and canny_hip_warp_frames, the rules in plain C++, live in canny_warp_host.cpp.
+
+int canny_hip_dev_compose_motion(canny_hip_ctx *ctx, const long long *d_motion, int n_pairs, int first_frame,
+                                 long long *d_xforms)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (n_pairs < 0 || first_frame < 0 || !d_xforms || (n_pairs > 0 && !d_motion) || ((uintptr_t)d_motion & 7) ||
+        ((uintptr_t)d_xforms & 7))
+        return CANNY_HIP_ERR_INVALID;
+    if (n_pairs > 65535) return CANNY_HIP_ERR_UNSUPPORTED;
+    if ((rc = finish_pending(ctx))) return rc;
+    StageTimer tm(ctx, canny_hip_ctx::kProfWarp + CANNY_HIP_WARP_PART_COMPOSE);
+    HIP_TRY(ctx, launch_warp_compose(d_motion, n_pairs, first_frame, d_xforms, ctx->stream));
+    return CANNY_HIP_OK;
+}
+
+namespace {
+bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb)
+{
+    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+    return pa < pb + nb && pb < pa + na;
+}
+
+// every check of the warp but the pointers
+int warp_check(int n_src, int src_h, int src_w, int n_out, int out_h, int out_w, int interp, int border)
+{
+    if (n_src < 1 || n_out < 1 || src_h < 1 || src_w < 1 || out_h < 1 || out_w < 1 ||
+        (interp != CANNY_HIP_WARP_NEAREST && interp != CANNY_HIP_WARP_BILINEAR) || border < 0 || border > 255)
+        return CANNY_HIP_ERR_INVALID;
+    if (src_h > 32768 || src_w > 32768 || out_h > 32768 || out_w > 32768 || (long long)src_h * src_w >= (1ll << 31) ||
+        (long long)out_h * out_w >= (1ll << 31) || n_src > 65535 || n_out > 65535)
+        return CANNY_HIP_ERR_UNSUPPORTED;
+    return CANNY_HIP_OK;
+}
+} // namespace
+
+int canny_hip_dev_warp_frames(canny_hip_ctx *ctx, const unsigned char *d_src, int n_src, int src_h, int src_w,
+                              const long long *d_xforms, int n_out, int out_h, int out_w, int interp, int border,
+                              unsigned char *d_out, unsigned char *d_valid_bits)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!d_src || !d_xforms || !d_out || ((uintptr_t)d_xforms & 7)) return CANNY_HIP_ERR_INVALID;
+    if ((rc = warp_check(n_src, src_h, src_w, n_out, out_h, out_w, interp, border))) return rc;
+    const size_t src_bytes = npx(src_h, src_w, n_src), out_bytes = npx(out_h, out_w, n_out);
+    const size_t valid_bytes = npx(out_h, (out_w + 7) / 8, n_out);
+    if (ranges_overlap(d_src, src_bytes, d_out, out_bytes) ||
+        (d_valid_bits && (ranges_overlap(d_src, src_bytes, d_valid_bits, valid_bytes) ||
+                          ranges_overlap(d_out, out_bytes, d_valid_bits, valid_bytes))))
+        return CANNY_HIP_ERR_INVALID;
+    if ((rc = finish_pending(ctx))) return rc;
+    StageTimer tm(ctx, canny_hip_ctx::kProfWarp + CANNY_HIP_WARP_PART_WARP);
+    HIP_TRY(ctx, launch_warp_frames(d_src, n_src, src_h, src_w, d_xforms, n_out, out_h, out_w, interp, border,
+                                    ctx->warp_route, d_out, d_valid_bits, ctx->stream));
+    return CANNY_HIP_OK;
+}
+
+int canny_hip_canny_align(canny_hip_ctx *ctx, const unsigned char *imgs, int n_frames, float sigma, int min_val, int max_val,
+                          int height, int width, int mode, int block, int k_q8, int quality_q16, long long min_response,
+                          int min_dist, int corners_max, int desc_options, int max_distance, int ratio_q8, int match_options,
+                          int model, int thr_q4, int hypotheses, unsigned seed, int interp, int border,
+                          unsigned char *aligned, long long *xforms, long long *motion, unsigned char *valid_bits)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    // every check of the chained calls, before anything is uploaded or queued
+    if (!imgs || !aligned || !xforms || max_distance < 0 || max_distance > CANNY_HIP_DESC_BITS || ratio_q8 < 0 ||
+        ratio_q8 > 256 || (match_options & ~CANNY_HIP_MATCH_CROSS_CHECK) || model < CANNY_HIP_MOTION_TRANSLATION ||
+        model > CANNY_HIP_MOTION_AFFINE || thr_q4 < 0 || thr_q4 > 4095 || hypotheses < 1 || ((uintptr_t)xforms & 7) ||
+        ((uintptr_t)motion & 7))
+        return CANNY_HIP_ERR_INVALID;
+    // the descriptor check wants its four pointers: the outputs that stay on the device stand in
+    if ((rc = descriptors_check(height, width, n_frames, corners_max, desc_options, xforms, xforms, xforms, xforms))) return rc;
+    const CornerArgs a{mode, block, k_q8, quality_q16, min_response, min_dist, corners_max};
+    if ((rc = corners_check(height, width, n_frames, a, CornerOut{xforms, (int *)xforms, nullptr, nullptr, nullptr}))) return rc;
+    if ((rc = warp_check(n_frames, height, width, n_frames, height, width, interp, border))) return rc;
+    if (hypotheses > CANNY_HIP_MOTION_MAX_HYPOTHESES) return CANNY_HIP_ERR_UNSUPPORTED;
+    const int n_pairs = n_frames - 1;
+    std::vector<int> pairs(2 * (size_t)n_pairs);
+    for (int p = 0; p < n_pairs; p++) pairs[2 * p] = p, pairs[2 * p + 1] = p + 1;
+    const size_t slots = (size_t)n_frames * corners_max, pslots = (size_t)n_pairs * corners_max;
+    const size_t frame_bytes = npx(height, width, n_frames), valid_bytes = npx(height, (width + 7) / 8, n_frames);
+    // one staging block: records | descriptors | motion records | transform records | meta | counts | matches | pair counts |
+    // aligned frames | valid bits
+    HIP_TRY(ctx, ctx->io[1].ensure(slots * (CANNY_HIP_CORNER_WORDS * sizeof(long long) +
+                                            CANNY_HIP_DESC_WORDS * sizeof(unsigned long long) + sizeof(int)) +
+                                   (size_t)n_pairs * CANNY_HIP_MOTION_WORDS * sizeof(long long) +
+                                   (size_t)n_frames * CANNY_HIP_XFORM_WORDS * sizeof(long long) +
+                                   (size_t)n_frames * sizeof(int) + pslots * CANNY_HIP_MATCH_WORDS * sizeof(int) +
+                                   (size_t)n_pairs * sizeof(int) + 16 + frame_bytes + valid_bytes));
+    long long *d_rec = (long long *)ctx->io[1].p;
+    unsigned long long *d_desc = (unsigned long long *)(d_rec + slots * CANNY_HIP_CORNER_WORDS);
+    long long *d_motion = (long long *)(d_desc + slots * CANNY_HIP_DESC_WORDS);
+    long long *d_xf = d_motion + (size_t)n_pairs * CANNY_HIP_MOTION_WORDS;
+    int *d_meta = (int *)(d_xf + (size_t)n_frames * CANNY_HIP_XFORM_WORDS), *d_cnt = d_meta + slots;
+    int *d_matches = d_cnt + n_frames, *d_pc = d_matches + pslots * CANNY_HIP_MATCH_WORDS;
+    unsigned char *d_aligned = (unsigned char *)(((uintptr_t)(d_pc + n_pairs) + 15) & ~(uintptr_t)15);
+    unsigned char *d_valid = d_aligned + frame_bytes;
+    if ((rc = h2d(ctx, ctx->io[0], imgs, frame_bytes))) return rc;
+    const unsigned char *d_gray = (const unsigned char *)ctx->io[0].p;
+    if (n_pairs > 0) {
+        if ((rc = canny_hip_dev_canny_corner_descriptors(ctx, d_gray, sigma, min_val, max_val, height, width, n_frames,
+                                                         nullptr, mode, block, k_q8, quality_q16, min_response, min_dist,
+                                                         corners_max, d_rec, d_cnt, nullptr, nullptr, nullptr, desc_options,
+                                                         d_desc, d_meta)))
+            return rc;
+        if ((rc = canny_hip_dev_match_descriptors(ctx, d_desc, d_cnt, n_frames, corners_max, d_desc, d_cnt, n_frames,
+                                                  corners_max, pairs.data(), n_pairs, max_distance, ratio_q8, match_options,
+                                                  d_matches, d_pc)))
+            return rc;
+        if ((rc = canny_hip_dev_estimate_motion(ctx, d_rec, d_cnt, n_frames, corners_max, d_rec, d_cnt, n_frames,
+                                                corners_max, pairs.data(), n_pairs, d_matches, model, thr_q4, hypotheses, seed,
+                                                d_motion, nullptr)))
+            return rc;
+    }
+    if ((rc = canny_hip_dev_compose_motion(ctx, n_pairs ? d_motion : nullptr, n_pairs, 0, d_xf))) return rc;
+    if ((rc = canny_hip_dev_warp_frames(ctx, d_gray, n_frames, height, width, d_xf, n_frames, height, width, interp, border,
+                                        d_aligned, valid_bits ? d_valid : nullptr)))
+        return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(aligned, d_aligned, frame_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(xforms, d_xf, (size_t)n_frames * CANNY_HIP_XFORM_WORDS * sizeof(long long),
+                                hipMemcpyDeviceToHost, ctx->stream));
+    if (motion && n_pairs)
+        HIP_TRY(ctx, hipMemcpyAsync(motion, d_motion, (size_t)n_pairs * CANNY_HIP_MOTION_WORDS * sizeof(long long),
+                                    hipMemcpyDeviceToHost, ctx->stream));
+    if (valid_bits) HIP_TRY(ctx, hipMemcpyAsync(valid_bits, d_valid, valid_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return CANNY_HIP_OK;
+}
+
+int canny_hip_warp_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches)
+{
+    if (part < 0 || part >= CANNY_HIP_WARP_PARTS || !total_ms || !launches) return CANNY_HIP_ERR_INVALID;
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if ((rc = profile_collect(ctx))) return rc;
+    *total_ms = ctx->total_ms[canny_hip_ctx::kProfWarp + part];
+    *launches = ctx->launches[canny_hip_ctx::kProfWarp + part];
+    return CANNY_HIP_OK;
+}
+
+// Host-only: the launch plan of the warp and, for one record and tile, what the tiled route does with it.
+int canny_hip_selftest_warp_plan(int n_out, int out_h, int out_w, unsigned long long *out, const long long *xform, int src_h,
+                                 int src_w, int interp, int tile_x, int tile_y, int *box)
+{
+    if (!out || warp_check(1, 1, 1, n_out, out_h, out_w, 0, 0)) return CANNY_HIP_ERR_INVALID;
+    const LaunchPlan p = plan_warp_tiles(n_out, out_h, out_w);
+    out[0] = p.units, out[1] = p.per_group, out[2] = p.grid, out[3] = p.trips(), out[4] = (unsigned long long)p.aux;
+    if (!xform) return CANNY_HIP_OK;
+    if (!box || warp_check(1, src_h, src_w, 1, 1, 1, interp, 0) || tile_x < 0 || tile_y < 0 || tile_x * 64 >= out_w ||
+        tile_y * 16 >= out_h)
+        return CANNY_HIP_ERR_INVALID;
+    box[0] = warp_tile_footprint(xform, interp, src_h, src_w, out_h, out_w, tile_x, tile_y, box + 1) ? 1 : 0;
     return CANNY_HIP_OK;
 }
 

@@ -825,6 +825,21 @@ hipError_t launch_motion_score(int stride_q, int n_pairs, int model, int thr_q4,
 hipError_t launch_motion_refit(int stride_q, int n_pairs, int model, int thr_q4, int hypotheses, unsigned seed,
                                const MotionWs &w, long long *motion, int *inlier, hipStream_t stream);
 
+// ---- frame alignment: the motions chained, frames warped (canny_warp.hip) --------------
+// warp: the n_out * ceil(out_h / 16) * ceil(out_w / 64) output tiles, one per workgroup and trip.  (Reported by
+// canny_hip_selftest_warp_plan, not by a kind.)
+LaunchPlan plan_warp_tiles(int n_out, int out_h, int out_w);
+// What the tiled route does with tile (tile_x, tile_y) of a frame warped by the record `xform` (8 words; its source index is
+// not looked at): true if the footprint is staged in LDS; box: the clipped footprint x0, y0, x1, y1 (empty: x1 < x0).
+bool warp_tile_footprint(const long long *xform, int interp, int src_h, int src_w, int out_h, int out_w, int tile_x,
+                         int tile_y, int box[4]);
+// n_pairs + 1 transform records from the motion records of the consecutive pairs; one lane.
+hipError_t launch_warp_compose(const long long *motion, int n_pairs, int first_frame, long long *xforms, hipStream_t stream);
+// Every output byte and (valid != NULL) every valid byte.  route: 0 automatic, 1 direct, 2 tiled.
+hipError_t launch_warp_frames(const uint8_t *src, int n_src, int src_h, int src_w, const long long *xforms, int n_out,
+                              int out_h, int out_w, int interp, int border, int route, uint8_t *out, uint8_t *valid,
+                              hipStream_t stream);
+
 // ---- measurement aid ------------------------------------------------------------------------
 // Plain device copy of nbytes (multiple of 16; both pointers 16-byte aligned): what a 1:1 read/write stream reaches.
 hipError_t launch_probe_copy(const void *src, void *dst, size_t nbytes, hipStream_t stream, const LaunchEvents &ev = {});

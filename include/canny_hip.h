@@ -52,7 +52,8 @@
 extern "C" {
 #endif
 
-#define CANNY_HIP_VERSION 2100       /* 0.21.0: + frame-to-frame motion from the corner matches (RANSAC) */
+#define CANNY_HIP_VERSION 2200       /* 0.22.0: + frame alignment: the motions chained, frames warped */
+/* 0.21.0: + frame-to-frame motion from the corner matches (RANSAC) */
 /* 0.20.0: + corner descriptors and Hamming matching between frames */
 /* 0.19.0: + corners: Harris / Shi-Tomasi on the smoothed plane */
 /* 0.18.0: + edge curves: the edge map linked into ordered chains */
@@ -2006,6 +2007,89 @@ int canny_hip_canny_motion(canny_hip_ctx *ctx, const unsigned char *imgs, int n_
                            int hypotheses, unsigned seed, long long *motion, long long *corners, int *counts, int *matches,
                            int *inlier);
 
+/* ---- frame alignment: chain the motions and warp frames ----------------------------------------------------------------------
+ * The motion records say how the camera moved between consecutive frames; this applies them.  The records of the pairs
+ * (f, f + 1) are chained into one transform per frame, and u8 frames are warped by such transforms -- what
+ * cv::warpAffine(..., WARP_INVERSE_MAP) answers -- on the GPU, on the context's stream, no host round trip, no atomics.  A
+ * motion record is stored query -> train in Q16, which is exactly the output -> source map of an inverse warp: aligning frame
+ * f + k onto frame f needs no matrix inversion.  All integers: the same bytes on every run and every machine.
+ * tests/warp_rule.py restates both rules in numpy and plain Python ints, csrc/canny_warp_host.cpp in plain C++.
+ * THE RULE:
+ *   Transform record, CANNY_HIP_XFORM_WORDS = 8 long long per output frame: 0 flags (bit 0 usable); 1 the source frame index;
+ *     2..7 a11, a12, tx, a21, a22, ty in Q16, in the order of words 4..9 of a motion record: output pixel (x, y) -> source
+ *     position.  A record is USABLE iff bit 0 is set, every |a_ij| <= 2^24, |tx|, |ty| <= 2^36 and 0 <= word 1 < n_src.
+ *     Callers may write such records themselves.
+ *   Chain (compose): d_motion holds the motion records of the consecutive pairs (f, f + 1), f = first_frame .., as
+ *     consecutive_pairs of the Python binding orders them; n_pairs + 1 records are written, record k maps the pixels of frame
+ *     first_frame into frame first_frame + k: word 1 = first_frame + k.  T_0 = (65536, 0, 0, 0, 65536, 0), the identity.
+ *     T_{k+1} = M_k o T_k, fl = floor toward -inf, m the motion's coefficients, p those of T_k:
+ *       a_ij = fl((m_i1 p_1j + m_i2 p_2j) / 65536),   t_i = fl((m_i1 p_tx + m_i2 p_ty) / 65536) + m_ti.
+ *     M_k is used only if its record has flag bits 0 and 1 (model and refit) and every |m_ij| <= 2^24, |m_ti| <= 2^36; if it
+ *     fails, or the composed record exceeds these limits, this record and every later one gets flags 0 and zero coefficients
+ *     (word 1 is still written).  Widths: the linear sums stay under 2^50 and the translation sums under 2^62, so signed 64
+ *     bits suffice.  The rounding makes composition non-associative, so the rule is sequential: one lane walks the chain.
+ *     0 <= n_pairs <= 65535, first_frame >= 0.
+ *   Warp: source planes [n_src][src_h][src_w] u8, output planes [n_out][out_h][out_w] u8, one record per output frame.  For
+ *     output pixel (x, y) of a frame with a usable record, exact integers, |X| < 2^41:
+ *       X = a11 x + a12 y + tx,   Y = a21 x + a22 y + ty.
+ *     CANNY_HIP_WARP_NEAREST = 0: sx = (X + 32768) >> 16, sy likewise (arithmetic shifts); the pixel is src[word 1][sy][sx] if
+ *       that lies inside the source, otherwise `border`.
+ *     CANNY_HIP_WARP_BILINEAR = 1: X8 = (X + 128) >> 8, ix = X8 >> 8, fx = X8 & 255, the same for y; four taps p00 = (iy, ix),
+ *       p01 = (iy, ix + 1), p10 = (iy + 1, ix), p11 = (iy + 1, ix + 1), each the source byte if inside, else `border`
+ *       (BORDER_CONSTANT);
+ *       out = ((256 - fx)(256 - fy) p00 + fx (256 - fy) p01 + (256 - fx) fy p10 + fx fy p11 + 32768) >> 16.
+ *       The weights are Q8, so the sum stays under 2^24 and the identity returns the input bytes.
+ *     Valid bit: 1 iff every tap with a non-zero weight lies inside the source (NEAREST: the one tap); the identity is valid
+ *       everywhere.  A record that is not usable: the whole frame is `border`, every valid bit 0.  Every output byte is
+ *       written, and every valid byte (layout of canny_hip_dev_canny_bits: rows MSB-first, padded to bytes, pad bits 0).
+ *   Limits: all four dimensions >= 1 and <= 32768, each plane < 2^31 pixels, at most 65535 frames on either side, 65535 pairs;
+ *     above: CANNY_HIP_ERR_UNSUPPORTED.  Bad ranges (interp, border outside [0, 255], counts < 1), NULL mandatory pointers, a
+ *     source and an output that overlap, record buffers that are not 8-byte aligned: CANNY_HIP_ERR_INVALID.  Both before
+ *     anything is queued; nothing is written.
+ *   The context option "warp_route" chooses how the taps are fetched: 0 automatic, 1 direct (gathered from global memory
+ *     through the vector cache), 2 tiled (the source footprint of every 64 x 16 output tile -- the bounding box of the images
+ *     of its four corners, one more row and column under BILINEAR, clipped to the source -- is staged in LDS with coalesced
+ *     row loads where it fits CANNY_HIP_WARP_LDS_BYTES, and that tile alone falls back to the direct gather where it does
+ *     not).  All routes give the same bytes.  Automatic is the direct route, except under BILINEAR for records with
+ *     |a21| >= |a11| (a turn of 45 degrees or more), where it is the tiled one: where the measurement shows each ahead.
+ * The two parts are timed by canny_hip_warp_profile_get (CANNY_HIP_WARP_PART_*); with "profile_stage_mask" they go by bit 30
+ *   like every part behind the polygons.
+ * Not covered -- follow-ups: inverting a model (anchors other than the first frame, trajectory smoothing); s16 or colour
+ * planes, and warping the finished edge maps; bicubic interpolation; a grammar of Main (it takes one frame); alignment through
+ * the batch pipeline or the multi-GPU sharder. */
+#define CANNY_HIP_XFORM_WORDS 8
+#define CANNY_HIP_WARP_LDS_BYTES 16384
+enum canny_hip_warp_interp { CANNY_HIP_WARP_NEAREST = 0, CANNY_HIP_WARP_BILINEAR = 1 };
+enum canny_hip_warp_part {
+    CANNY_HIP_WARP_PART_COMPOSE = 0, /* the chain of the motion records */
+    CANNY_HIP_WARP_PART_WARP = 1,    /* the warp of the frames */
+    CANNY_HIP_WARP_PARTS = 2
+};
+/* d_motion: n_pairs * 16 long long as the motion estimate wrote them (may be NULL if n_pairs == 0); d_xforms receives
+ * (n_pairs + 1) * 8 long long.  Asynchronous. */
+int canny_hip_dev_compose_motion(canny_hip_ctx *ctx, const long long *d_motion, int n_pairs, int first_frame,
+                                 long long *d_xforms);
+/* Host-only, needs no device: the same rule on host buffers. */
+int canny_hip_compose_motion(const long long *motion, int n_pairs, int first_frame, long long *xforms);
+/* d_xforms: n_out * 8 long long; d_out: n_out * out_h * out_w bytes; d_valid_bits: n_out * out_h * ((out_w + 7) / 8)
+ * bytes, may be NULL.  Asynchronous. */
+int canny_hip_dev_warp_frames(canny_hip_ctx *ctx, const unsigned char *d_src, int n_src, int src_h, int src_w,
+                              const long long *d_xforms, int n_out, int out_h, int out_w, int interp, int border,
+                              unsigned char *d_out, unsigned char *d_valid_bits);
+/* Host-only, needs no device: the same rule on host buffers. */
+int canny_hip_warp_frames(const unsigned char *src, int n_src, int src_h, int src_w, const long long *xforms, int n_out,
+                          int out_h, int out_w, int interp, int border, unsigned char *out, unsigned char *valid_bits);
+/* Host buffers, synchronous: canny, the corners, their descriptors, the matching and the motion over the consecutive pairs
+ * (f, f + 1), the chain from frame 0 and the warp of the INPUT gray frames to frame 0's geometry, all on the device.  aligned
+ * (n_frames * height * width bytes) and xforms (n_frames * 8 long long) come down and, where the pointer is not NULL, motion
+ * ((n_frames - 1) * 16 long long) and valid_bits (n_frames * height * ((width + 7) / 8) bytes).  n_frames == 1 returns the
+ * frame itself with an identity record. */
+int canny_hip_canny_align(canny_hip_ctx *ctx, const unsigned char *imgs, int n_frames, float sigma, int min_val, int max_val,
+                          int height, int width, int mode, int block, int k_q8, int quality_q16, long long min_response,
+                          int min_dist, int corners_max, int desc_options, int max_distance, int ratio_q8, int match_options,
+                          int model, int thr_q4, int hypotheses, unsigned seed, int interp, int border,
+                          unsigned char *aligned, long long *xforms, long long *motion, unsigned char *valid_bits);
+
 /* ---- per-stage HIP-event timing (events are recorded on the launch stream) ----------------- */
 int canny_hip_profile_enable(canny_hip_ctx *ctx, int on);
 int canny_hip_profile_reset(canny_hip_ctx *ctx);
@@ -2044,6 +2128,8 @@ int canny_hip_corners_profile_get(canny_hip_ctx *ctx, int part, double *total_ms
 int canny_hip_descriptors_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches);
 /* ... and for the three parts of the motion estimate (CANNY_HIP_MOTION_PART_*). */
 int canny_hip_motion_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches);
+/* ... and for the two parts of the frame alignment (CANNY_HIP_WARP_PART_*). */
+int canny_hip_warp_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches);
 
 /* ---- self-test hooks used by the GPU test-suite -------------------------------------------- */
 /* Runs the DEVICE magnitude / angle-bin functions over every (gx,gy) in [-lim,lim]^2 and writes
@@ -2214,6 +2300,14 @@ int canny_hip_selftest_descriptors_plan(int which, unsigned long long n, int str
  * out holds 5 words. */
 enum canny_hip_motion_plan { CANNY_HIP_MOTION_PLAN_GATHER = 0, CANNY_HIP_MOTION_PLAN_SCORE = 1, CANNY_HIP_MOTION_PLAN_REFIT = 2 };
 int canny_hip_selftest_motion_plan(int which, unsigned long long n_pairs, int hypotheses, unsigned long long *out);
+/* Host-only, the same five outputs for the capped launch of the warp (no kind above): items = the n_out * ceil(out_h / 16) *
+ * ceil(out_w / 64) output tiles, one per workgroup of 256 and trip, at most 4096 workgroups.  Dimensions within the warp's
+ * limits.  With xform != NULL (one record of 8 words, its source frame taken as present) also what the tiled route does with
+ * tile (tile_x, tile_y) of a frame warped from a src_h x src_w source: box receives 5 ints: 1 if the tile's footprint is
+ * staged in LDS, 0 if the tile gathers directly (the footprint exceeds CANNY_HIP_WARP_LDS_BYTES, is empty, or the record is
+ * not usable), then the clipped footprint x0, y0, x1, y1 (inclusive; x1 < x0 or y1 < y0: empty). */
+int canny_hip_selftest_warp_plan(int n_out, int out_h, int out_w, unsigned long long *out, const long long *xform, int src_h,
+                                 int src_w, int interp, int tile_x, int tile_y, int *box);
 
 #ifdef __cplusplus
 }
