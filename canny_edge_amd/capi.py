@@ -142,6 +142,9 @@ EXPORTS = (
     "canny_hip_selftest_motion_plan",
     "canny_hip_dev_compose_motion", "canny_hip_compose_motion", "canny_hip_dev_warp_frames", "canny_hip_warp_frames",
     "canny_hip_canny_align", "canny_hip_warp_profile_get", "canny_hip_selftest_warp_plan",
+    "canny_hip_dev_fuse_frames", "canny_hip_fuse_frames", "canny_hip_dev_change_mask", "canny_hip_change_mask",
+    "canny_hip_canny_background", "canny_hip_fuse_profile_get", "canny_hip_selftest_fuse_plan",
+    "canny_hip_selftest_fuse_mean",
 )
 
 _lib: Optional[C.CDLL] = None
@@ -384,6 +387,15 @@ def load() -> C.CDLL:
                                    p, p, p, p], i),
         "canny_hip_warp_profile_get": ([p, i, C.POINTER(C.c_double), C.POINTER(C.c_long)], i),
         "canny_hip_selftest_warp_plan": ([i, i, i, p, p, i, i, i, i, i, p], i),
+        "canny_hip_dev_fuse_frames": ([p, p, p, i, i, i, i, i, i, i, i, p, p], i),
+        "canny_hip_fuse_frames": ([p, p, i, i, i, i, i, i, i, i, p, p], i),
+        "canny_hip_dev_change_mask": ([p, p, p, i, i, i, p, p, i, i, i, p, p], i),
+        "canny_hip_change_mask": ([p, p, i, i, i, p, p, i, i, i, p, p], i),
+        "canny_hip_canny_background": ([p, p, i, f, i, i, i, i, i, i, i, i, C.c_longlong, i, i, i, i, i, i, i, i, i, C.c_uint,
+                                        i, i, i, i, i, i, p, p, p, p, p], i),
+        "canny_hip_fuse_profile_get": ([p, i, C.POINTER(C.c_double), C.POINTER(C.c_long)], i),
+        "canny_hip_selftest_fuse_plan": ([i, i, i, i, i, i, p], i),
+        "canny_hip_selftest_fuse_mean": ([p, p], i),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -1204,6 +1216,88 @@ def warp_tile(xform, src_h: int, src_w: int, out_h: int, out_w: int, interp: int
     if st:
         raise CannyHipError(st, "selftest_warp_plan")
     return WarpTile(bool(box[0]), *(int(v) for v in box[1:]))
+
+
+# ---- temporal fusion of aligned frames and change masks ---------------------------------------------
+FUSE_MEAN, FUSE_MEDIAN, FUSE_MIN, FUSE_MAX = 0, 1, 2, 3
+FUSE_ROUTE_AUTO, FUSE_ROUTE_REGISTERS, FUSE_ROUTE_PASSES = 0, 1, 2
+FUSE_MAX_GROUP = 255
+FUSE_MEAN_ROW = 65026
+FUSE_PARTS = ("fuse", "mask")
+
+
+def fuse_groups(n_frames: int, group_len: int, group_step: int) -> int:
+    """The number of windows of group_len frames, group_step apart, in a stack of n_frames."""
+    return (int(n_frames) - int(group_len)) // int(group_step) + 1
+
+
+def _stack(frames, valid_bits):
+    a = np.ascontiguousarray(frames, dtype=np.uint8)
+    if a.ndim != 3:
+        raise ValueError("expected uint8 [n_frames, H, W]")
+    v = None
+    if valid_bits is not None:
+        v = np.ascontiguousarray(valid_bits, dtype=np.uint8)
+        if v.shape != (a.shape[0], a.shape[1], (a.shape[2] + 7) // 8):
+            raise ValueError("expected valid bit maps uint8 [n_frames, H, ceil(W / 8)]")
+    return a, v
+
+
+def fuse_frames(frames, valid_bits=None, group_len: Optional[int] = None, group_step: Optional[int] = None,
+                op: int = FUSE_MEDIAN, fill: int = 0, min_count: int = 1):
+    """Host-only, needs no GPU: frames uint8 [n_frames, H, W] reduced over windows of group_len frames (default: all of them),
+    group_step apart (default: group_len), under the valid bit maps uint8 [n_frames, H, ceil(W / 8)] (rows MSB-first; None: all
+    valid) -> (fused uint8 [n_groups, H, W], count uint8 [n_groups, H, W])."""
+    a, v = _stack(frames, valid_bits)
+    n, h, w = a.shape
+    group_len = n if group_len is None else int(group_len)
+    group_step = group_len if group_step is None else int(group_step)
+    ok = 1 <= group_len <= n and group_step >= 1
+    n_groups = fuse_groups(n, group_len, group_step) if ok else 1
+    fused, count = np.zeros((n_groups, h, w), np.uint8), np.zeros((n_groups, h, w), np.uint8)
+    st = load().canny_hip_fuse_frames(_hp(a), _hp(v) if v is not None else None, n, h, w, group_len, group_step, int(op),
+                                      int(fill), int(min_count), _hp(fused), _hp(count))
+    if st:
+        raise CannyHipError(st, "fuse_frames")
+    return fused, count
+
+
+def change_mask(frames, background, valid_bits=None, bg_count=None, frames_per_background: Optional[int] = None, thr: int = 0,
+                min_count: int = 1):
+    """Host-only, needs no GPU: the change masks of frames uint8 [n_frames, H, W] against background uint8 [n_background, H, W]
+    (frame f against plane f // frames_per_background; default: one plane for all) -> (mask bit maps uint8 [n_frames, H,
+    ceil(W / 8)], rows MSB-first with pad bits 0; changed int64 [n_frames], the set bits of each frame)."""
+    a, v = _stack(frames, valid_bits)
+    n, h, w = a.shape
+    per = max(n, 1) if frames_per_background is None else int(frames_per_background)
+    bg = np.ascontiguousarray(background, dtype=np.uint8)
+    bg = bg[None] if bg.ndim == 2 else bg
+    bc = None
+    if bg_count is not None:
+        bc = np.ascontiguousarray(bg_count, dtype=np.uint8)
+        bc = bc[None] if bc.ndim == 2 else bc
+    n_bg = -(-n // per) if per >= 1 else 1
+    if bg.shape != (n_bg, h, w) or (bc is not None and bc.shape != bg.shape):
+        raise ValueError("expected background (and bg_count) uint8 [ceil(n_frames / frames_per_background), H, W]")
+    mask, changed = np.zeros((n, h, (w + 7) // 8), np.uint8), np.zeros(n, np.int64)
+    st = load().canny_hip_change_mask(_hp(a), _hp(v) if v is not None else None, n, h, w, _hp(bg),
+                                      _hp(bc) if bc is not None else None, per, int(thr), int(min_count), _hp(mask),
+                                      _hp(changed))
+    if st:
+        raise CannyHipError(st, "change_mask")
+    return mask, changed
+
+
+def fuse_plan(which, n_frames: int, h: int, w: int, group_len: int = 1, group_step: int = 1):
+    """Host-only: the LaunchPlan of a capped launch of the temporal fusion (one 64 x 16 output tile per workgroup and trip):
+    which is a name of FUSE_PARTS or its number.  "fuse": the tiles of the n_groups fused planes, aux = the route automatic
+    takes for a MEDIAN of group_len frames; "mask": the tiles of the n_frames masks."""
+    k = FUSE_PARTS.index(which) if isinstance(which, str) else int(which)
+    out = np.zeros(5, np.uint64)
+    st = load().canny_hip_selftest_fuse_plan(k, int(n_frames), int(h), int(w), int(group_len), int(group_step), _hp(out))
+    if st:
+        raise CannyHipError(st, "selftest_fuse_plan")
+    return LaunchPlan(*(int(v) for v in out))
 
 
 # ---- chamfer template matching (DESIGN.md section 26) --------------------------------------------------------------------
@@ -2681,6 +2775,70 @@ class Context:
         ms, n = C.c_double(0), C.c_long(0)
         self._check(self._L.canny_hip_warp_profile_get(self._h, part, C.byref(ms), C.byref(n)), "warp_profile_get")
         return ms.value, n.value
+
+    # ---- temporal fusion of aligned frames and change masks ------------------------------------
+    def dev_fuse_frames(self, d_frames: int, d_valid_bits: int, n_frames: int, h: int, w: int, group_len: int,
+                        group_step: int, d_fused: int, d_count: int = 0, op: int = FUSE_MEDIAN, fill: int = 0,
+                        min_count: int = 1):
+        """u8 planes [n_frames][h][w] reduced over windows of group_len frames, group_step apart, under the valid bit maps
+        (0: every pixel valid) into d_fused [n_groups][h][w] and, if given, the counts d_count.  Asynchronous."""
+        v = C.c_void_p
+        self._check(self._L.canny_hip_dev_fuse_frames(self._h, v(d_frames or None), v(d_valid_bits or None), n_frames, h, w,
+                                                      group_len, group_step, op, fill, min_count, v(d_fused or None),
+                                                      v(d_count or None)), "dev_fuse_frames")
+
+    def dev_change_mask(self, d_frames: int, d_valid_bits: int, n_frames: int, h: int, w: int, d_background: int,
+                        d_bg_count: int, frames_per_background: int, d_mask_bits: int, d_changed: int = 0, thr: int = 0,
+                        min_count: int = 1):
+        """The change masks of the frames against background plane f // frames_per_background into d_mask_bits
+        [n_frames][h][ceil(w / 8)] (the layout dev_components_bits takes) and, if given, the set bits of each frame as
+        int64 at d_changed.  Asynchronous."""
+        v = C.c_void_p
+        self._check(self._L.canny_hip_dev_change_mask(self._h, v(d_frames or None), v(d_valid_bits or None), n_frames, h, w,
+                                                      v(d_background or None), v(d_bg_count or None), frames_per_background,
+                                                      thr, min_count, v(d_mask_bits or None), v(d_changed or None)),
+                    "dev_change_mask")
+
+    def canny_background(self, imgs, sigma: float, min_val: int, max_val: int, mode: int = CORNERS_MIN_EIGEN, block: int = 3,
+                         k_q8: int = 0, quality_q16: int = 655, min_response: int = 0, min_dist: int = 0,
+                         corners_max: int = 256, steered: bool = False, max_distance: int = 64, ratio_q8: int = 205,
+                         match_options: int = MATCH_CROSS_CHECK, model: int = MOTION_SIMILARITY, thr_q4: int = 48,
+                         hypotheses: int = 256, seed: int = 0, interp: int = WARP_BILINEAR, border: int = 0,
+                         op: int = FUSE_MEDIAN, fill: int = 0, min_count: int = 1, thr: int = 0, details: bool = False):
+        """canny_align's chain, the fusion of all aligned frames into one background and the change masks of the aligned
+        frames against it, all on the GPU: imgs (N, H, W) uint8, N <= 255 -> (background uint8 [H, W], mask bit maps uint8
+        [N, H, ceil(W / 8)], changed int64 [N]); with details also (count uint8 [H, W], transform records XFORM_DTYPE
+        [N])."""
+        a = np.ascontiguousarray(imgs, dtype=np.uint8)
+        if a.ndim != 3:
+            raise ValueError("expected uint8 [n_frames, H, W]")
+        n, h, w = a.shape
+        bg, count = np.zeros((h, w), np.uint8), np.zeros((h, w), np.uint8)
+        mask, changed, xf = np.zeros((n, h, (w + 7) // 8), np.uint8), np.zeros(n, np.int64), np.zeros((n, XFORM_WORDS), np.int64)
+        self._check(self._L.canny_hip_canny_background(self._h, _hp(a), n, sigma, min_val, max_val, h, w, mode, block, k_q8,
+                                                       quality_q16, min_response, min_dist, corners_max,
+                                                       DESC_STEERED if steered else 0, max_distance, ratio_q8,
+                                                       match_options, model, thr_q4, hypotheses, int(seed) & 0xFFFFFFFF,
+                                                       interp, border, op, fill, min_count, thr, _hp(bg),
+                                                       _hp(count) if details else None, _hp(mask), _hp(changed), _hp(xf)),
+                    "canny_background")
+        if not details:
+            return bg, mask, changed
+        return bg, mask, changed, count, xf.view(XFORM_DTYPE).reshape(-1)
+
+    def fuse_profile(self, part) -> Tuple[float, int]:
+        """(total ms, launch groups) of part 0 fuse, 1 mask (FUSE_PARTS; a name or its number)."""
+        k = FUSE_PARTS.index(part) if isinstance(part, str) else int(part)
+        ms, n = C.c_double(0), C.c_long(0)
+        self._check(self._L.canny_hip_fuse_profile_get(self._h, k, C.byref(ms), C.byref(n)), "fuse_profile_get")
+        return ms.value, n.value
+
+    def selftest_fuse_mean(self):
+        """The fuse kernels' rounded mean over every c = 1..255, s = 0..255 c, from the device: uint8 [255, FUSE_MEAN_ROW],
+        row c - 1, unused cells 0."""
+        out = np.zeros((255, FUSE_MEAN_ROW), np.uint8)
+        self._check(self._L.canny_hip_selftest_fuse_mean(self._h, _hp(out)), "selftest_fuse_mean")
+        return out
 
     def motion_profile_get(self, part: int) -> Tuple[float, int]:
         """(total ms, launch groups) of part 0 gather, 1 score, 2 refit (MOTION_PARTS)."""

@@ -413,6 +413,7 @@ struct canny_hip_ctx {
     DevBuf chamfer_cost, chamfer_scores, chamfer_ws, chamfer_dist2;
     int chamfer_route = 0; // 0 auto, 1 direct, 2 tiled
     int warp_route = 0;    // 0 auto, 1 direct, 2 tiled
+    int fuse_route = 0;    // the median of the temporal fusion: 0 auto, 1 registers, 2 passes
     int chamfer_chunk_mb = 0; // A/B and tests: budget of the score workspace in MiB, 0 = 256
     std::vector<canny_hip_chamfer_set *> chamfer_sets; // the sets created on this context and not yet destroyed
     // corners, per chunk of frames: the collected keys, the radix select's state, the maxima, histograms and counters
@@ -455,7 +456,8 @@ struct canny_hip_ctx {
     // circle fits (canny_hip_circle_fits_profile_get), then the four of the chamfer matching
     // (canny_hip_chamfer_profile_get), then the three of the contour shape measures (canny_hip_shapes_profile_get), then the two of the edge curves
     // (canny_hip_curves_profile_get), then the four of the corners (canny_hip_corners_profile_get), then the four of the descriptors and their matching
-    // (canny_hip_descriptors_profile_get), then the three of the motion estimate (canny_hip_motion_profile_get), then the two of the frame alignment (canny_hip_warp_profile_get).  The mask is a non-negative int option: bit 30 is the last it can
+    // (canny_hip_descriptors_profile_get), then the three of the motion estimate (canny_hip_motion_profile_get), then the two of the frame alignment (canny_hip_warp_profile_get), then the two of the temporal fusion
+    // (canny_hip_fuse_profile_get).  The mask is a non-negative int option: bit 30 is the last it can
     // carry, and the three polygon slots, the two edgel slots, the line-fit slot and the circle-fit slot behind them go by
     // it together
     static constexpr int kProfHough = CANNY_HIP_STAGE_END, kProfComponents = CANNY_HIP_STAGE_END + 3;
@@ -474,7 +476,8 @@ struct canny_hip_ctx {
     static constexpr int kProfDescriptors = kProfCorners + CANNY_HIP_CORNER_PARTS;
     static constexpr int kProfMotion = kProfDescriptors + CANNY_HIP_DESC_PARTS;
     static constexpr int kProfWarp = kProfMotion + CANNY_HIP_MOTION_PARTS;
-    static constexpr int kProfSlots = kProfWarp + CANNY_HIP_WARP_PARTS;
+    static constexpr int kProfFuse = kProfWarp + CANNY_HIP_WARP_PARTS;
+    static constexpr int kProfSlots = kProfFuse + CANNY_HIP_FUSE_PARTS;
     static constexpr int kProfLastBit = 30;
     static_assert(kProfPolygons == kProfLastBit && kProfEdgels > kProfLastBit,
                   "profile_stage_mask has one bit per slot up to the polygon parts; every slot from there on follows bit 30");
@@ -2186,6 +2189,7 @@ int canny_hip_ctx_get_option(const canny_hip_ctx *ctx, const char *name, int *va
     else if (!std::strcmp(name, "tune_hough_lds_kb")) *value = ctx->hough_lds_kb;
     else if (!std::strcmp(name, "chamfer_route")) *value = ctx->chamfer_route;
     else if (!std::strcmp(name, "warp_route")) *value = ctx->warp_route;
+    else if (!std::strcmp(name, "fuse_route")) *value = ctx->fuse_route;
     else if (!std::strcmp(name, "tune_chamfer_chunk_mb")) *value = ctx->chamfer_chunk_mb;
     else if (!std::strcmp(name, "batch_expand_threads")) *value = ctx->expand_pool ? ctx->expand_pool->size() : 0; // read-only
     else return CANNY_HIP_ERR_INVALID;
@@ -2213,6 +2217,7 @@ int canny_hip_ctx_set_option(canny_hip_ctx *ctx, const char *name, int value)
     else if (!std::strcmp(name, "hough_path") && value <= 2) ctx->hough_path = value;
     else if (!std::strcmp(name, "chamfer_route") && value <= 2) ctx->chamfer_route = value;
     else if (!std::strcmp(name, "warp_route") && value <= 2) ctx->warp_route = value;
+    else if (!std::strcmp(name, "fuse_route") && value <= 2) ctx->fuse_route = value;
     else if (!std::strcmp(name, "tune_chamfer_chunk_mb") && value <= 4096) ctx->chamfer_chunk_mb = value;
     else if (!std::strcmp(name, "tune_hough_lds_kb") && value <= kHoughLdsMax / 1024) ctx->hough_lds_kb = value;
     else if (!std::strcmp(name, "tune_batch_expand_threads") && value <= 64) {
@@ -6414,16 +6419,26 @@ int canny_hip_dev_warp_frames(canny_hip_ctx *ctx, const unsigned char *d_src, in
     return CANNY_HIP_OK;
 }
 
-int canny_hip_canny_align(canny_hip_ctx *ctx, const unsigned char *imgs, int n_frames, float sigma, int min_val, int max_val,
-                          int height, int width, int mode, int block, int k_q8, int quality_q16, long long min_response,
-                          int min_dist, int corners_max, int desc_options, int max_distance, int ratio_q8, int match_options,
-                          int model, int thr_q4, int hypotheses, unsigned seed, int interp, int border,
-                          unsigned char *aligned, long long *xforms, long long *motion, unsigned char *valid_bits)
+namespace {
+// What the alignment chain leaves on the device, all inside the staging block io[1]: canny_hip_canny_align brings it down,
+// canny_hip_canny_background goes on from it.  extra: extra_bytes behind the valid bits, 16-byte aligned.
+struct AlignDev {
+    unsigned char *aligned = nullptr, *valid = nullptr, *extra = nullptr;
+    long long *xf = nullptr, *motion = nullptr;
+    size_t frame_bytes = 0, valid_bytes = 0;
+    int n_pairs = 0;
+};
+
+// The chain of canny_hip_canny_align up to the warp.  xforms, motion: the caller's host buffers, only checked here.
+int align_on_device(canny_hip_ctx *ctx, const unsigned char *imgs, int n_frames, float sigma, int min_val, int max_val,
+                    int height, int width, int mode, int block, int k_q8, int quality_q16, long long min_response,
+                    int min_dist, int corners_max, int desc_options, int max_distance, int ratio_q8, int match_options,
+                    int model, int thr_q4, int hypotheses, unsigned seed, int interp, int border, long long *xforms,
+                    const long long *motion, bool want_valid, size_t extra_bytes, AlignDev &dev)
 {
-    int rc = bind(ctx);
-    if (rc) return rc;
+    int rc;
     // every check of the chained calls, before anything is uploaded or queued
-    if (!imgs || !aligned || !xforms || max_distance < 0 || max_distance > CANNY_HIP_DESC_BITS || ratio_q8 < 0 ||
+    if (!imgs || !xforms || max_distance < 0 || max_distance > CANNY_HIP_DESC_BITS || ratio_q8 < 0 ||
         ratio_q8 > 256 || (match_options & ~CANNY_HIP_MATCH_CROSS_CHECK) || model < CANNY_HIP_MOTION_TRANSLATION ||
         model > CANNY_HIP_MOTION_AFFINE || thr_q4 < 0 || thr_q4 > 4095 || hypotheses < 1 || ((uintptr_t)xforms & 7) ||
         ((uintptr_t)motion & 7))
@@ -6440,13 +6455,13 @@ int canny_hip_canny_align(canny_hip_ctx *ctx, const unsigned char *imgs, int n_f
     const size_t slots = (size_t)n_frames * corners_max, pslots = (size_t)n_pairs * corners_max;
     const size_t frame_bytes = npx(height, width, n_frames), valid_bytes = npx(height, (width + 7) / 8, n_frames);
     // one staging block: records | descriptors | motion records | transform records | meta | counts | matches | pair counts |
-    // aligned frames | valid bits
+    // aligned frames | valid bits | what the caller asked for behind them
     HIP_TRY(ctx, ctx->io[1].ensure(slots * (CANNY_HIP_CORNER_WORDS * sizeof(long long) +
                                             CANNY_HIP_DESC_WORDS * sizeof(unsigned long long) + sizeof(int)) +
                                    (size_t)n_pairs * CANNY_HIP_MOTION_WORDS * sizeof(long long) +
                                    (size_t)n_frames * CANNY_HIP_XFORM_WORDS * sizeof(long long) +
                                    (size_t)n_frames * sizeof(int) + pslots * CANNY_HIP_MATCH_WORDS * sizeof(int) +
-                                   (size_t)n_pairs * sizeof(int) + 16 + frame_bytes + valid_bytes));
+                                   (size_t)n_pairs * sizeof(int) + 16 + frame_bytes + valid_bytes + 16 + extra_bytes));
     long long *d_rec = (long long *)ctx->io[1].p;
     unsigned long long *d_desc = (unsigned long long *)(d_rec + slots * CANNY_HIP_CORNER_WORDS);
     long long *d_motion = (long long *)(d_desc + slots * CANNY_HIP_DESC_WORDS);
@@ -6455,6 +6470,9 @@ int canny_hip_canny_align(canny_hip_ctx *ctx, const unsigned char *imgs, int n_f
     int *d_matches = d_cnt + n_frames, *d_pc = d_matches + pslots * CANNY_HIP_MATCH_WORDS;
     unsigned char *d_aligned = (unsigned char *)(((uintptr_t)(d_pc + n_pairs) + 15) & ~(uintptr_t)15);
     unsigned char *d_valid = d_aligned + frame_bytes;
+    dev.aligned = d_aligned, dev.valid = d_valid, dev.xf = d_xf, dev.motion = d_motion, dev.n_pairs = n_pairs;
+    dev.frame_bytes = frame_bytes, dev.valid_bytes = valid_bytes;
+    dev.extra = (unsigned char *)(((uintptr_t)(d_valid + valid_bytes) + 15) & ~(uintptr_t)15);
     if ((rc = h2d(ctx, ctx->io[0], imgs, frame_bytes))) return rc;
     const unsigned char *d_gray = (const unsigned char *)ctx->io[0].p;
     if (n_pairs > 0) {
@@ -6473,16 +6491,32 @@ int canny_hip_canny_align(canny_hip_ctx *ctx, const unsigned char *imgs, int n_f
             return rc;
     }
     if ((rc = canny_hip_dev_compose_motion(ctx, n_pairs ? d_motion : nullptr, n_pairs, 0, d_xf))) return rc;
-    if ((rc = canny_hip_dev_warp_frames(ctx, d_gray, n_frames, height, width, d_xf, n_frames, height, width, interp, border,
-                                        d_aligned, valid_bits ? d_valid : nullptr)))
+    return canny_hip_dev_warp_frames(ctx, d_gray, n_frames, height, width, d_xf, n_frames, height, width, interp, border,
+                                     d_aligned, want_valid ? d_valid : nullptr);
+}
+} // namespace
+
+int canny_hip_canny_align(canny_hip_ctx *ctx, const unsigned char *imgs, int n_frames, float sigma, int min_val, int max_val,
+                          int height, int width, int mode, int block, int k_q8, int quality_q16, long long min_response,
+                          int min_dist, int corners_max, int desc_options, int max_distance, int ratio_q8, int match_options,
+                          int model, int thr_q4, int hypotheses, unsigned seed, int interp, int border,
+                          unsigned char *aligned, long long *xforms, long long *motion, unsigned char *valid_bits)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!aligned) return CANNY_HIP_ERR_INVALID;
+    AlignDev dev;
+    if ((rc = align_on_device(ctx, imgs, n_frames, sigma, min_val, max_val, height, width, mode, block, k_q8, quality_q16,
+                              min_response, min_dist, corners_max, desc_options, max_distance, ratio_q8, match_options, model,
+                              thr_q4, hypotheses, seed, interp, border, xforms, motion, valid_bits != nullptr, 0, dev)))
         return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(aligned, d_aligned, frame_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(xforms, d_xf, (size_t)n_frames * CANNY_HIP_XFORM_WORDS * sizeof(long long),
+    HIP_TRY(ctx, hipMemcpyAsync(aligned, dev.aligned, dev.frame_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(xforms, dev.xf, (size_t)n_frames * CANNY_HIP_XFORM_WORDS * sizeof(long long),
                                 hipMemcpyDeviceToHost, ctx->stream));
-    if (motion && n_pairs)
-        HIP_TRY(ctx, hipMemcpyAsync(motion, d_motion, (size_t)n_pairs * CANNY_HIP_MOTION_WORDS * sizeof(long long),
+    if (motion && dev.n_pairs)
+        HIP_TRY(ctx, hipMemcpyAsync(motion, dev.motion, (size_t)dev.n_pairs * CANNY_HIP_MOTION_WORDS * sizeof(long long),
                                     hipMemcpyDeviceToHost, ctx->stream));
-    if (valid_bits) HIP_TRY(ctx, hipMemcpyAsync(valid_bits, d_valid, valid_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    if (valid_bits) HIP_TRY(ctx, hipMemcpyAsync(valid_bits, dev.valid, dev.valid_bytes, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return CANNY_HIP_OK;
 }
@@ -6511,6 +6545,169 @@ int canny_hip_selftest_warp_plan(int n_out, int out_h, int out_w, unsigned long 
         return CANNY_HIP_ERR_INVALID;
     box[0] = warp_tile_footprint(xform, interp, src_h, src_w, out_h, out_w, tile_x, tile_y, box + 1) ? 1 : 0;
     return CANNY_HIP_OK;
+}
+
+// ---- temporal fusion of aligned frames and change masks (canny_fuse.hip) ---------------------------
+// canny_hip_fuse_frames and canny_hip_change_mask, the rules in plain C++, live in canny_fuse_host.cpp.
+
+namespace {
+// the stack both calls read
+int fuse_stack_check(int n_frames, int h, int w)
+{
+    if (n_frames < 1 || h < 1 || w < 1) return CANNY_HIP_ERR_INVALID;
+    if (h > 32768 || w > 32768 || (long long)h * w >= (1ll << 31) || n_frames > 65535) return CANNY_HIP_ERR_UNSUPPORTED;
+    return CANNY_HIP_OK;
+}
+
+// every check of the fusion but the pointers
+int fuse_check(int n_frames, int h, int w, int group_len, int group_step, int op, int fill, int min_count)
+{
+    if (n_frames < 1 || h < 1 || w < 1 || group_len < 1 || group_len > CANNY_HIP_FUSE_MAX_GROUP || group_len > n_frames ||
+        group_step < 1 || op < CANNY_HIP_FUSE_MEAN || op > CANNY_HIP_FUSE_MAX || fill < 0 || fill > 255 || min_count < 1 ||
+        min_count > 255)
+        return CANNY_HIP_ERR_INVALID;
+    return fuse_stack_check(n_frames, h, w);
+}
+
+// ... and of the change mask
+int mask_check(int n_frames, int h, int w, int frames_per_background, int thr, int min_count)
+{
+    if (n_frames < 1 || h < 1 || w < 1 || frames_per_background < 1 || thr < 0 || thr > 255 || min_count < 1 || min_count > 255)
+        return CANNY_HIP_ERR_INVALID;
+    return fuse_stack_check(n_frames, h, w);
+}
+
+bool opt_overlap(const void *a, size_t na, const void *b, size_t nb) { return a && b && ranges_overlap(a, na, b, nb); }
+} // namespace
+
+int canny_hip_dev_fuse_frames(canny_hip_ctx *ctx, const unsigned char *d_frames, const unsigned char *d_valid_bits,
+                              int n_frames, int h, int w, int group_len, int group_step, int op, int fill, int min_count,
+                              unsigned char *d_fused, unsigned char *d_count)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!d_frames || !d_fused) return CANNY_HIP_ERR_INVALID;
+    if ((rc = fuse_check(n_frames, h, w, group_len, group_step, op, fill, min_count))) return rc;
+    const int n_groups = (n_frames - group_len) / group_step + 1;
+    const size_t in_bytes = npx(h, w, n_frames), vbytes = npx(h, (w + 7) / 8, n_frames), out_bytes = npx(h, w, n_groups);
+    if (opt_overlap(d_frames, in_bytes, d_fused, out_bytes) || opt_overlap(d_frames, in_bytes, d_count, out_bytes) ||
+        opt_overlap(d_valid_bits, vbytes, d_fused, out_bytes) || opt_overlap(d_valid_bits, vbytes, d_count, out_bytes) ||
+        opt_overlap(d_fused, out_bytes, d_count, out_bytes))
+        return CANNY_HIP_ERR_INVALID;
+    if ((rc = finish_pending(ctx))) return rc;
+    StageTimer tm(ctx, canny_hip_ctx::kProfFuse + CANNY_HIP_FUSE_PART_FUSE);
+    HIP_TRY(ctx, launch_fuse_frames(d_frames, d_valid_bits, n_frames, h, w, group_len, group_step, op, fill, min_count,
+                                    ctx->fuse_route, d_fused, d_count, ctx->stream));
+    return CANNY_HIP_OK;
+}
+
+int canny_hip_dev_change_mask(canny_hip_ctx *ctx, const unsigned char *d_frames, const unsigned char *d_valid_bits,
+                              int n_frames, int h, int w, const unsigned char *d_background,
+                              const unsigned char *d_bg_count, int frames_per_background, int thr, int min_count,
+                              unsigned char *d_mask_bits, long long *d_changed)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!d_frames || !d_background || !d_mask_bits || ((uintptr_t)d_changed & 7)) return CANNY_HIP_ERR_INVALID;
+    if ((rc = mask_check(n_frames, h, w, frames_per_background, thr, min_count))) return rc;
+    const size_t n_bg = ((size_t)n_frames + frames_per_background - 1) / frames_per_background;
+    const size_t in_bytes = npx(h, w, n_frames), vbytes = npx(h, (w + 7) / 8, n_frames), bg_bytes = (size_t)h * w * n_bg;
+    const size_t ch_bytes = (size_t)n_frames * sizeof(long long);
+    if (opt_overlap(d_frames, in_bytes, d_mask_bits, vbytes) || opt_overlap(d_valid_bits, vbytes, d_mask_bits, vbytes) ||
+        opt_overlap(d_background, bg_bytes, d_mask_bits, vbytes) || opt_overlap(d_bg_count, bg_bytes, d_mask_bits, vbytes) ||
+        opt_overlap(d_frames, in_bytes, d_changed, ch_bytes) || opt_overlap(d_valid_bits, vbytes, d_changed, ch_bytes) ||
+        opt_overlap(d_background, bg_bytes, d_changed, ch_bytes) || opt_overlap(d_bg_count, bg_bytes, d_changed, ch_bytes) ||
+        opt_overlap(d_mask_bits, vbytes, d_changed, ch_bytes))
+        return CANNY_HIP_ERR_INVALID;
+    if ((rc = finish_pending(ctx))) return rc;
+    StageTimer tm(ctx, canny_hip_ctx::kProfFuse + CANNY_HIP_FUSE_PART_MASK);
+    HIP_TRY(ctx, launch_change_mask(d_frames, d_valid_bits, n_frames, h, w, d_background, d_bg_count, frames_per_background,
+                                    thr, min_count, d_mask_bits, (unsigned long long *)d_changed, ctx->stream));
+    return CANNY_HIP_OK;
+}
+
+int canny_hip_canny_background(canny_hip_ctx *ctx, const unsigned char *imgs, int n_frames, float sigma, int min_val,
+                               int max_val, int height, int width, int mode, int block, int k_q8, int quality_q16,
+                               long long min_response, int min_dist, int corners_max, int desc_options, int max_distance,
+                               int ratio_q8, int match_options, int model, int thr_q4, int hypotheses, unsigned seed,
+                               int interp, int border, int op, int fill, int min_count, int thr, unsigned char *background,
+                               unsigned char *count, unsigned char *mask_bits, long long *changed, long long *xforms)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!background || ((uintptr_t)changed & 7)) return CANNY_HIP_ERR_INVALID;
+    // one window over the whole batch: group_len = n_frames
+    if ((rc = fuse_check(n_frames, height, width, n_frames, n_frames, op, fill, min_count))) return rc;
+    if ((rc = mask_check(n_frames, height, width, n_frames, thr, min_count))) return rc;
+    const size_t plane = (size_t)height * width, mask_bytes = npx(height, (width + 7) / 8, n_frames);
+    const size_t ch_bytes = (size_t)n_frames * sizeof(long long), plane16 = (plane + 15) & ~(size_t)15;
+    AlignDev dev;
+    // behind the valid bits: the counts of the frames | the fused plane | its counts | the masks
+    if ((rc = align_on_device(ctx, imgs, n_frames, sigma, min_val, max_val, height, width, mode, block, k_q8, quality_q16,
+                              min_response, min_dist, corners_max, desc_options, max_distance, ratio_q8, match_options, model,
+                              thr_q4, hypotheses, seed, interp, border, xforms, nullptr, true,
+                              ((ch_bytes + 15) & ~(size_t)15) + 2 * plane16 + mask_bytes, dev)))
+        return rc;
+    long long *d_changed = (long long *)dev.extra;
+    unsigned char *d_bg = dev.extra + ((ch_bytes + 15) & ~(size_t)15), *d_cnt = d_bg + plane16, *d_mask = d_cnt + plane16;
+    if ((rc = canny_hip_dev_fuse_frames(ctx, dev.aligned, dev.valid, n_frames, height, width, n_frames, n_frames, op, fill,
+                                        min_count, d_bg, d_cnt)))
+        return rc;
+    if (mask_bits || changed) {
+        if ((rc = canny_hip_dev_change_mask(ctx, dev.aligned, dev.valid, n_frames, height, width, d_bg, d_cnt, n_frames, thr,
+                                            min_count, d_mask, changed ? d_changed : nullptr)))
+            return rc;
+    }
+    HIP_TRY(ctx, hipMemcpyAsync(background, d_bg, plane, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(xforms, dev.xf, (size_t)n_frames * CANNY_HIP_XFORM_WORDS * sizeof(long long),
+                                hipMemcpyDeviceToHost, ctx->stream));
+    if (count) HIP_TRY(ctx, hipMemcpyAsync(count, d_cnt, plane, hipMemcpyDeviceToHost, ctx->stream));
+    if (mask_bits) HIP_TRY(ctx, hipMemcpyAsync(mask_bits, d_mask, mask_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    if (changed) HIP_TRY(ctx, hipMemcpyAsync(changed, d_changed, ch_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return CANNY_HIP_OK;
+}
+
+int canny_hip_fuse_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches)
+{
+    if (part < 0 || part >= CANNY_HIP_FUSE_PARTS || !total_ms || !launches) return CANNY_HIP_ERR_INVALID;
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if ((rc = profile_collect(ctx))) return rc;
+    *total_ms = ctx->total_ms[canny_hip_ctx::kProfFuse + part];
+    *launches = ctx->launches[canny_hip_ctx::kProfFuse + part];
+    return CANNY_HIP_OK;
+}
+
+// Host-only: the launch plans of the two capped launches of the temporal fusion.
+int canny_hip_selftest_fuse_plan(int which, int n_frames, int h, int w, int group_len, int group_step, unsigned long long *out)
+{
+    if (!out) return CANNY_HIP_ERR_INVALID;
+    LaunchPlan p;
+    if (which == CANNY_HIP_FUSE_PART_FUSE) {
+        if (fuse_check(n_frames, h, w, group_len, group_step, 0, 0, 1)) return CANNY_HIP_ERR_INVALID;
+        p = plan_fuse_tiles((n_frames - group_len) / group_step + 1, h, w);
+        p.aux = fuse_median_route(group_len, 0);
+    } else if (which == CANNY_HIP_FUSE_PART_MASK) {
+        if (fuse_stack_check(n_frames, h, w)) return CANNY_HIP_ERR_INVALID;
+        p = plan_fuse_tiles(n_frames, h, w);
+    } else {
+        return CANNY_HIP_ERR_INVALID;
+    }
+    out[0] = p.units, out[1] = p.per_group, out[2] = p.grid, out[3] = p.trips(), out[4] = (unsigned long long)p.aux;
+    return CANNY_HIP_OK;
+}
+
+int canny_hip_selftest_fuse_mean(canny_hip_ctx *ctx, unsigned char *out)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!out) return CANNY_HIP_ERR_INVALID;
+    if ((rc = finish_pending(ctx))) return rc;
+    const size_t bytes = (size_t)255 * CANNY_HIP_FUSE_MEAN_ROW;
+    HIP_TRY(ctx, ctx->io[1].ensure(bytes));
+    HIP_TRY(ctx, launch_fuse_mean_table((uint8_t *)ctx->io[1].p, ctx->stream));
+    return d2h_sync(ctx, out, ctx->io[1].p, bytes);
 }
 
 } // extern "C"

@@ -840,6 +840,23 @@ hipError_t launch_warp_frames(const uint8_t *src, int n_src, int src_h, int src_
                               int out_h, int out_w, int interp, int border, int route, uint8_t *out, uint8_t *valid,
                               hipStream_t stream);
 
+// ---- temporal fusion of aligned frames and change masks (canny_fuse.hip) ----------------
+// fuse: the n_groups * ceil(h / 16) * ceil(w / 64) output tiles, one per workgroup and trip; the change mask: the same with
+// its n_frames.  (Reported by canny_hip_selftest_fuse_plan, not by a kind.)
+LaunchPlan plan_fuse_tiles(int n_planes, int h, int w);
+// The route a MEDIAN of group_len frames takes under the option value `route` (0 automatic, 1 registers, 2 passes): 1 or 2.
+int fuse_median_route(int group_len, int route);
+// Every byte of fused [n_groups][h][w] and (count != NULL) of count.  valid may be NULL: every pixel is valid.
+hipError_t launch_fuse_frames(const uint8_t *frames, const uint8_t *valid, int n_frames, int h, int w, int group_len,
+                              int group_step, int op, int fill, int min_count, int route, uint8_t *fused, uint8_t *count,
+                              hipStream_t stream);
+// Every byte of mask [n_frames][h][ceil(w / 8)]; changed (may be NULL, 8-byte aligned) is zeroed on the stream, then summed.
+hipError_t launch_change_mask(const uint8_t *frames, const uint8_t *valid, int n_frames, int h, int w, const uint8_t *bg,
+                              const uint8_t *bg_count, int per_bg, int thr, int min_count, uint8_t *mask,
+                              unsigned long long *changed, hipStream_t stream);
+// canny_hip_selftest_fuse_mean: the kernels' rounded mean over every (c, s) into table [255][65026], unused cells 0.
+hipError_t launch_fuse_mean_table(uint8_t *table, hipStream_t stream);
+
 // ---- measurement aid ------------------------------------------------------------------------
 // Plain device copy of nbytes (multiple of 16; both pointers 16-byte aligned): what a 1:1 read/write stream reaches.
 hipError_t launch_probe_copy(const void *src, void *dst, size_t nbytes, hipStream_t stream, const LaunchEvents &ev = {});

@@ -52,7 +52,7 @@
 extern "C" {
 #endif
 
-#define CANNY_HIP_VERSION 2200       /* 0.22.0: + frame alignment: the motions chained, frames warped */
+#define CANNY_HIP_VERSION 2300       /* 0.23.0: + temporal fusion of aligned frames and change masks (0.22.0: + frame alignment) */
 /* 0.21.0: + frame-to-frame motion from the corner matches (RANSAC) */
 /* 0.20.0: + corner descriptors and Hamming matching between frames */
 /* 0.19.0: + corners: Harris / Shi-Tomasi on the smoothed plane */
@@ -2090,6 +2090,104 @@ int canny_hip_canny_align(canny_hip_ctx *ctx, const unsigned char *imgs, int n_f
                           int model, int thr_q4, int hypotheses, unsigned seed, int interp, int border,
                           unsigned char *aligned, long long *xforms, long long *motion, unsigned char *valid_bits);
 
+/* ---- temporal fusion of aligned frames and change masks -------------------------------------------------------------------
+ * What the alignment is for: a per-pixel reduction over the time axis of a stack of u8 frames that honours the valid bits the
+ * warp writes (average, median background, extremes), and a per-frame change mask against the fused plane, written in the
+ * packed bit-map layout that canny_hip_dev_components_bits, _edt_bits, _contours_bits and _points_from_bits take -- so a
+ * video batch goes to "what moved in each frame, as labelled components" on one stream, without a download.  All integers, no
+ * floats, no atomics whose order could matter: the same bytes on every run and every machine.  tests/fuse_rule.py restates
+ * the rule in numpy and Python ints, csrc/canny_fuse_host.cpp in plain C++.
+ * THE RULE:
+ *   Fuse.  frames [n_frames][h][w] u8; valid_bits [n_frames][h][(w + 7) / 8], rows MSB-first (the layout the warp writes);
+ *     the PAD BITS OF THE INPUT ARE IGNORED; valid_bits == NULL means every pixel is valid.
+ *     Windows: window g holds the frames g * group_step .. g * group_step + group_len - 1;
+ *       n_groups = (n_frames - group_len) / group_step + 1;  1 <= group_len <= min(n_frames, 255), group_step >= 1.
+ *       group_step = group_len: disjoint groups; group_step = 1: a sliding window; group_len = n_frames: one background.
+ *       Frames behind the last window belong to no window and are not read.
+ *     Per output pixel: c = the number of valid frames of the window (<= 255: a byte), v_0 <= .. <= v_{c-1} their values
+ *       sorted, s their sum (<= 255 * 255 = 65025).
+ *       CANNY_HIP_FUSE_MEAN   = 0: (2 s + c) / (2 c), integer division: rounds half up (2 s + c <= 130305 < 2^17)
+ *       CANNY_HIP_FUSE_MEDIAN = 1: v_{(c - 1) >> 1}, the lower median
+ *       CANNY_HIP_FUSE_MIN    = 2: v_0
+ *       CANNY_HIP_FUSE_MAX    = 3: v_{c-1}
+ *     If c < min_count (1 <= min_count <= 255) the pixel is `fill` (0..255).  fused [n_groups][h][w] u8 is always written in
+ *     full; count [n_groups][h][w] u8 receives c -- the true count, also where `fill` was written -- if the pointer is not
+ *     NULL.
+ *   Change mask.  Frame f is compared with background plane f / frames_per_background (frames_per_background >= 1;
+ *     n_background = ceil(n_frames / frames_per_background); frames_per_background >= n_frames: one background for all
+ *     frames; frames_per_background = group_len pairs with disjoint groups).  Bit (f, y, x) is 1 iff
+ *       the frame's valid bit is set, or valid_bits is NULL;  and
+ *       bg_count is NULL or bg_count[f / frames_per_background][y][x] >= min_count;  and
+ *       |frame - background| > thr, 0 <= thr <= 255.
+ *     mask_bits [n_frames][h][(w + 7) / 8]: the layout of canny_hip_dev_canny_bits -- rows MSB-first, padded to bytes, PAD
+ *     BITS WRITTEN 0, every byte written.  changed[f] (one long long per frame, the pointer may be NULL) is the number of set
+ *     bits of frame f: an integer sum, so it does not depend on order; it is fully written by the call, and not touched by a
+ *     refused one.
+ *   Limits: h, w in 1..32768, a plane < 2^31 pixels, at most 65535 frames; above: CANNY_HIP_ERR_UNSUPPORTED.  Bad ranges
+ *     (group_len, group_step, op, fill, min_count, frames_per_background, thr, counts < 1), NULL mandatory pointers, an output
+ *     that overlaps an input or another output, a `changed` buffer that is not 8-byte aligned: CANNY_HIP_ERR_INVALID.  Both
+ *     before anything is queued; nothing is written.
+ *   Kernels (csrc/canny_fuse.hip): one workgroup of 256 per 64 x 16 output tile and trip of a grid capped at 4096; a lane owns
+ *     four adjacent pixels, loads one 32-bit word per frame and stores one word (byte paths where w is no multiple of 4, the
+ *     buffer is not 4-byte aligned or the run crosses the row end); every output byte has one writer.  The mean's division
+ *     is a multiplication: q = (n * M(c)) >> 32 with n = 2 s + c and M(c) = floor((2^32 - 1) / (2 c)) + 1 from a table of 256
+ *     words in LDS; M(c) * 2c = 2^32 + e with 0 <= e < 2c <= 510, and n * e < 2^27 < 2^32, so q is the exact quotient for every
+ *     (s, c) of the domain -- canny_hip_selftest_fuse_mean runs that helper over all of them on the device.
+ *   The context option "fuse_route" chooses how the MEDIAN is selected: 0 automatic, 1 registers (group_len <= 32: the window
+ *     is read once and stays in registers as 16-bit lanes, 0x100 + v for an invalid sample so that it sorts behind every valid
+ *     one; an odd-even merge sorting network of packed 16-bit min/max over 8, 16 or 32 slots, two pixels an instruction; the
+ *     rank is picked by compares, no indexed registers), 2 passes (any group_len: a count pass and eight passes of a binary
+ *     radix select that re-read the window).  Route 1 with group_len > 32 runs the passes.  All routes give the same bytes;
+ *     the other ops take one pass under every route.
+ * The two parts are timed by canny_hip_fuse_profile_get (CANNY_HIP_FUSE_PART_*); with "profile_stage_mask" they go by bit 30
+ *   like every part behind the polygons.
+ * Not covered -- follow-ups: colour or s16 planes; a running background with exponential update; morphology on the mask; a
+ * grammar of Main; fusion through the batch pipeline or the multi-GPU sharder. */
+#define CANNY_HIP_FUSE_MAX_GROUP 255
+#define CANNY_HIP_FUSE_MEAN_ROW 65026 /* canny_hip_selftest_fuse_mean: cells of a row, s = 0 .. 255 * 255 */
+enum canny_hip_fuse_op {
+    CANNY_HIP_FUSE_MEAN = 0,
+    CANNY_HIP_FUSE_MEDIAN = 1,
+    CANNY_HIP_FUSE_MIN = 2,
+    CANNY_HIP_FUSE_MAX = 3
+};
+enum canny_hip_fuse_part {
+    CANNY_HIP_FUSE_PART_FUSE = 0, /* the reduction over the windows */
+    CANNY_HIP_FUSE_PART_MASK = 1, /* the change masks and their counts */
+    CANNY_HIP_FUSE_PARTS = 2
+};
+/* d_frames: n_frames * h * w bytes; d_valid_bits: n_frames * h * ((w + 7) / 8) bytes or NULL; d_fused and d_count (may be
+ * NULL): n_groups * h * w bytes.  Asynchronous. */
+int canny_hip_dev_fuse_frames(canny_hip_ctx *ctx, const unsigned char *d_frames, const unsigned char *d_valid_bits,
+                              int n_frames, int h, int w, int group_len, int group_step, int op, int fill, int min_count,
+                              unsigned char *d_fused, unsigned char *d_count);
+/* Host-only, needs no device: the same rule on host buffers. */
+int canny_hip_fuse_frames(const unsigned char *frames, const unsigned char *valid_bits, int n_frames, int h, int w,
+                          int group_len, int group_step, int op, int fill, int min_count, unsigned char *fused,
+                          unsigned char *count);
+/* d_background and d_bg_count (may be NULL): ceil(n_frames / frames_per_background) * h * w bytes; d_mask_bits: n_frames * h *
+ * ((w + 7) / 8) bytes; d_changed: n_frames long long, may be NULL.  Asynchronous. */
+int canny_hip_dev_change_mask(canny_hip_ctx *ctx, const unsigned char *d_frames, const unsigned char *d_valid_bits,
+                              int n_frames, int h, int w, const unsigned char *d_background,
+                              const unsigned char *d_bg_count, int frames_per_background, int thr, int min_count,
+                              unsigned char *d_mask_bits, long long *d_changed);
+/* Host-only, needs no device: the same rule on host buffers. */
+int canny_hip_change_mask(const unsigned char *frames, const unsigned char *valid_bits, int n_frames, int h, int w,
+                          const unsigned char *background, const unsigned char *bg_count, int frames_per_background, int thr,
+                          int min_count, unsigned char *mask_bits, long long *changed);
+/* Host buffers, synchronous: the whole chain of canny_hip_canny_align on the device (its arguments up to `border`), then all
+ * n_frames aligned frames fused into one plane (group_len = n_frames, so n_frames <= 255; more: CANNY_HIP_ERR_INVALID) with
+ * the alignment's valid bits, then the change masks of the aligned frames against that plane (with its counts and
+ * min_count).  background (height * width bytes) and xforms (n_frames * 8 long long) come down and, where the pointer is not
+ * NULL, count (height * width bytes), mask_bits (n_frames * height * ((width + 7) / 8) bytes) and changed (n_frames long
+ * long).  The aligned frames and their valid bits stay in a workspace of the context. */
+int canny_hip_canny_background(canny_hip_ctx *ctx, const unsigned char *imgs, int n_frames, float sigma, int min_val,
+                               int max_val, int height, int width, int mode, int block, int k_q8, int quality_q16,
+                               long long min_response, int min_dist, int corners_max, int desc_options, int max_distance,
+                               int ratio_q8, int match_options, int model, int thr_q4, int hypotheses, unsigned seed,
+                               int interp, int border, int op, int fill, int min_count, int thr, unsigned char *background,
+                               unsigned char *count, unsigned char *mask_bits, long long *changed, long long *xforms);
+
 /* ---- per-stage HIP-event timing (events are recorded on the launch stream) ----------------- */
 int canny_hip_profile_enable(canny_hip_ctx *ctx, int on);
 int canny_hip_profile_reset(canny_hip_ctx *ctx);
@@ -2130,6 +2228,8 @@ int canny_hip_descriptors_profile_get(canny_hip_ctx *ctx, int part, double *tota
 int canny_hip_motion_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches);
 /* ... and for the two parts of the frame alignment (CANNY_HIP_WARP_PART_*). */
 int canny_hip_warp_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches);
+/* ... and for the two parts of the temporal fusion (CANNY_HIP_FUSE_PART_*). */
+int canny_hip_fuse_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches);
 
 /* ---- self-test hooks used by the GPU test-suite -------------------------------------------- */
 /* Runs the DEVICE magnitude / angle-bin functions over every (gx,gy) in [-lim,lim]^2 and writes
@@ -2308,6 +2408,16 @@ int canny_hip_selftest_motion_plan(int which, unsigned long long n_pairs, int hy
  * not usable), then the clipped footprint x0, y0, x1, y1 (inclusive; x1 < x0 or y1 < y0: empty). */
 int canny_hip_selftest_warp_plan(int n_out, int out_h, int out_w, unsigned long long *out, const long long *xform, int src_h,
                                  int src_w, int interp, int tile_x, int tile_y, int *box);
+/* Host-only, the same five outputs for the two capped launches of the temporal fusion (no kind above): which = a
+ * canny_hip_fuse_part.  FUSE: items = n_groups * ceil(h / 16) * ceil(w / 64) output tiles with n_groups = (n_frames -
+ * group_len) / group_step + 1; MASK: items = n_frames * ceil(h / 16) * ceil(w / 64) (group_len and group_step are not read);
+ * one tile per workgroup of 256 and trip, at most 4096 workgroups.  The fifth word of FUSE is the route that automatic takes
+ * for a MEDIAN of group_len frames (1 registers, 2 passes).  Arguments within the limits of the calls. */
+int canny_hip_selftest_fuse_plan(int which, int n_frames, int h, int w, int group_len, int group_step,
+                                 unsigned long long *out);
+/* Runs the fuse kernels' own device helper for the rounded mean over every pair c = 1..255, s = 0..255 c, and writes the
+ * bytes to host memory as a table [255][CANNY_HIP_FUSE_MEAN_ROW]: out[(c - 1) * 65026 + s]; unused cells are 0. */
+int canny_hip_selftest_fuse_mean(canny_hip_ctx *ctx, unsigned char *out);
 
 #ifdef __cplusplus
 }
