@@ -145,6 +145,8 @@ EXPORTS = (
     "canny_hip_dev_fuse_frames", "canny_hip_fuse_frames", "canny_hip_dev_change_mask", "canny_hip_change_mask",
     "canny_hip_canny_background", "canny_hip_fuse_profile_get", "canny_hip_selftest_fuse_plan",
     "canny_hip_selftest_fuse_mean",
+    "canny_hip_dev_morph_bits", "canny_hip_dev_canny_morph", "canny_hip_canny_morph", "canny_hip_morph_bits",
+    "canny_hip_morph_element", "canny_hip_selftest_morph_plan", "canny_hip_morph_profile_get",
 )
 
 _lib: Optional[C.CDLL] = None
@@ -396,6 +398,13 @@ def load() -> C.CDLL:
         "canny_hip_fuse_profile_get": ([p, i, C.POINTER(C.c_double), C.POINTER(C.c_long)], i),
         "canny_hip_selftest_fuse_plan": ([i, i, i, i, i, i, p], i),
         "canny_hip_selftest_fuse_mean": ([p, p], i),
+        "canny_hip_dev_morph_bits": ([p, p, i, i, i, i, p, i, i, i, i, p, p], i),
+        "canny_hip_dev_canny_morph": ([p, i, i, i, i, p, i, i, i, i, p, p], i),
+        "canny_hip_canny_morph": ([p, p, i, f, i, i, i, i, i, p, i, i, i, i, p, p], i),
+        "canny_hip_morph_bits": ([p, i, i, i, i, p, i, i, i, i, p, p], i),
+        "canny_hip_morph_element": ([i, i, i, p], i),
+        "canny_hip_selftest_morph_plan": ([i, i, i, i, i, p], i),
+        "canny_hip_morph_profile_get": ([p, i, C.POINTER(C.c_double), C.POINTER(C.c_long)], i),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -1297,6 +1306,60 @@ def fuse_plan(which, n_frames: int, h: int, w: int, group_len: int = 1, group_st
     st = load().canny_hip_selftest_fuse_plan(k, int(n_frames), int(h), int(w), int(group_len), int(group_step), _hp(out))
     if st:
         raise CannyHipError(st, "selftest_fuse_plan")
+    return LaunchPlan(*(int(v) for v in out))
+
+
+# ---- binary morphology on packed bit maps ------------------------------------------------------------
+MORPH_ERODE, MORPH_DILATE, MORPH_OPEN, MORPH_CLOSE, MORPH_GRADIENT, MORPH_TOPHAT, MORPH_BLACKHAT = range(7)
+MORPH_OPS = ("erode", "dilate", "open", "close", "gradient", "tophat", "blackhat")
+MORPH_RECT, MORPH_CROSS, MORPH_ELLIPSE = 0, 1, 2
+MORPH_SHAPES = ("rect", "cross", "ellipse")
+MORPH_BORDER_ZERO, MORPH_BORDER_ONE, MORPH_BORDER_NEUTRAL = 0, 1, 2
+MORPH_ROUTE_AUTO, MORPH_ROUTE_GENERAL, MORPH_ROUTE_SEPARABLE = 0, 1, 2
+MORPH_MAX_EXTENT, MORPH_MAX_ITERATIONS = 31, 16
+
+
+def morph_element(shape: int, kw: int, kh: Optional[int] = None):
+    """Host-only: the rows of a RECT, CROSS or ELLIPSE element of kw x kh (kh defaults to kw) as uint32 [kh]; bit i of row j
+    is the offset (i - kw // 2, j - kh // 2)."""
+    kh = kw if kh is None else kh
+    rows = np.zeros(max(int(kh), 1), np.uint32)
+    st = load().canny_hip_morph_element(int(shape), int(kw), int(kh), _hp(rows))
+    if st:
+        raise CannyHipError(st, "morph_element")
+    return rows
+
+
+def _morph_rows(rows, kh: int):
+    r = np.ascontiguousarray(rows, dtype=np.uint32).reshape(-1)
+    if r.size != kh:
+        raise ValueError("expected kh element rows")
+    return r
+
+
+def morph_bits(bits, w: int, op: int, rows, kw: int, kh: int, border: int = MORPH_BORDER_NEUTRAL, iterations: int = 1):
+    """Host-only, needs no GPU: the operator on bit maps uint8 [n_frames, H, ceil(w / 8)] (rows MSB-first; pad bits ignored)
+    -> (bit maps of the same shape with pad bits 0, counts int64 [n_frames])."""
+    a = np.ascontiguousarray(bits, dtype=np.uint8)
+    if a.ndim != 3 or a.shape[2] != (int(w) + 7) // 8:
+        raise ValueError("expected bit maps uint8 [n_frames, H, ceil(w / 8)]")
+    n, h, _ = a.shape
+    r = _morph_rows(rows, kh)
+    out, counts = np.zeros_like(a), np.zeros(n, np.int64)
+    st = load().canny_hip_morph_bits(_hp(a), n, h, int(w), int(op), _hp(r), int(kw), int(kh), int(border), int(iterations),
+                                     _hp(out), _hp(counts))
+    if st:
+        raise CannyHipError(st, "morph_bits")
+    return out, counts
+
+
+def morph_plan(n_frames: int, h: int, w: int, kw: int = 3, kh: int = 3):
+    """Host-only: the LaunchPlan of one primitive step of the morphology (one tile of 8 words x 64 rows per workgroup and
+    trip); aux = the route automatic takes for a full rectangle of kw x kh (1 general, 2 separable)."""
+    out = np.zeros(5, np.uint64)
+    st = load().canny_hip_selftest_morph_plan(int(n_frames), int(h), int(w), int(kw), int(kh), _hp(out))
+    if st:
+        raise CannyHipError(st, "selftest_morph_plan")
     return LaunchPlan(*(int(v) for v in out))
 
 
@@ -2839,6 +2902,45 @@ class Context:
         out = np.zeros((255, FUSE_MEAN_ROW), np.uint8)
         self._check(self._L.canny_hip_selftest_fuse_mean(self._h, _hp(out)), "selftest_fuse_mean")
         return out
+
+    # ---- binary morphology on packed bit maps --------------------------------------------------
+    def dev_morph_bits(self, d_bits: int, n_frames: int, h: int, w: int, op: int, rows, kw: int, kh: int, d_out_bits: int,
+                       d_counts: int = 0, border: int = MORPH_BORDER_NEUTRAL, iterations: int = 1):
+        """The operator on device bit maps [n_frames][h][ceil(w / 8)] into d_out_bits and, if given, the set bits of each
+        output frame as int64 at d_counts.  rows: the element's kh words (host).  Asynchronous."""
+        v = C.c_void_p
+        r = _morph_rows(rows, kh)
+        self._check(self._L.canny_hip_dev_morph_bits(self._h, v(d_bits or None), n_frames, h, w, op, _hp(r), kw, kh, border,
+                                                     iterations, v(d_out_bits or None), v(d_counts or None)), "dev_morph_bits")
+
+    def dev_canny_morph(self, n_frames: int, h: int, w: int, op: int, rows, kw: int, kh: int, d_out_bits: int,
+                        d_counts: int = 0, border: int = MORPH_BORDER_NEUTRAL, iterations: int = 1):
+        """The operator on the strong bit-plane the preceding dev_canny of the same geometry left in the context.
+        Asynchronous."""
+        v = C.c_void_p
+        r = _morph_rows(rows, kh)
+        self._check(self._L.canny_hip_dev_canny_morph(self._h, n_frames, h, w, op, _hp(r), kw, kh, border, iterations,
+                                                      v(d_out_bits or None), v(d_counts or None)), "dev_canny_morph")
+
+    def canny_morph(self, imgs, sigma: float, min_val: int, max_val: int, op: int, rows, kw: int, kh: int,
+                    border: int = MORPH_BORDER_NEUTRAL, iterations: int = 1):
+        """Upload, canny and the operator on the finished map, all on the GPU: imgs (N, H, W) uint8 -> (bit maps uint8 [N, H,
+        ceil(W / 8)], counts int64 [N])."""
+        a = np.ascontiguousarray(imgs, dtype=np.uint8)
+        if a.ndim != 3:
+            raise ValueError("expected uint8 [n_frames, H, W]")
+        n, h, w = a.shape
+        r = _morph_rows(rows, kh)
+        out, counts = np.zeros((n, h, (w + 7) // 8), np.uint8), np.zeros(n, np.int64)
+        self._check(self._L.canny_hip_canny_morph(self._h, _hp(a), n, sigma, min_val, max_val, h, w, op, _hp(r), kw, kh,
+                                                  border, iterations, _hp(out), _hp(counts)), "canny_morph")
+        return out, counts
+
+    def morph_profile(self, part: int = 0) -> Tuple[float, int]:
+        """(total ms, launch groups) of part 0, all primitive steps of the morphology calls."""
+        ms, n = C.c_double(0), C.c_long(0)
+        self._check(self._L.canny_hip_morph_profile_get(self._h, int(part), C.byref(ms), C.byref(n)), "morph_profile_get")
+        return ms.value, n.value
 
     def motion_profile_get(self, part: int) -> Tuple[float, int]:
         """(total ms, launch groups) of part 0 gather, 1 score, 2 refit (MOTION_PARTS)."""

@@ -423,6 +423,9 @@ struct canny_hip_ctx {
     std::vector<int> desc_pairs; // the validated pairs of the last match call: what its upload reads
     // motion estimate: the compacted correspondences and their slots, the inlier counts per (pair, hypothesis), m, the pairs
     DevBuf motion_ws;
+    // binary morphology: the two intermediate bit maps of a call of more than one primitive step, back to back
+    DevBuf morph_ws;
+    int morph_route = 0;   // 0 auto, 1 general, 2 separable (full rectangles)
     std::vector<int> motion_pairs; // the validated pairs of the last motion call: what its upload reads
     DevBuf plane_s, plane_c, stamps, flags; // hysteresis bit-planes / scheduling words
     DevBuf io[4];     // staging for the host-pointer stage functions
@@ -477,7 +480,8 @@ struct canny_hip_ctx {
     static constexpr int kProfMotion = kProfDescriptors + CANNY_HIP_DESC_PARTS;
     static constexpr int kProfWarp = kProfMotion + CANNY_HIP_MOTION_PARTS;
     static constexpr int kProfFuse = kProfWarp + CANNY_HIP_WARP_PARTS;
-    static constexpr int kProfSlots = kProfFuse + CANNY_HIP_FUSE_PARTS;
+    static constexpr int kProfMorph = kProfFuse + CANNY_HIP_FUSE_PARTS; // the binary morphology (canny_hip_morph_profile_get)
+    static constexpr int kProfSlots = kProfMorph + CANNY_HIP_MORPH_PARTS;
     static constexpr int kProfLastBit = 30;
     static_assert(kProfPolygons == kProfLastBit && kProfEdgels > kProfLastBit,
                   "profile_stage_mask has one bit per slot up to the polygon parts; every slot from there on follows bit 30");
@@ -2016,6 +2020,7 @@ void collect_workspaces(const canny_hip_ctx *c, const std::string &prefix, std::
     add("corners_ws", c->corners_ws, I);   // keys address pixels, totals bound the sort, counters hand out slots
     add("desc_ws", c->desc_ws, I);         // the pairs address frames, the best queries are compared with indices
     add("motion_ws", c->motion_ws, I);     // the pairs address frames, m bounds the lists, the slots address the flags
+    add("morph_ws", c->morph_ws, D);
     add("plane_s", c->plane_s, D);
     add("plane_c", c->plane_c, D);
     add("stamps", c->stamps, I);           // tile queues and their counters
@@ -2133,6 +2138,7 @@ void canny_hip_ctx_destroy(canny_hip_ctx *ctx)
     ctx->corners_ws.release();
     ctx->desc_ws.release();
     ctx->motion_ws.release();
+    ctx->morph_ws.release();
     ctx->cc_parent.release();
     ctx->cc_ws.release();
     ctx->ct_ws.release();
@@ -2190,6 +2196,7 @@ int canny_hip_ctx_get_option(const canny_hip_ctx *ctx, const char *name, int *va
     else if (!std::strcmp(name, "chamfer_route")) *value = ctx->chamfer_route;
     else if (!std::strcmp(name, "warp_route")) *value = ctx->warp_route;
     else if (!std::strcmp(name, "fuse_route")) *value = ctx->fuse_route;
+    else if (!std::strcmp(name, "morph_route")) *value = ctx->morph_route;
     else if (!std::strcmp(name, "tune_chamfer_chunk_mb")) *value = ctx->chamfer_chunk_mb;
     else if (!std::strcmp(name, "batch_expand_threads")) *value = ctx->expand_pool ? ctx->expand_pool->size() : 0; // read-only
     else return CANNY_HIP_ERR_INVALID;
@@ -2218,6 +2225,7 @@ int canny_hip_ctx_set_option(canny_hip_ctx *ctx, const char *name, int value)
     else if (!std::strcmp(name, "chamfer_route") && value <= 2) ctx->chamfer_route = value;
     else if (!std::strcmp(name, "warp_route") && value <= 2) ctx->warp_route = value;
     else if (!std::strcmp(name, "fuse_route") && value <= 2) ctx->fuse_route = value;
+    else if (!std::strcmp(name, "morph_route") && value <= 2) ctx->morph_route = value;
     else if (!std::strcmp(name, "tune_chamfer_chunk_mb") && value <= 4096) ctx->chamfer_chunk_mb = value;
     else if (!std::strcmp(name, "tune_hough_lds_kb") && value <= kHoughLdsMax / 1024) ctx->hough_lds_kb = value;
     else if (!std::strcmp(name, "tune_batch_expand_threads") && value <= 64) {
@@ -6708,6 +6716,139 @@ int canny_hip_selftest_fuse_mean(canny_hip_ctx *ctx, unsigned char *out)
     HIP_TRY(ctx, ctx->io[1].ensure(bytes));
     HIP_TRY(ctx, launch_fuse_mean_table((uint8_t *)ctx->io[1].p, ctx->stream));
     return d2h_sync(ctx, out, ctx->io[1].p, bytes);
+}
+
+// ---- binary morphology on packed bit maps (canny_morph.hip) -----------------------------------------
+// canny_hip_morph_bits and canny_hip_morph_element, the rule in plain C++, live in canny_morph_host.cpp.
+
+namespace {
+// every check of the morphology but the pointers and the overlaps
+int morph_check(int n_frames, int h, int w, int op, const unsigned *rows, int kw, int kh, int border, int iterations)
+{
+    if (n_frames < 1 || h < 1 || w < 1 || op < CANNY_HIP_MORPH_ERODE || op > CANNY_HIP_MORPH_BLACKHAT || !rows || kw < 1 ||
+        kw > CANNY_HIP_MORPH_MAX_EXTENT || kh < 1 || kh > CANNY_HIP_MORPH_MAX_EXTENT || !(kw & 1) || !(kh & 1) ||
+        border < CANNY_HIP_MORPH_BORDER_ZERO || border > CANNY_HIP_MORPH_BORDER_NEUTRAL || iterations < 1 ||
+        iterations > CANNY_HIP_MORPH_MAX_ITERATIONS)
+        return CANNY_HIP_ERR_INVALID;
+    unsigned any = 0;
+    for (int j = 0; j < kh; j++) {
+        if (rows[j] >> kw) return CANNY_HIP_ERR_INVALID;
+        any |= rows[j];
+    }
+    if (!any) return CANNY_HIP_ERR_INVALID;
+    return fuse_stack_check(n_frames, h, w);
+}
+
+// The operator queued on the context's stream; src: a packed map or -- strong -- the context's strong bit-plane.  Everything
+// has been checked.
+int dev_morph(canny_hip_ctx *ctx, const void *src, bool strong, int n_frames, int h, int w, int op, const unsigned *rows,
+              int kw, int kh, int border, int iterations, unsigned char *d_out, long long *d_counts)
+{
+    const size_t bytes = npx(h, (w + 7) / 8, n_frames), slot = (bytes + 15) & ~(size_t)15;
+    const int n_steps = (op <= CANNY_HIP_MORPH_DILATE ? 1 : 2) * iterations;
+    uint8_t *ws_a = nullptr, *ws_b = nullptr;
+    if (n_steps > 1) {
+        HIP_TRY(ctx, ctx->morph_ws.ensure(2 * slot));
+        ws_a = (uint8_t *)ctx->morph_ws.p, ws_b = ws_a + slot;
+    }
+    StageTimer tm(ctx, canny_hip_ctx::kProfMorph + CANNY_HIP_MORPH_PART_STEPS);
+    HIP_TRY(ctx, launch_morph(src, strong, n_frames, h, w, op, rows, kw, kh, border, iterations, ctx->morph_route, ws_a, ws_b,
+                              d_out, (unsigned long long *)d_counts, ctx->stream));
+    return CANNY_HIP_OK;
+}
+} // namespace
+
+int canny_hip_dev_morph_bits(canny_hip_ctx *ctx, const unsigned char *d_bits, int n_frames, int h, int w, int op,
+                             const unsigned *rows, int kw, int kh, int border, int iterations, unsigned char *d_out_bits,
+                             long long *d_counts)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!d_bits || !d_out_bits || ((uintptr_t)d_counts & 7)) return CANNY_HIP_ERR_INVALID;
+    if ((rc = morph_check(n_frames, h, w, op, rows, kw, kh, border, iterations))) return rc;
+    const size_t bytes = npx(h, (w + 7) / 8, n_frames), cbytes = (size_t)n_frames * sizeof(long long);
+    if (ranges_overlap(d_bits, bytes, d_out_bits, bytes) || opt_overlap(d_bits, bytes, d_counts, cbytes) ||
+        opt_overlap(d_out_bits, bytes, d_counts, cbytes))
+        return CANNY_HIP_ERR_INVALID;
+    if ((rc = finish_pending(ctx))) return rc;
+    return dev_morph(ctx, d_bits, false, n_frames, h, w, op, rows, kw, kh, border, iterations, d_out_bits, d_counts);
+}
+
+int canny_hip_dev_canny_morph(canny_hip_ctx *ctx, int n_frames, int h, int w, int op, const unsigned *rows, int kw, int kh,
+                              int border, int iterations, unsigned char *d_out_bits, long long *d_counts)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!d_out_bits || ((uintptr_t)d_counts & 7)) return CANNY_HIP_ERR_INVALID;
+    if ((rc = morph_check(n_frames, h, w, op, rows, kw, kh, border, iterations))) return rc;
+    // the plane the last canny call left: only for the batch it belongs to
+    if (!ctx->last_canny_n || !ctx->plane_s.p || ctx->last_canny_n != n_frames || ctx->last_canny_h != h ||
+        ctx->last_canny_w != w)
+        return CANNY_HIP_ERR_INVALID;
+    if (opt_overlap(d_out_bits, npx(h, (w + 7) / 8, n_frames), d_counts, (size_t)n_frames * sizeof(long long)))
+        return CANNY_HIP_ERR_INVALID;
+    if ((rc = finish_pending(ctx))) return rc;
+    return dev_morph(ctx, ctx->plane_s.p, true, n_frames, h, w, op, rows, kw, kh, border, iterations, d_out_bits, d_counts);
+}
+
+int canny_hip_canny_morph(canny_hip_ctx *ctx, const unsigned char *imgs, int n_frames, float sigma, int min_val, int max_val,
+                          int height, int width, int op, const unsigned *rows, int kw, int kh, int border, int iterations,
+                          unsigned char *out_bits, long long *counts)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!imgs || !out_bits || ((uintptr_t)counts & 7)) return CANNY_HIP_ERR_INVALID;
+    if ((rc = morph_check(n_frames, height, width, op, rows, kw, kh, border, iterations))) return rc;
+    if ((rc = check_dims(height, width, n_frames))) return rc;
+    const size_t n = npx(height, width, n_frames), bytes = npx(height, (width + 7) / 8, n_frames);
+    const size_t cbytes = (size_t)n_frames * sizeof(long long), slot = (bytes + 15) & ~(size_t)15;
+    if ((rc = h2d(ctx, ctx->io[0], imgs, n))) return rc;
+    // one staging block: the output maps | the counts | the finished map as bits where the strong plane is not the map
+    HIP_TRY(ctx, ctx->io[1].ensure(2 * slot + ((cbytes + 15) & ~(size_t)15)));
+    unsigned char *d_out = (unsigned char *)ctx->io[1].p, *d_map = d_out + slot + ((cbytes + 15) & ~(size_t)15);
+    long long *d_counts = (long long *)(d_out + slot);
+    HIP_TRY(ctx, ctx->edges16.ensure(n * sizeof(short)));
+    if ((rc = dev_canny(ctx, (const unsigned char *)ctx->io[0].p, sigma, min_val, max_val, height, width, n_frames,
+                        (short *)ctx->edges16.p)))
+        return rc;
+    if (max_val > 255) { // the reference zeroes every reached pixel: the map, not the plane, is the source
+        HIP_TRY(ctx, launch_edges_to_bits((const int16_t *)ctx->edges16.p, d_map, height, width, n_frames, ctx->stream));
+        rc = dev_morph(ctx, d_map, false, n_frames, height, width, op, rows, kw, kh, border, iterations, d_out,
+                       counts ? d_counts : nullptr);
+    } else {
+        rc = dev_morph(ctx, ctx->plane_s.p, true, n_frames, height, width, op, rows, kw, kh, border, iterations, d_out,
+                       counts ? d_counts : nullptr);
+    }
+    if (rc) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(out_bits, d_out, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    if (counts) HIP_TRY(ctx, hipMemcpyAsync(counts, d_counts, cbytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return CANNY_HIP_OK;
+}
+
+int canny_hip_morph_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches)
+{
+    if (part < 0 || part >= CANNY_HIP_MORPH_PARTS || !total_ms || !launches) return CANNY_HIP_ERR_INVALID;
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if ((rc = profile_collect(ctx))) return rc;
+    *total_ms = ctx->total_ms[canny_hip_ctx::kProfMorph + part];
+    *launches = ctx->launches[canny_hip_ctx::kProfMorph + part];
+    return CANNY_HIP_OK;
+}
+
+// Host-only: the launch plan of one primitive step and the route automatic takes for a full rectangle of kw x kh.
+int canny_hip_selftest_morph_plan(int n_frames, int h, int w, int kw, int kh, unsigned long long *out)
+{
+    if (!out) return CANNY_HIP_ERR_INVALID;
+    if (kw < 1 || kw > CANNY_HIP_MORPH_MAX_EXTENT || kh < 1 || kh > CANNY_HIP_MORPH_MAX_EXTENT || !(kw & 1) || !(kh & 1))
+        return CANNY_HIP_ERR_INVALID;
+    const int rc = fuse_stack_check(n_frames, h, w);
+    if (rc) return rc;
+    const LaunchPlan p = plan_morph_tiles(n_frames, h, w);
+    out[0] = p.units, out[1] = p.per_group, out[2] = p.grid, out[3] = p.trips();
+    out[4] = (unsigned long long)morph_auto_route(kw, kh);
+    return CANNY_HIP_OK;
 }
 
 } // extern "C"

@@ -857,6 +857,21 @@ hipError_t launch_change_mask(const uint8_t *frames, const uint8_t *valid, int n
 // canny_hip_selftest_fuse_mean: the kernels' rounded mean over every (c, s) into table [255][65026], unused cells 0.
 hipError_t launch_fuse_mean_table(uint8_t *table, hipStream_t stream);
 
+// ---- binary morphology on packed bit maps (canny_morph.hip) ------------------------------
+// One primitive step is one launch over the n_frames * ceil(h / 64) * ceil(ceil(w / 64) / 8) tiles of 8 words x 64 rows, one
+// per workgroup and trip.  (Reported by canny_hip_selftest_morph_plan, not by a kind.)
+LaunchPlan plan_morph_tiles(int n_frames, int h, int w);
+// The route automatic takes for a full rectangle of kw x kh: 1 general, 2 separable.
+int morph_auto_route(int kw, int kh);
+// Every byte of out [n_frames][h][ceil(w / 8)], pad bits 0.  src: a packed map of that layout or -- src_plane -- the strong
+// bit-plane of make_hyst_geom(h, w, n_frames).  op, border: the header's enums; rows[kh]: host memory, read before the call
+// returns; route: 0 automatic, 1 general, 2 separable (full rectangles only).  ws_a, ws_b: two maps of out's size for the
+// intermediates of more than one (ws_a) or two (ws_b) primitive steps; out itself holds intermediates of GRADIENT.  counts
+// (may be NULL, 8-byte aligned) is zeroed on the stream, then summed by the last step.
+hipError_t launch_morph(const void *src, bool src_plane, int n_frames, int h, int w, int op, const unsigned *rows, int kw,
+                        int kh, int border, int iterations, int route, uint8_t *ws_a, uint8_t *ws_b, uint8_t *out,
+                        unsigned long long *counts, hipStream_t stream);
+
 // ---- measurement aid ------------------------------------------------------------------------
 // Plain device copy of nbytes (multiple of 16; both pointers 16-byte aligned): what a 1:1 read/write stream reaches.
 hipError_t launch_probe_copy(const void *src, void *dst, size_t nbytes, hipStream_t stream, const LaunchEvents &ev = {});

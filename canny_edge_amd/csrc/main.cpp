@@ -65,6 +65,10 @@
 // (their non-zero pixels, anchored at the centre) on the GPU (canny_hip_canny_chamfer) and writes one "frame x y template
 // score mean" row per match, in order, to canny_matches.txt in the -o directory (stdout without -o); mean is the mean
 // cost in pixels to four decimals.  A malformed -x is a usage error (exit 2).  Without -x nothing changes.
+// Added: -z op,kw[,kh[,shape[,iterations]]] applies a binary morphology operator to the finished edge map on the GPU
+// (canny_hip_canny_morph, the neutral border): op erode, dilate, open, close, gradient, tophat or blackhat; kw and kh (default
+// kw) odd, 1..31; shape rect (default), cross or ellipse; iterations 1..16 (default 1).  The map (0 / 255) goes to
+// canny_morph.pgm in the -o directory.  A malformed -z is a usage error (exit 2).  Without -z nothing changes.
 // Added: -e computes the sub-pixel edgel of every pixel of the frame's edge map on the GPU (canny_hip_canny_edgels) and
 // writes one "x y gx gy mag dir refined" row per edge pixel, in raster order, to canny_edgels.txt in the -o directory
 // (stdout without -o): x and y in pixels to three decimals, mag in grey levels, dir 0..3 (step (1,0), (1,1), (0,1), (1,-1)),
@@ -652,6 +656,37 @@ static int run_edt(const vector<unsigned char> &frame, int height, int width, fl
     return 0;
 }
 
+// -z: a morphology operator on the frame's edge map -> canny_morph.pgm.  m: op, kw, kh, shape, iterations
+static int run_morph(const vector<unsigned char> &frame, int height, int width, float sigma, int minVal, int maxVal, const int *m,
+                     const string &outdir)
+{
+    const size_t rb = ((size_t)width + 7) / 8;
+    vector<unsigned char> bits(rb * height);
+    unsigned rows[CANNY_HIP_MORPH_MAX_EXTENT];
+    canny_hip_ctx *ctx = nullptr;
+    int st = canny_hip_morph_element(m[3], m[1], m[2], rows);
+    if (!st) st = canny_hip_ctx_create(&ctx, 0);
+    if (!st)
+        st = canny_hip_canny_morph(ctx, frame.data(), 1, sigma, minVal, maxVal, height, width, m[0], rows, m[1], m[2],
+                                   CANNY_HIP_MORPH_BORDER_NEUTRAL, m[4], bits.data(), nullptr);
+    if (st) {
+        fprintf(stderr, "ERROR: -z: %s\n", st == CANNY_HIP_ERR_RUNTIME && ctx ? canny_hip_last_error(ctx) : canny_hip_status_string(st));
+        if (ctx) canny_hip_ctx_destroy(ctx);
+        return 1;
+    }
+    canny_hip_ctx_destroy(ctx);
+    vector<unsigned char> out((size_t)height * width);
+    for (int y = 0; y < height; y++)
+        for (int x = 0; x < width; x++)
+            out[(size_t)y * width + x] = (bits[(size_t)y * rb + (x >> 3)] >> (7 - (x & 7))) & 1 ? 255 : 0;
+    const string path = (outdir.empty() ? string(".") : outdir) + "/canny_morph" + (png_output ? ".png" : ".pgm");
+    if (!write_frame(path, out.data(), height, width)) {
+        fprintf(stderr, "ERROR: cannot write %s\n", path.c_str());
+        return 1;
+    }
+    return 0;
+}
+
 // -r: the circles of the frame's edge map, "frame x y radius votes support" per circle; with -k (fit != nullptr: band,
 // trim_q8, options) also the circle fit of every circle, "frame cx cy r n rms maxd sectors trim_failed degenerate" per circle
 static int run_circles(const vector<unsigned char> &frame, int height, int width, float sigma, int minVal, int maxVal,
@@ -869,6 +904,8 @@ int main(int argc, char *argv[])
     bool want_corners = false;
     int corner_args[5] = {0, 0, 0, 3, -1}; // -q: quality_q16, min_dist, corners_max, block, k_q8 (-1: Shi-Tomasi)
     int desc_options = -1;                 // -j: -1 absent, 0 upright, CANNY_HIP_DESC_STEERED
+    bool want_morph = false;
+    int morph_args[5] = {0, 3, 3, 0, 1};   // -z: op, kw, kh, shape, iterations
     int width = WIDTH, height = HEIGHT;
     vector<string> values;
 
@@ -1040,6 +1077,46 @@ int main(int argc, char *argv[])
                 exit(2);
             }
             desc_options = word == "steered" ? CANNY_HIP_DESC_STEERED : 0;
+        } else if (arg == "-z") {
+            // op,kw[,kh[,shape[,iterations]]]: words and whole integers, nothing empty, nothing behind the last one
+            static const char *const ops[] = {"erode", "dilate", "open", "close", "gradient", "tophat", "blackhat"};
+            static const char *const shapes[] = {"rect", "cross", "ellipse"};
+            vector<string> parts(1);
+            for (const char *p = i + 1 < argc ? argv[++i] : ""; *p; p++) {
+                if (*p == ',')
+                    parts.emplace_back();
+                else
+                    parts.back() += *p;
+            }
+            auto word = [](const string &w, const char *const *names, int n) {
+                for (int k = 0; k < n; k++)
+                    if (w == names[k]) return k;
+                return -1;
+            };
+            auto number = [](const string &w) { // 1..99 from digits alone, else -1
+                if (w.empty() || w.size() > 2) return -1;
+                for (char c : w)
+                    if (!isdigit((unsigned char)c)) return -1;
+                return atoi(w.c_str());
+            };
+            bool clean = parts.size() >= 2 && parts.size() <= 5;
+            if (clean) {
+                morph_args[0] = word(parts[0], ops, 7);
+                morph_args[1] = number(parts[1]);
+                morph_args[2] = parts.size() > 2 ? number(parts[2]) : morph_args[1];
+                morph_args[3] = parts.size() > 3 ? word(parts[3], shapes, 3) : CANNY_HIP_MORPH_RECT;
+                morph_args[4] = parts.size() > 4 ? number(parts[4]) : 1;
+                for (int k = 1; k <= 2; k++)
+                    clean = clean && morph_args[k] >= 1 && morph_args[k] <= CANNY_HIP_MORPH_MAX_EXTENT && (morph_args[k] & 1);
+                clean = clean && morph_args[0] >= 0 && morph_args[3] >= 0 && morph_args[4] >= 1 &&
+                        morph_args[4] <= CANNY_HIP_MORPH_MAX_ITERATIONS;
+            }
+            if (!clean) {
+                fprintf(stderr, "ERROR: -z expects op,kw[,kh[,shape[,iterations]]]: op erode, dilate, open, close, gradient, tophat or "
+                                "blackhat, kw and kh odd in 1..31, shape rect, cross or ellipse, iterations 1..16\n");
+                exit(2);
+            }
+            want_morph = true;
         } else if (arg == "-w" && i + 1 < argc) {
             char tail = 0; // a whole integer only
             if (sscanf(argv[++i], "%d%c", &curve_min_length, &tail) != 1) {
@@ -1124,6 +1201,8 @@ int main(int argc, char *argv[])
         fprintf(stderr, "       k in 1/256), one \"frame x y response rank\" line each -> canny_corners.txt in the -o dir\n");
         fprintf(stderr, "   -j upright|steered: with -q, the 256-bit descriptor of every corner (steered: turned to the patch's centroid),\n");
         fprintf(stderr, "       one \"x y k border\" and 64 hex digits each -> canny_descriptors.txt in the -o dir\n");
+        fprintf(stderr, "   -z op,kw[,kh[,shape[,iterations]]]: binary morphology of the edge map (erode, dilate, open, close, gradient,\n");
+        fprintf(stderr, "       tophat, blackhat; kw, kh odd 1..31; rect, cross, ellipse; 1..16 iterations) -> canny_morph.pgm in the -o dir\n");
         fprintf(stderr, "   -d: distance of every pixel to the nearest edge pixel, min(255, floor) -> canny_dist.pgm in the -o dir\n");
         fprintf(stderr, "   -e: sub-pixel edgel of every edge pixel, one \"x y gx gy mag dir refined\" line each (x, y in pixels to three\n");
         fprintf(stderr, "       decimals, mag in grey levels, dir 0..3) -> canny_edgels.txt in the -o dir\n");
@@ -1203,6 +1282,10 @@ int main(int argc, char *argv[])
     }
     if (want_edgels) {
         const int rc = run_edgels(frame, height, width, sigma, minVal, maxVal, outdir);
+        if (rc) return rc;
+    }
+    if (want_morph) {
+        const int rc = run_morph(frame, height, width, sigma, minVal, maxVal, morph_args, outdir);
         if (rc) return rc;
     }
     if (want_dist) {

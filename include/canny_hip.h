@@ -52,7 +52,8 @@
 extern "C" {
 #endif
 
-#define CANNY_HIP_VERSION 2300       /* 0.23.0: + temporal fusion of aligned frames and change masks (0.22.0: + frame alignment) */
+#define CANNY_HIP_VERSION 2400       /* 0.24.0: + binary morphology on packed bit maps */
+/* 0.23.0: + temporal fusion of aligned frames and change masks (0.22.0: + frame alignment) */
 /* 0.21.0: + frame-to-frame motion from the corner matches (RANSAC) */
 /* 0.20.0: + corner descriptors and Hamming matching between frames */
 /* 0.19.0: + corners: Harris / Shi-Tomasi on the smoothed plane */
@@ -2188,6 +2189,98 @@ int canny_hip_canny_background(canny_hip_ctx *ctx, const unsigned char *imgs, in
                                int interp, int border, int op, int fill, int min_count, int thr, unsigned char *background,
                                unsigned char *count, unsigned char *mask_bits, long long *changed, long long *xforms);
 
+/* ---- binary morphology on packed bit maps -------------------------------------------------------------------------------
+ * The operator that maps a bit map to a bit map: erode, dilate, open, close, gradient, top hat and black hat -- what
+ * cv::erode / cv::dilate / cv::morphologyEx answer on a binary image -- on the packed layout of canny_hip_dev_canny_bits and
+ * canny_hip_dev_change_mask, which canny_hip_dev_components_bits, _edt_bits, _contours_bits and _points_from_bits take as it
+ * is: a change mask is cleaned of salt and pepper, an edge map has its one-pixel breaks closed, on the context's stream,
+ * without a download.  All bit operations: the same bytes on every run and every machine.  tests/morph_rule.py restates the
+ * rule in numpy, csrc/canny_morph_host.cpp in plain C++.
+ * THE RULE:
+ *   Bit maps.  [n_frames][h][(w + 7) / 8] bytes, rows MSB-first.  THE PAD BITS OF THE INPUT ARE IGNORED: a column >= w is
+ *     outside the frame, whatever the byte holds.  THE PAD BITS OF THE OUTPUT ARE WRITTEN 0, and every output byte is written.
+ *   Element.  kw, kh odd, 1..31 (CANNY_HIP_MORPH_MAX_EXTENT); rows[kh] unsigned words; bit i (LSB = 0) of rows[j] is the offset
+ *     (dx, dy) = (i - kw / 2, j - kh / 2).  Bits at or above kw must be 0 and at least one bit must be set, otherwise
+ *     CANNY_HIP_ERR_INVALID.  The centre need not be set.  canny_hip_morph_element fills rows for a shape:
+ *       CANNY_HIP_MORPH_RECT    = 0: all bits set
+ *       CANNY_HIP_MORPH_CROSS   = 1: the centre row and the centre column
+ *       CANNY_HIP_MORPH_ELLIPSE = 2: dx^2 ry^2 + dy^2 rx^2 <= rx^2 ry^2 with rx = kw / 2, ry = kh / 2; all bits if rx or ry is
+ *         0.  For kw = kh = 2 r + 1 this is skimage.morphology.disk(r); 3 x 3 gives the cross.
+ *   Primitives, B the set of the element's offsets:
+ *       ERODE : out(p) = AND over b in B of in(p + b)
+ *       DILATE: out(p) = OR  over b in B of in(p - b)   -- the Minkowski sum: the element reflected
+ *     These are scipy.ndimage.binary_erosion / binary_dilation with structure = B, and cv::erode / cv::dilate for symmetric
+ *     elements.
+ *   Border.  What a pixel outside the frame reads as: CANNY_HIP_MORPH_BORDER_ZERO = 0 reads 0, _ONE = 1 reads 1, _NEUTRAL = 2
+ *     reads 1 in an erosion step and 0 in a dilation step (OpenCV's default: the outside constrains nothing).
+ *   Ops, iterations in 1..16 (CANNY_HIP_MORPH_MAX_ITERATIONS):
+ *       CANNY_HIP_MORPH_ERODE = 0, _DILATE = 1: the primitive `iterations` times in sequence
+ *       CANNY_HIP_MORPH_OPEN  = 2: `iterations` erosions, then `iterations` dilations
+ *       CANNY_HIP_MORPH_CLOSE = 3: `iterations` dilations, then `iterations` erosions
+ *       CANNY_HIP_MORPH_GRADIENT = 4: DILATE & ~ERODE;  _TOPHAT = 5: in & ~OPEN;  _BLACKHAT = 6: CLOSE & ~in -- inside the frame
+ *     With the reflected dilation and the neutral border OPEN is idempotent and anti-extensive and CLOSE idempotent and
+ *     extensive, for every element.
+ *   Counts.  counts may be NULL; otherwise n_frames long long, 8-byte aligned: the set bits of each output frame, an integer
+ *     sum (no order to depend on), zeroed on the stream inside the call, fully written by it and not touched by a refused one.
+ *   Limits: h, w in 1..32768, a plane < 2^31 pixels, at most 65535 frames; above: CANNY_HIP_ERR_UNSUPPORTED.  Bad enum values,
+ *     bad ranges, NULL mandatory pointers, a bad element, a misaligned counts buffer, an output that overlaps the input (there
+ *     is no in-place form) or the counts: CANNY_HIP_ERR_INVALID.  Both before anything is queued; nothing is written.
+ *   Kernels (csrc/canny_morph.hip): one launch per primitive step; a workgroup of 256 per tile of 8 x 64-bit words x 64 rows and
+ *     trip of a grid capped at 4096.  Rows become LSB-first 64-bit words in LDS with the outside value put in where the words
+ *     are formed; a horizontal offset is a shift with the carry from the neighbouring word, a run of L set element bits costs
+ *     O(log L) shifts by doubling, a vertical offset is another row's word.  The context option "morph_route": 0 automatic,
+ *     1 general (per element row its runs), 2 separable (full rectangles: the horizontal run, then the vertical run by doubling
+ *     in LDS; any other element runs the general route).  All routes give the same bytes.  Sequential steps go through one
+ *     context workspace of two maps (and, for GRADIENT, the output buffer); the final combination, the pad bits and the counts
+ *     belong to the last step's kernel.
+ * Not covered -- follow-ups: grey-level morphology on u8 planes; hit-or-miss and thinning; elements wider than 31; morphology
+ * through the batch pipeline or the multi-GPU sharder; a grammar of Main for fusion and change masks. */
+#define CANNY_HIP_MORPH_MAX_EXTENT 31
+#define CANNY_HIP_MORPH_MAX_ITERATIONS 16
+enum canny_hip_morph_op {
+    CANNY_HIP_MORPH_ERODE = 0,
+    CANNY_HIP_MORPH_DILATE = 1,
+    CANNY_HIP_MORPH_OPEN = 2,
+    CANNY_HIP_MORPH_CLOSE = 3,
+    CANNY_HIP_MORPH_GRADIENT = 4,
+    CANNY_HIP_MORPH_TOPHAT = 5,
+    CANNY_HIP_MORPH_BLACKHAT = 6
+};
+enum canny_hip_morph_shape {
+    CANNY_HIP_MORPH_RECT = 0,
+    CANNY_HIP_MORPH_CROSS = 1,
+    CANNY_HIP_MORPH_ELLIPSE = 2
+};
+enum canny_hip_morph_part {
+    CANNY_HIP_MORPH_PART_STEPS = 0, /* all primitive steps of a call, with the zeroing of the counts */
+    CANNY_HIP_MORPH_PARTS = 1
+};
+enum canny_hip_morph_border {
+    CANNY_HIP_MORPH_BORDER_ZERO = 0,
+    CANNY_HIP_MORPH_BORDER_ONE = 1,
+    CANNY_HIP_MORPH_BORDER_NEUTRAL = 2
+};
+/* d_bits, d_out_bits: n_frames * h * ((w + 7) / 8) bytes, any byte address; rows: kh words of HOST memory, copied at call
+ * time; d_counts: n_frames long long or NULL.  Asynchronous, on the context's stream. */
+int canny_hip_dev_morph_bits(canny_hip_ctx *ctx, const unsigned char *d_bits, int n_frames, int h, int w, int op,
+                             const unsigned *rows, int kw, int kh, int border, int iterations, unsigned char *d_out_bits,
+                             long long *d_counts);
+/* The same operator on the strong bit-plane that the preceding dev_canny of the same n_frames, h, w left in the context (any
+ * canny_hip_dev_canny* call; another geometry, or none yet: CANNY_HIP_ERR_INVALID).  The plane is the finished map for
+ * max_val <= 255; it is only read, so the call may be repeated and mixed with the other analysis calls.  Asynchronous. */
+int canny_hip_dev_canny_morph(canny_hip_ctx *ctx, int n_frames, int h, int w, int op, const unsigned *rows, int kw, int kh,
+                              int border, int iterations, unsigned char *d_out_bits, long long *d_counts);
+/* Host buffers, synchronous: upload, canny, the operator on the finished map; only out_bits (n_frames * height * ((width + 7)
+ * / 8) bytes) and, where the pointer is not NULL, counts come down. */
+int canny_hip_canny_morph(canny_hip_ctx *ctx, const unsigned char *imgs, int n_frames, float sigma, int min_val, int max_val,
+                          int height, int width, int op, const unsigned *rows, int kw, int kh, int border, int iterations,
+                          unsigned char *out_bits, long long *counts);
+/* Host-only, needs no device: the same rule on host buffers. */
+int canny_hip_morph_bits(const unsigned char *bits, int n_frames, int h, int w, int op, const unsigned *rows, int kw, int kh,
+                         int border, int iterations, unsigned char *out_bits, long long *counts);
+/* Host-only: rows[kh] of a canny_hip_morph_shape; kw, kh odd, 1..31. */
+int canny_hip_morph_element(int shape, int kw, int kh, unsigned *rows);
+
 /* ---- per-stage HIP-event timing (events are recorded on the launch stream) ----------------- */
 int canny_hip_profile_enable(canny_hip_ctx *ctx, int on);
 int canny_hip_profile_reset(canny_hip_ctx *ctx);
@@ -2230,6 +2323,8 @@ int canny_hip_motion_profile_get(canny_hip_ctx *ctx, int part, double *total_ms,
 int canny_hip_warp_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches);
 /* ... and for the two parts of the temporal fusion (CANNY_HIP_FUSE_PART_*). */
 int canny_hip_fuse_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches);
+/* ... and for the one part of the binary morphology (CANNY_HIP_MORPH_PART_*; bit 30 of "profile_stage_mask" like the others). */
+int canny_hip_morph_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches);
 
 /* ---- self-test hooks used by the GPU test-suite -------------------------------------------- */
 /* Runs the DEVICE magnitude / angle-bin functions over every (gx,gy) in [-lim,lim]^2 and writes
@@ -2415,6 +2510,11 @@ int canny_hip_selftest_warp_plan(int n_out, int out_h, int out_w, unsigned long 
  * for a MEDIAN of group_len frames (1 registers, 2 passes).  Arguments within the limits of the calls. */
 int canny_hip_selftest_fuse_plan(int which, int n_frames, int h, int w, int group_len, int group_step,
                                  unsigned long long *out);
+/* Host-only, the same five outputs for the capped launch of one primitive step of the binary morphology (no kind above): items
+ * = n_frames * ceil(h / 64) * ceil(ceil(w / 64) / 8) tiles, one per workgroup of 256 and trip, at most 4096 workgroups.  The
+ * fifth word is the route that automatic takes for a full rectangle of kw x kh (1 general, 2 separable).  Arguments within
+ * the limits of the calls. */
+int canny_hip_selftest_morph_plan(int n_frames, int h, int w, int kw, int kh, unsigned long long *out);
 /* Runs the fuse kernels' own device helper for the rounded mean over every pair c = 1..255, s = 0..255 c, and writes the
  * bytes to host memory as a table [255][CANNY_HIP_FUSE_MEAN_ROW]: out[(c - 1) * 65026 + s]; unused cells are 0. */
 int canny_hip_selftest_fuse_mean(canny_hip_ctx *ctx, unsigned char *out);
