@@ -161,6 +161,21 @@ class CannyHipError(RuntimeError):
         super().__init__(msg)
 
 
+def _ok(st: int, what: str):
+    """Raise for a non-zero status of a call that has no context to ask for details."""
+    if st:
+        raise CannyHipError(st, what)
+
+
+def _plan(name: str, *args, n: int = 5, tail=()):
+    """canny_hip_selftest_<name>(*args, out, *tail) on a zeroed uint64 [n]: the LaunchPlan of its first five words and, with
+    n > 5, the words behind them."""
+    out = np.zeros(n, np.uint64)
+    _ok(getattr(load(), "canny_hip_selftest_" + name)(*args, _hp(out), *tail), "selftest_" + name)
+    plan = LaunchPlan(*(int(v) for v in out[:5]))
+    return plan if n == 5 else (plan, *(int(v) for v in out[5:]))
+
+
 def load() -> C.CDLL:
     """Load the HIP library; fail loudly if it has not been built."""
     global _lib
@@ -431,10 +446,8 @@ def expand_bits(bits: np.ndarray, height: int, width: int, u8: bool = False, thr
     assert bits.size == height * ((width + 7) // 8)
     if out is None:
         out = np.empty((height, width), np.uint8 if u8 else np.int16)
-    st = load().canny_hip_selftest_expand_bits(bits.ctypes.data_as(C.c_void_p), height, width, int(u8),
-                                               out.ctypes.data_as(C.c_void_p), threads)
-    if st:
-        raise CannyHipError(st, "selftest_expand_bits")
+    _ok(load().canny_hip_selftest_expand_bits(bits.ctypes.data_as(C.c_void_p), height, width, int(u8),
+                                              out.ctypes.data_as(C.c_void_p), threads), "selftest_expand_bits")
     return out
 
 
@@ -448,14 +461,10 @@ def points_from_bits(bits, height: int, width: int, capacity: Optional[int] = No
     n = C.c_ulonglong(0)
     L = load()
     if capacity is None:
-        st = L.canny_hip_points_from_bits(_hp(b), height, width, None, 0, C.byref(n))
-        if st:
-            raise CannyHipError(st, "points_from_bits")
+        _ok(L.canny_hip_points_from_bits(_hp(b), height, width, None, 0, C.byref(n)), "points_from_bits")
     cap = n.value if capacity is None else int(capacity)
     pts = np.empty(cap, np.uint32)
-    st = L.canny_hip_points_from_bits(_hp(b), height, width, _hp(pts) if cap else None, cap, C.byref(n))
-    if st:
-        raise CannyHipError(st, "points_from_bits")
+    _ok(L.canny_hip_points_from_bits(_hp(b), height, width, _hp(pts) if cap else None, cap, C.byref(n)), "points_from_bits")
     return pts if capacity is None else (pts[:min(cap, n.value)], n.value)
 
 
@@ -476,16 +485,12 @@ def components_from_bits(bits, height: int, width: int, min_area: int = 1, want_
     L = load()
     n = C.c_ulonglong(0)
     if capacity is None:
-        st = L.canny_hip_components_from_bits(_hp(b), height, width, min_area, None, None, 0, C.byref(n))
-        if st:
-            raise CannyHipError(st, "components_from_bits")
+        _ok(L.canny_hip_components_from_bits(_hp(b), height, width, min_area, None, None, 0, C.byref(n)), "components_from_bits")
     cap = n.value if capacity is None else int(capacity)
     labels = np.empty((height, width), np.int32) if want_labels else None
     stats = np.empty((cap, CC_STATS), np.int32)
-    st = L.canny_hip_components_from_bits(_hp(b), height, width, min_area, _hp(labels) if want_labels else None,
-                                          _hp(stats) if cap else None, cap, C.byref(n))
-    if st:
-        raise CannyHipError(st, "components_from_bits")
+    _ok(L.canny_hip_components_from_bits(_hp(b), height, width, min_area, _hp(labels) if want_labels else None,
+                                         _hp(stats) if cap else None, cap, C.byref(n)), "components_from_bits")
     return labels, stats[:min(cap, n.value)], n.value
 
 
@@ -506,19 +511,16 @@ def contours_from_bits(bits, height: int, width: int, min_area: int = 1, want_st
     L = load()
     k, n = C.c_ulonglong(0), C.c_ulonglong(0)
     if capacity is None or point_capacity is None:
-        st = L.canny_hip_contours_from_bits(_hp(b), height, width, min_area, None, 0, C.byref(k), None, None, 0,
-                                            C.byref(n))
-        if st:
-            raise CannyHipError(st, "contours_from_bits")
+        _ok(L.canny_hip_contours_from_bits(_hp(b), height, width, min_area, None, 0, C.byref(k), None, None, 0,
+                                           C.byref(n)), "contours_from_bits")
     cap = k.value if capacity is None else int(capacity)
     pcap = n.value if point_capacity is None else int(point_capacity)
     stats = np.empty((cap, CC_STATS), np.int32) if want_stats else None
     chain = np.zeros(cap + 1, np.uint64)
     points = np.empty(pcap, np.int32)
-    st = L.canny_hip_contours_from_bits(_hp(b), height, width, min_area, _hp(stats) if want_stats and cap else None, cap,
-                                        C.byref(k), _hp(chain), _hp(points) if pcap else None, pcap, C.byref(n))
-    if st:
-        raise CannyHipError(st, "contours_from_bits")
+    _ok(L.canny_hip_contours_from_bits(_hp(b), height, width, min_area, _hp(stats) if want_stats and cap else None, cap,
+                                       C.byref(k), _hp(chain), _hp(points) if pcap else None, pcap, C.byref(n)),
+        "contours_from_bits")
     fit = min(cap, k.value)
     return (stats[:fit] if want_stats else None, chain[:fit + 1], points[:min(pcap, int(chain[fit]))], k.value, n.value)
 
@@ -557,11 +559,9 @@ def polygons_from_chains(chain_offsets, points, width: int, height: int, epsilon
     measures = np.zeros((k, 4), np.int64) if want_measures else None
 
     def call(verts, vcap):
-        st = L.canny_hip_polygons_from_chains(_hp(co), _hp(pts) if pts.size else None, k, pcap, width, height, epsilon_q8,
-                                              ratio_q16, _hp(voff), _hp(verts) if vcap else None, vcap,
-                                              _hp(measures) if want_measures and k else None)
-        if st:
-            raise CannyHipError(st, "polygons_from_chains")
+        _ok(L.canny_hip_polygons_from_chains(_hp(co), _hp(pts) if pts.size else None, k, pcap, width, height, epsilon_q8,
+                                             ratio_q16, _hp(voff), _hp(verts) if vcap else None, vcap,
+                                             _hp(measures) if want_measures and k else None), "polygons_from_chains")
 
     if vertex_capacity is None:
         call(None, 0)
@@ -600,11 +600,9 @@ def shapes_from_chains(chain_offsets, points, width: int, height: int, point_cap
     measures = np.zeros((k, SHAPE_WORDS), np.int64) if want_measures else None
 
     def call(hull, hcap):
-        st = L.canny_hip_shapes_from_chains(_hp(co), _hp(pts) if pts.size else None, k, pcap, width, height, _hp(hoff),
-                                            _hp(hull) if hcap else None, hcap,
-                                            _hp(measures) if want_measures and k else None)
-        if st:
-            raise CannyHipError(st, "shapes_from_chains")
+        _ok(L.canny_hip_shapes_from_chains(_hp(co), _hp(pts) if pts.size else None, k, pcap, width, height, _hp(hoff),
+                                           _hp(hull) if hcap else None, hcap,
+                                           _hp(measures) if want_measures and k else None), "shapes_from_chains")
 
     if hull_capacity is None:
         call(None, 0)
@@ -636,11 +634,7 @@ def shape_rectangle(measures_row, hull, width: int):
 def shapes_plan(which, capacity: int) -> "LaunchPlan":
     """Host-only: the launch plan of a capped launch of the shape stage ("records": the measure and the emit kernel,
     "scan_sums": the scan's pass over its chunks) at a record capacity; fields as launch_plan."""
-    out = np.zeros(5, np.uint64)
-    st = load().canny_hip_selftest_shapes_plan(SHAPES_PLANS.get(which, which), int(capacity), _hp(out))
-    if st:
-        raise CannyHipError(st, "selftest_shapes_plan")
-    return LaunchPlan(*(int(v) for v in out))
+    return _plan("shapes_plan", SHAPES_PLANS.get(which, which), int(capacity))
 
 
 CURVE_PARTS = ("count", "write")
@@ -663,18 +657,15 @@ def curves_from_bits(bits, height: int, width: int, min_length: int = 1, want_re
     L = load()
     k, n = C.c_ulonglong(0), C.c_ulonglong(0)
     if capacity is None or point_capacity is None:
-        st = L.canny_hip_curves_from_bits(_hp(b), height, width, min_length, None, 0, C.byref(k), None, None, 0, C.byref(n))
-        if st:
-            raise CannyHipError(st, "curves_from_bits")
+        _ok(L.canny_hip_curves_from_bits(_hp(b), height, width, min_length, None, 0, C.byref(k), None, None, 0, C.byref(n)),
+            "curves_from_bits")
     cap = k.value if capacity is None else int(capacity)
     pcap = n.value if point_capacity is None else int(point_capacity)
     records = np.empty((cap, CURVE_RECORD), np.int32) if want_records else None
     chain = np.zeros(cap + 1, np.uint64)
     points = np.empty(pcap, np.int32)
-    st = L.canny_hip_curves_from_bits(_hp(b), height, width, min_length, _hp(records) if want_records and cap else None, cap,
-                                      C.byref(k), _hp(chain), _hp(points) if pcap else None, pcap, C.byref(n))
-    if st:
-        raise CannyHipError(st, "curves_from_bits")
+    _ok(L.canny_hip_curves_from_bits(_hp(b), height, width, min_length, _hp(records) if want_records and cap else None, cap,
+                                     C.byref(k), _hp(chain), _hp(points) if pcap else None, pcap, C.byref(n)), "curves_from_bits")
     fit = min(cap, k.value)
     return (records[:fit] if want_records else None, chain[:fit + 1], points[:min(pcap, int(chain[fit]))], k.value, n.value)
 
@@ -682,11 +673,7 @@ def curves_from_bits(bits, height: int, width: int, min_length: int = 1, want_re
 def curves_plan(n_frames: int, height: int, width: int) -> "LaunchPlan":
     """Host-only: the launch plan of the edge curves' row kernels (count and write: one wave per image row of the batch and
     trip) for a batch of these sizes; fields as launch_plan."""
-    out = np.zeros(5, np.uint64)
-    st = load().canny_hip_selftest_curves_plan(int(n_frames), int(height), int(width), _hp(out))
-    if st:
-        raise CannyHipError(st, "selftest_curves_plan")
-    return LaunchPlan(*(int(v) for v in out))
+    return _plan("curves_plan", int(n_frames), int(height), int(width))
 
 
 EDT_NONE = 0x7FFFFFFF                                           # CANNY_HIP_EDT_NONE: dist2 of a frame without edge pixels
@@ -708,10 +695,8 @@ def edt_from_bits(bits, height: int, width: int, want_dist2: bool = True, want_d
     d2 = np.empty(shape, np.int32) if want_dist2 else None
     d = np.empty(shape, np.float32) if want_dist else None
     nn = np.empty(shape, np.int32) if want_nearest else None
-    st = load().canny_hip_edt_from_bits(_hp(b), height, width, _hp(d2) if want_dist2 else None,
-                                        _hp(d) if want_dist else None, _hp(nn) if want_nearest else None)
-    if st:
-        raise CannyHipError(st, "edt_from_bits")
+    _ok(load().canny_hip_edt_from_bits(_hp(b), height, width, _hp(d2) if want_dist2 else None,
+                                       _hp(d) if want_dist else None, _hp(nn) if want_nearest else None), "edt_from_bits")
     return d2, d, nn
 
 
@@ -768,11 +753,9 @@ def hough_segments_from_bits(bits, height: int, width: int, bases, rho: float = 
     n = C.c_int(0)
 
     def run(buf, cap):
-        st = L.canny_hip_hough_segments_from_bits(_hp(b), height, width, rho, theta, min_theta, max_theta,
-                                                  _hp(ba) if ba.size else None, int(ba.size), min_length, max_gap,
-                                                  exclusive, _hp(buf), cap, C.byref(n))
-        if st:
-            raise CannyHipError(st, "hough_segments_from_bits")
+        _ok(L.canny_hip_hough_segments_from_bits(_hp(b), height, width, rho, theta, min_theta, max_theta,
+                                                 _hp(ba) if ba.size else None, int(ba.size), min_length, max_gap,
+                                                 exclusive, _hp(buf), cap, C.byref(n)), "hough_segments_from_bits")
 
     if segments_max is None:
         run(np.empty(SEGMENT_INTS, np.int32), 1)
@@ -793,9 +776,7 @@ CIRCLE_DTYPE = np.dtype([("x", np.float32), ("y", np.float32), ("x2", np.int32),
 def hough_circles_step_of(gx: int, gy: int) -> Tuple[int, int]:
     """Host-only: the step (sx, sy) of one gradient as the rule of include/canny_hip.h defines it."""
     sx, sy = C.c_int(0), C.c_int(0)
-    st = load().canny_hip_hough_circles_step_of(int(gx), int(gy), C.byref(sx), C.byref(sy))
-    if st:
-        raise CannyHipError(st, "hough_circles_step_of")
+    _ok(load().canny_hip_hough_circles_step_of(int(gx), int(gy), C.byref(sx), C.byref(sy)), "hough_circles_step_of")
     return sx.value, sy.value
 
 
@@ -816,11 +797,10 @@ def hough_circles_from_bits(bits, gx, gy, height: int, width: int, min_radius: i
     acc = np.zeros(((height + c - 1) // c + 2, (width + c - 1) // c + 2), np.int32) if want_accum else None
     buf = out if out is not None else np.empty(max(int(centres_max), 1) * CIRCLE_INTS, np.int32)
     n, peaks = C.c_int(0), C.c_int(0)
-    st = load().canny_hip_hough_circles_from_bits(_hp(b), _hp(px), _hp(py), height, width, min_radius, max_radius,
-                                                  cell_shift, threshold, support_threshold, min_dist, centres_max,
-                                                  _hp(buf), C.byref(n), C.byref(peaks), _hp(acc) if want_accum else None)
-    if st:
-        raise CannyHipError(st, "hough_circles_from_bits")
+    _ok(load().canny_hip_hough_circles_from_bits(_hp(b), _hp(px), _hp(py), height, width, min_radius, max_radius,
+                                                 cell_shift, threshold, support_threshold, min_dist, centres_max,
+                                                 _hp(buf), C.byref(n), C.byref(peaks), _hp(acc) if want_accum else None),
+        "hough_circles_from_bits")
     rec = buf[:n.value * CIRCLE_INTS].reshape(n.value, CIRCLE_INTS)
     return (rec, peaks.value, acc) if want_accum else (rec, peaks.value)
 
@@ -839,10 +819,9 @@ def edgels_from_plane(plane, points) -> np.ndarray:
         raise ValueError("expected a 2-D uint8 or int16 plane")
     pts = np.ascontiguousarray(points, dtype=np.uint32).reshape(-1)
     rec = np.empty((pts.size, EDGEL_INTS), np.int32)
-    st = load().canny_hip_edgels_from_plane(_hp(a), int(a.dtype == np.uint8), a.shape[0], a.shape[1],
-                                            _hp(pts) if pts.size else None, pts.size, _hp(rec) if pts.size else None)
-    if st:
-        raise CannyHipError(st, "edgels_from_plane")
+    _ok(load().canny_hip_edgels_from_plane(_hp(a), int(a.dtype == np.uint8), a.shape[0], a.shape[1],
+                                           _hp(pts) if pts.size else None, pts.size, _hp(rec) if pts.size else None),
+        "edgels_from_plane")
     return rec
 
 
@@ -873,11 +852,7 @@ def edgels_flags(rec) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
 def edgels_plan(n_frames: int, height: int, width: int, n_points: int) -> "LaunchPlan":
     """Host-only: the launch plan of the index-driven edgel kernel (Context.dev_edgels_at) for a frame's list of n_points
     entries; fields as launch_plan."""
-    out = np.zeros(5, np.uint64)
-    st = load().canny_hip_selftest_edgels_plan(int(n_frames), int(height), int(width), int(n_points), _hp(out))
-    if st:
-        raise CannyHipError(st, "selftest_edgels_plan")
-    return LaunchPlan(*(int(v) for v in out))
+    return _plan("edgels_plan", int(n_frames), int(height), int(width), int(n_points))
 
 
 LINE_FIT_INTS = 12
@@ -903,12 +878,10 @@ def line_fits_from_plane(bits, plane, bases, segments, rho: float = 1.0, theta: 
     bs = np.ascontiguousarray(bases, dtype=np.uint32).reshape(-1)
     seg = np.ascontiguousarray(segments, dtype=np.int32).reshape(-1, SEGMENT_INTS)
     fits = np.empty((seg.shape[0], LINE_FIT_INTS), np.int32)
-    st = load().canny_hip_line_fits_from_plane(_hp(b), _hp(a), int(a.dtype == np.uint8), h, w, rho, numangle, numrho,
-                                               _hp(tc), _hp(ts), _hp(bs) if bs.size else None, bs.size,
-                                               _hp(seg) if seg.size else None, seg.shape[0], int(options),
-                                               _hp(fits) if seg.size else None)
-    if st:
-        raise CannyHipError(st, "line_fits_from_plane")
+    _ok(load().canny_hip_line_fits_from_plane(_hp(b), _hp(a), int(a.dtype == np.uint8), h, w, rho, numangle, numrho,
+                                              _hp(tc), _hp(ts), _hp(bs) if bs.size else None, bs.size,
+                                              _hp(seg) if seg.size else None, seg.shape[0], int(options),
+                                              _hp(fits) if seg.size else None), "line_fits_from_plane")
     return fits
 
 
@@ -917,9 +890,7 @@ def line_fits_finish(moments) -> np.ndarray:
     Suv, Svv, ddx, ddy) -> (k, 6) int32 (mu, mv, dx_q30, dy_q30, n, DEGENERATE or 0)."""
     m = np.ascontiguousarray(moments, dtype=np.int64).reshape(-1, 8)
     out = np.empty((m.shape[0], 6), np.int32)
-    st = load().canny_hip_line_fits_finish(_hp(m), m.shape[0], _hp(out))
-    if st:
-        raise CannyHipError(st, "line_fits_finish")
+    _ok(load().canny_hip_line_fits_finish(_hp(m), m.shape[0], _hp(out)), "line_fits_finish")
     return out
 
 
@@ -958,11 +929,9 @@ def circle_fits_from_plane(bits, plane, circles, band: int = 1, trim_q8: int = 0
         raise ValueError("bits must hold height * ceil(width / 8) bytes")
     rec = np.ascontiguousarray(circles, dtype=np.int32).reshape(-1, CIRCLE_INTS)
     fits = np.empty((rec.shape[0], CIRCLE_FIT_INTS), np.int32)
-    st = load().canny_hip_circle_fits_from_plane(_hp(b), _hp(a), int(a.dtype == np.uint8), h, w,
-                                                 _hp(rec) if rec.size else None, rec.shape[0], int(band), int(trim_q8),
-                                                 int(options), _hp(fits) if rec.size else None)
-    if st:
-        raise CannyHipError(st, "circle_fits_from_plane")
+    _ok(load().canny_hip_circle_fits_from_plane(_hp(b), _hp(a), int(a.dtype == np.uint8), h, w,
+                                                _hp(rec) if rec.size else None, rec.shape[0], int(band), int(trim_q8),
+                                                int(options), _hp(fits) if rec.size else None), "circle_fits_from_plane")
     return fits
 
 
@@ -971,9 +940,7 @@ def circle_fits_finish(moments) -> np.ndarray:
     Suu, Suv, Svv, Suz low, Suz high, Svz low, Svz high, band) -> (k, 4) int32 (move_x, move_y, n, DEGENERATE or 0)."""
     m = np.ascontiguousarray(moments, dtype=np.int64).reshape(-1, CIRCLE_FIT_MOMENT_WORDS)
     out = np.empty((m.shape[0], 4), np.int32)
-    st = load().canny_hip_circle_fits_finish(_hp(m), m.shape[0], _hp(out))
-    if st:
-        raise CannyHipError(st, "circle_fits_finish")
+    _ok(load().canny_hip_circle_fits_finish(_hp(m), m.shape[0], _hp(out)), "circle_fits_finish")
     return out
 
 
@@ -1012,9 +979,7 @@ CORNER_DTYPE = np.dtype([("x", np.int64), ("y", np.int64), ("response", np.int64
 def corner_response_of(sxx: int, syy: int, sxy: int, mode: int = CORNERS_MIN_EIGEN, k_q8: int = 0) -> int:
     """Host-only: the response R of the rule for one tensor (Sxx, Syy, Sxy)."""
     r = C.c_longlong(0)
-    st = load().canny_hip_corner_response_of(int(sxx), int(syy), int(sxy), int(mode), int(k_q8), C.byref(r))
-    if st:
-        raise CannyHipError(st, "corner_response_of")
+    _ok(load().canny_hip_corner_response_of(int(sxx), int(syy), int(sxy), int(mode), int(k_q8), C.byref(r)), "corner_response_of")
     return r.value
 
 
@@ -1029,11 +994,10 @@ def corners_from_plane(plane, mode: int = CORNERS_MIN_EIGEN, block: int = 3, k_q
     rec = np.zeros((max(int(corners_max), 1), CORNER_WORDS), np.int64)
     resp = np.zeros((h, w), np.int64) if want_response else None
     n, nc, rmax = C.c_int(0), C.c_int(0), C.c_longlong(0)
-    st = load().canny_hip_corners_from_plane(_hp(a), h, w, int(mode), int(block), int(k_q8), int(quality_q16),
-                                             int(min_response), int(min_dist), int(corners_max), _hp(rec), C.byref(n),
-                                             C.byref(nc), C.byref(rmax), _hp(resp) if want_response else None)
-    if st:
-        raise CannyHipError(st, "corners_from_plane")
+    _ok(load().canny_hip_corners_from_plane(_hp(a), h, w, int(mode), int(block), int(k_q8), int(quality_q16),
+                                            int(min_response), int(min_dist), int(corners_max), _hp(rec), C.byref(n),
+                                            C.byref(nc), C.byref(rmax), _hp(resp) if want_response else None),
+        "corners_from_plane")
     return rec[:n.value].copy(), nc.value, rmax.value, resp
 
 
@@ -1041,11 +1005,7 @@ def corners_plan(which, n_frames: int = 1, height: int = 2, width: int = 2, n: i
     """Host-only: (LaunchPlan, frames per chunk) of a capped corners launch: "tiles" (the passes over the plane, sized by
     one frame) or "arith" (dev_corners_arith on n triples)."""
     k = CORNERS_PLANS.index(which) if isinstance(which, str) else int(which)
-    out = np.zeros(6, np.uint64)
-    st = load().canny_hip_selftest_corners_plan(k, int(n_frames), int(height), int(width), int(n), _hp(out))
-    if st:
-        raise CannyHipError(st, "selftest_corners_plan")
-    return LaunchPlan(*(int(v) for v in out[:5])), int(out[5])
+    return _plan("corners_plan", k, int(n_frames), int(height), int(width), int(n), n=6)
 
 
 # ---- corner descriptors and Hamming matching (DESIGN.md section 30) -------------------------------------------------------
@@ -1060,9 +1020,7 @@ DESC_MATCH_DTYPE = np.dtype([("j", np.int32), ("d1", np.int32), ("d2", np.int32)
 def descriptor_pattern(k: int):
     """Host-only: int8 [256, 4], (ax, ay, bx, by) of every test in rotation k."""
     out = np.zeros((DESC_BITS, 4), np.int8)
-    st = load().canny_hip_descriptor_pattern(int(k), _hp(out))
-    if st:
-        raise CannyHipError(st, "descriptor_pattern")
+    _ok(load().canny_hip_descriptor_pattern(int(k), _hp(out)), "descriptor_pattern")
     return out
 
 
@@ -1076,10 +1034,9 @@ def corner_descriptors_from_plane(plane, corners, steered: bool = False):
     rec = np.zeros((len(c), CORNER_WORDS), np.int64)
     rec[:, :min(c.shape[1], CORNER_WORDS)] = c[:, :CORNER_WORDS]
     desc, meta = np.zeros((len(c), DESC_WORDS), np.uint64), np.zeros(len(c), np.int32)
-    st = load().canny_hip_corner_descriptors_from_plane(_hp(a), a.shape[0], a.shape[1], _hp(rec), len(c),
-                                                        DESC_STEERED if steered else 0, _hp(desc), _hp(meta))
-    if st:
-        raise CannyHipError(st, "corner_descriptors_from_plane")
+    _ok(load().canny_hip_corner_descriptors_from_plane(_hp(a), a.shape[0], a.shape[1], _hp(rec), len(c),
+                                                       DESC_STEERED if steered else 0, _hp(desc), _hp(meta)),
+        "corner_descriptors_from_plane")
     return desc, meta
 
 
@@ -1089,11 +1046,9 @@ def match_descriptors(q, t, max_distance: int = 64, ratio_q8: int = 205, options
     q = np.ascontiguousarray(q, np.uint64).reshape(-1, DESC_WORDS)
     t = np.ascontiguousarray(t, np.uint64).reshape(-1, DESC_WORDS)
     out, acc = np.zeros((len(q), MATCH_WORDS), np.int32), C.c_int(0)
-    st = load().canny_hip_match_descriptors(_hp(q) if len(q) else None, len(q), _hp(t) if len(t) else None, len(t),
-                                            int(max_distance), int(ratio_q8), int(options),
-                                            _hp(out) if len(q) else None, C.byref(acc))
-    if st:
-        raise CannyHipError(st, "match_descriptors")
+    _ok(load().canny_hip_match_descriptors(_hp(q) if len(q) else None, len(q), _hp(t) if len(t) else None, len(t),
+                                           int(max_distance), int(ratio_q8), int(options),
+                                           _hp(out) if len(q) else None, C.byref(acc)), "match_descriptors")
     return out, acc.value
 
 
@@ -1107,11 +1062,7 @@ def descriptors_plan(which, n: int, stride: int):
     """Host-only: the LaunchPlan of a capped descriptor launch: "describe" (n frames, stride = corners_max) or "match" (n
     pairs, stride of the side held in registers)."""
     k = DESCRIPTORS_PLANS.index(which) if isinstance(which, str) else int(which)
-    out = np.zeros(5, np.uint64)
-    st = load().canny_hip_selftest_descriptors_plan(k, int(n), int(stride), _hp(out))
-    if st:
-        raise CannyHipError(st, "selftest_descriptors_plan")
-    return LaunchPlan(*(int(v) for v in out))
+    return _plan("descriptors_plan", k, int(n), int(stride))
 
 
 # ---- frame-to-frame motion from the corner matches (DESIGN.md section 31) -------------------------------------------------
@@ -1141,22 +1092,16 @@ def estimate_motion(q_corners, t_corners, matches, model: int = MOTION_SIMILARIT
     if len(mt) != len(q):
         raise ValueError("one match row per query record")
     out, flags = np.zeros(MOTION_WORDS, np.int64), np.zeros(len(q), np.int32)
-    st = load().canny_hip_estimate_motion(_hp(q) if len(q) else None, len(q), _hp(t) if len(t) else None, len(t),
-                                          _hp(mt) if len(q) else None, int(model), int(thr_q4), int(hypotheses),
-                                          int(seed) & 0xFFFFFFFF, _hp(out), _hp(flags) if len(q) else None)
-    if st:
-        raise CannyHipError(st, "estimate_motion")
+    _ok(load().canny_hip_estimate_motion(_hp(q) if len(q) else None, len(q), _hp(t) if len(t) else None, len(t),
+                                         _hp(mt) if len(q) else None, int(model), int(thr_q4), int(hypotheses),
+                                         int(seed) & 0xFFFFFFFF, _hp(out), _hp(flags) if len(q) else None), "estimate_motion")
     return out, flags
 
 
 def motion_plan(which, n_pairs: int, hypotheses: int = 1):
     """Host-only: the LaunchPlan of a capped launch of the motion estimate: "gather", "score" or "refit"."""
     k = MOTION_PLANS.index(which) if isinstance(which, str) else int(which)
-    out = np.zeros(5, np.uint64)
-    st = load().canny_hip_selftest_motion_plan(k, int(n_pairs), int(hypotheses), _hp(out))
-    if st:
-        raise CannyHipError(st, "selftest_motion_plan")
-    return LaunchPlan(*(int(v) for v in out))
+    return _plan("motion_plan", k, int(n_pairs), int(hypotheses))
 
 
 # ---- frame alignment: the motions chained, frames warped (DESIGN.md section 32) ---------------------------------------------
@@ -1181,9 +1126,7 @@ def compose_motion(motion, first_frame: int = 0):
     into n_pairs + 1 transform records (XFORM_DTYPE); record k maps frame first_frame's pixels into frame first_frame + k."""
     m = _words(motion, MOTION_WORDS)
     out = np.zeros((len(m) + 1, XFORM_WORDS), np.int64)
-    st = load().canny_hip_compose_motion(_hp(m) if len(m) else None, len(m), int(first_frame), _hp(out))
-    if st:
-        raise CannyHipError(st, "compose_motion")
+    _ok(load().canny_hip_compose_motion(_hp(m) if len(m) else None, len(m), int(first_frame), _hp(out)), "compose_motion")
     return out.view(XFORM_DTYPE).reshape(-1)
 
 
@@ -1196,10 +1139,8 @@ def warp_frames(src, xforms, out_h: int, out_w: int, interp: int = WARP_BILINEAR
     x = _words(xforms, XFORM_WORDS)
     out = np.zeros((len(x), max(int(out_h), 0), max(int(out_w), 0)), np.uint8)
     valid = np.zeros((len(x), max(int(out_h), 0), (max(int(out_w), 0) + 7) // 8), np.uint8)
-    st = load().canny_hip_warp_frames(_hp(a), a.shape[0], a.shape[1], a.shape[2], _hp(x) if len(x) else None, len(x),
-                                      int(out_h), int(out_w), int(interp), int(border), _hp(out), _hp(valid))
-    if st:
-        raise CannyHipError(st, "warp_frames")
+    _ok(load().canny_hip_warp_frames(_hp(a), a.shape[0], a.shape[1], a.shape[2], _hp(x) if len(x) else None, len(x),
+                                     int(out_h), int(out_w), int(interp), int(border), _hp(out), _hp(valid)), "warp_frames")
     return out, valid
 
 
@@ -1208,11 +1149,7 @@ WarpTile = collections.namedtuple("WarpTile", "staged x0 y0 x1 y1")
 
 def warp_plan(n_out: int, out_h: int, out_w: int):
     """Host-only: the LaunchPlan of the warp's capped launch (one 64 x 16 output tile per workgroup and trip)."""
-    out = np.zeros(5, np.uint64)
-    st = load().canny_hip_selftest_warp_plan(int(n_out), int(out_h), int(out_w), _hp(out), None, 1, 1, 0, 0, 0, None)
-    if st:
-        raise CannyHipError(st, "selftest_warp_plan")
-    return LaunchPlan(*(int(v) for v in out))
+    return _plan("warp_plan", int(n_out), int(out_h), int(out_w), tail=(None, 1, 1, 0, 0, 0, None))
 
 
 def warp_tile(xform, src_h: int, src_w: int, out_h: int, out_w: int, interp: int, tile_x: int, tile_y: int):
@@ -1220,10 +1157,8 @@ def warp_tile(xform, src_h: int, src_w: int, out_h: int, out_w: int, interp: int
     x1, y1) -- staged in LDS or gathered directly, and the clipped source footprint (inclusive; x1 < x0: empty)."""
     x = _words(xform, XFORM_WORDS)[:1]
     out, box = np.zeros(5, np.uint64), np.zeros(5, np.int32)
-    st = load().canny_hip_selftest_warp_plan(1, int(out_h), int(out_w), _hp(out), _hp(x), int(src_h), int(src_w), int(interp),
-                                             int(tile_x), int(tile_y), _hp(box))
-    if st:
-        raise CannyHipError(st, "selftest_warp_plan")
+    _ok(load().canny_hip_selftest_warp_plan(1, int(out_h), int(out_w), _hp(out), _hp(x), int(src_h), int(src_w), int(interp),
+                                            int(tile_x), int(tile_y), _hp(box)), "selftest_warp_plan")
     return WarpTile(bool(box[0]), *(int(v) for v in box[1:]))
 
 
@@ -1264,10 +1199,8 @@ def fuse_frames(frames, valid_bits=None, group_len: Optional[int] = None, group_
     ok = 1 <= group_len <= n and group_step >= 1
     n_groups = fuse_groups(n, group_len, group_step) if ok else 1
     fused, count = np.zeros((n_groups, h, w), np.uint8), np.zeros((n_groups, h, w), np.uint8)
-    st = load().canny_hip_fuse_frames(_hp(a), _hp(v) if v is not None else None, n, h, w, group_len, group_step, int(op),
-                                      int(fill), int(min_count), _hp(fused), _hp(count))
-    if st:
-        raise CannyHipError(st, "fuse_frames")
+    _ok(load().canny_hip_fuse_frames(_hp(a), _hp(v) if v is not None else None, n, h, w, group_len, group_step, int(op),
+                                     int(fill), int(min_count), _hp(fused), _hp(count)), "fuse_frames")
     return fused, count
 
 
@@ -1289,11 +1222,9 @@ def change_mask(frames, background, valid_bits=None, bg_count=None, frames_per_b
     if bg.shape != (n_bg, h, w) or (bc is not None and bc.shape != bg.shape):
         raise ValueError("expected background (and bg_count) uint8 [ceil(n_frames / frames_per_background), H, W]")
     mask, changed = np.zeros((n, h, (w + 7) // 8), np.uint8), np.zeros(n, np.int64)
-    st = load().canny_hip_change_mask(_hp(a), _hp(v) if v is not None else None, n, h, w, _hp(bg),
-                                      _hp(bc) if bc is not None else None, per, int(thr), int(min_count), _hp(mask),
-                                      _hp(changed))
-    if st:
-        raise CannyHipError(st, "change_mask")
+    _ok(load().canny_hip_change_mask(_hp(a), _hp(v) if v is not None else None, n, h, w, _hp(bg),
+                                     _hp(bc) if bc is not None else None, per, int(thr), int(min_count), _hp(mask),
+                                     _hp(changed)), "change_mask")
     return mask, changed
 
 
@@ -1302,11 +1233,7 @@ def fuse_plan(which, n_frames: int, h: int, w: int, group_len: int = 1, group_st
     which is a name of FUSE_PARTS or its number.  "fuse": the tiles of the n_groups fused planes, aux = the route automatic
     takes for a MEDIAN of group_len frames; "mask": the tiles of the n_frames masks."""
     k = FUSE_PARTS.index(which) if isinstance(which, str) else int(which)
-    out = np.zeros(5, np.uint64)
-    st = load().canny_hip_selftest_fuse_plan(k, int(n_frames), int(h), int(w), int(group_len), int(group_step), _hp(out))
-    if st:
-        raise CannyHipError(st, "selftest_fuse_plan")
-    return LaunchPlan(*(int(v) for v in out))
+    return _plan("fuse_plan", k, int(n_frames), int(h), int(w), int(group_len), int(group_step))
 
 
 # ---- binary morphology on packed bit maps (DESIGN.md section 34) ------------------------------------------------------------
@@ -1324,9 +1251,7 @@ def morph_element(shape: int, kw: int, kh: Optional[int] = None):
     is the offset (i - kw // 2, j - kh // 2)."""
     kh = kw if kh is None else kh
     rows = np.zeros(max(int(kh), 1), np.uint32)
-    st = load().canny_hip_morph_element(int(shape), int(kw), int(kh), _hp(rows))
-    if st:
-        raise CannyHipError(st, "morph_element")
+    _ok(load().canny_hip_morph_element(int(shape), int(kw), int(kh), _hp(rows)), "morph_element")
     return rows
 
 
@@ -1346,21 +1271,15 @@ def morph_bits(bits, w: int, op: int, rows, kw: int, kh: int, border: int = MORP
     n, h, _ = a.shape
     r = _morph_rows(rows, kh)
     out, counts = np.zeros_like(a), np.zeros(n, np.int64)
-    st = load().canny_hip_morph_bits(_hp(a), n, h, int(w), int(op), _hp(r), int(kw), int(kh), int(border), int(iterations),
-                                     _hp(out), _hp(counts))
-    if st:
-        raise CannyHipError(st, "morph_bits")
+    _ok(load().canny_hip_morph_bits(_hp(a), n, h, int(w), int(op), _hp(r), int(kw), int(kh), int(border), int(iterations),
+                                    _hp(out), _hp(counts)), "morph_bits")
     return out, counts
 
 
 def morph_plan(n_frames: int, h: int, w: int, kw: int = 3, kh: int = 3):
     """Host-only: the LaunchPlan of one primitive step of the morphology (one tile of 8 words x 64 rows per workgroup and
     trip); aux = the route automatic takes for a full rectangle of kw x kh (1 general, 2 separable)."""
-    out = np.zeros(5, np.uint64)
-    st = load().canny_hip_selftest_morph_plan(int(n_frames), int(h), int(w), int(kw), int(kh), _hp(out))
-    if st:
-        raise CannyHipError(st, "selftest_morph_plan")
-    return LaunchPlan(*(int(v) for v in out))
+    return _plan("morph_plan", int(n_frames), int(h), int(w), int(kw), int(kh))
 
 
 # ---- chamfer template matching (DESIGN.md section 26) --------------------------------------------------------------------
@@ -1433,23 +1352,16 @@ def chamfer_from_dist2(dist2, templates, trunc_q4: int, max_mean_q4: int, min_di
     rec = np.zeros((max(int(matches_max), 1), MATCH_INTS), np.int32)
     scores = np.zeros((max(T, 1), h, w), np.uint32) if want_scores else None
     n, nc = C.c_int(0), C.c_int(0)
-    st = load().canny_hip_chamfer_from_dist2(_hp(d), h, w, _hp(off), _hp(pts), T, trunc_q4, max_mean_q4, min_dist,
-                                             matches_max, _hp(rec), C.byref(n), C.byref(nc),
-                                             _hp(scores) if want_scores else None)
-    if st:
-        raise CannyHipError(st, "chamfer_from_dist2")
+    _ok(load().canny_hip_chamfer_from_dist2(_hp(d), h, w, _hp(off), _hp(pts), T, trunc_q4, max_mean_q4, min_dist,
+                                            matches_max, _hp(rec), C.byref(n), C.byref(nc),
+                                            _hp(scores) if want_scores else None), "chamfer_from_dist2")
     return rec[:n.value].copy(), nc.value, scores
 
 
 def chamfer_plan(which, n_frames: int, height: int, width: int, n_templates: int, with_scores: bool = False):
     """Host-only: (LaunchPlan, frames per chunk) of a capped chamfer launch ("cost" or "cells") for a full chunk."""
     k = CHAMFER_PLANS.index(which) if isinstance(which, str) else int(which)
-    out = np.zeros(6, np.uint64)
-    st = load().canny_hip_selftest_chamfer_plan(k, int(n_frames), int(height), int(width), int(n_templates),
-                                                int(bool(with_scores)), _hp(out))
-    if st:
-        raise CannyHipError(st, "selftest_chamfer_plan")
-    return LaunchPlan(*(int(v) for v in out[:5])), int(out[5])
+    return _plan("chamfer_plan", k, int(n_frames), int(height), int(width), int(n_templates), int(bool(with_scores)), n=6)
 
 
 def chamfer_bands(templates, t: int = 0, csr=None) -> Tuple[int, int, int, int]:
@@ -1457,9 +1369,7 @@ def chamfer_bands(templates, t: int = 0, csr=None) -> Tuple[int, int, int, int]:
     score kernel for a template list."""
     off, pts = csr if csr is not None else chamfer_csr(templates)
     out = np.zeros(4, np.int32)
-    st = load().canny_hip_selftest_chamfer_bands(_hp(off), _hp(pts), len(off) - 1, int(t), _hp(out))
-    if st:
-        raise CannyHipError(st, "selftest_chamfer_bands")
+    _ok(load().canny_hip_selftest_chamfer_bands(_hp(off), _hp(pts), len(off) - 1, int(t), _hp(out)), "selftest_chamfer_bands")
     return tuple(int(v) for v in out)
 
 
@@ -1476,19 +1386,16 @@ def auto_thresholds_from_histogram(hist, rule="median", low: float = 0.67, high:
     if h.shape != (257,):
         raise ValueError(f"expected 257 bins, got shape {h.shape}")
     lo, hi = C.c_int(0), C.c_int(0)
-    st = load().canny_hip_auto_thresholds_from_histogram(_hp(h), int(rule) if isinstance(rule, (int, np.integer))
-                                                         else _rule(rule), low, high, C.byref(lo), C.byref(hi))
-    if st:
-        raise CannyHipError(st, "auto_thresholds_from_histogram")
+    _ok(load().canny_hip_auto_thresholds_from_histogram(_hp(h), int(rule) if isinstance(rule, (int, np.integer))
+                                                        else _rule(rule), low, high, C.byref(lo), C.byref(hi)),
+        "auto_thresholds_from_histogram")
     return lo.value, hi.value
 
 
 def march_order(n_segs: int, n_strips: int) -> np.ndarray:
     """Host-only: the (segment, strip) cell each wave index of a marching launch takes within a frame (border first)."""
     out = np.empty((n_segs * n_strips, 2), np.int32)
-    st = load().canny_hip_selftest_march_order(n_segs, n_strips, out.ctypes.data_as(C.c_void_p))
-    if st:
-        raise CannyHipError(st, "selftest_march_order")
+    _ok(load().canny_hip_selftest_march_order(n_segs, n_strips, out.ctypes.data_as(C.c_void_p)), "selftest_march_order")
     return out
 
 
@@ -1503,12 +1410,7 @@ def launch_plan(kind, n_frames: int = 1, height: int = 1, width: int = 1, extra:
     per_group)) -- 2 or more means some workgroup takes a second item --, aux: rows per wave for "edt_rows", else 0.
     The launchers take their grids from the helpers this reports, so it cannot drift from what runs."""
     k = PLAN_KINDS.index(kind) if isinstance(kind, str) else int(kind)
-    out = np.zeros(5, np.uint64)
-    st = load().canny_hip_selftest_launch_plan(k, int(n_frames), int(height), int(width), int(extra),
-                                               out.ctypes.data_as(C.c_void_p))
-    if st:
-        raise CannyHipError(st, "selftest_launch_plan")
-    return LaunchPlan(*(int(v) for v in out))
+    return _plan("launch_plan", k, int(n_frames), int(height), int(width), int(extra))
 
 
 def fma_div_table():
@@ -1525,9 +1427,7 @@ def fma_div_table():
 def shard_range(n_frames: int, rank: int, world: int) -> Tuple[int, int]:
     """Contiguous frame range of shard ``rank`` of ``world`` (pure host logic, no GPU needed)."""
     b, e = C.c_int(0), C.c_int(0)
-    st = load().canny_hip_shard_range(n_frames, rank, world, C.byref(b), C.byref(e))
-    if st:
-        raise CannyHipError(st, "canny_hip_shard_range")
+    _ok(load().canny_hip_shard_range(n_frames, rank, world, C.byref(b), C.byref(e)), "canny_hip_shard_range")
     return b.value, e.value
 
 
@@ -1560,9 +1460,7 @@ class Context:
     def __init__(self, device: int = 0):
         self._L = load()
         h = C.c_void_p()
-        st = self._L.canny_hip_ctx_create(C.byref(h), device)
-        if st:
-            raise CannyHipError(st, "canny_hip_ctx_create")
+        _ok(self._L.canny_hip_ctx_create(C.byref(h), device), "canny_hip_ctx_create")
         self._h = h
 
     def close(self):
@@ -1632,10 +1530,14 @@ class Context:
     def profile_reset(self):
         self._check(self._L.canny_hip_profile_reset(self._h), "profile_reset")
 
-    def profile_get(self, stage: int) -> Tuple[float, int]:
+    def _profile_part(self, fn_name: str, part: int) -> Tuple[float, int]:
+        """(total ms, launch groups) of one slot through canny_hip_<fn_name>: what every *_profile_get method returns."""
         ms, n = C.c_double(0), C.c_long(0)
-        self._check(self._L.canny_hip_profile_get(self._h, stage, C.byref(ms), C.byref(n)), "profile_get")
+        self._check(getattr(self._L, "canny_hip_" + fn_name)(self._h, part, C.byref(ms), C.byref(n)), fn_name)
         return ms.value, n.value
+
+    def profile_get(self, stage: int) -> Tuple[float, int]:
+        return self._profile_part("profile_get", stage)
 
     # ---- host-array stage API -----------------------------------------------------------------
     def gaussian(self, img, sigma: float) -> np.ndarray:
@@ -1867,9 +1769,7 @@ class Context:
                                                        v(d_t or None), v(d_refined or None)), "dev_edgels_arith")
 
     def edgels_profile_get(self, part: int) -> Tuple[float, int]:
-        ms, n = C.c_double(0), C.c_long(0)
-        self._check(self._L.canny_hip_edgels_profile_get(self._h, part, C.byref(ms), C.byref(n)), "edgels_profile_get")
-        return ms.value, n.value
+        return self._profile_part("edgels_profile_get", part)
 
     # ---- connected components of the finished map ----------------------------------------
     def canny_components(self, imgs, sigma: float, min_val: int, max_val: int, min_area: int = 1,
@@ -1922,10 +1822,7 @@ class Context:
 
     def components_profile_get(self, part: int) -> Tuple[float, int]:
         """(total ms, launch groups) of part 0 link, 1 resolve, 2 number, 3 write (CC_PARTS)."""
-        ms, n = C.c_double(0.0), C.c_long(0)
-        self._check(self._L.canny_hip_components_profile_get(self._h, part, C.byref(ms), C.byref(n)),
-                    "components_profile_get")
-        return ms.value, n.value
+        return self._profile_part("components_profile_get", part)
 
     # ---- outer contour chains of the finished map (DESIGN.md section 17) ----------------------------------------
     def canny_contours(self, imgs, sigma: float, min_val: int, max_val: int, min_area: int = 1, want_stats: bool = True,
@@ -1987,10 +1884,7 @@ class Context:
 
     def contours_profile_get(self, part: int) -> Tuple[float, int]:
         """(total ms, launch groups) of part 0 label, 1 count, 2 write, 3 stats (CONTOUR_PARTS)."""
-        ms, n = C.c_double(0.0), C.c_long(0)
-        self._check(self._L.canny_hip_contours_profile_get(self._h, part, C.byref(ms), C.byref(n)),
-                    "contours_profile_get")
-        return ms.value, n.value
+        return self._profile_part("contours_profile_get", part)
 
     # ---- edge curves: the map linked into ordered chains (DESIGN.md section 28) ------------------------------------
     def canny_curves(self, imgs, sigma: float, min_val: int, max_val: int, min_length: int = 1, want_records: bool = True,
@@ -2053,9 +1947,7 @@ class Context:
 
     def curves_profile_get(self, part: int) -> Tuple[float, int]:
         """(total ms, launch groups) of part 0 count, 1 write (CURVE_PARTS)."""
-        ms, n = C.c_double(0.0), C.c_long(0)
-        self._check(self._L.canny_hip_curves_profile_get(self._h, part, C.byref(ms), C.byref(n)), "curves_profile_get")
-        return ms.value, n.value
+        return self._profile_part("curves_profile_get", part)
 
     # ---- polygon approximation of the contour chains (DESIGN.md section 19) ---------------------------------------
     def canny_polygons(self, imgs, sigma: float, min_val: int, max_val: int, min_area: int = 1, epsilon: float = 0.0,
@@ -2135,10 +2027,7 @@ class Context:
 
     def polygons_profile_get(self, part: int) -> Tuple[float, int]:
         """(total ms, launch groups) of part 0 simplify, 1 scan, 2 emit (POLYGON_PARTS)."""
-        ms, n = C.c_double(0.0), C.c_long(0)
-        self._check(self._L.canny_hip_polygons_profile_get(self._h, part, C.byref(ms), C.byref(n)),
-                    "polygons_profile_get")
-        return ms.value, n.value
+        return self._profile_part("polygons_profile_get", part)
 
     # ---- contour shape measures (DESIGN.md section 27) ------------------------------------------------------------
     def canny_shapes(self, imgs, sigma: float, min_val: int, max_val: int, min_area: int = 1, want_stats: bool = False,
@@ -2212,9 +2101,7 @@ class Context:
 
     def shapes_profile_get(self, part: int) -> Tuple[float, int]:
         """(total ms, launch groups) of part 0 measure, 1 scan, 2 emit (SHAPE_PARTS)."""
-        ms, n = C.c_double(0.0), C.c_long(0)
-        self._check(self._L.canny_hip_shapes_profile_get(self._h, part, C.byref(ms), C.byref(n)), "shapes_profile_get")
-        return ms.value, n.value
+        return self._profile_part("shapes_profile_get", part)
 
     # ---- Euclidean distance transform of the finished map (DESIGN.md section 15) ---------------------------------
     def canny_edt(self, imgs, sigma: float, min_val: int, max_val: int, want_dist2: bool = True, want_dist: bool = True,
@@ -2254,9 +2141,7 @@ class Context:
 
     def edt_profile_get(self, part: int) -> Tuple[float, int]:
         """(total ms, launch groups) of part 0 rows, 1 columns (EDT_PARTS)."""
-        ms, n = C.c_double(0.0), C.c_long(0)
-        self._check(self._L.canny_hip_edt_profile_get(self._h, part, C.byref(ms), C.byref(n)), "edt_profile_get")
-        return ms.value, n.value
+        return self._profile_part("edt_profile_get", part)
 
     # ---- Hough lines of the finished map (cv::HoughLines semantics; DESIGN.md section 13) -----------------------
     def canny_hough(self, imgs, sigma: float, min_val: int, max_val: int, rho: float = 1.0, theta: float = np.pi / 180,
@@ -2316,9 +2201,7 @@ class Context:
 
     def hough_profile_get(self, part: int) -> Tuple[float, int]:
         """Accumulated device milliseconds and launch groups of a Hough part (0 vote, 1 peaks, 2 select + sort)."""
-        ms, n = C.c_double(0), C.c_long(0)
-        self._check(self._L.canny_hip_hough_profile_get(self._h, part, C.byref(ms), C.byref(n)), "hough_profile_get")
-        return ms.value, n.value
+        return self._profile_part("hough_profile_get", part)
 
     # ---- Hough line segments (DESIGN.md section 16) --------------------------------------------------------------
     def canny_hough_segments(self, imgs, sigma: float, min_val: int, max_val: int, rho: float = 1.0,
@@ -2382,10 +2265,7 @@ class Context:
 
     def hough_segments_profile_get(self, part: int) -> Tuple[float, int]:
         """(total ms, launch groups) of part 0 count, 1 emit, 2 exclusive (SEGMENT_PARTS)."""
-        ms, n = C.c_double(0), C.c_long(0)
-        self._check(self._L.canny_hip_hough_segments_profile_get(self._h, part, C.byref(ms), C.byref(n)),
-                    "hough_segments_profile_get")
-        return ms.value, n.value
+        return self._profile_part("hough_segments_profile_get", part)
 
     # ---- sub-pixel line fits (least-squares refit of the Hough segments from edgels; DESIGN.md section 24) -------
     def canny_hough_line_fits(self, imgs, sigma: float, min_val: int, max_val: int, rho: float = 1.0,
@@ -2461,10 +2341,7 @@ class Context:
 
     def line_fits_profile_get(self, part: int = 0) -> Tuple[float, int]:
         """(total ms, launch groups) of part 0, the fit kernel (LINE_FIT_PART_FIT)."""
-        ms, n = C.c_double(0), C.c_long(0)
-        self._check(self._L.canny_hip_line_fits_profile_get(self._h, part, C.byref(ms), C.byref(n)),
-                    "line_fits_profile_get")
-        return ms.value, n.value
+        return self._profile_part("line_fits_profile_get", part)
 
     # ---- Hough circles (cv::HoughCircles(HOUGH_GRADIENT) semantics; DESIGN.md section 18) ------------------------
     def canny_hough_circles(self, imgs, sigma: float, min_val: int, max_val: int, min_radius: int, max_radius: int,
@@ -2532,10 +2409,7 @@ class Context:
 
     def hough_circles_profile_get(self, part: int) -> Tuple[float, int]:
         """(total ms, launch groups) of part 0 vote, 1 centres, 2 radius, 3 accept (CIRCLE_PARTS)."""
-        ms, n = C.c_double(0), C.c_long(0)
-        self._check(self._L.canny_hip_hough_circles_profile_get(self._h, part, C.byref(ms), C.byref(n)),
-                    "hough_circles_profile_get")
-        return ms.value, n.value
+        return self._profile_part("hough_circles_profile_get", part)
 
     # ---- chamfer template matching on the distance transform (DESIGN.md section 26) -----------------------------
     def chamfer_set_create(self, templates=None, csr=None) -> int:
@@ -2609,9 +2483,7 @@ class Context:
 
     def chamfer_profile_get(self, part: int) -> Tuple[float, int]:
         """(total ms, launch groups) of part 0 cost, 1 score, 2 candidates, 3 accept (CHAMFER_PARTS)."""
-        ms, n = C.c_double(0), C.c_long(0)
-        self._check(self._L.canny_hip_chamfer_profile_get(self._h, part, C.byref(ms), C.byref(n)), "chamfer_profile_get")
-        return ms.value, n.value
+        return self._profile_part("chamfer_profile_get", part)
 
     # ---- corners, Harris / Shi-Tomasi on the smoothed plane (DESIGN.md section 29) ---------------------------------
     def dev_canny_corners(self, d_img: int, sigma: float, min_val: int, max_val: int, h: int, w: int, n: int, mode: int,
@@ -2667,9 +2539,7 @@ class Context:
 
     def corners_profile_get(self, part: int) -> Tuple[float, int]:
         """(total ms, launch groups) of part 0 max, 1 candidates, 2 collect, 3 accept (CORNER_PARTS)."""
-        ms, n = C.c_double(0), C.c_long(0)
-        self._check(self._L.canny_hip_corners_profile_get(self._h, part, C.byref(ms), C.byref(n)), "corners_profile_get")
-        return ms.value, n.value
+        return self._profile_part("corners_profile_get", part)
 
     # ---- corner descriptors and Hamming matching (DESIGN.md section 30) ---------------------------------------------
     def dev_canny_corner_descriptors(self, d_img: int, sigma: float, min_val: int, max_val: int, h: int, w: int, n: int,
@@ -2735,10 +2605,7 @@ class Context:
 
     def descriptors_profile_get(self, part: int) -> Tuple[float, int]:
         """(total ms, launch groups) of part 0 describe, 1 match, 2 reverse, 3 finalize (DESC_PARTS)."""
-        ms, n = C.c_double(0), C.c_long(0)
-        self._check(self._L.canny_hip_descriptors_profile_get(self._h, part, C.byref(ms), C.byref(n)),
-                    "descriptors_profile_get")
-        return ms.value, n.value
+        return self._profile_part("descriptors_profile_get", part)
 
     # ---- frame-to-frame motion from the corner matches (DESIGN.md section 31) ---------------------------------------
     def dev_estimate_motion(self, d_q_corners: int, d_q_counts: int, n_q_frames: int, stride_q: int, d_t_corners: int,
@@ -2835,9 +2702,7 @@ class Context:
 
     def warp_profile_get(self, part: int) -> Tuple[float, int]:
         """(total ms, launch groups) of part 0 compose, 1 warp (WARP_PARTS)."""
-        ms, n = C.c_double(0), C.c_long(0)
-        self._check(self._L.canny_hip_warp_profile_get(self._h, part, C.byref(ms), C.byref(n)), "warp_profile_get")
-        return ms.value, n.value
+        return self._profile_part("warp_profile_get", part)
 
     # ---- temporal fusion of aligned frames and change masks (DESIGN.md section 33) ------------------------------------
     def dev_fuse_frames(self, d_frames: int, d_valid_bits: int, n_frames: int, h: int, w: int, group_len: int,
@@ -2892,9 +2757,7 @@ class Context:
     def fuse_profile(self, part) -> Tuple[float, int]:
         """(total ms, launch groups) of part 0 fuse, 1 mask (FUSE_PARTS; a name or its number)."""
         k = FUSE_PARTS.index(part) if isinstance(part, str) else int(part)
-        ms, n = C.c_double(0), C.c_long(0)
-        self._check(self._L.canny_hip_fuse_profile_get(self._h, k, C.byref(ms), C.byref(n)), "fuse_profile_get")
-        return ms.value, n.value
+        return self._profile_part("fuse_profile_get", k)
 
     def selftest_fuse_mean(self):
         """The fuse kernels' rounded mean over every c = 1..255, s = 0..255 c, from the device: uint8 [255, FUSE_MEAN_ROW],
@@ -2938,15 +2801,11 @@ class Context:
 
     def morph_profile(self, part: int = 0) -> Tuple[float, int]:
         """(total ms, launch groups) of part 0, all primitive steps of the morphology calls."""
-        ms, n = C.c_double(0), C.c_long(0)
-        self._check(self._L.canny_hip_morph_profile_get(self._h, int(part), C.byref(ms), C.byref(n)), "morph_profile_get")
-        return ms.value, n.value
+        return self._profile_part("morph_profile_get", int(part))
 
     def motion_profile_get(self, part: int) -> Tuple[float, int]:
         """(total ms, launch groups) of part 0 gather, 1 score, 2 refit (MOTION_PARTS)."""
-        ms, n = C.c_double(0), C.c_long(0)
-        self._check(self._L.canny_hip_motion_profile_get(self._h, part, C.byref(ms), C.byref(n)), "motion_profile_get")
-        return ms.value, n.value
+        return self._profile_part("motion_profile_get", part)
 
     # ---- sub-pixel circle fits (least-squares refit of the Hough circles from edgels; DESIGN.md section 25) ------
     def canny_hough_circle_fits(self, imgs, sigma: float, min_val: int, max_val: int, min_radius: int, max_radius: int,
@@ -3009,10 +2868,7 @@ class Context:
 
     def circle_fits_profile_get(self, part: int = 0) -> Tuple[float, int]:
         """(total ms, launch groups) of part 0, the fit kernel (CIRCLE_FIT_PART_FIT)."""
-        ms, n = C.c_double(0), C.c_long(0)
-        self._check(self._L.canny_hip_circle_fits_profile_get(self._h, part, C.byref(ms), C.byref(n)),
-                    "circle_fits_profile_get")
-        return ms.value, n.value
+        return self._profile_part("circle_fits_profile_get", part)
 
     # ---- colour frames (interleaved BGR / RGB / BGRA / RGBA; the rule is the "gray_rule" option) --------------
     def to_gray(self, frame, order: str = "bgr") -> np.ndarray:
@@ -3209,16 +3065,12 @@ def canny_multi_gpu(imgs, sigma: float, min_val: int, max_val: int, n_devices: i
         raise ValueError(f"out must be a C-contiguous {np.dtype(dtype).name} array of shape {shape}")
     fn = load().canny_hip_canny_multi_gpu_bits if bits else \
         (load().canny_hip_canny_multi_gpu_u8 if u8 else load().canny_hip_canny_multi_gpu)
-    st = fn(_hp(a), a.shape[0], sigma, min_val, max_val, a.shape[1], a.shape[2], _hp(out), n_devices)
-    if st:
-        raise CannyHipError(st, "canny_multi_gpu")
+    _ok(fn(_hp(a), a.shape[0], sigma, min_val, max_val, a.shape[1], a.shape[2], _hp(out), n_devices), "canny_multi_gpu")
     return out
 
 
 def multi_gpu_set_option(name: str, value: int):
-    st = load().canny_hip_multi_gpu_set_option(name.encode(), value)
-    if st:
-        raise CannyHipError(st, f"multi_gpu_set_option({name})")
+    _ok(load().canny_hip_multi_gpu_set_option(name.encode(), value), f"multi_gpu_set_option({name})")
 
 
 def multi_gpu_release():
@@ -3253,9 +3105,7 @@ def createGaussianKernel(sigma: float) -> np.ndarray:
     """src/utils.cpp:77-95 (host-side): returns the normalised float taps; len() is the window."""
     taps = np.zeros(129, np.float32)
     w = C.c_int(0)
-    st = load().canny_hip_gaussian_kernel(sigma, _hp(taps), taps.size, C.byref(w))
-    if st:
-        raise CannyHipError(st, "createGaussianKernel")
+    _ok(load().canny_hip_gaussian_kernel(sigma, _hp(taps), taps.size, C.byref(w)), "createGaussianKernel")
     return taps[:w.value].copy()
 
 

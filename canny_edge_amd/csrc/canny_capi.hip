@@ -323,6 +323,48 @@ struct PropLane {
     bool converged = false;
 };
 
+// The profile slots: the canny stages, then every feature's parts (canny_hip_<name>_profile_get), in this order.  A new
+// feature adds a row at the end.
+struct ProfGroup {
+    const char *name;
+    int parts;
+};
+constexpr ProfGroup kProfGroups[] = {
+    {"stages", CANNY_HIP_STAGE_END},
+    {"hough", 3},
+    {"components", CANNY_HIP_CC_PARTS},
+    {"edt", CANNY_HIP_EDT_PARTS},
+    {"hough_segments", CANNY_HIP_SEGMENT_PARTS},
+    {"contours", CANNY_HIP_CONTOUR_PARTS},
+    {"hough_circles", CANNY_HIP_CIRCLE_PARTS},
+    {"polygons", CANNY_HIP_POLYGON_PARTS},
+    {"edgels", CANNY_HIP_EDGEL_PARTS},
+    {"line_fits", CANNY_HIP_LINE_FIT_PARTS},
+    {"circle_fits", CANNY_HIP_CIRCLE_FIT_PARTS},
+    {"chamfer", CANNY_HIP_CHAMFER_PARTS},
+    {"shapes", CANNY_HIP_SHAPE_PARTS},
+    {"curves", CANNY_HIP_CURVE_PARTS},
+    {"corners", CANNY_HIP_CORNER_PARTS},
+    {"descriptors", CANNY_HIP_DESC_PARTS},
+    {"motion", CANNY_HIP_MOTION_PARTS},
+    {"warp", CANNY_HIP_WARP_PARTS},
+    {"fuse", CANNY_HIP_FUSE_PARTS},
+    {"morph", CANNY_HIP_MORPH_PARTS},
+};
+
+// The first slot of the named group; with no name, the number of slots.  A name the table does not hold fails to compile.
+constexpr int prof_base(const char *name)
+{
+    int base = 0;
+    for (const ProfGroup &g : kProfGroups) {
+        const char *a = g.name, *b = name;
+        while (b && *a && *a == *b) a++, b++;
+        if (b && *a == *b) return base;
+        base += g.parts;
+    }
+    return name ? throw "no such profile group" : base;
+}
+
 } // namespace
 
 struct canny_hip_ctx {
@@ -450,40 +492,20 @@ struct canny_hip_ctx {
     bool prof = false;
     unsigned prof_mask = ~0u; // stages whose launches get an event pair (each pair costs a few us of stream time)
     unsigned prof_every = 1;  // ... and only every prof_every-th launch group of a stage gets one
-    // slots: the stages, then the three Hough parts (canny_hip_hough_profile_get), then the four parts of the component
-    // labelling (canny_hip_components_profile_get), then the two of the distance transform (canny_hip_edt_profile_get),
-    // then the three of the Hough segments (canny_hip_hough_segments_profile_get), then the four of the contour chains
-    // (canny_hip_contours_profile_get), then the four of the Hough circles (canny_hip_hough_circles_profile_get), then the
-    // three of the polygon approximation (canny_hip_polygons_profile_get), then the two of the sub-pixel edgels
-    // (canny_hip_edgels_profile_get), then the one of the line fits (canny_hip_line_fits_profile_get), then the one of the
-    // circle fits (canny_hip_circle_fits_profile_get), then the four of the chamfer matching
-    // (canny_hip_chamfer_profile_get), then the three of the contour shape measures (canny_hip_shapes_profile_get), then the two of the edge curves
-    // (canny_hip_curves_profile_get), then the four of the corners (canny_hip_corners_profile_get), then the four of the descriptors and their matching
-    // (canny_hip_descriptors_profile_get), then the three of the motion estimate (canny_hip_motion_profile_get), then the two of the frame alignment (canny_hip_warp_profile_get), then the two of the temporal fusion
-    // (canny_hip_fuse_profile_get).  The mask is a non-negative int option: bit 30 is the last it can
-    // carry, and the three polygon slots, the two edgel slots, the line-fit slot and the circle-fit slot behind them go by
-    // it together
-    static constexpr int kProfHough = CANNY_HIP_STAGE_END, kProfComponents = CANNY_HIP_STAGE_END + 3;
-    static constexpr int kProfEdt = kProfComponents + CANNY_HIP_CC_PARTS;
-    static constexpr int kProfSegments = kProfEdt + CANNY_HIP_EDT_PARTS;
-    static constexpr int kProfContours = kProfSegments + CANNY_HIP_SEGMENT_PARTS;
-    static constexpr int kProfCircles = kProfContours + CANNY_HIP_CONTOUR_PARTS;
-    static constexpr int kProfPolygons = kProfCircles + CANNY_HIP_CIRCLE_PARTS;
-    static constexpr int kProfEdgels = kProfPolygons + CANNY_HIP_POLYGON_PARTS;
-    static constexpr int kProfLineFits = kProfEdgels + CANNY_HIP_EDGEL_PARTS;
-    static constexpr int kProfCircleFits = kProfLineFits + CANNY_HIP_LINE_FIT_PARTS;
-    static constexpr int kProfChamfer = kProfCircleFits + CANNY_HIP_CIRCLE_FIT_PARTS;
-    static constexpr int kProfShapes = kProfChamfer + CANNY_HIP_CHAMFER_PARTS;
-    static constexpr int kProfCurves = kProfShapes + CANNY_HIP_SHAPE_PARTS;
-    static constexpr int kProfCorners = kProfCurves + CANNY_HIP_CURVE_PARTS;
-    static constexpr int kProfDescriptors = kProfCorners + CANNY_HIP_CORNER_PARTS;
-    static constexpr int kProfMotion = kProfDescriptors + CANNY_HIP_DESC_PARTS;
-    static constexpr int kProfWarp = kProfMotion + CANNY_HIP_MOTION_PARTS;
-    static constexpr int kProfFuse = kProfWarp + CANNY_HIP_WARP_PARTS;
-    static constexpr int kProfMorph = kProfFuse + CANNY_HIP_FUSE_PARTS; // the binary morphology (canny_hip_morph_profile_get)
-    static constexpr int kProfSlots = kProfMorph + CANNY_HIP_MORPH_PARTS;
+    // slots: kProfGroups in order; the aliases keep the call sites short
+    static constexpr int kProfHough = prof_base("hough"), kProfComponents = prof_base("components"),
+                         kProfEdt = prof_base("edt"), kProfSegments = prof_base("hough_segments"),
+                         kProfContours = prof_base("contours"), kProfCircles = prof_base("hough_circles"),
+                         kProfPolygons = prof_base("polygons"), kProfEdgels = prof_base("edgels"),
+                         kProfLineFits = prof_base("line_fits"), kProfCircleFits = prof_base("circle_fits"),
+                         kProfChamfer = prof_base("chamfer"), kProfShapes = prof_base("shapes"),
+                         kProfCurves = prof_base("curves"), kProfCorners = prof_base("corners"),
+                         kProfDescriptors = prof_base("descriptors"), kProfMotion = prof_base("motion"),
+                         kProfWarp = prof_base("warp"), kProfFuse = prof_base("fuse"), kProfMorph = prof_base("morph");
+    static constexpr int kProfSlots = prof_base(nullptr);
+    // "profile_stage_mask" is a non-negative int option: bit 30 is the last it can carry
     static constexpr int kProfLastBit = 30;
-    static_assert(kProfPolygons == kProfLastBit && kProfEdgels > kProfLastBit,
+    static_assert(prof_base("polygons") == kProfLastBit && prof_base("edgels") > kProfLastBit,
                   "profile_stage_mask has one bit per slot up to the polygon parts; every slot from there on follows bit 30");
     unsigned prof_seen[kProfSlots] = {0};
     std::vector<EventPair> pending[kProfSlots];
@@ -599,6 +621,12 @@ int make_taps(float sigma, GaussTaps &t)
     return CANNY_HIP_OK;
 }
 
+// What every canny_hip_selftest_*_plan export hands out of a launch plan: units, per_group, grid, trips, aux.
+void store_plan(unsigned long long *out, const LaunchPlan &p)
+{
+    out[0] = p.units, out[1] = p.per_group, out[2] = p.grid, out[3] = p.trips(), out[4] = (unsigned long long)p.aux;
+}
+
 int check_dims(int height, int width, int n_frames)
 {
     if (height < 1 || width < 1 || n_frames < 1) return CANNY_HIP_ERR_INVALID;
@@ -612,6 +640,13 @@ int check_dims(int height, int width, int n_frames)
 // is zeroed again -- unless the scan has already passed it: the result depends on the scan order, which the
 // parallel formulation does not have.  (If max_val > 255 as well everything ends as 0 either way.)
 bool hysteresis_order_dependent(int min_val, int max_val) { return min_val > 255 && max_val <= 255; }
+
+// Whether the last canny call ran on a batch of this geometry: only then are the planes it left in the context (smoothed,
+// plane_s) the ones a call without a plane of its own means.
+bool last_canny_was(const canny_hip_ctx *ctx, int n_frames, int height, int width)
+{
+    return ctx->last_canny_n && ctx->last_canny_n == n_frames && ctx->last_canny_h == height && ctx->last_canny_w == width;
+}
 
 size_t npx(int height, int width, int n_frames) { return (size_t)height * (size_t)width * (size_t)n_frames; }
 
@@ -1181,26 +1216,36 @@ int dev_points_scatter(canny_hip_ctx *ctx, const uint64_t *strong, const uint8_t
     return CANNY_HIP_OK;
 }
 
-// dev_canny (unchanged, into d_edges or the edges16 workspace), then count + scan of its map.  *strong_out receives the
-// source for the scatter: the strong plane, or null when the map is empty by rule (max_val > 255: the reference zeroes
-// every reached pixel, src/utils.cpp:336-340, although strong bits are set) and the offsets have been zeroed.
+// The prologue of every "canny, then the stage on its map" call: dev_canny (unchanged) into d_edges, or into the edges16
+// workspace when the caller passes none.  *strong_out receives the source of the finished map: the strong plane, or null
+// when the map is empty by rule (max_val > 255: the reference zeroes every reached pixel, src/utils.cpp:336-340,
+// although strong bits are set); what a stage stores for the empty map is the stage's business.
 // Every route through dev_canny leaves the converged strong plane of the WHOLE batch in ctx->plane_s, in stream order
 // (DESIGN.md section 12 goes through them), so the s16 map is never re-read.
-int dev_canny_points_count(canny_hip_ctx *ctx, const unsigned char *d_img, float sigma, int lo, int hi, int h, int w,
-                           int n, short *d_edges, unsigned long long *d_offsets, const uint64_t **strong_out)
+int dev_canny_map(canny_hip_ctx *ctx, const unsigned char *d_img, float sigma, int lo, int hi, int h, int w, int n,
+                  short *d_edges, const uint64_t **strong_out)
 {
-    int rc;
     if (!d_edges) {
         HIP_TRY(ctx, ctx->edges16.ensure(npx(h, w, n) * sizeof(short)));
         d_edges = (short *)ctx->edges16.p;
     }
-    if ((rc = dev_canny(ctx, d_img, sigma, lo, hi, h, w, n, d_edges))) return rc;
-    if (hi > 255) {
-        *strong_out = nullptr;
+    const int rc = dev_canny(ctx, d_img, sigma, lo, hi, h, w, n, d_edges);
+    if (rc) return rc;
+    *strong_out = hi > 255 ? nullptr : (const uint64_t *)ctx->plane_s.p;
+    return CANNY_HIP_OK;
+}
+
+// dev_canny_map, then count + scan of its map.  *strong_out receives the source for the scatter; when it is null the
+// offsets have been zeroed.
+int dev_canny_points_count(canny_hip_ctx *ctx, const unsigned char *d_img, float sigma, int lo, int hi, int h, int w,
+                           int n, short *d_edges, unsigned long long *d_offsets, const uint64_t **strong_out)
+{
+    int rc = dev_canny_map(ctx, d_img, sigma, lo, hi, h, w, n, d_edges, strong_out);
+    if (rc) return rc;
+    if (!*strong_out) {
         HIP_TRY(ctx, hipMemsetAsync(d_offsets, 0, ((size_t)n + 1) * sizeof(unsigned long long), ctx->stream));
         return CANNY_HIP_OK;
     }
-    *strong_out = (const uint64_t *)ctx->plane_s.p;
     return dev_points_count(ctx, *strong_out, nullptr, make_hyst_geom(h, w, n), d_offsets);
 }
 
@@ -1250,23 +1295,20 @@ int dev_components(canny_hip_ctx *ctx, const uint64_t *strong, const uint8_t *bi
 }
 
 // dev_canny (unchanged), then the labelling of its map from the converged strong plane.  The result follows the MAP:
-// max_val > 255 leaves no edge pixel (see dev_canny_points_count).
+// max_val > 255 leaves no edge pixel (see dev_canny_map).
 int dev_canny_components(canny_hip_ctx *ctx, const unsigned char *d_img, float sigma, int lo, int hi, int h, int w, int n,
                          short *d_edges, int min_area, const CcOut &out)
 {
-    int rc;
-    if (!d_edges) {
-        HIP_TRY(ctx, ctx->edges16.ensure(npx(h, w, n) * sizeof(short)));
-        d_edges = (short *)ctx->edges16.p;
-    }
-    if ((rc = dev_canny(ctx, d_img, sigma, lo, hi, h, w, n, d_edges))) return rc;
-    if (hi > 255) {
+    const uint64_t *strong;
+    int rc = dev_canny_map(ctx, d_img, sigma, lo, hi, h, w, n, d_edges, &strong);
+    if (rc) return rc;
+    if (!strong) {
         HIP_TRY(ctx, hipMemsetAsync(out.offsets, 0, ((size_t)n + 1) * sizeof(unsigned long long), ctx->stream));
         if (out.labels) HIP_TRY(ctx, hipMemsetAsync(out.labels, 0, npx(h, w, n) * sizeof(int), ctx->stream));
         if (out.kept) HIP_TRY(ctx, hipMemsetAsync(out.kept, 0, npx(h, w, n), ctx->stream));
         return CANNY_HIP_OK;
     }
-    return dev_components(ctx, (const uint64_t *)ctx->plane_s.p, nullptr, make_hyst_geom(h, w, n), min_area, out);
+    return dev_components(ctx, strong, nullptr, make_hyst_geom(h, w, n), min_area, out);
 }
 
 // ---- outer contour chains (canny_contours.hip) -----------------------------
@@ -1335,24 +1377,21 @@ int dev_contours(canny_hip_ctx *ctx, const uint64_t *strong, const uint8_t *bits
 }
 
 // dev_canny (unchanged), then the chains of its map from the converged strong plane.  The result follows the MAP:
-// max_val > 255 leaves no edge pixel (see dev_canny_points_count).
+// max_val > 255 leaves no edge pixel (see dev_canny_map).
 int dev_canny_contours(canny_hip_ctx *ctx, const unsigned char *d_img, float sigma, int lo, int hi, int h, int w, int n,
                        short *d_edges, int min_area, const CtOut &out)
 {
-    int rc;
-    if (!d_edges) {
-        HIP_TRY(ctx, ctx->edges16.ensure(npx(h, w, n) * sizeof(short)));
-        d_edges = (short *)ctx->edges16.p;
-    }
-    if ((rc = dev_canny(ctx, d_img, sigma, lo, hi, h, w, n, d_edges))) return rc;
-    if (hi > 255) {
+    const uint64_t *strong;
+    int rc = dev_canny_map(ctx, d_img, sigma, lo, hi, h, w, n, d_edges, &strong);
+    if (rc) return rc;
+    if (!strong) {
         const size_t off_bytes = ((size_t)n + 1) * sizeof(unsigned long long);
         HIP_TRY(ctx, hipMemsetAsync(out.offsets, 0, off_bytes, ctx->stream));
         HIP_TRY(ctx, hipMemsetAsync(out.point_offsets, 0, off_bytes, ctx->stream));
         if (out.chain_offsets) HIP_TRY(ctx, hipMemsetAsync(out.chain_offsets, 0, sizeof(unsigned long long), ctx->stream));
         return CANNY_HIP_OK;
     }
-    return dev_contours(ctx, (const uint64_t *)ctx->plane_s.p, nullptr, make_hyst_geom(h, w, n), min_area, out);
+    return dev_contours(ctx, strong, nullptr, make_hyst_geom(h, w, n), min_area, out);
 }
 
 // ---- edge curves (canny_curves.hip) ----------------------------------------
@@ -1400,24 +1439,21 @@ int dev_curves(canny_hip_ctx *ctx, const uint64_t *strong, const uint8_t *bits, 
 }
 
 // dev_canny (unchanged), then the curves of its map from the converged strong plane.  The result follows the MAP:
-// max_val > 255 leaves no edge pixel (see dev_canny_points_count).
+// max_val > 255 leaves no edge pixel (see dev_canny_map).
 int dev_canny_curves(canny_hip_ctx *ctx, const unsigned char *d_img, float sigma, int lo, int hi, int h, int w, int n,
                      short *d_edges, int min_length, const CvOut &out)
 {
-    int rc;
-    if (!d_edges) {
-        HIP_TRY(ctx, ctx->edges16.ensure(npx(h, w, n) * sizeof(short)));
-        d_edges = (short *)ctx->edges16.p;
-    }
-    if ((rc = dev_canny(ctx, d_img, sigma, lo, hi, h, w, n, d_edges))) return rc;
-    if (hi > 255) {
+    const uint64_t *strong;
+    int rc = dev_canny_map(ctx, d_img, sigma, lo, hi, h, w, n, d_edges, &strong);
+    if (rc) return rc;
+    if (!strong) {
         const size_t off_bytes = ((size_t)n + 1) * sizeof(unsigned long long);
         HIP_TRY(ctx, hipMemsetAsync(out.offsets, 0, off_bytes, ctx->stream));
         HIP_TRY(ctx, hipMemsetAsync(out.point_offsets, 0, off_bytes, ctx->stream));
         if (out.chain_offsets) HIP_TRY(ctx, hipMemsetAsync(out.chain_offsets, 0, sizeof(unsigned long long), ctx->stream));
         return CANNY_HIP_OK;
     }
-    return dev_curves(ctx, (const uint64_t *)ctx->plane_s.p, nullptr, make_hyst_geom(h, w, n), min_length, out);
+    return dev_curves(ctx, strong, nullptr, make_hyst_geom(h, w, n), min_length, out);
 }
 
 // ---- polygon approximation of the chains (canny_polygons.hip) --------------
@@ -1573,24 +1609,21 @@ int dev_edt(canny_hip_ctx *ctx, const uint64_t *strong, const uint8_t *bits, con
 }
 
 // dev_canny (unchanged), then the transform of its map from the converged strong plane.  The result follows the MAP:
-// max_val > 255 leaves no edge pixel (see dev_canny_points_count), so every plane takes its "no edge pixel" value.
+// max_val > 255 leaves no edge pixel (see dev_canny_map), so every plane takes its "no edge pixel" value.
 int dev_canny_edt(canny_hip_ctx *ctx, const unsigned char *d_img, float sigma, int lo, int hi, int h, int w, int n,
                   short *d_edges, const EdtOut &out)
 {
-    int rc;
-    if (!d_edges) {
-        HIP_TRY(ctx, ctx->edges16.ensure(npx(h, w, n) * sizeof(short)));
-        d_edges = (short *)ctx->edges16.p;
-    }
-    if ((rc = dev_canny(ctx, d_img, sigma, lo, hi, h, w, n, d_edges))) return rc;
-    if (hi > 255) {
+    const uint64_t *strong;
+    int rc = dev_canny_map(ctx, d_img, sigma, lo, hi, h, w, n, d_edges, &strong);
+    if (rc) return rc;
+    if (!strong) {
         const size_t count = npx(h, w, n);
         if (out.dist2) HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)out.dist2, CANNY_HIP_EDT_NONE, count, ctx->stream));
         if (out.dist) HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)out.dist, 0x7F800000, count, ctx->stream)); // +inf
         if (out.nearest) HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)out.nearest, -1, count, ctx->stream));
         return CANNY_HIP_OK;
     }
-    return dev_edt(ctx, (const uint64_t *)ctx->plane_s.p, nullptr, make_hyst_geom(h, w, n), out);
+    return dev_edt(ctx, strong, nullptr, make_hyst_geom(h, w, n), out);
 }
 
 // ---- Hough lines (canny_hough.hip) -----------------------------------------
@@ -3397,18 +3430,12 @@ namespace {
 int dev_canny_edgels_count(canny_hip_ctx *ctx, const unsigned char *d_img, float sigma, int lo, int hi, int h, int w, int n,
                            short *d_edges, unsigned long long *d_offsets, const uint64_t **strong_out)
 {
-    int rc;
-    if (!d_edges) {
-        HIP_TRY(ctx, ctx->edges16.ensure(npx(h, w, n) * sizeof(short)));
-        d_edges = (short *)ctx->edges16.p;
-    }
-    if ((rc = dev_canny(ctx, d_img, sigma, lo, hi, h, w, n, d_edges))) return rc;
-    if (hi > 255) { // the records follow the MAP: the reference zeroes every reached pixel
-        *strong_out = nullptr;
+    int rc = dev_canny_map(ctx, d_img, sigma, lo, hi, h, w, n, d_edges, strong_out);
+    if (rc) return rc;
+    if (!*strong_out) {
         HIP_TRY(ctx, hipMemsetAsync(d_offsets, 0, ((size_t)n + 1) * sizeof(unsigned long long), ctx->stream));
         return CANNY_HIP_OK;
     }
-    *strong_out = (const uint64_t *)ctx->plane_s.p;
     const HystGeom g = make_hyst_geom(h, w, n);
     HIP_TRY(ctx, ctx->points.ensure(g.n_frames * sizeof(unsigned long long) + (size_t)n * h * sizeof(uint32_t)));
     unsigned long long *totals = (unsigned long long *)ctx->points.p;
@@ -3460,9 +3487,7 @@ int canny_hip_dev_edgels_at(canny_hip_ctx *ctx, const void *d_plane, int plane_i
     if ((rc = check_dims(height, width, n_frames))) return rc;
     if (!d_plane) {
         // the plane the last canny call left: only for the batch it belongs to
-        if (!ctx->last_canny_n || !ctx->smoothed.p || ctx->last_canny_n != n_frames || ctx->last_canny_h != height ||
-            ctx->last_canny_w != width)
-            return CANNY_HIP_ERR_INVALID;
+        if (!last_canny_was(ctx, n_frames, height, width) || !ctx->smoothed.p) return CANNY_HIP_ERR_INVALID;
         d_plane = ctx->smoothed.p;
         plane_is_u8 = ctx->last_canny_u8;
     }
@@ -3526,15 +3551,21 @@ int canny_hip_dev_edgels_arith(canny_hip_ctx *ctx, const short *d_gx, const shor
 
 static int profile_collect(canny_hip_ctx *ctx);
 
-int canny_hip_edgels_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches)
+// What every canny_hip_<feature>_profile_get does: part `part` of the `parts` slots from `base` on.
+static int profile_part_get(canny_hip_ctx *ctx, int base, int parts, int part, double *total_ms, long *launches)
 {
-    if (part < 0 || part >= CANNY_HIP_EDGEL_PARTS || !total_ms || !launches) return CANNY_HIP_ERR_INVALID;
+    if (part < 0 || part >= parts || !total_ms || !launches) return CANNY_HIP_ERR_INVALID;
     int rc = bind(ctx);
     if (rc) return rc;
     if ((rc = profile_collect(ctx))) return rc;
-    *total_ms = ctx->total_ms[canny_hip_ctx::kProfEdgels + part];
-    *launches = ctx->launches[canny_hip_ctx::kProfEdgels + part];
+    *total_ms = ctx->total_ms[base + part];
+    *launches = ctx->launches[base + part];
     return CANNY_HIP_OK;
+}
+
+int canny_hip_edgels_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches)
+{
+    return profile_part_get(ctx, canny_hip_ctx::kProfEdgels, CANNY_HIP_EDGEL_PARTS, part, total_ms, launches);
 }
 
 // Host-only: the launch plan of the index-driven edgel kernel (plan_edgels_at), outputs as canny_hip_selftest_launch_plan.
@@ -3543,7 +3574,7 @@ int canny_hip_selftest_edgels_plan(int n_frames, int height, int width, unsigned
 {
     if (!out || !n_points || height < 2 || width < 2 || check_dims(height, width, n_frames)) return CANNY_HIP_ERR_INVALID;
     const LaunchPlan p = plan_edgels_at(height, width, n_points);
-    out[0] = p.units, out[1] = p.per_group, out[2] = p.grid, out[3] = p.trips(), out[4] = (unsigned long long)p.aux;
+    store_plan(out, p);
     return CANNY_HIP_OK;
 }
 
@@ -4431,13 +4462,8 @@ int canny_hip_dev_canny_hough(canny_hip_ctx *ctx, const unsigned char *d_img, fl
     int lds_rows = 0;
     if ((rc = hough_prepare(ctx, height, width, rho, theta, lines_max, min_theta, max_theta, out, hg, &lds_rows)))
         return rc;
-    if (!d_edges) {
-        HIP_TRY(ctx, ctx->edges16.ensure(npx(height, width, n_frames) * sizeof(short)));
-        d_edges = (short *)ctx->edges16.p;
-    }
-    if ((rc = dev_canny(ctx, d_img, sigma, min_val, max_val, height, width, n_frames, d_edges))) return rc;
-    // the transform follows the MAP: max_val > 255 zeroes every reached pixel although strong bits are set
-    const uint64_t *strong = max_val > 255 ? nullptr : (const uint64_t *)ctx->plane_s.p;
+    const uint64_t *strong;
+    if ((rc = dev_canny_map(ctx, d_img, sigma, min_val, max_val, height, width, n_frames, d_edges, &strong))) return rc;
     return dev_hough(ctx, strong, nullptr, nullptr, nullptr, make_hyst_geom(height, width, n_frames), hg, lds_rows,
                      threshold, lines_max, out);
 }
@@ -4720,9 +4746,7 @@ int canny_hip_dev_line_fits_bits(canny_hip_ctx *ctx, const unsigned char *d_bits
     hg.rho = rho, hg.theta = theta, hg.min_theta = min_theta;
     if (!d_plane) {
         // the plane the last canny call left: only for the batch it belongs to
-        if (!ctx->last_canny_n || !ctx->smoothed.p || ctx->last_canny_n != n_frames || ctx->last_canny_h != height ||
-            ctx->last_canny_w != width)
-            return CANNY_HIP_ERR_INVALID;
+        if (!last_canny_was(ctx, n_frames, height, width) || !ctx->smoothed.p) return CANNY_HIP_ERR_INVALID;
         d_plane = ctx->smoothed.p;
         plane_is_u8 = ctx->last_canny_u8;
     }
@@ -4839,79 +4863,37 @@ int canny_hip_dev_line_fits_arith(canny_hip_ctx *ctx, const long long *d_moments
 
 int canny_hip_line_fits_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches)
 {
-    if (part < 0 || part >= CANNY_HIP_LINE_FIT_PARTS || !total_ms || !launches) return CANNY_HIP_ERR_INVALID;
-    int rc = bind(ctx);
-    if (rc) return rc;
-    if ((rc = profile_collect(ctx))) return rc;
-    *total_ms = ctx->total_ms[canny_hip_ctx::kProfLineFits + part];
-    *launches = ctx->launches[canny_hip_ctx::kProfLineFits + part];
-    return CANNY_HIP_OK;
+    return profile_part_get(ctx, canny_hip_ctx::kProfLineFits, CANNY_HIP_LINE_FIT_PARTS, part, total_ms, launches);
 }
 
 int canny_hip_hough_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches)
 {
-    if (part < 0 || part > 2 || !total_ms || !launches) return CANNY_HIP_ERR_INVALID;
-    int rc = bind(ctx);
-    if (rc) return rc;
-    if ((rc = profile_collect(ctx))) return rc;
-    *total_ms = ctx->total_ms[CANNY_HIP_STAGE_END + part];
-    *launches = ctx->launches[CANNY_HIP_STAGE_END + part];
-    return CANNY_HIP_OK;
+    return profile_part_get(ctx, canny_hip_ctx::kProfHough, 3, part, total_ms, launches);
 }
 
 int canny_hip_components_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches)
 {
-    if (part < 0 || part >= CANNY_HIP_CC_PARTS || !total_ms || !launches) return CANNY_HIP_ERR_INVALID;
-    int rc = bind(ctx);
-    if (rc) return rc;
-    if ((rc = profile_collect(ctx))) return rc;
-    *total_ms = ctx->total_ms[canny_hip_ctx::kProfComponents + part];
-    *launches = ctx->launches[canny_hip_ctx::kProfComponents + part];
-    return CANNY_HIP_OK;
+    return profile_part_get(ctx, canny_hip_ctx::kProfComponents, CANNY_HIP_CC_PARTS, part, total_ms, launches);
 }
 
 int canny_hip_edt_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches)
 {
-    if (part < 0 || part >= CANNY_HIP_EDT_PARTS || !total_ms || !launches) return CANNY_HIP_ERR_INVALID;
-    int rc = bind(ctx);
-    if (rc) return rc;
-    if ((rc = profile_collect(ctx))) return rc;
-    *total_ms = ctx->total_ms[canny_hip_ctx::kProfEdt + part];
-    *launches = ctx->launches[canny_hip_ctx::kProfEdt + part];
-    return CANNY_HIP_OK;
+    return profile_part_get(ctx, canny_hip_ctx::kProfEdt, CANNY_HIP_EDT_PARTS, part, total_ms, launches);
 }
 
 int canny_hip_hough_segments_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches)
 {
-    if (part < 0 || part >= CANNY_HIP_SEGMENT_PARTS || !total_ms || !launches) return CANNY_HIP_ERR_INVALID;
-    int rc = bind(ctx);
-    if (rc) return rc;
-    if ((rc = profile_collect(ctx))) return rc;
-    *total_ms = ctx->total_ms[canny_hip_ctx::kProfSegments + part];
-    *launches = ctx->launches[canny_hip_ctx::kProfSegments + part];
-    return CANNY_HIP_OK;
+    return profile_part_get(ctx, canny_hip_ctx::kProfSegments, CANNY_HIP_SEGMENT_PARTS, part, total_ms, launches);
 }
 
 int canny_hip_contours_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches)
 {
-    if (part < 0 || part >= CANNY_HIP_CONTOUR_PARTS || !total_ms || !launches) return CANNY_HIP_ERR_INVALID;
-    int rc = bind(ctx);
-    if (rc) return rc;
-    if ((rc = profile_collect(ctx))) return rc;
-    *total_ms = ctx->total_ms[canny_hip_ctx::kProfContours + part];
-    *launches = ctx->launches[canny_hip_ctx::kProfContours + part];
-    return CANNY_HIP_OK;
+    return profile_part_get(ctx, canny_hip_ctx::kProfContours, CANNY_HIP_CONTOUR_PARTS, part, total_ms, launches);
 }
 
 int canny_hip_polygons_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches)
 {
-    if (part < 0 || part >= CANNY_HIP_POLYGON_PARTS || !total_ms || !launches) return CANNY_HIP_ERR_INVALID;
-    int rc = bind(ctx);
-    if (rc) return rc;
-    if ((rc = profile_collect(ctx))) return rc;
-    *total_ms = ctx->total_ms[canny_hip_ctx::kProfPolygons + part];
-    *launches = ctx->launches[canny_hip_ctx::kProfPolygons + part];
-    return CANNY_HIP_OK;
+    return profile_part_get(ctx, canny_hip_ctx::kProfPolygons, CANNY_HIP_POLYGON_PARTS, part, total_ms, launches);
 }
 
 // ---- Hough circles ----------------------------------------------------------------------------------------
@@ -5034,14 +5016,10 @@ int canny_hip_dev_canny_hough_circles(canny_hip_ctx *ctx, const unsigned char *d
     const CircleArgs a{min_radius, max_radius, cell_shift, threshold, support_threshold, min_dist, centres_max};
     CircleGeom cg;
     if ((rc = circles_prepare(height, width, a, d_counts, cg)) || (rc = check_dims(height, width, n_frames))) return rc;
-    if (!d_edges) {
-        HIP_TRY(ctx, ctx->edges16.ensure(npx(height, width, n_frames) * sizeof(short)));
-        d_edges = (short *)ctx->edges16.p;
-    }
-    if ((rc = dev_canny(ctx, d_img, sigma, min_val, max_val, height, width, n_frames, d_edges))) return rc;
-    // the transform follows the MAP: max_val > 255 zeroes every reached pixel although strong bits are set.  Every route of
-    // dev_canny leaves the whole batch's smoothed plane in ctx->smoothed, as bytes iff last_canny_u8.
-    const uint64_t *strong = max_val > 255 ? nullptr : (const uint64_t *)ctx->plane_s.p;
+    const uint64_t *strong;
+    if ((rc = dev_canny_map(ctx, d_img, sigma, min_val, max_val, height, width, n_frames, d_edges, &strong))) return rc;
+    // every route of dev_canny leaves the whole batch's smoothed plane in ctx->smoothed, as bytes iff last_canny_u8
+    // 
     return dev_circles(ctx, strong, nullptr, make_hyst_geom(height, width, n_frames), ctx->smoothed.p,
                        ctx->last_canny_u8 != 0, nullptr, nullptr, cg, a,
                        CircleOut{d_circles, d_counts, d_centre_counts, d_accum});
@@ -5097,13 +5075,7 @@ int canny_hip_dev_hough_circles_steps(canny_hip_ctx *ctx, const short *d_gx, con
 
 int canny_hip_hough_circles_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches)
 {
-    if (part < 0 || part >= CANNY_HIP_CIRCLE_PARTS || !total_ms || !launches) return CANNY_HIP_ERR_INVALID;
-    int rc = bind(ctx);
-    if (rc) return rc;
-    if ((rc = profile_collect(ctx))) return rc;
-    *total_ms = ctx->total_ms[canny_hip_ctx::kProfCircles + part];
-    *launches = ctx->launches[canny_hip_ctx::kProfCircles + part];
-    return CANNY_HIP_OK;
+    return profile_part_get(ctx, canny_hip_ctx::kProfCircles, CANNY_HIP_CIRCLE_PARTS, part, total_ms, launches);
 }
 
 // ---- sub-pixel circle fits (canny_circle_fits.hip) --------------------------------
@@ -5148,9 +5120,7 @@ int canny_hip_dev_circle_fits_bits(canny_hip_ctx *ctx, const unsigned char *d_bi
     if ((rc = circle_fits_check(height, width, n_frames, centres_max, band, trim_q8, options, d_fits))) return rc;
     if (!d_plane) {
         // the plane the last canny call left: only for the batch it belongs to
-        if (!ctx->last_canny_n || !ctx->smoothed.p || ctx->last_canny_n != n_frames || ctx->last_canny_h != height ||
-            ctx->last_canny_w != width)
-            return CANNY_HIP_ERR_INVALID;
+        if (!last_canny_was(ctx, n_frames, height, width) || !ctx->smoothed.p) return CANNY_HIP_ERR_INVALID;
         d_plane = ctx->smoothed.p;
         plane_is_u8 = ctx->last_canny_u8;
     }
@@ -5250,13 +5220,7 @@ int canny_hip_dev_circle_fits_arith(canny_hip_ctx *ctx, const long long *d_momen
 
 int canny_hip_circle_fits_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches)
 {
-    if (part < 0 || part >= CANNY_HIP_CIRCLE_FIT_PARTS || !total_ms || !launches) return CANNY_HIP_ERR_INVALID;
-    int rc = bind(ctx);
-    if (rc) return rc;
-    if ((rc = profile_collect(ctx))) return rc;
-    *total_ms = ctx->total_ms[canny_hip_ctx::kProfCircleFits + part];
-    *launches = ctx->launches[canny_hip_ctx::kProfCircleFits + part];
-    return CANNY_HIP_OK;
+    return profile_part_get(ctx, canny_hip_ctx::kProfCircleFits, CANNY_HIP_CIRCLE_FIT_PARTS, part, total_ms, launches);
 }
 
 // ---- measurement aid ------------------------------------------------------------------------------------
@@ -5354,7 +5318,7 @@ int canny_hip_selftest_launch_plan(int kind, int n_frames, int height, int width
         }
     }
     }
-    out[0] = p.units, out[1] = p.per_group, out[2] = p.grid, out[3] = p.trips(), out[4] = (unsigned long long)p.aux;
+    store_plan(out, p);
     return CANNY_HIP_OK;
 }
 
@@ -5742,35 +5706,17 @@ int canny_hip_dev_chamfer_costs(canny_hip_ctx *ctx, const int *d_dist2, size_t n
 
 int canny_hip_chamfer_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches)
 {
-    if (part < 0 || part >= CANNY_HIP_CHAMFER_PARTS || !total_ms || !launches) return CANNY_HIP_ERR_INVALID;
-    int rc = bind(ctx);
-    if (rc) return rc;
-    if ((rc = profile_collect(ctx))) return rc;
-    *total_ms = ctx->total_ms[canny_hip_ctx::kProfChamfer + part];
-    *launches = ctx->launches[canny_hip_ctx::kProfChamfer + part];
-    return CANNY_HIP_OK;
+    return profile_part_get(ctx, canny_hip_ctx::kProfChamfer, CANNY_HIP_CHAMFER_PARTS, part, total_ms, launches);
 }
 
 int canny_hip_shapes_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches)
 {
-    if (part < 0 || part >= CANNY_HIP_SHAPE_PARTS || !total_ms || !launches) return CANNY_HIP_ERR_INVALID;
-    int rc = bind(ctx);
-    if (rc) return rc;
-    if ((rc = profile_collect(ctx))) return rc;
-    *total_ms = ctx->total_ms[canny_hip_ctx::kProfShapes + part];
-    *launches = ctx->launches[canny_hip_ctx::kProfShapes + part];
-    return CANNY_HIP_OK;
+    return profile_part_get(ctx, canny_hip_ctx::kProfShapes, CANNY_HIP_SHAPE_PARTS, part, total_ms, launches);
 }
 
 int canny_hip_curves_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches)
 {
-    if (part < 0 || part >= CANNY_HIP_CURVE_PARTS || !total_ms || !launches) return CANNY_HIP_ERR_INVALID;
-    int rc = bind(ctx);
-    if (rc) return rc;
-    if ((rc = profile_collect(ctx))) return rc;
-    *total_ms = ctx->total_ms[canny_hip_ctx::kProfCurves + part];
-    *launches = ctx->launches[canny_hip_ctx::kProfCurves + part];
-    return CANNY_HIP_OK;
+    return profile_part_get(ctx, canny_hip_ctx::kProfCurves, CANNY_HIP_CURVE_PARTS, part, total_ms, launches);
 }
 
 // Host-only: the launch plan of the edge curves' row kernels.
@@ -5778,7 +5724,7 @@ int canny_hip_selftest_curves_plan(int n_frames, int height, int width, unsigned
 {
     if (!out || check_contour_dims(height, width, n_frames)) return CANNY_HIP_ERR_INVALID;
     const LaunchPlan p = plan_cv_rows(make_hyst_geom(height, width, n_frames));
-    out[0] = p.units, out[1] = p.per_group, out[2] = p.grid, out[3] = p.trips(), out[4] = (unsigned long long)p.aux;
+    store_plan(out, p);
     return CANNY_HIP_OK;
 }
 
@@ -5790,7 +5736,7 @@ int canny_hip_selftest_shapes_plan(int which, unsigned long long capacity, unsig
     if (which == CANNY_HIP_SHAPES_PLAN_RECORDS) p = plan_sh_records(capacity);
     else if (which == CANNY_HIP_SHAPES_PLAN_SCAN_SUMS) p = plan_pg_scan_sums(capacity);
     else return CANNY_HIP_ERR_INVALID;
-    out[0] = p.units, out[1] = p.per_group, out[2] = p.grid, out[3] = p.trips(), out[4] = (unsigned long long)p.aux;
+    store_plan(out, p);
     return CANNY_HIP_OK;
 }
 
@@ -5806,7 +5752,7 @@ int canny_hip_selftest_chamfer_plan(int which, int n_frames, int height, int wid
     if (which == CANNY_HIP_CHAMFER_PLAN_COST) p = plan_chamfer_cost((unsigned long long)chunk * height * width);
     else if (which == CANNY_HIP_CHAMFER_PLAN_CELLS) p = plan_chamfer_cells((unsigned long long)height * width * n_templates);
     else return CANNY_HIP_ERR_INVALID;
-    out[0] = p.units, out[1] = p.per_group, out[2] = p.grid, out[3] = p.trips(), out[4] = (unsigned long long)p.aux;
+    store_plan(out, p);
     out[5] = (unsigned long long)chunk;
     return CANNY_HIP_OK;
 }
@@ -5908,12 +5854,10 @@ int canny_hip_dev_canny_corners(canny_hip_ctx *ctx, const unsigned char *d_img, 
     const CornerArgs a{mode, block, k_q8, quality_q16, min_response, min_dist, corners_max};
     const CornerOut out{d_corners, d_counts, d_cand_counts, d_max_response, d_response};
     if ((rc = corners_check(height, width, n_frames, a, out))) return rc;
-    if (!d_edges) {
-        HIP_TRY(ctx, ctx->edges16.ensure(npx(height, width, n_frames) * sizeof(short)));
-        d_edges = (short *)ctx->edges16.p;
-    }
-    if ((rc = dev_canny(ctx, d_img, sigma, min_val, max_val, height, width, n_frames, d_edges))) return rc;
-    // dev_canny leaves the whole batch's smoothed plane in ctx->smoothed, as bytes iff last_canny_u8
+    // the corners come from the smoothed plane, not the map: dev_canny leaves the whole batch's in ctx->smoothed, as bytes
+    // iff last_canny_u8
+    const uint64_t *strong_unused;
+    if ((rc = dev_canny_map(ctx, d_img, sigma, min_val, max_val, height, width, n_frames, d_edges, &strong_unused))) return rc;
     return dev_corners(ctx, ctx->smoothed.p, ctx->last_canny_u8 != 0, n_frames, height, width, a, out);
 }
 
@@ -5931,9 +5875,7 @@ int canny_hip_dev_corners_plane(canny_hip_ctx *ctx, const unsigned char *d_plane
     bool plane_u8 = true;
     if (!d_plane) {
         // the plane the last canny call left: only for the batch it belongs to
-        if (!ctx->last_canny_n || !ctx->smoothed.p || ctx->last_canny_n != n_frames || ctx->last_canny_h != height ||
-            ctx->last_canny_w != width)
-            return CANNY_HIP_ERR_INVALID;
+        if (!last_canny_was(ctx, n_frames, height, width) || !ctx->smoothed.p) return CANNY_HIP_ERR_INVALID;
         plane = ctx->smoothed.p;
         plane_u8 = ctx->last_canny_u8 != 0;
     }
@@ -5994,13 +5936,7 @@ int canny_hip_dev_corners_arith(canny_hip_ctx *ctx, const int *d_sums, size_t n,
 
 int canny_hip_corners_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches)
 {
-    if (part < 0 || part >= CANNY_HIP_CORNER_PARTS || !total_ms || !launches) return CANNY_HIP_ERR_INVALID;
-    int rc = bind(ctx);
-    if (rc) return rc;
-    if ((rc = profile_collect(ctx))) return rc;
-    *total_ms = ctx->total_ms[canny_hip_ctx::kProfCorners + part];
-    *launches = ctx->launches[canny_hip_ctx::kProfCorners + part];
-    return CANNY_HIP_OK;
+    return profile_part_get(ctx, canny_hip_ctx::kProfCorners, CANNY_HIP_CORNER_PARTS, part, total_ms, launches);
 }
 
 // Host-only: the launch plans of the capped launches of the corners.
@@ -6020,7 +5956,7 @@ int canny_hip_selftest_corners_plan(int which, int n_frames, int height, int wid
     } else {
         return CANNY_HIP_ERR_INVALID;
     }
-    out[0] = p.units, out[1] = p.per_group, out[2] = p.grid, out[3] = p.trips(), out[4] = (unsigned long long)p.aux;
+    store_plan(out, p);
     return CANNY_HIP_OK;
 }
 
@@ -6086,9 +6022,7 @@ int canny_hip_dev_corner_descriptors(canny_hip_ctx *ctx, const unsigned char *d_
     bool plane_u8 = true;
     if (!d_plane) {
         // the plane the last canny call left: only for the batch it belongs to
-        if (!ctx->last_canny_n || !ctx->smoothed.p || ctx->last_canny_n != n_frames || ctx->last_canny_h != height ||
-            ctx->last_canny_w != width)
-            return CANNY_HIP_ERR_INVALID;
+        if (!last_canny_was(ctx, n_frames, height, width) || !ctx->smoothed.p) return CANNY_HIP_ERR_INVALID;
         plane = ctx->smoothed.p;
         plane_u8 = ctx->last_canny_u8 != 0;
     }
@@ -6191,13 +6125,7 @@ int canny_hip_dev_match_descriptors(canny_hip_ctx *ctx, const unsigned long long
 
 int canny_hip_descriptors_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches)
 {
-    if (part < 0 || part >= CANNY_HIP_DESC_PARTS || !total_ms || !launches) return CANNY_HIP_ERR_INVALID;
-    int rc = bind(ctx);
-    if (rc) return rc;
-    if ((rc = profile_collect(ctx))) return rc;
-    *total_ms = ctx->total_ms[canny_hip_ctx::kProfDescriptors + part];
-    *launches = ctx->launches[canny_hip_ctx::kProfDescriptors + part];
-    return CANNY_HIP_OK;
+    return profile_part_get(ctx, canny_hip_ctx::kProfDescriptors, CANNY_HIP_DESC_PARTS, part, total_ms, launches);
 }
 
 // Host-only: the launch plans of the capped launches of the descriptors and their matching.
@@ -6214,7 +6142,7 @@ int canny_hip_selftest_descriptors_plan(int which, unsigned long long n, int str
     } else {
         return CANNY_HIP_ERR_INVALID;
     }
-    out[0] = p.units, out[1] = p.per_group, out[2] = p.grid, out[3] = p.trips(), out[4] = (unsigned long long)p.aux;
+    store_plan(out, p);
     return CANNY_HIP_OK;
 }
 
@@ -6342,13 +6270,7 @@ int canny_hip_canny_motion(canny_hip_ctx *ctx, const unsigned char *imgs, int n_
 
 int canny_hip_motion_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches)
 {
-    if (part < 0 || part >= CANNY_HIP_MOTION_PARTS || !total_ms || !launches) return CANNY_HIP_ERR_INVALID;
-    int rc = bind(ctx);
-    if (rc) return rc;
-    if ((rc = profile_collect(ctx))) return rc;
-    *total_ms = ctx->total_ms[canny_hip_ctx::kProfMotion + part];
-    *launches = ctx->launches[canny_hip_ctx::kProfMotion + part];
-    return CANNY_HIP_OK;
+    return profile_part_get(ctx, canny_hip_ctx::kProfMotion, CANNY_HIP_MOTION_PARTS, part, total_ms, launches);
 }
 
 // Host-only: the launch plans of the capped launches of the motion estimate.
@@ -6364,7 +6286,7 @@ int canny_hip_selftest_motion_plan(int which, unsigned long long n_pairs, int hy
         p = plan_motion_score(n_pairs, hypotheses);
     else
         return CANNY_HIP_ERR_INVALID;
-    out[0] = p.units, out[1] = p.per_group, out[2] = p.grid, out[3] = p.trips(), out[4] = (unsigned long long)p.aux;
+    store_plan(out, p);
     return CANNY_HIP_OK;
 }
 
@@ -6531,13 +6453,7 @@ int canny_hip_canny_align(canny_hip_ctx *ctx, const unsigned char *imgs, int n_f
 
 int canny_hip_warp_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches)
 {
-    if (part < 0 || part >= CANNY_HIP_WARP_PARTS || !total_ms || !launches) return CANNY_HIP_ERR_INVALID;
-    int rc = bind(ctx);
-    if (rc) return rc;
-    if ((rc = profile_collect(ctx))) return rc;
-    *total_ms = ctx->total_ms[canny_hip_ctx::kProfWarp + part];
-    *launches = ctx->launches[canny_hip_ctx::kProfWarp + part];
-    return CANNY_HIP_OK;
+    return profile_part_get(ctx, canny_hip_ctx::kProfWarp, CANNY_HIP_WARP_PARTS, part, total_ms, launches);
 }
 
 // Host-only: the launch plan of the warp and, for one record and tile, what the tiled route does with it.
@@ -6546,7 +6462,7 @@ int canny_hip_selftest_warp_plan(int n_out, int out_h, int out_w, unsigned long 
 {
     if (!out || warp_check(1, 1, 1, n_out, out_h, out_w, 0, 0)) return CANNY_HIP_ERR_INVALID;
     const LaunchPlan p = plan_warp_tiles(n_out, out_h, out_w);
-    out[0] = p.units, out[1] = p.per_group, out[2] = p.grid, out[3] = p.trips(), out[4] = (unsigned long long)p.aux;
+    store_plan(out, p);
     if (!xform) return CANNY_HIP_OK;
     if (!box || warp_check(1, src_h, src_w, 1, 1, 1, interp, 0) || tile_x < 0 || tile_y < 0 || tile_x * 64 >= out_w ||
         tile_y * 16 >= out_h)
@@ -6678,13 +6594,7 @@ int canny_hip_canny_background(canny_hip_ctx *ctx, const unsigned char *imgs, in
 
 int canny_hip_fuse_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches)
 {
-    if (part < 0 || part >= CANNY_HIP_FUSE_PARTS || !total_ms || !launches) return CANNY_HIP_ERR_INVALID;
-    int rc = bind(ctx);
-    if (rc) return rc;
-    if ((rc = profile_collect(ctx))) return rc;
-    *total_ms = ctx->total_ms[canny_hip_ctx::kProfFuse + part];
-    *launches = ctx->launches[canny_hip_ctx::kProfFuse + part];
-    return CANNY_HIP_OK;
+    return profile_part_get(ctx, canny_hip_ctx::kProfFuse, CANNY_HIP_FUSE_PARTS, part, total_ms, launches);
 }
 
 // Host-only: the launch plans of the two capped launches of the temporal fusion.
@@ -6702,7 +6612,7 @@ int canny_hip_selftest_fuse_plan(int which, int n_frames, int h, int w, int grou
     } else {
         return CANNY_HIP_ERR_INVALID;
     }
-    out[0] = p.units, out[1] = p.per_group, out[2] = p.grid, out[3] = p.trips(), out[4] = (unsigned long long)p.aux;
+    store_plan(out, p);
     return CANNY_HIP_OK;
 }
 
@@ -6782,9 +6692,7 @@ int canny_hip_dev_canny_morph(canny_hip_ctx *ctx, int n_frames, int h, int w, in
     if (!d_out_bits || ((uintptr_t)d_counts & 7)) return CANNY_HIP_ERR_INVALID;
     if ((rc = morph_check(n_frames, h, w, op, rows, kw, kh, border, iterations))) return rc;
     // the plane the last canny call left: only for the batch it belongs to
-    if (!ctx->last_canny_n || !ctx->plane_s.p || ctx->last_canny_n != n_frames || ctx->last_canny_h != h ||
-        ctx->last_canny_w != w)
-        return CANNY_HIP_ERR_INVALID;
+    if (!last_canny_was(ctx, n_frames, h, w) || !ctx->plane_s.p) return CANNY_HIP_ERR_INVALID;
     if (opt_overlap(d_out_bits, npx(h, (w + 7) / 8, n_frames), d_counts, (size_t)n_frames * sizeof(long long)))
         return CANNY_HIP_ERR_INVALID;
     if ((rc = finish_pending(ctx))) return rc;
@@ -6828,13 +6736,7 @@ int canny_hip_canny_morph(canny_hip_ctx *ctx, const unsigned char *imgs, int n_f
 
 int canny_hip_morph_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches)
 {
-    if (part < 0 || part >= CANNY_HIP_MORPH_PARTS || !total_ms || !launches) return CANNY_HIP_ERR_INVALID;
-    int rc = bind(ctx);
-    if (rc) return rc;
-    if ((rc = profile_collect(ctx))) return rc;
-    *total_ms = ctx->total_ms[canny_hip_ctx::kProfMorph + part];
-    *launches = ctx->launches[canny_hip_ctx::kProfMorph + part];
-    return CANNY_HIP_OK;
+    return profile_part_get(ctx, canny_hip_ctx::kProfMorph, CANNY_HIP_MORPH_PARTS, part, total_ms, launches);
 }
 
 // Host-only: the launch plan of one primitive step and the route automatic takes for a full rectangle of kw x kh.
@@ -6846,8 +6748,8 @@ int canny_hip_selftest_morph_plan(int n_frames, int h, int w, int kw, int kh, un
     const int rc = fuse_stack_check(n_frames, h, w);
     if (rc) return rc;
     const LaunchPlan p = plan_morph_tiles(n_frames, h, w);
-    out[0] = p.units, out[1] = p.per_group, out[2] = p.grid, out[3] = p.trips();
-    out[4] = (unsigned long long)morph_auto_route(kw, kh);
+    store_plan(out, p);
+    out[4] = (unsigned long long)morph_auto_route(kw, kh); // the route, not aux
     return CANNY_HIP_OK;
 }
 

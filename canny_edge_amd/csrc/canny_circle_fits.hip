@@ -24,6 +24,7 @@
 //            edgels of the pixels past the queue: the same bytes, more slowly.
 // Threads 0 and 1 store the record as two 16-byte words.  Plain C++, no inline assembly, no scratch.
 #include "canny_line_support.h"
+#include "canny_wave.h"
 
 namespace canny {
 
@@ -268,13 +269,6 @@ __device__ __forceinline__ void cf_add(int pass, long long u, long long v, long 
     }
 }
 
-__device__ __forceinline__ long long cf_wave_sum(long long v)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-    return v;
-}
-
 // grid (centres_max, n_frames); one workgroup per circle slot
 template <bool BITS, class T>
 __global__ __launch_bounds__(kCfBlock, 3) void circle_fits_kernel(const void *__restrict__ src, HystGeom g, int row_bytes,
@@ -341,7 +335,7 @@ __global__ __launch_bounds__(kCfBlock, 3) void circle_fits_kernel(const void *__
         const bool moments = pass == 0 || (pass == 2 && trim_q8 > 0);
 #pragma unroll
         for (int i = 0; i < kCfSums; i++)
-            if (i == kCfSums - 1 ? pass != 0 : moments) v[i] = cf_wave_sum(v[i]);
+            if (i == kCfSums - 1 ? pass != 0 : moments) v[i] = wave_sum(v[i]);
 #pragma unroll
         for (int d = 32; d >= 1; d >>= 1) {
             a.maxd = max(a.maxd, __shfl_xor(a.maxd, d));

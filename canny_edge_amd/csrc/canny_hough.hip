@@ -20,6 +20,7 @@
 // -ffp-contract=off; __fmul_rn / __fadd_rn say so again at the place it matters): x*cos, y*sin, their sum; then
 // round-half-even to int (v_rndne_f32).  No transcendental function runs on the device: the tables come from the host.
 #include "canny_kernels.h"
+#include "canny_wave.h"
 
 #include <algorithm>
 
@@ -172,30 +173,6 @@ __device__ __forceinline__ int peak_votes(const int *__restrict__ acc, int strid
     return (v > p[-1] && v >= p[1] && v > p[-stride] && v >= p[stride]) ? v : 0;
 }
 
-// Exclusive prefix of one value per thread over a 256-thread workgroup; *total receives the workgroup's sum.
-__device__ __forceinline__ unsigned block_scan256(unsigned v, unsigned *s_wave, unsigned *total)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    unsigned incl = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const unsigned t = __shfl_up(incl, d);
-        if (lane >= d) incl += t;
-    }
-    if (lane == 63) s_wave[wave] = incl;
-    __syncthreads();
-    unsigned before = 0, sum = 0;
-#pragma unroll
-    for (int w = 0; w < 4; w++) {
-        const unsigned t = s_wave[w];
-        if (w < wave) before += t;
-        sum += t;
-    }
-    __syncthreads();
-    *total = sum;
-    return before + incl - v;
-}
-
 // grid (blocks, n_frames): counts[f] = peaks of frame f; hist[f][v] = peaks with v votes (v clamped to nb - 1, which the
 // host's bound on a cell's votes never reaches)
 __global__ __launch_bounds__(kCellBlock) void hough_peaks_kernel(const int *__restrict__ accum, int numangle, int numrho,
@@ -214,8 +191,7 @@ __global__ __launch_bounds__(kCellBlock) void hough_peaks_kernel(const int *__re
             atomicAdd(&hist[(size_t)f * nb + min(v, nb - 1)], 1u);
         }
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) mine += __shfl_xor(mine, d);
+    mine = wave_sum(mine);
     if ((threadIdx.x & 63) == 0 && mine) atomicAdd(&counts[f], (int)mine);
 }
 
@@ -242,7 +218,7 @@ __global__ __launch_bounds__(kCellBlock) void hough_cut_kernel(const int *__rest
         const int v = top - (int)threadIdx.x;
         const unsigned here = v >= 0 ? h[v] : 0u;
         unsigned chunk;
-        const unsigned ex = block_scan256(here, s_wave, &chunk);
+        const unsigned ex = block_exclusive_scan(here, s_wave, &chunk);
         if (here && above + ex < K && above + ex + here >= K) {
             c[kCutVote] = (unsigned)v;
             c[kCutNeed] = K - (above + ex);
@@ -290,7 +266,7 @@ __global__ __launch_bounds__(kCellBlock) void hough_tie_base_kernel(const int *_
         const int n = n0 + (int)threadIdx.x;
         const unsigned here = n < numangle ? t[n] : 0u;
         unsigned chunk;
-        const unsigned ex = block_scan256(here, s_wave, &chunk);
+        const unsigned ex = block_exclusive_scan(here, s_wave, &chunk);
         if (here && before + ex < need && before + ex + here >= need) {
             s_row = (unsigned)n;
             s_rank = need - (before + ex); // 1-based rank of the tie within its row
@@ -307,7 +283,7 @@ __global__ __launch_bounds__(kCellBlock) void hough_tie_base_kernel(const int *_
         const unsigned here =
             (r < numrho && acc[(size_t)(n + 1) * stride + r + 1] == vc && peak_votes(acc, stride, n, r, threshold)) ? 1u : 0u;
         unsigned chunk;
-        const unsigned ex = block_scan256(here, s_wave, &chunk);
+        const unsigned ex = block_exclusive_scan(here, s_wave, &chunk);
         if (here && before + ex + 1 == rank) c[kCutBase] = (unsigned)((n + 1) * stride + r + 1);
         before += chunk;
     }

@@ -12,6 +12,7 @@
 // over the same positions recomputes the edgels for the residuals and the extent (sum, max, min reductions), and lanes
 // 0..11 store one word each.  No LDS, no scratch, plain C++.
 #include "canny_line_support.h"
+#include "canny_wave.h"
 
 namespace canny {
 
@@ -126,31 +127,6 @@ __device__ __forceinline__ void fit_walk(const SegSrc &src, const HystGeom &g, i
             use((long long)((int)e.x - 256 * sgm.x0), (long long)((int)e.y - 256 * sgm.y0));
         }
     }
-}
-
-__device__ __forceinline__ long long wave_sum(long long v)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-    return v;
-}
-__device__ __forceinline__ long long wave_min(long long v)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        const long long o = __shfl_xor(v, d);
-        v = o < v ? o : v;
-    }
-    return v;
-}
-__device__ __forceinline__ long long wave_max(long long v)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        const long long o = __shfl_xor(v, d);
-        v = o > v ? o : v;
-    }
-    return v;
 }
 
 // grid (ceil(segments_max / 4), n_frames); one wave per segment slot

@@ -13,6 +13,7 @@
 //   refit  : one workgroup per pair: arg-max over (count desc, h asc), the inlier pass with the flags and the eleven sums
 //            (wave reductions), the 128-bit algebra with a restoring division on one lane, the residual pass, the record.
 #include "canny_kernels.h"
+#include "canny_wave.h"
 
 namespace canny {
 
@@ -123,12 +124,6 @@ __device__ __forceinline__ long long mt_floor_div64(long long n, long long d) //
     long long q = n / d;
     if (n % d != 0 && n < 0) q--;
     return q;
-}
-
-__device__ __forceinline__ long long mt_wave_sum(long long v)
-{
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d);
-    return v;
 }
 
 // grid plan_motion_pairs.  list, slot: [n_pairs][stride_q]; m_out: [n_pairs]
@@ -281,7 +276,7 @@ __global__ __launch_bounds__(kBlock) void motion_refit_kernel(const Packed *__re
         }
 #pragma unroll
         for (int k = 0; k < kSums; k++) {
-            const long long v = mt_wave_sum(s[k]);
+            const long long v = wave_sum(s[k]);
             if (lane == 0) s_sum[wave][k] = v;
         }
         __syncthreads();
@@ -339,7 +334,7 @@ __global__ __launch_bounds__(kBlock) void motion_refit_kernel(const Packed *__re
                 worst = max(worst, g);
             }
         }
-        total = mt_wave_sum(total);
+        total = wave_sum(total);
         for (int d = 32; d > 0; d >>= 1) worst = max(worst, __shfl_xor(worst, d));
         __syncthreads(); // s_sum: thread 0 has read the sums
         if (lane == 0) s_sum[wave][0] = total, s_sum[wave][1] = worst;

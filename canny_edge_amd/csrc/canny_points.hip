@@ -19,6 +19,7 @@
 //                  its padding bits are masked off, never trusted
 // Nothing is stored at or beyond points + capacity; the counts and offsets are always the true ones.
 #include "canny_kernels.h"
+#include "canny_wave.h"
 
 #include <algorithm>
 
@@ -45,32 +46,6 @@ __global__ __launch_bounds__(kPtsBlock) void points_count_kernel(const void *__r
     }
 }
 
-// Exclusive prefix of one value per thread over a 256-thread workgroup; *total receives the workgroup's sum.
-// s_wave: 4 words of LDS, free for reuse after the call.
-__device__ __forceinline__ unsigned long long block_exclusive_scan(unsigned long long v, unsigned long long *s_wave,
-                                                                   unsigned long long *total)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    unsigned long long incl = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const unsigned long long t = __shfl_up(incl, d);
-        if (lane >= d) incl += t;
-    }
-    if (lane == 63) s_wave[wave] = incl;
-    __syncthreads();
-    unsigned long long before = 0, sum = 0;
-#pragma unroll
-    for (int w = 0; w < 4; w++) {
-        const unsigned long long t = s_wave[w];
-        if (w < wave) before += t;
-        sum += t;
-    }
-    __syncthreads();
-    *total = sum;
-    return before + incl - v;
-}
-
 // rows[f][y]: count of row y -> number of edge pixels of frame f before row y; totals[f] = the frame's count
 __global__ __launch_bounds__(256) void points_scan_rows_kernel(uint32_t *__restrict__ rows,
                                                                unsigned long long *__restrict__ totals, int height)
@@ -81,7 +56,7 @@ __global__ __launch_bounds__(256) void points_scan_rows_kernel(uint32_t *__restr
     for (int base = 0; base < height; base += 256) {
         const int i = base + (int)threadIdx.x;
         unsigned long long chunk;
-        const unsigned long long ex = block_exclusive_scan(i < height ? r[i] : 0u, s_wave, &chunk);
+        const unsigned long long ex = block_exclusive_scan<unsigned long long>(i < height ? r[i] : 0u, s_wave, &chunk);
         if (i < height) r[i] = (uint32_t)(carry + ex); // < height * width < 2^31
         carry += chunk;
     }

@@ -25,6 +25,7 @@
 // stored once by one wave, nothing depends on the order in which waves run: the output is the same bytes on every run.
 // Every loop is bounded by the chain's length: no input can spin a kernel.
 #include "canny_kernels.h"
+#include "canny_wave.h"
 
 #include <algorithm>
 
@@ -36,23 +37,6 @@ constexpr int kPgBlock = 256;         // 4 waves: 4 records per workgroup step
 constexpr int kPgScanPerThread = 8;   // the scan: 8 consecutive entries per thread
 constexpr int kPgScanChunk = 256 * kPgScanPerThread;
 constexpr unsigned kPgEpsMax = 1u << 24;
-
-__device__ __forceinline__ unsigned long long pg_wave_max(unsigned long long v)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        const unsigned long long t = __shfl_xor(v, d);
-        v = t > v ? t : v;
-    }
-    return v;
-}
-
-__device__ __forceinline__ unsigned long long pg_wave_sum(unsigned long long v)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-    return v;
-}
 
 // a wave-uniform 64-bit value as a scalar
 __device__ __forceinline__ unsigned long long pg_uniform(unsigned long long v)
@@ -149,7 +133,7 @@ __global__ __launch_bounds__(kPgBlock) void pg_simplify_kernel(const unsigned lo
             const int x0 = __builtin_amdgcn_readfirstlane(x), y0 = __builtin_amdgcn_readfirstlane(y);
             const unsigned low = 63u - (unsigned)lane; // the complemented position
             const unsigned d0 = (unsigned)((x - x0) * (x - x0) + (y - y0) * (y - y0));
-            unsigned long long key = pg_uniform(pg_wave_max(mine ? ((unsigned long long)d0 << 32) | low : 0ull));
+            unsigned long long key = pg_uniform(wave_max(mine ? ((unsigned long long)d0 << 32) | low : 0ull));
             int a = 0, b = 63 - (int)(key & 63u); // b = k
             unsigned long long mask = nn ? 1ull | (1ull << b) : 0ull;
             for (int guard = 0; guard < 2 * nn + 2 && nn >= 2; guard++) {
@@ -159,7 +143,7 @@ __global__ __launch_bounds__(kPgBlock) void pg_simplify_kernel(const unsigned lo
                     const int bx = __builtin_amdgcn_readlane(x, bl), by = __builtin_amdgcn_readlane(y, bl);
                     const bool in = lane > a && lane < b;
                     const unsigned c = pg_dist(ax, ay, bx, by, x, y);
-                    key = pg_uniform(pg_wave_max(in ? ((unsigned long long)c << 32) | low : 0ull));
+                    key = pg_uniform(wave_max(in ? ((unsigned long long)c << 32) | low : 0ull));
                     if (pg_splits((unsigned)(key >> 32), bx - ax, by - ay, eps)) {
                         b = 63 - (int)(key & 63u);
                         mask |= 1ull << b;
@@ -191,9 +175,9 @@ __global__ __launch_bounds__(kPgBlock) void pg_simplify_kernel(const unsigned lo
                 key = k > key ? k : key;
                 flags[i] = 0;
             }
-            length_q8 = 256ull * pg_wave_sum(n_axis) + 362ull * pg_wave_sum(n_diag);
+            length_q8 = 256ull * wave_sum<unsigned long long>(n_axis) + 362ull * wave_sum<unsigned long long>(n_diag);
             const unsigned eps = pg_eps(epsilon_q8, ratio_q16, length_q8);
-            key = pg_uniform(pg_wave_max(key));
+            key = pg_uniform(wave_max(key));
             unsigned long long a = 0, b = 0xFFFFFFFFu - (unsigned)key; // b = k
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             if (lane == 0) flags[0] = 1, flags[b] = 1;
@@ -219,7 +203,7 @@ __global__ __launch_bounds__(kPgBlock) void pg_simplify_kernel(const unsigned lo
                             key = k > key ? k : key;
                         }
                     }
-                    key = pg_uniform(pg_wave_max(key));
+                    key = pg_uniform(wave_max(key));
                     if (pg_splits((unsigned)(key >> 32), bx - ax, by - ay, eps)) {
                         b = 0xFFFFFFFFu - (unsigned)key;
                         if (lane == 0) flags[b] = 1;
@@ -248,31 +232,6 @@ __global__ __launch_bounds__(kPgBlock) void pg_simplify_kernel(const unsigned lo
     }
 }
 
-// exclusive scan of one value per thread over the block's 256 threads; *total = the block's sum
-__device__ __forceinline__ unsigned long long pg_block_scan(unsigned long long v, unsigned long long *s_wave,
-                                                            unsigned long long *total)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    unsigned long long incl = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const unsigned long long t = __shfl_up(incl, d);
-        if (lane >= d) incl += t;
-    }
-    if (lane == 63) s_wave[wave] = incl;
-    __syncthreads();
-    unsigned long long before = 0, sum = 0;
-#pragma unroll
-    for (int w = 0; w < 4; w++) {
-        const unsigned long long t = s_wave[w];
-        if (w < wave) before += t;
-        sum += t;
-    }
-    __syncthreads();
-    *total = sum;
-    return before + incl - v;
-}
-
 __device__ __forceinline__ unsigned long long pg_records(const unsigned long long *offsets, int n_frames,
                                                          unsigned long long capacity)
 {
@@ -297,7 +256,7 @@ __global__ __launch_bounds__(256) void pg_scan_chunks_kernel(const unsigned long
         sum += v[k];
     }
     unsigned long long chunk;
-    unsigned long long run = pg_block_scan(sum, s_wave, &chunk);
+    unsigned long long run = block_exclusive_scan(sum, s_wave, &chunk);
 #pragma unroll
     for (int k = 0; k < kPgScanPerThread; k++) {
         run += v[k];
@@ -314,7 +273,7 @@ __global__ __launch_bounds__(256) void pg_scan_sums_kernel(unsigned long long *_
     for (unsigned base = 0; base < n_blocks; base += 256) {
         const unsigned i = base + threadIdx.x;
         unsigned long long chunk;
-        const unsigned long long ex = pg_block_scan(i < n_blocks ? block_sums[i] : 0ull, s_wave, &chunk);
+        const unsigned long long ex = block_exclusive_scan(i < n_blocks ? block_sums[i] : 0ull, s_wave, &chunk);
         if (i < n_blocks) block_sums[i] = carry + ex;
         carry += chunk;
     }
@@ -410,7 +369,7 @@ __global__ __launch_bounds__(kPgBlock) void pg_emit_kernel(const unsigned long l
             have += n_set;
         }
         if (!measures) continue;
-        long long area2 = (long long)pg_wave_sum((unsigned long long)area);
+        long long area2 = (long long)wave_sum((unsigned long long)area);
         if (have >= 1) area2 += pg_cross(l1x, l1y, f0x, f0y);
         if (have >= 3) {
             const long long t1 = pg_cross(l1x - l2x, l1y - l2y, f0x - l1x, f0y - l1y);

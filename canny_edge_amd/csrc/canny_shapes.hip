@@ -28,6 +28,7 @@
 // Every loop is bounded by the chain's length: no input can spin a kernel.  A chain whose bounding box is wider than its
 // point count is no 8-connected closed chain; it is answered like a cut one, so no input can write outside its own slots.
 #include "canny_kernels.h"
+#include "canny_wave.h"
 
 #include <limits.h>
 
@@ -40,13 +41,6 @@ constexpr int kShWords = 20;  // CANNY_HIP_SHAPE_WORDS
 constexpr int kShSums = 11;   // area2 .. s02
 
 typedef unsigned long long u64;
-
-__device__ __forceinline__ u64 sh_wave_sum(u64 v)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-    return v;
-}
 
 // The eleven sums of a wave at once, in 17 shuffles of 64 bits instead of 66: at every step of the butterfly a lane keeps half
 // of its values and hands the other half to its partner, which keeps those, so 8, 4, 2 and 1 values cross at the distances
@@ -69,26 +63,6 @@ __device__ __forceinline__ u64 sh_wave_sums(const u64 (&s)[11], int lane)
     d += __shfl_xor(d, 2);
     d += __shfl_xor(d, 1);
     return d;
-}
-
-__device__ __forceinline__ int sh_wave_min(int v)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        const int t = __shfl_xor(v, d);
-        v = t < v ? t : v;
-    }
-    return v;
-}
-
-__device__ __forceinline__ int sh_wave_max(int v)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        const int t = __shfl_xor(v, d);
-        v = t > v ? t : v;
-    }
-    return v;
 }
 
 __device__ __forceinline__ long long sh_cross(long long ax, long long ay, long long bx, long long by)
@@ -207,8 +181,8 @@ __global__ __launch_bounds__(kShBlock) void sh_measure_kernel(const u64 *__restr
             const int nxt = lane + 1 == nn ? 0 : lane + 1;
             const int xn = __shfl(x, nxt), yn = __shfl(y, nxt);
             if (mine) sh_terms(x - x0, y - y0, xn - x0, yn - y0, s);
-            left = sh_wave_min(x); // the spare lanes hold P_0
-            cols = sh_wave_max(x) - left + 1;
+            left = wave_min(x); // the spare lanes hold P_0
+            cols = wave_max(x) - left + 1;
             ylo = INT_MAX, yhi = -1;
             for (int k = 0; k < nn; k++) {
                 const int xk = __shfl(x, k), yk = __shfl(y, k);
@@ -224,8 +198,8 @@ __global__ __launch_bounds__(kShBlock) void sh_measure_kernel(const u64 *__restr
                 sh_terms(xi - x0, yi - y0, xn - x0, yn - y0, s);
                 xmin = xi < xmin ? xi : xmin, xmax = xi > xmax ? xi : xmax;
             }
-            left = sh_wave_min(xmin);
-            cols = sh_wave_max(xmax) - left + 1;
+            left = wave_min(xmin);
+            cols = wave_max(xmax) - left + 1;
         }
         bool bad = (u64)cols > n; // wider than it is long: not an 8-connected closed chain
         if (!bad && n > 64) {
@@ -424,7 +398,7 @@ __global__ __launch_bounds__(kShBlock) void sh_emit_kernel(const u64 *__restrict
             o.have = __shfl_xor((int)win.have, d) != 0;
             if (sh_better(o, win)) win = o;
         }
-        const long long area2 = (long long)sh_wave_sum((u64)area);
+        const long long area2 = (long long)wave_sum((u64)area);
         long long *m = measures + kShWords * j;
         if (lane == 0) m[14] = area2;
         if (best.have && best.k == win.k) { // the lane that tried the winning edge
