@@ -147,6 +147,8 @@ EXPORTS = (
     "canny_hip_selftest_fuse_mean",
     "canny_hip_dev_morph_bits", "canny_hip_dev_canny_morph", "canny_hip_canny_morph", "canny_hip_morph_bits",
     "canny_hip_morph_element", "canny_hip_selftest_morph_plan", "canny_hip_morph_profile_get",
+    "canny_hip_dev_binarize", "canny_hip_binarize_batch", "canny_hip_binarize", "canny_hip_otsu_from_histogram",
+    "canny_hip_selftest_binarize_plan", "canny_hip_profile_part_get",
 )
 
 _lib: Optional[C.CDLL] = None
@@ -420,6 +422,12 @@ def load() -> C.CDLL:
         "canny_hip_morph_element": ([i, i, i, p], i),
         "canny_hip_selftest_morph_plan": ([i, i, i, i, i, p], i),
         "canny_hip_morph_profile_get": ([p, i, C.POINTER(C.c_double), C.POINTER(C.c_long)], i),
+        "canny_hip_dev_binarize": ([p, p, i, i, i, i, i, i, i, i, p, p, p], i),
+        "canny_hip_binarize_batch": ([p, p, i, i, i, i, i, i, i, i, p, p, p], i),
+        "canny_hip_binarize": ([p, i, i, i, i, i, i, i, i, p, p, p], i),
+        "canny_hip_otsu_from_histogram": ([p, C.POINTER(C.c_int)], i),
+        "canny_hip_selftest_binarize_plan": ([i, i, i, i, i, i, p], i),
+        "canny_hip_profile_part_get": ([p, C.c_char_p, i, C.POINTER(C.c_double), C.POINTER(C.c_long)], i),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -1280,6 +1288,47 @@ def morph_plan(n_frames: int, h: int, w: int, kw: int = 3, kh: int = 3):
     """Host-only: the LaunchPlan of one primitive step of the morphology (one tile of 8 words x 64 rows per workgroup and
     trip); aux = the route automatic takes for a full rectangle of kw x kh (1 general, 2 separable)."""
     return _plan("morph_plan", int(n_frames), int(h), int(w), int(kw), int(kh))
+
+
+# ---- binarization: gray planes to packed bit maps (DESIGN.md section 36) --------------------------------------------------
+BIN_FIXED, BIN_OTSU, BIN_ADAPTIVE_MEAN = range(3)
+BIN_METHODS = ("fixed", "otsu", "mean")
+BIN_PARTS = ("histogram", "select", "map")
+BIN_ROUTE_AUTO, BIN_ROUTE_DIRECT, BIN_ROUTE_MARCH = 0, 1, 2
+BIN_MAX_EXTENT, BIN_OTSU_MAX_PIXELS = 255, 1 << 26
+BinarizeTiling = collections.namedtuple("BinarizeTiling", "strip_cols segment_rows direct_trips march_trips staged_cols")
+
+
+def binarize(imgs, method: int, thr_or_c: int = 0, kw: int = 3, kh: Optional[int] = None, invert: int = 0):
+    """Host-only, needs no GPU: the rule on frames uint8 [n_frames, H, W] -> (bit maps uint8 [n_frames, H, ceil(W / 8)] with
+    rows MSB-first and pad bits 0, counts int64 [n_frames], thresholds int32 [n_frames]: OTSU t[f], FIXED thr, MEAN c)."""
+    a = np.ascontiguousarray(imgs, dtype=np.uint8)
+    if a.ndim != 3:
+        raise ValueError("expected uint8 [n_frames, H, W]")
+    n, h, w = a.shape
+    out, counts, thr = np.zeros((n, h, (w + 7) // 8), np.uint8), np.zeros(n, np.int64), np.zeros(n, np.int32)
+    _ok(load().canny_hip_binarize(_hp(a), n, h, w, int(method), int(thr_or_c), int(kw), int(kw if kh is None else kh),
+                                  int(invert), _hp(out), _hp(counts), _hp(thr)), "binarize")
+    return out, counts, thr
+
+
+def otsu_from_histogram(hist) -> int:
+    """Host-only: Otsu's threshold of the rule for a histogram of 256 bins and at most 2^26 samples."""
+    h = np.ascontiguousarray(hist, dtype=np.uint64).reshape(-1)
+    if h.size != 256:
+        raise ValueError("expected 256 bins")
+    t = C.c_int(-1)
+    _ok(load().canny_hip_otsu_from_histogram(_hp(h), C.byref(t)), "otsu_from_histogram")
+    return t.value
+
+
+def binarize_plan(n_frames: int, h: int, w: int, method: int = BIN_ADAPTIVE_MEAN, kw: int = 3, kh: int = 3):
+    """Host-only: (LaunchPlan of the launch that writes the bits under the route automatic takes, aux = that route for
+    ADAPTIVE_MEAN (1 straightforward, 2 marching; 0 otherwise), BinarizeTiling: the useful columns of a marching strip, the
+    rows of a segment for kh, the trips of the straightforward (and FIXED / OTSU) launch, the trips of the marching launch,
+    the staged columns of a strip for kw)."""
+    plan, *tail = _plan("binarize_plan", int(n_frames), int(h), int(w), int(method), int(kw), int(kh), n=10)
+    return plan, BinarizeTiling(*tail)
 
 
 # ---- chamfer template matching (DESIGN.md section 26) --------------------------------------------------------------------
@@ -2802,6 +2851,38 @@ class Context:
     def morph_profile(self, part: int = 0) -> Tuple[float, int]:
         """(total ms, launch groups) of part 0, all primitive steps of the morphology calls."""
         return self._profile_part("morph_profile_get", int(part))
+
+    # ---- binarization: gray planes to packed bit maps (DESIGN.md section 36) -----------------------------------------
+    def dev_binarize(self, d_plane: int, n_frames: int, h: int, w: int, method: int, thr_or_c: int, d_out_bits: int,
+                     d_counts: int = 0, d_thresholds: int = 0, kw: int = 3, kh: int = 3, invert: int = 0):
+        """The operator on device planes uint8 [n_frames][h][w] (d_plane 0: the smoothed plane the preceding dev_canny of
+        the same geometry left in the context) into d_out_bits [n_frames][h][ceil(w / 8)] and, if given, the set bits of
+        each output frame as int64 at d_counts and the thresholds as int32 at d_thresholds.  Asynchronous."""
+        v = C.c_void_p
+        self._check(self._L.canny_hip_dev_binarize(self._h, v(d_plane or None), n_frames, h, w, method, thr_or_c, kw, kh,
+                                                   invert, v(d_out_bits or None), v(d_counts or None),
+                                                   v(d_thresholds or None)), "dev_binarize")
+
+    def binarize_batch(self, imgs, method: int, thr_or_c: int = 0, kw: int = 3, kh: Optional[int] = None, invert: int = 0):
+        """Upload and the operator on the GPU: imgs (N, H, W) uint8 -> (bit maps uint8 [N, H, ceil(W / 8)], counts int64 [N],
+        thresholds int32 [N])."""
+        a = np.ascontiguousarray(imgs, dtype=np.uint8)
+        if a.ndim != 3:
+            raise ValueError("expected uint8 [n_frames, H, W]")
+        n, h, w = a.shape
+        out, counts, thr = np.zeros((n, h, (w + 7) // 8), np.uint8), np.zeros(n, np.int64), np.zeros(n, np.int32)
+        self._check(self._L.canny_hip_binarize_batch(self._h, _hp(a), n, h, w, int(method), int(thr_or_c), int(kw),
+                                                     int(kw if kh is None else kh), int(invert), _hp(out), _hp(counts),
+                                                     _hp(thr)), "binarize_batch")
+        return out, counts, thr
+
+    def profile_part(self, feature: str, part: int) -> Tuple[float, int]:
+        """(total ms, launch groups) of part `part` of the named group of the profile table ("stages", "hough", ..., "morph",
+        "binarize": BIN_PARTS): what the group's own getter answers."""
+        ms, n = C.c_double(0), C.c_long(0)
+        self._check(self._L.canny_hip_profile_part_get(self._h, str(feature).encode(), int(part), C.byref(ms), C.byref(n)),
+                    "profile_part_get")
+        return ms.value, n.value
 
     def motion_profile_get(self, part: int) -> Tuple[float, int]:
         """(total ms, launch groups) of part 0 gather, 1 score, 2 refit (MOTION_PARTS)."""

@@ -350,6 +350,7 @@ constexpr ProfGroup kProfGroups[] = {
     {"warp", CANNY_HIP_WARP_PARTS},
     {"fuse", CANNY_HIP_FUSE_PARTS},
     {"morph", CANNY_HIP_MORPH_PARTS},
+    {"binarize", CANNY_HIP_BIN_PARTS},
 };
 
 // The first slot of the named group; with no name, the number of slots.  A name the table does not hold fails to compile.
@@ -468,6 +469,9 @@ struct canny_hip_ctx {
     // binary morphology: the two intermediate bit maps of a call of more than one primitive step, back to back
     DevBuf morph_ws;
     int morph_route = 0;   // 0 auto, 1 general, 2 separable (full rectangles)
+    // binarization: the histograms of the frames (OTSU) | the threshold of every frame
+    DevBuf binarize_ws;
+    int binarize_route = 0; // 0 auto, 1 straightforward, 2 marching (ADAPTIVE_MEAN)
     std::vector<int> motion_pairs; // the validated pairs of the last motion call: what its upload reads
     DevBuf plane_s, plane_c, stamps, flags; // hysteresis bit-planes / scheduling words
     DevBuf io[4];     // staging for the host-pointer stage functions
@@ -501,7 +505,8 @@ struct canny_hip_ctx {
                          kProfChamfer = prof_base("chamfer"), kProfShapes = prof_base("shapes"),
                          kProfCurves = prof_base("curves"), kProfCorners = prof_base("corners"),
                          kProfDescriptors = prof_base("descriptors"), kProfMotion = prof_base("motion"),
-                         kProfWarp = prof_base("warp"), kProfFuse = prof_base("fuse"), kProfMorph = prof_base("morph");
+                         kProfWarp = prof_base("warp"), kProfFuse = prof_base("fuse"), kProfMorph = prof_base("morph"),
+                         kProfBinarize = prof_base("binarize");
     static constexpr int kProfSlots = prof_base(nullptr);
     // "profile_stage_mask" is a non-negative int option: bit 30 is the last it can carry
     static constexpr int kProfLastBit = 30;
@@ -2054,6 +2059,7 @@ void collect_workspaces(const canny_hip_ctx *c, const std::string &prefix, std::
     add("desc_ws", c->desc_ws, I);         // the pairs address frames, the best queries are compared with indices
     add("motion_ws", c->motion_ws, I);     // the pairs address frames, m bounds the lists, the slots address the flags
     add("morph_ws", c->morph_ws, D);
+    add("binarize_ws", c->binarize_ws, D);
     add("plane_s", c->plane_s, D);
     add("plane_c", c->plane_c, D);
     add("stamps", c->stamps, I);           // tile queues and their counters
@@ -2172,6 +2178,7 @@ void canny_hip_ctx_destroy(canny_hip_ctx *ctx)
     ctx->desc_ws.release();
     ctx->motion_ws.release();
     ctx->morph_ws.release();
+    ctx->binarize_ws.release();
     ctx->cc_parent.release();
     ctx->cc_ws.release();
     ctx->ct_ws.release();
@@ -2230,6 +2237,7 @@ int canny_hip_ctx_get_option(const canny_hip_ctx *ctx, const char *name, int *va
     else if (!std::strcmp(name, "warp_route")) *value = ctx->warp_route;
     else if (!std::strcmp(name, "fuse_route")) *value = ctx->fuse_route;
     else if (!std::strcmp(name, "morph_route")) *value = ctx->morph_route;
+    else if (!std::strcmp(name, "binarize_route")) *value = ctx->binarize_route;
     else if (!std::strcmp(name, "tune_chamfer_chunk_mb")) *value = ctx->chamfer_chunk_mb;
     else if (!std::strcmp(name, "batch_expand_threads")) *value = ctx->expand_pool ? ctx->expand_pool->size() : 0; // read-only
     else return CANNY_HIP_ERR_INVALID;
@@ -2259,6 +2267,7 @@ int canny_hip_ctx_set_option(canny_hip_ctx *ctx, const char *name, int value)
     else if (!std::strcmp(name, "warp_route") && value <= 2) ctx->warp_route = value;
     else if (!std::strcmp(name, "fuse_route") && value <= 2) ctx->fuse_route = value;
     else if (!std::strcmp(name, "morph_route") && value <= 2) ctx->morph_route = value;
+    else if (!std::strcmp(name, "binarize_route") && value <= 2) ctx->binarize_route = value;
     else if (!std::strcmp(name, "tune_chamfer_chunk_mb") && value <= 4096) ctx->chamfer_chunk_mb = value;
     else if (!std::strcmp(name, "tune_hough_lds_kb") && value <= kHoughLdsMax / 1024) ctx->hough_lds_kb = value;
     else if (!std::strcmp(name, "tune_batch_expand_threads") && value <= 64) {
@@ -6750,6 +6759,155 @@ int canny_hip_selftest_morph_plan(int n_frames, int h, int w, int kw, int kh, un
     const LaunchPlan p = plan_morph_tiles(n_frames, h, w);
     store_plan(out, p);
     out[4] = (unsigned long long)morph_auto_route(kw, kh); // the route, not aux
+    return CANNY_HIP_OK;
+}
+
+// ---- binarization: gray planes to packed bit maps (canny_binarize.hip) ------------------------------
+// canny_hip_binarize and canny_hip_otsu_from_histogram, the rule in plain C++, live in canny_binarize_host.cpp.
+
+namespace {
+constexpr long long kOtsuMaxPixels = 1ll << 26;
+
+// every check of the binarization but the pointers and the overlaps
+int binarize_check(int n_frames, int h, int w, int method, int thr_or_c, int kw, int kh, int invert)
+{
+    if (n_frames < 1 || h < 1 || w < 1 || invert < 0 || invert > 1) return CANNY_HIP_ERR_INVALID;
+    if (method == CANNY_HIP_BIN_FIXED) {
+        if (thr_or_c < -1 || thr_or_c > 255) return CANNY_HIP_ERR_INVALID;
+    } else if (method == CANNY_HIP_BIN_ADAPTIVE_MEAN) {
+        if (thr_or_c < -255 || thr_or_c > 255 || kw < 3 || kw > CANNY_HIP_BIN_MAX_EXTENT || kh < 3 ||
+            kh > CANNY_HIP_BIN_MAX_EXTENT || !(kw & 1) || !(kh & 1))
+            return CANNY_HIP_ERR_INVALID;
+    } else if (method != CANNY_HIP_BIN_OTSU) {
+        return CANNY_HIP_ERR_INVALID;
+    }
+    const int rc = fuse_stack_check(n_frames, h, w);
+    if (rc) return rc;
+    if (method == CANNY_HIP_BIN_OTSU && (long long)h * w > kOtsuMaxPixels) return CANNY_HIP_ERR_UNSUPPORTED;
+    return CANNY_HIP_OK;
+}
+
+// The operator queued on the context's stream; everything has been checked.
+int dev_binarize(canny_hip_ctx *ctx, const void *plane, bool plane_u8, int n_frames, int h, int w, int method, int thr_or_c,
+                 int kw, int kh, int invert, unsigned char *d_out, long long *d_counts, int *d_thresholds)
+{
+    // the workspace: the histograms (OTSU) | the thresholds where the caller has no buffer for them
+    const size_t hist_bytes = method == CANNY_HIP_BIN_OTSU ? (((size_t)n_frames * kHistBins * sizeof(uint32_t) + 15) & ~(size_t)15) : 0;
+    int *thr = d_thresholds;
+    if (hist_bytes || (!thr && method != CANNY_HIP_BIN_ADAPTIVE_MEAN)) {
+        HIP_TRY(ctx, ctx->binarize_ws.ensure(hist_bytes + (size_t)n_frames * sizeof(int)));
+        if (!thr) thr = (int *)((unsigned char *)ctx->binarize_ws.p + hist_bytes);
+    }
+    if (method == CANNY_HIP_BIN_OTSU) {
+        uint32_t *hist = (uint32_t *)ctx->binarize_ws.p;
+        {
+            StageTimer tm(ctx, canny_hip_ctx::kProfBinarize + CANNY_HIP_BIN_PART_HISTOGRAM);
+            HIP_TRY(ctx, hipMemsetAsync(hist, 0, (size_t)n_frames * kHistBins * sizeof(uint32_t), ctx->stream));
+            HIP_TRY(ctx, launch_hist_intensity(plane, plane_u8, hist, h, w, n_frames, ctx->stream));
+        }
+        StageTimer tm(ctx, canny_hip_ctx::kProfBinarize + CANNY_HIP_BIN_PART_SELECT);
+        HIP_TRY(ctx, launch_binarize_otsu(hist, n_frames, thr, ctx->stream));
+    }
+    StageTimer tm(ctx, canny_hip_ctx::kProfBinarize + CANNY_HIP_BIN_PART_MAP);
+    if (method != CANNY_HIP_BIN_OTSU && thr) // FIXED: the kernel's thresholds; ADAPTIVE_MEAN: only what the caller reads
+        HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)thr, thr_or_c, (size_t)n_frames, ctx->stream));
+    if (method == CANNY_HIP_BIN_ADAPTIVE_MEAN)
+        HIP_TRY(ctx, launch_binarize_adaptive(plane, plane_u8, n_frames, h, w, thr_or_c, kw, kh, invert, ctx->binarize_route,
+                                              d_out, (unsigned long long *)d_counts, ctx->stream));
+    else
+        HIP_TRY(ctx, launch_binarize_map(plane, plane_u8, n_frames, h, w, thr, invert, d_out, (unsigned long long *)d_counts,
+                                         ctx->stream));
+    return CANNY_HIP_OK;
+}
+} // namespace
+
+int canny_hip_dev_binarize(canny_hip_ctx *ctx, const unsigned char *d_plane, int n_frames, int h, int w, int method,
+                           int thr_or_c, int kw, int kh, int invert, unsigned char *d_out_bits, long long *d_counts,
+                           int *d_thresholds)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!d_out_bits || ((uintptr_t)d_counts & 7) || ((uintptr_t)d_thresholds & 3)) return CANNY_HIP_ERR_INVALID;
+    if ((rc = binarize_check(n_frames, h, w, method, thr_or_c, kw, kh, invert))) return rc;
+    const void *plane = d_plane;
+    bool plane_u8 = true;
+    if (!d_plane) {
+        // the plane the last canny call left: only for the batch it belongs to
+        if (!last_canny_was(ctx, n_frames, h, w) || !ctx->smoothed.p) return CANNY_HIP_ERR_INVALID;
+        plane = ctx->smoothed.p;
+        plane_u8 = ctx->last_canny_u8 != 0;
+    }
+    const size_t in_bytes = npx(h, w, n_frames) * (plane_u8 ? 1 : 2), bytes = npx(h, (w + 7) / 8, n_frames);
+    const size_t cbytes = (size_t)n_frames * sizeof(long long), tbytes = (size_t)n_frames * sizeof(int);
+    if (ranges_overlap(plane, in_bytes, d_out_bits, bytes) || opt_overlap(plane, in_bytes, d_counts, cbytes) ||
+        opt_overlap(plane, in_bytes, d_thresholds, tbytes) || opt_overlap(d_out_bits, bytes, d_counts, cbytes) ||
+        opt_overlap(d_out_bits, bytes, d_thresholds, tbytes) || opt_overlap(d_counts, cbytes, d_thresholds, tbytes))
+        return CANNY_HIP_ERR_INVALID;
+    if ((rc = finish_pending(ctx))) return rc;
+    return dev_binarize(ctx, plane, plane_u8, n_frames, h, w, method, thr_or_c, kw, kh, invert, d_out_bits, d_counts,
+                        d_thresholds);
+}
+
+int canny_hip_binarize_batch(canny_hip_ctx *ctx, const unsigned char *imgs, int n_frames, int h, int w, int method,
+                             int thr_or_c, int kw, int kh, int invert, unsigned char *out_bits, long long *counts,
+                             int *thresholds)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!imgs || !out_bits || ((uintptr_t)counts & 7) || ((uintptr_t)thresholds & 3)) return CANNY_HIP_ERR_INVALID;
+    if ((rc = binarize_check(n_frames, h, w, method, thr_or_c, kw, kh, invert))) return rc;
+    const size_t n = npx(h, w, n_frames), bytes = npx(h, (w + 7) / 8, n_frames), slot = (bytes + 15) & ~(size_t)15;
+    const size_t cbytes = (size_t)n_frames * sizeof(long long), tbytes = (size_t)n_frames * sizeof(int);
+    if (ranges_overlap(imgs, n, out_bits, bytes) || opt_overlap(imgs, n, counts, cbytes) ||
+        opt_overlap(imgs, n, thresholds, tbytes) || opt_overlap(out_bits, bytes, counts, cbytes) ||
+        opt_overlap(out_bits, bytes, thresholds, tbytes) || opt_overlap(counts, cbytes, thresholds, tbytes))
+        return CANNY_HIP_ERR_INVALID;
+    if ((rc = finish_pending(ctx))) return rc;
+    if ((rc = h2d(ctx, ctx->io[0], imgs, n))) return rc;
+    // one staging block: the output maps | the counts | the thresholds
+    HIP_TRY(ctx, ctx->io[1].ensure(slot + ((cbytes + 15) & ~(size_t)15) + tbytes));
+    unsigned char *d_out = (unsigned char *)ctx->io[1].p;
+    long long *d_counts = (long long *)(d_out + slot);
+    int *d_thr = (int *)(d_out + slot + ((cbytes + 15) & ~(size_t)15));
+    if ((rc = dev_binarize(ctx, ctx->io[0].p, true, n_frames, h, w, method, thr_or_c, kw, kh, invert, d_out,
+                           counts ? d_counts : nullptr, thresholds ? d_thr : nullptr)))
+        return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(out_bits, d_out, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    if (counts) HIP_TRY(ctx, hipMemcpyAsync(counts, d_counts, cbytes, hipMemcpyDeviceToHost, ctx->stream));
+    if (thresholds) HIP_TRY(ctx, hipMemcpyAsync(thresholds, d_thr, tbytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return CANNY_HIP_OK;
+}
+
+// Every group of kProfGroups by name: what the named getters answer, for this and later features.
+int canny_hip_profile_part_get(canny_hip_ctx *ctx, const char *feature, int part, double *total_ms, long *launches)
+{
+    if (!feature) return CANNY_HIP_ERR_INVALID;
+    int base = 0;
+    for (const ProfGroup &g : kProfGroups) {
+        if (!std::strcmp(feature, g.name)) return profile_part_get(ctx, base, g.parts, part, total_ms, launches);
+        base += g.parts;
+    }
+    return CANNY_HIP_ERR_INVALID;
+}
+
+// Host-only: the launch plan of the kernel that writes the bits, and what the tests need to know about the marching tiling.
+int canny_hip_selftest_binarize_plan(int n_frames, int h, int w, int method, int kw, int kh, unsigned long long *out)
+{
+    if (!out) return CANNY_HIP_ERR_INVALID;
+    const bool adaptive = method == CANNY_HIP_BIN_ADAPTIVE_MEAN;
+    if (!adaptive) kw = kh = 3; // ignored, like the calls ignore them
+    const int rc = binarize_check(n_frames, h, w, method, 0, kw, kh, 0);
+    if (rc) return rc;
+    const int route = adaptive ? binarize_auto_route(kw, kh) : 0;
+    const LaunchPlan bytes = plan_binarize_bytes(n_frames, h, w), march = plan_binarize_march(n_frames, h, w, kh);
+    store_plan(out, route == 2 ? march : bytes);
+    out[4] = (unsigned long long)route; // the route, not aux
+    out[5] = (unsigned long long)binarize_strip_cols();
+    out[6] = (unsigned long long)binarize_segment_rows(kh);
+    out[7] = bytes.trips();
+    out[8] = march.trips();
+    out[9] = (unsigned long long)binarize_staged_cols(kw);
     return CANNY_HIP_OK;
 }
 

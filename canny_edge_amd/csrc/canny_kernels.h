@@ -872,6 +872,26 @@ hipError_t launch_morph(const void *src, bool src_plane, int n_frames, int h, in
                         int kh, int border, int iterations, int route, uint8_t *ws_a, uint8_t *ws_b, uint8_t *out,
                         unsigned long long *counts, hipStream_t stream);
 
+// ---- binarization: gray planes to packed bit maps (canny_binarize.hip) -------------------
+// plane: [n_frames][h][w] bytes (in_u8) or shorts in [0, 255]; out: every byte of [n_frames][h][ceil(w / 8)], pad bits 0.
+// counts (may be NULL, 8-byte aligned) is zeroed on the stream, then summed by the kernel that writes the bits.
+// The map of FIXED and OTSU: bit = (v > thr[f]) != invert; 256 output bytes per workgroup and trip.
+LaunchPlan plan_binarize_bytes(int n_frames, int h, int w);
+hipError_t launch_binarize_map(const void *plane, bool in_u8, int n_frames, int h, int w, const int *thr, int invert,
+                               uint8_t *out, unsigned long long *counts, hipStream_t stream);
+// One workgroup per frame: Otsu's threshold (the header's integer rule) of hist[f][kHistBins] -> thr[f].
+hipError_t launch_binarize_otsu(const uint32_t *hist, int n_frames, int *thr, hipStream_t stream);
+// ADAPTIVE_MEAN: bit = (2 S < kw kh (2 (v + c) - 1)) != invert, S the clamped kw x kh window sum.  route 1: every lane sums
+// its windows from global memory (plan_binarize_bytes); route 2: a wave marches down a strip of binarize_strip_cols()
+// useful columns, binarize_segment_rows(kh) rows a segment (plan_binarize_march); 0: binarize_auto_route(kw, kh).
+LaunchPlan plan_binarize_march(int n_frames, int h, int w, int kh);
+int binarize_strip_cols();
+int binarize_segment_rows(int kh);
+int binarize_staged_cols(int kw); // the strip and the halo a wave has room for: 64 lanes x 9 or 13 columns
+int binarize_auto_route(int kw, int kh);
+hipError_t launch_binarize_adaptive(const void *plane, bool in_u8, int n_frames, int h, int w, int c, int kw, int kh,
+                                    int invert, int route, uint8_t *out, unsigned long long *counts, hipStream_t stream);
+
 // ---- measurement aid ------------------------------------------------------------------------
 // Plain device copy of nbytes (multiple of 16; both pointers 16-byte aligned): what a 1:1 read/write stream reaches.
 hipError_t launch_probe_copy(const void *src, void *dst, size_t nbytes, hipStream_t stream, const LaunchEvents &ev = {});

@@ -69,6 +69,11 @@
 // (canny_hip_canny_morph, the neutral border): op erode, dilate, open, close, gradient, tophat or blackhat; kw and kh (default
 // kw) odd, 1..31; shape rect (default), cross or ellipse; iterations 1..16 (default 1).  The map (0 / 255) goes to
 // canny_morph.pgm in the -o directory.  A malformed -z is a usage error (exit 2).  Without -z nothing changes.
+// Added: -a method[,thr_or_c[,kw[,kh[,invert]]]] binarizes the input frame itself on the GPU (canny_hip_binarize_batch): method
+// fixed (thr_or_c the threshold, -1..255, default 127), otsu (the frame's own threshold, printed as "otsu threshold t"; the
+// other fields are ignored) or mean (the adaptive mean: thr_or_c the offset c, -255..255, default 7; kw and kh (default kw) odd,
+// 3..255, default 31); invert 0 (default) or 1.  The map (0 / 255) goes to canny_binary.pgm in the -o directory.  A malformed
+// -a is a usage error (exit 2).  Without -a nothing changes.
 // Added: -e computes the sub-pixel edgel of every pixel of the frame's edge map on the GPU (canny_hip_canny_edgels) and
 // writes one "x y gx gy mag dir refined" row per edge pixel, in raster order, to canny_edgels.txt in the -o directory
 // (stdout without -o): x and y in pixels to three decimals, mag in grey levels, dir 0..3 (step (1,0), (1,1), (0,1), (1,-1)),
@@ -687,6 +692,34 @@ static int run_morph(const vector<unsigned char> &frame, int height, int width, 
     return 0;
 }
 
+// -a: the frame binarized -> canny_binary.pgm.  a: method, thr_or_c, kw, kh, invert
+static int run_binarize(const vector<unsigned char> &frame, int height, int width, const int *a, const string &outdir)
+{
+    const size_t rb = ((size_t)width + 7) / 8;
+    vector<unsigned char> bits(rb * height);
+    int thr = 0;
+    canny_hip_ctx *ctx = nullptr;
+    int st = canny_hip_ctx_create(&ctx, 0);
+    if (!st) st = canny_hip_binarize_batch(ctx, frame.data(), 1, height, width, a[0], a[1], a[2], a[3], a[4], bits.data(), nullptr, &thr);
+    if (st) {
+        fprintf(stderr, "ERROR: -a: %s\n", st == CANNY_HIP_ERR_RUNTIME && ctx ? canny_hip_last_error(ctx) : canny_hip_status_string(st));
+        if (ctx) canny_hip_ctx_destroy(ctx);
+        return 1;
+    }
+    canny_hip_ctx_destroy(ctx);
+    if (a[0] == CANNY_HIP_BIN_OTSU) printf("otsu threshold %d\n", thr);
+    vector<unsigned char> out((size_t)height * width);
+    for (int y = 0; y < height; y++)
+        for (int x = 0; x < width; x++)
+            out[(size_t)y * width + x] = (bits[(size_t)y * rb + (x >> 3)] >> (7 - (x & 7))) & 1 ? 255 : 0;
+    const string path = (outdir.empty() ? string(".") : outdir) + "/canny_binary" + (png_output ? ".png" : ".pgm");
+    if (!write_frame(path, out.data(), height, width)) {
+        fprintf(stderr, "ERROR: cannot write %s\n", path.c_str());
+        return 1;
+    }
+    return 0;
+}
+
 // -r: the circles of the frame's edge map, "frame x y radius votes support" per circle; with -k (fit != nullptr: band,
 // trim_q8, options) also the circle fit of every circle, "frame cx cy r n rms maxd sectors trim_failed degenerate" per circle
 static int run_circles(const vector<unsigned char> &frame, int height, int width, float sigma, int minVal, int maxVal,
@@ -906,6 +939,8 @@ int main(int argc, char *argv[])
     int desc_options = -1;                 // -j: -1 absent, 0 upright, CANNY_HIP_DESC_STEERED
     bool want_morph = false;
     int morph_args[5] = {0, 3, 3, 0, 1};   // -z: op, kw, kh, shape, iterations
+    bool want_binarize = false;
+    int bin_args[5] = {0, 127, 31, 31, 0}; // -a: method, thr_or_c, kw, kh, invert
     int width = WIDTH, height = HEIGHT;
     vector<string> values;
 
@@ -1117,6 +1152,47 @@ int main(int argc, char *argv[])
                 exit(2);
             }
             want_morph = true;
+        } else if (arg == "-a") {
+            // method[,thr_or_c[,kw[,kh[,invert]]]]: a word and whole integers, nothing empty, nothing behind the last one
+            static const char *const methods[] = {"fixed", "otsu", "mean"};
+            vector<string> parts(1);
+            for (const char *p = i + 1 < argc ? argv[++i] : ""; *p; p++) {
+                if (*p == ',')
+                    parts.emplace_back();
+                else
+                    parts.back() += *p;
+            }
+            auto number = [](const string &w, int &v) { // -999..999 from an optional sign and digits alone
+                const size_t d = !w.empty() && w[0] == '-' ? 1 : 0;
+                if (w.size() == d || w.size() > d + 3) return false;
+                for (size_t k = d; k < w.size(); k++)
+                    if (!isdigit((unsigned char)w[k])) return false;
+                v = atoi(w.c_str());
+                return true;
+            };
+            bool clean = parts.size() >= 1 && parts.size() <= 5;
+            if (clean) {
+                bin_args[0] = -1;
+                for (int k = 0; k < 3; k++)
+                    if (parts[0] == methods[k]) bin_args[0] = k;
+                bin_args[1] = bin_args[0] == CANNY_HIP_BIN_FIXED ? 127 : (bin_args[0] == CANNY_HIP_BIN_OTSU ? 0 : 7);
+                clean = bin_args[0] >= 0;
+                for (size_t k = 1; k < parts.size(); k++) clean = clean && number(parts[k], bin_args[k]);
+                if (parts.size() < 4) bin_args[3] = bin_args[2];
+                if (clean && bin_args[0] == CANNY_HIP_BIN_FIXED) clean = bin_args[1] >= -1 && bin_args[1] <= 255;
+                if (clean && bin_args[0] == CANNY_HIP_BIN_ADAPTIVE_MEAN) {
+                    clean = bin_args[1] >= -255 && bin_args[1] <= 255;
+                    for (int k = 2; k <= 3; k++)
+                        clean = clean && bin_args[k] >= 3 && bin_args[k] <= CANNY_HIP_BIN_MAX_EXTENT && (bin_args[k] & 1);
+                }
+                clean = clean && (bin_args[4] == 0 || bin_args[4] == 1);
+            }
+            if (!clean) {
+                fprintf(stderr, "ERROR: -a expects method[,thr_or_c[,kw[,kh[,invert]]]]: method fixed (thr -1..255), otsu or mean (c "
+                                "-255..255, kw and kh odd in 3..255), invert 0 or 1\n");
+                exit(2);
+            }
+            want_binarize = true;
         } else if (arg == "-w" && i + 1 < argc) {
             char tail = 0; // a whole integer only
             if (sscanf(argv[++i], "%d%c", &curve_min_length, &tail) != 1) {
@@ -1203,6 +1279,8 @@ int main(int argc, char *argv[])
         fprintf(stderr, "       one \"x y k border\" and 64 hex digits each -> canny_descriptors.txt in the -o dir\n");
         fprintf(stderr, "   -z op,kw[,kh[,shape[,iterations]]]: binary morphology of the edge map (erode, dilate, open, close, gradient,\n");
         fprintf(stderr, "       tophat, blackhat; kw, kh odd 1..31; rect, cross, ellipse; 1..16 iterations) -> canny_morph.pgm in the -o dir\n");
+        fprintf(stderr, "   -a method[,thr_or_c[,kw[,kh[,invert]]]]: the input frame binarized (fixed: thr -1..255; otsu: the frame's own\n");
+        fprintf(stderr, "       threshold, printed; mean: adaptive, offset c, window kw x kh odd 3..255; invert 0 or 1) -> canny_binary.pgm in the -o dir\n");
         fprintf(stderr, "   -d: distance of every pixel to the nearest edge pixel, min(255, floor) -> canny_dist.pgm in the -o dir\n");
         fprintf(stderr, "   -e: sub-pixel edgel of every edge pixel, one \"x y gx gy mag dir refined\" line each (x, y in pixels to three\n");
         fprintf(stderr, "       decimals, mag in grey levels, dir 0..3) -> canny_edgels.txt in the -o dir\n");
@@ -1286,6 +1364,10 @@ int main(int argc, char *argv[])
     }
     if (want_morph) {
         const int rc = run_morph(frame, height, width, sigma, minVal, maxVal, morph_args, outdir);
+        if (rc) return rc;
+    }
+    if (want_binarize) {
+        const int rc = run_binarize(frame, height, width, bin_args, outdir);
         if (rc) return rc;
     }
     if (want_dist) {

@@ -52,7 +52,8 @@
 extern "C" {
 #endif
 
-#define CANNY_HIP_VERSION 2400       /* 0.24.0: + binary morphology on packed bit maps */
+#define CANNY_HIP_VERSION 2500       /* 0.25.0: + binarization: gray planes to packed bit maps (fixed, Otsu, adaptive) */
+/* 0.24.0: + binary morphology on packed bit maps */
 /* 0.23.0: + temporal fusion of aligned frames and change masks (0.22.0: + frame alignment) */
 /* 0.21.0: + frame-to-frame motion from the corner matches (RANSAC) */
 /* 0.20.0: + corner descriptors and Hamming matching between frames */
@@ -2281,6 +2282,80 @@ int canny_hip_morph_bits(const unsigned char *bits, int n_frames, int h, int w, 
 /* Host-only: rows[kh] of a canny_hip_morph_shape; kw, kh odd, 1..31. */
 int canny_hip_morph_element(int shape, int kw, int kh, unsigned *rows);
 
+/* ---- binarization: gray planes to packed bit maps ------------------------------------------------------------------------
+ * The operator in front of every stage that takes a packed bit map (components, contours, polygons, shapes, curves, the
+ * distance transform, chamfer matching, point lists, binary morphology): what cv::threshold(THRESH_BINARY[_INV]),
+ * cv::threshold(THRESH_OTSU) and cv::adaptiveThreshold(ADAPTIVE_THRESH_MEAN_C) answer, on u8 planes as they lie on the
+ * device (frames, warped frames, fused backgrounds, the smoothed plane dev_canny left in the context), on the context's
+ * stream, without a download.  All integers: the same bytes on every run and every machine.  tests/binarize_rule.py restates
+ * the rule in numpy and Python ints, csrc/canny_binarize_host.cpp in plain C++.
+ * THE RULE:
+ *   Input [n_frames][h][w] u8.  Output [n_frames][h][(w + 7) / 8] bytes, rows MSB-first, the layout of
+ *     canny_hip_dev_canny_bits.  THE PAD BITS ARE WRITTEN 0, and every output byte is written.
+ *   For a pixel of value v the bit is cond(v) XOR invert, invert in {0, 1}: 0 is THRESH_BINARY, 1 THRESH_BINARY_INV.  The XOR
+ *     applies inside the frame only.
+ *   CANNY_HIP_BIN_FIXED = 0: cond = v > thr, thr = thr_or_c in -1..255, the same for all frames; thr = -1 sets every pixel.
+ *   CANNY_HIP_BIN_OTSU = 1: cond = v > t[f], every frame with its own t[f] from its 256-bin histogram hist (thr_or_c is
+ *     ignored).  With N = sum hist, S = sum i hist[i] and, for t = 0..255,
+ *       w0 = sum_{i <= t} hist[i], s0 = sum_{i <= t} i hist[i], w1 = N - w0, s1 = S - s0, d = w1 s0 - s1 w0,
+ *       score(t) = 0 if w0 w1 == 0, else floor(d^2 / (w0 w1)),
+ *     t[f] is the SMALLEST t with the LARGEST score; a flat frame gets 0.  This is Otsu's between-class variance times the
+ *     frame's constant N^2, floored.  Domain: frames of at most 2^26 pixels (|d| < 2^58, d^2 < 2^116, w0 w1 <= 2^50: a 128-bit
+ *     product and a 128-by-64 division); above: CANNY_HIP_ERR_UNSUPPORTED.
+ *   CANNY_HIP_BIN_ADAPTIVE_MEAN = 2: cv::adaptiveThreshold(ADAPTIVE_THRESH_MEAN_C) with the build-dependent float mean
+ *     replaced by integers.  Window kw x kh, both odd, 3..255 (CANNY_HIP_BIN_MAX_EXTENT), A = kw kh; offset c = thr_or_c in
+ *     -255..255.  S = the sum of the window centred on the pixel, coordinates clamped to the frame (BORDER_REPLICATE,
+ *     OpenCV's border there); S <= 255 * 255 * 255 < 2^24.  m = (2 S + A) / (2 A), the mean rounded half up, and
+ *     cond = v > m - c.  EQUIVALENTLY, WITHOUT A DIVISION: cond = 2 S < A (2 (v + c) - 1) -- among integers v > m - c is
+ *     m <= v + c - 1, floor(x / k) <= n is x < k (n + 1) for k > 0, so it is 2 S + A < 2 A (v + c); the kernels compute this
+ *     form, the host the other.  kw and kh are ignored by the other methods.
+ *   counts may be NULL; otherwise n_frames long long, 8-byte aligned: the set bits of each output frame, an integer sum (no
+ *     order to depend on), zeroed on the stream inside the call, fully written by it and not touched by a refused one.
+ *   thresholds may be NULL; otherwise n_frames ints: OTSU t[f], FIXED thr, ADAPTIVE_MEAN c.
+ *   Limits: h, w in 1..32768, a plane < 2^31 pixels, at most 65535 frames (OTSU: a frame <= 2^26 pixels); above:
+ *     CANNY_HIP_ERR_UNSUPPORTED.  Bad enum values, bad ranges, NULL mandatory pointers, a misaligned counts buffer, buffers
+ *     that overlap: CANNY_HIP_ERR_INVALID.  Both before anything is queued; nothing is written.
+ *   Kernels (csrc/canny_binarize.hip).  FIXED and OTSU: one map kernel, the frame's threshold from a device array (FIXED
+ *     fills it on the stream), a lane per output byte, 256 bytes of one frame per workgroup and trip of a grid capped at 4096,
+ *     the counts by wave reduction and one atomic add per workgroup and frame.  OTSU: the u8 histogram kernel of the automatic
+ *     hysteresis thresholds, then one workgroup per frame (two block prefix sums, a candidate t per lane with a restoring
+ *     division, arg-max with ties to the smaller t).  ADAPTIVE_MEAN, the context option "binarize_route": 0 automatic,
+ *     1 straightforward (every lane sums its windows from global memory: the cross-check), 2 marching (a wave per strip of 512
+ *     useful columns and segment of rows: vertical running sums of the staged columns in registers, the horizontal window
+ *     from a prefix sum through LDS, the bits by ballot).  Both routes give the same bytes.
+ * Not covered -- follow-ups: Gaussian-weighted adaptive thresholds; Sauvola and Niblack; a valid-bits input; s16 planes;
+ * binarization through the batch pipeline or the multi-GPU sharder. */
+#define CANNY_HIP_BIN_MAX_EXTENT 255
+enum canny_hip_bin_method {
+    CANNY_HIP_BIN_FIXED = 0,
+    CANNY_HIP_BIN_OTSU = 1,
+    CANNY_HIP_BIN_ADAPTIVE_MEAN = 2
+};
+enum canny_hip_bin_part {
+    CANNY_HIP_BIN_PART_HISTOGRAM = 0, /* OTSU: the zeroing of the histograms and the histogram kernel */
+    CANNY_HIP_BIN_PART_SELECT = 1,    /* OTSU: the threshold of every frame */
+    CANNY_HIP_BIN_PART_MAP = 2,       /* every method: the kernel that writes the bits, with the zeroing of the counts */
+    CANNY_HIP_BIN_PARTS = 3
+};
+/* d_plane: n_frames * h * w bytes, any byte address, or NULL: the smoothed plane that the preceding dev_canny of the same
+ * n_frames, h, w left in the context (any canny_hip_dev_canny* call; another geometry, or none yet: CANNY_HIP_ERR_INVALID;
+ * the plane is only read).  d_out_bits: n_frames * h * ((w + 7) / 8) bytes, any byte address; d_counts: n_frames long long or
+ * NULL; d_thresholds: n_frames ints or NULL.  Asynchronous, on the context's stream. */
+int canny_hip_dev_binarize(canny_hip_ctx *ctx, const unsigned char *d_plane, int n_frames, int h, int w, int method,
+                           int thr_or_c, int kw, int kh, int invert, unsigned char *d_out_bits, long long *d_counts,
+                           int *d_thresholds);
+/* Host buffers, synchronous: upload, the operator; only out_bits and, where the pointers are not NULL, counts and thresholds
+ * come down. */
+int canny_hip_binarize_batch(canny_hip_ctx *ctx, const unsigned char *imgs, int n_frames, int h, int w, int method,
+                             int thr_or_c, int kw, int kh, int invert, unsigned char *out_bits, long long *counts,
+                             int *thresholds);
+/* Host-only, needs no device: the same rule on host buffers. */
+int canny_hip_binarize(const unsigned char *imgs, int n_frames, int h, int w, int method, int thr_or_c, int kw, int kh,
+                       int invert, unsigned char *out_bits, long long *counts, int *thresholds);
+/* Host-only: Otsu's threshold of the rule for a histogram of the caller's: 256 bins, at most 2^26 samples in all
+ * (CANNY_HIP_ERR_UNSUPPORTED above). */
+int canny_hip_otsu_from_histogram(const unsigned long long *hist256, int *t);
+
 /* ---- per-stage HIP-event timing (events are recorded on the launch stream) ----------------- */
 int canny_hip_profile_enable(canny_hip_ctx *ctx, int on);
 int canny_hip_profile_reset(canny_hip_ctx *ctx);
@@ -2325,6 +2400,12 @@ int canny_hip_warp_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, l
 int canny_hip_fuse_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches);
 /* ... and for the one part of the binary morphology (CANNY_HIP_MORPH_PART_*; bit 30 of "profile_stage_mask" like the others). */
 int canny_hip_morph_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches);
+/* Every group of parts by name, for this and later features: feature is "stages" (the canny stages of
+ * canny_hip_profile_get), "hough", "components", "edt", "hough_segments", "contours", "hough_circles", "polygons", "edgels",
+ * "line_fits", "circle_fits", "chamfer", "shapes", "curves", "corners", "descriptors", "motion", "warp", "fuse", "morph" or
+ * "binarize" (CANNY_HIP_BIN_PART_*; bit 30 of "profile_stage_mask" like the others); the answer is the named getter's.  An
+ * unknown name, a part the group does not have or a NULL: CANNY_HIP_ERR_INVALID, nothing is written. */
+int canny_hip_profile_part_get(canny_hip_ctx *ctx, const char *feature, int part, double *total_ms, long *launches);
 
 /* ---- self-test hooks used by the GPU test-suite -------------------------------------------- */
 /* Runs the DEVICE magnitude / angle-bin functions over every (gx,gy) in [-lim,lim]^2 and writes
@@ -2515,6 +2596,15 @@ int canny_hip_selftest_fuse_plan(int which, int n_frames, int h, int w, int grou
  * fifth word is the route that automatic takes for a full rectangle of kw x kh (1 general, 2 separable).  Arguments within
  * the limits of the calls. */
 int canny_hip_selftest_morph_plan(int n_frames, int h, int w, int kw, int kh, unsigned long long *out);
+/* Host-only, TEN words for the binarization (no kind above): the same five outputs for the launch that writes the bits under
+ * the route automatic takes -- FIXED, OTSU and route 1: items = n_frames * ceil(h * ceil(w / 8) / 256) chunks of 256 output
+ * bytes, one per workgroup of 256 and trip; route 2: items = n_frames * strips * segments, four (one a wave) per workgroup and
+ * trip; at most 4096 workgroups -- with the fifth word the route automatic takes for ADAPTIVE_MEAN (1 straightforward,
+ * 2 marching; 0 for the other methods).  out[5]: the useful columns of a marching strip; out[6]: the rows of a segment for
+ * this kh; out[7]: the trips of the launch of route 1 (and of FIXED and OTSU); out[8]: the trips of route 2; out[9]: the
+ * staged columns of a strip for this kw (out[5] + the halo it has room for).  kw, kh are checked for ADAPTIVE_MEAN only;
+ * arguments within the limits of the calls. */
+int canny_hip_selftest_binarize_plan(int n_frames, int h, int w, int method, int kw, int kh, unsigned long long *out);
 /* Runs the fuse kernels' own device helper for the rounded mean over every pair c = 1..255, s = 0..255 c, and writes the
  * bytes to host memory as a table [255][CANNY_HIP_FUSE_MEAN_ROW]: out[(c - 1) * 65026 + s]; unused cells are 0. */
 int canny_hip_selftest_fuse_mean(canny_hip_ctx *ctx, unsigned char *out);
