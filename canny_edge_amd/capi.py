@@ -149,6 +149,8 @@ EXPORTS = (
     "canny_hip_morph_element", "canny_hip_selftest_morph_plan", "canny_hip_morph_profile_get",
     "canny_hip_dev_binarize", "canny_hip_binarize_batch", "canny_hip_binarize", "canny_hip_otsu_from_histogram",
     "canny_hip_selftest_binarize_plan", "canny_hip_profile_part_get",
+    "canny_hip_dev_thin_bits", "canny_hip_dev_canny_thin", "canny_hip_thin_batch", "canny_hip_thin_bits",
+    "canny_hip_selftest_thin_plan",
 )
 
 _lib: Optional[C.CDLL] = None
@@ -428,6 +430,11 @@ def load() -> C.CDLL:
         "canny_hip_otsu_from_histogram": ([p, C.POINTER(C.c_int)], i),
         "canny_hip_selftest_binarize_plan": ([i, i, i, i, i, i, p], i),
         "canny_hip_profile_part_get": ([p, C.c_char_p, i, C.POINTER(C.c_double), C.POINTER(C.c_long)], i),
+        "canny_hip_dev_thin_bits": ([p, p, i, i, i, i, i, p, p], i),
+        "canny_hip_dev_canny_thin": ([p, i, i, i, i, i, p, p], i),
+        "canny_hip_thin_batch": ([p, p, i, i, i, i, i, p, p], i),
+        "canny_hip_thin_bits": ([p, i, i, i, i, i, p, p], i),
+        "canny_hip_selftest_thin_plan": ([i, i, i, i, p], i),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -1329,6 +1336,38 @@ def binarize_plan(n_frames: int, h: int, w: int, method: int = BIN_ADAPTIVE_MEAN
     the staged columns of a strip for kw)."""
     plan, *tail = _plan("binarize_plan", int(n_frames), int(h), int(w), int(method), int(kw), int(kh), n=10)
     return plan, BinarizeTiling(*tail)
+
+
+# ---- thinning of packed bit maps to one-pixel skeletons (DESIGN.md section 37) --------------------------------------------
+THIN_ZHANGSUEN, THIN_GUOHALL = 0, 1
+THIN_METHODS = ("zhangsuen", "guohall")
+THIN_ROUTE_AUTO, THIN_ROUTE_STEPWISE, THIN_ROUTE_FUSED = 0, 1, 2
+THIN_MAX_ITERATIONS, THIN_MAX_FUSE, THIN_INFO = 16384, 8, 4
+THIN_PARTS = ("passes", "info")
+
+
+def _thin_maps(bits, w: int):
+    a = np.ascontiguousarray(bits, dtype=np.uint8)
+    if a.ndim != 3 or a.shape[2] != (int(w) + 7) // 8:
+        raise ValueError("expected bit maps uint8 [n_frames, H, ceil(w / 8)]")
+    return a
+
+
+def thin_bits(bits, w: int, method: int = THIN_GUOHALL, max_iterations: int = 0):
+    """Host-only, needs no GPU: the thinning rule on bit maps uint8 [n_frames, H, ceil(w / 8)] (rows MSB-first; pad bits
+    ignored) -> (bit maps of the same shape with pad bits 0, info int64 [n_frames, 4]: set bits, iterations, pixels deleted,
+    converged)."""
+    a = _thin_maps(bits, w)
+    n, h, _ = a.shape
+    out, info = np.zeros_like(a), np.zeros((n, THIN_INFO), np.int64)
+    _ok(load().canny_hip_thin_bits(_hp(a), n, h, int(w), int(method), int(max_iterations), _hp(out), _hp(info)), "thin_bits")
+    return out, info
+
+
+def thin_plan(n_frames: int, h: int, w: int, fuse: int = 0):
+    """Host-only: the LaunchPlan of every launch of a thinning call (one tile of 8 words x 64 rows per workgroup and trip);
+    aux = the full iterations a launch runs: fuse, or for 0 what automatic takes (0: automatic is the stepwise route)."""
+    return _plan("thin_plan", int(n_frames), int(h), int(w), int(fuse))
 
 
 # ---- chamfer template matching (DESIGN.md section 26) --------------------------------------------------------------------
@@ -2876,9 +2915,35 @@ class Context:
                                                      _hp(thr)), "binarize_batch")
         return out, counts, thr
 
+    # ---- thinning of packed bit maps -------------------------------------------------------------
+    def dev_thin_bits(self, d_bits: int, n_frames: int, h: int, w: int, method: int, d_out_bits: int, d_info: int = 0,
+                      max_iterations: int = 0):
+        """Thins device bit maps [n_frames][h][ceil(w / 8)] into d_out_bits and, if given, 4 int64 a frame at d_info (set bits,
+        iterations, pixels deleted, converged).  max_iterations >= 1: asynchronous; 0 (to the fixed point): the stream is
+        synchronised before the call returns."""
+        v = C.c_void_p
+        self._check(self._L.canny_hip_dev_thin_bits(self._h, v(d_bits or None), n_frames, h, w, int(method), int(max_iterations),
+                                                    v(d_out_bits or None), v(d_info or None)), "dev_thin_bits")
+
+    def dev_canny_thin(self, n_frames: int, h: int, w: int, method: int, d_out_bits: int, d_info: int = 0,
+                       max_iterations: int = 0):
+        """The same on the strong bit-plane the preceding dev_canny of the same geometry left in the context."""
+        v = C.c_void_p
+        self._check(self._L.canny_hip_dev_canny_thin(self._h, n_frames, h, w, int(method), int(max_iterations),
+                                                     v(d_out_bits or None), v(d_info or None)), "dev_canny_thin")
+
+    def thin_batch(self, bits, w: int, method: int = THIN_GUOHALL, max_iterations: int = 0):
+        """Upload and the operator on the GPU: bit maps uint8 [N, H, ceil(w / 8)] -> (bit maps, info int64 [N, 4])."""
+        a = _thin_maps(bits, w)
+        n, h, _ = a.shape
+        out, info = np.zeros_like(a), np.zeros((n, THIN_INFO), np.int64)
+        self._check(self._L.canny_hip_thin_batch(self._h, _hp(a), n, h, int(w), int(method), int(max_iterations), _hp(out),
+                                                 _hp(info)), "thin_batch")
+        return out, info
+
     def profile_part(self, feature: str, part: int) -> Tuple[float, int]:
         """(total ms, launch groups) of part `part` of the named group of the profile table ("stages", "hough", ..., "morph",
-        "binarize": BIN_PARTS): what the group's own getter answers."""
+        "binarize": BIN_PARTS, "thin": THIN_PARTS): what the group's own getter answers."""
         ms, n = C.c_double(0), C.c_long(0)
         self._check(self._L.canny_hip_profile_part_get(self._h, str(feature).encode(), int(part), C.byref(ms), C.byref(n)),
                     "profile_part_get")

@@ -351,6 +351,7 @@ constexpr ProfGroup kProfGroups[] = {
     {"fuse", CANNY_HIP_FUSE_PARTS},
     {"morph", CANNY_HIP_MORPH_PARTS},
     {"binarize", CANNY_HIP_BIN_PARTS},
+    {"thin", CANNY_HIP_THIN_PARTS},
 };
 
 // The first slot of the named group; with no name, the number of slots.  A name the table does not hold fails to compile.
@@ -472,6 +473,9 @@ struct canny_hip_ctx {
     // binarization: the histograms of the frames (OTSU) | the threshold of every frame
     DevBuf binarize_ws;
     int binarize_route = 0; // 0 auto, 1 straightforward, 2 marching (ADAPTIVE_MEAN)
+    // thinning: two maps | the deletions per frame and iteration | the frames' states (thin_workspace_bytes)
+    DevBuf thin_ws;
+    int thin_route = 0, thin_fuse = 0; // 0 auto, 1 stepwise, 2 fused; 0 auto, 1..8 full iterations a fused launch
     std::vector<int> motion_pairs; // the validated pairs of the last motion call: what its upload reads
     DevBuf plane_s, plane_c, stamps, flags; // hysteresis bit-planes / scheduling words
     DevBuf io[4];     // staging for the host-pointer stage functions
@@ -506,7 +510,7 @@ struct canny_hip_ctx {
                          kProfCurves = prof_base("curves"), kProfCorners = prof_base("corners"),
                          kProfDescriptors = prof_base("descriptors"), kProfMotion = prof_base("motion"),
                          kProfWarp = prof_base("warp"), kProfFuse = prof_base("fuse"), kProfMorph = prof_base("morph"),
-                         kProfBinarize = prof_base("binarize");
+                         kProfBinarize = prof_base("binarize"), kProfThin = prof_base("thin");
     static constexpr int kProfSlots = prof_base(nullptr);
     // "profile_stage_mask" is a non-negative int option: bit 30 is the last it can carry
     static constexpr int kProfLastBit = 30;
@@ -2060,6 +2064,7 @@ void collect_workspaces(const canny_hip_ctx *c, const std::string &prefix, std::
     add("motion_ws", c->motion_ws, I);     // the pairs address frames, m bounds the lists, the slots address the flags
     add("morph_ws", c->morph_ws, D);
     add("binarize_ws", c->binarize_ws, D);
+    add("thin_ws", c->thin_ws, D);
     add("plane_s", c->plane_s, D);
     add("plane_c", c->plane_c, D);
     add("stamps", c->stamps, I);           // tile queues and their counters
@@ -2179,6 +2184,7 @@ void canny_hip_ctx_destroy(canny_hip_ctx *ctx)
     ctx->motion_ws.release();
     ctx->morph_ws.release();
     ctx->binarize_ws.release();
+    ctx->thin_ws.release();
     ctx->cc_parent.release();
     ctx->cc_ws.release();
     ctx->ct_ws.release();
@@ -2238,6 +2244,8 @@ int canny_hip_ctx_get_option(const canny_hip_ctx *ctx, const char *name, int *va
     else if (!std::strcmp(name, "fuse_route")) *value = ctx->fuse_route;
     else if (!std::strcmp(name, "morph_route")) *value = ctx->morph_route;
     else if (!std::strcmp(name, "binarize_route")) *value = ctx->binarize_route;
+    else if (!std::strcmp(name, "thin_route")) *value = ctx->thin_route;
+    else if (!std::strcmp(name, "thin_fuse")) *value = ctx->thin_fuse;
     else if (!std::strcmp(name, "tune_chamfer_chunk_mb")) *value = ctx->chamfer_chunk_mb;
     else if (!std::strcmp(name, "batch_expand_threads")) *value = ctx->expand_pool ? ctx->expand_pool->size() : 0; // read-only
     else return CANNY_HIP_ERR_INVALID;
@@ -2268,6 +2276,8 @@ int canny_hip_ctx_set_option(canny_hip_ctx *ctx, const char *name, int value)
     else if (!std::strcmp(name, "fuse_route") && value <= 2) ctx->fuse_route = value;
     else if (!std::strcmp(name, "morph_route") && value <= 2) ctx->morph_route = value;
     else if (!std::strcmp(name, "binarize_route") && value <= 2) ctx->binarize_route = value;
+    else if (!std::strcmp(name, "thin_route") && value <= 2) ctx->thin_route = value;
+    else if (!std::strcmp(name, "thin_fuse") && value <= 8) ctx->thin_fuse = value;
     else if (!std::strcmp(name, "tune_chamfer_chunk_mb") && value <= 4096) ctx->chamfer_chunk_mb = value;
     else if (!std::strcmp(name, "tune_hough_lds_kb") && value <= kHoughLdsMax / 1024) ctx->hough_lds_kb = value;
     else if (!std::strcmp(name, "tune_batch_expand_threads") && value <= 64) {
@@ -6908,6 +6918,110 @@ int canny_hip_selftest_binarize_plan(int n_frames, int h, int w, int method, int
     out[7] = bytes.trips();
     out[8] = march.trips();
     out[9] = (unsigned long long)binarize_staged_cols(kw);
+    return CANNY_HIP_OK;
+}
+
+// ---- thinning of packed bit maps (canny_thin.hip) ---------------------------------------------------
+// canny_hip_thin_bits, the rule in plain C++, lives in canny_thin_host.cpp.
+
+namespace {
+// every check of the thinning but the pointers and the overlaps
+int thin_check(int n_frames, int h, int w, int method, int max_iterations)
+{
+    if (n_frames < 1 || h < 1 || w < 1 || method < CANNY_HIP_THIN_ZHANGSUEN || method > CANNY_HIP_THIN_GUOHALL ||
+        max_iterations < 0 || max_iterations > CANNY_HIP_THIN_MAX_ITERATIONS)
+        return CANNY_HIP_ERR_INVALID;
+    return fuse_stack_check(n_frames, h, w);
+}
+
+// The operator on the context's stream; src: a packed map or -- strong -- the context's strong bit-plane.  Everything has been
+// checked.  max_iterations >= 1: queued; 0: the stream is idle when this returns.
+int dev_thin(canny_hip_ctx *ctx, const void *src, bool strong, int n_frames, int h, int w, int method, int max_iterations,
+             unsigned char *d_out, long long *d_info)
+{
+    HIP_TRY(ctx, ctx->thin_ws.ensure(thin_workspace_bytes(n_frames, h, w)));
+    {
+        StageTimer tm(ctx, canny_hip_ctx::kProfThin + CANNY_HIP_THIN_PART_INFO);
+        HIP_TRY(ctx, launch_thin_zero(ctx->thin_ws.p, n_frames, h, w, d_info, ctx->stream));
+    }
+    {
+        StageTimer tm(ctx, canny_hip_ctx::kProfThin + CANNY_HIP_THIN_PART_PASSES);
+        HIP_TRY(ctx, launch_thin_passes(src, strong, n_frames, h, w, method, max_iterations, ctx->thin_route, ctx->thin_fuse,
+                                        ctx->thin_ws.p, d_out, ctx->stream));
+    }
+    if (d_info) {
+        StageTimer tm(ctx, canny_hip_ctx::kProfThin + CANNY_HIP_THIN_PART_INFO);
+        HIP_TRY(ctx, launch_thin_info(ctx->thin_ws.p, n_frames, h, w, max_iterations, d_info, ctx->stream));
+    }
+    if (!max_iterations) HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); // as documented: also behind the last launches
+    return CANNY_HIP_OK;
+}
+} // namespace
+
+int canny_hip_dev_thin_bits(canny_hip_ctx *ctx, const unsigned char *d_bits, int n_frames, int h, int w, int method,
+                            int max_iterations, unsigned char *d_out_bits, long long *d_info)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!d_bits || !d_out_bits || ((uintptr_t)d_info & 7)) return CANNY_HIP_ERR_INVALID;
+    if ((rc = thin_check(n_frames, h, w, method, max_iterations))) return rc;
+    const size_t bytes = npx(h, (w + 7) / 8, n_frames), ibytes = (size_t)n_frames * CANNY_HIP_THIN_INFO * sizeof(long long);
+    if (ranges_overlap(d_bits, bytes, d_out_bits, bytes) || opt_overlap(d_bits, bytes, d_info, ibytes) ||
+        opt_overlap(d_out_bits, bytes, d_info, ibytes))
+        return CANNY_HIP_ERR_INVALID;
+    if ((rc = finish_pending(ctx))) return rc;
+    return dev_thin(ctx, d_bits, false, n_frames, h, w, method, max_iterations, d_out_bits, d_info);
+}
+
+int canny_hip_dev_canny_thin(canny_hip_ctx *ctx, int n_frames, int h, int w, int method, int max_iterations,
+                             unsigned char *d_out_bits, long long *d_info)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!d_out_bits || ((uintptr_t)d_info & 7)) return CANNY_HIP_ERR_INVALID;
+    if ((rc = thin_check(n_frames, h, w, method, max_iterations))) return rc;
+    // the plane the last canny call left: only for the batch it belongs to
+    if (!last_canny_was(ctx, n_frames, h, w) || !ctx->plane_s.p) return CANNY_HIP_ERR_INVALID;
+    if (opt_overlap(d_out_bits, npx(h, (w + 7) / 8, n_frames), d_info, (size_t)n_frames * CANNY_HIP_THIN_INFO * sizeof(long long)))
+        return CANNY_HIP_ERR_INVALID;
+    if ((rc = finish_pending(ctx))) return rc;
+    return dev_thin(ctx, ctx->plane_s.p, true, n_frames, h, w, method, max_iterations, d_out_bits, d_info);
+}
+
+int canny_hip_thin_batch(canny_hip_ctx *ctx, const unsigned char *bits, int n_frames, int h, int w, int method,
+                         int max_iterations, unsigned char *out_bits, long long *info)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!bits || !out_bits || ((uintptr_t)info & 7)) return CANNY_HIP_ERR_INVALID;
+    if ((rc = thin_check(n_frames, h, w, method, max_iterations))) return rc;
+    const size_t bytes = npx(h, (w + 7) / 8, n_frames), slot = (bytes + 15) & ~(size_t)15;
+    const size_t ibytes = (size_t)n_frames * CANNY_HIP_THIN_INFO * sizeof(long long);
+    if (ranges_overlap(bits, bytes, out_bits, bytes) || opt_overlap(bits, bytes, info, ibytes) ||
+        opt_overlap(out_bits, bytes, info, ibytes))
+        return CANNY_HIP_ERR_INVALID;
+    if ((rc = finish_pending(ctx))) return rc;
+    if ((rc = h2d(ctx, ctx->io[0], bits, bytes))) return rc;
+    // one staging block: the output maps | the info
+    HIP_TRY(ctx, ctx->io[1].ensure(slot + ibytes));
+    unsigned char *d_out = (unsigned char *)ctx->io[1].p;
+    long long *d_info = (long long *)(d_out + slot);
+    if ((rc = dev_thin(ctx, ctx->io[0].p, false, n_frames, h, w, method, max_iterations, d_out, info ? d_info : nullptr)))
+        return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(out_bits, d_out, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    if (info) HIP_TRY(ctx, hipMemcpyAsync(info, d_info, ibytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return CANNY_HIP_OK;
+}
+
+// Host-only: the launch plan of every launch of a call and the full iterations a launch runs.
+int canny_hip_selftest_thin_plan(int n_frames, int h, int w, int fuse, unsigned long long *out)
+{
+    if (!out || fuse < 0 || fuse > 8) return CANNY_HIP_ERR_INVALID;
+    const int rc = fuse_stack_check(n_frames, h, w);
+    if (rc) return rc;
+    store_plan(out, plan_thin_tiles(n_frames, h, w));
+    out[4] = (unsigned long long)(fuse ? fuse : thin_auto_fuse()); // aux: the full iterations a launch runs
     return CANNY_HIP_OK;
 }
 

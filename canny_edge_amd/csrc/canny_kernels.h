@@ -892,6 +892,22 @@ int binarize_auto_route(int kw, int kh);
 hipError_t launch_binarize_adaptive(const void *plane, bool in_u8, int n_frames, int h, int w, int c, int kw, int kh,
                                     int invert, int route, uint8_t *out, unsigned long long *counts, hipStream_t stream);
 
+// ---- thinning of packed bit maps (canny_thin.hip) ------------------------------------------
+// Every launch of a call walks the n_frames * ceil(h / 64) * ceil(ceil(w / 64) / 8) tiles of 8 words x 64 rows, one per
+// workgroup and trip.  (Reported by canny_hip_selftest_thin_plan, not by a kind.)
+LaunchPlan plan_thin_tiles(int n_frames, int h, int w);
+int thin_auto_fuse();  // the full iterations a launch of the automatic route runs; 0: automatic is the stepwise route
+// The context workspace of a call: two maps | the deletions per frame and iteration of two chunks | the frames' states | a word
+size_t thin_workspace_bytes(int n_frames, int h, int w);
+// A call is zero, passes, info on one stream.  src: a packed map [n_frames][h][ceil(w / 8)] or -- src_plane -- the strong
+// bit-plane of make_hyst_geom(h, w, n_frames); out: every byte of a packed map, pad bits 0.  method, max_iterations: the
+// header's; route: 0 automatic, 1 stepwise, 2 fused; fuse: 0 automatic, 1..8.  max_iterations = 0 synchronises the stream
+// between chunks of launches.  info (may be NULL, 8-byte aligned): 4 long long a frame.
+hipError_t launch_thin_zero(void *ws, int n_frames, int h, int w, long long *info, hipStream_t stream);
+hipError_t launch_thin_passes(const void *src, bool src_plane, int n_frames, int h, int w, int method, int max_iterations,
+                              int route, int fuse, void *ws, uint8_t *out, hipStream_t stream);
+hipError_t launch_thin_info(void *ws, int n_frames, int h, int w, int max_iterations, long long *info, hipStream_t stream);
+
 // ---- measurement aid ------------------------------------------------------------------------
 // Plain device copy of nbytes (multiple of 16; both pointers 16-byte aligned): what a 1:1 read/write stream reaches.
 hipError_t launch_probe_copy(const void *src, void *dst, size_t nbytes, hipStream_t stream, const LaunchEvents &ev = {});

@@ -19,6 +19,7 @@
 //   last step : the combination with another map (GRADIENT, TOPHAT, BLACKHAT), the clearing of the pad bits and the per-frame
 //               counts belong to the kernel of the last step.  A workgroup's trips are consecutive tiles, so a lane sums the
 //               set bits of a frame over its trips and a wave adds to counts[f] once or twice, not once per tile.
+#include "canny_bit_words.h" // flip_bits, morph_load, funnel
 #include "canny_kernels.h"
 
 namespace canny {
@@ -47,34 +48,6 @@ struct MorphArgs {
     int src_plane, other_plane; // the strong bit-plane of geometry g instead of a packed map
     int vec_src, vec_other, vec_dst; // packed map whose rows are whole, 8-byte aligned words
 };
-
-// bytes MSB-first in memory order <-> LSB-first word
-__device__ __forceinline__ uint64_t flip_bits(uint64_t v) { return __builtin_bswap64(__brevll(v)); }
-
-// Columns 64 k .. 64 k + 63 of row y of frame f; whatever lies outside the frame reads as `fill` (all ones or zero).
-__device__ __forceinline__ uint64_t morph_load(const void *__restrict__ src, bool plane, bool vec, const HystGeom &g, int rb,
-                                               int f, int y, int k, uint64_t fill)
-{
-    if (y < 0 || y >= g.height || k < 0 || k >= g.tiles_x) return fill;
-    const int left = g.width - (k << 6);
-    const uint64_t in = left >= 64 ? ~0ull : ((1ull << left) - 1ull);
-    uint64_t w;
-    if (plane)
-        w = row_word<false>(src, g, rb, f, y, k);
-    else if (vec)
-        w = flip_bits(*reinterpret_cast<const uint64_t *>(static_cast<const uint8_t *>(src) +
-                                                          ((size_t)f * g.height + y) * (size_t)rb + (size_t)k * 8));
-    else
-        w = row_word<true>(src, g, rb, f, y, k);
-    return (w & in) | (fill & ~in);
-}
-
-// columns 64 k + d .. 64 k + d + 63 from the words left of, at and right of k; -64 < d < 64
-__device__ __forceinline__ uint64_t funnel(uint64_t l, uint64_t c, uint64_t r, int d)
-{
-    if (d == 0) return c;
-    return d > 0 ? (c >> d) | (r << (64 - d)) : (c << -d) | (l >> (64 + d));
-}
 
 template <bool OR>
 __device__ __forceinline__ uint64_t comb(uint64_t a, uint64_t b)

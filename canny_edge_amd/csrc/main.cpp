@@ -74,6 +74,11 @@
 // other fields are ignored) or mean (the adaptive mean: thr_or_c the offset c, -255..255, default 7; kw and kh (default kw) odd,
 // 3..255, default 31); invert 0 (default) or 1.  The map (0 / 255) goes to canny_binary.pgm in the -o directory.  A malformed
 // -a is a usage error (exit 2).  Without -a nothing changes.
+// Added: -v method[,max_iterations] thins a bit map to a one-pixel skeleton on the GPU (canny_hip_dev_thin_bits): method guohall
+// or zhangsuen, max_iterations 0..16384 (default 0: to the fixed point).  With -a it is the binarized frame, binarized on the
+// device (canny_hip_dev_binarize) and thinned there with no download in between; without -a the finished edge map
+// (canny_hip_dev_canny_bits).  The skeleton (0 / 255) goes to canny_thin.pgm in the -o directory and "thin iterations D deleted
+// N" to stdout.  A malformed -v is a usage error (exit 2).  Without -v nothing changes.
 // Added: -e computes the sub-pixel edgel of every pixel of the frame's edge map on the GPU (canny_hip_canny_edgels) and
 // writes one "x y gx gy mag dir refined" row per edge pixel, in raster order, to canny_edgels.txt in the -o directory
 // (stdout without -o): x and y in pixels to three decimals, mag in grey levels, dir 0..3 (step (1,0), (1,1), (0,1), (1,-1)),
@@ -720,6 +725,52 @@ static int run_binarize(const vector<unsigned char> &frame, int height, int widt
     return 0;
 }
 
+// -v: a bit map of the frame thinned on the device -> canny_thin.pgm.  bin: the -a arguments (method, thr_or_c, kw, kh, invert)
+// or nullptr for the finished edge map; v: method, max_iterations
+static int run_thin(const vector<unsigned char> &frame, int height, int width, float sigma, int minVal, int maxVal, const int *bin,
+                    const int *v, const string &outdir)
+{
+    const size_t rb = ((size_t)width + 7) / 8, px = (size_t)height * width;
+    vector<unsigned char> bits(rb * height);
+    long long info[CANNY_HIP_THIN_INFO] = {0, 0, 0, 0};
+    canny_hip_ctx *ctx = nullptr;
+    void *d_img = nullptr, *d_bits = nullptr, *d_out = nullptr, *d_info = nullptr;
+    int st = canny_hip_ctx_create(&ctx, 0);
+    if (!st) st = canny_hip_malloc(ctx, &d_img, px);
+    if (!st) st = canny_hip_malloc(ctx, &d_bits, bits.size());
+    if (!st) st = canny_hip_malloc(ctx, &d_out, bits.size());
+    if (!st) st = canny_hip_malloc(ctx, &d_info, sizeof(info));
+    if (!st) st = canny_hip_memcpy_h2d(ctx, d_img, frame.data(), px);
+    if (!st && bin)
+        st = canny_hip_dev_binarize(ctx, (const unsigned char *)d_img, 1, height, width, bin[0], bin[1], bin[2], bin[3], bin[4],
+                                    (unsigned char *)d_bits, nullptr, nullptr);
+    if (!st && !bin)
+        st = canny_hip_dev_canny_bits(ctx, (const unsigned char *)d_img, sigma, minVal, maxVal, height, width, 1, (unsigned char *)d_bits);
+    if (!st)
+        st = canny_hip_dev_thin_bits(ctx, (const unsigned char *)d_bits, 1, height, width, v[0], v[1], (unsigned char *)d_out,
+                                     (long long *)d_info);
+    if (!st) st = canny_hip_memcpy_d2h(ctx, bits.data(), d_out, bits.size());
+    if (!st) st = canny_hip_memcpy_d2h(ctx, info, d_info, sizeof(info));
+    if (st) fprintf(stderr, "ERROR: -v: %s\n", st == CANNY_HIP_ERR_RUNTIME && ctx ? canny_hip_last_error(ctx) : canny_hip_status_string(st));
+    if (ctx) {
+        for (void *p : {d_img, d_bits, d_out, d_info})
+            if (p) canny_hip_free(ctx, p);
+        canny_hip_ctx_destroy(ctx);
+    }
+    if (st) return 1;
+    printf("thin iterations %lld deleted %lld\n", info[1], info[2]);
+    vector<unsigned char> out(px);
+    for (int y = 0; y < height; y++)
+        for (int x = 0; x < width; x++)
+            out[(size_t)y * width + x] = (bits[(size_t)y * rb + (x >> 3)] >> (7 - (x & 7))) & 1 ? 255 : 0;
+    const string path = (outdir.empty() ? string(".") : outdir) + "/canny_thin" + (png_output ? ".png" : ".pgm");
+    if (!write_frame(path, out.data(), height, width)) {
+        fprintf(stderr, "ERROR: cannot write %s\n", path.c_str());
+        return 1;
+    }
+    return 0;
+}
+
 // -r: the circles of the frame's edge map, "frame x y radius votes support" per circle; with -k (fit != nullptr: band,
 // trim_q8, options) also the circle fit of every circle, "frame cx cy r n rms maxd sectors trim_failed degenerate" per circle
 static int run_circles(const vector<unsigned char> &frame, int height, int width, float sigma, int minVal, int maxVal,
@@ -941,6 +992,8 @@ int main(int argc, char *argv[])
     int morph_args[5] = {0, 3, 3, 0, 1};   // -z: op, kw, kh, shape, iterations
     bool want_binarize = false;
     int bin_args[5] = {0, 127, 31, 31, 0}; // -a: method, thr_or_c, kw, kh, invert
+    bool want_thin = false;
+    int thin_args[2] = {CANNY_HIP_THIN_GUOHALL, 0}; // -v: method, max_iterations
     int width = WIDTH, height = HEIGHT;
     vector<string> values;
 
@@ -1193,6 +1246,21 @@ int main(int argc, char *argv[])
                 exit(2);
             }
             want_binarize = true;
+        } else if (arg == "-v") {
+            // method[,max_iterations]: a word and a whole number, nothing empty, nothing behind it
+            const string spec = i + 1 < argc ? argv[++i] : "";
+            const size_t comma = spec.find(',');
+            const string word = spec.substr(0, comma), num = comma == string::npos ? string("0") : spec.substr(comma + 1);
+            thin_args[0] = word == "guohall" ? CANNY_HIP_THIN_GUOHALL : (word == "zhangsuen" ? CANNY_HIP_THIN_ZHANGSUEN : -1);
+            bool clean = thin_args[0] >= 0 && !num.empty() && num.size() <= 5;
+            for (char c : num) clean = clean && isdigit((unsigned char)c);
+            if (clean) thin_args[1] = atoi(num.c_str());
+            if (!clean || thin_args[1] > CANNY_HIP_THIN_MAX_ITERATIONS) {
+                fprintf(stderr, "ERROR: -v expects method[,max_iterations]: method guohall or zhangsuen, max_iterations 0..16384 "
+                                "(0: to the fixed point)\n");
+                exit(2);
+            }
+            want_thin = true;
         } else if (arg == "-w" && i + 1 < argc) {
             char tail = 0; // a whole integer only
             if (sscanf(argv[++i], "%d%c", &curve_min_length, &tail) != 1) {
@@ -1281,6 +1349,8 @@ int main(int argc, char *argv[])
         fprintf(stderr, "       tophat, blackhat; kw, kh odd 1..31; rect, cross, ellipse; 1..16 iterations) -> canny_morph.pgm in the -o dir\n");
         fprintf(stderr, "   -a method[,thr_or_c[,kw[,kh[,invert]]]]: the input frame binarized (fixed: thr -1..255; otsu: the frame's own\n");
         fprintf(stderr, "       threshold, printed; mean: adaptive, offset c, window kw x kh odd 3..255; invert 0 or 1) -> canny_binary.pgm in the -o dir\n");
+        fprintf(stderr, "   -v method[,max_iterations]: the edge map -- with -a the binarized frame, on the device -- thinned to a one-pixel\n");
+        fprintf(stderr, "       skeleton (guohall or zhangsuen; 0..16384 iterations, 0: to the fixed point) -> canny_thin.pgm in the -o dir\n");
         fprintf(stderr, "   -d: distance of every pixel to the nearest edge pixel, min(255, floor) -> canny_dist.pgm in the -o dir\n");
         fprintf(stderr, "   -e: sub-pixel edgel of every edge pixel, one \"x y gx gy mag dir refined\" line each (x, y in pixels to three\n");
         fprintf(stderr, "       decimals, mag in grey levels, dir 0..3) -> canny_edgels.txt in the -o dir\n");
@@ -1368,6 +1438,10 @@ int main(int argc, char *argv[])
     }
     if (want_binarize) {
         const int rc = run_binarize(frame, height, width, bin_args, outdir);
+        if (rc) return rc;
+    }
+    if (want_thin) {
+        const int rc = run_thin(frame, height, width, sigma, minVal, maxVal, want_binarize ? bin_args : nullptr, thin_args, outdir);
         if (rc) return rc;
     }
     if (want_dist) {

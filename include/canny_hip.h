@@ -52,7 +52,8 @@
 extern "C" {
 #endif
 
-#define CANNY_HIP_VERSION 2500       /* 0.25.0: + binarization: gray planes to packed bit maps (fixed, Otsu, adaptive) */
+#define CANNY_HIP_VERSION 2600       /* 0.26.0: + thinning of packed bit maps to one-pixel skeletons */
+/* 0.25.0: + binarization: gray planes to packed bit maps (fixed, Otsu, adaptive) */
 /* 0.24.0: + binary morphology on packed bit maps */
 /* 0.23.0: + temporal fusion of aligned frames and change masks (0.22.0: + frame alignment) */
 /* 0.21.0: + frame-to-frame motion from the corner matches (RANSAC) */
@@ -2234,7 +2235,7 @@ int canny_hip_canny_background(canny_hip_ctx *ctx, const unsigned char *imgs, in
  *     in LDS; any other element runs the general route).  All routes give the same bytes.  Sequential steps go through one
  *     context workspace of two maps (and, for GRADIENT, the output buffer); the final combination, the pad bits and the counts
  *     belong to the last step's kernel.
- * Not covered -- follow-ups: grey-level morphology on u8 planes; hit-or-miss and thinning; elements wider than 31; morphology
+ * Not covered -- follow-ups: grey-level morphology on u8 planes; hit-or-miss (thinning: see below); elements wider than 31; morphology
  * through the batch pipeline or the multi-GPU sharder; a grammar of Main for fusion and change masks. */
 #define CANNY_HIP_MORPH_MAX_EXTENT 31
 #define CANNY_HIP_MORPH_MAX_ITERATIONS 16
@@ -2356,6 +2357,81 @@ int canny_hip_binarize(const unsigned char *imgs, int n_frames, int h, int w, in
  * (CANNY_HIP_ERR_UNSUPPORTED above). */
 int canny_hip_otsu_from_histogram(const unsigned long long *hist256, int *t);
 
+/* ---- thinning of packed bit maps to one-pixel skeletons --------------------------------------------------------------------
+ * The step between "bits" and the stages that assume strokes one pixel wide (the curve linker, the polygons, the line and
+ * circle fits): what cv::ximgproc::thinning and skimage.morphology.thin answer, on the packed layout of
+ * canny_hip_dev_canny_bits, on the context's stream, without a download.  A binarized frame or a change mask goes
+ * binarize -> morph -> thin -> curves on the device.  All bit operations: the same bytes on every run, route and machine.
+ * tests/thin_rule.py restates the rule in numpy, csrc/canny_thin_host.cpp pixel by pixel in plain C++.
+ * THE RULE:
+ *   Bit maps [n_frames][h][(w + 7) / 8] bytes, rows MSB-first.  THE PAD BITS OF THE INPUT ARE IGNORED, THE PAD BITS OF THE
+ *     OUTPUT ARE WRITTEN 0, every output byte is written, EVERYTHING OUTSIDE THE FRAME READS 0, frames never see each other.
+ *   Neighbours of a pixel P1 = (y, x): P2 = (y-1, x), P3 = (y-1, x+1), P4 = (y, x+1), P5 = (y+1, x+1), P6 = (y+1, x),
+ *     P7 = (y+1, x-1), P8 = (y, x-1), P9 = (y-1, x-1).
+ *   One full iteration is sub-iteration 0 on the whole frame, then sub-iteration 1 on the result; within a sub-iteration
+ *     every pixel decides from the same input map (fully parallel).
+ *   CANNY_HIP_THIN_ZHANGSUEN = 0: a set P1 is deleted iff B = P2 + .. + P9 is in 2..6, A = 1 -- A the number of i with
+ *     ring[i] = 0 and ring[i+1] = 1 over the cyclic ring P2, P3, .., P9, P2 -- and
+ *       sub-iteration 0: P2 P4 P6 = 0 and P4 P6 P8 = 0;   sub-iteration 1: P2 P4 P8 = 0 and P2 P6 P8 = 0.
+ *     ZHANGSUEN DOES NOT PRESERVE COMPONENTS: it erases a 2 x 2 square and reduces a two-pixel-wide diagonal to one pixel.
+ *   CANNY_HIP_THIN_GUOHALL = 1: a set P1 is deleted iff C = 1, 2 <= min(N1, N2) <= 3 and m = 0, with
+ *       C  = (!P2 & (P3 | P4)) + (!P4 & (P5 | P6)) + (!P6 & (P7 | P8)) + (!P8 & (P9 | P2)),
+ *       N1 = (P9 | P2) + (P3 | P4) + (P5 | P6) + (P7 | P8),   N2 = (P2 | P3) + (P4 | P5) + (P6 | P7) + (P8 | P9),
+ *       sub-iteration 0: m = (P6 | P7 | !P9) & P8;   sub-iteration 1: m = (P2 | P3 | !P5) & P4.
+ *     It kept the number of 8-connected components on every map tried and is what the examples and Main default to.
+ *   Stopping.  D = the number of full iterations, from the start, that delete at least one pixel (finite).  max_iterations =
+ *     k >= 1: the output is the map after min(k, D) full iterations; max_iterations = 0: after D, the fixed point.
+ *     max_iterations in 0..16384 (CANNY_HIP_THIN_MAX_ITERATIONS).
+ *   info may be NULL; otherwise 4 long long per frame, 8-byte aligned: [0] the set bits of the output frame, [1] iterations =
+ *     min(k, D), or D for k = 0, [2] the pixels deleted = the set bits of the input inside the frame minus [0], [3] converged =
+ *     1 if k = 0 or D < k, else 0 (a run cut at exactly D reports 0: no iteration proved the fixed point).  Zeroed on the
+ *     stream inside the call, fully written by it and not touched by a refused one.
+ *   Facts (tests/test_thin_rule.py): the output is a subset of the input and idempotent; a bar of thickness t takes t / 2
+ *     iterations and leaves one row; an all-set 33 x 47 frame takes 16; GUOHALL keeps 1 pixel of the 2 x 2 square and 13 of the
+ *     diagonal's 23.  No byte equality with OpenCV at the frame border is claimed: the rule above is the specification.
+ *   Limits: h, w in 1..32768, a plane < 2^31 pixels, at most 65535 frames; above: CANNY_HIP_ERR_UNSUPPORTED.  Bad enum values,
+ *     bad ranges, NULL mandatory pointers, a misaligned info buffer, an output that overlaps the input or the info (there is
+ *     no in-place form): CANNY_HIP_ERR_INVALID.  Both before anything is queued; nothing is written.
+ *   Kernels (csrc/canny_thin.hip): a workgroup of 256 per tile of 8 x 64-bit words x 64 rows of a grid capped at 4096, rows
+ *     staged in LDS as whole words with the outside zero put in where the words are formed (the morphology's idiom); the eight
+ *     neighbours are funnel shifts of three staged rows, the counts A, B, C, N1, N2 bit-sliced "exactly one / at least two"
+ *     pairs over 64 pixels at once.  The context option "thin_route": 0 automatic, 1 stepwise (one launch per sub-iteration
+ *     through a context workspace of two maps: the cross-check), 2 fused (one launch runs up to "thin_fuse" = 1..8 full
+ *     iterations, 0 automatic, on a tile without leaving LDS, staged with 2 F halo rows: after j sub-iterations the staged
+ *     region is exact except for a fringe of j pixels, which never reaches the tile).  Every setting gives the same bytes and
+ *     the same info.  The deletions of every frame and iteration are summed on the device; a workgroup that arrives at a frame
+ *     whose preceding iteration deleted nothing only copies its tile, and a tile stops when an iteration deleted nothing in
+ *     its staged region.  max_iterations >= 1 queues every launch up front; max_iterations = 0 reads one device word between
+ *     chunks of launches (8, 16, then 32 iterations) and stops when every frame has reported an iteration without deletions.
+ * Not covered -- follow-ups: hit-or-miss; spur pruning of the skeleton; medial-axis radii (the skeleton with the distance
+ * transform's value); thinning through the batch pipeline or the multi-GPU sharder; grey-level thinning. */
+#define CANNY_HIP_THIN_MAX_ITERATIONS 16384
+#define CANNY_HIP_THIN_INFO 4 /* long long per frame */
+enum canny_hip_thin_method {
+    CANNY_HIP_THIN_ZHANGSUEN = 0,
+    CANNY_HIP_THIN_GUOHALL = 1
+};
+enum canny_hip_thin_part {
+    CANNY_HIP_THIN_PART_PASSES = 0, /* all launches of a call that thin (with the bookkeeping between its chunks) */
+    CANNY_HIP_THIN_PART_INFO = 1,   /* the zeroing and the final reduction to info */
+    CANNY_HIP_THIN_PARTS = 2
+};
+/* d_bits, d_out_bits: n_frames * h * ((w + 7) / 8) bytes, any byte address; d_info: 4 * n_frames long long or NULL.  On the
+ * context's stream.  max_iterations >= 1: fully asynchronous.  max_iterations = 0: THE CALL SYNCHRONISES THE STREAM BEFORE IT
+ * RETURNS (it polls a device word between chunks of launches, as the hysteresis' host-driven route does). */
+int canny_hip_dev_thin_bits(canny_hip_ctx *ctx, const unsigned char *d_bits, int n_frames, int h, int w, int method,
+                            int max_iterations, unsigned char *d_out_bits, long long *d_info);
+/* The same on the strong bit-plane that the preceding dev_canny of the same n_frames, h, w left in the context (another
+ * geometry, or none yet: CANNY_HIP_ERR_INVALID; the plane is only read). */
+int canny_hip_dev_canny_thin(canny_hip_ctx *ctx, int n_frames, int h, int w, int method, int max_iterations,
+                             unsigned char *d_out_bits, long long *d_info);
+/* Host buffers, synchronous: upload, the operator; only out_bits and, if not NULL, info come down. */
+int canny_hip_thin_batch(canny_hip_ctx *ctx, const unsigned char *bits, int n_frames, int h, int w, int method,
+                         int max_iterations, unsigned char *out_bits, long long *info);
+/* Host-only, needs no device: the rule itself on host buffers. */
+int canny_hip_thin_bits(const unsigned char *bits, int n_frames, int h, int w, int method, int max_iterations,
+                        unsigned char *out_bits, long long *info);
+
 /* ---- per-stage HIP-event timing (events are recorded on the launch stream) ----------------- */
 int canny_hip_profile_enable(canny_hip_ctx *ctx, int on);
 int canny_hip_profile_reset(canny_hip_ctx *ctx);
@@ -2402,8 +2478,9 @@ int canny_hip_fuse_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, l
 int canny_hip_morph_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, long *launches);
 /* Every group of parts by name, for this and later features: feature is "stages" (the canny stages of
  * canny_hip_profile_get), "hough", "components", "edt", "hough_segments", "contours", "hough_circles", "polygons", "edgels",
- * "line_fits", "circle_fits", "chamfer", "shapes", "curves", "corners", "descriptors", "motion", "warp", "fuse", "morph" or
- * "binarize" (CANNY_HIP_BIN_PART_*; bit 30 of "profile_stage_mask" like the others); the answer is the named getter's.  An
+ * "line_fits", "circle_fits", "chamfer", "shapes", "curves", "corners", "descriptors", "motion", "warp", "fuse", "morph",
+ * "binarize" (CANNY_HIP_BIN_PART_*) or "thin" (CANNY_HIP_THIN_PART_*; both have no named getter and follow bit 30 of
+ * "profile_stage_mask" like the others); the answer is the named getter's.  An
  * unknown name, a part the group does not have or a NULL: CANNY_HIP_ERR_INVALID, nothing is written. */
 int canny_hip_profile_part_get(canny_hip_ctx *ctx, const char *feature, int part, double *total_ms, long *launches);
 
@@ -2605,6 +2682,11 @@ int canny_hip_selftest_morph_plan(int n_frames, int h, int w, int kw, int kh, un
  * staged columns of a strip for this kw (out[5] + the halo it has room for).  kw, kh are checked for ADAPTIVE_MEAN only;
  * arguments within the limits of the calls. */
 int canny_hip_selftest_binarize_plan(int n_frames, int h, int w, int method, int kw, int kh, unsigned long long *out);
+/* Host-only, the same five outputs for the capped launch of the thinning (no kind above; every launch of a call has this
+ * plan): items = n_frames * ceil(h / 64) * ceil(ceil(w / 64) / 8) tiles, one per workgroup of 256 and trip, at most 4096
+ * workgroups.  fuse: 0, or the "thin_fuse" to report (1..8).  The fifth word is the number of full iterations a launch runs:
+ * fuse, or for fuse = 0 what automatic takes (0 if automatic is the stepwise route).  It refuses what the calls refuse. */
+int canny_hip_selftest_thin_plan(int n_frames, int h, int w, int fuse, unsigned long long *out);
 /* Runs the fuse kernels' own device helper for the rounded mean over every pair c = 1..255, s = 0..255 c, and writes the
  * bytes to host memory as a table [255][CANNY_HIP_FUSE_MEAN_ROW]: out[(c - 1) * 65026 + s]; unused cells are 0. */
 int canny_hip_selftest_fuse_mean(canny_hip_ctx *ctx, unsigned char *out);
