@@ -367,9 +367,119 @@ constexpr int prof_base(const char *name)
     return name ? throw "no such profile group" : base;
 }
 
+// Every device workspace of a context but the staging blocks io[4]: canny_hip_ctx derives from this, so a workspace is
+// ctx->name.  Nothing but DevBuf members may stand here, and each has its row in kWorkspaces below (DESIGN.md section 20
+// has one too): the static_assert behind the table fails the build otherwise.
+struct Workspaces {
+    // device workspaces
+    DevBuf tmp_f32;   // generic Gaussian row-pass plane
+    DevBuf smoothed;  // pipeline: Gaussian output
+    DevBuf edges16;   // canny_hip_dev_canny_u8: the s16 edge map before narrowing
+    DevBuf gray;      // colour input: the converted plane when the Gaussian cannot convert itself
+    DevBuf hist;      // automatic thresholds: per-frame histograms (n_frames x 257 u32)
+    DevBuf thr;       // automatic thresholds: the pairs when the caller does not ask for them
+    DevBuf points;    // edge point lists: per-frame totals (n_frames u64), then per-row counts / prefixes (u32)
+    // Hough lines: the accumulators when the caller passes none; candidate keys, histograms, tie counts, cut words; the
+    // vote tables on the device with the host copy they were sent from and the arguments they belong to
+    DevBuf hough_accum, hough_ws, hough_tab;
+    // connected components: the parent array (4 B/px) when the caller passes no label plane; per-frame totals and per-row
+    // counts / prefixes of the numbering scan
+    DevBuf cc_parent, cc_ws;
+    // contour chains: per-frame totals and per-row sums / prefixes of the chain points (the scan's second use)
+    DevBuf ct_ws;
+    // polygon approximation: the vertex masks (8 B per record slot), the scan's block sums, the vertex flags of long chains
+    // (1 B per point slot); the chains themselves when canny_hip_canny_polygons keeps them on the device
+    DevBuf pg_ws, pg_points;
+    // contour shape measures: per point slot the column extremes, the two lists of the hull's rounds and the finished hull
+    // (20 B per point slot), then the scan's block sums
+    DevBuf sh_ws;
+    // distance transform: the row pass's u16 plane (2 B/px, rows padded to 64 pixels); the column scan's stack (4 B/px) when
+    // the caller passes no dist2 plane to keep it in
+    DevBuf edt_cols, edt_stack;
+    // Hough segments: per-line counts and offsets; bases and line counts when the caller passes none; the private copy of
+    // the map that exclusive mode clears pixels from
+    DevBuf seg_ws, seg_lines, seg_work;
+    // Hough circles: the accumulators when the caller passes none; candidate keys, votes, bases, radii, supports, peak
+    // counts, histograms, tie counts, cut words
+    DevBuf circ_accum, circ_ws;
+    // circle fits: the circle records and counts when the caller passes none
+    DevBuf circ_recs;
+    // chamfer matching, per chunk of frames: the u16 cost plane; the scores when the caller passes no plane for them; the
+    // candidate passes' keys, histograms and counters; and the dist2 plane of the whole batch when the caller passes none
+    DevBuf chamfer_cost, chamfer_scores, chamfer_ws, chamfer_dist2;
+    // corners, per chunk of frames: the collected keys, the radix select's state, the maxima, histograms and counters
+    DevBuf corners_ws;
+    // descriptor matching: the pairs as the kernels read them, then per (pair, train slot) its best query
+    DevBuf desc_ws;
+    // motion estimate: the compacted correspondences and their slots, the inlier counts per (pair, hypothesis), m, the pairs
+    DevBuf motion_ws;
+    // binary morphology: the two intermediate bit maps of a call of more than one primitive step, back to back
+    DevBuf morph_ws;
+    // binarization: the histograms of the frames (OTSU) | the threshold of every frame
+    DevBuf binarize_ws;
+    // thinning: two maps | the deletions per frame and iteration | the frames' states (thin_workspace_bytes)
+    DevBuf thin_ws;
+    DevBuf plane_s, plane_c, stamps, flags; // hysteresis bit-planes / scheduling words
+};
+
+// The workspaces by name, in the order canny_hip_selftest_workspace reports them: what it lists and what
+// canny_hip_ctx_destroy releases.  kind: CANNY_HIP_WS_*.
+struct WsRow {
+    const char *name;
+    DevBuf Workspaces::*buf;
+    int kind;
+};
+constexpr WsRow kWorkspaces[] = {
+    {"tmp_f32", &Workspaces::tmp_f32, CANNY_HIP_WS_DATA},
+    {"smoothed", &Workspaces::smoothed, CANNY_HIP_WS_DATA},
+    {"edges16", &Workspaces::edges16, CANNY_HIP_WS_DATA},
+    {"gray", &Workspaces::gray, CANNY_HIP_WS_DATA},
+    {"hist", &Workspaces::hist, CANNY_HIP_WS_DATA},
+    {"thr", &Workspaces::thr, CANNY_HIP_WS_DATA},
+    {"points", &Workspaces::points, CANNY_HIP_WS_INDEX},           // row prefixes: the scatter's write offsets
+    {"hough_accum", &Workspaces::hough_accum, CANNY_HIP_WS_DATA},
+    {"hough_ws", &Workspaces::hough_ws, CANNY_HIP_WS_INDEX},       // cut words: the select pass's slot counters
+    {"hough_tab", &Workspaces::hough_tab, CANNY_HIP_WS_CACHE},
+    {"cc_parent", &Workspaces::cc_parent, CANNY_HIP_WS_INDEX},
+    {"cc_ws", &Workspaces::cc_ws, CANNY_HIP_WS_INDEX},
+    {"ct_ws", &Workspaces::ct_ws, CANNY_HIP_WS_INDEX},
+    {"pg_ws", &Workspaces::pg_ws, CANNY_HIP_WS_INDEX},             // block sums of the vertex scan
+    {"pg_points", &Workspaces::pg_points, CANNY_HIP_WS_INDEX},     // pixel indices the stage decodes
+    // lists of columns that index the extremes; block sums of the hull scan
+    {"sh_ws", &Workspaces::sh_ws, CANNY_HIP_WS_INDEX},
+    {"edt_cols", &Workspaces::edt_cols, CANNY_HIP_WS_INDEX},       // reused as the column scan's stack of row numbers
+    {"edt_stack", &Workspaces::edt_stack, CANNY_HIP_WS_INDEX},
+    {"seg_ws", &Workspaces::seg_ws, CANNY_HIP_WS_INDEX},
+    {"seg_lines", &Workspaces::seg_lines, CANNY_HIP_WS_INDEX},     // bases decode into table rows, counts bound loops
+    {"seg_work", &Workspaces::seg_work, CANNY_HIP_WS_DATA},
+    {"circ_accum", &Workspaces::circ_accum, CANNY_HIP_WS_DATA},
+    {"circ_ws", &Workspaces::circ_ws, CANNY_HIP_WS_INDEX},         // bases address accumulator cells, peak counts bound loops
+    {"circ_recs", &Workspaces::circ_recs, CANNY_HIP_WS_INDEX},     // radii and centres bound the fit's row walk, counts its grid
+    {"chamfer_cost", &Workspaces::chamfer_cost, CANNY_HIP_WS_DATA},
+    {"chamfer_scores", &Workspaces::chamfer_scores, CANNY_HIP_WS_DATA},
+    // keys address score cells, totals bound the sort, counters hand out slots
+    {"chamfer_ws", &Workspaces::chamfer_ws, CANNY_HIP_WS_INDEX},
+    {"chamfer_dist2", &Workspaces::chamfer_dist2, CANNY_HIP_WS_INDEX}, // doubles as the column scan's stack (see edt_stack)
+    // keys address pixels, totals bound the sort, counters hand out slots
+    {"corners_ws", &Workspaces::corners_ws, CANNY_HIP_WS_INDEX},
+    // the pairs address frames, the best queries are compared with indices
+    {"desc_ws", &Workspaces::desc_ws, CANNY_HIP_WS_INDEX},
+    // the pairs address frames, m bounds the lists, the slots address the flags
+    {"motion_ws", &Workspaces::motion_ws, CANNY_HIP_WS_INDEX},
+    {"morph_ws", &Workspaces::morph_ws, CANNY_HIP_WS_DATA},
+    {"binarize_ws", &Workspaces::binarize_ws, CANNY_HIP_WS_DATA},
+    {"thin_ws", &Workspaces::thin_ws, CANNY_HIP_WS_DATA},
+    {"plane_s", &Workspaces::plane_s, CANNY_HIP_WS_DATA},
+    {"plane_c", &Workspaces::plane_c, CANNY_HIP_WS_DATA},
+    {"stamps", &Workspaces::stamps, CANNY_HIP_WS_INDEX},           // tile queues and their counters
+    {"flags", &Workspaces::flags, CANNY_HIP_WS_DATA},
+};
+static_assert(sizeof(Workspaces) == sizeof(kWorkspaces) / sizeof(kWorkspaces[0]) * sizeof(DevBuf),
+              "every DevBuf member of Workspaces needs its row in kWorkspaces (and nothing else may be a member)");
+
 } // namespace
 
-struct canny_hip_ctx {
+struct canny_hip_ctx : Workspaces {
     int device = 0;
     hipStream_t own_stream = nullptr;
     hipStream_t stream = nullptr;
@@ -414,70 +524,23 @@ struct canny_hip_ctx {
     struct BatchPipe;
     std::vector<BatchPipe *> batch_pool;
 
-    // device workspaces
-    DevBuf tmp_f32;   // generic Gaussian row-pass plane
-    DevBuf smoothed;  // pipeline: Gaussian output
-    DevBuf edges16;   // canny_hip_dev_canny_u8: the s16 edge map before narrowing
-    DevBuf gray;      // colour input: the converted plane when the Gaussian cannot convert itself
-    DevBuf hist;      // automatic thresholds: per-frame histograms (n_frames x 257 u32)
-    DevBuf thr;       // automatic thresholds: the pairs when the caller does not ask for them
-    DevBuf points;    // edge point lists: per-frame totals (n_frames u64), then per-row counts / prefixes (u32)
-    // Hough lines: the accumulators when the caller passes none; candidate keys, histograms, tie counts, cut words; the
-    // vote tables on the device with the host copy they were sent from and the arguments they belong to
-    DevBuf hough_accum, hough_ws, hough_tab;
+    // the features' options and host-side state (their device workspaces are in Workspaces); an int option gets its row in
+    // kOptions below.  Hough lines: the host copy the vote tables (hough_tab) were sent from, and the arguments they belong to
     std::vector<float> hough_tab_host;
     float hough_tab_key[3] = {0, 0, 0};
     int hough_tab_n = 0;
     int hough_path = 0;   // 0 auto (LDS rows when a row fits), 1 global atomics, 2 LDS rows
     int hough_lds_kb = 0; // A/B: LDS budget of a vote workgroup in KiB, 0 = automatic
-    // connected components: the parent array (4 B/px) when the caller passes no label plane; per-frame totals and per-row
-    // counts / prefixes of the numbering scan
-    DevBuf cc_parent, cc_ws;
-    // contour chains: per-frame totals and per-row sums / prefixes of the chain points (the scan's second use)
-    DevBuf ct_ws;
-    // polygon approximation: the vertex masks (8 B per record slot), the scan's block sums, the vertex flags of long chains
-    // (1 B per point slot); the chains themselves when canny_hip_canny_polygons keeps them on the device
-    DevBuf pg_ws, pg_points;
-    // contour shape measures: per point slot the column extremes, the two lists of the hull's rounds and the finished hull
-    // (20 B per point slot), then the scan's block sums
-    DevBuf sh_ws;
-    // distance transform: the row pass's u16 plane (2 B/px, rows padded to 64 pixels); the column scan's stack (4 B/px) when
-    // the caller passes no dist2 plane to keep it in
-    DevBuf edt_cols, edt_stack;
-    // Hough segments: per-line counts and offsets; bases and line counts when the caller passes none; the private copy of
-    // the map that exclusive mode clears pixels from
-    DevBuf seg_ws, seg_lines, seg_work;
-    // Hough circles: the accumulators when the caller passes none; candidate keys, votes, bases, radii, supports, peak
-    // counts, histograms, tie counts, cut words
-    DevBuf circ_accum, circ_ws;
-    // circle fits: the circle records and counts when the caller passes none
-    DevBuf circ_recs;
-    // chamfer matching, per chunk of frames: the u16 cost plane; the scores when the caller passes no plane for them; the
-    // candidate passes' keys, histograms and counters; and the dist2 plane of the whole batch when the caller passes none
-    DevBuf chamfer_cost, chamfer_scores, chamfer_ws, chamfer_dist2;
     int chamfer_route = 0; // 0 auto, 1 direct, 2 tiled
     int warp_route = 0;    // 0 auto, 1 direct, 2 tiled
     int fuse_route = 0;    // the median of the temporal fusion: 0 auto, 1 registers, 2 passes
     int chamfer_chunk_mb = 0; // A/B and tests: budget of the score workspace in MiB, 0 = 256
     std::vector<canny_hip_chamfer_set *> chamfer_sets; // the sets created on this context and not yet destroyed
-    // corners, per chunk of frames: the collected keys, the radix select's state, the maxima, histograms and counters
-    DevBuf corners_ws;
-    // descriptor matching: the pairs as the kernels read them, then per (pair, train slot) its best query
-    DevBuf desc_ws;
     std::vector<int> desc_pairs; // the validated pairs of the last match call: what its upload reads
-    // motion estimate: the compacted correspondences and their slots, the inlier counts per (pair, hypothesis), m, the pairs
-    DevBuf motion_ws;
-    // binary morphology: the two intermediate bit maps of a call of more than one primitive step, back to back
-    DevBuf morph_ws;
     int morph_route = 0;   // 0 auto, 1 general, 2 separable (full rectangles)
-    // binarization: the histograms of the frames (OTSU) | the threshold of every frame
-    DevBuf binarize_ws;
     int binarize_route = 0; // 0 auto, 1 straightforward, 2 marching (ADAPTIVE_MEAN)
-    // thinning: two maps | the deletions per frame and iteration | the frames' states (thin_workspace_bytes)
-    DevBuf thin_ws;
     int thin_route = 0, thin_fuse = 0; // 0 auto, 1 stepwise, 2 fused; 0 auto, 1..8 full iterations a fused launch
     std::vector<int> motion_pairs; // the validated pairs of the last motion call: what its upload reads
-    DevBuf plane_s, plane_c, stamps, flags; // hysteresis bit-planes / scheduling words
     DevBuf io[4];     // staging for the host-pointer stage functions
     std::string ws_name; // canny_hip_selftest_workspace: the name it handed out last
     unsigned *host_flags = nullptr;     // pinned + mapped, 4 words per lane: last_change, domain, sequence number, spare
@@ -522,6 +585,49 @@ struct canny_hip_ctx {
     double total_ms[kProfSlots] = {0};
     long launches[kProfSlots] = {0};
 };
+
+namespace {
+
+// The options that are a plain bounded load or store of an int member: canny_hip_ctx_get_option answers the readable
+// ones, canny_hip_ctx_set_option stores a value in [min, max] into the writable ones.  Everything else (stream_overlap,
+// the profile_* pair, the expand threads, the process-wide tune_* names) is explicit code behind the lookup.
+struct OptRow {
+    const char *name;
+    int canny_hip_ctx::*field;
+    int min, max;
+    bool readable, writable;
+};
+constexpr OptRow kOptions[] = {
+    {"gaussian_path", &canny_hip_ctx::gaussian_path, 0, 2, true, true},
+    {"sobel_nms_path", &canny_hip_ctx::sobel_nms_path, 0, 2, true, true},
+    {"tune_sobel_seg", &canny_hip_ctx::tune_sobel_seg, 0, 4096, false, true},
+    {"fuse_classify", &canny_hip_ctx::fuse_classify, 0, 1, true, true},
+    {"smoothed_u8", &canny_hip_ctx::smoothed_u8, 0, 1, true, true},
+    {"last_canny_smoothed_u8", &canny_hip_ctx::last_canny_u8, 0, 0, true, false},
+    {"gray_rule", &canny_hip_ctx::gray_rule, 0, 1, true, true},
+    {"fuse_gray", &canny_hip_ctx::fuse_gray, 0, 1, true, true},
+    {"last_canny_fused_gray", &canny_hip_ctx::last_fused_gray, 0, 0, true, false},
+    {"hysteresis_tail", &canny_hip_ctx::hyst_tail, 0, 1, true, true},
+    {"tune_hyst_tail_after", &canny_hip_ctx::hyst_tail_after, 1, 4, false, true},
+    {"overlap_hysteresis", &canny_hip_ctx::overlap_hysteresis, 0, 1, false, true},
+    {"tune_batch_workers", &canny_hip_ctx::batch_workers, 0, 16, false, true},
+    {"tune_batch_chunk_mb", &canny_hip_ctx::batch_chunk_mb, 0, 1024, false, true},
+    {"tune_batch_chunk_frames", &canny_hip_ctx::batch_chunk_frames, 0, 65535, false, true},
+    {"tune_batch_pipe_mode", &canny_hip_ctx::batch_pipe_mode, 0, 2, false, true},
+    {"tune_batch_compact", &canny_hip_ctx::batch_compact, 0, 1, true, true},
+    {"hough_path", &canny_hip_ctx::hough_path, 0, 2, true, true},
+    {"tune_hough_lds_kb", &canny_hip_ctx::hough_lds_kb, 0, kHoughLdsMax / 1024, true, true},
+    {"chamfer_route", &canny_hip_ctx::chamfer_route, 0, 2, true, true},
+    {"tune_chamfer_chunk_mb", &canny_hip_ctx::chamfer_chunk_mb, 0, 4096, true, true},
+    {"warp_route", &canny_hip_ctx::warp_route, 0, 2, true, true},
+    {"fuse_route", &canny_hip_ctx::fuse_route, 0, 2, true, true},
+    {"morph_route", &canny_hip_ctx::morph_route, 0, 2, true, true},
+    {"binarize_route", &canny_hip_ctx::binarize_route, 0, 2, true, true},
+    {"thin_route", &canny_hip_ctx::thin_route, 0, 2, true, true},
+    {"thin_fuse", &canny_hip_ctx::thin_fuse, 0, 8, true, true},
+};
+
+} // namespace
 
 // One batch pipeline: three streams and a ring of chunk slots.  Chunk j of the pipeline lives in slot j % kSlots:
 //   s_h2d:    host -> d_in                       (ev_h2d)
@@ -2018,8 +2124,8 @@ int ensure_copy_streams(canny_hip_ctx *ctx, canny_hip_ctx::BatchPipe &w)
     return CANNY_HIP_OK;
 }
 
-// Every device workspace of a context, in struct order, for canny_hip_selftest_workspace: one line per DevBuf member of
-// canny_hip_ctx (DESIGN.md section 20 has a row for each), then the staging of the cached batch pipelines and the
+// Every device workspace of a context, for canny_hip_selftest_workspace: the rows of kWorkspaces (DESIGN.md section 20 has
+// a row for each), the staging blocks io[4], then the staging of the cached batch pipelines and the
 // workspaces of the sub-contexts they own.  Pipeline 0 computes on the context itself, so only its staging is new.
 struct WsEntry {
     std::string name;
@@ -2031,44 +2137,7 @@ void collect_workspaces(const canny_hip_ctx *c, const std::string &prefix, std::
 {
     const int D = CANNY_HIP_WS_DATA, I = CANNY_HIP_WS_INDEX;
     auto add = [&](const char *name, const DevBuf &b, int kind) { v.push_back({prefix + name, &b, kind}); };
-    add("tmp_f32", c->tmp_f32, D);
-    add("smoothed", c->smoothed, D);
-    add("edges16", c->edges16, D);
-    add("gray", c->gray, D);
-    add("hist", c->hist, D);
-    add("thr", c->thr, D);
-    add("points", c->points, I);           // row prefixes: the scatter's write offsets
-    add("hough_accum", c->hough_accum, D);
-    add("hough_ws", c->hough_ws, I);       // cut words: the select pass's slot counters
-    add("hough_tab", c->hough_tab, CANNY_HIP_WS_CACHE);
-    add("cc_parent", c->cc_parent, I);
-    add("cc_ws", c->cc_ws, I);
-    add("ct_ws", c->ct_ws, I);
-    add("pg_ws", c->pg_ws, I);             // block sums of the vertex scan
-    add("pg_points", c->pg_points, I);     // pixel indices the stage decodes
-    add("sh_ws", c->sh_ws, I);             // lists of columns that index the extremes; block sums of the hull scan
-    add("edt_cols", c->edt_cols, I);       // reused as the column scan's stack of row numbers
-    add("edt_stack", c->edt_stack, I);
-    add("seg_ws", c->seg_ws, I);
-    add("seg_lines", c->seg_lines, I);     // bases decode into table rows, counts bound loops
-    add("seg_work", c->seg_work, D);
-    add("circ_accum", c->circ_accum, D);
-    add("circ_ws", c->circ_ws, I);         // bases address accumulator cells, peak counts bound loops
-    add("circ_recs", c->circ_recs, I);     // radii and centres bound the fit's row walk, counts its grid
-    add("chamfer_cost", c->chamfer_cost, D);
-    add("chamfer_scores", c->chamfer_scores, D);
-    add("chamfer_ws", c->chamfer_ws, I);   // keys address score cells, totals bound the sort, counters hand out slots
-    add("chamfer_dist2", c->chamfer_dist2, I); // doubles as the column scan's stack (see edt_stack)
-    add("corners_ws", c->corners_ws, I);   // keys address pixels, totals bound the sort, counters hand out slots
-    add("desc_ws", c->desc_ws, I);         // the pairs address frames, the best queries are compared with indices
-    add("motion_ws", c->motion_ws, I);     // the pairs address frames, m bounds the lists, the slots address the flags
-    add("morph_ws", c->morph_ws, D);
-    add("binarize_ws", c->binarize_ws, D);
-    add("thin_ws", c->thin_ws, D);
-    add("plane_s", c->plane_s, D);
-    add("plane_c", c->plane_c, D);
-    add("stamps", c->stamps, I);           // tile queues and their counters
-    add("flags", c->flags, D);
+    for (const WsRow &r : kWorkspaces) add(r.name, c->*r.buf, r.kind);
     for (int k = 0; k < 4; k++) add(("io" + std::to_string(k)).c_str(), c->io[k], I); // whatever a stage call staged last
     for (size_t p = 0; p < c->batch_pool.size(); p++) {
         const canny_hip_ctx::BatchPipe *w = c->batch_pool[p];
@@ -2157,44 +2226,8 @@ void canny_hip_ctx_destroy(canny_hip_ctx *ctx)
     (void)hipSetDevice(ctx->device);
     if (ctx->aux_stream) (void)hipStreamSynchronize(ctx->aux_stream);
     (void)hipStreamSynchronize(ctx->stream);
-    ctx->tmp_f32.release();
-    ctx->smoothed.release();
-    ctx->plane_s.release();
-    ctx->plane_c.release();
-    ctx->edges16.release();
-    ctx->hist.release();
-    ctx->thr.release();
-    ctx->points.release();
-    ctx->hough_accum.release();
-    ctx->hough_ws.release();
-    ctx->hough_tab.release();
-    ctx->seg_ws.release();
-    ctx->seg_lines.release();
-    ctx->seg_work.release();
-    ctx->circ_accum.release();
-    ctx->circ_ws.release();
-    ctx->circ_recs.release();
     while (!ctx->chamfer_sets.empty()) (void)canny_hip_chamfer_set_destroy(ctx, ctx->chamfer_sets.back());
-    ctx->chamfer_cost.release();
-    ctx->chamfer_scores.release();
-    ctx->chamfer_ws.release();
-    ctx->chamfer_dist2.release();
-    ctx->corners_ws.release();
-    ctx->desc_ws.release();
-    ctx->motion_ws.release();
-    ctx->morph_ws.release();
-    ctx->binarize_ws.release();
-    ctx->thin_ws.release();
-    ctx->cc_parent.release();
-    ctx->cc_ws.release();
-    ctx->ct_ws.release();
-    ctx->pg_ws.release();
-    ctx->pg_points.release();
-    ctx->sh_ws.release();
-    ctx->edt_cols.release();
-    ctx->edt_stack.release();
-    ctx->stamps.release();
-    ctx->flags.release();
+    for (const WsRow &r : kWorkspaces) (ctx->*r.buf).release();
     for (auto &b : ctx->io) b.release();
     if (ctx->host_flags) (void)hipHostFree(ctx->host_flags);
     if (ctx->flag_event) (void)hipEventDestroy(ctx->flag_event);
@@ -2227,27 +2260,13 @@ int canny_hip_ctx_device(const canny_hip_ctx *ctx) { return ctx ? ctx->device : 
 int canny_hip_ctx_get_option(const canny_hip_ctx *ctx, const char *name, int *value)
 {
     if (!ctx || !name || !value) return CANNY_HIP_ERR_INVALID;
-    if (!std::strcmp(name, "smoothed_u8")) *value = ctx->smoothed_u8;
-    else if (!std::strcmp(name, "last_canny_smoothed_u8")) *value = ctx->last_canny_u8; // read-only
-    else if (!std::strcmp(name, "gray_rule")) *value = ctx->gray_rule;
-    else if (!std::strcmp(name, "fuse_gray")) *value = ctx->fuse_gray;
-    else if (!std::strcmp(name, "last_canny_fused_gray")) *value = ctx->last_fused_gray; // read-only
-    else if (!std::strcmp(name, "fuse_classify")) *value = ctx->fuse_classify;
-    else if (!std::strcmp(name, "hysteresis_tail")) *value = ctx->hyst_tail;
-    else if (!std::strcmp(name, "gaussian_path")) *value = ctx->gaussian_path;
-    else if (!std::strcmp(name, "sobel_nms_path")) *value = ctx->sobel_nms_path;
-    else if (!std::strcmp(name, "tune_batch_compact")) *value = ctx->batch_compact;
-    else if (!std::strcmp(name, "hough_path")) *value = ctx->hough_path;
-    else if (!std::strcmp(name, "tune_hough_lds_kb")) *value = ctx->hough_lds_kb;
-    else if (!std::strcmp(name, "chamfer_route")) *value = ctx->chamfer_route;
-    else if (!std::strcmp(name, "warp_route")) *value = ctx->warp_route;
-    else if (!std::strcmp(name, "fuse_route")) *value = ctx->fuse_route;
-    else if (!std::strcmp(name, "morph_route")) *value = ctx->morph_route;
-    else if (!std::strcmp(name, "binarize_route")) *value = ctx->binarize_route;
-    else if (!std::strcmp(name, "thin_route")) *value = ctx->thin_route;
-    else if (!std::strcmp(name, "thin_fuse")) *value = ctx->thin_fuse;
-    else if (!std::strcmp(name, "tune_chamfer_chunk_mb")) *value = ctx->chamfer_chunk_mb;
-    else if (!std::strcmp(name, "batch_expand_threads")) *value = ctx->expand_pool ? ctx->expand_pool->size() : 0; // read-only
+    for (const OptRow &o : kOptions)
+        if (!std::strcmp(name, o.name)) {
+            if (!o.readable) return CANNY_HIP_ERR_INVALID;
+            *value = ctx->*o.field;
+            return CANNY_HIP_OK;
+        }
+    if (!std::strcmp(name, "batch_expand_threads")) *value = ctx->expand_pool ? ctx->expand_pool->size() : 0; // read-only
     else return CANNY_HIP_ERR_INVALID;
     return CANNY_HIP_OK;
 }
@@ -2255,32 +2274,13 @@ int canny_hip_ctx_get_option(const canny_hip_ctx *ctx, const char *name, int *va
 int canny_hip_ctx_set_option(canny_hip_ctx *ctx, const char *name, int value)
 {
     if (!ctx || !name || value < 0) return CANNY_HIP_ERR_INVALID;
-    if (!std::strcmp(name, "gaussian_path") && value <= 2) ctx->gaussian_path = value;
-    else if (!std::strcmp(name, "sobel_nms_path") && value <= 2) ctx->sobel_nms_path = value;
-    else if (!std::strcmp(name, "tune_sobel_seg") && value <= 4096) ctx->tune_sobel_seg = value;
-    else if (!std::strcmp(name, "fuse_classify") && value <= 1) ctx->fuse_classify = value;
-    else if (!std::strcmp(name, "smoothed_u8") && value <= 1) ctx->smoothed_u8 = value;
-    else if (!std::strcmp(name, "gray_rule") && value <= 1) ctx->gray_rule = value;
-    else if (!std::strcmp(name, "fuse_gray") && value <= 1) ctx->fuse_gray = value;
-    else if (!std::strcmp(name, "hysteresis_tail") && value <= 1) ctx->hyst_tail = value;
-    else if (!std::strcmp(name, "tune_hyst_tail_after") && value >= 1 && value <= 4) ctx->hyst_tail_after = value;
-    else if (!std::strcmp(name, "overlap_hysteresis") && value <= 1) ctx->overlap_hysteresis = value;
-    else if (!std::strcmp(name, "tune_batch_workers") && value <= 16) ctx->batch_workers = value;
-    else if (!std::strcmp(name, "tune_batch_chunk_mb") && value <= 1024) ctx->batch_chunk_mb = value;
-    else if (!std::strcmp(name, "tune_batch_chunk_frames") && value <= 65535) ctx->batch_chunk_frames = value;
-    else if (!std::strcmp(name, "tune_batch_pipe_mode") && value <= 2) ctx->batch_pipe_mode = value;
-    else if (!std::strcmp(name, "tune_batch_compact") && value <= 1) ctx->batch_compact = value;
-    else if (!std::strcmp(name, "hough_path") && value <= 2) ctx->hough_path = value;
-    else if (!std::strcmp(name, "chamfer_route") && value <= 2) ctx->chamfer_route = value;
-    else if (!std::strcmp(name, "warp_route") && value <= 2) ctx->warp_route = value;
-    else if (!std::strcmp(name, "fuse_route") && value <= 2) ctx->fuse_route = value;
-    else if (!std::strcmp(name, "morph_route") && value <= 2) ctx->morph_route = value;
-    else if (!std::strcmp(name, "binarize_route") && value <= 2) ctx->binarize_route = value;
-    else if (!std::strcmp(name, "thin_route") && value <= 2) ctx->thin_route = value;
-    else if (!std::strcmp(name, "thin_fuse") && value <= 8) ctx->thin_fuse = value;
-    else if (!std::strcmp(name, "tune_chamfer_chunk_mb") && value <= 4096) ctx->chamfer_chunk_mb = value;
-    else if (!std::strcmp(name, "tune_hough_lds_kb") && value <= kHoughLdsMax / 1024) ctx->hough_lds_kb = value;
-    else if (!std::strcmp(name, "tune_batch_expand_threads") && value <= 64) {
+    for (const OptRow &o : kOptions)
+        if (!std::strcmp(name, o.name)) {
+            if (!o.writable || value < o.min || value > o.max) return CANNY_HIP_ERR_INVALID;
+            ctx->*o.field = value;
+            return CANNY_HIP_OK;
+        }
+    if (!std::strcmp(name, "tune_batch_expand_threads") && value <= 64) {
         if (value != ctx->batch_expand_threads) ctx->expand_pool.reset();
         ctx->batch_expand_threads = value;
     }
