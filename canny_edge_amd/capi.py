@@ -151,6 +151,8 @@ EXPORTS = (
     "canny_hip_selftest_binarize_plan", "canny_hip_profile_part_get",
     "canny_hip_dev_thin_bits", "canny_hip_dev_canny_thin", "canny_hip_thin_batch", "canny_hip_thin_bits",
     "canny_hip_selftest_thin_plan",
+    "canny_hip_dev_reconstruct_bits", "canny_hip_dev_canny_reconstruct", "canny_hip_reconstruct_batch",
+    "canny_hip_reconstruct_bits", "canny_hip_selftest_reconstruct_plan",
 )
 
 _lib: Optional[C.CDLL] = None
@@ -435,6 +437,11 @@ def load() -> C.CDLL:
         "canny_hip_thin_batch": ([p, p, i, i, i, i, i, p, p], i),
         "canny_hip_thin_bits": ([p, i, i, i, i, i, p, p], i),
         "canny_hip_selftest_thin_plan": ([i, i, i, i, p], i),
+        "canny_hip_dev_reconstruct_bits": ([p, p, p, i, i, i, i, i, p, p], i),
+        "canny_hip_dev_canny_reconstruct": ([p, p, i, i, i, i, i, p, p], i),
+        "canny_hip_reconstruct_batch": ([p, p, p, i, i, i, i, i, p, p], i),
+        "canny_hip_reconstruct_bits": ([p, p, i, i, i, i, i, p, p], i),
+        "canny_hip_selftest_reconstruct_plan": ([i, i, i, i, p], i),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -1368,6 +1375,42 @@ def thin_plan(n_frames: int, h: int, w: int, fuse: int = 0):
     """Host-only: the LaunchPlan of every launch of a thinning call (one tile of 8 words x 64 rows per workgroup and trip);
     aux = the full iterations a launch runs: fuse, or for 0 what automatic takes (0: automatic is the stepwise route)."""
     return _plan("thin_plan", int(n_frames), int(h), int(w), int(fuse))
+
+
+# ---- morphological reconstruction of packed bit maps (DESIGN.md section 38) ----------------------------------------------
+RECON_SEEDED, RECON_FILL_HOLES, RECON_CLEAR_BORDER = 0, 1, 2
+RECON_OPS = ("seeded", "fill", "clear")
+RECON_ROUTE_AUTO, RECON_ROUTE_STEPWISE, RECON_ROUTE_TILES = 0, 1, 2
+RECON_INFO = 3
+RECON_PARTS = ("sweeps", "info")
+
+
+def _recon_maps(marker, mask, w: int, op: int):
+    m = _thin_maps(mask, w)
+    if (marker is None) != (int(op) != RECON_SEEDED):
+        raise ValueError("a marker goes with RECON_SEEDED and with no other op")
+    k = None if marker is None else _thin_maps(marker, w)
+    if k is not None and k.shape != m.shape:
+        raise ValueError("marker and mask differ in shape")
+    return k, m
+
+
+def reconstruct_bits(marker, mask, w: int, op: int = RECON_SEEDED, connectivity: int = 8):
+    """Host-only, needs no GPU: the reconstruction rule on bit maps uint8 [n_frames, H, ceil(w / 8)] (rows MSB-first; pad bits
+    ignored; marker None unless op is RECON_SEEDED) -> (bit maps of the same shape with pad bits 0, info int64 [n_frames, 3]:
+    set bits of the output, of the mask, of the start set)."""
+    k, m = _recon_maps(marker, mask, w, op)
+    n, h, _ = m.shape
+    out, info = np.zeros_like(m), np.zeros((n, RECON_INFO), np.int64)
+    _ok(load().canny_hip_reconstruct_bits(None if k is None else _hp(k), _hp(m), n, h, int(w), int(op), int(connectivity),
+                                          _hp(out), _hp(info)), "reconstruct_bits")
+    return out, info
+
+
+def reconstruct_plan(n_frames: int, h: int, w: int, route: int = 0):
+    """Host-only: the LaunchPlan of the sweep launches of a reconstruction call (route 2: one tile of 8 words x 64 rows per
+    workgroup and trip; route 1: 256 words); aux = the route automatic takes."""
+    return _plan("reconstruct_plan", int(n_frames), int(h), int(w), int(route))
 
 
 # ---- chamfer template matching (DESIGN.md section 26) --------------------------------------------------------------------
@@ -2941,9 +2984,36 @@ class Context:
                                                  _hp(info)), "thin_batch")
         return out, info
 
+    # ---- morphological reconstruction of packed bit maps ------------------------------------------
+    def dev_reconstruct_bits(self, d_marker: int, d_mask: int, n_frames: int, h: int, w: int, op: int, connectivity: int,
+                             d_out_bits: int, d_info: int = 0):
+        """Floods the start set of `op` (d_marker for RECON_SEEDED, else 0: the border ring) inside device bit maps
+        [n_frames][h][ceil(w / 8)] to the fixed point, into d_out_bits and, if given, 3 int64 a frame at d_info (set bits of the
+        output, of the mask, of the start set).  The stream is synchronised before the call returns."""
+        v = C.c_void_p
+        self._check(self._L.canny_hip_dev_reconstruct_bits(self._h, v(d_marker or None), v(d_mask or None), n_frames, h, w, int(op),
+                                                           int(connectivity), v(d_out_bits or None), v(d_info or None)),
+                    "dev_reconstruct_bits")
+
+    def dev_canny_reconstruct(self, d_marker: int, n_frames: int, h: int, w: int, op: int, connectivity: int, d_out_bits: int,
+                              d_info: int = 0):
+        """The same with the strong bit-plane the preceding dev_canny of the same geometry left in the context as the mask."""
+        v = C.c_void_p
+        self._check(self._L.canny_hip_dev_canny_reconstruct(self._h, v(d_marker or None), n_frames, h, w, int(op), int(connectivity),
+                                                            v(d_out_bits or None), v(d_info or None)), "dev_canny_reconstruct")
+
+    def reconstruct_batch(self, marker, mask, w: int, op: int = RECON_SEEDED, connectivity: int = 8):
+        """Upload and the operator on the GPU: bit maps uint8 [N, H, ceil(w / 8)] -> (bit maps, info int64 [N, 3])."""
+        k, m = _recon_maps(marker, mask, w, op)
+        n, h, _ = m.shape
+        out, info = np.zeros_like(m), np.zeros((n, RECON_INFO), np.int64)
+        self._check(self._L.canny_hip_reconstruct_batch(self._h, None if k is None else _hp(k), _hp(m), n, h, int(w), int(op),
+                                                        int(connectivity), _hp(out), _hp(info)), "reconstruct_batch")
+        return out, info
+
     def profile_part(self, feature: str, part: int) -> Tuple[float, int]:
         """(total ms, launch groups) of part `part` of the named group of the profile table ("stages", "hough", ..., "morph",
-        "binarize": BIN_PARTS, "thin": THIN_PARTS): what the group's own getter answers."""
+        "binarize": BIN_PARTS, "thin": THIN_PARTS, "reconstruct": RECON_PARTS): what the group's own getter answers."""
         ms, n = C.c_double(0), C.c_long(0)
         self._check(self._L.canny_hip_profile_part_get(self._h, str(feature).encode(), int(part), C.byref(ms), C.byref(n)),
                     "profile_part_get")

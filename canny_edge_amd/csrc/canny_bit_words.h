@@ -1,5 +1,5 @@
 // canny_bit_words.h -- rows of a bit map as LSB-first 64-bit words, for the kernels that work on whole words in LDS
-// (canny_morph.hip, canny_thin.hip).  Device code only.
+// (canny_morph.hip, canny_thin.hip, canny_reconstruct.hip).  Device code only.
 #pragma once
 #include "canny_kernels.h"
 

@@ -352,6 +352,7 @@ constexpr ProfGroup kProfGroups[] = {
     {"morph", CANNY_HIP_MORPH_PARTS},
     {"binarize", CANNY_HIP_BIN_PARTS},
     {"thin", CANNY_HIP_THIN_PARTS},
+    {"reconstruct", CANNY_HIP_RECON_PARTS},
 };
 
 // The first slot of the named group; with no name, the number of slots.  A name the table does not hold fails to compile.
@@ -417,7 +418,8 @@ struct Workspaces {
     DevBuf morph_ws;
     // binarization: the histograms of the frames (OTSU) | the threshold of every frame
     DevBuf binarize_ws;
-    // thinning: two maps | the deletions per frame and iteration | the frames' states (thin_workspace_bytes)
+    // thinning: two maps | the deletions per frame and iteration | the frames' states (thin_workspace_bytes); reconstruction:
+    // a word-aligned copy of the state | the changed words per frame and launch | the accumulators (reconstruct_workspace_bytes)
     DevBuf thin_ws;
     DevBuf plane_s, plane_c, stamps, flags; // hysteresis bit-planes / scheduling words
 };
@@ -540,6 +542,8 @@ struct canny_hip_ctx : Workspaces {
     int morph_route = 0;   // 0 auto, 1 general, 2 separable (full rectangles)
     int binarize_route = 0; // 0 auto, 1 straightforward, 2 marching (ADAPTIVE_MEAN)
     int thin_route = 0, thin_fuse = 0; // 0 auto, 1 stepwise, 2 fused; 0 auto, 1..8 full iterations a fused launch
+    int reconstruct_route = 0;         // 0 auto, 1 stepwise, 2 tile flood
+    int last_reconstruct_launches = 0; // the sweep launches the last reconstruction call queued: a diagnostic
     std::vector<int> motion_pairs; // the validated pairs of the last motion call: what its upload reads
     DevBuf io[4];     // staging for the host-pointer stage functions
     std::string ws_name; // canny_hip_selftest_workspace: the name it handed out last
@@ -573,7 +577,8 @@ struct canny_hip_ctx : Workspaces {
                          kProfCurves = prof_base("curves"), kProfCorners = prof_base("corners"),
                          kProfDescriptors = prof_base("descriptors"), kProfMotion = prof_base("motion"),
                          kProfWarp = prof_base("warp"), kProfFuse = prof_base("fuse"), kProfMorph = prof_base("morph"),
-                         kProfBinarize = prof_base("binarize"), kProfThin = prof_base("thin");
+                         kProfBinarize = prof_base("binarize"), kProfThin = prof_base("thin"),
+                         kProfReconstruct = prof_base("reconstruct");
     static constexpr int kProfSlots = prof_base(nullptr);
     // "profile_stage_mask" is a non-negative int option: bit 30 is the last it can carry
     static constexpr int kProfLastBit = 30;
@@ -625,6 +630,8 @@ constexpr OptRow kOptions[] = {
     {"binarize_route", &canny_hip_ctx::binarize_route, 0, 2, true, true},
     {"thin_route", &canny_hip_ctx::thin_route, 0, 2, true, true},
     {"thin_fuse", &canny_hip_ctx::thin_fuse, 0, 8, true, true},
+    {"reconstruct_route", &canny_hip_ctx::reconstruct_route, 0, 2, true, true},
+    {"last_reconstruct_launches", &canny_hip_ctx::last_reconstruct_launches, 0, 0, true, false},
 };
 
 } // namespace
@@ -7022,6 +7029,117 @@ int canny_hip_selftest_thin_plan(int n_frames, int h, int w, int fuse, unsigned 
     if (rc) return rc;
     store_plan(out, plan_thin_tiles(n_frames, h, w));
     out[4] = (unsigned long long)(fuse ? fuse : thin_auto_fuse()); // aux: the full iterations a launch runs
+    return CANNY_HIP_OK;
+}
+
+// ---- morphological reconstruction of packed bit maps (canny_reconstruct.hip) ------------------------
+// canny_hip_reconstruct_bits, the rule in plain C++, lives in canny_reconstruct_host.cpp.
+
+namespace {
+// every check of the reconstruction but the mask pointer and the overlaps
+int recon_check(const void *marker, const void *out, const void *info, int n_frames, int h, int w, int op, int connectivity)
+{
+    if (!out || ((uintptr_t)info & 7) || n_frames < 1 || h < 1 || w < 1 || op < CANNY_HIP_RECON_SEEDED ||
+        op > CANNY_HIP_RECON_CLEAR_BORDER || (connectivity != 4 && connectivity != 8) ||
+        (op == CANNY_HIP_RECON_SEEDED) != (marker != nullptr))
+        return CANNY_HIP_ERR_INVALID;
+    return fuse_stack_check(n_frames, h, w);
+}
+
+// The operator on the context's stream; mask: a packed map or -- strong -- the context's strong bit-plane.  Everything has
+// been checked.  The stream is idle when this returns.
+int dev_reconstruct(canny_hip_ctx *ctx, const unsigned char *marker, const void *mask, bool strong, int n_frames, int h, int w,
+                    int op, int connectivity, unsigned char *d_out, long long *d_info)
+{
+    HIP_TRY(ctx, ctx->thin_ws.ensure(reconstruct_workspace_bytes(n_frames, h, w)));
+    auto phase = [&](int which) {
+        return launch_reconstruct(which, marker, mask, strong, n_frames, h, w, op, connectivity, ctx->reconstruct_route,
+                                  ctx->thin_ws.p, d_out, d_info, &ctx->last_reconstruct_launches, ctx->stream);
+    };
+    {
+        StageTimer tm(ctx, canny_hip_ctx::kProfReconstruct + CANNY_HIP_RECON_PART_INFO);
+        HIP_TRY(ctx, phase(RECON_INIT));
+    }
+    {
+        StageTimer tm(ctx, canny_hip_ctx::kProfReconstruct + CANNY_HIP_RECON_PART_SWEEPS);
+        HIP_TRY(ctx, phase(RECON_SWEEPS));
+    }
+    {
+        StageTimer tm(ctx, canny_hip_ctx::kProfReconstruct + CANNY_HIP_RECON_PART_INFO);
+        HIP_TRY(ctx, phase(RECON_FINISH));
+    }
+    return CANNY_HIP_OK;
+}
+} // namespace
+
+int canny_hip_dev_reconstruct_bits(canny_hip_ctx *ctx, const unsigned char *d_marker, const unsigned char *d_mask, int n_frames,
+                                   int h, int w, int op, int connectivity, unsigned char *d_out, long long *d_info)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!d_mask) return CANNY_HIP_ERR_INVALID;
+    if ((rc = recon_check(d_marker, d_out, d_info, n_frames, h, w, op, connectivity))) return rc;
+    const size_t bytes = npx(h, (w + 7) / 8, n_frames), ibytes = (size_t)n_frames * CANNY_HIP_RECON_INFO * sizeof(long long);
+    if (opt_overlap(d_marker, bytes, d_out, bytes) || ranges_overlap(d_mask, bytes, d_out, bytes) ||
+        opt_overlap(d_out, bytes, d_info, ibytes) || opt_overlap(d_marker, bytes, d_info, ibytes) ||
+        opt_overlap(d_mask, bytes, d_info, ibytes))
+        return CANNY_HIP_ERR_INVALID;
+    if ((rc = finish_pending(ctx))) return rc;
+    return dev_reconstruct(ctx, d_marker, d_mask, false, n_frames, h, w, op, connectivity, d_out, d_info);
+}
+
+int canny_hip_dev_canny_reconstruct(canny_hip_ctx *ctx, const unsigned char *d_marker, int n_frames, int h, int w, int op,
+                                    int connectivity, unsigned char *d_out, long long *d_info)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if ((rc = recon_check(d_marker, d_out, d_info, n_frames, h, w, op, connectivity))) return rc;
+    // the plane the last canny call left: only for the batch it belongs to
+    if (!last_canny_was(ctx, n_frames, h, w) || !ctx->plane_s.p) return CANNY_HIP_ERR_INVALID;
+    const size_t bytes = npx(h, (w + 7) / 8, n_frames), ibytes = (size_t)n_frames * CANNY_HIP_RECON_INFO * sizeof(long long);
+    if (opt_overlap(d_marker, bytes, d_out, bytes) || opt_overlap(d_out, bytes, d_info, ibytes) ||
+        opt_overlap(d_marker, bytes, d_info, ibytes))
+        return CANNY_HIP_ERR_INVALID;
+    if ((rc = finish_pending(ctx))) return rc;
+    return dev_reconstruct(ctx, d_marker, ctx->plane_s.p, true, n_frames, h, w, op, connectivity, d_out, d_info);
+}
+
+int canny_hip_reconstruct_batch(canny_hip_ctx *ctx, const unsigned char *marker, const unsigned char *mask, int n_frames, int h,
+                                int w, int op, int connectivity, unsigned char *out, long long *info)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!mask) return CANNY_HIP_ERR_INVALID;
+    if ((rc = recon_check(marker, out, info, n_frames, h, w, op, connectivity))) return rc;
+    const size_t bytes = npx(h, (w + 7) / 8, n_frames), slot = (bytes + 15) & ~(size_t)15;
+    const size_t ibytes = (size_t)n_frames * CANNY_HIP_RECON_INFO * sizeof(long long);
+    if (opt_overlap(marker, bytes, out, bytes) || ranges_overlap(mask, bytes, out, bytes) || opt_overlap(out, bytes, info, ibytes) ||
+        opt_overlap(marker, bytes, info, ibytes) || opt_overlap(mask, bytes, info, ibytes))
+        return CANNY_HIP_ERR_INVALID;
+    if ((rc = finish_pending(ctx))) return rc;
+    if ((rc = h2d(ctx, ctx->io[0], mask, bytes))) return rc;
+    if (marker && (rc = h2d(ctx, ctx->io[2], marker, bytes))) return rc;
+    // one staging block: the output maps | the info
+    HIP_TRY(ctx, ctx->io[1].ensure(slot + ibytes));
+    unsigned char *d_out = (unsigned char *)ctx->io[1].p;
+    long long *d_info = (long long *)(d_out + slot);
+    if ((rc = dev_reconstruct(ctx, marker ? (const unsigned char *)ctx->io[2].p : nullptr, ctx->io[0].p, false, n_frames, h, w, op,
+                              connectivity, d_out, info ? d_info : nullptr)))
+        return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(out, d_out, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    if (info) HIP_TRY(ctx, hipMemcpyAsync(info, d_info, ibytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return CANNY_HIP_OK;
+}
+
+// Host-only: the launch plan of the sweep launches of a call and the route automatic takes.
+int canny_hip_selftest_reconstruct_plan(int n_frames, int h, int w, int route, unsigned long long *out)
+{
+    if (!out || route < 0 || route > 2) return CANNY_HIP_ERR_INVALID;
+    const int rc = fuse_stack_check(n_frames, h, w);
+    if (rc) return rc;
+    store_plan(out, plan_reconstruct(n_frames, h, w, route));
+    out[4] = (unsigned long long)reconstruct_auto_route(); // aux: the route automatic takes
     return CANNY_HIP_OK;
 }
 

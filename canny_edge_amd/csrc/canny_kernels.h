@@ -908,6 +908,27 @@ hipError_t launch_thin_passes(const void *src, bool src_plane, int n_frames, int
                               int route, int fuse, void *ws, uint8_t *out, hipStream_t stream);
 hipError_t launch_thin_info(void *ws, int n_frames, int h, int w, int max_iterations, long long *info, hipStream_t stream);
 
+// ---- morphological reconstruction of packed bit maps (canny_reconstruct.hip) ---------------
+// The sweep launches of a call.  route 2 (and 0 where automatic is the tile flood): the n_frames * ceil(h / 64) *
+// ceil(ceil(w / 64) / 8) tiles of 8 words x 64 rows, one per workgroup and trip; route 1: the n_frames * h * ceil(w / 64)
+// words, 256 per workgroup and trip.  Init and finish have the plan of route 1.  (Reported by
+// canny_hip_selftest_reconstruct_plan, not by a kind.)
+LaunchPlan plan_reconstruct(int n_frames, int h, int w, int route);
+int reconstruct_auto_route(); // 1 stepwise or 2 tile flood
+// What a call needs of the context's thin_ws: a word-aligned copy of the state | the changed words of two chunks of launches
+// | three accumulators a frame | the poll word
+size_t reconstruct_workspace_bytes(int n_frames, int h, int w);
+// A call is the three phases in this order with the same arguments on one stream.  marker: a packed map
+// [n_frames][h][ceil(w / 8)] for op 0, NULL otherwise; mask: a packed map or -- mask_plane -- the strong bit-plane of
+// make_hyst_geom(h, w, n_frames); out: every byte of a packed map, pad bits 0; between the phases it (or the workspace, where
+// its rows are not whole aligned words) holds the flood's state.  op, connectivity: the header's; route: 0 automatic,
+// 1 stepwise, 2 tile flood.  SWEEPS synchronises the stream behind every chunk of launches and reports the sweep launches it
+// queued in *launches; FINISH synchronises it once more.  info (may be NULL, 8-byte aligned): 3 long long a frame.
+enum { RECON_INIT = 0, RECON_SWEEPS = 1, RECON_FINISH = 2 };
+hipError_t launch_reconstruct(int phase, const uint8_t *marker, const void *mask, bool mask_plane, int n_frames, int h, int w,
+                              int op, int connectivity, int route, void *ws, uint8_t *out, long long *info, int *launches,
+                              hipStream_t stream);
+
 // ---- measurement aid ------------------------------------------------------------------------
 // Plain device copy of nbytes (multiple of 16; both pointers 16-byte aligned): what a 1:1 read/write stream reaches.
 hipError_t launch_probe_copy(const void *src, void *dst, size_t nbytes, hipStream_t stream, const LaunchEvents &ev = {});

@@ -79,6 +79,13 @@
 // device (canny_hip_dev_binarize) and thinned there with no download in between; without -a the finished edge map
 // (canny_hip_dev_canny_bits).  The skeleton (0 / 255) goes to canny_thin.pgm in the -o directory and "thin iterations D deleted
 // N" to stdout.  A malformed -v is a usage error (exit 2).  Without -v nothing changes.
+// Added: -R op[,connectivity[,thr]] reconstructs a bit map on the GPU (canny_hip_dev_reconstruct_bits): op fill (the holes of
+// the blobs filled), clear (the blobs that touch the frame border dropped) or seeded; connectivity 4 or 8 (default 8).  The map
+// is chosen as -v chooses it: with -a the binarized frame, binarized on the device, without -a the finished edge map
+// (canny_hip_dev_canny_bits).  seeded needs -a fixed,... and thr (-1..255): its marker is a second FIXED binarization of the
+// same plane at thr with the polarity of -a, so that -a fixed,lo -R seeded,8,hi is hysteresis thresholding of the gray plane,
+// all on the device.  The map (0 / 255) goes to canny_reconstruct.pgm in the -o directory and "reconstruct set N mask M start
+// S" to stdout.  A malformed -R, or seeded without -a fixed, is a usage error (exit 2).  Without -R nothing changes.
 // Added: -e computes the sub-pixel edgel of every pixel of the frame's edge map on the GPU (canny_hip_canny_edgels) and
 // writes one "x y gx gy mag dir refined" row per edge pixel, in raster order, to canny_edgels.txt in the -o directory
 // (stdout without -o): x and y in pixels to three decimals, mag in grey levels, dir 0..3 (step (1,0), (1,1), (0,1), (1,-1)),
@@ -771,6 +778,57 @@ static int run_thin(const vector<unsigned char> &frame, int height, int width, f
     return 0;
 }
 
+// -R: a bit map of the frame reconstructed on the device -> canny_reconstruct.pgm.  bin: the -a arguments (method, thr_or_c, kw,
+// kh, invert) or nullptr for the finished edge map; r: op, connectivity, thr of the marker (seeded)
+static int run_reconstruct(const vector<unsigned char> &frame, int height, int width, float sigma, int minVal, int maxVal,
+                           const int *bin, const int *r, const string &outdir)
+{
+    const size_t rb = ((size_t)width + 7) / 8, px = (size_t)height * width;
+    vector<unsigned char> bits(rb * height);
+    long long info[CANNY_HIP_RECON_INFO] = {0, 0, 0};
+    canny_hip_ctx *ctx = nullptr;
+    void *d_img = nullptr, *d_bits = nullptr, *d_marker = nullptr, *d_out = nullptr, *d_info = nullptr;
+    const bool seeded = r[0] == CANNY_HIP_RECON_SEEDED;
+    int st = canny_hip_ctx_create(&ctx, 0);
+    if (!st) st = canny_hip_malloc(ctx, &d_img, px);
+    if (!st) st = canny_hip_malloc(ctx, &d_bits, bits.size());
+    if (!st) st = canny_hip_malloc(ctx, &d_marker, bits.size());
+    if (!st) st = canny_hip_malloc(ctx, &d_out, bits.size());
+    if (!st) st = canny_hip_malloc(ctx, &d_info, sizeof(info));
+    if (!st) st = canny_hip_memcpy_h2d(ctx, d_img, frame.data(), px);
+    if (!st && bin)
+        st = canny_hip_dev_binarize(ctx, (const unsigned char *)d_img, 1, height, width, bin[0], bin[1], bin[2], bin[3], bin[4],
+                                    (unsigned char *)d_bits, nullptr, nullptr);
+    if (!st && !bin)
+        st = canny_hip_dev_canny_bits(ctx, (const unsigned char *)d_img, sigma, minVal, maxVal, height, width, 1, (unsigned char *)d_bits);
+    if (!st && seeded) // the marker: the same plane at the second threshold, the polarity of -a
+        st = canny_hip_dev_binarize(ctx, (const unsigned char *)d_img, 1, height, width, CANNY_HIP_BIN_FIXED, r[2], 3, 3, bin[4],
+                                    (unsigned char *)d_marker, nullptr, nullptr);
+    if (!st)
+        st = canny_hip_dev_reconstruct_bits(ctx, seeded ? (const unsigned char *)d_marker : nullptr, (const unsigned char *)d_bits, 1,
+                                            height, width, r[0], r[1], (unsigned char *)d_out, (long long *)d_info);
+    if (!st) st = canny_hip_memcpy_d2h(ctx, bits.data(), d_out, bits.size());
+    if (!st) st = canny_hip_memcpy_d2h(ctx, info, d_info, sizeof(info));
+    if (st) fprintf(stderr, "ERROR: -R: %s\n", st == CANNY_HIP_ERR_RUNTIME && ctx ? canny_hip_last_error(ctx) : canny_hip_status_string(st));
+    if (ctx) {
+        for (void *p : {d_img, d_bits, d_marker, d_out, d_info})
+            if (p) canny_hip_free(ctx, p);
+        canny_hip_ctx_destroy(ctx);
+    }
+    if (st) return 1;
+    printf("reconstruct set %lld mask %lld start %lld\n", info[0], info[1], info[2]);
+    vector<unsigned char> out(px);
+    for (int y = 0; y < height; y++)
+        for (int x = 0; x < width; x++)
+            out[(size_t)y * width + x] = (bits[(size_t)y * rb + (x >> 3)] >> (7 - (x & 7))) & 1 ? 255 : 0;
+    const string path = (outdir.empty() ? string(".") : outdir) + "/canny_reconstruct" + (png_output ? ".png" : ".pgm");
+    if (!write_frame(path, out.data(), height, width)) {
+        fprintf(stderr, "ERROR: cannot write %s\n", path.c_str());
+        return 1;
+    }
+    return 0;
+}
+
 // -r: the circles of the frame's edge map, "frame x y radius votes support" per circle; with -k (fit != nullptr: band,
 // trim_q8, options) also the circle fit of every circle, "frame cx cy r n rms maxd sectors trim_failed degenerate" per circle
 static int run_circles(const vector<unsigned char> &frame, int height, int width, float sigma, int minVal, int maxVal,
@@ -994,6 +1052,8 @@ int main(int argc, char *argv[])
     int bin_args[5] = {0, 127, 31, 31, 0}; // -a: method, thr_or_c, kw, kh, invert
     bool want_thin = false;
     int thin_args[2] = {CANNY_HIP_THIN_GUOHALL, 0}; // -v: method, max_iterations
+    bool want_recon = false, recon_thr_given = false;
+    int recon_args[3] = {CANNY_HIP_RECON_FILL_HOLES, 8, 0}; // -R: op, connectivity, thr of the marker (seeded)
     int width = WIDTH, height = HEIGHT;
     vector<string> values;
 
@@ -1261,6 +1321,40 @@ int main(int argc, char *argv[])
                 exit(2);
             }
             want_thin = true;
+        } else if (arg == "-R") {
+            // op[,connectivity[,thr]]: a word, 4 or 8, and for seeded a whole number -1..255; nothing empty, nothing behind it
+            static const char *const ops[] = {"seeded", "fill", "clear"};
+            vector<string> parts(1);
+            for (const char *p = i + 1 < argc ? argv[++i] : ""; *p; p++) {
+                if (*p == ',')
+                    parts.emplace_back();
+                else
+                    parts.back() += *p;
+            }
+            recon_args[0] = -1, recon_args[1] = 8, recon_thr_given = false;
+            for (int k = 0; k < 3; k++)
+                if (parts[0] == ops[k]) recon_args[0] = k;
+            bool clean = recon_args[0] >= 0 && parts.size() <= (recon_args[0] == CANNY_HIP_RECON_SEEDED ? 3u : 2u);
+            if (clean && parts.size() >= 2) {
+                clean = parts[1] == "4" || parts[1] == "8";
+                recon_args[1] = parts[1] == "4" ? 4 : 8;
+            }
+            if (clean && parts.size() == 3) {
+                const string &t = parts[2];
+                const size_t d = !t.empty() && t[0] == '-' ? 1 : 0;
+                clean = t.size() > d && t.size() <= d + 3;
+                for (size_t k = d; k < t.size(); k++) clean = clean && isdigit((unsigned char)t[k]);
+                if (clean) recon_args[2] = atoi(t.c_str());
+                clean = clean && recon_args[2] >= -1 && recon_args[2] <= 255;
+                recon_thr_given = clean;
+            }
+            if (clean && recon_args[0] == CANNY_HIP_RECON_SEEDED) clean = recon_thr_given;
+            if (!clean) {
+                fprintf(stderr, "ERROR: -R expects op[,connectivity[,thr]]: op fill, clear or seeded, connectivity 4 or 8, and for "
+                                "seeded (with -a fixed,...) the marker's threshold thr -1..255\n");
+                exit(2);
+            }
+            want_recon = true;
         } else if (arg == "-w" && i + 1 < argc) {
             char tail = 0; // a whole integer only
             if (sscanf(argv[++i], "%d%c", &curve_min_length, &tail) != 1) {
@@ -1302,6 +1396,10 @@ int main(int argc, char *argv[])
     }
     if (want_shapes && !want_contours) {
         fprintf(stderr, "ERROR: -u needs the contours of -t\n");
+        exit(2);
+    }
+    if (want_recon && recon_args[0] == CANNY_HIP_RECON_SEEDED && !(want_binarize && bin_args[0] == CANNY_HIP_BIN_FIXED)) {
+        fprintf(stderr, "ERROR: -R seeded needs -a fixed,...: its marker is the same plane binarized at thr\n");
         exit(2);
     }
     if (values.size() != 3) {
@@ -1351,6 +1449,9 @@ int main(int argc, char *argv[])
         fprintf(stderr, "       threshold, printed; mean: adaptive, offset c, window kw x kh odd 3..255; invert 0 or 1) -> canny_binary.pgm in the -o dir\n");
         fprintf(stderr, "   -v method[,max_iterations]: the edge map -- with -a the binarized frame, on the device -- thinned to a one-pixel\n");
         fprintf(stderr, "       skeleton (guohall or zhangsuen; 0..16384 iterations, 0: to the fixed point) -> canny_thin.pgm in the -o dir\n");
+        fprintf(stderr, "   -R op[,connectivity[,thr]]: the edge map -- with -a the binarized frame, on the device -- reconstructed: fill (holes\n");
+        fprintf(stderr, "       filled), clear (blobs at the frame border dropped) or seeded (with -a fixed,lo: the blobs that hold a pixel above\n");
+        fprintf(stderr, "       thr, hysteresis thresholding of the frame); connectivity 4 or 8 -> canny_reconstruct.pgm in the -o dir\n");
         fprintf(stderr, "   -d: distance of every pixel to the nearest edge pixel, min(255, floor) -> canny_dist.pgm in the -o dir\n");
         fprintf(stderr, "   -e: sub-pixel edgel of every edge pixel, one \"x y gx gy mag dir refined\" line each (x, y in pixels to three\n");
         fprintf(stderr, "       decimals, mag in grey levels, dir 0..3) -> canny_edgels.txt in the -o dir\n");
@@ -1442,6 +1543,11 @@ int main(int argc, char *argv[])
     }
     if (want_thin) {
         const int rc = run_thin(frame, height, width, sigma, minVal, maxVal, want_binarize ? bin_args : nullptr, thin_args, outdir);
+        if (rc) return rc;
+    }
+    if (want_recon) {
+        const int rc = run_reconstruct(frame, height, width, sigma, minVal, maxVal, want_binarize ? bin_args : nullptr, recon_args,
+                                       outdir);
         if (rc) return rc;
     }
     if (want_dist) {

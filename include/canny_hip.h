@@ -52,7 +52,8 @@
 extern "C" {
 #endif
 
-#define CANNY_HIP_VERSION 2600       /* 0.26.0: + thinning of packed bit maps to one-pixel skeletons */
+#define CANNY_HIP_VERSION 2700       /* 0.27.0: + morphological reconstruction of packed bit maps (seeded, fill holes, clear border) */
+/* 0.26.0: + thinning of packed bit maps to one-pixel skeletons */
 /* 0.25.0: + binarization: gray planes to packed bit maps (fixed, Otsu, adaptive) */
 /* 0.24.0: + binary morphology on packed bit maps */
 /* 0.23.0: + temporal fusion of aligned frames and change masks (0.22.0: + frame alignment) */
@@ -2432,6 +2433,87 @@ int canny_hip_thin_batch(canny_hip_ctx *ctx, const unsigned char *bits, int n_fr
 int canny_hip_thin_bits(const unsigned char *bits, int n_frames, int h, int w, int method, int max_iterations,
                         unsigned char *out_bits, long long *info);
 
+/* ---- morphological reconstruction of packed bit maps ---------------------------------------------------------------------------
+ * The connectivity-driven step that follows a threshold: keep the blobs that hold a seed (scipy.ndimage.binary_propagation,
+ * imreconstruct, cv::floodFill from many seeds), fill the holes of blobs (scipy.ndimage.binary_fill_holes, imfill 'holes'),
+ * drop the blobs that touch the frame border (skimage.segmentation.clear_border, imclearborder), and with two binarizations
+ * hysteresis thresholding of any plane (skimage.filters.apply_hysteresis_threshold) -- on the packed layout of
+ * canny_hip_dev_canny_bits, on the context's stream, without a download.  All three are ONE operator, reconstruction by
+ * dilation: a start set is flooded inside a set that conducts, to its fixed point.  All bit operations; the fixed point is
+ * unique: the same bytes on every run, route and machine.  tests/reconstruct_rule.py restates the rule in numpy,
+ * csrc/canny_reconstruct_host.cpp as a stack flood in plain C++.
+ * THE RULE:
+ *   Bit maps [n_frames][h][(w + 7) / 8] bytes, rows MSB-first.  THE PAD BITS OF THE INPUTS ARE IGNORED (a column >= w is
+ *     outside the frame), THE PAD BITS OF THE OUTPUT ARE WRITTEN 0, every output byte is written, EVERYTHING OUTSIDE THE
+ *     FRAME IS NOT PART OF ANY SET, frames never see each other.
+ *   M = the in-frame set of mask; B = the frame's border ring (row 0, row h-1, column 0, column w-1); c = connectivity, 4 or 8;
+ *     R_c(S, G) = the pixels of G joined to a pixel of S & G by a c-connected path that lies inside G.
+ *   CANNY_HIP_RECON_SEEDED = 0: out = R_c(marker, M) = scipy.ndimage.binary_propagation(marker & mask, structure_c, mask=mask).
+ *   CANNY_HIP_RECON_FILL_HOLES = 1: out = frame \ R_c'(B, frame \ M) with c' = 12 - c: THE BACKGROUND TAKES THE DUAL
+ *     CONNECTIVITY (foreground 8 <-> background 4) = scipy.ndimage.binary_fill_holes(mask, structure_c'); scipy's default is
+ *     c = 8 here.  marker must be NULL.
+ *   CANNY_HIP_RECON_CLEAR_BORDER = 2: out = M \ R_c(B, M).  marker must be NULL.
+ *   info may be NULL; otherwise CANNY_HIP_RECON_INFO = 3 long long per frame, 8-byte aligned: [0] the set bits of the output,
+ *     [1] the set bits of M, [2] the pixels of the start set: marker & M, resp. B \ M, resp. B & M.  Zeroed on the stream inside
+ *     the call, fully written by it and not touched by a refused one.  It deliberately holds NO launch or sweep count: the
+ *     bytes are the same on every run, route and machine, the number of launches that reach them is not.
+ *   Facts (tests/test_reconstruct_rule.py): out is a subset of M for SEEDED and CLEAR_BORDER, M a subset of out for
+ *     FILL_HOLES; all three are idempotent; SEEDED is monotone in the marker and returns M for marker = M; on the 96 x 160
+ *     scene of the thinning (a ring 8 thick and a bar 7 thick, 1735 pixels) FILL_HOLES at c = 8 gives 3248 pixels (1513
+ *     filled), SEEDED from the first set pixel keeps 427, CLEAR_BORDER keeps all 1735; the 7 x 7 diamond ring closed only by
+ *     diagonal steps fills 13 pixels at c = 8 and 0 at c = 4.
+ *   Limits: h, w in 1..32768, a plane < 2^31 pixels, at most 65535 frames; above: CANNY_HIP_ERR_UNSUPPORTED.  Bad enum values,
+ *     a connectivity other than 4 or 8, NULL mandatory pointers, a marker where none is allowed, a misaligned info buffer, an
+ *     output that overlaps marker, mask or info: CANNY_HIP_ERR_INVALID.  Both before anything is queued; nothing is written.
+ *   Kernels (csrc/canny_reconstruct.hip): the flood's state lives IN THE CALLER'S OUTPUT where its rows are whole 8-byte
+ *     aligned words, otherwise in a word-aligned copy in the context's thinning workspace.  An init kernel writes the start set,
+ *     sweep launches grow it in place, a finish kernel turns it into the op's output.  The state only grows and never beyond
+ *     the fixed point, so a workgroup that reads a neighbour's stale word is only delayed; words that another workgroup may
+ *     write are accessed with relaxed atomics on aligned 64-bit words.  The context option "reconstruct_route": 0 automatic
+ *     (the tile flood), 1 stepwise (a lane per word, one geodesic dilation step a launch through global memory: the
+ *     cross-check, hopeless on long paths), 2 tile flood (a workgroup of 256 per tile of 8 x 64-bit words x 64 rows of a grid
+ *     capped at 4096 floods the tile in LDS to its own fixed point behind a halo of one row and one word: per round
+ *     s |= n & g, then the horizontal fill within the word in six doubling steps each way, csrc/canny_recon_words.h).  Both
+ *     give the same bytes and the same info.  The waves that changed a word are counted per frame and launch on the device:
+ *     a workgroup that arrives at a frame whose preceding launch changed nothing returns at once; launches are queued in
+ *     chunks of 4, 8, 16, 32, then 64, and the host reads ONE word behind each chunk: the frames that still changed.
+ *     THE CALLS THEREFORE SYNCHRONISE THE STREAM BEFORE THEY RETURN.  The read-only option "last_reconstruct_launches"
+ *     answers the sweep launches the context's last call queued (0 on a fresh context): a diagnostic, run-dependent and not
+ *     part of the result.
+ *   Measured on an MI355X at 128 x 4K, c = 8: FILL_HOLES of Otsu-binarized frames 10.7 ms (28 launches),
+ *     CLEAR_BORDER 12.4 ms, SEEDED on the strong plane 2.0 ms, on blobs 4.2 ms; the stepwise route 630, 590, 21.7 and 24.9 ms;
+ *     canny_hip_dev_components_bits on the same masks 23.5, 5.7 and 54.9 ms.  A launch runs every tile once, so a path that
+ *     winds through t tile borders takes up to t launches: a full-frame zigzag took 59,964 launches and 15 s, where the label
+ *     pass takes 0.6 s -- ON SERPENTINE MAPS A LABEL PASS (canny_hip_dev_components_bits and a decision per label) IS FASTER.
+ * Not covered -- follow-ups: grey-level reconstruction (h-maxima, imregionalmax); per-tile dirty stamps, so that a sweep visits
+ * only tiles whose neighbourhood changed; a label-based route (run union-find, flag the roots that hold a seed) for serpentine
+ * maps; an asynchronous form with a launch budget; reconstruction through the batch pipeline or the multi-GPU sharder. */
+#define CANNY_HIP_RECON_INFO 3 /* long long per frame */
+enum canny_hip_recon_op {
+    CANNY_HIP_RECON_SEEDED = 0,
+    CANNY_HIP_RECON_FILL_HOLES = 1,
+    CANNY_HIP_RECON_CLEAR_BORDER = 2
+};
+enum canny_hip_recon_part {
+    CANNY_HIP_RECON_PART_SWEEPS = 0, /* all sweep launches of a call (with the polls between its chunks) */
+    CANNY_HIP_RECON_PART_INFO = 1,   /* the zeroing, the init and the finish kernels and the reduction to info */
+    CANNY_HIP_RECON_PARTS = 2
+};
+/* d_marker (SEEDED; NULL otherwise), d_mask, d_out: n_frames * h * ((w + 7) / 8) bytes, any byte address; d_info:
+ * 3 * n_frames long long or NULL.  On the context's stream; THE CALL SYNCHRONISES THE STREAM BEFORE IT RETURNS. */
+int canny_hip_dev_reconstruct_bits(canny_hip_ctx *ctx, const unsigned char *d_marker, const unsigned char *d_mask, int n_frames,
+                                   int h, int w, int op, int connectivity, unsigned char *d_out, long long *d_info);
+/* The same with the strong bit-plane that the preceding dev_canny of the same n_frames, h, w left in the context as the mask
+ * (another geometry, or none yet: CANNY_HIP_ERR_INVALID; the plane is only read). */
+int canny_hip_dev_canny_reconstruct(canny_hip_ctx *ctx, const unsigned char *d_marker, int n_frames, int h, int w, int op,
+                                    int connectivity, unsigned char *d_out, long long *d_info);
+/* Host buffers, synchronous: upload, the operator; only out and, if not NULL, info come down. */
+int canny_hip_reconstruct_batch(canny_hip_ctx *ctx, const unsigned char *marker, const unsigned char *mask, int n_frames, int h,
+                                int w, int op, int connectivity, unsigned char *out, long long *info);
+/* Host-only, needs no device: the rule itself on host buffers, a stack flood. */
+int canny_hip_reconstruct_bits(const unsigned char *marker, const unsigned char *mask, int n_frames, int h, int w, int op,
+                               int connectivity, unsigned char *out, long long *info);
+
 /* ---- per-stage HIP-event timing (events are recorded on the launch stream) ----------------- */
 int canny_hip_profile_enable(canny_hip_ctx *ctx, int on);
 int canny_hip_profile_reset(canny_hip_ctx *ctx);
@@ -2479,8 +2561,8 @@ int canny_hip_morph_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, 
 /* Every group of parts by name, for this and later features: feature is "stages" (the canny stages of
  * canny_hip_profile_get), "hough", "components", "edt", "hough_segments", "contours", "hough_circles", "polygons", "edgels",
  * "line_fits", "circle_fits", "chamfer", "shapes", "curves", "corners", "descriptors", "motion", "warp", "fuse", "morph",
- * "binarize" (CANNY_HIP_BIN_PART_*) or "thin" (CANNY_HIP_THIN_PART_*; both have no named getter and follow bit 30 of
- * "profile_stage_mask" like the others); the answer is the named getter's.  An
+ * "binarize" (CANNY_HIP_BIN_PART_*), "thin" (CANNY_HIP_THIN_PART_*) or "reconstruct" (CANNY_HIP_RECON_PART_*; the three have no
+ * named getter and follow bit 30 of "profile_stage_mask" like the others); the answer is the named getter's.  An
  * unknown name, a part the group does not have or a NULL: CANNY_HIP_ERR_INVALID, nothing is written. */
 int canny_hip_profile_part_get(canny_hip_ctx *ctx, const char *feature, int part, double *total_ms, long *launches);
 
@@ -2687,6 +2769,11 @@ int canny_hip_selftest_binarize_plan(int n_frames, int h, int w, int method, int
  * workgroups.  fuse: 0, or the "thin_fuse" to report (1..8).  The fifth word is the number of full iterations a launch runs:
  * fuse, or for fuse = 0 what automatic takes (0 if automatic is the stepwise route).  It refuses what the calls refuse. */
 int canny_hip_selftest_thin_plan(int n_frames, int h, int w, int fuse, unsigned long long *out);
+/* Host-only, the same five outputs for the sweep launches of the reconstruction (no kind above).  route 2, and 0 where
+ * automatic takes the tile flood: items = n_frames * ceil(h / 64) * ceil(ceil(w / 64) / 8) tiles, one per workgroup of 256 and
+ * trip; route 1: items = n_frames * h * ceil(w / 64) words, 256 per workgroup and trip (also the plan of the init and finish
+ * kernels); at most 4096 workgroups.  The fifth word is the route automatic takes (1 or 2).  It refuses what the calls refuse. */
+int canny_hip_selftest_reconstruct_plan(int n_frames, int h, int w, int route, unsigned long long *out);
 /* Runs the fuse kernels' own device helper for the rounded mean over every pair c = 1..255, s = 0..255 c, and writes the
  * bytes to host memory as a table [255][CANNY_HIP_FUSE_MEAN_ROW]: out[(c - 1) * 65026 + s]; unused cells are 0. */
 int canny_hip_selftest_fuse_mean(canny_hip_ctx *ctx, unsigned char *out);
