@@ -153,6 +153,7 @@ EXPORTS = (
     "canny_hip_selftest_thin_plan",
     "canny_hip_dev_reconstruct_bits", "canny_hip_dev_canny_reconstruct", "canny_hip_reconstruct_batch",
     "canny_hip_reconstruct_bits", "canny_hip_selftest_reconstruct_plan",
+    "canny_hip_dev_gray_morph", "canny_hip_gray_morph_batch", "canny_hip_gray_morph", "canny_hip_selftest_gray_morph_plan",
 )
 
 _lib: Optional[C.CDLL] = None
@@ -442,6 +443,10 @@ def load() -> C.CDLL:
         "canny_hip_reconstruct_batch": ([p, p, p, i, i, i, i, i, p, p], i),
         "canny_hip_reconstruct_bits": ([p, p, i, i, i, i, i, p, p], i),
         "canny_hip_selftest_reconstruct_plan": ([i, i, i, i, p], i),
+        "canny_hip_dev_gray_morph": ([p, p, i, i, i, i, p, i, i, i, i, i, p], i),
+        "canny_hip_gray_morph_batch": ([p, p, i, i, i, i, p, i, i, i, i, i, p], i),
+        "canny_hip_gray_morph": ([p, i, i, i, i, p, i, i, i, i, i, p], i),
+        "canny_hip_selftest_gray_morph_plan": ([i, i, i, i, i, i, p], i),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -1411,6 +1416,41 @@ def reconstruct_plan(n_frames: int, h: int, w: int, route: int = 0):
     """Host-only: the LaunchPlan of the sweep launches of a reconstruction call (route 2: one tile of 8 words x 64 rows per
     workgroup and trip; route 1: 256 words); aux = the route automatic takes."""
     return _plan("reconstruct_plan", int(n_frames), int(h), int(w), int(route))
+
+
+# ---- grey-level morphology and median filtering of u8 planes (DESIGN.md section 39) ----------------------------------------
+(GRAY_ERODE, GRAY_DILATE, GRAY_OPEN, GRAY_CLOSE, GRAY_GRADIENT, GRAY_TOPHAT, GRAY_BLACKHAT, GRAY_MEDIAN) = range(8)
+GRAY_OPS = MORPH_OPS + ("median",)
+GRAY_BORDER_NEUTRAL, GRAY_BORDER_REPLICATE, GRAY_BORDER_CONSTANT = 0, 1, 2
+GRAY_BORDERS = ("neutral", "replicate", "constant")
+GRAY_ROUTE_AUTO, GRAY_ROUTE_GENERAL, GRAY_ROUTE_FAST = 0, 1, 2
+GRAY_PARTS = ("steps",)
+
+
+def _gray_planes(imgs):
+    a = np.ascontiguousarray(imgs, dtype=np.uint8)
+    if a.ndim != 3:
+        raise ValueError("expected uint8 [n_frames, H, W]")
+    return a
+
+
+def gray_morph(imgs, op: int, rows, kw: int, kh: int, border_mode: int = GRAY_BORDER_NEUTRAL, border_value: int = 0,
+               iterations: int = 1):
+    """Host-only, needs no GPU: the grey-level operator on planes uint8 [n_frames, H, W] -> planes of the same shape.  The
+    element is the binary morphology's (morph_element); GRAY_MEDIAN takes the full 3 x 3 or 5 x 5 rectangle."""
+    a = _gray_planes(imgs)
+    n, h, w = a.shape
+    r = _morph_rows(rows, kh)
+    out = np.zeros_like(a)
+    _ok(load().canny_hip_gray_morph(_hp(a), n, h, w, int(op), _hp(r), int(kw), int(kh), int(border_mode), int(border_value),
+                                    int(iterations), _hp(out)), "gray_morph")
+    return out
+
+
+def gray_morph_plan(n_frames: int, h: int, w: int, op: int = GRAY_ERODE, kw: int = 3, kh: int = 3):
+    """Host-only: the LaunchPlan of one primitive step of the grey-level morphology (one tile of 128 columns x 32 rows per
+    workgroup and trip); aux = the route automatic takes for op with a full rectangle of kw x kh (1 general, 2 fast)."""
+    return _plan("gray_morph_plan", int(n_frames), int(h), int(w), int(op), int(kw), int(kh))
 
 
 # ---- chamfer template matching (DESIGN.md section 26) --------------------------------------------------------------------
@@ -3010,6 +3050,29 @@ class Context:
         self._check(self._L.canny_hip_reconstruct_batch(self._h, None if k is None else _hp(k), _hp(m), n, h, int(w), int(op),
                                                         int(connectivity), _hp(out), _hp(info)), "reconstruct_batch")
         return out, info
+
+    # ---- grey-level morphology and median filtering of u8 planes -----------------------------------
+    def dev_gray_morph(self, d_plane: int, n_frames: int, h: int, w: int, op: int, rows, kw: int, kh: int, d_out: int,
+                       border_mode: int = GRAY_BORDER_NEUTRAL, border_value: int = 0, iterations: int = 1):
+        """The grey-level operator on device planes uint8 [n_frames][h][w] (d_plane 0: the smoothed plane the preceding
+        dev_canny of the same geometry left in the context) into d_out of the same size.  Asynchronous."""
+        v = C.c_void_p
+        r = _morph_rows(rows, kh)
+        self._check(self._L.canny_hip_dev_gray_morph(self._h, v(d_plane or None), n_frames, h, w, int(op), _hp(r), kw, kh,
+                                                     int(border_mode), int(border_value), int(iterations), v(d_out or None)),
+                    "dev_gray_morph")
+
+    def gray_morph_batch(self, imgs, op: int, rows, kw: int, kh: int, border_mode: int = GRAY_BORDER_NEUTRAL,
+                         border_value: int = 0, iterations: int = 1):
+        """Upload, the grey-level operator on the GPU and download: imgs (N, H, W) uint8 -> planes of the same shape."""
+        a = _gray_planes(imgs)
+        n, h, w = a.shape
+        r = _morph_rows(rows, kh)
+        out = np.zeros_like(a)
+        self._check(self._L.canny_hip_gray_morph_batch(self._h, _hp(a), n, h, w, int(op), _hp(r), int(kw), int(kh),
+                                                       int(border_mode), int(border_value), int(iterations), _hp(out)),
+                    "gray_morph_batch")
+        return out
 
     def profile_part(self, feature: str, part: int) -> Tuple[float, int]:
         """(total ms, launch groups) of part `part` of the named group of the profile table ("stages", "hough", ..., "morph",

@@ -353,6 +353,7 @@ constexpr ProfGroup kProfGroups[] = {
     {"binarize", CANNY_HIP_BIN_PARTS},
     {"thin", CANNY_HIP_THIN_PARTS},
     {"reconstruct", CANNY_HIP_RECON_PARTS},
+    {"gray_morph", CANNY_HIP_GRAY_PARTS},
 };
 
 // The first slot of the named group; with no name, the number of slots.  A name the table does not hold fails to compile.
@@ -414,7 +415,8 @@ struct Workspaces {
     DevBuf desc_ws;
     // motion estimate: the compacted correspondences and their slots, the inlier counts per (pair, hypothesis), m, the pairs
     DevBuf motion_ws;
-    // binary morphology: the two intermediate bit maps of a call of more than one primitive step, back to back
+    // binary morphology: the two intermediate bit maps of a call of more than one primitive step, back to back; grey-level
+    // morphology: its two intermediate u8 planes, the same way (every call sizes and writes what it reads)
     DevBuf morph_ws;
     // binarization: the histograms of the frames (OTSU) | the threshold of every frame
     DevBuf binarize_ws;
@@ -544,6 +546,7 @@ struct canny_hip_ctx : Workspaces {
     int thin_route = 0, thin_fuse = 0; // 0 auto, 1 stepwise, 2 fused; 0 auto, 1..8 full iterations a fused launch
     int reconstruct_route = 0;         // 0 auto, 1 stepwise, 2 tile flood
     int last_reconstruct_launches = 0; // the sweep launches the last reconstruction call queued: a diagnostic
+    int gray_morph_route = 0;          // 0 auto, 1 general, 2 fast (full rectangles separably, the median by a network)
     std::vector<int> motion_pairs; // the validated pairs of the last motion call: what its upload reads
     DevBuf io[4];     // staging for the host-pointer stage functions
     std::string ws_name; // canny_hip_selftest_workspace: the name it handed out last
@@ -578,7 +581,7 @@ struct canny_hip_ctx : Workspaces {
                          kProfDescriptors = prof_base("descriptors"), kProfMotion = prof_base("motion"),
                          kProfWarp = prof_base("warp"), kProfFuse = prof_base("fuse"), kProfMorph = prof_base("morph"),
                          kProfBinarize = prof_base("binarize"), kProfThin = prof_base("thin"),
-                         kProfReconstruct = prof_base("reconstruct");
+                         kProfReconstruct = prof_base("reconstruct"), kProfGrayMorph = prof_base("gray_morph");
     static constexpr int kProfSlots = prof_base(nullptr);
     // "profile_stage_mask" is a non-negative int option: bit 30 is the last it can carry
     static constexpr int kProfLastBit = 30;
@@ -632,6 +635,7 @@ constexpr OptRow kOptions[] = {
     {"thin_fuse", &canny_hip_ctx::thin_fuse, 0, 8, true, true},
     {"reconstruct_route", &canny_hip_ctx::reconstruct_route, 0, 2, true, true},
     {"last_reconstruct_launches", &canny_hip_ctx::last_reconstruct_launches, 0, 0, true, false},
+    {"gray_morph_route", &canny_hip_ctx::gray_morph_route, 0, 2, true, true},
 };
 
 } // namespace
@@ -7029,6 +7033,104 @@ int canny_hip_selftest_thin_plan(int n_frames, int h, int w, int fuse, unsigned 
     if (rc) return rc;
     store_plan(out, plan_thin_tiles(n_frames, h, w));
     out[4] = (unsigned long long)(fuse ? fuse : thin_auto_fuse()); // aux: the full iterations a launch runs
+    return CANNY_HIP_OK;
+}
+
+// ---- grey-level morphology and median filtering of u8 planes (canny_gray_morph.hip) ------------------
+// canny_hip_gray_morph, the rule in plain C++, lives in canny_gray_morph_host.cpp.
+
+namespace {
+// every check of the grey-level morphology but the pointers and the overlaps
+int gray_morph_check(int n_frames, int h, int w, int op, const unsigned *rows, int kw, int kh, int border_mode, int border_value,
+                     int iterations)
+{
+    if (op < CANNY_HIP_GRAY_ERODE || op > CANNY_HIP_GRAY_MEDIAN || border_mode < CANNY_HIP_GRAY_BORDER_NEUTRAL ||
+        border_mode > CANNY_HIP_GRAY_BORDER_CONSTANT ||
+        (border_mode == CANNY_HIP_GRAY_BORDER_CONSTANT && (border_value < 0 || border_value > 255)))
+        return CANNY_HIP_ERR_INVALID;
+    // the element, the iterations and the limits: the binary morphology's own checks
+    const int rc = morph_check(n_frames, h, w, CANNY_HIP_MORPH_ERODE, rows, kw, kh, CANNY_HIP_MORPH_BORDER_NEUTRAL, iterations);
+    if (rc == CANNY_HIP_ERR_INVALID) return rc;
+    if (op == CANNY_HIP_GRAY_MEDIAN) {
+        if (kw != kh || (kw != 3 && kw != 5) || border_mode == CANNY_HIP_GRAY_BORDER_NEUTRAL) return CANNY_HIP_ERR_INVALID;
+        for (int j = 0; j < kh; j++)
+            if (rows[j] != (1u << kw) - 1u) return CANNY_HIP_ERR_INVALID;
+    }
+    return rc;
+}
+
+// The operator queued on the context's stream; everything has been checked.
+int dev_gray_morph(canny_hip_ctx *ctx, const void *plane, bool plane_u8, int n_frames, int h, int w, int op, const unsigned *rows,
+                   int kw, int kh, int border_mode, int border_value, int iterations, unsigned char *d_out)
+{
+    const size_t bytes = npx(h, w, n_frames), slot = (bytes + 15) & ~(size_t)15;
+    const bool single = op <= CANNY_HIP_GRAY_DILATE || op == CANNY_HIP_GRAY_MEDIAN;
+    const int n_steps = (single ? 1 : 2) * iterations;
+    uint8_t *ws_a = nullptr, *ws_b = nullptr;
+    if (n_steps > 1) {
+        HIP_TRY(ctx, ctx->morph_ws.ensure(2 * slot)); // shared with the binary morphology: no call reads what another left
+        ws_a = (uint8_t *)ctx->morph_ws.p, ws_b = ws_a + slot;
+    }
+    StageTimer tm(ctx, canny_hip_ctx::kProfGrayMorph + CANNY_HIP_GRAY_PART_STEPS);
+    HIP_TRY(ctx, launch_gray_morph(plane, !plane_u8, n_frames, h, w, op, rows, kw, kh, border_mode, border_value, iterations,
+                                   ctx->gray_morph_route, ws_a, ws_b, d_out, ctx->stream));
+    return CANNY_HIP_OK;
+}
+} // namespace
+
+int canny_hip_dev_gray_morph(canny_hip_ctx *ctx, const unsigned char *d_plane, int n_frames, int h, int w, int op,
+                             const unsigned *rows, int kw, int kh, int border_mode, int border_value, int iterations,
+                             unsigned char *d_out)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!d_out) return CANNY_HIP_ERR_INVALID;
+    if ((rc = gray_morph_check(n_frames, h, w, op, rows, kw, kh, border_mode, border_value, iterations))) return rc;
+    const void *plane = d_plane;
+    bool plane_u8 = true;
+    if (!d_plane) {
+        // the plane the last canny call left: only for the batch it belongs to
+        if (!last_canny_was(ctx, n_frames, h, w) || !ctx->smoothed.p) return CANNY_HIP_ERR_INVALID;
+        plane = ctx->smoothed.p;
+        plane_u8 = ctx->last_canny_u8 != 0;
+    }
+    const size_t bytes = npx(h, w, n_frames);
+    if (ranges_overlap(plane, bytes * (plane_u8 ? 1 : 2), d_out, bytes)) return CANNY_HIP_ERR_INVALID;
+    if ((rc = finish_pending(ctx))) return rc;
+    return dev_gray_morph(ctx, plane, plane_u8, n_frames, h, w, op, rows, kw, kh, border_mode, border_value, iterations, d_out);
+}
+
+int canny_hip_gray_morph_batch(canny_hip_ctx *ctx, const unsigned char *imgs, int n_frames, int h, int w, int op,
+                               const unsigned *rows, int kw, int kh, int border_mode, int border_value, int iterations,
+                               unsigned char *out)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!imgs || !out) return CANNY_HIP_ERR_INVALID;
+    if ((rc = gray_morph_check(n_frames, h, w, op, rows, kw, kh, border_mode, border_value, iterations))) return rc;
+    const size_t bytes = npx(h, w, n_frames);
+    if (ranges_overlap(imgs, bytes, out, bytes)) return CANNY_HIP_ERR_INVALID;
+    if ((rc = finish_pending(ctx))) return rc;
+    if ((rc = h2d(ctx, ctx->io[0], imgs, bytes))) return rc;
+    HIP_TRY(ctx, ctx->io[1].ensure(bytes));
+    if ((rc = dev_gray_morph(ctx, ctx->io[0].p, true, n_frames, h, w, op, rows, kw, kh, border_mode, border_value, iterations,
+                             (unsigned char *)ctx->io[1].p)))
+        return rc;
+    return d2h_sync(ctx, out, ctx->io[1].p, bytes);
+}
+
+// Host-only: the launch plan of one primitive step and the route automatic takes for op with a full rectangle of kw x kh.
+int canny_hip_selftest_gray_morph_plan(int n_frames, int h, int w, int op, int kw, int kh, unsigned long long *out)
+{
+    if (!out) return CANNY_HIP_ERR_INVALID;
+    if (op < CANNY_HIP_GRAY_ERODE || op > CANNY_HIP_GRAY_MEDIAN || kw < 1 || kw > CANNY_HIP_MORPH_MAX_EXTENT || kh < 1 ||
+        kh > CANNY_HIP_MORPH_MAX_EXTENT || !(kw & 1) || !(kh & 1) ||
+        (op == CANNY_HIP_GRAY_MEDIAN && (kw != kh || (kw != 3 && kw != 5))))
+        return CANNY_HIP_ERR_INVALID;
+    const int rc = fuse_stack_check(n_frames, h, w);
+    if (rc) return rc;
+    store_plan(out, plan_gray_morph_tiles(n_frames, h, w));
+    out[4] = (unsigned long long)gray_morph_auto_route(op, kw, kh); // the route, not aux
     return CANNY_HIP_OK;
 }
 

@@ -929,6 +929,20 @@ hipError_t launch_reconstruct(int phase, const uint8_t *marker, const void *mask
                               int op, int connectivity, int route, void *ws, uint8_t *out, long long *info, int *launches,
                               hipStream_t stream);
 
+// ---- grey-level morphology and median filtering of u8 planes (canny_gray_morph.hip) ---------
+// One primitive step is one launch over the n_frames * ceil(h / 32) * ceil(w / 128) tiles of 128 columns x 32 rows, one per
+// workgroup and trip.  (Reported by canny_hip_selftest_gray_morph_plan, not by a kind.)
+LaunchPlan plan_gray_morph_tiles(int n_frames, int h, int w);
+// The route automatic takes for op (the header's enum) with a full rectangle of kw x kh: 1 general, 2 fast.
+int gray_morph_auto_route(int op, int kw, int kh);
+// Every byte of out [n_frames][h][w].  src: a plane of bytes or -- src_s16 -- of shorts in [0, 255].  op, border_mode: the
+// header's enums; rows[kh]: host memory, read before the call returns; route: 0 automatic, 1 general, 2 fast (full rectangles
+// and the median).  ws_a, ws_b: two planes of out's size for the intermediates of more than one (ws_a) or two (ws_b)
+// primitive steps; out itself holds intermediates of GRADIENT.
+hipError_t launch_gray_morph(const void *src, bool src_s16, int n_frames, int h, int w, int op, const unsigned *rows, int kw,
+                             int kh, int border_mode, int border_value, int iterations, int route, uint8_t *ws_a, uint8_t *ws_b,
+                             uint8_t *out, hipStream_t stream);
+
 // ---- measurement aid ------------------------------------------------------------------------
 // Plain device copy of nbytes (multiple of 16; both pointers 16-byte aligned): what a 1:1 read/write stream reaches.
 hipError_t launch_probe_copy(const void *src, void *dst, size_t nbytes, hipStream_t stream, const LaunchEvents &ev = {});

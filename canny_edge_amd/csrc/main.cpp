@@ -86,6 +86,12 @@
 // same plane at thr with the polarity of -a, so that -a fixed,lo -R seeded,8,hi is hysteresis thresholding of the gray plane,
 // all on the device.  The map (0 / 255) goes to canny_reconstruct.pgm in the -o directory and "reconstruct set N mask M start
 // S" to stdout.  A malformed -R, or seeded without -a fixed, is a usage error (exit 2).  Without -R nothing changes.
+// Added: -G op,kw[,kh[,shape[,iterations[,border]]]] applies a grey-level operator to the input frame itself on the GPU
+// (canny_hip_dev_gray_morph): op is a word of -z or median; kw, kh, shape and iterations as in -z (median: 3 or 5, square,
+// rect); border neutral (the default; not for median, whose default is replicate), replicate or a constant 0..255.  The plane
+// goes to canny_gray.pgm in the -o directory; with -a also given, the binarization of THAT plane, binarized on the device with
+// no download in between, goes to canny_gray_binary.pgm (canny_binary.pgm stays the binarization of the input frame).  A
+// malformed -G is a usage error (exit 2).  Without -G nothing changes.
 // Added: -e computes the sub-pixel edgel of every pixel of the frame's edge map on the GPU (canny_hip_canny_edgels) and
 // writes one "x y gx gy mag dir refined" row per edge pixel, in raster order, to canny_edgels.txt in the -o directory
 // (stdout without -o): x and y in pixels to three decimals, mag in grey levels, dir 0..3 (step (1,0), (1,1), (0,1), (1,-1)),
@@ -732,6 +738,56 @@ static int run_binarize(const vector<unsigned char> &frame, int height, int widt
     return 0;
 }
 
+// -G: a grey-level operator on the frame -> canny_gray.pgm and, with bin (the -a arguments), the binarization of that plane ->
+// canny_gray_binary.pgm.  g: op, kw, kh, shape, iterations, border_mode, border_value
+static int run_gray_morph(const vector<unsigned char> &frame, int height, int width, const int *g, const int *bin, const string &outdir)
+{
+    const size_t rb = ((size_t)width + 7) / 8, px = (size_t)height * width;
+    vector<unsigned char> plane(px), bits(rb * height);
+    unsigned rows[CANNY_HIP_MORPH_MAX_EXTENT];
+    int thr = 0;
+    canny_hip_ctx *ctx = nullptr;
+    void *d_img = nullptr, *d_out = nullptr, *d_bits = nullptr, *d_thr = nullptr;
+    int st = canny_hip_morph_element(g[3], g[1], g[2], rows);
+    if (!st) st = canny_hip_ctx_create(&ctx, 0);
+    if (!st) st = canny_hip_malloc(ctx, &d_img, px);
+    if (!st) st = canny_hip_malloc(ctx, &d_out, px);
+    if (!st && bin) st = canny_hip_malloc(ctx, &d_bits, bits.size());
+    if (!st && bin) st = canny_hip_malloc(ctx, &d_thr, sizeof(int));
+    if (!st) st = canny_hip_memcpy_h2d(ctx, d_img, frame.data(), px);
+    if (!st)
+        st = canny_hip_dev_gray_morph(ctx, (const unsigned char *)d_img, 1, height, width, g[0], rows, g[1], g[2], g[5], g[6], g[4],
+                                      (unsigned char *)d_out);
+    if (!st && bin)
+        st = canny_hip_dev_binarize(ctx, (const unsigned char *)d_out, 1, height, width, bin[0], bin[1], bin[2], bin[3], bin[4],
+                                    (unsigned char *)d_bits, nullptr, (int *)d_thr);
+    if (!st) st = canny_hip_memcpy_d2h(ctx, plane.data(), d_out, px);
+    if (!st && bin) st = canny_hip_memcpy_d2h(ctx, bits.data(), d_bits, bits.size());
+    if (!st && bin) st = canny_hip_memcpy_d2h(ctx, &thr, d_thr, sizeof(int));
+    if (st) fprintf(stderr, "ERROR: -G: %s\n", st == CANNY_HIP_ERR_RUNTIME && ctx ? canny_hip_last_error(ctx) : canny_hip_status_string(st));
+    if (ctx) {
+        for (void *p : {d_img, d_out, d_bits, d_thr})
+            if (p) canny_hip_free(ctx, p);
+        canny_hip_ctx_destroy(ctx);
+    }
+    if (st) return 1;
+    const string dir = outdir.empty() ? string(".") : outdir, ext = png_output ? ".png" : ".pgm";
+    if (!write_frame(dir + "/canny_gray" + ext, plane.data(), height, width)) {
+        fprintf(stderr, "ERROR: cannot write %s\n", (dir + "/canny_gray" + ext).c_str());
+        return 1;
+    }
+    if (!bin) return 0;
+    if (bin[0] == CANNY_HIP_BIN_OTSU) printf("gray otsu threshold %d\n", thr);
+    for (int y = 0; y < height; y++)
+        for (int x = 0; x < width; x++)
+            plane[(size_t)y * width + x] = (bits[(size_t)y * rb + (x >> 3)] >> (7 - (x & 7))) & 1 ? 255 : 0;
+    if (!write_frame(dir + "/canny_gray_binary" + ext, plane.data(), height, width)) {
+        fprintf(stderr, "ERROR: cannot write %s\n", (dir + "/canny_gray_binary" + ext).c_str());
+        return 1;
+    }
+    return 0;
+}
+
 // -v: a bit map of the frame thinned on the device -> canny_thin.pgm.  bin: the -a arguments (method, thr_or_c, kw, kh, invert)
 // or nullptr for the finished edge map; v: method, max_iterations
 static int run_thin(const vector<unsigned char> &frame, int height, int width, float sigma, int minVal, int maxVal, const int *bin,
@@ -1048,6 +1104,8 @@ int main(int argc, char *argv[])
     int desc_options = -1;                 // -j: -1 absent, 0 upright, CANNY_HIP_DESC_STEERED
     bool want_morph = false;
     int morph_args[5] = {0, 3, 3, 0, 1};   // -z: op, kw, kh, shape, iterations
+    bool want_gray = false;
+    int gray_args[7] = {0, 3, 3, 0, 1, 0, 0}; // -G: op, kw, kh, shape, iterations, border_mode, border_value
     bool want_binarize = false;
     int bin_args[5] = {0, 127, 31, 31, 0}; // -a: method, thr_or_c, kw, kh, invert
     bool want_thin = false;
@@ -1265,6 +1323,62 @@ int main(int argc, char *argv[])
                 exit(2);
             }
             want_morph = true;
+        } else if (arg == "-G") {
+            // op,kw[,kh[,shape[,iterations[,border]]]]: words and whole integers, nothing empty, nothing behind the last one
+            static const char *const ops[] = {"erode", "dilate", "open", "close", "gradient", "tophat", "blackhat", "median"};
+            static const char *const shapes[] = {"rect", "cross", "ellipse"};
+            vector<string> parts(1);
+            for (const char *p = i + 1 < argc ? argv[++i] : ""; *p; p++) {
+                if (*p == ',')
+                    parts.emplace_back();
+                else
+                    parts.back() += *p;
+            }
+            auto word = [](const string &w, const char *const *names, int n) {
+                for (int k = 0; k < n; k++)
+                    if (w == names[k]) return k;
+                return -1;
+            };
+            auto number = [](const string &w, size_t digits) { // from digits alone, else -1
+                if (w.empty() || w.size() > digits) return -1;
+                for (char c : w)
+                    if (!isdigit((unsigned char)c)) return -1;
+                return atoi(w.c_str());
+            };
+            bool clean = parts.size() >= 2 && parts.size() <= 6;
+            if (clean) {
+                gray_args[0] = word(parts[0], ops, 8);
+                const bool median = gray_args[0] == CANNY_HIP_GRAY_MEDIAN;
+                gray_args[1] = number(parts[1], 2);
+                gray_args[2] = parts.size() > 2 ? number(parts[2], 2) : gray_args[1];
+                gray_args[3] = parts.size() > 3 ? word(parts[3], shapes, 3) : CANNY_HIP_MORPH_RECT;
+                gray_args[4] = parts.size() > 4 ? number(parts[4], 2) : 1;
+                gray_args[5] = median ? CANNY_HIP_GRAY_BORDER_REPLICATE : CANNY_HIP_GRAY_BORDER_NEUTRAL, gray_args[6] = 0;
+                if (parts.size() > 5) {
+                    if (parts[5] == "neutral") {
+                        gray_args[5] = CANNY_HIP_GRAY_BORDER_NEUTRAL;
+                    } else if (parts[5] == "replicate") {
+                        gray_args[5] = CANNY_HIP_GRAY_BORDER_REPLICATE;
+                    } else {
+                        gray_args[5] = CANNY_HIP_GRAY_BORDER_CONSTANT, gray_args[6] = number(parts[5], 3);
+                        clean = gray_args[6] >= 0 && gray_args[6] <= 255;
+                    }
+                }
+                for (int k = 1; k <= 2; k++)
+                    clean = clean && gray_args[k] >= 1 && gray_args[k] <= CANNY_HIP_MORPH_MAX_EXTENT && (gray_args[k] & 1);
+                clean = clean && gray_args[0] >= 0 && gray_args[3] >= 0 && gray_args[4] >= 1 &&
+                        gray_args[4] <= CANNY_HIP_MORPH_MAX_ITERATIONS;
+                if (median)
+                    clean = clean && (gray_args[1] == 3 || gray_args[1] == 5) && gray_args[2] == gray_args[1] &&
+                            gray_args[3] == CANNY_HIP_MORPH_RECT && gray_args[5] != CANNY_HIP_GRAY_BORDER_NEUTRAL;
+            }
+            if (!clean) {
+                fprintf(stderr, "ERROR: -G expects op,kw[,kh[,shape[,iterations[,border]]]]: op erode, dilate, open, close, gradient, "
+                                "tophat, blackhat or median, kw and kh odd in 1..31 (median: 3 or 5, square, rect), shape rect, cross "
+                                "or ellipse, iterations 1..16, border neutral (not for median), replicate or 0..255\n");
+                exit(2);
+            }
+            want_gray = true;
         } else if (arg == "-a") {
             // method[,thr_or_c[,kw[,kh[,invert]]]]: a word and whole integers, nothing empty, nothing behind the last one
             static const char *const methods[] = {"fixed", "otsu", "mean"};
@@ -1445,6 +1559,9 @@ int main(int argc, char *argv[])
         fprintf(stderr, "       one \"x y k border\" and 64 hex digits each -> canny_descriptors.txt in the -o dir\n");
         fprintf(stderr, "   -z op,kw[,kh[,shape[,iterations]]]: binary morphology of the edge map (erode, dilate, open, close, gradient,\n");
         fprintf(stderr, "       tophat, blackhat; kw, kh odd 1..31; rect, cross, ellipse; 1..16 iterations) -> canny_morph.pgm in the -o dir\n");
+        fprintf(stderr, "   -G op,kw[,kh[,shape[,iterations[,border]]]]: a grey-level operator on the input frame (the words of -z, or median\n");
+        fprintf(stderr, "       with kw 3 or 5; border neutral, replicate or 0..255) -> canny_gray.pgm in the -o dir; with -a also the\n");
+        fprintf(stderr, "       binarization of that plane, on the device -> canny_gray_binary.pgm\n");
         fprintf(stderr, "   -a method[,thr_or_c[,kw[,kh[,invert]]]]: the input frame binarized (fixed: thr -1..255; otsu: the frame's own\n");
         fprintf(stderr, "       threshold, printed; mean: adaptive, offset c, window kw x kh odd 3..255; invert 0 or 1) -> canny_binary.pgm in the -o dir\n");
         fprintf(stderr, "   -v method[,max_iterations]: the edge map -- with -a the binarized frame, on the device -- thinned to a one-pixel\n");
@@ -1539,6 +1656,10 @@ int main(int argc, char *argv[])
     }
     if (want_binarize) {
         const int rc = run_binarize(frame, height, width, bin_args, outdir);
+        if (rc) return rc;
+    }
+    if (want_gray) {
+        const int rc = run_gray_morph(frame, height, width, gray_args, want_binarize ? bin_args : nullptr, outdir);
         if (rc) return rc;
     }
     if (want_thin) {

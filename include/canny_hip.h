@@ -52,7 +52,8 @@
 extern "C" {
 #endif
 
-#define CANNY_HIP_VERSION 2700       /* 0.27.0: + morphological reconstruction of packed bit maps (seeded, fill holes, clear border) */
+#define CANNY_HIP_VERSION 2800       /* 0.28.0: + grey-level morphology and median filtering of u8 planes */
+/* 0.27.0: + morphological reconstruction of packed bit maps (seeded, fill holes, clear border) */
 /* 0.26.0: + thinning of packed bit maps to one-pixel skeletons */
 /* 0.25.0: + binarization: gray planes to packed bit maps (fixed, Otsu, adaptive) */
 /* 0.24.0: + binary morphology on packed bit maps */
@@ -2514,6 +2515,92 @@ int canny_hip_reconstruct_batch(canny_hip_ctx *ctx, const unsigned char *marker,
 int canny_hip_reconstruct_bits(const unsigned char *marker, const unsigned char *mask, int n_frames, int h, int w, int op,
                                int connectivity, unsigned char *out, long long *info);
 
+/* ---- grey-level morphology and median filtering of u8 planes -------------------------------------------------------------------
+ * What prepares a plane BEFORE it is thresholded: cv::erode / cv::dilate / cv::morphologyEx on a grey image
+ * (scipy.ndimage.grey_erosion / grey_dilation, minimum_filter / maximum_filter) and cv::medianBlur
+ * (scipy.ndimage.median_filter), on u8 planes as they lie on the device (frames, warped frames, fused backgrounds, the smoothed
+ * plane dev_canny left in the context), on the context's stream, without a download.  A top hat or black hat flattens uneven
+ * lighting in front of CANNY_HIP_BIN_OTSU, a median removes salt and pepper in front of canny; the binarization, corner,
+ * descriptor, warp, fusion and canny calls take the output as it is.  All integers: the same bytes on every run, route and
+ * machine.  tests/gray_morph_rule.py restates the rule in numpy, csrc/canny_gray_morph_host.cpp in plain C++.
+ * THE RULE:
+ *   Planes.  Input and output [n_frames][h][w] u8, any byte address.  Every output byte is written.  There is no in-place form:
+ *     buffers that overlap give CANNY_HIP_ERR_INVALID.
+ *   Element.  The binary morphology's: rows[kh] words, kw and kh odd in 1..31, bit i of rows[j] the offset (i - kw / 2,
+ *     j - kh / 2), filled by canny_hip_morph_element for rect, cross and ellipse; flat (no weights); the same checks.
+ *   Primitives, B the set of the element's offsets:
+ *       ERODE : out(p) = min over b in B of in(p + b)
+ *       DILATE: out(p) = max over b in B of in(p - b)   -- the element reflected, as the binary operator does
+ *     These are scipy.ndimage.grey_erosion / grey_dilation with footprint = B.
+ *   Border, border_mode with border_value:
+ *       CANNY_HIP_GRAY_BORDER_NEUTRAL = 0: the outside reads 255 in an erosion step and 0 in a dilation step (OpenCV's default
+ *         for morphology; scipy mode='constant' with cval 255 or 0)
+ *       CANNY_HIP_GRAY_BORDER_REPLICATE = 1: coordinates are clamped to the frame (scipy mode='nearest')
+ *       CANNY_HIP_GRAY_BORDER_CONSTANT = 2: the outside reads border_value, 0..255, in every step (scipy mode='constant')
+ *     border_value is ignored by the other two modes.
+ *   Ops, iterations in 1..16 as in the binary operator:
+ *       CANNY_HIP_GRAY_ERODE = 0, _DILATE = 1: the primitive `iterations` times in sequence
+ *       CANNY_HIP_GRAY_OPEN  = 2: `iterations` erosions, then `iterations` dilations;  _CLOSE = 3: the dual
+ *       CANNY_HIP_GRAY_GRADIENT = 4: DILATE - ERODE;  _TOPHAT = 5: in - OPEN;  _BLACKHAT = 6: CLOSE - in.  THE THREE DIFFERENCES
+ *         SATURATE AT 0 (cv::subtract on u8): under CONSTANT borders OPEN need not lie below the input.
+ *       CANNY_HIP_GRAY_MEDIAN = 7: the element must be the full 3 x 3 or 5 x 5 rectangle; out(p) is the (k^2 - 1) / 2-th
+ *         smallest (counted from 0) of the k^2 window values: cv::medianBlur, scipy.ndimage.median_filter(size=k).  The border
+ *         is REPLICATE (cv::medianBlur's own) or CONSTANT; NEUTRAL: CANNY_HIP_ERR_INVALID.  iterations repeats the median.
+ *   Facts (tests/test_gray_morph_rule.py).  THRESHOLD DECOMPOSITION: for every thr, binarizing the result at thr (v > thr) is
+ *     the binary operator on the plane binarized at thr -- ERODE, DILATE, OPEN, CLOSE under NEUTRAL and under CONSTANT 0 or 255
+ *     (binary NEUTRAL, ZERO, ONE); the median of a 0/1 plane is the majority.  TWO-VALUED PLANES: on a plane of only 0 and 255
+ *     the grey operator is the binary operator, byte for byte.
+ *   Limits: h, w in 1..32768, a plane < 2^31 pixels, at most 65535 frames; above: CANNY_HIP_ERR_UNSUPPORTED.  Bad enum values,
+ *     bad ranges, NULL mandatory pointers, a bad element, buffers that overlap: CANNY_HIP_ERR_INVALID.  Both before anything is
+ *     queued; nothing is written.
+ *   Kernels (csrc/canny_gray_morph.hip): one launch per primitive step; a workgroup of 256 per tile of 128 columns x 32 rows
+ *     and trip of a grid capped at 4096, a lane owning four adjacent pixels of four rows.  The tile and its halo are staged in
+ *     LDS as words of four pixels with the border rule put in where they are formed; the arithmetic is packed 16-bit min / max
+ *     on the even and the odd bytes of a word side by side.  The context option "gray_morph_route": 0 automatic, 1 general
+ *     (per element row the set offsets of its runs; MEDIAN: a rank by counting, per pixel), 2 fast (full rectangles: the
+ *     horizontal run of kw, then the vertical run of kh, both by doubling in LDS; MEDIAN: a min / max selection network of 19
+ *     or 99 exchanges; any other element runs the general route).  All routes give the same bytes.  Sequential steps go
+ *     through two planes in the binary morphology's context workspace (and, for GRADIENT, the output buffer; no call reads
+ *     what another left there); the saturating difference belongs
+ *     to the last step's kernel.
+ * The one part is timed through canny_hip_profile_part_get("gray_morph", CANNY_HIP_GRAY_PART_STEPS); with "profile_stage_mask"
+ * it goes by bit 30 like the other features' parts.
+ * Not covered -- follow-ups: window medians above 5 x 5 by histogram; iteration fusing (several steps a launch); s16 planes;
+ * grey-level reconstruction; non-flat elements; grey morphology through the batch pipeline or the multi-GPU sharder. */
+enum canny_hip_gray_op {
+    CANNY_HIP_GRAY_ERODE = 0,
+    CANNY_HIP_GRAY_DILATE = 1,
+    CANNY_HIP_GRAY_OPEN = 2,
+    CANNY_HIP_GRAY_CLOSE = 3,
+    CANNY_HIP_GRAY_GRADIENT = 4,
+    CANNY_HIP_GRAY_TOPHAT = 5,
+    CANNY_HIP_GRAY_BLACKHAT = 6,
+    CANNY_HIP_GRAY_MEDIAN = 7
+};
+enum canny_hip_gray_border {
+    CANNY_HIP_GRAY_BORDER_NEUTRAL = 0,
+    CANNY_HIP_GRAY_BORDER_REPLICATE = 1,
+    CANNY_HIP_GRAY_BORDER_CONSTANT = 2
+};
+enum canny_hip_gray_part {
+    CANNY_HIP_GRAY_PART_STEPS = 0, /* all primitive steps of a call */
+    CANNY_HIP_GRAY_PARTS = 1
+};
+/* d_plane: n_frames * h * w bytes, any byte address, or NULL: the smoothed plane that the preceding dev_canny of the same
+ * n_frames, h, w left in the context (any canny_hip_dev_canny* call; another geometry, or none yet: CANNY_HIP_ERR_INVALID;
+ * the plane is only read).  d_out: n_frames * h * w bytes, any byte address; rows: kh words of HOST memory, copied at call
+ * time.  Asynchronous, on the context's stream. */
+int canny_hip_dev_gray_morph(canny_hip_ctx *ctx, const unsigned char *d_plane, int n_frames, int h, int w, int op,
+                             const unsigned *rows, int kw, int kh, int border_mode, int border_value, int iterations,
+                             unsigned char *d_out);
+/* Host buffers, synchronous: upload, the operator; out comes down. */
+int canny_hip_gray_morph_batch(canny_hip_ctx *ctx, const unsigned char *imgs, int n_frames, int h, int w, int op,
+                               const unsigned *rows, int kw, int kh, int border_mode, int border_value, int iterations,
+                               unsigned char *out);
+/* Host-only, needs no device: the same rule on host buffers. */
+int canny_hip_gray_morph(const unsigned char *imgs, int n_frames, int h, int w, int op, const unsigned *rows, int kw, int kh,
+                         int border_mode, int border_value, int iterations, unsigned char *out);
+
 /* ---- per-stage HIP-event timing (events are recorded on the launch stream) ----------------- */
 int canny_hip_profile_enable(canny_hip_ctx *ctx, int on);
 int canny_hip_profile_reset(canny_hip_ctx *ctx);
@@ -2561,8 +2648,9 @@ int canny_hip_morph_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, 
 /* Every group of parts by name, for this and later features: feature is "stages" (the canny stages of
  * canny_hip_profile_get), "hough", "components", "edt", "hough_segments", "contours", "hough_circles", "polygons", "edgels",
  * "line_fits", "circle_fits", "chamfer", "shapes", "curves", "corners", "descriptors", "motion", "warp", "fuse", "morph",
- * "binarize" (CANNY_HIP_BIN_PART_*), "thin" (CANNY_HIP_THIN_PART_*) or "reconstruct" (CANNY_HIP_RECON_PART_*; the three have no
- * named getter and follow bit 30 of "profile_stage_mask" like the others); the answer is the named getter's.  An
+ * "binarize" (CANNY_HIP_BIN_PART_*), "thin" (CANNY_HIP_THIN_PART_*), "reconstruct" (CANNY_HIP_RECON_PART_*) or "gray_morph"
+ * (CANNY_HIP_GRAY_PART_*; the four have no named getter and follow bit 30 of "profile_stage_mask" like the others); the answer
+ * is the named getter's.  An
  * unknown name, a part the group does not have or a NULL: CANNY_HIP_ERR_INVALID, nothing is written. */
 int canny_hip_profile_part_get(canny_hip_ctx *ctx, const char *feature, int part, double *total_ms, long *launches);
 
@@ -2774,6 +2862,11 @@ int canny_hip_selftest_thin_plan(int n_frames, int h, int w, int fuse, unsigned 
  * trip; route 1: items = n_frames * h * ceil(w / 64) words, 256 per workgroup and trip (also the plan of the init and finish
  * kernels); at most 4096 workgroups.  The fifth word is the route automatic takes (1 or 2).  It refuses what the calls refuse. */
 int canny_hip_selftest_reconstruct_plan(int n_frames, int h, int w, int route, unsigned long long *out);
+/* Host-only, the same five outputs for the capped launch of one primitive step of the grey-level morphology (no kind above):
+ * items = n_frames * ceil(h / 32) * ceil(w / 128) tiles, one per workgroup of 256 and trip, at most 4096 workgroups.  The fifth
+ * word is the route that automatic takes for op with a full rectangle of kw x kh (1 general, 2 fast); it depends on op, kw and
+ * kh alone.  kw, kh odd in 1..31 (MEDIAN: 3 x 3 or 5 x 5); it refuses what the calls refuse. */
+int canny_hip_selftest_gray_morph_plan(int n_frames, int h, int w, int op, int kw, int kh, unsigned long long *out);
 /* Runs the fuse kernels' own device helper for the rounded mean over every pair c = 1..255, s = 0..255 c, and writes the
  * bytes to host memory as a table [255][CANNY_HIP_FUSE_MEAN_ROW]: out[(c - 1) * 65026 + s]; unused cells are 0. */
 int canny_hip_selftest_fuse_mean(canny_hip_ctx *ctx, unsigned char *out);
