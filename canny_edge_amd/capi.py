@@ -154,6 +154,8 @@ EXPORTS = (
     "canny_hip_dev_reconstruct_bits", "canny_hip_dev_canny_reconstruct", "canny_hip_reconstruct_batch",
     "canny_hip_reconstruct_bits", "canny_hip_selftest_reconstruct_plan",
     "canny_hip_dev_gray_morph", "canny_hip_gray_morph_batch", "canny_hip_gray_morph", "canny_hip_selftest_gray_morph_plan",
+    "canny_hip_pyramid_layout", "canny_hip_dev_pyr_down", "canny_hip_dev_pyramid", "canny_hip_dev_pyr_up",
+    "canny_hip_pyramid_batch", "canny_hip_pyr_up_batch", "canny_hip_pyramid", "canny_hip_pyr_up", "canny_hip_selftest_pyramid_plan",
 )
 
 _lib: Optional[C.CDLL] = None
@@ -447,6 +449,15 @@ def load() -> C.CDLL:
         "canny_hip_gray_morph_batch": ([p, p, i, i, i, i, p, i, i, i, i, i, p], i),
         "canny_hip_gray_morph": ([p, i, i, i, i, p, i, i, i, i, i, p], i),
         "canny_hip_selftest_gray_morph_plan": ([i, i, i, i, i, i, p], i),
+        "canny_hip_pyramid_layout": ([i, i, i, i, p, p], i),
+        "canny_hip_dev_pyr_down": ([p, p, i, i, i, p], i),
+        "canny_hip_dev_pyramid": ([p, p, i, i, i, i, p], i),
+        "canny_hip_dev_pyr_up": ([p, p, i, i, i, i, i, p], i),
+        "canny_hip_pyramid_batch": ([p, p, i, i, i, i, p], i),
+        "canny_hip_pyr_up_batch": ([p, p, i, i, i, i, i, p], i),
+        "canny_hip_pyramid": ([p, i, i, i, i, p], i),
+        "canny_hip_pyr_up": ([p, i, i, i, i, i, p], i),
+        "canny_hip_selftest_pyramid_plan": ([i, i, i, p], i),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -1451,6 +1462,64 @@ def gray_morph_plan(n_frames: int, h: int, w: int, op: int = GRAY_ERODE, kw: int
     """Host-only: the LaunchPlan of one primitive step of the grey-level morphology (one tile of 128 columns x 32 rows per
     workgroup and trip); aux = the route automatic takes for op with a full rectangle of kw x kh (1 general, 2 fast)."""
     return _plan("gray_morph_plan", int(n_frames), int(h), int(w), int(op), int(kw), int(kh))
+
+
+# ---- image pyramids of u8 planes: pyrDown, pyrUp, whole pyramids (DESIGN.md section 40) ------------------------------------
+PYR_MAX_LEVELS = 15
+PYR_ROUTE_AUTO, PYR_ROUTE_DIRECT, PYR_ROUTE_TILED = 0, 1, 2
+PYR_PART_DOWN, PYR_PART_UP = 0, 1
+PYR_PARTS = ("down", "up")
+
+
+def pyramid_layout(n_frames: int, h: int, w: int, levels: int):
+    """Host-only: (info, total_bytes) of the pyramid's one buffer; info int64 [levels, 4]: (h, w, offset, bytes) of level
+    l + 1 in row l, every offset a multiple of 256; total_bytes: the end of the last level."""
+    info = np.zeros((min(max(int(levels), 1), PYR_MAX_LEVELS), 4), np.int64)   # a refused call writes nothing
+    total = np.zeros(1, np.int64)
+    _ok(load().canny_hip_pyramid_layout(int(n_frames), int(h), int(w), int(levels), _hp(info), _hp(total)), "pyramid_layout")
+    return info, int(total[0])
+
+
+def _pyramid_levels(buf: np.ndarray, n: int, info: np.ndarray):
+    """The levels of a pyramid buffer as views [n, h_l, w_l]."""
+    return [buf[off:off + nbytes].reshape(n, hl, wl) for hl, wl, off, nbytes in info.tolist()]
+
+
+def pyramid(imgs, levels: int):
+    """Host-only, needs no GPU: the levels 1..levels of planes uint8 [n_frames, H, W], a list of arrays [n_frames, h_l, w_l]
+    (views of one buffer in the layout of pyramid_layout)."""
+    a = _gray_planes(imgs)
+    n, h, w = a.shape
+    info, total = pyramid_layout(n, h, w, levels)
+    out = np.zeros(total, np.uint8)
+    _ok(load().canny_hip_pyramid(_hp(a), n, h, w, int(levels), _hp(out)), "pyramid")
+    return _pyramid_levels(out, n, info)
+
+
+def pyr_up(imgs, oh: int, ow: int):
+    """Host-only, needs no GPU: pyrUp of planes uint8 [n_frames, H, W] to [n_frames, oh, ow], oh in (2 H - 1, 2 H), ow in
+    (2 W - 1, 2 W)."""
+    a = _gray_planes(imgs)
+    n, h, w = a.shape
+    out = np.zeros((n, max(int(oh), 0), max(int(ow), 0)), np.uint8)
+    _ok(load().canny_hip_pyr_up(_hp(a), n, h, w, int(oh), int(ow), _hp(out)), "pyr_up")
+    return out
+
+
+def pyramid_batch(ctx, imgs, levels: int):
+    """ctx.pyramid_batch(imgs, levels)."""
+    return ctx.pyramid_batch(imgs, levels)
+
+
+def pyr_up_batch(ctx, imgs, oh: int, ow: int):
+    """ctx.pyr_up_batch(imgs, oh, ow)."""
+    return ctx.pyr_up_batch(imgs, oh, ow)
+
+
+def pyramid_plan(n_frames: int, h: int, w: int):
+    """Host-only: the LaunchPlan of one pyrDown of planes [n_frames, h, w] (one tile of 128 columns x 32 rows of the output
+    per workgroup and trip; a pyrUp into planes of that output size has the same plan); aux = the route automatic takes."""
+    return _plan("pyramid_plan", int(n_frames), int(h), int(w))
 
 
 # ---- chamfer template matching (DESIGN.md section 26) --------------------------------------------------------------------
@@ -3074,9 +3143,45 @@ class Context:
                     "gray_morph_batch")
         return out
 
+    # ---- image pyramids of u8 planes --------------------------------------------------------------
+    def dev_pyr_down(self, d_plane: int, n_frames: int, h: int, w: int, d_out: int):
+        """pyrDown of device planes uint8 [n_frames][h][w] (d_plane 0: the smoothed plane the preceding dev_canny of the same
+        geometry left in the context) into d_out [n_frames][(h + 1) // 2][(w + 1) // 2].  Asynchronous."""
+        v = C.c_void_p
+        self._check(self._L.canny_hip_dev_pyr_down(self._h, v(d_plane or None), n_frames, h, w, v(d_out or None)), "dev_pyr_down")
+
+    def dev_pyramid(self, d_plane: int, n_frames: int, h: int, w: int, levels: int, d_out: int):
+        """The levels 1..levels into d_out in the layout of pyramid_layout, one launch per level.  Asynchronous."""
+        v = C.c_void_p
+        self._check(self._L.canny_hip_dev_pyramid(self._h, v(d_plane or None), n_frames, h, w, int(levels), v(d_out or None)),
+                    "dev_pyramid")
+
+    def dev_pyr_up(self, d_plane: int, n_frames: int, h: int, w: int, oh: int, ow: int, d_out: int):
+        """pyrUp of device planes uint8 [n_frames][h][w] into d_out [n_frames][oh][ow].  Asynchronous."""
+        v = C.c_void_p
+        self._check(self._L.canny_hip_dev_pyr_up(self._h, v(d_plane or None), n_frames, h, w, int(oh), int(ow), v(d_out or None)),
+                    "dev_pyr_up")
+
+    def pyramid_batch(self, imgs, levels: int):
+        """Upload, the levels on the GPU and download: imgs (N, H, W) uint8 -> a list of arrays [N, h_l, w_l]."""
+        a = _gray_planes(imgs)
+        n, h, w = a.shape
+        info, total = pyramid_layout(n, h, w, levels)
+        out = np.zeros(total, np.uint8)
+        self._check(self._L.canny_hip_pyramid_batch(self._h, _hp(a), n, h, w, int(levels), _hp(out)), "pyramid_batch")
+        return _pyramid_levels(out, n, info)
+
+    def pyr_up_batch(self, imgs, oh: int, ow: int):
+        """Upload, pyrUp on the GPU and download: imgs (N, H, W) uint8 -> (N, oh, ow)."""
+        a = _gray_planes(imgs)
+        n, h, w = a.shape
+        out = np.zeros((n, max(int(oh), 0), max(int(ow), 0)), np.uint8)
+        self._check(self._L.canny_hip_pyr_up_batch(self._h, _hp(a), n, h, w, int(oh), int(ow), _hp(out)), "pyr_up_batch")
+        return out
+
     def profile_part(self, feature: str, part: int) -> Tuple[float, int]:
         """(total ms, launch groups) of part `part` of the named group of the profile table ("stages", "hough", ..., "morph",
-        "binarize": BIN_PARTS, "thin": THIN_PARTS, "reconstruct": RECON_PARTS): what the group's own getter answers."""
+        "binarize": BIN_PARTS, "thin": THIN_PARTS, "reconstruct": RECON_PARTS, "pyramid": PYR_PARTS): what the group's own getter answers."""
         ms, n = C.c_double(0), C.c_long(0)
         self._check(self._L.canny_hip_profile_part_get(self._h, str(feature).encode(), int(part), C.byref(ms), C.byref(n)),
                     "profile_part_get")

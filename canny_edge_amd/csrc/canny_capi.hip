@@ -354,6 +354,7 @@ constexpr ProfGroup kProfGroups[] = {
     {"thin", CANNY_HIP_THIN_PARTS},
     {"reconstruct", CANNY_HIP_RECON_PARTS},
     {"gray_morph", CANNY_HIP_GRAY_PARTS},
+    {"pyramid", CANNY_HIP_PYR_PARTS},
 };
 
 // The first slot of the named group; with no name, the number of slots.  A name the table does not hold fails to compile.
@@ -547,6 +548,7 @@ struct canny_hip_ctx : Workspaces {
     int reconstruct_route = 0;         // 0 auto, 1 stepwise, 2 tile flood
     int last_reconstruct_launches = 0; // the sweep launches the last reconstruction call queued: a diagnostic
     int gray_morph_route = 0;          // 0 auto, 1 general, 2 fast (full rectangles separably, the median by a network)
+    int pyramid_route = 0;             // 0 auto, 1 direct, 2 tiled
     std::vector<int> motion_pairs; // the validated pairs of the last motion call: what its upload reads
     DevBuf io[4];     // staging for the host-pointer stage functions
     std::string ws_name; // canny_hip_selftest_workspace: the name it handed out last
@@ -581,7 +583,8 @@ struct canny_hip_ctx : Workspaces {
                          kProfDescriptors = prof_base("descriptors"), kProfMotion = prof_base("motion"),
                          kProfWarp = prof_base("warp"), kProfFuse = prof_base("fuse"), kProfMorph = prof_base("morph"),
                          kProfBinarize = prof_base("binarize"), kProfThin = prof_base("thin"),
-                         kProfReconstruct = prof_base("reconstruct"), kProfGrayMorph = prof_base("gray_morph");
+                         kProfReconstruct = prof_base("reconstruct"), kProfGrayMorph = prof_base("gray_morph"),
+                         kProfPyramid = prof_base("pyramid");
     static constexpr int kProfSlots = prof_base(nullptr);
     // "profile_stage_mask" is a non-negative int option: bit 30 is the last it can carry
     static constexpr int kProfLastBit = 30;
@@ -636,6 +639,7 @@ constexpr OptRow kOptions[] = {
     {"reconstruct_route", &canny_hip_ctx::reconstruct_route, 0, 2, true, true},
     {"last_reconstruct_launches", &canny_hip_ctx::last_reconstruct_launches, 0, 0, true, false},
     {"gray_morph_route", &canny_hip_ctx::gray_morph_route, 0, 2, true, true},
+    {"pyramid_route", &canny_hip_ctx::pyramid_route, 0, 2, true, true},
 };
 
 } // namespace
@@ -7131,6 +7135,144 @@ int canny_hip_selftest_gray_morph_plan(int n_frames, int h, int w, int op, int k
     if (rc) return rc;
     store_plan(out, plan_gray_morph_tiles(n_frames, h, w));
     out[4] = (unsigned long long)gray_morph_auto_route(op, kw, kh); // the route, not aux
+    return CANNY_HIP_OK;
+}
+
+// ---- image pyramids of u8 planes (canny_pyramid.hip) ------------------------------------------------
+// canny_hip_pyramid_layout, canny_hip_pyramid and canny_hip_pyr_up, the rule in plain C++, live in canny_pyramid_host.cpp.
+
+namespace {
+// The plane a pyrDown reads: the caller's, or for NULL the smoothed plane the last canny call of this geometry left.
+int pyr_source(canny_hip_ctx *ctx, const unsigned char *d_plane, int n_frames, int h, int w, const void **plane, bool *plane_u8)
+{
+    *plane = d_plane, *plane_u8 = true;
+    if (d_plane) return CANNY_HIP_OK;
+    if (!last_canny_was(ctx, n_frames, h, w) || !ctx->smoothed.p) return CANNY_HIP_ERR_INVALID;
+    *plane = ctx->smoothed.p, *plane_u8 = ctx->last_canny_u8 != 0;
+    return CANNY_HIP_OK;
+}
+
+// The levels queued on the context's stream, one launch each; everything has been checked.  info: the layout.
+int dev_pyramid(canny_hip_ctx *ctx, const void *plane, bool plane_u8, int n_frames, int h, int w, int levels, const long long *info,
+                unsigned char *d_out)
+{
+    StageTimer tm(ctx, canny_hip_ctx::kProfPyramid + CANNY_HIP_PYR_PART_DOWN);
+    for (int l = 0; l < levels; l++) {
+        unsigned char *level = d_out + info[4 * l + 2];
+        HIP_TRY(ctx, launch_pyr_down(plane, !plane_u8, n_frames, h, w, ctx->pyramid_route, level, ctx->stream));
+        plane = level, plane_u8 = true, h = (int)info[4 * l], w = (int)info[4 * l + 1];
+    }
+    return CANNY_HIP_OK;
+}
+
+// every check of pyrUp but the pointers and the overlap
+int pyr_up_check(int n_frames, int h, int w, int oh, int ow)
+{
+    if (n_frames < 1 || h < 1 || w < 1 || (oh != 2 * h - 1 && oh != 2 * h) || (ow != 2 * w - 1 && ow != 2 * w) || oh < 1 || ow < 1)
+        return CANNY_HIP_ERR_INVALID;
+    const int rc = fuse_stack_check(n_frames, h, w);
+    return rc ? rc : fuse_stack_check(n_frames, oh, ow);
+}
+
+int dev_pyr_up(canny_hip_ctx *ctx, const unsigned char *plane, int n_frames, int h, int w, int oh, int ow, unsigned char *d_out)
+{
+    StageTimer tm(ctx, canny_hip_ctx::kProfPyramid + CANNY_HIP_PYR_PART_UP);
+    HIP_TRY(ctx, launch_pyr_up(plane, n_frames, h, w, oh, ow, d_out, ctx->stream));
+    return CANNY_HIP_OK;
+}
+} // namespace
+
+int canny_hip_dev_pyr_down(canny_hip_ctx *ctx, const unsigned char *d_plane, int n_frames, int h, int w, unsigned char *d_out)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!d_out) return CANNY_HIP_ERR_INVALID;
+    if ((rc = fuse_stack_check(n_frames, h, w))) return rc;
+    const void *plane;
+    bool plane_u8;
+    if ((rc = pyr_source(ctx, d_plane, n_frames, h, w, &plane, &plane_u8))) return rc;
+    const long long level[4] = {(h + 1) / 2, (w + 1) / 2, 0, 0};
+    if (ranges_overlap(plane, npx(h, w, n_frames) * (plane_u8 ? 1 : 2), d_out, npx((int)level[0], (int)level[1], n_frames)))
+        return CANNY_HIP_ERR_INVALID;
+    if ((rc = finish_pending(ctx))) return rc;
+    return dev_pyramid(ctx, plane, plane_u8, n_frames, h, w, 1, level, d_out);
+}
+
+int canny_hip_dev_pyramid(canny_hip_ctx *ctx, const unsigned char *d_plane, int n_frames, int h, int w, int levels,
+                          unsigned char *d_out)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!d_out) return CANNY_HIP_ERR_INVALID;
+    long long info[4 * CANNY_HIP_PYR_MAX_LEVELS], total = 0;
+    if ((rc = canny_hip_pyramid_layout(n_frames, h, w, levels, info, &total))) return rc;
+    const void *plane;
+    bool plane_u8;
+    if ((rc = pyr_source(ctx, d_plane, n_frames, h, w, &plane, &plane_u8))) return rc;
+    if (ranges_overlap(plane, npx(h, w, n_frames) * (plane_u8 ? 1 : 2), d_out, (size_t)total)) return CANNY_HIP_ERR_INVALID;
+    if ((rc = finish_pending(ctx))) return rc;
+    return dev_pyramid(ctx, plane, plane_u8, n_frames, h, w, levels, info, d_out);
+}
+
+int canny_hip_dev_pyr_up(canny_hip_ctx *ctx, const unsigned char *d_plane, int n_frames, int h, int w, int oh, int ow,
+                         unsigned char *d_out)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!d_plane || !d_out) return CANNY_HIP_ERR_INVALID;
+    if ((rc = pyr_up_check(n_frames, h, w, oh, ow))) return rc;
+    if (ranges_overlap(d_plane, npx(h, w, n_frames), d_out, npx(oh, ow, n_frames))) return CANNY_HIP_ERR_INVALID;
+    if ((rc = finish_pending(ctx))) return rc;
+    return dev_pyr_up(ctx, d_plane, n_frames, h, w, oh, ow, d_out);
+}
+
+int canny_hip_pyramid_batch(canny_hip_ctx *ctx, const unsigned char *imgs, int n_frames, int h, int w, int levels,
+                            unsigned char *out)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!imgs || !out) return CANNY_HIP_ERR_INVALID;
+    long long info[4 * CANNY_HIP_PYR_MAX_LEVELS], total = 0;
+    if ((rc = canny_hip_pyramid_layout(n_frames, h, w, levels, info, &total))) return rc;
+    const size_t bytes = npx(h, w, n_frames);
+    if (ranges_overlap(imgs, bytes, out, (size_t)total)) return CANNY_HIP_ERR_INVALID;
+    if ((rc = finish_pending(ctx))) return rc;
+    if ((rc = h2d(ctx, ctx->io[0], imgs, bytes))) return rc;
+    HIP_TRY(ctx, ctx->io[1].ensure((size_t)total));
+    unsigned char *d_out = (unsigned char *)ctx->io[1].p;
+    if ((rc = dev_pyramid(ctx, ctx->io[0].p, true, n_frames, h, w, levels, info, d_out))) return rc;
+    // level by level: the pad bytes of the caller's buffer stay as they are
+    for (int l = 0; l + 1 < levels; l++)
+        HIP_TRY(ctx, hipMemcpyAsync(out + info[4 * l + 2], d_out + info[4 * l + 2], (size_t)info[4 * l + 3], hipMemcpyDeviceToHost,
+                                    ctx->stream));
+    const long long *last = info + 4 * (levels - 1);
+    return d2h_sync(ctx, out + last[2], d_out + last[2], (size_t)last[3]);
+}
+
+int canny_hip_pyr_up_batch(canny_hip_ctx *ctx, const unsigned char *imgs, int n_frames, int h, int w, int oh, int ow,
+                           unsigned char *out)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!imgs || !out) return CANNY_HIP_ERR_INVALID;
+    if ((rc = pyr_up_check(n_frames, h, w, oh, ow))) return rc;
+    const size_t bytes = npx(h, w, n_frames), out_bytes = npx(oh, ow, n_frames);
+    if (ranges_overlap(imgs, bytes, out, out_bytes)) return CANNY_HIP_ERR_INVALID;
+    if ((rc = finish_pending(ctx))) return rc;
+    if ((rc = h2d(ctx, ctx->io[0], imgs, bytes))) return rc;
+    HIP_TRY(ctx, ctx->io[1].ensure(out_bytes));
+    if ((rc = dev_pyr_up(ctx, (const unsigned char *)ctx->io[0].p, n_frames, h, w, oh, ow, (unsigned char *)ctx->io[1].p))) return rc;
+    return d2h_sync(ctx, out, ctx->io[1].p, out_bytes);
+}
+
+// Host-only: the launch plan of one pyrDown of planes [n_frames][h][w] and the route automatic takes.
+int canny_hip_selftest_pyramid_plan(int n_frames, int h, int w, unsigned long long *out)
+{
+    if (!out) return CANNY_HIP_ERR_INVALID;
+    const int rc = fuse_stack_check(n_frames, h, w);
+    if (rc) return rc;
+    store_plan(out, plan_pyramid_tiles(n_frames, (h + 1) / 2, (w + 1) / 2));
+    out[4] = (unsigned long long)pyramid_auto_route(); // the route, not aux
     return CANNY_HIP_OK;
 }
 

@@ -943,6 +943,18 @@ hipError_t launch_gray_morph(const void *src, bool src_s16, int n_frames, int h,
                              int kh, int border_mode, int border_value, int iterations, int route, uint8_t *ws_a, uint8_t *ws_b,
                              uint8_t *out, hipStream_t stream);
 
+// ---- image pyramids of u8 planes: pyrDown and pyrUp (canny_pyramid.hip) ---------------------
+// Every launch walks the n_frames * ceil(out_h / 32) * ceil(out_w / 128) tiles of 128 columns x 32 rows of its OUTPUT, one per
+// workgroup and trip.  (Reported by canny_hip_selftest_pyramid_plan, not by a kind.)
+LaunchPlan plan_pyramid_tiles(int n_frames, int out_h, int out_w);
+// The route automatic takes for pyrDown: 1 direct, 2 tiled.  It depends on nothing.
+int pyramid_auto_route();
+// Every byte of out [n_frames][(h + 1) / 2][(w + 1) / 2].  src: a plane [n_frames][h][w] of bytes or -- src_s16 -- of shorts
+// in [0, 255]; route: 0 automatic, 1 direct, 2 tiled.  One launch.
+hipError_t launch_pyr_down(const void *src, bool src_s16, int n_frames, int h, int w, int route, uint8_t *out, hipStream_t stream);
+// Every byte of out [n_frames][oh][ow], oh in {2 h - 1, 2 h}, ow in {2 w - 1, 2 w}.  One launch.
+hipError_t launch_pyr_up(const uint8_t *src, int n_frames, int h, int w, int oh, int ow, uint8_t *out, hipStream_t stream);
+
 // ---- measurement aid ------------------------------------------------------------------------
 // Plain device copy of nbytes (multiple of 16; both pointers 16-byte aligned): what a 1:1 read/write stream reaches.
 hipError_t launch_probe_copy(const void *src, void *dst, size_t nbytes, hipStream_t stream, const LaunchEvents &ev = {});

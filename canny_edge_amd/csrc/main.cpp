@@ -92,6 +92,10 @@
 // goes to canny_gray.pgm in the -o directory; with -a also given, the binarization of THAT plane, binarized on the device with
 // no download in between, goes to canny_gray_binary.pgm (canny_binary.pgm stays the binarization of the input frame).  A
 // malformed -G is a usage error (exit 2).  Without -G nothing changes.
+// Added: -P levels[,up] builds the pyramid of the input frame on the GPU (canny_hip_dev_pyramid: level l is cv::pyrDown of level
+// l - 1) and writes its levels to canny_pyr1.pgm .. canny_pyr<levels>.pgm in the -o directory; with up, level 1 is also brought
+// back to the frame's size (canny_hip_dev_pyr_up, cv::pyrUp) into canny_pyr_up.pgm.  levels is 1..15 and at most
+// ceil(log2(max(height, width))); a malformed -P is a usage error (exit 2).  Without -P nothing changes.
 // Added: -e computes the sub-pixel edgel of every pixel of the frame's edge map on the GPU (canny_hip_canny_edgels) and
 // writes one "x y gx gy mag dir refined" row per edge pixel, in raster order, to canny_edgels.txt in the -o directory
 // (stdout without -o): x and y in pixels to three decimals, mag in grey levels, dir 0..3 (step (1,0), (1,1), (0,1), (1,-1)),
@@ -788,6 +792,54 @@ static int run_gray_morph(const vector<unsigned char> &frame, int height, int wi
     return 0;
 }
 
+// -P: the levels 1..levels of the frame's pyramid on the device -> canny_pyr1.pgm .. canny_pyr<levels>.pgm and, with up,
+// level 1 brought back to the frame's size -> canny_pyr_up.pgm
+static int run_pyramid(const vector<unsigned char> &frame, int height, int width, int levels, bool up, const string &outdir)
+{
+    long long info[4 * CANNY_HIP_PYR_MAX_LEVELS], total = 0;
+    int st = canny_hip_pyramid_layout(1, height, width, levels, info, &total);
+    if (st) {
+        fprintf(stderr, "ERROR: -P: a frame of %d x %d has no level %d\n", width, height, levels);
+        return 1;
+    }
+    const size_t px = (size_t)height * width;
+    vector<unsigned char> pyr((size_t)total), back(up ? px : 0);
+    canny_hip_ctx *ctx = nullptr;
+    void *d_img = nullptr, *d_pyr = nullptr, *d_up = nullptr;
+    st = canny_hip_ctx_create(&ctx, 0);
+    if (!st) st = canny_hip_malloc(ctx, &d_img, px);
+    if (!st) st = canny_hip_malloc(ctx, &d_pyr, pyr.size());
+    if (!st && up) st = canny_hip_malloc(ctx, &d_up, px);
+    if (!st) st = canny_hip_memcpy_h2d(ctx, d_img, frame.data(), px);
+    if (!st) st = canny_hip_dev_pyramid(ctx, (const unsigned char *)d_img, 1, height, width, levels, (unsigned char *)d_pyr);
+    if (!st && up)
+        st = canny_hip_dev_pyr_up(ctx, (const unsigned char *)d_pyr, 1, (int)info[0], (int)info[1], height, width,
+                                  (unsigned char *)d_up);
+    for (int l = 0; l < levels && !st; l++) // level by level: the pads were never written
+        st = canny_hip_memcpy_d2h(ctx, pyr.data() + info[4 * l + 2], (unsigned char *)d_pyr + info[4 * l + 2], (size_t)info[4 * l + 3]);
+    if (!st && up) st = canny_hip_memcpy_d2h(ctx, back.data(), d_up, px);
+    if (st) fprintf(stderr, "ERROR: -P: %s\n", st == CANNY_HIP_ERR_RUNTIME && ctx ? canny_hip_last_error(ctx) : canny_hip_status_string(st));
+    if (ctx) {
+        for (void *p : {d_img, d_pyr, d_up})
+            if (p) canny_hip_free(ctx, p);
+        canny_hip_ctx_destroy(ctx);
+    }
+    if (st) return 1;
+    const string dir = outdir.empty() ? string(".") : outdir, ext = png_output ? ".png" : ".pgm";
+    for (int l = 0; l < levels; l++) {
+        const string path = dir + "/canny_pyr" + to_string(l + 1) + ext;
+        if (!write_frame(path, pyr.data() + info[4 * l + 2], (int)info[4 * l], (int)info[4 * l + 1])) {
+            fprintf(stderr, "ERROR: cannot write %s\n", path.c_str());
+            return 1;
+        }
+    }
+    if (up && !write_frame(dir + "/canny_pyr_up" + ext, back.data(), height, width)) {
+        fprintf(stderr, "ERROR: cannot write %s\n", (dir + "/canny_pyr_up" + ext).c_str());
+        return 1;
+    }
+    return 0;
+}
+
 // -v: a bit map of the frame thinned on the device -> canny_thin.pgm.  bin: the -a arguments (method, thr_or_c, kw, kh, invert)
 // or nullptr for the finished edge map; v: method, max_iterations
 static int run_thin(const vector<unsigned char> &frame, int height, int width, float sigma, int minVal, int maxVal, const int *bin,
@@ -1105,6 +1157,8 @@ int main(int argc, char *argv[])
     bool want_morph = false;
     int morph_args[5] = {0, 3, 3, 0, 1};   // -z: op, kw, kh, shape, iterations
     bool want_gray = false;
+    bool want_pyramid = false, pyramid_up = false; // -P levels[,up]
+    int pyramid_levels = 0;
     int gray_args[7] = {0, 3, 3, 0, 1, 0, 0}; // -G: op, kw, kh, shape, iterations, border_mode, border_value
     bool want_binarize = false;
     int bin_args[5] = {0, 127, 31, 31, 0}; // -a: method, thr_or_c, kw, kh, invert
@@ -1379,6 +1433,21 @@ int main(int argc, char *argv[])
                 exit(2);
             }
             want_gray = true;
+        } else if (arg == "-P") {
+            // levels[,up]: a whole integer 1..15 of digits alone and the word up, nothing empty, nothing behind the last one
+            const string value = i + 1 < argc ? argv[++i] : "";
+            const size_t comma = value.find(',');
+            const string number = value.substr(0, comma);
+            bool clean = !number.empty() && number.size() <= 2 && (comma == string::npos || value.substr(comma + 1) == "up");
+            for (char c : number) clean = clean && isdigit((unsigned char)c);
+            if (clean) pyramid_levels = atoi(number.c_str());
+            clean = clean && pyramid_levels >= 1 && pyramid_levels <= CANNY_HIP_PYR_MAX_LEVELS;
+            if (!clean) {
+                fprintf(stderr, "ERROR: -P expects levels[,up]: levels 1..15 (at most ceil(log2(max(height, width)))), up to also bring "
+                                "level 1 back to the frame's size\n");
+                exit(2);
+            }
+            want_pyramid = true, pyramid_up = comma != string::npos;
         } else if (arg == "-a") {
             // method[,thr_or_c[,kw[,kh[,invert]]]]: a word and whole integers, nothing empty, nothing behind the last one
             static const char *const methods[] = {"fixed", "otsu", "mean"};
@@ -1562,6 +1631,9 @@ int main(int argc, char *argv[])
         fprintf(stderr, "   -G op,kw[,kh[,shape[,iterations[,border]]]]: a grey-level operator on the input frame (the words of -z, or median\n");
         fprintf(stderr, "       with kw 3 or 5; border neutral, replicate or 0..255) -> canny_gray.pgm in the -o dir; with -a also the\n");
         fprintf(stderr, "       binarization of that plane, on the device -> canny_gray_binary.pgm\n");
+        fprintf(stderr, "   -P levels[,up]: the pyramid of the input frame on the device (pyrDown: 5 x 5 binomial, every second pixel; levels\n");
+        fprintf(stderr, "       1..15) -> canny_pyr1.pgm .. canny_pyr<levels>.pgm in the -o dir; with up also level 1 brought back to the\n");
+        fprintf(stderr, "       frame's size (pyrUp) -> canny_pyr_up.pgm\n");
         fprintf(stderr, "   -a method[,thr_or_c[,kw[,kh[,invert]]]]: the input frame binarized (fixed: thr -1..255; otsu: the frame's own\n");
         fprintf(stderr, "       threshold, printed; mean: adaptive, offset c, window kw x kh odd 3..255; invert 0 or 1) -> canny_binary.pgm in the -o dir\n");
         fprintf(stderr, "   -v method[,max_iterations]: the edge map -- with -a the binarized frame, on the device -- thinned to a one-pixel\n");
@@ -1660,6 +1732,10 @@ int main(int argc, char *argv[])
     }
     if (want_gray) {
         const int rc = run_gray_morph(frame, height, width, gray_args, want_binarize ? bin_args : nullptr, outdir);
+        if (rc) return rc;
+    }
+    if (want_pyramid) {
+        const int rc = run_pyramid(frame, height, width, pyramid_levels, pyramid_up, outdir);
         if (rc) return rc;
     }
     if (want_thin) {

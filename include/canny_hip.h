@@ -52,7 +52,8 @@
 extern "C" {
 #endif
 
-#define CANNY_HIP_VERSION 2800       /* 0.28.0: + grey-level morphology and median filtering of u8 planes */
+#define CANNY_HIP_VERSION 2900       /* 0.29.0: + image pyramids: pyrDown, pyrUp and whole pyramids of u8 planes */
+/* 0.28.0: + grey-level morphology and median filtering of u8 planes */
 /* 0.27.0: + morphological reconstruction of packed bit maps (seeded, fill holes, clear border) */
 /* 0.26.0: + thinning of packed bit maps to one-pixel skeletons */
 /* 0.25.0: + binarization: gray planes to packed bit maps (fixed, Otsu, adaptive) */
@@ -2601,6 +2602,81 @@ int canny_hip_gray_morph_batch(canny_hip_ctx *ctx, const unsigned char *imgs, in
 int canny_hip_gray_morph(const unsigned char *imgs, int n_frames, int h, int w, int op, const unsigned *rows, int kw, int kh,
                          int border_mode, int border_value, int iterations, unsigned char *out);
 
+/* ---- image pyramids: pyrDown, pyrUp and whole pyramids of u8 planes ----------------------------------------------------------
+ * What maps a u8 plane to a plane of half or twice the size, low-passed: cv::pyrDown / cv::pyrUp / cv::buildPyramid on CV_8U,
+ * on planes as they lie on the device (frames, warped frames, fused backgrounds, the smoothed plane dev_canny left in the
+ * context), on the context's stream, without a download.  Every level is one contiguous [n_frames][h_l][w_l] block, so the
+ * canny, corner, descriptor, binarization, grey-morphology, warp and fusion calls take a level as it lies (d_out + off_l) --
+ * edges, corners and matches at half and quarter resolution, coarse-to-fine search.  All integers: the same bytes on every run,
+ * route and machine.  tests/pyramid_rule.py restates the rule in numpy, csrc/canny_pyramid_host.cpp in plain C++.
+ * THE RULE:
+ *   Fold.  fold(p, n) is reflect-101 (cv::BORDER_DEFAULT, scipy mode='mirror'): 0 if n == 1; otherwise, while p < 0 or
+ *     p >= n: p = -p if p < 0, else p = 2 (n - 1) - p.  THE LOOP MATTERS for n = 2 and 3.
+ *   pyrDown, taps k = (1, 4, 6, 4, 1).  Input [n][h][w] u8, output [n][oh][ow] with oh = (h + 1) / 2, ow = (w + 1) / 2:
+ *       out(y, x) = (sum over j, i in 0..4 of k[j] k[i] in(fold(2 y + j - 2, h), fold(2 x + i - 2, w)) + 128) >> 8
+ *     The sum is at most 255 * 256, a horizontal partial sum at most 4080: the rule runs on 16-bit halves WITHOUT A CARRY.
+ *     This is cv::pyrDown on CV_8U; it equals scipy.ndimage.correlate1d(k, mode='mirror') on both axes, [::2, ::2],
+ *     (t + 128) >> 8.
+ *   pyrUp.  Input [n][h][w], output [n][oh][ow] with oh in {2 h - 1, 2 h} and ow in {2 w - 1, 2 w}, THE CALLER'S CHOICE, so
+ *     that level l + 1 goes back up onto an odd-sized level l.  Per axis, with s[-1] := s[min(1, w - 1)] and s[w] := s[w - 1]:
+ *       even output 2 x     : s[x - 1] + 6 s[x] + s[x + 1]
+ *       odd  output 2 x + 1 : 4 (s[x] + s[x + 1])
+ *     and out = (the sum of the products of the two axes' weights + 32) >> 6; the weights of every output sum to 64, the sum is
+ *     at most 16320.  The values do not depend on whether the last row or column is cropped.  This is the zero-inserted grid
+ *     of 2 h x 2 w filtered by k (x) k with mode='mirror' (scipy), and cv::pyrUp in the interior.
+ *   Pyramid.  Level 0 is the input and is not copied; level l = 1..levels is the pyrDown of level l - 1.  levels in
+ *     1..CANNY_HIP_PYR_MAX_LEVELS and levels <= ceil(log2(max(h, w))), so that no level repeats a 1 x 1 plane.  The output is
+ *     ONE buffer: level l at byte offset off_l as contiguous [n][h_l][w_l], off_1 = 0, off_(l+1) = off_l + n h_l w_l rounded up
+ *     to a multiple of 256.  canny_hip_pyramid_layout answers (h_l, w_l, off_l, bytes_l) per level and the total, the end of
+ *     the last level.  THE PAD BYTES between levels are never written.
+ *   Facts (tests/test_pyramid_rule.py).  A CONSTANT PLANE stays constant under both operators.  FLIPS: pyrDown commutes with a
+ *     flip of an axis of odd length (of even length the decimation grid moves); pyrUp commutes with a flip of an axis whose
+ *     output has 2 s - 1 samples.  pyrDown then pyrUp of a LINEAR RAMP reproduces the ramp away from the border.
+ *   Limits: h, w (and oh, ow) in 1..32768, a plane < 2^31 pixels, at most 65535 frames; above: CANNY_HIP_ERR_UNSUPPORTED.  NULL
+ *     mandatory pointers, bad sizes, bad oh / ow, bad levels, an input and an output that overlap: CANNY_HIP_ERR_INVALID.  Both
+ *     before anything is queued; nothing is written.  Every pointer may have any byte address.
+ *   Kernels (csrc/canny_pyramid.hip): one launch per level; a workgroup of 256 per tile of 128 columns x 32 rows of the OUTPUT
+ *     and trip of a grid capped at 4096.  The context option "pyramid_route": 0 automatic, 1 direct (a lane per output pixel,
+ *     25 taps from global memory, every index folded: the cross-check), 2 tiled (a lane loads one word of four source bytes
+ *     and takes its neighbours' by cross-lane moves; the horizontal five taps with decimation give partial sums kept as the
+ *     two 16-bit halves of LDS words; the vertical five taps run on the packed halves; a lane stores four pixels as one word
+ *     where aligned; tiles inside the frame load without a test, border tiles fold).  All routes give the same bytes.  pyrUp
+ *     has one route: a lane produces blocks of 4 x 2 outputs from 3 x 4 source pixels on packed halves.
+ * The two parts are timed through canny_hip_profile_part_get("pyramid", CANNY_HIP_PYR_PART_*); with "profile_stage_mask" they
+ * go by bit 30 like the other features' parts.
+ * Not covered -- follow-ups: two levels in one launch; Laplacian pyramids (s16 planes); cv::resize with arbitrary factors;
+ * multi-scale corners and descriptors as one call; pyramids through the batch pipeline or the multi-GPU sharder; colour
+ * planes. */
+#define CANNY_HIP_PYR_MAX_LEVELS 15
+enum canny_hip_pyr_part {
+    CANNY_HIP_PYR_PART_DOWN = 0, /* every pyrDown launch of a call */
+    CANNY_HIP_PYR_PART_UP = 1,
+    CANNY_HIP_PYR_PARTS = 2
+};
+/* Host-only, needs no device: info[4 l + 0..3] = (h, w, offset, bytes) of level l + 1, l = 0..levels - 1; *total_bytes: the
+ * size of the pyramid's buffer.  Both pointers are mandatory. */
+int canny_hip_pyramid_layout(int n_frames, int h, int w, int levels, long long *info, long long *total_bytes);
+/* One level.  d_plane: n_frames * h * w bytes, any byte address, or NULL: the smoothed plane that the preceding dev_canny of
+ * the same n_frames, h, w left in the context (any canny_hip_dev_canny* call, bytes or shorts; another geometry, or none yet:
+ * CANNY_HIP_ERR_INVALID; the plane is only read).  d_out: n_frames * ((h + 1) / 2) * ((w + 1) / 2) bytes.  Asynchronous, on
+ * the context's stream. */
+int canny_hip_dev_pyr_down(canny_hip_ctx *ctx, const unsigned char *d_plane, int n_frames, int h, int w, unsigned char *d_out);
+/* All levels into d_out (total_bytes of the layout), one launch per level; level l is read back from d_out to make level
+ * l + 1.  d_plane as above. */
+int canny_hip_dev_pyramid(canny_hip_ctx *ctx, const unsigned char *d_plane, int n_frames, int h, int w, int levels,
+                          unsigned char *d_out);
+/* d_plane [n_frames][h][w] is mandatory; d_out: n_frames * oh * ow bytes. */
+int canny_hip_dev_pyr_up(canny_hip_ctx *ctx, const unsigned char *d_plane, int n_frames, int h, int w, int oh, int ow,
+                         unsigned char *d_out);
+/* Host buffers, synchronous: upload, the levels; the levels come down into out (the layout; its pad bytes are not written). */
+int canny_hip_pyramid_batch(canny_hip_ctx *ctx, const unsigned char *imgs, int n_frames, int h, int w, int levels,
+                            unsigned char *out);
+int canny_hip_pyr_up_batch(canny_hip_ctx *ctx, const unsigned char *imgs, int n_frames, int h, int w, int oh, int ow,
+                           unsigned char *out);
+/* Host-only, need no device: the same rule on host buffers. */
+int canny_hip_pyramid(const unsigned char *imgs, int n_frames, int h, int w, int levels, unsigned char *out);
+int canny_hip_pyr_up(const unsigned char *imgs, int n_frames, int h, int w, int oh, int ow, unsigned char *out);
+
 /* ---- per-stage HIP-event timing (events are recorded on the launch stream) ----------------- */
 int canny_hip_profile_enable(canny_hip_ctx *ctx, int on);
 int canny_hip_profile_reset(canny_hip_ctx *ctx);
@@ -2648,10 +2724,9 @@ int canny_hip_morph_profile_get(canny_hip_ctx *ctx, int part, double *total_ms, 
 /* Every group of parts by name, for this and later features: feature is "stages" (the canny stages of
  * canny_hip_profile_get), "hough", "components", "edt", "hough_segments", "contours", "hough_circles", "polygons", "edgels",
  * "line_fits", "circle_fits", "chamfer", "shapes", "curves", "corners", "descriptors", "motion", "warp", "fuse", "morph",
- * "binarize" (CANNY_HIP_BIN_PART_*), "thin" (CANNY_HIP_THIN_PART_*), "reconstruct" (CANNY_HIP_RECON_PART_*) or "gray_morph"
- * (CANNY_HIP_GRAY_PART_*; the four have no named getter and follow bit 30 of "profile_stage_mask" like the others); the answer
- * is the named getter's.  An
- * unknown name, a part the group does not have or a NULL: CANNY_HIP_ERR_INVALID, nothing is written. */
+ * "binarize" (CANNY_HIP_BIN_PART_*), "thin" (CANNY_HIP_THIN_PART_*), "reconstruct" (CANNY_HIP_RECON_PART_*), "gray_morph"
+ * (CANNY_HIP_GRAY_PART_*) or "pyramid" (CANNY_HIP_PYR_PART_*; the five have no named getter and follow bit 30 of
+ * "profile_stage_mask" like the others); the answer is the named getter's.  An unknown name, a part the group does not have or a NULL: CANNY_HIP_ERR_INVALID, nothing is written. */
 int canny_hip_profile_part_get(canny_hip_ctx *ctx, const char *feature, int part, double *total_ms, long *launches);
 
 /* ---- self-test hooks used by the GPU test-suite -------------------------------------------- */
@@ -2867,6 +2942,11 @@ int canny_hip_selftest_reconstruct_plan(int n_frames, int h, int w, int route, u
  * word is the route that automatic takes for op with a full rectangle of kw x kh (1 general, 2 fast); it depends on op, kw and
  * kh alone.  kw, kh odd in 1..31 (MEDIAN: 3 x 3 or 5 x 5); it refuses what the calls refuse. */
 int canny_hip_selftest_gray_morph_plan(int n_frames, int h, int w, int op, int kw, int kh, unsigned long long *out);
+/* Host-only, the same five outputs for the capped launch of one pyrDown of planes [n_frames][h][w] (no kind above): items =
+ * n_frames * ceil(oh / 32) * ceil(ow / 128) tiles of the OUTPUT (oh = (h + 1) / 2, ow = (w + 1) / 2), one per workgroup of 256
+ * and trip, at most 4096 workgroups; a pyrUp INTO planes of oh x ow has the same plan.  The fifth word is the route automatic
+ * takes (1 direct, 2 tiled); it depends on nothing.  It refuses what the calls refuse. */
+int canny_hip_selftest_pyramid_plan(int n_frames, int h, int w, unsigned long long *out);
 /* Runs the fuse kernels' own device helper for the rounded mean over every pair c = 1..255, s = 0..255 c, and writes the
  * bytes to host memory as a table [255][CANNY_HIP_FUSE_MEAN_ROW]: out[(c - 1) * 65026 + s]; unused cells are 0. */
 int canny_hip_selftest_fuse_mean(canny_hip_ctx *ctx, unsigned char *out);
