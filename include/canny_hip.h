@@ -803,7 +803,8 @@ int canny_hip_line_fits_from_plane(const unsigned char *bits, const void *plane,
                                    float rho, int numangle, int numrho, const float *tab_cos, const float *tab_sin,
                                    const unsigned int *bases, int n_lines, const int *segments, int n_segments,
                                    int options, int *fits);
-/* Device bit maps (layout of canny_hip_dev_canny_bits), a device plane (bytes if plane_is_u8 else shorts, n_frames contiguous
+/* Device bit maps (layout of canny_hip_dev_canny_bits, any byte alignment; the padding bits of a row are ignored, whatever
+ * they hold), a device plane (bytes if plane_is_u8 else shorts, n_frames contiguous
  * planes) and the bases, line counts, segments and segment counts that the earlier calls left on the device.  d_plane ==
  * NULL means the smoothed plane the last canny_hip_dev_canny-family call on this context left, under the rule of
  * canny_hip_dev_edgels_at: CANNY_HIP_ERR_INVALID, nothing queued, if no such call ran or its shape differs.  d_fits:
@@ -1030,7 +1031,8 @@ enum canny_hip_circle_fit_part {
  * fits receives n_circles records of 8 ints. */
 int canny_hip_circle_fits_from_plane(const unsigned char *bits, const void *plane, int plane_is_u8, int height, int width,
                                      const int *circles, int n_circles, int band, int trim_q8, int options, int *fits);
-/* Device bit maps (layout of canny_hip_dev_canny_bits), a device plane (bytes if plane_is_u8 else shorts, n_frames contiguous
+/* Device bit maps (layout of canny_hip_dev_canny_bits, any byte alignment; the padding bits of a row are ignored, whatever
+ * they hold), a device plane (bytes if plane_is_u8 else shorts, n_frames contiguous
  * planes) and the circle records and counts an earlier call left on the device (or the caller made: this is where INVALID
  * records come from).  d_plane == NULL means the smoothed plane the last canny_hip_dev_canny-family call on this context
  * left, under the rule of canny_hip_dev_edgels_at: CANNY_HIP_ERR_INVALID, nothing queued, if no such call ran or its shape

@@ -9,6 +9,7 @@ import re
 import numpy as np
 import pytest
 
+import bits_inputs as bi
 import hough_rule as hr
 import hough_segments_rule as sr
 from canny_edge_amd import capi
@@ -139,6 +140,33 @@ def test_exclusive_mode_claims_pixels_once():
     assert np.array_equal(got, sr.segments(mask, bases, numrho, *tabs, 0, 2, 1))
     twice, _ = _lib(mask, bases, 1.0, np.pi / 180, 0.0, np.pi, 0, 2, 0, 4096)
     assert twice[:, 5].sum() > mask.sum()  # ... which the non-exclusive result does
+
+
+@pytest.mark.parametrize("shape", bi.SHAPES[:4], ids=bi.SHAPE_IDS[:4])
+def test_dirty_pad_bits_give_what_clean_ones_give(shape):
+    """The padding bits of a row are ignored, whatever they hold: the shapes and masks of tests/test_gpu_bits_inputs.py
+    (a line that ends on column w - 1, a vertical line on it), the pad bits all set and random.  The control first: the
+    rule with the pad columns counted as pixels gives other records, so a walk that trusted a pad bit would show."""
+    n, h, w = shape
+    rb = bi.row_bytes(w)
+    masks = bi.line_masks(n, h, w)
+    for f, mask in enumerate(masks):
+        bases, _, numrho, tabs = _lines_of(mask, 1.0, np.pi / 180, 0.0, np.pi, lines_max=16, threshold=2 * h // 3 if w >= 9 else 1)
+        assert len(bases) >= 1
+        for exclusive in (0, 1):
+            want = sr.segments(mask, bases, numrho, *tabs, 3, 1, exclusive)
+            assert len(want) >= 1
+            for pad in bi.PADS[1:]:
+                bits = bi.packed(mask, pad, seed=h + f)
+                assert bits.shape == (h, rb) and np.array_equal(bi.widened(bits)[:, :w], mask)
+                wide = sr.segments(bi.widened(bits), bases, numrho, *tabs, 3, 1, exclusive)
+                assert wide.shape != want.shape or not np.array_equal(wide, want), "the case cannot see a trusted pad bit"
+                buf = np.full((len(want) + 3) * 6 + N_GUARD, SENT, np.int32)
+                got, count = capi.hough_segments_from_bits(bits, h, w, bases, 1.0, np.pi / 180, 0.0, np.pi, 3, 1, exclusive,
+                                                           segments_max=len(want) + 3, out=buf)
+                what = f"{shape} frame {f} exclusive {exclusive} pad bits {pad}"
+                assert count == len(want) and np.array_equal(got, want), what
+                assert (buf[len(want) * 6:] == SENT).all(), what + ": slots past the count (or the guard) were written"
 
 
 def test_bad_and_duplicate_bases_and_a_short_capacity():
